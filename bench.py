@@ -52,6 +52,7 @@ CLS_TAIL_BOUND = {"bf16": 5e-3, "f16": 1e-3}
 
 EXTRAS_FILE = os.path.join(ROOT, "bench_extras.json")
 COMPACT_LIMIT = 6144      # bytes: the driver reads the LAST stdout line; r05's 28 KB line was not parsed
+DUMP_LIMIT = 64 << 20     # bytes: everything --dump-outputs writes, in all
 
 
 def _pick(d, keys):
@@ -161,6 +162,20 @@ def write_extras(out):
                     f.write(txt + "\n")
         except OSError:
             pass
+
+
+def dump_outputs(out_dir, name, a, limit=DUMP_LIMIT):
+    """--dump-outputs: `a` (one row per image) as out_dir/<name>.npy in float32, so that two builds can be compared output for output.
+    Above `limit` bytes only a fixed, seeded sample of its rows is written, and their ids beside it (<name>_rows.npy, float64)."""
+    import numpy as np
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    keep = (limit - 4096) // (a[0].nbytes + 8)          # 4 KiB for the two .npy headers, 8 bytes per row id
+    if a.shape[0] > keep:
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+        np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
+        a = a[rows]
+    np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def committed_traffic():
@@ -412,7 +427,11 @@ def main():
     ap.add_argument("--allow-overrides", action="store_true", help="run although a VITX_* development override is set; the line is stamped invalid")
     ap.add_argument("--stub-engine", action="store_true", help="CPU plumbing test only (tests/test_cpu_dist.py): gloo instead of RCCL, a stand-in for the forward; "
                                                                 "exercises the rank / barrier / gather / JSON logic of an N-process run; the line is stamped invalid")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the class probabilities of the last timed step (N > 1: the gathered "
+                                                          "[N x batch, classes] tensor) as DIR/probs.npy, float32, at most 64 MB (a seeded row sample beyond)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     overrides = development_overrides()
     if overrides and not args.allow_overrides:
@@ -557,6 +576,8 @@ def main():
                 want = torch.softmax(torch.arange(C, dtype=torch.float32)[None, :] * (0.001 * (1 + torch.arange(B, dtype=torch.float32))[:, None]) + r, 1)
                 assert torch.allclose(state["all"][r * B:(r + 1) * B], want), f"shard {r} of the gathered tensor is not rank {r}'s"
     timed_probs = probs.cpu().numpy()            # the probabilities the timed region produced (parity is checked on THESE)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, "probs", state["all"].cpu().numpy() if dist is not None else timed_probs)
 
     # per-kernel HIP events (on the launch stream) bracket every launch of ONE MORE step, outside the clock: while they are on, the engine
     # runs its two sub-batches back to back on one stream (exclusive kernel durations, ~6 % slower than the production schedule)

@@ -70,7 +70,7 @@ def test_shard_bounds_cover_and_balance(pkg):
 
 
 @pytest.mark.parametrize("world", [8, 2])
-def test_bench_plumbing_under_torchrun(world):
+def test_bench_plumbing_under_torchrun(world, tmp_path):
     """bench.py exactly as the driver launches it for the scaling run -- `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
     --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W` -- with the engine stubbed (--stub-engine: gloo, a
     stand-in forward that encodes the rank), so that a rank / port / barrier / gather-order bug cannot be the first thing an 8-GPU node
@@ -81,7 +81,8 @@ def test_bench_plumbing_under_torchrun(world):
     port = _free_port()
     env = {k: v for k, v in os.environ.items() if not k.startswith("VITX_")}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--stub-engine", "--model", "vit_tiny_patch16_224", "--batch", "4"]
+           os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--stub-engine", "--model", "vit_tiny_patch16_224", "--batch", "4",
+           "--dump-outputs", str(tmp_path / "out")]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -95,6 +96,28 @@ def test_bench_plumbing_under_torchrun(world):
     assert d["config"]["global_batch"] == 4 * world
     assert abs(d["value"] - 4 * world * 3 / (d["ms_per_step"] * 3e-3)) <= 0.02 * d["value"]          # whole-job aggregate, not per rank
     assert "stub" in d["invalid"]
+    assert os.listdir(tmp_path / "out") == ["probs.npy"]                # --dump-outputs: what the caller receives, the gathered tensor
+    import torch
+    dumped = np.load(tmp_path / "out" / "probs.npy")
+    block = torch.softmax(torch.arange(1000, dtype=torch.float32)[None, :] * (0.001 * (1 + torch.arange(4, dtype=torch.float32))[:, None]), 1).numpy()
+    assert dumped.dtype == np.float32 and np.allclose(dumped, np.tile(block, (world, 1)))
+
+
+def test_bench_dump_outputs_keeps_a_seeded_row_sample_under_the_limit(tmp_path):
+    """An output larger than the dump limit is written as a fixed, seeded sample of its rows, with the row ids beside it."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    a = np.arange(5000 * 100, dtype=np.float64).reshape(5000, 100)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), "probs", a, limit=1 << 20)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["probs.npy", "probs_rows.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 1 << 20
+    rows, got = np.load(tmp_path / "a" / "probs_rows.npy"), np.load(tmp_path / "a" / "probs.npy")
+    assert rows.dtype == np.float64 and got.dtype == np.float32 and np.array_equal(got, a[rows.astype(int)].astype(np.float32))
+    assert len(np.unique(rows)) == len(rows) > 2000
+    assert all(np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)) for f in files)
 
 
 def test_bench_refuses_development_overrides():

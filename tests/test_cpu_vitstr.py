@@ -1,7 +1,10 @@
-"""The ViTSTR scene-text extension (/root/reference/extensions/vitstr.cpp), host side: file format, grey preprocess and greedy
+"""The ViTSTR scene-text extension (the reference's extensions/vitstr.cpp), host side: file format, grey preprocess and greedy
 decode -- pinned to code compiled from the extension's own sources (oracle/_ref/libvitstr_ref_*.so, built by oracle/build_ref.sh
-from vitstr.h / vitstr.cpp line ranges; those two functions need no ggml)."""
+from vitstr.h / vitstr.cpp line ranges; those two functions need no ggml), through what that code returned on the inputs below,
+recorded in tests/golden/ref_vitstr.json (tests/golden/make_ref_golden.py)."""
 import ctypes as C
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -11,21 +14,26 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 REF_DIR = os.path.join(ROOT, "oracle", "_ref")
 ASSET_DIR = os.path.join(HERE, "golden", "assets")
+GOLDEN = os.path.join(HERE, "golden", "ref_vitstr.json")
 
 
 def _ref(build):
+    """The reference-compiled library in oracle/_ref, or None where it was not built: the pins then rest on GOLDEN alone; where it
+    was, every test also checks that it still returns exactly what GOLDEN holds."""
     path = os.path.join(REF_DIR, build)
     if not os.path.exists(path):
-        if os.path.exists("/root/reference/extensions/vitstr.cpp/vitstr.cpp"):
-            import subprocess
-            subprocess.check_call(["bash", os.path.join(ROOT, "oracle", "build_ref.sh")])
-        if not os.path.exists(path):
-            pytest.skip("oracle/_ref is not built and /root/reference is not present")
+        return None
     L = C.CDLL(path)
     L.ref_vitstr_preprocess.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.ref_vitstr_decode.restype = C.c_double
     L.ref_vitstr_decode.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_int]
     return L
+
+
+@pytest.fixture(scope="module")
+def gold():
+    with open(GOLDEN) as f:
+        return json.load(f)
 
 
 def _ref_pre(L, img, S):
@@ -35,12 +43,43 @@ def _ref_pre(L, img, S):
     return out
 
 
+def preprocess_record(strict, fma, img, S):
+    """The strict build's output as a sha1 (the product must equal it bit for bit) and the largest distance of the FMA-contracting
+    build's output from it."""
+    s, f = _ref_pre(strict, img, S), _ref_pre(fma, img, S)
+    return {"sha1": hashlib.sha1(s.tobytes()).hexdigest(), "fma_max_dev": float(np.abs(f - s).max())}
+
+
+def decode_record(strict, labels, p):
+    arr = (C.c_char_p * 96)(*[labels[i].encode() for i in range(96)])
+    buf = C.create_string_buffer(256)
+    score = strict.ref_vitstr_decode(p.ctypes.data_as(C.POINTER(C.c_float)), 96, 25, arr, buf, 256)
+    return {"text": buf.value.decode(), "score": score}
+
+
 def _images():
     rng = np.random.default_rng(5)
     out = [rng.integers(0, 256, (ny, nx, 3), dtype=np.uint8) for ny, nx in [(32, 100), (57, 131), (224, 224), (2, 2), (300, 17), (480, 640)]]
     grey = np.repeat(rng.integers(0, 256, (40, 90, 1), dtype=np.uint8), 3, axis=2)     # r == g == b: 0.299 + 0.587 + 0.114 lands on the truncation edge
     out.append(grey)
     return out
+
+
+def images(binding):
+    return _images() + [binding.load_image(os.path.join(ASSET_DIR, f)) for f in sorted(os.listdir(ASSET_DIR))[:4]]
+
+
+def decode_cases():
+    rng = np.random.default_rng(11)
+    cases = []
+    for k in range(6):
+        p = rng.random((25, 96)).astype(np.float32); p /= p.sum(1, keepdims=True)
+        if k >= 1: p[3 + 4 * k if 3 + 4 * k < 25 else 24, 1] = 2.0      # "[s]" wins at some position: the text ends there
+        if k == 2: p[1, 1] = 3.0                                         # ends immediately: empty text, score 1
+        if k == 3: p[2, 7] = p[2, 40] = 5.0                              # a tie: the first maximum wins (strict '>')
+        if k == 4: p[:, 1] = 0.0                                         # no "[s]" at all: all 24 positions are emitted
+        cases.append(p)
+    return cases
 
 
 def test_file_format_and_model_kind(pkg, binding, tmp_path):
@@ -66,41 +105,35 @@ def test_file_format_and_model_kind(pkg, binding, tmp_path):
         binding.Model(bad)
 
 
-def test_preprocess_matches_reference_compiled_code(binding, oracle):
+def test_preprocess_matches_reference_compiled_code(binding, oracle, gold):
     strict, fma = _ref("libvitstr_ref_strict.so"), _ref("libvitstr_ref_fma.so")
-    imgs = _images() + [binding.load_image(os.path.join(ASSET_DIR, f)) for f in sorted(os.listdir(ASSET_DIR))[:4]]
-    for img in imgs:
+    for i, img in enumerate(images(binding)):
         for S in (224, 64):
+            rec = gold["preprocess"][f"{i}|{S}"]
             got = binding.preprocess_vitstr(img, S)
+            if strict is not None and fma is not None:      # the live builds (the contracting one's compiler may differ from the recording's)
+                assert hashlib.sha1(_ref_pre(strict, img, S).tobytes()).hexdigest() == rec["sha1"], (i, S, "live strict build vs the recording")
+                assert np.abs(got - _ref_pre(fma, img, S)).max() <= 2.0 / 255.0 + 1e-6
             assert got.shape == (S, S) and got.min() >= -1.0 - 1e-6 and got.max() <= 1.0 + 1e-6      # the 4-term blend may land one ulp outside
             assert np.array_equal(got, oracle.preprocess_vitstr(img, S))                 # product == restatement
-            assert np.array_equal(got, _ref_pre(strict, img, S))                         # == the extension's own code, no FP contraction
+            assert hashlib.sha1(got.tobytes()).hexdigest() == rec["sha1"]                # == the extension's own code, no FP contraction
             # built the way the extension's CMakeLists builds it (-O3 -march=native -> FMA contraction) the grey conversion
             # (uint8)(0.299 r + 0.587 g + 0.114 b) truncates differently on exact-integer sums: one grey level = 2/255 after scaling
-            assert np.abs(got - _ref_pre(fma, img, S)).max() <= 2.0 / 255.0 + 1e-6
+            # (got equals the strict build's output, so its distance from the contracting build's is the recorded one)
+            assert rec["fma_max_dev"] <= 2.0 / 255.0 + 1e-6
     with pytest.raises(binding.VitxError):
         binding.preprocess_vitstr(np.zeros((1, 5, 3), np.uint8), 32)                    # the reference reads pixel (x + 1, y + 1) unconditionally
 
 
-def test_greedy_decode_matches_reference_compiled_code(pkg, binding):
+def test_greedy_decode_matches_reference_compiled_code(pkg, binding, gold):
     strict = _ref("libvitstr_ref_strict.so")
     labels = pkg.synth.VITSTR_LABELS
-    arr = (C.c_char_p * 96)(*[labels[i].encode() for i in range(96)])
-    rng = np.random.default_rng(11)
-    cases = []
-    for k in range(6):
-        p = rng.random((25, 96)).astype(np.float32); p /= p.sum(1, keepdims=True)
-        if k >= 1: p[3 + 4 * k if 3 + 4 * k < 25 else 24, 1] = 2.0      # "[s]" wins at some position: the text ends there
-        if k == 2: p[1, 1] = 3.0                                         # ends immediately: empty text, score 1
-        if k == 3: p[2, 7] = p[2, 40] = 5.0                              # a tie: the first maximum wins (strict '>')
-        if k == 4: p[:, 1] = 0.0                                         # no "[s]" at all: all 24 positions are emitted
-        cases.append(p)
-    for p in cases:
+    for p, rec in zip(decode_cases(), gold["decode"], strict=True):
+        if strict is not None:
+            assert decode_record(strict, labels, p) == rec
         ids, score = binding.vitstr_decode(p)
-        buf = C.create_string_buffer(256)
-        want_score = strict.ref_vitstr_decode(p.ctypes.data_as(C.POINTER(C.c_float)), 96, 25, arr, buf, 256)
-        assert "".join(labels[i] for i in ids) == buf.value.decode()
-        assert score == want_score
+        assert "".join(labels[i] for i in ids) == rec["text"]
+        assert score == rec["score"]
 
 
 def test_oracle_sequence_head(pkg, oracle, tmp_path):

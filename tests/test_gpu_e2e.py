@@ -291,6 +291,36 @@ def test_bench_rccl_path_single_rank(torch_gpu):
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["unit"] == "images/s" and d["scaling"] == "weak"
 
 
+def test_bench_dump_outputs_are_the_timed_probabilities(pkg, binding, torch_gpu, tmp_path):
+    """bench.py --dump-outputs DIR: the class probabilities of the last timed step as DIR/probs.npy (float32).  The inputs are seeded, so two
+    runs with different step counts write the same array, and it is what a direct forward of the same images returns."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B = 16
+    dumps = []
+    for steps in (2, 3):
+        d = tmp_path / f"s{steps}"
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--model", "vit_tiny_patch16_224",
+               "--batch", str(B), "--no-cpu-baseline", "--no-host-feed", "--no-profile", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert json.loads(r.stdout.splitlines()[-1])["steps"] == steps
+        assert sorted(os.listdir(d)) == ["probs.npy"]
+        dumps.append(np.load(d / "probs.npy"))
+    a, b = dumps
+    assert a.dtype == np.float32 and a.shape == (B, 1000) and np.abs(a.sum(1) - 1).max() < 1e-3
+    assert np.array_equal(a, b)
+    torch = torch_gpu        # bench.py's seeded batch, through the same context configuration
+    g = torch.Generator(device="cpu").manual_seed(4321)
+    u8 = torch.randint(0, 256, (B, 224, 224, 3), generator=g, dtype=torch.uint8)
+    imgs = ((u8.float() - torch.tensor(pkg.synth.IMAGENET_MEAN)) / torch.tensor(pkg.synth.IMAGENET_STD)).numpy()
+    model = binding.Model(pkg.synth.cached_synthetic("vit_tiny_patch16_224", head_scale=8.0))
+    ctx = binding.Context(model, device=0, max_batch=B, dtype=binding.BF16, last_layer_all_rows=1)
+    direct = ctx.forward(imgs)
+    ctx.close(); model.close()
+    assert np.abs(a - direct).max() <= 1e-3
+
+
 def test_cli_prints_topk_like_the_reference_and_walks_a_directory(pkg, binding, oracle, torch_gpu, tmp_path):
     """vit_cli.py (= main.cpp + the accuracy harness): stdout lines ' > label : 0.xx' (vit.cpp:1062-1067) for the bundled
     tench.jpg agree with the oracle's top-5; --dir mode scores <label>/<image> trees."""
