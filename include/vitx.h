@@ -287,6 +287,8 @@ long long vitx_ctx_ln_fallbacks(vitx_ctx *c);
 /* Diagnostic: internal sub-batch streams the context re-created because a 40 us probe showed them serialised with the caller's stream
  * (the runtime's stream -> hardware-queue mapping depends on the other streams alive in the process).  0 in a fresh process. */
 int vitx_ctx_stream_retries(const vitx_ctx *c);
+/* Diagnostic: forwards this context enqueued by launching a cached hipGraph (vitx_ctx_options::graph) since it was created; -1 for NULL. */
+long long vitx_ctx_graph_launches(const vitx_ctx *c);
 /* 1 = norm2 / the next norm1 are computed in the proj / fc2 GEMMs' epilogues where the shape allows it (the default on an 8-XCD device); 0 = every
  * LayerNorm is its own launch (option no_ln_fusion, graph cache, a device that does not report 8 XCDs); -1 = the context switched the fusion off
  * itself because more than 8 tiles per forward (averaged over 16 forwards) had to fall back -- peers' CUs held by other work; it tries the fused
@@ -328,6 +330,40 @@ int vitx_op_softmax_dt(int dtype, const void *d_logits, void *d_probs, int rows,
  * can differ from the same context's untraced forward by the operand type's rounding (bf16 about 1e-3). */
 int vitx_trace_enable(vitx_ctx *c, const int32_t *image_ids, int n);
 int vitx_trace_read(vitx_ctx *c, float *out, size_t n_floats);
+
+/* ---- attention maps and attention rollout (what the model looked at) --------- */
+/* Opt-in outputs of the forward, for classifier contexts.  Notation for one image, layer l, head h, N tokens, hd = D / H:
+ *   q, k  = the f32 values of the operands the context holds after that layer's qkv projection: the bf16 values (VITX_BF16); the fp16 values
+ *           (VITX_F16 with f16_fast_attention, and every VITX_F16 context whose head dim is not 64: it has no parity mode); hi + lo * 2^-11 of
+ *           the two planes of the F16 parity mode (VITX_F16, head dim 64, the default);
+ *   s[i][j] = (q_i . k_j) / sqrt(hd) in f32;   A_h[i][j] = expf(s[i][j] - max_j s[i]) / sum_j (...)  with f32 expf.
+ * The maps are f32 softmaxes of the context's own q, k -- NOT the numerators that multiply v (those use the reference's fp16 exp table or the
+ * kernels' rounded numerators).
+ *   class-token map of layer l:  A_h[0][0..N) for every head; index 0 is the class token itself, 1..N-1 the patches in raster order.
+ *   rollout (Abnar & Zuidema 2020):  A^_l = 0.5 mean_h A_h + 0.5 I,  R = A^_(L-1) ... A^_0,  output = row 0 of R (length N; rows of R sum to 1).
+ *     The last factor only ever needs row 0 of A^_(L-1), which is built from that layer's class-token maps -- so it is available when the last
+ *     layer carries only the class rows (the default; see last_layer_all_rows) and gives the same bits with last_layer_all_rows = 1.
+ * vitx_attn_enable(ctx, layer_mask, flags): bit l of layer_mask selects layer l's class-token maps, VITX_ATTN_ROLLOUT adds the rollout row;
+ *   mask 0 and flags 0 = off (frees the buffers).  Buffers are sized for max_batch images and allocated here (VITX_ERR_NOMEM when that fails);
+ *   rollout keeps two N x N f32 matrices per image and is VITX_ERR_UNSUPPORTED above 1024 tokens.  Mask bits at or beyond L: VITX_ERR_ARG.
+ *   ViTSTR contexts: VITX_ERR_UNSUPPORTED.  Synchronises the device.
+ * While maps are on, a forward of more than one pass (vitx_ctx_split) is VITX_ERR_ARG, and forwards do not use the hipGraph cache (as with the
+ * trace); maps are written only by forwards made while they are on.  Turning them off launches nothing and allocates nothing: the forward
+ * is the one without maps (probabilities and logits are the same bits with maps on and off).
+ * vitx_attn_floats: floats per image = popcount(mask) * H * N + (rollout ? N : 0).  Layout per image: the selected layers in ascending order,
+ *   each [H][N], then the rollout row [N].
+ * vitx_attn_read: synchronises and copies the maps of the last forward's n images ([n][vitx_attn_floats] f32); VITX_ERR_ARG before any
+ *   forward with maps on or when n_floats is too small.  vitx_attn_images: that n (0 before any forward with maps on since vitx_attn_enable).
+ * vitx_op_attention_map: the kernels on their own (device pointers; only enqueues): d_cls [n_img][H][N] class-token maps, d_mean
+ *   [n_img][N][N] mean_h A_h (N <= 1024); either may be NULL.  d_qkv [n_img * N][3 D] as the qkv projection writes it; lo_off != 0: the lo
+ *   plane of the F16 parity mode lies lo_off elements behind (VITX_F16 only, a multiple of 8, at least n_img * N * 3 D).  head_dim: any
+ *   multiple of 8 up to 128. */
+#define VITX_ATTN_ROLLOUT 1
+int vitx_attn_enable(vitx_ctx *c, uint64_t layer_mask, int flags);
+int vitx_attn_floats(const vitx_ctx *c);
+int vitx_attn_images(const vitx_ctx *c);
+int vitx_attn_read(vitx_ctx *c, float *out, size_t n_floats);
+int vitx_op_attention_map(int dtype, const void *d_qkv, long lo_off, void *d_cls, void *d_mean, int n_img, int N, int D, int H, void *stream);
 
 #ifdef __cplusplus
 }

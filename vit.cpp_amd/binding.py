@@ -23,6 +23,7 @@ BICUBIC, BILINEAR = 0, 1
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_BIAS_F32, EPI_PATCH, EPI_BIAS_HILO = 0, 1, 2, 3, 4, 5
 GEMM_AUTO, GEMM_PP, GEMM_AUTO_SPLIT = 0, 1, 2          # vitx_op_gemm_ex `kernel` (or a ring configuration: 945, 445, 245, 122)
 ATTN_AUTO, ATTN_SINGLE, ATTN_FLOW, ATTN_PERSIST, ATTN_STREAM = 0, 1, 3, 4, 5   # vitx_op_attention_ex `kernel`
+ATTN_ROLLOUT = 1                # vitx_attn_enable flag
 
 EXPORTS = [
     "vitx_status_str", "vitx_last_error", "vitx_model_load", "vitx_model_free", "vitx_model_uid", "vitx_model_hparams", "vitx_model_num_labels",
@@ -31,6 +32,7 @@ EXPORTS = [
     "vitx_topk", "vitx_group_create", "vitx_group_free", "vitx_group_num_devices", "vitx_group_forward", "vitx_group_out_floats", "vitx_group_forward_device", "vitx_group_result", "vitx_group_result_rows", "vitx_profile_enable", "vitx_profile_read", "vitx_profile_bracket_us", "vitx_op_layernorm", "vitx_op_gemm", "vitx_op_gemm_ex", "vitx_op_attention", "vitx_op_attention_ex", "vitx_op_softmax", "vitx_op_softmax_dt", "vitx_trace_enable", "vitx_trace_read",
     "vitx_op_dequant", "vitx_op_gemm_q4", "vitx_ctx_weight_bytes", "vitx_ctx_shares_weights", "vitx_probe_mfma", "vitx_op_gemm_ln", "vitx_ctx_ln_fallbacks", "vitx_ctx_stream_retries",
     "vitx_model_in_channels", "vitx_model_seq_len", "vitx_ctx_out_rows", "vitx_ctx_split", "vitx_ctx_ln_fusion_active", "vitx_op_attention_f32", "vitx_op_attention_planes", "vitx_op_attention_cls", "vitx_preprocess_vitstr_u8", "vitx_vitstr_decode",
+    "vitx_attn_enable", "vitx_attn_floats", "vitx_attn_images", "vitx_attn_read", "vitx_op_attention_map", "vitx_ctx_graph_launches",
 ]
 
 
@@ -131,6 +133,13 @@ def lib():
             L.vitx_op_attention_cls.argtypes = [ip, vp, C.c_long, vp, ip, ip, ip, ip, vp]
         L.vitx_preprocess_vitstr_u8.argtypes = [C.POINTER(C.c_uint8), ip, ip, ip, C.POINTER(C.c_float)]
         L.vitx_vitstr_decode.argtypes = [C.POINTER(C.c_float), ip, ip, C.POINTER(C.c_int32), C.POINTER(ip), C.POINTER(C.c_double)]
+        if hasattr(L, "vitx_attn_enable"):
+            L.vitx_attn_enable.argtypes = [vp, C.c_uint64, ip]
+            L.vitx_attn_floats.argtypes = [vp]
+            L.vitx_attn_images.argtypes = [vp]
+            L.vitx_ctx_graph_launches.restype = C.c_longlong; L.vitx_ctx_graph_launches.argtypes = [vp]
+            L.vitx_attn_read.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t]
+            L.vitx_op_attention_map.argtypes = [ip, vp, C.c_long, vp, vp, ip, ip, ip, ip, vp]
         _lib = L
     return _lib
 
@@ -308,6 +317,47 @@ class Context:
         check(lib().vitx_trace_read(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size), "vitx_trace_read")
         return out
 
+    def attn_enable(self, layers=None, rollout: bool = False) -> None:
+        """Attention maps of every later forward (vitx_attn_enable): the class-token maps of `layers` (None = every layer, [] = none) and,
+        with rollout=True, the attention-rollout row.  attn_enable([]) turns them off and frees the buffers."""
+        L = self.model.hparams.num_hidden_layers
+        sel = list(range(L)) if layers is None else sorted(set(int(l) for l in layers))
+        mask = 0
+        for l in sel:
+            if l < 0 or l >= 64:
+                raise ValueError(f"layer {l} outside 0..63")
+            mask |= 1 << l
+        check(lib().vitx_attn_enable(self._h, mask, ATTN_ROLLOUT if rollout else 0), "vitx_attn_enable")
+        self._attn_layers, self._attn_rollout = sel, bool(rollout)
+
+    def attn_disable(self) -> None:
+        self.attn_enable([], rollout=False)
+
+    def attn_read(self, n: Optional[int] = None):
+        """Maps of the last forward made with maps on, all of its n images: (cls [n, n_sel, H, N] f32, rollout [n, N] f32 or None).
+        Index 0 of a map is the class token, 1.. the patches in raster order (attn_grid reshapes).  `n`, if given, must be that batch."""
+        hp = self.model.hparams
+        N, H = (hp.img_size // hp.patch_size) ** 2 + 1, hp.num_attention_heads
+        fpi = lib().vitx_attn_floats(self._h)
+        sel, roll = getattr(self, "_attn_layers", []), getattr(self, "_attn_rollout", False)
+        assert fpi == len(sel) * H * N + (N if roll else 0)
+        have = lib().vitx_attn_images(self._h)
+        if n is not None and n != have:
+            raise ValueError(f"attn_read: the last forward with maps on had {have} images, not {n}")
+        n = have
+        if n == 0:
+            raise VitxError("attn_read: no forward has run with attention maps on since attn_enable")
+        out = np.empty((n, fpi), np.float32)
+        check(lib().vitx_attn_read(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size), "vitx_attn_read")
+        cls = out[:, :len(sel) * H * N].reshape(n, len(sel), H, N)
+        return cls, (out[:, len(sel) * H * N:].copy() if roll else None)
+
+    def attn_grid(self, m: np.ndarray) -> np.ndarray:
+        """[..., N] map -> [..., g, g] patch grid (g = img_size / patch_size): drops index 0 (the class token)."""
+        hp = self.model.hparams
+        g = hp.img_size // hp.patch_size
+        return np.asarray(m)[..., 1:].reshape(*np.shape(m)[:-1], g, g)
+
     def synchronize(self) -> None:
         check(lib().vitx_ctx_synchronize(self._h), "vitx_ctx_synchronize")
 
@@ -342,6 +392,10 @@ class Context:
     def ln_fusion_active(self) -> int:
         """1 fused LayerNorms, 0 stand-alone launches, -1 switched off by the fall-back budget (vitx_ctx_ln_fusion_active)."""
         return int(lib().vitx_ctx_ln_fusion_active(self._h))
+
+    def graph_launches(self) -> int:
+        """Forwards enqueued by launching a cached hipGraph (vitx_ctx_graph_launches; contexts created with graph=1)."""
+        return int(lib().vitx_ctx_graph_launches(self._h))
 
     def stream_retries(self) -> int:
         """Internal sub-batch streams re-created because they did not run beside the caller's stream (vitx_ctx_stream_retries)."""
@@ -407,6 +461,11 @@ def probe_mfma(device: int = 0, dtype: int = BF16, fill: int = 2, target_ms: flo
     tf = C.c_double(); mhz = C.c_double()
     check(lib().vitx_probe_mfma(device, dtype, fill, target_ms, C.byref(tf), C.byref(mhz)), "vitx_probe_mfma")
     return tf.value, mhz.value
+
+
+def op_attention_map(dtype: int, d_qkv: int, d_cls: int, d_mean: int, n_img: int, N: int, D: int, H: int, lo_off: int = 0, stream: int = 0) -> None:
+    """vitx_op_attention_map: class-token maps [n_img, H, N] and / or the head mean [n_img, N, N] (f32, device pointers; 0 = not wanted)."""
+    check(lib().vitx_op_attention_map(dtype, d_qkv, lo_off, d_cls or None, d_mean or None, n_img, N, D, H, stream or None), "vitx_op_attention_map")
 
 
 def topk(probs_row: np.ndarray, k: int = 5):

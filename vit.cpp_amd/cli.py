@@ -3,6 +3,7 @@ directory-walk accuracy harness:
 
     python vit_cli.py -m model.gguf -i image.jpg [-k 5] [--dtype f16|bf16] [--interp bicubic|bilinear]
     python vit_cli.py -m model.gguf --dir imagenet_val/ [--batch 256]       # top-1 over <dir>/<label>/*.jpg
+    python vit_cli.py -m model.gguf -i image.jpg --attn-map map.pgm [--attn-kind rollout|last]   # + where the model looked (P5 picture)
 
 Same flags as vit_params_parse (vit.cpp:955-1002: -m -i -t -k -s -e; -t, -s and -e are accepted and ignored exactly
 as the reference's forward ignores seed and eps), same stdout lines (" > label : 0.xx", vit.cpp:1062-1067) and the
@@ -25,6 +26,16 @@ def _decode(path: str) -> np.ndarray:
     return np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8)
 
 
+def attn_pgm(grid: np.ndarray, img_size: int) -> bytes:
+    """[g, g] patch map -> binary PGM (P5) of img_size^2 bytes: nearest-neighbour upsampling, scaled to 0..255 (the maximum is 255)."""
+    g = grid.shape[0]
+    m = np.asarray(grid, np.float64)
+    lo, hi = float(m.min()), float(m.max())
+    u8 = np.zeros_like(m, np.uint8) if hi <= lo else np.rint((m - lo) / (hi - lo) * 255.0).astype(np.uint8)
+    idx = np.arange(img_size) * g // img_size                  # source patch of every output pixel
+    return f"P5\n{img_size} {img_size}\n255\n".encode() + u8[idx][:, idx].tobytes()
+
+
 def main(argv: List[str] | None = None) -> int:
     from . import binding
     ap = argparse.ArgumentParser(prog="vit", description="ViT inference on MI355X (drop-in for staghado/vit.cpp's CLI)")
@@ -39,7 +50,12 @@ def main(argv: List[str] | None = None) -> int:
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--dir", default=None, help="accuracy harness: walk DIR/<label>/* and report top-1 against the directory name")
     ap.add_argument("--batch", type=int, default=256, help="images per forward in --dir mode")
+    ap.add_argument("--attn-map", default=None, metavar="PATH", help="with -i: write the image's attention map as a binary PGM (P5), img_size x img_size")
+    ap.add_argument("--attn-kind", default="rollout", choices=["rollout", "last"],
+                    help="rollout: attention rollout through all layers; last: head mean of the last layer's class-token map")
     a = ap.parse_args(argv)
+    if a.attn_map and a.dir is not None:
+        ap.error("--attn-map takes the single image of -i, not --dir")
 
     t_main = time.perf_counter()
     print(f"main: seed = {a.seed if a.seed >= 0 else int(time.time())}", file=sys.stderr)
@@ -63,7 +79,16 @@ def main(argv: List[str] | None = None) -> int:
         img1 = binding.preprocess(img0, S, interp)
         print(f"processed, out dims : ({S} x {S})", file=sys.stderr)
         ctx = binding.Context(model, device=a.device, max_batch=1, dtype=dt)
+        if a.attn_map:
+            L = model.hparams.num_hidden_layers
+            ctx.attn_enable([] if a.attn_kind == "rollout" else [L - 1], rollout=a.attn_kind == "rollout")
         probs = ctx.forward(img1[None])[0]
+        if a.attn_map:
+            cls, roll = ctx.attn_read()
+            m = roll[0] if a.attn_kind == "rollout" else cls[0, 0].mean(axis=0)
+            with open(a.attn_map, "wb") as f:
+                f.write(attn_pgm(ctx.attn_grid(m), S))
+            print(f"main: wrote the {a.attn_kind} attention map to '{a.attn_map}'", file=sys.stderr)
         idx, val = binding.topk(probs, a.topk)
         print("", file=sys.stderr)
         for i, p in zip(idx, val):                                          # vit.cpp:1062-1067

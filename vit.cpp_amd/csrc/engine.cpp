@@ -35,10 +35,10 @@ namespace {
 
 enum ProfClass {
     PC_GEMM_PATCH = 0, PC_LAYERNORM, PC_GEMM_QKV, PC_ATTENTION, PC_GEMM_PROJ, PC_GEMM_FC1, PC_GEMM_FC2,
-    PC_GEMM_HEAD, PC_SOFTMAX, PC_DEQUANT, PC_ATTENTION_CLS, PC_GEMM_TAIL, PC_COUNT
+    PC_GEMM_HEAD, PC_SOFTMAX, PC_DEQUANT, PC_ATTENTION_CLS, PC_GEMM_TAIL, PC_ATTN_MAP, PC_COUNT
 };
 const char *kProfNames[PC_COUNT] = {"patch_embed", "layernorm", "gemm_qkv_bias", "attention", "gemm_proj_resid",
-                                    "gemm_fc1_gelu", "gemm_fc2_resid", "gemm_head", "softmax", "dequant_weights", "attention_cls", "gemm_cls_tail"};
+                                    "gemm_fc1_gelu", "gemm_fc2_resid", "gemm_head", "softmax", "dequant_weights", "attention_cls", "gemm_cls_tail", "attention_map"};
 
 // A weight matrix kept in the file's block form on the device (quant.hip): `blocks` = N rows of K/32 blocks in the file's byte
 // layout -- except q4_0, which is split into a nibble plane (`blocks`, 16 B per block, rows padded to n_pad) and an f16 scale
@@ -165,6 +165,19 @@ struct vitx_ctx {
     // residual-stream trace (vitx_trace_enable)
     std::vector<int> trace_ids;
     float *trace_buf = nullptr;  // [L + 1][n_ids][N][D]
+    // attention maps (vitx_attn_enable): nothing is allocated or launched while attn_mask == 0 and attn_flags == 0
+    uint64_t attn_mask = 0;
+    int attn_flags = 0;
+    int attn_fpi = 0;            // floats per image: popcount(mask) * H * N (+ N with VITX_ATTN_ROLLOUT)
+    int attn_cap = 0;            // images the buffers hold (= the images one pass takes)
+    int attn_n = 0;              // images of the last forward made with maps on (0: none since vitx_attn_enable)
+    float *attn_out = nullptr;   // [attn_cap][attn_fpi]: per image the selected layers' [H][N] class-token maps in ascending order, then the rollout row [N]
+    float *attn_roll[2] = {nullptr, nullptr};   // rollout: [attn_cap][N][N] x 2, A^_l written into one, the product R_l in place of it (ping-pong)
+    float *attn_cls_last = nullptr;             // rollout without the last layer in the mask: its class-token maps [attn_cap][H][N]
+    bool attn_on() const { return attn_mask != 0 || attn_flags != 0; }
+    void attn_free() {
+        for (float **p : {&attn_out, &attn_roll[0], &attn_roll[1], &attn_cls_last}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    }
     // hipGraph cache of the single-stream (small-batch) forward, opt-in (vitx_ctx_options::graph).  Key = (images, batch, outputs): the graph
     // bakes the pointers in.  An entry is captured the second time in a row its key is seen (one-off calls are never captured).
     // Measured (profiles/r02f/hipgraph_small_batch.txt): replaying the ~100 dependent launches as a graph takes the enqueue work off
@@ -174,6 +187,7 @@ struct vitx_ctx {
     std::vector<GraphEntry> graphs;
     GraphEntry graph_last{nullptr, nullptr, nullptr, 0, nullptr};
     bool graphs_on = false;
+    long long graph_launches = 0;        // forwards enqueued as a cached graph (vitx_ctx_graph_launches)
     // profiling
     bool prof_on = false;
     hipEvent_t prof_base = nullptr;
@@ -193,6 +207,7 @@ struct vitx_ctx {
         if (prof_base) (void)hipEventDestroy(prof_base);
         if (ln_fb_host) (void)hipHostFree(ln_fb_host);
         if (trace_buf) (void)hipFree(trace_buf);
+        attn_free();
         for (void *p : allocs) (void)hipFree(p);
         if (stream) (void)hipStreamDestroy(stream);
     }
@@ -528,6 +543,46 @@ int vitx_ctx_split(const vitx_ctx *c, int n, int32_t *images, int max_parts) {
 }
 int vitx_ctx_out_rows(const vitx_ctx *c) { return c ? c->R : 0; }
 
+// Attention maps of layer il (vitx_attn_enable) for the n images first_img .. of a sub-batch, from the QKV its qkv projection has just written
+// (lo_off: the parity mode's lo plane).  The kernels only read QKV and write the context's map buffers at the images' global positions.
+// Rollout: A^_l goes to attn_roll[l & 1] and becomes R_l = A^_l R_(l-1) in place; the last layer contributes row 0 of its factor only,
+// built from its class-token maps -- the rows a cls_tail context still has.
+static int attention_maps(vitx_ctx *c, hipStream_t st, const void *qkv, long lo_off, int il, int first_img, int n) {
+    const int N = c->N, D = c->D, H = c->H, L = c->L, fpi = c->attn_fpi;
+    const size_t NN = (size_t)N * N;
+    const bool rollout = (c->attn_flags & VITX_ATTN_ROLLOUT) != 0;
+    const double qk_bytes = (double)n * N * 2 * D * 2 * (lo_off ? 2 : 1);        // q and k of every token (both planes in the parity mode)
+    float *out_img = c->attn_out + (size_t)first_img * fpi;
+    float *cls = nullptr;
+    long cls_stride = 0;
+    if ((c->attn_mask >> il) & 1) {
+        cls = out_img + (size_t)__builtin_popcountll(c->attn_mask & ((1ull << il) - 1)) * H * N; cls_stride = fpi;
+    } else if (rollout && il + 1 == L) {
+        cls = c->attn_cls_last + (size_t)first_img * H * N; cls_stride = (long)H * N;
+    }
+    if (cls) {
+        ProfScope ps(c, st, PC_ATTN_MAP, 2.0 * n * (double)N * D, qk_bytes / 2 + (double)n * H * N * 4);
+        HIP_TRY(launch_attention_cls_map(c->dtype, qkv, lo_off, cls, cls_stride, n, N, D, H, st));
+    }
+    if (!rollout) return VITX_OK;
+    if (il + 1 < L) {
+        float *a = c->attn_roll[il & 1] + (size_t)first_img * NN;
+        {
+            ProfScope ps(c, st, PC_ATTN_MAP, 2.0 * n * (double)NN * D, qk_bytes + (double)n * NN * 4);
+            HIP_TRY(launch_attention_head_mean(c->dtype, qkv, lo_off, a, n, N, D, H, true, st));
+        }
+        if (il > 0) {
+            ProfScope ps(c, st, PC_ATTN_MAP, 2.0 * n * (double)NN * N, (double)n * NN * 12);
+            HIP_TRY(launch_rollout_step(a, c->attn_roll[(il + 1) & 1] + (size_t)first_img * NN, n, N, st));
+        }
+        return VITX_OK;
+    }
+    const float *r = L > 1 ? c->attn_roll[(L - 2) & 1] + (size_t)first_img * NN : nullptr;
+    ProfScope ps(c, st, PC_ATTN_MAP, 2.0 * n * (double)NN, (double)n * NN * 4);
+    HIP_TRY(launch_rollout_row(cls, cls_stride, r, out_img + (fpi - N), fpi, n, N, H, st));
+    return VITX_OK;
+}
+
 static int forward_slice(vitx_ctx *c, vitx_ctx::Slice &sl, hipStream_t st, const void *d_imgs, int first_img, int n, void *d_probs, void *d_logits) {
     // residual-stream trace: copy X of the traced images that live in this sub-batch (stage 0 = after patch embedding, il + 1 = after layer il)
     auto trace = [&](int stage) -> int {
@@ -654,6 +709,7 @@ static int forward_slice(vitx_ctx *c, vitx_ctx::Slice &sl, hipStream_t st, const
 #endif
         if ((rc = gemm(c, tn_, st, PC_GEMM_QKV, (c->prec_attn && prec_dbg != 2) ? EPI_BIAS_HILO : EPI_BIAS, sl.U, Wl[W_QKV], w.qkv_b, sl.QKV, nullptr, M, M_real, 3 * D, round_up(3 * D, tn), D, D, D, 3 * D, 0, 2, Fl[W_QKV], nullptr,
                        fix_u.todo ? &fix_u : nullptr, lo_off))) return rc;
+        if (c->attn_on() && (rc = attention_maps(c, st, sl.QKV, lo_off, il, first_img, n))) return rc;
         if (tail_now) {
             {   // attention of token 0 (vit.cpp:848-858 for the one row vit.cpp:910-911 keeps) -> compact rows U[b]; class rows of X -> Xc[b]
                 ProfScope ps(c, st, PC_ATTENTION_CLS, 4.0 * n * c->H * (double)N * (D / c->H), (double)M_real * 2 * D * eb * (c->prec_attn ? 2 : 1) + (double)n * D * (eb + 8));
@@ -788,7 +844,7 @@ static int forward_graph(vitx_ctx *c, hipStream_t st, const void *d_imgs, int n,
     *done = false;
     for (auto &ge : c->graphs)
         if (ge.imgs == d_imgs && ge.n == n && ge.probs == d_probs && ge.logits == d_logits) {
-            if (hipGraphLaunch(ge.exec, st) == hipSuccess) { *done = true; return VITX_OK; }
+            if (hipGraphLaunch(ge.exec, st) == hipSuccess) { *done = true; ++c->graph_launches; return VITX_OK; }
             (void)hipGetLastError(); c->graphs_on = false; return VITX_OK;       // never seen; stay on the direct path from here on
         }
     vitx_ctx::GraphEntry &last = c->graph_last;
@@ -812,6 +868,7 @@ static int forward_graph(vitx_ctx *c, hipStream_t st, const void *d_imgs, int n,
     c->graphs.push_back(vitx_ctx::GraphEntry{d_imgs, d_probs, d_logits, n, exec});
     if (hipGraphLaunch(exec, st) != hipSuccess) { set_error("vitx_forward_device: hipGraphLaunch: %s", hipGetErrorString(hipGetLastError())); return VITX_ERR_HIP; }
     *done = true;
+    ++c->graph_launches;
     return VITX_OK;
 }
 
@@ -884,12 +941,14 @@ int vitx_forward_device(vitx_ctx *c, const void *d_imgs, int n, void *d_probs, v
     // one pass of the kernels takes call_limit images (32-bit buffer window, vitx_ctx_create_ex); a larger batch is several passes, back to back on the
     // caller's stream through the same scratch -- images are independent, so the results are the ones a single pass would give
     if (n > c->call_limit && !c->trace_ids.empty()) { set_error("vitx_forward_device: the residual-stream trace takes one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
+    if (n > c->call_limit && c->attn_on()) { set_error("vitx_forward_device: attention maps take one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
     for (int i0 = 0; i0 < n; i0 += c->call_limit) {
         const int ni = std::min(c->call_limit, n - i0);
         const int rc = forward_pass(c, (const float *)d_imgs + (size_t)i0 * c->S * c->S * c->Cin, ni, (float *)d_probs + (size_t)i0 * c->R * c->C,
                                     d_logits ? (float *)d_logits + (size_t)i0 * c->R * c->C : nullptr, st);
         if (rc) return rc;
     }
+    if (c->attn_on()) c->attn_n = n;
     return VITX_OK;
 }
 static int forward_pass(vitx_ctx *c, const void *d_imgs, int n, void *d_probs, void *d_logits, hipStream_t st) {
@@ -918,7 +977,7 @@ static int forward_pass(vitx_ctx *c, const void *d_imgs, int n, void *d_probs, v
     const bool serial = c->prof_on;
     const int ns = (c->nslices > 1 && n >= 8 * c->nslices) ? c->nslices : 1;
     if (ns == 1) {
-        if (c->graphs_on && !c->prof_on && c->trace_ids.empty()) {
+        if (c->graphs_on && !c->prof_on && c->trace_ids.empty() && !c->attn_on()) {
             bool done = false;
             const int rc = forward_graph(c, st, d_imgs, n, d_probs, d_logits, &done);
             if (rc != VITX_OK || done) return rc;
@@ -1136,6 +1195,7 @@ int vitx_op_gemm_q4(int dtype, int epi, const void *a, const void *qs, const voi
 size_t vitx_ctx_weight_bytes(const vitx_ctx *c) { return c ? c->weight_bytes : 0; }
 int vitx_ctx_shares_weights(const vitx_ctx *c) { return c && c->weights_shared ? 1 : 0; }
 int vitx_ctx_stream_retries(const vitx_ctx *c) { return c ? c->stream_retries : -1; }
+long long vitx_ctx_graph_launches(const vitx_ctx *c) { return c ? c->graph_launches : -1; }
 int vitx_ctx_ln_fusion_active(const vitx_ctx *c) { return c ? ((c->ln_fuse && !c->slices.empty() && c->slices[0].ln_sync && c->tune->n_xcd == 8) ? 1 : (c->ln_fuse_disabled ? -1 : 0)) : 0; }
 long long vitx_ctx_ln_fallbacks(vitx_ctx *c) {
     if (!c) return -1;
@@ -1241,6 +1301,58 @@ int vitx_trace_read(vitx_ctx *c, float *out, size_t n_floats) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, c->trace_buf, need * 4, hipMemcpyDeviceToHost));
+    return VITX_OK;
+}
+
+int vitx_attn_enable(vitx_ctx *c, uint64_t layer_mask, int flags) {
+    if (!c) return VITX_ERR_ARG;
+    if (flags & ~VITX_ATTN_ROLLOUT) { set_error("vitx_attn_enable: unknown flags 0x%x", flags); return VITX_ERR_ARG; }
+    if (c->L < 64 && (layer_mask >> c->L)) { set_error("vitx_attn_enable: layer mask 0x%llx names layers beyond the model's %d", (unsigned long long)layer_mask, c->L); return VITX_ERR_ARG; }
+    const bool on = layer_mask != 0 || flags != 0, rollout = (flags & VITX_ATTN_ROLLOUT) != 0;
+    if (on && c->R != 1) { set_error("vitx_attn_enable: attention maps are not available for ViTSTR contexts"); return VITX_ERR_UNSUPPORTED; }
+    if (on && !attention_map_supports(c->N, c->D, c->H)) { set_error("vitx_attn_enable: head_dim %d is not covered by the map kernels", c->D / c->H); return VITX_ERR_UNSUPPORTED; }
+    if (rollout && !attention_mean_supports(c->N, c->D, c->H)) { set_error("vitx_attn_enable: rollout keeps two N x N matrices per image and takes at most %d tokens (this model: %d)", kAttnMeanMaxTokens, c->N); return VITX_ERR_UNSUPPORTED; }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());          // no forward in flight writes the buffers about to be freed
+    c->attn_free();
+    c->attn_mask = 0; c->attn_flags = 0; c->attn_fpi = 0; c->attn_cap = 0; c->attn_n = 0;
+    if (!on) return VITX_OK;
+    const int cap = std::min(c->max_batch, c->call_limit), N = c->N, H = c->H;
+    const int fpi = __builtin_popcountll(layer_mask) * H * N + (rollout ? N : 0);
+    auto alloc = [&](float **p, size_t floats) { if (hipMalloc((void **)p, floats * 4) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; } return true; };
+    bool ok = alloc(&c->attn_out, (size_t)cap * fpi);
+    if (ok && rollout) ok = alloc(&c->attn_roll[0], (size_t)cap * N * N) && alloc(&c->attn_roll[1], (size_t)cap * N * N);
+    if (ok && rollout && !((layer_mask >> (c->L - 1)) & 1)) ok = alloc(&c->attn_cls_last, (size_t)cap * H * N);
+    if (!ok) { c->attn_free(); set_error("vitx_attn_enable: cannot allocate the map buffers for %d images", cap); return VITX_ERR_NOMEM; }
+    c->attn_mask = layer_mask; c->attn_flags = flags; c->attn_fpi = fpi; c->attn_cap = cap;
+    return VITX_OK;
+}
+int vitx_attn_floats(const vitx_ctx *c) { return c ? c->attn_fpi : 0; }
+int vitx_attn_images(const vitx_ctx *c) { return c ? c->attn_n : 0; }
+int vitx_attn_read(vitx_ctx *c, float *out, size_t n_floats) {
+    if (!c || !out) return VITX_ERR_ARG;
+    if (!c->attn_on() || c->attn_n == 0) { set_error("vitx_attn_read: no forward has run with attention maps on since vitx_attn_enable"); return VITX_ERR_ARG; }
+    const size_t need = (size_t)c->attn_n * c->attn_fpi;
+    if (n_floats < need) { set_error("vitx_attn_read: buffer too small (%zu floats needed for %d images)", need, c->attn_n); return VITX_ERR_ARG; }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, c->attn_out, need * 4, hipMemcpyDeviceToHost));
+    return VITX_OK;
+}
+// The map kernels on their own (the parity tests): d_cls [n_img][H][N] class-token rows, d_mean [n_img][N][N] mean_h A_h (either may be NULL).
+int vitx_op_attention_map(int dtype, const void *d_qkv, long lo_off, void *d_cls, void *d_mean, int n_img, int N, int D, int H, void *stream) {
+    if (!d_qkv || (!d_cls && !d_mean) || n_img <= 0 || N <= 0 || D <= 0 || H <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_attention_map: invalid argument"); return VITX_ERR_ARG; }
+    if (lo_off && (dtype != VITX_F16 || lo_off < (long)n_img * N * 3 * D || lo_off % 8 != 0)) {
+        set_error("vitx_op_attention_map: a lo plane needs VITX_F16 and lo_off %ld a multiple of 8 elements, at least n_img * N * 3 * D = %ld", lo_off, (long)n_img * N * 3 * D);
+        return VITX_ERR_ARG;
+    }
+    if (!attention_map_supports(N, D, H)) { set_error("vitx_op_attention_map: head_dim must be a multiple of 8 up to 128 (D %d, H %d)", D, H); return VITX_ERR_UNSUPPORTED; }
+    if (d_mean && !attention_mean_supports(N, D, H)) { set_error("vitx_op_attention_map: the head mean takes at most %d tokens (N %d)", kAttnMeanMaxTokens, N); return VITX_ERR_UNSUPPORTED; }
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSuccess;
+    if (d_cls) e = launch_attention_cls_map(dtype, d_qkv, lo_off, (float *)d_cls, (long)H * N, n_img, N, D, H, st);
+    if (e == hipSuccess && d_mean) e = launch_attention_head_mean(dtype, d_qkv, lo_off, (float *)d_mean, n_img, N, D, H, false, st);
+    if (e != hipSuccess) { set_error("vitx_op_attention_map: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
     return VITX_OK;
 }
 

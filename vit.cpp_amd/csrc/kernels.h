@@ -138,6 +138,18 @@ hipError_t launch_split_hilo(int dtype, const float *x, void *hi, void *lo, size
 // (lo_off != 0: the parity mode's lo plane, F16 only); xc != nullptr: also xc[b][D] = x[b * N][D] (the class rows of the f32 residual stream)
 hipError_t launch_attention_cls(int dtype, const void *qkv, long lo_off, void *out, const float *x, float *xc, int n_img, int N, int D, int H, hipStream_t stream);
 bool attention_cls_supports(int N, int D, int H);  // head_dim 8, 16, 32, 64 or 128
+// Attention maps (attention_map.hip; vitx_attn_enable): f32 softmaxes of the operands in qkv (lo_off != 0: the parity mode's two planes, F16 only).
+//   cls_map:   out[b * img_stride + h * N + j] = A_h[0][j] of image b (class-token row of every head)
+//   head_mean: out[b][i][j] = mean_h A_h[i][j], or 0.5 mean_h A_h[i][j] + 0.5 [i == j] (half_identity: the rollout factor);  N <= kAttnMeanMaxTokens
+//   rollout_step: a[b] <- a[b] . r[b] in place ([N][N] f32, exact f32 products);  rollout_row: out[b][k] = sum_j w_j r[b][j][k], w = row 0 of the
+//   last layer's rollout factor from its class-token maps cls[b * cls_stride + h * N + j] (r == nullptr: out = w)
+constexpr int kAttnMeanMaxTokens = 1024;
+bool attention_map_supports(int N, int D, int H);      // head_dim a multiple of 8 up to 128, any token count
+bool attention_mean_supports(int N, int D, int H);     // the same, at most kAttnMeanMaxTokens tokens
+hipError_t launch_attention_cls_map(int dtype, const void *qkv, long lo_off, float *out, long img_stride, int n_img, int N, int D, int H, hipStream_t stream);
+hipError_t launch_attention_head_mean(int dtype, const void *qkv, long lo_off, float *out, int n_img, int N, int D, int H, bool half_identity, hipStream_t stream);
+hipError_t launch_rollout_step(float *a, const float *r, int n_img, int N, hipStream_t stream);
+hipError_t launch_rollout_row(const float *cls, long cls_stride, const float *r, float *out, long out_stride, int n_img, int N, int H, hipStream_t stream);
 bool attention_supports(int N, int D, int H);     // any token count; head_dim 64 (tuned kernels) or any other multiple of 8 up to 128 (generic kernel)
 bool attention_single_pass_supports(int N);       // instantiation table of the register-resident kernel
 bool layernorm_supports(int D);
