@@ -82,26 +82,21 @@ struct vitx_ctx {
         void *pe_w = nullptr, *head_w = nullptr;
         QuantW head_q;
         std::vector<LayerW> layers;
-        size_t weight_bytes = 0;
+        size_t weight_bytes = 0;         // device bytes held by weight matrices (vitx_ctx_weight_bytes)
         ~WeightSet() {       // may run on any thread (the last context of the set): leave the caller's current device as it was
             int cur = -1; (void)hipGetDevice(&cur);
             (void)hipSetDevice(device); for (void *p : allocs) (void)hipFree(p);
             if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
         }
     };
-    std::shared_ptr<WeightSet> wset;
+    std::shared_ptr<WeightSet> wset;     // never null once the context exists
     bool weights_shared = false;         // this context found the set already uploaded (vitx_ctx_shares_weights)
-    float *cls = nullptr, *pos = nullptr, *pe_b = nullptr, *norm_w = nullptr, *norm_b = nullptr, *head_b = nullptr;
-    void *pe_w = nullptr, *head_w = nullptr;
-    QuantW head_q;
-    std::vector<LayerW> layers;
     // quantised files: vitx_ctx_options::quant_on_host restores the r01 behaviour (expand once on the host at upload, 16 bits per weight in HBM)
     bool quant_on_device = true;
     // q4_0 GEMMs with at most this many rows expand the blocks inside the GEMM's LDS-fill path (vitx_ctx_options::q4_fused_rows).  0 = never:
     // measured on ViT-B (profiles/r02c_quant.txt) the 128x128-tile fused kernel loses to "expand the layer just in time, then the skinny ring
     // kernels" at every batch size (batch 1: 1.75 vs 1.06 ms, batch 8: 2.15 vs 1.33 ms), so it is an option, not the default.
     int q4_fused_rows = 0;
-    size_t weight_bytes = 0;             // device bytes held by weight matrices (vitx_ctx_weight_bytes)
     // LayerNorm fused into the residual GEMMs (GemmLn, kernels.h): norm2 rides in proj, the next layer's norm1 in fc2, wherever those GEMMs
     // run on the wide persistent kernel.  vitx_ctx_options::no_ln_fusion turns it off (every LayerNorm its own launch; same bits).
     // F16 = the parity mode: q, k, v stay f32-grade into the attention products, as the reference's do (vit.cpp:826-858).  The QKV GEMM then
@@ -151,7 +146,6 @@ struct vitx_ctx {
         float *logits = nullptr;     // [Bpad][C_pad]
         hipStream_t stream = nullptr;
         hipEvent_t done = nullptr;
-        Tuning tune;                 // the device's tuning with n_cu = the CUs this slice's stream may use (CU-masked streams)
     };
     int nslices = 1;
     std::vector<Slice> slices;
@@ -260,7 +254,7 @@ int upload_matrix(vitx_ctx *c, const HostTensor *t, int Nrows, int K, int n_pad,
     int rc = c->wmalloc(out, h.size() * 2);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(*out, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-    c->weight_bytes += h.size() * 2;
+    c->wset->weight_bytes += h.size() * 2;
     return VITX_OK;
 }
 int upload_quant(vitx_ctx *c, const HostTensor *t, int Nrows, int K, int n_pad, QuantW *q);
@@ -289,12 +283,12 @@ int upload_quant(vitx_ctx *c, const HostTensor *t, int Nrows, int K, int n_pad, 
         if ((rc = c->wmalloc((void **)&q->scales, ds.size() * 2))) return rc;
         HIP_TRY(hipMemcpy(q->blocks, qs.data(), qs.size(), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(q->scales, ds.data(), ds.size() * 2, hipMemcpyHostToDevice));
-        c->weight_bytes += qs.size() + ds.size() * 2;
+        c->wset->weight_bytes += qs.size() + ds.size() * 2;
     } else {
         const size_t bytes = (size_t)Nrows * nbk * bb;
         if ((rc = c->wmalloc(&q->blocks, bytes))) return rc;
         HIP_TRY(hipMemcpy(q->blocks, t->raw.data(), bytes, hipMemcpyHostToDevice));
-        c->weight_bytes += bytes;
+        c->wset->weight_bytes += bytes;
     }
     return VITX_OK;
 }
@@ -310,29 +304,26 @@ struct ProfScope {
     ~ProfScope() { if (on) (void)hipEventRecord(c->recs[idx].b, s); }
 };
 
-// `fused` != nullptr: W is that q4_0 matrix and the GEMM expands the blocks in its own LDS-fill path (small batches).
-// `fix`: the GemmLn of the LayerNorm-fusing GEMM that produced A (GemmArgs::fix); when the kernel this shape selects cannot recompute the
-// row blocks that GEMM left behind, they are fixed by a launch of their own first.
-int gemm(vitx_ctx *c, const Tuning &tune, hipStream_t st, int pc, int epi, const void *A, const void *W, const float *bias, void *out, const float *pos,
-         int M, int M_real, int N, int N_pad, int K, int lda, int ldw, int ldo, int tpi, size_t out_elem_bytes, const QuantW *fused = nullptr, const GemmLn *ln = nullptr,
+// One GEMM launch (+ its profile record).  `fused` != nullptr: W is that q4_0 matrix and the GEMM expands the blocks in its own LDS-fill path
+// (small batches).  `fix`: the GemmLn of the LayerNorm-fusing GEMM that produced A (GemmArgs::fix); when the kernel this shape selects cannot
+// recompute the row blocks that GEMM left behind, they are fixed by a launch of their own first.  `rows_alg`: the rows the profile counts
+// (0 = a.M_real).
+int gemm(vitx_ctx *c, hipStream_t st, int pc, int epi, GemmArgs a, const QuantW *fused = nullptr, const GemmLn *ln = nullptr,
          const GemmLn *fix = nullptr, long hilo_off = 0, int rows_alg = 0) {
-    GemmArgs a{};
-    a.A = A; a.W = W; a.bias = bias; a.out = out; a.pos = pos; a.hilo_off = hilo_off;
-    a.M = M; a.M_real = M_real; a.N = N; a.N_pad = N_pad; a.K = K; a.lda = lda; a.ldw = ldw; a.ldo = ldo; a.tpi = tpi;
-    a.ln = ln;
+    a.hilo_off = hilo_off; a.ln = ln;
     if (fix) {
-        if (!fused && gemm_fix_capable(tune, a)) a.fix = fix;
+        if (!fused && gemm_fix_capable(*c->tune, a)) a.fix = fix;
         else {
             ProfScope ps(c, st, PC_LAYERNORM, 0, 0);
-            HIP_TRY(launch_layernorm_fixup(c->dtype, fix->x, fix->w, fix->b, fix->out, M, K, fix->eps, fix->todo, fix->epoch, st));
+            HIP_TRY(launch_layernorm_fixup(c->dtype, fix->x, fix->w, fix->b, fix->out, a.M, a.K, fix->eps, fix->todo, fix->epoch, st));
         }
     }
     // algorithmic work of the launch: the REAL rows (a LayerNorm-fusing launch computes and stores its pad rows too -- GemmLn -- but they are not work
     // the forward asked for: r03 counted them, +0.46 % on the fc2 figure)
-    const int M_alg = rows_alg > 0 ? rows_alg : M_real;
-    double bytes = (double)M_alg * K * 2 + (double)N * K * (fused ? 0.5625 : 2.0) + (double)M_alg * N * out_elem_bytes;
+    const int M_alg = rows_alg > 0 ? rows_alg : a.M_real, N = a.N, K = a.K, esz = epi_out_bytes(epi);
+    double bytes = (double)M_alg * K * 2 + (double)N * K * (fused ? 0.5625 : 2.0) + (double)M_alg * N * esz;
     if (epi == EPI_BIAS_RESID) bytes += (double)M_alg * N * 4;
-    if (epi == EPI_BIAS_HILO) bytes += (double)M_alg * N * out_elem_bytes;        // the second plane
+    if (epi == EPI_BIAS_HILO) bytes += (double)M_alg * N * esz;        // the second plane
     if (ln) bytes += (double)M_alg * N * 2;
     ProfScope ps(c, st, pc, 2.0 * M_alg * (double)N * K, bytes);
     if (fused) {
@@ -340,7 +331,7 @@ int gemm(vitx_ctx *c, const Tuning &tune, hipStream_t st, int pc, int epi, const
         HIP_TRY(launch_gemm_q4(c->dtype, epi, a, st));
         return VITX_OK;
     }
-    HIP_TRY(launch_gemm(tune, c->dtype, epi, a, st));
+    HIP_TRY(launch_gemm(*c->tune, c->dtype, epi, a, st));
     return VITX_OK;
 }
 
@@ -399,7 +390,6 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
     c->ln_fuse = !opt.no_ln_fusion && !opt.graph;        // a captured launch would replay its epoch tag: no fusion under the graph cache
 #ifdef VITX_LAB
     if (const char *e = getenv("VITX_SKIP")) c->skip = atoi(e);
-    if (const char *e = getenv("VITX_SPLIT")) c->split_first = atoi(e);
 #endif
     HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
 
@@ -416,42 +406,34 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
         c->wset = have; c->weights_shared = true;
     } else {
         c->wset = std::make_shared<vitx_ctx::WeightSet>();
-        c->wset->device = device;
-    }
-    if (!c->weights_shared) {
-    if ((rc = upload_f32(c.get(), T("cls_token"), &c->cls))) return rc;
-    if ((rc = upload_f32(c.get(), T("pos_embed"), &c->pos))) return rc;
-    if ((rc = upload_f32(c.get(), T("patch_embed.proj.bias"), &c->pe_b, round_up(D, tn)))) return rc;
-    if ((rc = upload_matrix(c.get(), T("patch_embed.proj.weight"), D, c->Kpe, round_up(D, tn), c->Kpe_pad, &c->pe_w, c->P, c->Cin))) return rc;
-    c->layers.resize(c->L);
-    for (int i = 0; i < c->L; ++i) {
-        const std::string p = "blocks." + std::to_string(i) + ".";
-        LayerW &w = c->layers[i];
-        if ((rc = upload_f32(c.get(), T(p + "norm1.weight"), &w.ln1_w))) return rc;
-        if ((rc = upload_f32(c.get(), T(p + "norm1.bias"), &w.ln1_b))) return rc;
-        if ((rc = upload_f32(c.get(), T(p + "norm2.weight"), &w.ln2_w))) return rc;
-        if ((rc = upload_f32(c.get(), T(p + "norm2.bias"), &w.ln2_b))) return rc;
-        if ((rc = upload_f32(c.get(), T(p + "attn.qkv.bias"), &w.qkv_b, round_up(3 * D, tn)))) return rc;
-        if ((rc = upload_f32(c.get(), T(p + "attn.proj.bias"), &w.proj_b, round_up(D, tn)))) return rc;
-        if ((rc = upload_f32(c.get(), T(p + "mlp.fc1.bias"), &w.fc1_b, round_up(4 * D, tn)))) return rc;
-        if ((rc = upload_f32(c.get(), T(p + "mlp.fc2.bias"), &w.fc2_b, round_up(D, tn)))) return rc;
-        if ((rc = upload_weight(c.get(), T(p + "attn.qkv.weight"), 3 * D, D, round_up(3 * D, tn), &w.qkv_w, &w.q[W_QKV]))) return rc;
-        if ((rc = upload_weight(c.get(), T(p + "attn.proj.weight"), D, D, round_up(D, tn), &w.proj_w, &w.q[W_PROJ]))) return rc;
-        if ((rc = upload_weight(c.get(), T(p + "mlp.fc1.weight"), 4 * D, D, round_up(4 * D, tn), &w.fc1_w, &w.q[W_FC1]))) return rc;
-        if ((rc = upload_weight(c.get(), T(p + "mlp.fc2.weight"), D, 4 * D, round_up(D, tn), &w.fc2_w, &w.q[W_FC2]))) return rc;
-    }
-    if ((rc = upload_f32(c.get(), T("norm.weight"), &c->norm_w))) return rc;
-    if ((rc = upload_f32(c.get(), T("norm.bias"), &c->norm_b))) return rc;
-    if ((rc = upload_f32(c.get(), T("head.bias"), &c->head_b, c->C_pad))) return rc;
-    if ((rc = upload_weight(c.get(), T("head.weight"), c->C, D, c->C_pad, &c->head_w, &c->head_q))) return rc;
-        vitx_ctx::WeightSet &w = *c->wset;
-        w.cls = c->cls; w.pos = c->pos; w.pe_b = c->pe_b; w.norm_w = c->norm_w; w.norm_b = c->norm_b; w.head_b = c->head_b;
-        w.pe_w = c->pe_w; w.head_w = c->head_w; w.head_q = c->head_q; w.layers = c->layers; w.weight_bytes = c->weight_bytes;
+        vitx_ctx::WeightSet &ws = *c->wset;
+        ws.device = device;
+        if ((rc = upload_f32(c.get(), T("cls_token"), &ws.cls))) return rc;
+        if ((rc = upload_f32(c.get(), T("pos_embed"), &ws.pos))) return rc;
+        if ((rc = upload_f32(c.get(), T("patch_embed.proj.bias"), &ws.pe_b, round_up(D, tn)))) return rc;
+        if ((rc = upload_matrix(c.get(), T("patch_embed.proj.weight"), D, c->Kpe, round_up(D, tn), c->Kpe_pad, &ws.pe_w, c->P, c->Cin))) return rc;
+        ws.layers.resize(c->L);
+        for (int i = 0; i < c->L; ++i) {
+            const std::string p = "blocks." + std::to_string(i) + ".";
+            LayerW &w = ws.layers[i];
+            if ((rc = upload_f32(c.get(), T(p + "norm1.weight"), &w.ln1_w))) return rc;
+            if ((rc = upload_f32(c.get(), T(p + "norm1.bias"), &w.ln1_b))) return rc;
+            if ((rc = upload_f32(c.get(), T(p + "norm2.weight"), &w.ln2_w))) return rc;
+            if ((rc = upload_f32(c.get(), T(p + "norm2.bias"), &w.ln2_b))) return rc;
+            if ((rc = upload_f32(c.get(), T(p + "attn.qkv.bias"), &w.qkv_b, round_up(3 * D, tn)))) return rc;
+            if ((rc = upload_f32(c.get(), T(p + "attn.proj.bias"), &w.proj_b, round_up(D, tn)))) return rc;
+            if ((rc = upload_f32(c.get(), T(p + "mlp.fc1.bias"), &w.fc1_b, round_up(4 * D, tn)))) return rc;
+            if ((rc = upload_f32(c.get(), T(p + "mlp.fc2.bias"), &w.fc2_b, round_up(D, tn)))) return rc;
+            if ((rc = upload_weight(c.get(), T(p + "attn.qkv.weight"), 3 * D, D, round_up(3 * D, tn), &w.qkv_w, &w.q[W_QKV]))) return rc;
+            if ((rc = upload_weight(c.get(), T(p + "attn.proj.weight"), D, D, round_up(D, tn), &w.proj_w, &w.q[W_PROJ]))) return rc;
+            if ((rc = upload_weight(c.get(), T(p + "mlp.fc1.weight"), 4 * D, D, round_up(4 * D, tn), &w.fc1_w, &w.q[W_FC1]))) return rc;
+            if ((rc = upload_weight(c.get(), T(p + "mlp.fc2.weight"), D, 4 * D, round_up(D, tn), &w.fc2_w, &w.q[W_FC2]))) return rc;
+        }
+        if ((rc = upload_f32(c.get(), T("norm.weight"), &ws.norm_w))) return rc;
+        if ((rc = upload_f32(c.get(), T("norm.bias"), &ws.norm_b))) return rc;
+        if ((rc = upload_f32(c.get(), T("head.bias"), &ws.head_b, c->C_pad))) return rc;
+        if ((rc = upload_weight(c.get(), T("head.weight"), c->C, D, c->C_pad, &ws.head_w, &ws.head_q))) return rc;
         wreg[wkey] = c->wset;
-    } else {
-        const vitx_ctx::WeightSet &w = *c->wset;
-        c->cls = w.cls; c->pos = w.pos; c->pe_b = w.pe_b; c->norm_w = w.norm_w; c->norm_b = w.norm_b; c->head_b = w.head_b;
-        c->pe_w = w.pe_w; c->head_w = w.head_w; c->head_q = w.head_q; c->layers = w.layers; c->weight_bytes = w.weight_bytes;
     }
     wlock.unlock();
 
@@ -495,14 +477,11 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
         // expansion scratch for quantised matrices: one buffer per matrix kind, shared by all layers (the largest layer decides)
         for (int k = 0; k < W_PER_LAYER; ++k) {
             size_t need = 0;
-            for (const LayerW &w : c->layers) if (w.q[k].blocks) need = std::max(need, (size_t)w.q[k].n_pad * w.q[k].K * 2);
+            for (const LayerW &w : c->wset->layers) if (w.q[k].blocks) need = std::max(need, (size_t)w.q[k].n_pad * w.q[k].K * 2);
             if (need && (rc = c->dmalloc(&sl.Wq[k], need, false))) return rc;
         }
-        if (c->head_q.blocks && (rc = c->dmalloc(&sl.Wq_head, (size_t)c->head_q.n_pad * c->head_q.K * 2, false))) return rc;
-        sl.tune = *c->tune;
-#ifdef VITX_LAB
-        if (const char *e = getenv("VITX_SLICE_CU")) { if (ns > 1 && atoi(e) > 0) sl.tune.n_cu = atoi(e); }      // persistent grids of each sub-batch capped (experiment)
-#endif
+        const QuantW &hq = c->wset->head_q;
+        if (hq.blocks && (rc = c->dmalloc(&sl.Wq_head, (size_t)hq.n_pad * hq.K * 2, false))) return rc;
         if (ns > 1 && i > 0) {
             // Slice 0 runs on the CALLER's stream, slices 1.. on internal HIGH-priority streams.  The runtime multiplexes all streams of one
             // priority onto a small pool of hardware queues (GPU_MAX_HW_QUEUES, 4 by default), round-robin in creation order; a hardware queue
@@ -594,10 +573,9 @@ static int forward_slice(vitx_ctx *c, vitx_ctx::Slice &sl, hipStream_t st, const
         }
         return VITX_OK;
     };
+    const vitx_ctx::WeightSet &ws = *c->wset;
     const int D = c->D, N = c->N, tm = c->tm, tn = c->tn, dt = c->dtype;
-    const int tpi = c->g * c->g;
-    const Tuning &tn_ = sl.tune;
-    const int Mp_real = n * tpi;                                   // patch rows
+    const int Mp_real = n * c->g * c->g;                           // patch rows
     const int M_real = n * N, M = round_up(M_real, tm);            // token rows
     const double eb = 2.0;                                          // operand bytes
     const long lo_off = c->prec_attn ? (long)M * 3 * D : 0;         // F16 parity mode: the lo plane of q, k, v right behind this sub-batch's hi plane (elements)
@@ -606,7 +584,7 @@ static int forward_slice(vitx_ctx *c, vitx_ctx::Slice &sl, hipStream_t st, const
     int rc;
     {
         ProfScope ps(c, st, PC_GEMM_PATCH, 2.0 * Mp_real * (double)D * c->Kpe, (double)n * c->S * c->S * c->Cin * 4 + (double)M_real * D * 4);
-        HIP_TRY(launch_patch_embed(dt, (const float *)d_imgs, c->pe_w, c->pe_b, c->pos, c->cls, sl.X, n, c->S, c->P, c->Cin, D, round_up(D, tn), c->Kpe_pad, st));
+        HIP_TRY(launch_patch_embed(dt, (const float *)d_imgs, ws.pe_w, ws.pe_b, ws.pos, ws.cls, sl.X, n, c->S, c->P, c->Cin, D, round_up(D, tn), c->Kpe_pad, st));
     }
     if (!c->trace_ids.empty() && (rc = trace(0))) return rc;
     // Quantised matrices (block form in HBM): a q4_0 GEMM with few rows expands the blocks in its own LDS-fill path; everything else
@@ -633,44 +611,53 @@ static int forward_slice(vitx_ctx *c, vitx_ctx::Slice &sl, hipStream_t st, const
 #else
     constexpr int skip = 0;
 #endif
+    // one LayerNorm launch (+ its profile record): `rows` rows of x (row stride ldx; group > 1: see launch_layernorm) -> y [rows][D]
+    auto layernorm = [&](const float *x, long ldx, const float *lw, const float *lb, void *y, int rows, int group = 1, long gstride = 0) -> int {
+        ProfScope ps(c, st, PC_LAYERNORM, 0, (double)rows * D * (4 + eb));
+        HIP_TRY(launch_layernorm(dt, x, ldx, lw, lb, y, D, rows, D, c->hp.eps, st, group, gstride));
+        return VITX_OK;
+    };
     // LayerNorm fusion: decided per forward (the GEMM shape of this sub-batch must take the wide persistent kernel; never while the caller is
     // capturing a graph -- the epoch tag of a captured launch would be replayed).  The padded rows M_real .. M of X are then computed and
     // stored as well (GemmLn): they belong to this slice's scratch, start as zeros and stay finite.
     bool fuse = false;
     if (c->ln_fuse && sl.ln_sync) {
-        GemmArgs probe{}; probe.M = M; probe.N = D; probe.N_pad = round_up(D, tn); probe.K = D; probe.lda = D; probe.ldw = D; probe.ldo = D;
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
-        GemmArgs probe2 = probe; probe2.K = 4 * D; probe2.lda = 4 * D; probe2.ldw = 4 * D;
-        fuse = cs == hipStreamCaptureStatusNone && gemm_ln_fusable(tn_, probe) && gemm_ln_fusable(tn_, probe2);
+        fuse = cs == hipStreamCaptureStatusNone && gemm_ln_fusable(*c->tune, dense_gemm(nullptr, nullptr, nullptr, nullptr, M, M, D, round_up(D, tn), D)) &&
+               gemm_ln_fusable(*c->tune, dense_gemm(nullptr, nullptr, nullptr, nullptr, M, M, D, round_up(D, tn), 4 * D));
     }
-    // residual GEMM (+ the LayerNorm that follows it, fused when `fuse`; otherwise its own launch) -- proj + norm2, fc2 + the next norm1
+    // The rows a layer carries past its attention (proj + norm2, fc1, fc2 + the next norm1): every token row of the sub-batch, or -- the last
+    // layer of a cls_tail context (vitx_ctx::cls_tail) -- the n class-token rows Xc, padded to Mc, never LayerNorm-fused
+    struct Rows { float *X; int M, M_real, pc_proj, pc_fc1, pc_fc2; bool fuse; };
+    const Rows all_rows{sl.X, M, M_real, PC_GEMM_PROJ, PC_GEMM_FC1, PC_GEMM_FC2, fuse};
+    const Rows cls_rows{sl.Xc, round_up(n, tm), n, PC_GEMM_TAIL, PC_GEMM_TAIL, PC_GEMM_TAIL, false};
+    // residual GEMM (+ the LayerNorm that follows it, fused when r.fuse; otherwise its own launch) -- proj + norm2, fc2 + the next norm1
     // `pend` receives the launch's GemmLn when the LayerNorm was fused: the GEMM that consumes ln_out next gets it as its `fix` argument
-    auto resid_gemm_ln = [&](int pc, const void *A, const void *W, const float *bias, int K, const QuantW *fq, const float *lw, const float *lb, void *ln_out, GemmLn *pend) -> int {
+    auto resid_gemm_ln = [&](const Rows &r, int pc, const void *A, const void *W, const float *bias, int K, const QuantW *fq, const float *lw, const float *lb, void *ln_out, GemmLn *pend) -> int {
         int rc2;
         pend->todo = nullptr;
-        if (fuse && lw && !fq) {
+        GemmArgs a = dense_gemm(A, W, bias, r.X, r.M, r.M_real, D, round_up(D, tn), K);
+        if (r.fuse && lw && !fq) {
             GemmLn ln{};
-            ln.w = lw; ln.b = lb; ln.x = sl.X; ln.out = ln_out; ln.eps = c->hp.eps; ln.sync = sl.ln_sync; ln.todo = sl.ln_todo; ln.fallbacks = sl.ln_todo + sl.ln_blocks;
+            ln.w = lw; ln.b = lb; ln.x = r.X; ln.out = ln_out; ln.eps = c->hp.eps; ln.sync = sl.ln_sync; ln.todo = sl.ln_todo; ln.fallbacks = sl.ln_todo + sl.ln_blocks;
             if (++c->ln_epoch == 0) c->ln_epoch = 1;
             ln.epoch = c->ln_epoch; ln.timeout = c->ln_timeout; ln.test = c->ln_test;
-            if ((rc2 = gemm(c, tn_, st, pc, EPI_BIAS_RESID, A, W, bias, sl.X, nullptr, M, M, D, round_up(D, tn), K, K, K, D, 0, 4, nullptr, &ln, nullptr, 0, M_real))) return rc2;
+            a.M_real = r.M;             // the pad rows are stored too; the profile counts the real ones
+            if ((rc2 = gemm(c, st, pc, EPI_BIAS_RESID, a, nullptr, &ln, nullptr, 0, r.M_real))) return rc2;
             *pend = ln;
             return VITX_OK;
         }
-        if ((rc2 = gemm(c, tn_, st, pc, EPI_BIAS_RESID, A, W, bias, sl.X, nullptr, M, M_real, D, round_up(D, tn), K, K, K, D, 0, 4, fq))) return rc2;
-        if (lw) {
-            ProfScope ps(c, st, PC_LAYERNORM, 0, (double)M_real * D * (4 + eb));
-            if (!(skip & 2)) HIP_TRY(launch_layernorm(dt, sl.X, D, lw, lb, ln_out, D, M_real, D, c->hp.eps, st));
-        }
+        if ((rc2 = gemm(c, st, pc, EPI_BIAS_RESID, a, fq))) return rc2;
+        if (lw && !(skip & 2)) return layernorm(r.X, D, lw, lb, ln_out, r.M_real);
         return VITX_OK;
     };
     GemmLn fix_u{}, fix_u2{};          // fused LayerNorm launches whose output (U / U2) has not been consumed yet
     const bool tail = c->cls_tail && c->trace_ids.empty();      // the last layer carries only the class-token rows past its qkv projection (vitx_ctx::cls_tail)
-    const int Mc = round_up(n, tm);                             // rows of the tail GEMMs (n real ones)
     for (int il = 0; il < c->L; ++il) {
-        const LayerW &w = c->layers[il];
+        const LayerW &w = ws.layers[il];
         const bool tail_now = tail && il + 1 == c->L;
+        const Rows &r = tail_now ? cls_rows : all_rows;
         const void *Wl[W_PER_LAYER] = {w.qkv_w, w.proj_w, w.fc1_w, w.fc2_w};
         const QuantW *Fl[W_PER_LAYER] = {nullptr, nullptr, nullptr, nullptr};      // matrices the fused kernel takes
         {
@@ -678,106 +665,52 @@ static int forward_slice(vitx_ctx *c, vitx_ctx::Slice &sl, hipStream_t st, const
             bool any = false;
             for (int k = 0; k < W_PER_LAYER; ++k) {
                 if (!w.q[k].blocks) continue;
-                if (fused_ok(w.q[k], (tail_now && k != W_QKV) ? Mc : M)) Fl[k] = &w.q[k];
+                if (fused_ok(w.q[k], k == W_QKV ? M : r.M)) Fl[k] = &w.q[k];
                 else { todo[k] = &w.q[k]; Wl[k] = sl.Wq[k]; any = true; }
             }
             if (any && (rc = expand(todo, sl.Wq, W_PER_LAYER))) return rc;
         }
-        if (il == 0) {   // norm1 of the first layer (vit.cpp:808-812); every later norm1 comes out of the previous layer's fc2
-            ProfScope ps(c, st, PC_LAYERNORM, 0, (double)M_real * D * (4 + eb));
-            if (!(skip & 2)) HIP_TRY(launch_layernorm(dt, sl.X, D, w.ln1_w, w.ln1_b, sl.U, D, M_real, D, c->hp.eps, st));
-        }
-#ifdef VITX_LAB
-        if (il == 0 && getenv("VITX_SNAP")) {      // lab: X and the first norm1 output of this slice
-            static int run1[4] = {0, 0, 0, 0};
-            const int si = (int)(&sl - &c->slices[0]);
-            std::vector<char> hx((size_t)M_real * D * 4), hu((size_t)M_real * D * 2);
-            HIP_TRY(hipMemcpyAsync(hx.data(), sl.X, hx.size(), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(hu.data(), sl.U, hu.size(), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            char fn[512];
-            snprintf(fn, sizeof fn, "%s/snap_s%d_r%d_x0.bin", getenv("VITX_SNAP"), si, run1[si]); { FILE *f = fopen(fn, "wb"); if (f) { fwrite(hx.data(), 1, hx.size(), f); fclose(f); } }
-            snprintf(fn, sizeof fn, "%s/snap_s%d_r%d_ln1.bin", getenv("VITX_SNAP"), si, run1[si]); { FILE *f = fopen(fn, "wb"); if (f) { fwrite(hu.data(), 1, hu.size(), f); fclose(f); } }
-            ++run1[si];
-        }
-#endif
+        // norm1 of the first layer (vit.cpp:808-812); every later norm1 comes out of the previous layer's fc2
+        if (il == 0 && !(skip & 2) && (rc = layernorm(sl.X, D, w.ln1_w, w.ln1_b, sl.U, M_real))) return rc;
         // qkv projection (vit.cpp:820-821); `fix_u`: row blocks of U the previous layer's fc2 left to the fix-up are normalised in its prologue
-#ifdef VITX_LAB
-        static const int prec_dbg = getenv("VITX_PREC_DBG") ? atoi(getenv("VITX_PREC_DBG")) : 0;      // 1: HILO GEMM + fast attention on the hi plane; 2: plain GEMM + precise attention (lo plane stays zero)
-#else
-        constexpr int prec_dbg = 0;
-#endif
-        if ((rc = gemm(c, tn_, st, PC_GEMM_QKV, (c->prec_attn && prec_dbg != 2) ? EPI_BIAS_HILO : EPI_BIAS, sl.U, Wl[W_QKV], w.qkv_b, sl.QKV, nullptr, M, M_real, 3 * D, round_up(3 * D, tn), D, D, D, 3 * D, 0, 2, Fl[W_QKV], nullptr,
-                       fix_u.todo ? &fix_u : nullptr, lo_off))) return rc;
+        if ((rc = gemm(c, st, PC_GEMM_QKV, c->prec_attn ? EPI_BIAS_HILO : EPI_BIAS, dense_gemm(sl.U, Wl[W_QKV], w.qkv_b, sl.QKV, M, M_real, 3 * D, round_up(3 * D, tn), D),
+                       Fl[W_QKV], nullptr, fix_u.todo ? &fix_u : nullptr, lo_off))) return rc;
         if (c->attn_on() && (rc = attention_maps(c, st, sl.QKV, lo_off, il, first_img, n))) return rc;
-        if (tail_now) {
-            {   // attention of token 0 (vit.cpp:848-858 for the one row vit.cpp:910-911 keeps) -> compact rows U[b]; class rows of X -> Xc[b]
-                ProfScope ps(c, st, PC_ATTENTION_CLS, 4.0 * n * c->H * (double)N * (D / c->H), (double)M_real * 2 * D * eb * (c->prec_attn ? 2 : 1) + (double)n * D * (eb + 8));
-                HIP_TRY(launch_attention_cls(dt, sl.QKV, lo_off, sl.U, sl.X, sl.Xc, n, N, D, c->H, st));
-            }
-            // output projection + residual, norm2, MLP (vit.cpp:868-900) on the n class rows
-            if ((rc = gemm(c, tn_, st, PC_GEMM_TAIL, EPI_BIAS_RESID, sl.U, Wl[W_PROJ], w.proj_b, sl.Xc, nullptr, Mc, n, D, round_up(D, tn), D, D, D, D, 0, 4, Fl[W_PROJ]))) return rc;
-            {
-                ProfScope ps(c, st, PC_LAYERNORM, 0, (double)n * D * (4 + eb));
-                HIP_TRY(launch_layernorm(dt, sl.Xc, D, w.ln2_w, w.ln2_b, sl.U2, D, n, D, c->hp.eps, st));
-            }
-            if ((rc = gemm(c, tn_, st, PC_GEMM_TAIL, EPI_BIAS_GELU, sl.U2, Wl[W_FC1], w.fc1_b, sl.Hbuf, nullptr, Mc, n, 4 * D, round_up(4 * D, tn), D, D, D, 4 * D, 0, 2, Fl[W_FC1]))) return rc;
-            if ((rc = gemm(c, tn_, st, PC_GEMM_TAIL, EPI_BIAS_RESID, sl.Hbuf, Wl[W_FC2], w.fc2_b, sl.Xc, nullptr, Mc, n, D, round_up(D, tn), 4 * D, 4 * D, 4 * D, D, 0, 4, Fl[W_FC2]))) return rc;
-            break;
-        }
-        {   // attention (vit.cpp:826-866)
+        if (tail_now) {   // attention of token 0 (vit.cpp:848-858 for the one row vit.cpp:910-911 keeps) -> compact rows U[b]; class rows of X -> Xc[b]
+            ProfScope ps(c, st, PC_ATTENTION_CLS, 4.0 * n * c->H * (double)N * (D / c->H), (double)M_real * 2 * D * eb * (c->prec_attn ? 2 : 1) + (double)n * D * (eb + 8));
+            HIP_TRY(launch_attention_cls(dt, sl.QKV, lo_off, sl.U, sl.X, sl.Xc, n, N, D, c->H, st));
+        } else {          // attention (vit.cpp:826-866)
             ProfScope ps(c, st, PC_ATTENTION, 4.0 * n * c->H * (double)N * N * (D / c->H), (double)M_real * (c->prec_attn ? 7 : 4) * D * eb);
             if (!(skip & 1)) {
-                if (c->prec_attn && prec_dbg != 1) {
-                    if (prec_dbg == 3) HIP_TRY(hipDeviceSynchronize());          // lab: the attention kernel runs alone on the device
-                    HIP_TRY(launch_attention_stream(dt, true, sl.QKV, sl.U, n, N, D, c->H, lo_off, st));
-                    if (prec_dbg == 3) HIP_TRY(hipDeviceSynchronize());
-                    if (prec_dbg == 4) HIP_TRY(hipStreamSynchronize(st));        // lab: host-side order after it, other stream keeps running
-                }
+                if (c->prec_attn) HIP_TRY(launch_attention_stream(dt, true, sl.QKV, sl.U, n, N, D, c->H, lo_off, st));
                 else HIP_TRY(launch_attention(*c->tune, dt, sl.QKV, sl.U, n, N, D, c->H, st));
             }
         }
-#ifdef VITX_LAB
-        if (il == 0 && getenv("VITX_SNAP")) {      // lab: QKV (hi plane) and the attention output of layer 0 of this slice, to files (synchronous)
-            static int run[4] = {0, 0, 0, 0};
-            const int si = (int)(&sl - &c->slices[0]);
-            std::vector<char> hq((size_t)M_real * 3 * D * 2), hu((size_t)M_real * D * 2);
-            HIP_TRY(hipMemcpyAsync(hq.data(), sl.QKV, hq.size(), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(hu.data(), sl.U, hu.size(), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            char fn[512];
-            snprintf(fn, sizeof fn, "%s/snap_s%d_r%d_qkv.bin", getenv("VITX_SNAP"), si, run[si]); { FILE *f = fopen(fn, "wb"); if (f) { fwrite(hq.data(), 1, hq.size(), f); fclose(f); } }
-            snprintf(fn, sizeof fn, "%s/snap_s%d_r%d_u.bin", getenv("VITX_SNAP"), si, run[si]); { FILE *f = fopen(fn, "wb"); if (f) { fwrite(hu.data(), 1, hu.size(), f); fclose(f); } }
-            ++run[si];
-        }
-#endif
         // output projection + residual (vit.cpp:868-873), then norm2 (vit.cpp:881-885) -> U2
-        if ((rc = resid_gemm_ln(PC_GEMM_PROJ, sl.U, Wl[W_PROJ], w.proj_b, D, Fl[W_PROJ], w.ln2_w, w.ln2_b, sl.U2, &fix_u2))) return rc;
-        // MLP (vit.cpp:889-900), then the NEXT layer's norm1 (vit.cpp:808-812) -> U; the last layer is followed by the cls-row norm instead
-        if ((rc = gemm(c, tn_, st, PC_GEMM_FC1, EPI_BIAS_GELU, sl.U2, Wl[W_FC1], w.fc1_b, sl.Hbuf, nullptr, M, M_real, 4 * D, round_up(4 * D, tn), D, D, D, 4 * D, 0, 2, Fl[W_FC1], nullptr,
+        if ((rc = resid_gemm_ln(r, r.pc_proj, sl.U, Wl[W_PROJ], w.proj_b, D, Fl[W_PROJ], w.ln2_w, w.ln2_b, sl.U2, &fix_u2))) return rc;
+        // MLP (vit.cpp:889-900), then the NEXT layer's norm1 (vit.cpp:808-812) -> U; the last layer is followed by the final norm instead
+        if ((rc = gemm(c, st, r.pc_fc1, EPI_BIAS_GELU, dense_gemm(sl.U2, Wl[W_FC1], w.fc1_b, sl.Hbuf, r.M, r.M_real, 4 * D, round_up(4 * D, tn), D), Fl[W_FC1], nullptr,
                        fix_u2.todo ? &fix_u2 : nullptr))) return rc;
-        const LayerW *nx = il + 1 < c->L ? &c->layers[il + 1] : nullptr;
-        if ((rc = resid_gemm_ln(PC_GEMM_FC2, sl.Hbuf, Wl[W_FC2], w.fc2_b, 4 * D, Fl[W_FC2], nx ? nx->ln1_w : nullptr, nx ? nx->ln1_b : nullptr, sl.U, &fix_u))) return rc;
+        const LayerW *nx = il + 1 < c->L ? &ws.layers[il + 1] : nullptr;
+        if ((rc = resid_gemm_ln(r, r.pc_fc2, sl.Hbuf, Wl[W_FC2], w.fc2_b, 4 * D, Fl[W_FC2], nx ? nx->ln1_w : nullptr, nx ? nx->ln1_b : nullptr, sl.U, &fix_u))) return rc;
         if (!c->trace_ids.empty() && (rc = trace(il + 1))) return rc;
     }
     // cls pooling + final norm (vit.cpp:910-919): row b*N of X, i.e. row stride N*D.  ViTSTR (vitstr.cpp:864-895) keeps the first
     // R = 25 tokens of every image instead: output row r = image r / R, token r % R.
     const int nR = n * c->R;
-    {
-        ProfScope ps(c, st, PC_LAYERNORM, 0, (double)nR * D * (4 + eb));
-        // classifier: one row per image, row stride N*D; ViTSTR: groups of R consecutive token rows (stride D), group stride N*D
-        if (tail) HIP_TRY(launch_layernorm(dt, sl.Xc, D, c->norm_w, c->norm_b, sl.Z, D, n, D, c->hp.eps, st));
-        else HIP_TRY(launch_layernorm(dt, sl.X, c->R == 1 ? (long)N * D : (long)D, c->norm_w, c->norm_b, sl.Z, D, nR, D, c->hp.eps, st, c->R, (long)N * D));
-    }
+    // classifier: one row per image, row stride N*D; ViTSTR: groups of R consecutive token rows (stride D), group stride N*D
+    if (tail) rc = layernorm(sl.Xc, D, ws.norm_w, ws.norm_b, sl.Z, n);
+    else rc = layernorm(sl.X, c->R == 1 ? (long)N * D : (long)D, ws.norm_w, ws.norm_b, sl.Z, nR, c->R, (long)N * D);
+    if (rc) return rc;
     // classifier (vit.cpp:927-928) and class softmax (vit.cpp:931-933)
     float *lg = d_logits ? (float *)d_logits : sl.logits;
     const int ldl = d_logits ? c->C : c->C_pad;
-    const void *head_w = c->head_w; const QuantW *head_f = nullptr;
-    if (c->head_q.blocks) {
-        if (fused_ok(c->head_q, round_up(nR, tm))) head_f = &c->head_q;
-        else { const QuantW *todo[1] = {&c->head_q}; void *dst[1] = {sl.Wq_head}; if ((rc = expand(todo, dst, 1))) return rc; head_w = sl.Wq_head; }
+    const void *head_w = ws.head_w; const QuantW *head_f = nullptr;
+    if (ws.head_q.blocks) {
+        if (fused_ok(ws.head_q, round_up(nR, tm))) head_f = &ws.head_q;
+        else { const QuantW *todo[1] = {&ws.head_q}; void *dst[1] = {sl.Wq_head}; if ((rc = expand(todo, dst, 1))) return rc; head_w = sl.Wq_head; }
     }
-    if ((rc = gemm(c, tn_, st, PC_GEMM_HEAD, EPI_BIAS_F32, sl.Z, head_w, c->head_b, lg, nullptr, round_up(nR, tm), nR, c->C, c->C_pad, D, D, D, ldl, 0, 4, head_f))) return rc;
+    if ((rc = gemm(c, st, PC_GEMM_HEAD, EPI_BIAS_F32, dense_gemm(sl.Z, head_w, ws.head_b, lg, round_up(nR, tm), nR, c->C, c->C_pad, D, ldl), head_f))) return rc;
     {
         ProfScope ps(c, st, PC_SOFTMAX, 0, (double)nR * c->C * 8);
         HIP_TRY(launch_softmax(dt, lg, (float *)d_probs, nR, c->C, ldl, st));
@@ -790,7 +723,7 @@ static int forward_slice(vitx_ctx *c, vitx_ctx::Slice &sl, hipStream_t st, const
 // under whole rounds: for ViT-B on 256 CUs 110 images are 85 row tiles = 255 / 765 / 1020 tiles for N = 768 / 2304 / 3072
 // (1, 3 and 4 rounds) while 128 images cost 2 rounds' worth of time for 1.15 rounds of proj / fc2 work.  The first
 // sub-batch size is the minimiser of a tile-round model of the four GEMMs of a layer (same tiling rules as launch_gemm);
-// VITX_SPLIT=<images> overrides it.  More than two sub-batches are split evenly.
+// vitx_ctx_options::split_first overrides it.  More than two sub-batches are split evenly.
 static double gemm_round_cost(long rows, int N, int K, int n_cu) {
     const long ntm = (rows + 255) / 256, ntn = (N + 255) / 256, tiles = ntm * ntn, rounds = tiles / n_cu, rem = tiles % n_cu;
     const double slots = K / 32.0, t_tile = slots * 0.98 + 3.5, t_half = slots * 0.6 + 3.0;
@@ -1123,9 +1056,8 @@ static int op_gemm_impl(int dtype, int epi, int kernel, const void *a, const voi
     else if (kernel == 1) t.gemm_cfg = 1;                  // ping-pong persistent kernel
     else if (kernel != 0) t.gemm_cfg = kernel;
     // W (and bias) must hold n_pad rows; rows beyond N are never stored
-    GemmArgs g{};
-    g.A = a; g.W = w; g.bias = (const float *)bias; g.out = out; g.pos = (const float *)pos;
-    g.M = M; g.M_real = M_real; g.N = N; g.N_pad = n_pad; g.K = K; g.lda = K; g.ldw = K; g.ldo = N; g.tpi = tpi;
+    GemmArgs g = dense_gemm(a, w, (const float *)bias, out, M, M_real, N, n_pad, K);
+    g.pos = (const float *)pos; g.tpi = tpi;
     g.hilo_off = epi == EPI_BIAS_HILO ? (long)M * N : 0;          // the lo plane follows the [M][N] hi plane
     hipError_t e = launch_gemm(t, dtype, epi, g, (hipStream_t)stream);
     if (e == hipErrorInvalidValue) { set_error("vitx_op_gemm: kernel %d cannot tile M %d N %d K %d", kernel, M, N, K); return VITX_ERR_UNSUPPORTED; }
@@ -1146,8 +1078,7 @@ int vitx_op_gemm_ln(int dtype, const void *a, const void *w, const void *bias, v
     if (!a || !w || !bias || !x || !ln_w || !ln_b || !y || M <= 0 || timeout_us < 0) { set_error("vitx_op_gemm_ln: invalid argument"); return VITX_ERR_ARG; }
     const Tuning *t0 = tuning_for_device(-1);
     if (!t0) { set_error("vitx_op_gemm_ln: kernel bring-up failed"); return VITX_ERR_HIP; }
-    GemmArgs g{};
-    g.A = a; g.W = w; g.bias = (const float *)bias; g.out = x; g.M = M; g.M_real = M; g.N = N; g.N_pad = N; g.K = K; g.lda = K; g.ldw = K; g.ldo = N;
+    GemmArgs g = dense_gemm(a, w, (const float *)bias, x, M, M, N, N, K);
     if (!gemm_ln_fusable(*t0, g)) { set_error("vitx_op_gemm_ln: M %d N %d K %d does not take the LayerNorm-fusing kernel (M %% 256, N in {256,512,768,1024}, >= 128 tiles, K %% 128)", M, N, K); return VITX_ERR_UNSUPPORTED; }
     static unsigned epoch = 0x40000000u;       // its own tag range (the scratch is private to the call anyway)
     const size_t nb = (size_t)M / 256, sync_bytes = nb * (N / 256) * 256 * 2 * sizeof(unsigned long long);
@@ -1184,15 +1115,14 @@ int vitx_op_dequant(int dtype, int qtype, const void *blocks, const void *scales
 int vitx_op_gemm_q4(int dtype, int epi, const void *a, const void *qs, const void *scales, const void *bias, void *out, int M, int M_real, int N, int K, void *stream) {
     if (!a || !qs || !scales || !bias || !out || epi < 0 || epi > EPI_BIAS_F32 || M_real <= 0 || M_real > M) { set_error("vitx_op_gemm_q4: invalid argument"); return VITX_ERR_ARG; }
     if (!tuning_for_device(-1)) { set_error("vitx_op_gemm_q4: kernel bring-up failed"); return VITX_ERR_HIP; }
-    GemmArgs g{};
-    g.A = a; g.W = qs; g.Wscale = (const uint16_t *)scales; g.bias = (const float *)bias; g.out = out;
-    g.M = M; g.M_real = M_real; g.N = N; g.N_pad = round_up(N, 128); g.K = K; g.lda = K; g.ldw = K; g.ldo = N;
+    GemmArgs g = dense_gemm(a, qs, (const float *)bias, out, M, M_real, N, round_up(N, 128), K);
+    g.Wscale = (const uint16_t *)scales;
     hipError_t e = launch_gemm_q4(dtype, epi, g, (hipStream_t)stream);
     if (e == hipErrorInvalidValue) { set_error("vitx_op_gemm_q4: M %% 128, K %% 64 must be 0 (M %d N %d K %d)", M, N, K); return VITX_ERR_UNSUPPORTED; }
     if (e != hipSuccess) { set_error("vitx_op_gemm_q4: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
     return VITX_OK;
 }
-size_t vitx_ctx_weight_bytes(const vitx_ctx *c) { return c ? c->weight_bytes : 0; }
+size_t vitx_ctx_weight_bytes(const vitx_ctx *c) { return c ? c->wset->weight_bytes : 0; }
 int vitx_ctx_shares_weights(const vitx_ctx *c) { return c && c->weights_shared ? 1 : 0; }
 int vitx_ctx_stream_retries(const vitx_ctx *c) { return c ? c->stream_retries : -1; }
 long long vitx_ctx_graph_launches(const vitx_ctx *c) { return c ? c->graph_launches : -1; }

@@ -231,7 +231,7 @@ template <typename T, int EPI, int NB>
 __device__ __forceinline__ void epilogue16_tile(const GemmArgs &g, f32x4 (&acc)[2 * NB][4], bool full, int m0, int n0, int wave_row0, int wave_col0, char *patch, int lane) {
     const int l15 = lane & 15, g4 = lane >> 4;
     if constexpr (EPI != EPI_PATCH) {
-        constexpr int esz = (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_HILO) ? 2 : 4;
+        constexpr int esz = epi_out_bytes(EPI);
         if (full && (size_t)g.M * g.ldo * esz + (EPI == EPI_BIAS_HILO ? (size_t)g.hilo_off * esz : 0) < 0xf0000000u && (g.ldo & 3) == 0) {
             f32x4 bq[4];
 #pragma unroll

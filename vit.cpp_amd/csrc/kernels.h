@@ -20,6 +20,8 @@ enum {
                          // (vit.cpp:826-858: ggml_mul_mat of f32 views), and hi + lo / 2048 reproduces v to 2^-22
 };
 constexpr float kHiLoScale = 2048.0f, kHiLoInv = 1.0f / 2048.0f;
+// bytes of one output element: the operand type (qkv, fc1) or f32 (residual, head, patch embedding)
+constexpr __host__ __device__ int epi_out_bytes(int epi) { return (epi == EPI_BIAS || epi == EPI_BIAS_GELU || epi == EPI_BIAS_HILO) ? 2 : 4; }
 
 struct GemmArgs {
     const void *A; const void *W; const float *bias; void *out; const float *pos;
@@ -44,6 +46,13 @@ struct GemmArgs {
     // shape selects does this; otherwise the caller launches launch_layernorm_fixup.
     const struct GemmLn *fix;
 };
+// The dense row-major case: A [M][K], W [N_pad][K], out [M][ldo] (ldo = N unless given); every other field zero
+inline GemmArgs dense_gemm(const void *A, const void *W, const float *bias, void *out, int M, int M_real, int N, int N_pad, int K, int ldo = 0) {
+    GemmArgs g{};
+    g.A = A; g.W = W; g.bias = bias; g.out = out;
+    g.M = M; g.M_real = M_real; g.N = N; g.N_pad = N_pad; g.K = K; g.lda = K; g.ldw = K; g.ldo = ldo ? ldo : N;
+    return g;
+}
 
 // The LayerNorm that follows a residual GEMM (vit.cpp:881-885 after proj, :808-812 of the next layer after fc2), computed by the
 // GEMM's own epilogue: every workgroup reduces its 256-column tile's per-row statistics from the accumulators, publishes them as

@@ -237,9 +237,8 @@ hipError_t launch_gemm(const Tuning &t, int dtype, int epi, const GemmArgs &a, h
             const int rows_main = m_main * 256;
             GemmArgs head = a, tail = a;
             head.M = rows_main; head.M_real = std::min(a.M_real, rows_main);
-            const size_t esz_out = (epi == EPI_BIAS || epi == EPI_BIAS_GELU || epi == EPI_BIAS_HILO) ? 2 : 4;
             tail.A = (const char *)a.A + (size_t)rows_main * a.lda * 2;
-            tail.out = (char *)a.out + (size_t)rows_main * a.ldo * esz_out;
+            tail.out = (char *)a.out + (size_t)rows_main * a.ldo * epi_out_bytes(epi);
             tail.M = a.M - rows_main; tail.M_real = a.M_real - rows_main;
             if (m_main >= 1 && rows_main < a.M && gemm_ring_supports(tail, 245)) {
                 hipError_t e = launch_wide(t, dtype, epi, head, stream);
