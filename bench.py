@@ -11,14 +11,18 @@ N>1: one process per GPU, images sharded by batch (weak scaling: 256 per GPU), w
 replicated, and ONE RCCL all-gather of the [256,1000] class probabilities per step.
 Prints one JSON line (rank 0).
 
-The line CERTIFIES parity (r03 verdict): the probabilities the timed steps produced are compared with the CPU oracle on 48 rows of
-the batch -- the images on either side of every sub-batch stream boundary among them -- next to the oracle's own summation-order
-noise on the same rows, and the run FAILS (exit code 1, line stamped invalid) when the timed configuration is outside the bounds
-the parity tests claim: F16 <= max(1e-3, 2 x noise floor), bf16 <= max(2e-2, 10 x noise floor), top-1 equal wherever the reference decides it.
-After the primary timed region, outside `value`, the same process measures with the SAME procedure (warm-up, timed steps, one
-per-kernel-profiled step outside the clock, oracle rows): the F16 parity mode ("parity_mode") and BASELINE.json's configs 3
-(ViT-L/16-384 bs 128) and 5 (q4_0 file) ("other_configs"); a >= 10 s sustained run with the package power / clock series; HBM-side
-traffic of the dominant kernel from two rocprofv3 --pmc passes spawned by this run.
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, --dump-outputs, the line.  Its `parity` says
+"unverified": nothing is compared with the oracle.
+
+--full adds everything else, after the timed region and outside `value`.  The line then CERTIFIES parity (r03 verdict): the
+probabilities the timed steps produced are compared with the CPU oracle on 48 rows of the batch -- the images on either side of every
+sub-batch stream boundary among them -- next to the oracle's own summation-order noise on the same rows, and the run FAILS (exit code 1,
+line stamped invalid) when the timed configuration is outside the bounds the parity tests claim: F16 <= max(1e-3, 2 x noise floor),
+bf16 <= max(2e-2, 10 x noise floor), top-1 equal wherever the reference decides it.  The same process also measures one per-kernel-profiled
+step (`roofline`, `kernel_breakdown`), the matrix-pipe probe, the host-fed rate, and with the SAME procedure (warm-up, timed steps, one
+profiled step outside the clock, oracle rows): the F16 parity mode ("parity_mode") and BASELINE.json's configs 3 (ViT-L/16-384 bs 128)
+and 5 (q4_0 file) ("other_configs"); a >= 10 s sustained run with the package power / clock series; HBM-side traffic of the dominant
+kernel from two rocprofv3 --pmc passes spawned by this run.  The full record goes to bench_extras.json.
 """
 import argparse
 import json
@@ -87,9 +91,10 @@ def _short_config(line):
     return s
 
 
-def compact_line(out):
+def compact_line(out, extras=True):
     """The ONE line the driver parses: the contract's keys, `roofline`, `cpu_baseline`, the gates, and one short summary per other
-    configuration.  Everything else of `out` (per-kernel tables, power series, row ids, prose) goes to bench_extras.json."""
+    configuration.  Everything else of `out` (per-kernel tables, power series, row ids, prose) goes to bench_extras.json, which the line
+    names when `extras` says that the run wrote it."""
     c = _pick(out, ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data"))
     cfg = out.get("config", {})
     c["config"] = {"workload": cfg.get("workload_short", cfg.get("workload")), "graph": "whole reference graph (every token row of every layer)",
@@ -137,7 +142,8 @@ def compact_line(out):
     for k in ("host_fed_images_per_s", "two_forwards_in_flight"):
         if isinstance(out.get(k), dict):
             c[k] = out[k].get("value", out[k].get("error"))
-    c["extras"] = os.path.basename(EXTRAS_FILE)
+    if extras:
+        c["extras"] = os.path.basename(EXTRAS_FILE)
     line = json.dumps(c, separators=(",", ":"))
     if len(line) > COMPACT_LIMIT:      # never let the line outgrow the driver's reader again: drop the optional summaries, largest first
         for k in ("kernels", "kernels_fields", "config1", "class_rows_last_layer", "sustained", "host_fed_images_per_s", "two_forwards_in_flight"):
@@ -416,14 +422,17 @@ def main():
     ap.add_argument("--model", default="vit_base_patch16_224")
     ap.add_argument("--batch", type=int, default=256, help="images per GPU per step")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16"])
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU oracle legs (cpu_baseline AND parity: the line is then stamped unverified)")
-    ap.add_argument("--cpu-images", type=int, default=48, help="rows of the batch checked against / timed through the CPU oracle (~10-15 s on the 128-thread GPU host)")
-    ap.add_argument("--no-profile", action="store_true", help="no per-kernel profiled step after the timed region (no roofline object)")
     ap.add_argument("--ftype", default="f16", choices=sorted(FTYPES), help="weight file type (BASELINE config 5: q4_0)")
-    ap.add_argument("--no-host-feed", action="store_true", help="skip the secondary u8-from-host measurement")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements after the timed region (parity mode, sustained run, PMC traffic, configs 3 and 5)")
-    ap.add_argument("--no-pmc", action="store_true", help="do not spawn the two rocprofv3 --pmc passes that measure roofline.traffic")
-    ap.add_argument("--sustain-s", type=float, default=10.0, help="length of the sustained run (seconds)")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run everything else the benchmark measures and checks: oracle parity gates and "
+                                                       "cpu_baseline, the profiled step (roofline), the host-fed rate and, N = 1 only, the secondary measurements; "
+                                                       "writes the full record to bench_extras.json")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle legs (cpu_baseline AND parity: the line is then stamped unverified)")
+    ap.add_argument("--cpu-images", type=int, default=48, help="--full: rows of the batch checked against / timed through the CPU oracle (~10-15 s on a 128-thread host)")
+    ap.add_argument("--no-profile", action="store_true", help="--full: no per-kernel profiled step after the timed region (no roofline object)")
+    ap.add_argument("--no-host-feed", action="store_true", help="--full: skip the secondary u8-from-host measurement")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the secondary measurements after the timed region (parity mode, sustained run, PMC traffic, configs 3 and 5)")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: do not spawn the two rocprofv3 --pmc passes that measure roofline.traffic")
+    ap.add_argument("--sustain-s", type=float, default=10.0, help="--full: length of the sustained run (seconds)")
     ap.add_argument("--allow-overrides", action="store_true", help="run although a VITX_* development override is set; the line is stamped invalid")
     ap.add_argument("--stub-engine", action="store_true", help="CPU plumbing test only (tests/test_cpu_dist.py): gloo instead of RCCL, a stand-in for the forward; "
                                                                 "exercises the rank / barrier / gather / JSON logic of an N-process run; the line is stamped invalid")
@@ -589,7 +598,7 @@ def main():
         pr = c.profile_read()
         c.profile_enable(False)
         return pr
-    prof = [] if (args.no_profile or stub) else profiled_step(ctx, B, imgs, torch.empty_like(probs))
+    prof = profiled_step(ctx, B, imgs, torch.empty_like(probs)) if (args.full and not args.no_profile and not stub) else []
     def bracket_of(c):
         try:
             return c.profile_bracket_us()
@@ -614,7 +623,7 @@ def main():
     # secondary, NOT the metric: the same step fed from host memory -- u8 images in pinned RAM -> H2D -> device-side
     # vit_image_preprocess (bicubic, here 224 -> 224) -> forward; PCIe-inclusive rate for DESIGN.md
     host_feed = None
-    if world == 1 and not args.no_host_feed and not stub:
+    if args.full and world == 1 and not args.no_host_feed and not stub:
         u8_pinned = u8.pin_memory()
         d_u8 = torch.empty_like(u8, device="cuda")
         imgs2 = torch.empty_like(imgs)
@@ -669,7 +678,7 @@ def main():
             out["invalid"] = f"development overrides in the environment: {overrides}"
         if stub:
             out["invalid"] = "stub engine (CPU plumbing test): not a measurement"
-        extras = world == 1 and not args.no_extras and not stub
+        extras = args.full and world == 1 and not args.no_extras and not stub
         # roofline of the dominant kernel: algorithmic flops / HIP-event time on the launch stream; HBM-side traffic by PMC, measured now
         if prof:
             traffic, traffic_src = (None, "not measured (--no-pmc / --no-extras / N > 1)")
@@ -702,7 +711,7 @@ def main():
 
         # ---- parity of the timed configuration + the CPU baseline (the oracle is the checker and the baseline, never the product)
         oracle_ctx = None
-        if world == 1 and not args.no_cpu_baseline and not stub:
+        if args.full and world == 1 and not args.no_cpu_baseline and not stub:
             import dataclasses
             from oracle import oracle as O
             om = O.OracleModel(path)
@@ -736,7 +745,7 @@ def main():
                 failed.append(f"timed configuration ({args.dtype}) outside its parity bound: {out['parity']['max_dprob_vs_ref']:.3e} > {bound:.3e} or a decided top-1 differs")
             oracle_ctx = (O, rows, cpu_imgs, ref_p, noise)
         elif not stub:
-            out["parity"] = {"unverified": "--no-cpu-baseline or N > 1: the oracle leg did not run"}
+            out["parity"] = {"unverified": "--no-cpu-baseline or N > 1: the oracle leg did not run" if args.full else "not checked: the oracle leg runs under --full"}
 
         # ---- secondary measurements, after the timed region and outside `value`
         if extras and args.model == "vit_base_patch16_224" and args.ftype == "f16":
@@ -902,8 +911,9 @@ def main():
             out["extras_wall_s"] = round(time.perf_counter() - extras_t0, 1)
         if failed:
             out["invalid"] = "parity gate failed: " + "; ".join(failed)
-        write_extras(out)
-        print(compact_line(out), flush=True)
+        if args.full:
+            write_extras(out)
+        print(compact_line(out, extras=args.full), flush=True)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

@@ -183,6 +183,8 @@ def test_bench_last_line_is_compact():
     assert c["parity"]["passed"] is True and c["parity"]["bound"] > c["parity"]["max_dprob_vs_ref"] > 0
     assert c["parity_mode"]["parity"]["passed"] is True and c["parity_mode"]["value"] == full["parity_mode"]["value"]
     assert len(c["other_configs"]) == 3 and all("value" in v and "frac" in v and v["parity"]["passed"] for v in c["other_configs"].values())
+    # the line names the full record only when the run wrote one (--full)
+    assert c["extras"] == "bench_extras.json" and "extras" not in json.loads(bench.compact_line(full, extras=False))
     # a record with absurdly many configurations still fits: the optional blocks go first
     fat = dict(full, other_configs={f"cfg{i}": v for i in range(6) for v in full["other_configs"].values()})
     assert len(bench.compact_line(fat).encode()) <= 8192

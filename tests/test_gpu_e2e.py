@@ -321,6 +321,34 @@ def test_bench_dump_outputs_are_the_timed_probabilities(pkg, binding, torch_gpu,
     assert np.abs(a - direct).max() <= 1e-3
 
 
+def test_bench_plain_run_is_lean_and_full_adds_the_checks():
+    """A plain bench.py run measures the headline only: no profiled step, no oracle leg, no full record written.  --full adds the
+    roofline, cpu_baseline and the parity gate on the timed probabilities, and names the full record it wrote."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    extras = os.path.join(root, "bench_extras.json")
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--model", "vit_tiny_patch16_224", "--batch", "16"]
+    before = os.stat(extras).st_mtime_ns if os.path.exists(extras) else None
+    r = subprocess.run(base, capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.splitlines()[-1])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["unit"] == "images/s" and d["dtype"] == "bf16"
+    assert abs(d["value"] - 16 / (d["ms_per_step"] * 1e-3)) <= 0.01 * d["value"]
+    for k in ("roofline", "cpu_baseline", "kernels", "probe_tflops", "host_fed_images_per_s", "extras"):
+        assert k not in d, k
+    assert "unverified" in d["parity"] and "passed" not in d["parity"]
+    assert (os.stat(extras).st_mtime_ns if os.path.exists(extras) else None) == before
+    r = subprocess.run(base + ["--full", "--no-pmc", "--no-host-feed", "--cpu-images", "8"], capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.splitlines()[-1])
+    assert d["steps"] == 2 and d["value"] > 0
+    assert d["roofline"]["kernel"].startswith("gemm_") and d["roofline"]["achieved"] > 0 and d["kernels"]
+    assert d["cpu_baseline"]["value"] > 0 and d["parity"]["passed"] is True and d["parity"]["rows"] > 0
+    assert d["extras"] == "bench_extras.json"
+    with open(extras) as f:
+        assert json.load(f)["value"] == d["value"]
+
+
 def test_cli_prints_topk_like_the_reference_and_walks_a_directory(pkg, binding, oracle, torch_gpu, tmp_path):
     """vit_cli.py (= main.cpp + the accuracy harness): stdout lines ' > label : 0.xx' (vit.cpp:1062-1067) for the bundled
     tench.jpg agree with the oracle's top-5; --dir mode scores <label>/<image> trees."""

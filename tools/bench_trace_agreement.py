@@ -1,5 +1,5 @@
 """Does the bench line agree with a kernel trace of THE SAME COMMAND?
-    cd /tmp && rocprofv3 --kernel-trace -d DIR -o b -- python bench.py --no-extras --no-cpu-baseline > line.json
+    cd /tmp && rocprofv3 --kernel-trace -d DIR -o b -- python bench.py --full --no-extras --no-cpu-baseline > line.json
     python tools/bench_trace_agreement.py DIR/.../b_results.db line.json
 bench.py times its steps on the production schedule (two sub-batches on two streams) and then runs ONE more forward with the context's profiling
 schedule (sub-batches back to back on one stream, every launch bracketed by HIP events): `roofline` and `kernel_breakdown` come from that forward.
