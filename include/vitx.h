@@ -41,7 +41,28 @@ enum vitx_status {
 /* Arithmetic type of the MFMA operands (accumulation, LayerNorm, softmax and the
  * residual stream are always f32).  F16 reproduces the reference's rounding points
  * (ggml rounds mul_mat activations to fp16); BF16 is the mode BASELINE.json names. */
-enum vitx_dtype { VITX_F16 = 0, VITX_BF16 = 1 };
+enum vitx_dtype { VITX_F16 = 0, VITX_BF16 = 1, VITX_MXFP8 = 2 };
+
+/* VITX_MXFP8 is EXPERIMENTAL: measured slower than VITX_BF16 on MI355X; VITX_BF16 stays the mode to use.
+ * VITX_MXFP8 (vitx_ctx_create, vitx_ctx_create_ex, vitx_group_create, vit_state.dtype; the vitx_op_* entry points above VITX_MXFP8
+ * take dtype 0 or 1 only -- MX has its own, below):
+ *   qkv, fc1 and fc2 of every layer (the class-row tail of the last layer included) multiply MX operands, A and W, on the block-scaled
+ *   MFMA.  Everything else is what a VITX_BF16 context computes: patch embedding, attention (on the bf16 q, k, v the qkv GEMM writes),
+ *   proj + residual (its A operand comes from the attention kernels), the LayerNorm statistics, final norm, head, softmax and the f32
+ *   residual stream.  LayerNorm fusion is off (vitx_ctx_ln_fusion_active returns 0): each LayerNorm is its own launch and writes MX.
+ *   Hidden sizes that are not a multiple of 32: VITX_ERR_UNSUPPORTED at context creation (every context already requires a multiple of 64).
+ * Block encoding: a block is 32 consecutive K elements of one row; elements are OCP e4m3fn (not fnuz); one E8M0 scale byte s per block;
+ * a block decodes to q_i * 2^(s - 127).  For a block x in f32:
+ *   a = max |x_i|; a == 0: s = 127 and every q_i = 0.  Otherwise a = m * 2^E with m in [1, 2), exact from the bits (f32 subnormals
+ *   included); e = E - 8 if m <= 1.75, else E - 7 -- the smallest e with a * 2^-e <= 448; e is clamped to at least -127; s = e + 127;
+ *   q_i = RNE_e4m3(x_i * 2^-e).  Nothing saturates or overflows; small values go to subnormals or zero by round-to-nearest-even.
+ *   This deliberately differs from the OCP MX rule e = floor(log2 a) - 8, which clips the block maximum (1.75 * 2^8 = 448 is the
+ *   largest e4m3 value, so blocks with m > 1.75 would saturate).
+ * Stored layout: elements [rows][K_pad] bytes, scales [rows][K_pad / 32] bytes, K_pad = K rounded up to 128 (the MFMA's K step);
+ * padding = zero elements with scale 127, written by the producers.
+ * Rounding points: norm1 and norm2 outputs are encoded from the f32 LayerNorm value (the value a VITX_BF16 context rounds to bf16); the
+ * fc1 output is encoded from f32 gelu_tanh(acc + bias) (ditto); the weights are encoded once at upload on the host from the file's f32
+ * decode (vitx_model_tensor_f32), whatever the file type; the qkv output is bf16 and fc2 adds into the f32 residual stream. */
 
 /* Interpolation of vit_image_preprocess (vit_hparams::interpolation, vit.h:30). */
 enum vitx_interp { VITX_BICUBIC = 0, VITX_BILINEAR = 1 };
@@ -221,7 +242,8 @@ typedef struct vitx_prof_entry {
     double busy_ms;       /* wall time during which >= 1 launch of this class was running (union over the
                              context's concurrent sub-batch streams); == total_ms on a single stream */
 } vitx_prof_entry;
-/* Matrix-pipe probe: back-to-back v_mfma_f32_16x16x32 (the instruction of the GEMM kernels) on register operands on every CU for ~target_ms (no LDS, no memory).
+/* Matrix-pipe probe: back-to-back v_mfma_f32_16x16x32 (the instruction of the GEMM kernels) on register operands on every CU for ~target_ms (no LDS, no memory);
+ * dtype VITX_MXFP8: v_mfma_scale_f32_16x16x128_f8f6f4 on e4m3 operands with unit scales (the ceiling of the MX GEMMs).
  * fill 0 = zero operands, 1 = constant, 2 = uniform random in [-1, 1).  Returns TFLOP/s and the shader clock the device actually ran
  * at.  MI355X is power-capped on random operands (bf16 ~1830 of the nominal 2517 TFLOP/s): the roofline bench.py reports carries
  * this measured ceiling next to the nominal peak. */
@@ -364,6 +386,23 @@ int vitx_attn_floats(const vitx_ctx *c);
 int vitx_attn_images(const vitx_ctx *c);
 int vitx_attn_read(vitx_ctx *c, float *out, size_t n_floats);
 int vitx_op_attention_map(int dtype, const void *d_qkv, long lo_off, void *d_cls, void *d_mean, int n_img, int N, int D, int H, void *stream);
+
+/* ---- MXFP8 operands (VITX_MXFP8, encoding above) ------------------------------- */
+/* Host encoder: x f32 [rows][K] -> q [rows][k_pad] e4m3 bytes + scales [rows][k_pad / 32] (k_pad >= K, a multiple of 32; columns
+ * K .. k_pad are zero elements, whole padding blocks get scale 127).  VITX_ERR_ARG on NULL or a bad size. */
+int vitx_mxfp8_quantize(const float *x, int rows, int K, int k_pad, uint8_t *q, uint8_t *scales);
+/* The device encoder on its own (device pointers, same arguments and bits as vitx_mxfp8_quantize; only enqueues). */
+int vitx_op_quantize_mxfp8(const void *d_x, int rows, int K, int k_pad, void *d_q, void *d_scales, void *stream);
+/* LayerNorm -> MX: d_x f32 [M][D] -> d_q [M][K_pad(D)] + d_scales [M][K_pad(D) / 32] of the f32 value vitx_op_layernorm rounds. */
+int vitx_op_layernorm_mxfp8(const void *d_x, const void *d_w, const void *d_b, void *d_q, void *d_scales, int M, int D, float eps, void *stream);
+/* C = A . W^T on MX operands (v_mfma_scale_f32_16x16x128_f8f6f4): d_a [M][K_pad] + d_a_scales [M][K_pad / 32]; d_w and d_w_scales hold
+ * N rounded up to 128 rows (zero blocks beyond N); d_bias N f32.  K_pad = K rounded up to 128.  Any M.
+ *   epi 0: out bf16 [M][N] = acc + bias                                            (qkv)
+ *   epi 1: out MX [M][K_pad(N)] + d_out_scales [M][K_pad(N) / 32] of gelu_tanh(acc + bias), columns N .. K_pad(N) zero   (fc1)
+ *   epi 2: out f32 [M][N] = (acc + bias) + out in place                            (fc2)
+ * VITX_ERR_ARG on NULL pointers (d_out_scales only for epi 1) or another epi. */
+int vitx_op_gemm_mxfp8(int epi, const void *d_a, const void *d_a_scales, const void *d_w, const void *d_w_scales, const void *d_bias, void *d_out,
+                       void *d_out_scales, int M, int N, int K, void *stream);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # VITX_LIB: development override (the -DVITX_LAB laboratory build, A/B builds).  bench.py marks its line invalid when it is set.
 LIB_PATH = os.environ.get("VITX_LIB") or os.path.join(_HERE, "libvitx.so")
 
-F16, BF16 = 0, 1
+F16, BF16, MXFP8 = 0, 1, 2      # MXFP8: qkv, fc1 and fc2 on block-scaled e4m3 operands (include/vitx.h VITX_MXFP8; mxfp8.py)
 LN_TEST_KEY = 0x7e570000        # vitx_ctx_options::ln_test is honoured only as LN_TEST_KEY | mode
 BICUBIC, BILINEAR = 0, 1
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_BIAS_F32, EPI_PATCH, EPI_BIAS_HILO = 0, 1, 2, 3, 4, 5
@@ -33,6 +33,7 @@ EXPORTS = [
     "vitx_op_dequant", "vitx_op_gemm_q4", "vitx_ctx_weight_bytes", "vitx_ctx_shares_weights", "vitx_probe_mfma", "vitx_op_gemm_ln", "vitx_ctx_ln_fallbacks", "vitx_ctx_stream_retries",
     "vitx_model_in_channels", "vitx_model_seq_len", "vitx_ctx_out_rows", "vitx_ctx_split", "vitx_ctx_ln_fusion_active", "vitx_op_attention_f32", "vitx_op_attention_planes", "vitx_op_attention_cls", "vitx_preprocess_vitstr_u8", "vitx_vitstr_decode",
     "vitx_attn_enable", "vitx_attn_floats", "vitx_attn_images", "vitx_attn_read", "vitx_op_attention_map", "vitx_ctx_graph_launches",
+    "vitx_mxfp8_quantize", "vitx_op_quantize_mxfp8", "vitx_op_layernorm_mxfp8", "vitx_op_gemm_mxfp8",
 ]
 
 
@@ -140,6 +141,11 @@ def lib():
             L.vitx_ctx_graph_launches.restype = C.c_longlong; L.vitx_ctx_graph_launches.argtypes = [vp]
             L.vitx_attn_read.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t]
             L.vitx_op_attention_map.argtypes = [ip, vp, C.c_long, vp, vp, ip, ip, ip, ip, vp]
+        if hasattr(L, "vitx_mxfp8_quantize"):
+            L.vitx_mxfp8_quantize.argtypes = [C.POINTER(C.c_float), ip, ip, ip, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]
+            L.vitx_op_quantize_mxfp8.argtypes = [vp, ip, ip, ip, vp, vp, vp]
+            L.vitx_op_layernorm_mxfp8.argtypes = [vp, vp, vp, vp, vp, ip, ip, C.c_float, vp]
+            L.vitx_op_gemm_mxfp8.argtypes = [ip, vp, vp, vp, vp, vp, vp, vp, ip, ip, ip, vp]
         _lib = L
     return _lib
 
@@ -466,6 +472,37 @@ def probe_mfma(device: int = 0, dtype: int = BF16, fill: int = 2, target_ms: flo
 def op_attention_map(dtype: int, d_qkv: int, d_cls: int, d_mean: int, n_img: int, N: int, D: int, H: int, lo_off: int = 0, stream: int = 0) -> None:
     """vitx_op_attention_map: class-token maps [n_img, H, N] and / or the head mean [n_img, N, N] (f32, device pointers; 0 = not wanted)."""
     check(lib().vitx_op_attention_map(dtype, d_qkv, lo_off, d_cls or None, d_mean or None, n_img, N, D, H, stream or None), "vitx_op_attention_map")
+
+
+def mx_k_pad(K: int) -> int:
+    """Row length of an MXFP8 operand: K rounded up to the 128-deep K step of the block-scaled MFMA."""
+    return (K + 127) // 128 * 128
+
+
+def mxfp8_quantize(x: np.ndarray, k_pad: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """Host encoder (vitx_mxfp8_quantize): f32 [rows, K] -> (e4m3 bytes [rows, k_pad] uint8, E8M0 scales [rows, k_pad / 32] uint8)."""
+    x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+    rows, K = x.shape
+    k_pad = mx_k_pad(K) if k_pad is None else k_pad
+    q = np.zeros((rows, k_pad), np.uint8); s = np.zeros((rows, max(k_pad // 32, 1)), np.uint8)
+    check(lib().vitx_mxfp8_quantize(x.ctypes.data_as(C.POINTER(C.c_float)), rows, K, k_pad, q.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                    s.ctypes.data_as(C.POINTER(C.c_uint8))), "vitx_mxfp8_quantize")
+    return q, s
+
+
+def op_quantize_mxfp8(d_x: int, rows: int, K: int, k_pad: int, d_q: int, d_scales: int, stream: int = 0) -> None:
+    """vitx_op_quantize_mxfp8: the device encoder on f32 [rows][K] (device pointers)."""
+    check(lib().vitx_op_quantize_mxfp8(d_x, rows, K, k_pad, d_q, d_scales, stream or None), "vitx_op_quantize_mxfp8")
+
+
+def op_layernorm_mxfp8(d_x: int, d_w: int, d_b: int, d_q: int, d_scales: int, M: int, D: int, eps: float = 1e-6, stream: int = 0) -> None:
+    """vitx_op_layernorm_mxfp8: LayerNorm of f32 [M][D] -> MX [M][mx_k_pad(D)] + scales (device pointers)."""
+    check(lib().vitx_op_layernorm_mxfp8(d_x, d_w, d_b, d_q, d_scales, M, D, eps, stream or None), "vitx_op_layernorm_mxfp8")
+
+
+def op_gemm_mxfp8(epi: int, d_a: int, d_as: int, d_w: int, d_ws: int, d_bias: int, d_out: int, d_out_scales: int, M: int, N: int, K: int, stream: int = 0) -> None:
+    """vitx_op_gemm_mxfp8: epi EPI_BIAS (bf16 out), EPI_BIAS_GELU (MX out + scales), EPI_BIAS_RESID (f32 out +=)."""
+    check(lib().vitx_op_gemm_mxfp8(epi, d_a, d_as, d_w, d_ws, d_bias, d_out, d_out_scales or None, M, N, K, stream or None), "vitx_op_gemm_mxfp8")
 
 
 def topk(probs_row: np.ndarray, k: int = 5):

@@ -1,7 +1,7 @@
 """Command-line front end equivalent to the reference's `vit` binary (/root/reference/main.cpp:25-112) and its
 directory-walk accuracy harness:
 
-    python vit_cli.py -m model.gguf -i image.jpg [-k 5] [--dtype f16|bf16] [--interp bicubic|bilinear]
+    python vit_cli.py -m model.gguf -i image.jpg [-k 5] [--dtype f16|bf16|mxfp8] [--interp bicubic|bilinear]
     python vit_cli.py -m model.gguf --dir imagenet_val/ [--batch 256]       # top-1 over <dir>/<label>/*.jpg
     python vit_cli.py -m model.gguf -i image.jpg --attn-map map.pgm [--attn-kind rollout|last]   # + where the model looked (P5 picture)
 
@@ -45,7 +45,9 @@ def main(argv: List[str] | None = None) -> int:
     ap.add_argument("-k", "--topk", type=int, default=5)
     ap.add_argument("-s", "--seed", type=int, default=-1, help="accepted for compatibility (unused by the forward, as in the reference)")
     ap.add_argument("-e", "--epsilon", type=float, default=1e-6, help="accepted for compatibility (the reference's forward uses hparams.eps = 1e-6)")
-    ap.add_argument("--dtype", default="f16", choices=["f16", "bf16"], help="MFMA operand type; f16 reproduces the reference's rounding points")
+    ap.add_argument("--dtype", default="f16", choices=["f16", "bf16", "mxfp8"],
+                    help="MFMA operand type; f16 reproduces the reference's rounding points; mxfp8 is EXPERIMENTAL (qkv, fc1, fc2 on block-scaled e4m3, "
+                         "the rest bf16): slower than bf16 on MI355X and less accurate (DESIGN.md section 4)")
     ap.add_argument("--interp", default="bicubic", choices=["bicubic", "bilinear"])
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--dir", default=None, help="accuracy harness: walk DIR/<label>/* and report top-1 against the directory name")
@@ -65,7 +67,7 @@ def main(argv: List[str] | None = None) -> int:
         print(f"main: failed to load model from '{a.model}': {e}", file=sys.stderr)
         return 1
     t_load = time.perf_counter() - t_main
-    dt = binding.F16 if a.dtype == "f16" else binding.BF16
+    dt = {"f16": binding.F16, "bf16": binding.BF16, "mxfp8": binding.MXFP8}[a.dtype]
     interp = binding.BICUBIC if a.interp == "bicubic" else binding.BILINEAR
     S = model.img_size
 

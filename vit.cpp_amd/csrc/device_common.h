@@ -192,9 +192,9 @@ __device__ __forceinline__ void ln_combine(const float (&mc)[LN_MAX_TILES], cons
 // One row of NT * 256 values by one wave, the tiled definition above: lane l holds piece l of each tile (w = l >> 4, j = (l >> 3) & 1,
 // k = l & 7): one fully coalesced 1 KiB load per tile.  Used by layernorm_kernel, layernorm_fixup_kernel (kernels.hip) and by the
 // prologue of a GEMM that consumes rows a LayerNorm-fusing GEMM left to the fix-up (gemm_pp.hip).
-template <typename T, int NT>
-__device__ __forceinline__ void ln_row_tiled(const float *__restrict__ xr, const float *__restrict__ w, const float *__restrict__ b, T *__restrict__ yr, float eps, int lane) {
-    f32x4 v[NT];
+// The row's values (v[c] = columns c * 256 + 4 lane ..) and their statistics, the tiled definition above.
+template <int NT>
+__device__ __forceinline__ void ln_tiled_stats(const float *__restrict__ xr, float eps, int lane, f32x4 (&v)[NT], float &mean, float &rstd) {
     float mc[LN_MAX_TILES] = {0.0f, 0.0f, 0.0f, 0.0f}, m2[LN_MAX_TILES] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
     for (int c = 0; c < NT; ++c) v[c] = *(const f32x4 *)(xr + c * 256 + lane * 4);
@@ -209,8 +209,13 @@ __device__ __forceinline__ void ln_row_tiled(const float *__restrict__ xr, const
         mc[c] = tile_total(ln_piece_sum(v[c])) * (1.0f / 256.0f);
         m2[c] = tile_total(ln_piece_sq(v[c], mc[c]));
     }
-    float mean, rstd;
     ln_combine(mc, m2, NT, NT * 256, eps, mean, rstd);
+}
+template <typename T, int NT>
+__device__ __forceinline__ void ln_row_tiled(const float *__restrict__ xr, const float *__restrict__ w, const float *__restrict__ b, T *__restrict__ yr, float eps, int lane) {
+    f32x4 v[NT];
+    float mean, rstd;
+    ln_tiled_stats<NT>(xr, eps, lane, v, mean, rstd);
 #pragma unroll
     for (int c = 0; c < NT; ++c) {
         const int idx = c * 256 + lane * 4;
@@ -221,6 +226,34 @@ __device__ __forceinline__ void ln_row_tiled(const float *__restrict__ xr, const
         const typename Pair<T>::v2 lo = round_pair<T>(o[0], o[1]), hi = round_pair<T>(o[2], o[3]);
         *(typename Elem<T>::v4 *)(yr + idx) = typename Elem<T>::v4{lo[0], lo[1], hi[0], hi[1]};
     }
+}
+
+// Hidden sizes the tiled definition does not cover (launch_layernorm): lane l holds VEC consecutive columns idx = (i * 64 + l) * VEC of
+// each of NV pieces; sum and sum of squared deviations over the whole wave.  Returns v[i][j] = x - mean and scale = 1 / sqrt(var + eps).
+template <int VEC, int NV>
+__device__ __forceinline__ void ln_flat_stats(const float *__restrict__ xr, float eps, int lane, float (&v)[NV][VEC], float &scale) {
+    constexpr int D = 64 * VEC * NV;
+    float sum = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int idx = (i * 64 + lane) * VEC;
+        if constexpr (VEC == 4) { const float4 t = *(const float4 *)(xr + idx); v[i][0] = t.x; v[i][1] = t.y; v[i][2] = t.z; v[i][3] = t.w; }
+        else if constexpr (VEC == 2) { const float2 t = *(const float2 *)(xr + idx); v[i][0] = t.x; v[i][1] = t.y; }
+        else v[i][0] = xr[idx];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) sum += v[i][j];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    const float mean = sum / (float)D;
+    float sum2 = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) { v[i][j] -= mean; sum2 += v[i][j] * v[i][j]; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum2 += __shfl_xor(sum2, o);
+    scale = 1.0f / sqrtf(sum2 / (float)D + eps);
 }
 
 // ------------------------------------------------------------------------------------------------

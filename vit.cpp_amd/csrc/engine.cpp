@@ -22,6 +22,7 @@
 
 #include "kernels.h"
 #include "model_file.h"
+#include "mxfp8.h"
 
 using namespace vitx;
 
@@ -48,10 +49,16 @@ struct QuantW {
     int type = 0, N = 0, K = 0, n_pad = 0;
 };
 enum { W_QKV = 0, W_PROJ, W_FC1, W_FC2, W_PER_LAYER };
+// A weight matrix of a VITX_MXFP8 context (mxfp8.h): elements [n_pad][k_pad] e4m3 and scales [n_pad][k_pad / 32], encoded on the host at upload
+struct MxW {
+    uint8_t *q = nullptr, *s = nullptr;
+    int N = 0, K = 0, n_pad = 0, k_pad = 0;
+};
 struct LayerW {
     float *ln1_w, *ln1_b, *ln2_w, *ln2_b, *qkv_b, *proj_b, *fc1_b, *fc2_b;
-    void *qkv_w, *proj_w, *fc1_w, *fc2_w;      // expanded operand-type matrices; nullptr where the blocks stay quantised (q[])
+    void *qkv_w, *proj_w, *fc1_w, *fc2_w;      // expanded operand-type matrices; nullptr where the blocks stay quantised (q[]) or are MX (mx[])
     QuantW q[W_PER_LAYER];
+    MxW mx[W_PER_LAYER];                       // VITX_MXFP8: qkv, fc1 and fc2 (proj stays bf16)
 };
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
@@ -61,7 +68,8 @@ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 struct vitx_ctx {
     const vitx_model *model = nullptr;
     vitx_hparams hp{};
-    int device = 0, dtype = VITX_F16, max_batch = 0;
+    int device = 0, dtype = VITX_F16, max_batch = 0;   // dtype: the type of every bf16 / f16 kernel (VITX_BF16 in an MXFP8 context)
+    bool mx = false;                     // VITX_MXFP8: qkv, fc1 and fc2 take MX operands (norm1, norm2 and the fc1 output are encoded)
     int D = 0, L = 0, H = 0, C = 0, P = 0, S = 0, g = 0, N = 0, Kpe = 0, Kpe_pad = 0, C_pad = 0;
     int Cin = 3;                         // input channels: 3 (RGB classifier) or 1 (ViTSTR, grey)
     int R = 1;                           // probability rows per image: 1 (cls token) or 25 (ViTSTR: tokens 0..24, vitstr.cpp:864-904)
@@ -141,6 +149,8 @@ struct vitx_ctx {
         void *Hbuf = nullptr;        // [Mpad][4D]  (also the im2col rows of the patch-embed GEMM)
         float *Xc = nullptr;         // [Bpad][D] f32 class-token rows of the residual stream through the last layer's tail (cls_tail)
         void *Z = nullptr;           // [Bpad][D] final-LN output of the cls rows
+        // VITX_MXFP8: norm1 and norm2 outputs [Mpad][k_pad(D)] + scales; the fc1 output [Mpad][4D] + scales lives in Hbuf
+        uint8_t *Umx = nullptr, *Umx_s = nullptr, *U2mx = nullptr, *U2mx_s = nullptr, *Hmx = nullptr, *Hmx_s = nullptr;
         void *Wq[W_PER_LAYER] = {nullptr, nullptr, nullptr, nullptr};   // just-in-time expansion of the current layer's quantised matrices
         void *Wq_head = nullptr;
         float *logits = nullptr;     // [Bpad][C_pad]
@@ -266,6 +276,22 @@ int upload_weight(vitx_ctx *c, const HostTensor *t, int Nrows, int K, int n_pad,
     return upload_matrix(c, t, Nrows, K, n_pad, K, dense);
 }
 
+// [N][K] matrix -> MX operand (VITX_MXFP8): the f32 decode of any file type, encoded once on the host; rows N..n_pad are zero blocks
+int upload_mx(vitx_ctx *c, const HostTensor *t, int Nrows, int K, int n_pad, MxW *w) {
+    w->N = Nrows; w->K = K; w->n_pad = n_pad; w->k_pad = mx_k_pad(K);
+    std::vector<float> f((size_t)n_pad * K, 0.0f);
+    t->decode_f32(f.data());
+    std::vector<uint8_t> q((size_t)n_pad * w->k_pad), sc((size_t)n_pad * (w->k_pad / kMxBlock));
+    mxfp8_encode_rows(f.data(), n_pad, K, w->k_pad, q.data(), sc.data());
+    int rc;
+    if ((rc = c->wmalloc((void **)&w->q, q.size()))) return rc;
+    if ((rc = c->wmalloc((void **)&w->s, sc.size()))) return rc;
+    HIP_TRY(hipMemcpy(w->q, q.data(), q.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(w->s, sc.data(), sc.size(), hipMemcpyHostToDevice));
+    c->wset->weight_bytes += q.size() + sc.size();
+    return VITX_OK;
+}
+
 // Quantised [N][K] matrix -> device, still in block form.  Returns VITX_OK with q->blocks == nullptr when the tensor is not a
 // block type (the caller then uploads the expanded matrix).
 int upload_quant(vitx_ctx *c, const HostTensor *t, int Nrows, int K, int n_pad, QuantW *q) {
@@ -335,6 +361,18 @@ int gemm(vitx_ctx *c, hipStream_t st, int pc, int epi, GemmArgs a, const QuantW 
     return VITX_OK;
 }
 
+// One MXFP8 GEMM (gemm_mx8.hip) on rows A / As of `rows` rows; the profile counts operand bytes as 1 per element + 1 per 32 (scales)
+int gemm_mx(vitx_ctx *c, hipStream_t st, int pc, int epi, const uint8_t *A, const uint8_t *As, const MxW &w, const float *bias, void *out, uint8_t *out_s,
+            int rows, int ldo) {
+    const GemmArgs a = dense_gemm(A, w.q, bias, out, rows, rows, w.N, w.n_pad, w.k_pad, ldo);
+    constexpr double mxb = 1.0 + 1.0 / kMxBlock;
+    double bytes = (double)rows * w.k_pad * mxb + (double)w.n_pad * w.k_pad * mxb + (epi == EPI_BIAS_GELU ? (double)rows * ldo * mxb : (double)rows * w.N * epi_out_bytes(epi));
+    if (epi == EPI_BIAS_RESID) bytes += (double)rows * w.N * 4;
+    ProfScope ps(c, st, pc, 2.0 * rows * (double)w.N * w.K, bytes);
+    HIP_TRY(launch_gemm_mx8(epi, a, As, w.s, out_s, st));
+    return VITX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -342,7 +380,7 @@ extern "C" {
 int vitx_ctx_create(const vitx_model *m, int device, int max_batch, int dtype, vitx_ctx **out) { return vitx_ctx_create_ex(m, device, max_batch, dtype, nullptr, out); }
 
 int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype, const vitx_ctx_options *opt_in, vitx_ctx **out) {
-    if (!m || !out || max_batch <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_ctx_create: invalid argument"); return VITX_ERR_ARG; }
+    if (!m || !out || max_batch <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16 && dtype != VITX_MXFP8)) { set_error("vitx_ctx_create: invalid argument"); return VITX_ERR_ARG; }
     *out = nullptr;
     vitx_ctx_options opt{};                   // all zero = every default
     if (opt_in) {
@@ -356,10 +394,13 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
     const vitx_hparams &hp = m->hp;
     if (hp.num_attention_heads <= 0 || hp.hidden_size % hp.num_attention_heads) { set_error("vitx_ctx_create: hidden_size %d is not a multiple of %d heads", hp.hidden_size, hp.num_attention_heads); return VITX_ERR_UNSUPPORTED; }
     if (hp.hidden_size % 64) { set_error("vitx_ctx_create: hidden_size must be a multiple of 64"); return VITX_ERR_UNSUPPORTED; }
+    // (VITX_MXFP8 needs whole 32-element blocks per row: the multiple of 64 above already guarantees it, so no check of its own)
+    static_assert(64 % kMxBlock == 0, "the hidden-size rule above must cover the MX block");
     HIP_TRY(hipSetDevice(device));
     std::unique_ptr<vitx_ctx> c(new (std::nothrow) vitx_ctx());
     if (!c) return VITX_ERR_NOMEM;
-    c->model = m; c->hp = hp; c->device = device; c->dtype = dtype; c->max_batch = max_batch;
+    c->model = m; c->hp = hp; c->device = device; c->max_batch = max_batch;
+    c->mx = dtype == VITX_MXFP8; c->dtype = c->mx ? VITX_BF16 : dtype;      // everything but the MX GEMMs runs as in a VITX_BF16 context
     c->D = hp.hidden_size; c->L = hp.num_hidden_layers; c->H = hp.num_attention_heads; c->C = hp.num_classes; c->P = hp.patch_size; c->S = hp.img_size;
     c->Cin = m->in_chans; c->R = m->in_chans == 1 ? VITX_VITSTR_SEQ_LEN : 1;
     c->g = c->S / c->P; c->N = c->g * c->g + 1; c->Kpe = c->Cin * c->P * c->P; c->Kpe_pad = round_up(c->Kpe, 64);
@@ -387,7 +428,8 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
         if (c->ln_test & ~7) { set_error("vitx_ctx_create_ex: ln_test mode %d has bits outside 1 | 2 | 4", c->ln_test); return VITX_ERR_ARG; }
         if ((c->ln_test & 3) == 3) c->ln_timeout = 5000;       // real time-outs in the test: 50 us (with or without bit 4; the kernel tests the bits one by one too)
     }
-    c->ln_fuse = !opt.no_ln_fusion && !opt.graph;        // a captured launch would replay its epoch tag: no fusion under the graph cache
+    // a captured launch would replay its epoch tag: no fusion under the graph cache; MX: every LayerNorm is its own launch (it writes MX)
+    c->ln_fuse = !opt.no_ln_fusion && !opt.graph && !c->mx;
 #ifdef VITX_LAB
     if (const char *e = getenv("VITX_SKIP")) c->skip = atoi(e);
 #endif
@@ -424,10 +466,17 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
             if ((rc = upload_f32(c.get(), T(p + "attn.proj.bias"), &w.proj_b, round_up(D, tn)))) return rc;
             if ((rc = upload_f32(c.get(), T(p + "mlp.fc1.bias"), &w.fc1_b, round_up(4 * D, tn)))) return rc;
             if ((rc = upload_f32(c.get(), T(p + "mlp.fc2.bias"), &w.fc2_b, round_up(D, tn)))) return rc;
-            if ((rc = upload_weight(c.get(), T(p + "attn.qkv.weight"), 3 * D, D, round_up(3 * D, tn), &w.qkv_w, &w.q[W_QKV]))) return rc;
+            w.qkv_w = w.fc1_w = w.fc2_w = nullptr;
+            if (c->mx) {
+                if ((rc = upload_mx(c.get(), T(p + "attn.qkv.weight"), 3 * D, D, round_up(3 * D, 128), &w.mx[W_QKV]))) return rc;
+                if ((rc = upload_mx(c.get(), T(p + "mlp.fc1.weight"), 4 * D, D, round_up(4 * D, 128), &w.mx[W_FC1]))) return rc;
+                if ((rc = upload_mx(c.get(), T(p + "mlp.fc2.weight"), D, 4 * D, round_up(D, 128), &w.mx[W_FC2]))) return rc;
+            } else {
+                if ((rc = upload_weight(c.get(), T(p + "attn.qkv.weight"), 3 * D, D, round_up(3 * D, tn), &w.qkv_w, &w.q[W_QKV]))) return rc;
+                if ((rc = upload_weight(c.get(), T(p + "mlp.fc1.weight"), 4 * D, D, round_up(4 * D, tn), &w.fc1_w, &w.q[W_FC1]))) return rc;
+                if ((rc = upload_weight(c.get(), T(p + "mlp.fc2.weight"), D, 4 * D, round_up(D, tn), &w.fc2_w, &w.q[W_FC2]))) return rc;
+            }
             if ((rc = upload_weight(c.get(), T(p + "attn.proj.weight"), D, D, round_up(D, tn), &w.proj_w, &w.q[W_PROJ]))) return rc;
-            if ((rc = upload_weight(c.get(), T(p + "mlp.fc1.weight"), 4 * D, D, round_up(4 * D, tn), &w.fc1_w, &w.q[W_FC1]))) return rc;
-            if ((rc = upload_weight(c.get(), T(p + "mlp.fc2.weight"), D, 4 * D, round_up(D, tn), &w.fc2_w, &w.q[W_FC2]))) return rc;
         }
         if ((rc = upload_f32(c.get(), T("norm.weight"), &ws.norm_w))) return rc;
         if ((rc = upload_f32(c.get(), T("norm.bias"), &ws.norm_b))) return rc;
@@ -472,6 +521,13 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
         sl.qkv_lo_off = c->prec_attn ? (long)(Mpad * 3 * D) : 0;       // capacity; a forward places the lo plane right behind ITS rows (forward_slice)
         if ((rc = c->dmalloc(&sl.Hbuf, Mpad * hcols * 2, true))) return rc;
         if ((rc = c->dmalloc(&sl.Z, Bpad * D * 2, true))) return rc;
+        if (c->mx) {
+            const size_t kp = (size_t)mx_k_pad(D), kh = (size_t)mx_k_pad(4 * D);
+            if ((rc = c->dmalloc((void **)&sl.Umx, Mpad * kp * 33 / 32, true))) return rc;
+            if ((rc = c->dmalloc((void **)&sl.U2mx, Mpad * kp * 33 / 32, true))) return rc;
+            sl.Umx_s = sl.Umx + Mpad * kp; sl.U2mx_s = sl.U2mx + Mpad * kp;
+            sl.Hmx = (uint8_t *)sl.Hbuf; sl.Hmx_s = sl.Hmx + Mpad * kh;             // Mpad * kh * 33 / 32 <= Mpad * 4 D * 2 bytes of Hbuf
+        }
         if (c->cls_tail && (rc = c->dmalloc((void **)&sl.Xc, Bpad * D * 4, true))) return rc;
         if ((rc = c->dmalloc((void **)&sl.logits, Bpad * c->C_pad * 4, true))) return rc;
         // expansion scratch for quantised matrices: one buffer per matrix kind, shared by all layers (the largest layer decides)
@@ -617,6 +673,14 @@ static int forward_slice(vitx_ctx *c, vitx_ctx::Slice &sl, hipStream_t st, const
         HIP_TRY(launch_layernorm(dt, x, ldx, lw, lb, y, D, rows, D, c->hp.eps, st, group, gstride));
         return VITX_OK;
     };
+    // VITX_MXFP8: a LayerNorm whose output is the A operand of an MX GEMM (norm1, norm2) writes MX elements + scales
+    const int Dk = mx_k_pad(D);
+    auto layernorm_mx = [&](const float *x, const float *lw, const float *lb, uint8_t *q, uint8_t *s, int rows) -> int {
+        if (skip & 2) return VITX_OK;
+        ProfScope ps(c, st, PC_LAYERNORM, 0, (double)rows * D * 4 + (double)rows * Dk * (1.0 + 1.0 / kMxBlock));
+        HIP_TRY(launch_layernorm_mx8(x, D, lw, lb, q, s, Dk, rows, D, c->hp.eps, st));
+        return VITX_OK;
+    };
     // LayerNorm fusion: decided per forward (the GEMM shape of this sub-batch must take the wide persistent kernel; never while the caller is
     // capturing a graph -- the epoch tag of a captured launch would be replayed).  The padded rows M_real .. M of X are then computed and
     // stored as well (GemmLn): they belong to this slice's scratch, start as zeros and stay finite.
@@ -671,10 +735,15 @@ static int forward_slice(vitx_ctx *c, vitx_ctx::Slice &sl, hipStream_t st, const
             if (any && (rc = expand(todo, sl.Wq, W_PER_LAYER))) return rc;
         }
         // norm1 of the first layer (vit.cpp:808-812); every later norm1 comes out of the previous layer's fc2
-        if (il == 0 && !(skip & 2) && (rc = layernorm(sl.X, D, w.ln1_w, w.ln1_b, sl.U, M_real))) return rc;
-        // qkv projection (vit.cpp:820-821); `fix_u`: row blocks of U the previous layer's fc2 left to the fix-up are normalised in its prologue
-        if ((rc = gemm(c, st, PC_GEMM_QKV, c->prec_attn ? EPI_BIAS_HILO : EPI_BIAS, dense_gemm(sl.U, Wl[W_QKV], w.qkv_b, sl.QKV, M, M_real, 3 * D, round_up(3 * D, tn), D),
-                       Fl[W_QKV], nullptr, fix_u.todo ? &fix_u : nullptr, lo_off))) return rc;
+        if (c->mx) {
+            if (il == 0 && (rc = layernorm_mx(sl.X, w.ln1_w, w.ln1_b, sl.Umx, sl.Umx_s, M_real))) return rc;
+            if ((rc = gemm_mx(c, st, PC_GEMM_QKV, EPI_BIAS, sl.Umx, sl.Umx_s, w.mx[W_QKV], w.qkv_b, sl.QKV, nullptr, M_real, 3 * D))) return rc;
+        } else {
+            if (il == 0 && !(skip & 2) && (rc = layernorm(sl.X, D, w.ln1_w, w.ln1_b, sl.U, M_real))) return rc;
+            // qkv projection (vit.cpp:820-821); `fix_u`: row blocks of U the previous layer's fc2 left to the fix-up are normalised in its prologue
+            if ((rc = gemm(c, st, PC_GEMM_QKV, c->prec_attn ? EPI_BIAS_HILO : EPI_BIAS, dense_gemm(sl.U, Wl[W_QKV], w.qkv_b, sl.QKV, M, M_real, 3 * D, round_up(3 * D, tn), D),
+                           Fl[W_QKV], nullptr, fix_u.todo ? &fix_u : nullptr, lo_off))) return rc;
+        }
         if (c->attn_on() && (rc = attention_maps(c, st, sl.QKV, lo_off, il, first_img, n))) return rc;
         if (tail_now) {   // attention of token 0 (vit.cpp:848-858 for the one row vit.cpp:910-911 keeps) -> compact rows U[b]; class rows of X -> Xc[b]
             ProfScope ps(c, st, PC_ATTENTION_CLS, 4.0 * n * c->H * (double)N * (D / c->H), (double)M_real * 2 * D * eb * (c->prec_attn ? 2 : 1) + (double)n * D * (eb + 8));
@@ -686,12 +755,21 @@ static int forward_slice(vitx_ctx *c, vitx_ctx::Slice &sl, hipStream_t st, const
                 else HIP_TRY(launch_attention(*c->tune, dt, sl.QKV, sl.U, n, N, D, c->H, st));
             }
         }
+        const LayerW *nx = il + 1 < c->L ? &ws.layers[il + 1] : nullptr;
+        if (c->mx) {      // proj in bf16, norm2 -> MX, fc1 -> MX (GELU epilogue), fc2 into X, the next norm1 -> MX
+            if ((rc = gemm(c, st, r.pc_proj, EPI_BIAS_RESID, dense_gemm(sl.U, Wl[W_PROJ], w.proj_b, r.X, r.M, r.M_real, D, round_up(D, tn), D), Fl[W_PROJ]))) return rc;
+            if ((rc = layernorm_mx(r.X, w.ln2_w, w.ln2_b, sl.U2mx, sl.U2mx_s, r.M_real))) return rc;
+            if ((rc = gemm_mx(c, st, r.pc_fc1, EPI_BIAS_GELU, sl.U2mx, sl.U2mx_s, w.mx[W_FC1], w.fc1_b, sl.Hmx, sl.Hmx_s, r.M_real, mx_k_pad(4 * D)))) return rc;
+            if ((rc = gemm_mx(c, st, r.pc_fc2, EPI_BIAS_RESID, sl.Hmx, sl.Hmx_s, w.mx[W_FC2], w.fc2_b, r.X, nullptr, r.M_real, D))) return rc;
+            if (nx && (rc = layernorm_mx(r.X, nx->ln1_w, nx->ln1_b, sl.Umx, sl.Umx_s, r.M_real))) return rc;
+            if (!c->trace_ids.empty() && (rc = trace(il + 1))) return rc;
+            continue;
+        }
         // output projection + residual (vit.cpp:868-873), then norm2 (vit.cpp:881-885) -> U2
         if ((rc = resid_gemm_ln(r, r.pc_proj, sl.U, Wl[W_PROJ], w.proj_b, D, Fl[W_PROJ], w.ln2_w, w.ln2_b, sl.U2, &fix_u2))) return rc;
         // MLP (vit.cpp:889-900), then the NEXT layer's norm1 (vit.cpp:808-812) -> U; the last layer is followed by the final norm instead
         if ((rc = gemm(c, st, r.pc_fc1, EPI_BIAS_GELU, dense_gemm(sl.U2, Wl[W_FC1], w.fc1_b, sl.Hbuf, r.M, r.M_real, 4 * D, round_up(4 * D, tn), D), Fl[W_FC1], nullptr,
                        fix_u2.todo ? &fix_u2 : nullptr))) return rc;
-        const LayerW *nx = il + 1 < c->L ? &ws.layers[il + 1] : nullptr;
         if ((rc = resid_gemm_ln(r, r.pc_fc2, sl.Hbuf, Wl[W_FC2], w.fc2_b, 4 * D, Fl[W_FC2], nx ? nx->ln1_w : nullptr, nx ? nx->ln1_b : nullptr, sl.U, &fix_u))) return rc;
         if (!c->trace_ids.empty() && (rc = trace(il + 1))) return rc;
     }
@@ -1123,6 +1201,32 @@ int vitx_op_gemm_q4(int dtype, int epi, const void *a, const void *qs, const voi
     return VITX_OK;
 }
 size_t vitx_ctx_weight_bytes(const vitx_ctx *c) { return c ? c->wset->weight_bytes : 0; }
+// ---- MXFP8 single-kernel entry points (include/vitx.h) ----
+int vitx_op_quantize_mxfp8(const void *x, int rows, int K, int k_pad, void *q, void *scales, void *stream) {
+    if (!x || !q || !scales || rows <= 0 || K <= 0 || k_pad < K || k_pad % kMxBlock) { set_error("vitx_op_quantize_mxfp8: invalid argument"); return VITX_ERR_ARG; }
+    const hipError_t e = launch_quantize_mx8((const float *)x, rows, K, k_pad, (uint8_t *)q, (uint8_t *)scales, (hipStream_t)stream);
+    if (e != hipSuccess) { set_error("vitx_op_quantize_mxfp8: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
+    return VITX_OK;
+}
+int vitx_op_layernorm_mxfp8(const void *x, const void *w, const void *b, void *q, void *scales, int M, int D, float eps, void *stream) {
+    if (!x || !w || !b || !q || !scales || M <= 0 || D <= 0) { set_error("vitx_op_layernorm_mxfp8: invalid argument"); return VITX_ERR_ARG; }
+    if (D % kMxBlock || !layernorm_supports(D)) { set_error("vitx_op_layernorm_mxfp8: hidden size %d has no MX LayerNorm instantiation", D); return VITX_ERR_UNSUPPORTED; }
+    const hipError_t e = launch_layernorm_mx8((const float *)x, D, (const float *)w, (const float *)b, (uint8_t *)q, (uint8_t *)scales, mx_k_pad(D), M, D, eps, (hipStream_t)stream);
+    if (e != hipSuccess) { set_error("vitx_op_layernorm_mxfp8: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
+    return VITX_OK;
+}
+int vitx_op_gemm_mxfp8(int epi, const void *a, const void *a_scales, const void *w, const void *w_scales, const void *bias, void *out, void *out_scales,
+                       int M, int N, int K, void *stream) {
+    if (!a || !a_scales || !w || !w_scales || !bias || !out || M <= 0 || N <= 0 || K <= 0 || (epi != EPI_BIAS && epi != EPI_BIAS_GELU && epi != EPI_BIAS_RESID) ||
+        (epi == EPI_BIAS_GELU && !out_scales)) { set_error("vitx_op_gemm_mxfp8: invalid argument"); return VITX_ERR_ARG; }
+    if (!tuning_for_device(-1)) { set_error("vitx_op_gemm_mxfp8: kernel bring-up failed"); return VITX_ERR_HIP; }
+    const GemmArgs g = dense_gemm(a, w, (const float *)bias, out, M, M, N, round_up(N, 128), mx_k_pad(K), epi == EPI_BIAS_GELU ? mx_k_pad(N) : N);
+    const hipError_t e = launch_gemm_mx8(epi, g, (const uint8_t *)a_scales, (const uint8_t *)w_scales, (uint8_t *)out_scales, (hipStream_t)stream);
+    if (e == hipErrorInvalidValue) { set_error("vitx_op_gemm_mxfp8: the kernel cannot tile M %d N %d K %d", M, N, K); return VITX_ERR_UNSUPPORTED; }
+    if (e != hipSuccess) { set_error("vitx_op_gemm_mxfp8: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
+    return VITX_OK;
+}
+
 int vitx_ctx_shares_weights(const vitx_ctx *c) { return c && c->weights_shared ? 1 : 0; }
 int vitx_ctx_stream_retries(const vitx_ctx *c) { return c ? c->stream_retries : -1; }
 long long vitx_ctx_graph_launches(const vitx_ctx *c) { return c ? c->graph_launches : -1; }

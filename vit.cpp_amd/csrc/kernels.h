@@ -162,6 +162,11 @@ hipError_t launch_rollout_row(const float *cls, long cls_stride, const float *r,
 bool attention_supports(int N, int D, int H);     // any token count; head_dim 64 (tuned kernels) or any other multiple of 8 up to 128 (generic kernel)
 bool attention_single_pass_supports(int N);       // instantiation table of the register-resident kernel
 bool layernorm_supports(int D);
+// The LayerNorm instantiation table (hidden size D, columns per lane VEC, pieces NV; D = 64 VEC NV), ONE list for layernorm_supports, launch_layernorm
+// and launch_layernorm_mx8: widths of the timm ViTs (SO400M 1152, ViT-g 1408, ViT-G 1664, ...) and of small test models
+#define VITX_LN_WIDTHS(X)                                                                                                  \
+    X(64, 1, 1) X(128, 2, 1) X(192, 1, 3) X(256, 4, 1) X(384, 2, 3) X(512, 4, 2) X(768, 4, 3) X(1024, 4, 4) X(1280, 4, 5) X(1536, 4, 6) \
+    X(320, 1, 5) X(448, 1, 7) X(576, 1, 9) X(640, 2, 5) X(896, 2, 7) X(1152, 2, 9) X(1408, 2, 11) X(1664, 2, 13) X(2048, 4, 8)
 // class softmax with the reference's fp16 (or bf16) exp rounding (vit.cpp:931)
 hipError_t launch_softmax(int dtype, const float *logits, float *probs, int rows, int cols, int ld, hipStream_t stream);
 hipError_t launch_preprocess(const void *u8, float *out, int n, int nx, int ny, int S, int bicubic, hipStream_t stream);
@@ -173,6 +178,19 @@ hipError_t launch_spin(int microseconds, hipStream_t stream);
 // the same, writing its first and last wall-clock reading (100 MHz ticks) to stamps[0..1] (device memory)
 hipError_t launch_spin_stamp(int microseconds, long long *stamps, hipStream_t stream);
 
+
+// ---- MXFP8 operands (gemm_mx8.hip; include/vitx.h VITX_MXFP8, the encoding: mxfp8.h) ---------------------------------
+// C = A . W^T on v_mfma_scale_f32_16x16x128_f8f6f4.  a.A = elements [M_real][K], a.W = [N_pad][K] (K = K_pad, a multiple of 128;
+// N_pad a multiple of 128), scales [rows][K / 32] beside them.  EPI_BIAS -> bf16 [M][ldo]; EPI_BIAS_RESID -> f32 [M][ldo] += ;
+// EPI_BIAS_GELU -> MX elements a.out [M][ldo] (ldo = the next GEMM's K_pad) + out_scales [M][ldo / 32] of gelu_tanh(acc + bias).
+hipError_t launch_gemm_mx8(int epi, const GemmArgs &a, const uint8_t *a_scales, const uint8_t *w_scales, uint8_t *out_scales, hipStream_t stream);
+bool gemm_mx8_supports(const GemmArgs &a);
+// LayerNorm -> MX: the f32 value launch_layernorm rounds, encoded; rows [M][k_pad] + [M][k_pad / 32], columns D .. k_pad zero (scale 127)
+hipError_t launch_layernorm_mx8(const float *x, long ldx, const float *w, const float *b, uint8_t *q, uint8_t *s, int k_pad, int M, int D, float eps, hipStream_t stream);
+// x f32 [rows][K] -> MX [rows][k_pad] (test entry point of the device encoder)
+hipError_t launch_quantize_mx8(const float *x, int rows, int K, int k_pad, uint8_t *q, uint8_t *s, hipStream_t stream);
+// host encoder (mxfp8.cpp): the same rule, bit for bit
+void mxfp8_encode_rows(const float *x, int rows, int K, int k_pad, uint8_t *q, uint8_t *scales);
 
 // internal: kernel families.  `prepare` = only set the dynamic-LDS attribute of the instantiation (device bring-up).
 hipError_t launch_gemm_ring(const Tuning &t, int dtype, int epi, const GemmArgs &a, int cfg, hipStream_t stream, bool prepare = false);

@@ -276,7 +276,6 @@ hipError_t launch_gemm_q4(int dtype, int epi, const GemmArgs &a, hipStream_t str
 template <typename T, int VEC, int NV>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float *__restrict__ x, long ldx, const float *__restrict__ w, const float *__restrict__ b,
                                                         T *__restrict__ y, long ldy, int M, float eps, int group, long gstride) {
-    constexpr int D = 64 * VEC * NV;
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= M) return;
@@ -286,27 +285,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float *__restrict_
     T *yr = y + (size_t)row * ldy;
     if constexpr (VEC == 4 && NV <= LN_MAX_TILES) { ln_row_tiled<T, NV>(xr, w, b, yr, eps, lane); return; }
     float v[NV][VEC];
-    float sum = 0.0f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int idx = (i * 64 + lane) * VEC;
-        if constexpr (VEC == 4) { const float4 t = *(const float4 *)(xr + idx); v[i][0] = t.x; v[i][1] = t.y; v[i][2] = t.z; v[i][3] = t.w; }
-        else if constexpr (VEC == 2) { const float2 t = *(const float2 *)(xr + idx); v[i][0] = t.x; v[i][1] = t.y; }
-        else v[i][0] = xr[idx];
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) sum += v[i][j];
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-    const float mean = sum / (float)D;
-    float sum2 = 0.0f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) { v[i][j] -= mean; sum2 += v[i][j] * v[i][j]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum2 += __shfl_xor(sum2, o);
-    const float scale = 1.0f / sqrtf(sum2 / (float)D + eps);
+    float scale;
+    ln_flat_stats<VEC, NV>(xr, eps, lane, v, scale);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         const int idx = (i * 64 + lane) * VEC;
@@ -362,18 +342,16 @@ static hipError_t launch_layernorm_t(const float *x, long ldx, const float *w, c
 #define VITX_LN_CASE(DD, VEC, NV) \
     case DD: hipLaunchKernelGGL((layernorm_kernel<T, VEC, NV>), grid, blk, 0, stream, x, ldx, w, b, (T *)y, ldy, M, eps, group, gstride); break;
     switch (D) {
-        VITX_LN_CASE(64, 1, 1) VITX_LN_CASE(128, 2, 1) VITX_LN_CASE(192, 1, 3) VITX_LN_CASE(256, 4, 1) VITX_LN_CASE(384, 2, 3)
-        VITX_LN_CASE(512, 4, 2) VITX_LN_CASE(768, 4, 3) VITX_LN_CASE(1024, 4, 4) VITX_LN_CASE(1280, 4, 5) VITX_LN_CASE(1536, 4, 6)
-        // widths of other timm ViTs (SO400M 1152, ViT-g 1408, ViT-G 1664, ...) and of small test models
-        VITX_LN_CASE(320, 1, 5) VITX_LN_CASE(448, 1, 7) VITX_LN_CASE(576, 1, 9) VITX_LN_CASE(640, 2, 5) VITX_LN_CASE(896, 2, 7)
-        VITX_LN_CASE(1152, 2, 9) VITX_LN_CASE(1408, 2, 11) VITX_LN_CASE(1664, 2, 13) VITX_LN_CASE(2048, 4, 8)
+        VITX_LN_WIDTHS(VITX_LN_CASE)
     default: return hipErrorInvalidValue;
     }
 #undef VITX_LN_CASE
     return hipGetLastError();
 }
 bool layernorm_supports(int D) {
-    switch (D) { case 64: case 128: case 192: case 256: case 320: case 384: case 448: case 512: case 576: case 640: case 768: case 896: case 1024: case 1152: case 1280: case 1408: case 1536: case 1664: case 2048: return true; default: return false; }
+#define VITX_LN_SUPPORTED(DD, VEC, NV) case DD:
+    switch (D) { VITX_LN_WIDTHS(VITX_LN_SUPPORTED) return true; default: return false; }
+#undef VITX_LN_SUPPORTED
 }
 hipError_t launch_layernorm(int dtype, const float *x, long ldx, const float *w, const float *b, void *y, long ldy, int M, int D, float eps, hipStream_t stream, int group, long gstride) {
     if (group < 1) return hipErrorInvalidValue;

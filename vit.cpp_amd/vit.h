@@ -56,7 +56,7 @@ struct vit_state {                        // vit.h:72-80: per-caller mutable scr
                                           // not the pointer: `vit_model m; vit_model_load(f, m);` in a loop usually re-allocates the same address
     int device = 0;
     int max_batch = 1;                    // capacity of ctx; grown on demand by vit_predict_batch
-    int dtype = VITX_F16;                 // MFMA operand type (VITX_F16 reproduces the reference's rounding)
+    int dtype = VITX_F16;                 // MFMA operand type (VITX_F16 reproduces the reference's rounding); VITX_MXFP8: experimental, slower than bf16
     std::vector<float> prediction;        // class probabilities of the last call ([n][num_classes])
     vit_state() = default;
     vit_state(const vit_state &) = delete;
