@@ -387,6 +387,59 @@ int vitx_attn_images(const vitx_ctx *c);
 int vitx_attn_read(vitx_ctx *c, float *out, size_t n_floats);
 int vitx_op_attention_map(int dtype, const void *d_qkv, long lo_off, void *d_cls, void *d_mean, int n_img, int N, int D, int H, void *stream);
 
+/* ---- image embeddings and token features (what retrieval, probes and dense heads read) --------- */
+/* Opt-in outputs of the forward, for classifier contexts of every operand type (the residual stream is f32 in all of them).
+ * For one image, a selected layer l, N tokens, hidden size D:
+ *   X_l = the f32 residual stream after encoder layer l -- the tensor vitx_trace_read returns as stage l + 1 (vit.cpp:900);
+ *   F_l = ((X_l - mean) * rstd) * norm.weight + norm.bias per row, in f32, with the model's FINAL norm (vit.cpp:915-919), eps inside the
+ *         square root, the engine's own statistics (by 256-column tiles for D in {256, 512, 768, 1024}, over the whole row otherwise) and
+ *         the operation order of its LayerNorm kernels.  F_l is NOT rounded to the operand type.
+ *   For l = L - 1, row 0 of F_l is exactly the value the forward rounds (to nearest even) into the operand of the head GEMM: the embedding
+ *   is what the classifier saw.  For l < L - 1 it is the "intermediate layer, norm applied" convention (DINO get_intermediate_layers(norm=True)).
+ * Outputs (flags of vitx_feat_enable):
+ *   VITX_FEAT_CLS     F_l[0], [D];
+ *   VITX_FEAT_MEAN    (sum over t = 1 .. N-1 of F_l[t]) / (N - 1), [D]: global average pooling over the patch tokens, class token excluded;
+ *   VITX_FEAT_TOKENS  F_l[1 .. N-1], [N-1][D], patches in raster order;
+ *   VITX_FEAT_L2      modifier: the CLS and MEAN vectors are divided by their Euclidean norm (sum of squares and square root in f32; an
+ *                     all-zero vector stays zero).  Tokens are never normalised.  Alone it is VITX_ERR_ARG.
+ * Layout per image: the selected layers in ascending order; per layer [cls D], then [mean D], then [tokens (N-1) * D], only the selected parts.
+ *   vitx_feat_floats = popcount(layers) * (D * [CLS] + D * [MEAN] + (N-1) * D * [TOKENS]).
+ * Determinism: the pooled sum has a fixed order (one workgroup per image and layer, no atomics).  An image's feature bits do not depend on
+ *   its batch, its position in the batch, the sub-batch cut or the number of streams -- the invariant the probabilities keep.
+ * vitx_feat_enable(ctx, flags, layer_mask): bit l of layer_mask selects layer l; layer_mask 0 = the last layer only; flags 0 = off (frees
+ *   the buffer).  The buffer is sized for the images one pass takes and allocated here (VITX_ERR_NOMEM when that fails).  Mask bits at or
+ *   beyond L, unknown flags, VITX_FEAT_L2 alone: VITX_ERR_ARG.  ViTSTR contexts: VITX_ERR_UNSUPPORTED.  Synchronises the device.
+ * The last layer:
+ *   CLS only: the last layer still carries only the class rows (the default; see last_layer_all_rows): probabilities and logits are the same
+ *     bits as with features off.
+ *   MEAN or TOKENS of the last layer: while enabled, the context evaluates EVERY row of the last layer (as with last_layer_all_rows = 1): its
+ *     probabilities are those of the whole graph and can differ from the same context's forward without features by the operand type's
+ *     rounding (bf16 about 1e-3).  They are the bits of a last_layer_all_rows = 1 context.
+ *   Intermediate layers never change the forward.
+ * While features are on, a forward of more than one pass (vitx_ctx_split) is VITX_ERR_ARG, and forwards do not use the hipGraph cache (as
+ *   with the trace and the maps); profiling reports the launches as class "features".  With features off nothing is launched or allocated.
+ * vitx_feat_read: synchronises and copies the features of the last forward's n images ([n][vitx_feat_floats] f32); VITX_ERR_ARG before any
+ *   forward with features on or when n_floats is too small.  vitx_feat_images: that n (0 before any such forward since vitx_feat_enable).
+ * vitx_feat_device: the device buffer itself ([capacity][vitx_feat_floats] f32; NULL while off) for callers that stay on the GPU.  It is
+ *   written by the forward's streams: work that reads it is ordered after the caller's stream, like d_probs.
+ * vitx_op_features: the kernel on its own (device pointers; only enqueues).  Row t of image i is read at d_x + i * img_stride + t * row_stride
+ *   (floats; the compact class rows of a class-rows-only last layer are N = 1, img_stride = D); d_w, d_b [D]; image i's outputs go to
+ *   d_cls / d_mean / d_tokens + i * out_img_stride.  Any output may be NULL (at least one is not); row 0 is read only for d_cls, rows 1 .. N-1
+ *   only for d_mean / d_tokens.  NULL inputs, n_img or N < 1, N == 1 with d_mean or d_tokens, pointers not 16-byte aligned or strides not
+ *   multiples of 4 floats: VITX_ERR_ARG; a hidden size without a LayerNorm instantiation: VITX_ERR_UNSUPPORTED (both before any device call). */
+#define VITX_FEAT_CLS 1
+#define VITX_FEAT_MEAN 2
+#define VITX_FEAT_TOKENS 4
+#define VITX_FEAT_L2 8
+int vitx_feat_enable(vitx_ctx *c, int flags, uint64_t layer_mask);
+int vitx_feat_floats(const vitx_ctx *c);
+int vitx_feat_images(const vitx_ctx *c);
+int vitx_feat_read(vitx_ctx *c, float *out, size_t n_floats);
+const void *vitx_feat_device(const vitx_ctx *c);
+int vitx_op_features(const void *d_x, long row_stride, long img_stride, const void *d_w, const void *d_b,
+                     void *d_cls, void *d_mean, void *d_tokens, long out_img_stride,
+                     int n_img, int N, int D, float eps, int l2, void *stream);
+
 /* ---- MXFP8 operands (VITX_MXFP8, encoding above) ------------------------------- */
 /* Host encoder: x f32 [rows][K] -> q [rows][k_pad] e4m3 bytes + scales [rows][k_pad / 32] (k_pad >= K, a multiple of 32; columns
  * K .. k_pad are zero elements, whole padding blocks get scale 127).  VITX_ERR_ARG on NULL or a bad size. */

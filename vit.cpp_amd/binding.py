@@ -24,6 +24,7 @@ EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_BIAS_F32, EPI_PATCH, EPI_BIAS_HILO 
 GEMM_AUTO, GEMM_PP, GEMM_AUTO_SPLIT = 0, 1, 2          # vitx_op_gemm_ex `kernel` (or a ring configuration: 945, 445, 245, 122)
 ATTN_AUTO, ATTN_SINGLE, ATTN_FLOW, ATTN_PERSIST, ATTN_STREAM = 0, 1, 3, 4, 5   # vitx_op_attention_ex `kernel`
 ATTN_ROLLOUT = 1                # vitx_attn_enable flag
+FEAT_CLS, FEAT_MEAN, FEAT_TOKENS, FEAT_L2 = 1, 2, 4, 8      # vitx_feat_enable flags
 
 EXPORTS = [
     "vitx_status_str", "vitx_last_error", "vitx_model_load", "vitx_model_free", "vitx_model_uid", "vitx_model_hparams", "vitx_model_num_labels",
@@ -34,6 +35,7 @@ EXPORTS = [
     "vitx_model_in_channels", "vitx_model_seq_len", "vitx_ctx_out_rows", "vitx_ctx_split", "vitx_ctx_ln_fusion_active", "vitx_op_attention_f32", "vitx_op_attention_planes", "vitx_op_attention_cls", "vitx_preprocess_vitstr_u8", "vitx_vitstr_decode",
     "vitx_attn_enable", "vitx_attn_floats", "vitx_attn_images", "vitx_attn_read", "vitx_op_attention_map", "vitx_ctx_graph_launches",
     "vitx_mxfp8_quantize", "vitx_op_quantize_mxfp8", "vitx_op_layernorm_mxfp8", "vitx_op_gemm_mxfp8",
+    "vitx_feat_enable", "vitx_feat_floats", "vitx_feat_images", "vitx_feat_read", "vitx_feat_device", "vitx_op_features",
 ]
 
 
@@ -146,6 +148,13 @@ def lib():
             L.vitx_op_quantize_mxfp8.argtypes = [vp, ip, ip, ip, vp, vp, vp]
             L.vitx_op_layernorm_mxfp8.argtypes = [vp, vp, vp, vp, vp, ip, ip, C.c_float, vp]
             L.vitx_op_gemm_mxfp8.argtypes = [ip, vp, vp, vp, vp, vp, vp, vp, ip, ip, ip, vp]
+        if hasattr(L, "vitx_feat_enable"):
+            L.vitx_feat_enable.argtypes = [vp, ip, C.c_uint64]
+            L.vitx_feat_floats.argtypes = [vp]
+            L.vitx_feat_images.argtypes = [vp]
+            L.vitx_feat_read.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t]
+            L.vitx_feat_device.restype = C.c_void_p; L.vitx_feat_device.argtypes = [vp]
+            L.vitx_op_features.argtypes = [vp, C.c_long, C.c_long, vp, vp, vp, vp, vp, C.c_long, ip, ip, ip, C.c_float, ip, vp]
         _lib = L
     return _lib
 
@@ -364,6 +373,58 @@ class Context:
         g = hp.img_size // hp.patch_size
         return np.asarray(m)[..., 1:].reshape(*np.shape(m)[:-1], g, g)
 
+    def feat_enable(self, cls: bool = True, mean: bool = False, tokens: bool = False, l2: bool = False, layers=None) -> None:
+        """Embeddings and token features of every later forward (vitx_feat_enable): the final-norm class embedding, the mean of the patch
+        features and / or the patch features themselves, of `layers` (None = the last layer).  l2=True divides cls and mean by their norm.
+        mean or tokens of the last layer make it compute every row (the probabilities of a last_layer_all_rows=1 context)."""
+        L = self.model.hparams.num_hidden_layers
+        sel = [L - 1] if layers is None else sorted(set(int(l) for l in layers))
+        mask = 0
+        for l in sel:
+            if l < 0 or l >= 64:
+                raise ValueError(f"layer {l} outside 0..63")
+            mask |= 1 << l
+        flags = (FEAT_CLS if cls else 0) | (FEAT_MEAN if mean else 0) | (FEAT_TOKENS if tokens else 0) | (FEAT_L2 if l2 else 0)
+        if not sel:
+            raise ValueError("feat_enable: no layer selected (feat_disable() turns the features off)")
+        check(lib().vitx_feat_enable(self._h, flags, mask), "vitx_feat_enable")
+        self._feat_layers, self._feat_flags = (sel if flags else []), flags
+
+    def feat_disable(self) -> None:
+        check(lib().vitx_feat_enable(self._h, 0, 0), "vitx_feat_enable")
+        self._feat_layers, self._feat_flags = [], 0
+
+    def feat_read(self, n: Optional[int] = None):
+        """Features of the last forward made with features on, all of its n images: {layer: {"cls": [n, D], "mean": [n, D],
+        "tokens": [n, N - 1, D]}} f32 with the selected kinds only.  `n`, if given, must be that batch."""
+        hp = self.model.hparams
+        N, D = (hp.img_size // hp.patch_size) ** 2 + 1, hp.hidden_size
+        sel, flags = getattr(self, "_feat_layers", []), getattr(self, "_feat_flags", 0)
+        fpi = lib().vitx_feat_floats(self._h)
+        have = lib().vitx_feat_images(self._h)
+        if n is not None and n != have:
+            raise ValueError(f"feat_read: the last forward with features on had {have} images, not {n}")
+        n = have
+        if n == 0:
+            raise VitxError("feat_read: no forward has run with features on since feat_enable")
+        out = np.empty((n, fpi), np.float32)
+        check(lib().vitx_feat_read(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size), "vitx_feat_read")
+        kinds = [(k, rows) for k, bit, rows in (("cls", FEAT_CLS, 1), ("mean", FEAT_MEAN, 1), ("tokens", FEAT_TOKENS, N - 1)) if flags & bit]
+        assert fpi == len(sel) * D * sum(rows for _, rows in kinds)
+        res, off = {}, 0
+        for l in sel:
+            res[l] = {}
+            for k, rows in kinds:
+                v = out[:, off:off + rows * D]
+                res[l][k] = v.reshape(n, N - 1, D) if k == "tokens" else v
+                off += rows * D
+        return res
+
+    def feat_device(self) -> Tuple[int, int]:
+        """(device pointer of the feature buffer [capacity][floats per image] f32, floats per image) for callers that stay on the GPU
+        (vitx_feat_device); the layout per image is feat_read()'s order.  Ordered after the forward's stream, like d_probs."""
+        return int(lib().vitx_feat_device(self._h) or 0), int(lib().vitx_feat_floats(self._h))
+
     def synchronize(self) -> None:
         check(lib().vitx_ctx_synchronize(self._h), "vitx_ctx_synchronize")
 
@@ -472,6 +533,13 @@ def probe_mfma(device: int = 0, dtype: int = BF16, fill: int = 2, target_ms: flo
 def op_attention_map(dtype: int, d_qkv: int, d_cls: int, d_mean: int, n_img: int, N: int, D: int, H: int, lo_off: int = 0, stream: int = 0) -> None:
     """vitx_op_attention_map: class-token maps [n_img, H, N] and / or the head mean [n_img, N, N] (f32, device pointers; 0 = not wanted)."""
     check(lib().vitx_op_attention_map(dtype, d_qkv, lo_off, d_cls or None, d_mean or None, n_img, N, D, H, stream or None), "vitx_op_attention_map")
+
+
+def op_features(d_x: int, row_stride: int, img_stride: int, d_w: int, d_b: int, d_cls: int, d_mean: int, d_tokens: int, out_img_stride: int,
+                n_img: int, N: int, D: int, eps: float = 1e-6, l2: bool = False, stream: int = 0) -> None:
+    """vitx_op_features: the f32 final-norm features of n_img images of N rows (device pointers; 0 = output not wanted; strides in floats)."""
+    check(lib().vitx_op_features(d_x, row_stride, img_stride, d_w, d_b, d_cls or None, d_mean or None, d_tokens or None, out_img_stride,
+                                 n_img, N, D, eps, int(l2), stream or None), "vitx_op_features")
 
 
 def mx_k_pad(K: int) -> int:

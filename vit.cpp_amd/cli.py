@@ -4,6 +4,7 @@ directory-walk accuracy harness:
     python vit_cli.py -m model.gguf -i image.jpg [-k 5] [--dtype f16|bf16|mxfp8] [--interp bicubic|bilinear]
     python vit_cli.py -m model.gguf --dir imagenet_val/ [--batch 256]       # top-1 over <dir>/<label>/*.jpg
     python vit_cli.py -m model.gguf -i image.jpg --attn-map map.pgm [--attn-kind rollout|last]   # + where the model looked (P5 picture)
+    python vit_cli.py -m model.gguf (-i image.jpg | --dir DIR) --embed out.npy [--embed-kind cls|mean|tokens] [--embed-l2]   # + the embeddings
 
 Same flags as vit_params_parse (vit.cpp:955-1002: -m -i -t -k -s -e; -t, -s and -e are accepted and ignored exactly
 as the reference's forward ignores seed and eps), same stdout lines (" > label : 0.xx", vit.cpp:1062-1067) and the
@@ -55,9 +56,21 @@ def main(argv: List[str] | None = None) -> int:
     ap.add_argument("--attn-map", default=None, metavar="PATH", help="with -i: write the image's attention map as a binary PGM (P5), img_size x img_size")
     ap.add_argument("--attn-kind", default="rollout", choices=["rollout", "last"],
                     help="rollout: attention rollout through all layers; last: head mean of the last layer's class-token map")
+    ap.add_argument("--embed", default=None, metavar="OUT.npy",
+                    help="also write the last layer's final-norm features as an .npy array, one row per image (with --dir: in walk order, and the "
+                         "file names to OUT.npy.txt); the classification output is unchanged")
+    ap.add_argument("--embed-kind", default="cls", choices=["cls", "mean", "tokens"],
+                    help="cls: the class-token embedding [D]; mean: the mean of the patch features [D]; tokens: the patch features [N-1, D]")
+    ap.add_argument("--embed-l2", action="store_true", help="divide the cls / mean embedding by its Euclidean norm")
     a = ap.parse_args(argv)
     if a.attn_map and a.dir is not None:
         ap.error("--attn-map takes the single image of -i, not --dir")
+    if a.embed is None and (a.embed_l2 or a.embed_kind != "cls"):
+        ap.error("--embed-kind and --embed-l2 need --embed OUT.npy")
+    if a.embed_l2 and a.embed_kind == "tokens":
+        ap.error("--embed-l2 normalises the cls / mean embedding; token features are never normalised")
+    feat = dict(cls=a.embed_kind == "cls", mean=a.embed_kind == "mean", tokens=a.embed_kind == "tokens", l2=a.embed_l2)
+    last = lambda ctx: ctx.feat_read()[model.hparams.num_hidden_layers - 1][a.embed_kind]
 
     t_main = time.perf_counter()
     print(f"main: seed = {a.seed if a.seed >= 0 else int(time.time())}", file=sys.stderr)
@@ -84,7 +97,12 @@ def main(argv: List[str] | None = None) -> int:
         if a.attn_map:
             L = model.hparams.num_hidden_layers
             ctx.attn_enable([] if a.attn_kind == "rollout" else [L - 1], rollout=a.attn_kind == "rollout")
+        if a.embed:
+            ctx.feat_enable(**feat)
         probs = ctx.forward(img1[None])[0]
+        if a.embed:
+            np.save(a.embed, last(ctx))
+            print(f"main: wrote the {a.embed_kind} embedding to '{a.embed}'", file=sys.stderr)
         if a.attn_map:
             cls, roll = ctx.attn_read()
             m = roll[0] if a.attn_kind == "rollout" else cls[0, 0].mean(axis=0)
@@ -115,14 +133,24 @@ def main(argv: List[str] | None = None) -> int:
         print(f"main: no <label>/<image> files under '{a.dir}' match the model's labels", file=sys.stderr)
         return 1
     ctx = binding.Context(model, device=a.device, max_batch=min(a.batch, len(files)), dtype=dt)
+    if a.embed:
+        ctx.feat_enable(**feat)
+    rows = []
     correct = 0
     t0 = time.perf_counter()
     for lo in range(0, len(files), ctx.max_batch):
         chunk = files[lo:lo + ctx.max_batch]
         batch = np.stack([binding.preprocess(_decode(f), S, interp) for f in chunk])
         pred = ctx.forward(batch).argmax(1)
+        if a.embed:
+            rows.append(last(ctx).copy())
         correct += int((pred == np.asarray(truth[lo:lo + len(chunk)])).sum())
     el = time.perf_counter() - t0
+    if a.embed:
+        np.save(a.embed, np.concatenate(rows))
+        with open(a.embed + ".txt", "w") as f:
+            f.write("".join(p + "\n" for p in files))
+        print(f"main: wrote {len(files)} {a.embed_kind} embeddings to '{a.embed}' and their file names to '{a.embed}.txt'", file=sys.stderr)
     print(f"top-1 accuracy: {correct / len(files):.4f} ({correct}/{len(files)})  {len(files) / el:.1f} images/s incl. decode + preprocess")
     return 0
 

@@ -36,10 +36,12 @@ namespace {
 
 enum ProfClass {
     PC_GEMM_PATCH = 0, PC_LAYERNORM, PC_GEMM_QKV, PC_ATTENTION, PC_GEMM_PROJ, PC_GEMM_FC1, PC_GEMM_FC2,
-    PC_GEMM_HEAD, PC_SOFTMAX, PC_DEQUANT, PC_ATTENTION_CLS, PC_GEMM_TAIL, PC_ATTN_MAP, PC_COUNT
+    PC_GEMM_HEAD, PC_SOFTMAX, PC_DEQUANT, PC_ATTENTION_CLS, PC_GEMM_TAIL, PC_ATTN_MAP, PC_FEATURES, PC_COUNT
 };
 const char *kProfNames[PC_COUNT] = {"patch_embed", "layernorm", "gemm_qkv_bias", "attention", "gemm_proj_resid",
-                                    "gemm_fc1_gelu", "gemm_fc2_resid", "gemm_head", "softmax", "dequant_weights", "attention_cls", "gemm_cls_tail", "attention_map"};
+                                    "gemm_fc1_gelu", "gemm_fc2_resid", "gemm_head", "softmax", "dequant_weights", "attention_cls", "gemm_cls_tail", "attention_map",
+                                    "features"};
+static_assert(PC_COUNT <= VITX_PROF_MAX_CLASSES, "vitx_profile_read callers size their arrays by VITX_PROF_MAX_CLASSES");
 
 // A weight matrix kept in the file's block form on the device (quant.hip): `blocks` = N rows of K/32 blocks in the file's byte
 // layout -- except q4_0, which is split into a nibble plane (`blocks`, 16 B per block, rows padded to n_pad) and an f16 scale
@@ -182,6 +184,18 @@ struct vitx_ctx {
     void attn_free() {
         for (float **p : {&attn_out, &attn_roll[0], &attn_roll[1], &attn_cls_last}) { if (*p) (void)hipFree(*p); *p = nullptr; }
     }
+    // embeddings and token features (vitx_feat_enable): nothing is allocated or launched while feat_flags == 0
+    int feat_flags = 0;          // VITX_FEAT_*
+    uint64_t feat_mask = 0;      // selected layers (never 0 while on: "the last layer" is resolved at vitx_feat_enable)
+    int feat_fpi = 0;            // floats per image: popcount(mask) * feat_layer_floats()
+    int feat_cap = 0;            // images the buffer holds (= the images one pass takes)
+    int feat_n = 0;              // images of the last forward made with features on (0: none since vitx_feat_enable)
+    float *feat_out = nullptr;   // [feat_cap][feat_fpi]: per image the selected layers in ascending order, each [cls D][mean D][tokens (N-1) D] (selected parts only)
+    bool feat_on() const { return feat_flags != 0; }
+    int feat_layer_floats() const { return D * ((feat_flags & VITX_FEAT_CLS ? 1 : 0) + (feat_flags & VITX_FEAT_MEAN ? 1 : 0) + (feat_flags & VITX_FEAT_TOKENS ? N - 1 : 0)); }
+    // MEAN or TOKENS of the last layer need every row of it: no class-rows-only tail while they are on (as while the trace is)
+    bool feat_last_all_rows() const { return (feat_flags & (VITX_FEAT_MEAN | VITX_FEAT_TOKENS)) && ((feat_mask >> (L - 1)) & 1); }
+    void feat_free() { if (feat_out) (void)hipFree(feat_out); feat_out = nullptr; }
     // hipGraph cache of the single-stream (small-batch) forward, opt-in (vitx_ctx_options::graph).  Key = (images, batch, outputs): the graph
     // bakes the pointers in.  An entry is captured the second time in a row its key is seen (one-off calls are never captured).
     // Measured (profiles/r02f/hipgraph_small_batch.txt): replaying the ~100 dependent launches as a graph takes the enqueue work off
@@ -212,6 +226,7 @@ struct vitx_ctx {
         if (ln_fb_host) (void)hipHostFree(ln_fb_host);
         if (trace_buf) (void)hipFree(trace_buf);
         attn_free();
+        feat_free();
         for (void *p : allocs) (void)hipFree(p);
         if (stream) (void)hipStreamDestroy(stream);
     }
@@ -631,6 +646,22 @@ static int forward_slice(vitx_ctx *c, vitx_ctx::Slice &sl, hipStream_t st, const
     };
     const vitx_ctx::WeightSet &ws = *c->wset;
     const int D = c->D, N = c->N, tm = c->tm, tn = c->tn, dt = c->dtype;
+    // embeddings and token features of layer il (vitx_feat_enable), from the residual stream its fc2 has just completed: one launch writes this
+    // sub-batch's images straight into the packed per-image layout.  cls_rows: X is the compact class rows Xc of the class-rows-only last layer.
+    auto features = [&](int il, bool cls_rows) -> int {
+        if (!((c->feat_mask >> il) & 1)) return VITX_OK;
+        const int fl = c->feat_flags;
+        float *o = c->feat_out + (size_t)first_img * c->feat_fpi + (size_t)__builtin_popcountll(c->feat_mask & ((1ull << il) - 1)) * c->feat_layer_floats();
+        float *o_cls = nullptr, *o_mean = nullptr, *o_tok = nullptr;
+        if (fl & VITX_FEAT_CLS) { o_cls = o; o += D; }
+        if (fl & VITX_FEAT_MEAN) { o_mean = o; o += D; }
+        if (fl & VITX_FEAT_TOKENS) o_tok = o;
+        const double rows = (double)n * ((o_cls ? 1 : 0) + (o_mean || o_tok ? N - 1 : 0));
+        ProfScope ps(c, st, PC_FEATURES, 0, rows * D * 4 + (double)n * D * 4 * ((o_cls ? 1 : 0) + (o_mean ? 1 : 0) + (o_tok ? N - 1 : 0)));
+        HIP_TRY(launch_features(cls_rows ? sl.Xc : sl.X, D, cls_rows ? (long)D : (long)N * D, ws.norm_w, ws.norm_b, o_cls, o_mean, o_tok, c->feat_fpi,
+                                n, cls_rows ? 1 : N, D, c->hp.eps, (fl & VITX_FEAT_L2) != 0, st));
+        return VITX_OK;
+    };
     const int Mp_real = n * c->g * c->g;                           // patch rows
     const int M_real = n * N, M = round_up(M_real, tm);            // token rows
     const double eb = 2.0;                                          // operand bytes
@@ -717,7 +748,7 @@ static int forward_slice(vitx_ctx *c, vitx_ctx::Slice &sl, hipStream_t st, const
         return VITX_OK;
     };
     GemmLn fix_u{}, fix_u2{};          // fused LayerNorm launches whose output (U / U2) has not been consumed yet
-    const bool tail = c->cls_tail && c->trace_ids.empty();      // the last layer carries only the class-token rows past its qkv projection (vitx_ctx::cls_tail)
+    const bool tail = c->cls_tail && c->trace_ids.empty() && !c->feat_last_all_rows();      // the last layer carries only the class-token rows past its qkv projection (vitx_ctx::cls_tail)
     for (int il = 0; il < c->L; ++il) {
         const LayerW &w = ws.layers[il];
         const bool tail_now = tail && il + 1 == c->L;
@@ -763,6 +794,7 @@ static int forward_slice(vitx_ctx *c, vitx_ctx::Slice &sl, hipStream_t st, const
             if ((rc = gemm_mx(c, st, r.pc_fc2, EPI_BIAS_RESID, sl.Hmx, sl.Hmx_s, w.mx[W_FC2], w.fc2_b, r.X, nullptr, r.M_real, D))) return rc;
             if (nx && (rc = layernorm_mx(r.X, nx->ln1_w, nx->ln1_b, sl.Umx, sl.Umx_s, r.M_real))) return rc;
             if (!c->trace_ids.empty() && (rc = trace(il + 1))) return rc;
+            if (c->feat_on() && (rc = features(il, tail_now))) return rc;
             continue;
         }
         // output projection + residual (vit.cpp:868-873), then norm2 (vit.cpp:881-885) -> U2
@@ -772,6 +804,7 @@ static int forward_slice(vitx_ctx *c, vitx_ctx::Slice &sl, hipStream_t st, const
                        fix_u2.todo ? &fix_u2 : nullptr))) return rc;
         if ((rc = resid_gemm_ln(r, r.pc_fc2, sl.Hbuf, Wl[W_FC2], w.fc2_b, 4 * D, Fl[W_FC2], nx ? nx->ln1_w : nullptr, nx ? nx->ln1_b : nullptr, sl.U, &fix_u))) return rc;
         if (!c->trace_ids.empty() && (rc = trace(il + 1))) return rc;
+        if (c->feat_on() && (rc = features(il, tail_now))) return rc;
     }
     // cls pooling + final norm (vit.cpp:910-919): row b*N of X, i.e. row stride N*D.  ViTSTR (vitstr.cpp:864-895) keeps the first
     // R = 25 tokens of every image instead: output row r = image r / R, token r % R.
@@ -953,6 +986,7 @@ int vitx_forward_device(vitx_ctx *c, const void *d_imgs, int n, void *d_probs, v
     // caller's stream through the same scratch -- images are independent, so the results are the ones a single pass would give
     if (n > c->call_limit && !c->trace_ids.empty()) { set_error("vitx_forward_device: the residual-stream trace takes one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
     if (n > c->call_limit && c->attn_on()) { set_error("vitx_forward_device: attention maps take one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
+    if (n > c->call_limit && c->feat_on()) { set_error("vitx_forward_device: features take one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
     for (int i0 = 0; i0 < n; i0 += c->call_limit) {
         const int ni = std::min(c->call_limit, n - i0);
         const int rc = forward_pass(c, (const float *)d_imgs + (size_t)i0 * c->S * c->S * c->Cin, ni, (float *)d_probs + (size_t)i0 * c->R * c->C,
@@ -960,6 +994,7 @@ int vitx_forward_device(vitx_ctx *c, const void *d_imgs, int n, void *d_probs, v
         if (rc) return rc;
     }
     if (c->attn_on()) c->attn_n = n;
+    if (c->feat_on()) c->feat_n = n;
     return VITX_OK;
 }
 static int forward_pass(vitx_ctx *c, const void *d_imgs, int n, void *d_probs, void *d_logits, hipStream_t st) {
@@ -988,7 +1023,7 @@ static int forward_pass(vitx_ctx *c, const void *d_imgs, int n, void *d_probs, v
     const bool serial = c->prof_on;
     const int ns = (c->nslices > 1 && n >= 8 * c->nslices) ? c->nslices : 1;
     if (ns == 1) {
-        if (c->graphs_on && !c->prof_on && c->trace_ids.empty() && !c->attn_on()) {
+        if (c->graphs_on && !c->prof_on && c->trace_ids.empty() && !c->attn_on() && !c->feat_on()) {
             bool done = false;
             const int rc = forward_graph(c, st, d_imgs, n, d_probs, d_logits, &done);
             if (rc != VITX_OK || done) return rc;
@@ -1371,6 +1406,58 @@ int vitx_attn_read(vitx_ctx *c, float *out, size_t n_floats) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, c->attn_out, need * 4, hipMemcpyDeviceToHost));
+    return VITX_OK;
+}
+
+int vitx_feat_enable(vitx_ctx *c, int flags, uint64_t layer_mask) {
+    if (!c) return VITX_ERR_ARG;
+    constexpr int kinds = VITX_FEAT_CLS | VITX_FEAT_MEAN | VITX_FEAT_TOKENS;
+    if (flags & ~(kinds | VITX_FEAT_L2)) { set_error("vitx_feat_enable: unknown flags 0x%x", flags); return VITX_ERR_ARG; }
+    if (flags && !(flags & kinds)) { set_error("vitx_feat_enable: VITX_FEAT_L2 modifies VITX_FEAT_CLS / VITX_FEAT_MEAN and selects nothing on its own"); return VITX_ERR_ARG; }
+    if (c->L < 64 && (layer_mask >> c->L)) { set_error("vitx_feat_enable: layer mask 0x%llx names layers beyond the model's %d", (unsigned long long)layer_mask, c->L); return VITX_ERR_ARG; }
+    if (flags && c->R != 1) { set_error("vitx_feat_enable: features are not available for ViTSTR contexts"); return VITX_ERR_UNSUPPORTED; }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());          // no forward in flight writes the buffer about to be freed
+    c->feat_free();
+    c->feat_flags = 0; c->feat_mask = 0; c->feat_fpi = 0; c->feat_cap = 0; c->feat_n = 0;
+    if (!flags) return VITX_OK;
+    if (!layer_mask) layer_mask = 1ull << (c->L - 1);
+    c->feat_flags = flags;                    // feat_layer_floats() reads it
+    const int cap = std::min(c->max_batch, c->call_limit);
+    const size_t fpi = (size_t)__builtin_popcountll(layer_mask) * c->feat_layer_floats();
+    if (fpi > 0x7fffffff || hipMalloc((void **)&c->feat_out, (size_t)cap * fpi * 4) != hipSuccess) {
+        (void)hipGetLastError(); c->feat_out = nullptr; c->feat_flags = 0;
+        set_error("vitx_feat_enable: cannot allocate the feature buffer for %d images of %zu floats", cap, fpi);
+        return VITX_ERR_NOMEM;
+    }
+    c->feat_mask = layer_mask; c->feat_fpi = (int)fpi; c->feat_cap = cap;
+    return VITX_OK;
+}
+int vitx_feat_floats(const vitx_ctx *c) { return c ? c->feat_fpi : 0; }
+int vitx_feat_images(const vitx_ctx *c) { return c ? c->feat_n : 0; }
+const void *vitx_feat_device(const vitx_ctx *c) { return c ? c->feat_out : nullptr; }
+int vitx_feat_read(vitx_ctx *c, float *out, size_t n_floats) {
+    if (!c || !out) return VITX_ERR_ARG;
+    if (!c->feat_on() || c->feat_n == 0) { set_error("vitx_feat_read: no forward has run with features on since vitx_feat_enable"); return VITX_ERR_ARG; }
+    const size_t need = (size_t)c->feat_n * c->feat_fpi;
+    if (n_floats < need) { set_error("vitx_feat_read: buffer too small (%zu floats needed for %d images)", need, c->feat_n); return VITX_ERR_ARG; }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, c->feat_out, need * 4, hipMemcpyDeviceToHost));
+    return VITX_OK;
+}
+// The feature kernel on its own.  Every argument check comes before the first device call.
+int vitx_op_features(const void *d_x, long row_stride, long img_stride, const void *d_w, const void *d_b, void *d_cls, void *d_mean, void *d_tokens, long out_img_stride,
+                     int n_img, int N, int D, float eps, int l2, void *stream) {
+    if (!d_x || !d_w || !d_b || (!d_cls && !d_mean && !d_tokens) || n_img <= 0 || N <= 0 || D <= 0) { set_error("vitx_op_features: invalid argument"); return VITX_ERR_ARG; }
+    if (N == 1 && (d_mean || d_tokens)) { set_error("vitx_op_features: the mean and the tokens need at least one patch row (N %d)", N); return VITX_ERR_ARG; }
+    for (const void *p : {d_x, d_w, d_b, (const void *)d_cls, (const void *)d_mean, (const void *)d_tokens})
+        if ((uintptr_t)p % 16) { set_error("vitx_op_features: pointers must be 16-byte aligned"); return VITX_ERR_ARG; }
+    if (row_stride % 4 || img_stride % 4 || out_img_stride % 4) { set_error("vitx_op_features: strides must be multiples of 4 floats"); return VITX_ERR_ARG; }
+    if (!layernorm_supports(D)) { set_error("vitx_op_features: hidden size %d has no LayerNorm instantiation", D); return VITX_ERR_UNSUPPORTED; }
+    hipError_t e = launch_features((const float *)d_x, row_stride, img_stride, (const float *)d_w, (const float *)d_b, (float *)d_cls, (float *)d_mean, (float *)d_tokens,
+                                   out_img_stride, n_img, N, D, eps, l2 != 0, (hipStream_t)stream);
+    if (e != hipSuccess) { set_error("vitx_op_features: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
     return VITX_OK;
 }
 // The map kernels on their own (the parity tests): d_cls [n_img][H][N] class-token rows, d_mean [n_img][N][N] mean_h A_h (either may be NULL).

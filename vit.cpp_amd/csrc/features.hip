@@ -1,0 +1,157 @@
+// features.hip -- image embeddings and token features (vitx_feat_enable, vitx_op_features; the contract: include/vitx.h).
+//
+// F = ((X - mean) * rstd) * norm.weight + norm.bias of the f32 residual stream X, per row, in f32: the arithmetic of ln_row_tiled /
+// layernorm_kernel (device_common.h, kernels.hip) operation for operation on the shared statistics helpers, WITHOUT the final rounding to
+// the operand type -- so F rounded to nearest even IS what those kernels store (-ffp-contract=off, as for every kernel of the library).
+//
+// One workgroup per image, W waves (feat_waves; one wave when only the class row is asked for), one pass over the image's rows, every row read once:
+//   * wave W - 1 takes the class row (row 0) first, when the class embedding is asked for;
+//   * wave w takes the patch rows 1 + w, 1 + w + W, ... in ascending order: stores F (TOKENS) and adds it to per-lane column
+//     accumulators (MEAN).  Rows go two at a time at the widths up to 1024 (both rows' loads are issued before either is used);
+//   * the W partial sums are added into one LDS row in wave order, ((p_0 + p_1) + p_2) + ..., then divided by N - 1.
+// No atomics, nothing depends on the batch: an image's bits are a function of its own rows, N and D only.
+// Column ownership follows the statistics helpers: lane l holds columns c * 256 + 4 l .. + 3 of tile c (tiled widths: 16-byte loads and
+// stores, 1 KiB contiguous per wave instruction) or (i * 64 + l) * VEC .. of piece i (flat widths, VEC of the instantiation table).
+#include "device_common.h"
+#include "kernels.h"
+
+namespace vitx {
+
+namespace {
+
+// waves per workgroup: 16 (4 per SIMD, 128 VGPRs each) up to 768 columns; 8 above, where a row, the accumulators and the second row or the
+// weights of a piece need more than 128 registers per lane (checked with -save-temps: no instantiation spills)
+constexpr int feat_waves(int D) { return D <= 768 ? 16 : 8; }
+
+template <int VEC, int NV> struct FeatRow {
+    static constexpr bool kTiled = VEC == 4 && NV <= LN_MAX_TILES;
+    static __device__ __forceinline__ int col(int i, int lane) { return kTiled ? i * 256 + lane * 4 : (i * 64 + lane) * VEC; }
+    // f[i][j] = F at column col(i) + j of the row xr
+    static __device__ __forceinline__ void norm(const float *__restrict__ xr, const float *__restrict__ w, const float *__restrict__ b, float eps, int lane, float (&f)[NV][VEC]) {
+        if constexpr (kTiled) {
+            f32x4 v[NV];
+            float mean, rstd;
+            ln_tiled_stats<NV>(xr, eps, lane, v, mean, rstd);
+#pragma unroll
+            for (int c = 0; c < NV; ++c) {
+                const f32x4 ww = *(const f32x4 *)(w + col(c, lane)), bb = *(const f32x4 *)(b + col(c, lane));
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { float t = (v[c][e] - mean) * rstd; t = t * ww[e]; f[c][e] = t + bb[e]; }
+            }
+        } else {
+            float scale;
+            ln_flat_stats<VEC, NV>(xr, eps, lane, f, scale);         // f = x - mean
+#pragma unroll
+            for (int i = 0; i < NV; ++i)
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) { float t = f[i][j] * scale; t = t * w[col(i, lane) + j]; f[i][j] = t + b[col(i, lane) + j]; }
+        }
+    }
+    static __device__ __forceinline__ void store(float *__restrict__ yr, int lane, const float (&f)[NV][VEC]) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            float *p = yr + col(i, lane);
+            if constexpr (VEC == 4) *(f32x4 *)p = f32x4{f[i][0], f[i][1], f[i][2], f[i][3]};
+            else if constexpr (VEC == 2) *(f32x2 *)p = f32x2{f[i][0], f[i][1]};
+            else *p = f[i][0];
+        }
+    }
+    // VITX_FEAT_L2: f / sqrt(sum of squares), both in f32 (per-lane sums in column order, then a butterfly: the same bits in every lane);
+    // an all-zero vector stays zero
+    static __device__ __forceinline__ void l2(float (&f)[NV][VEC]) {
+        float ss = 0.0f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) ss += f[i][j] * f[i][j];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+        const float nrm = sqrtf(ss);
+        if (nrm > 0.0f) {
+#pragma unroll
+            for (int i = 0; i < NV; ++i)
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) f[i][j] = f[i][j] / nrm;
+        }
+    }
+};
+
+template <int VEC, int NV>
+__global__ __launch_bounds__(feat_waves(64 * VEC * NV) * 64) void features_kernel(const float *__restrict__ x, long row_stride, long img_stride, const float *__restrict__ w,
+                                                                   const float *__restrict__ b, float *__restrict__ cls, float *__restrict__ mean, float *__restrict__ tokens,
+                                                                   long out_img_stride, int N, float eps, int l2) {
+    typedef FeatRow<VEC, NV> R;
+    constexpr int D = 64 * VEC * NV;
+    constexpr int U = D <= 1024 ? 2 : 1;          // patch rows per step of a wave
+    __shared__ float pool[D];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, W = blockDim.x >> 6;
+    const float *xi = x + (size_t)blockIdx.x * img_stride;
+    const size_t out_off = (size_t)blockIdx.x * out_img_stride;
+    float f[U][NV][VEC];
+    if (cls && wave == W - 1) {
+        R::norm(xi, w, b, eps, lane, f[0]);
+        if (l2) R::l2(f[0]);
+        R::store(cls + out_off, lane, f[0]);
+    }
+    if (!mean && !tokens) return;
+    float acc[NV][VEC];
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) acc[i][j] = 0.0f;
+    float *tok = tokens ? tokens + out_off : nullptr;
+    for (int t = 1 + wave; t < N; t += U * W) {
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (t + u * W < N) R::norm(xi + (size_t)(t + u * W) * row_stride, w, b, eps, lane, f[u]);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (t + u * W >= N) break;
+            if (tok) R::store(tok + (size_t)(t + u * W - 1) * D, lane, f[u]);
+#pragma unroll
+            for (int i = 0; i < NV; ++i)
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) acc[i][j] += f[u][i][j];
+        }
+    }
+    if (!mean) return;
+    // the waves' partial sums, added in wave order into one row of LDS (a wave without rows adds its zeros)
+    for (int k = 0; k < W; ++k) {
+        if (wave == k) {
+#pragma unroll
+            for (int i = 0; i < NV; ++i)
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) { float *p = pool + R::col(i, lane) + j; *p = k == 0 ? acc[i][j] : *p + acc[i][j]; }
+        }
+        __syncthreads();
+    }
+    if (wave != 0) return;
+    const float cnt = (float)(N - 1);
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) f[0][i][j] = pool[R::col(i, lane) + j] / cnt;
+    if (l2) R::l2(f[0]);
+    R::store(mean + out_off, lane, f[0]);
+}
+
+}  // namespace
+
+// F of n_img images of N rows (row t of image i at x + i * img_stride + t * row_stride): cls[i * out_img_stride ..] = F[0] [D],
+// mean[i * out_img_stride ..] = mean of F[1 .. N-1] [D], tokens[i * out_img_stride ..] = F[1 .. N-1] [N - 1][D]; any output may be nullptr.
+// Row 0 is read only for cls, rows 1 .. only for mean / tokens.  hipErrorInvalidValue: no instantiation for D (layernorm_supports).
+hipError_t launch_features(const float *x, long row_stride, long img_stride, const float *w, const float *b, float *cls, float *mean, float *tokens,
+                           long out_img_stride, int n_img, int N, int D, float eps, bool l2, hipStream_t stream) {
+    const bool rows = mean || tokens;
+    const dim3 grid(n_img), blk(64 * (rows ? feat_waves(D) : 1));
+#define VITX_FEAT_CASE(DD, VEC, NV) \
+    case DD: hipLaunchKernelGGL((features_kernel<VEC, NV>), grid, blk, 0, stream, x, row_stride, img_stride, w, b, cls, mean, tokens, out_img_stride, N, eps, l2 ? 1 : 0); break;
+    switch (D) {
+        VITX_LN_WIDTHS(VITX_FEAT_CASE)
+    default: return hipErrorInvalidValue;
+    }
+#undef VITX_FEAT_CASE
+    return hipGetLastError();
+}
+
+}  // namespace vitx

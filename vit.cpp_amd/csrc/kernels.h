@@ -159,6 +159,12 @@ hipError_t launch_attention_cls_map(int dtype, const void *qkv, long lo_off, flo
 hipError_t launch_attention_head_mean(int dtype, const void *qkv, long lo_off, float *out, int n_img, int N, int D, int H, bool half_identity, hipStream_t stream);
 hipError_t launch_rollout_step(float *a, const float *r, int n_img, int N, hipStream_t stream);
 hipError_t launch_rollout_row(const float *cls, long cls_stride, const float *r, float *out, long out_stride, int n_img, int N, int H, hipStream_t stream);
+// Image embeddings and token features (features.hip; vitx_feat_enable): F = the f32 LayerNorm of launch_layernorm before its rounding.  Row t of
+// image i is read at x + i * img_stride + t * row_stride; cls[i * out_img_stride ..] = F[0], mean[..] = mean of F[1 .. N-1], tokens[..] = F[1 .. N-1]
+// ([N-1][D]); any output may be nullptr (row 0 is read only for cls, the other rows only for mean / tokens); l2: cls and mean divided by their norm.
+// Every width of VITX_LN_WIDTHS; pointers 16-byte aligned, strides multiples of 4 floats.
+hipError_t launch_features(const float *x, long row_stride, long img_stride, const float *w, const float *b, float *cls, float *mean, float *tokens,
+                           long out_img_stride, int n_img, int N, int D, float eps, bool l2, hipStream_t stream);
 bool attention_supports(int N, int D, int H);     // any token count; head_dim 64 (tuned kernels) or any other multiple of 8 up to 128 (generic kernel)
 bool attention_single_pass_supports(int N);       // instantiation table of the register-resident kernel
 bool layernorm_supports(int D);

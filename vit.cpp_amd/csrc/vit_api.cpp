@@ -107,6 +107,41 @@ int vit_predict_batch(const vit_model &model, vit_state &state, const image_f32 
     return 0;
 }
 
+// No counterpart in the reference (its forward ends in the class probabilities): the last layer's final-norm features of n images
+int vit_embed_batch(const vit_model &model, vit_state &state, const image_f32 *imgs, int n, int flags, std::vector<std::vector<float>> &out) {
+    out.clear();
+    if (!model.handle || !imgs || n <= 0 || !flags) { fprintf(stderr, "%s: invalid argument\n", __func__); return 1; }
+    if (vitx_model_seq_len(model.handle) > 0) { fprintf(stderr, "%s: this is a ViTSTR model: it has no image embedding\n", __func__); return 1; }
+    const int S = model.hparams.img_size, C = model.hparams.num_classes;
+    for (int i = 0; i < n; ++i)
+        if (imgs[i].nx != S || imgs[i].ny != S || imgs[i].data.size() != (size_t)3 * S * S) {
+            fprintf(stderr, "%s: image %d is %dx%d, model expects %dx%d\n", __func__, i, imgs[i].nx, imgs[i].ny, S, S);
+            return 1;
+        }
+    if (ensure_ctx(model, state, n) != VITX_OK) { fprintf(stderr, "%s: failed to create the context: %s\n", __func__, vitx_last_error()); return 1; }
+    if (vitx_feat_enable(state.ctx, flags, 0) != VITX_OK) { fprintf(stderr, "%s: %s\n", __func__, vitx_last_error()); return 1; }
+    std::vector<float> batch((size_t)n * 3 * S * S);
+    for (int i = 0; i < n; ++i) std::copy(imgs[i].data.begin(), imgs[i].data.end(), batch.begin() + (size_t)i * 3 * S * S);
+    state.prediction.resize((size_t)n * C);
+    const size_t fpi = (size_t)vitx_feat_floats(state.ctx);
+    std::vector<float> all((size_t)n * fpi);
+    const bool ok = vitx_forward(state.ctx, batch.data(), n, state.prediction.data(), nullptr) == VITX_OK && vitx_feat_read(state.ctx, all.data(), all.size()) == VITX_OK;
+    if (!ok) fprintf(stderr, "%s: failed to encode image: %s\n", __func__, vitx_last_error());
+    (void)vitx_feat_enable(state.ctx, 0, 0);
+    if (!ok) return 1;
+    out.resize(n);
+    for (int i = 0; i < n; ++i) out[i].assign(all.begin() + (size_t)i * fpi, all.begin() + (size_t)(i + 1) * fpi);
+    return 0;
+}
+
+int vit_embed(const vit_model &model, vit_state &state, const image_f32 &img1, int flags, std::vector<float> &out) {
+    std::vector<std::vector<float>> all;
+    const int rc = vit_embed_batch(model, state, &img1, 1, flags, all);
+    out.clear();
+    if (rc == 0) out = std::move(all[0]);
+    return rc;
+}
+
 // extensions/vitstr.cpp/vitstr.cpp:135-201
 bool vitstr_image_preprocess(const image_u8 &img, image_f32 &res, const vit_hparams &params) {
     const int S = params.n_img_size();

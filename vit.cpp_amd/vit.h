@@ -8,7 +8,8 @@
 //     ggml_tensor* / ggml_context* (the reference's fields are ggml internals);
 //   * vit_predict still fills `predictions` with all (prob, class) pairs sorted
 //     descending and prints the top-k lines to stdout (vit.cpp:1043-1067);
-//   * vit_predict_batch is NEW (the reference has no batched call): n images per launch.
+//   * vit_predict_batch is NEW (the reference has no batched call): n images per launch;
+//   * vit_embed / vit_embed_batch are NEW (the reference returns class probabilities only): the image embedding.
 // Everything below is a thin wrapper over the C ABI in include/vitx.h.
 #pragma once
 
@@ -83,6 +84,12 @@ int vit_predict(const vit_model &model, vit_state &state, const image_f32 img1, 
                 std::vector<std::pair<float, int>> &predictions);                                      // vit.h:122
 int vit_predict_batch(const vit_model &model, vit_state &state, const image_f32 *imgs, int n, const vit_params &params,
                       std::vector<std::vector<std::pair<float, int>>> &predictions, bool print = false);
+// NEW, no counterpart in the reference: the embeddings of n preprocessed images -- the f32 final-norm features of the last layer
+// (include/vitx.h, "image embeddings and token features").  flags = VITX_FEAT_CLS, VITX_FEAT_MEAN, VITX_FEAT_TOKENS, optionally | VITX_FEAT_L2;
+// out[i] = image i's floats in the order [cls D][mean D][tokens (N-1) * D] (the selected parts).  state.prediction holds the class
+// probabilities of the same forward; the features are switched off again before returning.  0 ok / 1 failure.
+int vit_embed_batch(const vit_model &model, vit_state &state, const image_f32 *imgs, int n, int flags, std::vector<std::vector<float>> &out);
+int vit_embed(const vit_model &model, vit_state &state, const image_f32 &img1, int flags, std::vector<float> &out);
 // ---- the ViTSTR scene-text extension (extensions/vitstr.cpp).  It is a separate program in the reference that re-uses the names
 // vit_image_preprocess / vit_predict with different bodies (vitstr.h:115-119); here both programs live in one library, so the
 // extension's two functions carry a vitstr_ prefix.  vit_model_load is shared: a file whose patch kernel has ONE input channel is
