@@ -1,27 +1,48 @@
 // embed_main.cpp -- image embeddings through the C++ header vit.cpp_amd/vit.h: loads a model and two images, takes the class-token
 // embedding of both in ONE forward (vit_embed_batch, which the reference has no counterpart of) and prints their cosine similarity.
-//   usage: embed_main MODEL.gguf IMAGE_A IMAGE_B
+//   usage: embed_main MODEL.gguf IMAGE_A IMAGE_B [--img-size N] [--out FILE]
+// --img-size N runs the state at N x N instead of the file's size (vit_state::img_size: the position table is resampled); --out writes
+// image A's embedding as raw f32.
 // Build:  g++ -std=c++17 -O2 examples/embed_main.cpp -Ivit.cpp_amd -Lvit.cpp_amd -lvitx -Wl,-rpath,$PWD/vit.cpp_amd -o embed_main
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
+#include <string>
 
 #include "vit.h"
 
 int main(int argc, char **argv) {
-    if (argc != 4) { fprintf(stderr, "usage: %s MODEL.gguf IMAGE_A IMAGE_B\n", argv[0]); return 1; }
+    int img_size = 0;
+    const char *out_path = nullptr;
+    bool bad = argc < 4;
+    for (int i = 4; i < argc && !bad; ++i) {
+        const std::string a = argv[i];
+        if (a == "--img-size" && i + 1 < argc) img_size = atoi(argv[++i]);
+        else if (a == "--out" && i + 1 < argc) out_path = argv[++i];
+        else bad = true;
+    }
+    if (bad) { fprintf(stderr, "usage: %s MODEL.gguf IMAGE_A IMAGE_B [--img-size N] [--out FILE]\n", argv[0]); return 1; }
     vit_model model;
     vit_state state;
     if (!vit_model_load(argv[1], model)) { fprintf(stderr, "%s: failed to load model from '%s'\n", __func__, argv[1]); return 1; }
+    state.img_size = img_size;                      // 0 = the file's
+    vit_hparams pre = model.hparams;                // vit_image_preprocess resizes to whatever img_size it is handed
+    if (img_size > 0) pre.img_size = img_size;
     image_f32 imgs[2];
     for (int i = 0; i < 2; ++i) {
         image_u8 raw;
         if (!load_image_from_file(argv[2 + i], raw)) { fprintf(stderr, "%s: failed to load image from '%s'\n", __func__, argv[2 + i]); return 1; }
-        if (!vit_image_preprocess(raw, imgs[i], model.hparams)) { fprintf(stderr, "%s: failed to preprocess '%s'\n", __func__, argv[2 + i]); return 1; }
+        if (!vit_image_preprocess(raw, imgs[i], pre)) { fprintf(stderr, "%s: failed to preprocess '%s'\n", __func__, argv[2 + i]); return 1; }
     }
     std::vector<std::vector<float>> emb;
     if (vit_embed_batch(model, state, imgs, 2, VITX_FEAT_CLS | VITX_FEAT_L2, emb) != 0) return 1;
     double dot = 0.0, na = 0.0, nb = 0.0;          // the vectors are unit length already (VITX_FEAT_L2); the norms are kept for clarity
     for (size_t k = 0; k < emb[0].size(); ++k) { dot += (double)emb[0][k] * emb[1][k]; na += (double)emb[0][k] * emb[0][k]; nb += (double)emb[1][k] * emb[1][k]; }
+    if (out_path) {
+        FILE *f = fopen(out_path, "wb");
+        if (!f || fwrite(emb[0].data(), sizeof(float), emb[0].size(), f) != emb[0].size()) { fprintf(stderr, "%s: cannot write '%s'\n", __func__, out_path); return 1; }
+        fclose(f);
+    }
     printf("embedding: %zu floats per image (class token, final norm, L2-normalised)\n", emb[0].size());
     printf("cosine similarity : %.6f\n", dot / std::sqrt(na * nb));
     return 0;

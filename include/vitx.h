@@ -170,11 +170,20 @@ typedef struct vitx_ctx_options {
                                  probabilities are equal within the operand type's rounding (measured on 256 images: 1.1e-3 bf16, 3.0e-4 F16, top-1 equal), not
                                  bit for bit; 0.76 of one layer's work is not done (ViT-B: 6.3 % of the forward's flops).  ViTSTR contexts and contexts with a
                                  residual-stream trace always compute every row. */
+    int32_t img_size;         /* 0 = the file's; else the side of the square input of THIS context, a positive multiple of patch_size: the context runs
+                                 [n][img_size][img_size][3] images on (img_size / patch_size)^2 + 1 tokens with the file's position table resampled on the
+                                 device at creation (vitx_pos_embed_resample below).  Equal to the file's: today's context bit for bit, nothing is launched.
+                                 Not a positive multiple of the patch size: VITX_ERR_ARG; a ViTSTR file at a size other than its own: VITX_ERR_UNSUPPORTED. */
+    int32_t pos_interp;       /* enum vitx_pos_interp; used only when img_size differs from the file's (an unknown value is VITX_ERR_ARG in any case) */
 } vitx_ctx_options;
 #define VITX_LN_TEST_KEY 0x7e570000
 int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype, const vitx_ctx_options *options, vitx_ctx **out);
 void vitx_ctx_free(vitx_ctx *c);
 int vitx_ctx_max_batch(const vitx_ctx *c);
+/* The geometry of THIS context (vitx_ctx_options::img_size): what vitx_forward expects is [n][img_size][img_size][3] (ViTSTR: one plane), and
+ * N = (img_size / patch_size)^2 + 1 tokens size the trace, the attention maps and the token features.  0 for NULL. */
+int vitx_ctx_img_size(const vitx_ctx *c);
+int vitx_ctx_tokens(const vitx_ctx *c);
 /* Probability rows per image that vitx_forward / vitx_forward_device write: 1 for a classifier ([n][num_classes]), 25 for a ViTSTR
  * file ([n][25][num_classes], row t = token t of the image; decode with vitx_vitstr_decode).  Images are then ONE grey channel:
  * [img_size][img_size] f32, as vitx_preprocess_vitstr_u8 emits. */
@@ -198,6 +207,41 @@ int vitx_ctx_split(const vitx_ctx *c, int n, int32_t *images, int max_parts);
 int vitx_forward(vitx_ctx *c, const float *imgs_hwc, int n, float *probs, float *logits);
 int vitx_forward_device(vitx_ctx *c, const void *d_imgs_hwc, int n, void *d_probs, void *d_logits, void *stream);
 int vitx_ctx_synchronize(vitx_ctx *c);
+
+/* ---- contexts at another image size: the position table is resampled ------------ */
+/* The file stores pos_embed for ONE grid, [1 + g^2][D] with g = img_size / patch_size (row 0 = class token, then the grid in raster order, x
+ * fastest).  A context created with vitx_ctx_options::img_size keeps the model's weight matrices (contexts of one loaded model at different
+ * sizes share ONE device copy: vitx_ctx_shares_weights, vitx_ctx_weight_bytes unchanged) and owns a table resampled to its own grid, computed
+ * by the device kernel at creation from the f32 table already uploaded; the file's table is left as it is.  vitx_group_* has no options argument:
+ * a group stays at the file's size.  Contexts are square; a size per call on one context is not offered.
+ * Two conventions are in use and differ by 1e-3 .. 5e-2 on a trained table, so both are offered, each equal to CPU torch:
+ *   VITX_POS_BICUBIC     torch.nn.functional.interpolate(mode="bicubic", align_corners=False, antialias=False) -- HuggingFace
+ *                        interpolate_pos_encoding, DINO: cubic convolution with A = -0.75 on 4 x 4 taps, border indices clamped;
+ *   VITX_POS_BICUBIC_AA  the same call with antialias=True -- timm resample_abs_pos_embed: separable, a = -0.5, the support widened by
+ *                        max(in / out, 1), taps outside the grid dropped and the remaining weights normalised to sum 1.
+ * Arithmetic, f32 throughout, the same operations in the same order on host and device with no FMA contraction, so both give the same bits.
+ * Per axis (in source cells, out target cells, target index o), scale = (float)in / (float)out:
+ *   BICUBIC     x = scale * ((float)o + 0.5f) - 0.5f; i0 = floorf(x); t = x - i0; taps i0 - 1 .. i0 + 2 clamped to [0, in - 1] with
+ *               w0 = ((A u - 5A) u + 8A) u - 4A at u = t + 1;  w1 = ((A + 2) t - (A + 3)) t t + 1;  w2 = the w1 form at 1 - t;  w3 = the w0 form at 2 - t;
+ *   BICUBIC_AA  support = scale >= 1 ? 2 scale : 2; inv = scale >= 1 ? 1 / scale : 1; center = scale * ((float)o + 0.5f);
+ *               first = max((int)(center - support + 0.5f), 0); n = min((int)(center + support + 0.5f), in) - first (truncating casts);
+ *               f_j = k(((float)(first + j) - center + 0.5f) * inv) with k(x) = ((a + 2)|x| - (a + 3))|x||x| + 1 for |x| < 1,
+ *               (((|x| - 5)|x| + 8)|x| - 4) a for |x| < 2, else 0;  total = ((f_0 + f_1) + f_2) + ...;  w_j = f_j / total.
+ * Per output cell and channel (horizontal first, then vertical, every sum from the first tap on):
+ *   h_i = ((v(y_i, x_0) wx_0 + v(y_i, x_1) wx_1) + v(y_i, x_2) wx_2) + ...;   out = ((h_0 wy_0 + h_1 wy_1) + h_2 wy_2) + ...
+ * Row 0 is copied bit for bit; equal grids are an exact copy in both conventions.  Grids may be rectangular in these two entry points.
+ * NULL pointers, non-positive sizes, an unknown interp or a table of 2^31 floats or more: VITX_ERR_ARG.
+ *   vitx_pos_embed_resample     host: pos f32 [1 + gy_in * gx_in][D] -> out f32 [1 + gy_out * gx_out][D];
+ *   vitx_op_pos_embed_resample  the gfx950 kernel on device pointers, same arguments and bits; only enqueues on `stream`;
+ *   vitx_model_resize_file      writes path_out = path_in with hparams.img_size = img_size and pos_embed resampled on the host; every other byte of
+ *                               the file is copied through (quantised files included: pos_embed is always f32).  The result is an ordinary model
+ *                               file: this library, the oracle and the reference's own vit_model_load read it.  img_size not a positive multiple
+ *                               of the patch size, an unknown interp or path_out == path_in: VITX_ERR_ARG; a ViTSTR file at another size than its
+ *                               own: VITX_ERR_UNSUPPORTED; an unreadable input: VITX_ERR_IO. */
+enum vitx_pos_interp { VITX_POS_BICUBIC = 0, VITX_POS_BICUBIC_AA = 1 };
+int vitx_pos_embed_resample(const float *pos, int gy_in, int gx_in, int D, int gy_out, int gx_out, int interp, float *out);
+int vitx_op_pos_embed_resample(const void *d_pos, int gy_in, int gx_in, int D, int gy_out, int gx_out, int interp, void *d_out, void *stream);
+int vitx_model_resize_file(const char *path_in, const char *path_out, int img_size, int interp);
 
 /* ---- several GPUs in one process (north_star: batch shards + one RCCL gather) -- */
 /* One context (replicated weights) and one PERSISTENT host thread per listed device (created here, parked between calls).  Images are

@@ -25,6 +25,7 @@ GEMM_AUTO, GEMM_PP, GEMM_AUTO_SPLIT = 0, 1, 2          # vitx_op_gemm_ex `kernel
 ATTN_AUTO, ATTN_SINGLE, ATTN_FLOW, ATTN_PERSIST, ATTN_STREAM = 0, 1, 3, 4, 5   # vitx_op_attention_ex `kernel`
 ATTN_ROLLOUT = 1                # vitx_attn_enable flag
 FEAT_CLS, FEAT_MEAN, FEAT_TOKENS, FEAT_L2 = 1, 2, 4, 8      # vitx_feat_enable flags
+POS_BICUBIC, POS_BICUBIC_AA = 0, 1      # vitx_pos_interp: F.interpolate(mode="bicubic") without / with antialias=True (include/vitx.h)
 
 EXPORTS = [
     "vitx_status_str", "vitx_last_error", "vitx_model_load", "vitx_model_free", "vitx_model_uid", "vitx_model_hparams", "vitx_model_num_labels",
@@ -36,6 +37,7 @@ EXPORTS = [
     "vitx_attn_enable", "vitx_attn_floats", "vitx_attn_images", "vitx_attn_read", "vitx_op_attention_map", "vitx_ctx_graph_launches",
     "vitx_mxfp8_quantize", "vitx_op_quantize_mxfp8", "vitx_op_layernorm_mxfp8", "vitx_op_gemm_mxfp8",
     "vitx_feat_enable", "vitx_feat_floats", "vitx_feat_images", "vitx_feat_read", "vitx_feat_device", "vitx_op_features",
+    "vitx_ctx_img_size", "vitx_ctx_tokens", "vitx_pos_embed_resample", "vitx_op_pos_embed_resample", "vitx_model_resize_file",
 ]
 
 
@@ -46,7 +48,8 @@ class HParams(C.Structure):
 
 class CtxOptions(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("streams", C.c_int32), ("graph", C.c_int32), ("quant_on_host", C.c_int32), ("q4_fused_rows", C.c_int32),
-                ("split_first", C.c_int32), ("no_ln_fusion", C.c_int32), ("ln_test", C.c_int32), ("f16_fast_attention", C.c_int32), ("last_layer_all_rows", C.c_int32)]
+                ("split_first", C.c_int32), ("no_ln_fusion", C.c_int32), ("ln_test", C.c_int32), ("f16_fast_attention", C.c_int32), ("last_layer_all_rows", C.c_int32),
+                ("img_size", C.c_int32), ("pos_interp", C.c_int32)]
 
 
 class ProfEntry(C.Structure):
@@ -155,6 +158,11 @@ def lib():
             L.vitx_feat_read.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t]
             L.vitx_feat_device.restype = C.c_void_p; L.vitx_feat_device.argtypes = [vp]
             L.vitx_op_features.argtypes = [vp, C.c_long, C.c_long, vp, vp, vp, vp, vp, C.c_long, ip, ip, ip, C.c_float, ip, vp]
+        if hasattr(L, "vitx_ctx_img_size"):
+            L.vitx_ctx_img_size.argtypes = [vp]; L.vitx_ctx_tokens.argtypes = [vp]
+            L.vitx_pos_embed_resample.argtypes = [C.POINTER(C.c_float), ip, ip, ip, ip, ip, ip, C.POINTER(C.c_float)]
+            L.vitx_op_pos_embed_resample.argtypes = [vp, ip, ip, ip, ip, ip, ip, vp, vp]
+            L.vitx_model_resize_file.argtypes = [C.c_char_p, C.c_char_p, ip, ip]
         _lib = L
     return _lib
 
@@ -218,6 +226,38 @@ def quantize_file(path_in: str, path_out: str, ftype: int) -> None:
     check(lib().vitx_quantize_file(path_in.encode(), path_out.encode(), ftype), "vitx_quantize_file")
 
 
+def resize_file(path_in: str, path_out: str, img_size: int, interp: int = POS_BICUBIC) -> None:
+    """vitx_model_resize_file: the same model at another img_size (pos_embed resampled on the host, every other byte copied through)."""
+    check(lib().vitx_model_resize_file(path_in.encode(), path_out.encode(), img_size, interp), "vitx_model_resize_file")
+
+
+def _grid(g) -> Tuple[int, int]:
+    return (int(g), int(g)) if np.isscalar(g) else (int(g[0]), int(g[1]))
+
+
+def pos_embed_resample(pos: np.ndarray, grid_out, interp: int = POS_BICUBIC, grid_in=None) -> np.ndarray:
+    """vitx_pos_embed_resample on the host: pos [1 + gy * gx, D] f32 (row 0 = class token) -> [1 + gy' * gx', D].  grid_out (and grid_in) are a
+    side or a (gy, gx) pair; grid_in defaults to the square grid the row count implies."""
+    p = np.ascontiguousarray(pos, np.float32)
+    if p.ndim != 2:
+        raise ValueError(f"pos must be [1 + gy * gx, D], got {p.shape}")
+    if grid_in is None:
+        g = int(round((p.shape[0] - 1) ** 0.5)); grid_in = (g, g)
+    (gy, gx), (oy, ox) = _grid(grid_in), _grid(grid_out)
+    if 1 + gy * gx != p.shape[0]:
+        raise ValueError(f"pos has {p.shape[0]} rows, a {gy} x {gx} grid needs {1 + gy * gx}")
+    out = np.empty((1 + max(oy, 0) * max(ox, 0), p.shape[1]), np.float32)
+    fp = C.POINTER(C.c_float)
+    check(lib().vitx_pos_embed_resample(p.ctypes.data_as(fp), gy, gx, p.shape[1], oy, ox, interp, out.ctypes.data_as(fp)), "vitx_pos_embed_resample")
+    return out
+
+
+def op_pos_embed_resample(d_pos: int, grid_in, D: int, grid_out, interp: int, d_out: int, stream: int = 0) -> None:
+    """vitx_op_pos_embed_resample: the device kernel (device pointers, same arguments and bits as pos_embed_resample; only enqueues)."""
+    (gy, gx), (oy, ox) = _grid(grid_in), _grid(grid_out)
+    check(lib().vitx_op_pos_embed_resample(d_pos, gy, gx, D, oy, ox, interp, d_out, stream or None), "vitx_op_pos_embed_resample")
+
+
 def load_image(path: str) -> np.ndarray:
     """load_image_from_file (vit.cpp:109-127): JPEG / PNG / PPM file -> HWC u8 RGB, decoded by libvitx.so itself."""
     data = C.POINTER(C.c_uint8)(); nx = C.c_int(); ny = C.c_int()
@@ -266,9 +306,10 @@ def preprocess_device(d_u8: int, n: int, nx: int, ny: int, img_size: int, d_out:
     check(lib().vitx_preprocess_u8_device(d_u8, n, nx, ny, img_size, interp, d_out, stream or None), "vitx_preprocess_u8_device")
 
 
-def _check_image_shape(model: "Model", x: np.ndarray) -> None:
-    """[n, S, S, 3] for a classifier, [n, S, S] (one grey plane) for a ViTSTR file: the C ABI reads n * S * S * in_channels floats."""
-    S = model.img_size
+def _check_image_shape(model: "Model", x: np.ndarray, img_size: Optional[int] = None) -> None:
+    """[n, S, S, 3] for a classifier, [n, S, S] (one grey plane) for a ViTSTR file: the C ABI reads n * S * S * in_channels floats.
+    S is the context's img_size (a Group runs at the file's)."""
+    S = model.img_size if img_size is None else img_size
     want = (S, S, 3) if model.in_channels == 3 else (S, S)
     if x.ndim != 1 + len(want) or tuple(x.shape[1:]) != want:
         raise ValueError(f"images must be [n, {', '.join(map(str, want))}] for this model, got {tuple(x.shape)}")
@@ -278,7 +319,8 @@ class Context:
     """Per-(thread, GPU) execution context (vit_state): weights in HBM + activation scratch."""
 
     def __init__(self, model: Model, device: int = 0, max_batch: int = 1, dtype: int = F16, **options):
-        """options: the fields of vitx_ctx_options (streams, graph, quant_on_host, q4_fused_rows, split_first, no_ln_fusion)."""
+        """options: the fields of vitx_ctx_options (streams, graph, quant_on_host, q4_fused_rows, split_first, no_ln_fusion, ...,
+        img_size, pos_interp: a context at another input size than the file's, on the position table resampled to its grid)."""
         self.model = model; self.device = device; self.max_batch = max_batch; self.dtype = dtype
         self._h = C.c_void_p()
         opt = CtxOptions(struct_size=C.sizeof(CtxOptions))
@@ -292,6 +334,11 @@ class Context:
         last = max([i for i, f in enumerate(names) if f != "struct_size" and getattr(opt, f) != 0] + [names.index("f16_fast_attention")])
         opt.struct_size = 4 * (last + 1)
         check(lib().vitx_ctx_create_ex(model._h, device, max_batch, dtype, C.byref(opt), C.byref(self._h)), "vitx_ctx_create_ex")
+        # the geometry of THIS context (vitx_ctx_options::img_size); a build that predates the option runs at the file's
+        L = lib()
+        self.img_size = int(L.vitx_ctx_img_size(self._h)) if hasattr(L, "vitx_ctx_img_size") else model.img_size
+        self.tokens = int(L.vitx_ctx_tokens(self._h)) if hasattr(L, "vitx_ctx_tokens") else (model.img_size // model.hparams.patch_size) ** 2 + 1
+        self.grid = self.img_size // model.hparams.patch_size
 
     def close(self):
         if getattr(self, "_h", None) and self._h:
@@ -306,7 +353,7 @@ class Context:
     def forward(self, imgs_hwc: np.ndarray, want_logits: bool = False):
         """Host arrays in/out (copies + sync): [n,S,S,3] f32 -> probs [n,C] (and logits)."""
         x = np.ascontiguousarray(imgs_hwc, np.float32); n = x.shape[0]
-        _check_image_shape(self.model, x)
+        _check_image_shape(self.model, x, self.img_size)
         R = self.model.seq_len                      # ViTSTR: [n, S, S] grey in, [n, 25, C] out
         probs = np.empty((n, self.model.num_classes) if R == 0 else (n, R, self.model.num_classes), np.float32)
         logits = np.empty_like(probs) if want_logits else None
@@ -327,7 +374,7 @@ class Context:
     def trace_read(self) -> np.ndarray:
         """[L + 1, n_ids, tokens, hidden] f32 of the last forward."""
         hp = self.model.hparams
-        N = (hp.img_size // hp.patch_size) ** 2 + 1
+        N = self.tokens
         out = np.empty((hp.num_hidden_layers + 1, self._trace_n, N, hp.hidden_size), np.float32)
         check(lib().vitx_trace_read(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size), "vitx_trace_read")
         return out
@@ -352,7 +399,7 @@ class Context:
         """Maps of the last forward made with maps on, all of its n images: (cls [n, n_sel, H, N] f32, rollout [n, N] f32 or None).
         Index 0 of a map is the class token, 1.. the patches in raster order (attn_grid reshapes).  `n`, if given, must be that batch."""
         hp = self.model.hparams
-        N, H = (hp.img_size // hp.patch_size) ** 2 + 1, hp.num_attention_heads
+        N, H = self.tokens, hp.num_attention_heads
         fpi = lib().vitx_attn_floats(self._h)
         sel, roll = getattr(self, "_attn_layers", []), getattr(self, "_attn_rollout", False)
         assert fpi == len(sel) * H * N + (N if roll else 0)
@@ -368,9 +415,8 @@ class Context:
         return cls, (out[:, len(sel) * H * N:].copy() if roll else None)
 
     def attn_grid(self, m: np.ndarray) -> np.ndarray:
-        """[..., N] map -> [..., g, g] patch grid (g = img_size / patch_size): drops index 0 (the class token)."""
-        hp = self.model.hparams
-        g = hp.img_size // hp.patch_size
+        """[..., N] map -> [..., g, g] patch grid (g = the context's img_size / patch_size): drops index 0 (the class token)."""
+        g = self.grid
         return np.asarray(m)[..., 1:].reshape(*np.shape(m)[:-1], g, g)
 
     def feat_enable(self, cls: bool = True, mean: bool = False, tokens: bool = False, l2: bool = False, layers=None) -> None:
@@ -398,7 +444,7 @@ class Context:
         """Features of the last forward made with features on, all of its n images: {layer: {"cls": [n, D], "mean": [n, D],
         "tokens": [n, N - 1, D]}} f32 with the selected kinds only.  `n`, if given, must be that batch."""
         hp = self.model.hparams
-        N, D = (hp.img_size // hp.patch_size) ** 2 + 1, hp.hidden_size
+        N, D = self.tokens, hp.hidden_size
         sel, flags = getattr(self, "_feat_layers", []), getattr(self, "_feat_flags", 0)
         fpi = lib().vitx_feat_floats(self._h)
         have = lib().vitx_feat_images(self._h)

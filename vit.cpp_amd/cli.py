@@ -5,6 +5,7 @@ directory-walk accuracy harness:
     python vit_cli.py -m model.gguf --dir imagenet_val/ [--batch 256]       # top-1 over <dir>/<label>/*.jpg
     python vit_cli.py -m model.gguf -i image.jpg --attn-map map.pgm [--attn-kind rollout|last]   # + where the model looked (P5 picture)
     python vit_cli.py -m model.gguf (-i image.jpg | --dir DIR) --embed out.npy [--embed-kind cls|mean|tokens] [--embed-l2]   # + the embeddings
+    python vit_cli.py -m model.gguf ... --img-size 384 [--pos-interp bicubic|bicubic-aa]   # run at another input size than the file's
 
 Same flags as vit_params_parse (vit.cpp:955-1002: -m -i -t -k -s -e; -t, -s and -e are accepted and ignored exactly
 as the reference's forward ignores seed and eps), same stdout lines (" > label : 0.xx", vit.cpp:1062-1067) and the
@@ -62,6 +63,12 @@ def main(argv: List[str] | None = None) -> int:
     ap.add_argument("--embed-kind", default="cls", choices=["cls", "mean", "tokens"],
                     help="cls: the class-token embedding [D]; mean: the mean of the patch features [D]; tokens: the patch features [N-1, D]")
     ap.add_argument("--embed-l2", action="store_true", help="divide the cls / mean embedding by its Euclidean norm")
+    ap.add_argument("--img-size", type=int, default=0, metavar="N",
+                    help="run at N x N instead of the file's img_size (a multiple of the patch size): the position table is resampled to the new grid; "
+                         "the preprocess, the --attn-map picture and the --embed shapes follow")
+    ap.add_argument("--pos-interp", default="bicubic", choices=["bicubic", "bicubic-aa"],
+                    help="with --img-size: bicubic = F.interpolate(mode='bicubic') (HuggingFace interpolate_pos_encoding, DINO); "
+                         "bicubic-aa = the same with antialias=True (timm resample_abs_pos_embed)")
     a = ap.parse_args(argv)
     if a.attn_map and a.dir is not None:
         ap.error("--attn-map takes the single image of -i, not --dir")
@@ -82,7 +89,11 @@ def main(argv: List[str] | None = None) -> int:
     t_load = time.perf_counter() - t_main
     dt = {"f16": binding.F16, "bf16": binding.BF16, "mxfp8": binding.MXFP8}[a.dtype]
     interp = binding.BICUBIC if a.interp == "bicubic" else binding.BILINEAR
-    S = model.img_size
+    if a.img_size < 0:
+        print(f"main: --img-size {a.img_size} is not a positive multiple of the patch size {model.hparams.patch_size}", file=sys.stderr)
+        return 1
+    S = a.img_size or model.img_size                     # the context's size: preprocess, maps and features follow it
+    geometry = dict(img_size=a.img_size, pos_interp=binding.POS_BICUBIC_AA if a.pos_interp == "bicubic-aa" else binding.POS_BICUBIC) if a.img_size else {}
 
     if a.dir is None:
         try:
@@ -93,7 +104,11 @@ def main(argv: List[str] | None = None) -> int:
         print(f"main: loaded image '{a.inp}' ({img0.shape[1]} x {img0.shape[0]})", file=sys.stderr)
         img1 = binding.preprocess(img0, S, interp)
         print(f"processed, out dims : ({S} x {S})", file=sys.stderr)
-        ctx = binding.Context(model, device=a.device, max_batch=1, dtype=dt)
+        try:
+            ctx = binding.Context(model, device=a.device, max_batch=1, dtype=dt, **geometry)
+        except binding.VitxError as e:
+            print(f"main: failed to create the context: {e}", file=sys.stderr)
+            return 1
         if a.attn_map:
             L = model.hparams.num_hidden_layers
             ctx.attn_enable([] if a.attn_kind == "rollout" else [L - 1], rollout=a.attn_kind == "rollout")
@@ -132,7 +147,11 @@ def main(argv: List[str] | None = None) -> int:
     if not files:
         print(f"main: no <label>/<image> files under '{a.dir}' match the model's labels", file=sys.stderr)
         return 1
-    ctx = binding.Context(model, device=a.device, max_batch=min(a.batch, len(files)), dtype=dt)
+    try:
+        ctx = binding.Context(model, device=a.device, max_batch=min(a.batch, len(files)), dtype=dt, **geometry)
+    except binding.VitxError as e:
+        print(f"main: failed to create the context: {e}", file=sys.stderr)
+        return 1
     if a.embed:
         ctx.feat_enable(**feat)
     rows = []

@@ -134,18 +134,37 @@ def main(argv=None) -> int:
     ap.add_argument("--timm-state-dict", action="store_true", help="`model` is a torch-saved timm VisionTransformer state_dict (.pth); no timm import needed")
     ap.add_argument("--heads", type=int, default=0, help="attention heads of a timm checkpoint (inferred only for the widths of released timm ViTs; required otherwise)")
     ap.add_argument("--labels", default=None, help="JSON file {class id: label} for a timm checkpoint (default: none are written)")
+    ap.add_argument("--img-size", type=int, default=0, metavar="N",
+                    help="write the file at N x N instead of the checkpoint's size: pos_embed is resampled (vitx_model_resize_file), nothing else changes")
+    ap.add_argument("--pos-interp", default="bicubic", choices=["bicubic", "bicubic-aa"],
+                    help="with --img-size: F.interpolate(mode='bicubic') without (HuggingFace, DINO) or with antialias=True (timm)")
     a = ap.parse_args(argv)
+
+    def resized(hp):
+        """The converted file is written at the checkpoint's size first, then replaced by its --img-size version."""
+        if a.img_size and a.img_size != hp.img_size:
+            import os
+            from . import binding
+            tmp = a.out + f".src{os.getpid()}"
+            os.replace(a.out, tmp)
+            try:
+                binding.resize_file(tmp, a.out, a.img_size, binding.POS_BICUBIC_AA if a.pos_interp == "bicubic-aa" else binding.POS_BICUBIC)
+            finally:
+                os.remove(tmp)
+            hp.img_size = a.img_size
+        return hp
+
     if a.timm_state_dict:
         import json
         import torch
         sd = torch.load(a.model, map_location="cpu", weights_only=True)
         labels = {int(k): str(v) for k, v in json.load(open(a.labels)).items()} if a.labels else None
-        hp = convert_timm_state_dict(sd, a.out, a.ftype, heads=a.heads, id2label=labels)
+        hp = resized(convert_timm_state_dict(sd, a.out, a.ftype, heads=a.heads, id2label=labels))
         print(f"wrote {a.out}: hidden {hp.hidden_size}, layers {hp.num_hidden_layers}, heads {hp.num_attention_heads}, classes {hp.num_classes}, patch {hp.patch_size}, img {hp.img_size}, ftype {a.ftype}")
         return 0
     import transformers
     m = transformers.ViTForImageClassification.from_pretrained(a.model).eval()
-    hp = convert_hf_model(m, a.out, a.ftype, vitstr=a.vitstr)
+    hp = resized(convert_hf_model(m, a.out, a.ftype, vitstr=a.vitstr))
     print(f"wrote {a.out}: hidden {hp.hidden_size}, layers {hp.num_hidden_layers}, heads {hp.num_attention_heads}, classes {hp.num_classes}, patch {hp.patch_size}, img {hp.img_size}, ftype {a.ftype}")
     return 0
 

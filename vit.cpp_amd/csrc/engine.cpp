@@ -100,6 +100,8 @@ struct vitx_ctx {
         }
     };
     std::shared_ptr<WeightSet> wset;     // never null once the context exists
+    const float *pos = nullptr;          // [N][D] position table the patch embedding adds: wset->pos, or pos_own when img_size differs from the file's
+    float *pos_own = nullptr;            // the table resampled to this context's grid (vitx_ctx_options::img_size, pos_interp); in `allocs`
     bool weights_shared = false;         // this context found the set already uploaded (vitx_ctx_shares_weights)
     // quantised files: vitx_ctx_options::quant_on_host restores the r01 behaviour (expand once on the host at upload, 16 bits per weight in HBM)
     bool quant_on_device = true;
@@ -403,6 +405,13 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
         memcpy(&opt, opt_in, (size_t)opt_in->struct_size);
         if (opt.streams < 0 || opt.streams > 4 || opt.q4_fused_rows < 0 || opt.split_first < 0 || (opt.last_layer_all_rows & ~1)) { set_error("vitx_ctx_create_ex: option out of range"); return VITX_ERR_ARG; }
     }
+    // geometry of this context (vitx_ctx_options::img_size): checked before any device is touched
+    if (opt.pos_interp != VITX_POS_BICUBIC && opt.pos_interp != VITX_POS_BICUBIC_AA) { set_error("vitx_ctx_create_ex: unknown pos_interp %d (0 bicubic, 1 bicubic with antialias)", opt.pos_interp); return VITX_ERR_ARG; }
+    if (opt.img_size < 0 || (opt.img_size > 0 && (m->hp.patch_size <= 0 || opt.img_size % m->hp.patch_size))) {
+        set_error("vitx_ctx_create_ex: img_size %d is not a positive multiple of the patch size %d", opt.img_size, m->hp.patch_size); return VITX_ERR_ARG;
+    }
+    const int img_size = opt.img_size > 0 ? opt.img_size : m->hp.img_size;
+    if (m->in_chans == 1 && img_size != m->hp.img_size) { set_error("vitx_ctx_create_ex: a ViTSTR context stays at the file's img_size (%d)", m->hp.img_size); return VITX_ERR_UNSUPPORTED; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("vitx_ctx_create: no HIP device available (this engine has no CPU fallback)"); return VITX_ERR_HIP; }
     if (device < 0 || device >= ndev) { set_error("vitx_ctx_create: device %d out of range (%d devices)", device, ndev); return VITX_ERR_ARG; }
@@ -416,7 +425,7 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
     if (!c) return VITX_ERR_NOMEM;
     c->model = m; c->hp = hp; c->device = device; c->max_batch = max_batch;
     c->mx = dtype == VITX_MXFP8; c->dtype = c->mx ? VITX_BF16 : dtype;      // everything but the MX GEMMs runs as in a VITX_BF16 context
-    c->D = hp.hidden_size; c->L = hp.num_hidden_layers; c->H = hp.num_attention_heads; c->C = hp.num_classes; c->P = hp.patch_size; c->S = hp.img_size;
+    c->D = hp.hidden_size; c->L = hp.num_hidden_layers; c->H = hp.num_attention_heads; c->C = hp.num_classes; c->P = hp.patch_size; c->S = img_size;
     c->Cin = m->in_chans; c->R = m->in_chans == 1 ? VITX_VITSTR_SEQ_LEN : 1;
     c->g = c->S / c->P; c->N = c->g * c->g + 1; c->Kpe = c->Cin * c->P * c->P; c->Kpe_pad = round_up(c->Kpe, 64);
     if (c->N < c->R) { set_error("vitx_ctx_create: a ViTSTR head reads %d tokens, this model has %d (img_size %d, patch_size %d)", c->R, c->N, c->S, c->P); return VITX_ERR_UNSUPPORTED; }
@@ -500,6 +509,14 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
         wreg[wkey] = c->wset;
     }
     wlock.unlock();
+    // the position table of THIS context: the set's (the file's) at the file's size, else resampled on the device into scratch the context owns
+    c->pos = c->wset->pos;
+    if (c->S != hp.img_size) {
+        const int g_in = hp.img_size / hp.patch_size;
+        if ((rc = c->dmalloc((void **)&c->pos_own, (size_t)c->N * D * 4, false))) return rc;
+        HIP_TRY(launch_pos_resample(c->wset->pos, g_in, g_in, D, c->g, c->g, opt.pos_interp, c->pos_own, c->stream));
+        c->pos = c->pos_own;                 // (the hipDeviceSynchronize at the end of the creation covers the launch)
+    }
 
     // sub-batch slices (vitx_ctx_options::streams; 1 = single stream).  Small contexts stay single-slice.
     int ns = opt.streams > 0 ? opt.streams : 2;
@@ -580,6 +597,8 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
 
 void vitx_ctx_free(vitx_ctx *c) { delete c; }
 int vitx_ctx_max_batch(const vitx_ctx *c) { return c ? c->max_batch : 0; }
+int vitx_ctx_img_size(const vitx_ctx *c) { return c ? c->S : 0; }
+int vitx_ctx_tokens(const vitx_ctx *c) { return c ? c->N : 0; }
 static void split_batch(const vitx_ctx *c, int n, int ns, int *m);
 int vitx_ctx_split(const vitx_ctx *c, int n, int32_t *images, int max_parts) {
     if (!c || !images || max_parts <= 0 || n <= 0 || n > c->max_batch) return 0;
@@ -671,7 +690,7 @@ static int forward_slice(vitx_ctx *c, vitx_ctx::Slice &sl, hipStream_t st, const
     int rc;
     {
         ProfScope ps(c, st, PC_GEMM_PATCH, 2.0 * Mp_real * (double)D * c->Kpe, (double)n * c->S * c->S * c->Cin * 4 + (double)M_real * D * 4);
-        HIP_TRY(launch_patch_embed(dt, (const float *)d_imgs, ws.pe_w, ws.pe_b, ws.pos, ws.cls, sl.X, n, c->S, c->P, c->Cin, D, round_up(D, tn), c->Kpe_pad, st));
+        HIP_TRY(launch_patch_embed(dt, (const float *)d_imgs, ws.pe_w, ws.pe_b, c->pos, ws.cls, sl.X, n, c->S, c->P, c->Cin, D, round_up(D, tn), c->Kpe_pad, st));
     }
     if (!c->trace_ids.empty() && (rc = trace(0))) return rc;
     // Quantised matrices (block form in HBM): a q4_0 GEMM with few rows expands the blocks in its own LDS-fill path; everything else

@@ -165,6 +165,8 @@ hipError_t launch_rollout_row(const float *cls, long cls_stride, const float *r,
 // Every width of VITX_LN_WIDTHS; pointers 16-byte aligned, strides multiples of 4 floats.
 hipError_t launch_features(const float *x, long row_stride, long img_stride, const float *w, const float *b, float *cls, float *mean, float *tokens,
                            long out_img_stride, int n_img, int N, int D, float eps, bool l2, hipStream_t stream);
+// pos [1 + gy_in * gx_in][D] f32 -> out [1 + gy_out * gx_out][D] f32 (pos_resample.hip; the arithmetic: pos_resample.h); only enqueues
+hipError_t launch_pos_resample(const float *pos, int gy_in, int gx_in, int D, int gy_out, int gx_out, int interp, float *out, hipStream_t stream);
 bool attention_supports(int N, int D, int H);     // any token count; head_dim 64 (tuned kernels) or any other multiple of 8 up to 128 (generic kernel)
 bool attention_single_pass_supports(int N);       // instantiation table of the register-resident kernel
 bool layernorm_supports(int D);

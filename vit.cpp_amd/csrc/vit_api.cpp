@@ -59,12 +59,19 @@ bool vit_image_preprocess(const image_u8 &img, image_f32 &res, const vit_hparams
 
 // The reference's vit_state carries no weights and can be reused with any model; ours caches a context that does, so the cache
 // is keyed on the unique id of the parsed model it was built from (vit_model_load frees and replaces that handle on every call).
+// The input side a state's context takes: vit_state::img_size, or the file's when that is 0
+static int state_img_size(const vit_model &model, const vit_state &state) { return state.img_size > 0 ? state.img_size : model.hparams.img_size; }
+
 static int ensure_ctx(const vit_model &model, vit_state &state, int n) {
-    if (state.ctx && state.ctx_model_uid == vitx_model_uid(model.handle) && vitx_ctx_max_batch(state.ctx) >= n) return VITX_OK;
+    const int S = state_img_size(model, state);
+    const bool same_geometry = state.ctx && vitx_ctx_img_size(state.ctx) == S && (S == model.hparams.img_size || state.ctx_pos_interp == state.pos_interp);
+    if (same_geometry && state.ctx_model_uid == vitx_model_uid(model.handle) && vitx_ctx_max_batch(state.ctx) >= n) return VITX_OK;
     vitx_ctx_free(state.ctx); state.ctx = nullptr; state.ctx_model_uid = 0;
     state.max_batch = std::max(state.max_batch, n);
-    const int rc = vitx_ctx_create(model.handle, state.device, state.max_batch, state.dtype, &state.ctx);
-    if (rc == VITX_OK) state.ctx_model_uid = vitx_model_uid(model.handle);
+    vitx_ctx_options opt{};
+    opt.struct_size = (int32_t)sizeof(opt); opt.img_size = state.img_size; opt.pos_interp = state.pos_interp;
+    const int rc = vitx_ctx_create_ex(model.handle, state.device, state.max_batch, state.dtype, &opt, &state.ctx);
+    if (rc == VITX_OK) { state.ctx_model_uid = vitx_model_uid(model.handle); state.ctx_pos_interp = state.pos_interp; }
     return rc;
 }
 
@@ -73,10 +80,10 @@ int vit_predict_batch(const vit_model &model, vit_state &state, const image_f32 
     predictions.clear();
     if (!model.handle || !imgs || n <= 0) { fprintf(stderr, "%s: invalid argument\n", __func__); return 1; }
     if (vitx_model_seq_len(model.handle) > 0) { fprintf(stderr, "%s: this is a ViTSTR model (one-channel patch kernel): use vitstr_predict\n", __func__); return 1; }
-    const int S = model.hparams.img_size, C = model.hparams.num_classes;
+    const int S = state_img_size(model, state), C = model.hparams.num_classes;
     for (int i = 0; i < n; ++i)
         if (imgs[i].nx != S || imgs[i].ny != S || imgs[i].data.size() != (size_t)3 * S * S) {      // GGML_ASSERT at vit.cpp:757
-            fprintf(stderr, "%s: image %d is %dx%d, model expects %dx%d\n", __func__, i, imgs[i].nx, imgs[i].ny, S, S);
+            fprintf(stderr, "%s: image %d is %dx%d, this state expects %dx%d\n", __func__, i, imgs[i].nx, imgs[i].ny, S, S);
             abort();
         }
     if (ensure_ctx(model, state, n) != VITX_OK) { fprintf(stderr, "%s: failed to encode image: %s\n", __func__, vitx_last_error()); return 1; }
@@ -112,10 +119,10 @@ int vit_embed_batch(const vit_model &model, vit_state &state, const image_f32 *i
     out.clear();
     if (!model.handle || !imgs || n <= 0 || !flags) { fprintf(stderr, "%s: invalid argument\n", __func__); return 1; }
     if (vitx_model_seq_len(model.handle) > 0) { fprintf(stderr, "%s: this is a ViTSTR model: it has no image embedding\n", __func__); return 1; }
-    const int S = model.hparams.img_size, C = model.hparams.num_classes;
+    const int S = state_img_size(model, state), C = model.hparams.num_classes;
     for (int i = 0; i < n; ++i)
         if (imgs[i].nx != S || imgs[i].ny != S || imgs[i].data.size() != (size_t)3 * S * S) {
-            fprintf(stderr, "%s: image %d is %dx%d, model expects %dx%d\n", __func__, i, imgs[i].nx, imgs[i].ny, S, S);
+            fprintf(stderr, "%s: image %d is %dx%d, this state expects %dx%d\n", __func__, i, imgs[i].nx, imgs[i].ny, S, S);
             return 1;
         }
     if (ensure_ctx(model, state, n) != VITX_OK) { fprintf(stderr, "%s: failed to create the context: %s\n", __func__, vitx_last_error()); return 1; }

@@ -58,6 +58,12 @@ struct vit_state {                        // vit.h:72-80: per-caller mutable scr
     int device = 0;
     int max_batch = 1;                    // capacity of ctx; grown on demand by vit_predict_batch
     int dtype = VITX_F16;                 // MFMA operand type (VITX_F16 reproduces the reference's rounding); VITX_MXFP8: experimental, slower than bf16
+    int img_size = 0;                     // 0 = the file's; else the side of the images THIS state takes (a positive multiple of the patch size): the context
+                                          // runs on the file's position table resampled to that grid (vitx_ctx_options::img_size).  vit_predict, vit_predict_batch
+                                          // and vit_embed_batch check their images against this size; preprocess to it by passing vit_image_preprocess a copy of
+                                          // the hparams with img_size set.  Changing it (or pos_interp) replaces the context on the next call.  Not for ViTSTR.
+    int pos_interp = VITX_POS_BICUBIC;    // enum vitx_pos_interp: which bicubic convention resamples the table (include/vitx.h)
+    int ctx_pos_interp = 0;               // the pos_interp `ctx` was created with
     std::vector<float> prediction;        // class probabilities of the last call ([n][num_classes])
     vit_state() = default;
     vit_state(const vit_state &) = delete;
@@ -79,6 +85,7 @@ struct vit_params {                       // vit.h:105-113
 
 bool load_image_from_file(const std::string &fname, image_u8 &img);                                    // vit.h:118 (stbi_load replaced by csrc/image_decode.cpp)
 bool vit_model_load(const std::string &fname, vit_model &model);                                       // vit.h:120
+// resizes to params.img_size, whatever it is: for a state at another size than the file's, pass a copy of model.hparams with img_size = state.img_size
 bool vit_image_preprocess(const image_u8 &img, image_f32 &res, const vit_hparams &params);            // vit.h:119
 int vit_predict(const vit_model &model, vit_state &state, const image_f32 img1, const vit_params &params,
                 std::vector<std::pair<float, int>> &predictions);                                      // vit.h:122
