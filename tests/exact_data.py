@@ -1,12 +1,15 @@
-"""Data generators and CPU-side conditions of the exact and hostile-data kernel tests (test_gpu_exact.py, test_gpu_hostile.py).
+"""Data generators and CPU-side conditions of the exact and hostile-data kernel tests (test_gpu_exact.py, test_gpu_hostile.py,
+test_gpu_attention.py).
 
 Nothing here touches a GPU or libvitx.so: tests/test_cpu_exact_data.py checks every condition the GPU tests rely on.
 
 "Exact" data makes a kernel's correct result unique, so a test needs no tolerance and can compare every element of an output buffer:
   * GEMM operands are small integers (times a power of two): every product and every partial sum is an integer (times that power of two)
     far below 2^24, so f32 accumulation is exact IN ANY ORDER;
-  * attention operands route every query to one key by a score gap so large that every other probability vanishes in f32.
+  * attention operands route every query to one key by a score gap so large that every other probability vanishes in f32, or make every
+    key of an item the same vector, so that every numerator is exactly 1 and the sums are integers ("flat": every key weighs 1 / N).
 "Hostile" data keeps a float64 reference and a tolerance, but has the shape of a trained model's residual stream instead of randn.
+"Spread" / "peaked" attention data is randn; its gates are derived from the float64 reference and an emulation of the definition.
 """
 from __future__ import annotations
 
@@ -213,7 +216,7 @@ ATTN_CASES = {
     "auto": [(2, 197, 3, 64), (3, 17, 2, 64), (1, 257, 2, 64), (1, 577, 2, 64), (2, 50, 1, 64), (1, 785, 2, 64)],
     "single": [(2, 197, 3, 64), (3, 17, 2, 64), (1, 257, 2, 64), (1, 577, 2, 64), (2, 224, 1, 64), (1, 608, 1, 64)],
     "flow": [(2, 197, 3, 64), (1, 577, 2, 64), (2, 300, 1, 64), (1, 785, 2, 64), (3, 17, 2, 64), (1, 4097, 1, 64)],
-    "persist": [(45, 197, 12, 64), (3, 208, 2, 64), (2, 224, 3, 64), (2, 193, 3, 64)],
+    "persist": [(45, 197, 12, 64), (3, 208, 2, 64), (2, 224, 3, 64), (2, 193, 3, 64), (2, 215, 3, 64)],
     "stream": [(1, 577, 2, 64), (2, 197, 3, 64), (1, 785, 2, 64), (2, 300, 1, 64), (3, 225, 2, 64), (1, 1025, 1, 64), (2, 129, 2, 64), (9, 65, 1, 64),
                (2, 64, 3, 64), (1, 1, 1, 64), (4, 33, 2, 64), (1, 31, 1, 64), (1, 4097, 1, 64)],
     "precise": [(2, 197, 3, 64), (1, 577, 2, 64), (3, 17, 2, 64), (1, 1, 1, 64), (2, 65, 2, 64), (1, 128, 1, 64), (1, 129, 3, 64), (1, 257, 2, 64),
@@ -247,6 +250,235 @@ def attention64(qkv: np.ndarray, n_img: int, N: int, H: int, hd: int) -> np.ndar
     p = np.exp(s - s.max(axis=-1, keepdims=True))
     p /= p.sum(axis=-1, keepdims=True)
     return (p @ v).transpose(0, 2, 1, 3).reshape(n_img * N, H * hd)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Attention with a flat softmax: every key carries the same weight, and the output is still exact
+# ------------------------------------------------------------------------------------------------------------------
+FLAT_SIGNS = (-1, 0, 1)
+
+
+def flat_gain(hd: int) -> int:
+    return int(round(48.0 / np.sqrt(hd)))
+
+
+def flat_qkv(n_img: int, N: int, H: int, hd: int, sign: int, seed: int):
+    """qkv [n_img * N][3 * H * hd] f32 (exact in f16 and bf16) and c [n_img][H][hd]: the one correct output is c in every row.
+    Per (image, head): every key is the same +-1 vector kappa; q_i = sign * g * kappa on a random half of the columns (another half for
+    every query), g = flat_gain(hd), so every raw score of the item is the integer sign * g * hd / 2 (about sign * 24 after the scale)
+    whatever the summation order, s - max = 0 and every numerator is 1; v_j = c + z_j with integer c in 1..3 per column and integer
+    16 <= |z_j| <= 64 whose column sums vanish (pairs +a, -a; an odd N holds one triple a, b, -(a + b) with a, b <= 32), rows shuffled
+    per column.  All partial sums of numerators and of numerator * v are integers below 2^24: sum p v = N c and sum p = N exactly.
+    N = 1 leaves z = 0 (the only sum-free choice)."""
+    rng = np.random.default_rng(seed)
+    g = flat_gain(hd)
+    qkv = np.zeros((n_img, N, 3, H, hd), np.float32)
+    c = np.empty((n_img, H, hd), np.float32)
+    for b in range(n_img):
+        for h in range(H):
+            kappa = rng.integers(0, 2, hd) * 2.0 - 1.0
+            half = np.argsort(rng.random((N, hd)), axis=1) < hd // 2          # hd / 2 columns of every query
+            cc = ((np.arange(hd) + rng.integers(0, 3)) % 3 + 1.0)[rng.permutation(hd)]
+            z = np.zeros((N, hd))
+            n_pair, odd = (N - 3) // 2 if N % 2 and N >= 3 else N // 2, N % 2 and N >= 3
+            a = rng.integers(16, 65, (n_pair, hd))
+            parts = [a, -a]
+            if odd:
+                t = rng.integers(16, 33, (2, hd)) * rng.choice([-1, 1], (1, hd))
+                parts.append(np.concatenate([t, -t.sum(axis=0, keepdims=True)]))
+            if N >= 2:
+                z = rng.permuted(np.concatenate(parts), axis=0)
+            qkv[b, :, 0, h] = sign * g * kappa * half; qkv[b, :, 1, h] = kappa; qkv[b, :, 2, h] = cc + z
+            c[b, h] = cc
+    return qkv.reshape(n_img * N, 3 * H * hd), c
+
+
+def flat_expected(c: np.ndarray, N: int) -> np.ndarray:
+    """[n_img * N][H * hd]: c of the row's image in every row."""
+    n_img, H, hd = c.shape
+    return np.repeat(c.reshape(n_img, 1, H * hd), N, axis=1).reshape(n_img * N, H * hd)
+
+
+# family -> [(n_img, N, H, head_dim)] of the flat, spread and peaked cases: flat data needs no score gap, so every token count runs.  Each
+# family meets N % 16 in {15, 0, 1} and N % 64 in {63, 0, 1} inside its own range with three images (first, middle, last) and two heads:
+#   single   instantiated for ceil(N / 32) in {1 .. 7, 9, 19}: 1 .. 224, 257 .. 288, 577 .. 608 tokens (kAttnNkt, kernels.hip);
+#   persist  193 .. 224 tokens, 13 sixteen-key tiles up to 208 and 14 above; 215 = a partly filled fourteenth tile, odd head count;
+#   flow / stream / precise  any count, 64-key chunks (precise: the persistent build for 193 .. 224, the two-pass build elsewhere);
+#   auto     both sides of 192 | 193 (single -> persistent), 208 | 209 (13 -> 14 tiles), 224 | 225 (persistent -> pipelined),
+#            256 | 257 (pipelined -> single), 288 | 289 (single -> pipelined);
+#   generic  head dims 8 .. 128 other than 64, 16-key tiles, 32-key steps, 64-query workgroups;  cls / map  any count.
+def _three(ns, H=2, hd=64):
+    return [(3, n, H, hd) for n in ns]
+
+
+_CHUNK_EDGES = (15, 16, 17, 63, 64, 65, 127, 128, 129, 191, 192, 193, 255, 256, 257)
+FLAT_CASES = {
+    "auto": _three((192, 193, 208, 209, 224, 225, 256, 257, 288, 289, 577)) + [(2, 1, 2, 64)],
+    "single": _three((15, 16, 17, 63, 64, 65, 127, 128, 129, 191, 192, 193, 223, 224, 257, 271, 272, 273, 287, 288, 577, 591, 592, 593, 607, 608)),
+    "flow": _three(_CHUNK_EDGES + (575, 576, 577, 1023, 1024, 1025)) + [(2, 4097, 2, 64)],
+    "persist": _three((193, 197, 207, 208, 209, 223, 224)) + [(2, 215, 3, 64)],
+    "stream": _three((1,) + _CHUNK_EDGES + (577, 1023, 1024, 1025)) + [(2, 4097, 2, 64)],
+    "precise": _three((1,) + _CHUNK_EDGES + (197, 207, 208, 209, 223, 224, 225, 577, 1023, 1024, 1025)) + [(2, 215, 3, 64), (2, 4097, 2, 64)],
+    "generic": _three((15, 16, 17, 197), hd=32) + _three((63, 64, 65, 257), hd=80) + _three((127, 128, 129), hd=96) + _three((31, 32, 33, 193), hd=128)
+               + [(3, 50, 2, 16), (3, 49, 3, 8), (2, 1, 2, 32)],
+    "cls": _three((1, 15, 16, 17, 255, 256, 257, 1025)) + _three((63, 64, 65), 4, 32) + _three((127, 128, 129), hd=128) + [(3, 197, 12, 64), (3, 577, 2, 16), (2, 4097, 2, 64)],
+    "map": _three((15, 16, 63, 257)) + [(3, 17, 2, 32), (3, 64, 2, 128), (3, 65, 2, 80), (3, 197, 3, 64), (2, 577, 2, 64), (2, 1, 2, 64), (2, 1024, 2, 64)],
+}
+# Spread and peaked data run the same lists without the counts below 15 tokens: with one key the softmax is the constant 1, no scale can
+# move it, and condition (c) of test_cpu_exact_data.py (a 2 % scale fault must break a gate) has nothing to act on.  The flat cases keep N = 1.
+SPREAD_MIN_N = 15
+SPREAD_CASES = {f: [c for c in cs if c[1] >= SPREAD_MIN_N] for f, cs in FLAT_CASES.items() if f != "map"}
+SPREAD_MAX_N = 1025            # above it only "peaked" runs: see spread_kinds
+CPU_FULL_MAX_N = 1025          # test_cpu_exact_data.py: above it the float64 conditions take the first 512 query rows of every item (minutes otherwise)
+
+
+def spread_kinds(N: int):
+    """The data kinds of a token count.  One key of 4097 carries 2.4e-4 of a spread row's weight, a sixteenth of bf16's unit round-off:
+    no gate that lets the bf16 definition's own rounding through can see it leak (measured on the float64 reference: 0.26 of the bound,
+    3.0 times the emulation's mean), so above 1025 tokens the data is sharpened instead of the condition being dropped."""
+    return ("spread", "peaked") if N <= SPREAD_MAX_N else ("peaked",)
+
+
+def spread_qkv(n_img: int, N: int, H: int, hd: int, seed: int, kind: str = "spread") -> np.ndarray:
+    """randn * 0.8 q, k, v (a softmax over hundreds of keys); "peaked": q times 3 (an effective support of ten or so keys)."""
+    D = H * hd
+    x = (np.random.default_rng(seed).standard_normal((n_img * N, 3 * D)) * 0.8).astype(np.float32)
+    if kind == "peaked":
+        x[:, :D] *= 3.0
+    elif kind != "spread":
+        raise ValueError(kind)
+    return x
+
+
+# The gates of the spread / peaked tests (test_gpu_attention.py) and everything they are made of.  torch, on whatever device the operands
+# are on: the GPU tests compute reference, bound and emulation in float64 / f32 on the device, the CPU conditions run the same code.
+ATTN_K = 1                     # the k of the bound: smallest of 1, 2, 4 that leaves the emulation below half of the bound on every case
+ATTN_MEAN_FACTOR = 3.0         # head-room of the mean gate over the emulation's own mean error: summation order, MFMA accumulation
+ATTN_UNIT = {"f16": 2.0 ** -11, "bf16": 2.0 ** -8}       # unit round-off of the type numerators and exponent arguments are rounded to
+ATTN_ULP = {"f16": 2.0 ** -10, "bf16": 2.0 ** -7}        # one ulp of the output type, relative
+LOG2E = 1.44269504088896340736
+
+
+def heads_of(t, n_img: int, N: int, H: int, hd: int):
+    """[n_img * N][3 * H * hd] -> q, k, v [n_img * H][N][hd]"""
+    x = t.reshape(n_img, N, 3, H, hd).permute(2, 0, 3, 1, 4).reshape(3, n_img * H, N, hd)
+    return x[0], x[1], x[2]
+
+
+def rows_of(o, n_img: int, N: int, H: int, hd: int):
+    """[n_img * H][N][hd] -> [n_img * N][H * hd]"""
+    return o.reshape(n_img, H, N, hd).permute(0, 2, 1, 3).reshape(n_img * N, H * hd)
+
+
+def attention_ref(q, k, v, scale: float, want_bound: bool = False):
+    """float64 softmax attention of q [B][Nq][hd] against k, v [B][Nk][hd]; with want_bound also
+    cond[b][i][d] = sum_j w_ij (2 + |s_ij - max_i|) |v_jd - out_id|: the first-order effect on out of a relative error on every weight and
+    an absolute error proportional to |s - max| on every exponent argument (a constant v costs nothing: only its spread is charged)."""
+    import torch
+    q, k, v = q.double(), k.double(), v.double()
+    s = q @ k.transpose(1, 2) * scale
+    d = s - s.amax(dim=2, keepdim=True)
+    w = torch.exp(d)
+    w = w / w.sum(dim=2, keepdim=True)
+    out = w @ v
+    if not want_bound:
+        return out
+    a = w * (2.0 + d.abs())
+    del s, d, w
+    B, Nq, hd = out.shape
+    cond = torch.empty_like(out)
+    step = max(1, (1 << 25) // (B * k.shape[1] * hd))
+    for i in range(0, Nq, step):
+        cond[:, i:i + step] = (a[:, i:i + step, :, None] * (v[:, None, :, :] - out[:, i:i + step, None, :]).abs()).sum(dim=2)
+    return out, cond
+
+
+def attention_bound(ref, cond, dtype_name: str, k: int = ATTN_K):
+    """|got - ref64| <= |ref64| * ulp_out + k * u * cond + 1e-7"""
+    return ref.abs() * ATTN_ULP[dtype_name] + k * ATTN_UNIT[dtype_name] * cond + 1e-7
+
+
+def attention_emu(q, k, v, scale: float, dtype_name: str, schedule: str = "single"):
+    """f32 emulation of a family's DEFINITION (device_common.h AttnExp / AttnExpRt, the kernels' headers), not of a kernel's output:
+    operands rounded to the type ("precise": the f32 values as they are -- two fp16 planes carry 22 bits of them), f32 raw scores,
+      f16 / precise:  e = round16(exp2(round16(fma(s, scale, -(scale * max))) * log2 e)),
+      bf16:           e = round_bf16(exp2(fma(s, kk, -(kk * max)))), kk = scale * log2 e,
+    f32 row sum of the ROUNDED numerators, f32 P.V of the unnormalised numerators, (P.V) * (1 / sum) rounded once to the output type.
+    schedule "online" (the bf16 pipelined kernel): keys in tiles of 32, queries in waves of 32 rows (rows past N repeat the last one);
+    the subtracted constant is a RUNNING maximum that a wave moves, for all its rows at once, only when some row's tile maximum exceeds
+    it by more than 8 / kk; sum and accumulators are then multiplied by exp2 of each row's own shift; numerators are rounded at the
+    scale they have when formed.  What no emulation models: the order of the f32 sums and the MFMA's internal accumulation."""
+    import torch
+    f32 = torch.float32
+    tdt = torch.float16 if dtype_name == "f16" else torch.bfloat16
+    rnd = lambda x: x.to(tdt).to(f32)
+    fma = lambda s, kk, nmx: (s.double() * kk + nmx.double()).to(f32)          # exact product and sum, one rounding
+    if schedule == "precise":
+        assert dtype_name == "f16"
+        q, k, v = q.to(f32), k.to(f32), v.to(f32)
+    else:
+        q, k, v = rnd(q.to(f32)), rnd(k.to(f32)), rnd(v.to(f32))
+    if dtype_name == "f16":
+        kk = float(np.float32(scale))
+        numer = lambda s, nmx: rnd(torch.exp2(rnd(fma(s, kk, nmx)) * float(np.float32(1.44269504))))
+    else:
+        kk = float(np.float32(scale) * np.float32(LOG2E))
+        numer = lambda s, nmx: rnd(torch.exp2(fma(s, kk, nmx)))
+    kk32 = torch.tensor(kk, dtype=f32, device=q.device)
+    if schedule != "online":
+        s = q @ k.transpose(1, 2)
+        e = numer(s, -(kk32 * s.amax(dim=2, keepdim=True)))
+        return rnd((e @ v) * (1.0 / e.sum(dim=2, keepdim=True)))
+    assert dtype_name == "bf16"
+    B, Nq, hd = q.shape
+    nb = (Nq + 31) // 32
+    qp = q[:, torch.arange(nb * 32, device=q.device).clamp(max=Nq - 1)].reshape(B, nb, 32, hd)
+    mxs = torch.full((B, nb, 32, 1), -float("inf"), dtype=f32, device=q.device)
+    nmx = torch.zeros_like(mxs); tot = torch.zeros_like(mxs)
+    o = torch.zeros((B, nb, 32, hd), dtype=f32, device=q.device)
+    tau = float(np.float32(8.0) / np.float32(kk))
+    for t0 in range(0, k.shape[1], 32):
+        kt, vt = k[:, None, t0:t0 + 32], v[:, None, t0:t0 + 32]
+        s = qp @ kt.transpose(2, 3)
+        tm = s.amax(dim=3, keepdim=True)
+        move = (tm > mxs + tau).flatten(2).any(dim=2)[:, :, None, None]
+        mnew = torch.maximum(mxs, tm)
+        sc = torch.where(move, torch.exp2((mxs - mnew) * kk32), torch.ones_like(mxs))
+        mxs = torch.where(move, mnew, mxs)
+        nmx = -(kk32 * mxs)
+        tot = tot * sc; o = o * sc
+        e = numer(s, nmx)
+        tot = tot + e.sum(dim=3, keepdim=True); o = o + e @ vt
+    return rnd(o * (1.0 / tot)).reshape(B, nb * 32, hd)[:, :Nq]
+
+
+def attention_schedule(family: str, dtype_name: str, N: int) -> str:
+    """Which definition a family follows at a token count: the bf16 pipelined kernel (forced, or the automatic choice outside the
+    single-pass and persistent ranges) keeps a running maximum; `precise` multiplies f32 values; everything else is single-pass."""
+    if family == "precise":
+        return "precise"
+    single = (N + 31) // 32 in (1, 2, 3, 4, 5, 6, 7, 9, 19)
+    if dtype_name == "bf16" and (family == "flow" or (family == "auto" and not (192 < N <= 224) and not (single and N <= 288))):
+        return "online"
+    return "single"
+
+
+def attention_faults(q, k, v, scale: float, n_img: int, H: int):
+    """The three faults the gates must see, applied to the float64 reference: {name: out64}.  leak: one more key, token 0 of the next
+    image's same head (a zero key and value behind the last image: what a buffer load returns past the end); drop: the last key is
+    missing; scale: the softmax scale 2 % too large."""
+    import torch
+    B, N, hd = k.shape
+    nxt = lambda t: torch.cat([t.reshape(n_img, H, N, hd)[1:, :, :1], torch.zeros((1, H, 1, hd), dtype=t.dtype, device=t.device)]).reshape(B, 1, hd)
+    return {"leak": attention_ref(q, torch.cat([k, nxt(k)], dim=1), torch.cat([v, nxt(v)], dim=1), scale),
+            "drop": attention_ref(q, k[:, :-1], v[:, :-1], scale),
+            "scale": attention_ref(q, k, v, scale * 1.02)}
+
+
+def attention_gate_ratios(got, ref, bound, emu):
+    """(worst |got - ref| / bound, mean|got - ref| / mean|emu - ref|): the test passes with the first <= 1 and the second <= ATTN_MEAN_FACTOR"""
+    err = (got.double() - ref).abs()
+    return float((err / bound).max()), float(err.mean() / (emu.double() - ref).abs().mean())
 
 
 # ------------------------------------------------------------------------------------------------------------------

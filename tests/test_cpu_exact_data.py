@@ -115,6 +115,131 @@ def test_issue_gaps_at_head_dim_64():
         assert X.routing_qkv(1, N, 1, 64, X.attn_seed(1, N, 1, 64))[2] == want
 
 
+FLAT_N = (1, 2, 3, 17, 64, 65, 193, 197, 208, 224, 225, 289, 577, 785, 1025, 4097)
+
+
+def _flat_moved(q, k, v, c, hd, dn, schedule):
+    """per query row: does the emulated output differ from c somewhere?"""
+    out = X.attention_emu(q, k, v, 1.0 / np.sqrt(hd), dn, schedule)
+    return ~(out == c).all(dim=2)
+
+
+@pytest.mark.parametrize("hd", [32, 64, 128])
+def test_flat_softmax_data_is_exact_and_sees_a_dropped_or_padded_key(hd):
+    """flat_qkv: every value representable in both operand types, z sums to zero per column and is never zero, every raw score of an item
+    is one integer; the f32 / operand-type emulation of every definition gives c bit for bit; and the sensitivity the GPU test relies on:
+    a dropped key moves every output row at every N >= 2 in both types; a zero pad key (k = 0, v = 0) counted in the row sum moves every
+    row for sign = -1 at every N, for sign = 0 only while c N / (N + 1) does not round back to c (bf16: up to 289 tokens, not from 577;
+    f16: up to 1025, not at 4097), never for sign = +1: hence all three signs, and sign = -1 as the pad detector."""
+    for N in FLAT_N:
+        if N == 4097 and hd != 64:
+            continue
+        for sign in X.FLAT_SIGNS:
+            qkv, c = X.flat_qkv(2, N, 1, hd, sign, X.attn_seed(2, N, 1, hd) + 17 * sign)
+            t = torch.from_numpy(qkv)
+            assert torch.equal(t.to(torch.float16).float(), t) and torch.equal(t.to(torch.bfloat16).float(), t)
+            q, k, v = X.heads_of(t, 2, N, 1, hd)
+            cc = torch.from_numpy(c).reshape(2, 1, hd)
+            z = v - cc
+            assert (z.sum(dim=1) == 0).all() and ((z != 0).all() if N > 1 else not z.any()) and z.abs().max() <= 64 and (N == 1 or z.abs().min() >= 16)
+            assert cc.min() >= 1 and cc.max() <= 3 and not torch.equal(cc[0], cc[1])
+            raw = q.double() @ k.double().transpose(1, 2)
+            assert (raw == sign * X.flat_gain(hd) * (hd // 2)).all() and abs(abs(raw[0, 0, 0].item()) / np.sqrt(hd) - 24 * abs(sign)) < 2.5
+            assert (v.abs().sum(dim=1) < 2 ** 24).all()
+            assert np.array_equal(X.rows_of(cc.expand(2, N, hd).contiguous(), 2, N, 1, hd).numpy(), X.flat_expected(c, N))
+            zero = torch.zeros((2, 1, hd))
+            for dn, schedule in (("f16", "single"), ("bf16", "single"), ("bf16", "online"), ("f16", "precise")):
+                if schedule != "single" and hd != 64:
+                    continue
+                what = (N, hd, sign, dn, schedule)
+                assert not _flat_moved(q, k, v, cc, hd, dn, schedule).any(), what
+                if N >= 2:
+                    assert _flat_moved(q, k[:, :-1], v[:, :-1], cc, hd, dn, schedule).all(), what
+                pad = _flat_moved(q, torch.cat([k, zero], 1), torch.cat([v, zero], 1), cc, hd, dn, schedule)
+                if sign == -1:
+                    assert pad.all(), what
+                elif sign == 1:
+                    assert not pad.any(), what
+                elif N <= 289 or (dn == "f16" and N <= 1025):
+                    assert pad.all(), what
+                elif N >= (577 if dn == "bf16" else 4097):
+                    assert not pad.any(), what
+
+
+def test_attention_case_lists_meet_every_edge():
+    """Every family: at least two images and two heads everywhere, three images at every edge; N % 16 in {15, 0, 1} and N % 64 in {63, 0, 1}
+    inside its range; the automatic choice on both sides of each of its thresholds; a partly filled fourteenth tile with an odd head count."""
+    for f, cases in X.FLAT_CASES.items():
+        assert all(n_img >= 2 and H >= 2 for n_img, N, H, hd in cases), f
+        ns = {N for n_img, N, H, hd in cases if n_img >= 3}
+        assert {n % 16 for n in ns} >= {15, 0, 1} and {n % 64 for n in ns} >= {63, 0, 1} or f in ("auto", "persist"), f
+    assert {N for _, N, _, _ in X.FLAT_CASES["auto"]} >= {192, 193, 208, 209, 224, 225, 256, 257, 288, 289}
+    assert {n % 16 for _, n, _, _ in X.FLAT_CASES["persist"]} >= {15, 0, 1} and all(192 < n <= 224 for _, n, _, _ in X.FLAT_CASES["persist"])
+    assert any(208 < N < 224 and H % 2 for fam in (X.FLAT_CASES, X.ATTN_CASES) for _, N, H, _ in fam["persist"])
+    assert all((N + 31) // 32 in (1, 2, 3, 4, 5, 6, 7, 9, 19) for _, N, _, _ in X.FLAT_CASES["single"])
+    assert all(hd != 64 for _, _, _, hd in X.FLAT_CASES["generic"]) and {hd for _, _, _, hd in X.FLAT_CASES["generic"]} >= {32, 80, 96, 128}
+    for f, cases in X.SPREAD_CASES.items():
+        assert cases == [c for c in X.FLAT_CASES[f] if c[1] >= X.SPREAD_MIN_N] and len(cases) >= len(X.FLAT_CASES[f]) - 1
+    # what the emulation's schedule follows: the dispatcher's ranges (launch_attention, kernels.hip)
+    S = X.attention_schedule
+    assert [S("auto", "bf16", n) for n in (192, 193, 224, 225, 256, 257, 288, 289, 577)] == ["single", "single", "single", "online", "online", "single", "single", "online", "online"]
+    assert S("auto", "f16", 4097) == "single" and S("flow", "bf16", 197) == "online" and S("precise", "f16", 197) == "precise" and S("stream", "bf16", 577) == "single"
+
+
+SPREAD_DISTINCT = sorted({(c[1], c[2], c[3]) for cs in X.SPREAD_CASES.values() for c in cs})
+
+
+@pytest.mark.parametrize("N,H,hd", SPREAD_DISTINCT, ids=lambda v: str(v))
+def test_attention_gates_see_a_leaked_key_a_dropped_key_and_a_wrong_scale(N, H, hd):
+    """For every spread / peaked case (the gates do not depend on the family: one per distinct N, H, head dim, operand type and
+    schedule; two images, which is what the leak needs): with the gates of test_gpu_attention.py computed from the float64 reference and
+    the emulation,
+      * the emulation of the definition needs at most half of the per-element bound with k = ATTN_K = 1, the smallest candidate;
+      * one leaked key (token 0 of the next image; a zero key behind the last image), the dropped last key and a scale 2 % too large,
+        each applied to the float64 reference, break the per-element gate or the mean gate.
+    Above CPU_FULL_MAX_N tokens the first 512 query rows of every item stand for the buffer (rows are independent; the whole float64
+    problem takes minutes here); test_gpu_attention.py asserts the same on the whole buffer of those cases."""
+    scale = 1.0 / np.sqrt(hd)
+    for kind in X.spread_kinds(N):
+        x = torch.from_numpy(X.spread_qkv(2, N, H, hd, X.attn_seed(2, N, H, hd), kind))
+        for dn, schedules in (("f16", ("single",)), ("bf16", ("single", "online")), ("f16", ("precise",))):
+            if schedules != ("single",) and hd != 64:
+                continue
+            q, k, v = X.heads_of(x if schedules == ("precise",) else x.to(torch.float16 if dn == "f16" else torch.bfloat16).float(), 2, N, H, hd)
+            if N > X.CPU_FULL_MAX_N:
+                q = q[:, :512]
+            ref, cond = X.attention_ref(q, k, v, scale, want_bound=True)
+            bound = X.attention_bound(ref, cond, dn)
+            faults = X.attention_faults(q, k, v, scale, 2, H)
+            for schedule in schedules:
+                emu = X.attention_emu(q, k, v, scale, dn, schedule)
+                need, _ = X.attention_gate_ratios(emu, ref, bound, emu)
+                line = f"N {N} H {H} hd {hd} {kind} {dn} {schedule}: emulation {need:.3f} of the bound;"
+                assert need <= 0.5, line
+                for name, out in faults.items():
+                    worst, mean = X.attention_gate_ratios(out, ref, bound, emu)
+                    line += f" {name} {worst:.2f} of the bound, {mean:.2f} of the emulation's mean;"
+                    assert worst > 1.0 or mean > X.ATTN_MEAN_FACTOR, line
+                print(line)
+
+
+def test_attention_emulation_restates_the_oracle():
+    """exact_data.attention_emu (single-pass) against oracle.attention in the modes that restate the engine's rounding points: same
+    definition, another summation order and another exp (expf / the fp16 table against exp2), the oracle's output not rounded to the
+    operand type: the two agree within one output ulp plus what two exps one f32 ulp apart do to a numerator of the operand type."""
+    from oracle import oracle as O
+    O.build()
+    n_img, N, H, hd = 2, 197, 2, 64
+    x32 = X.spread_qkv(n_img, N, H, hd, 3)
+    for dn, mode, tdt in (("f16", O.GPU_F16, torch.float16), ("bf16", O.GPU_BF16, torch.bfloat16)):
+        xr = torch.from_numpy(x32).to(tdt).float()
+        q, k, v = X.heads_of(xr, n_img, N, H, hd)
+        emu = X.rows_of(X.attention_emu(q, k, v, 0.125, dn), n_img, N, H, hd).numpy()
+        ora = O.attention(xr.numpy(), n_img, N, H * hd, H, mode)
+        err = np.abs(emu - ora)
+        assert err.max() <= np.abs(ora).max() * X.ATTN_ULP[dn] and err.mean() <= 0.5 * np.abs(ora).mean() * X.ATTN_ULP[dn], (dn, err.max(), err.mean())
+
+
 @pytest.mark.parametrize("D", [256, 512, 768, 1024])
 def test_layernorm_bound_is_pinned_by_an_f32_emulation(D):
     """The tolerance of the hostile-row LayerNorm tests is set by the problem's conditioning, not by the kernels: an f32 emulation of the
