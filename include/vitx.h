@@ -268,7 +268,8 @@ int vitx_group_forward_device(vitx_group *g, const void *const *d_imgs, const in
 const void *vitx_group_result(const vitx_group *g, int device_index);
 int vitx_group_result_rows(const vitx_group *g);
 
-/* Sorted top-k of one probability row (vit.cpp:1043-1057: descending by prob). */
+/* Sorted top-k of one probability row (vit.cpp:1043-1057: descending by prob, ties by the lower class; +0 and -0 tie).  Entries that are
+ * NaN come after every other entry, by class: every index returned lies in [0, num_classes) and none repeats, whatever the row holds. */
 int vitx_topk(const float *probs, int num_classes, int k, int32_t *out_idx, float *out_prob);
 
 /* ---- measurement ------------------------------------------------------------ */
@@ -338,6 +339,11 @@ int vitx_op_gemm_ln(int dtype, const void *d_a, const void *d_w, const void *d_b
  *   vitx_op_gemm_q4 : C = A[M][K] . dequant(W)^T with the q4_0 blocks expanded in the GEMM's LDS-fill path; d_qs / d_scales as
  *                     above but with N rounded up to 128 rows (zero scales in the pad rows), epi 0..3 as vitx_op_gemm. */
 int vitx_op_dequant(int dtype, int qtype, const void *d_blocks, const void *d_scales, void *d_out, int N, int n_pad, int K, void *stream);
+/* The same for njobs = 1..4 matrices of one block type in ONE launch, as the forward expands the qkv, proj, fc1 and fc2 matrices of a
+ * layer (launch_dequant, quant.hip): job j takes d_blocks[j], d_scales[j] (d_scales may be NULL for every type but q4_0), d_out[j],
+ * N[j], n_pad[j], K[j] under the rules above.  The arrays live on the host; the destinations must not overlap. */
+int vitx_op_dequant_jobs(int dtype, int qtype, int njobs, const void *const *d_blocks, const void *const *d_scales, void *const *d_out,
+                         const int *N, const int *n_pad, const int *K, void *stream);
 int vitx_op_gemm_q4(int dtype, int epi, const void *d_a, const void *d_qs, const void *d_scales, const void *d_bias, void *d_out,
                     int M, int M_real, int N, int K, void *stream);
 /* Device bytes held by the context's weight matrices (blocks for quantised tensors, 16-bit operands otherwise). */
@@ -383,10 +389,13 @@ int vitx_op_attention_f32(const float *d_qkv_f32, void *d_out, int n_img, int N,
 /* The same kernel on planes that are already split (the output of vitx_op_gemm_ex epi 5): d_hi [n_img * N][3 D] fp16, the lo plane lo_off
  * ELEMENTS behind it (a multiple of 4, at least n_img * N * 3 D, both planes below 0xf0000000 bytes).  Only enqueues on `stream`. */
 int vitx_op_attention_planes(const void *d_hi, long lo_off, void *d_out, int n_img, int N, int D, int H, void *stream);
-/* probs = softmax(logits) over num_classes with the reference's fp16 exp rounding (vit.cpp:931). */
+/* probs[rows][cols] = softmax(logits[rows][ld]) over num_classes with the reference's fp16 exp rounding (vit.cpp:931); ld >= cols. */
 int vitx_op_softmax(const void *d_logits, void *d_probs, int rows, int cols, int ld, void *stream);
 /* The same with the rounding type of the exp explicit (VITX_F16 = the reference's LUT semantics, VITX_BF16 = the bf16 engine). */
 int vitx_op_softmax_dt(int dtype, const void *d_logits, void *d_probs, int rows, int cols, int ld, void *stream);
+/* The device-side top-k of vitx_group_forward_device (topk_kernel, kernels.hip): d_pairs[rows][k] = {f32 probability, i32 class} of
+ * d_probs[rows][cols] f32 in the order of vitx_topk; 0 < k <= cols.  Only enqueues on `stream`. */
+int vitx_op_topk(const void *d_probs, int rows, int cols, int k, void *d_pairs, void *stream);
 
 /* ---- residual-stream trace (parity localisation) ------------------------------ */
 /* After vitx_trace_enable(ctx, ids, n) every forward also copies the f32 residual stream X of images ids[0..n) -- after the

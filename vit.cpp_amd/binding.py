@@ -38,6 +38,7 @@ EXPORTS = [
     "vitx_mxfp8_quantize", "vitx_op_quantize_mxfp8", "vitx_op_layernorm_mxfp8", "vitx_op_gemm_mxfp8",
     "vitx_feat_enable", "vitx_feat_floats", "vitx_feat_images", "vitx_feat_read", "vitx_feat_device", "vitx_op_features",
     "vitx_ctx_img_size", "vitx_ctx_tokens", "vitx_pos_embed_resample", "vitx_op_pos_embed_resample", "vitx_model_resize_file",
+    "vitx_op_topk", "vitx_op_dequant_jobs",
 ]
 
 
@@ -163,6 +164,9 @@ def lib():
             L.vitx_pos_embed_resample.argtypes = [C.POINTER(C.c_float), ip, ip, ip, ip, ip, ip, C.POINTER(C.c_float)]
             L.vitx_op_pos_embed_resample.argtypes = [vp, ip, ip, ip, ip, ip, ip, vp, vp]
             L.vitx_model_resize_file.argtypes = [C.c_char_p, C.c_char_p, ip, ip]
+        if hasattr(L, "vitx_op_topk"):
+            L.vitx_op_topk.argtypes = [vp, ip, ip, ip, vp, vp]
+            L.vitx_op_dequant_jobs.argtypes = [ip, ip, ip, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(ip), C.POINTER(ip), C.POINTER(ip), vp]
         _lib = L
     return _lib
 

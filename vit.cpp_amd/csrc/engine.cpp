@@ -1244,6 +1244,18 @@ int vitx_op_dequant(int dtype, int qtype, const void *blocks, const void *scales
     if (e != hipSuccess) { set_error("vitx_op_dequant: %s", hipGetErrorString(e)); return e == hipErrorInvalidValue ? VITX_ERR_ARG : VITX_ERR_HIP; }
     return VITX_OK;
 }
+// launch_dequant as the forward calls it (expand, above): up to four matrices of one block type in ONE launch
+int vitx_op_dequant_jobs(int dtype, int qtype, int njobs, const void *const *blocks, const void *const *scales, void *const *out, const int *N, const int *n_pad, const int *K, void *stream) {
+    if (njobs < 1 || njobs > 4 || !blocks || !out || !N || !n_pad || !K || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_dequant_jobs: invalid argument"); return VITX_ERR_ARG; }
+    DequantJob jobs[4];
+    for (int j = 0; j < njobs; ++j) {
+        if (!blocks[j] || !out[j] || N[j] <= 0 || n_pad[j] < N[j] || K[j] <= 0 || K[j] % 32) { set_error("vitx_op_dequant_jobs: invalid argument in job %d", j); return VITX_ERR_ARG; }
+        jobs[j] = DequantJob{blocks[j], scales ? scales[j] : nullptr, out[j], N[j], n_pad[j], K[j] / 32};
+    }
+    hipError_t e = launch_dequant(dtype, qtype, jobs, njobs, (hipStream_t)stream);
+    if (e != hipSuccess) { set_error("vitx_op_dequant_jobs: %s", hipGetErrorString(e)); return e == hipErrorInvalidValue ? VITX_ERR_ARG : VITX_ERR_HIP; }
+    return VITX_OK;
+}
 int vitx_op_gemm_q4(int dtype, int epi, const void *a, const void *qs, const void *scales, const void *bias, void *out, int M, int M_real, int N, int K, void *stream) {
     if (!a || !qs || !scales || !bias || !out || epi < 0 || epi > EPI_BIAS_F32 || M_real <= 0 || M_real > M) { set_error("vitx_op_gemm_q4: invalid argument"); return VITX_ERR_ARG; }
     if (!tuning_for_device(-1)) { set_error("vitx_op_gemm_q4: kernel bring-up failed"); return VITX_ERR_HIP; }
@@ -1365,12 +1377,19 @@ int vitx_op_attention_f32(const float *qkv_f32, void *out, int n_img, int N, int
     return VITX_OK;
 }
 int vitx_op_softmax_dt(int dtype, const void *logits, void *probs, int rows, int cols, int ld, void *stream) {
-    if (!logits || !probs || rows <= 0 || cols <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) return VITX_ERR_ARG;
+    if (!logits || !probs || rows <= 0 || cols <= 0 || ld < cols || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_softmax: invalid argument"); return VITX_ERR_ARG; }
     hipError_t e = launch_softmax(dtype, (const float *)logits, (float *)probs, rows, cols, ld, (hipStream_t)stream);
     if (e != hipSuccess) { set_error("vitx_op_softmax: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
     return VITX_OK;
 }
 int vitx_op_softmax(const void *logits, void *probs, int rows, int cols, int ld, void *stream) { return vitx_op_softmax_dt(VITX_F16, logits, probs, rows, cols, ld, stream); }
+// launch_topk as the sharded forward calls it (sharded.cpp): pairs {f32 probability, i32 class} of every row
+int vitx_op_topk(const void *probs, int rows, int cols, int k, void *pairs, void *stream) {
+    if (!probs || !pairs || rows <= 0 || cols <= 0 || k <= 0 || k > cols) { set_error("vitx_op_topk: invalid argument"); return VITX_ERR_ARG; }
+    hipError_t e = launch_topk((const float *)probs, rows, cols, k, pairs, (hipStream_t)stream);
+    if (e != hipSuccess) { set_error("vitx_op_topk: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
+    return VITX_OK;
+}
 
 int vitx_trace_enable(vitx_ctx *c, const int32_t *image_ids, int n) {
     if (!c || n < 0 || (n > 0 && !image_ids)) return VITX_ERR_ARG;

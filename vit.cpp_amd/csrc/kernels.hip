@@ -1526,27 +1526,38 @@ hipError_t launch_softmax(int dtype, const float *logits, float *probs, int rows
 
 // ------------------------------------------------------------------------------------------------
 // Top-k of every probability row (vit_predict's sort, vit.cpp:1043-1057): one wave per row, k selection passes; pass i takes the
-// largest entry that comes after pass i - 1's in the order (probability descending, class index ascending) -- no scratch, no ties lost.
+// largest entry that comes after pass i - 1's in the order -- no scratch, no ties lost.
+// The order is vitx_topk's (model_file.cpp): entries that are not NaN first, by probability descending then class index ascending
+// (+0 and -0 tie), NaN entries last by class index ascending.  It is TOTAL: a value maps to a 32-bit rank that grows with it (0 for
+// a NaN, below -inf's) and an entry to rank << 32 | ~index, so with k <= cols every pass finds an entry and every class written lies
+// in [0, cols) and is written once -- also for a row of NaNs, which float comparisons alone would answer with no entry at all.
 // ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned topk_rank(float v) {
+    if (v != v) return 0u;
+    const unsigned b = __builtin_bit_cast(unsigned, v + 0.0f);            // -0 + 0 = +0: the two zeros share a rank
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
 __global__ __launch_bounds__(256) void topk_kernel(const float *__restrict__ probs, int rows, int cols, int k, float *__restrict__ out) {
     const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const float *p = probs + (size_t)row * cols;
-    float pv = INFINITY; int pi = -1;
+    unsigned long long prev = ~0ull;                                     // above every entry (no value has rank 0xffffffff)
     for (int it = 0; it < k; ++it) {
-        float bv = -INFINITY; int bi = 0x7fffffff;
+        unsigned long long best = 0; float bv = 0.0f;                    // 0 = none yet: an entry's low word is ~index >= 0x80000000
         for (int i = lane; i < cols; i += 64) {
             const float v = p[i];
-            const bool after = v < pv || (v == pv && i > pi);            // not yet taken
-            if (after && (v > bv || (v == bv && i < bi))) { bv = v; bi = i; }
+            const unsigned long long e = ((unsigned long long)topk_rank(v) << 32) | (unsigned)~i;
+            if (e < prev && e > best) { best = e; bv = v; }              // not yet taken, and ahead of this lane's best
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o); const int oi = __shfl_xor(bi, o);
-            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+            const unsigned long long oe = __shfl_xor(best, o);
+            if (oe > best) best = oe;
         }
+        const int bi = (int)~(unsigned)best;
+        bv = __shfl(bv, bi & 63);                                        // the value as stored (sign of a zero, bits of a NaN): lane bi % 64 read it
         if (lane == 0) { out[((size_t)row * k + it) * 2] = bv; ((int *)out)[((size_t)row * k + it) * 2 + 1] = bi; }
-        pv = bv; pi = bi;
+        prev = best;
     }
 }
 __global__ void spin_kernel(long long ticks) {

@@ -244,10 +244,17 @@ int vitx_model_tensor_f32(const vitx_model *m, int i, float *out, size_t n) {
 int vitx_topk(const float *probs, int C, int k, int32_t *idx, float *p) {
     if (!probs || !idx || C <= 0 || k <= 0) return VITX_ERR_ARG;
     if (k > C) k = C;
-    // descending by probability (vit.cpp:1053-1057); ties broken by lower class id for determinism
+    // descending by probability (vit.cpp:1053-1057); ties broken by lower class id for determinism.  NaN entries come last, by class id:
+    // with them left to `>` and `==` the comparison is no strict weak order and std::partial_sort is undefined.  topk_kernel
+    // (kernels.hip) follows the same order.
     std::vector<int32_t> order((size_t)C);
     for (int i = 0; i < C; ++i) order[i] = i;
-    std::partial_sort(order.begin(), order.begin() + k, order.end(), [&](int32_t a, int32_t b) { return probs[a] > probs[b] || (probs[a] == probs[b] && a < b); });
+    std::partial_sort(order.begin(), order.begin() + k, order.end(), [&](int32_t a, int32_t b) {
+        const float pa = probs[a], pb = probs[b];
+        const bool na = pa != pa, nb = pb != pb;
+        if (na || nb) return na == nb ? a < b : nb;
+        return pa > pb || (pa == pb && a < b);
+    });
     for (int i = 0; i < k; ++i) { idx[i] = order[i]; if (p) p[i] = probs[order[i]]; }
     return VITX_OK;
 }
