@@ -101,6 +101,31 @@ const char *vitx_model_label(const vitx_model *m, int class_id);
 #define VITX_VITSTR_SEQ_LEN 25
 int vitx_model_in_channels(const vitx_model *m);
 int vitx_model_seq_len(const vitx_model *m);
+/* ---- register tokens and the pooled head (DINOv2-class models) ---------------
+ * Two optional extensions of the file, recognised by tensor name and shape; magic and the seven hparams are unchanged:
+ *   `reg_token`   f32 [1][R][D], R >= 1 (ggml dims [D, R, 1]), written directly after cls_token: R learned register tokens that sit between
+ *                 the class token and the patches and receive NO position embedding.  The file then holds 4 + 12 L + 4 + 1 tensors.
+ *   `head.weight` of [C][2 D] instead of [C][D]: the DINOv2 linear head over concat(cls, mean of the patch tokens) of the final norm.
+ * Any other type or shape of reg_token, or a head.weight whose rows are neither D nor 2 D long: VITX_ERR_FORMAT.  The reference's vit_model_load
+ * cannot read a file with either extension (unknown tensor / wrong shape, vit.cpp:618-641) -- the models it cannot run are the only ones that
+ * need them; files without them load and run exactly as before, bit for bit.
+ * Token layout of an image, T = 1 + R prefix tokens, N = g^2 + T (vitx_ctx_tokens):
+ *   row 0            cls_token + pos_embed[0]
+ *   rows 1 .. R      reg_token[r]                      (no position embedding)
+ *   rows T .. N-1    patch p + pos_embed[1 + p]        (raster order)
+ * pos_embed keeps its [1 + g^2][D] shape (and is resampled as before: registers are untouched).  Token 0 is the class token everywhere; the
+ * trace and the attention maps cover all N tokens (map index 0 = cls, 1 .. R = registers, T .. = patches); MEAN and TOKENS features cover the
+ * patch rows T .. N-1 only -- registers are not exposed as features (DINOv2 discards them).
+ * VITX_POOL_CLS_MEAN: the head GEMM's operand is Z[i] = RNE(F[0]) ‖ RNE(mean over t = T .. N-1 of F[t]), [2 D] in the operand type, F = the f32
+ * final-norm rows defined under "image embeddings and token features", the mean in VITX_FEAT_MEAN's fixed order -- so with VITX_FEAT_CLS |
+ * VITX_FEAT_MEAN on for the last layer (no VITX_FEAT_L2), RNE(feature) == the head operand bit for bit.  Such a context evaluates every row of
+ * the last layer: it behaves exactly as, and is bit-identical to, one created with last_layer_all_rows = 1.  A class-token head with registers
+ * keeps the class-rows-only last layer.  ViTSTR (one-channel) files with either extension, and VITX_MXFP8 contexts of such files, are
+ * VITX_ERR_UNSUPPORTED at context creation.
+ * LayerScale needs no slot: the converter folds it into attn.proj / mlp.fc2 (convert.py). */
+enum vitx_head_pool { VITX_POOL_CLS = 0, VITX_POOL_CLS_MEAN = 1 };
+int vitx_model_num_registers(const vitx_model *m);   /* R; 0 without reg_token (and for NULL) */
+int vitx_model_head_pool(const vitx_model *m);       /* enum vitx_head_pool, from head.weight's shape */
 int vitx_model_num_tensors(const vitx_model *m);
 /* Name, file type code (0 f32,1 f16,2 q4_0,3 q4_1,6 q5_0,7 q5_1,8 q8_0), ggml-order dims. */
 int vitx_model_tensor_info(const vitx_model *m, int index, const char **name, int32_t *type, int64_t ne[4], size_t *nbytes);
@@ -110,7 +135,8 @@ int vitx_model_tensor_f32(const vitx_model *m, int index, float *out, size_t n_e
 /* Re-encodes an f16/f32 model file with its 2-D "*weight" tensors in block format `ftype`
  * (2 q4_0, 3 q4_1, 6 q5_0, 7 q5_1, 8 q8_0), byte-identical to what the reference's offline
  * `quantize` tool writes (quantize.cpp:34-353: header ftype, label order, which tensors, block
- * encoders).  Host only.  VITX_ERR_ARG for another ftype, VITX_ERR_FORMAT if already quantised. */
+ * encoders).  Host only.  VITX_ERR_ARG for another ftype, VITX_ERR_FORMAT if already quantised.
+ * Files with the extensions above pass through: reg_token is copied, a [C][2 D] head is quantised like any 2-D "*weight". */
 int vitx_quantize_file(const char *path_in, const char *path_out, int ftype);
 
 /* ---- image files (replaces load_image_from_file = stbi_load(..., 3), vit.cpp:109-127) ---- */
@@ -171,7 +197,7 @@ typedef struct vitx_ctx_options {
                                  bit for bit; 0.76 of one layer's work is not done (ViT-B: 6.3 % of the forward's flops).  ViTSTR contexts and contexts with a
                                  residual-stream trace always compute every row. */
     int32_t img_size;         /* 0 = the file's; else the side of the square input of THIS context, a positive multiple of patch_size: the context runs
-                                 [n][img_size][img_size][3] images on (img_size / patch_size)^2 + 1 tokens with the file's position table resampled on the
+                                 [n][img_size][img_size][3] images on (img_size / patch_size)^2 + 1 (+ the model's registers) tokens with the file's position table resampled on the
                                  device at creation (vitx_pos_embed_resample below).  Equal to the file's: today's context bit for bit, nothing is launched.
                                  Not a positive multiple of the patch size: VITX_ERR_ARG; a ViTSTR file at a size other than its own: VITX_ERR_UNSUPPORTED. */
     int32_t pos_interp;       /* enum vitx_pos_interp; used only when img_size differs from the file's (an unknown value is VITX_ERR_ARG in any case) */
@@ -181,9 +207,11 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
 void vitx_ctx_free(vitx_ctx *c);
 int vitx_ctx_max_batch(const vitx_ctx *c);
 /* The geometry of THIS context (vitx_ctx_options::img_size): what vitx_forward expects is [n][img_size][img_size][3] (ViTSTR: one plane), and
- * N = (img_size / patch_size)^2 + 1 tokens size the trace, the attention maps and the token features.  0 for NULL. */
+ * N = (img_size / patch_size)^2 + 1 + R tokens (R = vitx_ctx_registers, the model's register tokens) size the trace and the attention maps;
+ * the token features have N - 1 - R rows.  0 for NULL. */
 int vitx_ctx_img_size(const vitx_ctx *c);
 int vitx_ctx_tokens(const vitx_ctx *c);
+int vitx_ctx_registers(const vitx_ctx *c);
 /* Probability rows per image that vitx_forward / vitx_forward_device write: 1 for a classifier ([n][num_classes]), 25 for a ViTSTR
  * file ([n][25][num_classes], row t = token t of the image; decode with vitx_vitstr_decode).  Images are then ONE grey channel:
  * [img_size][img_size] f32, as vitx_preprocess_vitstr_u8 emits. */
@@ -235,7 +263,8 @@ int vitx_ctx_synchronize(vitx_ctx *c);
  *   vitx_op_pos_embed_resample  the gfx950 kernel on device pointers, same arguments and bits; only enqueues on `stream`;
  *   vitx_model_resize_file      writes path_out = path_in with hparams.img_size = img_size and pos_embed resampled on the host; every other byte of
  *                               the file is copied through (quantised files included: pos_embed is always f32).  The result is an ordinary model
- *                               file: this library, the oracle and the reference's own vit_model_load read it.  img_size not a positive multiple
+ *                               file: this library, the oracle and the reference's own vit_model_load read it (a file with reg_token or the
+ *                               pooled head stays one only this library reads; reg_token is copied, pos_embed keeps 1 + g^2 rows).  img_size not a positive multiple
  *                               of the patch size, an unknown interp or path_out == path_in: VITX_ERR_ARG; a ViTSTR file at another size than its
  *                               own: VITX_ERR_UNSUPPORTED; an unreadable input: VITX_ERR_IO. */
 enum vitx_pos_interp { VITX_POS_BICUBIC = 0, VITX_POS_BICUBIC_AA = 1 };
@@ -414,7 +443,8 @@ int vitx_trace_read(vitx_ctx *c, float *out, size_t n_floats);
  *   s[i][j] = (q_i . k_j) / sqrt(hd) in f32;   A_h[i][j] = expf(s[i][j] - max_j s[i]) / sum_j (...)  with f32 expf.
  * The maps are f32 softmaxes of the context's own q, k -- NOT the numerators that multiply v (those use the reference's fp16 exp table or the
  * kernels' rounded numerators).
- *   class-token map of layer l:  A_h[0][0..N) for every head; index 0 is the class token itself, 1..N-1 the patches in raster order.
+ *   class-token map of layer l:  A_h[0][0..N) for every head; index 0 is the class token itself, 1..N-1 the patches in raster order
+ *     (a model with R register tokens: N includes them, 1..R are the registers, 1 + R.. the patches).
  *   rollout (Abnar & Zuidema 2020):  A^_l = 0.5 mean_h A_h + 0.5 I,  R = A^_(L-1) ... A^_0,  output = row 0 of R (length N; rows of R sum to 1).
  *     The last factor only ever needs row 0 of A^_(L-1), which is built from that layer's class-token maps -- so it is available when the last
  *     layer carries only the class rows (the default; see last_layer_all_rows) and gives the same bits with last_layer_all_rows = 1.
@@ -451,12 +481,13 @@ int vitx_op_attention_map(int dtype, const void *d_qkv, long lo_off, void *d_cls
  *   is what the classifier saw.  For l < L - 1 it is the "intermediate layer, norm applied" convention (DINO get_intermediate_layers(norm=True)).
  * Outputs (flags of vitx_feat_enable):
  *   VITX_FEAT_CLS     F_l[0], [D];
- *   VITX_FEAT_MEAN    (sum over t = 1 .. N-1 of F_l[t]) / (N - 1), [D]: global average pooling over the patch tokens, class token excluded;
- *   VITX_FEAT_TOKENS  F_l[1 .. N-1], [N-1][D], patches in raster order;
+ *   VITX_FEAT_MEAN    (sum over t = T .. N-1 of F_l[t]) / (N - T), [D]: global average pooling over the patch tokens; the class token and the
+ *                     register tokens are excluded (T = 1 + vitx_ctx_registers: 1 for a model without registers);
+ *   VITX_FEAT_TOKENS  F_l[T .. N-1], [N-T][D], patches in raster order;
  *   VITX_FEAT_L2      modifier: the CLS and MEAN vectors are divided by their Euclidean norm (sum of squares and square root in f32; an
  *                     all-zero vector stays zero).  Tokens are never normalised.  Alone it is VITX_ERR_ARG.
- * Layout per image: the selected layers in ascending order; per layer [cls D], then [mean D], then [tokens (N-1) * D], only the selected parts.
- *   vitx_feat_floats = popcount(layers) * (D * [CLS] + D * [MEAN] + (N-1) * D * [TOKENS]).
+ * Layout per image: the selected layers in ascending order; per layer [cls D], then [mean D], then [tokens (N-T) * D], only the selected parts.
+ *   vitx_feat_floats = popcount(layers) * (D * [CLS] + D * [MEAN] + (N-T) * D * [TOKENS]).
  * Determinism: the pooled sum has a fixed order (one workgroup per image and layer, no atomics).  An image's feature bits do not depend on
  *   its batch, its position in the batch, the sub-batch cut or the number of streams -- the invariant the probabilities keep.
  * vitx_feat_enable(ctx, flags, layer_mask): bit l of layer_mask selects layer l; layer_mask 0 = the last layer only; flags 0 = off (frees
@@ -479,7 +510,15 @@ int vitx_op_attention_map(int dtype, const void *d_qkv, long lo_off, void *d_cls
  *   (floats; the compact class rows of a class-rows-only last layer are N = 1, img_stride = D); d_w, d_b [D]; image i's outputs go to
  *   d_cls / d_mean / d_tokens + i * out_img_stride.  Any output may be NULL (at least one is not); row 0 is read only for d_cls, rows 1 .. N-1
  *   only for d_mean / d_tokens.  NULL inputs, n_img or N < 1, N == 1 with d_mean or d_tokens, pointers not 16-byte aligned or strides not
- *   multiples of 4 floats: VITX_ERR_ARG; a hidden size without a LayerNorm instantiation: VITX_ERR_UNSUPPORTED (both before any device call). */
+ *   multiples of 4 floats: VITX_ERR_ARG; a hidden size without a LayerNorm instantiation: VITX_ERR_UNSUPPORTED (both before any device call).
+ * vitx_op_features_ex: the same with `first` = T, the first patch row (1 <= first <= N; vitx_op_features is first = 1): d_mean / d_tokens cover rows
+ *   first .. N-1 ([N - first][D]), rows 1 .. first-1 are never read.  d_z != NULL: also the pooled head's operand (VITX_POOL_CLS_MEAN),
+ *   d_z[i] = RNE(F[0]) ‖ RNE(mean) as [2 D] elements of `dtype` (VITX_F16 / VITX_BF16), rounded before any l2 -- the launch the forward of a
+ *   pooled-head context makes (one launch serves the features and the head; profiling class "head_pool" when no feature of the last layer is on).
+ * vitx_op_patch_embed: the forward's patch-embedding kernel on its own.  TEST ONLY: it allocates, uploads and synchronises.  d_img f32
+ *   [n_img][S][S][Cin]; d_w f32 [D][Cin * P * P] in the file's (channel-major) order -- rounded to `dtype`, permuted and padded inside as the
+ *   context does at upload; d_bias [D], d_pos [1 + (S/P)^2][D], d_cls [D], d_reg [R][D] (NULL when R == 0), all f32; d_X f32
+ *   [n_img * ((S/P)^2 + 1 + R)][D] receives the token rows in the layout above and nothing beyond them. */
 #define VITX_FEAT_CLS 1
 #define VITX_FEAT_MEAN 2
 #define VITX_FEAT_TOKENS 4
@@ -492,6 +531,11 @@ const void *vitx_feat_device(const vitx_ctx *c);
 int vitx_op_features(const void *d_x, long row_stride, long img_stride, const void *d_w, const void *d_b,
                      void *d_cls, void *d_mean, void *d_tokens, long out_img_stride,
                      int n_img, int N, int D, float eps, int l2, void *stream);
+int vitx_op_features_ex(const void *d_x, long row_stride, long img_stride, const void *d_w, const void *d_b,
+                        void *d_cls, void *d_mean, void *d_tokens, long out_img_stride,
+                        int n_img, int N, int first, int D, float eps, int l2, void *d_z, int dtype, void *stream);
+int vitx_op_patch_embed(int dtype, const void *d_img, const void *d_w, const void *d_bias, const void *d_pos, const void *d_cls, const void *d_reg, int R,
+                        void *d_X, int n_img, int S, int P, int Cin, int D, void *stream);
 
 /* ---- MXFP8 operands (VITX_MXFP8, encoding above) ------------------------------- */
 /* Host encoder: x f32 [rows][K] -> q [rows][k_pad] e4m3 bytes + scales [rows][k_pad / 32] (k_pad >= K, a multiple of 32; columns

@@ -25,6 +25,7 @@ GEMM_AUTO, GEMM_PP, GEMM_AUTO_SPLIT = 0, 1, 2          # vitx_op_gemm_ex `kernel
 ATTN_AUTO, ATTN_SINGLE, ATTN_FLOW, ATTN_PERSIST, ATTN_STREAM = 0, 1, 3, 4, 5   # vitx_op_attention_ex `kernel`
 ATTN_ROLLOUT = 1                # vitx_attn_enable flag
 FEAT_CLS, FEAT_MEAN, FEAT_TOKENS, FEAT_L2 = 1, 2, 4, 8      # vitx_feat_enable flags
+POOL_CLS, POOL_CLS_MEAN = 0, 1          # vitx_model_head_pool: the head reads the class token, or concat(cls, mean of the patch tokens)
 POS_BICUBIC, POS_BICUBIC_AA = 0, 1      # vitx_pos_interp: F.interpolate(mode="bicubic") without / with antialias=True (include/vitx.h)
 
 EXPORTS = [
@@ -39,6 +40,7 @@ EXPORTS = [
     "vitx_feat_enable", "vitx_feat_floats", "vitx_feat_images", "vitx_feat_read", "vitx_feat_device", "vitx_op_features",
     "vitx_ctx_img_size", "vitx_ctx_tokens", "vitx_pos_embed_resample", "vitx_op_pos_embed_resample", "vitx_model_resize_file",
     "vitx_op_topk", "vitx_op_dequant_jobs",
+    "vitx_model_num_registers", "vitx_model_head_pool", "vitx_ctx_registers", "vitx_op_features_ex", "vitx_op_patch_embed",
 ]
 
 
@@ -167,6 +169,10 @@ def lib():
         if hasattr(L, "vitx_op_topk"):
             L.vitx_op_topk.argtypes = [vp, ip, ip, ip, vp, vp]
             L.vitx_op_dequant_jobs.argtypes = [ip, ip, ip, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(ip), C.POINTER(ip), C.POINTER(ip), vp]
+        if hasattr(L, "vitx_model_num_registers"):
+            L.vitx_model_num_registers.argtypes = [vp]; L.vitx_model_head_pool.argtypes = [vp]; L.vitx_ctx_registers.argtypes = [vp]
+            L.vitx_op_features_ex.argtypes = [vp, C.c_long, C.c_long, vp, vp, vp, vp, vp, C.c_long, ip, ip, ip, ip, C.c_float, ip, vp, ip, vp]
+            L.vitx_op_patch_embed.argtypes = [ip, vp, vp, vp, vp, vp, vp, ip, vp, ip, ip, ip, ip, ip, vp]
         _lib = L
     return _lib
 
@@ -201,6 +207,12 @@ class Model:
     def in_channels(self) -> int: return lib().vitx_model_in_channels(self._h)      # 3, or 1 for a ViTSTR file
     @property
     def seq_len(self) -> int: return lib().vitx_model_seq_len(self._h)              # 0 (classifier) or 25 (ViTSTR: rows per image)
+    @property
+    def num_registers(self) -> int:                                                 # register tokens (reg_token [1][R][D]); 0 without
+        return lib().vitx_model_num_registers(self._h) if hasattr(lib(), "vitx_model_num_registers") else 0
+    @property
+    def head_pool(self) -> int:                                                     # POOL_CLS, or POOL_CLS_MEAN for a [C][2 D] head
+        return lib().vitx_model_head_pool(self._h) if hasattr(lib(), "vitx_model_head_pool") else 0
     @property
     def num_classes(self) -> int: return self.hparams.num_classes
     @property
@@ -343,6 +355,8 @@ class Context:
         self.img_size = int(L.vitx_ctx_img_size(self._h)) if hasattr(L, "vitx_ctx_img_size") else model.img_size
         self.tokens = int(L.vitx_ctx_tokens(self._h)) if hasattr(L, "vitx_ctx_tokens") else (model.img_size // model.hparams.patch_size) ** 2 + 1
         self.grid = self.img_size // model.hparams.patch_size
+        self.registers = int(L.vitx_ctx_registers(self._h)) if hasattr(L, "vitx_ctx_registers") else 0
+        self.prefix = 1 + self.registers              # tokens in front of the patches: the class token and the registers
 
     def close(self):
         if getattr(self, "_h", None) and self._h:
@@ -401,7 +415,8 @@ class Context:
 
     def attn_read(self, n: Optional[int] = None):
         """Maps of the last forward made with maps on, all of its n images: (cls [n, n_sel, H, N] f32, rollout [n, N] f32 or None).
-        Index 0 of a map is the class token, 1.. the patches in raster order (attn_grid reshapes).  `n`, if given, must be that batch."""
+        Index 0 of a map is the class token, 1 .. registers the register tokens (models that have them), then the patches in raster order
+        (attn_grid reshapes).  `n`, if given, must be that batch."""
         hp = self.model.hparams
         N, H = self.tokens, hp.num_attention_heads
         fpi = lib().vitx_attn_floats(self._h)
@@ -419,9 +434,9 @@ class Context:
         return cls, (out[:, len(sel) * H * N:].copy() if roll else None)
 
     def attn_grid(self, m: np.ndarray) -> np.ndarray:
-        """[..., N] map -> [..., g, g] patch grid (g = the context's img_size / patch_size): drops index 0 (the class token)."""
+        """[..., N] map -> [..., g, g] patch grid (g = the context's img_size / patch_size): drops the class token and the register tokens."""
         g = self.grid
-        return np.asarray(m)[..., 1:].reshape(*np.shape(m)[:-1], g, g)
+        return np.asarray(m)[..., self.prefix:].reshape(*np.shape(m)[:-1], g, g)
 
     def feat_enable(self, cls: bool = True, mean: bool = False, tokens: bool = False, l2: bool = False, layers=None) -> None:
         """Embeddings and token features of every later forward (vitx_feat_enable): the final-norm class embedding, the mean of the patch
@@ -446,9 +461,9 @@ class Context:
 
     def feat_read(self, n: Optional[int] = None):
         """Features of the last forward made with features on, all of its n images: {layer: {"cls": [n, D], "mean": [n, D],
-        "tokens": [n, N - 1, D]}} f32 with the selected kinds only.  `n`, if given, must be that batch."""
+        "tokens": [n, N - T, D]}} f32 with the selected kinds only (T = 1 + registers: the patch rows).  `n`, if given, must be that batch."""
         hp = self.model.hparams
-        N, D = self.tokens, hp.hidden_size
+        N, D, T = self.tokens, hp.hidden_size, self.prefix
         sel, flags = getattr(self, "_feat_layers", []), getattr(self, "_feat_flags", 0)
         fpi = lib().vitx_feat_floats(self._h)
         have = lib().vitx_feat_images(self._h)
@@ -459,14 +474,14 @@ class Context:
             raise VitxError("feat_read: no forward has run with features on since feat_enable")
         out = np.empty((n, fpi), np.float32)
         check(lib().vitx_feat_read(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size), "vitx_feat_read")
-        kinds = [(k, rows) for k, bit, rows in (("cls", FEAT_CLS, 1), ("mean", FEAT_MEAN, 1), ("tokens", FEAT_TOKENS, N - 1)) if flags & bit]
+        kinds = [(k, rows) for k, bit, rows in (("cls", FEAT_CLS, 1), ("mean", FEAT_MEAN, 1), ("tokens", FEAT_TOKENS, N - T)) if flags & bit]
         assert fpi == len(sel) * D * sum(rows for _, rows in kinds)
         res, off = {}, 0
         for l in sel:
             res[l] = {}
             for k, rows in kinds:
                 v = out[:, off:off + rows * D]
-                res[l][k] = v.reshape(n, N - 1, D) if k == "tokens" else v
+                res[l][k] = v.reshape(n, N - T, D) if k == "tokens" else v
                 off += rows * D
         return res
 
@@ -590,6 +605,21 @@ def op_features(d_x: int, row_stride: int, img_stride: int, d_w: int, d_b: int, 
     """vitx_op_features: the f32 final-norm features of n_img images of N rows (device pointers; 0 = output not wanted; strides in floats)."""
     check(lib().vitx_op_features(d_x, row_stride, img_stride, d_w, d_b, d_cls or None, d_mean or None, d_tokens or None, out_img_stride,
                                  n_img, N, D, eps, int(l2), stream or None), "vitx_op_features")
+
+
+def op_features_ex(d_x: int, row_stride: int, img_stride: int, d_w: int, d_b: int, d_cls: int, d_mean: int, d_tokens: int, out_img_stride: int,
+                   n_img: int, N: int, first: int, D: int, eps: float = 1e-6, l2: bool = False, d_z: int = 0, dtype: int = F16, stream: int = 0) -> None:
+    """vitx_op_features_ex: op_features with the first patch row `first` (1 + registers) and, with d_z, the pooled head's operand
+    [n_img, 2 D] = RNE(cls) ‖ RNE(mean) in `dtype`."""
+    check(lib().vitx_op_features_ex(d_x, row_stride, img_stride, d_w, d_b, d_cls or None, d_mean or None, d_tokens or None, out_img_stride,
+                                    n_img, N, first, D, eps, int(l2), d_z or None, dtype, stream or None), "vitx_op_features_ex")
+
+
+def op_patch_embed(dtype: int, d_img: int, d_w: int, d_bias: int, d_pos: int, d_cls: int, d_reg: int, R: int, d_X: int, n_img: int, S: int, P: int,
+                   Cin: int, D: int, stream: int = 0) -> None:
+    """vitx_op_patch_embed (test only; synchronous): the forward's patch-embedding kernel with R register rows per image.  d_w is the f32
+    kernel [D, Cin * P * P] in the file's order; every pointer is a device pointer to f32."""
+    check(lib().vitx_op_patch_embed(dtype, d_img, d_w, d_bias, d_pos, d_cls, d_reg or None, R, d_X, n_img, S, P, Cin, D, stream or None), "vitx_op_patch_embed")
 
 
 def mx_k_pad(K: int) -> int:

@@ -61,7 +61,7 @@ def main(argv: List[str] | None = None) -> int:
                     help="also write the last layer's final-norm features as an .npy array, one row per image (with --dir: in walk order, and the "
                          "file names to OUT.npy.txt); the classification output is unchanged")
     ap.add_argument("--embed-kind", default="cls", choices=["cls", "mean", "tokens"],
-                    help="cls: the class-token embedding [D]; mean: the mean of the patch features [D]; tokens: the patch features [N-1, D]")
+                    help="cls: the class-token embedding [D]; mean: the mean of the patch features [D]; tokens: the patch features [patches, D] (the class token and any register tokens excluded)")
     ap.add_argument("--embed-l2", action="store_true", help="divide the cls / mean embedding by its Euclidean norm")
     ap.add_argument("--img-size", type=int, default=0, metavar="N",
                     help="run at N x N instead of the file's img_size (a multiple of the patch size): the position table is resampled to the new grid; "

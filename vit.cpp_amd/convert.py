@@ -1,4 +1,4 @@
-"""Converter: a HuggingFace `transformers` ViTForImageClassification -> the reference's legacy-ggml ".gguf" file.
+"""Converter: a HuggingFace `transformers` ViTForImageClassification or DINOv2 model -> the reference's legacy-ggml ".gguf" file.
 
 Counterpart of the reference's /root/reference/convert-pth-to-ggml.py (which needs `timm`): same output layout
 (writer rules convert-pth-to-ggml.py:105-158 live in ggml_file.write_model), different source naming -- HF splits
@@ -11,7 +11,15 @@ A timm checkpoint needs no `timm` either: its state_dict already carries the nam
 writes `timm_model.state_dict()` verbatim, convert-pth-to-ggml.py:121-133), so `--timm-state-dict model.pth` loads the tensors with
 torch.load and derives the hyper-parameters the reference reads from the timm module (:96-103) from the tensor shapes.
 
-    python -m ... convert.py <hf_model_dir_or_name> <out.gguf> [--ftype 1]
+DINOv2 (Dinov2ForImageClassification, Dinov2WithRegistersForImageClassification; the backbones Dinov2Model / Dinov2WithRegistersModel with
+--no-head) writes the two file extensions of include/vitx.h ("register tokens and the pooled head"): `reg_token` [1][R][D] and the
+[C][2 D] head over concat(cls, mean of the patch tokens); the reference's vit_model_load cannot read such a file.  LayerScale has no
+file slot and needs none: y = x + lambda * (W a + b) = x + (lambda * W) a + lambda * b, so lambda is folded into attn.proj / mlp.fc2 in f32,
+before the file type's rounding.  mask_token is dropped.  SwiGLU, qk-norm, fc_norm and distillation tokens are refused by name.
+At another input size transformers 5.x resamples the DINOv2-with-registers position table with antialias=True, so `--pos-interp bicubic-aa`
+reproduces it (plain Dinov2 and ViT: `bicubic`).
+
+    python -m ... convert.py <hf_model_dir_or_name> <out.gguf> [--ftype 1] [--no-head]
     python -m ... convert.py --timm-state-dict <checkpoint.pth> <out.gguf> [--ftype 1] [--heads H] [--labels labels.json]
 """
 from __future__ import annotations
@@ -52,8 +60,59 @@ def state_dict_to_timm(sd: Dict[str, np.ndarray], num_layers: int) -> Dict[str, 
     return {k: np.ascontiguousarray(np.asarray(v, np.float32)) for k, v in out.items()}
 
 
-def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False) -> HParams:
-    """model: transformers.ViTForImageClassification (eval).  Writes `path`; returns the hparams written.
+def fold_layer_scale(weight: np.ndarray, bias: np.ndarray, lam: np.ndarray):
+    """LayerScale folded into the linear layer in front of it, in f32: (lambda[o] * W[o][:], lambda[o] * b[o])."""
+    lam = np.asarray(lam, np.float32).reshape(-1)
+    return (np.asarray(weight, np.float32) * lam[:, None]).astype(np.float32), (np.asarray(bias, np.float32) * lam).astype(np.float32)
+
+
+def dinov2_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, no_head: bool = False) -> Dict[str, np.ndarray]:
+    """Rename / fuse / fold an HF Dinov2[WithRegisters]{ForImageClassification, Model} state dict (numpy arrays) into the file's names and order."""
+    if getattr(cfg, "use_swiglu_ffn", False):
+        raise ValueError("use_swiglu_ffn: the SwiGLU MLP of the DINOv2 giant models is not supported (the forward path has the GELU MLP only)")
+    for k in sd:
+        for bad, what in (("q_norm", "qk-norm"), ("k_norm", "qk-norm"), ("fc_norm", "fc_norm"), ("dist_token", "a distillation token"), ("distillation", "a distillation token")):
+            if bad in k:
+                raise ValueError(f"tensor {k!r}: {what} is not supported")
+    if getattr(cfg, "mlp_ratio", 4) != 4:
+        raise ValueError(f"mlp_ratio {cfg.mlp_ratio}: the file format holds a 4 x hidden MLP")
+    pre = next((p for p in ("dinov2_with_registers.", "dinov2.", "") if p + "embeddings.cls_token" in sd), None)
+    if pre is None:
+        raise ValueError("not a DINOv2 state dict: embeddings.cls_token is missing")
+    e = pre + "embeddings."
+    D = int(np.shape(sd[e + "cls_token"])[-1])
+    out: Dict[str, np.ndarray] = {}
+    out["cls_token"] = sd[e + "cls_token"]
+    if e + "register_tokens" in sd:
+        out["reg_token"] = sd[e + "register_tokens"]
+    out["pos_embed"] = sd[e + "position_embeddings"]
+    out["patch_embed.proj.weight"] = sd[e + "patch_embeddings.projection.weight"]
+    out["patch_embed.proj.bias"] = sd[e + "patch_embeddings.projection.bias"]
+    for i in range(cfg.num_hidden_layers):
+        q, p = f"{pre}encoder.layer.{i}.", f"blocks.{i}."
+        qkv = [q + "attention.attention." + n for n in ("query", "key", "value")]
+        if any(n + ".bias" not in sd for n in qkv):
+            raise ValueError("qkv_bias=False: the file format carries the fused qkv bias")
+        out[p + "norm1.weight"] = sd[q + "norm1.weight"]; out[p + "norm1.bias"] = sd[q + "norm1.bias"]
+        out[p + "attn.qkv.weight"] = np.concatenate([sd[n + ".weight"] for n in qkv], 0)
+        out[p + "attn.qkv.bias"] = np.concatenate([sd[n + ".bias"] for n in qkv], 0)
+        out[p + "attn.proj.weight"], out[p + "attn.proj.bias"] = fold_layer_scale(sd[q + "attention.output.dense.weight"], sd[q + "attention.output.dense.bias"], sd[q + "layer_scale1.lambda1"])
+        out[p + "norm2.weight"] = sd[q + "norm2.weight"]; out[p + "norm2.bias"] = sd[q + "norm2.bias"]
+        out[p + "mlp.fc1.weight"] = sd[q + "mlp.fc1.weight"]; out[p + "mlp.fc1.bias"] = sd[q + "mlp.fc1.bias"]
+        out[p + "mlp.fc2.weight"], out[p + "mlp.fc2.bias"] = fold_layer_scale(sd[q + "mlp.fc2.weight"], sd[q + "mlp.fc2.bias"], sd[q + "layer_scale2.lambda1"])
+    out["norm.weight"] = sd[pre + "layernorm.weight"]; out["norm.bias"] = sd[pre + "layernorm.bias"]
+    if no_head:          # a backbone: a one-class class-token head of zeros keeps the file well-formed; embeddings are read through vitx_feat_*
+        out["head.weight"] = np.zeros((1, D), np.float32); out["head.bias"] = np.zeros((1,), np.float32)
+    else:
+        if "classifier.weight" not in sd:
+            raise ValueError("the model has no classifier: convert a backbone with no_head=True (--no-head)")
+        out["head.weight"] = sd["classifier.weight"]; out["head.bias"] = sd["classifier.bias"]
+    return {k: np.ascontiguousarray(np.asarray(v, np.float32)) for k, v in out.items()}
+
+
+def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_head: bool = False) -> HParams:
+    """model: transformers.ViTForImageClassification, Dinov2ForImageClassification or Dinov2WithRegistersForImageClassification (eval);
+    with no_head=True a Dinov2Model / Dinov2WithRegistersModel backbone.  Writes `path`; returns the hparams written.
     vitstr=True: the model is a ViTSTR scene-text recogniser (/root/reference/extensions/vitstr.cpp/convert-pth-to-ggml.py: a ViT with ONE
     input channel whose classifier is applied to the first 25 tokens); the file then carries the character set as labels, and the
     one-channel patch kernel is what makes vit_model_load / vitx_model_load treat it as a ViTSTR model (vitstr.cpp:482)."""
@@ -63,8 +122,21 @@ def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False) -> 
     hd = cfg.hidden_size // cfg.num_attention_heads
     if cfg.hidden_size % cfg.num_attention_heads or hd % 8 or not 8 <= hd <= 128:
         raise ValueError(f"head_dim {hd}: the forward path takes multiples of 8 up to 128 (64 runs the tuned attention kernels)")
-    hp = HParams(cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, cfg.num_labels, cfg.patch_size, cfg.image_size, ftype)
     sd = {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
+    if getattr(cfg, "model_type", "") in ("dinov2", "dinov2_with_registers"):
+        if vitstr:
+            raise ValueError("a DINOv2 model is not a ViTSTR model")
+        tensors = dinov2_state_dict_to_timm(sd, cfg, no_head=no_head)
+        g = int(round((tensors["pos_embed"].shape[1] - 1) ** 0.5))       # the checkpoint's own grid (config.image_size states it too)
+        if g * g + 1 != tensors["pos_embed"].shape[1]:
+            raise ValueError(f"position_embeddings {tensors['pos_embed'].shape}: not 1 + a square grid")
+        hp = HParams(cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, int(tensors["head.weight"].shape[0]), cfg.patch_size, g * cfg.patch_size, ftype)
+        id2label = {0: "(no head)"} if no_head else ({int(k): str(v) for k, v in (getattr(cfg, "id2label", None) or {}).items()} or None)
+        write_model(path, hp, tensors, id2label=id2label, ftype=ftype)
+        return hp
+    if no_head:
+        raise ValueError("no_head converts a DINOv2 backbone (Dinov2Model, Dinov2WithRegistersModel)")
+    hp = HParams(cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, cfg.num_labels, cfg.patch_size, cfg.image_size, ftype)
     tensors = state_dict_to_timm(sd, cfg.num_hidden_layers)
     id2label = {int(k): str(v) for k, v in (getattr(cfg, "id2label", None) or {}).items()} or None
     if vitstr:
@@ -76,7 +148,8 @@ def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False) -> 
     return hp
 
 
-_TIMM_UNSUPPORTED = ("fc_norm.", "reg_token", "dist_token", "head_dist.", ".ls1.", ".ls2.", ".q_norm.", ".k_norm.", "attn_pool.")
+_TIMM_UNSUPPORTED = {"fc_norm.": "fc_norm", "dist_token": "a distillation token", "head_dist.": "a distillation head", ".q_norm.": "qk-norm", ".k_norm.": "qk-norm",
+                     "attn_pool.": "attention pooling"}
 
 
 def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2label=None) -> HParams:
@@ -84,22 +157,44 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
     /root/reference/convert-pth-to-ggml.py:96-158 without importing timm: hidden size, depth, classes, patch and image size come from the
     tensor shapes (the reference reads them off the timm module), `norm_pre.*` is skipped exactly as there (:117-120), the ViTSTR
     extension's checkpoints lose their "module.vitstr." prefix (extensions/vitstr.cpp/convert-pth-to-ggml.py:226-229) and are recognised
-    by their one-channel patch kernel.  Models with tensors the reference's loader has no slot for (fc_norm, layer-scale, register or
-    distillation tokens, qk-norm: vit.cpp:618-622 would reject the file) are refused here, by name."""
+    by their one-channel patch kernel.  DINOv2-class checkpoints are taken: `blocks.N.ls1.gamma` / `ls2.gamma` (LayerScale) are folded into
+    attn.proj / mlp.fc2 in f32, `reg_token` becomes the file's reg_token, and a `pos_embed` of g^2 rows (timm's no_embed_class layout of the
+    reg4 DINOv2 models: the class token gets no position term there) gets a zero row in front, which is exact.  Models with other tensors
+    the file has no slot for (fc_norm, distillation tokens, qk-norm, attention pooling) are refused here, by name."""
     sd = {k: v for k, v in (sd.get("model", sd) if isinstance(sd, dict) and "model" in sd and not hasattr(sd["model"], "shape") else sd).items()}
     t: Dict[str, np.ndarray] = {}
     for k, v in sd.items():
         k = k.replace("module.vitstr.", "")
         if k.startswith("norm_pre"):
             continue
-        if any(u in k for u in _TIMM_UNSUPPORTED):
-            raise ValueError(f"tensor {k!r}: this timm variant has components the reference's file format has no slot for")
+        for u, what in _TIMM_UNSUPPORTED.items():
+            if u in k:
+                raise ValueError(f"tensor {k!r}: {what} is not supported (the file format has no slot for it)")
         t[k] = np.ascontiguousarray(np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, np.float32))
     for need in ("cls_token", "pos_embed", "patch_embed.proj.weight", "patch_embed.proj.bias", "norm.weight", "norm.bias", "head.weight", "head.bias"):
         if need not in t:
             raise ValueError(f"not a timm VisionTransformer state_dict: {need!r} is missing")
     D = int(t["cls_token"].shape[-1])
     L = 1 + max(int(k.split(".")[1]) for k in t if k.startswith("blocks."))
+    # LayerScale: folded, no file slot.  A model has it on both branches of every block or not at all: a partial set is a damaged checkpoint
+    ls_keys = [f"blocks.{i}.{ls}.gamma" for i in range(L) for ls in ("ls1", "ls2")]
+    ls_have = [k for k in ls_keys if k in t]
+    if ls_have and len(ls_have) != len(ls_keys):
+        raise ValueError(f"LayerScale is incomplete: {ls_have[0]!r} is present, {next(k for k in ls_keys if k not in t)!r} is missing")
+    for gk in ls_have:
+        p = gk.replace(".ls1.gamma", ".attn.proj.").replace(".ls2.gamma", ".mlp.fc2.")
+        t[p + "weight"], t[p + "bias"] = fold_layer_scale(t[p + "weight"], t[p + "bias"], t.pop(gk))
+    n_rows = int(t["pos_embed"].shape[1])
+    if "reg_token" in t and int(round(n_rows ** 0.5)) ** 2 == n_rows and n_rows > 1:       # no_embed_class: g^2 rows, none for the class token
+        t["pos_embed"] = np.ascontiguousarray(np.concatenate([np.zeros((1, 1, D), np.float32), t["pos_embed"]], axis=1))
+    if "reg_token" in t:                                       # the file's order: directly after cls_token
+        reg = t.pop("reg_token")
+        ordered: Dict[str, np.ndarray] = {}
+        for k, v in t.items():
+            ordered[k] = v
+            if k == "cls_token":
+                ordered["reg_token"] = reg
+        t = ordered
     Dw, cin, P, P2 = t["patch_embed.proj.weight"].shape
     n_tok = int(t["pos_embed"].shape[1])
     g = int(round((n_tok - 1) ** 0.5))
@@ -119,7 +214,7 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
         from .synth import VITSTR_LABELS
         if hp.num_classes == len(VITSTR_LABELS):
             id2label = dict(VITSTR_LABELS)
-    expected = 4 + 12 * L + 4
+    expected = 4 + 12 * L + 4 + (1 if "reg_token" in t else 0)
     if len(t) != expected:
         raise ValueError(f"{len(t)} tensors after filtering, the file format holds exactly {expected} for {L} layers (vit.cpp:512-574)")
     write_model(path, hp, t, id2label=id2label, ftype=ftype)
@@ -131,13 +226,16 @@ def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("model"); ap.add_argument("out"); ap.add_argument("--ftype", type=int, default=1, help="0 f32, 1 f16 (default), 2/3/6/7/8 q4_0/q4_1/q5_0/q5_1/q8_0")
     ap.add_argument("--vitstr", action="store_true", help="one-channel ViTSTR scene-text model: write the character set as labels")
+    ap.add_argument("--no-head", action="store_true", help="a DINOv2 backbone (Dinov2Model / Dinov2WithRegistersModel): the file gets a one-class head of zeros "
+                                                           "labelled '(no head)'; read the embeddings with --embed / vitx_feat_*")
     ap.add_argument("--timm-state-dict", action="store_true", help="`model` is a torch-saved timm VisionTransformer state_dict (.pth); no timm import needed")
     ap.add_argument("--heads", type=int, default=0, help="attention heads of a timm checkpoint (inferred only for the widths of released timm ViTs; required otherwise)")
     ap.add_argument("--labels", default=None, help="JSON file {class id: label} for a timm checkpoint (default: none are written)")
     ap.add_argument("--img-size", type=int, default=0, metavar="N",
                     help="write the file at N x N instead of the checkpoint's size: pos_embed is resampled (vitx_model_resize_file), nothing else changes")
     ap.add_argument("--pos-interp", default="bicubic", choices=["bicubic", "bicubic-aa"],
-                    help="with --img-size: F.interpolate(mode='bicubic') without (HuggingFace, DINO) or with antialias=True (timm)")
+                    help="with --img-size: F.interpolate(mode='bicubic') without (HuggingFace ViT / Dinov2, DINO) or with antialias=True (timm; "
+                         "transformers 5.x for Dinov2WithRegisters)")
     a = ap.parse_args(argv)
 
     def resized(hp):
@@ -163,8 +261,11 @@ def main(argv=None) -> int:
         print(f"wrote {a.out}: hidden {hp.hidden_size}, layers {hp.num_hidden_layers}, heads {hp.num_attention_heads}, classes {hp.num_classes}, patch {hp.patch_size}, img {hp.img_size}, ftype {a.ftype}")
         return 0
     import transformers
-    m = transformers.ViTForImageClassification.from_pretrained(a.model).eval()
-    hp = resized(convert_hf_model(m, a.out, a.ftype, vitstr=a.vitstr))
+    if transformers.AutoConfig.from_pretrained(a.model).model_type in ("dinov2", "dinov2_with_registers"):
+        m = (transformers.AutoModel if a.no_head else transformers.AutoModelForImageClassification).from_pretrained(a.model).eval()
+    else:
+        m = transformers.ViTForImageClassification.from_pretrained(a.model).eval()
+    hp = resized(convert_hf_model(m, a.out, a.ftype, vitstr=a.vitstr, no_head=a.no_head))
     print(f"wrote {a.out}: hidden {hp.hidden_size}, layers {hp.num_hidden_layers}, heads {hp.num_attention_heads}, classes {hp.num_classes}, patch {hp.patch_size}, img {hp.img_size}, ftype {a.ftype}")
     return 0
 

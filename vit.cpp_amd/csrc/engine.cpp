@@ -36,11 +36,11 @@ namespace {
 
 enum ProfClass {
     PC_GEMM_PATCH = 0, PC_LAYERNORM, PC_GEMM_QKV, PC_ATTENTION, PC_GEMM_PROJ, PC_GEMM_FC1, PC_GEMM_FC2,
-    PC_GEMM_HEAD, PC_SOFTMAX, PC_DEQUANT, PC_ATTENTION_CLS, PC_GEMM_TAIL, PC_ATTN_MAP, PC_FEATURES, PC_COUNT
+    PC_GEMM_HEAD, PC_SOFTMAX, PC_DEQUANT, PC_ATTENTION_CLS, PC_GEMM_TAIL, PC_ATTN_MAP, PC_FEATURES, PC_HEAD_POOL, PC_COUNT
 };
 const char *kProfNames[PC_COUNT] = {"patch_embed", "layernorm", "gemm_qkv_bias", "attention", "gemm_proj_resid",
                                     "gemm_fc1_gelu", "gemm_fc2_resid", "gemm_head", "softmax", "dequant_weights", "attention_cls", "gemm_cls_tail", "attention_map",
-                                    "features"};
+                                    "features", "head_pool"};
 static_assert(PC_COUNT <= VITX_PROF_MAX_CLASSES, "vitx_profile_read callers size their arrays by VITX_PROF_MAX_CLASSES");
 
 // A weight matrix kept in the file's block form on the device (quant.hip): `blocks` = N rows of K/32 blocks in the file's byte
@@ -75,6 +75,10 @@ struct vitx_ctx {
     int D = 0, L = 0, H = 0, C = 0, P = 0, S = 0, g = 0, N = 0, Kpe = 0, Kpe_pad = 0, C_pad = 0;
     int Cin = 3;                         // input channels: 3 (RGB classifier) or 1 (ViTSTR, grey)
     int R = 1;                           // probability rows per image: 1 (cls token) or 25 (ViTSTR: tokens 0..24, vitstr.cpp:864-904)
+    // Token layout of an image (include/vitx.h "Register tokens and the pooled head"): row 0 = class token, rows 1 .. nreg = register tokens,
+    // rows Tp .. N - 1 = patches in raster order; N = g * g + Tp
+    int nreg = 0, Tp = 1;                // register tokens of the model (reg_token), prefix tokens 1 + nreg
+    bool pool = false;                   // VITX_POOL_CLS_MEAN: the head reads concat(cls, mean of the patch tokens) of the final norm, K = 2 D
     int tm = 128, tn = 128;
     const Tuning *tune = nullptr;        // per-device launch parameters (CU count, kernel selection), immutable
     int split_first = 0;                 // vitx_ctx_options::split_first: images of the first of two sub-batches (0 = the tile-round model)
@@ -88,7 +92,7 @@ struct vitx_ctx {
     struct WeightSet {
         int device = 0;
         std::vector<void *> allocs;
-        float *cls = nullptr, *pos = nullptr, *pe_b = nullptr, *norm_w = nullptr, *norm_b = nullptr, *head_b = nullptr;
+        float *cls = nullptr, *reg = nullptr, *pos = nullptr, *pe_b = nullptr, *norm_w = nullptr, *norm_b = nullptr, *head_b = nullptr;
         void *pe_w = nullptr, *head_w = nullptr;
         QuantW head_q;
         std::vector<LayerW> layers;
@@ -100,7 +104,7 @@ struct vitx_ctx {
         }
     };
     std::shared_ptr<WeightSet> wset;     // never null once the context exists
-    const float *pos = nullptr;          // [N][D] position table the patch embedding adds: wset->pos, or pos_own when img_size differs from the file's
+    const float *pos = nullptr;          // [1 + g * g][D] position table the patch embedding adds: wset->pos, or pos_own when img_size differs from the file's
     float *pos_own = nullptr;            // the table resampled to this context's grid (vitx_ctx_options::img_size, pos_interp); in `allocs`
     bool weights_shared = false;         // this context found the set already uploaded (vitx_ctx_shares_weights)
     // quantised files: vitx_ctx_options::quant_on_host restores the r01 behaviour (expand once on the host at upload, 16 bits per weight in HBM)
@@ -152,7 +156,7 @@ struct vitx_ctx {
         long qkv_lo_off = 0;
         void *Hbuf = nullptr;        // [Mpad][4D]  (also the im2col rows of the patch-embed GEMM)
         float *Xc = nullptr;         // [Bpad][D] f32 class-token rows of the residual stream through the last layer's tail (cls_tail)
-        void *Z = nullptr;           // [Bpad][D] final-LN output of the cls rows
+        void *Z = nullptr;           // [Bpad][D] final-LN output of the cls rows; pooled head: [Bpad][2 D] = RNE(cls) ‖ RNE(mean of the patch rows)
         // VITX_MXFP8: norm1 and norm2 outputs [Mpad][k_pad(D)] + scales; the fc1 output [Mpad][4D] + scales lives in Hbuf
         uint8_t *Umx = nullptr, *Umx_s = nullptr, *U2mx = nullptr, *U2mx_s = nullptr, *Hmx = nullptr, *Hmx_s = nullptr;
         void *Wq[W_PER_LAYER] = {nullptr, nullptr, nullptr, nullptr};   // just-in-time expansion of the current layer's quantised matrices
@@ -192,9 +196,9 @@ struct vitx_ctx {
     int feat_fpi = 0;            // floats per image: popcount(mask) * feat_layer_floats()
     int feat_cap = 0;            // images the buffer holds (= the images one pass takes)
     int feat_n = 0;              // images of the last forward made with features on (0: none since vitx_feat_enable)
-    float *feat_out = nullptr;   // [feat_cap][feat_fpi]: per image the selected layers in ascending order, each [cls D][mean D][tokens (N-1) D] (selected parts only)
+    float *feat_out = nullptr;   // [feat_cap][feat_fpi]: per image the selected layers in ascending order, each [cls D][mean D][tokens (N-Tp) D] (selected parts only)
     bool feat_on() const { return feat_flags != 0; }
-    int feat_layer_floats() const { return D * ((feat_flags & VITX_FEAT_CLS ? 1 : 0) + (feat_flags & VITX_FEAT_MEAN ? 1 : 0) + (feat_flags & VITX_FEAT_TOKENS ? N - 1 : 0)); }
+    int feat_layer_floats() const { return D * ((feat_flags & VITX_FEAT_CLS ? 1 : 0) + (feat_flags & VITX_FEAT_MEAN ? 1 : 0) + (feat_flags & VITX_FEAT_TOKENS ? N - Tp : 0)); }
     // MEAN or TOKENS of the last layer need every row of it: no class-rows-only tail while they are on (as while the trace is)
     bool feat_last_all_rows() const { return (feat_flags & (VITX_FEAT_MEAN | VITX_FEAT_TOKENS)) && ((feat_mask >> (L - 1)) & 1); }
     void feat_free() { if (feat_out) (void)hipFree(feat_out); feat_out = nullptr; }
@@ -411,6 +415,8 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
         set_error("vitx_ctx_create_ex: img_size %d is not a positive multiple of the patch size %d", opt.img_size, m->hp.patch_size); return VITX_ERR_ARG;
     }
     const int img_size = opt.img_size > 0 ? opt.img_size : m->hp.img_size;
+    if (m->in_chans == 1 && (m->num_registers || m->head_pool != VITX_POOL_CLS)) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes neither register tokens nor the pooled head"); return VITX_ERR_UNSUPPORTED; }
+    if (dtype == VITX_MXFP8 && (m->num_registers || m->head_pool != VITX_POOL_CLS)) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts do not take models with register tokens or the pooled head"); return VITX_ERR_UNSUPPORTED; }
     if (m->in_chans == 1 && img_size != m->hp.img_size) { set_error("vitx_ctx_create_ex: a ViTSTR context stays at the file's img_size (%d)", m->hp.img_size); return VITX_ERR_UNSUPPORTED; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("vitx_ctx_create: no HIP device available (this engine has no CPU fallback)"); return VITX_ERR_HIP; }
@@ -427,7 +433,8 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
     c->mx = dtype == VITX_MXFP8; c->dtype = c->mx ? VITX_BF16 : dtype;      // everything but the MX GEMMs runs as in a VITX_BF16 context
     c->D = hp.hidden_size; c->L = hp.num_hidden_layers; c->H = hp.num_attention_heads; c->C = hp.num_classes; c->P = hp.patch_size; c->S = img_size;
     c->Cin = m->in_chans; c->R = m->in_chans == 1 ? VITX_VITSTR_SEQ_LEN : 1;
-    c->g = c->S / c->P; c->N = c->g * c->g + 1; c->Kpe = c->Cin * c->P * c->P; c->Kpe_pad = round_up(c->Kpe, 64);
+    c->nreg = m->num_registers; c->Tp = 1 + c->nreg; c->pool = m->head_pool == VITX_POOL_CLS_MEAN;
+    c->g = c->S / c->P; c->N = c->g * c->g + c->Tp; c->Kpe = c->Cin * c->P * c->P; c->Kpe_pad = round_up(c->Kpe, 64);
     if (c->N < c->R) { set_error("vitx_ctx_create: a ViTSTR head reads %d tokens, this model has %d (img_size %d, patch_size %d)", c->R, c->N, c->S, c->P); return VITX_ERR_UNSUPPORTED; }
     c->tm = gemm_tile_m(); c->tn = gemm_tile_n();
     c->C_pad = round_up(c->C, c->tn);
@@ -442,7 +449,8 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
     c->split_first = opt.split_first;
     c->prec_attn = dtype == VITX_F16 && c->D == c->H * 64 && !opt.f16_fast_attention;
     c->quant_on_device = !opt.quant_on_host;
-    c->cls_tail = !opt.last_layer_all_rows && c->R == 1 && attention_cls_supports(c->N, c->D, c->H);
+    // the pooled head averages every patch row of the last layer: such a context runs exactly as one created with last_layer_all_rows = 1
+    c->cls_tail = !opt.last_layer_all_rows && !c->pool && c->R == 1 && attention_cls_supports(c->N, c->D, c->H);
     c->q4_fused_rows = opt.q4_fused_rows;
     c->graphs_on = opt.graph != 0;
     // fault injection for the parity tests: honoured only with the key in the upper half (VITX_LN_TEST_KEY | mode), so that no caller sets it by accident
@@ -475,6 +483,7 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
         vitx_ctx::WeightSet &ws = *c->wset;
         ws.device = device;
         if ((rc = upload_f32(c.get(), T("cls_token"), &ws.cls))) return rc;
+        if (c->nreg && (rc = upload_f32(c.get(), T("reg_token"), &ws.reg))) return rc;
         if ((rc = upload_f32(c.get(), T("pos_embed"), &ws.pos))) return rc;
         if ((rc = upload_f32(c.get(), T("patch_embed.proj.bias"), &ws.pe_b, round_up(D, tn)))) return rc;
         if ((rc = upload_matrix(c.get(), T("patch_embed.proj.weight"), D, c->Kpe, round_up(D, tn), c->Kpe_pad, &ws.pe_w, c->P, c->Cin))) return rc;
@@ -505,7 +514,7 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
         if ((rc = upload_f32(c.get(), T("norm.weight"), &ws.norm_w))) return rc;
         if ((rc = upload_f32(c.get(), T("norm.bias"), &ws.norm_b))) return rc;
         if ((rc = upload_f32(c.get(), T("head.bias"), &ws.head_b, c->C_pad))) return rc;
-        if ((rc = upload_weight(c.get(), T("head.weight"), c->C, D, c->C_pad, &ws.head_w, &ws.head_q))) return rc;
+        if ((rc = upload_weight(c.get(), T("head.weight"), c->C, c->pool ? 2 * D : D, c->C_pad, &ws.head_w, &ws.head_q))) return rc;
         wreg[wkey] = c->wset;
     }
     wlock.unlock();
@@ -513,7 +522,7 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
     c->pos = c->wset->pos;
     if (c->S != hp.img_size) {
         const int g_in = hp.img_size / hp.patch_size;
-        if ((rc = c->dmalloc((void **)&c->pos_own, (size_t)c->N * D * 4, false))) return rc;
+        if ((rc = c->dmalloc((void **)&c->pos_own, (size_t)(c->g * c->g + 1) * D * 4, false))) return rc;
         HIP_TRY(launch_pos_resample(c->wset->pos, g_in, g_in, D, c->g, c->g, opt.pos_interp, c->pos_own, c->stream));
         c->pos = c->pos_own;                 // (the hipDeviceSynchronize at the end of the creation covers the launch)
     }
@@ -552,7 +561,7 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
         if ((rc = c->dmalloc(&sl.QKV, Mpad * 3 * D * 2 * (c->prec_attn ? 2 : 1), true))) return rc;
         sl.qkv_lo_off = c->prec_attn ? (long)(Mpad * 3 * D) : 0;       // capacity; a forward places the lo plane right behind ITS rows (forward_slice)
         if ((rc = c->dmalloc(&sl.Hbuf, Mpad * hcols * 2, true))) return rc;
-        if ((rc = c->dmalloc(&sl.Z, Bpad * D * 2, true))) return rc;
+        if ((rc = c->dmalloc(&sl.Z, Bpad * D * 2 * (c->pool ? 2 : 1), true))) return rc;
         if (c->mx) {
             const size_t kp = (size_t)mx_k_pad(D), kh = (size_t)mx_k_pad(4 * D);
             if ((rc = c->dmalloc((void **)&sl.Umx, Mpad * kp * 33 / 32, true))) return rc;
@@ -599,6 +608,7 @@ void vitx_ctx_free(vitx_ctx *c) { delete c; }
 int vitx_ctx_max_batch(const vitx_ctx *c) { return c ? c->max_batch : 0; }
 int vitx_ctx_img_size(const vitx_ctx *c) { return c ? c->S : 0; }
 int vitx_ctx_tokens(const vitx_ctx *c) { return c ? c->N : 0; }
+int vitx_ctx_registers(const vitx_ctx *c) { return c ? c->nreg : 0; }
 static void split_batch(const vitx_ctx *c, int n, int ns, int *m);
 int vitx_ctx_split(const vitx_ctx *c, int n, int32_t *images, int max_parts) {
     if (!c || !images || max_parts <= 0 || n <= 0 || n > c->max_batch) return 0;
@@ -665,32 +675,35 @@ static int forward_slice(vitx_ctx *c, vitx_ctx::Slice &sl, hipStream_t st, const
     };
     const vitx_ctx::WeightSet &ws = *c->wset;
     const int D = c->D, N = c->N, tm = c->tm, tn = c->tn, dt = c->dtype;
+    const double eb = 2.0;                                          // operand bytes
     // embeddings and token features of layer il (vitx_feat_enable), from the residual stream its fc2 has just completed: one launch writes this
     // sub-batch's images straight into the packed per-image layout.  cls_rows: X is the compact class rows Xc of the class-rows-only last layer.
-    auto features = [&](int il, bool cls_rows) -> int {
-        if (!((c->feat_mask >> il) & 1)) return VITX_OK;
-        const int fl = c->feat_flags;
+    // z != nullptr (the last layer of a pooled-head context): the same launch also writes the head's operand rows RNE(cls) ‖ RNE(mean), with or
+    // without features of that layer selected -- one pass over the residual stream serves both.
+    auto features = [&](int il, bool cls_rows, void *z = nullptr) -> int {
+        const bool sel = c->feat_on() && ((c->feat_mask >> il) & 1);
+        if (!sel && !z) return VITX_OK;
+        const int fl = sel ? c->feat_flags : 0, Tp = c->Tp;
         float *o = c->feat_out + (size_t)first_img * c->feat_fpi + (size_t)__builtin_popcountll(c->feat_mask & ((1ull << il) - 1)) * c->feat_layer_floats();
         float *o_cls = nullptr, *o_mean = nullptr, *o_tok = nullptr;
         if (fl & VITX_FEAT_CLS) { o_cls = o; o += D; }
         if (fl & VITX_FEAT_MEAN) { o_mean = o; o += D; }
         if (fl & VITX_FEAT_TOKENS) o_tok = o;
-        const double rows = (double)n * ((o_cls ? 1 : 0) + (o_mean || o_tok ? N - 1 : 0));
-        ProfScope ps(c, st, PC_FEATURES, 0, rows * D * 4 + (double)n * D * 4 * ((o_cls ? 1 : 0) + (o_mean ? 1 : 0) + (o_tok ? N - 1 : 0)));
+        const double rows = (double)n * ((o_cls || z ? 1 : 0) + (o_mean || o_tok || z ? N - Tp : 0));
+        ProfScope ps(c, st, sel ? PC_FEATURES : PC_HEAD_POOL, 0, rows * D * 4 + (double)n * D * 4 * ((o_cls ? 1 : 0) + (o_mean ? 1 : 0) + (o_tok ? N - Tp : 0)) + (z ? (double)n * 2 * D * eb : 0.0));
         HIP_TRY(launch_features(cls_rows ? sl.Xc : sl.X, D, cls_rows ? (long)D : (long)N * D, ws.norm_w, ws.norm_b, o_cls, o_mean, o_tok, c->feat_fpi,
-                                n, cls_rows ? 1 : N, D, c->hp.eps, (fl & VITX_FEAT_L2) != 0, st));
+                                n, cls_rows ? 1 : N, D, c->hp.eps, (fl & VITX_FEAT_L2) != 0, st, cls_rows ? 1 : Tp, z, dt));
         return VITX_OK;
     };
     const int Mp_real = n * c->g * c->g;                           // patch rows
     const int M_real = n * N, M = round_up(M_real, tm);            // token rows
-    const double eb = 2.0;                                          // operand bytes
     const long lo_off = c->prec_attn ? (long)M * 3 * D : 0;         // F16 parity mode: the lo plane of q, k, v right behind this sub-batch's hi plane (elements)
 
     // patch embedding (vit.cpp:747-797) in one launch: im2col gather, GEMM, + bias + pos, token scatter, class rows (patch_embed.hip)
     int rc;
     {
         ProfScope ps(c, st, PC_GEMM_PATCH, 2.0 * Mp_real * (double)D * c->Kpe, (double)n * c->S * c->S * c->Cin * 4 + (double)M_real * D * 4);
-        HIP_TRY(launch_patch_embed(dt, (const float *)d_imgs, ws.pe_w, ws.pe_b, c->pos, ws.cls, sl.X, n, c->S, c->P, c->Cin, D, round_up(D, tn), c->Kpe_pad, st));
+        HIP_TRY(launch_patch_embed(dt, (const float *)d_imgs, ws.pe_w, ws.pe_b, c->pos, ws.cls, ws.reg, c->nreg, sl.X, n, c->S, c->P, c->Cin, D, round_up(D, tn), c->Kpe_pad, st));
     }
     if (!c->trace_ids.empty() && (rc = trace(0))) return rc;
     // Quantised matrices (block form in HBM): a q4_0 GEMM with few rows expands the blocks in its own LDS-fill path; everything else
@@ -823,13 +836,15 @@ static int forward_slice(vitx_ctx *c, vitx_ctx::Slice &sl, hipStream_t st, const
                        fix_u2.todo ? &fix_u2 : nullptr))) return rc;
         if ((rc = resid_gemm_ln(r, r.pc_fc2, sl.Hbuf, Wl[W_FC2], w.fc2_b, 4 * D, Fl[W_FC2], nx ? nx->ln1_w : nullptr, nx ? nx->ln1_b : nullptr, sl.U, &fix_u))) return rc;
         if (!c->trace_ids.empty() && (rc = trace(il + 1))) return rc;
-        if (c->feat_on() && (rc = features(il, tail_now))) return rc;
+        if ((rc = features(il, tail_now, c->pool && il + 1 == c->L ? sl.Z : nullptr))) return rc;
     }
     // cls pooling + final norm (vit.cpp:910-919): row b*N of X, i.e. row stride N*D.  ViTSTR (vitstr.cpp:864-895) keeps the first
     // R = 25 tokens of every image instead: output row r = image r / R, token r % R.
     const int nR = n * c->R;
     // classifier: one row per image, row stride N*D; ViTSTR: groups of R consecutive token rows (stride D), group stride N*D
-    if (tail) rc = layernorm(sl.Xc, D, ws.norm_w, ws.norm_b, sl.Z, n);
+    // pooled head: Z [n][2 D] was written by the last layer's feature launch above (final norm of row 0 ‖ mean of the patch rows' final norm)
+    if (c->pool) rc = VITX_OK;
+    else if (tail) rc = layernorm(sl.Xc, D, ws.norm_w, ws.norm_b, sl.Z, n);
     else rc = layernorm(sl.X, c->R == 1 ? (long)N * D : (long)D, ws.norm_w, ws.norm_b, sl.Z, nR, c->R, (long)N * D);
     if (rc) return rc;
     // classifier (vit.cpp:927-928) and class softmax (vit.cpp:931-933)
@@ -840,7 +855,7 @@ static int forward_slice(vitx_ctx *c, vitx_ctx::Slice &sl, hipStream_t st, const
         if (fused_ok(ws.head_q, round_up(nR, tm))) head_f = &ws.head_q;
         else { const QuantW *todo[1] = {&ws.head_q}; void *dst[1] = {sl.Wq_head}; if ((rc = expand(todo, dst, 1))) return rc; head_w = sl.Wq_head; }
     }
-    if ((rc = gemm(c, st, PC_GEMM_HEAD, EPI_BIAS_F32, dense_gemm(sl.Z, head_w, ws.head_b, lg, round_up(nR, tm), nR, c->C, c->C_pad, D, ldl), head_f))) return rc;
+    if ((rc = gemm(c, st, PC_GEMM_HEAD, EPI_BIAS_F32, dense_gemm(sl.Z, head_w, ws.head_b, lg, round_up(nR, tm), nR, c->C, c->C_pad, c->pool ? 2 * D : D, ldl), head_f))) return rc;
     {
         ProfScope ps(c, st, PC_SOFTMAX, 0, (double)nR * c->C * 8);
         HIP_TRY(launch_softmax(dt, lg, (float *)d_probs, nR, c->C, ldl, st));
@@ -1496,6 +1511,48 @@ int vitx_op_features(const void *d_x, long row_stride, long img_stride, const vo
     hipError_t e = launch_features((const float *)d_x, row_stride, img_stride, (const float *)d_w, (const float *)d_b, (float *)d_cls, (float *)d_mean, (float *)d_tokens,
                                    out_img_stride, n_img, N, D, eps, l2 != 0, (hipStream_t)stream);
     if (e != hipSuccess) { set_error("vitx_op_features: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
+    return VITX_OK;
+}
+int vitx_op_features_ex(const void *d_x, long row_stride, long img_stride, const void *d_w, const void *d_b, void *d_cls, void *d_mean, void *d_tokens, long out_img_stride,
+                        int n_img, int N, int first, int D, float eps, int l2, void *d_z, int dtype, void *stream) {
+    if (!d_x || !d_w || !d_b || (!d_cls && !d_mean && !d_tokens && !d_z) || n_img <= 0 || N <= 0 || D <= 0 || first < 1 || first > N) { set_error("vitx_op_features_ex: invalid argument"); return VITX_ERR_ARG; }
+    if (first == N && (d_mean || d_tokens || d_z)) { set_error("vitx_op_features_ex: the mean and the tokens need at least one patch row (N %d, first %d)", N, first); return VITX_ERR_ARG; }
+    if (d_z && dtype != VITX_F16 && dtype != VITX_BF16) { set_error("vitx_op_features_ex: the head operand is VITX_F16 or VITX_BF16"); return VITX_ERR_ARG; }
+    for (const void *p : {d_x, d_w, d_b, (const void *)d_cls, (const void *)d_mean, (const void *)d_tokens, (const void *)d_z})
+        if ((uintptr_t)p % 16) { set_error("vitx_op_features_ex: pointers must be 16-byte aligned"); return VITX_ERR_ARG; }
+    if (row_stride % 4 || img_stride % 4 || out_img_stride % 4) { set_error("vitx_op_features_ex: strides must be multiples of 4 floats"); return VITX_ERR_ARG; }
+    if (!layernorm_supports(D)) { set_error("vitx_op_features_ex: hidden size %d has no LayerNorm instantiation", D); return VITX_ERR_UNSUPPORTED; }
+    hipError_t e = launch_features((const float *)d_x, row_stride, img_stride, (const float *)d_w, (const float *)d_b, (float *)d_cls, (float *)d_mean, (float *)d_tokens,
+                                   out_img_stride, n_img, N, D, eps, l2 != 0, (hipStream_t)stream, first, d_z, dtype == VITX_BF16 ? DT_BF16 : DT_F16);
+    if (e != hipSuccess) { set_error("vitx_op_features_ex: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
+    return VITX_OK;
+}
+// The product's patch-embedding kernel on its own (TEST ONLY: allocates, uploads and synchronises).  d_w: the f32 kernel [D][Cin * P * P] in the
+// file's order (channel-major); it is rounded (RNE) to the operand type, K-permuted and padded exactly as the context does at upload.
+int vitx_op_patch_embed(int dtype, const void *d_img, const void *d_w, const void *d_bias, const void *d_pos, const void *d_cls, const void *d_reg, int R, void *d_X,
+                        int n_img, int S, int P, int Cin, int D, void *stream) {
+    if (!d_img || !d_w || !d_bias || !d_pos || !d_cls || !d_X || R < 0 || (R > 0 && !d_reg) || n_img <= 0 || S <= 0 || P <= 0 || S % P || Cin <= 0 || D <= 0 || D % 4 ||
+        (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_patch_embed: invalid argument"); return VITX_ERR_ARG; }
+    if (!tuning_for_device(-1)) { set_error("vitx_op_patch_embed: kernel bring-up failed"); return VITX_ERR_HIP; }
+    const int K = Cin * P * P, k_pad = round_up(K, 64), n_pad = round_up(D, gemm_tile_n());
+    std::vector<float> wf((size_t)D * K);
+    HIP_TRY(hipMemcpy(wf.data(), d_w, wf.size() * 4, hipMemcpyDeviceToHost));
+    std::vector<uint16_t> h((size_t)n_pad * k_pad, 0), hp(h.size(), 0);
+    for (int n = 0; n < D; ++n)
+        for (int k = 0; k < K; ++k) h[(size_t)n * k_pad + k] = dtype == VITX_F16 ? f32_to_f16_bits(wf[(size_t)n * K + k]) : f32_to_bf16_bits(wf[(size_t)n * K + k]);
+    patch_embed_permute_k(h.data(), hp.data(), D, Cin, P, k_pad);
+    void *w_perm = nullptr; float *bias = nullptr;
+    HIP_TRY(hipMalloc(&w_perm, hp.size() * 2));
+    if (hipMalloc((void **)&bias, (size_t)n_pad * 4) != hipSuccess) { (void)hipFree(w_perm); return VITX_ERR_NOMEM; }
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemcpy(w_perm, hp.data(), hp.size() * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(bias, 0, (size_t)n_pad * 4);
+    if (e == hipSuccess) e = hipMemcpy(bias, d_bias, (size_t)D * 4, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = launch_patch_embed(dtype == VITX_F16 ? DT_F16 : DT_BF16, (const float *)d_img, w_perm, bias, (const float *)d_pos, (const float *)d_cls, (const float *)d_reg, R,
+                                                (float *)d_X, n_img, S, P, Cin, D, n_pad, k_pad, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(w_perm); (void)hipFree(bias);
+    if (e != hipSuccess) { set_error("vitx_op_patch_embed: %s", hipGetErrorString(e)); return e == hipErrorInvalidValue ? VITX_ERR_UNSUPPORTED : VITX_ERR_HIP; }
     return VITX_OK;
 }
 // The map kernels on their own (the parity tests): d_cls [n_img][H][N] class-token rows, d_mean [n_img][N][N] mean_h A_h (either may be NULL).

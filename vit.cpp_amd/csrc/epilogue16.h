@@ -80,9 +80,9 @@ __device__ __forceinline__ void epilogue16(const GemmArgs &g, f32x4 (&acc)[TM][T
                 const int row = row0 + t * 16;
                 add[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
                 const bool row_ok = FULL || row < g.M_real;
-                if constexpr (EPI == EPI_PATCH) {           // patch row -> token row (+1 per image for the cls slot), + position embedding
+                if constexpr (EPI == EPI_PATCH) {           // patch row -> token row (+ the prefix rows of images 0 .. b: cls and registers), + position embedding
                     const int b = row / g.tpi, tk = row - b * g.tpi;
-                    o[t] = (float *)g.out + ((size_t)row + b + 1) * g.ldo + c;
+                    o[t] = (float *)g.out + ((size_t)row + (size_t)(b + 1) * g.prefix) * g.ldo + c;
                     const float *pe = g.pos + (size_t)(tk + 1) * g.ldo + c;
                     if (row_ok) {
                         if (vec) add[t] = *(const f32x4 *)pe;

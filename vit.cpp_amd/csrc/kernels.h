@@ -14,7 +14,7 @@ enum {
     EPI_BIAS_GELU = 1,   // out(dtype)[m][n] = gelu_tanh(round(acc + bias[n]))     fc1      (vit.cpp:889-893)
     EPI_BIAS_RESID = 2,  // out(f32)[m][n]   = (acc + bias[n]) + out[m][n]         proj/fc2 (vit.cpp:868-873, 896-900)
     EPI_BIAS_F32 = 3,    // out(f32)[m][n]   = acc + bias[n]                       head     (vit.cpp:927-928)
-    EPI_PATCH = 4,       // out(f32)[m + m/tpi + 1][n] = (acc + bias[n]) + pos[(m%tpi + 1)][n]   (vit.cpp:772-797)
+    EPI_PATCH = 4,       // out(f32)[m + (m/tpi + 1) * prefix][n] = (acc + bias[n]) + pos[(m%tpi + 1)][n]   (vit.cpp:772-797; prefix = 1 there)
     EPI_BIAS_HILO = 5    // qkv of the F16 parity mode: v = acc + bias[n] kept to f32 grade as TWO 16-bit planes, out[m][n] = hi = round(v) and
                          // out[hilo_off + ..] = lo = round((v - hi) * 2048): the reference's q, k, v stay f32 into the attention products
                          // (vit.cpp:826-858: ggml_mul_mat of f32 views), and hi + lo / 2048 reproduces v to 2^-22
@@ -32,6 +32,7 @@ struct GemmArgs {
     int K;        // multiple of 64
     int lda, ldw, ldo;
     int tpi;      // EPI_PATCH: patch tokens per image (g*g)
+    int prefix = 1;  // EPI_PATCH: tokens of an image in front of its patches: the class token + R register tokens (an image has tpi + prefix rows)
     long hilo_off;  // EPI_BIAS_HILO: ELEMENT offset of the lo plane behind `out` (a whole number of rows; the byte offset must fit 32 bits)
     int dbg;      // ablation bits of the ring kernel's laboratory build (VITX_LAB only; 0 in the product)
     // q4_0 weights kept in block form (launch_gemm_q4 only): W = nibble plane [N_pad][K/2] bytes (16 per block), Wscale = f16 block
@@ -125,11 +126,13 @@ hipError_t launch_layernorm_fixup(int dtype, const float *x, const float *w, con
 int gemm_tile_m();   // M granularity the GEMM needs (buffer row padding)
 int gemm_tile_n();
 
-// Patch embedding in one launch (patch_embed.hip; vit.cpp:747-797): X[b * N + 1 + t][:] = W . patch(b, t) + bias + pos[1 + t], X[b * N][:] = cls + pos[0].
+// Patch embedding in one launch (patch_embed.hip; vit.cpp:747-797): with T = 1 + n_reg prefix tokens and N = T + patches rows per image,
+// X[b * N + T + t][:] = W . patch(b, t) + bias + pos[1 + t], X[b * N][:] = cls + pos[0], X[b * N + 1 + r][:] = reg[r] (no position term).
 // img: f32 HWC [n_img][S][S][Cin] (Cin = 3: RGB classifier input; 1: the grey ViTSTR input, extensions/vitstr.cpp/vitstr.cpp:713-731);
-// w_perm: the [n_pad][k_pad] operand-type kernel with its K axis permuted by patch_embed_permute_k (host side, at upload); pos [N][D], cls [D].
-hipError_t launch_patch_embed(int dtype, const float *img, const void *w_perm, const float *bias, const float *pos, const float *cls, float *X,
-                              int n_img, int S, int P, int Cin, int D, int n_pad, int k_pad, hipStream_t stream, bool prepare = false);
+// w_perm: the [n_pad][k_pad] operand-type kernel with its K axis permuted by patch_embed_permute_k (host side, at upload); pos [1 + patches][D],
+// cls [D], reg [n_reg][D] (nullptr when n_reg == 0).
+hipError_t launch_patch_embed(int dtype, const float *img, const void *w_perm, const float *bias, const float *pos, const float *cls, const float *reg, int n_reg,
+                              float *X, int n_img, int S, int P, int Cin, int D, int n_pad, int k_pad, hipStream_t stream, bool prepare = false);
 void patch_embed_permute_k(const uint16_t *w, uint16_t *w_perm, int N, int Cin, int P, int k_pad);
 // y[r][:] (dtype) = LN(x[r*ldx ...]) * w + b   (vit.cpp:808-812)
 // group > 1: input row r = x + (r / group) * gstride + (r % group) * ldx (the first `group` tokens of every image: ViTSTR head)
@@ -160,11 +163,14 @@ hipError_t launch_attention_head_mean(int dtype, const void *qkv, long lo_off, f
 hipError_t launch_rollout_step(float *a, const float *r, int n_img, int N, hipStream_t stream);
 hipError_t launch_rollout_row(const float *cls, long cls_stride, const float *r, float *out, long out_stride, int n_img, int N, int H, hipStream_t stream);
 // Image embeddings and token features (features.hip; vitx_feat_enable): F = the f32 LayerNorm of launch_layernorm before its rounding.  Row t of
-// image i is read at x + i * img_stride + t * row_stride; cls[i * out_img_stride ..] = F[0], mean[..] = mean of F[1 .. N-1], tokens[..] = F[1 .. N-1]
-// ([N-1][D]); any output may be nullptr (row 0 is read only for cls, the other rows only for mean / tokens); l2: cls and mean divided by their norm.
+// image i is read at x + i * img_stride + t * row_stride; T = `first` is the first patch row (1 + the register tokens): cls[i * out_img_stride ..] =
+// F[0], mean[..] = mean of F[T .. N-1], tokens[..] = F[T .. N-1] ([N-T][D]); any output may be nullptr (row 0 is read only for cls / z, rows T ..
+// only for mean / tokens / z, rows 1 .. T-1 never); l2: cls and mean divided by their norm.
+// z != nullptr: the pooled head's operand (VITX_POOL_CLS_MEAN), z[i][0 .. D) = RNE(F[0]), z[i][D .. 2 D) = RNE(mean) in the operand type `dtype`,
+// rows of 2 D elements, rounded BEFORE any l2 -- the same launch that serves the features.
 // Every width of VITX_LN_WIDTHS; pointers 16-byte aligned, strides multiples of 4 floats.
 hipError_t launch_features(const float *x, long row_stride, long img_stride, const float *w, const float *b, float *cls, float *mean, float *tokens,
-                           long out_img_stride, int n_img, int N, int D, float eps, bool l2, hipStream_t stream);
+                           long out_img_stride, int n_img, int N, int D, float eps, bool l2, hipStream_t stream, int first = 1, void *z = nullptr, int dtype = DT_F16);
 // pos [1 + gy_in * gx_in][D] f32 -> out [1 + gy_out * gx_out][D] f32 (pos_resample.hip; the arithmetic: pos_resample.h); only enqueues
 hipError_t launch_pos_resample(const float *pos, int gy_in, int gx_in, int D, int gy_out, int gx_out, int interp, float *out, hipStream_t stream);
 bool attention_supports(int N, int D, int H);     // any token count; head_dim 64 (tuned kernels) or any other multiple of 8 up to 128 (generic kernel)

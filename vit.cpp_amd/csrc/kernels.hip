@@ -1448,7 +1448,7 @@ static hipError_t prepare_device_kernels(const Tuning &t) {
 #endif
             if ((e = (dt == DT_F16 ? launch_gemm_t<_Float16, true>(epi, none, nullptr, true) : launch_gemm_t<__bf16, true>(epi, none, nullptr, true))) != hipSuccess) return e;
         }
-        if (dt == 0 && (e = launch_patch_embed(0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0, nullptr, true)) != hipSuccess) return e;
+        if (dt == 0 && (e = launch_patch_embed(0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, 0, 0, 0, 0, 0, 0, nullptr, true)) != hipSuccess) return e;
         if ((e = (dt == DT_F16 ? launch_attention_flow<_Float16>(nullptr, nullptr, 0, 64, 64, 1, nullptr) : launch_attention_flow<__bf16>(nullptr, nullptr, 0, 64, 64, 1, nullptr))) != hipSuccess) return e;
         if ((e = launch_attention_stream(dt, false, nullptr, nullptr, 0, 64, 64, 1, 0, nullptr)) != hipSuccess) return e;
         if (dt == DT_F16 && (e = launch_attention_stream(dt, true, nullptr, nullptr, 0, 64, 64, 1, 0, nullptr)) != hipSuccess) return e;

@@ -7,6 +7,8 @@
 // (680-685), and every expected tensor must appear exactly once (697-701).  One deliberate
 // widening: patch_embed.proj.weight is accepted as f32 as well as f16 (the reference only
 // takes f16 there, vit.cpp:515, so "--ftype 0" files it cannot load are loadable here).
+// Two optional extensions the reference's loader has no slot for (DINOv2-class models; include/vitx.h "Register tokens and the pooled
+// head"), recognised by name and shape: `reg_token` f32 [1][R][D], and a `head.weight` of [C][2 D].
 #include "model_file.h"
 
 #include <stdarg.h>
@@ -155,12 +157,29 @@ static int load_impl(const char *path, vitx_model &m) {
         for (int i = 0; i < n_dims; ++i) { int32_t v; if (!rd_i32(v) || v <= 0) { set_error("vitx_model_load: bad dims"); return VITX_ERR_FORMAT; } t.ne[i] = v; }
         t.name.resize((size_t)name_len);
         if (fread(&t.name[0], 1, (size_t)name_len, f) != (size_t)name_len) { set_error("vitx_model_load: truncated name"); return VITX_ERR_IO; }
+        if (t.name == "reg_token") {                                 // optional: R register tokens, f32 [1][R][D] (ggml order [D, R, 1])
+            if (m.index.count(t.name)) { set_error("vitx_model_load: duplicate tensor '%s'", t.name.c_str()); return VITX_ERR_FORMAT; }
+            if (ttype != T_F32 || n_dims != 3 || t.ne[0] != hp.hidden_size || t.ne[1] < 1 || t.ne[1] > 4096 || t.ne[2] != 1) {
+                set_error("vitx_model_load: tensor 'reg_token' must be f32 [1][R][%d] with 1 <= R <= 4096: got type %d, %d dims [%lld, %lld, %lld]", hp.hidden_size, ttype, n_dims,
+                          (long long)t.ne[0], (long long)t.ne[1], (long long)t.ne[2]);
+                return VITX_ERR_FORMAT;
+            }
+            const size_t nbytes = (size_t)t.nelements() * 4;
+            t.raw.resize(nbytes);
+            if (fread(t.raw.data(), 1, nbytes, f) != nbytes) { set_error("vitx_model_load: tensor '%s' is truncated", t.name.c_str()); return VITX_ERR_IO; }
+            m.num_registers = (int)t.ne[1];
+            m.index[t.name] = (int)m.tensors.size();
+            m.tensors.push_back(std::move(t));
+            continue;
+        }
         auto it = expect.find(t.name);
         if (it == expect.end()) { set_error("vitx_model_load: unknown tensor '%s' in model file", t.name.c_str()); return VITX_ERR_FORMAT; }
         if (m.index.count(t.name)) { set_error("vitx_model_load: duplicate tensor '%s'", t.name.c_str()); return VITX_ERR_FORMAT; }
         Expect ex = it->second;
         // ViTSTR files (extensions/vitstr.cpp/vitstr.cpp:482) carry a ONE-channel patch kernel [P, P, 1, D]: same format otherwise
         if (t.name == "patch_embed.proj.weight" && t.ne[2] == 1 && t.ne[0] == ex.ne[0] && t.ne[1] == ex.ne[1] && t.ne[3] == ex.ne[3]) { ex.ne[2] = 1; m.in_chans = 1; }
+        // a head over concat(cls, mean of the patch tokens) has rows of 2 D (VITX_POOL_CLS_MEAN); any other row length fails the shape check below
+        if (t.name == "head.weight" && t.ne[0] == 2 * ex.ne[0] && t.ne[1] == ex.ne[1] && t.ne[2] == 1 && t.ne[3] == 1) { ex.ne[0] *= 2; m.head_pool = VITX_POOL_CLS_MEAN; }
         const int64_t want = ex.ne[0] * ex.ne[1] * ex.ne[2] * ex.ne[3];
         if (t.nelements() != want) { set_error("vitx_model_load: tensor '%s' has wrong size in model file: got %lld, expected %lld", t.name.c_str(), (long long)t.nelements(), (long long)want); return VITX_ERR_FORMAT; }
         if (t.ne[0] != ex.ne[0] || t.ne[1] != ex.ne[1] || t.ne[2] != ex.ne[2] || t.ne[3] != ex.ne[3]) {
@@ -180,8 +199,9 @@ static int load_impl(const char *path, vitx_model &m) {
         m.index[t.name] = (int)m.tensors.size();
         m.tensors.push_back(std::move(t));
     }
-    if (m.tensors.size() != expect.size()) {
-        set_error("vitx_model_load: model file has %d tensors, but %d tensors were expected", (int)m.tensors.size(), (int)expect.size());
+    const size_t n_expect = expect.size() + (m.num_registers ? 1 : 0);
+    if (m.tensors.size() != n_expect) {
+        set_error("vitx_model_load: model file has %d tensors, but %d tensors were expected", (int)m.tensors.size(), (int)n_expect);
         return VITX_ERR_FORMAT;
     }
     return VITX_OK;
@@ -220,6 +240,8 @@ int vitx_model_hparams(const vitx_model *m, vitx_hparams *out) {
 }
 int vitx_model_num_labels(const vitx_model *m) { return m ? (int)m->id2label.size() : 0; }
 int vitx_model_in_channels(const vitx_model *m) { return m ? m->in_chans : 0; }
+int vitx_model_num_registers(const vitx_model *m) { return m ? m->num_registers : 0; }
+int vitx_model_head_pool(const vitx_model *m) { return m ? m->head_pool : 0; }
 int vitx_model_seq_len(const vitx_model *m) { return (m && m->in_chans == 1) ? VITX_VITSTR_SEQ_LEN : 0; }
 const char *vitx_model_label(const vitx_model *m, int id) {
     if (!m) return nullptr;

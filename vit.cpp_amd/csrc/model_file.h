@@ -31,6 +31,8 @@ struct vitx_model {
     vitx_hparams hp;
     uint64_t uid = 0;                                 // unique per successful vitx_model_load in this process (never reused: an address can be)
     int in_chans = 3;                                 // 1 = ViTSTR file (grey input, sequence head), from the patch kernel's shape
+    int num_registers = 0;                            // R of an optional `reg_token` [1][R][D]: tokens between the class token and the patches
+    int head_pool = VITX_POOL_CLS;                    // VITX_POOL_CLS_MEAN: head.weight is [C][2 D], over concat(cls, mean of the patch tokens)
     std::map<int, std::string> id2label;
     std::vector<vitx::HostTensor> tensors;            // file order
     std::map<std::string, int> index;                 // name -> position

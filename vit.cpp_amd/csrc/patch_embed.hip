@@ -11,8 +11,9 @@
 //   * 128 x 128 x 64 tiles, 4 waves, the LDS image / fragment layout / products / epilogue of the v1 GEMM (kernels.hip): W by LDS-DMA, A by
 //     registers -- each thread loads 2 x 16 floats of the next K-tile under the current K-tile's MFMAs, rounds them to the operand type
 //     exactly where ggml's im2col emits fp16, and writes two 16-byte slots of the swizzled image;
-//   * the epilogue (epilogue16.h, EPI_PATCH) adds bias and pos_embed[1 + patch], scatters to token row image * N + 1 + patch, and the
-//     lanes that hold patch 0 of an image also write its class row cls_token + pos_embed[0].
+//   * the epilogue (epilogue16.h, EPI_PATCH) adds bias and pos_embed[1 + patch], scatters to token row image * N + T + patch (T = 1 + R
+//     prefix tokens, GemmArgs::prefix), and the lanes that hold patch 0 of an image also write its class row cls_token + pos_embed[0] and
+//     its R register rows reg_token[r] -- copied as they are: registers carry no position embedding.
 // 0.7 % of the forward's FLOPs: a plain double-buffered kernel, not the persistent one.
 #include "device_common.h"
 #include "kernels.h"
@@ -26,7 +27,7 @@ constexpr int TILE = BM * BK * 2, STAGE = 2 * TILE, LDS_BYTES = 2 * STAGE;      
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void patch_embed_kernel(GemmArgs g, const float *__restrict__ img, const float *__restrict__ cls, int S, int P, int Cin, int gsz /* patches per image row */) {
+__global__ __launch_bounds__(256) void patch_embed_kernel(GemmArgs g, const float *__restrict__ img, const float *__restrict__ cls, const float *__restrict__ reg, int S, int P, int Cin, int gsz /* patches per image row */) {
     using namespace pe;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef typename Elem<T>::v8 v8;
@@ -135,16 +136,25 @@ __global__ __launch_bounds__(256) void patch_embed_kernel(GemmArgs g, const floa
     const int row0 = m0 + wm * 64 + l15, col0 = n0 + wn * 64 + 4 * g4;
     if (full) epilogue16<T, EPI_PATCH, 4, 4, true>(g, acc, row0, col0);
     else epilogue16<T, EPI_PATCH, 4, 4, false>(g, acc, row0, col0);
-    // class rows (vit.cpp:794-797): token 0 of image b = cls_token + pos_embed[0]; written by the lanes that hold patch 0 of that image
+    // class rows (vit.cpp:794-797): token 0 of image b = cls_token + pos_embed[0]; written by the lanes that hold patch 0 of that image,
+    // and behind it the image's register rows 1 .. prefix - 1 = reg_token[r]
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const int row = row0 + t * 16;
         if (row >= g.M_real || row % tpi) continue;
-        float *o = (float *)g.out + ((size_t)row + row / tpi) * g.ldo;          // token row b * (tpi + 1)
+        float *o = (float *)g.out + ((size_t)row + (size_t)(row / tpi) * g.prefix) * g.ldo;          // token row b * (tpi + prefix)
 #pragma unroll
         for (int u = 0; u < 4; ++u)
 #pragma unroll
             for (int e = 0; e < 4; ++e) { const int c = col0 + u * 16 + e; if (c < g.N) o[c] = cls[c] + g.pos[c]; }
+        for (int r = 1; r < g.prefix; ++r) {
+            const float *src = reg + (size_t)(r - 1) * g.ldo;
+            float *orow = o + (size_t)r * g.ldo;
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { const int c = col0 + u * 16 + e; if (c < g.N) orow[c] = src[c]; }
+        }
     }
 }
 
@@ -158,21 +168,21 @@ void patch_embed_permute_k(const uint16_t *w, uint16_t *w_perm, int N, int Cin, 
     (void)K;
 }
 
-hipError_t launch_patch_embed(int dtype, const float *img, const void *w_perm, const float *bias, const float *pos, const float *cls, float *X,
-                              int n_img, int S, int P, int Cin, int D, int n_pad, int k_pad, hipStream_t stream, bool prepare) {
+hipError_t launch_patch_embed(int dtype, const float *img, const void *w_perm, const float *bias, const float *pos, const float *cls, const float *reg, int n_reg,
+                              float *X, int n_img, int S, int P, int Cin, int D, int n_pad, int k_pad, hipStream_t stream, bool prepare) {
     if (prepare) {
         hipError_t e = hipFuncSetAttribute((const void *)patch_embed_kernel<_Float16>, hipFuncAttributeMaxDynamicSharedMemorySize, pe::LDS_BYTES);
         if (e != hipSuccess) return e;
         return hipFuncSetAttribute((const void *)patch_embed_kernel<__bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, pe::LDS_BYTES);
     }
     const int gsz = S / P, tpi = gsz * gsz;
-    if (n_img <= 0 || P <= 0 || S % P || n_pad % pe::BN || k_pad % pe::BK || k_pad < Cin * P * P || D % 4) return hipErrorInvalidValue;
+    if (n_img <= 0 || P <= 0 || S % P || n_pad % pe::BN || k_pad % pe::BK || k_pad < Cin * P * P || D % 4 || n_reg < 0 || (n_reg > 0 && !reg)) return hipErrorInvalidValue;
     GemmArgs g{};
     g.W = w_perm; g.bias = bias; g.out = X; g.pos = pos;
-    g.M_real = n_img * tpi; g.M = (g.M_real + pe::BM - 1) / pe::BM * pe::BM; g.N = D; g.N_pad = n_pad; g.K = k_pad; g.ldw = k_pad; g.ldo = D; g.tpi = tpi;
+    g.M_real = n_img * tpi; g.M = (g.M_real + pe::BM - 1) / pe::BM * pe::BM; g.N = D; g.N_pad = n_pad; g.K = k_pad; g.ldw = k_pad; g.ldo = D; g.tpi = tpi; g.prefix = 1 + n_reg;
     const int grid = (g.M / pe::BM) * (n_pad / pe::BN);
-    if (dtype == DT_F16) hipLaunchKernelGGL(patch_embed_kernel<_Float16>, dim3(grid), dim3(256), pe::LDS_BYTES, stream, g, img, cls, S, P, Cin, gsz);
-    else hipLaunchKernelGGL(patch_embed_kernel<__bf16>, dim3(grid), dim3(256), pe::LDS_BYTES, stream, g, img, cls, S, P, Cin, gsz);
+    if (dtype == DT_F16) hipLaunchKernelGGL(patch_embed_kernel<_Float16>, dim3(grid), dim3(256), pe::LDS_BYTES, stream, g, img, cls, reg, S, P, Cin, gsz);
+    else hipLaunchKernelGGL(patch_embed_kernel<__bf16>, dim3(grid), dim3(256), pe::LDS_BYTES, stream, g, img, cls, reg, S, P, Cin, gsz);
     return hipGetLastError();
 }
 

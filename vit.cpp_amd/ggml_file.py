@@ -12,6 +12,9 @@ File (little endian, no padding):
   int32 magic 0x67676d6c ; int32 hidden, layers, heads, classes, patch, img ; int32 ftype
   int32 n_labels ; n_labels x { int32 key ; int32 len ; bytes }
   until EOF: int32 n_dims, name_len, ttype ; int32 ne[n_dims] (reversed torch shape) ; name ; data
+
+Two optional extensions the reference's loader cannot read (include/vitx.h "register tokens and the pooled head"): a `reg_token` f32
+[1][R][D] directly after cls_token, and a `head.weight` of [C][2 D].  Magic and hparams are unchanged; both are read off the shapes.
 """
 from __future__ import annotations
 
@@ -41,6 +44,7 @@ class HParams:
 
     @property
     def n_tokens(self) -> int:
+        """Rows of pos_embed: the class token + the patch grid (register tokens carry no position row and are not counted)."""
         g = self.img_size // self.patch_size
         return g * g + 1
 
@@ -197,11 +201,28 @@ def dequantize(ttype: int, raw: bytes, n: int) -> np.ndarray:
 
 # --------------------------------------------------------------------------- write / read
 def write_model(path: str, hp: HParams, tensors: Dict[str, np.ndarray], id2label: Dict[int, str] | None = None,
-                ftype: int = 1, patch_f16: bool = True) -> None:
+                ftype: int = 1, patch_f16: bool = True, registers: int | None = None, head_pool: int | None = None) -> None:
     """Write torch-shaped f32 tensors (timm state_dict naming) as the reference converter does:
     1-D tensors, pos_embed and cls_token stay f32; everything else f16 when ftype>=1
     (convert-pth-to-ggml.py:141-148).  ftype in {2,3,6,7,8} additionally quantises the 2-D
-    '*weight' tensors exactly like quantize.cpp:207-303 does to an f16 file."""
+    '*weight' tensors exactly like quantize.cpp:207-303 does to an f16 file.
+    registers / head_pool (optional) state what the caller means to write -- R register tokens (`reg_token` [1][R][D], f32, directly
+    after cls_token) and the head kind (0 class token: head.weight [C][D]; 1 cls + mean: [C][2 D]) -- and are checked against `tensors`."""
+    D = hp.hidden_size
+    have_r = int(np.shape(tensors["reg_token"])[1]) if "reg_token" in tensors else 0
+    if "reg_token" in tensors:
+        if tuple(np.shape(tensors["reg_token"])) != (1, have_r, D) or have_r < 1:
+            raise ValueError(f"reg_token must be [1][R][{D}] with R >= 1, got {np.shape(tensors['reg_token'])}")
+        if list(tensors)[list(tensors).index("reg_token") - 1] != "cls_token":
+            raise ValueError("reg_token is written directly after cls_token")
+    if registers is not None and registers != have_r:
+        raise ValueError(f"registers={registers}, but the tensors hold {have_r} register tokens")
+    if "head.weight" in tensors:
+        hw = np.shape(tensors["head.weight"])
+        if len(hw) != 2 or hw[1] not in (D, 2 * D):
+            raise ValueError(f"head.weight must be [C][{D}] (class-token head) or [C][{2 * D}] (cls + mean head), got {hw}")
+        if head_pool is not None and hw[1] != (2 * D if head_pool else D):
+            raise ValueError(f"head_pool={head_pool}, but head.weight is {hw}")
     id2label = id2label if id2label is not None else {i: f"LABEL_{i}" for i in range(hp.num_classes)}
     with open(path, "wb") as f:
         f.write(struct.pack("<i", GGML_MAGIC))
@@ -216,7 +237,7 @@ def write_model(path: str, hp: HParams, tensors: Dict[str, np.ndarray], id2label
             data = np.asarray(t, np.float32)
             if name == "patch_embed.proj.bias":
                 data = data.reshape(1, data.shape[0], 1, 1)              # convert:150-151
-            keep_f32 = data.ndim == 1 or name in ("pos_embed", "cls_token") or name == "patch_embed.proj.bias"
+            keep_f32 = data.ndim == 1 or name in ("pos_embed", "cls_token", "reg_token") or name == "patch_embed.proj.bias"
             if ftype == 0 and not (patch_f16 and name == "patch_embed.proj.weight"):
                 keep_f32 = True
             ttype = F32 if keep_f32 else F16

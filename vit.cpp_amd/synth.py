@@ -20,6 +20,8 @@ from .ggml_file import HParams, write_model
 CONFIGS = {
     # name: (hidden, layers, heads, classes, patch, img)
     "vit_micro_patch16_64": (128, 2, 2, 10, 16, 64),       # test-only toy (N=17)
+    "vit_micro_patch14_56": (128, 2, 2, 10, 14, 56),       # test-only toy at DINOv2's patch size (16 patches: N = 17, or 21 with 4 register tokens)
+    "vit_base_patch14_224": (768, 12, 12, 1000, 14, 224),  # DINOv2 ViT-B/14 (257 tokens, 261 with 4 register tokens)
     "vit_micro_c37_patch16_64": (128, 2, 2, 37, 16, 64),   # test-only toy with an ODD class count (the head GEMM's last column group is ragged)
     "vit_micro_c21843_patch16_64": (128, 2, 2, 21843, 16, 64),   # test-only toy with ImageNet-21k's class count (timm *_in21k heads): 86 column tiles of the head GEMM, a 21843-wide class softmax
     "vit_micro_patch8_224": (128, 2, 2, 10, 8, 224),       # test-only toy with the token count of the reference's default hparams (N=785)
@@ -57,7 +59,10 @@ def gflop_per_image(hp: HParams) -> float:
     return 2.0 * (g * g * 3 * P * P * D + L * per_layer + D * C) / 1e9
 
 
-def make_weights(hp: HParams, seed: int = 1234, head_scale: float = 8.0, in_chans: int = 3) -> Dict[str, np.ndarray]:
+def make_weights(hp: HParams, seed: int = 1234, head_scale: float = 8.0, in_chans: int = 3, registers: int = 0, head_pool: int = 0,
+                 reg_scale: float = 1.0) -> Dict[str, np.ndarray]:
+    """registers > 0 adds `reg_token` [1][R][D] (x reg_scale), head_pool = 1 widens head.weight to [C][2 D] (cls ‖ mean of the patch tokens).
+    Both are drawn AFTER every draw of the plain model, so files without them keep their bytes (tests/golden/weights_sha1.json)."""
     rng = np.random.default_rng(seed)
     D, L, C, P = hp.hidden_size, hp.num_hidden_layers, hp.num_classes, hp.patch_size
     N = hp.n_tokens
@@ -84,24 +89,37 @@ def make_weights(hp: HParams, seed: int = 1234, head_scale: float = 8.0, in_chan
     t["norm.weight"] = vec(D, 1.0); t["norm.bias"] = vec(D)
     t["head.weight"] = (mat(C, D) * np.float32(head_scale)).astype(np.float32)
     t["head.bias"] = vec(C)
+    if head_pool:
+        t["head.weight"] = np.concatenate([t["head.weight"], (mat(C, D) * np.float32(head_scale)).astype(np.float32)], axis=1)
+    if registers:
+        reg = (mat(1, registers, D) * np.float32(reg_scale)).astype(np.float32)
+        out: Dict[str, np.ndarray] = {}
+        for k, v in t.items():          # directly after cls_token
+            out[k] = v
+            if k == "cls_token":
+                out["reg_token"] = reg
+        t = out
     return t
 
 
-def write_synthetic(path: str, name: str, ftype: int = 1, seed: int = 1234, head_scale: float = 8.0) -> HParams:
+def write_synthetic(path: str, name: str, ftype: int = 1, seed: int = 1234, head_scale: float = 8.0, registers: int = 0, head_pool: int = 0) -> HParams:
     hp = hparams_for(name, ftype)
     ic = IN_CHANS.get(name, 3)
-    write_model(path, hp, make_weights(hp, seed, head_scale, in_chans=ic), ftype=ftype, id2label=dict(VITSTR_LABELS) if ic == 1 else None)
+    write_model(path, hp, make_weights(hp, seed, head_scale, in_chans=ic, registers=registers, head_pool=head_pool), ftype=ftype,
+                id2label=dict(VITSTR_LABELS) if ic == 1 else None, registers=registers, head_pool=head_pool)
     return hp
 
 
-def cached_synthetic(name: str, ftype: int = 1, seed: int = 1234, head_scale: float = 8.0, cache_dir: str | None = None) -> str:
+def cached_synthetic(name: str, ftype: int = 1, seed: int = 1234, head_scale: float = 8.0, cache_dir: str | None = None, registers: int = 0,
+                     head_pool: int = 0) -> str:
     """Write (once) and return the path of a synthetic model file under a scratch dir."""
     cache_dir = cache_dir or os.environ.get("VITX_CACHE", "/tmp/vitx_cache")
     os.makedirs(cache_dir, exist_ok=True)
-    path = os.path.join(cache_dir, f"{name}-s{seed}-h{head_scale:g}-ft{ftype}.gguf")
+    ext = (f"-r{registers}" if registers else "") + ("-pool" if head_pool else "")
+    path = os.path.join(cache_dir, f"{name}-s{seed}-h{head_scale:g}-ft{ftype}{ext}.gguf")
     if not os.path.exists(path):
         tmp = path + f".tmp{os.getpid()}"
-        write_synthetic(tmp, name, ftype, seed, head_scale)
+        write_synthetic(tmp, name, ftype, seed, head_scale, registers, head_pool)
         os.replace(tmp, path)
     return path
 
