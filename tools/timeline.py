@@ -3,7 +3,7 @@
 usage: python tools/timeline.py <results.db> [--skip N] [--forwards K]
 
 rocprofv3 stamps every dispatch with its start / end on the device clock and the hardware queue it came through.  The engine runs
-sub-batch 0 on the caller's stream and sub-batch 1 on an internal stream (engine.cpp), so the two queues of a forward are the two that
+sub-batch 0 on the caller's stream and sub-batch 1 on an internal stream (forward.cpp), so the two queues of a forward are the two that
 carry its patch_embed launches.  For each of the last K forwards (after skipping N warm-up ones) this prints
   * wall = first start -> last end, the sum of kernel durations per queue, and wall - max(sum per queue);
   * time with 0 / 1 / 2 kernels resident (union over both queues) and the queue gaps (next.start - prev.end inside a queue);

@@ -1,0 +1,346 @@
+// context.cpp -- creation of the execution context of the MI355X ViT engine: weight upload, scratch, streams.
+// Replaces vit_state + the set-up half of vit_predict of the reference (vit.cpp:718-941, 1004-1040).  Differences by design: the batch is
+// n images (the reference hard-wires 1, vit.cpp:747), weights live in HBM in the MFMA operand type, all activation scratch is allocated
+// once per context (the reference builds the graph twice and reallocates per call, vit.cpp:1009-1035), and the ~90 launches of a
+// forward are enqueued on one HIP stream without host synchronisation (forward.cpp).
+#include <stdlib.h>
+#include <string.h>
+
+#include <map>
+#include <mutex>
+#include <new>
+#include <string>
+#include <tuple>
+
+#include "context.h"
+
+std::vector<uint16_t> vitx::operand_matrix_host(int dtype, const float *f, const uint16_t *bits, int Nrows, int K, int n_pad, int k_pad, int patch_P, int patch_Cin) {
+    std::vector<uint16_t> h((size_t)n_pad * k_pad, 0);
+    for (int n = 0; n < Nrows; ++n) {
+        if (bits) { memcpy(&h[(size_t)n * k_pad], bits + (size_t)n * K, (size_t)K * 2); continue; }
+        for (int k = 0; k < K; ++k) h[(size_t)n * k_pad + k] = dtype == VITX_F16 ? f32_to_f16_bits(f[(size_t)n * K + k]) : f32_to_bf16_bits(f[(size_t)n * K + k]);
+    }
+    if (patch_P > 0) { std::vector<uint16_t> hp(h.size(), 0); patch_embed_permute_k(h.data(), hp.data(), Nrows, patch_Cin, patch_P, k_pad); h.swap(hp); }
+    return h;
+}
+
+namespace {
+
+// f32 vector -> device f32 (padded with zeros to n_pad)
+int upload_f32(vitx_ctx *c, const HostTensor *t, float **out, size_t n_pad = 0) {
+    std::vector<float> h((size_t)t->nelements());
+    t->decode_f32(h.data());
+    if (n_pad > h.size()) h.resize(n_pad, 0.0f);
+    int rc = c->wmalloc((void **)out, h.size() * 4);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(*out, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+    return VITX_OK;
+}
+
+// [N][K] matrix -> operand type, rows padded to n_pad, cols to k_pad (zeros).  f16 file data is
+// forwarded bit-exact in F16 mode; everything else is decoded to f32 and rounded once (RNE).
+// patch_P > 0: the patch-embedding kernel [D][Cin * P * P]: its K axis is permuted to the image's memory order (patch_embed.hip)
+int upload_matrix(vitx_ctx *c, const HostTensor *t, int Nrows, int K, int n_pad, int k_pad, void **out, int patch_P = 0, int patch_Cin = 0) {
+    const bool exact = t->type == T_F16 && c->dtype == VITX_F16;
+    std::vector<float> f(exact ? 0 : (size_t)Nrows * K);
+    if (!exact) t->decode_f32(f.data());
+    const std::vector<uint16_t> h = operand_matrix_host(c->dtype, f.data(), exact ? (const uint16_t *)t->raw.data() : nullptr, Nrows, K, n_pad, k_pad, patch_P, patch_Cin);
+    int rc = c->wmalloc(out, h.size() * 2);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(*out, h.data(), h.size() * 2, hipMemcpyHostToDevice));
+    c->wset->weight_bytes += h.size() * 2;
+    return VITX_OK;
+}
+int upload_quant(vitx_ctx *c, const HostTensor *t, int Nrows, int K, int n_pad, QuantW *q);
+// A 2-D "*weight" tensor: block types stay quantised on the device (q), everything else is uploaded expanded (dense).
+int upload_weight(vitx_ctx *c, const HostTensor *t, int Nrows, int K, int n_pad, void **dense, QuantW *q) {
+    *dense = nullptr;
+    if (c->quant_on_device) { int rc = upload_quant(c, t, Nrows, K, n_pad, q); if (rc) return rc; }
+    if (q->blocks) return VITX_OK;
+    return upload_matrix(c, t, Nrows, K, n_pad, K, dense);
+}
+
+// [N][K] matrix -> MX operand (VITX_MXFP8): the f32 decode of any file type, encoded once on the host; rows N..n_pad are zero blocks
+int upload_mx(vitx_ctx *c, const HostTensor *t, int Nrows, int K, int n_pad, MxW *w) {
+    w->N = Nrows; w->K = K; w->n_pad = n_pad; w->k_pad = mx_k_pad(K);
+    std::vector<float> f((size_t)n_pad * K, 0.0f);
+    t->decode_f32(f.data());
+    std::vector<uint8_t> q((size_t)n_pad * w->k_pad), sc((size_t)n_pad * (w->k_pad / kMxBlock));
+    mxfp8_encode_rows(f.data(), n_pad, K, w->k_pad, q.data(), sc.data());
+    int rc;
+    if ((rc = c->wmalloc((void **)&w->q, q.size()))) return rc;
+    if ((rc = c->wmalloc((void **)&w->s, sc.size()))) return rc;
+    HIP_TRY(hipMemcpy(w->q, q.data(), q.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(w->s, sc.data(), sc.size(), hipMemcpyHostToDevice));
+    c->wset->weight_bytes += q.size() + sc.size();
+    return VITX_OK;
+}
+
+// Quantised [N][K] matrix -> device, still in block form.  Returns VITX_OK with q->blocks == nullptr when the tensor is not a
+// block type (the caller then uploads the expanded matrix).
+int upload_quant(vitx_ctx *c, const HostTensor *t, int Nrows, int K, int n_pad, QuantW *q) {
+    const int bb = type_block_bytes(t->type);
+    if (t->type == T_F32 || t->type == T_F16 || !bb || K % 32) return VITX_OK;
+    const size_t nbk = (size_t)K / 32;
+    q->type = t->type; q->N = Nrows; q->K = K; q->n_pad = n_pad;
+    int rc;
+    if (t->type == T_Q4_0) {        // split planes, rows padded (zero scales -> the pad rows expand to zeros)
+        std::vector<uint8_t> qs((size_t)n_pad * nbk * 16, 0);
+        std::vector<uint16_t> ds((size_t)n_pad * nbk, 0);
+        const uint8_t *src = t->raw.data();
+        for (size_t b = 0; b < (size_t)Nrows * nbk; ++b) { memcpy(&ds[b], src + b * 18, 2); memcpy(&qs[b * 16], src + b * 18 + 2, 16); }
+        if ((rc = c->wmalloc(&q->blocks, qs.size()))) return rc;
+        if ((rc = c->wmalloc((void **)&q->scales, ds.size() * 2))) return rc;
+        HIP_TRY(hipMemcpy(q->blocks, qs.data(), qs.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(q->scales, ds.data(), ds.size() * 2, hipMemcpyHostToDevice));
+        c->wset->weight_bytes += qs.size() + ds.size() * 2;
+    } else {
+        const size_t bytes = (size_t)Nrows * nbk * bb;
+        if ((rc = c->wmalloc(&q->blocks, bytes))) return rc;
+        HIP_TRY(hipMemcpy(q->blocks, t->raw.data(), bytes, hipMemcpyHostToDevice));
+        c->wset->weight_bytes += bytes;
+    }
+    return VITX_OK;
+}
+
+// vitx_ctx_create_ex, step 1: the options (all zero = every default) and the geometry they ask for are validated, then the context is made and
+// its fields are derived from them.  Every check keeps its place: the first one that fails is the one reported.
+int configure(const vitx_model *m, int device, int max_batch, int dtype, const vitx_ctx_options *opt_in, vitx_ctx_options &opt, std::unique_ptr<vitx_ctx> &c) {
+    if (opt_in) {
+        if (opt_in->struct_size < 8 || opt_in->struct_size > (int)sizeof(vitx_ctx_options)) { set_error("vitx_ctx_create_ex: options.struct_size %d is not a size this library knows", opt_in->struct_size); return VITX_ERR_ARG; }
+        memcpy(&opt, opt_in, (size_t)opt_in->struct_size);
+        if (opt.streams < 0 || opt.streams > 4 || opt.q4_fused_rows < 0 || opt.split_first < 0 || (opt.last_layer_all_rows & ~1)) { set_error("vitx_ctx_create_ex: option out of range"); return VITX_ERR_ARG; }
+    }
+    // geometry of this context (vitx_ctx_options::img_size): checked before any device is touched
+    if (opt.pos_interp != VITX_POS_BICUBIC && opt.pos_interp != VITX_POS_BICUBIC_AA) { set_error("vitx_ctx_create_ex: unknown pos_interp %d (0 bicubic, 1 bicubic with antialias)", opt.pos_interp); return VITX_ERR_ARG; }
+    if (opt.img_size < 0 || (opt.img_size > 0 && (m->hp.patch_size <= 0 || opt.img_size % m->hp.patch_size))) {
+        set_error("vitx_ctx_create_ex: img_size %d is not a positive multiple of the patch size %d", opt.img_size, m->hp.patch_size); return VITX_ERR_ARG;
+    }
+    const int img_size = opt.img_size > 0 ? opt.img_size : m->hp.img_size;
+    if (m->in_chans == 1 && (m->num_registers || m->head_pool != VITX_POOL_CLS)) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes neither register tokens nor the pooled head"); return VITX_ERR_UNSUPPORTED; }
+    if (dtype == VITX_MXFP8 && (m->num_registers || m->head_pool != VITX_POOL_CLS)) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts do not take models with register tokens or the pooled head"); return VITX_ERR_UNSUPPORTED; }
+    if (m->in_chans == 1 && img_size != m->hp.img_size) { set_error("vitx_ctx_create_ex: a ViTSTR context stays at the file's img_size (%d)", m->hp.img_size); return VITX_ERR_UNSUPPORTED; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("vitx_ctx_create: no HIP device available (this engine has no CPU fallback)"); return VITX_ERR_HIP; }
+    if (device < 0 || device >= ndev) { set_error("vitx_ctx_create: device %d out of range (%d devices)", device, ndev); return VITX_ERR_ARG; }
+    const vitx_hparams &hp = m->hp;
+    if (hp.num_attention_heads <= 0 || hp.hidden_size % hp.num_attention_heads) { set_error("vitx_ctx_create: hidden_size %d is not a multiple of %d heads", hp.hidden_size, hp.num_attention_heads); return VITX_ERR_UNSUPPORTED; }
+    if (hp.hidden_size % 64) { set_error("vitx_ctx_create: hidden_size must be a multiple of 64"); return VITX_ERR_UNSUPPORTED; }
+    // (VITX_MXFP8 needs whole 32-element blocks per row: the multiple of 64 above already guarantees it, so no check of its own)
+    static_assert(64 % kMxBlock == 0, "the hidden-size rule above must cover the MX block");
+    HIP_TRY(hipSetDevice(device));
+    c.reset(new (std::nothrow) vitx_ctx());
+    if (!c) return VITX_ERR_NOMEM;
+    c->model = m; c->hp = hp; c->device = device; c->max_batch = max_batch;
+    c->mx = dtype == VITX_MXFP8; c->dtype = c->mx ? VITX_BF16 : dtype;      // everything but the MX GEMMs runs as in a VITX_BF16 context
+    c->D = hp.hidden_size; c->L = hp.num_hidden_layers; c->H = hp.num_attention_heads; c->C = hp.num_classes; c->P = hp.patch_size; c->S = img_size;
+    c->Cin = m->in_chans; c->R = m->in_chans == 1 ? VITX_VITSTR_SEQ_LEN : 1;
+    c->nreg = m->num_registers; c->Tp = 1 + c->nreg; c->pool = m->head_pool == VITX_POOL_CLS_MEAN;
+    c->g = c->S / c->P; c->N = c->g * c->g + c->Tp; c->Kpe = c->Cin * c->P * c->P; c->Kpe_pad = round_up(c->Kpe, 64);
+    if (c->N < c->R) { set_error("vitx_ctx_create: a ViTSTR head reads %d tokens, this model has %d (img_size %d, patch_size %d)", c->R, c->N, c->S, c->P); return VITX_ERR_UNSUPPORTED; }
+    c->tm = gemm_tile_m(); c->tn = gemm_tile_n();
+    c->C_pad = round_up(c->C, c->tn);
+    // validate against what the kernels are actually instantiated for (a context that would fail on its first forward is refused here)
+    if (!attention_supports(c->N, c->D, c->H)) {
+        set_error("vitx_ctx_create: attention needs a head_dim that is a multiple of 8 up to 128 (this model: %d) and at least one token (%d tokens, img_size %d, patch_size %d)", c->D / c->H, c->N, c->S, c->P);
+        return VITX_ERR_UNSUPPORTED;
+    }
+    if (!layernorm_supports(c->D)) { set_error("vitx_ctx_create: hidden_size %d has no LayerNorm instantiation (64, 128, 192, 256, 320, 384, 448, 512, 576, 640, 768, 896, 1024, 1152, 1280, 1408, 1536, 1664, 2048)", c->D); return VITX_ERR_UNSUPPORTED; }
+    c->tune = tuning_for_device(device);
+    if (!c->tune) { set_error("vitx_ctx_create: kernel bring-up on device %d failed: %s", device, hipGetErrorString(hipGetLastError())); return VITX_ERR_HIP; }
+    c->split_first = opt.split_first;
+    c->prec_attn = dtype == VITX_F16 && c->D == c->H * 64 && !opt.f16_fast_attention;
+    c->quant_on_device = !opt.quant_on_host;
+    // the pooled head averages every patch row of the last layer: such a context runs exactly as one created with last_layer_all_rows = 1
+    c->cls_tail = !opt.last_layer_all_rows && !c->pool && c->R == 1 && attention_cls_supports(c->N, c->D, c->H);
+    c->q4_fused_rows = opt.q4_fused_rows;
+    c->graphs_on = opt.graph != 0;
+    // fault injection for the parity tests: honoured only with the key in the upper half (VITX_LN_TEST_KEY | mode), so that no caller sets it by accident
+    if (opt.ln_test) {
+        if ((opt.ln_test & (int32_t)0xffff0000) != (int32_t)VITX_LN_TEST_KEY) { set_error("vitx_ctx_create_ex: ln_test is a test-only switch (it needs its key: include/vitx.h)"); return VITX_ERR_ARG; }
+        c->ln_test = opt.ln_test & 0xffff;
+        if (c->ln_test & ~7) { set_error("vitx_ctx_create_ex: ln_test mode %d has bits outside 1 | 2 | 4", c->ln_test); return VITX_ERR_ARG; }
+        if ((c->ln_test & 3) == 3) c->ln_timeout = 5000;       // real time-outs in the test: 50 us (with or without bit 4; the kernel tests the bits one by one too)
+    }
+    // a captured launch would replay its epoch tag: no fusion under the graph cache; MX: every LayerNorm is its own launch (it writes MX)
+    c->ln_fuse = !opt.no_ln_fusion && !opt.graph && !c->mx;
+#ifdef VITX_LAB
+    if (const char *e = getenv("VITX_SKIP")) c->skip = atoi(e);
+#endif
+    HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    return VITX_OK;
+}
+
+// Step 2: the device copies of the weights, found in the registry or uploaded.  `dtype`: the type the caller asked for (the key tells MXFP8 from BF16)
+int obtain_weights(vitx_ctx *c, int dtype) {
+    const vitx_model *m = c->model;
+    const int device = c->device, D = c->D, tn = c->tn;
+    int rc;
+    auto T = [&](const std::string &n) { return m->find(n); };
+    // device copies of the weights: one set per (loaded model, device, operand type, block mode), shared by every context that asks for it
+    static std::mutex wreg_mu;
+    static std::map<std::tuple<uint64_t, int, int, int>, std::weak_ptr<vitx_ctx::WeightSet>> wreg;
+    const auto wkey = std::make_tuple(m->uid, device, dtype, c->quant_on_device ? 1 : 0);
+    std::unique_lock<std::mutex> wlock(wreg_mu);           // held through the upload: a second context of the same model waits for the first
+    for (auto it = wreg.begin(); it != wreg.end();) it = it->second.expired() ? wreg.erase(it) : std::next(it);      // sets whose last context is gone
+    if (auto have = wreg[wkey].lock()) {
+        c->wset = have; c->weights_shared = true;
+    } else {
+        c->wset = std::make_shared<vitx_ctx::WeightSet>();
+        vitx_ctx::WeightSet &ws = *c->wset;
+        ws.device = device;
+        if ((rc = upload_f32(c, T("cls_token"), &ws.cls))) return rc;
+        if (c->nreg && (rc = upload_f32(c, T("reg_token"), &ws.reg))) return rc;
+        if ((rc = upload_f32(c, T("pos_embed"), &ws.pos))) return rc;
+        if ((rc = upload_f32(c, T("patch_embed.proj.bias"), &ws.pe_b, round_up(D, tn)))) return rc;
+        if ((rc = upload_matrix(c, T("patch_embed.proj.weight"), D, c->Kpe, round_up(D, tn), c->Kpe_pad, &ws.pe_w, c->P, c->Cin))) return rc;
+        ws.layers.resize(c->L);
+        for (int i = 0; i < c->L; ++i) {
+            const std::string p = "blocks." + std::to_string(i) + ".";
+            LayerW &w = ws.layers[i];
+            if ((rc = upload_f32(c, T(p + "norm1.weight"), &w.ln1_w))) return rc;
+            if ((rc = upload_f32(c, T(p + "norm1.bias"), &w.ln1_b))) return rc;
+            if ((rc = upload_f32(c, T(p + "norm2.weight"), &w.ln2_w))) return rc;
+            if ((rc = upload_f32(c, T(p + "norm2.bias"), &w.ln2_b))) return rc;
+            if ((rc = upload_f32(c, T(p + "attn.qkv.bias"), &w.qkv_b, round_up(3 * D, tn)))) return rc;
+            if ((rc = upload_f32(c, T(p + "attn.proj.bias"), &w.proj_b, round_up(D, tn)))) return rc;
+            if ((rc = upload_f32(c, T(p + "mlp.fc1.bias"), &w.fc1_b, round_up(4 * D, tn)))) return rc;
+            if ((rc = upload_f32(c, T(p + "mlp.fc2.bias"), &w.fc2_b, round_up(D, tn)))) return rc;
+            w.qkv_w = w.fc1_w = w.fc2_w = nullptr;
+            if (c->mx) {
+                if ((rc = upload_mx(c, T(p + "attn.qkv.weight"), 3 * D, D, round_up(3 * D, 128), &w.mx[W_QKV]))) return rc;
+                if ((rc = upload_mx(c, T(p + "mlp.fc1.weight"), 4 * D, D, round_up(4 * D, 128), &w.mx[W_FC1]))) return rc;
+                if ((rc = upload_mx(c, T(p + "mlp.fc2.weight"), D, 4 * D, round_up(D, 128), &w.mx[W_FC2]))) return rc;
+            } else {
+                if ((rc = upload_weight(c, T(p + "attn.qkv.weight"), 3 * D, D, round_up(3 * D, tn), &w.qkv_w, &w.q[W_QKV]))) return rc;
+                if ((rc = upload_weight(c, T(p + "mlp.fc1.weight"), 4 * D, D, round_up(4 * D, tn), &w.fc1_w, &w.q[W_FC1]))) return rc;
+                if ((rc = upload_weight(c, T(p + "mlp.fc2.weight"), D, 4 * D, round_up(D, tn), &w.fc2_w, &w.q[W_FC2]))) return rc;
+            }
+            if ((rc = upload_weight(c, T(p + "attn.proj.weight"), D, D, round_up(D, tn), &w.proj_w, &w.q[W_PROJ]))) return rc;
+        }
+        if ((rc = upload_f32(c, T("norm.weight"), &ws.norm_w))) return rc;
+        if ((rc = upload_f32(c, T("norm.bias"), &ws.norm_b))) return rc;
+        if ((rc = upload_f32(c, T("head.bias"), &ws.head_b, c->C_pad))) return rc;
+        if ((rc = upload_weight(c, T("head.weight"), c->C, c->pool ? 2 * D : D, c->C_pad, &ws.head_w, &ws.head_q))) return rc;
+        wreg[wkey] = c->wset;
+    }
+    return VITX_OK;               // (the lock is released here: held through the upload)
+}
+
+// Step 3: the scratch of one sub-batch slice; `internal`: a slice that runs on a stream of its own (every slice but the first of several)
+int alloc_slice(vitx_ctx *c, vitx_ctx::Slice &sl, size_t hcols, bool internal) {
+    const int D = c->D;
+    int rc;
+    sl.cap = c->pass_cap();     // every slice can hold a whole pass: the split point is chosen per call (split_batch)
+    const size_t Mpad = (size_t)round_up(sl.cap * c->N, c->tm), Bpad = (size_t)round_up(sl.cap * c->R, c->tm);
+    if ((rc = c->dmalloc((void **)&sl.X, Mpad * D * 4, true))) return rc;
+    if ((rc = c->dmalloc(&sl.U, Mpad * D * 2, true))) return rc;
+    if ((rc = c->dmalloc(&sl.U2, Mpad * D * 2, true))) return rc;
+    if (D % 256 == 0 && D / 256 <= 4) {
+        if ((rc = c->dmalloc((void **)&sl.ln_sync, (Mpad / 256) * (size_t)(D / 256) * 256 * 2 * sizeof(unsigned long long), true))) return rc;
+        if ((rc = c->dmalloc((void **)&sl.ln_todo, (Mpad / 256 + 1) * sizeof(unsigned), true))) return rc;
+        sl.ln_blocks = (int)(Mpad / 256);
+    }
+    if ((rc = c->dmalloc(&sl.QKV, Mpad * 3 * D * 2 * (c->prec_attn ? 2 : 1), true))) return rc;
+    sl.qkv_lo_off = c->prec_attn ? (long)(Mpad * 3 * D) : 0;       // capacity; a forward places the lo plane right behind ITS rows (SliceForward)
+    if ((rc = c->dmalloc(&sl.Hbuf, Mpad * hcols * 2, true))) return rc;
+    if ((rc = c->dmalloc(&sl.Z, Bpad * D * 2 * (c->pool ? 2 : 1), true))) return rc;
+    if (c->mx) {
+        const size_t kp = (size_t)mx_k_pad(D), kh = (size_t)mx_k_pad(4 * D);
+        if ((rc = c->dmalloc((void **)&sl.Umx, Mpad * kp * 33 / 32, true))) return rc;
+        if ((rc = c->dmalloc((void **)&sl.U2mx, Mpad * kp * 33 / 32, true))) return rc;
+        sl.Umx_s = sl.Umx + Mpad * kp; sl.U2mx_s = sl.U2mx + Mpad * kp;
+        sl.Hmx = (uint8_t *)sl.Hbuf; sl.Hmx_s = sl.Hmx + Mpad * kh;             // Mpad * kh * 33 / 32 <= Mpad * 4 D * 2 bytes of Hbuf
+    }
+    if (c->cls_tail && (rc = c->dmalloc((void **)&sl.Xc, Bpad * D * 4, true))) return rc;
+    if ((rc = c->dmalloc((void **)&sl.logits, Bpad * c->C_pad * 4, true))) return rc;
+    // expansion scratch for quantised matrices: one buffer per matrix kind, shared by all layers (the largest layer decides)
+    for (int k = 0; k < W_PER_LAYER; ++k) {
+        size_t need = 0;
+        for (const LayerW &w : c->wset->layers) if (w.q[k].blocks) need = std::max(need, (size_t)w.q[k].n_pad * w.q[k].K * 2);
+        if (need && (rc = c->dmalloc(&sl.Wq[k], need, false))) return rc;
+    }
+    const QuantW &hq = c->wset->head_q;
+    if (hq.blocks && (rc = c->dmalloc(&sl.Wq_head, (size_t)hq.n_pad * hq.K * 2, false))) return rc;
+    if (internal) {
+        // Slice 0 runs on the CALLER's stream, slices 1.. on internal HIGH-priority streams.  The runtime multiplexes all streams of one
+        // priority onto a small pool of hardware queues (GPU_MAX_HW_QUEUES, 4 by default), round-robin in creation order; a hardware queue
+        // executes its packets in order.  r02 gave slice 0 its own normal-priority stream: whenever that stream shared a hardware queue
+        // with the caller's (torch's pool of streams, a second context in the process ...), step k + 1's slice-0 kernels queued up behind
+        // the caller stream's wait for step k's slice 1, and the two sub-batches ran back to back -- measured r03: the 2nd and the 6th
+        // context created in one process ran 11.8 instead of 9.9 ms per forward.  Pools are per priority: the caller's stream (normal,
+        // unless the caller chose otherwise) and the internal ones (high, created back to back) can never share a queue.
+        int least = 0, greatest = 0;
+        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIP_TRY(hipStreamCreateWithPriority(&sl.stream, hipStreamNonBlocking, greatest));
+        HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    }
+    return VITX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vitx_ctx_create(const vitx_model *m, int device, int max_batch, int dtype, vitx_ctx **out) { return vitx_ctx_create_ex(m, device, max_batch, dtype, nullptr, out); }
+
+int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype, const vitx_ctx_options *opt_in, vitx_ctx **out) {
+    if (!m || !out || max_batch <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16 && dtype != VITX_MXFP8)) { set_error("vitx_ctx_create: invalid argument"); return VITX_ERR_ARG; }
+    *out = nullptr;
+    vitx_ctx_options opt{};                   // all zero = every default
+    std::unique_ptr<vitx_ctx> c;
+    int rc;
+    if ((rc = configure(m, device, max_batch, dtype, opt_in, opt, c))) return rc;
+    if ((rc = obtain_weights(c.get(), dtype))) return rc;
+    const vitx_hparams &hp = m->hp;
+    const int D = c->D;
+    // the position table of THIS context: the set's (the file's) at the file's size, else resampled on the device into scratch the context owns
+    c->pos = c->wset->pos;
+    if (c->S != hp.img_size) {
+        const int g_in = hp.img_size / hp.patch_size;
+        if ((rc = c->dmalloc((void **)&c->pos_own, (size_t)(c->g * c->g + 1) * D * 4, false))) return rc;
+        HIP_TRY(launch_pos_resample(c->wset->pos, g_in, g_in, D, c->g, c->g, opt.pos_interp, c->pos_own, c->stream));
+        c->pos = c->pos_own;                 // (the hipDeviceSynchronize at the end of the creation covers the launch)
+    }
+
+    // sub-batch slices (vitx_ctx_options::streams; 1 = single stream).  Small contexts stay single-slice.
+    int ns = opt.streams > 0 ? opt.streams : 2;
+    if (ns < 1) ns = 1;
+    if (ns > 4) ns = 4;
+    if (max_batch < 8 * ns) ns = 1;
+    c->nslices = ns;
+    c->slices.resize(ns);
+    const size_t hcols = std::max<size_t>((size_t)4 * D, (size_t)c->Kpe_pad);
+    {
+        // The kernels address every activation buffer with 32-bit BYTE offsets (buffer instructions): a sub-batch must keep its largest buffer --
+        // the MLP hidden tensor, or the two QKV planes of the F16 parity mode -- below 0xf0000000 bytes (ViT-B: 3326 images per sub-batch, 2217 in
+        // parity mode).  Batches beyond one such window run as several passes through the same scratch (vitx_forward_device), so max_batch
+        // itself is only bounded by memory.  r04: the guards used to sit in the individual launchers only, and a 10 000-image batch computed garbage.
+        const size_t row_bytes = std::max<size_t>(hcols * 2, (size_t)3 * D * 2 * (c->prec_attn ? 2 : 1));
+        const size_t rows = (size_t)0xf0000000u / row_bytes / 256 * 256;
+        const long per_slice = (long)(rows / c->N);
+        if (per_slice < 1) { set_error("vitx_ctx_create: a single image exceeds the kernels' 32-bit buffer window (%d tokens x %d)", c->N, D); return VITX_ERR_UNSUPPORTED; }
+        c->call_limit = (int)std::min<long>((long)max_batch, per_slice);          // whatever the split of a pass, no sub-batch exceeds the window
+    }
+    for (int i = 0; i < ns; ++i) if ((rc = alloc_slice(c.get(), c->slices[i], hcols, ns > 1 && i > 0))) return rc;
+    if (ns > 1) HIP_TRY(hipEventCreateWithFlags(&c->fork, hipEventDisableTiming));
+    HIP_TRY(hipHostMalloc((void **)&c->ln_fb_host, sizeof(unsigned) * 4, hipHostMallocDefault));
+    for (int i = 0; i < 4; ++i) c->ln_fb_host[i] = 0;
+    if ((rc = c->dmalloc((void **)&c->img, (size_t)max_batch * c->S * c->S * c->Cin * 4, false))) return rc;
+    if ((rc = c->dmalloc((void **)&c->probs, (size_t)max_batch * c->R * c->C * 4, true))) return rc;
+    if ((rc = c->dmalloc((void **)&c->logits_all, (size_t)max_batch * c->R * c->C * 4, true))) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    *out = c.release();
+    return VITX_OK;
+}
+
+void vitx_ctx_free(vitx_ctx *c) { delete c; }
+int vitx_ctx_max_batch(const vitx_ctx *c) { return c ? c->max_batch : 0; }
+int vitx_ctx_img_size(const vitx_ctx *c) { return c ? c->S : 0; }
+int vitx_ctx_tokens(const vitx_ctx *c) { return c ? c->N : 0; }
+int vitx_ctx_registers(const vitx_ctx *c) { return c ? c->nreg : 0; }
+int vitx_ctx_out_rows(const vitx_ctx *c) { return c ? c->R : 0; }
+size_t vitx_ctx_weight_bytes(const vitx_ctx *c) { return c ? c->wset->weight_bytes : 0; }
+int vitx_ctx_shares_weights(const vitx_ctx *c) { return c && c->weights_shared ? 1 : 0; }
+
+}  // extern "C"

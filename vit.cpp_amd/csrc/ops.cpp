@@ -1,0 +1,267 @@
+// ops.cpp -- single-kernel entry points (vitx_op_*, vitx_preprocess_u8_device): one launcher each, on the caller's buffers, for the
+// parity tests and the kernel benchmarks.  None takes a context.
+#include <initializer_list>
+
+#include "context.h"
+
+// A launcher's hipError_t -> the entry point's return code, with "<name>: <hip string>" as the error text.  `invalid`: the code that
+// hipErrorInvalidValue (the launchers' "no instantiation for this shape") maps to -- each entry point keeps the mapping it always had
+static int op_rc(const char *name, hipError_t e, int invalid = VITX_ERR_HIP) {
+    if (e == hipSuccess) return VITX_OK;
+    set_error("%s: %s", name, hipGetErrorString(e));
+    return e == hipErrorInvalidValue ? invalid : VITX_ERR_HIP;
+}
+// The lo plane of the F16 parity mode behind d_qkv (vitx_op_attention_cls, vitx_op_attention_map): VITX_F16 only, past the hi plane's rows
+static bool lo_plane_ok(const char *name, int dtype, long lo_off, long hi_elems) {
+    if (!lo_off || (dtype == VITX_F16 && lo_off >= hi_elems && lo_off % 8 == 0)) return true;
+    set_error("%s: a lo plane needs VITX_F16 and lo_off %ld a multiple of 8 elements, at least n_img * N * 3 * D = %ld", name, lo_off, hi_elems);
+    return false;
+}
+
+extern "C" {
+
+// ---- single-kernel entry points --------------------------------------------------------------
+int vitx_op_layernorm(int dtype, const void *x, const void *w, const void *b, void *y, int M, int D, float eps, void *stream) {
+    if (!x || !w || !b || !y || M <= 0) return VITX_ERR_ARG;
+    return op_rc("vitx_op_layernorm", launch_layernorm(dtype, (const float *)x, D, (const float *)w, (const float *)b, y, D, M, D, eps, (hipStream_t)stream), VITX_ERR_UNSUPPORTED);
+}
+static int op_gemm_impl(int dtype, int epi, int kernel, const void *a, const void *w, const void *bias, void *out, const void *pos, int M, int M_real, int N, int n_pad, int K, int tpi, void *stream) {
+    if (!a || !w || !out || !bias || epi < 0 || epi > EPI_BIAS_HILO || M_real <= 0 || M_real > M || (epi == EPI_PATCH && (!pos || tpi <= 0))) { set_error("vitx_op_gemm_ex: invalid argument"); return VITX_ERR_ARG; }
+    if (M % 128 || N % 4 || K % 64) { set_error("vitx_op_gemm: M %% 128, N %% 4, K %% 64 must be 0"); return VITX_ERR_ARG; }
+    const Tuning *t0 = tuning_for_device(-1);
+    if (!t0) { set_error("vitx_op_gemm: kernel bring-up failed"); return VITX_ERR_HIP; }
+    Tuning t = *t0;
+    if (kernel == 2) t.gemm_split = 1;
+    else if (kernel == 1) t.gemm_cfg = 1;                  // ping-pong persistent kernel
+    else if (kernel != 0) t.gemm_cfg = kernel;
+    // W (and bias) must hold n_pad rows; rows beyond N are never stored
+    GemmArgs g = dense_gemm(a, w, (const float *)bias, out, M, M_real, N, n_pad, K);
+    g.pos = (const float *)pos; g.tpi = tpi;
+    g.hilo_off = epi == EPI_BIAS_HILO ? (long)M * N : 0;          // the lo plane follows the [M][N] hi plane
+    hipError_t e = launch_gemm(t, dtype, epi, g, (hipStream_t)stream);
+    if (e == hipErrorInvalidValue) { set_error("vitx_op_gemm: kernel %d cannot tile M %d N %d K %d", kernel, M, N, K); return VITX_ERR_UNSUPPORTED; }
+    return op_rc("vitx_op_gemm", e);
+}
+int vitx_op_gemm_ex(int dtype, int epi, int kernel, const void *a, const void *w, const void *bias, void *out, const void *pos, int M, int M_real, int N, int K, int tpi, void *stream) {
+    return op_gemm_impl(dtype, epi, kernel, a, w, bias, out, pos, M, M_real, N, round_up(N, 256), K, tpi, stream);     // W and bias hold N rounded up to 256 rows
+}
+int vitx_op_gemm(int dtype, int epi, const void *a, const void *w, const void *bias, void *out, int M, int N, int K, void *stream) {
+    if (epi < 0 || epi > 3 || N % 64) { set_error("vitx_op_gemm: epi 0..3, N %% 64 == 0"); return VITX_ERR_ARG; }
+    return op_gemm_impl(dtype, epi, 0, a, w, bias, out, nullptr, M, M, N, round_up(N, gemm_tile_n()), K, 0, stream);   // W and bias hold N rounded up to 128 rows
+}
+// x[M][N] f32 += A[M][K] . W[N][K]^T + bias, then y[M][N] (dtype) = LayerNorm(x) * ln_w + ln_b computed by the GEMM's own epilogue
+// (GemmLn) + the fix-up launch.  `test`: GemmLn::test (forced time-outs).  Synchronous; *fallbacks = tiles that took the fix-up path.
+int vitx_op_gemm_ln(int dtype, const void *a, const void *w, const void *bias, void *x, const void *ln_w, const void *ln_b, void *y, int M, int N, int K, float eps,
+                    int test, int timeout_us, int *fallbacks, void *stream) {
+    if (!a || !w || !bias || !x || !ln_w || !ln_b || !y || M <= 0 || timeout_us < 0) { set_error("vitx_op_gemm_ln: invalid argument"); return VITX_ERR_ARG; }
+    const Tuning *t0 = tuning_for_device(-1);
+    if (!t0) { set_error("vitx_op_gemm_ln: kernel bring-up failed"); return VITX_ERR_HIP; }
+    GemmArgs g = dense_gemm(a, w, (const float *)bias, x, M, M, N, N, K);
+    if (!gemm_ln_fusable(*t0, g)) { set_error("vitx_op_gemm_ln: M %d N %d K %d does not take the LayerNorm-fusing kernel (M %% 256, N in {256,512,768,1024}, >= 128 tiles, K %% 128)", M, N, K); return VITX_ERR_UNSUPPORTED; }
+    static unsigned epoch = 0x40000000u;       // its own tag range (the scratch is private to the call anyway)
+    const size_t nb = (size_t)M / 256, sync_bytes = nb * (N / 256) * 256 * 2 * sizeof(unsigned long long);
+    unsigned long long *sync = nullptr; unsigned *todo = nullptr;
+    HIP_TRY(hipMalloc((void **)&sync, sync_bytes));
+    const DevMem sync_own(sync);
+    if (hipMalloc((void **)&todo, (nb + 1) * 4) != hipSuccess) return VITX_ERR_NOMEM;
+    const DevMem todo_own(todo);
+    hipStream_t st = (hipStream_t)stream;
+    GemmLn ln{};
+    ln.w = (const float *)ln_w; ln.b = (const float *)ln_b; ln.out = y; ln.eps = eps; ln.sync = sync; ln.todo = todo; ln.fallbacks = todo + nb;
+    ln.epoch = ++epoch; ln.timeout = (unsigned)timeout_us * 100u; ln.test = test;
+    g.ln = &ln;
+    hipError_t e = hipMemsetAsync(sync, 0, sync_bytes, st);
+    if (e == hipSuccess) e = hipMemsetAsync(todo, 0, (nb + 1) * 4, st);
+    if (e == hipSuccess) e = launch_gemm(*t0, dtype, EPI_BIAS_RESID, g, st);
+    if (e == hipSuccess) e = launch_layernorm_fixup(dtype, (const float *)x, ln.w, ln.b, y, M, N, eps, todo, ln.epoch, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    unsigned fb = 0;
+    if (e == hipSuccess) e = hipMemcpy(&fb, todo + nb, 4, hipMemcpyDeviceToHost);
+    if (fallbacks) *fallbacks = (int)fb;
+    return op_rc("vitx_op_gemm_ln", e);
+}
+// quantised-weight kernels (quant.hip, gemm_nt_kernel<.., Q4>): blocks in the FILE's byte layout for every type except q4_0, whose
+// nibble plane / scale plane split is done here the way the context does it at upload
+int vitx_op_dequant(int dtype, int qtype, const void *blocks, const void *scales, void *out, int N, int n_pad, int K, void *stream) {
+    if (!blocks || !out || N <= 0 || n_pad < N || K <= 0 || K % 32 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_dequant: invalid argument"); return VITX_ERR_ARG; }
+    DequantJob j{blocks, scales, out, N, n_pad, K / 32};
+    return op_rc("vitx_op_dequant", launch_dequant(dtype, qtype, &j, 1, (hipStream_t)stream), VITX_ERR_ARG);
+}
+// launch_dequant as the forward calls it (SliceForward::expand, forward.cpp): up to four matrices of one block type in ONE launch
+int vitx_op_dequant_jobs(int dtype, int qtype, int njobs, const void *const *blocks, const void *const *scales, void *const *out, const int *N, const int *n_pad, const int *K, void *stream) {
+    if (njobs < 1 || njobs > 4 || !blocks || !out || !N || !n_pad || !K || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_dequant_jobs: invalid argument"); return VITX_ERR_ARG; }
+    DequantJob jobs[4];
+    for (int j = 0; j < njobs; ++j) {
+        if (!blocks[j] || !out[j] || N[j] <= 0 || n_pad[j] < N[j] || K[j] <= 0 || K[j] % 32) { set_error("vitx_op_dequant_jobs: invalid argument in job %d", j); return VITX_ERR_ARG; }
+        jobs[j] = DequantJob{blocks[j], scales ? scales[j] : nullptr, out[j], N[j], n_pad[j], K[j] / 32};
+    }
+    return op_rc("vitx_op_dequant_jobs", launch_dequant(dtype, qtype, jobs, njobs, (hipStream_t)stream), VITX_ERR_ARG);
+}
+int vitx_op_gemm_q4(int dtype, int epi, const void *a, const void *qs, const void *scales, const void *bias, void *out, int M, int M_real, int N, int K, void *stream) {
+    if (!a || !qs || !scales || !bias || !out || epi < 0 || epi > EPI_BIAS_F32 || M_real <= 0 || M_real > M) { set_error("vitx_op_gemm_q4: invalid argument"); return VITX_ERR_ARG; }
+    if (!tuning_for_device(-1)) { set_error("vitx_op_gemm_q4: kernel bring-up failed"); return VITX_ERR_HIP; }
+    GemmArgs g = dense_gemm(a, qs, (const float *)bias, out, M, M_real, N, round_up(N, 128), K);
+    g.Wscale = (const uint16_t *)scales;
+    hipError_t e = launch_gemm_q4(dtype, epi, g, (hipStream_t)stream);
+    if (e == hipErrorInvalidValue) { set_error("vitx_op_gemm_q4: M %% 128, K %% 64 must be 0 (M %d N %d K %d)", M, N, K); return VITX_ERR_UNSUPPORTED; }
+    return op_rc("vitx_op_gemm_q4", e);
+}
+// ---- MXFP8 single-kernel entry points (include/vitx.h) ----
+int vitx_op_quantize_mxfp8(const void *x, int rows, int K, int k_pad, void *q, void *scales, void *stream) {
+    if (!x || !q || !scales || rows <= 0 || K <= 0 || k_pad < K || k_pad % kMxBlock) { set_error("vitx_op_quantize_mxfp8: invalid argument"); return VITX_ERR_ARG; }
+    return op_rc("vitx_op_quantize_mxfp8", launch_quantize_mx8((const float *)x, rows, K, k_pad, (uint8_t *)q, (uint8_t *)scales, (hipStream_t)stream));
+}
+int vitx_op_layernorm_mxfp8(const void *x, const void *w, const void *b, void *q, void *scales, int M, int D, float eps, void *stream) {
+    if (!x || !w || !b || !q || !scales || M <= 0 || D <= 0) { set_error("vitx_op_layernorm_mxfp8: invalid argument"); return VITX_ERR_ARG; }
+    if (D % kMxBlock || !layernorm_supports(D)) { set_error("vitx_op_layernorm_mxfp8: hidden size %d has no MX LayerNorm instantiation", D); return VITX_ERR_UNSUPPORTED; }
+    return op_rc("vitx_op_layernorm_mxfp8", launch_layernorm_mx8((const float *)x, D, (const float *)w, (const float *)b, (uint8_t *)q, (uint8_t *)scales, mx_k_pad(D), M, D, eps, (hipStream_t)stream));
+}
+int vitx_op_gemm_mxfp8(int epi, const void *a, const void *a_scales, const void *w, const void *w_scales, const void *bias, void *out, void *out_scales,
+                       int M, int N, int K, void *stream) {
+    if (!a || !a_scales || !w || !w_scales || !bias || !out || M <= 0 || N <= 0 || K <= 0 || (epi != EPI_BIAS && epi != EPI_BIAS_GELU && epi != EPI_BIAS_RESID) ||
+        (epi == EPI_BIAS_GELU && !out_scales)) { set_error("vitx_op_gemm_mxfp8: invalid argument"); return VITX_ERR_ARG; }
+    if (!tuning_for_device(-1)) { set_error("vitx_op_gemm_mxfp8: kernel bring-up failed"); return VITX_ERR_HIP; }
+    const GemmArgs g = dense_gemm(a, w, (const float *)bias, out, M, M, N, round_up(N, 128), mx_k_pad(K), epi == EPI_BIAS_GELU ? mx_k_pad(N) : N);
+    const hipError_t e = launch_gemm_mx8(epi, g, (const uint8_t *)a_scales, (const uint8_t *)w_scales, (uint8_t *)out_scales, (hipStream_t)stream);
+    if (e == hipErrorInvalidValue) { set_error("vitx_op_gemm_mxfp8: the kernel cannot tile M %d N %d K %d", M, N, K); return VITX_ERR_UNSUPPORTED; }
+    return op_rc("vitx_op_gemm_mxfp8", e);
+}
+
+int vitx_op_attention_ex(int dtype, int kernel, const void *qkv, void *out, int n_img, int N, int D, int H, void *stream) {
+    if (!qkv || !out || n_img <= 0 || kernel < 0) return VITX_ERR_ARG;
+    const Tuning *t0 = tuning_for_device(-1);
+    if (!t0) { set_error("vitx_op_attention: kernel bring-up failed"); return VITX_ERR_HIP; }
+    Tuning t = *t0;
+#ifdef VITX_LAB
+    t.attn_flags = kernel >> 4; kernel &= 15;                // bits 4+: ablation build of the pipelined kernel (tools/attn_bench.py only)
+#endif
+    if (kernel == ATTN_PERSIST) {                            // persistent single-pass kernel (193..224 tokens)
+        if (N <= 192 || N > 224) { set_error("vitx_op_attention: the persistent kernel takes 193..224 tokens, not %d", N); return VITX_ERR_UNSUPPORTED; }
+    } else if (kernel == ATTN_SINGLE) {                      // single-pass kernel, also where the automatic choice prefers the pipelined one
+        if (!attention_single_pass_supports(N)) { set_error("vitx_op_attention: no single-pass instantiation for %d tokens", N); return VITX_ERR_UNSUPPORTED; }
+    } else if (kernel == ATTN_STREAM) {                      // streaming two-pass kernel (attention_stream.hip), head dim 64
+        if (!attention_stream_supports(n_img, N, D, H)) { set_error("vitx_op_attention: the streaming kernel needs head_dim 64"); return VITX_ERR_UNSUPPORTED; }
+    } else if (kernel != ATTN_AUTO && kernel != ATTN_FLOW) { set_error("vitx_op_attention: unknown kernel id %d", kernel); return VITX_ERR_ARG; }
+    t.attn_kernel = kernel;
+    return op_rc("vitx_op_attention", launch_attention(t, dtype, qkv, out, n_img, N, D, H, (hipStream_t)stream), VITX_ERR_UNSUPPORTED);
+}
+int vitx_op_attention(int dtype, const void *qkv, void *out, int n_img, int N, int D, int H, void *stream) { return vitx_op_attention_ex(dtype, 0, qkv, out, n_img, N, D, H, stream); }
+// The precise kernel on planes that are already split (what the QKV GEMM's epilogue 5 emits): d_hi [n_img * N][3 D] fp16, the lo plane lo_off
+// ELEMENTS behind it.  Only enqueues on `stream`.
+int vitx_op_attention_planes(const void *d_hi, long lo_off, void *out, int n_img, int N, int D, int H, void *stream) {
+    if (!d_hi || !out || n_img <= 0 || N <= 0 || D <= 0 || H <= 0) { set_error("vitx_op_attention_planes: invalid argument"); return VITX_ERR_ARG; }
+    // the lo plane lies a whole number of 4-element groups behind the hi plane's rows and inside the 32-bit byte window the kernels address
+    if (lo_off < (long)n_img * N * 3 * D || lo_off % 4 != 0 || (size_t)lo_off * 2 + (size_t)n_img * N * 3 * D * 2 > 0xf0000000u) {
+        set_error("vitx_op_attention_planes: lo_off %ld must be a multiple of 4 elements, at least n_img * N * 3 * D = %ld, and keep both planes below 0xf0000000 bytes", lo_off, (long)n_img * N * 3 * D);
+        return VITX_ERR_ARG;
+    }
+    if (!tuning_for_device(-1)) { set_error("vitx_op_attention_planes: kernel bring-up failed"); return VITX_ERR_HIP; }
+    if (!attention_stream_supports(n_img, N, D, H)) { set_error("vitx_op_attention_planes: head_dim must be 64"); return VITX_ERR_UNSUPPORTED; }
+    return op_rc("vitx_op_attention_planes", launch_attention_stream(DT_F16, true, d_hi, out, n_img, N, D, H, lo_off, (hipStream_t)stream));
+}
+// Attention of token 0 of every image (the row the last layer of a classifier keeps, vit.cpp:910-911): out[n_img][D] (dtype).  lo_off != 0: the two
+// fp16 planes of the F16 parity mode (VITX_F16 only), as vitx_op_attention_planes takes them.  Only enqueues on `stream`.
+int vitx_op_attention_cls(int dtype, const void *d_qkv, long lo_off, void *out, int n_img, int N, int D, int H, void *stream) {
+    if (!d_qkv || !out || n_img <= 0 || N <= 0 || D <= 0 || H <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_attention_cls: invalid argument"); return VITX_ERR_ARG; }
+    if (!lo_plane_ok("vitx_op_attention_cls", dtype, lo_off, (long)n_img * N * 3 * D)) return VITX_ERR_ARG;
+    if (!attention_cls_supports(N, D, H)) { set_error("vitx_op_attention_cls: head_dim must be 8, 16, 32, 64 or 128 and N at most 15360 (head_dim %d, N %d)", D / H, N); return VITX_ERR_UNSUPPORTED; }
+    return op_rc("vitx_op_attention_cls", launch_attention_cls(dtype, d_qkv, lo_off, out, nullptr, nullptr, n_img, N, D, H, (hipStream_t)stream));
+}
+// The parity mode's attention on f32 q, k, v (what the reference multiplies, vit.cpp:848,858): splits the rows into the two fp16 planes the
+// QKV GEMM's EPI_BIAS_HILO epilogue emits, then runs the precise streaming kernel.  Synchronous (allocates its own scratch).
+int vitx_op_attention_f32(const float *qkv_f32, void *out, int n_img, int N, int D, int H, void *stream) {
+    if (!qkv_f32 || !out || n_img <= 0 || N <= 0 || D <= 0 || H <= 0) { set_error("vitx_op_attention_f32: invalid argument"); return VITX_ERR_ARG; }
+    if (!tuning_for_device(-1)) { set_error("vitx_op_attention_f32: kernel bring-up failed"); return VITX_ERR_HIP; }
+    if (!attention_stream_supports(n_img, N, D, H)) { set_error("vitx_op_attention_f32: head_dim must be 64"); return VITX_ERR_UNSUPPORTED; }
+    const size_t n = (size_t)n_img * N * 3 * D;
+    void *planes = nullptr;
+    HIP_TRY(hipMalloc(&planes, n * 2 * 2 + 64));
+    const DevMem planes_own(planes);
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = launch_split_hilo(DT_F16, qkv_f32, planes, (char *)planes + n * 2, n, st);
+    if (e == hipSuccess) e = launch_attention_stream(DT_F16, true, planes, out, n_img, N, D, H, (long)n, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    return op_rc("vitx_op_attention_f32", e);
+}
+int vitx_op_softmax_dt(int dtype, const void *logits, void *probs, int rows, int cols, int ld, void *stream) {
+    if (!logits || !probs || rows <= 0 || cols <= 0 || ld < cols || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_softmax: invalid argument"); return VITX_ERR_ARG; }
+    return op_rc("vitx_op_softmax", launch_softmax(dtype, (const float *)logits, (float *)probs, rows, cols, ld, (hipStream_t)stream));
+}
+int vitx_op_softmax(const void *logits, void *probs, int rows, int cols, int ld, void *stream) { return vitx_op_softmax_dt(VITX_F16, logits, probs, rows, cols, ld, stream); }
+// launch_topk as the sharded forward calls it (sharded.cpp): pairs {f32 probability, i32 class} of every row
+int vitx_op_topk(const void *probs, int rows, int cols, int k, void *pairs, void *stream) {
+    if (!probs || !pairs || rows <= 0 || cols <= 0 || k <= 0 || k > cols) { set_error("vitx_op_topk: invalid argument"); return VITX_ERR_ARG; }
+    return op_rc("vitx_op_topk", launch_topk((const float *)probs, rows, cols, k, pairs, (hipStream_t)stream));
+}
+
+// The feature kernel on its own.  Every argument check comes before the first device call.  `name`: the entry point that was called; `ex`:
+// it is vitx_op_features_ex, whose texts also tell `first`.  vitx_op_features is first = 1 and no head operand (so d_z never counts as its output).
+static int op_features(const char *name, bool ex, const void *d_x, long row_stride, long img_stride, const void *d_w, const void *d_b, void *d_cls, void *d_mean,
+                       void *d_tokens, long out_img_stride, int n_img, int N, int first, int D, float eps, int l2, void *d_z, int dtype, void *stream) {
+    if (!d_x || !d_w || !d_b || (!d_cls && !d_mean && !d_tokens && !d_z) || n_img <= 0 || N <= 0 || D <= 0 || first < 1 || first > N) { set_error("%s: invalid argument", name); return VITX_ERR_ARG; }
+    if (first == N && (d_mean || d_tokens || d_z)) {
+        if (ex) set_error("vitx_op_features_ex: the mean and the tokens need at least one patch row (N %d, first %d)", N, first);
+        else set_error("vitx_op_features: the mean and the tokens need at least one patch row (N %d)", N);
+        return VITX_ERR_ARG;
+    }
+    if (d_z && dtype != VITX_F16 && dtype != VITX_BF16) { set_error("%s: the head operand is VITX_F16 or VITX_BF16", name); return VITX_ERR_ARG; }
+    for (const void *p : {d_x, d_w, d_b, (const void *)d_cls, (const void *)d_mean, (const void *)d_tokens, (const void *)d_z})
+        if ((uintptr_t)p % 16) { set_error("%s: pointers must be 16-byte aligned", name); return VITX_ERR_ARG; }
+    if (row_stride % 4 || img_stride % 4 || out_img_stride % 4) { set_error("%s: strides must be multiples of 4 floats", name); return VITX_ERR_ARG; }
+    if (!layernorm_supports(D)) { set_error("%s: hidden size %d has no LayerNorm instantiation", name, D); return VITX_ERR_UNSUPPORTED; }
+    return op_rc(name, launch_features((const float *)d_x, row_stride, img_stride, (const float *)d_w, (const float *)d_b, (float *)d_cls, (float *)d_mean, (float *)d_tokens,
+                                       out_img_stride, n_img, N, D, eps, l2 != 0, (hipStream_t)stream, first, d_z, dtype));
+}
+int vitx_op_features(const void *d_x, long row_stride, long img_stride, const void *d_w, const void *d_b, void *d_cls, void *d_mean, void *d_tokens, long out_img_stride,
+                     int n_img, int N, int D, float eps, int l2, void *stream) {
+    return op_features("vitx_op_features", false, d_x, row_stride, img_stride, d_w, d_b, d_cls, d_mean, d_tokens, out_img_stride, n_img, N, 1, D, eps, l2, nullptr, VITX_F16, stream);
+}
+int vitx_op_features_ex(const void *d_x, long row_stride, long img_stride, const void *d_w, const void *d_b, void *d_cls, void *d_mean, void *d_tokens, long out_img_stride,
+                        int n_img, int N, int first, int D, float eps, int l2, void *d_z, int dtype, void *stream) {
+    return op_features("vitx_op_features_ex", true, d_x, row_stride, img_stride, d_w, d_b, d_cls, d_mean, d_tokens, out_img_stride, n_img, N, first, D, eps, l2, d_z, dtype, stream);
+}
+// The product's patch-embedding kernel on its own (TEST ONLY: allocates, uploads and synchronises).  d_w: the f32 kernel [D][Cin * P * P] in the
+// file's order (channel-major); it is rounded (RNE) to the operand type, K-permuted and padded exactly as the context does at upload.
+int vitx_op_patch_embed(int dtype, const void *d_img, const void *d_w, const void *d_bias, const void *d_pos, const void *d_cls, const void *d_reg, int R, void *d_X,
+                        int n_img, int S, int P, int Cin, int D, void *stream) {
+    if (!d_img || !d_w || !d_bias || !d_pos || !d_cls || !d_X || R < 0 || (R > 0 && !d_reg) || n_img <= 0 || S <= 0 || P <= 0 || S % P || Cin <= 0 || D <= 0 || D % 4 ||
+        (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_patch_embed: invalid argument"); return VITX_ERR_ARG; }
+    if (!tuning_for_device(-1)) { set_error("vitx_op_patch_embed: kernel bring-up failed"); return VITX_ERR_HIP; }
+    const int K = Cin * P * P, k_pad = round_up(K, 64), n_pad = round_up(D, gemm_tile_n());
+    std::vector<float> wf((size_t)D * K);
+    HIP_TRY(hipMemcpy(wf.data(), d_w, wf.size() * 4, hipMemcpyDeviceToHost));
+    const std::vector<uint16_t> hp = operand_matrix_host(dtype, wf.data(), nullptr, D, K, n_pad, k_pad, P, Cin);
+    void *w_perm = nullptr; float *bias = nullptr;
+    HIP_TRY(hipMalloc(&w_perm, hp.size() * 2));
+    const DevMem w_own(w_perm);
+    if (hipMalloc((void **)&bias, (size_t)n_pad * 4) != hipSuccess) return VITX_ERR_NOMEM;
+    const DevMem bias_own(bias);
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemcpy(w_perm, hp.data(), hp.size() * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(bias, 0, (size_t)n_pad * 4);
+    if (e == hipSuccess) e = hipMemcpy(bias, d_bias, (size_t)D * 4, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = launch_patch_embed(dtype, (const float *)d_img, w_perm, bias, (const float *)d_pos, (const float *)d_cls, (const float *)d_reg, R,
+                                                (float *)d_X, n_img, S, P, Cin, D, n_pad, k_pad, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    return op_rc("vitx_op_patch_embed", e, VITX_ERR_UNSUPPORTED);
+}
+// The map kernels on their own (the parity tests): d_cls [n_img][H][N] class-token rows, d_mean [n_img][N][N] mean_h A_h (either may be NULL).
+int vitx_op_attention_map(int dtype, const void *d_qkv, long lo_off, void *d_cls, void *d_mean, int n_img, int N, int D, int H, void *stream) {
+    if (!d_qkv || (!d_cls && !d_mean) || n_img <= 0 || N <= 0 || D <= 0 || H <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_attention_map: invalid argument"); return VITX_ERR_ARG; }
+    if (!lo_plane_ok("vitx_op_attention_map", dtype, lo_off, (long)n_img * N * 3 * D)) return VITX_ERR_ARG;
+    if (!attention_map_supports(N, D, H)) { set_error("vitx_op_attention_map: head_dim must be a multiple of 8 up to 128 (D %d, H %d)", D, H); return VITX_ERR_UNSUPPORTED; }
+    if (d_mean && !attention_mean_supports(N, D, H)) { set_error("vitx_op_attention_map: the head mean takes at most %d tokens (N %d)", kAttnMeanMaxTokens, N); return VITX_ERR_UNSUPPORTED; }
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSuccess;
+    if (d_cls) e = launch_attention_cls_map(dtype, d_qkv, lo_off, (float *)d_cls, (long)H * N, n_img, N, D, H, st);
+    if (e == hipSuccess && d_mean) e = launch_attention_head_mean(dtype, d_qkv, lo_off, (float *)d_mean, n_img, N, D, H, false, st);
+    return op_rc("vitx_op_attention_map", e);
+}
+
+int vitx_preprocess_u8_device(const void *d_hwc, int n, int nx, int ny, int img_size, int interp, void *d_out, void *stream) {
+    if (!d_hwc || !d_out || n <= 0 || nx <= 0 || ny <= 0 || img_size <= 0) { set_error("vitx_preprocess_u8_device: invalid argument"); return VITX_ERR_ARG; }
+    if (interp != VITX_BICUBIC && interp != VITX_BILINEAR) { set_error("vitx_preprocess_u8_device: interpolation mode %d is not supported", interp); return VITX_ERR_ARG; }
+    return op_rc("vitx_preprocess_u8_device", launch_preprocess(d_hwc, (float *)d_out, n, nx, ny, img_size, interp == VITX_BICUBIC, (hipStream_t)stream));
+}
+
+}  // extern "C"

@@ -1,0 +1,197 @@
+// outputs.cpp -- what a context gives besides probabilities: the per-kernel profile, the residual-stream trace, attention maps, features,
+// and the diagnostics counters.  All opt-in; the forward (forward.cpp) launches nothing for an output that is off.
+#include <utility>
+
+#include "context.h"
+
+// Synchronise and copy the n x fpi floats of an opt-in output to the host, or say why not.  `api`: "vitx_attn" / "vitx_feat"; n: the images
+// of the last forward made with the output on (0: it is off, or no forward since <api>_enable)
+static int read_output(vitx_ctx *c, const char *api, const char *what, int n, int fpi, const float *buf, float *out, size_t n_floats) {
+    if (!out) return VITX_ERR_ARG;
+    if (n == 0) { set_error("%s_read: no forward has run with %s on since %s_enable", api, what, api); return VITX_ERR_ARG; }
+    const size_t need = (size_t)n * fpi;
+    if (n_floats < need) { set_error("%s_read: buffer too small (%zu floats needed for %d images)", api, need, n); return VITX_ERR_ARG; }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, buf, need * 4, hipMemcpyDeviceToHost));
+    return VITX_OK;
+}
+
+extern "C" {
+
+int vitx_profile_enable(vitx_ctx *c, int on) {
+    if (!c) return VITX_ERR_ARG;
+    HIP_TRY(hipSetDevice(c->device));
+    c->prof_on = on != 0; c->recs.clear(); c->ev_used = 0;
+    if (on) {       // time origin for the busy-interval union (kernels of concurrent slices overlap)
+        if (!c->prof_base) HIP_TRY(hipEventCreate(&c->prof_base));
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipEventRecord(c->prof_base, c->stream));
+        HIP_TRY(hipEventSynchronize(c->prof_base));
+    }
+    return VITX_OK;
+}
+
+// What the HIP-event bracket of vitx_profile_enable adds to ONE launch: 32 x [record, 20 us kernel that stamps its own first and last
+// wall-clock reading, record] queued back to back on the context's stream like a profiled forward; the median of
+// (event interval - the kernel's own interval).  bench.py subtracts it from every launch of the profiled step (r04: the bracket read
+// 5.3-5.5 us above the device's dispatch stamps for every kernel class, so `roofline.achieved` was 4-13 % low).
+int vitx_profile_bracket_us(vitx_ctx *c, double *bracket_us) {
+    if (!c || !bracket_us) return VITX_ERR_ARG;
+    HIP_TRY(hipSetDevice(c->device));
+    constexpr int NB = 32;
+    long long *d_st = nullptr; hipEvent_t ev[2 * NB];
+    HIP_TRY(hipMalloc((void **)&d_st, sizeof(long long) * 2 * NB));
+    const DevMem d_st_own(d_st);
+    int made = 0; hipError_t e = hipSuccess;
+    while (made < 2 * NB) { if ((e = hipEventCreate(&ev[made])) != hipSuccess) break; ++made; }      // `made` counts the handles that exist
+    // nothing else of this device may be in flight (another slice stream's forward would stretch the brackets): the whole device, not only c->stream
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    for (int i = 0; i < NB && e == hipSuccess; ++i) {
+        e = hipEventRecord(ev[2 * i], c->stream);
+        if (e == hipSuccess) e = launch_spin_stamp(20, d_st + 2 * i, c->stream);
+        if (e == hipSuccess) e = hipEventRecord(ev[2 * i + 1], c->stream);
+    }
+    long long h_st[2 * NB];
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(h_st, d_st, sizeof h_st, hipMemcpyDeviceToHost);
+    std::vector<double> over;
+    for (int i = 0; i < NB && e == hipSuccess; ++i) {
+        float ms = 0.0f;
+        e = hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]);
+        over.push_back((double)ms * 1e3 - (double)(h_st[2 * i + 1] - h_st[2 * i]) * 0.01);
+    }
+    for (int i = 0; i < made; ++i) (void)hipEventDestroy(ev[i]);
+    if (e != hipSuccess) { set_error("vitx_profile_bracket_us: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
+    std::sort(over.begin(), over.end());
+    *bracket_us = over[over.size() / 2];
+    return VITX_OK;
+}
+
+int vitx_profile_read(vitx_ctx *c, vitx_prof_entry *out, int max_entries, int *n_entries) {
+    if (!c || !out || !n_entries) return VITX_ERR_ARG;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());
+    vitx_prof_entry acc[PC_COUNT];
+    std::vector<std::pair<float, float>> iv[PC_COUNT];
+    for (int i = 0; i < PC_COUNT; ++i) acc[i] = vitx_prof_entry{kProfNames[i], 0, 0.0, 0.0, 0.0, 0.0};
+    for (const auto &r : c->recs) {
+        float ms = 0.0f, ta = 0.0f, tb = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, r.a, r.b));
+        if (c->prof_base) { HIP_TRY(hipEventElapsedTime(&ta, c->prof_base, r.a)); HIP_TRY(hipEventElapsedTime(&tb, c->prof_base, r.b)); iv[r.cls].push_back({ta, tb}); }
+        acc[r.cls].launches++; acc[r.cls].total_ms += ms; acc[r.cls].flops += r.flops; acc[r.cls].bytes += r.bytes;
+    }
+    for (int i = 0; i < PC_COUNT; ++i) {        // union of this class's [start, stop] intervals over all streams
+        std::sort(iv[i].begin(), iv[i].end());
+        double busy = 0.0; float cur_a = 0, cur_b = -1;
+        for (auto &p : iv[i]) {
+            if (cur_b < cur_a || p.first > cur_b) { if (cur_b >= cur_a) busy += cur_b - cur_a; cur_a = p.first; cur_b = p.second; }
+            else cur_b = std::max(cur_b, p.second);
+        }
+        if (cur_b >= cur_a && !iv[i].empty()) busy += cur_b - cur_a;
+        acc[i].busy_ms = iv[i].empty() ? acc[i].total_ms : busy;
+    }
+    int k = 0;
+    for (int i = 0; i < PC_COUNT && k < max_entries; ++i) if (acc[i].launches) out[k++] = acc[i];
+    *n_entries = k;
+    c->recs.clear(); c->ev_used = 0;
+    return VITX_OK;
+}
+
+int vitx_ctx_stream_retries(const vitx_ctx *c) { return c ? c->stream_retries : -1; }
+long long vitx_ctx_graph_launches(const vitx_ctx *c) { return c ? c->graph_launches : -1; }
+int vitx_ctx_ln_fusion_active(const vitx_ctx *c) { return c ? ((c->ln_fuse && !c->slices.empty() && c->slices[0].ln_sync && c->tune->n_xcd == 8) ? 1 : (c->ln_fuse_disabled ? -1 : 0)) : 0; }
+long long vitx_ctx_ln_fallbacks(vitx_ctx *c) {
+    if (!c) return -1;
+    if (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return -1;
+    long long total = 0;
+    for (auto &sl : c->slices) {
+        if (!sl.ln_todo) continue;
+        unsigned v = 0;
+        if (hipMemcpy(&v, sl.ln_todo + sl.ln_blocks, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        total += v;
+    }
+    return total;
+}
+
+int vitx_trace_enable(vitx_ctx *c, const int32_t *image_ids, int n) {
+    if (!c || n < 0 || (n > 0 && !image_ids)) return VITX_ERR_ARG;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());
+    if (c->trace_buf) { (void)hipFree(c->trace_buf); c->trace_buf = nullptr; }
+    c->trace_ids.assign(image_ids, image_ids + n);
+    for (int id : c->trace_ids) if (id < 0 || id >= c->max_batch) { c->trace_ids.clear(); set_error("vitx_trace_enable: image id %d outside 0..%d", id, c->max_batch - 1); return VITX_ERR_ARG; }
+    if (n) HIP_TRY(hipMalloc((void **)&c->trace_buf, (size_t)(c->L + 1) * n * c->N * c->D * 4));
+    return VITX_OK;
+}
+int vitx_trace_read(vitx_ctx *c, float *out, size_t n_floats) {
+    if (!c || !out) return VITX_ERR_ARG;
+    const size_t need = (size_t)(c->L + 1) * c->trace_ids.size() * c->N * c->D;
+    if (!c->trace_buf || n_floats < need) { set_error("vitx_trace_read: trace not enabled or buffer too small (%zu floats needed)", need); return VITX_ERR_ARG; }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, c->trace_buf, need * 4, hipMemcpyDeviceToHost));
+    return VITX_OK;
+}
+
+int vitx_attn_enable(vitx_ctx *c, uint64_t layer_mask, int flags) {
+    if (!c) return VITX_ERR_ARG;
+    if (flags & ~VITX_ATTN_ROLLOUT) { set_error("vitx_attn_enable: unknown flags 0x%x", flags); return VITX_ERR_ARG; }
+    if (c->L < 64 && (layer_mask >> c->L)) { set_error("vitx_attn_enable: layer mask 0x%llx names layers beyond the model's %d", (unsigned long long)layer_mask, c->L); return VITX_ERR_ARG; }
+    const bool on = layer_mask != 0 || flags != 0, rollout = (flags & VITX_ATTN_ROLLOUT) != 0;
+    if (on && c->R != 1) { set_error("vitx_attn_enable: attention maps are not available for ViTSTR contexts"); return VITX_ERR_UNSUPPORTED; }
+    if (on && !attention_map_supports(c->N, c->D, c->H)) { set_error("vitx_attn_enable: head_dim %d is not covered by the map kernels", c->D / c->H); return VITX_ERR_UNSUPPORTED; }
+    if (rollout && !attention_mean_supports(c->N, c->D, c->H)) { set_error("vitx_attn_enable: rollout keeps two N x N matrices per image and takes at most %d tokens (this model: %d)", kAttnMeanMaxTokens, c->N); return VITX_ERR_UNSUPPORTED; }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());          // no forward in flight writes the buffers about to be freed
+    c->attn_free();
+    c->attn_mask = 0; c->attn_flags = 0; c->attn_fpi = 0; c->attn_cap = 0; c->attn_n = 0;
+    if (!on) return VITX_OK;
+    const int cap = c->pass_cap(), N = c->N, H = c->H;
+    const int fpi = layer_slot(layer_mask, c->L) * H * N + (rollout ? N : 0);
+    auto alloc = [&](float **p, size_t floats) { if (hipMalloc((void **)p, floats * 4) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; } return true; };
+    bool ok = alloc(&c->attn_out, (size_t)cap * fpi);
+    if (ok && rollout) ok = alloc(&c->attn_roll[0], (size_t)cap * N * N) && alloc(&c->attn_roll[1], (size_t)cap * N * N);
+    if (ok && rollout && !((layer_mask >> (c->L - 1)) & 1)) ok = alloc(&c->attn_cls_last, (size_t)cap * H * N);
+    if (!ok) { c->attn_free(); set_error("vitx_attn_enable: cannot allocate the map buffers for %d images", cap); return VITX_ERR_NOMEM; }
+    c->attn_mask = layer_mask; c->attn_flags = flags; c->attn_fpi = fpi; c->attn_cap = cap;
+    return VITX_OK;
+}
+int vitx_attn_floats(const vitx_ctx *c) { return c ? c->attn_fpi : 0; }
+int vitx_attn_images(const vitx_ctx *c) { return c ? c->attn_n : 0; }
+int vitx_attn_read(vitx_ctx *c, float *out, size_t n_floats) {
+    return c ? read_output(c, "vitx_attn", "attention maps", c->attn_on() ? c->attn_n : 0, c->attn_fpi, c->attn_out, out, n_floats) : VITX_ERR_ARG;
+}
+
+int vitx_feat_enable(vitx_ctx *c, int flags, uint64_t layer_mask) {
+    if (!c) return VITX_ERR_ARG;
+    constexpr int kinds = VITX_FEAT_CLS | VITX_FEAT_MEAN | VITX_FEAT_TOKENS;
+    if (flags & ~(kinds | VITX_FEAT_L2)) { set_error("vitx_feat_enable: unknown flags 0x%x", flags); return VITX_ERR_ARG; }
+    if (flags && !(flags & kinds)) { set_error("vitx_feat_enable: VITX_FEAT_L2 modifies VITX_FEAT_CLS / VITX_FEAT_MEAN and selects nothing on its own"); return VITX_ERR_ARG; }
+    if (c->L < 64 && (layer_mask >> c->L)) { set_error("vitx_feat_enable: layer mask 0x%llx names layers beyond the model's %d", (unsigned long long)layer_mask, c->L); return VITX_ERR_ARG; }
+    if (flags && c->R != 1) { set_error("vitx_feat_enable: features are not available for ViTSTR contexts"); return VITX_ERR_UNSUPPORTED; }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());          // no forward in flight writes the buffer about to be freed
+    c->feat_free();
+    c->feat_flags = 0; c->feat_mask = 0; c->feat_fpi = 0; c->feat_cap = 0; c->feat_n = 0;
+    if (!flags) return VITX_OK;
+    if (!layer_mask) layer_mask = 1ull << (c->L - 1);
+    c->feat_flags = flags;                    // feat_layer_floats() reads it
+    const int cap = c->pass_cap();
+    const size_t fpi = (size_t)layer_slot(layer_mask, c->L) * c->feat_layer_floats();
+    if (fpi > 0x7fffffff || hipMalloc((void **)&c->feat_out, (size_t)cap * fpi * 4) != hipSuccess) {
+        (void)hipGetLastError(); c->feat_out = nullptr; c->feat_flags = 0;
+        set_error("vitx_feat_enable: cannot allocate the feature buffer for %d images of %zu floats", cap, fpi);
+        return VITX_ERR_NOMEM;
+    }
+    c->feat_mask = layer_mask; c->feat_fpi = (int)fpi; c->feat_cap = cap;
+    return VITX_OK;
+}
+int vitx_feat_floats(const vitx_ctx *c) { return c ? c->feat_fpi : 0; }
+int vitx_feat_images(const vitx_ctx *c) { return c ? c->feat_n : 0; }
+const void *vitx_feat_device(const vitx_ctx *c) { return c ? c->feat_out : nullptr; }
+int vitx_feat_read(vitx_ctx *c, float *out, size_t n_floats) {
+    return c ? read_output(c, "vitx_feat", "features", c->feat_on() ? c->feat_n : 0, c->feat_fpi, c->feat_out, out, n_floats) : VITX_ERR_ARG;
+}
+
+}  // extern "C"
