@@ -422,7 +422,7 @@ int vitx_op_attention_planes(const void *d_hi, long lo_off, void *d_out, int n_i
 int vitx_op_softmax(const void *d_logits, void *d_probs, int rows, int cols, int ld, void *stream);
 /* The same with the rounding type of the exp explicit (VITX_F16 = the reference's LUT semantics, VITX_BF16 = the bf16 engine). */
 int vitx_op_softmax_dt(int dtype, const void *d_logits, void *d_probs, int rows, int cols, int ld, void *stream);
-/* The device-side top-k of vitx_group_forward_device (topk_kernel, kernels.hip): d_pairs[rows][k] = {f32 probability, i32 class} of
+/* The device-side top-k of vitx_group_forward_device (topk_kernel, softmax_topk.hip): d_pairs[rows][k] = {f32 probability, i32 class} of
  * d_probs[rows][cols] f32 in the order of vitx_topk; 0 < k <= cols.  Only enqueues on `stream`. */
 int vitx_op_topk(const void *d_probs, int rows, int cols, int k, void *d_pairs, void *stream);
 

@@ -56,12 +56,12 @@ def gemm_wide_cases():
 
 
 def is_wide(M: int, N: int, K: int) -> bool:
-    """Restatement of the dispatcher's is_wide() (kernels.hip) for vitx_op_gemm_ex, whose W holds N rounded up to 256 rows."""
+    """Restatement of the dispatcher's is_wide() (gemm.hip) for vitx_op_gemm_ex, whose W holds N rounded up to 256 rows."""
     return M % 256 == 0 and (M // 256) * (round_up(N, 256) // 256) >= 128
 
 
 def tail_split_rows(M: int, N: int, n_cu: int) -> int:
-    """Rows the forced tail split (kernel 2) leaves to its first launch, 0 when it does not split (launch_gemm, kernels.hip)."""
+    """Rows the forced tail split (kernel 2) leaves to its first launch, 0 when it does not split (launch_gemm, gemm.hip)."""
     ntm, ntn = M // 256, round_up(N, 256) // 256
     tiles = ntm * ntn
     rounds, rem = tiles // n_cu, tiles % n_cu
@@ -301,7 +301,7 @@ def flat_expected(c: np.ndarray, N: int) -> np.ndarray:
 
 # family -> [(n_img, N, H, head_dim)] of the flat, spread and peaked cases: flat data needs no score gap, so every token count runs.  Each
 # family meets N % 16 in {15, 0, 1} and N % 64 in {63, 0, 1} inside its own range with three images (first, middle, last) and two heads:
-#   single   instantiated for ceil(N / 32) in {1 .. 7, 9, 19}: 1 .. 224, 257 .. 288, 577 .. 608 tokens (kAttnNkt, kernels.hip);
+#   single   instantiated for ceil(N / 32) in {1 .. 7, 9, 19}: 1 .. 224, 257 .. 288, 577 .. 608 tokens (kAttnNkt, attention_single.hip);
 #   persist  193 .. 224 tokens, 13 sixteen-key tiles up to 208 and 14 above; 215 = a partly filled fourteenth tile, odd head count;
 #   flow / stream / precise  any count, 64-key chunks (precise: the persistent build for 193 .. 224, the two-pass build elsewhere);
 #   auto     both sides of 192 | 193 (single -> persistent), 208 | 209 (13 -> 14 tiles), 224 | 225 (persistent -> pipelined),

@@ -71,7 +71,7 @@ def is_nan_bits(b: np.ndarray, dtype: int) -> np.ndarray:
 # ------------------------------------------------------------------------------------------------------------------
 # class softmax
 # ------------------------------------------------------------------------------------------------------------------
-# softmax_kernel (kernels.hip):  mx = max x;  e_i = rnd<T>(expf(rnd<T>(x_i - mx)));  p_i = e_i * (1 / sum e).
+# softmax_kernel (softmax_topk.hip):  mx = max x;  e_i = rnd<T>(expf(rnd<T>(x_i - mx)));  p_i = e_i * (1 / sum e).
 EXP_LOW_BITS = {F16: 0xCD00, BF16: 0xC1A0}       # -20 in either type
 SAFE_ULPS = 64                                   # distance kept from every rounding tie of the type, in f32 ulps of exp(x)
 SM_COLS = (1, 2, 63, 64, 65, 255, 256, 257, 1000, 1001, 21843)

@@ -180,7 +180,7 @@ def test_attention_case_lists_meet_every_edge():
     assert all(hd != 64 for _, _, _, hd in X.FLAT_CASES["generic"]) and {hd for _, _, _, hd in X.FLAT_CASES["generic"]} >= {32, 80, 96, 128}
     for f, cases in X.SPREAD_CASES.items():
         assert cases == [c for c in X.FLAT_CASES[f] if c[1] >= X.SPREAD_MIN_N] and len(cases) >= len(X.FLAT_CASES[f]) - 1
-    # what the emulation's schedule follows: the dispatcher's ranges (launch_attention, kernels.hip)
+    # what the emulation's schedule follows: the dispatcher's ranges (launch_attention, attention.hip)
     S = X.attention_schedule
     assert [S("auto", "bf16", n) for n in (192, 193, 224, 225, 256, 257, 288, 289, 577)] == ["single", "single", "single", "online", "online", "single", "single", "online", "online"]
     assert S("auto", "f16", 4097) == "single" and S("flow", "bf16", 197) == "online" and S("precise", "f16", 197) == "precise" and S("stream", "bf16", 577) == "single"

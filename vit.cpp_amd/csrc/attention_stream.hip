@@ -822,9 +822,9 @@ __global__ __launch_bounds__(1024, 4) void attention_precise_kernel(const _Float
 
 static hipError_t check_register_claim(const void *kernel, int threads, int lds, int want_regs);
 template <typename T, int QT, bool PREC>
-static hipError_t launch_stream_inst(const void *qkv, void *out, int n_img, int N, int D, int H, long lo_off, hipStream_t stream) {
+static hipError_t launch_stream_inst(const void *qkv, void *out, int n_img, int N, int D, int H, long lo_off, hipStream_t stream, bool prepare = false) {
     constexpr int W = as::nwaves<PREC>(), NSLOT = as::nslot<PREC>(), lds = NSLOT * as::slot_bytes<PREC>();
-    if (n_img == 0) {      // device bring-up
+    if (prepare) {      // device bring-up
         hipError_t e = hipFuncSetAttribute((const void *)attention_stream_kernel<T, QT, PREC, W, NSLOT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 #if AS_CLAIM
         if (e == hipSuccess) e = check_register_claim((const void *)attention_stream_kernel<T, QT, PREC, W, NSLOT>, W * 64, lds, W == 16 ? 128 : 256);
@@ -853,9 +853,9 @@ static hipError_t check_register_claim(const void *kernel, int threads, int lds,
 }
 
 template <int RES>
-static hipError_t launch_precise_inst(const void *qkv, void *out, int n_img, int N, int D, int H, long lo_off, hipStream_t stream) {
+static hipError_t launch_precise_inst(const void *qkv, void *out, int n_img, int N, int D, int H, long lo_off, hipStream_t stream, bool prepare = false) {
     constexpr int lds = 10 * 2 * as::KB;          // 4 Q chunks + 6 ring slots of 16 KiB
-    if (n_img == 0) {      // device bring-up
+    if (prepare) {      // device bring-up
         hipError_t e = hipFuncSetAttribute((const void *)attention_precise_kernel<RES>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (e == hipSuccess) e = check_register_claim((const void *)attention_precise_kernel<RES>, 1024, lds, 128);
         return e;
@@ -870,25 +870,31 @@ static hipError_t launch_precise_inst(const void *qkv, void *out, int n_img, int
 }
 
 bool attention_stream_supports(int n_img, int N, int D, int H) { return N > 0 && H > 0 && D == H * 64 && n_img >= 0; }
+template <typename T>      // the long-sequence build of an operand type
+static hipError_t launch_stream_t(const void *qkv, void *out, int n_img, int N, int D, int H, hipStream_t stream, bool prepare) {
+    return launch_stream_inst<T, 2, false>(qkv, out, n_img, N, D, H, 0, stream, prepare);
+}
 
 // precise = the F16 parity mode's f32-grade products: qkv holds the hi plane, the lo plane lies lo_off ELEMENTS behind it (EPI_BIAS_HILO)
 hipError_t launch_attention_stream(int dtype, bool precise, const void *qkv, void *out, int n_img, int N, int D, int H, long lo_off, hipStream_t stream) {
-    if (n_img != 0 && !attention_stream_supports(n_img, N, D, H)) return hipErrorInvalidValue;
+    if (n_img <= 0 || !attention_stream_supports(n_img, N, D, H)) return hipErrorInvalidValue;
     if (precise) {
         if (dtype != DT_F16) return hipErrorInvalidValue;
-        if (n_img == 0) {       // bring-up: every precise build
-            hipError_t e = launch_stream_inst<_Float16, 1, true>(qkv, out, 0, N, D, H, lo_off, stream);
-            if (e == hipSuccess) e = launch_precise_inst<13>(qkv, out, 0, N, D, H, lo_off, stream);
-            if (e == hipSuccess) e = launch_precise_inst<14>(qkv, out, 0, N, D, H, lo_off, stream);
-            return e;
-        }
         // 193..224 tokens (ViT-*/16 at 224^2): the persistent kernel -- the score tiles stay in registers, K is streamed once, one workgroup per
         // CU walks the items.  One build per token count, at every batch size: an image's result does not depend on the batch it arrives in.
         if (N > 192 && N <= 208) return launch_precise_inst<13>(qkv, out, n_img, N, D, H, lo_off, stream);
         if (N > 208 && N <= 224) return launch_precise_inst<14>(qkv, out, n_img, N, D, H, lo_off, stream);
         return launch_stream_inst<_Float16, 1, true>(qkv, out, n_img, N, D, H, lo_off, stream);
     }
-    return dtype == DT_F16 ? launch_stream_inst<_Float16, 2, false>(qkv, out, n_img, N, D, H, 0, stream) : launch_stream_inst<__bf16, 2, false>(qkv, out, n_img, N, D, H, 0, stream);
+    return VITX_BY_DTYPE(dtype, launch_stream_t, qkv, out, n_img, N, D, H, stream, false);
+}
+hipError_t prepare_attention_stream() {       // device bring-up: the long-sequence build of both types, then every precise build
+    hipError_t e = hipSuccess;
+    for (int dt = 0; dt < 2 && e == hipSuccess; ++dt) e = VITX_BY_DTYPE(dt, launch_stream_t, nullptr, nullptr, 0, 64, 64, 1, nullptr, true);
+    if (e == hipSuccess) e = launch_stream_inst<_Float16, 1, true>(nullptr, nullptr, 0, 64, 64, 1, 0, nullptr, true);
+    if (e == hipSuccess) e = launch_precise_inst<13>(nullptr, nullptr, 0, 64, 64, 1, 0, nullptr, true);
+    if (e == hipSuccess) e = launch_precise_inst<14>(nullptr, nullptr, 0, 64, 64, 1, 0, nullptr, true);
+    return e;
 }
 
 // ------------------------------------------------------------------------------------------------

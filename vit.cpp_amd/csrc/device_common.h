@@ -151,7 +151,7 @@ __device__ __forceinline__ float rows4_sum(float x) {       // (row 0 + row 1) +
 
 // ------------------------------------------------------------------------------------------------
 // LayerNorm statistics by 256-column tiles (ggml_norm, /root/reference/vit.cpp:808-812, 881-885): the ONE definition both the
-// stand-alone kernel (kernels.hip) and the LayerNorm fused into the residual GEMMs (gemm_pp.hip) follow, operation for operation,
+// stand-alone kernel (layernorm.hip) and the LayerNorm fused into the residual GEMMs (gemm_pp.hip) follow, operation for operation,
 // so that a row's result does not depend on which of them produced it (batch-size independence of the whole forward).
 //   tile c (columns 256 c ..): the row's 256 values are 64 pieces of 4 consecutive columns; piece id = 16 w + 8 j + k
 //     a(piece)  = (x0 + x1) + (x2 + x3)
@@ -190,7 +190,7 @@ __device__ __forceinline__ void ln_combine(const float (&mc)[LN_MAX_TILES], cons
 }
 
 // One row of NT * 256 values by one wave, the tiled definition above: lane l holds piece l of each tile (w = l >> 4, j = (l >> 3) & 1,
-// k = l & 7): one fully coalesced 1 KiB load per tile.  Used by layernorm_kernel, layernorm_fixup_kernel (kernels.hip) and by the
+// k = l & 7): one fully coalesced 1 KiB load per tile.  Used by layernorm_kernel, layernorm_fixup_kernel (layernorm.hip) and by the
 // prologue of a GEMM that consumes rows a LayerNorm-fusing GEMM left to the fix-up (gemm_pp.hip).
 // The row's values (v[c] = columns c * 256 + 4 lane ..) and their statistics, the tiled definition above.
 template <int NT>

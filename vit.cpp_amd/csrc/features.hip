@@ -1,7 +1,7 @@
 // features.hip -- image embeddings and token features (vitx_feat_enable, vitx_op_features; the contract: include/vitx.h).
 //
 // F = ((X - mean) * rstd) * norm.weight + norm.bias of the f32 residual stream X, per row, in f32: the arithmetic of ln_row_tiled /
-// layernorm_kernel (device_common.h, kernels.hip) operation for operation on the shared statistics helpers, WITHOUT the final rounding to
+// layernorm_kernel (device_common.h, layernorm.hip) operation for operation on the shared statistics helpers, WITHOUT the final rounding to
 // the operand type -- so F rounded to nearest even IS what those kernels store (-ffp-contract=off, as for every kernel of the library).
 //
 // One workgroup per image, W waves (feat_waves; one wave when only the class row is asked for), one pass over the image's rows, every row read once:

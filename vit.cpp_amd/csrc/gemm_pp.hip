@@ -655,7 +655,7 @@ static hipError_t launch_pp_t(int epi, const GemmArgs &a, int n_cu, hipStream_t 
 }
 hipError_t launch_gemm_pp(int dtype, int epi, const GemmArgs &a, int n_cu, hipStream_t stream, int flags, bool prepare) {
     if (!prepare && !gemm_pp_supports(a)) return hipErrorInvalidValue;
-    return dtype == DT_F16 ? launch_pp_t<_Float16>(epi, a, n_cu, stream, flags, prepare) : launch_pp_t<__bf16>(epi, a, n_cu, stream, flags, prepare);
+    return VITX_BY_DTYPE(dtype, launch_pp_t, epi, a, n_cu, stream, flags, prepare);
 }
 
 }  // namespace vitx

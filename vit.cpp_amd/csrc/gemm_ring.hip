@@ -417,7 +417,7 @@ bool gemm_ring_supports(const GemmArgs &a, int cfg) {
 }
 
 hipError_t launch_gemm_ring(const Tuning &t, int dtype, int epi, const GemmArgs &a0, int cfg, hipStream_t stream, bool prepare) {
-    if (prepare) return dtype == DT_F16 ? launch_ring_t<_Float16>(a0, epi, cfg, t.n_cu, stream, true) : launch_ring_t<__bf16>(a0, epi, cfg, t.n_cu, stream, true);
+    if (prepare) return VITX_BY_DTYPE(dtype, launch_ring_t, a0, epi, cfg, t.n_cu, stream, true);
     if (!gemm_ring_supports(a0, cfg)) return hipErrorInvalidValue;
     GemmArgs a = a0; a.dbg = 0;
 #ifdef VITX_LAB
@@ -429,7 +429,7 @@ hipError_t launch_gemm_ring(const Tuning &t, int dtype, int epi, const GemmArgs 
         long long *buf = nullptr;
         if (hipHostMalloc((void **)&buf, (size_t)nwg * 32, 0) != hipSuccess) return hipErrorOutOfMemory;
         a.pos = (const float *)buf;
-        hipError_t e = dtype == DT_F16 ? launch_ring_t<_Float16>(a, epi, cfg, t.n_cu, stream, false) : launch_ring_t<__bf16>(a, epi, cfg, t.n_cu, stream, false);
+        hipError_t e = VITX_BY_DTYPE(dtype, launch_ring_t, a, epi, cfg, t.n_cu, stream, false);
         (void)hipDeviceSynchronize();
         long long t0 = buf[0], t1 = 0; double sum = 0, sumc = 0;
         for (int b = 0; b < nwg; ++b) { t0 = std::min(t0, buf[b * 4]); t1 = std::max(t1, buf[b * 4 + 1]); sum += buf[b * 4 + 1] - buf[b * 4]; sumc += buf[b * 4 + 2]; }
@@ -438,7 +438,7 @@ hipError_t launch_gemm_ring(const Tuning &t, int dtype, int epi, const GemmArgs 
         return e;
     }
 #endif
-    return dtype == DT_F16 ? launch_ring_t<_Float16>(a, epi, cfg, t.n_cu, stream, false) : launch_ring_t<__bf16>(a, epi, cfg, t.n_cu, stream, false);
+    return VITX_BY_DTYPE(dtype, launch_ring_t, a, epi, cfg, t.n_cu, stream, false);
 }
 
 }  // namespace vitx

@@ -1,4 +1,10 @@
-// kernels.h -- launchers of the hand-written gfx950 kernels (kernels.hip).
+// kernels.h -- launchers of the hand-written CDNA4 (gfx950) kernels of the ViT forward path, one translation unit per kernel family
+// (gemm*.hip, layernorm.hip, attention*.hip, patch_embed.hip, softmax_topk.hip, image_preprocess.hip, features.hip, quant.hip, ...): each
+// declaration below names its file.
+// Written for MI355X only: 64-lane wavefronts, v_mfma_f32_16x16x32_{f16,bf16} (GEMMs) / v_mfma_f32_32x32x16 (attention),
+// global_load_lds (LDS-DMA) staging with a source-side XOR swizzle, 160 KiB LDS.
+// The math each kernel implements is the ggml op sequence vit_encode_image emits
+// (/root/reference/vit.cpp:718-941); per-kernel citations at the kernels.
 // All pointers are device pointers; every launcher only enqueues on `stream`.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -85,7 +91,7 @@ struct DequantJob { const void *src; const void *scales; void *dst; int N, n_pad
 // Expands up to 4 matrices of one block type in ONE launch: value = exactly what HostTensor::decode_f32 computes, rounded once (RNE) to
 // the operand type -- bit-identical to the host-side expansion at upload.
 hipError_t launch_dequant(int dtype, int qtype, const DequantJob *jobs, int njobs, hipStream_t stream);
-// C = A . dequant(W)^T with the q4_0 blocks expanded inside the GEMM's LDS-fill path (128x128x64 tiles; any epilogue)
+// C = A . dequant(W)^T with the q4_0 blocks expanded inside the GEMM's LDS-fill path (gemm.hip; 128x128x64 tiles; any epilogue)
 hipError_t launch_gemm_q4(int dtype, int epi, const GemmArgs &a, hipStream_t stream);
 bool gemm_q4_supports(const GemmArgs &a);
 
@@ -110,9 +116,10 @@ struct Tuning {
     int attn_grid = 0;       // persistent attention: workgroups (0 = one per CU)
 };
 // Looks the device up (hipGetDevice when device < 0) and on first use of a device
-// sets the dynamic-LDS attribute of every kernel instantiation on it.  Thread-safe.  Returns nullptr if HIP fails.
+// sets the dynamic-LDS attribute of every kernel instantiation on it (tuning.cpp).  Thread-safe.  Returns nullptr if HIP fails.
 const Tuning *tuning_for_device(int device);
 
+// The GEMM dispatcher (gemm.hip): picks the kernel family for the shape
 hipError_t launch_gemm(const Tuning &t, int dtype, int epi, const GemmArgs &a, hipStream_t stream);
 // true when launch_gemm runs this EPI_BIAS_RESID GEMM on the ping-pong kernel in one launch with whole rows (N == N_pad == ldo,
 // N / 256 <= 4 column tiles), so that GemmArgs::ln may be set; the caller then launches launch_layernorm_fixup instead of launch_layernorm
@@ -121,7 +128,7 @@ bool gemm_ln_fusable(const Tuning &t, const GemmArgs &a);
 bool gemm_fix_capable(const Tuning &t, const GemmArgs &a);
 // persistent grid of that GEMM (for the sub-batch cost model): workgroups per XCD are a multiple of the column tiles
 int gemm_ln_grid(int n_cu, int M, int N);
-// normalises the row blocks a fused GEMM left behind (todo[rb] == epoch) from x; a few microseconds when there are none
+// normalises the row blocks a fused GEMM left behind (todo[rb] == epoch) from x (layernorm.hip); a few microseconds when there are none
 hipError_t launch_layernorm_fixup(int dtype, const float *x, const float *w, const float *b, void *y, int M, int D, float eps, const unsigned *todo, unsigned epoch, hipStream_t stream);
 int gemm_tile_m();   // M granularity the GEMM needs (buffer row padding)
 int gemm_tile_n();
@@ -132,21 +139,21 @@ int gemm_tile_n();
 // w_perm: the [n_pad][k_pad] operand-type kernel with its K axis permuted by patch_embed_permute_k (host side, at upload); pos [1 + patches][D],
 // cls [D], reg [n_reg][D] (nullptr when n_reg == 0).
 hipError_t launch_patch_embed(int dtype, const float *img, const void *w_perm, const float *bias, const float *pos, const float *cls, const float *reg, int n_reg,
-                              float *X, int n_img, int S, int P, int Cin, int D, int n_pad, int k_pad, hipStream_t stream, bool prepare = false);
+                              float *X, int n_img, int S, int P, int Cin, int D, int n_pad, int k_pad, hipStream_t stream);
 void patch_embed_permute_k(const uint16_t *w, uint16_t *w_perm, int N, int Cin, int P, int k_pad);
-// y[r][:] (dtype) = LN(x[r*ldx ...]) * w + b   (vit.cpp:808-812)
+// y[r][:] (dtype) = LN(x[r*ldx ...]) * w + b   (layernorm.hip; vit.cpp:808-812)
 // group > 1: input row r = x + (r / group) * gstride + (r % group) * ldx (the first `group` tokens of every image: ViTSTR head)
 hipError_t launch_layernorm(int dtype, const float *x, long ldx, const float *w, const float *b, void *y, long ldy, int M, int D, float eps, hipStream_t stream, int group = 1, long gstride = 0);
-// fused per-(image,head) attention  (vit.cpp:826-866)
+// fused per-(image,head) attention  (vit.cpp:826-866): the dispatcher over the attention families (attention.hip)
 hipError_t launch_attention(const Tuning &t, int dtype, const void *qkv, void *out, int n_img, int N, int D, int H, hipStream_t stream);
 // Streaming two-pass kernel (attention_stream.hip), head dim 64, any token count.  precise = false: the long-sequence kernel of both
 // operand types; precise = true (f16 only): the F16 parity mode's f32-grade products -- qkv is then the HI plane of the QKV GEMM's
-// EPI_BIAS_HILO output and the LO plane lies lo_off elements behind it.  n_img == 0: device bring-up (dynamic-LDS attribute).
+// EPI_BIAS_HILO output and the LO plane lies lo_off elements behind it.
 hipError_t launch_attention_stream(int dtype, bool precise, const void *qkv, void *out, int n_img, int N, int D, int H, long lo_off, hipStream_t stream);
 bool attention_stream_supports(int n_img, int N, int D, int H);
 // x[n] f32 -> hi[n] = round(x), lo[n] = round((x - hi) * 2048) in the operand type (what EPI_BIAS_HILO emits; parity-test entry point)
 hipError_t launch_split_hilo(int dtype, const float *x, void *hi, void *lo, size_t n, hipStream_t stream);
-// Attention of token 0 only (the last layer of a classifier needs nothing else, vit.cpp:910-911): out[b][D] (dtype) from qkv[n_img * N][3 D]
+// Attention of token 0 only (attention_cls.hip; the last layer of a classifier needs nothing else, vit.cpp:910-911): out[b][D] (dtype) from qkv[n_img * N][3 D]
 // (lo_off != 0: the parity mode's lo plane, F16 only); xc != nullptr: also xc[b][D] = x[b * N][D] (the class rows of the f32 residual stream)
 hipError_t launch_attention_cls(int dtype, const void *qkv, long lo_off, void *out, const float *x, float *xc, int n_img, int N, int D, int H, hipStream_t stream);
 bool attention_cls_supports(int N, int D, int H);  // head_dim 8, 16, 32, 64 or 128
@@ -181,13 +188,14 @@ bool layernorm_supports(int D);
 #define VITX_LN_WIDTHS(X)                                                                                                  \
     X(64, 1, 1) X(128, 2, 1) X(192, 1, 3) X(256, 4, 1) X(384, 2, 3) X(512, 4, 2) X(768, 4, 3) X(1024, 4, 4) X(1280, 4, 5) X(1536, 4, 6) \
     X(320, 1, 5) X(448, 1, 7) X(576, 1, 9) X(640, 2, 5) X(896, 2, 7) X(1152, 2, 9) X(1408, 2, 11) X(1664, 2, 13) X(2048, 4, 8)
-// class softmax with the reference's fp16 (or bf16) exp rounding (vit.cpp:931)
+// class softmax with the reference's fp16 (or bf16) exp rounding (softmax_topk.hip; vit.cpp:931)
 hipError_t launch_softmax(int dtype, const float *logits, float *probs, int rows, int cols, int ld, hipStream_t stream);
+// u8 HWC [n][ny][nx][3] -> f32 HWC [n][S][S][3], resized and normalised (image_preprocess.hip; bit for bit the host version in preprocess.cpp)
 hipError_t launch_preprocess(const void *u8, float *out, int n, int nx, int ny, int S, int bicubic, hipStream_t stream);
 // out[row][k] = {f32 probability, i32 class} of the k largest entries of probs[row][0..cols), descending, ties by the lower class index
-// (the sort of vit_predict, vit.cpp:1043-1057, on the device: the multi-GPU gather then moves 8 k bytes per row instead of 4 cols)
+// (softmax_topk.hip; the sort of vit_predict, vit.cpp:1043-1057, on the device: the multi-GPU gather then moves 8 k bytes per row instead of 4 cols)
 hipError_t launch_topk(const float *probs, int rows, int cols, int k, void *out_pairs, hipStream_t stream);
-// one workgroup that does nothing for `microseconds` of the 100 MHz wall clock (stream-concurrency probe of the execution context)
+// one workgroup that does nothing for `microseconds` of the 100 MHz wall clock (probe.hip; stream-concurrency probe of the execution context)
 hipError_t launch_spin(int microseconds, hipStream_t stream);
 // the same, writing its first and last wall-clock reading (100 MHz ticks) to stamps[0..1] (device memory)
 hipError_t launch_spin_stamp(int microseconds, long long *stamps, hipStream_t stream);
@@ -215,5 +223,30 @@ bool gemm_pp_supports(const GemmArgs &a);
 // per SIMD, 128 x 128 per wave.  EPI_BIAS, EPI_BIAS_GELU; same bits as the other families
 hipError_t launch_gemm_w4(int dtype, int epi, const GemmArgs &a, int n_cu, hipStream_t stream, int flags = 0, bool prepare = false, int waves = 8);
 bool gemm_w4_supports(const GemmArgs &a);
+bool attention_persist_supports(int n_img, int N, int D);      // attention_persist.hip: 193..224 tokens, the whole QKV tensor below 0xf0000000 bytes
+bool attention_generic_supports(int D, int H);                 // attention_generic.hip: head_dim any multiple of 8 up to 128
+
+// FN<_Float16>(args) for DT_F16, FN<__bf16>(args) for any other dtype: how a launcher that takes `int dtype` enters its per-type template.
+// VITX_BY_DTYPE2: FN has one more template argument X after the type.
+#define VITX_BY_DTYPE(dtype, FN, ...) ((dtype) == DT_F16 ? FN<_Float16>(__VA_ARGS__) : FN<__bf16>(__VA_ARGS__))
+#define VITX_BY_DTYPE2(dtype, FN, X, ...) ((dtype) == DT_F16 ? FN<_Float16, X>(__VA_ARGS__) : FN<__bf16, X>(__VA_ARGS__))
+
+// The rest is reached from inside the library only (launch_attention, tuning_for_device) and stays out of its dynamic symbol table.
+#pragma GCC visibility push(hidden)
+// The attention families launch_attention chooses among, head dim 64 unless said otherwise; each checks nothing launch_attention has checked.
+hipError_t launch_attention_single(int dtype, const void *qkv, void *out, int n_img, int N, int D, int H, hipStream_t stream);      // attention_single.hip: N per attention_single_pass_supports
+hipError_t launch_attention_flow(int dtype, const void *qkv, void *out, int n_img, int N, int D, int H, hipStream_t stream, int flags = 0);      // attention_flow.hip: any N
+hipError_t launch_attention_persist(int dtype, const void *qkv, void *out, int n_img, int N, int D, int H, int n_cu, hipStream_t stream, int flags = 0);      // attention_persist.hip
+hipError_t launch_attention_generic(int dtype, const void *qkv, void *out, int n_img, int N, int D, int H, hipStream_t stream);      // attention_generic.hip
+// Device bring-up: every kernel instantiation that needs more than 64 KiB of LDS gets its dynamic-LDS attribute on the current device, by the
+// file that holds the instantiation table.  tuning_for_device runs these once per device.
+hipError_t prepare_gemm(const Tuning &t);              // gemm.hip: ring, ping-pong and q4_0 GEMMs (laboratory build: gemm_w4 too)
+hipError_t prepare_patch_embed();                      // patch_embed.hip
+hipError_t prepare_attention();                        // attention.hip: the four below, each in its family's file
+hipError_t prepare_attention_single();
+hipError_t prepare_attention_flow();
+hipError_t prepare_attention_persist();
+hipError_t prepare_attention_stream();
+#pragma GCC visibility pop
 
 }  // namespace vitx

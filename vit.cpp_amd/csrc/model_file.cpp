@@ -268,7 +268,7 @@ int vitx_topk(const float *probs, int C, int k, int32_t *idx, float *p) {
     if (k > C) k = C;
     // descending by probability (vit.cpp:1053-1057); ties broken by lower class id for determinism.  NaN entries come last, by class id:
     // with them left to `>` and `==` the comparison is no strict weak order and std::partial_sort is undefined.  topk_kernel
-    // (kernels.hip) follows the same order.
+    // (softmax_topk.hip) follows the same order.
     std::vector<int32_t> order((size_t)C);
     for (int i = 0; i < C; ++i) order[i] = i;
     std::partial_sort(order.begin(), order.begin() + k, order.end(), [&](int32_t a, int32_t b) {

@@ -8,7 +8,7 @@
 //     the sum over k is the same set of products, grouped differently -- f32 summation noise against ggml's channel-major order), so
 //     16 consecutive k' are 64 contiguous bytes of one image row whenever P * Cin is a multiple of 16 (every patch-16 / patch-32 model, RGB
 //     or the one-channel ViTSTR input); other geometries (patch 8 or 14) take a per-element gather;
-//   * 128 x 128 x 64 tiles, 4 waves, the LDS image / fragment layout / products / epilogue of the v1 GEMM (kernels.hip): W by LDS-DMA, A by
+//   * 128 x 128 x 64 tiles, 4 waves, the LDS image / fragment layout / products / epilogue of the v1 GEMM (gemm.hip): W by LDS-DMA, A by
 //     registers -- each thread loads 2 x 16 floats of the next K-tile under the current K-tile's MFMAs, rounds them to the operand type
 //     exactly where ggml's im2col emits fp16, and writes two 16-byte slots of the swizzled image;
 //   * the epilogue (epilogue16.h, EPI_PATCH) adds bias and pos_embed[1 + patch], scatters to token row image * N + T + patch (T = 1 + R
@@ -168,13 +168,14 @@ void patch_embed_permute_k(const uint16_t *w, uint16_t *w_perm, int N, int Cin, 
     (void)K;
 }
 
+hipError_t prepare_patch_embed() {       // device bring-up
+    hipError_t e = hipFuncSetAttribute((const void *)patch_embed_kernel<_Float16>, hipFuncAttributeMaxDynamicSharedMemorySize, pe::LDS_BYTES);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute((const void *)patch_embed_kernel<__bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, pe::LDS_BYTES);
+}
+
 hipError_t launch_patch_embed(int dtype, const float *img, const void *w_perm, const float *bias, const float *pos, const float *cls, const float *reg, int n_reg,
-                              float *X, int n_img, int S, int P, int Cin, int D, int n_pad, int k_pad, hipStream_t stream, bool prepare) {
-    if (prepare) {
-        hipError_t e = hipFuncSetAttribute((const void *)patch_embed_kernel<_Float16>, hipFuncAttributeMaxDynamicSharedMemorySize, pe::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        return hipFuncSetAttribute((const void *)patch_embed_kernel<__bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, pe::LDS_BYTES);
-    }
+                              float *X, int n_img, int S, int P, int Cin, int D, int n_pad, int k_pad, hipStream_t stream) {
     const int gsz = S / P, tpi = gsz * gsz;
     if (n_img <= 0 || P <= 0 || S % P || n_pad % pe::BN || k_pad % pe::BK || k_pad < Cin * P * P || D % 4 || n_reg < 0 || (n_reg > 0 && !reg)) return hipErrorInvalidValue;
     GemmArgs g{};

@@ -12,6 +12,7 @@
 
 #include "../../include/vitx.h"
 #include "device_common.h"
+#include "kernels.h"
 #include "model_file.h"
 #include "mxfp8.h"
 
@@ -90,6 +91,29 @@ __global__ __launch_bounds__(512, 2) void mfma_probe_mx8_kernel(ProbeOut *out, i
 }
 
 }  // namespace
+
+// Stream probes of the execution context (launch_spin, launch_spin_stamp: kernels.h)
+__global__ void spin_kernel(long long ticks) {
+    const long long t0 = wall_clock64();
+    while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(16);
+}
+hipError_t launch_spin(int microseconds, hipStream_t stream) {
+    hipLaunchKernelGGL(spin_kernel, dim3(1), dim3(64), 0, stream, (long long)microseconds * 100);
+    return hipGetLastError();
+}
+// the same, leaving its own first and last reading of the 100 MHz wall clock in stamps[0..1]: a kernel whose duration the device itself
+// states, the yardstick for what a HIP-event bracket adds to a launch (vitx_profile_bracket_us)
+__global__ void spin_stamp_kernel(long long ticks, long long *stamps) {
+    const long long t0 = wall_clock64();
+    long long t1 = t0;
+    while (t1 - t0 < ticks) { __builtin_amdgcn_s_sleep(2); t1 = wall_clock64(); }
+    if (threadIdx.x == 0) { stamps[0] = t0; stamps[1] = t1; }
+}
+hipError_t launch_spin_stamp(int microseconds, long long *stamps, hipStream_t stream) {
+    hipLaunchKernelGGL(spin_stamp_kernel, dim3(1), dim3(64), 0, stream, (long long)microseconds * 100, stamps);
+    return hipGetLastError();
+}
+
 }  // namespace vitx
 
 using namespace vitx;

@@ -7,7 +7,7 @@
 //   * launch_dequant: one launch expands the (up to four) matrices of an encoder layer into an operand-type scratch that the
 //     wide-tile GEMMs then stream like any other weight matrix.  The scratch is per sub-batch stream and re-used by every
 //     layer (ViT-B: 14 MB, resident in the 256 MB Infinity Cache), so HBM only ever holds and serves the blocks.
-//   * the small-batch GEMM expands q4_0 blocks inside its own LDS-fill path instead (gemm_nt_kernel<.., Q4 = true> in kernels.hip).
+//   * the small-batch GEMM expands q4_0 blocks inside its own LDS-fill path instead (gemm_nt_kernel<.., Q4 = true> in gemm.hip).
 // Values are exactly HostTensor::decode_f32 (model_file.cpp; ggml's dequantize_row_*), rounded ONCE to the operand type with
 // round-to-nearest-even -- bit-identical to expanding on the host at upload, which the tests assert.
 #include <stdint.h>
@@ -169,7 +169,7 @@ hipError_t launch_dequant(int dtype, int qtype, const DequantJob *jobs, int njob
         if (total > 0x1fffffffL) return hipErrorInvalidValue;      // (x 4 lanes per block in the q4_0 kernel's thread index)
     }
     for (int j = njobs; j <= 4; ++j) a.first[j] = (int)total;
-    return dtype == DT_F16 ? launch_dequant_t<_Float16>(qtype, a, stream) : launch_dequant_t<__bf16>(qtype, a, stream);
+    return VITX_BY_DTYPE(dtype, launch_dequant_t, qtype, a, stream);
 }
 
 }  // namespace vitx
