@@ -67,7 +67,8 @@ enum vitx_dtype { VITX_F16 = 0, VITX_BF16 = 1, VITX_MXFP8 = 2 };
 /* Interpolation of vit_image_preprocess (vit_hparams::interpolation, vit.h:30). */
 enum vitx_interp { VITX_BICUBIC = 0, VITX_BILINEAR = 1 };
 
-/* Mirrors vit_hparams (vit.h:20-37); eps is not stored in the file (always 1e-6). */
+/* Mirrors vit_hparams (vit.h:20-37); eps is the LayerNorm epsilon of every norm of the model: 1e-6 unless the file carries an `arch` tensor
+ * ("activation, epsilon and pre-norm" below). */
 typedef struct vitx_hparams {
     int32_t hidden_size;
     int32_t num_hidden_layers;
@@ -126,6 +127,28 @@ int vitx_model_seq_len(const vitx_model *m);
 enum vitx_head_pool { VITX_POOL_CLS = 0, VITX_POOL_CLS_MEAN = 1 };
 int vitx_model_num_registers(const vitx_model *m);   /* R; 0 without reg_token (and for NULL) */
 int vitx_model_head_pool(const vitx_model *m);       /* enum vitx_head_pool, from head.weight's shape */
+/* ---- activation, epsilon and pre-norm (HuggingFace ViT, timm, DINOv2, CLIP) ----
+ * Two more optional extensions of the file, recognised by tensor name and shape; magic and the seven hparams are unchanged:
+ *   `arch`         f32 [4] = {activation, eps, 0, 0}.  activation: enum vitx_activation, the function between mlp.fc1 and mlp.fc2
+ *                  (0 ggml's tanh-GELU, 1 the erf GELU x Phi(x) of nn.GELU, 2 QuickGELU x sigmoid(1.702 x)); eps: the epsilon of EVERY LayerNorm of
+ *                  the model, a finite f32 > 0, reported as vitx_hparams::eps.  Slots 2 and 3 are reserved and must be 0.  Without `arch` a file
+ *                  means {0, 1e-6}: the reference's arithmetic, which is what such files have always run as.  The converter writes it first.
+ *   `pre_norm.weight`, `pre_norm.bias`   f32 [D], both or neither: a LayerNorm (the model's eps) of every token row -- class and register rows
+ *                  included -- after the patch embedding and before layer 0: CLIP's pre_layrnorm.  Written directly after pos_embed.
+ * Any other type, shape or activation code, an eps that is not finite and positive, a non-zero reserved slot, a duplicate, or one pre_norm tensor
+ * without the other: VITX_ERR_FORMAT.  The loader takes them anywhere in the file; vitx_quantize_file and vitx_model_resize_file copy them
+ * through byte for byte.  The reference's vit_model_load cannot read a file with either (unknown tensor, vit.cpp:618-622); files without them load
+ * and run exactly as before, bit for bit.
+ * Rounding points of the activation are those of tanh-GELU for all three: VITX_F16 rounds the argument and the result to fp16 (ggml's fp16
+ * tables: ggml_gelu, ggml_gelu_quick), VITX_BF16 rounds only the stored value.
+ * With a pre-norm, stage 0 of the residual-stream trace is the stream that ENTERS layer 0, i.e. after the pre-norm.
+ * A CLIP file's head is the bias-free visual projection: its logits are CLIP's image_embeds (L2-normalise them on the host), its
+ * "probabilities" mean nothing.
+ * ViTSTR (one-channel) files with a pre-norm or an activation other than tanh-GELU, and VITX_MXFP8 contexts of a file whose activation is not
+ * tanh-GELU, are VITX_ERR_UNSUPPORTED at context creation (eps and the pre-norm do work under VITX_MXFP8). */
+enum vitx_activation { VITX_ACT_GELU_TANH = 0, VITX_ACT_GELU_ERF = 1, VITX_ACT_QUICK_GELU = 2 };
+int vitx_model_activation(const vitx_model *m);      /* enum vitx_activation; 0 without `arch` (and for NULL) */
+int vitx_model_has_pre_norm(const vitx_model *m);    /* 1 when the file carries pre_norm.weight / pre_norm.bias */
 int vitx_model_num_tensors(const vitx_model *m);
 /* Name, file type code (0 f32,1 f16,2 q4_0,3 q4_1,6 q5_0,7 q5_1,8 q8_0), ggml-order dims. */
 int vitx_model_tensor_info(const vitx_model *m, int index, const char **name, int32_t *type, int64_t ne[4], size_t *nbytes);
@@ -332,9 +355,15 @@ int vitx_profile_bracket_us(vitx_ctx *c, double *bracket_us);
 /* ---- single-kernel entry points (device pointers; used by the parity tests) - */
 /* y[M][N] (dtype) = LayerNorm(x[M][D] f32) * w + b, eps inside the sqrt (vit.cpp:808-812). */
 int vitx_op_layernorm(int dtype, const void *d_x, const void *d_w, const void *d_b, void *d_y, int M, int D, float eps, void *stream);
+/* The same LayerNorm with the result left in f32, not rounded: y[M][D] f32 = ((x - mean) * rstd) * w + b, the value vitx_op_layernorm rounds (same
+ * statistics, same operation order, every hidden size it covers).  d_y == d_x (in place) is allowed.  This is the pre-norm launch of a file
+ * with pre_norm.*.  Only enqueues on `stream`; argument errors as vitx_op_layernorm. */
+int vitx_op_layernorm_f32(const void *d_x, const void *d_w, const void *d_b, void *d_y, int M, int D, float eps, void *stream);
 /* C = A[M][K] . W[N][K]^T with a fused epilogue; A, W in `dtype`.
  *   epi 0: out dtype  = acc + bias                  (vit.cpp:820-821)
  *   epi 1: out dtype  = gelu_tanh(acc + bias)       (vit.cpp:889-893)
+ *   epi 6: out dtype  = gelu_erf(acc + bias)        (x Phi(x): VITX_ACT_GELU_ERF)   } the rounding points of epi 1: F16 rounds the argument
+ *   epi 7: out dtype  = quick_gelu(acc + bias)      (x sigmoid(1.702 x): VITX_ACT_QUICK_GELU) } and the result, BF16 the result only
  *   epi 2: out f32    = (acc + bias) + out  in place (vit.cpp:868-873, 896-900)
  *   epi 3: out f32    = acc + bias                  (vit.cpp:927-928)
  *   epi 5: out dtype  = TWO planes of acc + bias: hi = round(v) at out[m][n], lo = round((v - hi) * 2048) at out[M * N + m * N + n]
@@ -366,7 +395,7 @@ int vitx_op_gemm_ln(int dtype, const void *d_a, const void *d_w, const void *d_b
  *                     d_scales = f16 block scales [N][K/32] (d_scales is ignored for the other types); rows N..n_pad are zeros.
  *                     Values are the reference's dequantize_row_* results rounded once (nearest-even) to dtype.
  *   vitx_op_gemm_q4 : C = A[M][K] . dequant(W)^T with the q4_0 blocks expanded in the GEMM's LDS-fill path; d_qs / d_scales as
- *                     above but with N rounded up to 128 rows (zero scales in the pad rows), epi 0..3 as vitx_op_gemm. */
+ *                     above but with N rounded up to 128 rows (zero scales in the pad rows), epi 0..3, 6 and 7 as vitx_op_gemm. */
 int vitx_op_dequant(int dtype, int qtype, const void *d_blocks, const void *d_scales, void *d_out, int N, int n_pad, int K, void *stream);
 /* The same for njobs = 1..4 matrices of one block type in ONE launch, as the forward expands the qkv, proj, fc1 and fc2 matrices of a
  * layer (launch_dequant, quant.hip): job j takes d_blocks[j], d_scales[j] (d_scales may be NULL for every type but q4_0), d_out[j],

@@ -21,6 +21,9 @@ F16, BF16, MXFP8 = 0, 1, 2      # MXFP8: qkv, fc1 and fc2 on block-scaled e4m3 o
 LN_TEST_KEY = 0x7e570000        # vitx_ctx_options::ln_test is honoured only as LN_TEST_KEY | mode
 BICUBIC, BILINEAR = 0, 1
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_BIAS_F32, EPI_PATCH, EPI_BIAS_HILO = 0, 1, 2, 3, 4, 5
+EPI_BIAS_GELU_ERF, EPI_BIAS_QGELU = 6, 7      # fc1 epilogues of the other two activations (same rounding points as EPI_BIAS_GELU)
+ACT_GELU_TANH, ACT_GELU_ERF, ACT_QUICK_GELU = 0, 1, 2      # vitx_model_activation (the file's `arch` tensor; tanh-GELU without it)
+ERR_IO, ERR_FORMAT, ERR_ARG, ERR_HIP, ERR_UNSUPPORTED, ERR_NOMEM = 1, 2, 3, 4, 5, 6      # status codes (VitxError.code)
 GEMM_AUTO, GEMM_PP, GEMM_AUTO_SPLIT = 0, 1, 2          # vitx_op_gemm_ex `kernel` (or a ring configuration: 945, 445, 245, 122)
 ATTN_AUTO, ATTN_SINGLE, ATTN_FLOW, ATTN_PERSIST, ATTN_STREAM = 0, 1, 3, 4, 5   # vitx_op_attention_ex `kernel`
 ATTN_ROLLOUT = 1                # vitx_attn_enable flag
@@ -41,6 +44,7 @@ EXPORTS = [
     "vitx_ctx_img_size", "vitx_ctx_tokens", "vitx_pos_embed_resample", "vitx_op_pos_embed_resample", "vitx_model_resize_file",
     "vitx_op_topk", "vitx_op_dequant_jobs",
     "vitx_model_num_registers", "vitx_model_head_pool", "vitx_ctx_registers", "vitx_op_features_ex", "vitx_op_patch_embed",
+    "vitx_model_activation", "vitx_model_has_pre_norm", "vitx_op_layernorm_f32",
 ]
 
 
@@ -60,7 +64,7 @@ class ProfEntry(C.Structure):
 
 
 class VitxError(RuntimeError):
-    pass
+    code = 0        # the vitx_status behind the error (ERR_*), where check() raised it
 
 
 def build(force: bool = False) -> str:
@@ -173,6 +177,9 @@ def lib():
             L.vitx_model_num_registers.argtypes = [vp]; L.vitx_model_head_pool.argtypes = [vp]; L.vitx_ctx_registers.argtypes = [vp]
             L.vitx_op_features_ex.argtypes = [vp, C.c_long, C.c_long, vp, vp, vp, vp, vp, C.c_long, ip, ip, ip, ip, C.c_float, ip, vp, ip, vp]
             L.vitx_op_patch_embed.argtypes = [ip, vp, vp, vp, vp, vp, vp, ip, vp, ip, ip, ip, ip, ip, vp]
+        if hasattr(L, "vitx_model_activation"):
+            L.vitx_model_activation.argtypes = [vp]; L.vitx_model_has_pre_norm.argtypes = [vp]
+            L.vitx_op_layernorm_f32.argtypes = [vp, vp, vp, vp, ip, ip, C.c_float, vp]
         _lib = L
     return _lib
 
@@ -180,7 +187,9 @@ def lib():
 def check(rc: int, what: str = "") -> None:
     if rc != 0:
         L = lib()
-        raise VitxError(f"{what}: {L.vitx_status_str(rc).decode()} ({rc}): {L.vitx_last_error().decode()}")
+        e = VitxError(f"{what}: {L.vitx_status_str(rc).decode()} ({rc}): {L.vitx_last_error().decode()}")
+        e.code = rc
+        raise e
 
 
 class Model:
@@ -213,6 +222,12 @@ class Model:
     @property
     def head_pool(self) -> int:                                                     # POOL_CLS, or POOL_CLS_MEAN for a [C][2 D] head
         return lib().vitx_model_head_pool(self._h) if hasattr(lib(), "vitx_model_head_pool") else 0
+    @property
+    def activation(self) -> int:                                                    # ACT_GELU_TANH / ACT_GELU_ERF / ACT_QUICK_GELU (the file's `arch`)
+        return lib().vitx_model_activation(self._h) if hasattr(lib(), "vitx_model_activation") else 0
+    @property
+    def has_pre_norm(self) -> bool:                                                 # pre_norm.weight / pre_norm.bias: CLIP's pre_layrnorm
+        return bool(lib().vitx_model_has_pre_norm(self._h)) if hasattr(lib(), "vitx_model_has_pre_norm") else False
     @property
     def num_classes(self) -> int: return self.hparams.num_classes
     @property
@@ -636,6 +651,11 @@ def mxfp8_quantize(x: np.ndarray, k_pad: Optional[int] = None) -> Tuple[np.ndarr
     check(lib().vitx_mxfp8_quantize(x.ctypes.data_as(C.POINTER(C.c_float)), rows, K, k_pad, q.ctypes.data_as(C.POINTER(C.c_uint8)),
                                     s.ctypes.data_as(C.POINTER(C.c_uint8))), "vitx_mxfp8_quantize")
     return q, s
+
+
+def op_layernorm_f32(d_x: int, d_w: int, d_b: int, d_y: int, M: int, D: int, eps: float = 1e-6, stream: int = 0) -> None:
+    """vitx_op_layernorm_f32: y [M][D] f32 = the LayerNorm of x [M][D] f32 before any rounding (d_y == d_x: in place).  Only enqueues."""
+    check(lib().vitx_op_layernorm_f32(d_x, d_w, d_b, d_y, M, D, eps, stream or None), "vitx_op_layernorm_f32")
 
 
 def op_quantize_mxfp8(d_x: int, rows: int, K: int, k_pad: int, d_q: int, d_scales: int, stream: int = 0) -> None:

@@ -1,11 +1,22 @@
-"""Converter: a HuggingFace `transformers` ViTForImageClassification or DINOv2 model -> the reference's legacy-ggml ".gguf" file.
+"""Converter: a HuggingFace `transformers` ViTForImageClassification, DINOv2 or CLIP vision model -> the reference's legacy-ggml ".gguf" file.
 
 Counterpart of the reference's /root/reference/convert-pth-to-ggml.py (which needs `timm`): same output layout
 (writer rules convert-pth-to-ggml.py:105-158 live in ggml_file.write_model), different source naming -- HF splits
 the fused qkv projection into query/key/value (concatenated here in timm's q,k,v order, vit.cpp:826-834) and calls
 the sub-modules `vit.encoder.layer.N.*` (transformers < 5) or `vit.layers.N.*` (>= 5).  Offline tool, not on the
-compute path.  The model must use tanh-GELU or exact GELU weights trained for it: the forward path implements
-ggml_gelu (tanh form, vit.cpp:889-893) only.
+compute path.
+
+The model's own MLP activation and LayerNorm epsilon are read from its config (`hidden_act`: gelu -> erf-GELU, gelu_pytorch_tanh / gelu_new ->
+tanh-GELU, quick_gelu -> QuickGELU, anything else is refused by name; `layer_norm_eps`) and written as the file's `arch` tensor, f32 [4] =
+{activation, eps, 0, 0}, the first tensor of the file (include/vitx.h "activation, epsilon and pre-norm").  `arch` is written ONLY when
+(activation, eps) differs from (tanh-GELU, 1e-6), the reference's arithmetic: such a conversion is byte for byte what it always was and stays
+readable by the reference.  Every other model -- the HuggingFace ViT default is erf-GELU with 1e-12, timm and DINOv2 use erf-GELU -- used to be
+written without its settings and run with tanh-GELU and 1e-6; it now carries them, which is the one intended change of this converter's output.
+
+CLIP (CLIPVisionModelWithProjection; CLIPModel: its vision tower and visual_projection; CLIPVisionModel with --no-head): class_embedding ->
+cls_token, position_embedding -> pos_embed, the bias-free patch convolution gets a zero bias, pre_layrnorm -> `pre_norm.*` (directly after
+pos_embed), q/k/v_proj are fused, post_layernorm -> norm, and the bias-free visual_projection [E][D] becomes head.weight with a zero head.bias:
+the file has E "classes" labelled dim_0 .. dim_{E-1}, its logits are CLIP's image_embeds and its probabilities mean nothing.
 
 A timm checkpoint needs no `timm` either: its state_dict already carries the names the file format uses (the reference's converter
 writes `timm_model.state_dict()` verbatim, convert-pth-to-ggml.py:121-133), so `--timm-state-dict model.pth` loads the tensors with
@@ -20,7 +31,10 @@ At another input size transformers 5.x resamples the DINOv2-with-registers posit
 reproduces it (plain Dinov2 and ViT: `bicubic`).
 
     python -m ... convert.py <hf_model_dir_or_name> <out.gguf> [--ftype 1] [--no-head]
-    python -m ... convert.py --timm-state-dict <checkpoint.pth> <out.gguf> [--ftype 1] [--heads H] [--labels labels.json]
+    python -m ... convert.py --timm-state-dict <checkpoint.pth> <out.gguf> [--ftype 1] [--heads H] [--labels labels.json] [--act erf] [--eps 1e-6]
+
+A timm state dict carries no config, so --act {tanh,erf,quick} and --eps state its settings; without them the file is the reference's (tanh-GELU,
+1e-6, no `arch`), as before.  timm's VisionTransformer uses nn.GELU: convert its checkpoints with --act erf.
 """
 from __future__ import annotations
 
@@ -29,6 +43,32 @@ from typing import Dict
 import numpy as np
 
 from .ggml_file import HParams, write_model
+
+
+ACT_TANH, ACT_ERF, ACT_QUICK = 0, 1, 2          # enum vitx_activation
+_HF_ACTS = {"gelu": ACT_ERF, "gelu_pytorch_tanh": ACT_TANH, "gelu_new": ACT_TANH, "quick_gelu": ACT_QUICK}
+_ACT_NAMES = {"tanh": ACT_TANH, "erf": ACT_ERF, "quick": ACT_QUICK}
+
+
+def hf_activation(cfg) -> int:
+    """enum vitx_activation of a HuggingFace config's hidden_act; an activation the forward path does not evaluate is refused by name."""
+    act = getattr(cfg, "hidden_act", "gelu")
+    if not isinstance(act, str) or act not in _HF_ACTS:
+        raise ValueError(f"hidden_act {act!r} is not supported (the forward path evaluates {sorted(_HF_ACTS)})")
+    return _HF_ACTS[act]
+
+
+def with_arch(tensors: Dict[str, np.ndarray], activation: int, eps: float) -> Dict[str, np.ndarray]:
+    """`tensors` with the `arch` tensor [activation, eps, 0, 0] in front -- only when it says something else than (tanh-GELU, 1e-6), so that a
+    file of the reference's arithmetic stays byte for byte what it was."""
+    eps32 = np.float32(eps)
+    if activation not in (ACT_TANH, ACT_ERF, ACT_QUICK) or not np.isfinite(eps32) or not eps32 > 0:
+        raise ValueError(f"activation {activation} / eps {eps}: the activation is 0, 1 or 2, eps a finite float32 > 0")
+    if activation == ACT_TANH and eps32 == np.float32(1e-6):
+        return tensors
+    out = {"arch": np.array([activation, eps32, 0, 0], np.float32)}
+    out.update(tensors)
+    return out
 
 
 def state_dict_to_timm(sd: Dict[str, np.ndarray], num_layers: int) -> Dict[str, np.ndarray]:
@@ -110,19 +150,72 @@ def dinov2_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, no_head: bool = Fa
     return {k: np.ascontiguousarray(np.asarray(v, np.float32)) for k, v in out.items()}
 
 
+def clip_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, no_head: bool = False) -> Dict[str, np.ndarray]:
+    """Rename / fuse an HF CLIPVisionModelWithProjection / CLIPModel / CLIPVisionModel state dict (numpy arrays) into the file's names and order."""
+    pre = next((p for p in ("vision_model.", "") if p + "embeddings.class_embedding" in sd), None)
+    if pre is None:
+        raise ValueError("not a CLIP vision state dict: embeddings.class_embedding is missing")
+    D = int(np.shape(sd[pre + "embeddings.class_embedding"])[-1])
+    if getattr(cfg, "intermediate_size", 4 * D) != 4 * D:
+        raise ValueError(f"intermediate_size {cfg.intermediate_size}: the file format holds a 4 x hidden MLP")
+    if pre + "embeddings.patch_embedding.bias" in sd:
+        raise ValueError("patch_embedding.bias: not a CLIP vision tower (its patch convolution has no bias)")
+    out: Dict[str, np.ndarray] = {}
+    out["cls_token"] = np.reshape(sd[pre + "embeddings.class_embedding"], (1, 1, D))
+    out["pos_embed"] = np.reshape(sd[pre + "embeddings.position_embedding.weight"], (1, -1, D))
+    out["pre_norm.weight"] = sd[pre + "pre_layrnorm.weight"]; out["pre_norm.bias"] = sd[pre + "pre_layrnorm.bias"]
+    out["patch_embed.proj.weight"] = sd[pre + "embeddings.patch_embedding.weight"]
+    out["patch_embed.proj.bias"] = np.zeros((D,), np.float32)
+    for i in range(cfg.num_hidden_layers):
+        q, p = f"{pre}encoder.layers.{i}.", f"blocks.{i}."
+        qkv = [q + "self_attn." + n for n in ("q_proj", "k_proj", "v_proj")]
+        out[p + "norm1.weight"] = sd[q + "layer_norm1.weight"]; out[p + "norm1.bias"] = sd[q + "layer_norm1.bias"]
+        out[p + "attn.qkv.weight"] = np.concatenate([sd[n + ".weight"] for n in qkv], 0)
+        out[p + "attn.qkv.bias"] = np.concatenate([sd[n + ".bias"] for n in qkv], 0)
+        out[p + "attn.proj.weight"] = sd[q + "self_attn.out_proj.weight"]; out[p + "attn.proj.bias"] = sd[q + "self_attn.out_proj.bias"]
+        out[p + "norm2.weight"] = sd[q + "layer_norm2.weight"]; out[p + "norm2.bias"] = sd[q + "layer_norm2.bias"]
+        out[p + "mlp.fc1.weight"] = sd[q + "mlp.fc1.weight"]; out[p + "mlp.fc1.bias"] = sd[q + "mlp.fc1.bias"]
+        out[p + "mlp.fc2.weight"] = sd[q + "mlp.fc2.weight"]; out[p + "mlp.fc2.bias"] = sd[q + "mlp.fc2.bias"]
+    out["norm.weight"] = sd[pre + "post_layernorm.weight"]; out["norm.bias"] = sd[pre + "post_layernorm.bias"]
+    if no_head:          # a tower without projection: a one-class head of zeros keeps the file well-formed; embeddings are read through vitx_feat_*
+        out["head.weight"] = np.zeros((1, D), np.float32); out["head.bias"] = np.zeros((1,), np.float32)
+    else:
+        if "visual_projection.weight" not in sd:
+            raise ValueError("the model has no visual_projection: convert a CLIPVisionModel with no_head=True (--no-head)")
+        out["head.weight"] = sd["visual_projection.weight"]
+        out["head.bias"] = np.zeros((int(np.shape(out["head.weight"])[0]),), np.float32)
+    return {k: np.ascontiguousarray(np.asarray(v, np.float32)) for k, v in out.items()}
+
+
 def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_head: bool = False) -> HParams:
-    """model: transformers.ViTForImageClassification, Dinov2ForImageClassification or Dinov2WithRegistersForImageClassification (eval);
-    with no_head=True a Dinov2Model / Dinov2WithRegistersModel backbone.  Writes `path`; returns the hparams written.
+    """model: transformers.ViTForImageClassification, Dinov2ForImageClassification, Dinov2WithRegistersForImageClassification,
+    CLIPVisionModelWithProjection or CLIPModel (eval); with no_head=True a Dinov2Model / Dinov2WithRegistersModel backbone or a CLIPVisionModel.
+    The activation and the LayerNorm epsilon are the config's (with_arch).  Writes `path`; returns the hparams written.
     vitstr=True: the model is a ViTSTR scene-text recogniser (/root/reference/extensions/vitstr.cpp/convert-pth-to-ggml.py: a ViT with ONE
     input channel whose classifier is applied to the first 25 tokens); the file then carries the character set as labels, and the
     one-channel patch kernel is what makes vit_model_load / vitx_model_load treat it as a ViTSTR model (vitstr.cpp:482)."""
     cfg = model.config
+    if getattr(cfg, "model_type", "") == "clip":
+        cfg = cfg.vision_config
     if vitstr and getattr(cfg, "num_channels", 3) != 1:
         raise ValueError("a ViTSTR model takes one (grey) input channel")
     hd = cfg.hidden_size // cfg.num_attention_heads
     if cfg.hidden_size % cfg.num_attention_heads or hd % 8 or not 8 <= hd <= 128:
         raise ValueError(f"head_dim {hd}: the forward path takes multiples of 8 up to 128 (64 runs the tuned attention kernels)")
     sd = {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
+    act, eps = hf_activation(cfg), float(getattr(cfg, "layer_norm_eps", 1e-6))
+    if getattr(cfg, "model_type", "") == "clip_vision_model":
+        if vitstr:
+            raise ValueError("a CLIP model is not a ViTSTR model")
+        tensors = clip_state_dict_to_timm(sd, cfg, no_head=no_head)
+        g = int(round((tensors["pos_embed"].shape[1] - 1) ** 0.5))
+        if g * g + 1 != tensors["pos_embed"].shape[1]:
+            raise ValueError(f"position_embedding {tensors['pos_embed'].shape}: not 1 + a square grid")
+        E = int(tensors["head.weight"].shape[0])
+        hp = HParams(cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, E, cfg.patch_size, g * cfg.patch_size, ftype)
+        id2label = {0: "(no head)"} if no_head else {i: f"dim_{i}" for i in range(E)}
+        write_model(path, hp, with_arch(tensors, act, eps), id2label=id2label, ftype=ftype)
+        return hp
     if getattr(cfg, "model_type", "") in ("dinov2", "dinov2_with_registers"):
         if vitstr:
             raise ValueError("a DINOv2 model is not a ViTSTR model")
@@ -132,10 +225,10 @@ def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_
             raise ValueError(f"position_embeddings {tensors['pos_embed'].shape}: not 1 + a square grid")
         hp = HParams(cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, int(tensors["head.weight"].shape[0]), cfg.patch_size, g * cfg.patch_size, ftype)
         id2label = {0: "(no head)"} if no_head else ({int(k): str(v) for k, v in (getattr(cfg, "id2label", None) or {}).items()} or None)
-        write_model(path, hp, tensors, id2label=id2label, ftype=ftype)
+        write_model(path, hp, with_arch(tensors, act, eps), id2label=id2label, ftype=ftype)
         return hp
     if no_head:
-        raise ValueError("no_head converts a DINOv2 backbone (Dinov2Model, Dinov2WithRegistersModel)")
+        raise ValueError("no_head converts a DINOv2 backbone (Dinov2Model, Dinov2WithRegistersModel) or a CLIPVisionModel")
     hp = HParams(cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, cfg.num_labels, cfg.patch_size, cfg.image_size, ftype)
     tensors = state_dict_to_timm(sd, cfg.num_hidden_layers)
     id2label = {int(k): str(v) for k, v in (getattr(cfg, "id2label", None) or {}).items()} or None
@@ -144,7 +237,7 @@ def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_
         if cfg.num_labels != len(VITSTR_LABELS):
             raise ValueError(f"ViTSTR's character set has {len(VITSTR_LABELS)} classes ([GO], [s], 94 printable characters), the model has {cfg.num_labels}")
         id2label = dict(VITSTR_LABELS)
-    write_model(path, hp, tensors, id2label=id2label, ftype=ftype)
+    write_model(path, hp, with_arch(tensors, act, eps), id2label=id2label, ftype=ftype)
     return hp
 
 
@@ -152,7 +245,7 @@ _TIMM_UNSUPPORTED = {"fc_norm.": "fc_norm", "dist_token": "a distillation token"
                      "attn_pool.": "attention pooling"}
 
 
-def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2label=None) -> HParams:
+def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2label=None, act: str = "tanh", eps: float = 1e-6) -> HParams:
     """sd: a timm VisionTransformer state_dict (name -> array / tensor), e.g. torch.load("vit_base_patch16_224.pth").  Mirrors
     /root/reference/convert-pth-to-ggml.py:96-158 without importing timm: hidden size, depth, classes, patch and image size come from the
     tensor shapes (the reference reads them off the timm module), `norm_pre.*` is skipped exactly as there (:117-120), the ViTSTR
@@ -160,7 +253,12 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
     by their one-channel patch kernel.  DINOv2-class checkpoints are taken: `blocks.N.ls1.gamma` / `ls2.gamma` (LayerScale) are folded into
     attn.proj / mlp.fc2 in f32, `reg_token` becomes the file's reg_token, and a `pos_embed` of g^2 rows (timm's no_embed_class layout of the
     reg4 DINOv2 models: the class token gets no position term there) gets a zero row in front, which is exact.  Models with other tensors
-    the file has no slot for (fc_norm, distillation tokens, qk-norm, attention pooling) are refused here, by name."""
+    the file has no slot for (fc_norm, distillation tokens, qk-norm, attention pooling) are refused here, by name.
+    A state dict carries no config: `act` ("tanh", "erf", "quick") and `eps` state the model's activation and LayerNorm epsilon.  The default
+    (tanh, 1e-6) writes the reference's file, without `arch`, as this function always has; a checkpoint of timm's VisionTransformer was trained
+    with nn.GELU and wants act="erf" (eps 1e-6 is timm's too)."""
+    if act not in _ACT_NAMES:
+        raise ValueError(f"act {act!r}: one of {sorted(_ACT_NAMES)}")
     sd = {k: v for k, v in (sd.get("model", sd) if isinstance(sd, dict) and "model" in sd and not hasattr(sd["model"], "shape") else sd).items()}
     t: Dict[str, np.ndarray] = {}
     for k, v in sd.items():
@@ -217,7 +315,7 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
     expected = 4 + 12 * L + 4 + (1 if "reg_token" in t else 0)
     if len(t) != expected:
         raise ValueError(f"{len(t)} tensors after filtering, the file format holds exactly {expected} for {L} layers (vit.cpp:512-574)")
-    write_model(path, hp, t, id2label=id2label, ftype=ftype)
+    write_model(path, hp, with_arch(t, _ACT_NAMES[act], eps), id2label=id2label, ftype=ftype)
     return hp
 
 
@@ -230,6 +328,9 @@ def main(argv=None) -> int:
                                                            "labelled '(no head)'; read the embeddings with --embed / vitx_feat_*")
     ap.add_argument("--timm-state-dict", action="store_true", help="`model` is a torch-saved timm VisionTransformer state_dict (.pth); no timm import needed")
     ap.add_argument("--heads", type=int, default=0, help="attention heads of a timm checkpoint (inferred only for the widths of released timm ViTs; required otherwise)")
+    ap.add_argument("--act", default="tanh", choices=sorted(_ACT_NAMES), help="MLP activation of a timm checkpoint (a state dict carries no config): tanh = ggml's GELU, the "
+                                                                                  "reference's (default); erf = nn.GELU, what timm's VisionTransformer uses; quick = QuickGELU")
+    ap.add_argument("--eps", type=float, default=1e-6, help="LayerNorm epsilon of a timm checkpoint (default 1e-6, timm's)")
     ap.add_argument("--labels", default=None, help="JSON file {class id: label} for a timm checkpoint (default: none are written)")
     ap.add_argument("--img-size", type=int, default=0, metavar="N",
                     help="write the file at N x N instead of the checkpoint's size: pos_embed is resampled (vitx_model_resize_file), nothing else changes")
@@ -257,12 +358,15 @@ def main(argv=None) -> int:
         import torch
         sd = torch.load(a.model, map_location="cpu", weights_only=True)
         labels = {int(k): str(v) for k, v in json.load(open(a.labels)).items()} if a.labels else None
-        hp = resized(convert_timm_state_dict(sd, a.out, a.ftype, heads=a.heads, id2label=labels))
+        hp = resized(convert_timm_state_dict(sd, a.out, a.ftype, heads=a.heads, id2label=labels, act=a.act, eps=a.eps))
         print(f"wrote {a.out}: hidden {hp.hidden_size}, layers {hp.num_hidden_layers}, heads {hp.num_attention_heads}, classes {hp.num_classes}, patch {hp.patch_size}, img {hp.img_size}, ftype {a.ftype}")
         return 0
     import transformers
-    if transformers.AutoConfig.from_pretrained(a.model).model_type in ("dinov2", "dinov2_with_registers"):
+    model_type = transformers.AutoConfig.from_pretrained(a.model).model_type
+    if model_type in ("dinov2", "dinov2_with_registers"):
         m = (transformers.AutoModel if a.no_head else transformers.AutoModelForImageClassification).from_pretrained(a.model).eval()
+    elif model_type in ("clip", "clip_vision_model"):
+        m = (transformers.CLIPVisionModel if a.no_head else transformers.CLIPVisionModelWithProjection).from_pretrained(a.model).eval()
     else:
         m = transformers.ViTForImageClassification.from_pretrained(a.model).eval()
     hp = resized(convert_hf_model(m, a.out, a.ftype, vitstr=a.vitstr, no_head=a.no_head))

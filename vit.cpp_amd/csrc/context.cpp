@@ -119,6 +119,8 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
     const int img_size = opt.img_size > 0 ? opt.img_size : m->hp.img_size;
     if (m->in_chans == 1 && (m->num_registers || m->head_pool != VITX_POOL_CLS)) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes neither register tokens nor the pooled head"); return VITX_ERR_UNSUPPORTED; }
     if (dtype == VITX_MXFP8 && (m->num_registers || m->head_pool != VITX_POOL_CLS)) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts do not take models with register tokens or the pooled head"); return VITX_ERR_UNSUPPORTED; }
+    if (m->in_chans == 1 && (m->has_pre_norm || m->activation != VITX_ACT_GELU_TANH)) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes neither a pre-norm nor an activation other than tanh-GELU"); return VITX_ERR_UNSUPPORTED; }
+    if (dtype == VITX_MXFP8 && m->activation != VITX_ACT_GELU_TANH) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts evaluate tanh-GELU only (this model's activation: %d)", m->activation); return VITX_ERR_UNSUPPORTED; }
     if (m->in_chans == 1 && img_size != m->hp.img_size) { set_error("vitx_ctx_create_ex: a ViTSTR context stays at the file's img_size (%d)", m->hp.img_size); return VITX_ERR_UNSUPPORTED; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("vitx_ctx_create: no HIP device available (this engine has no CPU fallback)"); return VITX_ERR_HIP; }
@@ -135,6 +137,7 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
     c->mx = dtype == VITX_MXFP8; c->dtype = c->mx ? VITX_BF16 : dtype;      // everything but the MX GEMMs runs as in a VITX_BF16 context
     c->D = hp.hidden_size; c->L = hp.num_hidden_layers; c->H = hp.num_attention_heads; c->C = hp.num_classes; c->P = hp.patch_size; c->S = img_size;
     c->Cin = m->in_chans; c->R = m->in_chans == 1 ? VITX_VITSTR_SEQ_LEN : 1;
+    c->fc1_epi = act_epi(m->activation);
     c->nreg = m->num_registers; c->Tp = 1 + c->nreg; c->pool = m->head_pool == VITX_POOL_CLS_MEAN;
     c->g = c->S / c->P; c->N = c->g * c->g + c->Tp; c->Kpe = c->Cin * c->P * c->P; c->Kpe_pad = round_up(c->Kpe, 64);
     if (c->N < c->R) { set_error("vitx_ctx_create: a ViTSTR head reads %d tokens, this model has %d (img_size %d, patch_size %d)", c->R, c->N, c->S, c->P); return VITX_ERR_UNSUPPORTED; }
@@ -192,6 +195,7 @@ int obtain_weights(vitx_ctx *c, int dtype) {
         if ((rc = upload_f32(c, T("cls_token"), &ws.cls))) return rc;
         if (c->nreg && (rc = upload_f32(c, T("reg_token"), &ws.reg))) return rc;
         if ((rc = upload_f32(c, T("pos_embed"), &ws.pos))) return rc;
+        if (m->has_pre_norm && ((rc = upload_f32(c, T("pre_norm.weight"), &ws.pre_w)) || (rc = upload_f32(c, T("pre_norm.bias"), &ws.pre_b)))) return rc;
         if ((rc = upload_f32(c, T("patch_embed.proj.bias"), &ws.pe_b, round_up(D, tn)))) return rc;
         if ((rc = upload_matrix(c, T("patch_embed.proj.weight"), D, c->Kpe, round_up(D, tn), c->Kpe_pad, &ws.pe_w, c->P, c->Cin))) return rc;
         ws.layers.resize(c->L);

@@ -79,6 +79,7 @@ struct vitx_ctx {
     // Token layout of an image (include/vitx.h "Register tokens and the pooled head"): row 0 = class token, rows 1 .. nreg = register tokens,
     // rows Tp .. N - 1 = patches in raster order; N = g * g + Tp
     int nreg = 0, Tp = 1;                // register tokens of the model (reg_token), prefix tokens 1 + nreg
+    int fc1_epi = EPI_BIAS_GELU;         // the fc1 epilogue of the model's activation (vitx_model_activation), taken once at creation
     bool pool = false;                   // VITX_POOL_CLS_MEAN: the head reads concat(cls, mean of the patch tokens) of the final norm, K = 2 D
     int tm = 128, tn = 128;
     const Tuning *tune = nullptr;        // per-device launch parameters (CU count, kernel selection), immutable
@@ -93,6 +94,7 @@ struct vitx_ctx {
     struct WeightSet {
         int device = 0;
         std::vector<void *> allocs;
+        float *pre_w = nullptr, *pre_b = nullptr;      // pre_norm.* (nullptr without them): LayerNorm of the token rows in front of layer 0
         float *cls = nullptr, *reg = nullptr, *pos = nullptr, *pe_b = nullptr, *norm_w = nullptr, *norm_b = nullptr, *head_b = nullptr;
         void *pe_w = nullptr, *head_w = nullptr;
         QuantW head_q;

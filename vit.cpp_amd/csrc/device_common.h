@@ -67,20 +67,67 @@ __device__ __forceinline__ f32x2 gelu_tanh2(f32x2 x) {
     return x * f32x2{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
 }
 
+// QuickGELU (CLIP; ggml_gelu_quick): x * sigmoid(1.702 x) = x / (1 + exp2(-1.702 log2(e) x)) -- the shape of gelu_tanh2 without the cubic term:
+// 2 packed multiplies, 1 packed add, v_exp_f32 and v_rcp_f32 per element.
+__device__ __forceinline__ f32x2 quick_gelu2(f32x2 x) {
+    constexpr float B = -1.702f * 1.44269504088896340736f;
+    const f32x2 t = x * f32x2{B, B};
+    const f32x2 d = f32x2{__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])} + f32x2{1.0f, 1.0f};
+    return x * f32x2{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
+}
+
+// erf-GELU (nn.GELU, HuggingFace "gelu"): x * Phi(x).  With z = |x| / sqrt(2) and q = erfc(z) / 2 in (0, 1/2]:
+//   Phi(x) = q for x < 0, 1 - q for x >= 0   =>   x Phi(x) = max(x, 0) - |x| q
+// so the negative tail is the product |x| q itself (full relative accuracy of q: nothing like 1 + erf cancels) and the positive side subtracts a
+// term that is at most x / 2.  q = (poly(t) * t) * exp(-z^2), t = 1 / (1 + p z): Abramowitz & Stegun 7.1.26, |error of erfc| <= 1.5e-7, with
+// the 1/2 folded into the coefficients and 1 / sqrt(2) into p and the exponent: exp(-z^2) = exp2(-log2(e) / 2 * x^2).
+// Per element: one v_min (|x| as a source modifier, clamped at 16 where exp2 has long flushed to 0 -- keeps inf * 0 out), one v_max, v_rcp_f32,
+// v_exp_f32; per pair: 6 v_pk_fma_f32 and 3 v_pk_mul_f32.  No branch, no range split (the device library's erff is a multi-range polynomial).
+__device__ __forceinline__ f32x2 gelu_erf2(f32x2 x) {
+    constexpr float P = 0.3275911f * 0.70710678118654752440f;
+    constexpr float E = -0.5f * 1.44269504088896340736f;
+    constexpr float A1 = 0.5f * 0.254829592f, A2 = 0.5f * -0.284496736f, A3 = 0.5f * 1.421413741f, A4 = 0.5f * -1.453152027f, A5 = 0.5f * 1.061405429f;
+    const f32x2 ax = f32x2{__builtin_fminf(__builtin_fabsf(x[0]), 16.0f), __builtin_fminf(__builtin_fabsf(x[1]), 16.0f)};
+    const f32x2 d = __builtin_elementwise_fma(ax, f32x2{P, P}, f32x2{1.0f, 1.0f});
+    const f32x2 t = f32x2{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
+    const f32x2 s = (ax * ax) * f32x2{E, E};
+    const f32x2 e = f32x2{__builtin_amdgcn_exp2f(s[0]), __builtin_amdgcn_exp2f(s[1])};
+    f32x2 p = __builtin_elementwise_fma(t, f32x2{A5, A5}, f32x2{A4, A4});
+    p = __builtin_elementwise_fma(p, t, f32x2{A3, A3});
+    p = __builtin_elementwise_fma(p, t, f32x2{A2, A2});
+    p = __builtin_elementwise_fma(p, t, f32x2{A1, A1});
+    const f32x2 q = (p * t) * e;
+    return __builtin_elementwise_fma(-ax, q, f32x2{__builtin_fmaxf(x[0], 0.0f), __builtin_fmaxf(x[1], 0.0f)});
+}
+
+// The MLP activation by its id (enum vitx_activation: 0 tanh-GELU, 1 erf-GELU, 2 QuickGELU), a compile-time choice: no run-time branch in an epilogue
+template <int ACT> __device__ __forceinline__ f32x2 act2(f32x2 x) {
+    static_assert(ACT >= 0 && ACT <= 2, "enum vitx_activation");
+    if constexpr (ACT == 1) return gelu_erf2(x);
+    else if constexpr (ACT == 2) return quick_gelu2(x);
+    else return gelu_tanh2(x);
+}
+
 // fc1 epilogue activation of two adjacent outputs (ggml_gelu through the fp16 table, /root/reference/vit.cpp:893).
-//   F16 (parity mode): the table's semantics -- argument rounded to fp16, result rounded to fp16.
+//   F16 (parity mode): the table's semantics -- argument rounded to fp16, result rounded to fp16 (ggml_gelu_quick goes through the same kind of table).
 //   BF16 (the dtype BASELINE names): there is no bf16 rounding point in the reference to reproduce, so the argument stays f32 and only
 //   the stored value is rounded (it is the next GEMM's operand): one convert and two unpacks per pair less, same tolerance band.
-template <typename T> __device__ __forceinline__ typename Pair<T>::v2 gelu_out_pair(float v0, float v1);
-template <> __device__ __forceinline__ Pair<_Float16>::v2 gelu_out_pair<_Float16>(float v0, float v1) {
-    const Pair<_Float16>::v2 p = round_pair<_Float16>(v0, v1);
-    const f32x2 y = gelu_tanh2(f32x2{(float)p[0], (float)p[1]});
-    return round_pair<_Float16>(y[0], y[1]);
-}
-template <> __device__ __forceinline__ Pair<__bf16>::v2 gelu_out_pair<__bf16>(float v0, float v1) {
-    const f32x2 y = gelu_tanh2(f32x2{v0, v1});
-    return round_pair<__bf16>(y[0], y[1]);
-}
+// ACT: the activation (act2); the rounding points are the same for all three.
+template <typename T, int ACT = 0> struct GeluOut;
+template <int ACT> struct GeluOut<_Float16, ACT> {
+    static __device__ __forceinline__ Pair<_Float16>::v2 pair(float v0, float v1) {
+        const Pair<_Float16>::v2 p = round_pair<_Float16>(v0, v1);
+        const f32x2 y = act2<ACT>(f32x2{(float)p[0], (float)p[1]});
+        return round_pair<_Float16>(y[0], y[1]);
+    }
+};
+template <int ACT> struct GeluOut<__bf16, ACT> {
+    static __device__ __forceinline__ Pair<__bf16>::v2 pair(float v0, float v1) {
+        const f32x2 y = act2<ACT>(f32x2{v0, v1});
+        return round_pair<__bf16>(y[0], y[1]);
+    }
+};
+template <typename T, int ACT = 0> __device__ __forceinline__ typename Pair<T>::v2 gelu_out_pair(float v0, float v1) { return GeluOut<T, ACT>::pair(v0, v1); }
 
 // Softmax numerators of the attention kernels for two adjacent keys (ggml_soft_max, /root/reference/vit.cpp:856).
 //   F16 (parity mode): e = round(exp(round(s/8 - max/8))) -- the fp16 exp table's semantics; nmx = -max * kScale, kScale = 1/8 (exact).

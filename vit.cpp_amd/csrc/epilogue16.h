@@ -7,7 +7,8 @@
 // element is the same bits whichever kernel the batch size selects (tests/test_gpu_parity_r02.py).
 //
 // Epilogues (reference: /root/reference/vit.cpp): EPI_BIAS qkv (:820-823); EPI_BIAS_GELU fc1 + ggml_gelu through the fp16
-// table (:888-893; gelu_out_pair: F16 rounds the value before and after the activation as the table does, BF16 only after); EPI_BIAS_RESID proj / fc2 +
+// table (:888-893; gelu_out_pair: F16 rounds the value before and after the activation as the table does, BF16 only after; EPI_BIAS_GELU_ERF and
+// EPI_BIAS_QGELU are the same epilogue with another activation, chosen at compile time); EPI_BIAS_RESID proj / fc2 +
 // residual add in f32 (:868-873, :899-902); EPI_BIAS_F32 classifier head (:917-922); EPI_PATCH patch embedding + position
 // embedding, patch row -> token row (:774-800).
 #pragma once
@@ -44,14 +45,14 @@ __device__ __forceinline__ void epilogue16(const GemmArgs &g, f32x4 (&acc)[TM][T
             }
         }
         const bool vec = FULL || (c + 3 < g.N && (g.ldo & 3) == 0);       // this lane's four columns exist and are 8 / 16-byte aligned
-        if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_HILO) {
+        if constexpr (EPI == EPI_BIAS || epi_is_act(EPI) || EPI == EPI_BIAS_HILO) {
 #pragma unroll
             for (int t = 0; t < TM; ++t) {
                 const int row = row0 + t * 16;
                 if (!FULL && row >= g.M_real) continue;
                 const f32x4 v = ACC::get(acc[t][u], t * 8 + u + idx0) + bv;
                 v2 p0, p1;
-                if constexpr (EPI == EPI_BIAS_GELU) { p0 = gelu_out_pair<T>(v[0], v[1]); p1 = gelu_out_pair<T>(v[2], v[3]); }
+                if constexpr (epi_is_act(EPI)) { p0 = gelu_out_pair<T, epi_act(EPI)>(v[0], v[1]); p1 = gelu_out_pair<T, epi_act(EPI)>(v[2], v[3]); }
                 else { p0 = round_pair<T>(v[0], v[1]); p1 = round_pair<T>(v[2], v[3]); }
                 T *o = (T *)g.out + (size_t)row * g.ldo + c;
                 if (vec) *(v4 *)o = v4{p0[0], p0[1], p1[0], p1[1]};
@@ -157,7 +158,7 @@ __device__ __forceinline__ void epilogue16_staged(f32x4 (&acc)[2 * NB][4], const
     const int rd_off = (lane >> 3) * 128 + (((lane & 7) ^ ((lane >> 3) & 7)) * 16);         // row layout: row (lane>>3) + 8t, 16-byte piece lane&7
     const int wr_row = l15 * 128, x16 = (l15 & 7) * 16;                                    // MFMA layout: this lane's row of a 16-row block
     pp_lds_fence();
-    if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_HILO) {
+    if constexpr (EPI == EPI_BIAS || epi_is_act(EPI) || EPI == EPI_BIAS_HILO) {
         typedef typename Pair<T>::v2 v2;
         // EPI_BIAS_HILO stores every 16-row block twice: pass q = 2 b + plane, plane 0 = hi at the tile's place, plane 1 = lo behind
         // `hilo_soff` bytes (2 x the stores: 32 per NB = 4 tile, what pp_epi_stores counts)
@@ -169,7 +170,7 @@ __device__ __forceinline__ void epilogue16_staged(f32x4 (&acc)[2 * NB][4], const
             for (int u = 0; u < 4; ++u) {
                 const f32x4 v = ACC::get(acc[b][u], b * 8 + u + idx0) + bq[u];
                 v2 p0, p1;
-                if constexpr (EPI == EPI_BIAS_GELU) { p0 = gelu_out_pair<T>(v[0], v[1]); p1 = gelu_out_pair<T>(v[2], v[3]); }
+                if constexpr (epi_is_act(EPI)) { p0 = gelu_out_pair<T, epi_act(EPI)>(v[0], v[1]); p1 = gelu_out_pair<T, epi_act(EPI)>(v[2], v[3]); }
                 else { p0 = round_pair<T>(v[0], v[1]); p1 = round_pair<T>(v[2], v[3]); }
                 if (PL == 2 && plane == 1) { p0 = hilo_lo_pair<T>(v[0], v[1], p0); p1 = hilo_lo_pair<T>(v[2], v[3], p1); }
                 // columns u * 16 + 4 g4 .. + 3 -> bytes u * 32 + 8 g4 of the 128-byte patch row: 16-byte slot 2u + (g4 >> 1), half g4 & 1

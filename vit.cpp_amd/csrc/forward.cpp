@@ -247,7 +247,7 @@ struct SliceForward {
         // output projection + residual (vit.cpp:868-873), then norm2 (vit.cpp:881-885) -> U2
         if ((rc = resid_gemm_ln(r, r.pc_proj, sl.U, Wl[W_PROJ], w.proj_b, D, Fl[W_PROJ], w.ln2_w, w.ln2_b, sl.U2, &fix_u2))) return rc;
         // MLP (vit.cpp:889-900), then the NEXT layer's norm1 (vit.cpp:808-812) -> U; the last layer is followed by the final norm instead
-        if ((rc = gemm(c, st, r.pc_fc1, EPI_BIAS_GELU, dense_gemm(sl.U2, Wl[W_FC1], w.fc1_b, sl.Hbuf, r.M, r.M_real, 4 * D, round_up(4 * D, tn), D), Fl[W_FC1], nullptr,
+        if ((rc = gemm(c, st, r.pc_fc1, c->fc1_epi, dense_gemm(sl.U2, Wl[W_FC1], w.fc1_b, sl.Hbuf, r.M, r.M_real, 4 * D, round_up(4 * D, tn), D), Fl[W_FC1], nullptr,
                        fix_u2.todo ? &fix_u2 : nullptr))) return rc;
         if ((rc = resid_gemm_ln(r, r.pc_fc2, sl.Hbuf, Wl[W_FC2], w.fc2_b, 4 * D, Fl[W_FC2], nx ? nx->ln1_w : nullptr, nx ? nx->ln1_b : nullptr, sl.U, &fix_u))) return rc;
         if (!c->trace_ids.empty() && (rc = trace(il + 1))) return rc;
@@ -260,6 +260,11 @@ struct SliceForward {
         {
             ProfScope ps(c, st, PC_GEMM_PATCH, 2.0 * Mp_real * (double)D * c->Kpe, (double)n * c->S * c->S * c->Cin * 4 + (double)M_real * D * 4);
             HIP_TRY(launch_patch_embed(dt, (const float *)d_imgs, ws.pe_w, ws.pe_b, c->pos, ws.cls, ws.reg, c->nreg, sl.X, n, c->S, c->P, c->Cin, D, round_up(D, tn), c->Kpe_pad, st));
+        }
+        // pre-norm of a file with pre_norm.* (CLIP's pre_layrnorm): every token row, in place, before layer 0 -- trace stage 0 is the stream that enters it
+        if (ws.pre_w) {
+            ProfScope ps(c, st, PC_LAYERNORM, 0, (double)M_real * D * 8);
+            HIP_TRY(launch_layernorm_f32(sl.X, ws.pre_w, ws.pre_b, sl.X, M_real, D, c->hp.eps, st));
         }
         if (!c->trace_ids.empty() && (rc = trace(0))) return rc;
         // LayerNorm fusion: decided per forward (the GEMM shape of this sub-batch must take the wide persistent kernel; never while the caller is

@@ -153,6 +153,8 @@ static hipError_t launch_gemm_t(int epi, const GemmArgs &a, hipStream_t stream, 
         VITX_GEMM_CASE(EPI_BIAS_F32)
         VITX_GEMM_CASE(EPI_PATCH)
         VITX_GEMM_CASE(EPI_BIAS_HILO)
+        VITX_GEMM_CASE(EPI_BIAS_GELU_ERF)
+        VITX_GEMM_CASE(EPI_BIAS_QGELU)
     default: return hipErrorInvalidValue;
     }
 #undef VITX_GEMM_CASE
@@ -202,7 +204,7 @@ static hipError_t launch_wide(const Tuning &t, int dtype, int epi, const GemmArg
     // whole weight matrix fits beside the A panels in the XCD's 4 MiB L2 (+ a little: ViT-B qkv 3.4 MiB, fc1 4.5 MiB), group_m = 1 -- every CU of the
     // XCD on the same few row blocks, W resident, A streamed once -- is 0.4-0.7 % of the ViT-B forward faster than 8 (two independent A/Bs, same
     // bits); with ViT-L's matrices (6 / 8 MiB) it is 0.6 % slower, so they keep the A-resident groups of 8.
-    if (!a.group_m && !a.ln && (epi == EPI_BIAS || epi == EPI_BIAS_HILO || epi == EPI_BIAS_GELU)) a.group_m = ((size_t)a.N_pad * a.K * 2 <= ((size_t)5 << 20)) ? 1 : 8;
+    if (!a.group_m && !a.ln && (epi == EPI_BIAS || epi == EPI_BIAS_HILO || epi_is_act(epi))) a.group_m = ((size_t)a.N_pad * a.K * 2 <= ((size_t)5 << 20)) ? 1 : 8;
     if (a.ln) return (epi == EPI_BIAS_RESID && gemm_ln_fusable(t, a)) ? launch_gemm_pp(dtype, epi, a, t.n_cu, stream, 0) : hipErrorInvalidValue;
     if (gemm_pp_supports(a)) return launch_gemm_pp(dtype, epi, a, pp_grid(t, a), stream, t.pp_flags);
     return launch_gemm_ring(t, dtype, epi, a, wide_ring_cfg(a), stream);
@@ -258,7 +260,7 @@ hipError_t prepare_gemm(const Tuning &t) {
     GemmArgs none{};
     hipError_t e;
     for (int dt = 0; dt < 2; ++dt) {
-        for (int epi = 0; epi <= EPI_BIAS_HILO; ++epi) {
+        for (int epi = 0; epi < EPI_COUNT; ++epi) {
             for (int cfg : {945, 445, 245, 122}) if ((e = launch_gemm_ring(t, dt, epi, none, cfg, nullptr, true)) != hipSuccess) return e;
             if ((e = launch_gemm_pp(dt, epi, none, t.n_cu, nullptr, 0, true)) != hipSuccess) return e;
 #ifdef VITX_LAB

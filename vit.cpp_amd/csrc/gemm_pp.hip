@@ -48,7 +48,7 @@
 #define PP_AUX_QKV 2            // stores of the EPI_BIAS / EPI_BIAS_HILO epilogue (qkv -> attention)
 #endif
 #ifndef PP_AUX_H
-#define PP_AUX_H 2              // stores of the EPI_BIAS_GELU epilogue (fc1 -> fc2)
+#define PP_AUX_H 2              // stores of the fc1 epilogues EPI_BIAS_GELU / _GELU_ERF / _QGELU (fc1 -> fc2)
 #endif
 #ifndef PP_AUX_A_LNF
 #define PP_AUX_A_LNF 2          // A-operand LDS-DMA of the LayerNorm-fusing launches (proj: the attention output, fc2: H)
@@ -83,7 +83,7 @@ template <int N> __device__ __forceinline__ void pp_wait_vm_lgkm() { asm volatil
 __device__ __forceinline__ void pp_barrier() { asm volatile("s_barrier" ::: "memory"); }
 
 // whole-row stores of the staged epilogue per wave and tile (epilogue16_staged): the next tile's K loop skips over exactly this many
-template <int EPI> __host__ __device__ constexpr int pp_epi_stores() { return (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU) ? 16 : 32; }      // (EPI_BIAS_HILO: two 16-bit planes = 32)
+template <int EPI> __host__ __device__ constexpr int pp_epi_stores() { return (EPI == EPI_BIAS || epi_is_act(EPI)) ? 16 : 32; }      // (EPI_BIAS_HILO: two 16-bit planes = 32)
 
 // ---- EPI_BIAS_RESID + LayerNorm of the finished rows (GemmLn, kernels.h), for one full 256 x 256 tile of the persistent kernel.
 // Statistics follow device_common.h "LayerNorm statistics by 256-column tiles": this workgroup's tile is tile c = n0 / 256 of its rows;
@@ -552,7 +552,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_num_vgpr(PP_MAX_VGPR)
             // buffer op in a waterfall loop over the (uniform) SGPR offset
             if constexpr (LNF) relaxed = pp_epilogue_ln<T>(g, ln, acc16, rsrcO, smem, voff, __builtin_amdgcn_readfirstlane((m0 * g.ldo + n0) * esz), 8 * g.ldo * esz, tid, m0, n0, ntn);
             else {
-                epilogue16_staged<T, EPI, 4, (EPI == EPI_BIAS_GELU ? PP_AUX_H : ((EPI == EPI_BIAS || EPI == EPI_BIAS_HILO) ? PP_AUX_QKV : 0))>(acc16, bq, rsrcO, smem + LDS + wave * 4096, voff, __builtin_amdgcn_readfirstlane((m0 * g.ldo + n0) * esz), 8 * g.ldo * esz, lane, (int)(g.hilo_off * esz));
+                epilogue16_staged<T, EPI, 4, (epi_is_act(EPI) ? PP_AUX_H : ((EPI == EPI_BIAS || EPI == EPI_BIAS_HILO) ? PP_AUX_QKV : 0))>(acc16, bq, rsrcO, smem + LDS + wave * 4096, voff, __builtin_amdgcn_readfirstlane((m0 * g.ldo + n0) * esz), 8 * g.ldo * esz, lane, (int)(g.hilo_off * esz));
                 relaxed = true;
             }
         } else {
@@ -650,6 +650,8 @@ static hipError_t launch_pp_t(int epi, const GemmArgs &a, int n_cu, hipStream_t 
     case EPI_BIAS_F32: return launch_pp_inst<T, EPI_BIAS_F32, 0>(a, n_cu, stream, prepare);
     case EPI_PATCH: return launch_pp_inst<T, EPI_PATCH, 0>(a, n_cu, stream, prepare);
     case EPI_BIAS_HILO: return launch_pp_inst<T, EPI_BIAS_HILO, 0>(a, n_cu, stream, prepare);
+    case EPI_BIAS_GELU_ERF: return launch_pp_inst<T, EPI_BIAS_GELU_ERF, 0>(a, n_cu, stream, prepare);
+    case EPI_BIAS_QGELU: return launch_pp_inst<T, EPI_BIAS_QGELU, 0>(a, n_cu, stream, prepare);
     default: return hipErrorInvalidValue;
     }
 }

@@ -21,13 +21,20 @@ enum {
     EPI_BIAS_RESID = 2,  // out(f32)[m][n]   = (acc + bias[n]) + out[m][n]         proj/fc2 (vit.cpp:868-873, 896-900)
     EPI_BIAS_F32 = 3,    // out(f32)[m][n]   = acc + bias[n]                       head     (vit.cpp:927-928)
     EPI_PATCH = 4,       // out(f32)[m + (m/tpi + 1) * prefix][n] = (acc + bias[n]) + pos[(m%tpi + 1)][n]   (vit.cpp:772-797; prefix = 1 there)
-    EPI_BIAS_HILO = 5    // qkv of the F16 parity mode: v = acc + bias[n] kept to f32 grade as TWO 16-bit planes, out[m][n] = hi = round(v) and
+    EPI_BIAS_HILO = 5,   // qkv of the F16 parity mode: v = acc + bias[n] kept to f32 grade as TWO 16-bit planes, out[m][n] = hi = round(v) and
                          // out[hilo_off + ..] = lo = round((v - hi) * 2048): the reference's q, k, v stay f32 into the attention products
                          // (vit.cpp:826-858: ggml_mul_mat of f32 views), and hi + lo / 2048 reproduces v to 2^-22
+    EPI_BIAS_GELU_ERF = 6,  // fc1 of a VITX_ACT_GELU_ERF model:   EPI_BIAS_GELU with x Phi(x) (gelu_erf2) in place of gelu_tanh, same rounding points
+    EPI_BIAS_QGELU = 7      // fc1 of a VITX_ACT_QUICK_GELU model: ... with x sigmoid(1.702 x) (quick_gelu2)
 };
+constexpr int EPI_COUNT = 8;
+// the three fc1 epilogues: out(dtype) = act(acc + bias), and the activation each evaluates (enum vitx_activation, act2 of device_common.h)
+constexpr __host__ __device__ bool epi_is_act(int epi) { return epi == EPI_BIAS_GELU || epi == EPI_BIAS_GELU_ERF || epi == EPI_BIAS_QGELU; }
+constexpr __host__ __device__ int epi_act(int epi) { return epi == EPI_BIAS_GELU_ERF ? 1 : epi == EPI_BIAS_QGELU ? 2 : 0; }
+constexpr int act_epi(int activation) { return activation == 1 ? EPI_BIAS_GELU_ERF : activation == 2 ? EPI_BIAS_QGELU : EPI_BIAS_GELU; }
 constexpr float kHiLoScale = 2048.0f, kHiLoInv = 1.0f / 2048.0f;
 // bytes of one output element: the operand type (qkv, fc1) or f32 (residual, head, patch embedding)
-constexpr __host__ __device__ int epi_out_bytes(int epi) { return (epi == EPI_BIAS || epi == EPI_BIAS_GELU || epi == EPI_BIAS_HILO) ? 2 : 4; }
+constexpr __host__ __device__ int epi_out_bytes(int epi) { return (epi == EPI_BIAS || epi_is_act(epi) || epi == EPI_BIAS_HILO) ? 2 : 4; }
 
 struct GemmArgs {
     const void *A; const void *W; const float *bias; void *out; const float *pos;
@@ -144,6 +151,9 @@ void patch_embed_permute_k(const uint16_t *w, uint16_t *w_perm, int N, int Cin, 
 // y[r][:] (dtype) = LN(x[r*ldx ...]) * w + b   (layernorm.hip; vit.cpp:808-812)
 // group > 1: input row r = x + (r / group) * gstride + (r % group) * ldx (the first `group` tokens of every image: ViTSTR head)
 hipError_t launch_layernorm(int dtype, const float *x, long ldx, const float *w, const float *b, void *y, long ldy, int M, int D, float eps, hipStream_t stream, int group = 1, long gstride = 0);
+// y[r][:] (f32, NOT rounded) = LN(x[r][:]) * w + b, rows of D floats: the value launch_layernorm rounds -- same statistics, same operation order, every
+// width of VITX_LN_WIDTHS.  y == x is allowed (a wave owns whole rows).  The pre-norm of a file with pre_norm.* (CLIP's pre_layrnorm), in place on X.
+hipError_t launch_layernorm_f32(const float *x, const float *w, const float *b, float *y, int M, int D, float eps, hipStream_t stream);
 // fused per-(image,head) attention  (vit.cpp:826-866): the dispatcher over the attention families (attention.hip)
 hipError_t launch_attention(const Tuning &t, int dtype, const void *qkv, void *out, int n_img, int N, int D, int H, hipStream_t stream);
 // Streaming two-pass kernel (attention_stream.hip), head dim 64, any token count.  precise = false: the long-sequence kernel of both
@@ -220,7 +230,7 @@ bool gemm_ring_supports(const GemmArgs &a, int cfg);
 hipError_t launch_gemm_pp(int dtype, int epi, const GemmArgs &a, int n_cu, hipStream_t stream, int flags = 0, bool prepare = false);
 bool gemm_pp_supports(const GemmArgs &a);
 // free-running wide kernels (gemm_w4.hip; LABORATORY BUILD ONLY: tools/Makefile), waves = 8: two waves per SIMD, 128 x 64 of C per wave; 4: one
-// per SIMD, 128 x 128 per wave.  EPI_BIAS, EPI_BIAS_GELU; same bits as the other families
+// per SIMD, 128 x 128 per wave.  EPI_BIAS, EPI_BIAS_GELU (tanh only: hipErrorInvalidValue for the other activations); same bits as the other families
 hipError_t launch_gemm_w4(int dtype, int epi, const GemmArgs &a, int n_cu, hipStream_t stream, int flags = 0, bool prepare = false, int waves = 8);
 bool gemm_w4_supports(const GemmArgs &a);
 bool attention_persist_supports(int n_img, int N, int D);      // attention_persist.hip: 193..224 tokens, the whole QKV tensor below 0xf0000000 bytes

@@ -42,6 +42,60 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float *__restrict_
     }
 }
 
+// The same LayerNorm with the f32 result stored as it is (launch_layernorm_f32: the pre-norm of a file with pre_norm.*, in place on the residual
+// stream): the statistics and the operation order of ln_row_tiled / the flat path above, so that RNE(y) is layernorm_kernel's output bit for bit.
+// One wave per row; the whole row is in registers before the first store, so y == x is allowed.
+template <int VEC, int NV>
+__global__ __launch_bounds__(256) void layernorm_f32_kernel(const float *x, const float *__restrict__ w, const float *__restrict__ b, float *y, int M, float eps) {
+    constexpr int D = 64 * VEC * NV;
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const float *xr = x + (size_t)row * D;
+    float *yr = y + (size_t)row * D;
+    if constexpr (VEC == 4 && NV <= LN_MAX_TILES) {
+        f32x4 v[NV];
+        float mean, rstd;
+        ln_tiled_stats<NV>(xr, eps, lane, v, mean, rstd);
+#pragma unroll
+        for (int c = 0; c < NV; ++c) {
+            const int idx = c * 256 + lane * 4;
+            const f32x4 ww = *(const f32x4 *)(w + idx), bb = *(const f32x4 *)(b + idx);
+            f32x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { float t = (v[c][e] - mean) * rstd; t = t * ww[e]; o[e] = t + bb[e]; }
+            *(f32x4 *)(yr + idx) = o;
+        }
+    } else {
+        float v[NV][VEC];
+        float scale;
+        ln_flat_stats<VEC, NV>(xr, eps, lane, v, scale);
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int idx = (i * 64 + lane) * VEC;
+            float o[VEC];
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) { float t = v[i][j] * scale; t = t * w[idx + j]; o[j] = t + b[idx + j]; }
+            if constexpr (VEC == 4) *(f32x4 *)(yr + idx) = f32x4{o[0], o[1], o[2], o[3]};
+            else {
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) yr[idx + j] = o[j];
+            }
+        }
+    }
+}
+hipError_t launch_layernorm_f32(const float *x, const float *w, const float *b, float *y, int M, int D, float eps, hipStream_t stream) {
+    const dim3 grid((M + 3) / 4), blk(256);
+#define VITX_LN_CASE(DD, VEC, NV) \
+    case DD: hipLaunchKernelGGL((layernorm_f32_kernel<VEC, NV>), grid, blk, 0, stream, x, w, b, y, M, eps); break;
+    switch (D) {
+        VITX_LN_WIDTHS(VITX_LN_CASE)
+    default: return hipErrorInvalidValue;
+    }
+#undef VITX_LN_CASE
+    return hipGetLastError();
+}
+
 // Row blocks a LayerNorm-fusing GEMM left behind (GemmLn: todo[rb] == epoch): 64 workgroups, every wave takes one row of each such
 // block -- no single-CU tail.  With nothing to do (the normal case) a workgroup reads the flags and exits.
 template <typename T, int NT>

@@ -9,6 +9,8 @@
 // takes f16 there, vit.cpp:515, so "--ftype 0" files it cannot load are loadable here).
 // Two optional extensions the reference's loader has no slot for (DINOv2-class models; include/vitx.h "Register tokens and the pooled
 // head"), recognised by name and shape: `reg_token` f32 [1][R][D], and a `head.weight` of [C][2 D].
+// Two more (include/vitx.h "Activation, epsilon and pre-norm"): `arch` f32 [4] = {activation, eps, 0, 0} and the pair `pre_norm.weight`,
+// `pre_norm.bias` f32 [D] (CLIP's pre_layrnorm).  Without `arch` a file means tanh-GELU and eps 1e-6, the reference's arithmetic.
 #include "model_file.h"
 
 #include <stdarg.h>
@@ -148,6 +150,7 @@ static int load_impl(const char *path, vitx_model &m) {
         m.id2label[key] = v;
     }
     const auto expect = expected_tensors(hp);
+    int n_optional = 0;                                              // `arch`, `pre_norm.*` records seen
     for (;;) {
         int32_t n_dims, name_len, ttype;
         if (!rd_i32(n_dims)) break;                                  // clean EOF (vit.cpp:600-603)
@@ -170,6 +173,40 @@ static int load_impl(const char *path, vitx_model &m) {
             m.num_registers = (int)t.ne[1];
             m.index[t.name] = (int)m.tensors.size();
             m.tensors.push_back(std::move(t));
+            continue;
+        }
+        if (t.name == "arch") {                                      // optional: f32 [4] = {activation, eps, 0, 0} (include/vitx.h "Activation, epsilon and pre-norm")
+            if (m.index.count(t.name)) { set_error("vitx_model_load: duplicate tensor '%s'", t.name.c_str()); return VITX_ERR_FORMAT; }
+            if (ttype != T_F32 || n_dims != 1 || t.ne[0] != 4) {
+                set_error("vitx_model_load: tensor 'arch' must be f32 [4] = {activation, eps, 0, 0}: got type %d, %d dims [%lld, ..]", ttype, n_dims, (long long)t.ne[0]);
+                return VITX_ERR_FORMAT;
+            }
+            t.raw.resize(16);
+            if (fread(t.raw.data(), 1, 16, f) != 16) { set_error("vitx_model_load: tensor '%s' is truncated", t.name.c_str()); return VITX_ERR_IO; }
+            float a[4]; memcpy(a, t.raw.data(), 16);
+            if (a[0] != (float)VITX_ACT_GELU_TANH && a[0] != (float)VITX_ACT_GELU_ERF && a[0] != (float)VITX_ACT_QUICK_GELU) {
+                set_error("vitx_model_load: tensor 'arch' names activation %g: 0 tanh-GELU, 1 erf-GELU and 2 QuickGELU exist", (double)a[0]); return VITX_ERR_FORMAT;
+            }
+            if (!(a[1] > 0.0f) || !(a[1] <= 3.402823466e38f)) { set_error("vitx_model_load: tensor 'arch' carries LayerNorm eps %g: it must be finite and positive", (double)a[1]); return VITX_ERR_FORMAT; }
+            if (a[2] != 0.0f || a[3] != 0.0f) { set_error("vitx_model_load: tensor 'arch' has reserved slots {%g, %g}: they must be 0", (double)a[2], (double)a[3]); return VITX_ERR_FORMAT; }
+            m.activation = (int)a[0]; hp.eps = a[1];
+            m.index[t.name] = (int)m.tensors.size();
+            m.tensors.push_back(std::move(t));
+            ++n_optional;
+            continue;
+        }
+        if (t.name == "pre_norm.weight" || t.name == "pre_norm.bias") {   // optional pair: LayerNorm of the token rows in front of layer 0, f32 [D]
+            if (m.index.count(t.name)) { set_error("vitx_model_load: duplicate tensor '%s'", t.name.c_str()); return VITX_ERR_FORMAT; }
+            if (ttype != T_F32 || n_dims != 1 || t.ne[0] != hp.hidden_size) {
+                set_error("vitx_model_load: tensor '%s' must be f32 [%d]: got type %d, %d dims [%lld, ..]", t.name.c_str(), hp.hidden_size, ttype, n_dims, (long long)t.ne[0]);
+                return VITX_ERR_FORMAT;
+            }
+            const size_t nbytes = (size_t)t.nelements() * 4;
+            t.raw.resize(nbytes);
+            if (fread(t.raw.data(), 1, nbytes, f) != nbytes) { set_error("vitx_model_load: tensor '%s' is truncated", t.name.c_str()); return VITX_ERR_IO; }
+            m.index[t.name] = (int)m.tensors.size();
+            m.tensors.push_back(std::move(t));
+            ++n_optional;
             continue;
         }
         auto it = expect.find(t.name);
@@ -199,7 +236,12 @@ static int load_impl(const char *path, vitx_model &m) {
         m.index[t.name] = (int)m.tensors.size();
         m.tensors.push_back(std::move(t));
     }
-    const size_t n_expect = expect.size() + (m.num_registers ? 1 : 0);
+    if ((m.find("pre_norm.weight") != nullptr) != (m.find("pre_norm.bias") != nullptr)) {
+        set_error("vitx_model_load: tensor '%s' has no partner: pre_norm.weight and pre_norm.bias come together", m.find("pre_norm.weight") ? "pre_norm.weight" : "pre_norm.bias");
+        return VITX_ERR_FORMAT;
+    }
+    m.has_pre_norm = m.find("pre_norm.weight") != nullptr;
+    const size_t n_expect = expect.size() + (m.num_registers ? 1 : 0) + (size_t)n_optional;
     if (m.tensors.size() != n_expect) {
         set_error("vitx_model_load: model file has %d tensors, but %d tensors were expected", (int)m.tensors.size(), (int)n_expect);
         return VITX_ERR_FORMAT;
@@ -242,6 +284,8 @@ int vitx_model_num_labels(const vitx_model *m) { return m ? (int)m->id2label.siz
 int vitx_model_in_channels(const vitx_model *m) { return m ? m->in_chans : 0; }
 int vitx_model_num_registers(const vitx_model *m) { return m ? m->num_registers : 0; }
 int vitx_model_head_pool(const vitx_model *m) { return m ? m->head_pool : 0; }
+int vitx_model_activation(const vitx_model *m) { return m ? m->activation : 0; }
+int vitx_model_has_pre_norm(const vitx_model *m) { return m && m->has_pre_norm ? 1 : 0; }
 int vitx_model_seq_len(const vitx_model *m) { return (m && m->in_chans == 1) ? VITX_VITSTR_SEQ_LEN : 0; }
 const char *vitx_model_label(const vitx_model *m, int id) {
     if (!m) return nullptr;

@@ -33,6 +33,8 @@ struct vitx_model {
     int in_chans = 3;                                 // 1 = ViTSTR file (grey input, sequence head), from the patch kernel's shape
     int num_registers = 0;                            // R of an optional `reg_token` [1][R][D]: tokens between the class token and the patches
     int head_pool = VITX_POOL_CLS;                    // VITX_POOL_CLS_MEAN: head.weight is [C][2 D], over concat(cls, mean of the patch tokens)
+    int activation = VITX_ACT_GELU_TANH;              // MLP activation, from an optional `arch` [4] = {activation, eps, 0, 0}; hp.eps carries its eps
+    bool has_pre_norm = false;                        // `pre_norm.weight` / `pre_norm.bias` [D]: LayerNorm of every token row in front of layer 0
     std::map<int, std::string> id2label;
     std::vector<vitx::HostTensor> tensors;            // file order
     std::map<std::string, int> index;                 // name -> position

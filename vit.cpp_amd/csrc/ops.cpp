@@ -25,8 +25,12 @@ int vitx_op_layernorm(int dtype, const void *x, const void *w, const void *b, vo
     if (!x || !w || !b || !y || M <= 0) return VITX_ERR_ARG;
     return op_rc("vitx_op_layernorm", launch_layernorm(dtype, (const float *)x, D, (const float *)w, (const float *)b, y, D, M, D, eps, (hipStream_t)stream), VITX_ERR_UNSUPPORTED);
 }
+int vitx_op_layernorm_f32(const void *x, const void *w, const void *b, void *y, int M, int D, float eps, void *stream) {
+    if (!x || !w || !b || !y || M <= 0) return VITX_ERR_ARG;
+    return op_rc("vitx_op_layernorm_f32", launch_layernorm_f32((const float *)x, (const float *)w, (const float *)b, (float *)y, M, D, eps, (hipStream_t)stream), VITX_ERR_UNSUPPORTED);
+}
 static int op_gemm_impl(int dtype, int epi, int kernel, const void *a, const void *w, const void *bias, void *out, const void *pos, int M, int M_real, int N, int n_pad, int K, int tpi, void *stream) {
-    if (!a || !w || !out || !bias || epi < 0 || epi > EPI_BIAS_HILO || M_real <= 0 || M_real > M || (epi == EPI_PATCH && (!pos || tpi <= 0))) { set_error("vitx_op_gemm_ex: invalid argument"); return VITX_ERR_ARG; }
+    if (!a || !w || !out || !bias || epi < 0 || epi >= EPI_COUNT || M_real <= 0 || M_real > M || (epi == EPI_PATCH && (!pos || tpi <= 0))) { set_error("vitx_op_gemm_ex: invalid argument"); return VITX_ERR_ARG; }
     if (M % 128 || N % 4 || K % 64) { set_error("vitx_op_gemm: M %% 128, N %% 4, K %% 64 must be 0"); return VITX_ERR_ARG; }
     const Tuning *t0 = tuning_for_device(-1);
     if (!t0) { set_error("vitx_op_gemm: kernel bring-up failed"); return VITX_ERR_HIP; }
@@ -46,7 +50,7 @@ int vitx_op_gemm_ex(int dtype, int epi, int kernel, const void *a, const void *w
     return op_gemm_impl(dtype, epi, kernel, a, w, bias, out, pos, M, M_real, N, round_up(N, 256), K, tpi, stream);     // W and bias hold N rounded up to 256 rows
 }
 int vitx_op_gemm(int dtype, int epi, const void *a, const void *w, const void *bias, void *out, int M, int N, int K, void *stream) {
-    if (epi < 0 || epi > 3 || N % 64) { set_error("vitx_op_gemm: epi 0..3, N %% 64 == 0"); return VITX_ERR_ARG; }
+    if (epi < 0 || (epi > 3 && !epi_is_act(epi)) || N % 64) { set_error("vitx_op_gemm: epi 0..3, 6 or 7, N %% 64 == 0"); return VITX_ERR_ARG; }
     return op_gemm_impl(dtype, epi, 0, a, w, bias, out, nullptr, M, M, N, round_up(N, gemm_tile_n()), K, 0, stream);   // W and bias hold N rounded up to 128 rows
 }
 // x[M][N] f32 += A[M][K] . W[N][K]^T + bias, then y[M][N] (dtype) = LayerNorm(x) * ln_w + ln_b computed by the GEMM's own epilogue
@@ -98,7 +102,7 @@ int vitx_op_dequant_jobs(int dtype, int qtype, int njobs, const void *const *blo
     return op_rc("vitx_op_dequant_jobs", launch_dequant(dtype, qtype, jobs, njobs, (hipStream_t)stream), VITX_ERR_ARG);
 }
 int vitx_op_gemm_q4(int dtype, int epi, const void *a, const void *qs, const void *scales, const void *bias, void *out, int M, int M_real, int N, int K, void *stream) {
-    if (!a || !qs || !scales || !bias || !out || epi < 0 || epi > EPI_BIAS_F32 || M_real <= 0 || M_real > M) { set_error("vitx_op_gemm_q4: invalid argument"); return VITX_ERR_ARG; }
+    if (!a || !qs || !scales || !bias || !out || epi < 0 || (epi > EPI_BIAS_F32 && !epi_is_act(epi)) || M_real <= 0 || M_real > M) { set_error("vitx_op_gemm_q4: invalid argument"); return VITX_ERR_ARG; }
     if (!tuning_for_device(-1)) { set_error("vitx_op_gemm_q4: kernel bring-up failed"); return VITX_ERR_HIP; }
     GemmArgs g = dense_gemm(a, qs, (const float *)bias, out, M, M_real, N, round_up(N, 128), K);
     g.Wscale = (const uint16_t *)scales;

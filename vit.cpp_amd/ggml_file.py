@@ -15,6 +15,8 @@ File (little endian, no padding):
 
 Two optional extensions the reference's loader cannot read (include/vitx.h "register tokens and the pooled head"): a `reg_token` f32
 [1][R][D] directly after cls_token, and a `head.weight` of [C][2 D].  Magic and hparams are unchanged; both are read off the shapes.
+Two more ("activation, epsilon and pre-norm"): `arch` f32 [4] = {activation, eps, 0, 0}, written first, and `pre_norm.weight` / `pre_norm.bias`
+f32 [D] directly after pos_embed.  All three are 1-D, so write_model stores them in f32 like every other vector, in the order it is given them.
 """
 from __future__ import annotations
 
