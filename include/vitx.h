@@ -149,6 +149,69 @@ int vitx_model_head_pool(const vitx_model *m);       /* enum vitx_head_pool, fro
 enum vitx_activation { VITX_ACT_GELU_TANH = 0, VITX_ACT_GELU_ERF = 1, VITX_ACT_QUICK_GELU = 2 };
 int vitx_model_activation(const vitx_model *m);      /* enum vitx_activation; 0 without `arch` (and for NULL) */
 int vitx_model_has_pre_norm(const vitx_model *m);    /* 1 when the file carries pre_norm.weight / pre_norm.bias */
+/* ---- each model's own preprocessing (CLIP, DINOv2, HuggingFace ViT, timm) ----
+ * How the publisher's image processor turns a decoded u8 RGB image into the model's input: resize (stretch, or shortest edge with the aspect
+ * kept), an optional square centre crop, mean / std.  The PIL filters are Pillow's Image.resize on u8 -- separable, antialiased, fixed-point
+ * coefficients, u8 between the passes -- and are matched BIT FOR BIT, on the host and on the device (arithmetic below); the REF filters are the
+ * reference's vit_image_preprocess (vitx_preprocess_u8), which is what a file without a description has always meant.
+ *   SHORTEST_EDGE: the short side becomes resize_a, the long side (int)((double)(resize_a * long_src) / (double)short_src) -- truncated, as
+ *     transformers and torchvision do (500 x 375 at 224 -> 298 x 224); the width is the short side when nx <= ny.
+ *   Output: crop x crop, or resize_a x resize_b when crop == 0.  Outputs are square: STRETCH without a crop needs resize_a == resize_b, and
+ *     SHORTEST_EDGE needs a crop.
+ *   Crop offset per axis, d = resized - crop: d / 2 for even d; odd d: (d - 1) / 2 with crop_round 0 (transformers' floor), d / 2.0 rounded half
+ *     to even with crop_round 1 (torchvision CenterCrop).
+ *   VITX_ERR_ARG: a crop larger than either resized side of the given source (padding is not offered), non-positive sizes (or any side above
+ *     16384, a source side above 2^20), resize_b != 0 with SHORTEST_EDGE, a REF filter with anything but STRETCH and no crop, a non-square
+ *     output, a mean255 that is not finite or a std255 that is not finite and positive, an unknown enum value.
+ * Arithmetic of the PIL filters (csrc/preproc_resample.h: ONE definition for host and device; no FMA contraction).  Per axis, in = source
+ * length, out = resized length, everything up to k_j in double:
+ *   scale = (double)in / out;  fs = max(scale, 1.0);  support = S0 * fs (S0: bilinear 1.0, bicubic 2.0);  ss = 1.0 / fs
+ *   target index o:  center = (o + 0.5) * scale;  first = max((int)(center - support + 0.5), 0);
+ *     n = min((int)(center + support + 0.5), in) - first   (truncating casts);   w_j = f((j + first - center + 0.5) * ss), j = 0 .. n-1
+ *     f bilinear: |x| < 1 ? 1 - |x| : 0;   f bicubic (a = -0.5): |x| < 1: ((a+2)|x| - (a+3))|x||x| + 1;  |x| < 2: (((|x|-5)|x| + 8)|x| - 4) a;  else 0
+ *     ww = ((w_0 + w_1) + w_2) + ...;  ww != 0: w_j = w_j / ww;   k_j = w_j < 0 ? (int)(-0.5 + w_j * 4194304.0) : (int)(0.5 + w_j * 4194304.0)
+ *   Per pixel and channel, int32: acc = 2^21 + sum_j px_j * k_j;  q = clamp(acc >> 22, 0, 255) (arithmetic shift).
+ *   The horizontal pass runs first, over the source rows the vertical taps need, into a u8 intermediate; then the vertical pass.  An axis with
+ *   in == out is skipped.  The crop window is a slice of the result: only its rows and columns are computed.
+ *   out = ((float)q - mean255[c]) / std255[c] in f32 with IEEE division, HWC -- the form of the reference's normalisation.
+ * File extension `preproc`: f32 [16] = {resize_mode, resize_a, resize_b, filter, crop, crop_round, mean255 r g b, std255 r g b, 0, 0, 0, 0}; the
+ * integers are stored exactly, the four reserved slots must be 0.  Any other type or shape, a duplicate, an invalid description, an output side
+ * other than hparams.img_size, or the tensor in a one-channel (ViTSTR) file: VITX_ERR_FORMAT.  The loader takes it anywhere in the file (the
+ * converter writes it directly after `arch`); vitx_quantize_file copies it through byte for byte; vitx_model_resize_file writes the
+ * vitx_preproc_at_size values.  The reference's vit_model_load cannot read such a file; files without it load, preprocess and run as before.
+ *   vitx_model_preproc      the file's description; without the tensor the reference default {STRETCH, img_size, img_size, REF_BICUBIC, 0, 0,
+ *                           the ImageNet mean255 / std255 of vitx_preprocess_u8}.  f32(255.0 * m) of the ImageNet mean / std equals those six
+ *                           literals bit for bit, so a DINOv2 file normalises exactly as vitx_preprocess_u8 does.
+ *   vitx_model_has_preproc  1 when the file carries the tensor.
+ *   vitx_preproc_at_size    the description for a context at another img_size -- THIS LIBRARY'S convention (publishers define one size only):
+ *                           crop' = img_size when a crop is set; every resize side becomes (2 * side * img_size + old) / (2 * old) in integers,
+ *                           old = the old output side: the crop fraction is kept, rounded to nearest.  in == out is allowed.
+ *   vitx_preprocess_ex      host: hwc u8 [ny][nx][3] -> out f32 [S][S][3], S = the output side; rows are split over host threads.  With a REF
+ *                           filter it runs vitx_preprocess_u8's code with the description's mean / std: the default description gives its bits.
+ *   vitx_preprocess_ex_device   the same for n images of one source size on device pointers, bit for bit; ONE launch, no scratch, only
+ *                           enqueues on `stream`.  A workgroup owns a 32 x 8 tile of one image's output window and keeps its coefficients, a
+ *                           staged source row per wave and the u8 intermediate of its tile in LDS, so the LDS need grows with the down-scale
+ *                           factor: about 96 * (8 * scale_y + 2 * support_y) + 12 * (32 * scale_x + 2 * support_x) + 4 * (32 * taps_x + 8 * taps_y)
+ *                           bytes, at most 64 KiB (a 4032 x 3024 source at shortest edge 256 needs about 26 KiB; a bicubic stretch of 8 x 576 to 8 x 8
+ *                           is the limit).  Beyond it: VITX_ERR_UNSUPPORTED before any launch; the host path has no bound.
+ *   vitx_preprocess_ex_device_supports   1 / 0 for that bound (0 also for an invalid description or source); no device call. */
+enum vitx_pp_filter { VITX_PP_REF_BICUBIC = 0, VITX_PP_REF_BILINEAR = 1,   /* the reference's (vitx_preprocess_u8's two) */
+                      VITX_PP_PIL_BILINEAR = 2, VITX_PP_PIL_BICUBIC = 3 }; /* Pillow Image.resize on u8 */
+enum vitx_pp_resize { VITX_PP_STRETCH = 0, VITX_PP_SHORTEST_EDGE = 1 };
+typedef struct vitx_preproc {
+    int32_t resize_mode;   /* STRETCH: to resize_a (width) x resize_b (height); SHORTEST_EDGE: short edge = resize_a, resize_b = 0 */
+    int32_t resize_a, resize_b;
+    int32_t filter;
+    int32_t crop;          /* side of the square centre crop; 0 = none */
+    int32_t crop_round;    /* offset = d/2 for even d = resized - crop; odd d: 0 = floor (transformers), 1 = round half to even (torchvision CenterCrop) */
+    float mean255[3], std255[3];   /* the f32 values the arithmetic uses: out = ((float)q - mean255[c]) / std255[c] */
+} vitx_preproc;
+int vitx_model_preproc(const vitx_model *m, vitx_preproc *out);
+int vitx_model_has_preproc(const vitx_model *m);
+int vitx_preproc_at_size(const vitx_preproc *in, int img_size, vitx_preproc *out);
+int vitx_preprocess_ex(const vitx_preproc *pp, const uint8_t *hwc, int nx, int ny, float *out_hwc);          /* out: [S][S][3] */
+int vitx_preprocess_ex_device(const vitx_preproc *pp, const void *d_hwc, int n, int nx, int ny, void *d_out_hwc, void *stream);
+int vitx_preprocess_ex_device_supports(const vitx_preproc *pp, int nx, int ny);   /* 1 / 0, no device call */
 int vitx_model_num_tensors(const vitx_model *m);
 /* Name, file type code (0 f32,1 f16,2 q4_0,3 q4_1,6 q5_0,7 q5_1,8 q8_0), ggml-order dims. */
 int vitx_model_tensor_info(const vitx_model *m, int index, const char **name, int32_t *type, int64_t ne[4], size_t *nbytes);
@@ -287,7 +350,8 @@ int vitx_ctx_synchronize(vitx_ctx *c);
  *   vitx_model_resize_file      writes path_out = path_in with hparams.img_size = img_size and pos_embed resampled on the host; every other byte of
  *                               the file is copied through (quantised files included: pos_embed is always f32).  The result is an ordinary model
  *                               file: this library, the oracle and the reference's own vit_model_load read it (a file with reg_token or the
- *                               pooled head stays one only this library reads; reg_token is copied, pos_embed keeps 1 + g^2 rows).  img_size not a positive multiple
+ *                               pooled head stays one only this library reads; reg_token is copied, pos_embed keeps 1 + g^2 rows; a `preproc` tensor is
+ *                               rewritten with its vitx_preproc_at_size values).  img_size not a positive multiple
  *                               of the patch size, an unknown interp or path_out == path_in: VITX_ERR_ARG; a ViTSTR file at another size than its
  *                               own: VITX_ERR_UNSUPPORTED; an unreadable input: VITX_ERR_IO. */
 enum vitx_pos_interp { VITX_POS_BICUBIC = 0, VITX_POS_BICUBIC_AA = 1 };

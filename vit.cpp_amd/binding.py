@@ -29,6 +29,8 @@ ATTN_AUTO, ATTN_SINGLE, ATTN_FLOW, ATTN_PERSIST, ATTN_STREAM = 0, 1, 3, 4, 5   #
 ATTN_ROLLOUT = 1                # vitx_attn_enable flag
 FEAT_CLS, FEAT_MEAN, FEAT_TOKENS, FEAT_L2 = 1, 2, 4, 8      # vitx_feat_enable flags
 POOL_CLS, POOL_CLS_MEAN = 0, 1          # vitx_model_head_pool: the head reads the class token, or concat(cls, mean of the patch tokens)
+PP_REF_BICUBIC, PP_REF_BILINEAR, PP_PIL_BILINEAR, PP_PIL_BICUBIC = 0, 1, 2, 3      # vitx_pp_filter: the reference's two, Pillow's Image.resize on u8
+PP_STRETCH, PP_SHORTEST_EDGE = 0, 1     # vitx_pp_resize
 POS_BICUBIC, POS_BICUBIC_AA = 0, 1      # vitx_pos_interp: F.interpolate(mode="bicubic") without / with antialias=True (include/vitx.h)
 
 EXPORTS = [
@@ -45,6 +47,7 @@ EXPORTS = [
     "vitx_op_topk", "vitx_op_dequant_jobs",
     "vitx_model_num_registers", "vitx_model_head_pool", "vitx_ctx_registers", "vitx_op_features_ex", "vitx_op_patch_embed",
     "vitx_model_activation", "vitx_model_has_pre_norm", "vitx_op_layernorm_f32",
+    "vitx_model_preproc", "vitx_model_has_preproc", "vitx_preproc_at_size", "vitx_preprocess_ex", "vitx_preprocess_ex_device", "vitx_preprocess_ex_device_supports",
 ]
 
 
@@ -57,6 +60,24 @@ class CtxOptions(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("streams", C.c_int32), ("graph", C.c_int32), ("quant_on_host", C.c_int32), ("q4_fused_rows", C.c_int32),
                 ("split_first", C.c_int32), ("no_ln_fusion", C.c_int32), ("ln_test", C.c_int32), ("f16_fast_attention", C.c_int32), ("last_layer_all_rows", C.c_int32),
                 ("img_size", C.c_int32), ("pos_interp", C.c_int32)]
+
+
+class Preproc(C.Structure):
+    """vitx_preproc: how a model's publisher turns a decoded u8 RGB image into its input (include/vitx.h "each model's own preprocessing")."""
+    _fields_ = [("resize_mode", C.c_int32), ("resize_a", C.c_int32), ("resize_b", C.c_int32), ("filter", C.c_int32), ("crop", C.c_int32), ("crop_round", C.c_int32),
+                ("mean255", C.c_float * 3), ("std255", C.c_float * 3)]
+
+    @classmethod
+    def make(cls, resize_mode=PP_STRETCH, resize_a=224, resize_b=0, filter=PP_PIL_BICUBIC, crop=0, crop_round=0, mean255=(0.0, 0.0, 0.0), std255=(1.0, 1.0, 1.0)) -> "Preproc":
+        return cls(resize_mode, resize_a, resize_b, filter, crop, crop_round, (C.c_float * 3)(*mean255), (C.c_float * 3)(*std255))
+
+    @property
+    def out_size(self) -> int:
+        return self.crop or self.resize_a
+
+    def fields(self) -> dict:
+        return dict(resize_mode=self.resize_mode, resize_a=self.resize_a, resize_b=self.resize_b, filter=self.filter, crop=self.crop, crop_round=self.crop_round,
+                    mean255=tuple(np.float32(v) for v in self.mean255), std255=tuple(np.float32(v) for v in self.std255))
 
 
 class ProfEntry(C.Structure):
@@ -180,6 +201,13 @@ def lib():
         if hasattr(L, "vitx_model_activation"):
             L.vitx_model_activation.argtypes = [vp]; L.vitx_model_has_pre_norm.argtypes = [vp]
             L.vitx_op_layernorm_f32.argtypes = [vp, vp, vp, vp, ip, ip, C.c_float, vp]
+        if hasattr(L, "vitx_preprocess_ex"):
+            pp = C.POINTER(Preproc)
+            L.vitx_model_preproc.argtypes = [vp, pp]; L.vitx_model_has_preproc.argtypes = [vp]
+            L.vitx_preproc_at_size.argtypes = [pp, ip, pp]
+            L.vitx_preprocess_ex.argtypes = [pp, C.POINTER(C.c_uint8), ip, ip, C.POINTER(C.c_float)]
+            L.vitx_preprocess_ex_device.argtypes = [pp, vp, ip, ip, ip, vp, vp]
+            L.vitx_preprocess_ex_device_supports.argtypes = [pp, ip, ip]
         _lib = L
     return _lib
 
@@ -228,6 +256,16 @@ class Model:
     @property
     def has_pre_norm(self) -> bool:                                                 # pre_norm.weight / pre_norm.bias: CLIP's pre_layrnorm
         return bool(lib().vitx_model_has_pre_norm(self._h)) if hasattr(lib(), "vitx_model_has_pre_norm") else False
+    @property
+    def has_preproc(self) -> bool:                                                  # the file carries a `preproc` tensor
+        return bool(lib().vitx_model_has_preproc(self._h))
+
+    def preproc(self) -> "Preproc":
+        """vitx_model_preproc: the file's preprocessing; without the tensor the reference default (stretch, REF_BICUBIC, ImageNet mean / std)."""
+        pp = Preproc()
+        check(lib().vitx_model_preproc(self._h, C.byref(pp)), "vitx_model_preproc")
+        return pp
+
     @property
     def num_classes(self) -> int: return self.hparams.num_classes
     @property
@@ -314,6 +352,32 @@ def preprocess(img_u8: np.ndarray, img_size: int, interp: int = BICUBIC) -> np.n
     out = np.empty((img_size, img_size, 3), np.float32)
     check(lib().vitx_preprocess_u8(img.ctypes.data_as(C.POINTER(C.c_uint8)), nx, ny, img_size, interp, out.ctypes.data_as(C.POINTER(C.c_float))), "vitx_preprocess_u8")
     return out
+
+
+def preproc_at_size(pp: Preproc, img_size: int) -> Preproc:
+    """vitx_preproc_at_size: the description for a context at another img_size (the crop fraction is kept, rounded to nearest)."""
+    out = Preproc()
+    check(lib().vitx_preproc_at_size(C.byref(pp), img_size, C.byref(out)), "vitx_preproc_at_size")
+    return out
+
+
+def preprocess_ex(img_u8: np.ndarray, pp: Preproc) -> np.ndarray:
+    """vitx_preprocess_ex: HWC u8 any size -> HWC f32 [S,S,3] by the description (resize, centre crop, mean / std), on the host."""
+    img = np.ascontiguousarray(img_u8, np.uint8); ny, nx = img.shape[:2]
+    S = max(int(pp.out_size), 1)
+    out = np.empty((S, S, 3), np.float32)
+    check(lib().vitx_preprocess_ex(C.byref(pp), img.ctypes.data_as(C.POINTER(C.c_uint8)), nx, ny, out.ctypes.data_as(C.POINTER(C.c_float))), "vitx_preprocess_ex")
+    return out
+
+
+def preprocess_ex_device(pp: Preproc, d_u8: int, n: int, nx: int, ny: int, d_out: int, stream: int = 0) -> None:
+    """vitx_preprocess_ex_device: the same on the GPU for n images of one source size (device pointers; one launch, enqueue only)."""
+    check(lib().vitx_preprocess_ex_device(C.byref(pp), d_u8, n, nx, ny, d_out, stream or None), "vitx_preprocess_ex_device")
+
+
+def preprocess_ex_device_supports(pp: Preproc, nx: int, ny: int) -> bool:
+    """vitx_preprocess_ex_device_supports: whether the device kernel's LDS tile covers this down-scale (no device call)."""
+    return bool(lib().vitx_preprocess_ex_device_supports(C.byref(pp), nx, ny))
 
 
 def preprocess_vitstr(img_u8: np.ndarray, img_size: int) -> np.ndarray:

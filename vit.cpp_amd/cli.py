@@ -6,6 +6,12 @@ directory-walk accuracy harness:
     python vit_cli.py -m model.gguf -i image.jpg --attn-map map.pgm [--attn-kind rollout|last]   # + where the model looked (P5 picture)
     python vit_cli.py -m model.gguf (-i image.jpg | --dir DIR) --embed out.npy [--embed-kind cls|mean|tokens] [--embed-l2]   # + the embeddings
     python vit_cli.py -m model.gguf ... --img-size 384 [--pos-interp bicubic|bicubic-aa]   # run at another input size than the file's
+    python vit_cli.py -m model.gguf ... [--preprocess model|reference]   # the file's own preprocessing (default) or the reference's for any file
+
+--preprocess model follows the file's `preproc` tensor (include/vitx.h "each model's own preprocessing": what convert.py reads from a
+HuggingFace preprocessor_config.json -- CLIP: Pillow-bicubic shortest edge 224, centre crop 224, CLIP's mean / std; DINOv2: shortest edge 256,
+crop 224; HuggingFace ViT: Pillow-bilinear stretch, mean = std = 0.5); with --img-size it is rescaled by vitx_preproc_at_size.  A file without
+the tensor -- every file of the reference's converter -- is preprocessed by the reference's vit_image_preprocess with --interp, as always.
 
 Same flags as vit_params_parse (vit.cpp:955-1002: -m -i -t -k -s -e; -t, -s and -e are accepted and ignored exactly
 as the reference's forward ignores seed and eps), same stdout lines (" > label : 0.xx", vit.cpp:1062-1067) and the
@@ -51,6 +57,9 @@ def main(argv: List[str] | None = None) -> int:
                     help="MFMA operand type; f16 reproduces the reference's rounding points; mxfp8 is EXPERIMENTAL (qkv, fc1, fc2 on block-scaled e4m3, "
                          "the rest bf16): slower than bf16 on MI355X and less accurate (DESIGN.md section 4)")
     ap.add_argument("--interp", default="bicubic", choices=["bicubic", "bilinear"])
+    ap.add_argument("--preprocess", default="model", choices=["model", "reference"],
+                    help="model (default): the file's own preprocessing where it carries one (resize, centre crop, mean / std as the model's publisher defines "
+                         "them), the reference's otherwise; reference: the reference's stretch to img_size^2 with --interp and ImageNet mean / std for any file")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--dir", default=None, help="accuracy harness: walk DIR/<label>/* and report top-1 against the directory name")
     ap.add_argument("--batch", type=int, default=256, help="images per forward in --dir mode")
@@ -93,6 +102,17 @@ def main(argv: List[str] | None = None) -> int:
         print(f"main: --img-size {a.img_size} is not a positive multiple of the patch size {model.hparams.patch_size}", file=sys.stderr)
         return 1
     S = a.img_size or model.img_size                     # the context's size: preprocess, maps and features follow it
+    if a.preprocess == "model" and model.has_preproc:
+        pp = model.preproc()
+        if S != model.img_size:
+            try:
+                pp = binding.preproc_at_size(pp, S)
+            except binding.VitxError as e:
+                print(f"main: the model's preprocessing has no form at --img-size {S}: {e}", file=sys.stderr)
+                return 1
+        preprocess = lambda img: binding.preprocess_ex(img, pp)
+    else:
+        preprocess = lambda img: binding.preprocess(img, S, interp)
     geometry = dict(img_size=a.img_size, pos_interp=binding.POS_BICUBIC_AA if a.pos_interp == "bicubic-aa" else binding.POS_BICUBIC) if a.img_size else {}
 
     if a.dir is None:
@@ -102,7 +122,11 @@ def main(argv: List[str] | None = None) -> int:
             print(f"main: failed to load image from '{a.inp}': {e}", file=sys.stderr)
             return 1
         print(f"main: loaded image '{a.inp}' ({img0.shape[1]} x {img0.shape[0]})", file=sys.stderr)
-        img1 = binding.preprocess(img0, S, interp)
+        try:
+            img1 = preprocess(img0)
+        except binding.VitxError as e:
+            print(f"main: failed to preprocess '{a.inp}': {e}", file=sys.stderr)
+            return 1
         print(f"processed, out dims : ({S} x {S})", file=sys.stderr)
         try:
             ctx = binding.Context(model, device=a.device, max_batch=1, dtype=dt, **geometry)
@@ -159,7 +183,7 @@ def main(argv: List[str] | None = None) -> int:
     t0 = time.perf_counter()
     for lo in range(0, len(files), ctx.max_batch):
         chunk = files[lo:lo + ctx.max_batch]
-        batch = np.stack([binding.preprocess(_decode(f), S, interp) for f in chunk])
+        batch = np.stack([preprocess(_decode(f)) for f in chunk])
         pred = ctx.forward(batch).argmax(1)
         if a.embed:
             rows.append(last(ctx).copy())

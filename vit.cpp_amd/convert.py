@@ -30,7 +30,16 @@ before the file type's rounding.  mask_token is dropped.  SwiGLU, qk-norm, fc_no
 At another input size transformers 5.x resamples the DINOv2-with-registers position table with antialias=True, so `--pos-interp bicubic-aa`
 reproduces it (plain Dinov2 and ViT: `bicubic`).
 
-    python -m ... convert.py <hf_model_dir_or_name> <out.gguf> [--ftype 1] [--no-head]
+The model's own preprocessing travels with it: for a HuggingFace checkpoint directory the `preprocessor_config.json` beside the weights is read
+(hf_preproc: `do_resize` / `size` {"shortest_edge"} or {"height", "width"}, `resample` 2 = PIL bilinear or 3 = PIL bicubic, `do_center_crop` /
+`crop_size`, `image_mean`, `image_std`, `do_rescale` with the usual 1/255) and written as the file's `preproc` tensor directly after `arch`
+(include/vitx.h "each model's own preprocessing"), with mean255 = f32(255.0 * mean).  Anything the engine's preprocess cannot honour -- another
+resample code, do_resize off, padding, a channel flip, a final size that is not the model's -- is an error that names the field; --no-preproc writes
+the file without the tensor (the reference's stretch and ImageNet mean / std then apply, as before).  A timm state dict carries no processor:
+--pp-resize N (shortest edge), --pp-crop N, --pp-filter, --pp-mean, --pp-std and --pp-crop-round state one; with none of them given no tensor is
+written and the reference's files keep their bytes.
+
+    python -m ... convert.py <hf_model_dir_or_name> <out.gguf> [--ftype 1] [--no-head] [--no-preproc]
     python -m ... convert.py --timm-state-dict <checkpoint.pth> <out.gguf> [--ftype 1] [--heads H] [--labels labels.json] [--act erf] [--eps 1e-6]
 
 A timm state dict carries no config, so --act {tanh,erf,quick} and --eps state its settings; without them the file is the reference's (tanh-GELU,
@@ -42,7 +51,8 @@ from typing import Dict
 
 import numpy as np
 
-from .ggml_file import HParams, write_model
+from .ggml_file import (HParams, write_model, preproc_slots, preproc_fields, IMAGENET_MEAN, IMAGENET_STD,
+                        PP_STRETCH, PP_SHORTEST_EDGE, PP_PIL_BILINEAR, PP_PIL_BICUBIC)
 
 
 ACT_TANH, ACT_ERF, ACT_QUICK = 0, 1, 2          # enum vitx_activation
@@ -69,6 +79,97 @@ def with_arch(tensors: Dict[str, np.ndarray], activation: int, eps: float) -> Di
     out = {"arch": np.array([activation, eps32, 0, 0], np.float32)}
     out.update(tensors)
     return out
+
+
+def _square(v, field: str):
+    """A processor's size entry -- {"height": h, "width": w}, [h, w] or an int -- as (width, height)."""
+    if isinstance(v, dict) and "height" in v and "width" in v:
+        return int(v["width"]), int(v["height"])
+    if isinstance(v, (list, tuple)) and len(v) == 2:
+        return int(v[1]), int(v[0])
+    if isinstance(v, int) and not isinstance(v, bool):
+        return v, v
+    raise ValueError(f"preprocessor_config: {field} = {v!r} is not a height / width pair")
+
+
+def hf_preproc(cfg: dict, img_size: int) -> np.ndarray:
+    """The 16 slots of the `preproc` tensor from a HuggingFace preprocessor_config.json (a dict), for a model that takes img_size^2 images.
+    Defaults are the image processors' own: do_resize, do_rescale and do_normalize on, do_center_crop off.  A legacy integer `size` is the
+    shortest edge when the processor centre-crops (CLIP's) and a square otherwise (ViT's).  Whatever the engine cannot honour raises a
+    ValueError that names the field."""
+    for field in ("do_pad", "do_flip_channel_order", "do_color_quantize", "do_reduce_labels"):
+        if cfg.get(field):
+            raise ValueError(f"preprocessor_config: {field} = {cfg[field]!r} is not supported")
+    if cfg.get("do_convert_rgb") is False and cfg.get("image_mode") not in (None, "RGB"):
+        raise ValueError(f"preprocessor_config: do_convert_rgb is off for {cfg.get('image_mode')!r} images; the engine decodes every file to RGB")
+    if not cfg.get("do_rescale", True):
+        raise ValueError("preprocessor_config: do_rescale = False is not supported (pixels are scaled by 1/255 before mean / std)")
+    rf = cfg.get("rescale_factor", 1.0 / 255.0)
+    if abs(float(rf) * 255.0 - 1.0) > 1e-6:
+        raise ValueError(f"preprocessor_config: rescale_factor = {rf!r} is not the usual 1/255")
+    if not cfg.get("do_resize", True):
+        raise ValueError("preprocessor_config: do_resize = False is not supported (the engine's preprocess always resizes)")
+    if "resample" not in cfg or cfg["resample"] not in (2, 3):
+        raise ValueError(f"preprocessor_config: resample = {cfg.get('resample')!r}: 2 (PIL bilinear) and 3 (PIL bicubic) are supported")
+    filt = PP_PIL_BILINEAR if cfg["resample"] == 2 else PP_PIL_BICUBIC
+    crop = 0
+    if cfg.get("do_center_crop", False):
+        if "crop_size" not in cfg:
+            raise ValueError("preprocessor_config: do_center_crop without crop_size")
+        cw, ch = _square(cfg["crop_size"], "crop_size")
+        if cw != ch:
+            raise ValueError(f"preprocessor_config: crop_size = {cfg['crop_size']!r} is not square")
+        crop = cw
+    size = cfg.get("size")
+    if isinstance(size, dict) and "shortest_edge" in size and "height" not in size:
+        if "longest_edge" in size:
+            raise ValueError(f"preprocessor_config: size = {size!r}: a longest_edge bound is not supported")
+        mode, a, b = PP_SHORTEST_EDGE, int(size["shortest_edge"]), 0
+    elif isinstance(size, int) and not isinstance(size, bool) and crop:
+        mode, a, b = PP_SHORTEST_EDGE, size, 0
+    elif size is not None:
+        mode = PP_STRETCH
+        a, b = _square(size, "size")
+    else:
+        raise ValueError("preprocessor_config: size is missing")
+    if mode == PP_SHORTEST_EDGE and not crop:
+        raise ValueError(f"preprocessor_config: size = {size!r} without do_center_crop gives images of the source's aspect; the model takes {img_size} x {img_size}")
+    if crop:
+        if crop != img_size:
+            raise ValueError(f"preprocessor_config: crop_size = {cfg['crop_size']!r}, the model takes {img_size} x {img_size}")
+        if crop > a or (mode == PP_STRETCH and crop > b):
+            raise ValueError(f"preprocessor_config: crop_size = {cfg['crop_size']!r} is larger than size = {size!r} (padding is not supported)")
+    elif (a, b) != (img_size, img_size):
+        raise ValueError(f"preprocessor_config: size = {size!r}, the model takes {img_size} x {img_size}")
+    if cfg.get("do_normalize", True):
+        mean, std = cfg.get("image_mean"), cfg.get("image_std")
+        for field, v in (("image_mean", mean), ("image_std", std)):
+            if not isinstance(v, (list, tuple)) or len(v) != 3:
+                raise ValueError(f"preprocessor_config: {field} = {v!r} is not one value per RGB channel")
+        if not all(np.isfinite(np.float32(255.0 * x)) and np.float32(255.0 * x) > 0 for x in std):
+            raise ValueError(f"preprocessor_config: image_std = {std!r} is not finite and positive")
+    else:
+        mean, std = (0.0, 0.0, 0.0), (1.0, 1.0, 1.0)          # out = q / 255
+    return preproc_slots(mode, a, b, filt, crop=crop, crop_round=0, mean=mean, std=std)
+
+
+def cli_preproc(img_size: int, resize: int = 0, crop: int = 0, filt: str = "", mean=None, std=None, crop_round: str = ""):
+    """The `preproc` slots of a timm checkpoint from the --pp-* options (torchvision's Resize(N) + CenterCrop(M) + Normalize on PIL images);
+    None when none of them is given.  resize: the shortest edge (default: the crop); crop: the centre crop (default: the model's img_size)."""
+    if not (resize or crop or filt or mean or std or crop_round):
+        return None
+    crop = crop or img_size
+    if crop != img_size:
+        raise ValueError(f"--pp-crop {crop}: the model takes {img_size} x {img_size}")
+    resize = resize or crop
+    if resize < crop:
+        raise ValueError(f"--pp-resize {resize} is smaller than the crop {crop} (padding is not supported)")
+    if (filt or "bicubic") not in ("bilinear", "bicubic"):
+        raise ValueError(f"--pp-filter {filt!r}: bilinear or bicubic")
+    if (crop_round or "floor") not in ("floor", "torchvision"):
+        raise ValueError(f"--pp-crop-round {crop_round!r}: floor or torchvision")
+    return preproc_slots(PP_SHORTEST_EDGE, resize, 0, PP_PIL_BILINEAR if filt == "bilinear" else PP_PIL_BICUBIC, crop=crop,
+                         crop_round=1 if crop_round == "torchvision" else 0, mean=mean or IMAGENET_MEAN, std=std or IMAGENET_STD)
 
 
 def state_dict_to_timm(sd: Dict[str, np.ndarray], num_layers: int) -> Dict[str, np.ndarray]:
@@ -187,16 +288,20 @@ def clip_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, no_head: bool = Fals
     return {k: np.ascontiguousarray(np.asarray(v, np.float32)) for k, v in out.items()}
 
 
-def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_head: bool = False) -> HParams:
+def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_head: bool = False, preprocessor_config: dict | None = None) -> HParams:
     """model: transformers.ViTForImageClassification, Dinov2ForImageClassification, Dinov2WithRegistersForImageClassification,
     CLIPVisionModelWithProjection or CLIPModel (eval); with no_head=True a Dinov2Model / Dinov2WithRegistersModel backbone or a CLIPVisionModel.
-    The activation and the LayerNorm epsilon are the config's (with_arch).  Writes `path`; returns the hparams written.
+    The activation and the LayerNorm epsilon are the config's (with_arch).  preprocessor_config: the checkpoint's preprocessor_config.json as a
+    dict -- its preprocessing is written as the `preproc` tensor (hf_preproc); None writes the file without one.  Writes `path`; returns the hparams written.
     vitstr=True: the model is a ViTSTR scene-text recogniser (/root/reference/extensions/vitstr.cpp/convert-pth-to-ggml.py: a ViT with ONE
     input channel whose classifier is applied to the first 25 tokens); the file then carries the character set as labels, and the
     one-channel patch kernel is what makes vit_model_load / vitx_model_load treat it as a ViTSTR model (vitstr.cpp:482)."""
     cfg = model.config
     if getattr(cfg, "model_type", "") == "clip":
         cfg = cfg.vision_config
+    if vitstr and preprocessor_config is not None:
+        raise ValueError("a ViTSTR model's preprocessing is fixed: convert it without a preprocessor_config")
+    pp = (lambda img_size: hf_preproc(preprocessor_config, img_size)) if preprocessor_config is not None else (lambda img_size: None)
     if vitstr and getattr(cfg, "num_channels", 3) != 1:
         raise ValueError("a ViTSTR model takes one (grey) input channel")
     hd = cfg.hidden_size // cfg.num_attention_heads
@@ -214,7 +319,7 @@ def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_
         E = int(tensors["head.weight"].shape[0])
         hp = HParams(cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, E, cfg.patch_size, g * cfg.patch_size, ftype)
         id2label = {0: "(no head)"} if no_head else {i: f"dim_{i}" for i in range(E)}
-        write_model(path, hp, with_arch(tensors, act, eps), id2label=id2label, ftype=ftype)
+        write_model(path, hp, with_arch(tensors, act, eps), id2label=id2label, ftype=ftype, preproc=pp(hp.img_size))
         return hp
     if getattr(cfg, "model_type", "") in ("dinov2", "dinov2_with_registers"):
         if vitstr:
@@ -225,7 +330,7 @@ def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_
             raise ValueError(f"position_embeddings {tensors['pos_embed'].shape}: not 1 + a square grid")
         hp = HParams(cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, int(tensors["head.weight"].shape[0]), cfg.patch_size, g * cfg.patch_size, ftype)
         id2label = {0: "(no head)"} if no_head else ({int(k): str(v) for k, v in (getattr(cfg, "id2label", None) or {}).items()} or None)
-        write_model(path, hp, with_arch(tensors, act, eps), id2label=id2label, ftype=ftype)
+        write_model(path, hp, with_arch(tensors, act, eps), id2label=id2label, ftype=ftype, preproc=pp(hp.img_size))
         return hp
     if no_head:
         raise ValueError("no_head converts a DINOv2 backbone (Dinov2Model, Dinov2WithRegistersModel) or a CLIPVisionModel")
@@ -237,7 +342,7 @@ def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_
         if cfg.num_labels != len(VITSTR_LABELS):
             raise ValueError(f"ViTSTR's character set has {len(VITSTR_LABELS)} classes ([GO], [s], 94 printable characters), the model has {cfg.num_labels}")
         id2label = dict(VITSTR_LABELS)
-    write_model(path, hp, with_arch(tensors, act, eps), id2label=id2label, ftype=ftype)
+    write_model(path, hp, with_arch(tensors, act, eps), id2label=id2label, ftype=ftype, preproc=pp(hp.img_size))
     return hp
 
 
@@ -245,7 +350,7 @@ _TIMM_UNSUPPORTED = {"fc_norm.": "fc_norm", "dist_token": "a distillation token"
                      "attn_pool.": "attention pooling"}
 
 
-def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2label=None, act: str = "tanh", eps: float = 1e-6) -> HParams:
+def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2label=None, act: str = "tanh", eps: float = 1e-6, preproc: dict | None = None) -> HParams:
     """sd: a timm VisionTransformer state_dict (name -> array / tensor), e.g. torch.load("vit_base_patch16_224.pth").  Mirrors
     /root/reference/convert-pth-to-ggml.py:96-158 without importing timm: hidden size, depth, classes, patch and image size come from the
     tensor shapes (the reference reads them off the timm module), `norm_pre.*` is skipped exactly as there (:117-120), the ViTSTR
@@ -256,7 +361,9 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
     the file has no slot for (fc_norm, distillation tokens, qk-norm, attention pooling) are refused here, by name.
     A state dict carries no config: `act` ("tanh", "erf", "quick") and `eps` state the model's activation and LayerNorm epsilon.  The default
     (tanh, 1e-6) writes the reference's file, without `arch`, as this function always has; a checkpoint of timm's VisionTransformer was trained
-    with nn.GELU and wants act="erf" (eps 1e-6 is timm's too)."""
+    with nn.GELU and wants act="erf" (eps 1e-6 is timm's too).
+    preproc: the keyword arguments of cli_preproc (resize, crop, filt, mean, std, crop_round) -- the checkpoint's preprocessing, written as the
+    `preproc` tensor; None or all unset: no tensor, the file is what this function always wrote."""
     if act not in _ACT_NAMES:
         raise ValueError(f"act {act!r}: one of {sorted(_ACT_NAMES)}")
     sd = {k: v for k, v in (sd.get("model", sd) if isinstance(sd, dict) and "model" in sd and not hasattr(sd["model"], "shape") else sd).items()}
@@ -315,7 +422,9 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
     expected = 4 + 12 * L + 4 + (1 if "reg_token" in t else 0)
     if len(t) != expected:
         raise ValueError(f"{len(t)} tensors after filtering, the file format holds exactly {expected} for {L} layers (vit.cpp:512-574)")
-    write_model(path, hp, with_arch(t, _ACT_NAMES[act], eps), id2label=id2label, ftype=ftype)
+    if cin == 1 and preproc and cli_preproc(hp.img_size, **preproc) is not None:
+        raise ValueError("a ViTSTR model's preprocessing is fixed: the --pp-* options do not apply")
+    write_model(path, hp, with_arch(t, _ACT_NAMES[act], eps), id2label=id2label, ftype=ftype, preproc=cli_preproc(hp.img_size, **preproc) if preproc else None)
     return hp
 
 
@@ -337,7 +446,18 @@ def main(argv=None) -> int:
     ap.add_argument("--pos-interp", default="bicubic", choices=["bicubic", "bicubic-aa"],
                     help="with --img-size: F.interpolate(mode='bicubic') without (HuggingFace ViT / Dinov2, DINO) or with antialias=True (timm; "
                          "transformers 5.x for Dinov2WithRegisters)")
+    ap.add_argument("--no-preproc", action="store_true", help="write the file without the `preproc` tensor even when a preprocessor_config.json lies beside the model")
+    ap.add_argument("--pp-resize", type=int, default=0, metavar="N", help="timm checkpoint: Resize(N), the shortest edge (default: the crop)")
+    ap.add_argument("--pp-crop", type=int, default=0, metavar="N", help="timm checkpoint: CenterCrop(N) (default and only value: the model's img_size)")
+    ap.add_argument("--pp-filter", default="", choices=["", "bilinear", "bicubic"], help="timm checkpoint: Pillow's resize filter (default bicubic)")
+    ap.add_argument("--pp-mean", type=float, nargs=3, default=None, metavar=("R", "G", "B"), help="timm checkpoint: Normalize mean on the 0..1 scale (default ImageNet's)")
+    ap.add_argument("--pp-std", type=float, nargs=3, default=None, metavar=("R", "G", "B"), help="timm checkpoint: Normalize std on the 0..1 scale (default ImageNet's)")
+    ap.add_argument("--pp-crop-round", default="", choices=["", "floor", "torchvision"],
+                    help="timm checkpoint: the crop offset of an odd difference: floor (default; transformers) or torchvision (CenterCrop rounds half to even)")
     a = ap.parse_args(argv)
+    pp_cli = dict(resize=a.pp_resize, crop=a.pp_crop, filt=a.pp_filter, mean=a.pp_mean, std=a.pp_std, crop_round=a.pp_crop_round)
+    if not a.timm_state_dict and any(pp_cli.values()):
+        ap.error("--pp-* describe a timm checkpoint (--timm-state-dict); a HuggingFace checkpoint brings its preprocessor_config.json")
 
     def resized(hp):
         """The converted file is written at the checkpoint's size first, then replaced by its --img-size version."""
@@ -358,7 +478,7 @@ def main(argv=None) -> int:
         import torch
         sd = torch.load(a.model, map_location="cpu", weights_only=True)
         labels = {int(k): str(v) for k, v in json.load(open(a.labels)).items()} if a.labels else None
-        hp = resized(convert_timm_state_dict(sd, a.out, a.ftype, heads=a.heads, id2label=labels, act=a.act, eps=a.eps))
+        hp = resized(convert_timm_state_dict(sd, a.out, a.ftype, heads=a.heads, id2label=labels, act=a.act, eps=a.eps, preproc=None if a.no_preproc else pp_cli))
         print(f"wrote {a.out}: hidden {hp.hidden_size}, layers {hp.num_hidden_layers}, heads {hp.num_attention_heads}, classes {hp.num_classes}, patch {hp.patch_size}, img {hp.img_size}, ftype {a.ftype}")
         return 0
     import transformers
@@ -369,7 +489,17 @@ def main(argv=None) -> int:
         m = (transformers.CLIPVisionModel if a.no_head else transformers.CLIPVisionModelWithProjection).from_pretrained(a.model).eval()
     else:
         m = transformers.ViTForImageClassification.from_pretrained(a.model).eval()
-    hp = resized(convert_hf_model(m, a.out, a.ftype, vitstr=a.vitstr, no_head=a.no_head))
+    import json
+    import os
+    pc_path = os.path.join(a.model, "preprocessor_config.json")
+    pc = None
+    if not a.no_preproc and not a.vitstr:
+        if os.path.isfile(pc_path):
+            with open(pc_path) as f:
+                pc = json.load(f)
+        else:
+            print(f"note: no preprocessor_config.json beside '{a.model}': the file is written without a `preproc` tensor")
+    hp = resized(convert_hf_model(m, a.out, a.ftype, vitstr=a.vitstr, no_head=a.no_head, preprocessor_config=pc))
     print(f"wrote {a.out}: hidden {hp.hidden_size}, layers {hp.num_hidden_layers}, heads {hp.num_attention_heads}, classes {hp.num_classes}, patch {hp.patch_size}, img {hp.img_size}, ftype {a.ftype}")
     return 0
 

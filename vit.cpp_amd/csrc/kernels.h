@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/vitx.h"
+
 namespace vitx {
 
 enum { DT_F16 = 0, DT_BF16 = 1 };
@@ -202,6 +204,10 @@ bool layernorm_supports(int D);
 hipError_t launch_softmax(int dtype, const float *logits, float *probs, int rows, int cols, int ld, hipStream_t stream);
 // u8 HWC [n][ny][nx][3] -> f32 HWC [n][S][S][3], resized and normalised (image_preprocess.hip; bit for bit the host version in preprocess.cpp)
 hipError_t launch_preprocess(const void *u8, float *out, int n, int nx, int ny, int S, int bicubic, hipStream_t stream);
+// the same by a description (include/vitx.h vitx_preproc): the reference's resize with its mean / std, or Pillow's resize + centre crop, one launch.
+// hipErrorInvalidValue for an invalid description or source, or a down-scale whose tile does not fit the LDS (preprocess_ex_supports)
+hipError_t launch_preprocess_ex(const vitx_preproc &p, const void *u8, float *out, int n, int nx, int ny, hipStream_t stream);
+bool preprocess_ex_supports(const vitx_preproc &p, int nx, int ny);
 // out[row][k] = {f32 probability, i32 class} of the k largest entries of probs[row][0..cols), descending, ties by the lower class index
 // (softmax_topk.hip; the sort of vit_predict, vit.cpp:1043-1057, on the device: the multi-GPU gather then moves 8 k bytes per row instead of 4 cols)
 hipError_t launch_topk(const float *probs, int rows, int cols, int k, void *out_pairs, hipStream_t stream);

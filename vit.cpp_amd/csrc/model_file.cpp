@@ -150,7 +150,7 @@ static int load_impl(const char *path, vitx_model &m) {
         m.id2label[key] = v;
     }
     const auto expect = expected_tensors(hp);
-    int n_optional = 0;                                              // `arch`, `pre_norm.*` records seen
+    int n_optional = 0;                                              // `arch`, `preproc`, `pre_norm.*` records seen
     for (;;) {
         int32_t n_dims, name_len, ttype;
         if (!rd_i32(n_dims)) break;                                  // clean EOF (vit.cpp:600-603)
@@ -190,6 +190,24 @@ static int load_impl(const char *path, vitx_model &m) {
             if (!(a[1] > 0.0f) || !(a[1] <= 3.402823466e38f)) { set_error("vitx_model_load: tensor 'arch' carries LayerNorm eps %g: it must be finite and positive", (double)a[1]); return VITX_ERR_FORMAT; }
             if (a[2] != 0.0f || a[3] != 0.0f) { set_error("vitx_model_load: tensor 'arch' has reserved slots {%g, %g}: they must be 0", (double)a[2], (double)a[3]); return VITX_ERR_FORMAT; }
             m.activation = (int)a[0]; hp.eps = a[1];
+            m.index[t.name] = (int)m.tensors.size();
+            m.tensors.push_back(std::move(t));
+            ++n_optional;
+            continue;
+        }
+        if (t.name == "preproc") {                                   // optional: f32 [16], the model's own preprocessing (include/vitx.h "each model's own preprocessing")
+            if (m.index.count(t.name)) { set_error("vitx_model_load: duplicate tensor '%s'", t.name.c_str()); return VITX_ERR_FORMAT; }
+            if (ttype != T_F32 || n_dims != 1 || t.ne[0] != 16) {
+                set_error("vitx_model_load: tensor 'preproc' must be f32 [16]: got type %d, %d dims [%lld, ..]", ttype, n_dims, (long long)t.ne[0]);
+                return VITX_ERR_FORMAT;
+            }
+            t.raw.resize(64);
+            if (fread(t.raw.data(), 1, 64, f) != 64) { set_error("vitx_model_load: tensor '%s' is truncated", t.name.c_str()); return VITX_ERR_IO; }
+            float a[16]; memcpy(a, t.raw.data(), 64);
+            if (const char *bad = pp_from_slots(a, m.preproc)) { set_error("vitx_model_load: tensor 'preproc': %s", bad); return VITX_ERR_FORMAT; }
+            const int side = m.preproc.crop ? m.preproc.crop : m.preproc.resize_a;
+            if (side != hp.img_size) { set_error("vitx_model_load: tensor 'preproc' describes a %d x %d output, the model takes %d x %d", side, side, hp.img_size, hp.img_size); return VITX_ERR_FORMAT; }
+            m.has_preproc = true;
             m.index[t.name] = (int)m.tensors.size();
             m.tensors.push_back(std::move(t));
             ++n_optional;
@@ -241,6 +259,8 @@ static int load_impl(const char *path, vitx_model &m) {
         return VITX_ERR_FORMAT;
     }
     m.has_pre_norm = m.find("pre_norm.weight") != nullptr;
+    if (m.has_preproc && m.in_chans == 1) { set_error("vitx_model_load: tensor 'preproc' in a one-channel (ViTSTR) file: its preprocessing is fixed"); return VITX_ERR_FORMAT; }
+    if (!m.has_preproc) m.preproc = pp_default(hp.img_size);
     const size_t n_expect = expect.size() + (m.num_registers ? 1 : 0) + (size_t)n_optional;
     if (m.tensors.size() != n_expect) {
         set_error("vitx_model_load: model file has %d tensors, but %d tensors were expected", (int)m.tensors.size(), (int)n_expect);
@@ -286,6 +306,11 @@ int vitx_model_num_registers(const vitx_model *m) { return m ? m->num_registers 
 int vitx_model_head_pool(const vitx_model *m) { return m ? m->head_pool : 0; }
 int vitx_model_activation(const vitx_model *m) { return m ? m->activation : 0; }
 int vitx_model_has_pre_norm(const vitx_model *m) { return m && m->has_pre_norm ? 1 : 0; }
+int vitx_model_has_preproc(const vitx_model *m) { return m && m->has_preproc ? 1 : 0; }
+int vitx_model_preproc(const vitx_model *m, vitx_preproc *out) {
+    if (!m || !out) return VITX_ERR_ARG;
+    *out = m->preproc; return VITX_OK;
+}
 int vitx_model_seq_len(const vitx_model *m) { return (m && m->in_chans == 1) ? VITX_VITSTR_SEQ_LEN : 0; }
 const char *vitx_model_label(const vitx_model *m, int id) {
     if (!m) return nullptr;

@@ -35,6 +35,8 @@ struct vitx_model {
     int head_pool = VITX_POOL_CLS;                    // VITX_POOL_CLS_MEAN: head.weight is [C][2 D], over concat(cls, mean of the patch tokens)
     int activation = VITX_ACT_GELU_TANH;              // MLP activation, from an optional `arch` [4] = {activation, eps, 0, 0}; hp.eps carries its eps
     bool has_pre_norm = false;                        // `pre_norm.weight` / `pre_norm.bias` [D]: LayerNorm of every token row in front of layer 0
+    bool has_preproc = false;                         // `preproc` [16]: the model's own preprocessing (include/vitx.h); without it `preproc` is the reference default
+    vitx_preproc preproc;
     std::map<int, std::string> id2label;
     std::vector<vitx::HostTensor> tensors;            // file order
     std::map<std::string, int> index;                 // name -> position
@@ -49,4 +51,9 @@ void set_error(const char *fmt, ...);
 float f16_bits_to_f32(uint16_t h);
 uint16_t f32_to_f16_bits(float f);     // round-to-nearest-even
 uint16_t f32_to_bf16_bits(float f);    // round-to-nearest-even
+// the `preproc` tensor (preprocess.cpp): the reference default at img_size; description <-> the 16 f32 slots (pp_from_slots: nullptr = fine,
+// else what is wrong with the slots or the description)
+vitx_preproc pp_default(int img_size);
+void pp_to_slots(const vitx_preproc &p, float slots[16]);
+const char *pp_from_slots(const float slots[16], vitx_preproc &p);
 }  // namespace vitx

@@ -3,6 +3,7 @@
 #include <initializer_list>
 
 #include "context.h"
+#include "preproc_resample.h"
 
 // A launcher's hipError_t -> the entry point's return code, with "<name>: <hip string>" as the error text.  `invalid`: the code that
 // hipErrorInvalidValue (the launchers' "no instantiation for this shape") maps to -- each entry point keeps the mapping it always had
@@ -262,6 +263,19 @@ int vitx_op_attention_map(int dtype, const void *d_qkv, long lo_off, void *d_cls
     return op_rc("vitx_op_attention_map", e);
 }
 
+int vitx_preprocess_ex_device_supports(const vitx_preproc *pp, int nx, int ny) { return pp && preprocess_ex_supports(*pp, nx, ny) ? 1 : 0; }
+int vitx_preprocess_ex_device(const vitx_preproc *pp, const void *d_hwc, int n, int nx, int ny, void *d_out, void *stream) {
+    if (!pp || !d_hwc || !d_out || n <= 0) { set_error("vitx_preprocess_ex_device: invalid argument"); return VITX_ERR_ARG; }
+    PpGeom g;
+    const char *bad = pp_check(*pp);
+    if (!bad) bad = pp_geometry(*pp, nx, ny, g);
+    if (bad) { set_error("vitx_preprocess_ex_device: %s", bad); return VITX_ERR_ARG; }
+    if (!preprocess_ex_supports(*pp, nx, ny)) {
+        set_error("vitx_preprocess_ex_device: a %d x %d source resized to %d x %d needs more than 64 KiB of LDS per tile (use vitx_preprocess_ex)", nx, ny, g.W, g.H);
+        return VITX_ERR_UNSUPPORTED;
+    }
+    return op_rc("vitx_preprocess_ex_device", launch_preprocess_ex(*pp, d_hwc, (float *)d_out, n, nx, ny, (hipStream_t)stream));
+}
 int vitx_preprocess_u8_device(const void *d_hwc, int n, int nx, int ny, int img_size, int interp, void *d_out, void *stream) {
     if (!d_hwc || !d_out || n <= 0 || nx <= 0 || ny <= 0 || img_size <= 0) { set_error("vitx_preprocess_u8_device: invalid argument"); return VITX_ERR_ARG; }
     if (interp != VITX_BICUBIC && interp != VITX_BILINEAR) { set_error("vitx_preprocess_u8_device: interpolation mode %d is not supported", interp); return VITX_ERR_ARG; }

@@ -52,11 +52,19 @@ extern "C" int vitx_model_resize_file(const char *path_in, const char *path_out,
     if (rc != VITX_OK) return rc;
     const vitx_hparams hp = m->hp;
     const int in_chans = m->in_chans;
+    const bool has_preproc = m->has_preproc;
+    const vitx_preproc pp_in = m->preproc;
     std::vector<float> pos;
     if (const HostTensor *t = m->find("pos_embed")) { pos.resize((size_t)t->nelements()); t->decode_f32(pos.data()); }
     vitx_model_free(m);
     if (img_size % hp.patch_size) { set_error("vitx_model_resize_file: img_size %d is not a multiple of the patch size %d", img_size, hp.patch_size); return VITX_ERR_ARG; }
     if (in_chans == 1 && img_size != hp.img_size) { set_error("vitx_model_resize_file: a ViTSTR file stays at its own img_size (%d)", hp.img_size); return VITX_ERR_UNSUPPORTED; }
+    float pp_slots[16] = {0};
+    if (has_preproc) {                                                // the model's preprocessing follows the size (vitx_preproc_at_size)
+        vitx_preproc pp_out;
+        if ((rc = vitx_preproc_at_size(&pp_in, img_size, &pp_out))) return rc;
+        pp_to_slots(pp_out, pp_slots);
+    }
     const int g_in = hp.img_size / hp.patch_size, g_out = img_size / hp.patch_size, D = hp.hidden_size;
     std::vector<float> res(((size_t)g_out * g_out + 1) * D);
     if ((rc = vitx_pos_embed_resample(pos.data(), g_in, g_in, D, g_out, g_out, interp, res.data()))) return rc;
@@ -100,6 +108,8 @@ extern "C" int vitx_model_resize_file(const char *path_in, const char *path_out,
             int32_t head[3] = {n_dims, name_len, ttype};
             ne[1] = g_out * g_out + 1;
             put(head, 12); put(ne, 4 * (size_t)n_dims); put(&in[name_at], (size_t)name_len); put(res.data(), res.size() * 4);
+        } else if (has_preproc && nbytes == sizeof(pp_slots) && std::string((const char *)&in[name_at], (size_t)name_len) == "preproc") {
+            put(&in[rec], data_at - rec); put(pp_slots, sizeof(pp_slots));
         } else put(&in[rec], data_at + nbytes - rec);
     }
     if (fclose(f) != 0) ok = false;

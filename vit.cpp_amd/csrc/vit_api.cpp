@@ -57,6 +57,18 @@ bool vit_image_preprocess(const image_u8 &img, image_f32 &res, const vit_hparams
     return vitx_preprocess_u8(img.data.data(), img.nx, img.ny, S, interp, res.data.data()) == VITX_OK;
 }
 
+// No counterpart in the reference: the file's own preprocessing (vitx_model_preproc), at the file's size or at another one
+bool vit_image_preprocess_model(const image_u8 &img, image_f32 &res, const vit_model &model, int img_size) {
+    vitx_preproc pp;
+    if (!model.handle || vitx_model_preproc(model.handle, &pp) != VITX_OK) { fprintf(stderr, "%s: no model is loaded\n", __func__); return false; }
+    if (img_size > 0 && img_size != model.hparams.img_size && vitx_preproc_at_size(&pp, img_size, &pp) != VITX_OK) { fprintf(stderr, "%s: %s\n", __func__, vitx_last_error()); return false; }
+    const int S = pp.crop ? pp.crop : pp.resize_a;
+    res.nx = S; res.ny = S;
+    res.data.resize((size_t)3 * S * S);
+    if (vitx_preprocess_ex(&pp, img.data.data(), img.nx, img.ny, res.data.data()) != VITX_OK) { fprintf(stderr, "%s: %s\n", __func__, vitx_last_error()); return false; }
+    return true;
+}
+
 // The reference's vit_state carries no weights and can be reused with any model; ours caches a context that does, so the cache
 // is keyed on the unique id of the parsed model it was built from (vit_model_load frees and replaces that handle on every call).
 // The input side a state's context takes: vit_state::img_size, or the file's when that is 0

@@ -17,6 +17,8 @@ Two optional extensions the reference's loader cannot read (include/vitx.h "regi
 [1][R][D] directly after cls_token, and a `head.weight` of [C][2 D].  Magic and hparams are unchanged; both are read off the shapes.
 Two more ("activation, epsilon and pre-norm"): `arch` f32 [4] = {activation, eps, 0, 0}, written first, and `pre_norm.weight` / `pre_norm.bias`
 f32 [D] directly after pos_embed.  All three are 1-D, so write_model stores them in f32 like every other vector, in the order it is given them.
+One more ("each model's own preprocessing"): `preproc` f32 [16] = {resize_mode, resize_a, resize_b, filter, crop, crop_round, mean255 r g b, std255
+r g b, 0, 0, 0, 0}, directly after `arch` (first without it): preproc_slots builds it, write_model(preproc=) places it, ModelFile.preproc reads it.
 """
 from __future__ import annotations
 
@@ -64,6 +66,52 @@ class ModelFile:
     hparams: HParams
     id2label: Dict[int, str] = field(default_factory=dict)
     tensors: List[TensorRec] = field(default_factory=list)
+
+    @property
+    def preproc(self):
+        """The `preproc` tensor as a dict of vitx_preproc's fields (mean255 / std255: float32 triples); None for a file without it."""
+        for t in self.tensors:
+            if t.name == "preproc":
+                return preproc_fields(np.frombuffer(t.raw, "<f4", 16))
+        return None
+
+
+# --------------------------------------------------------------------------- the `preproc` tensor
+PP_REF_BICUBIC, PP_REF_BILINEAR, PP_PIL_BILINEAR, PP_PIL_BICUBIC = 0, 1, 2, 3      # enum vitx_pp_filter
+PP_STRETCH, PP_SHORTEST_EDGE = 0, 1                                                # enum vitx_pp_resize
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+def preproc_slots(resize_mode: int, resize_a: int, resize_b: int, filter: int, crop: int = 0, crop_round: int = 0,
+                  mean=IMAGENET_MEAN, std=IMAGENET_STD, mean255=None, std255=None) -> np.ndarray:
+    """The 16 f32 slots of the `preproc` tensor.  mean / std are the publisher's (on the 0..1 scale): the slots hold f32(255.0 * m), the
+    values the arithmetic uses; mean255 / std255 give them directly."""
+    m = np.asarray(mean255, np.float32) if mean255 is not None else (255.0 * np.asarray(mean, np.float64)).astype(np.float32)
+    s = np.asarray(std255, np.float32) if std255 is not None else (255.0 * np.asarray(std, np.float64)).astype(np.float32)
+    if m.shape != (3,) or s.shape != (3,):
+        raise ValueError("mean and std hold one value per RGB channel")
+    return np.concatenate([np.array([resize_mode, resize_a, resize_b, filter, crop, crop_round], np.float32), m, s, np.zeros(4, np.float32)])
+
+
+def preproc_fields(slots) -> dict:
+    a = np.asarray(slots, np.float32).reshape(16)
+    return dict(resize_mode=int(a[0]), resize_a=int(a[1]), resize_b=int(a[2]), filter=int(a[3]), crop=int(a[4]), crop_round=int(a[5]),
+                mean255=tuple(a[6:9]), std255=tuple(a[9:12]))
+
+
+def with_preproc(tensors: Dict[str, np.ndarray], slots) -> Dict[str, np.ndarray]:
+    """`tensors` with the `preproc` tensor directly after `arch` (in front without one); slots None: unchanged."""
+    if slots is None:
+        return tensors
+    slots = np.asarray(slots, np.float32).reshape(16)
+    out: Dict[str, np.ndarray] = {}
+    if "arch" not in tensors:
+        out["preproc"] = slots
+    for k, v in tensors.items():
+        out[k] = v
+        if k == "arch":
+            out["preproc"] = slots
+    return out
 
 
 # --------------------------------------------------------------------------- block encoders
@@ -203,13 +251,15 @@ def dequantize(ttype: int, raw: bytes, n: int) -> np.ndarray:
 
 # --------------------------------------------------------------------------- write / read
 def write_model(path: str, hp: HParams, tensors: Dict[str, np.ndarray], id2label: Dict[int, str] | None = None,
-                ftype: int = 1, patch_f16: bool = True, registers: int | None = None, head_pool: int | None = None) -> None:
+                ftype: int = 1, patch_f16: bool = True, registers: int | None = None, head_pool: int | None = None, preproc=None) -> None:
     """Write torch-shaped f32 tensors (timm state_dict naming) as the reference converter does:
     1-D tensors, pos_embed and cls_token stay f32; everything else f16 when ftype>=1
     (convert-pth-to-ggml.py:141-148).  ftype in {2,3,6,7,8} additionally quantises the 2-D
     '*weight' tensors exactly like quantize.cpp:207-303 does to an f16 file.
     registers / head_pool (optional) state what the caller means to write -- R register tokens (`reg_token` [1][R][D], f32, directly
-    after cls_token) and the head kind (0 class token: head.weight [C][D]; 1 cls + mean: [C][2 D]) -- and are checked against `tensors`."""
+    after cls_token) and the head kind (0 class token: head.weight [C][D]; 1 cls + mean: [C][2 D]) -- and are checked against `tensors`.
+    preproc (optional): the 16 slots of the `preproc` tensor (preproc_slots), written directly after `arch`; None writes the file without it."""
+    tensors = with_preproc(tensors, preproc)
     D = hp.hidden_size
     have_r = int(np.shape(tensors["reg_token"])[1]) if "reg_token" in tensors else 0
     if "reg_token" in tensors:

@@ -20,6 +20,7 @@ from .ggml_file import HParams, write_model
 CONFIGS = {
     # name: (hidden, layers, heads, classes, patch, img)
     "vit_micro_patch16_64": (128, 2, 2, 10, 16, 64),       # test-only toy (N=17)
+    "vit_nano_patch16_32": (64, 2, 1, 10, 16, 32),         # test-only toy of the preprocessing tests: 2 x 2 patches (N = 5), one head of 64
     "vit_micro_patch14_56": (128, 2, 2, 10, 14, 56),       # test-only toy at DINOv2's patch size (16 patches: N = 17, or 21 with 4 register tokens)
     "vit_base_patch14_224": (768, 12, 12, 1000, 14, 224),  # DINOv2 ViT-B/14 (257 tokens, 261 with 4 register tokens)
     "vit_micro_c37_patch16_64": (128, 2, 2, 37, 16, 64),   # test-only toy with an ODD class count (the head GEMM's last column group is ragged)
@@ -102,24 +103,29 @@ def make_weights(hp: HParams, seed: int = 1234, head_scale: float = 8.0, in_chan
     return t
 
 
-def write_synthetic(path: str, name: str, ftype: int = 1, seed: int = 1234, head_scale: float = 8.0, registers: int = 0, head_pool: int = 0) -> HParams:
+def write_synthetic(path: str, name: str, ftype: int = 1, seed: int = 1234, head_scale: float = 8.0, registers: int = 0, head_pool: int = 0,
+                    preproc=None) -> HParams:
+    """preproc: the 16 slots of a `preproc` tensor (ggml_file.preproc_slots) for the file to carry; None = a file without one."""
     hp = hparams_for(name, ftype)
     ic = IN_CHANS.get(name, 3)
     write_model(path, hp, make_weights(hp, seed, head_scale, in_chans=ic, registers=registers, head_pool=head_pool), ftype=ftype,
-                id2label=dict(VITSTR_LABELS) if ic == 1 else None, registers=registers, head_pool=head_pool)
+                id2label=dict(VITSTR_LABELS) if ic == 1 else None, registers=registers, head_pool=head_pool, preproc=preproc)
     return hp
 
 
 def cached_synthetic(name: str, ftype: int = 1, seed: int = 1234, head_scale: float = 8.0, cache_dir: str | None = None, registers: int = 0,
-                     head_pool: int = 0) -> str:
+                     head_pool: int = 0, preproc=None) -> str:
     """Write (once) and return the path of a synthetic model file under a scratch dir."""
     cache_dir = cache_dir or os.environ.get("VITX_CACHE", "/tmp/vitx_cache")
     os.makedirs(cache_dir, exist_ok=True)
     ext = (f"-r{registers}" if registers else "") + ("-pool" if head_pool else "")
+    if preproc is not None:
+        import hashlib
+        ext += "-pp" + hashlib.sha1(np.asarray(preproc, "<f4").tobytes()).hexdigest()[:10]
     path = os.path.join(cache_dir, f"{name}-s{seed}-h{head_scale:g}-ft{ftype}{ext}.gguf")
     if not os.path.exists(path):
         tmp = path + f".tmp{os.getpid()}"
-        write_synthetic(tmp, name, ftype, seed, head_scale, registers, head_pool)
+        write_synthetic(tmp, name, ftype, seed, head_scale, registers, head_pool, preproc)
         os.replace(tmp, path)
     return path
 

@@ -87,6 +87,11 @@ bool load_image_from_file(const std::string &fname, image_u8 &img);             
 bool vit_model_load(const std::string &fname, vit_model &model);                                       // vit.h:120
 // resizes to params.img_size, whatever it is: for a state at another size than the file's, pass a copy of model.hparams with img_size = state.img_size
 bool vit_image_preprocess(const image_u8 &img, image_f32 &res, const vit_hparams &params);            // vit.h:119
+// NEW, no counterpart in the reference: the preprocessing the MODEL FILE describes (include/vitx.h "each model's own preprocessing": CLIP's and
+// DINOv2's shortest-edge resize + centre crop, HuggingFace ViT's stretch, each with Pillow's filter and the publisher's mean / std).  A file
+// without a description gets vit_image_preprocess with bicubic interpolation: the reference's own files are preprocessed as always.
+// img_size 0 = the file's; else the side of the images a state with that vit_state::img_size takes (vitx_preproc_at_size).
+bool vit_image_preprocess_model(const image_u8 &img, image_f32 &res, const vit_model &model, int img_size = 0);
 int vit_predict(const vit_model &model, vit_state &state, const image_f32 img1, const vit_params &params,
                 std::vector<std::pair<float, int>> &predictions);                                      // vit.h:122
 int vit_predict_batch(const vit_model &model, vit_state &state, const image_f32 *imgs, int n, const vit_params &params,
