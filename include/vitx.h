@@ -124,9 +124,40 @@ int vitx_model_seq_len(const vitx_model *m);
  * keeps the class-rows-only last layer.  ViTSTR (one-channel) files with either extension, and VITX_MXFP8 contexts of such files, are
  * VITX_ERR_UNSUPPORTED at context creation.
  * LayerScale needs no slot: the converter folds it into attn.proj / mlp.fc2 (convert.py). */
-enum vitx_head_pool { VITX_POOL_CLS = 0, VITX_POOL_CLS_MEAN = 1 };
+enum vitx_head_pool { VITX_POOL_CLS = 0, VITX_POOL_CLS_MEAN = 1, VITX_POOL_MAP = 2 };
 int vitx_model_num_registers(const vitx_model *m);   /* R; 0 without reg_token (and for NULL) */
-int vitx_model_head_pool(const vitx_model *m);       /* enum vitx_head_pool, from head.weight's shape */
+int vitx_model_head_pool(const vitx_model *m);       /* enum vitx_head_pool, from head.weight's shape and the presence of attn_pool.* */
+/* ---- no class token and the attention-pooling head (SigLIP-class models) --------
+ * One more optional extension, recognised by the presence of the thirteen `attn_pool.*` tensors (timm's AttentionPoolLatent names; transformers'
+ * SiglipMultiheadAttentionPoolingHead), written after norm.bias and before head.*: VITX_POOL_MAP.
+ *   attn_pool.latent [1][1][D] f32; attn_pool.q.weight [D][D], .q.bias [D]; attn_pool.kv.weight [2 D][D], .kv.bias [2 D] (K rows first, then V);
+ *   attn_pool.proj.weight [D][D], .proj.bias [D]; attn_pool.norm.weight, .norm.bias [D]; attn_pool.mlp.fc1.weight [4 D][D], .fc1.bias [4 D];
+ *   attn_pool.mlp.fc2.weight [D][4 D], .fc2.bias [D].  Vectors are f32, matrices f32 or f16: they are never block-quantised (vitx_quantize_file
+ *   copies all thirteen through byte for byte).
+ * Such a file has NO cls_token and no reg_token, and its pos_embed is [1][g^2][D]: it holds 3 + 12 L + 2 + 13 + 2 tensors.  VITX_ERR_FORMAT:
+ * attn_pool.* together with a class or register token (or a [C][2 D] head); a missing class token without attn_pool.*; a partial set, a wrong
+ * shape or type, a duplicate; a pos_embed whose row count does not fit.  head.weight stays [C][D], over the pooled embedding e.
+ * Token layout: an image is its g^2 patch rows, patch t + pos_embed[t]; N = g^2, T = vitx_model_num_prefix = 0.
+ * Textbook definition, F[t] = the f32 final-norm row of token t (the F of "image embeddings and token features", unrounded), d = D / H:
+ *   q = Wq latent + bq;  k_t = Wk F[t] + bk;  v_t = Wv F[t] + bv;  per head h: p_h = softmax_t(q_h . k_{t,h} / sqrt(d)), o_h = sum_t p_{h,t} v_{t,h};
+ *   a = Wproj o + bproj;  e = a + fc2(act(fc1(LN(a)))) with the file's activation and eps.  e [D] is the pooled embedding.
+ * What the engine evaluates (identical in exact arithmetic):
+ *   at context creation, on the host, in double from vitx_model_tensor_f32's decode: u_h = Wk_h^T q_h / sqrt(d), stored as f32 [H][D]
+ *     (vitx_model_pool_query returns it).  q_h . bk_h is constant over t and cancels in the softmax: kv.bias's K half never reaches the device;
+ *   the pooling kernel (attention_pool.hip): s_{h,t} = u_h . F[t], p_h = softmax_t(s_h), M_h = sum_t p_{h,t} F[t], all in f32, M is [n][H][D];
+ *   o_h = Wv_h RNE(M_h) + bv_h (RNE to the operand type, as every GEMM operand is rounded; uses sum_t p = 1): H launches of the short-M GEMM,
+ *     head h reads M[:, h, :] and writes columns h d .. (h + 1) d;
+ *   proj (a stays f32), LayerNorm, fc1 + activation, fc2 + residual on n rows through the GEMM dispatcher and the LayerNorm launcher; e stays f32;
+ *   the head GEMM's operand is RNE(e).
+ * A VITX_POOL_MAP context evaluates every row of the last layer, exactly as a VITX_POOL_CLS_MEAN context does.  Features: VITX_FEAT_CLS is the
+ * f32 pooled embedding e (the last layer only: any other layer in the mask is VITX_ERR_ARG; RNE(e) equals the head operand bit for bit);
+ * VITX_FEAT_MEAN and VITX_FEAT_TOKENS cover all N rows; VITX_FEAT_L2 applies as before.
+ * VITX_ERR_UNSUPPORTED: ViTSTR files with the extension and VITX_MXFP8 contexts of such files (at context creation); vitx_attn_enable on such a
+ * context (the maps are defined by the class-token row, which does not exist); a context at another img_size than the file's and
+ * vitx_model_resize_file of such a file (the g^2-row position table has no resampling path yet). */
+int vitx_model_num_prefix(const vitx_model *m);      /* tokens in front of the patches: 0 for a VITX_POOL_MAP file, 1 + R otherwise (0 for NULL) */
+/* u [H][D] f32 of a VITX_POOL_MAP file (above); host only.  VITX_ERR_ARG for NULL or a file without the head. */
+int vitx_model_pool_query(const vitx_model *m, float *out /* [H][D] */);
 /* ---- activation, epsilon and pre-norm (HuggingFace ViT, timm, DINOv2, CLIP) ----
  * Two more optional extensions of the file, recognised by tensor name and shape; magic and the seven hparams are unchanged:
  *   `arch`         f32 [4] = {activation, eps, 0, 0}.  activation: enum vitx_activation, the function between mlp.fc1 and mlp.fc2
@@ -222,7 +253,8 @@ int vitx_model_tensor_f32(const vitx_model *m, int index, float *out, size_t n_e
  * (2 q4_0, 3 q4_1, 6 q5_0, 7 q5_1, 8 q8_0), byte-identical to what the reference's offline
  * `quantize` tool writes (quantize.cpp:34-353: header ftype, label order, which tensors, block
  * encoders).  Host only.  VITX_ERR_ARG for another ftype, VITX_ERR_FORMAT if already quantised.
- * Files with the extensions above pass through: reg_token is copied, a [C][2 D] head is quantised like any 2-D "*weight". */
+ * Files with the extensions above pass through: reg_token is copied, a [C][2 D] head is quantised like any 2-D "*weight", the thirteen
+ * attn_pool.* tensors are copied byte for byte (the selection over the reference's own tensors stays the reference's). */
 int vitx_quantize_file(const char *path_in, const char *path_out, int ftype);
 
 /* ---- image files (replaces load_image_from_file = stbi_load(..., 3), vit.cpp:109-127) ---- */
@@ -611,7 +643,15 @@ int vitx_op_attention_map(int dtype, const void *d_qkv, long lo_off, void *d_cls
  * vitx_op_patch_embed: the forward's patch-embedding kernel on its own.  TEST ONLY: it allocates, uploads and synchronises.  d_img f32
  *   [n_img][S][S][Cin]; d_w f32 [D][Cin * P * P] in the file's (channel-major) order -- rounded to `dtype`, permuted and padded inside as the
  *   context does at upload; d_bias [D], d_pos [1 + (S/P)^2][D], d_cls [D], d_reg [R][D] (NULL when R == 0), all f32; d_X f32
- *   [n_img * ((S/P)^2 + 1 + R)][D] receives the token rows in the layout above and nothing beyond them. */
+ *   [n_img * ((S/P)^2 + 1 + R)][D] receives the token rows in the layout above and nothing beyond them.
+ * vitx_op_features_ex also takes first = 0 (a model without prefix tokens: VITX_POOL_MAP): d_mean / d_tokens cover rows 0 .. N-1; d_cls and d_z
+ *   are then VITX_ERR_ARG (there is no class row).  vitx_op_patch_embed takes d_cls == NULL with R == 0: no prefix row is written, patch t
+ *   takes d_pos[t] (d_pos [(S/P)^2][D]) and d_X is [n_img * (S/P)^2][D].
+ * vitx_op_attention_pool: the pooling kernel of a VITX_POOL_MAP head on its own (device pointers; only enqueues).  Row t of image i is read at
+ *   d_x + i * img_stride + t * row_stride (floats); d_ln_w, d_ln_b [D] and eps are the final norm; d_u [H][D] f32; d_M [n_img][H][D] f32 receives
+ *   M_h; d_p (may be NULL) [n_img][H][N] f32 receives p_h.  Every width of the LayerNorm table, 1 <= H <= 32, any N >= 1.  No atomics: an image's
+ *   M is a function of its own rows, N, D and H only -- the same bits at any batch size and position.  NULL inputs, n_img, N < 1, H outside
+ *   1 .. 32, pointers not 16-byte aligned or strides not multiples of 4 floats: VITX_ERR_ARG; a width without an instantiation: VITX_ERR_UNSUPPORTED. */
 #define VITX_FEAT_CLS 1
 #define VITX_FEAT_MEAN 2
 #define VITX_FEAT_TOKENS 4
@@ -629,6 +669,8 @@ int vitx_op_features_ex(const void *d_x, long row_stride, long img_stride, const
                         int n_img, int N, int first, int D, float eps, int l2, void *d_z, int dtype, void *stream);
 int vitx_op_patch_embed(int dtype, const void *d_img, const void *d_w, const void *d_bias, const void *d_pos, const void *d_cls, const void *d_reg, int R,
                         void *d_X, int n_img, int S, int P, int Cin, int D, void *stream);
+int vitx_op_attention_pool(const void *d_x, long row_stride, long img_stride, const void *d_ln_w, const void *d_ln_b, float eps, const void *d_u, void *d_M,
+                           void *d_p /* [n_img][H][N] or NULL */, int n_img, int N, int D, int H, void *stream);
 
 /* ---- MXFP8 operands (VITX_MXFP8, encoding above) ------------------------------- */
 /* Host encoder: x f32 [rows][K] -> q [rows][k_pad] e4m3 bytes + scales [rows][k_pad / 32] (k_pad >= K, a multiple of 32; columns

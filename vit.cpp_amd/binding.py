@@ -28,7 +28,7 @@ GEMM_AUTO, GEMM_PP, GEMM_AUTO_SPLIT = 0, 1, 2          # vitx_op_gemm_ex `kernel
 ATTN_AUTO, ATTN_SINGLE, ATTN_FLOW, ATTN_PERSIST, ATTN_STREAM = 0, 1, 3, 4, 5   # vitx_op_attention_ex `kernel`
 ATTN_ROLLOUT = 1                # vitx_attn_enable flag
 FEAT_CLS, FEAT_MEAN, FEAT_TOKENS, FEAT_L2 = 1, 2, 4, 8      # vitx_feat_enable flags
-POOL_CLS, POOL_CLS_MEAN = 0, 1          # vitx_model_head_pool: the head reads the class token, or concat(cls, mean of the patch tokens)
+POOL_CLS, POOL_CLS_MEAN, POOL_MAP = 0, 1, 2      # vitx_model_head_pool: the head reads the class token, concat(cls, mean of the patch tokens), or the attention-pooled embedding
 PP_REF_BICUBIC, PP_REF_BILINEAR, PP_PIL_BILINEAR, PP_PIL_BICUBIC = 0, 1, 2, 3      # vitx_pp_filter: the reference's two, Pillow's Image.resize on u8
 PP_STRETCH, PP_SHORTEST_EDGE = 0, 1     # vitx_pp_resize
 POS_BICUBIC, POS_BICUBIC_AA = 0, 1      # vitx_pos_interp: F.interpolate(mode="bicubic") without / with antialias=True (include/vitx.h)
@@ -48,6 +48,7 @@ EXPORTS = [
     "vitx_model_num_registers", "vitx_model_head_pool", "vitx_ctx_registers", "vitx_op_features_ex", "vitx_op_patch_embed",
     "vitx_model_activation", "vitx_model_has_pre_norm", "vitx_op_layernorm_f32",
     "vitx_model_preproc", "vitx_model_has_preproc", "vitx_preproc_at_size", "vitx_preprocess_ex", "vitx_preprocess_ex_device", "vitx_preprocess_ex_device_supports",
+    "vitx_model_num_prefix", "vitx_model_pool_query", "vitx_op_attention_pool",
 ]
 
 
@@ -208,6 +209,10 @@ def lib():
             L.vitx_preprocess_ex.argtypes = [pp, C.POINTER(C.c_uint8), ip, ip, C.POINTER(C.c_float)]
             L.vitx_preprocess_ex_device.argtypes = [pp, vp, ip, ip, ip, vp, vp]
             L.vitx_preprocess_ex_device_supports.argtypes = [pp, ip, ip]
+        if hasattr(L, "vitx_model_num_prefix"):
+            L.vitx_model_num_prefix.argtypes = [vp]
+            L.vitx_model_pool_query.argtypes = [vp, C.POINTER(C.c_float)]
+            L.vitx_op_attention_pool.argtypes = [vp, C.c_long, C.c_long, vp, vp, C.c_float, vp, vp, vp, ip, ip, ip, ip, vp]
         _lib = L
     return _lib
 
@@ -250,6 +255,17 @@ class Model:
     @property
     def head_pool(self) -> int:                                                     # POOL_CLS, or POOL_CLS_MEAN for a [C][2 D] head
         return lib().vitx_model_head_pool(self._h) if hasattr(lib(), "vitx_model_head_pool") else 0
+    @property
+    def num_prefix(self) -> int:                                                    # tokens in front of the patches: 1 + registers, or 0 for a POOL_MAP file
+        return lib().vitx_model_num_prefix(self._h) if hasattr(lib(), "vitx_model_num_prefix") else 1 + self.num_registers
+
+    def pool_query(self) -> np.ndarray:
+        """vitx_model_pool_query: u [H, D] f32 of a POOL_MAP file, u_h = Wk_h^T q_h / sqrt(d) (the probe folded through the K projection)."""
+        hp = self.hparams
+        u = np.empty((hp.num_attention_heads, hp.hidden_size), np.float32)
+        check(lib().vitx_model_pool_query(self._h, u.ctypes.data_as(C.POINTER(C.c_float))), "vitx_model_pool_query")
+        return u
+
     @property
     def activation(self) -> int:                                                    # ACT_GELU_TANH / ACT_GELU_ERF / ACT_QUICK_GELU (the file's `arch`)
         return lib().vitx_model_activation(self._h) if hasattr(lib(), "vitx_model_activation") else 0
@@ -435,7 +451,7 @@ class Context:
         self.tokens = int(L.vitx_ctx_tokens(self._h)) if hasattr(L, "vitx_ctx_tokens") else (model.img_size // model.hparams.patch_size) ** 2 + 1
         self.grid = self.img_size // model.hparams.patch_size
         self.registers = int(L.vitx_ctx_registers(self._h)) if hasattr(L, "vitx_ctx_registers") else 0
-        self.prefix = 1 + self.registers              # tokens in front of the patches: the class token and the registers
+        self.prefix = model.num_prefix                # tokens in front of the patches: the class token and the registers (0 for a POOL_MAP model)
 
     def close(self):
         if getattr(self, "_h", None) and self._h:
@@ -697,8 +713,16 @@ def op_features_ex(d_x: int, row_stride: int, img_stride: int, d_w: int, d_b: in
 def op_patch_embed(dtype: int, d_img: int, d_w: int, d_bias: int, d_pos: int, d_cls: int, d_reg: int, R: int, d_X: int, n_img: int, S: int, P: int,
                    Cin: int, D: int, stream: int = 0) -> None:
     """vitx_op_patch_embed (test only; synchronous): the forward's patch-embedding kernel with R register rows per image.  d_w is the f32
-    kernel [D, Cin * P * P] in the file's order; every pointer is a device pointer to f32."""
-    check(lib().vitx_op_patch_embed(dtype, d_img, d_w, d_bias, d_pos, d_cls, d_reg or None, R, d_X, n_img, S, P, Cin, D, stream or None), "vitx_op_patch_embed")
+    kernel [D, Cin * P * P] in the file's order; every pointer is a device pointer to f32.  d_cls = 0 (R = 0): a model without a class token --
+    no prefix row, d_pos [(S/P)^2, D]."""
+    check(lib().vitx_op_patch_embed(dtype, d_img, d_w, d_bias, d_pos, d_cls or None, d_reg or None, R, d_X, n_img, S, P, Cin, D, stream or None), "vitx_op_patch_embed")
+
+
+def op_attention_pool(d_x: int, row_stride: int, img_stride: int, d_ln_w: int, d_ln_b: int, eps: float, d_u: int, d_M: int, d_p: int,
+                      n_img: int, N: int, D: int, H: int, stream: int = 0) -> None:
+    """vitx_op_attention_pool: the pooling kernel of the attention-pooling head (device pointers, strides in floats): M [n_img, H, D] f32 and,
+    with d_p, the probabilities [n_img, H, N] f32."""
+    check(lib().vitx_op_attention_pool(d_x, row_stride, img_stride, d_ln_w, d_ln_b, eps, d_u, d_M, d_p or None, n_img, N, D, H, stream or None), "vitx_op_attention_pool")
 
 
 def mx_k_pad(K: int) -> int:

@@ -18,6 +18,14 @@ cls_token, position_embedding -> pos_embed, the bias-free patch convolution gets
 pos_embed), q/k/v_proj are fused, post_layernorm -> norm, and the bias-free visual_projection [E][D] becomes head.weight with a zero head.bias:
 the file has E "classes" labelled dim_0 .. dim_{E-1}, its logits are CLIP's image_embeds and its probabilities mean nothing.
 
+SigLIP (SiglipVisionModel; SiglipModel: its vision tower): there is NO class token -- position_embedding [g^2][D] -> pos_embed [1][g^2][D] --, q/k/v_proj
+are fused, post_layernorm -> norm, and the multi-head attention-pooling head becomes the thirteen `attn_pool.*` tensors of include/vitx.h ("no
+class token and the attention-pooling head", timm's AttentionPoolLatent names): head.probe -> latent, head.attention.in_proj_weight / in_proj_bias are
+split into q (rows 0 .. D) and kv (rows D .. 3 D), out_proj -> proj, head.layernorm -> norm, head.mlp -> mlp.  A tower has no classifier: the file
+gets the one-class head of zeros labelled "(no head)" (--no-head is accepted and not required) and its pooled embedding -- SigLIP's pooler_output /
+image_embeds -- is read with --embed-kind cls / VITX_FEAT_CLS.  Refused by name: intermediate_size != 4 D (SO400M), vision_use_head = False,
+SiglipForImageClassification (a mean-pool classifier, no MAP head: no slot), Siglip2VisionModel (NaFlex: its patch embedding is a Linear).
+
 A timm checkpoint needs no `timm` either: its state_dict already carries the names the file format uses (the reference's converter
 writes `timm_model.state_dict()` verbatim, convert-pth-to-ggml.py:121-133), so `--timm-state-dict model.pth` loads the tensors with
 torch.load and derives the hyper-parameters the reference reads from the timm module (:96-103) from the tensor shapes.
@@ -288,6 +296,53 @@ def clip_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, no_head: bool = Fals
     return {k: np.ascontiguousarray(np.asarray(v, np.float32)) for k, v in out.items()}
 
 
+_POOL_ORDER = ("latent", "q.weight", "q.bias", "kv.weight", "kv.bias", "proj.weight", "proj.bias", "norm.weight", "norm.bias",
+               "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")
+
+
+def siglip_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg) -> Dict[str, np.ndarray]:
+    """Rename / fuse / split an HF SiglipVisionModel / SiglipModel state dict (numpy arrays) into the file's names and order (no cls_token; the
+    thirteen attn_pool.* tensors after norm.bias; the one-class head of zeros)."""
+    pre = next((p for p in ("vision_model.", "") if p + "embeddings.position_embedding.weight" in sd), None)
+    if pre is None:
+        raise ValueError("not a SigLIP vision state dict: embeddings.position_embedding.weight is missing")
+    if pre + "embeddings.patch_embedding.weight" not in sd or np.ndim(sd[pre + "embeddings.patch_embedding.weight"]) != 4:
+        raise ValueError("Siglip2VisionModel (NaFlex) is not supported: its patch embedding is a Linear over flattened patches, not a convolution")
+    D = int(cfg.hidden_size)
+    if getattr(cfg, "intermediate_size", 4 * D) != 4 * D:
+        raise ValueError(f"intermediate_size {cfg.intermediate_size}: the file format holds a 4 x hidden MLP (SO400M's 4304 is not supported)")
+    if getattr(cfg, "vision_use_head", True) is False or pre + "head.probe" not in sd:
+        raise ValueError("vision_use_head = False: the tower has no attention-pooling head, and the file format has no slot for a SigLIP tower without it")
+    out: Dict[str, np.ndarray] = {}
+    out["pos_embed"] = np.reshape(sd[pre + "embeddings.position_embedding.weight"], (1, -1, D))
+    out["patch_embed.proj.weight"] = sd[pre + "embeddings.patch_embedding.weight"]
+    out["patch_embed.proj.bias"] = sd[pre + "embeddings.patch_embedding.bias"]
+    for i in range(cfg.num_hidden_layers):
+        q, p = f"{pre}encoder.layers.{i}.", f"blocks.{i}."
+        qkv = [q + "self_attn." + n for n in ("q_proj", "k_proj", "v_proj")]
+        out[p + "norm1.weight"] = sd[q + "layer_norm1.weight"]; out[p + "norm1.bias"] = sd[q + "layer_norm1.bias"]
+        out[p + "attn.qkv.weight"] = np.concatenate([sd[n + ".weight"] for n in qkv], 0)
+        out[p + "attn.qkv.bias"] = np.concatenate([sd[n + ".bias"] for n in qkv], 0)
+        out[p + "attn.proj.weight"] = sd[q + "self_attn.out_proj.weight"]; out[p + "attn.proj.bias"] = sd[q + "self_attn.out_proj.bias"]
+        out[p + "norm2.weight"] = sd[q + "layer_norm2.weight"]; out[p + "norm2.bias"] = sd[q + "layer_norm2.bias"]
+        out[p + "mlp.fc1.weight"] = sd[q + "mlp.fc1.weight"]; out[p + "mlp.fc1.bias"] = sd[q + "mlp.fc1.bias"]
+        out[p + "mlp.fc2.weight"] = sd[q + "mlp.fc2.weight"]; out[p + "mlp.fc2.bias"] = sd[q + "mlp.fc2.bias"]
+    out["norm.weight"] = sd[pre + "post_layernorm.weight"]; out["norm.bias"] = sd[pre + "post_layernorm.bias"]
+    h = pre + "head."
+    w, b = np.asarray(sd[h + "attention.in_proj_weight"]), np.asarray(sd[h + "attention.in_proj_bias"])
+    if w.shape != (3 * D, D) or b.shape != (3 * D,):
+        raise ValueError(f"head.attention.in_proj_weight {w.shape}: expected [{3 * D}][{D}]")
+    out["attn_pool.latent"] = np.reshape(sd[h + "probe"], (1, 1, D))
+    out["attn_pool.q.weight"] = w[:D]; out["attn_pool.q.bias"] = b[:D]
+    out["attn_pool.kv.weight"] = w[D:]; out["attn_pool.kv.bias"] = b[D:]
+    out["attn_pool.proj.weight"] = sd[h + "attention.out_proj.weight"]; out["attn_pool.proj.bias"] = sd[h + "attention.out_proj.bias"]
+    out["attn_pool.norm.weight"] = sd[h + "layernorm.weight"]; out["attn_pool.norm.bias"] = sd[h + "layernorm.bias"]
+    out["attn_pool.mlp.fc1.weight"] = sd[h + "mlp.fc1.weight"]; out["attn_pool.mlp.fc1.bias"] = sd[h + "mlp.fc1.bias"]
+    out["attn_pool.mlp.fc2.weight"] = sd[h + "mlp.fc2.weight"]; out["attn_pool.mlp.fc2.bias"] = sd[h + "mlp.fc2.bias"]
+    out["head.weight"] = np.zeros((1, D), np.float32); out["head.bias"] = np.zeros((1,), np.float32)
+    return {k: np.ascontiguousarray(np.asarray(v, np.float32)) for k, v in out.items()}
+
+
 def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_head: bool = False, preprocessor_config: dict | None = None) -> HParams:
     """model: transformers.ViTForImageClassification, Dinov2ForImageClassification, Dinov2WithRegistersForImageClassification,
     CLIPVisionModelWithProjection or CLIPModel (eval); with no_head=True a Dinov2Model / Dinov2WithRegistersModel backbone or a CLIPVisionModel.
@@ -297,7 +352,12 @@ def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_
     input channel whose classifier is applied to the first 25 tokens); the file then carries the character set as labels, and the
     one-channel patch kernel is what makes vit_model_load / vitx_model_load treat it as a ViTSTR model (vitstr.cpp:482)."""
     cfg = model.config
-    if getattr(cfg, "model_type", "") == "clip":
+    cls_name = type(model).__name__
+    if cls_name.startswith("Siglip2") or getattr(cfg, "model_type", "").startswith("siglip2"):
+        raise ValueError(f"{cls_name} (Siglip2VisionModel, NaFlex) is not supported: its patch embedding is a Linear over flattened patches")
+    if cls_name == "SiglipForImageClassification":
+        raise ValueError("SiglipForImageClassification is not supported: it classifies the mean of the patch tokens and has no attention-pooling head (no slot for it)")
+    if getattr(cfg, "model_type", "") in ("clip", "siglip"):
         cfg = cfg.vision_config
     if vitstr and preprocessor_config is not None:
         raise ValueError("a ViTSTR model's preprocessing is fixed: convert it without a preprocessor_config")
@@ -321,6 +381,16 @@ def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_
         id2label = {0: "(no head)"} if no_head else {i: f"dim_{i}" for i in range(E)}
         write_model(path, hp, with_arch(tensors, act, eps), id2label=id2label, ftype=ftype, preproc=pp(hp.img_size))
         return hp
+    if getattr(cfg, "model_type", "") == "siglip_vision_model":
+        if vitstr:
+            raise ValueError("a SigLIP model is not a ViTSTR model")
+        tensors = siglip_state_dict_to_timm(sd, cfg)
+        g = int(round(tensors["pos_embed"].shape[1] ** 0.5))
+        if g * g != tensors["pos_embed"].shape[1]:
+            raise ValueError(f"position_embedding {tensors['pos_embed'].shape}: not a square grid")
+        hp = HParams(cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, 1, cfg.patch_size, g * cfg.patch_size, ftype)
+        write_model(path, hp, with_arch(tensors, act, eps), id2label={0: "(no head)"}, ftype=ftype, preproc=pp(hp.img_size))
+        return hp
     if getattr(cfg, "model_type", "") in ("dinov2", "dinov2_with_registers"):
         if vitstr:
             raise ValueError("a DINOv2 model is not a ViTSTR model")
@@ -333,7 +403,7 @@ def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_
         write_model(path, hp, with_arch(tensors, act, eps), id2label=id2label, ftype=ftype, preproc=pp(hp.img_size))
         return hp
     if no_head:
-        raise ValueError("no_head converts a DINOv2 backbone (Dinov2Model, Dinov2WithRegistersModel) or a CLIPVisionModel")
+        raise ValueError("no_head converts a DINOv2 backbone (Dinov2Model, Dinov2WithRegistersModel), a CLIPVisionModel or a SigLIP tower")
     hp = HParams(cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, cfg.num_labels, cfg.patch_size, cfg.image_size, ftype)
     tensors = state_dict_to_timm(sd, cfg.num_hidden_layers)
     id2label = {int(k): str(v) for k, v in (getattr(cfg, "id2label", None) or {}).items()} or None
@@ -347,7 +417,7 @@ def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_
 
 
 _TIMM_UNSUPPORTED = {"fc_norm.": "fc_norm", "dist_token": "a distillation token", "head_dist.": "a distillation head", ".q_norm.": "qk-norm", ".k_norm.": "qk-norm",
-                     "attn_pool.": "attention pooling"}
+                     "attn_pool.pos_embed": "a position embedding inside the attention pooling"}
 
 
 def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2label=None, act: str = "tanh", eps: float = 1e-6, preproc: dict | None = None) -> HParams:
@@ -358,7 +428,9 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
     by their one-channel patch kernel.  DINOv2-class checkpoints are taken: `blocks.N.ls1.gamma` / `ls2.gamma` (LayerScale) are folded into
     attn.proj / mlp.fc2 in f32, `reg_token` becomes the file's reg_token, and a `pos_embed` of g^2 rows (timm's no_embed_class layout of the
     reg4 DINOv2 models: the class token gets no position term there) gets a zero row in front, which is exact.  Models with other tensors
-    the file has no slot for (fc_norm, distillation tokens, qk-norm, attention pooling) are refused here, by name.
+    the file has no slot for (fc_norm, distillation tokens, qk-norm) are refused here, by name.  `attn_pool.*` (AttentionPoolLatent: SigLIP) is
+    taken, without cls_token only, as the file's attention-pooling head; its qk-norm and position embedding (attn_pool.q_norm / k_norm / pos_embed) are
+    refused by name; a checkpoint without head.* (num_classes 0) gets the one-class head of zeros.
     A state dict carries no config: `act` ("tanh", "erf", "quick") and `eps` state the model's activation and LayerNorm epsilon.  The default
     (tanh, 1e-6) writes the reference's file, without `arch`, as this function always has; a checkpoint of timm's VisionTransformer was trained
     with nn.GELU and wants act="erf" (eps 1e-6 is timm's too).
@@ -376,10 +448,27 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
             if u in k:
                 raise ValueError(f"tensor {k!r}: {what} is not supported (the file format has no slot for it)")
         t[k] = np.ascontiguousarray(np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, np.float32))
+    map_head = any(k.startswith("attn_pool.") for k in t)
+    if map_head:
+        if "cls_token" in t or "reg_token" in t:
+            raise ValueError("attn_pool.* beside cls_token / reg_token: the attention-pooling head is taken only from a model without a class token")
+        D = int(t["pos_embed"].shape[-1]) if "pos_embed" in t else 0
+        missing = [f"attn_pool.{n}" for n in _POOL_ORDER if f"attn_pool.{n}" not in t]
+        extra = [k for k in t if k.startswith("attn_pool.") and k[len("attn_pool."):] not in _POOL_ORDER]
+        if missing or extra:
+            raise ValueError(f"the attention-pooling head is not the thirteen tensors the file holds: missing {missing}, unknown {extra}")
+        if "head.weight" not in t:                        # num_classes 0: the zero head
+            t["head.weight"] = np.zeros((1, D), np.float32); t["head.bias"] = np.zeros((1,), np.float32)
+            id2label = id2label if id2label is not None else {0: "(no head)"}
+        t["attn_pool.latent"] = t["attn_pool.latent"].reshape(1, 1, D)
+        ordered: Dict[str, np.ndarray] = {k: v for k, v in t.items() if not k.startswith(("attn_pool.", "head."))}
+        ordered.update({f"attn_pool.{n}": t[f"attn_pool.{n}"] for n in _POOL_ORDER})
+        ordered.update({k: v for k, v in t.items() if k.startswith("head.")})
+        t = ordered
     for need in ("cls_token", "pos_embed", "patch_embed.proj.weight", "patch_embed.proj.bias", "norm.weight", "norm.bias", "head.weight", "head.bias"):
-        if need not in t:
+        if need not in t and not (map_head and need == "cls_token"):
             raise ValueError(f"not a timm VisionTransformer state_dict: {need!r} is missing")
-    D = int(t["cls_token"].shape[-1])
+    D = int(t["pos_embed"].shape[-1] if map_head else t["cls_token"].shape[-1])
     L = 1 + max(int(k.split(".")[1]) for k in t if k.startswith("blocks."))
     # LayerScale: folded, no file slot.  A model has it on both branches of every block or not at all: a partial set is a damaged checkpoint
     ls_keys = [f"blocks.{i}.{ls}.gamma" for i in range(L) for ls in ("ls1", "ls2")]
@@ -402,8 +491,8 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
         t = ordered
     Dw, cin, P, P2 = t["patch_embed.proj.weight"].shape
     n_tok = int(t["pos_embed"].shape[1])
-    g = int(round((n_tok - 1) ** 0.5))
-    if Dw != D or P != P2 or g * g + 1 != n_tok or cin not in (1, 3):
+    g = int(round((n_tok - (0 if map_head else 1)) ** 0.5))
+    if Dw != D or P != P2 or g * g + (0 if map_head else 1) != n_tok or cin not in (1, 3):
         raise ValueError(f"unexpected shapes: patch kernel {t['patch_embed.proj.weight'].shape}, pos_embed {t['pos_embed'].shape}")
     # The head count is NOT in a state_dict (the reference reads timm's module attribute, convert-pth-to-ggml.py): it is only inferred for
     # the widths of timm's released ViTs, where it is unambiguous; any other width needs --heads (r03 advisor: D // 64 silently turned
@@ -419,7 +508,7 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
         from .synth import VITSTR_LABELS
         if hp.num_classes == len(VITSTR_LABELS):
             id2label = dict(VITSTR_LABELS)
-    expected = 4 + 12 * L + 4 + (1 if "reg_token" in t else 0)
+    expected = 4 + 12 * L + 4 + (1 if "reg_token" in t else 0) + (12 if map_head else 0)
     if len(t) != expected:
         raise ValueError(f"{len(t)} tensors after filtering, the file format holds exactly {expected} for {L} layers (vit.cpp:512-574)")
     if cin == 1 and preproc and cli_preproc(hp.img_size, **preproc) is not None:
@@ -487,6 +576,9 @@ def main(argv=None) -> int:
         m = (transformers.AutoModel if a.no_head else transformers.AutoModelForImageClassification).from_pretrained(a.model).eval()
     elif model_type in ("clip", "clip_vision_model"):
         m = (transformers.CLIPVisionModel if a.no_head else transformers.CLIPVisionModelWithProjection).from_pretrained(a.model).eval()
+    elif model_type in ("siglip", "siglip_vision_model"):
+        m = transformers.SiglipVisionModel.from_pretrained(a.model).eval()
+        a.no_head = False                                      # a tower never has a classifier: the flag is accepted and not required
     else:
         m = transformers.ViTForImageClassification.from_pretrained(a.model).eval()
     import json

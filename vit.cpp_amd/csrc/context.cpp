@@ -103,6 +103,42 @@ int upload_quant(vitx_ctx *c, const HostTensor *t, int Nrows, int K, int n_pad, 
     return VITX_OK;
 }
 
+// The attention-pooling head (VITX_POOL_MAP; include/vitx.h): the folded probe u, the V half of kv.*, proj, norm, fc1, fc2.  The matrices are f32
+// or f16 in the file, never blocks.
+int upload_map_head(vitx_ctx *c) {
+    const vitx_model *m = c->model;
+    vitx_ctx::WeightSet &ws = *c->wset;
+    const int D = c->D, tn = c->tn;
+    int rc;
+    std::vector<float> u((size_t)c->H * D);
+    if ((rc = vitx_model_pool_query(m, u.data()))) return rc;
+    if ((rc = c->wmalloc((void **)&ws.map_u, u.size() * 4))) return rc;
+    HIP_TRY(hipMemcpy(ws.map_u, u.data(), u.size() * 4, hipMemcpyHostToDevice));
+    // V: rows D .. 2 D of kv.weight, elements D .. 2 D of kv.bias; 128 zero rows behind them: the value projection of the last head reads a whole column tile
+    const HostTensor *kvw = m->find("attn_pool.kv.weight"), *kvb = m->find("attn_pool.kv.bias");
+    std::vector<float> f((size_t)2 * D * D), fb((size_t)2 * D);
+    kvw->decode_f32(f.data()); kvb->decode_f32(fb.data());
+    const int v_pad = round_up(D, tn) + 128;
+    const std::vector<uint16_t> hv = operand_matrix_host(c->dtype, f.data() + (size_t)D * D, nullptr, D, D, v_pad, D, 0, 0);
+    if ((rc = c->wmalloc(&ws.map_v_w, hv.size() * 2))) return rc;
+    HIP_TRY(hipMemcpy(ws.map_v_w, hv.data(), hv.size() * 2, hipMemcpyHostToDevice));
+    ws.weight_bytes += hv.size() * 2;
+    std::vector<float> vb((size_t)v_pad, 0.0f);
+    std::copy(fb.begin() + D, fb.end(), vb.begin());
+    if ((rc = c->wmalloc((void **)&ws.map_v_b, vb.size() * 4))) return rc;
+    HIP_TRY(hipMemcpy(ws.map_v_b, vb.data(), vb.size() * 4, hipMemcpyHostToDevice));
+    auto T = [&](const char *n) { return m->find(n); };
+    if ((rc = upload_f32(c, T("attn_pool.proj.bias"), &ws.map_proj_b, round_up(D, tn)))) return rc;
+    if ((rc = upload_f32(c, T("attn_pool.norm.weight"), &ws.map_ln_w))) return rc;
+    if ((rc = upload_f32(c, T("attn_pool.norm.bias"), &ws.map_ln_b))) return rc;
+    if ((rc = upload_f32(c, T("attn_pool.mlp.fc1.bias"), &ws.map_fc1_b, round_up(4 * D, tn)))) return rc;
+    if ((rc = upload_f32(c, T("attn_pool.mlp.fc2.bias"), &ws.map_fc2_b, round_up(D, tn)))) return rc;
+    if ((rc = upload_matrix(c, T("attn_pool.proj.weight"), D, D, round_up(D, tn), D, &ws.map_proj_w))) return rc;
+    if ((rc = upload_matrix(c, T("attn_pool.mlp.fc1.weight"), 4 * D, D, round_up(4 * D, tn), D, &ws.map_fc1_w))) return rc;
+    if ((rc = upload_matrix(c, T("attn_pool.mlp.fc2.weight"), D, 4 * D, round_up(D, tn), 4 * D, &ws.map_fc2_w))) return rc;
+    return VITX_OK;
+}
+
 // vitx_ctx_create_ex, step 1: the options (all zero = every default) and the geometry they ask for are validated, then the context is made and
 // its fields are derived from them.  Every check keeps its place: the first one that fails is the one reported.
 int configure(const vitx_model *m, int device, int max_batch, int dtype, const vitx_ctx_options *opt_in, vitx_ctx_options &opt, std::unique_ptr<vitx_ctx> &c) {
@@ -117,8 +153,12 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
         set_error("vitx_ctx_create_ex: img_size %d is not a positive multiple of the patch size %d", opt.img_size, m->hp.patch_size); return VITX_ERR_ARG;
     }
     const int img_size = opt.img_size > 0 ? opt.img_size : m->hp.img_size;
-    if (m->in_chans == 1 && (m->num_registers || m->head_pool != VITX_POOL_CLS)) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes neither register tokens nor the pooled head"); return VITX_ERR_UNSUPPORTED; }
-    if (dtype == VITX_MXFP8 && (m->num_registers || m->head_pool != VITX_POOL_CLS)) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts do not take models with register tokens or the pooled head"); return VITX_ERR_UNSUPPORTED; }
+    if (m->in_chans == 1 && (m->num_registers || m->head_pool != VITX_POOL_CLS)) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes neither register tokens nor a pooled or attention-pooling head"); return VITX_ERR_UNSUPPORTED; }
+    if (dtype == VITX_MXFP8 && (m->num_registers || m->head_pool != VITX_POOL_CLS)) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts do not take models with register tokens, the pooled head or the attention-pooling head"); return VITX_ERR_UNSUPPORTED; }
+    if (m->head_pool == VITX_POOL_MAP && img_size != m->hp.img_size) {
+        set_error("vitx_ctx_create_ex: a model with the attention-pooling head stays at the file's img_size (%d): its position table has no class row and no resampling path yet", m->hp.img_size);
+        return VITX_ERR_UNSUPPORTED;
+    }
     if (m->in_chans == 1 && (m->has_pre_norm || m->activation != VITX_ACT_GELU_TANH)) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes neither a pre-norm nor an activation other than tanh-GELU"); return VITX_ERR_UNSUPPORTED; }
     if (dtype == VITX_MXFP8 && m->activation != VITX_ACT_GELU_TANH) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts evaluate tanh-GELU only (this model's activation: %d)", m->activation); return VITX_ERR_UNSUPPORTED; }
     if (m->in_chans == 1 && img_size != m->hp.img_size) { set_error("vitx_ctx_create_ex: a ViTSTR context stays at the file's img_size (%d)", m->hp.img_size); return VITX_ERR_UNSUPPORTED; }
@@ -138,7 +178,9 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
     c->D = hp.hidden_size; c->L = hp.num_hidden_layers; c->H = hp.num_attention_heads; c->C = hp.num_classes; c->P = hp.patch_size; c->S = img_size;
     c->Cin = m->in_chans; c->R = m->in_chans == 1 ? VITX_VITSTR_SEQ_LEN : 1;
     c->fc1_epi = act_epi(m->activation);
-    c->nreg = m->num_registers; c->Tp = 1 + c->nreg; c->pool = m->head_pool == VITX_POOL_CLS_MEAN;
+    c->nreg = m->num_registers; c->pool = m->head_pool == VITX_POOL_CLS_MEAN; c->map = m->head_pool == VITX_POOL_MAP;
+    c->Tp = c->map ? 0 : 1 + c->nreg;
+    if (c->map && c->H > kPoolMaxHeads) { set_error("vitx_ctx_create: the attention-pooling kernel takes at most %d heads (this model: %d)", kPoolMaxHeads, c->H); return VITX_ERR_UNSUPPORTED; }
     c->g = c->S / c->P; c->N = c->g * c->g + c->Tp; c->Kpe = c->Cin * c->P * c->P; c->Kpe_pad = round_up(c->Kpe, 64);
     if (c->N < c->R) { set_error("vitx_ctx_create: a ViTSTR head reads %d tokens, this model has %d (img_size %d, patch_size %d)", c->R, c->N, c->S, c->P); return VITX_ERR_UNSUPPORTED; }
     c->tm = gemm_tile_m(); c->tn = gemm_tile_n();
@@ -154,8 +196,8 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
     c->split_first = opt.split_first;
     c->prec_attn = dtype == VITX_F16 && c->D == c->H * 64 && !opt.f16_fast_attention;
     c->quant_on_device = !opt.quant_on_host;
-    // the pooled head averages every patch row of the last layer: such a context runs exactly as one created with last_layer_all_rows = 1
-    c->cls_tail = !opt.last_layer_all_rows && !c->pool && c->R == 1 && attention_cls_supports(c->N, c->D, c->H);
+    // the pooled head averages every patch row of the last layer, the attention-pooling head attends over them: such a context runs exactly as one created with last_layer_all_rows = 1
+    c->cls_tail = !opt.last_layer_all_rows && !c->pool && !c->map && c->R == 1 && attention_cls_supports(c->N, c->D, c->H);
     c->q4_fused_rows = opt.q4_fused_rows;
     c->graphs_on = opt.graph != 0;
     // fault injection for the parity tests: honoured only with the key in the upper half (VITX_LN_TEST_KEY | mode), so that no caller sets it by accident
@@ -192,7 +234,7 @@ int obtain_weights(vitx_ctx *c, int dtype) {
         c->wset = std::make_shared<vitx_ctx::WeightSet>();
         vitx_ctx::WeightSet &ws = *c->wset;
         ws.device = device;
-        if ((rc = upload_f32(c, T("cls_token"), &ws.cls))) return rc;
+        if (!c->map && (rc = upload_f32(c, T("cls_token"), &ws.cls))) return rc;
         if (c->nreg && (rc = upload_f32(c, T("reg_token"), &ws.reg))) return rc;
         if ((rc = upload_f32(c, T("pos_embed"), &ws.pos))) return rc;
         if (m->has_pre_norm && ((rc = upload_f32(c, T("pre_norm.weight"), &ws.pre_w)) || (rc = upload_f32(c, T("pre_norm.bias"), &ws.pre_b)))) return rc;
@@ -224,6 +266,7 @@ int obtain_weights(vitx_ctx *c, int dtype) {
         }
         if ((rc = upload_f32(c, T("norm.weight"), &ws.norm_w))) return rc;
         if ((rc = upload_f32(c, T("norm.bias"), &ws.norm_b))) return rc;
+        if (c->map && (rc = upload_map_head(c))) return rc;
         if ((rc = upload_f32(c, T("head.bias"), &ws.head_b, c->C_pad))) return rc;
         if ((rc = upload_weight(c, T("head.weight"), c->C, c->pool ? 2 * D : D, c->C_pad, &ws.head_w, &ws.head_q))) return rc;
         wreg[wkey] = c->wset;
@@ -256,7 +299,8 @@ int alloc_slice(vitx_ctx *c, vitx_ctx::Slice &sl, size_t hcols, bool internal) {
         sl.Umx_s = sl.Umx + Mpad * kp; sl.U2mx_s = sl.U2mx + Mpad * kp;
         sl.Hmx = (uint8_t *)sl.Hbuf; sl.Hmx_s = sl.Hmx + Mpad * kh;             // Mpad * kh * 33 / 32 <= Mpad * 4 D * 2 bytes of Hbuf
     }
-    if (c->cls_tail && (rc = c->dmalloc((void **)&sl.Xc, Bpad * D * 4, true))) return rc;
+    if ((c->cls_tail || c->map) && (rc = c->dmalloc((void **)&sl.Xc, Bpad * D * 4, true))) return rc;
+    if (c->map && (rc = c->dmalloc(&sl.Mp, Bpad * c->H * D * 2, true))) return rc;
     if ((rc = c->dmalloc((void **)&sl.logits, Bpad * c->C_pad * 4, true))) return rc;
     // expansion scratch for quantised matrices: one buffer per matrix kind, shared by all layers (the largest layer decides)
     for (int k = 0; k < W_PER_LAYER; ++k) {
@@ -302,7 +346,7 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
     c->pos = c->wset->pos;
     if (c->S != hp.img_size) {
         const int g_in = hp.img_size / hp.patch_size;
-        if ((rc = c->dmalloc((void **)&c->pos_own, (size_t)(c->g * c->g + 1) * D * 4, false))) return rc;
+        if ((rc = c->dmalloc((void **)&c->pos_own, (size_t)(c->g * c->g + 1) * D * 4, false))) return rc;      // (never a VITX_POOL_MAP model: configure refuses it)
         HIP_TRY(launch_pos_resample(c->wset->pos, g_in, g_in, D, c->g, c->g, opt.pos_interp, c->pos_own, c->stream));
         c->pos = c->pos_own;                 // (the hipDeviceSynchronize at the end of the creation covers the launch)
     }

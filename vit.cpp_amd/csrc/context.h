@@ -78,9 +78,10 @@ struct vitx_ctx {
     int R = 1;                           // probability rows per image: 1 (cls token) or 25 (ViTSTR: tokens 0..24, vitstr.cpp:864-904)
     // Token layout of an image (include/vitx.h "Register tokens and the pooled head"): row 0 = class token, rows 1 .. nreg = register tokens,
     // rows Tp .. N - 1 = patches in raster order; N = g * g + Tp
-    int nreg = 0, Tp = 1;                // register tokens of the model (reg_token), prefix tokens 1 + nreg
+    int nreg = 0, Tp = 1;                // register tokens of the model (reg_token), prefix tokens 1 + nreg (0 for a VITX_POOL_MAP model: no class token)
     int fc1_epi = EPI_BIAS_GELU;         // the fc1 epilogue of the model's activation (vitx_model_activation), taken once at creation
     bool pool = false;                   // VITX_POOL_CLS_MEAN: the head reads concat(cls, mean of the patch tokens) of the final norm, K = 2 D
+    bool map = false;                    // VITX_POOL_MAP: no class token; the head reads the attention-pooled embedding e (SliceForward::pooled_tail)
     int tm = 128, tn = 128;
     const Tuning *tune = nullptr;        // per-device launch parameters (CU count, kernel selection), immutable
     int split_first = 0;                 // vitx_ctx_options::split_first: images of the first of two sub-batches (0 = the tile-round model)
@@ -98,6 +99,10 @@ struct vitx_ctx {
         float *cls = nullptr, *reg = nullptr, *pos = nullptr, *pe_b = nullptr, *norm_w = nullptr, *norm_b = nullptr, *head_b = nullptr;
         void *pe_w = nullptr, *head_w = nullptr;
         QuantW head_q;
+        // VITX_POOL_MAP (attn_pool.*): u [H][D] f32 (the folded probe, vitx_model_pool_query); the V half of kv.weight / kv.bias, padded by 128 rows so that
+        // every head's [d][D] block can be read as a whole column tile; proj, norm, fc1, fc2 like a block's
+        float *map_u = nullptr, *map_v_b = nullptr, *map_proj_b = nullptr, *map_ln_w = nullptr, *map_ln_b = nullptr, *map_fc1_b = nullptr, *map_fc2_b = nullptr;
+        void *map_v_w = nullptr, *map_proj_w = nullptr, *map_fc1_w = nullptr, *map_fc2_w = nullptr;
         std::vector<LayerW> layers;
         size_t weight_bytes = 0;         // device bytes held by weight matrices (vitx_ctx_weight_bytes)
         ~WeightSet() {       // may run on any thread (the last context of the set): leave the caller's current device as it was
@@ -160,7 +165,8 @@ struct vitx_ctx {
         long qkv_lo_off = 0;
         void *Hbuf = nullptr;        // [Mpad][4D]  (also the im2col rows of the patch-embed GEMM)
         float *Xc = nullptr;         // [Bpad][D] f32 class-token rows of the residual stream through the last layer's tail (cls_tail)
-        void *Z = nullptr;           // [Bpad][D] final-LN output of the cls rows; pooled head: [Bpad][2 D] = RNE(cls) ‖ RNE(mean of the patch rows)
+        void *Z = nullptr;           // [Bpad][D] final-LN output of the cls rows; pooled head: [Bpad][2 D] = RNE(cls) ‖ RNE(mean of the patch rows); MAP head: RNE(e)
+        void *Mp = nullptr;          // VITX_POOL_MAP: [Bpad][H][D] RNE(M), the A operand of the value projection (Xc holds a, then e, in f32)
         // VITX_MXFP8: norm1 and norm2 outputs [Mpad][k_pad(D)] + scales; the fc1 output [Mpad][4D] + scales lives in Hbuf
         uint8_t *Umx = nullptr, *Umx_s = nullptr, *U2mx = nullptr, *U2mx_s = nullptr, *Hmx = nullptr, *Hmx_s = nullptr;
         void *Wq[W_PER_LAYER] = {nullptr, nullptr, nullptr, nullptr};   // just-in-time expansion of the current layer's quantised matrices
@@ -203,6 +209,14 @@ struct vitx_ctx {
     float *feat_out = nullptr;   // [feat_cap][feat_fpi]: per image the selected layers in ascending order, each [cls D][mean D][tokens (N-Tp) D] (selected parts only)
     bool feat_on() const { return feat_flags != 0; }
     int feat_layer_floats() const { return D * ((feat_flags & VITX_FEAT_CLS ? 1 : 0) + (feat_flags & VITX_FEAT_MEAN ? 1 : 0) + (feat_flags & VITX_FEAT_TOKENS ? N - Tp : 0)); }
+    // the slots of layer il in image first_img's block of feat_out (nullptr: not selected), in the layout's order cls, mean, tokens
+    void feat_slots(int first_img, int il, int flags, float **o_cls, float **o_mean, float **o_tok) const {
+        float *o = feat_out + (size_t)first_img * feat_fpi + (size_t)layer_slot(feat_mask, il) * feat_layer_floats();
+        *o_cls = *o_mean = *o_tok = nullptr;
+        if (flags & VITX_FEAT_CLS) { *o_cls = o; o += D; }
+        if (flags & VITX_FEAT_MEAN) { *o_mean = o; o += D; }
+        if (flags & VITX_FEAT_TOKENS) *o_tok = o;
+    }
     // MEAN or TOKENS of the last layer need every row of it: no class-rows-only tail while they are on (as while the trace is)
     bool feat_last_all_rows() const { return (feat_flags & (VITX_FEAT_MEAN | VITX_FEAT_TOKENS)) && ((feat_mask >> (L - 1)) & 1); }
     void feat_free() { if (feat_out) (void)hipFree(feat_out); feat_out = nullptr; }

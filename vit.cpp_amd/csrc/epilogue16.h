@@ -84,7 +84,7 @@ __device__ __forceinline__ void epilogue16(const GemmArgs &g, f32x4 (&acc)[TM][T
                 if constexpr (EPI == EPI_PATCH) {           // patch row -> token row (+ the prefix rows of images 0 .. b: cls and registers), + position embedding
                     const int b = row / g.tpi, tk = row - b * g.tpi;
                     o[t] = (float *)g.out + ((size_t)row + (size_t)(b + 1) * g.prefix) * g.ldo + c;
-                    const float *pe = g.pos + (size_t)(tk + 1) * g.ldo + c;
+                    const float *pe = g.pos + (size_t)(tk + (g.prefix > 0 ? 1 : 0)) * g.ldo + c;      // prefix 0: the table has no class row
                     if (row_ok) {
                         if (vec) add[t] = *(const f32x4 *)pe;
                         else {

@@ -16,6 +16,7 @@
 // Column ownership follows the statistics helpers: lane l holds columns c * 256 + 4 l .. + 3 of tile c (tiled widths: 16-byte loads and
 // stores, 1 KiB contiguous per wave instruction) or (i * 64 + l) * VEC .. of piece i (flat widths, VEC of the instantiation table).
 #include "device_common.h"
+#include "feat_row.h"
 #include "kernels.h"
 
 namespace vitx {
@@ -25,66 +26,6 @@ namespace {
 // waves per workgroup: 16 (4 per SIMD, 128 VGPRs each) up to 768 columns; 8 above, where a row, the accumulators and the second row or the
 // weights of a piece need more than 128 registers per lane (checked with -save-temps: no instantiation spills)
 constexpr int feat_waves(int D) { return D <= 768 ? 16 : 8; }
-
-template <int VEC, int NV> struct FeatRow {
-    static constexpr bool kTiled = VEC == 4 && NV <= LN_MAX_TILES;
-    static __device__ __forceinline__ int col(int i, int lane) { return kTiled ? i * 256 + lane * 4 : (i * 64 + lane) * VEC; }
-    // f[i][j] = F at column col(i) + j of the row xr
-    static __device__ __forceinline__ void norm(const float *__restrict__ xr, const float *__restrict__ w, const float *__restrict__ b, float eps, int lane, float (&f)[NV][VEC]) {
-        if constexpr (kTiled) {
-            f32x4 v[NV];
-            float mean, rstd;
-            ln_tiled_stats<NV>(xr, eps, lane, v, mean, rstd);
-#pragma unroll
-            for (int c = 0; c < NV; ++c) {
-                const f32x4 ww = *(const f32x4 *)(w + col(c, lane)), bb = *(const f32x4 *)(b + col(c, lane));
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { float t = (v[c][e] - mean) * rstd; t = t * ww[e]; f[c][e] = t + bb[e]; }
-            }
-        } else {
-            float scale;
-            ln_flat_stats<VEC, NV>(xr, eps, lane, f, scale);         // f = x - mean
-#pragma unroll
-            for (int i = 0; i < NV; ++i)
-#pragma unroll
-                for (int j = 0; j < VEC; ++j) { float t = f[i][j] * scale; t = t * w[col(i, lane) + j]; f[i][j] = t + b[col(i, lane) + j]; }
-        }
-    }
-    // RNE to the operand type T16 (the rounding layernorm_kernel applies to the same f32 value), row zr of D elements
-    template <typename T16> static __device__ __forceinline__ void store_rne(T16 *__restrict__ zr, int lane, const float (&f)[NV][VEC]) {
-#pragma unroll
-        for (int i = 0; i < NV; ++i)
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) zr[col(i, lane) + j] = (T16)f[i][j];
-    }
-    static __device__ __forceinline__ void store(float *__restrict__ yr, int lane, const float (&f)[NV][VEC]) {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            float *p = yr + col(i, lane);
-            if constexpr (VEC == 4) *(f32x4 *)p = f32x4{f[i][0], f[i][1], f[i][2], f[i][3]};
-            else if constexpr (VEC == 2) *(f32x2 *)p = f32x2{f[i][0], f[i][1]};
-            else *p = f[i][0];
-        }
-    }
-    // VITX_FEAT_L2: f / sqrt(sum of squares), both in f32 (per-lane sums in column order, then a butterfly: the same bits in every lane);
-    // an all-zero vector stays zero
-    static __device__ __forceinline__ void l2(float (&f)[NV][VEC]) {
-        float ss = 0.0f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i)
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) ss += f[i][j] * f[i][j];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
-        const float nrm = sqrtf(ss);
-        if (nrm > 0.0f) {
-#pragma unroll
-            for (int i = 0; i < NV; ++i)
-#pragma unroll
-                for (int j = 0; j < VEC; ++j) f[i][j] = f[i][j] / nrm;
-        }
-    }
-};
 
 template <int VEC, int NV>
 __global__ __launch_bounds__(feat_waves(64 * VEC * NV) * 64) void features_kernel(const float *__restrict__ x, long row_stride, long img_stride, const float *__restrict__ w,
@@ -161,10 +102,10 @@ __global__ __launch_bounds__(feat_waves(64 * VEC * NV) * 64) void features_kerne
 // F of n_img images of N rows (row t of image i at x + i * img_stride + t * row_stride), T = first: cls[i * out_img_stride ..] = F[0] [D],
 // mean[i * out_img_stride ..] = mean of F[T .. N-1] [D], tokens[i * out_img_stride ..] = F[T .. N-1] [N - T][D]; any output may be nullptr.
 // z: the pooled head's operand rows [n_img][2 D] in `dtype` (kernels.h).  Row 0 is read only for cls / z, rows T .. only for mean / tokens / z.
-// hipErrorInvalidValue: no instantiation for D (layernorm_supports), or first outside 1 .. N.
+// hipErrorInvalidValue: no instantiation for D (layernorm_supports), first outside 0 .. N, or first = 0 with cls / z.
 hipError_t launch_features(const float *x, long row_stride, long img_stride, const float *w, const float *b, float *cls, float *mean, float *tokens,
                            long out_img_stride, int n_img, int N, int D, float eps, bool l2, hipStream_t stream, int first, void *z, int dtype) {
-    if (first < 1 || first > N) return hipErrorInvalidValue;
+    if (first < 0 || first > N || (first == 0 && (cls || z))) return hipErrorInvalidValue;     // first = 0: a model without prefix tokens has no class row
     const bool rows = mean || tokens || z;
     const dim3 grid(n_img), blk(64 * (rows ? feat_waves(D) : 1));
 #define VITX_FEAT_CASE(DD, VEC, NV) \

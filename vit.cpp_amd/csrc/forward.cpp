@@ -128,15 +128,44 @@ struct SliceForward {
         const bool sel = c->feat_on() && ((c->feat_mask >> il) & 1);
         if (!sel && !z) return VITX_OK;
         const int fl = sel ? c->feat_flags : 0, Tp = c->Tp;
-        float *o = c->feat_out + (size_t)first_img * c->feat_fpi + (size_t)layer_slot(c->feat_mask, il) * c->feat_layer_floats();
-        float *o_cls = nullptr, *o_mean = nullptr, *o_tok = nullptr;
-        if (fl & VITX_FEAT_CLS) { o_cls = o; o += D; }
-        if (fl & VITX_FEAT_MEAN) { o_mean = o; o += D; }
-        if (fl & VITX_FEAT_TOKENS) o_tok = o;
+        float *o_cls, *o_mean, *o_tok;
+        c->feat_slots(first_img, il, fl, &o_cls, &o_mean, &o_tok);
+        if (c->map) {        // no class row: VITX_FEAT_CLS of such a context is the pooled embedding, written by pooled_tail
+            o_cls = nullptr;
+            if (!o_mean && !o_tok) return VITX_OK;
+        }
         const double rows = (double)n * ((o_cls || z ? 1 : 0) + (o_mean || o_tok || z ? N - Tp : 0));
         ProfScope ps(c, st, sel ? PC_FEATURES : PC_HEAD_POOL, 0, rows * D * 4 + (double)n * D * 4 * ((o_cls ? 1 : 0) + (o_mean ? 1 : 0) + (o_tok ? N - Tp : 0)) + (z ? (double)n * 2 * D * eb : 0.0));
         HIP_TRY(launch_features(cls_rows ? sl.Xc : sl.X, D, cls_rows ? (long)D : (long)N * D, ws.norm_w, ws.norm_b, o_cls, o_mean, o_tok, c->feat_fpi,
                                 n, cls_rows ? 1 : N, D, c->hp.eps, (fl & VITX_FEAT_L2) != 0, st, cls_rows ? 1 : Tp, z, dt));
+        return VITX_OK;
+    }
+    // The attention-pooling head (VITX_POOL_MAP; include/vitx.h) on the n images of this sub-batch, after the last layer: the pooling pass over the
+    // residual stream (attention_pool.hip) -> Mp = RNE(M) [n][H][D]; the value projection, H launches of the short-M GEMM on strided operands (head h
+    // reads Mp[:, h, :] and writes columns h d .. (h + 1) d of U); proj -> a (f32, Xc); LayerNorm -> U2; fc1 + activation -> Hbuf; fc2 + residual
+    // -> e (Xc, in place); Z = RNE(e) and the VITX_FEAT_CLS feature.  6 + H launches; all but the first work on one row per image.
+    int pooled_tail() {
+        int rc;
+        const int H = c->H, d = D / H, Mc = round_up(n, tm);
+        {
+            ProfScope ps(c, st, PC_HEAD_POOL, 4.0 * n * H * (double)N * D, (double)M_real * D * 4 + (double)n * H * D * eb);
+            HIP_TRY(launch_attention_pool(sl.X, D, (long)N * D, ws.norm_w, ws.norm_b, c->hp.eps, ws.map_u, nullptr, sl.Mp, dt, nullptr, n, N, D, H, st));
+        }
+        for (int h = 0; h < H; ++h) {
+            GemmArgs a = dense_gemm((const char *)sl.Mp + (size_t)h * D * 2, (const char *)ws.map_v_w + (size_t)h * d * D * 2, ws.map_v_b + h * d, (char *)sl.U + (size_t)h * d * 2,
+                                    Mc, n, d, round_up(d, 128), D, D);
+            a.lda = H * D;
+            if ((rc = gemm(c, st, PC_GEMM_TAIL, EPI_BIAS, a))) return rc;
+        }
+        if ((rc = gemm(c, st, PC_GEMM_TAIL, EPI_BIAS_F32, dense_gemm(sl.U, ws.map_proj_w, ws.map_proj_b, sl.Xc, Mc, n, D, round_up(D, tn), D)))) return rc;
+        if ((rc = layernorm(sl.Xc, D, ws.map_ln_w, ws.map_ln_b, sl.U2, n))) return rc;
+        if ((rc = gemm(c, st, PC_GEMM_TAIL, c->fc1_epi, dense_gemm(sl.U2, ws.map_fc1_w, ws.map_fc1_b, sl.Hbuf, Mc, n, 4 * D, round_up(4 * D, tn), D)))) return rc;
+        if ((rc = gemm(c, st, PC_GEMM_TAIL, EPI_BIAS_RESID, dense_gemm(sl.Hbuf, ws.map_fc2_w, ws.map_fc2_b, sl.Xc, Mc, n, D, round_up(D, tn), 4 * D)))) return rc;
+        float *o_cls = nullptr, *o_mean, *o_tok;
+        const bool sel = c->feat_on() && ((c->feat_mask >> (c->L - 1)) & 1);
+        if (sel) c->feat_slots(first_img, c->L - 1, c->feat_flags, &o_cls, &o_mean, &o_tok);
+        ProfScope ps(c, st, sel && o_cls ? PC_FEATURES : PC_HEAD_POOL, 0, (double)n * D * (4 + eb + (o_cls ? 4 : 0)));
+        HIP_TRY(launch_pool_embed(sl.Xc, sl.Z, dt, o_cls, c->feat_fpi, (c->feat_flags & VITX_FEAT_L2) != 0, n, D, st));
         return VITX_OK;
     }
     // Quantised matrices (block form in HBM): a q4_0 GEMM with few rows expands the blocks in its own LDS-fill path; everything else
@@ -291,7 +320,9 @@ struct SliceForward {
         const int nR = n * c->R;
         // classifier: one row per image, row stride N*D; ViTSTR: groups of R consecutive token rows (stride D), group stride N*D
         // pooled head: Z [n][2 D] was written by the last layer's feature launch above (final norm of row 0 ‖ mean of the patch rows' final norm)
+        // attention-pooling head: one row per image comes out of pooled_tail
         if (c->pool) rc = VITX_OK;
+        else if (c->map) rc = pooled_tail();             // Z = RNE(e), the attention-pooled embedding
         else if (tail) rc = layernorm(sl.Xc, D, ws.norm_w, ws.norm_b, sl.Z, n);
         else rc = layernorm(sl.X, c->R == 1 ? (long)N * D : (long)D, ws.norm_w, ws.norm_b, sl.Z, nR, c->R, (long)N * D);
         if (rc) return rc;

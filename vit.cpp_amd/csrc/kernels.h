@@ -47,7 +47,7 @@ struct GemmArgs {
     int K;        // multiple of 64
     int lda, ldw, ldo;
     int tpi;      // EPI_PATCH: patch tokens per image (g*g)
-    int prefix = 1;  // EPI_PATCH: tokens of an image in front of its patches: the class token + R register tokens (an image has tpi + prefix rows)
+    int prefix = 1;  // EPI_PATCH: tokens of an image in front of its patches: the class token + R register tokens (an image has tpi + prefix rows); 0: none, and pos has no class row
     long hilo_off;  // EPI_BIAS_HILO: ELEMENT offset of the lo plane behind `out` (a whole number of rows; the byte offset must fit 32 bits)
     int dbg;      // ablation bits of the ring kernel's laboratory build (VITX_LAB only; 0 in the product)
     // q4_0 weights kept in block form (launch_gemm_q4 only): W = nibble plane [N_pad][K/2] bytes (16 per block), Wscale = f16 block
@@ -146,7 +146,8 @@ int gemm_tile_n();
 // X[b * N + T + t][:] = W . patch(b, t) + bias + pos[1 + t], X[b * N][:] = cls + pos[0], X[b * N + 1 + r][:] = reg[r] (no position term).
 // img: f32 HWC [n_img][S][S][Cin] (Cin = 3: RGB classifier input; 1: the grey ViTSTR input, extensions/vitstr.cpp/vitstr.cpp:713-731);
 // w_perm: the [n_pad][k_pad] operand-type kernel with its K axis permuted by patch_embed_permute_k (host side, at upload); pos [1 + patches][D],
-// cls [D], reg [n_reg][D] (nullptr when n_reg == 0).
+// cls [D], reg [n_reg][D] (nullptr when n_reg == 0).  cls == nullptr (n_reg == 0): no prefix token at all -- N = patches, X[b * N + t][:] = W . patch(b, t) + bias + pos[t],
+// pos [patches][D] (a VITX_POOL_MAP model).
 hipError_t launch_patch_embed(int dtype, const float *img, const void *w_perm, const float *bias, const float *pos, const float *cls, const float *reg, int n_reg,
                               float *X, int n_img, int S, int P, int Cin, int D, int n_pad, int k_pad, hipStream_t stream);
 void patch_embed_permute_k(const uint16_t *w, uint16_t *w_perm, int N, int Cin, int P, int k_pad);
@@ -190,6 +191,17 @@ hipError_t launch_rollout_row(const float *cls, long cls_stride, const float *r,
 // Every width of VITX_LN_WIDTHS; pointers 16-byte aligned, strides multiples of 4 floats.
 hipError_t launch_features(const float *x, long row_stride, long img_stride, const float *w, const float *b, float *cls, float *mean, float *tokens,
                            long out_img_stride, int n_img, int N, int D, float eps, bool l2, hipStream_t stream, int first = 1, void *z = nullptr, int dtype = DT_F16);
+// The pooling kernel of the attention-pooling head (attention_pool.hip; include/vitx.h "no class token and the attention-pooling head"): with F[t] the
+// f32 final-norm row of token t (launch_features' F, same statistics and operation order), s_{h,t} = u_h . F[t], p_h = softmax_t(s_h),
+// M_h = sum_t p_{h,t} F[t], all f32.  Row t of image i is read at x + i * img_stride + t * row_stride; u [H][D] f32.  Outputs, each may be nullptr:
+// M [n_img][H][D] f32; m16 [n_img][H][D] = RNE(M) in the operand type `dtype` (the value projection's A operand); p [n_img][H][N] f32.
+// Every width of VITX_LN_WIDTHS, 1 <= H <= kPoolMaxHeads, any N >= 1; one workgroup per image and group of heads, no atomics.  hipErrorInvalidValue otherwise.
+constexpr int kPoolMaxHeads = 32;
+hipError_t launch_attention_pool(const float *x, long row_stride, long img_stride, const float *w, const float *b, float eps, const float *u, float *M, void *m16, int dtype,
+                                 float *p, int n_img, int N, int D, int H, hipStream_t stream);
+// The end of the pooled tail: e [n_img][D] f32 -> z [n_img][D] = RNE(e) in `dtype` (the head GEMM's operand) and, cls != nullptr, the feature
+// cls[i * out_img_stride ..] = e[i] (l2: divided by its norm, VITX_FEAT_L2's arithmetic).  One wave per image.
+hipError_t launch_pool_embed(const float *e, void *z, int dtype, float *cls, long out_img_stride, bool l2, int n_img, int D, hipStream_t stream);
 // pos [1 + gy_in * gx_in][D] f32 -> out [1 + gy_out * gx_out][D] f32 (pos_resample.hip; the arithmetic: pos_resample.h); only enqueues
 hipError_t launch_pos_resample(const float *pos, int gy_in, int gx_in, int D, int gy_out, int gx_out, int interp, float *out, hipStream_t stream);
 bool attention_supports(int N, int D, int H);     // any token count; head_dim 64 (tuned kernels) or any other multiple of 8 up to 128 (generic kernel)

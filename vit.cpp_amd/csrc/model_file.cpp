@@ -11,8 +11,11 @@
 // head"), recognised by name and shape: `reg_token` f32 [1][R][D], and a `head.weight` of [C][2 D].
 // Two more (include/vitx.h "Activation, epsilon and pre-norm"): `arch` f32 [4] = {activation, eps, 0, 0} and the pair `pre_norm.weight`,
 // `pre_norm.bias` f32 [D] (CLIP's pre_layrnorm).  Without `arch` a file means tanh-GELU and eps 1e-6, the reference's arithmetic.
+// One more (include/vitx.h "no class token and the attention-pooling head"): the thirteen `attn_pool.*` tensors of a SigLIP-class model, which
+// come without cls_token / reg_token and with a pos_embed of g^2 rows (VITX_POOL_MAP).
 #include "model_file.h"
 
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <atomic>
@@ -98,7 +101,7 @@ void HostTensor::decode_f32(float *out) const {
 }
 
 // expected tensors and their ggml shapes (vit.cpp:506-581); type classes: 0 = must be f32,
-// 1 = "wtype" (f32/f16/q*), 2 = patch kernel (f16, f32 also accepted here)
+// 1 = "wtype" (f32/f16/q*), 2 = patch kernel (f16, f32 also accepted here), 3 = attn_pool.* matrix (f16 or f32: never block-quantised)
 struct Expect { int64_t ne[4]; int cls; };
 static std::map<std::string, Expect> expected_tensors(const vitx_hparams &hp) {
     std::map<std::string, Expect> e;
@@ -118,6 +121,20 @@ static std::map<std::string, Expect> expected_tensors(const vitx_hparams &hp) {
     }
     e["norm.weight"] = {{D, 1, 1, 1}, 0}; e["norm.bias"] = {{D, 1, 1, 1}, 0};
     e["head.weight"] = {{D, C, 1, 1}, 1}; e["head.bias"] = {{C, 1, 1, 1}, 0};
+    return e;
+}
+
+// the attention-pooling head (VITX_POOL_MAP): all thirteen or none; matrices f32 or f16 (never block-quantised), everything else f32
+static std::map<std::string, Expect> pool_tensors(const vitx_hparams &hp) {
+    std::map<std::string, Expect> e;
+    const int64_t D = hp.hidden_size;
+    e["attn_pool.latent"] = {{D, 1, 1, 1}, 0};
+    e["attn_pool.q.weight"] = {{D, D, 1, 1}, 3}; e["attn_pool.q.bias"] = {{D, 1, 1, 1}, 0};
+    e["attn_pool.kv.weight"] = {{D, 2 * D, 1, 1}, 3}; e["attn_pool.kv.bias"] = {{2 * D, 1, 1, 1}, 0};
+    e["attn_pool.proj.weight"] = {{D, D, 1, 1}, 3}; e["attn_pool.proj.bias"] = {{D, 1, 1, 1}, 0};
+    e["attn_pool.norm.weight"] = {{D, 1, 1, 1}, 0}; e["attn_pool.norm.bias"] = {{D, 1, 1, 1}, 0};
+    e["attn_pool.mlp.fc1.weight"] = {{D, 4 * D, 1, 1}, 3}; e["attn_pool.mlp.fc1.bias"] = {{4 * D, 1, 1, 1}, 0};
+    e["attn_pool.mlp.fc2.weight"] = {{4 * D, D, 1, 1}, 3}; e["attn_pool.mlp.fc2.bias"] = {{D, 1, 1, 1}, 0};
     return e;
 }
 
@@ -150,7 +167,10 @@ static int load_impl(const char *path, vitx_model &m) {
         m.id2label[key] = v;
     }
     const auto expect = expected_tensors(hp);
+    const auto pool_expect = pool_tensors(hp);
     int n_optional = 0;                                              // `arch`, `preproc`, `pre_norm.*` records seen
+    int n_pool = 0;                                                  // `attn_pool.*` records seen
+    bool pos_no_cls = false;                                         // pos_embed has g^2 rows (no class row)
     for (;;) {
         int32_t n_dims, name_len, ttype;
         if (!rd_i32(n_dims)) break;                                  // clean EOF (vit.cpp:600-603)
@@ -227,10 +247,16 @@ static int load_impl(const char *path, vitx_model &m) {
             ++n_optional;
             continue;
         }
-        auto it = expect.find(t.name);
-        if (it == expect.end()) { set_error("vitx_model_load: unknown tensor '%s' in model file", t.name.c_str()); return VITX_ERR_FORMAT; }
+        const Expect *known = nullptr;
+        bool is_pool = false;
+        if (auto it = expect.find(t.name); it != expect.end()) known = &it->second;
+        else if (auto ip = pool_expect.find(t.name); ip != pool_expect.end()) { known = &ip->second; is_pool = true; }
+        if (!known) { set_error("vitx_model_load: unknown tensor '%s' in model file", t.name.c_str()); return VITX_ERR_FORMAT; }
         if (m.index.count(t.name)) { set_error("vitx_model_load: duplicate tensor '%s'", t.name.c_str()); return VITX_ERR_FORMAT; }
-        Expect ex = it->second;
+        Expect ex = *known;
+        if (is_pool) ++n_pool;
+        // attn_pool.latent is [1][1][D] (ggml dims [D, 1, 1]); a model without a class token has a pos_embed of g^2 rows (checked against attn_pool.* below)
+        if (t.name == "pos_embed" && t.ne[1] == ex.ne[1] - 1 && t.ne[1] >= 1) { ex.ne[1] -= 1; pos_no_cls = true; }
         // ViTSTR files (extensions/vitstr.cpp/vitstr.cpp:482) carry a ONE-channel patch kernel [P, P, 1, D]: same format otherwise
         if (t.name == "patch_embed.proj.weight" && t.ne[2] == 1 && t.ne[0] == ex.ne[0] && t.ne[1] == ex.ne[1] && t.ne[3] == ex.ne[3]) { ex.ne[2] = 1; m.in_chans = 1; }
         // a head over concat(cls, mean of the patch tokens) has rows of 2 D (VITX_POOL_CLS_MEAN); any other row length fails the shape check below
@@ -246,7 +272,7 @@ static int load_impl(const char *path, vitx_model &m) {
         if (!bb) { set_error("vitx_model_load: unknown ftype %d in model file", ttype); return VITX_ERR_FORMAT; }
         if (be > 1 && t.ne[0] % 64) { set_error("vitx_model_load: quantised tensor '%s' needs ne[0] %% 64 == 0", t.name.c_str()); return VITX_ERR_FORMAT; }
         // the declared type of each slot decides the expected byte size (vit.cpp:680-685)
-        const bool type_ok = (ex.cls == 0) ? (ttype == T_F32) : (ex.cls == 2) ? (ttype == T_F16 || ttype == T_F32) : (ttype == hp.ftype);
+        const bool type_ok = (ex.cls == 0) ? (ttype == T_F32) : (ex.cls == 2 || ex.cls == 3) ? (ttype == T_F16 || ttype == T_F32) : (ttype == hp.ftype);
         if (!type_ok) { set_error("vitx_model_load: tensor '%s' has wrong size in model file (type %d not allowed for this slot, file ftype %d)", t.name.c_str(), ttype, hp.ftype); return VITX_ERR_FORMAT; }
         const size_t nbytes = (size_t)(t.nelements() / be) * bb;
         t.raw.resize(nbytes);
@@ -261,7 +287,20 @@ static int load_impl(const char *path, vitx_model &m) {
     m.has_pre_norm = m.find("pre_norm.weight") != nullptr;
     if (m.has_preproc && m.in_chans == 1) { set_error("vitx_model_load: tensor 'preproc' in a one-channel (ViTSTR) file: its preprocessing is fixed"); return VITX_ERR_FORMAT; }
     if (!m.has_preproc) m.preproc = pp_default(hp.img_size);
-    const size_t n_expect = expect.size() + (m.num_registers ? 1 : 0) + (size_t)n_optional;
+    // the attention-pooling head: all thirteen tensors, no class or register token, a position table without a class row -- or none of it
+    const bool has_cls = m.find("cls_token") != nullptr;
+    if (n_pool) {
+        for (const auto &kv : pool_expect)
+            if (!m.find(kv.first)) { set_error("vitx_model_load: the attention-pooling head is incomplete: tensor '%s' is missing (%d of %d attn_pool.* tensors)", kv.first.c_str(), n_pool, (int)pool_expect.size()); return VITX_ERR_FORMAT; }
+        if (has_cls || m.num_registers) { set_error("vitx_model_load: attn_pool.* together with '%s': a model with the attention-pooling head has no class or register token", has_cls ? "cls_token" : "reg_token"); return VITX_ERR_FORMAT; }
+        if (!pos_no_cls && m.find("pos_embed")) { set_error("vitx_model_load: tensor 'pos_embed' has a class row, but the file has attn_pool.* and no class token"); return VITX_ERR_FORMAT; }
+        if (m.head_pool != VITX_POOL_CLS) { set_error("vitx_model_load: attn_pool.* together with a [C][2 D] head: the head of such a model reads the pooled embedding [D]"); return VITX_ERR_FORMAT; }
+        m.head_pool = VITX_POOL_MAP;
+    } else {
+        if (!has_cls) { set_error("vitx_model_load: tensor 'cls_token' is missing (only a file with the attn_pool.* tensors has no class token)"); return VITX_ERR_FORMAT; }
+        if (pos_no_cls) { set_error("vitx_model_load: tensor 'pos_embed' has no class row, but the file has a class token"); return VITX_ERR_FORMAT; }
+    }
+    const size_t n_expect = expect.size() - (n_pool ? 1 : 0) + (size_t)n_pool + (m.num_registers ? 1 : 0) + (size_t)n_optional;
     if (m.tensors.size() != n_expect) {
         set_error("vitx_model_load: model file has %d tensors, but %d tensors were expected", (int)m.tensors.size(), (int)n_expect);
         return VITX_ERR_FORMAT;
@@ -304,6 +343,25 @@ int vitx_model_num_labels(const vitx_model *m) { return m ? (int)m->id2label.siz
 int vitx_model_in_channels(const vitx_model *m) { return m ? m->in_chans : 0; }
 int vitx_model_num_registers(const vitx_model *m) { return m ? m->num_registers : 0; }
 int vitx_model_head_pool(const vitx_model *m) { return m ? m->head_pool : 0; }
+int vitx_model_num_prefix(const vitx_model *m) { return m ? (m->head_pool == VITX_POOL_MAP ? 0 : 1 + m->num_registers) : 0; }
+// u_h = Wk_h^T q_h / sqrt(d), q = Wq latent + bq, in double from the file's f32 decode; rounded once to f32 (include/vitx.h)
+int vitx_model_pool_query(const vitx_model *m, float *out) {
+    if (!m || !out) { vitx::set_error("vitx_model_pool_query: NULL argument"); return VITX_ERR_ARG; }
+    if (m->head_pool != VITX_POOL_MAP) { vitx::set_error("vitx_model_pool_query: the model has no attention-pooling head"); return VITX_ERR_ARG; }
+    const int D = m->hp.hidden_size, H = m->hp.num_attention_heads, d = D / H;
+    auto dec = [&](const char *n) { const vitx::HostTensor *t = m->find(n); std::vector<float> v((size_t)t->nelements()); t->decode_f32(v.data()); return v; };
+    const std::vector<float> lat = dec("attn_pool.latent"), wq = dec("attn_pool.q.weight"), bq = dec("attn_pool.q.bias"), wkv = dec("attn_pool.kv.weight");
+    std::vector<double> q((size_t)D);
+    for (int i = 0; i < D; ++i) { double s = 0.0; for (int k = 0; k < D; ++k) s += (double)wq[(size_t)i * D + k] * (double)lat[k]; q[i] = s + (double)bq[i]; }
+    const double scale = 1.0 / sqrt((double)d);
+    for (int h = 0; h < H; ++h)
+        for (int k = 0; k < D; ++k) {
+            double s = 0.0;
+            for (int j = 0; j < d; ++j) s += (double)wkv[(size_t)(h * d + j) * D + k] * q[h * d + j];      // the K half: rows 0 .. D-1 of kv.weight
+            out[(size_t)h * D + k] = (float)(s * scale);
+        }
+    return VITX_OK;
+}
 int vitx_model_activation(const vitx_model *m) { return m ? m->activation : 0; }
 int vitx_model_has_pre_norm(const vitx_model *m) { return m && m->has_pre_norm ? 1 : 0; }
 int vitx_model_has_preproc(const vitx_model *m) { return m && m->has_preproc ? 1 : 0; }

@@ -32,7 +32,8 @@ struct vitx_model {
     uint64_t uid = 0;                                 // unique per successful vitx_model_load in this process (never reused: an address can be)
     int in_chans = 3;                                 // 1 = ViTSTR file (grey input, sequence head), from the patch kernel's shape
     int num_registers = 0;                            // R of an optional `reg_token` [1][R][D]: tokens between the class token and the patches
-    int head_pool = VITX_POOL_CLS;                    // VITX_POOL_CLS_MEAN: head.weight is [C][2 D], over concat(cls, mean of the patch tokens)
+    int head_pool = VITX_POOL_CLS;                    // VITX_POOL_CLS_MEAN: head.weight is [C][2 D], over concat(cls, mean of the patch tokens);
+                                                      // VITX_POOL_MAP: the thirteen attn_pool.* tensors, no cls_token, pos_embed of g^2 rows
     int activation = VITX_ACT_GELU_TANH;              // MLP activation, from an optional `arch` [4] = {activation, eps, 0, 0}; hp.eps carries its eps
     bool has_pre_norm = false;                        // `pre_norm.weight` / `pre_norm.bias` [D]: LayerNorm of every token row in front of layer 0
     bool has_preproc = false;                         // `preproc` [16]: the model's own preprocessing (include/vitx.h); without it `preproc` is the reference default

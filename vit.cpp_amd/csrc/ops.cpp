@@ -203,7 +203,8 @@ int vitx_op_topk(const void *probs, int rows, int cols, int k, void *pairs, void
 // it is vitx_op_features_ex, whose texts also tell `first`.  vitx_op_features is first = 1 and no head operand (so d_z never counts as its output).
 static int op_features(const char *name, bool ex, const void *d_x, long row_stride, long img_stride, const void *d_w, const void *d_b, void *d_cls, void *d_mean,
                        void *d_tokens, long out_img_stride, int n_img, int N, int first, int D, float eps, int l2, void *d_z, int dtype, void *stream) {
-    if (!d_x || !d_w || !d_b || (!d_cls && !d_mean && !d_tokens && !d_z) || n_img <= 0 || N <= 0 || D <= 0 || first < 1 || first > N) { set_error("%s: invalid argument", name); return VITX_ERR_ARG; }
+    if (!d_x || !d_w || !d_b || (!d_cls && !d_mean && !d_tokens && !d_z) || n_img <= 0 || N <= 0 || D <= 0 || first < 0 || first > N || (!ex && first < 1)) { set_error("%s: invalid argument", name); return VITX_ERR_ARG; }
+    if (first == 0 && (d_cls || d_z)) { set_error("vitx_op_features_ex: first = 0 means no class row: d_cls and d_z cannot be asked for"); return VITX_ERR_ARG; }
     if (first == N && (d_mean || d_tokens || d_z)) {
         if (ex) set_error("vitx_op_features_ex: the mean and the tokens need at least one patch row (N %d, first %d)", N, first);
         else set_error("vitx_op_features: the mean and the tokens need at least one patch row (N %d)", N);
@@ -229,7 +230,7 @@ int vitx_op_features_ex(const void *d_x, long row_stride, long img_stride, const
 // file's order (channel-major); it is rounded (RNE) to the operand type, K-permuted and padded exactly as the context does at upload.
 int vitx_op_patch_embed(int dtype, const void *d_img, const void *d_w, const void *d_bias, const void *d_pos, const void *d_cls, const void *d_reg, int R, void *d_X,
                         int n_img, int S, int P, int Cin, int D, void *stream) {
-    if (!d_img || !d_w || !d_bias || !d_pos || !d_cls || !d_X || R < 0 || (R > 0 && !d_reg) || n_img <= 0 || S <= 0 || P <= 0 || S % P || Cin <= 0 || D <= 0 || D % 4 ||
+    if (!d_img || !d_w || !d_bias || !d_pos || (!d_cls && R != 0) || !d_X || R < 0 || (R > 0 && !d_reg) || n_img <= 0 || S <= 0 || P <= 0 || S % P || Cin <= 0 || D <= 0 || D % 4 ||
         (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_patch_embed: invalid argument"); return VITX_ERR_ARG; }
     if (!tuning_for_device(-1)) { set_error("vitx_op_patch_embed: kernel bring-up failed"); return VITX_ERR_HIP; }
     const int K = Cin * P * P, k_pad = round_up(K, 64), n_pad = round_up(D, gemm_tile_n());
@@ -249,6 +250,17 @@ int vitx_op_patch_embed(int dtype, const void *d_img, const void *d_w, const voi
                                                 (float *)d_X, n_img, S, P, Cin, D, n_pad, k_pad, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     return op_rc("vitx_op_patch_embed", e, VITX_ERR_UNSUPPORTED);
+}
+// The pooling kernel of the attention-pooling head on its own.  Every argument check comes before the first device call.
+int vitx_op_attention_pool(const void *d_x, long row_stride, long img_stride, const void *d_ln_w, const void *d_ln_b, float eps, const void *d_u, void *d_M, void *d_p,
+                           int n_img, int N, int D, int H, void *stream) {
+    if (!d_x || !d_ln_w || !d_ln_b || !d_u || !d_M || n_img <= 0 || N <= 0 || D <= 0 || H <= 0 || H > kPoolMaxHeads) { set_error("vitx_op_attention_pool: invalid argument (1 <= H <= %d)", kPoolMaxHeads); return VITX_ERR_ARG; }
+    for (const void *p : {d_x, d_ln_w, d_ln_b, d_u, (const void *)d_M, (const void *)d_p})
+        if ((uintptr_t)p % 16) { set_error("vitx_op_attention_pool: pointers must be 16-byte aligned"); return VITX_ERR_ARG; }
+    if (row_stride % 4 || img_stride % 4) { set_error("vitx_op_attention_pool: strides must be multiples of 4 floats"); return VITX_ERR_ARG; }
+    if (!layernorm_supports(D)) { set_error("vitx_op_attention_pool: hidden size %d has no LayerNorm instantiation", D); return VITX_ERR_UNSUPPORTED; }
+    return op_rc("vitx_op_attention_pool", launch_attention_pool((const float *)d_x, row_stride, img_stride, (const float *)d_ln_w, (const float *)d_ln_b, eps, (const float *)d_u,
+                                                                 (float *)d_M, nullptr, DT_F16, (float *)d_p, n_img, N, D, H, (hipStream_t)stream), VITX_ERR_UNSUPPORTED);
 }
 // The map kernels on their own (the parity tests): d_cls [n_img][H][N] class-token rows, d_mean [n_img][N][N] mean_h A_h (either may be NULL).
 int vitx_op_attention_map(int dtype, const void *d_qkv, long lo_off, void *d_cls, void *d_mean, int n_img, int N, int D, int H, void *stream) {

@@ -140,6 +140,7 @@ int vitx_attn_enable(vitx_ctx *c, uint64_t layer_mask, int flags) {
     if (c->L < 64 && (layer_mask >> c->L)) { set_error("vitx_attn_enable: layer mask 0x%llx names layers beyond the model's %d", (unsigned long long)layer_mask, c->L); return VITX_ERR_ARG; }
     const bool on = layer_mask != 0 || flags != 0, rollout = (flags & VITX_ATTN_ROLLOUT) != 0;
     if (on && c->R != 1) { set_error("vitx_attn_enable: attention maps are not available for ViTSTR contexts"); return VITX_ERR_UNSUPPORTED; }
+    if (on && c->map) { set_error("vitx_attn_enable: the maps are defined by the class-token row, and a model with the attention-pooling head has no class token"); return VITX_ERR_UNSUPPORTED; }
     if (on && !attention_map_supports(c->N, c->D, c->H)) { set_error("vitx_attn_enable: head_dim %d is not covered by the map kernels", c->D / c->H); return VITX_ERR_UNSUPPORTED; }
     if (rollout && !attention_mean_supports(c->N, c->D, c->H)) { set_error("vitx_attn_enable: rollout keeps two N x N matrices per image and takes at most %d tokens (this model: %d)", kAttnMeanMaxTokens, c->N); return VITX_ERR_UNSUPPORTED; }
     HIP_TRY(hipSetDevice(c->device));
@@ -176,6 +177,10 @@ int vitx_feat_enable(vitx_ctx *c, int flags, uint64_t layer_mask) {
     c->feat_flags = 0; c->feat_mask = 0; c->feat_fpi = 0; c->feat_cap = 0; c->feat_n = 0;
     if (!flags) return VITX_OK;
     if (!layer_mask) layer_mask = 1ull << (c->L - 1);
+    if (c->map && (flags & VITX_FEAT_CLS) && layer_mask != 1ull << (c->L - 1)) {
+        set_error("vitx_feat_enable: VITX_FEAT_CLS of a model with the attention-pooling head is the pooled embedding: it exists for the last layer only (mask 0x%llx)", (unsigned long long)layer_mask);
+        return VITX_ERR_ARG;
+    }
     c->feat_flags = flags;                    // feat_layer_floats() reads it
     const int cap = c->pass_cap();
     const size_t fpi = (size_t)layer_slot(layer_mask, c->L) * c->feat_layer_floats();

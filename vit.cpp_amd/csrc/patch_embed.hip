@@ -13,7 +13,8 @@
 //     exactly where ggml's im2col emits fp16, and writes two 16-byte slots of the swizzled image;
 //   * the epilogue (epilogue16.h, EPI_PATCH) adds bias and pos_embed[1 + patch], scatters to token row image * N + T + patch (T = 1 + R
 //     prefix tokens, GemmArgs::prefix), and the lanes that hold patch 0 of an image also write its class row cls_token + pos_embed[0] and
-//     its R register rows reg_token[r] -- copied as they are: registers carry no position embedding.
+//     its R register rows reg_token[r] -- copied as they are: registers carry no position embedding.  cls == nullptr (a model without a
+//     class token: prefix 0): no prefix row is written and patch t takes pos[t].
 // 0.7 % of the forward's FLOPs: a plain double-buffered kernel, not the persistent one.
 #include "device_common.h"
 #include "kernels.h"
@@ -138,6 +139,7 @@ __global__ __launch_bounds__(256) void patch_embed_kernel(GemmArgs g, const floa
     else epilogue16<T, EPI_PATCH, 4, 4, false>(g, acc, row0, col0);
     // class rows (vit.cpp:794-797): token 0 of image b = cls_token + pos_embed[0]; written by the lanes that hold patch 0 of that image,
     // and behind it the image's register rows 1 .. prefix - 1 = reg_token[r]
+    if (g.prefix == 0) return;          // a model without a class token (VITX_POOL_MAP): an image is its patch rows
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const int row = row0 + t * 16;
@@ -177,10 +179,10 @@ hipError_t prepare_patch_embed() {       // device bring-up
 hipError_t launch_patch_embed(int dtype, const float *img, const void *w_perm, const float *bias, const float *pos, const float *cls, const float *reg, int n_reg,
                               float *X, int n_img, int S, int P, int Cin, int D, int n_pad, int k_pad, hipStream_t stream) {
     const int gsz = S / P, tpi = gsz * gsz;
-    if (n_img <= 0 || P <= 0 || S % P || n_pad % pe::BN || k_pad % pe::BK || k_pad < Cin * P * P || D % 4 || n_reg < 0 || (n_reg > 0 && !reg)) return hipErrorInvalidValue;
+    if (n_img <= 0 || P <= 0 || S % P || n_pad % pe::BN || k_pad % pe::BK || k_pad < Cin * P * P || D % 4 || n_reg < 0 || (n_reg > 0 && (!reg || !cls))) return hipErrorInvalidValue;
     GemmArgs g{};
     g.W = w_perm; g.bias = bias; g.out = X; g.pos = pos;
-    g.M_real = n_img * tpi; g.M = (g.M_real + pe::BM - 1) / pe::BM * pe::BM; g.N = D; g.N_pad = n_pad; g.K = k_pad; g.ldw = k_pad; g.ldo = D; g.tpi = tpi; g.prefix = 1 + n_reg;
+    g.M_real = n_img * tpi; g.M = (g.M_real + pe::BM - 1) / pe::BM * pe::BM; g.N = D; g.N_pad = n_pad; g.K = k_pad; g.ldw = k_pad; g.ldo = D; g.tpi = tpi; g.prefix = cls ? 1 + n_reg : 0;
     const int grid = (g.M / pe::BM) * (n_pad / pe::BN);
     if (dtype == DT_F16) hipLaunchKernelGGL(patch_embed_kernel<_Float16>, dim3(grid), dim3(256), pe::LDS_BYTES, stream, g, img, cls, reg, S, P, Cin, gsz);
     else hipLaunchKernelGGL(patch_embed_kernel<__bf16>, dim3(grid), dim3(256), pe::LDS_BYTES, stream, g, img, cls, reg, S, P, Cin, gsz);

@@ -52,12 +52,14 @@ extern "C" int vitx_model_resize_file(const char *path_in, const char *path_out,
     if (rc != VITX_OK) return rc;
     const vitx_hparams hp = m->hp;
     const int in_chans = m->in_chans;
+    const bool map_head = m->head_pool == VITX_POOL_MAP;
     const bool has_preproc = m->has_preproc;
     const vitx_preproc pp_in = m->preproc;
     std::vector<float> pos;
     if (const HostTensor *t = m->find("pos_embed")) { pos.resize((size_t)t->nelements()); t->decode_f32(pos.data()); }
     vitx_model_free(m);
     if (img_size % hp.patch_size) { set_error("vitx_model_resize_file: img_size %d is not a multiple of the patch size %d", img_size, hp.patch_size); return VITX_ERR_ARG; }
+    if (map_head) { set_error("vitx_model_resize_file: a file with the attention-pooling head has a position table without a class row: resampling it is not supported yet"); return VITX_ERR_UNSUPPORTED; }
     if (in_chans == 1 && img_size != hp.img_size) { set_error("vitx_model_resize_file: a ViTSTR file stays at its own img_size (%d)", hp.img_size); return VITX_ERR_UNSUPPORTED; }
     float pp_slots[16] = {0};
     if (has_preproc) {                                                // the model's preprocessing follows the size (vitx_preproc_at_size)

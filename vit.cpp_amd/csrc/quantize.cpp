@@ -88,6 +88,9 @@ static bool ends_with(const std::string &s, const char *suffix) {
     const size_t n = strlen(suffix);
     return s.size() >= n && s.compare(s.size() - n, n, suffix) == 0;
 }
+// the reference's selection (quantize.cpp:207-223) over the tensors it knows; the attention-pooling head (attn_pool.*, about 5 % of a base
+// model) is no tensor of the reference's and is copied through byte for byte
+static bool is_quantised(const HostTensor &t) { return t.n_dims == 2 && ends_with(t.name, "weight") && t.name.compare(0, 10, "attn_pool.") != 0; }
 
 }  // namespace vitx
 
@@ -106,7 +109,7 @@ extern "C" int vitx_quantize_file(const char *path_in, const char *path_out, int
     // validate every tensor BEFORE any byte is written, then write to a temporary file that replaces path_out only on success:
     // a failure never leaves a truncated model behind
     for (const HostTensor &t : m->tensors) {
-        if (!(t.n_dims == 2 && ends_with(t.name, "weight"))) continue;
+        if (!is_quantised(t)) continue;
         if (t.type != T_F32 && t.type != T_F16) { set_error("vitx_quantize_file: tensor '%s' is already quantised (type %d)", t.name.c_str(), t.type); vitx_model_free(m); return VITX_ERR_FORMAT; }
         if (t.ne[0] % 32) { set_error("vitx_quantize_file: row length %lld of '%s' is not a multiple of 32", (long long)t.ne[0], t.name.c_str()); vitx_model_free(m); return VITX_ERR_FORMAT; }
     }
@@ -120,7 +123,7 @@ extern "C" int vitx_quantize_file(const char *path_in, const char *path_out, int
     std::vector<float> f32;
     std::vector<uint8_t> blocks;
     for (const HostTensor &t : m->tensors) {
-        const bool quantize = t.n_dims == 2 && ends_with(t.name, "weight");
+        const bool quantize = is_quantised(t);
         int32_t out_type = t.type;
         if (quantize) {
             if (t.type != T_F32 && t.type != T_F16) { set_error("vitx_quantize_file: tensor '%s' is already quantised (type %d)", t.name.c_str(), t.type); rc = VITX_ERR_FORMAT; break; }

@@ -19,6 +19,8 @@ Two more ("activation, epsilon and pre-norm"): `arch` f32 [4] = {activation, eps
 f32 [D] directly after pos_embed.  All three are 1-D, so write_model stores them in f32 like every other vector, in the order it is given them.
 One more ("each model's own preprocessing"): `preproc` f32 [16] = {resize_mode, resize_a, resize_b, filter, crop, crop_round, mean255 r g b, std255
 r g b, 0, 0, 0, 0}, directly after `arch` (first without it): preproc_slots builds it, write_model(preproc=) places it, ModelFile.preproc reads it.
+One more ("no class token and the attention-pooling head"): the thirteen `attn_pool.*` tensors after norm.bias, in a file without cls_token whose
+pos_embed has g^2 rows.  `attn_pool.latent` [1][1][D] stays f32; the matrices are f16 under every ftype >= 1: they are never block-quantised.
 """
 from __future__ import annotations
 
@@ -269,6 +271,13 @@ def write_model(path: str, hp: HParams, tensors: Dict[str, np.ndarray], id2label
             raise ValueError("reg_token is written directly after cls_token")
     if registers is not None and registers != have_r:
         raise ValueError(f"registers={registers}, but the tensors hold {have_r} register tokens")
+    pool_names = [k for k in tensors if k.startswith("attn_pool.")]
+    if pool_names:
+        if "cls_token" in tensors or "reg_token" in tensors:
+            raise ValueError("attn_pool.*: a model with the attention-pooling head has no class or register token")
+        g = hp.img_size // hp.patch_size
+        if tuple(np.shape(tensors["pos_embed"])) != (1, g * g, D):
+            raise ValueError(f"pos_embed must be [1][{g * g}][{D}] beside attn_pool.* (no class row), got {np.shape(tensors['pos_embed'])}")
     if "head.weight" in tensors:
         hw = np.shape(tensors["head.weight"])
         if len(hw) != 2 or hw[1] not in (D, 2 * D):
@@ -289,11 +298,11 @@ def write_model(path: str, hp: HParams, tensors: Dict[str, np.ndarray], id2label
             data = np.asarray(t, np.float32)
             if name == "patch_embed.proj.bias":
                 data = data.reshape(1, data.shape[0], 1, 1)              # convert:150-151
-            keep_f32 = data.ndim == 1 or name in ("pos_embed", "cls_token", "reg_token") or name == "patch_embed.proj.bias"
+            keep_f32 = data.ndim == 1 or name in ("pos_embed", "cls_token", "reg_token", "attn_pool.latent") or name == "patch_embed.proj.bias"
             if ftype == 0 and not (patch_f16 and name == "patch_embed.proj.weight"):
                 keep_f32 = True
             ttype = F32 if keep_f32 else F16
-            if not keep_f32 and ftype in QUANTIZERS and data.ndim == 2 and name.endswith("weight"):
+            if not keep_f32 and ftype in QUANTIZERS and data.ndim == 2 and name.endswith("weight") and not name.startswith("attn_pool."):
                 ttype = ftype
             nb = name.encode("utf-8")
             f.write(struct.pack("<iii", data.ndim, len(nb), ttype))

@@ -98,7 +98,7 @@ int vit_predict_batch(const vit_model &model, vit_state &state, const image_f32 
                       std::vector<std::vector<std::pair<float, int>>> &predictions, bool print = false);
 // NEW, no counterpart in the reference: the embeddings of n preprocessed images -- the f32 final-norm features of the last layer
 // (include/vitx.h, "image embeddings and token features").  flags = VITX_FEAT_CLS, VITX_FEAT_MEAN, VITX_FEAT_TOKENS, optionally | VITX_FEAT_L2;
-// out[i] = image i's floats in the order [cls D][mean D][tokens (N-T) * D] (the selected parts; T = 1 + the model's register tokens).  state.prediction holds the class
+// out[i] = image i's floats in the order [cls D][mean D][tokens (N-T) * D] (the selected parts; T = 1 + the model's register tokens, 0 for a model with the attention-pooling head, whose cls part is the pooled embedding).  state.prediction holds the class
 // probabilities of the same forward; the features are switched off again before returning.  0 ok / 1 failure.
 int vit_embed_batch(const vit_model &model, vit_state &state, const image_f32 *imgs, int n, int flags, std::vector<std::vector<float>> &out);
 int vit_embed(const vit_model &model, vit_state &state, const image_f32 &img1, int flags, std::vector<float> &out);
