@@ -173,8 +173,8 @@ int vitx_model_pool_query(const vitx_model *m, float *out /* [H][D] */);
  * Rounding points of the activation are those of tanh-GELU for all three: VITX_F16 rounds the argument and the result to fp16 (ggml's fp16
  * tables: ggml_gelu, ggml_gelu_quick), VITX_BF16 rounds only the stored value.
  * With a pre-norm, stage 0 of the residual-stream trace is the stream that ENTERS layer 0, i.e. after the pre-norm.
- * A CLIP file's head is the bias-free visual projection: its logits are CLIP's image_embeds (L2-normalise them on the host), its
- * "probabilities" mean nothing.
+ * A CLIP file's head is the bias-free visual projection: its logits are CLIP's image_embeds (L2-normalise them on the host, or
+ * give the context a bank of text embeddings: "zero-shot classification" below), its "probabilities" mean nothing.
  * ViTSTR (one-channel) files with a pre-norm or an activation other than tanh-GELU, and VITX_MXFP8 contexts of a file whose activation is not
  * tanh-GELU, are VITX_ERR_UNSUPPORTED at context creation (eps and the pre-norm do work under VITX_MXFP8). */
 enum vitx_activation { VITX_ACT_GELU_TANH = 0, VITX_ACT_GELU_ERF = 1, VITX_ACT_QUICK_GELU = 2 };
@@ -671,6 +671,62 @@ int vitx_op_patch_embed(int dtype, const void *d_img, const void *d_w, const voi
                         void *d_X, int n_img, int S, int P, int Cin, int D, void *stream);
 int vitx_op_attention_pool(const void *d_x, long row_stride, long img_stride, const void *d_ln_w, const void *d_ln_b, float eps, const void *d_u, void *d_M,
                            void *d_p /* [n_img][H][N] or NULL */, int n_img, int N, int D, int H, void *stream);
+
+/* ---- zero-shot classification (CLIP, SigLIP): a bank of class embeddings --------- */
+/* An opt-in output of the forward, in the manner of the maps and the features.  A context is given a BANK: K unit-length class (text) embeddings
+ * of width E, a kind, a scale and a bias; every forward then also writes [n][K] zero-shot logits and probabilities.  Nothing else the forward
+ * writes changes (probabilities and logits are the same bits with a bank set and without); with no bank nothing is launched or allocated.
+ * For one image, z = its f32 embedding of width E:
+ *   a VITX_POOL_MAP context:          z = the pooled embedding e [D], the value VITX_FEAT_CLS returns (unnormalised); E = D = hidden_size;
+ *   every other classifier context:   z = the f32 logits row [C] of the head GEMM -- image_embeds for a CLIP file; E = C = num_classes.  It is the row
+ *                                     the caller gets in `logits`, computed whether or not the caller passes d_logits.
+ * Per image:
+ *   ss = sum z_i^2 in f32, in a fixed order that depends on E only; nrm = sqrtf(ss), IEEE.
+ *   a_i = RNE_dtype(z_i / nrm), IEEE division; an all-zero z gives a = 0.  (VITX_FEAT_L2's rule.  The two are separate device functions: that
+ *     one follows the LayerNorm tables' column ownership and exists for their widths only, this one takes any E that is a multiple of 64.)
+ *   dtype = the context's operand type; a VITX_MXFP8 context uses bf16 here, as its head does.
+ *   c_k = sum_i a_i * RNE_dtype(t_{k,i}), f32 accumulation on the MFMA: the bank GEMM is the head's GEMM dispatcher, so the forward's shape gets the
+ *     family the dispatcher chooses.  t = the bank row as given: the engine does NOT renormalise it.
+ *   l_k = c_k * scale + bias in f32: one multiply, one add, no contraction.
+ *   VITX_ZS_SOFTMAX (CLIP):  p_k = expf(l_k - max_j l_j) / sum_j expf(l_j - max_j l_j), f32 expf, over the K real classes only (the sum: per thread of
+ *     a 256-thread workgroup over k = t, t + 256, ... ascending, a butterfly over each wave's lanes, then the four waves in order).
+ *   VITX_ZS_SIGMOID (SigLIP): p_k = 1 / (1 + expf(-l_k)), evaluated as written for l_k <= 0 and as 1 - 1 / (1 + expf(l_k)) for l_k > 0 -- the
+ *     same function; the second form keeps the bits just below 1 that the first loses when 1 + expf(-l_k) rounds to 1 (16.7 < l_k < 17.3).
+ *   scale = the multiplier itself, exp(logit_scale) of both publishers; it must be finite.
+ * Determinism: an image's outputs are a function of its own z and the bank only -- the same bits at any batch size, position in the batch,
+ *   sub-batch cut and stream count.
+ * vitx_zeroshot_set(ctx, bank, K, E, kind, scale, bias): bank = host [K][E] f32.  Uploads it rounded (RNE) to the operand type and padded with
+ *   zero rows to the GEMM's column tile (128), allocates the operand rows and the accumulator scratch of every sub-batch slice and the output
+ *   buffer for the images one pass takes, synchronises the device.  Setting a bank again replaces it (new prompts need no new context);
+ *   bank NULL and K 0 turn the output off and free the buffers.
+ *   VITX_ERR_ARG: NULL bank with K > 0, K < 1 otherwise, E different from the context's embedding width, an unknown kind, a scale, bias or bank
+ *     entry that is not finite.  VITX_ERR_UNSUPPORTED: a ViTSTR context; E not a multiple of 64 (the GEMMs' K step); K above
+ *     vitx_zeroshot_max_classes(E) = the multiple of 128 below 0xf0000000 / (2 E): the padded bank must lie inside the 32-bit byte window the
+ *     GEMM kernels address their operands with (E 512: 3 932 160 classes; the score kernel itself takes any K).  VITX_ERR_NOMEM: an allocation
+ *     fails (the bank is then off).  All but the last are raised before any device call.
+ * While a bank is set, a forward of more than one pass (vitx_ctx_split) is VITX_ERR_ARG, and forwards do not use the hipGraph cache (as with the
+ *   maps and the features); profiling reports the three launches per sub-batch as class "zeroshot".
+ * vitx_zeroshot_classes: K (0 while off).  vitx_zeroshot_images: the images of the last forward made with a bank set (0 before any since
+ *   vitx_zeroshot_set).  vitx_zeroshot_read: synchronises and copies that forward's probabilities [n][K] and, unless NULL, logits [n][K];
+ *   VITX_ERR_ARG before any such forward or when n_floats_each < n * K.
+ * vitx_zeroshot_device: the device buffer itself, [capacity][2][K] f32 -- per image the probabilities, then the logits (NULL while off).  It is
+ *   written by the forward's streams: work that reads it is ordered after the caller's stream, like d_probs.
+ * vitx_group_* has no bank: a group computes probabilities only.
+ * vitx_op_zeroshot: the three launches on their own (device pointers; only enqueues).  Row i of z is read at d_z + i * z_stride floats (z_stride
+ *   >= E, a multiple of 4); d_bank [K_pad][E] in `dtype`, K_pad = K rounded up to 128, zero rows beyond K; d_a_scratch [n_pad][E] in `dtype`
+ *   and d_acc_scratch [n_pad + 1][K_pad] f32 with n_pad = n rounded up to 256 (the last row becomes the GEMM's zero bias; pad rows of a are
+ *   written as zeros, pad rows and columns of acc are neither written nor read); d_probs, d_logits [n][K] f32.  dtype VITX_F16 or VITX_BF16.
+ *   NULL pointers, n, K, E < 1, an unknown kind, a scale or bias that is not finite, a bad z_stride, d_z, d_bank or scratch not 16-byte
+ *   aligned: VITX_ERR_ARG; E not a multiple of 64 or K above vitx_zeroshot_max_classes(E): VITX_ERR_UNSUPPORTED (all before any device call). */
+enum vitx_zs_kind { VITX_ZS_SOFTMAX = 0, VITX_ZS_SIGMOID = 1 };
+int vitx_zeroshot_set(vitx_ctx *c, const float *bank /* host [K][E] f32 */, int K, int E, int kind, float scale, float bias);  /* bank NULL && K == 0: off, frees */
+int vitx_zeroshot_classes(const vitx_ctx *c);        /* K; 0 while off */
+int vitx_zeroshot_images(const vitx_ctx *c);
+int vitx_zeroshot_read(vitx_ctx *c, float *probs /* [n][K] */, float *logits /* [n][K] or NULL */, size_t n_floats_each);
+const void *vitx_zeroshot_device(const vitx_ctx *c); /* [capacity][2][K] f32: probs then logits per image; NULL while off */
+int vitx_zeroshot_max_classes(int E);                /* the bound on K for width E (0 for an E that is not a positive multiple of 64) */
+int vitx_op_zeroshot(int dtype, const void *d_z, long z_stride, const void *d_bank /* dtype, [K_pad][E], zero rows beyond K */,
+                     void *d_a_scratch, void *d_acc_scratch, void *d_probs, void *d_logits, int n, int K, int E, int kind, float scale, float bias, void *stream);
 
 /* ---- MXFP8 operands (VITX_MXFP8, encoding above) ------------------------------- */
 /* Host encoder: x f32 [rows][K] -> q [rows][k_pad] e4m3 bytes + scales [rows][k_pad / 32] (k_pad >= K, a multiple of 32; columns

@@ -28,6 +28,7 @@ GEMM_AUTO, GEMM_PP, GEMM_AUTO_SPLIT = 0, 1, 2          # vitx_op_gemm_ex `kernel
 ATTN_AUTO, ATTN_SINGLE, ATTN_FLOW, ATTN_PERSIST, ATTN_STREAM = 0, 1, 3, 4, 5   # vitx_op_attention_ex `kernel`
 ATTN_ROLLOUT = 1                # vitx_attn_enable flag
 FEAT_CLS, FEAT_MEAN, FEAT_TOKENS, FEAT_L2 = 1, 2, 4, 8      # vitx_feat_enable flags
+ZS_SOFTMAX, ZS_SIGMOID = 0, 1      # vitx_zs_kind: CLIP's softmax over the classes, SigLIP's sigmoid per class
 POOL_CLS, POOL_CLS_MEAN, POOL_MAP = 0, 1, 2      # vitx_model_head_pool: the head reads the class token, concat(cls, mean of the patch tokens), or the attention-pooled embedding
 PP_REF_BICUBIC, PP_REF_BILINEAR, PP_PIL_BILINEAR, PP_PIL_BICUBIC = 0, 1, 2, 3      # vitx_pp_filter: the reference's two, Pillow's Image.resize on u8
 PP_STRETCH, PP_SHORTEST_EDGE = 0, 1     # vitx_pp_resize
@@ -49,6 +50,7 @@ EXPORTS = [
     "vitx_model_activation", "vitx_model_has_pre_norm", "vitx_op_layernorm_f32",
     "vitx_model_preproc", "vitx_model_has_preproc", "vitx_preproc_at_size", "vitx_preprocess_ex", "vitx_preprocess_ex_device", "vitx_preprocess_ex_device_supports",
     "vitx_model_num_prefix", "vitx_model_pool_query", "vitx_op_attention_pool",
+    "vitx_zeroshot_set", "vitx_zeroshot_classes", "vitx_zeroshot_images", "vitx_zeroshot_read", "vitx_zeroshot_device", "vitx_zeroshot_max_classes", "vitx_op_zeroshot",
 ]
 
 
@@ -213,6 +215,13 @@ def lib():
             L.vitx_model_num_prefix.argtypes = [vp]
             L.vitx_model_pool_query.argtypes = [vp, C.POINTER(C.c_float)]
             L.vitx_op_attention_pool.argtypes = [vp, C.c_long, C.c_long, vp, vp, C.c_float, vp, vp, vp, ip, ip, ip, ip, vp]
+        if hasattr(L, "vitx_zeroshot_set"):
+            fp = C.POINTER(C.c_float)
+            L.vitx_zeroshot_set.argtypes = [vp, fp, ip, ip, ip, C.c_float, C.c_float]
+            L.vitx_zeroshot_classes.argtypes = [vp]; L.vitx_zeroshot_images.argtypes = [vp]; L.vitx_zeroshot_max_classes.argtypes = [ip]
+            L.vitx_zeroshot_read.argtypes = [vp, fp, fp, C.c_size_t]
+            L.vitx_zeroshot_device.restype = C.c_void_p; L.vitx_zeroshot_device.argtypes = [vp]
+            L.vitx_op_zeroshot.argtypes = [ip, vp, C.c_long, vp, vp, vp, vp, vp, ip, ip, ip, ip, C.c_float, C.c_float, vp]
         _lib = L
     return _lib
 
@@ -585,6 +594,34 @@ class Context:
         (vitx_feat_device); the layout per image is feat_read()'s order.  Ordered after the forward's stream, like d_probs."""
         return int(lib().vitx_feat_device(self._h) or 0), int(lib().vitx_feat_floats(self._h))
 
+    def zeroshot_set(self, embeds: Optional[np.ndarray], kind: int = ZS_SOFTMAX, scale: float = 1.0, bias: float = 0.0) -> None:
+        """Zero-shot logits and probabilities of every later forward against the bank `embeds` [K, E] f32 of unit-length class embeddings
+        (vitx_zeroshot_set; E = the context's embedding width: num_classes of a CLIP file, hidden_size of a SigLIP file).  kind ZS_SOFTMAX /
+        ZS_SIGMOID, scale = exp(logit_scale), bias = logit_bias.  None turns the output off and frees its buffers."""
+        if embeds is None:
+            check(lib().vitx_zeroshot_set(self._h, None, 0, 0, 0, 0.0, 0.0), "vitx_zeroshot_set")
+            return
+        e = np.ascontiguousarray(embeds, dtype=np.float32)
+        if e.ndim != 2:
+            raise ValueError("zeroshot_set: embeds must be [K, E]")
+        check(lib().vitx_zeroshot_set(self._h, e.ctypes.data_as(C.POINTER(C.c_float)), e.shape[0], e.shape[1], int(kind), float(scale), float(bias)), "vitx_zeroshot_set")
+
+    def zeroshot_read(self, n: Optional[int] = None, want_logits: bool = False):
+        """Zero-shot probabilities [n, K] f32 of the last forward made with a bank set (and, want_logits, the logits).  `n`, if given, must be that batch."""
+        K, have = lib().vitx_zeroshot_classes(self._h), lib().vitx_zeroshot_images(self._h)
+        if n is not None and n != have:
+            raise ValueError(f"zeroshot_read: the last forward with a bank set had {have} images, not {n}")
+        probs = np.empty((max(have, 1), max(K, 1)), np.float32)
+        logits = np.empty_like(probs) if want_logits else None
+        fp = C.POINTER(C.c_float)
+        check(lib().vitx_zeroshot_read(self._h, probs.ctypes.data_as(fp), logits.ctypes.data_as(fp) if want_logits else None, have * K), "vitx_zeroshot_read")
+        return (probs, logits) if want_logits else probs
+
+    def zeroshot_device(self) -> Tuple[int, int]:
+        """(device pointer of the zero-shot buffer [capacity][2][K] f32 -- per image the probabilities, then the logits --, K) for callers that
+        stay on the GPU (vitx_zeroshot_device).  Ordered after the forward's stream, like d_probs."""
+        return int(lib().vitx_zeroshot_device(self._h) or 0), int(lib().vitx_zeroshot_classes(self._h))
+
     def synchronize(self) -> None:
         check(lib().vitx_ctx_synchronize(self._h), "vitx_ctx_synchronize")
 
@@ -723,6 +760,20 @@ def op_attention_pool(d_x: int, row_stride: int, img_stride: int, d_ln_w: int, d
     """vitx_op_attention_pool: the pooling kernel of the attention-pooling head (device pointers, strides in floats): M [n_img, H, D] f32 and,
     with d_p, the probabilities [n_img, H, N] f32."""
     check(lib().vitx_op_attention_pool(d_x, row_stride, img_stride, d_ln_w, d_ln_b, eps, d_u, d_M, d_p or None, n_img, N, D, H, stream or None), "vitx_op_attention_pool")
+
+
+def zeroshot_max_classes(E: int) -> int:
+    """vitx_zeroshot_max_classes: the largest bank (classes) of width E the bank GEMM's 32-bit window takes; 0 for an E that is not a multiple of 64."""
+    return int(lib().vitx_zeroshot_max_classes(E))
+
+
+def op_zeroshot(dtype: int, d_z: int, z_stride: int, d_bank: int, d_a: int, d_acc: int, d_probs: int, d_logits: int, n: int, K: int, E: int,
+                kind: int = ZS_SOFTMAX, scale: float = 1.0, bias: float = 0.0, stream: int = 0) -> None:
+    """vitx_op_zeroshot: the zero-shot launches on their own (device pointers; z_stride in floats).  d_bank [K_pad, E] in `dtype` (K_pad = K
+    rounded up to 128, zero rows beyond K), d_a [n_pad, E] in `dtype`, d_acc [n_pad + 1, K_pad] f32 (n_pad = n rounded up to 256),
+    d_probs and d_logits [n, K] f32."""
+    check(lib().vitx_op_zeroshot(dtype, d_z or None, z_stride, d_bank or None, d_a or None, d_acc or None, d_probs or None, d_logits or None, n, K, E,
+                                 int(kind), float(scale), float(bias), stream or None), "vitx_op_zeroshot")
 
 
 def mx_k_pad(K: int) -> int:

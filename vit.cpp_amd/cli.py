@@ -7,6 +7,7 @@ directory-walk accuracy harness:
     python vit_cli.py -m model.gguf (-i image.jpg | --dir DIR) --embed out.npy [--embed-kind cls|mean|tokens] [--embed-l2]   # + the embeddings
     python vit_cli.py -m model.gguf ... --img-size 384 [--pos-interp bicubic|bicubic-aa]   # run at another input size than the file's
     python vit_cli.py -m model.gguf ... [--preprocess model|reference]   # the file's own preprocessing (default) or the reference's for any file
+    python vit_cli.py -m clip.gguf -i image.jpg -k 5 --zero-shot bank.npz   # zero-shot classes of a CLIP / SigLIP file (bank: convert.py --zero-shot-out)
 
 --preprocess model follows the file's `preproc` tensor (include/vitx.h "each model's own preprocessing": what convert.py reads from a
 HuggingFace preprocessor_config.json -- CLIP: Pillow-bicubic shortest edge 224, centre crop 224, CLIP's mean / std; DINOv2: shortest edge 256,
@@ -44,8 +45,7 @@ def attn_pgm(grid: np.ndarray, img_size: int) -> bytes:
     return f"P5\n{img_size} {img_size}\n255\n".encode() + u8[idx][:, idx].tobytes()
 
 
-def main(argv: List[str] | None = None) -> int:
-    from . import binding
+def make_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="vit", description="ViT inference on MI355X (drop-in for staghado/vit.cpp's CLI)")
     ap.add_argument("-m", "--model", default="../ggml-model-f16.gguf")
     ap.add_argument("-i", "--inp", default="../assets/tench.jpg")
@@ -78,7 +78,18 @@ def main(argv: List[str] | None = None) -> int:
     ap.add_argument("--pos-interp", default="bicubic", choices=["bicubic", "bicubic-aa"],
                     help="with --img-size: bicubic = F.interpolate(mode='bicubic') (HuggingFace interpolate_pos_encoding, DINO); "
                          "bicubic-aa = the same with antialias=True (timm resample_abs_pos_embed)")
+    ap.add_argument("--zero-shot", default=None, metavar="BANK.npz",
+                    help="with -i, a CLIP or SigLIP file: classify against the bank of text embeddings in BANK.npz (convert.py --zero-shot-out) instead of the "
+                         "file's own head; the ' > label : 0.xx' lines are the bank's labels and the zero-shot probabilities (softmax for CLIP, sigmoid for SigLIP)")
+    return ap
+
+
+def main(argv: List[str] | None = None) -> int:
+    from . import binding
+    ap = make_parser()
     a = ap.parse_args(argv)
+    if a.zero_shot and a.dir is not None:
+        ap.error("--zero-shot takes the single image of -i, not --dir")
     if a.attn_map and a.dir is not None:
         ap.error("--attn-map takes the single image of -i, not --dir")
     if a.embed is None and (a.embed_l2 or a.embed_kind != "cls"):
@@ -115,6 +126,15 @@ def main(argv: List[str] | None = None) -> int:
         preprocess = lambda img: binding.preprocess(img, S, interp)
     geometry = dict(img_size=a.img_size, pos_interp=binding.POS_BICUBIC_AA if a.pos_interp == "bicubic-aa" else binding.POS_BICUBIC) if a.img_size else {}
 
+    bank = None
+    if a.zero_shot:
+        from .convert import load_bank
+        try:
+            bank = load_bank(a.zero_shot)
+        except (OSError, ValueError) as e:
+            print(f"main: failed to load the zero-shot bank from '{a.zero_shot}': {e}", file=sys.stderr)
+            return 1
+
     if a.dir is None:
         try:
             img0 = _decode(a.inp)
@@ -138,6 +158,12 @@ def main(argv: List[str] | None = None) -> int:
             ctx.attn_enable([] if a.attn_kind == "rollout" else [L - 1], rollout=a.attn_kind == "rollout")
         if a.embed:
             ctx.feat_enable(**feat)
+        if bank:
+            try:
+                ctx.zeroshot_set(bank["embeds"], bank["kind"], bank["scale"], bank["bias"])
+            except binding.VitxError as e:
+                print(f"main: the bank of '{a.zero_shot}' does not fit this model: {e}", file=sys.stderr)
+                return 1
         probs = ctx.forward(img1[None])[0]
         if a.embed:
             np.save(a.embed, last(ctx))
@@ -148,10 +174,13 @@ def main(argv: List[str] | None = None) -> int:
             with open(a.attn_map, "wb") as f:
                 f.write(attn_pgm(ctx.attn_grid(m), S))
             print(f"main: wrote the {a.attn_kind} attention map to '{a.attn_map}'", file=sys.stderr)
+        label = model.label
+        if bank:                                                            # the bank's classes in place of the file's own head
+            probs, label = ctx.zeroshot_read(1)[0], lambda i: bank["labels"][i]
         idx, val = binding.topk(probs, a.topk)
         print("", file=sys.stderr)
         for i, p in zip(idx, val):                                          # vit.cpp:1062-1067
-            print(f" > {model.label(i)} : {p:.2f}")
+            print(f" > {label(i)} : {p:.2f}")
         t_all = time.perf_counter() - t_main
         print("\n", file=sys.stderr)
         print(f"main:    model load time = {t_load * 1e3:8.2f} ms", file=sys.stderr)

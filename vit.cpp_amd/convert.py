@@ -16,7 +16,8 @@ written without its settings and run with tanh-GELU and 1e-6; it now carries the
 CLIP (CLIPVisionModelWithProjection; CLIPModel: its vision tower and visual_projection; CLIPVisionModel with --no-head): class_embedding ->
 cls_token, position_embedding -> pos_embed, the bias-free patch convolution gets a zero bias, pre_layrnorm -> `pre_norm.*` (directly after
 pos_embed), q/k/v_proj are fused, post_layernorm -> norm, and the bias-free visual_projection [E][D] becomes head.weight with a zero head.bias:
-the file has E "classes" labelled dim_0 .. dim_{E-1}, its logits are CLIP's image_embeds and its probabilities mean nothing.
+the file has E "classes" labelled dim_0 .. dim_{E-1}, its logits are CLIP's image_embeds and its probabilities mean nothing (zero-shot
+probabilities come from a bank of text embeddings: below).
 
 SigLIP (SiglipVisionModel; SiglipModel: its vision tower): there is NO class token -- position_embedding [g^2][D] -> pos_embed [1][g^2][D] --, q/k/v_proj
 are fused, post_layernorm -> norm, and the multi-head attention-pooling head becomes the thirteen `attn_pool.*` tensors of include/vitx.h ("no
@@ -47,7 +48,15 @@ the file without the tensor (the reference's stretch and ImageNet mean / std the
 --pp-resize N (shortest edge), --pp-crop N, --pp-filter, --pp-mean, --pp-std and --pp-crop-round state one; with none of them given no tensor is
 written and the reference's files keep their bytes.
 
+Zero-shot banks (include/vitx.h "zero-shot classification"): zeroshot_bank() runs the TEXT tower of a transformers CLIPModel / SiglipModel on
+token ids and returns what vitx_zeroshot_set takes -- the unit-length text embeddings [K][E], the kind (softmax for CLIP, sigmoid for SigLIP),
+exp(logit_scale) and logit_bias (0 for CLIP); `groups` averages the normalised embeddings of several prompts per class and renormalises (prompt
+ensembling).  --zero-shot-ids ids.npy [--zero-shot-labels labels.txt] --zero-shot-out bank.npz writes it as an .npz with `embeds`, `labels`, `kind`,
+`scale`, `bias` (save_bank / load_bank; vit_cli.py --zero-shot reads it); the model file itself is converted as usual.  The engine has no text
+encoder and no tokenizer: the bank is computed here, once per set of prompts.
+
     python -m ... convert.py <hf_model_dir_or_name> <out.gguf> [--ftype 1] [--no-head] [--no-preproc]
+    python -m ... convert.py <hf_clip_or_siglip_dir> <out.gguf> --zero-shot-ids ids.npy [--zero-shot-labels labels.txt] --zero-shot-out bank.npz
     python -m ... convert.py --timm-state-dict <checkpoint.pth> <out.gguf> [--ftype 1] [--heads H] [--labels labels.json] [--act erf] [--eps 1e-6]
 
 A timm state dict carries no config, so --act {tanh,erf,quick} and --eps state its settings; without them the file is the reference's (tanh-GELU,
@@ -517,6 +526,73 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
     return hp
 
 
+ZS_SOFTMAX, ZS_SIGMOID = 0, 1                   # enum vitx_zs_kind
+
+
+def _l2_rows(x: np.ndarray) -> np.ndarray:
+    return x / np.sqrt((x * x).sum(axis=1, keepdims=True))
+
+
+def zeroshot_bank(model, input_ids, attention_mask=None, groups=None):
+    """The zero-shot bank of a transformers CLIPModel / SiglipModel: (embeds [K][E] float64, kind, scale, bias).
+
+    Row p of `input_ids` [P][T] is one tokenised prompt; its text embedding (the text tower's pooled, projected output) is L2-normalised.
+    groups = None: K = P, class k is prompt k.  groups [P] of class ids 0 .. K-1: the normalised rows of each class are averaged and the mean is
+    normalised again (prompt ensembling; every class needs at least one prompt).  kind = ZS_SOFTMAX for CLIP, ZS_SIGMOID for SigLIP;
+    scale = exp(logit_scale), bias = logit_bias (0 for CLIP): logits_per_image = scale * image_embeds . embeds^T + bias.
+    The arithmetic past the text tower is float64 whatever the model's dtype."""
+    import torch
+    mt = getattr(model.config, "model_type", "")
+    if mt not in ("clip", "siglip"):
+        raise ValueError(f"zeroshot_bank: a CLIPModel or a SiglipModel is needed (both towers and logit_scale), not model_type '{mt}'")
+    ids = torch.as_tensor(np.asarray(input_ids), dtype=torch.long)
+    if ids.ndim != 2:
+        raise ValueError("zeroshot_bank: input_ids must be [prompts][tokens]")
+    kw = {} if attention_mask is None else {"attention_mask": torch.as_tensor(np.asarray(attention_mask), dtype=torch.long)}
+    with torch.no_grad():
+        f = model.get_text_features(input_ids=ids, **kw)
+    if not torch.is_tensor(f):             # transformers 5.x returns the tower's output object: pooler_output holds the projected features
+        f = f.pooler_output
+    e = _l2_rows(f.detach().to(torch.float64).cpu().numpy())
+    if groups is not None:
+        g = np.asarray(groups, dtype=np.int64)
+        if g.shape != (e.shape[0],) or g.min() < 0:
+            raise ValueError("zeroshot_bank: groups must give one class id >= 0 per prompt")
+        K = int(g.max()) + 1
+        counts = np.bincount(g, minlength=K)
+        if (counts == 0).any():
+            raise ValueError(f"zeroshot_bank: class {int(np.flatnonzero(counts == 0)[0])} has no prompt")
+        mean = np.zeros((K, e.shape[1]), np.float64)
+        np.add.at(mean, g, e)
+        e = _l2_rows(mean / counts[:, None])
+    scale = float(np.exp(np.float64(model.logit_scale.detach().to(torch.float64).reshape(-1)[0].item())))
+    bias = float(model.logit_bias.detach().to(torch.float64).reshape(-1)[0].item()) if mt == "siglip" else 0.0
+    return e, (ZS_SIGMOID if mt == "siglip" else ZS_SOFTMAX), scale, bias
+
+
+def save_bank(path: str, embeds, kind: int, scale: float, bias: float, labels=None) -> None:
+    """The bank file: an .npz with embeds [K][E] f32, labels [K] (class_<k> where none are given), kind, scale, bias."""
+    e = np.asarray(embeds, np.float32)
+    lab = [f"class_{k}" for k in range(e.shape[0])] if labels is None else [str(l) for l in labels]
+    if e.ndim != 2 or len(lab) != e.shape[0]:
+        raise ValueError(f"save_bank: {len(lab)} labels for embeds of shape {e.shape}")
+    with open(path, "wb") as f:            # (np.savez on a name would append .npz)
+        np.savez(f, embeds=e, labels=np.asarray(lab, dtype=np.str_), kind=np.int32(kind), scale=np.float32(scale), bias=np.float32(bias))
+
+
+def load_bank(path: str) -> dict:
+    """-> {"embeds" [K][E] f32, "labels" list of K str, "kind" int, "scale" float, "bias" float}; ValueError for a file that is not a bank."""
+    with np.load(path, allow_pickle=False) as z:
+        missing = [k for k in ("embeds", "labels", "kind", "scale", "bias") if k not in z.files]
+        if missing:
+            raise ValueError(f"load_bank: '{path}' lacks {', '.join(missing)}")
+        b = dict(embeds=np.ascontiguousarray(z["embeds"], np.float32), labels=[str(l) for l in z["labels"]], kind=int(z["kind"]),
+                 scale=float(z["scale"]), bias=float(z["bias"]))
+    if b["embeds"].ndim != 2 or len(b["labels"]) != b["embeds"].shape[0] or b["kind"] not in (ZS_SOFTMAX, ZS_SIGMOID):
+        raise ValueError(f"load_bank: '{path}' is not a consistent bank (embeds {b['embeds'].shape}, {len(b['labels'])} labels, kind {b['kind']})")
+    return b
+
+
 def main(argv=None) -> int:
     import argparse
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
@@ -543,7 +619,21 @@ def main(argv=None) -> int:
     ap.add_argument("--pp-std", type=float, nargs=3, default=None, metavar=("R", "G", "B"), help="timm checkpoint: Normalize std on the 0..1 scale (default ImageNet's)")
     ap.add_argument("--pp-crop-round", default="", choices=["", "floor", "torchvision"],
                     help="timm checkpoint: the crop offset of an odd difference: floor (default; transformers) or torchvision (CenterCrop rounds half to even)")
+    ap.add_argument("--zero-shot-ids", default=None, metavar="IDS.npy", help="CLIPModel / SiglipModel directory: also write a zero-shot bank from these token ids, "
+                                                                              "an integer array [prompts][tokens] (IDS.mask.npy beside it, if present, is the attention mask)")
+    ap.add_argument("--zero-shot-prompts", default=None, metavar="PROMPTS.txt",
+                    help="the same from one prompt per line, tokenised with the tokenizer found in the model directory (padding='max_length', as both publishers do). "
+                         "UNTESTED: the tokenisation step has never run in this project's tests -- no tokenizer files were available to them; everything after "
+                         "the token ids is the tested --zero-shot-ids path")
+    ap.add_argument("--zero-shot-labels", default=None, metavar="LABELS.txt", help="one class name per line (default: the prompts themselves, or class_<k>)")
+    ap.add_argument("--zero-shot-out", default=None, metavar="BANK.npz", help="where the bank goes (embeds, labels, kind, scale, bias)")
     a = ap.parse_args(argv)
+    if (a.zero_shot_ids is None) == (a.zero_shot_prompts is None) and a.zero_shot_out:
+        ap.error("--zero-shot-out needs exactly one of --zero-shot-ids and --zero-shot-prompts")
+    if (a.zero_shot_ids or a.zero_shot_prompts or a.zero_shot_labels) and not a.zero_shot_out:
+        ap.error("--zero-shot-ids / --zero-shot-prompts / --zero-shot-labels need --zero-shot-out BANK.npz")
+    if a.zero_shot_out and a.timm_state_dict:
+        ap.error("a zero-shot bank needs the text tower of a HuggingFace CLIPModel / SiglipModel, not a timm state dict")
     pp_cli = dict(resize=a.pp_resize, crop=a.pp_crop, filt=a.pp_filter, mean=a.pp_mean, std=a.pp_std, crop_round=a.pp_crop_round)
     if not a.timm_state_dict and any(pp_cli.values()):
         ap.error("--pp-* describe a timm checkpoint (--timm-state-dict); a HuggingFace checkpoint brings its preprocessor_config.json")
@@ -572,6 +662,31 @@ def main(argv=None) -> int:
         return 0
     import transformers
     model_type = transformers.AutoConfig.from_pretrained(a.model).model_type
+    if a.zero_shot_out:
+        import os
+        if model_type not in ("clip", "siglip"):
+            ap.error(f"a zero-shot bank needs a CLIPModel or SiglipModel checkpoint (both towers), not model_type '{model_type}'")
+        both = (transformers.CLIPModel if model_type == "clip" else transformers.SiglipModel).from_pretrained(a.model).eval()
+        mask = None
+        if a.zero_shot_ids:
+            ids = np.load(a.zero_shot_ids)
+            mask_path = a.zero_shot_ids[:-4] + ".mask.npy" if a.zero_shot_ids.endswith(".npy") else a.zero_shot_ids + ".mask.npy"
+            if os.path.isfile(mask_path):
+                mask = np.load(mask_path)
+            labels = None
+        else:
+            with open(a.zero_shot_prompts) as f:
+                labels = [l.rstrip("\n") for l in f if l.strip()]
+            tok = transformers.AutoTokenizer.from_pretrained(a.model)(labels, padding="max_length", truncation=True, return_tensors="np")
+            ids = tok["input_ids"]
+            mask = tok.get("attention_mask") if model_type == "clip" else None        # SigLIP was trained without a mask
+        if a.zero_shot_labels:
+            with open(a.zero_shot_labels) as f:
+                labels = [l.rstrip("\n") for l in f if l.strip()]
+        embeds, kind, scale, bias = zeroshot_bank(both, ids, mask)
+        save_bank(a.zero_shot_out, embeds, kind, scale, bias, labels)
+        print(f"wrote {a.zero_shot_out}: {embeds.shape[0]} classes of width {embeds.shape[1]}, {'sigmoid' if kind == ZS_SIGMOID else 'softmax'}, scale {scale:.6g}, bias {bias:.6g}")
+        del both
     if model_type in ("dinov2", "dinov2_with_registers"):
         m = (transformers.AutoModel if a.no_head else transformers.AutoModelForImageClassification).from_pretrained(a.model).eval()
     elif model_type in ("clip", "clip_vision_model"):

@@ -22,11 +22,11 @@ namespace vitx {
 
 enum ProfClass {
     PC_GEMM_PATCH = 0, PC_LAYERNORM, PC_GEMM_QKV, PC_ATTENTION, PC_GEMM_PROJ, PC_GEMM_FC1, PC_GEMM_FC2,
-    PC_GEMM_HEAD, PC_SOFTMAX, PC_DEQUANT, PC_ATTENTION_CLS, PC_GEMM_TAIL, PC_ATTN_MAP, PC_FEATURES, PC_HEAD_POOL, PC_COUNT
+    PC_GEMM_HEAD, PC_SOFTMAX, PC_DEQUANT, PC_ATTENTION_CLS, PC_GEMM_TAIL, PC_ATTN_MAP, PC_FEATURES, PC_HEAD_POOL, PC_ZEROSHOT, PC_COUNT
 };
 inline const char *const kProfNames[PC_COUNT] = {"patch_embed", "layernorm", "gemm_qkv_bias", "attention", "gemm_proj_resid",
                                     "gemm_fc1_gelu", "gemm_fc2_resid", "gemm_head", "softmax", "dequant_weights", "attention_cls", "gemm_cls_tail", "attention_map",
-                                    "features", "head_pool"};
+                                    "features", "head_pool", "zeroshot"};
 static_assert(PC_COUNT <= VITX_PROF_MAX_CLASSES, "vitx_profile_read callers size their arrays by VITX_PROF_MAX_CLASSES");
 
 // A weight matrix kept in the file's block form on the device (quant.hip): `blocks` = N rows of K/32 blocks in the file's byte
@@ -220,6 +220,29 @@ struct vitx_ctx {
     // MEAN or TOKENS of the last layer need every row of it: no class-rows-only tail while they are on (as while the trace is)
     bool feat_last_all_rows() const { return (feat_flags & (VITX_FEAT_MEAN | VITX_FEAT_TOKENS)) && ((feat_mask >> (L - 1)) & 1); }
     void feat_free() { if (feat_out) (void)hipFree(feat_out); feat_out = nullptr; }
+    // zero-shot classification (vitx_zeroshot_set): nothing is allocated or launched while zs_K == 0
+    int zs_K = 0, zs_Kpad = 0;   // classes of the bank; its rows on the device (K rounded up to the GEMM's column tile `tn`, zero rows beyond K)
+    int zs_kind = 0;             // enum vitx_zs_kind
+    float zs_scale = 1.0f, zs_bias = 0.0f;
+    int zs_cap = 0;              // images the buffers hold (= the images one pass takes)
+    int zs_n = 0;                // images of the last forward made with a bank set (0: none since vitx_zeroshot_set)
+    void *zs_bank = nullptr;     // [zs_Kpad][zs_width()] operand type
+    float *zs_zero = nullptr;    // [zs_Kpad] zeros: the bank GEMM's bias
+    float *zs_out = nullptr;     // [zs_cap][2][zs_K]: per image the probabilities, then the logits
+    std::vector<void *> zs_a;    // per slice: [round_up(zs_cap, tm)][zs_width()] operand type, the normalised embeddings (the GEMM's A rows)
+    std::vector<float *> zs_acc; // per slice: [round_up(zs_cap, tm)][zs_Kpad] f32, the GEMM's output
+    bool zs_on() const { return zs_K != 0; }
+    int zs_width() const { return map ? D : C; }      // E: the pooled embedding e, or the head GEMM's logits row (CLIP: image_embeds)
+    void zs_free() {
+        for (void *p : zs_a) if (p) (void)hipFree(p);
+        for (float *p : zs_acc) if (p) (void)hipFree(p);
+        zs_a.clear(); zs_acc.clear();
+        if (zs_bank) (void)hipFree(zs_bank);
+        if (zs_zero) (void)hipFree(zs_zero);
+        if (zs_out) (void)hipFree(zs_out);
+        zs_bank = nullptr; zs_zero = nullptr; zs_out = nullptr;
+        zs_K = zs_Kpad = zs_cap = zs_n = 0;
+    }
     // hipGraph cache of the single-stream (small-batch) forward, opt-in (vitx_ctx_options::graph).  Key = (images, batch, outputs): the graph
     // bakes the pointers in.  An entry is captured the second time in a row its key is seen (one-off calls are never captured).
     // Measured (profiles/r02f/hipgraph_small_batch.txt): replaying the ~100 dependent launches as a graph takes the enqueue work off
@@ -251,6 +274,7 @@ struct vitx_ctx {
         if (trace_buf) (void)hipFree(trace_buf);
         attn_free();
         feat_free();
+        zs_free();
         for (void *p : allocs) (void)hipFree(p);
         if (stream) (void)hipStreamDestroy(stream);
     }

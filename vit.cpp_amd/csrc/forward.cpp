@@ -168,6 +168,23 @@ struct SliceForward {
         HIP_TRY(launch_pool_embed(sl.Xc, sl.Z, dt, o_cls, c->feat_fpi, (c->feat_flags & VITX_FEAT_L2) != 0, n, D, st));
         return VITX_OK;
     }
+    // Zero-shot classification (vitx_zeroshot_set), after the head: z = the f32 embedding rows of this sub-batch (row stride ldz floats) -> unit rows in
+    // the operand type, the bank GEMM through the dispatcher as the head's goes, then logits and probabilities at the images' global positions
+    int zeroshot(const float *z, long ldz) {
+        int rc;
+        const int K = c->zs_K, Kpad = c->zs_Kpad, E = c->zs_width(), Mz = round_up(n, tm);
+        const size_t si = &sl - &c->slices[0];
+        void *a = c->zs_a[si]; float *acc = c->zs_acc[si];
+        {
+            ProfScope ps(c, st, PC_ZEROSHOT, 0, (double)n * E * 4 + (double)Mz * E * eb);
+            HIP_TRY(launch_zs_embed(dt, z, ldz, a, n, Mz, E, st));
+        }
+        if ((rc = gemm(c, st, PC_ZEROSHOT, EPI_BIAS_F32, dense_gemm(a, c->zs_bank, c->zs_zero, acc, Mz, n, K, Kpad, E, Kpad)))) return rc;
+        float *out = c->zs_out + (size_t)first_img * 2 * K;
+        ProfScope ps(c, st, PC_ZEROSHOT, 0, (double)n * K * 4 * (c->zs_kind == VITX_ZS_SOFTMAX ? 7 : 3));
+        HIP_TRY(launch_zs_score(acc, Kpad, out, out + K, 2L * K, n, K, c->zs_kind, c->zs_scale, c->zs_bias, st));
+        return VITX_OK;
+    }
     // Quantised matrices (block form in HBM): a q4_0 GEMM with few rows expands the blocks in its own LDS-fill path; everything else
     // is expanded just in time, one launch per layer, into the slice's scratch and then streamed by the wide-tile kernels.
     bool fused_ok(const QuantW &q, int rows) const { return q.blocks && q.type == T_Q4_0 && rows <= c->q4_fused_rows && rows % 128 == 0 && q.n_pad % 128 == 0 && q.K % 64 == 0; }
@@ -339,6 +356,8 @@ struct SliceForward {
             ProfScope ps(c, st, PC_SOFTMAX, 0, (double)nR * c->C * 8);
             HIP_TRY(launch_softmax(dt, lg, (float *)d_probs, nR, c->C, ldl, st));
         }
+        // zero-shot logits and probabilities of a context with a bank: from the pooled embedding e (attention-pooling head), else from the logits row
+        if (c->zs_on() && (rc = c->map ? zeroshot(sl.Xc, D) : zeroshot(lg, ldl))) return rc;
         if (fuse && c->ln_fb_host) HIP_TRY(hipMemcpyAsync(c->ln_fb_host + (&sl - &c->slices[0]), sl.ln_todo + sl.ln_blocks, sizeof(unsigned), hipMemcpyDeviceToHost, st));       // fall-back budget
         return VITX_OK;
     }
@@ -516,7 +535,7 @@ static int forward_pass(vitx_ctx *c, const void *d_imgs, int n, void *d_probs, v
     const bool serial = c->prof_on;
     const int ns = (c->nslices > 1 && n >= 8 * c->nslices) ? c->nslices : 1;
     if (ns == 1) {
-        if (c->graphs_on && !c->prof_on && c->trace_ids.empty() && !c->attn_on() && !c->feat_on()) {
+        if (c->graphs_on && !c->prof_on && c->trace_ids.empty() && !c->attn_on() && !c->feat_on() && !c->zs_on()) {
             bool done = false;
             const int rc = forward_graph(c, st, d_imgs, n, d_probs, d_logits, &done);
             if (rc != VITX_OK || done) return rc;
@@ -569,6 +588,7 @@ int vitx_forward_device(vitx_ctx *c, const void *d_imgs, int n, void *d_probs, v
     if (n > c->call_limit && !c->trace_ids.empty()) { set_error("vitx_forward_device: the residual-stream trace takes one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
     if (n > c->call_limit && c->attn_on()) { set_error("vitx_forward_device: attention maps take one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
     if (n > c->call_limit && c->feat_on()) { set_error("vitx_forward_device: features take one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
+    if (n > c->call_limit && c->zs_on()) { set_error("vitx_forward_device: zero-shot classification takes one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
     for (int i0 = 0; i0 < n; i0 += c->call_limit) {
         const int ni = std::min(c->call_limit, n - i0);
         const int rc = forward_pass(c, (const float *)d_imgs + (size_t)i0 * c->S * c->S * c->Cin, ni, (float *)d_probs + (size_t)i0 * c->R * c->C,
@@ -577,6 +597,7 @@ int vitx_forward_device(vitx_ctx *c, const void *d_imgs, int n, void *d_probs, v
     }
     if (c->attn_on()) c->attn_n = n;
     if (c->feat_on()) c->feat_n = n;
+    if (c->zs_on()) c->zs_n = n;
     return VITX_OK;
 }
 int vitx_forward(vitx_ctx *c, const float *imgs, int n, float *probs, float *logits) {

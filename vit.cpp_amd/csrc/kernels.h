@@ -202,6 +202,14 @@ hipError_t launch_attention_pool(const float *x, long row_stride, long img_strid
 // The end of the pooled tail: e [n_img][D] f32 -> z [n_img][D] = RNE(e) in `dtype` (the head GEMM's operand) and, cls != nullptr, the feature
 // cls[i * out_img_stride ..] = e[i] (l2: divided by its norm, VITX_FEAT_L2's arithmetic).  One wave per image.
 hipError_t launch_pool_embed(const float *e, void *z, int dtype, float *cls, long out_img_stride, bool l2, int n_img, int D, hipStream_t stream);
+// Zero-shot classification (zeroshot.hip; include/vitx.h "zero-shot classification"): the two kernels around the bank GEMM.
+//   zs_embed: row i of z (f32, at z + i * z_stride floats) -> a[i][0 .. E) = RNE(z / sqrt(sum z^2)) in `dtype`, an all-zero row stays zero; rows
+//             n .. m_pad of a are written as zeros.  E a multiple of 64; z rows 16-byte aligned (z_stride a multiple of 4).
+//   zs_score: acc [n][ld] f32 -> logits[i * out_img_stride + k] = acc[i][k] * scale + bias and probs[..] = softmax over k < K (VITX_ZS_SOFTMAX) or
+//             the sigmoid (VITX_ZS_SIGMOID); columns K .. ld are never read.  One workgroup per image.
+// hipErrorInvalidValue for a shape outside that.
+hipError_t launch_zs_embed(int dtype, const float *z, long z_stride, void *a, int n, int m_pad, int E, hipStream_t stream);
+hipError_t launch_zs_score(const float *acc, int ld, float *probs, float *logits, long out_img_stride, int n, int K, int kind, float scale, float bias, hipStream_t stream);
 // pos [1 + gy_in * gx_in][D] f32 -> out [1 + gy_out * gx_out][D] f32 (pos_resample.hip; the arithmetic: pos_resample.h); only enqueues
 hipError_t launch_pos_resample(const float *pos, int gy_in, int gx_in, int D, int gy_out, int gx_out, int interp, float *out, hipStream_t stream);
 bool attention_supports(int N, int D, int H);     // any token count; head_dim 64 (tuned kernels) or any other multiple of 8 up to 128 (generic kernel)

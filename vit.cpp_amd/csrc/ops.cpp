@@ -1,5 +1,6 @@
 // ops.cpp -- single-kernel entry points (vitx_op_*, vitx_preprocess_u8_device): one launcher each, on the caller's buffers, for the
 // parity tests and the kernel benchmarks.  None takes a context.
+#include <cmath>
 #include <initializer_list>
 
 #include "context.h"
@@ -273,6 +274,35 @@ int vitx_op_attention_map(int dtype, const void *d_qkv, long lo_off, void *d_cls
     if (d_cls) e = launch_attention_cls_map(dtype, d_qkv, lo_off, (float *)d_cls, (long)H * N, n_img, N, D, H, st);
     if (e == hipSuccess && d_mean) e = launch_attention_head_mean(dtype, d_qkv, lo_off, (float *)d_mean, n_img, N, D, H, false, st);
     return op_rc("vitx_op_attention_map", e);
+}
+
+// Zero-shot classification on the caller's buffers: the three launches the forward of a context with a bank makes (SliceForward::zeroshot), the
+// bank GEMM through the dispatcher.  Every argument check comes before the first device call.  The GEMM's bias is the row of zeros the call
+// writes behind the accumulator rows (d_acc_scratch holds round_up(n, 256) + 1 rows of K_pad floats).
+int vitx_zeroshot_max_classes(int E) {
+    if (E <= 0 || E % 64) return 0;
+    return (int)std::min<size_t>((size_t)0xf0000000u / ((size_t)E * 2) / gemm_tile_n() * gemm_tile_n(), (size_t)0x7fffff80);
+}
+int vitx_op_zeroshot(int dtype, const void *d_z, long z_stride, const void *d_bank, void *d_a_scratch, void *d_acc_scratch, void *d_probs, void *d_logits,
+                     int n, int K, int E, int kind, float scale, float bias, void *stream) {
+    if (!d_z || !d_bank || !d_a_scratch || !d_acc_scratch || !d_probs || !d_logits || n <= 0 || K <= 0 || E <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_zeroshot: invalid argument"); return VITX_ERR_ARG; }
+    if (kind != VITX_ZS_SOFTMAX && kind != VITX_ZS_SIGMOID) { set_error("vitx_op_zeroshot: unknown kind %d (0 softmax, 1 sigmoid)", kind); return VITX_ERR_ARG; }
+    if (!std::isfinite(scale) || !std::isfinite(bias)) { set_error("vitx_op_zeroshot: scale and bias must be finite"); return VITX_ERR_ARG; }
+    if (z_stride < E || z_stride % 4) { set_error("vitx_op_zeroshot: z_stride %ld must be at least E = %d and a multiple of 4 floats", z_stride, E); return VITX_ERR_ARG; }
+    for (const void *p : {d_z, d_bank, (const void *)d_a_scratch, (const void *)d_acc_scratch})
+        if ((uintptr_t)p % 16) { set_error("vitx_op_zeroshot: d_z, d_bank and the scratch buffers must be 16-byte aligned"); return VITX_ERR_ARG; }
+    if (E % 64) { set_error("vitx_op_zeroshot: E = %d is not a multiple of 64 (the GEMMs' K step)", E); return VITX_ERR_UNSUPPORTED; }
+    if (K > vitx_zeroshot_max_classes(E)) { set_error("vitx_op_zeroshot: %d classes of width %d exceed the bank GEMM's 32-bit window (at most %d)", K, E, vitx_zeroshot_max_classes(E)); return VITX_ERR_UNSUPPORTED; }
+    const Tuning *t = tuning_for_device(-1);
+    if (!t) { set_error("vitx_op_zeroshot: kernel bring-up failed"); return VITX_ERR_HIP; }
+    const int Kpad = round_up(K, gemm_tile_n()), M = round_up(n, gemm_tile_m());
+    hipStream_t st = (hipStream_t)stream;
+    float *acc = (float *)d_acc_scratch, *zero = acc + (size_t)M * Kpad;
+    hipError_t e = hipMemsetAsync(zero, 0, (size_t)Kpad * 4, st);
+    if (e == hipSuccess) e = launch_zs_embed(dtype, (const float *)d_z, z_stride, d_a_scratch, n, M, E, st);
+    if (e == hipSuccess) e = launch_gemm(*t, dtype, EPI_BIAS_F32, dense_gemm(d_a_scratch, d_bank, zero, acc, M, n, K, Kpad, E, Kpad), st);
+    if (e == hipSuccess) e = launch_zs_score(acc, Kpad, (float *)d_probs, (float *)d_logits, K, n, K, kind, scale, bias, st);
+    return op_rc("vitx_op_zeroshot", e, VITX_ERR_UNSUPPORTED);
 }
 
 int vitx_preprocess_ex_device_supports(const vitx_preproc *pp, int nx, int ny) { return pp && preprocess_ex_supports(*pp, nx, ny) ? 1 : 0; }

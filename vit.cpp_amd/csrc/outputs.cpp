@@ -1,5 +1,6 @@
 // outputs.cpp -- what a context gives besides probabilities: the per-kernel profile, the residual-stream trace, attention maps, features,
 // and the diagnostics counters.  All opt-in; the forward (forward.cpp) launches nothing for an output that is off.
+#include <cmath>
 #include <utility>
 
 #include "context.h"
@@ -197,6 +198,57 @@ int vitx_feat_images(const vitx_ctx *c) { return c ? c->feat_n : 0; }
 const void *vitx_feat_device(const vitx_ctx *c) { return c ? c->feat_out : nullptr; }
 int vitx_feat_read(vitx_ctx *c, float *out, size_t n_floats) {
     return c ? read_output(c, "vitx_feat", "features", c->feat_on() ? c->feat_n : 0, c->feat_fpi, c->feat_out, out, n_floats) : VITX_ERR_ARG;
+}
+
+// Zero-shot classification: the bank of a context (include/vitx.h).  Every argument check comes before the first device call.
+int vitx_zeroshot_set(vitx_ctx *c, const float *bank, int K, int E, int kind, float scale, float bias) {
+    if (!c) return VITX_ERR_ARG;
+    const bool off = !bank && K == 0;
+    if (!off) {
+        if (!bank) { set_error("vitx_zeroshot_set: NULL bank with K = %d", K); return VITX_ERR_ARG; }
+        if (K < 1) { set_error("vitx_zeroshot_set: K = %d (a bank has at least one class; NULL and 0 turn it off)", K); return VITX_ERR_ARG; }
+        if (kind != VITX_ZS_SOFTMAX && kind != VITX_ZS_SIGMOID) { set_error("vitx_zeroshot_set: unknown kind %d (0 softmax, 1 sigmoid)", kind); return VITX_ERR_ARG; }
+        if (!std::isfinite(scale) || !std::isfinite(bias)) { set_error("vitx_zeroshot_set: scale and bias must be finite"); return VITX_ERR_ARG; }
+        if (c->R != 1) { set_error("vitx_zeroshot_set: zero-shot classification is not available for ViTSTR contexts"); return VITX_ERR_UNSUPPORTED; }
+        if (E != c->zs_width()) { set_error("vitx_zeroshot_set: the bank's width %d is not this context's embedding width %d (%s)", E, c->zs_width(), c->map ? "the pooled embedding: hidden_size" : "the head's rows: num_classes"); return VITX_ERR_ARG; }
+        if (E % 64) { set_error("vitx_zeroshot_set: the embedding width %d is not a multiple of 64 (the GEMMs' K step)", E); return VITX_ERR_UNSUPPORTED; }
+        if (K > vitx_zeroshot_max_classes(E)) { set_error("vitx_zeroshot_set: %d classes of width %d exceed the bank GEMM's 32-bit window (at most %d)", K, E, vitx_zeroshot_max_classes(E)); return VITX_ERR_UNSUPPORTED; }
+        for (size_t i = 0, nb = (size_t)K * E; i < nb; ++i)
+            if (!std::isfinite(bank[i])) { set_error("vitx_zeroshot_set: bank entry [%zu][%zu] is not finite", i / E, i % E); return VITX_ERR_ARG; }
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());          // no forward in flight reads or writes the buffers about to be freed
+    c->zs_free();
+    if (off) return VITX_OK;
+    const int Kpad = round_up(K, c->tn), cap = c->pass_cap();
+    const size_t rows = (size_t)round_up(cap, c->tm);
+    const std::vector<uint16_t> hb = operand_matrix_host(c->dtype, bank, nullptr, K, E, Kpad, E, 0, 0);
+    auto alloc = [](void **p, size_t bytes) { if (hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; } return true; };
+    bool ok = alloc(&c->zs_bank, hb.size() * 2) && alloc((void **)&c->zs_zero, (size_t)Kpad * 4) && alloc((void **)&c->zs_out, (size_t)cap * 2 * K * 4);
+    c->zs_a.assign(c->nslices, nullptr); c->zs_acc.assign(c->nslices, nullptr);
+    for (int i = 0; ok && i < c->nslices; ++i) ok = alloc(&c->zs_a[i], rows * E * 2) && alloc((void **)&c->zs_acc[i], rows * Kpad * 4);
+    if (!ok) { c->zs_free(); set_error("vitx_zeroshot_set: cannot allocate the buffers for %d classes and %d images", K, cap); return VITX_ERR_NOMEM; }
+    hipError_t e = hipMemcpy(c->zs_bank, hb.data(), hb.size() * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(c->zs_zero, 0, (size_t)Kpad * 4);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { c->zs_free(); set_error("vitx_zeroshot_set: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
+    c->zs_K = K; c->zs_Kpad = Kpad; c->zs_kind = kind; c->zs_scale = scale; c->zs_bias = bias; c->zs_cap = cap;
+    return VITX_OK;
+}
+int vitx_zeroshot_classes(const vitx_ctx *c) { return c ? c->zs_K : 0; }
+int vitx_zeroshot_images(const vitx_ctx *c) { return c ? c->zs_n : 0; }
+const void *vitx_zeroshot_device(const vitx_ctx *c) { return c ? c->zs_out : nullptr; }
+int vitx_zeroshot_read(vitx_ctx *c, float *probs, float *logits, size_t n_floats_each) {
+    if (!c || !probs) return VITX_ERR_ARG;
+    const int n = c->zs_on() ? c->zs_n : 0, K = c->zs_K;
+    if (n == 0) { set_error("vitx_zeroshot_read: no forward has run with a bank set since vitx_zeroshot_set"); return VITX_ERR_ARG; }
+    const size_t need = (size_t)n * K;
+    if (n_floats_each < need) { set_error("vitx_zeroshot_read: buffer too small (%zu floats needed for %d images of %d classes)", need, n, K); return VITX_ERR_ARG; }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy2D(probs, (size_t)K * 4, c->zs_out, (size_t)2 * K * 4, (size_t)K * 4, n, hipMemcpyDeviceToHost));
+    if (logits) HIP_TRY(hipMemcpy2D(logits, (size_t)K * 4, c->zs_out + K, (size_t)2 * K * 4, (size_t)K * 4, n, hipMemcpyDeviceToHost));
+    return VITX_OK;
 }
 
 }  // extern "C"

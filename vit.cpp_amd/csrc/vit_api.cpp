@@ -161,6 +161,37 @@ int vit_embed(const vit_model &model, vit_state &state, const image_f32 &img1, i
     return rc;
 }
 
+// No counterpart in the reference: zero-shot classification of n images against a bank of class (text) embeddings (include/vitx.h)
+int vit_zeroshot_batch(const vit_model &model, vit_state &state, const image_f32 *imgs, int n, const vit_zeroshot_bank &bank, std::vector<std::vector<std::pair<float, int>>> &out, int topk) {
+    out.clear();
+    if (!model.handle || !imgs || n <= 0 || bank.K <= 0 || bank.E <= 0 || bank.embeds.size() != (size_t)bank.K * bank.E) { fprintf(stderr, "%s: invalid argument\n", __func__); return 1; }
+    if (vitx_model_seq_len(model.handle) > 0) { fprintf(stderr, "%s: this is a ViTSTR model: it has no image embedding\n", __func__); return 1; }
+    const int S = state_img_size(model, state), C = model.hparams.num_classes, K = bank.K;
+    for (int i = 0; i < n; ++i)
+        if (imgs[i].nx != S || imgs[i].ny != S || imgs[i].data.size() != (size_t)3 * S * S) {
+            fprintf(stderr, "%s: image %d is %dx%d, this state expects %dx%d\n", __func__, i, imgs[i].nx, imgs[i].ny, S, S);
+            return 1;
+        }
+    if (ensure_ctx(model, state, n) != VITX_OK) { fprintf(stderr, "%s: failed to create the context: %s\n", __func__, vitx_last_error()); return 1; }
+    if (vitx_zeroshot_set(state.ctx, bank.embeds.data(), K, bank.E, bank.kind, bank.scale, bank.bias) != VITX_OK) { fprintf(stderr, "%s: %s\n", __func__, vitx_last_error()); return 1; }
+    std::vector<float> batch((size_t)n * 3 * S * S);
+    for (int i = 0; i < n; ++i) std::copy(imgs[i].data.begin(), imgs[i].data.end(), batch.begin() + (size_t)i * 3 * S * S);
+    state.prediction.resize((size_t)n * C);
+    std::vector<float> probs((size_t)n * K);
+    const bool ok = vitx_forward(state.ctx, batch.data(), n, state.prediction.data(), nullptr) == VITX_OK && vitx_zeroshot_read(state.ctx, probs.data(), nullptr, probs.size()) == VITX_OK;
+    if (!ok) fprintf(stderr, "%s: failed to encode image: %s\n", __func__, vitx_last_error());
+    (void)vitx_zeroshot_set(state.ctx, nullptr, 0, 0, 0, 0.0f, 0.0f);
+    if (!ok) return 1;
+    const int k = std::min(topk > 0 ? topk : K, K);
+    std::vector<int32_t> idx(k); std::vector<float> pr(k);
+    out.resize(n);
+    for (int i = 0; i < n; ++i) {
+        if (vitx_topk(probs.data() + (size_t)i * K, K, k, idx.data(), pr.data()) != VITX_OK) { fprintf(stderr, "%s: %s\n", __func__, vitx_last_error()); out.clear(); return 1; }
+        for (int j = 0; j < k; ++j) out[i].push_back(std::make_pair(pr[j], (int)idx[j]));
+    }
+    return 0;
+}
+
 // extensions/vitstr.cpp/vitstr.cpp:135-201
 bool vitstr_image_preprocess(const image_u8 &img, image_f32 &res, const vit_hparams &params) {
     const int S = params.n_img_size();

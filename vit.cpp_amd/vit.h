@@ -9,7 +9,8 @@
 //   * vit_predict still fills `predictions` with all (prob, class) pairs sorted
 //     descending and prints the top-k lines to stdout (vit.cpp:1043-1067);
 //   * vit_predict_batch is NEW (the reference has no batched call): n images per launch;
-//   * vit_embed / vit_embed_batch are NEW (the reference returns class probabilities only): the image embedding.
+//   * vit_embed / vit_embed_batch are NEW (the reference returns class probabilities only): the image embedding;
+//   * vit_zeroshot_batch is NEW: zero-shot classes of a CLIP / SigLIP file against a bank of text embeddings.
 // Everything below is a thin wrapper over the C ABI in include/vitx.h.
 #pragma once
 
@@ -102,6 +103,20 @@ int vit_predict_batch(const vit_model &model, vit_state &state, const image_f32 
 // probabilities of the same forward; the features are switched off again before returning.  0 ok / 1 failure.
 int vit_embed_batch(const vit_model &model, vit_state &state, const image_f32 *imgs, int n, int flags, std::vector<std::vector<float>> &out);
 int vit_embed(const vit_model &model, vit_state &state, const image_f32 &img1, int flags, std::vector<float> &out);
+// NEW, no counterpart in the reference: zero-shot classification (include/vitx.h "zero-shot classification").  A bank = K unit-length class
+// (text) embeddings of width E -- the model's embedding width: num_classes of a CLIP file (its head is the visual projection), hidden_size of a
+// SigLIP file -- with the publisher's kind, scale = exp(logit_scale) and bias (convert.py zeroshot_bank computes all of it from a transformers model).
+struct vit_zeroshot_bank {
+    std::vector<float> embeds;            // [K][E], rows of unit length (the engine does not renormalise them)
+    int K = 0, E = 0;
+    int kind = VITX_ZS_SOFTMAX;           // VITX_ZS_SOFTMAX (CLIP) or VITX_ZS_SIGMOID (SigLIP)
+    float scale = 1.0f, bias = 0.0f;
+    std::vector<std::string> labels;      // K names, or empty
+};
+// out[i] = image i's topk (probability, class) pairs in vitx_topk's order (topk <= 0 or > K: all K).  The bank is set for this call and switched off again before
+// returning; state.prediction holds the file's own class "probabilities" of the same forward.  0 ok / 1 failure.
+int vit_zeroshot_batch(const vit_model &model, vit_state &state, const image_f32 *imgs, int n, const vit_zeroshot_bank &bank,
+                       std::vector<std::vector<std::pair<float, int>>> &out, int topk = 5);
 // ---- the ViTSTR scene-text extension (extensions/vitstr.cpp).  It is a separate program in the reference that re-uses the names
 // vit_image_preprocess / vit_predict with different bodies (vitstr.h:115-119); here both programs live in one library, so the
 // extension's two functions carry a vitstr_ prefix.  vit_model_load is shared: a file whose patch kernel has ONE input channel is
