@@ -22,7 +22,7 @@ for i, v in enumerate(a.variants):
     name, _, rest = v.partition("=")
     lib, _, opts = rest.partition(":")
     os.environ["VITX_LIB"] = os.path.abspath(lib)
-    spec = importlib.util.spec_from_file_location(f"binding_ab{i}", os.path.join(ROOT, "vit.cpp_amd", "binding.py"))
+    spec = importlib.util.spec_from_file_location(f"{pkg.__name__}.binding_ab{i}", os.path.join(ROOT, "vit.cpp_amd", "binding.py"))
     B = importlib.util.module_from_spec(spec); spec.loader.exec_module(B)
     kw = {k: int(x) for k, x in (o.split("=") for o in opts.split(",") if o)}
     m = B.Model(path)

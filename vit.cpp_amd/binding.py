@@ -13,6 +13,11 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
+# the enums a model file or a zero-shot bank carries are numbered once, in ggml_file.py (which needs no library)
+from .ggml_file import (ACT_TANH as ACT_GELU_TANH, ACT_ERF as ACT_GELU_ERF, ACT_QUICK as ACT_QUICK_GELU,      # vitx_model_activation (tanh-GELU without `arch`)
+                        ZS_SOFTMAX, ZS_SIGMOID, POOL_CLS, POOL_CLS_MEAN, POOL_MAP,                           # vitx_zs_kind, vitx_model_head_pool
+                        PP_REF_BICUBIC, PP_REF_BILINEAR, PP_PIL_BILINEAR, PP_PIL_BICUBIC, PP_STRETCH, PP_SHORTEST_EDGE)      # vitx_pp_filter, vitx_pp_resize
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # VITX_LIB: development override (the -DVITX_LAB laboratory build, A/B builds).  bench.py marks its line invalid when it is set.
 LIB_PATH = os.environ.get("VITX_LIB") or os.path.join(_HERE, "libvitx.so")
@@ -22,16 +27,11 @@ LN_TEST_KEY = 0x7e570000        # vitx_ctx_options::ln_test is honoured only as 
 BICUBIC, BILINEAR = 0, 1
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_BIAS_F32, EPI_PATCH, EPI_BIAS_HILO = 0, 1, 2, 3, 4, 5
 EPI_BIAS_GELU_ERF, EPI_BIAS_QGELU = 6, 7      # fc1 epilogues of the other two activations (same rounding points as EPI_BIAS_GELU)
-ACT_GELU_TANH, ACT_GELU_ERF, ACT_QUICK_GELU = 0, 1, 2      # vitx_model_activation (the file's `arch` tensor; tanh-GELU without it)
 ERR_IO, ERR_FORMAT, ERR_ARG, ERR_HIP, ERR_UNSUPPORTED, ERR_NOMEM = 1, 2, 3, 4, 5, 6      # status codes (VitxError.code)
 GEMM_AUTO, GEMM_PP, GEMM_AUTO_SPLIT = 0, 1, 2          # vitx_op_gemm_ex `kernel` (or a ring configuration: 945, 445, 245, 122)
 ATTN_AUTO, ATTN_SINGLE, ATTN_FLOW, ATTN_PERSIST, ATTN_STREAM = 0, 1, 3, 4, 5   # vitx_op_attention_ex `kernel`
 ATTN_ROLLOUT = 1                # vitx_attn_enable flag
 FEAT_CLS, FEAT_MEAN, FEAT_TOKENS, FEAT_L2 = 1, 2, 4, 8      # vitx_feat_enable flags
-ZS_SOFTMAX, ZS_SIGMOID = 0, 1      # vitx_zs_kind: CLIP's softmax over the classes, SigLIP's sigmoid per class
-POOL_CLS, POOL_CLS_MEAN, POOL_MAP = 0, 1, 2      # vitx_model_head_pool: the head reads the class token, concat(cls, mean of the patch tokens), or the attention-pooled embedding
-PP_REF_BICUBIC, PP_REF_BILINEAR, PP_PIL_BILINEAR, PP_PIL_BICUBIC = 0, 1, 2, 3      # vitx_pp_filter: the reference's two, Pillow's Image.resize on u8
-PP_STRETCH, PP_SHORTEST_EDGE = 0, 1     # vitx_pp_resize
 POS_BICUBIC, POS_BICUBIC_AA = 0, 1      # vitx_pos_interp: F.interpolate(mode="bicubic") without / with antialias=True (include/vitx.h)
 
 EXPORTS = [

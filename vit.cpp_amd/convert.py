@@ -1,80 +1,69 @@
-"""Converter: a HuggingFace `transformers` ViTForImageClassification, DINOv2 or CLIP vision model -> the reference's legacy-ggml ".gguf" file.
+"""Converter: a HuggingFace `transformers` vision model or a timm state dict -> the legacy-ggml ".gguf" model file (ggml_file.write_model).
 
-Counterpart of the reference's /root/reference/convert-pth-to-ggml.py (which needs `timm`): same output layout
-(writer rules convert-pth-to-ggml.py:105-158 live in ggml_file.write_model), different source naming -- HF splits
-the fused qkv projection into query/key/value (concatenated here in timm's q,k,v order, vit.cpp:826-834) and calls
-the sub-modules `vit.encoder.layer.N.*` (transformers < 5) or `vit.layers.N.*` (>= 5).  Offline tool, not on the
-compute path.
+An offline tool, not on the compute path.  The file holds timm's VisionTransformer names in the order the loader reads them -- cls_token, pos_embed,
+patch_embed.proj.*, per block norm1, the fused attn.qkv (q, k, v rows in that order), attn.proj, norm2, mlp.fc1, mlp.fc2, then norm.* and head.* --
+plus the extensions of include/vitx.h: `arch`, `preproc`, `reg_token`, `pre_norm.*`, the [C][2 D] head and `attn_pool.*`.  A HuggingFace family
+differs from it in its names and in a few tensors around the blocks: BlockNames states a family's block names as data and map_blocks is the one
+place that renames, fuses and folds a block; the embeddings, the final norm and the head are each family's own few lines (its *_state_dict_to_timm
+function documents them).  convert_hf_model writes every family through one path, chosen by the FAMILIES table.
 
-The model's own MLP activation and LayerNorm epsilon are read from its config (`hidden_act`: gelu -> erf-GELU, gelu_pytorch_tanh / gelu_new ->
-tanh-GELU, quick_gelu -> QuickGELU, anything else is refused by name; `layer_norm_eps`) and written as the file's `arch` tensor, f32 [4] =
-{activation, eps, 0, 0}, the first tensor of the file (include/vitx.h "activation, epsilon and pre-norm").  `arch` is written ONLY when
-(activation, eps) differs from (tanh-GELU, 1e-6), the reference's arithmetic: such a conversion is byte for byte what it always was and stays
-readable by the reference.  Every other model -- the HuggingFace ViT default is erf-GELU with 1e-12, timm and DINOv2 use erf-GELU -- used to be
-written without its settings and run with tanh-GELU and 1e-6; it now carries them, which is the one intended change of this converter's output.
+What is converted
+  ViT      ViTForImageClassification, both namings (`vit.encoder.layer.N` before transformers 5, `vit.layers.N` from 5 on); with --vitstr a
+           one-channel ViTSTR scene-text recogniser, whose file carries the character set as labels.
+  DINOv2   Dinov2ForImageClassification, Dinov2WithRegistersForImageClassification; with --no-head the backbones Dinov2Model /
+           Dinov2WithRegistersModel.  Register tokens, folded LayerScale, the head over concat(cls, mean of the patch tokens).
+  CLIP     CLIPVisionModelWithProjection, CLIPModel (its vision tower and visual_projection); with --no-head a CLIPVisionModel.
+  SigLIP   SiglipVisionModel, SiglipModel (its vision tower): no class token, the attention-pooling head.
+  timm     a VisionTransformer state_dict (--timm-state-dict model.pth, no `timm` import): convert_timm_state_dict.
 
-CLIP (CLIPVisionModelWithProjection; CLIPModel: its vision tower and visual_projection; CLIPVisionModel with --no-head): class_embedding ->
-cls_token, position_embedding -> pos_embed, the bias-free patch convolution gets a zero bias, pre_layrnorm -> `pre_norm.*` (directly after
-pos_embed), q/k/v_proj are fused, post_layernorm -> norm, and the bias-free visual_projection [E][D] becomes head.weight with a zero head.bias:
-the file has E "classes" labelled dim_0 .. dim_{E-1}, its logits are CLIP's image_embeds and its probabilities mean nothing (zero-shot
-probabilities come from a bank of text embeddings: below).
+Every model's settings travel with it.  The MLP activation (`hidden_act`: gelu -> erf-GELU, gelu_pytorch_tanh / gelu_new -> tanh-GELU, quick_gelu ->
+QuickGELU) and `layer_norm_eps` become the `arch` tensor, f32 [4] = {activation, eps, 0, 0}, the first of the file -- written ONLY when they differ
+from (tanh-GELU, 1e-6), the reference's arithmetic, so that such a file is byte for byte the reference converter's and stays readable by the
+reference (with_arch).  The HuggingFace ViT default is erf-GELU with 1e-12; timm and DINOv2 use erf-GELU.  A timm state dict carries no config:
+--act {tanh,erf,quick} and --eps state its settings (timm's VisionTransformer uses nn.GELU: --act erf); without them the file is the reference's.
 
-SigLIP (SiglipVisionModel; SiglipModel: its vision tower): there is NO class token -- position_embedding [g^2][D] -> pos_embed [1][g^2][D] --, q/k/v_proj
-are fused, post_layernorm -> norm, and the multi-head attention-pooling head becomes the thirteen `attn_pool.*` tensors of include/vitx.h ("no
-class token and the attention-pooling head", timm's AttentionPoolLatent names): head.probe -> latent, head.attention.in_proj_weight / in_proj_bias are
-split into q (rows 0 .. D) and kv (rows D .. 3 D), out_proj -> proj, head.layernorm -> norm, head.mlp -> mlp.  A tower has no classifier: the file
-gets the one-class head of zeros labelled "(no head)" (--no-head is accepted and not required) and its pooled embedding -- SigLIP's pooler_output /
-image_embeds -- is read with --embed-kind cls / VITX_FEAT_CLS.  Refused by name: intermediate_size != 4 D (SO400M), vision_use_head = False,
-SiglipForImageClassification (a mean-pool classifier, no MAP head: no slot), Siglip2VisionModel (NaFlex: its patch embedding is a Linear).
-
-A timm checkpoint needs no `timm` either: its state_dict already carries the names the file format uses (the reference's converter
-writes `timm_model.state_dict()` verbatim, convert-pth-to-ggml.py:121-133), so `--timm-state-dict model.pth` loads the tensors with
-torch.load and derives the hyper-parameters the reference reads from the timm module (:96-103) from the tensor shapes.
-
-DINOv2 (Dinov2ForImageClassification, Dinov2WithRegistersForImageClassification; the backbones Dinov2Model / Dinov2WithRegistersModel with
---no-head) writes the two file extensions of include/vitx.h ("register tokens and the pooled head"): `reg_token` [1][R][D] and the
-[C][2 D] head over concat(cls, mean of the patch tokens); the reference's vit_model_load cannot read such a file.  LayerScale has no
-file slot and needs none: y = x + lambda * (W a + b) = x + (lambda * W) a + lambda * b, so lambda is folded into attn.proj / mlp.fc2 in f32,
-before the file type's rounding.  mask_token is dropped.  SwiGLU, qk-norm, fc_norm and distillation tokens are refused by name.
-At another input size transformers 5.x resamples the DINOv2-with-registers position table with antialias=True, so `--pos-interp bicubic-aa`
-reproduces it (plain Dinov2 and ViT: `bicubic`).
-
-The model's own preprocessing travels with it: for a HuggingFace checkpoint directory the `preprocessor_config.json` beside the weights is read
+Its preprocessing travels too (include/vitx.h "each model's own preprocessing"): the `preprocessor_config.json` beside a HuggingFace checkpoint
 (hf_preproc: `do_resize` / `size` {"shortest_edge"} or {"height", "width"}, `resample` 2 = PIL bilinear or 3 = PIL bicubic, `do_center_crop` /
-`crop_size`, `image_mean`, `image_std`, `do_rescale` with the usual 1/255) and written as the file's `preproc` tensor directly after `arch`
-(include/vitx.h "each model's own preprocessing"), with mean255 = f32(255.0 * mean).  Anything the engine's preprocess cannot honour -- another
-resample code, do_resize off, padding, a channel flip, a final size that is not the model's -- is an error that names the field; --no-preproc writes
-the file without the tensor (the reference's stretch and ImageNet mean / std then apply, as before).  A timm state dict carries no processor:
---pp-resize N (shortest edge), --pp-crop N, --pp-filter, --pp-mean, --pp-std and --pp-crop-round state one; with none of them given no tensor is
-written and the reference's files keep their bytes.
+`crop_size`, `image_mean`, `image_std`, `do_rescale` with the usual 1/255) is written as the `preproc` tensor directly after `arch`, with mean255 =
+f32(255.0 * mean).  --no-preproc writes the file without it: the reference's stretch and ImageNet mean / std then apply.  A timm checkpoint has no
+processor: the --pp-* options state one (cli_preproc); with none of them no tensor is written and the file keeps the reference's bytes.
 
-Zero-shot banks (include/vitx.h "zero-shot classification"): zeroshot_bank() runs the TEXT tower of a transformers CLIPModel / SiglipModel on
-token ids and returns what vitx_zeroshot_set takes -- the unit-length text embeddings [K][E], the kind (softmax for CLIP, sigmoid for SigLIP),
-exp(logit_scale) and logit_bias (0 for CLIP); `groups` averages the normalised embeddings of several prompts per class and renormalises (prompt
-ensembling).  --zero-shot-ids ids.npy [--zero-shot-labels labels.txt] --zero-shot-out bank.npz writes it as an .npz with `embeds`, `labels`, `kind`,
-`scale`, `bias` (save_bank / load_bank; vit_cli.py --zero-shot reads it); the model file itself is converted as usual.  The engine has no text
-encoder and no tokenizer: the bank is computed here, once per set of prompts.
+What is refused, by name: an activation the forward path does not evaluate; an MLP that is not 4 x hidden (SigLIP SO400M's 4304); a head_dim that
+is no multiple of 8 up to 128; qkv_bias=False; SwiGLU, qk-norm, fc_norm and distillation tokens; a SigLIP tower without its pooling head
+(vision_use_head = False), SiglipForImageClassification (a mean-pool classifier: no slot), Siglip2VisionModel (NaFlex: its patch embedding is a
+Linear); --no-head on a ViT, and a model without classifier or projection converted without it; --vitstr on anything but a one-channel ViT; in a
+preprocessor_config whatever the engine's preprocess cannot honour -- another resample code, do_resize off, padding, a channel flip, a final size
+that is not the model's -- with the field's name.
 
-    python -m ... convert.py <hf_model_dir_or_name> <out.gguf> [--ftype 1] [--no-head] [--no-preproc]
+Zero-shot banks (include/vitx.h "zero-shot classification"): the engine has no text encoder and no tokenizer, so the bank of a CLIPModel /
+SiglipModel is computed here, once per set of prompts, by its TEXT tower (zeroshot_bank).  --zero-shot-ids ids.npy [--zero-shot-labels labels.txt]
+--zero-shot-out bank.npz writes it as an .npz (save_bank / load_bank; vit_cli.py --zero-shot reads it); the model file is converted as usual.
+
+At another input size (--img-size N) pos_embed is resampled; transformers 5.x resamples the DINOv2-with-registers table with antialias=True, which
+`--pos-interp bicubic-aa` reproduces (plain Dinov2 and ViT: `bicubic`).
+
+    python -m ... convert.py <hf_model_dir_or_name> <out.gguf> [--ftype 1] [--no-head] [--no-preproc] [--vitstr] [--img-size N]
     python -m ... convert.py <hf_clip_or_siglip_dir> <out.gguf> --zero-shot-ids ids.npy [--zero-shot-labels labels.txt] --zero-shot-out bank.npz
-    python -m ... convert.py --timm-state-dict <checkpoint.pth> <out.gguf> [--ftype 1] [--heads H] [--labels labels.json] [--act erf] [--eps 1e-6]
-
-A timm state dict carries no config, so --act {tanh,erf,quick} and --eps state its settings; without them the file is the reference's (tanh-GELU,
-1e-6, no `arch`), as before.  timm's VisionTransformer uses nn.GELU: convert its checkpoints with --act erf.
+    python -m ... convert.py --timm-state-dict <checkpoint.pth> <out.gguf> [--ftype 1] [--heads H] [--labels labels.json] [--act erf] [--eps 1e-6] [--pp-*]
 """
 from __future__ import annotations
 
+import argparse
+import json
+import os
+from collections import namedtuple
 from typing import Dict
 
 import numpy as np
 
 from .ggml_file import (HParams, write_model, preproc_slots, preproc_fields, IMAGENET_MEAN, IMAGENET_STD,
-                        PP_STRETCH, PP_SHORTEST_EDGE, PP_PIL_BILINEAR, PP_PIL_BICUBIC)
+                        PP_STRETCH, PP_SHORTEST_EDGE, PP_PIL_BILINEAR, PP_PIL_BICUBIC,
+                        ACT_TANH, ACT_ERF, ACT_QUICK, ZS_SOFTMAX, ZS_SIGMOID)
 
 
-ACT_TANH, ACT_ERF, ACT_QUICK = 0, 1, 2          # enum vitx_activation
 _HF_ACTS = {"gelu": ACT_ERF, "gelu_pytorch_tanh": ACT_TANH, "gelu_new": ACT_TANH, "quick_gelu": ACT_QUICK}
 _ACT_NAMES = {"tanh": ACT_TANH, "erf": ACT_ERF, "quick": ACT_QUICK}
+NO_HEAD_LABELS = {0: "(no head)"}
 
 
 def hf_activation(cfg) -> int:
@@ -189,120 +178,149 @@ def cli_preproc(img_size: int, resize: int = 0, crop: int = 0, filt: str = "", m
                          crop_round=1 if crop_round == "torchvision" else 0, mean=mean or IMAGENET_MEAN, std=std or IMAGENET_STD)
 
 
-def state_dict_to_timm(sd: Dict[str, np.ndarray], num_layers: int) -> Dict[str, np.ndarray]:
-    """Rename / fuse an HF ViTForImageClassification state dict (numpy arrays) into timm's names, in the tensor
-    order the reference's loader expects to find them (vit.cpp:512-574)."""
-    new = "vit.layers.0.attention.q_proj.weight" in sd
-    out: Dict[str, np.ndarray] = {}
-    out["cls_token"] = sd["vit.embeddings.cls_token"]
-    out["pos_embed"] = sd["vit.embeddings.position_embeddings"]
-    out["patch_embed.proj.weight"] = sd["vit.embeddings.patch_embeddings.projection.weight"]
-    out["patch_embed.proj.bias"] = sd["vit.embeddings.patch_embeddings.projection.bias"]
-    for i in range(num_layers):
-        q = f"vit.layers.{i}." if new else f"vit.encoder.layer.{i}."
-        p = f"blocks.{i}."
-        qkv = ("attention.q_proj", "attention.k_proj", "attention.v_proj") if new else \
-              ("attention.attention.query", "attention.attention.key", "attention.attention.value")
-        o = "attention.o_proj" if new else "attention.output.dense"
-        f1 = "mlp.fc1" if new else "intermediate.dense"
-        f2 = "mlp.fc2" if new else "output.dense"
-        out[p + "norm1.weight"] = sd[q + "layernorm_before.weight"]; out[p + "norm1.bias"] = sd[q + "layernorm_before.bias"]
-        out[p + "attn.qkv.weight"] = np.concatenate([sd[q + n + ".weight"] for n in qkv], 0)
-        out[p + "attn.qkv.bias"] = np.concatenate([sd[q + n + ".bias"] for n in qkv], 0)
-        out[p + "attn.proj.weight"] = sd[q + o + ".weight"]; out[p + "attn.proj.bias"] = sd[q + o + ".bias"]
-        out[p + "norm2.weight"] = sd[q + "layernorm_after.weight"]; out[p + "norm2.bias"] = sd[q + "layernorm_after.bias"]
-        out[p + "mlp.fc1.weight"] = sd[q + f1 + ".weight"]; out[p + "mlp.fc1.bias"] = sd[q + f1 + ".bias"]
-        out[p + "mlp.fc2.weight"] = sd[q + f2 + ".weight"]; out[p + "mlp.fc2.bias"] = sd[q + f2 + ".bias"]
-    out["norm.weight"] = sd["vit.layernorm.weight"]; out["norm.bias"] = sd["vit.layernorm.bias"]
-    out["head.weight"] = sd["classifier.weight"]; out["head.bias"] = sd["classifier.bias"]
-    return {k: np.ascontiguousarray(np.asarray(v, np.float32)) for k, v in out.items()}
-
-
+# --------------------------------------------------------------------------- what every family shares
 def fold_layer_scale(weight: np.ndarray, bias: np.ndarray, lam: np.ndarray):
-    """LayerScale folded into the linear layer in front of it, in f32: (lambda[o] * W[o][:], lambda[o] * b[o])."""
+    """LayerScale folded into the linear layer in front of it, in f32: (lambda[o] * W[o][:], lambda[o] * b[o]).  It has no file slot and needs
+    none: y = x + lambda * (W a + b) = x + (lambda * W) a + lambda * b; the fold happens before the file type's rounding."""
     lam = np.asarray(lam, np.float32).reshape(-1)
     return (np.asarray(weight, np.float32) * lam[:, None]).astype(np.float32), (np.asarray(bias, np.float32) * lam).astype(np.float32)
 
 
+# One family's names for the tensors of a transformer block, each without its .weight / .bias.  layer: the block's prefix behind the state dict's
+# own, with {i} for the layer; qkv: the three projections the file fuses; ls1 / ls2: the LayerScale tensors behind the attention and the MLP.
+BlockNames = namedtuple("BlockNames", "layer qkv norm1 proj norm2 fc1 fc2 ls1 ls2", defaults=("", ""))
+
+
+_HF_QKV = ("attention.attention.query", "attention.attention.key", "attention.attention.value")
+VIT_BLOCKS_V4 = BlockNames("vit.encoder.layer.{i}.", _HF_QKV, "layernorm_before", "attention.output.dense", "layernorm_after", "intermediate.dense", "output.dense")
+VIT_BLOCKS_V5 = BlockNames("vit.layers.{i}.", ("attention.q_proj", "attention.k_proj", "attention.v_proj"), "layernorm_before", "attention.o_proj", "layernorm_after",
+                           "mlp.fc1", "mlp.fc2")
+DINOV2_BLOCKS = BlockNames("encoder.layer.{i}.", _HF_QKV, "norm1", "attention.output.dense", "norm2", "mlp.fc1", "mlp.fc2", "layer_scale1.lambda1", "layer_scale2.lambda1")
+CLIP_BLOCKS = BlockNames("encoder.layers.{i}.", ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"), "layer_norm1", "self_attn.out_proj", "layer_norm2",
+                         "mlp.fc1", "mlp.fc2")          # SigLIP's too
+
+
+def _put(out: dict, dst: str, sd, src: str, layer_scale: str = "") -> None:
+    w, b = sd[src + ".weight"], sd[src + ".bias"]
+    out[dst + ".weight"], out[dst + ".bias"] = fold_layer_scale(w, b, sd[layer_scale]) if layer_scale else (w, b)
+
+
+def map_blocks(out: dict, sd, names: BlockNames, num_layers: int, pre: str = "") -> None:
+    """Append the blocks of `sd` to `out` under the file's names and in its order: per layer norm1, attn.qkv (q, k, v concatenated along the
+    rows, timm's order: vit.cpp:826-834), attn.proj, norm2, mlp.fc1, mlp.fc2, each as .weight then .bias.  LayerScale, where the family
+    has it, is folded."""
+    for i in range(num_layers):
+        q, p = pre + names.layer.format(i=i), f"blocks.{i}."
+        qkv = [q + n for n in names.qkv]
+        if any(n + ".bias" not in sd for n in qkv):
+            raise ValueError("qkv_bias=False: the file format carries the fused qkv bias")
+        _put(out, p + "norm1", sd, q + names.norm1)
+        out[p + "attn.qkv.weight"] = np.concatenate([sd[n + ".weight"] for n in qkv], 0)
+        out[p + "attn.qkv.bias"] = np.concatenate([sd[n + ".bias"] for n in qkv], 0)
+        _put(out, p + "attn.proj", sd, q + names.proj, names.ls1 and q + names.ls1)
+        _put(out, p + "norm2", sd, q + names.norm2)
+        _put(out, p + "mlp.fc1", sd, q + names.fc1)
+        _put(out, p + "mlp.fc2", sd, q + names.fc2, names.ls2 and q + names.ls2)
+
+
+def _zero_head(out: dict, D: int) -> None:
+    """The one-class class-token head of zeros that keeps a file without classifier well-formed (NO_HEAD_LABELS); embeddings are read through vitx_feat_*."""
+    out["head.weight"] = np.zeros((1, D), np.float32); out["head.bias"] = np.zeros((1,), np.float32)
+
+
+def _require_mlp_4x(cfg, field: str, want: int, note: str = "") -> None:
+    have = getattr(cfg, field, want)
+    if have != want:
+        raise ValueError(f"{field} {have}: the file format holds a 4 x hidden MLP{note}")
+
+
+def _f32(tensors: dict) -> Dict[str, np.ndarray]:
+    """Every tensor (a numpy array or a torch tensor) as a contiguous f32 array, in the order given."""
+    return {k: np.ascontiguousarray(np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, np.float32)) for k, v in tensors.items()}
+
+
+def grid_side(pos_embed, prefix_rows: int) -> int:
+    """g of a position table [1][prefix_rows + g^2][D] (prefix_rows 1: the class token's row; 0: a model without class token)."""
+    n = int(np.shape(pos_embed)[1])
+    g = int(round(max(n - prefix_rows, 0) ** 0.5))
+    if g < 1 or g * g + prefix_rows != n:
+        raise ValueError(f"pos_embed {tuple(np.shape(pos_embed))}: not {'1 + ' if prefix_rows else ''}a square grid")
+    return g
+
+
+# --------------------------------------------------------------------------- the families' embeddings, final norm and head
+def state_dict_to_timm(sd: Dict[str, np.ndarray], num_layers: int) -> Dict[str, np.ndarray]:
+    """An HF ViTForImageClassification state dict (numpy arrays) under the file's names, in the order the loader reads them.  The two namings of
+    the blocks are told apart by probing for transformers 5's `vit.layers.0`."""
+    e = "vit.embeddings."
+    out = {"cls_token": sd[e + "cls_token"], "pos_embed": sd[e + "position_embeddings"]}
+    _put(out, "patch_embed.proj", sd, e + "patch_embeddings.projection")
+    map_blocks(out, sd, VIT_BLOCKS_V5 if "vit.layers.0.attention.q_proj.weight" in sd else VIT_BLOCKS_V4, num_layers)
+    _put(out, "norm", sd, "vit.layernorm")
+    _put(out, "head", sd, "classifier")
+    return _f32(out)
+
+
 def dinov2_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, no_head: bool = False) -> Dict[str, np.ndarray]:
-    """Rename / fuse / fold an HF Dinov2[WithRegisters]{ForImageClassification, Model} state dict (numpy arrays) into the file's names and order."""
+    """An HF Dinov2[WithRegisters]{ForImageClassification, Model} state dict (numpy arrays) under the file's names and order.  register_tokens ->
+    `reg_token` [1][R][D] directly after cls_token; the classifier is the [C][2 D] head over concat(cls, mean of the patch tokens) (include/vitx.h
+    "register tokens and the pooled head": the reference's loader cannot read such a file); LayerScale is folded (fold_layer_scale); mask_token is
+    dropped.  SwiGLU, qk-norm, fc_norm and distillation tokens are refused by name.  no_head: a backbone, which gets the zero head."""
     if getattr(cfg, "use_swiglu_ffn", False):
         raise ValueError("use_swiglu_ffn: the SwiGLU MLP of the DINOv2 giant models is not supported (the forward path has the GELU MLP only)")
     for k in sd:
         for bad, what in (("q_norm", "qk-norm"), ("k_norm", "qk-norm"), ("fc_norm", "fc_norm"), ("dist_token", "a distillation token"), ("distillation", "a distillation token")):
             if bad in k:
                 raise ValueError(f"tensor {k!r}: {what} is not supported")
-    if getattr(cfg, "mlp_ratio", 4) != 4:
-        raise ValueError(f"mlp_ratio {cfg.mlp_ratio}: the file format holds a 4 x hidden MLP")
+    _require_mlp_4x(cfg, "mlp_ratio", 4)
     pre = next((p for p in ("dinov2_with_registers.", "dinov2.", "") if p + "embeddings.cls_token" in sd), None)
     if pre is None:
         raise ValueError("not a DINOv2 state dict: embeddings.cls_token is missing")
     e = pre + "embeddings."
-    D = int(np.shape(sd[e + "cls_token"])[-1])
-    out: Dict[str, np.ndarray] = {}
-    out["cls_token"] = sd[e + "cls_token"]
+    out = {"cls_token": sd[e + "cls_token"]}
     if e + "register_tokens" in sd:
         out["reg_token"] = sd[e + "register_tokens"]
     out["pos_embed"] = sd[e + "position_embeddings"]
-    out["patch_embed.proj.weight"] = sd[e + "patch_embeddings.projection.weight"]
-    out["patch_embed.proj.bias"] = sd[e + "patch_embeddings.projection.bias"]
-    for i in range(cfg.num_hidden_layers):
-        q, p = f"{pre}encoder.layer.{i}.", f"blocks.{i}."
-        qkv = [q + "attention.attention." + n for n in ("query", "key", "value")]
-        if any(n + ".bias" not in sd for n in qkv):
-            raise ValueError("qkv_bias=False: the file format carries the fused qkv bias")
-        out[p + "norm1.weight"] = sd[q + "norm1.weight"]; out[p + "norm1.bias"] = sd[q + "norm1.bias"]
-        out[p + "attn.qkv.weight"] = np.concatenate([sd[n + ".weight"] for n in qkv], 0)
-        out[p + "attn.qkv.bias"] = np.concatenate([sd[n + ".bias"] for n in qkv], 0)
-        out[p + "attn.proj.weight"], out[p + "attn.proj.bias"] = fold_layer_scale(sd[q + "attention.output.dense.weight"], sd[q + "attention.output.dense.bias"], sd[q + "layer_scale1.lambda1"])
-        out[p + "norm2.weight"] = sd[q + "norm2.weight"]; out[p + "norm2.bias"] = sd[q + "norm2.bias"]
-        out[p + "mlp.fc1.weight"] = sd[q + "mlp.fc1.weight"]; out[p + "mlp.fc1.bias"] = sd[q + "mlp.fc1.bias"]
-        out[p + "mlp.fc2.weight"], out[p + "mlp.fc2.bias"] = fold_layer_scale(sd[q + "mlp.fc2.weight"], sd[q + "mlp.fc2.bias"], sd[q + "layer_scale2.lambda1"])
-    out["norm.weight"] = sd[pre + "layernorm.weight"]; out["norm.bias"] = sd[pre + "layernorm.bias"]
-    if no_head:          # a backbone: a one-class class-token head of zeros keeps the file well-formed; embeddings are read through vitx_feat_*
-        out["head.weight"] = np.zeros((1, D), np.float32); out["head.bias"] = np.zeros((1,), np.float32)
+    _put(out, "patch_embed.proj", sd, e + "patch_embeddings.projection")
+    map_blocks(out, sd, DINOV2_BLOCKS, cfg.num_hidden_layers, pre)
+    _put(out, "norm", sd, pre + "layernorm")
+    if no_head:
+        _zero_head(out, int(np.shape(out["cls_token"])[-1]))
+    elif "classifier.weight" not in sd:
+        raise ValueError("the model has no classifier: convert a backbone with no_head=True (--no-head)")
     else:
-        if "classifier.weight" not in sd:
-            raise ValueError("the model has no classifier: convert a backbone with no_head=True (--no-head)")
-        out["head.weight"] = sd["classifier.weight"]; out["head.bias"] = sd["classifier.bias"]
-    return {k: np.ascontiguousarray(np.asarray(v, np.float32)) for k, v in out.items()}
+        _put(out, "head", sd, "classifier")
+    return _f32(out)
 
 
 def clip_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, no_head: bool = False) -> Dict[str, np.ndarray]:
-    """Rename / fuse an HF CLIPVisionModelWithProjection / CLIPModel / CLIPVisionModel state dict (numpy arrays) into the file's names and order."""
+    """An HF CLIPVisionModelWithProjection / CLIPModel / CLIPVisionModel state dict (numpy arrays) under the file's names and order.
+    class_embedding -> cls_token, position_embedding -> pos_embed, pre_layrnorm -> `pre_norm.*` directly after pos_embed, the bias-free patch
+    convolution gets a zero bias, post_layernorm -> norm, and the bias-free visual_projection [E][D] becomes head.weight with a zero head.bias:
+    the file has E "classes" (labelled dim_0 .. dim_{E-1}), its logits are CLIP's image_embeds and its probabilities mean nothing -- zero-shot
+    probabilities come from a bank of text embeddings (zeroshot_bank).  no_head: a tower without projection, which gets the zero head."""
     pre = next((p for p in ("vision_model.", "") if p + "embeddings.class_embedding" in sd), None)
     if pre is None:
         raise ValueError("not a CLIP vision state dict: embeddings.class_embedding is missing")
-    D = int(np.shape(sd[pre + "embeddings.class_embedding"])[-1])
-    if getattr(cfg, "intermediate_size", 4 * D) != 4 * D:
-        raise ValueError(f"intermediate_size {cfg.intermediate_size}: the file format holds a 4 x hidden MLP")
-    if pre + "embeddings.patch_embedding.bias" in sd:
+    e = pre + "embeddings."
+    D = int(np.shape(sd[e + "class_embedding"])[-1])
+    _require_mlp_4x(cfg, "intermediate_size", 4 * D)
+    if e + "patch_embedding.bias" in sd:
         raise ValueError("patch_embedding.bias: not a CLIP vision tower (its patch convolution has no bias)")
-    out: Dict[str, np.ndarray] = {}
-    out["cls_token"] = np.reshape(sd[pre + "embeddings.class_embedding"], (1, 1, D))
-    out["pos_embed"] = np.reshape(sd[pre + "embeddings.position_embedding.weight"], (1, -1, D))
-    out["pre_norm.weight"] = sd[pre + "pre_layrnorm.weight"]; out["pre_norm.bias"] = sd[pre + "pre_layrnorm.bias"]
-    out["patch_embed.proj.weight"] = sd[pre + "embeddings.patch_embedding.weight"]
+    out = {"cls_token": np.reshape(sd[e + "class_embedding"], (1, 1, D)), "pos_embed": np.reshape(sd[e + "position_embedding.weight"], (1, -1, D))}
+    _put(out, "pre_norm", sd, pre + "pre_layrnorm")
+    out["patch_embed.proj.weight"] = sd[e + "patch_embedding.weight"]
     out["patch_embed.proj.bias"] = np.zeros((D,), np.float32)
-    for i in range(cfg.num_hidden_layers):
-        q, p = f"{pre}encoder.layers.{i}.", f"blocks.{i}."
-        qkv = [q + "self_attn." + n for n in ("q_proj", "k_proj", "v_proj")]
-        out[p + "norm1.weight"] = sd[q + "layer_norm1.weight"]; out[p + "norm1.bias"] = sd[q + "layer_norm1.bias"]
-        out[p + "attn.qkv.weight"] = np.concatenate([sd[n + ".weight"] for n in qkv], 0)
-        out[p + "attn.qkv.bias"] = np.concatenate([sd[n + ".bias"] for n in qkv], 0)
-        out[p + "attn.proj.weight"] = sd[q + "self_attn.out_proj.weight"]; out[p + "attn.proj.bias"] = sd[q + "self_attn.out_proj.bias"]
-        out[p + "norm2.weight"] = sd[q + "layer_norm2.weight"]; out[p + "norm2.bias"] = sd[q + "layer_norm2.bias"]
-        out[p + "mlp.fc1.weight"] = sd[q + "mlp.fc1.weight"]; out[p + "mlp.fc1.bias"] = sd[q + "mlp.fc1.bias"]
-        out[p + "mlp.fc2.weight"] = sd[q + "mlp.fc2.weight"]; out[p + "mlp.fc2.bias"] = sd[q + "mlp.fc2.bias"]
-    out["norm.weight"] = sd[pre + "post_layernorm.weight"]; out["norm.bias"] = sd[pre + "post_layernorm.bias"]
-    if no_head:          # a tower without projection: a one-class head of zeros keeps the file well-formed; embeddings are read through vitx_feat_*
-        out["head.weight"] = np.zeros((1, D), np.float32); out["head.bias"] = np.zeros((1,), np.float32)
+    map_blocks(out, sd, CLIP_BLOCKS, cfg.num_hidden_layers, pre)
+    _put(out, "norm", sd, pre + "post_layernorm")
+    if no_head:
+        _zero_head(out, D)
+    elif "visual_projection.weight" not in sd:
+        raise ValueError("the model has no visual_projection: convert a CLIPVisionModel with no_head=True (--no-head)")
     else:
-        if "visual_projection.weight" not in sd:
-            raise ValueError("the model has no visual_projection: convert a CLIPVisionModel with no_head=True (--no-head)")
         out["head.weight"] = sd["visual_projection.weight"]
         out["head.bias"] = np.zeros((int(np.shape(out["head.weight"])[0]),), np.float32)
-    return {k: np.ascontiguousarray(np.asarray(v, np.float32)) for k, v in out.items()}
+    return _f32(out)
 
 
 _POOL_ORDER = ("latent", "q.weight", "q.bias", "kv.weight", "kv.bias", "proj.weight", "proj.bias", "norm.weight", "norm.bias",
@@ -310,170 +328,166 @@ _POOL_ORDER = ("latent", "q.weight", "q.bias", "kv.weight", "kv.bias", "proj.wei
 
 
 def siglip_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg) -> Dict[str, np.ndarray]:
-    """Rename / fuse / split an HF SiglipVisionModel / SiglipModel state dict (numpy arrays) into the file's names and order (no cls_token; the
-    thirteen attn_pool.* tensors after norm.bias; the one-class head of zeros)."""
+    """An HF SiglipVisionModel / SiglipModel state dict (numpy arrays) under the file's names and order.  There is NO class token:
+    position_embedding [g^2][D] -> pos_embed [1][g^2][D]; post_layernorm -> norm; the multi-head attention-pooling head becomes the thirteen
+    `attn_pool.*` tensors after norm.bias (include/vitx.h "no class token and the attention-pooling head", timm's AttentionPoolLatent names):
+    head.probe -> latent, head.attention.in_proj_weight / in_proj_bias split into q (rows 0 .. D) and kv (rows D .. 3 D), out_proj -> proj,
+    head.layernorm -> norm, head.mlp -> mlp.  A tower has no classifier: the file gets the zero head, and its pooled embedding -- SigLIP's
+    pooler_output / image_embeds -- is read with --embed-kind cls / VITX_FEAT_CLS."""
     pre = next((p for p in ("vision_model.", "") if p + "embeddings.position_embedding.weight" in sd), None)
     if pre is None:
         raise ValueError("not a SigLIP vision state dict: embeddings.position_embedding.weight is missing")
-    if pre + "embeddings.patch_embedding.weight" not in sd or np.ndim(sd[pre + "embeddings.patch_embedding.weight"]) != 4:
+    e, h = pre + "embeddings.", pre + "head."
+    if e + "patch_embedding.weight" not in sd or np.ndim(sd[e + "patch_embedding.weight"]) != 4:
         raise ValueError("Siglip2VisionModel (NaFlex) is not supported: its patch embedding is a Linear over flattened patches, not a convolution")
     D = int(cfg.hidden_size)
-    if getattr(cfg, "intermediate_size", 4 * D) != 4 * D:
-        raise ValueError(f"intermediate_size {cfg.intermediate_size}: the file format holds a 4 x hidden MLP (SO400M's 4304 is not supported)")
-    if getattr(cfg, "vision_use_head", True) is False or pre + "head.probe" not in sd:
+    _require_mlp_4x(cfg, "intermediate_size", 4 * D, " (SO400M's 4304 is not supported)")
+    if getattr(cfg, "vision_use_head", True) is False or h + "probe" not in sd:
         raise ValueError("vision_use_head = False: the tower has no attention-pooling head, and the file format has no slot for a SigLIP tower without it")
-    out: Dict[str, np.ndarray] = {}
-    out["pos_embed"] = np.reshape(sd[pre + "embeddings.position_embedding.weight"], (1, -1, D))
-    out["patch_embed.proj.weight"] = sd[pre + "embeddings.patch_embedding.weight"]
-    out["patch_embed.proj.bias"] = sd[pre + "embeddings.patch_embedding.bias"]
-    for i in range(cfg.num_hidden_layers):
-        q, p = f"{pre}encoder.layers.{i}.", f"blocks.{i}."
-        qkv = [q + "self_attn." + n for n in ("q_proj", "k_proj", "v_proj")]
-        out[p + "norm1.weight"] = sd[q + "layer_norm1.weight"]; out[p + "norm1.bias"] = sd[q + "layer_norm1.bias"]
-        out[p + "attn.qkv.weight"] = np.concatenate([sd[n + ".weight"] for n in qkv], 0)
-        out[p + "attn.qkv.bias"] = np.concatenate([sd[n + ".bias"] for n in qkv], 0)
-        out[p + "attn.proj.weight"] = sd[q + "self_attn.out_proj.weight"]; out[p + "attn.proj.bias"] = sd[q + "self_attn.out_proj.bias"]
-        out[p + "norm2.weight"] = sd[q + "layer_norm2.weight"]; out[p + "norm2.bias"] = sd[q + "layer_norm2.bias"]
-        out[p + "mlp.fc1.weight"] = sd[q + "mlp.fc1.weight"]; out[p + "mlp.fc1.bias"] = sd[q + "mlp.fc1.bias"]
-        out[p + "mlp.fc2.weight"] = sd[q + "mlp.fc2.weight"]; out[p + "mlp.fc2.bias"] = sd[q + "mlp.fc2.bias"]
-    out["norm.weight"] = sd[pre + "post_layernorm.weight"]; out["norm.bias"] = sd[pre + "post_layernorm.bias"]
-    h = pre + "head."
+    out = {"pos_embed": np.reshape(sd[e + "position_embedding.weight"], (1, -1, D))}
+    _put(out, "patch_embed.proj", sd, e + "patch_embedding")
+    map_blocks(out, sd, CLIP_BLOCKS, cfg.num_hidden_layers, pre)
+    _put(out, "norm", sd, pre + "post_layernorm")
     w, b = np.asarray(sd[h + "attention.in_proj_weight"]), np.asarray(sd[h + "attention.in_proj_bias"])
     if w.shape != (3 * D, D) or b.shape != (3 * D,):
         raise ValueError(f"head.attention.in_proj_weight {w.shape}: expected [{3 * D}][{D}]")
     out["attn_pool.latent"] = np.reshape(sd[h + "probe"], (1, 1, D))
     out["attn_pool.q.weight"] = w[:D]; out["attn_pool.q.bias"] = b[:D]
     out["attn_pool.kv.weight"] = w[D:]; out["attn_pool.kv.bias"] = b[D:]
-    out["attn_pool.proj.weight"] = sd[h + "attention.out_proj.weight"]; out["attn_pool.proj.bias"] = sd[h + "attention.out_proj.bias"]
-    out["attn_pool.norm.weight"] = sd[h + "layernorm.weight"]; out["attn_pool.norm.bias"] = sd[h + "layernorm.bias"]
-    out["attn_pool.mlp.fc1.weight"] = sd[h + "mlp.fc1.weight"]; out["attn_pool.mlp.fc1.bias"] = sd[h + "mlp.fc1.bias"]
-    out["attn_pool.mlp.fc2.weight"] = sd[h + "mlp.fc2.weight"]; out["attn_pool.mlp.fc2.bias"] = sd[h + "mlp.fc2.bias"]
-    out["head.weight"] = np.zeros((1, D), np.float32); out["head.bias"] = np.zeros((1,), np.float32)
-    return {k: np.ascontiguousarray(np.asarray(v, np.float32)) for k, v in out.items()}
+    for dst, src in (("proj", "attention.out_proj"), ("norm", "layernorm"), ("mlp.fc1", "mlp.fc1"), ("mlp.fc2", "mlp.fc2")):
+        _put(out, "attn_pool." + dst, sd, h + src)
+    _zero_head(out, D)
+    return _f32(out)
+
+
+# --------------------------------------------------------------------------- one write path for every HuggingFace family
+def _config_labels(cfg, num_classes: int):
+    return {int(k): str(v) for k, v in (getattr(cfg, "id2label", None) or {}).items()} or None
+
+
+# name: as the refusals call the family; mapper(sd, cfg, no_head) -> the file's tensors; prefix_rows: rows of pos_embed in front of the patch grid;
+# labels(cfg, num_classes) -> id2label of a model converted with its head; head: "always" -- no_head is refused --, "optional" -- no_head converts a
+# model without classifier / projection -- or "never" -- the family has no classifier, no_head is accepted and not required; loaders: the
+# transformers classes main() loads a checkpoint with, (with its head, with --no-head).
+Family = namedtuple("Family", "name mapper prefix_rows labels head loaders")
+
+
+_VIT = Family("ViT", lambda sd, cfg, no_head: state_dict_to_timm(sd, cfg.num_hidden_layers), 1, _config_labels, "always", ("ViTForImageClassification",) * 2)
+_DINOV2 = Family("DINOv2", dinov2_state_dict_to_timm, 1, _config_labels, "optional", ("AutoModelForImageClassification", "AutoModel"))
+_CLIP = Family("CLIP", clip_state_dict_to_timm, 1, lambda cfg, E: {i: f"dim_{i}" for i in range(E)}, "optional", ("CLIPVisionModelWithProjection", "CLIPVisionModel"))
+_SIGLIP = Family("SigLIP", lambda sd, cfg, no_head: siglip_state_dict_to_timm(sd, cfg), 0, None, "never", ("SiglipVisionModel",) * 2)
+_TWO_TOWERS = ("clip", "siglip")          # converted as their vision tower (config.vision_config)
+# by model_type, the vision tower's or, for main(), the checkpoint's; any other model_type is taken for a ViT
+FAMILIES = {"vit": _VIT, "dinov2": _DINOV2, "dinov2_with_registers": _DINOV2, "clip_vision_model": _CLIP, "clip": _CLIP, "siglip_vision_model": _SIGLIP, "siglip": _SIGLIP}
 
 
 def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_head: bool = False, preprocessor_config: dict | None = None) -> HParams:
-    """model: transformers.ViTForImageClassification, Dinov2ForImageClassification, Dinov2WithRegistersForImageClassification,
-    CLIPVisionModelWithProjection or CLIPModel (eval); with no_head=True a Dinov2Model / Dinov2WithRegistersModel backbone or a CLIPVisionModel.
-    The activation and the LayerNorm epsilon are the config's (with_arch).  preprocessor_config: the checkpoint's preprocessor_config.json as a
-    dict -- its preprocessing is written as the `preproc` tensor (hf_preproc); None writes the file without one.  Writes `path`; returns the hparams written.
-    vitstr=True: the model is a ViTSTR scene-text recogniser (/root/reference/extensions/vitstr.cpp/convert-pth-to-ggml.py: a ViT with ONE
-    input channel whose classifier is applied to the first 25 tokens); the file then carries the character set as labels, and the
-    one-channel patch kernel is what makes vit_model_load / vitx_model_load treat it as a ViTSTR model (vitstr.cpp:482)."""
+    """model: a transformers model of one of FAMILIES, in eval mode (the module docstring lists the classes); no_head=True converts a model
+    without classifier or projection, whose file gets the zero head labelled "(no head)" (a SigLIP tower always does).  The activation and the
+    LayerNorm epsilon are the config's (with_arch); the class count and the image size are read off head.weight and pos_embed.
+    preprocessor_config: the checkpoint's preprocessor_config.json as a dict -- its preprocessing is written as the `preproc` tensor (hf_preproc);
+    None writes the file without one.  Writes `path`; returns the hparams written.
+    vitstr=True: the model is a ViTSTR scene-text recogniser (the reference's extensions/vitstr.cpp/convert-pth-to-ggml.py: a ViT with ONE input
+    channel whose classifier is applied to the first 25 tokens); the file then carries the character set as labels, and the one-channel patch
+    kernel is what makes vit_model_load / vitx_model_load treat it as a ViTSTR model (vitstr.cpp:482)."""
     cfg = model.config
     cls_name = type(model).__name__
     if cls_name.startswith("Siglip2") or getattr(cfg, "model_type", "").startswith("siglip2"):
         raise ValueError(f"{cls_name} (Siglip2VisionModel, NaFlex) is not supported: its patch embedding is a Linear over flattened patches")
     if cls_name == "SiglipForImageClassification":
         raise ValueError("SiglipForImageClassification is not supported: it classifies the mean of the patch tokens and has no attention-pooling head (no slot for it)")
-    if getattr(cfg, "model_type", "") in ("clip", "siglip"):
+    if getattr(cfg, "model_type", "") in _TWO_TOWERS:
         cfg = cfg.vision_config
+    fam = FAMILIES.get(getattr(cfg, "model_type", ""), _VIT)
     if vitstr and preprocessor_config is not None:
         raise ValueError("a ViTSTR model's preprocessing is fixed: convert it without a preprocessor_config")
-    pp = (lambda img_size: hf_preproc(preprocessor_config, img_size)) if preprocessor_config is not None else (lambda img_size: None)
     if vitstr and getattr(cfg, "num_channels", 3) != 1:
         raise ValueError("a ViTSTR model takes one (grey) input channel")
     hd = cfg.hidden_size // cfg.num_attention_heads
     if cfg.hidden_size % cfg.num_attention_heads or hd % 8 or not 8 <= hd <= 128:
         raise ValueError(f"head_dim {hd}: the forward path takes multiples of 8 up to 128 (64 runs the tuned attention kernels)")
+    if vitstr and fam.name != "ViT":
+        raise ValueError(f"a {fam.name} model is not a ViTSTR model")
+    if no_head and fam.head == "always":
+        raise ValueError("no_head converts a DINOv2 backbone (Dinov2Model, Dinov2WithRegistersModel), a CLIPVisionModel or a SigLIP tower")
+    headless = fam.head == "never" or no_head
     sd = {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
     act, eps = hf_activation(cfg), float(getattr(cfg, "layer_norm_eps", 1e-6))
-    if getattr(cfg, "model_type", "") == "clip_vision_model":
-        if vitstr:
-            raise ValueError("a CLIP model is not a ViTSTR model")
-        tensors = clip_state_dict_to_timm(sd, cfg, no_head=no_head)
-        g = int(round((tensors["pos_embed"].shape[1] - 1) ** 0.5))
-        if g * g + 1 != tensors["pos_embed"].shape[1]:
-            raise ValueError(f"position_embedding {tensors['pos_embed'].shape}: not 1 + a square grid")
-        E = int(tensors["head.weight"].shape[0])
-        hp = HParams(cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, E, cfg.patch_size, g * cfg.patch_size, ftype)
-        id2label = {0: "(no head)"} if no_head else {i: f"dim_{i}" for i in range(E)}
-        write_model(path, hp, with_arch(tensors, act, eps), id2label=id2label, ftype=ftype, preproc=pp(hp.img_size))
-        return hp
-    if getattr(cfg, "model_type", "") == "siglip_vision_model":
-        if vitstr:
-            raise ValueError("a SigLIP model is not a ViTSTR model")
-        tensors = siglip_state_dict_to_timm(sd, cfg)
-        g = int(round(tensors["pos_embed"].shape[1] ** 0.5))
-        if g * g != tensors["pos_embed"].shape[1]:
-            raise ValueError(f"position_embedding {tensors['pos_embed'].shape}: not a square grid")
-        hp = HParams(cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, 1, cfg.patch_size, g * cfg.patch_size, ftype)
-        write_model(path, hp, with_arch(tensors, act, eps), id2label={0: "(no head)"}, ftype=ftype, preproc=pp(hp.img_size))
-        return hp
-    if getattr(cfg, "model_type", "") in ("dinov2", "dinov2_with_registers"):
-        if vitstr:
-            raise ValueError("a DINOv2 model is not a ViTSTR model")
-        tensors = dinov2_state_dict_to_timm(sd, cfg, no_head=no_head)
-        g = int(round((tensors["pos_embed"].shape[1] - 1) ** 0.5))       # the checkpoint's own grid (config.image_size states it too)
-        if g * g + 1 != tensors["pos_embed"].shape[1]:
-            raise ValueError(f"position_embeddings {tensors['pos_embed'].shape}: not 1 + a square grid")
-        hp = HParams(cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, int(tensors["head.weight"].shape[0]), cfg.patch_size, g * cfg.patch_size, ftype)
-        id2label = {0: "(no head)"} if no_head else ({int(k): str(v) for k, v in (getattr(cfg, "id2label", None) or {}).items()} or None)
-        write_model(path, hp, with_arch(tensors, act, eps), id2label=id2label, ftype=ftype, preproc=pp(hp.img_size))
-        return hp
-    if no_head:
-        raise ValueError("no_head converts a DINOv2 backbone (Dinov2Model, Dinov2WithRegistersModel), a CLIPVisionModel or a SigLIP tower")
-    hp = HParams(cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, cfg.num_labels, cfg.patch_size, cfg.image_size, ftype)
-    tensors = state_dict_to_timm(sd, cfg.num_hidden_layers)
-    id2label = {int(k): str(v) for k, v in (getattr(cfg, "id2label", None) or {}).items()} or None
+    tensors = fam.mapper(sd, cfg, no_head)
+    g = grid_side(tensors["pos_embed"], fam.prefix_rows)          # the checkpoint's own grid (config.image_size states it too)
+    hp = HParams(cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, int(tensors["head.weight"].shape[0]), cfg.patch_size, g * cfg.patch_size, ftype)
+    id2label = NO_HEAD_LABELS if headless else fam.labels(cfg, hp.num_classes)
     if vitstr:
         from .synth import VITSTR_LABELS
-        if cfg.num_labels != len(VITSTR_LABELS):
-            raise ValueError(f"ViTSTR's character set has {len(VITSTR_LABELS)} classes ([GO], [s], 94 printable characters), the model has {cfg.num_labels}")
+        if hp.num_classes != len(VITSTR_LABELS):
+            raise ValueError(f"ViTSTR's character set has {len(VITSTR_LABELS)} classes ([GO], [s], 94 printable characters), the model has {hp.num_classes}")
         id2label = dict(VITSTR_LABELS)
-    write_model(path, hp, with_arch(tensors, act, eps), id2label=id2label, ftype=ftype, preproc=pp(hp.img_size))
+    write_model(path, hp, with_arch(tensors, act, eps), id2label=id2label, ftype=ftype,
+                preproc=hf_preproc(preprocessor_config, hp.img_size) if preprocessor_config is not None else None)
     return hp
 
 
+# --------------------------------------------------------------------------- timm state dicts
 _TIMM_UNSUPPORTED = {"fc_norm.": "fc_norm", "dist_token": "a distillation token", "head_dist.": "a distillation head", ".q_norm.": "qk-norm", ".k_norm.": "qk-norm",
                      "attn_pool.pos_embed": "a position embedding inside the attention pooling"}
+# The head count is NOT in a state_dict (the reference reads timm's module attribute): it is inferred only for the widths of timm's released ViTs,
+# where it is unambiguous; any other width needs --heads (D // 64 would turn ViT-H/14's 16 heads of 80 into 20 heads of 64 -- a file that loads,
+# runs and is wrong).
+_TIMM_HEADS = {192: 3, 384: 6, 768: 12, 1024: 16, 1280: 16, 1152: 16, 1408: 16, 1664: 16}      # tiny, small, base, large, huge, so400m, giant, gigantic
+
+
+def _placed_after(t: dict, anchor: str, names) -> dict:
+    """`t` with the tensors `names`, in that order, directly after `anchor`; every other tensor keeps its place."""
+    moved = {k: t[k] for k in names}
+    out = {}
+    for k, v in t.items():
+        if k not in moved:
+            out[k] = v
+        if k == anchor:
+            out.update(moved)
+    return out
 
 
 def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2label=None, act: str = "tanh", eps: float = 1e-6, preproc: dict | None = None) -> HParams:
-    """sd: a timm VisionTransformer state_dict (name -> array / tensor), e.g. torch.load("vit_base_patch16_224.pth").  Mirrors
-    /root/reference/convert-pth-to-ggml.py:96-158 without importing timm: hidden size, depth, classes, patch and image size come from the
-    tensor shapes (the reference reads them off the timm module), `norm_pre.*` is skipped exactly as there (:117-120), the ViTSTR
-    extension's checkpoints lose their "module.vitstr." prefix (extensions/vitstr.cpp/convert-pth-to-ggml.py:226-229) and are recognised
-    by their one-channel patch kernel.  DINOv2-class checkpoints are taken: `blocks.N.ls1.gamma` / `ls2.gamma` (LayerScale) are folded into
-    attn.proj / mlp.fc2 in f32, `reg_token` becomes the file's reg_token, and a `pos_embed` of g^2 rows (timm's no_embed_class layout of the
-    reg4 DINOv2 models: the class token gets no position term there) gets a zero row in front, which is exact.  Models with other tensors
-    the file has no slot for (fc_norm, distillation tokens, qk-norm) are refused here, by name.  `attn_pool.*` (AttentionPoolLatent: SigLIP) is
-    taken, without cls_token only, as the file's attention-pooling head; its qk-norm and position embedding (attn_pool.q_norm / k_norm / pos_embed) are
-    refused by name; a checkpoint without head.* (num_classes 0) gets the one-class head of zeros.
+    """sd: a timm VisionTransformer state_dict (name -> array / tensor), e.g. torch.load("vit_base_patch16_224.pth").  It already carries the names
+    the file uses -- the reference's convert-pth-to-ggml.py:96-158 writes `timm_model.state_dict()` verbatim -- so no `timm` is needed: hidden
+    size, depth, classes, patch and image size come from the tensor shapes (the reference reads them off the timm module), `norm_pre.*` is skipped
+    exactly as there (:117-120), the ViTSTR extension's checkpoints lose their "module.vitstr." prefix (extensions/vitstr.cpp/convert-pth-to-ggml.py:
+    226-229) and are recognised by their one-channel patch kernel.  The tensors keep the state dict's own order, apart from two placements: reg_token
+    goes directly after cls_token, and `attn_pool.*`, in the file's order, then head.* go behind everything else.
+    DINOv2-class checkpoints are taken: `blocks.N.ls1.gamma` / `ls2.gamma` (LayerScale) are folded into attn.proj / mlp.fc2 in f32, and a `pos_embed`
+    of g^2 rows beside `reg_token` (timm's no_embed_class layout of the reg4 DINOv2 models: the class token gets no position term there) gets a zero
+    row in front, which is exact.  `attn_pool.*` (AttentionPoolLatent: SigLIP) is taken, without cls_token only, as the file's attention-pooling
+    head; a checkpoint without head.* (num_classes 0) gets the zero head.  Tensors the file has no slot for (_TIMM_UNSUPPORTED) are refused by name.
     A state dict carries no config: `act` ("tanh", "erf", "quick") and `eps` state the model's activation and LayerNorm epsilon.  The default
-    (tanh, 1e-6) writes the reference's file, without `arch`, as this function always has; a checkpoint of timm's VisionTransformer was trained
-    with nn.GELU and wants act="erf" (eps 1e-6 is timm's too).
+    (tanh, 1e-6) writes the reference's file, without `arch`; timm's VisionTransformer was trained with nn.GELU and wants act="erf" (its eps is 1e-6).
     preproc: the keyword arguments of cli_preproc (resize, crop, filt, mean, std, crop_round) -- the checkpoint's preprocessing, written as the
-    `preproc` tensor; None or all unset: no tensor, the file is what this function always wrote."""
+    `preproc` tensor; None or all unset: no tensor."""
     if act not in _ACT_NAMES:
         raise ValueError(f"act {act!r}: one of {sorted(_ACT_NAMES)}")
-    sd = {k: v for k, v in (sd.get("model", sd) if isinstance(sd, dict) and "model" in sd and not hasattr(sd["model"], "shape") else sd).items()}
-    t: Dict[str, np.ndarray] = {}
-    for k, v in sd.items():
-        k = k.replace("module.vitstr.", "")
-        if k.startswith("norm_pre"):
-            continue
+    if isinstance(sd, dict) and "model" in sd and not hasattr(sd["model"], "shape"):
+        sd = sd["model"]
+    t = {k.replace("module.vitstr.", ""): v for k, v in sd.items()}
+    t = {k: v for k, v in t.items() if not k.startswith("norm_pre")}
+    for k in t:
         for u, what in _TIMM_UNSUPPORTED.items():
             if u in k:
                 raise ValueError(f"tensor {k!r}: {what} is not supported (the file format has no slot for it)")
-        t[k] = np.ascontiguousarray(np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, np.float32))
+    t = _f32(t)
     map_head = any(k.startswith("attn_pool.") for k in t)
     if map_head:
         if "cls_token" in t or "reg_token" in t:
             raise ValueError("attn_pool.* beside cls_token / reg_token: the attention-pooling head is taken only from a model without a class token")
-        D = int(t["pos_embed"].shape[-1]) if "pos_embed" in t else 0
-        missing = [f"attn_pool.{n}" for n in _POOL_ORDER if f"attn_pool.{n}" not in t]
-        extra = [k for k in t if k.startswith("attn_pool.") and k[len("attn_pool."):] not in _POOL_ORDER]
+        pool = [f"attn_pool.{n}" for n in _POOL_ORDER]
+        missing = [k for k in pool if k not in t]
+        extra = [k for k in t if k.startswith("attn_pool.") and k not in pool]
         if missing or extra:
             raise ValueError(f"the attention-pooling head is not the thirteen tensors the file holds: missing {missing}, unknown {extra}")
-        if "head.weight" not in t:                        # num_classes 0: the zero head
-            t["head.weight"] = np.zeros((1, D), np.float32); t["head.bias"] = np.zeros((1,), np.float32)
-            id2label = id2label if id2label is not None else {0: "(no head)"}
+        D = int(t["pos_embed"].shape[-1]) if "pos_embed" in t else 0
+        if "head.weight" not in t:                        # num_classes 0
+            _zero_head(t, D)
+            id2label = id2label if id2label is not None else NO_HEAD_LABELS
         t["attn_pool.latent"] = t["attn_pool.latent"].reshape(1, 1, D)
-        ordered: Dict[str, np.ndarray] = {k: v for k, v in t.items() if not k.startswith(("attn_pool.", "head."))}
-        ordered.update({f"attn_pool.{n}": t[f"attn_pool.{n}"] for n in _POOL_ORDER})
-        ordered.update({k: v for k, v in t.items() if k.startswith("head.")})
-        t = ordered
     for need in ("cls_token", "pos_embed", "patch_embed.proj.weight", "patch_embed.proj.bias", "norm.weight", "norm.bias", "head.weight", "head.bias"):
         if need not in t and not (map_head and need == "cls_token"):
             raise ValueError(f"not a timm VisionTransformer state_dict: {need!r} is missing")
@@ -487,26 +501,18 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
     for gk in ls_have:
         p = gk.replace(".ls1.gamma", ".attn.proj.").replace(".ls2.gamma", ".mlp.fc2.")
         t[p + "weight"], t[p + "bias"] = fold_layer_scale(t[p + "weight"], t[p + "bias"], t.pop(gk))
-    n_rows = int(t["pos_embed"].shape[1])
-    if "reg_token" in t and int(round(n_rows ** 0.5)) ** 2 == n_rows and n_rows > 1:       # no_embed_class: g^2 rows, none for the class token
-        t["pos_embed"] = np.ascontiguousarray(np.concatenate([np.zeros((1, 1, D), np.float32), t["pos_embed"]], axis=1))
-    if "reg_token" in t:                                       # the file's order: directly after cls_token
-        reg = t.pop("reg_token")
-        ordered: Dict[str, np.ndarray] = {}
-        for k, v in t.items():
-            ordered[k] = v
-            if k == "cls_token":
-                ordered["reg_token"] = reg
-        t = ordered
+    if "reg_token" in t:
+        n_rows = int(t["pos_embed"].shape[1])
+        if int(round(n_rows ** 0.5)) ** 2 == n_rows and n_rows > 1:       # no_embed_class: g^2 rows, none for the class token
+            t["pos_embed"] = np.ascontiguousarray(np.concatenate([np.zeros((1, 1, D), np.float32), t["pos_embed"]], axis=1))
+        t = _placed_after(t, "cls_token", ["reg_token"])
+    if map_head:
+        last = [k for k in t if not k.startswith(("attn_pool.", "head."))][-1]
+        t = _placed_after(t, last, pool + [k for k in t if k.startswith("head.")])
     Dw, cin, P, P2 = t["patch_embed.proj.weight"].shape
-    n_tok = int(t["pos_embed"].shape[1])
-    g = int(round((n_tok - (0 if map_head else 1)) ** 0.5))
-    if Dw != D or P != P2 or g * g + (0 if map_head else 1) != n_tok or cin not in (1, 3):
+    g = grid_side(t["pos_embed"], 0 if map_head else 1)
+    if Dw != D or P != P2 or cin not in (1, 3):
         raise ValueError(f"unexpected shapes: patch kernel {t['patch_embed.proj.weight'].shape}, pos_embed {t['pos_embed'].shape}")
-    # The head count is NOT in a state_dict (the reference reads timm's module attribute, convert-pth-to-ggml.py): it is only inferred for
-    # the widths of timm's released ViTs, where it is unambiguous; any other width needs --heads (r03 advisor: D // 64 silently turned
-    # ViT-H/14's 16 heads of 80 into 20 heads of 64 -- a file that loads, runs and is wrong).
-    _TIMM_HEADS = {192: 3, 384: 6, 768: 12, 1024: 16, 1280: 16, 1152: 16, 1408: 16, 1664: 16}      # tiny, small, base, large, huge, so400m, giant, gigantic
     H = heads or _TIMM_HEADS.get(D, 0)
     if H <= 0:
         raise ValueError(f"hidden size {D} is not a released timm ViT width ({sorted(_TIMM_HEADS)}): pass the head count (--heads)")
@@ -517,18 +523,18 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
         from .synth import VITSTR_LABELS
         if hp.num_classes == len(VITSTR_LABELS):
             id2label = dict(VITSTR_LABELS)
-    expected = 4 + 12 * L + 4 + (1 if "reg_token" in t else 0) + (12 if map_head else 0)
+    # pos_embed, the patch kernel and bias, 12 per block, norm.* and head.*; the class token (+ registers) or the thirteen of the pooling head
+    expected = 3 + 12 * L + 4 + (len(_POOL_ORDER) if map_head else 1 + ("reg_token" in t))
     if len(t) != expected:
         raise ValueError(f"{len(t)} tensors after filtering, the file format holds exactly {expected} for {L} layers (vit.cpp:512-574)")
-    if cin == 1 and preproc and cli_preproc(hp.img_size, **preproc) is not None:
+    slots = cli_preproc(hp.img_size, **preproc) if preproc else None
+    if cin == 1 and slots is not None:
         raise ValueError("a ViTSTR model's preprocessing is fixed: the --pp-* options do not apply")
-    write_model(path, hp, with_arch(t, _ACT_NAMES[act], eps), id2label=id2label, ftype=ftype, preproc=cli_preproc(hp.img_size, **preproc) if preproc else None)
+    write_model(path, hp, with_arch(t, _ACT_NAMES[act], eps), id2label=id2label, ftype=ftype, preproc=slots)
     return hp
 
 
-ZS_SOFTMAX, ZS_SIGMOID = 0, 1                   # enum vitx_zs_kind
-
-
+# --------------------------------------------------------------------------- zero-shot banks
 def _l2_rows(x: np.ndarray) -> np.ndarray:
     return x / np.sqrt((x * x).sum(axis=1, keepdims=True))
 
@@ -593,8 +599,31 @@ def load_bank(path: str) -> dict:
     return b
 
 
+def _main_bank(a, transformers, model_type: str) -> None:
+    """--zero-shot-out: the bank of the checkpoint's text tower, from token ids or from prompts."""
+    both = (transformers.CLIPModel if model_type == "clip" else transformers.SiglipModel).from_pretrained(a.model).eval()
+    mask = None
+    if a.zero_shot_ids:
+        ids = np.load(a.zero_shot_ids)
+        mask_path = a.zero_shot_ids[:-4] + ".mask.npy" if a.zero_shot_ids.endswith(".npy") else a.zero_shot_ids + ".mask.npy"
+        if os.path.isfile(mask_path):
+            mask = np.load(mask_path)
+        labels = None
+    else:
+        with open(a.zero_shot_prompts) as f:
+            labels = [l.rstrip("\n") for l in f if l.strip()]
+        tok = transformers.AutoTokenizer.from_pretrained(a.model)(labels, padding="max_length", truncation=True, return_tensors="np")
+        ids = tok["input_ids"]
+        mask = tok.get("attention_mask") if model_type == "clip" else None        # SigLIP was trained without a mask
+    if a.zero_shot_labels:
+        with open(a.zero_shot_labels) as f:
+            labels = [l.rstrip("\n") for l in f if l.strip()]
+    embeds, kind, scale, bias = zeroshot_bank(both, ids, mask)
+    save_bank(a.zero_shot_out, embeds, kind, scale, bias, labels)
+    print(f"wrote {a.zero_shot_out}: {embeds.shape[0]} classes of width {embeds.shape[1]}, {'sigmoid' if kind == ZS_SIGMOID else 'softmax'}, scale {scale:.6g}, bias {bias:.6g}")
+
+
 def main(argv=None) -> int:
-    import argparse
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("model"); ap.add_argument("out"); ap.add_argument("--ftype", type=int, default=1, help="0 f32, 1 f16 (default), 2/3/6/7/8 q4_0/q4_1/q5_0/q5_1/q8_0")
     ap.add_argument("--vitstr", action="store_true", help="one-channel ViTSTR scene-text model: write the character set as labels")
@@ -634,79 +663,40 @@ def main(argv=None) -> int:
         ap.error("--zero-shot-ids / --zero-shot-prompts / --zero-shot-labels need --zero-shot-out BANK.npz")
     if a.zero_shot_out and a.timm_state_dict:
         ap.error("a zero-shot bank needs the text tower of a HuggingFace CLIPModel / SiglipModel, not a timm state dict")
-    pp_cli = dict(resize=a.pp_resize, crop=a.pp_crop, filt=a.pp_filter, mean=a.pp_mean, std=a.pp_std, crop_round=a.pp_crop_round)
-    if not a.timm_state_dict and any(pp_cli.values()):
+    if not a.timm_state_dict and any((a.pp_resize, a.pp_crop, a.pp_filter, a.pp_mean, a.pp_std, a.pp_crop_round)):
         ap.error("--pp-* describe a timm checkpoint (--timm-state-dict); a HuggingFace checkpoint brings its preprocessor_config.json")
-
-    def resized(hp):
-        """The converted file is written at the checkpoint's size first, then replaced by its --img-size version."""
-        if a.img_size and a.img_size != hp.img_size:
-            import os
-            from . import binding
-            tmp = a.out + f".src{os.getpid()}"
-            os.replace(a.out, tmp)
-            try:
-                binding.resize_file(tmp, a.out, a.img_size, binding.POS_BICUBIC_AA if a.pos_interp == "bicubic-aa" else binding.POS_BICUBIC)
-            finally:
-                os.remove(tmp)
-            hp.img_size = a.img_size
-        return hp
-
     if a.timm_state_dict:
-        import json
         import torch
         sd = torch.load(a.model, map_location="cpu", weights_only=True)
         labels = {int(k): str(v) for k, v in json.load(open(a.labels)).items()} if a.labels else None
-        hp = resized(convert_timm_state_dict(sd, a.out, a.ftype, heads=a.heads, id2label=labels, act=a.act, eps=a.eps, preproc=None if a.no_preproc else pp_cli))
-        print(f"wrote {a.out}: hidden {hp.hidden_size}, layers {hp.num_hidden_layers}, heads {hp.num_attention_heads}, classes {hp.num_classes}, patch {hp.patch_size}, img {hp.img_size}, ftype {a.ftype}")
-        return 0
-    import transformers
-    model_type = transformers.AutoConfig.from_pretrained(a.model).model_type
-    if a.zero_shot_out:
-        import os
-        if model_type not in ("clip", "siglip"):
-            ap.error(f"a zero-shot bank needs a CLIPModel or SiglipModel checkpoint (both towers), not model_type '{model_type}'")
-        both = (transformers.CLIPModel if model_type == "clip" else transformers.SiglipModel).from_pretrained(a.model).eval()
-        mask = None
-        if a.zero_shot_ids:
-            ids = np.load(a.zero_shot_ids)
-            mask_path = a.zero_shot_ids[:-4] + ".mask.npy" if a.zero_shot_ids.endswith(".npy") else a.zero_shot_ids + ".mask.npy"
-            if os.path.isfile(mask_path):
-                mask = np.load(mask_path)
-            labels = None
-        else:
-            with open(a.zero_shot_prompts) as f:
-                labels = [l.rstrip("\n") for l in f if l.strip()]
-            tok = transformers.AutoTokenizer.from_pretrained(a.model)(labels, padding="max_length", truncation=True, return_tensors="np")
-            ids = tok["input_ids"]
-            mask = tok.get("attention_mask") if model_type == "clip" else None        # SigLIP was trained without a mask
-        if a.zero_shot_labels:
-            with open(a.zero_shot_labels) as f:
-                labels = [l.rstrip("\n") for l in f if l.strip()]
-        embeds, kind, scale, bias = zeroshot_bank(both, ids, mask)
-        save_bank(a.zero_shot_out, embeds, kind, scale, bias, labels)
-        print(f"wrote {a.zero_shot_out}: {embeds.shape[0]} classes of width {embeds.shape[1]}, {'sigmoid' if kind == ZS_SIGMOID else 'softmax'}, scale {scale:.6g}, bias {bias:.6g}")
-        del both
-    if model_type in ("dinov2", "dinov2_with_registers"):
-        m = (transformers.AutoModel if a.no_head else transformers.AutoModelForImageClassification).from_pretrained(a.model).eval()
-    elif model_type in ("clip", "clip_vision_model"):
-        m = (transformers.CLIPVisionModel if a.no_head else transformers.CLIPVisionModelWithProjection).from_pretrained(a.model).eval()
-    elif model_type in ("siglip", "siglip_vision_model"):
-        m = transformers.SiglipVisionModel.from_pretrained(a.model).eval()
-        a.no_head = False                                      # a tower never has a classifier: the flag is accepted and not required
+        pp_cli = dict(resize=a.pp_resize, crop=a.pp_crop, filt=a.pp_filter, mean=a.pp_mean, std=a.pp_std, crop_round=a.pp_crop_round)
+        hp = convert_timm_state_dict(sd, a.out, a.ftype, heads=a.heads, id2label=labels, act=a.act, eps=a.eps, preproc=None if a.no_preproc else pp_cli)
     else:
-        m = transformers.ViTForImageClassification.from_pretrained(a.model).eval()
-    import json
-    import os
-    pc_path = os.path.join(a.model, "preprocessor_config.json")
-    pc = None
-    if not a.no_preproc and not a.vitstr:
-        if os.path.isfile(pc_path):
-            with open(pc_path) as f:
-                pc = json.load(f)
-        else:
-            print(f"note: no preprocessor_config.json beside '{a.model}': the file is written without a `preproc` tensor")
-    hp = resized(convert_hf_model(m, a.out, a.ftype, vitstr=a.vitstr, no_head=a.no_head, preprocessor_config=pc))
+        import transformers
+        model_type = transformers.AutoConfig.from_pretrained(a.model).model_type
+        if a.zero_shot_out:
+            if model_type not in _TWO_TOWERS:
+                ap.error(f"a zero-shot bank needs a CLIPModel or SiglipModel checkpoint (both towers), not model_type '{model_type}'")
+            _main_bank(a, transformers, model_type)
+        fam = FAMILIES.get(model_type, _VIT)
+        m = getattr(transformers, fam.loaders[1 if a.no_head and fam.head == "optional" else 0]).from_pretrained(a.model).eval()
+        pc, pc_path = None, os.path.join(a.model, "preprocessor_config.json")
+        if not a.no_preproc and not a.vitstr:
+            if os.path.isfile(pc_path):
+                with open(pc_path) as f:
+                    pc = json.load(f)
+            else:
+                print(f"note: no preprocessor_config.json beside '{a.model}': the file is written without a `preproc` tensor")
+        hp = convert_hf_model(m, a.out, a.ftype, vitstr=a.vitstr, no_head=a.no_head, preprocessor_config=pc)
+    if a.img_size and a.img_size != hp.img_size:           # written at the checkpoint's size first, then replaced by its --img-size version
+        from . import binding
+        tmp = a.out + f".src{os.getpid()}"
+        os.replace(a.out, tmp)
+        try:
+            binding.resize_file(tmp, a.out, a.img_size, binding.POS_BICUBIC_AA if a.pos_interp == "bicubic-aa" else binding.POS_BICUBIC)
+        finally:
+            os.remove(tmp)
+        hp.img_size = a.img_size
     print(f"wrote {a.out}: hidden {hp.hidden_size}, layers {hp.num_hidden_layers}, heads {hp.num_attention_heads}, classes {hp.num_classes}, patch {hp.patch_size}, img {hp.img_size}, ftype {a.ftype}")
     return 0
 

@@ -78,9 +78,15 @@ class ModelFile:
         return None
 
 
-# --------------------------------------------------------------------------- the `preproc` tensor
-PP_REF_BICUBIC, PP_REF_BILINEAR, PP_PIL_BILINEAR, PP_PIL_BICUBIC = 0, 1, 2, 3      # enum vitx_pp_filter
+# --------------------------------------------------------------------------- the enums of include/vitx.h a file or a bank carries: numbered here and
+# nowhere else in Python; convert.py and binding.py import them (binding.py under the header's longer ACT_* names)
+ACT_TANH, ACT_ERF, ACT_QUICK = 0, 1, 2                  # enum vitx_activation (slot 0 of `arch`): tanh-GELU, erf-GELU, QuickGELU
+ZS_SOFTMAX, ZS_SIGMOID = 0, 1                           # enum vitx_zs_kind: CLIP's softmax over the classes, SigLIP's sigmoid per class
+POOL_CLS, POOL_CLS_MEAN, POOL_MAP = 0, 1, 2             # enum vitx_head_pool: the head reads the class token, concat(cls, mean of the patches), or the pooled embedding
+PP_REF_BICUBIC, PP_REF_BILINEAR, PP_PIL_BILINEAR, PP_PIL_BICUBIC = 0, 1, 2, 3      # enum vitx_pp_filter: the reference's two, Pillow's Image.resize on u8
 PP_STRETCH, PP_SHORTEST_EDGE = 0, 1                                                # enum vitx_pp_resize
+
+# --------------------------------------------------------------------------- the `preproc` tensor
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 
 
