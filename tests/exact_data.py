@@ -549,7 +549,7 @@ def ln_bound(y64, w, rstd, xmax, ulp_out: float):
 
 
 def ln_tiled_f32(x: np.ndarray, w: np.ndarray, b: np.ndarray, eps: float = LN_EPS) -> np.ndarray:
-    """f32 emulation of the tiled two-pass LayerNorm definition (device_common.h): per 256-column tile a fixed tree for the sum and, around the
+    """f32 emulation of the tiled two-pass LayerNorm definition (ln_row.h): per 256-column tile a fixed tree for the sum and, around the
     tile's own mean, for the squared deviations; tiles merged in index order (equal counts).  Every operation rounds to f32."""
     f = np.float32
     x = np.asarray(x, f)

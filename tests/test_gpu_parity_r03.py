@@ -153,7 +153,7 @@ def _gemm_ln_case(binding, torch, dt, tdt, M, N, K, test, timeout_us=200, seed=0
 def test_gemm_ln_fused_vs_reference_and_standalone(binding, torch_gpu, M, N, K, dtype_name):
     """The fused residual GEMM + LayerNorm: X against float64 products (as every GEMM test), Y against a float64 LayerNorm of the X the
     kernel itself produced (within one output ulp), and BIT-IDENTICAL to the stand-alone kernel applied to that X (the same tiled
-    statistics: device_common.h).  1, 2, 3 and 4 column tiles; row-block counts that are not multiples of 8 (uneven XCD shares) and
+    statistics: ln_row.h).  1, 2, 3 and 4 column tiles; row-block counts that are not multiples of 8 (uneven XCD shares) and
     leave partial rounds; no tile may fall back on an otherwise idle GPU."""
     torch = torch_gpu
     dt = binding.F16 if dtype_name == "f16" else binding.BF16

@@ -4,7 +4,7 @@
 // The probe of the head is a constant of the model, so its K projection folds into one vector per head, u_h = Wk_h^T q_h / sqrt(d) (host, at
 // context creation), and -- because the softmax weights sum to 1 -- the V projection commutes with the weighted sum.  What is left per image is
 // one pass over the f32 residual stream:
-//     F[t]   = the final-norm row of token t (FeatRow: the arithmetic of features.hip, unrounded)
+//     F[t]   = the final-norm row of token t (LnRow::norm, ln_row.h: the row of features.hip, unrounded)
 //     s[h,t] = u_h . F[t];   p_h = softmax_t(s_h);   M_h = sum_t p[h,t] F[t]            -- all f32, M is [H][D]
 //
 // One workgroup of 4 waves per (image, head group): heads go in groups of HG, HG x D / 64 accumulators per lane within kPoolAcc registers, and the
@@ -22,7 +22,7 @@
 // An image's M is a function of its own rows, N, D and H only: nothing depends on the batch or on the position in it, and there are no atomics.
 // p (optional): the raw scores are parked in the output during the pass and turned into exp(s - m) / L by the workgroup once m and L are known.
 #include "device_common.h"
-#include "feat_row.h"
+#include "ln_row.h"
 #include "kernels.h"
 
 namespace vitx {
@@ -38,7 +38,7 @@ template <int VEC, int NV, typename T16>
 __global__ __launch_bounds__(kPoolWaves * 64) void attention_pool_kernel(const float *__restrict__ x, long row_stride, long img_stride, const float *__restrict__ w,
                                                                          const float *__restrict__ b, float eps, const float *__restrict__ u, float *__restrict__ M,
                                                                          T16 *__restrict__ m16, float *__restrict__ p, int N, int H) {
-    typedef FeatRow<VEC, NV> R;
+    typedef LnRow<VEC, NV> R;
     constexpr int D = 64 * VEC * NV, CPL = VEC * NV, HG = pool_group(CPL), W = kPoolWaves;
     constexpr int U = D <= 1024 ? 2 : 1;          // rows per step of a wave
     __shared__ __attribute__((aligned(16))) float blk[HG * D];      // u of the group during the pass, then the combined accumulators
@@ -195,7 +195,7 @@ __global__ __launch_bounds__(kPoolWaves * 64) void attention_pool_kernel(const f
 
 template <int VEC, int NV, typename T16>
 __global__ __launch_bounds__(64) void pool_embed_kernel(const float *__restrict__ e, T16 *__restrict__ z, float *__restrict__ cls, long out_img_stride, int l2) {
-    typedef FeatRow<VEC, NV> R;
+    typedef LnRow<VEC, NV> R;
     constexpr int D = 64 * VEC * NV;
     const int lane = threadIdx.x;
     const float *er = e + (size_t)blockIdx.x * D;
@@ -210,39 +210,36 @@ __global__ __launch_bounds__(64) void pool_embed_kernel(const float *__restrict_
     R::store(cls + (size_t)blockIdx.x * out_img_stride, lane, f);
 }
 
+template <typename T16>
+hipError_t launch_attention_pool_t(const float *x, long row_stride, long img_stride, const float *w, const float *b, float eps, const float *u, float *M, void *m16, float *p,
+                                   int n_img, int N, int D, int H, hipStream_t stream) {
+    const bool ok = ln_for_width(D, [&](auto vec, auto nv) {
+        constexpr int HG = pool_group(vec() * nv());
+        hipLaunchKernelGGL((attention_pool_kernel<vec(), nv(), T16>), dim3(n_img, (H + HG - 1) / HG), dim3(kPoolWaves * 64), 0, stream, x, row_stride, img_stride, w, b, eps, u, M,
+                           (T16 *)m16, p, N, H);
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+template <typename T16>
+hipError_t launch_pool_embed_t(const float *e, void *z, float *cls, long out_img_stride, bool l2, int n_img, int D, hipStream_t stream) {
+    const bool ok = ln_for_width(D, [&](auto vec, auto nv) {
+        hipLaunchKernelGGL((pool_embed_kernel<vec(), nv(), T16>), dim3(n_img), dim3(64), 0, stream, e, (T16 *)z, cls, out_img_stride, l2 ? 1 : 0);
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
+}
+
 }  // namespace
 
 hipError_t launch_attention_pool(const float *x, long row_stride, long img_stride, const float *w, const float *b, float eps, const float *u, float *M, void *m16, int dtype,
                                  float *p, int n_img, int N, int D, int H, hipStream_t stream) {
     if (n_img <= 0 || N <= 0 || H <= 0 || H > kPoolMaxHeads || (!M && !m16)) return hipErrorInvalidValue;
-    const dim3 blk(kPoolWaves * 64);
-#define VITX_POOL_CASE(DD, VEC, NV)                                                                                                                             \
-    case DD:                                                                                                                                                    \
-        if (dtype == DT_F16) hipLaunchKernelGGL((attention_pool_kernel<VEC, NV, _Float16>), dim3(n_img, (H + pool_group(VEC * NV) - 1) / pool_group(VEC * NV)), blk, 0, stream, x, row_stride, img_stride, w, b, eps, u, M, (_Float16 *)m16, p, N, H); \
-        else hipLaunchKernelGGL((attention_pool_kernel<VEC, NV, __bf16>), dim3(n_img, (H + pool_group(VEC * NV) - 1) / pool_group(VEC * NV)), blk, 0, stream, x, row_stride, img_stride, w, b, eps, u, M, (__bf16 *)m16, p, N, H);                  \
-        break;
-    switch (D) {
-        VITX_LN_WIDTHS(VITX_POOL_CASE)
-    default: return hipErrorInvalidValue;
-    }
-#undef VITX_POOL_CASE
-    return hipGetLastError();
+    return VITX_BY_DTYPE(dtype, launch_attention_pool_t, x, row_stride, img_stride, w, b, eps, u, M, m16, p, n_img, N, D, H, stream);
 }
 
 hipError_t launch_pool_embed(const float *e, void *z, int dtype, float *cls, long out_img_stride, bool l2, int n_img, int D, hipStream_t stream) {
     if (n_img <= 0 || (!z && !cls)) return hipErrorInvalidValue;
-    const dim3 grid(n_img), blk(64);
-#define VITX_POOL_CASE(DD, VEC, NV)                                                                                                                 \
-    case DD:                                                                                                                                        \
-        if (dtype == DT_F16) hipLaunchKernelGGL((pool_embed_kernel<VEC, NV, _Float16>), grid, blk, 0, stream, e, (_Float16 *)z, cls, out_img_stride, l2 ? 1 : 0); \
-        else hipLaunchKernelGGL((pool_embed_kernel<VEC, NV, __bf16>), grid, blk, 0, stream, e, (__bf16 *)z, cls, out_img_stride, l2 ? 1 : 0);                  \
-        break;
-    switch (D) {
-        VITX_LN_WIDTHS(VITX_POOL_CASE)
-    default: return hipErrorInvalidValue;
-    }
-#undef VITX_POOL_CASE
-    return hipGetLastError();
+    return VITX_BY_DTYPE(dtype, launch_pool_embed_t, e, z, cls, out_img_stride, l2, n_img, D, stream);
 }
 
 }  // namespace vitx

@@ -1,8 +1,8 @@
 // features.hip -- image embeddings and token features (vitx_feat_enable, vitx_op_features; the contract: include/vitx.h).
 //
-// F = ((X - mean) * rstd) * norm.weight + norm.bias of the f32 residual stream X, per row, in f32: the arithmetic of ln_row_tiled /
-// layernorm_kernel (device_common.h, layernorm.hip) operation for operation on the shared statistics helpers, WITHOUT the final rounding to
-// the operand type -- so F rounded to nearest even IS what those kernels store (-ffp-contract=off, as for every kernel of the library).
+// F = ((X - mean) * rstd) * norm.weight + norm.bias of the f32 residual stream X, per row, in f32: LnRow::norm (ln_row.h), the row
+// layernorm_kernel (layernorm.hip) rounds to the operand type, WITHOUT that rounding -- so F rounded to nearest even IS what that kernel
+// stores (-ffp-contract=off, as for every kernel of the library).
 //
 // One workgroup per image, W waves (feat_waves; one wave when only the class row is asked for), one pass over the image's rows, every row read once:
 //   * wave W - 1 takes the class row (row 0) first, when the class embedding is asked for;
@@ -16,7 +16,7 @@
 // Column ownership follows the statistics helpers: lane l holds columns c * 256 + 4 l .. + 3 of tile c (tiled widths: 16-byte loads and
 // stores, 1 KiB contiguous per wave instruction) or (i * 64 + l) * VEC .. of piece i (flat widths, VEC of the instantiation table).
 #include "device_common.h"
-#include "feat_row.h"
+#include "ln_row.h"
 #include "kernels.h"
 
 namespace vitx {
@@ -31,7 +31,7 @@ template <int VEC, int NV>
 __global__ __launch_bounds__(feat_waves(64 * VEC * NV) * 64) void features_kernel(const float *__restrict__ x, long row_stride, long img_stride, const float *__restrict__ w,
                                                                    const float *__restrict__ b, float *__restrict__ cls, float *__restrict__ mean, float *__restrict__ tokens,
                                                                    long out_img_stride, int N, float eps, int l2, int first, void *__restrict__ z, int z_bf16) {
-    typedef FeatRow<VEC, NV> R;
+    typedef LnRow<VEC, NV> R;
     constexpr int D = 64 * VEC * NV;
     constexpr int U = D <= 1024 ? 2 : 1;          // patch rows per step of a wave
     __shared__ float pool[D];
@@ -108,14 +108,10 @@ hipError_t launch_features(const float *x, long row_stride, long img_stride, con
     if (first < 0 || first > N || (first == 0 && (cls || z))) return hipErrorInvalidValue;     // first = 0: a model without prefix tokens has no class row
     const bool rows = mean || tokens || z;
     const dim3 grid(n_img), blk(64 * (rows ? feat_waves(D) : 1));
-#define VITX_FEAT_CASE(DD, VEC, NV) \
-    case DD: hipLaunchKernelGGL((features_kernel<VEC, NV>), grid, blk, 0, stream, x, row_stride, img_stride, w, b, cls, mean, tokens, out_img_stride, N, eps, l2 ? 1 : 0, first, z, dtype == DT_BF16 ? 1 : 0); break;
-    switch (D) {
-        VITX_LN_WIDTHS(VITX_FEAT_CASE)
-    default: return hipErrorInvalidValue;
-    }
-#undef VITX_FEAT_CASE
-    return hipGetLastError();
+    const bool ok = ln_for_width(D, [&](auto vec, auto nv) {
+        hipLaunchKernelGGL((features_kernel<vec(), nv()>), grid, blk, 0, stream, x, row_stride, img_stride, w, b, cls, mean, tokens, out_img_stride, N, eps, l2 ? 1 : 0, first, z, dtype == DT_BF16 ? 1 : 0);
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace vitx

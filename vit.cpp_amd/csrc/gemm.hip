@@ -5,6 +5,7 @@
 #include "kernels.h"
 #include "epilogue16.h"
 #include "device_common.h"
+#include "ln_row.h"      // LN_MAX_TILES: the widths the LayerNorm-fusing GEMM takes
 
 namespace vitx {
 

@@ -19,6 +19,7 @@
 #include "device_common.h"
 #include "epilogue16.h"
 #include "kernels.h"
+#include "ln_row.h"
 #include "mxfp8.h"
 
 namespace vitx {
@@ -160,11 +161,12 @@ __global__ __launch_bounds__(256, 2) void gemm_mx8_kernel(GemmArgs g, const uint
     }
 }
 
-// One wave per row: the f32 value the bf16 LayerNorm rounds (statistics from device_common.h, the same output arithmetic), encoded.
+// One wave per row: the f32 row the bf16 LayerNorm rounds (LnRow, ln_row.h), encoded.
 // A 32-column block is 32 / VEC consecutive lanes.  Columns D .. k_pad are written as zero elements with scale 127.
 template <int VEC, int NV>
 __global__ __launch_bounds__(256) void layernorm_mx8_kernel(const float *__restrict__ x, long ldx, const float *__restrict__ w, const float *__restrict__ b,
                                                             uint8_t *__restrict__ q, uint8_t *__restrict__ s, int k_pad, int M, float eps) {
+    typedef LnRow<VEC, NV> R;
     constexpr int D = 64 * VEC * NV;
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -185,32 +187,7 @@ __global__ __launch_bounds__(256) void layernorm_mx8_kernel(const float *__restr
         }
         if ((idx & 31) == 0) sr[idx / 32] = (uint8_t)(e + 127);
     };
-    if constexpr (VEC == 4 && NV <= LN_MAX_TILES) {          // hidden 256 .. 1024: the tiled statistics (ln_row_tiled's)
-        f32x4 v[NV];
-        float mean, rstd;
-        ln_tiled_stats<NV>(xr, eps, lane, v, mean, rstd);
-#pragma unroll
-        for (int c = 0; c < NV; ++c) {
-            const int idx = c * 256 + lane * 4;
-            const f32x4 ww = *(const f32x4 *)(w + idx), bb = *(const f32x4 *)(b + idx);
-            float o[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { float t = (v[c][e] - mean) * rstd; t = t * ww[e]; o[e] = t + bb[e]; }
-            store(idx, o);
-        }
-    } else {                                                 // every other width: the flat statistics (layernorm_kernel's)
-        float v[NV][VEC];
-        float scale;
-        ln_flat_stats<VEC, NV>(xr, eps, lane, v, scale);
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int idx = (i * 64 + lane) * VEC;
-            float o[VEC];
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) { float t = v[i][j] * scale; t = t * w[idx + j]; o[j] = t + b[idx + j]; }
-            store(idx, o);
-        }
-    }
+    R::each(xr, w, b, eps, lane, [&](int, int idx, const float (&o)[VEC]) { store(idx, o); });
     for (int k = D + lane * 4; k < k_pad; k += 256) *(uint32_t *)(qr + k) = 0u;
     for (int k = D / 32 + lane; k < k_pad / 32; k += 64) sr[k] = 127;
 }
@@ -251,14 +228,10 @@ hipError_t launch_gemm_mx8(int epi, const GemmArgs &a, const uint8_t *a_scales, 
 hipError_t launch_layernorm_mx8(const float *x, long ldx, const float *w, const float *b, uint8_t *q, uint8_t *s, int k_pad, int M, int D, float eps, hipStream_t stream) {
     if (D % 32 || k_pad < D || k_pad % MX_BK || M <= 0) return hipErrorInvalidValue;
     const dim3 grid((M + 3) / 4), blk(256);
-#define VITX_LNMX_CASE(DD, VEC, NV) \
-    case DD: hipLaunchKernelGGL((layernorm_mx8_kernel<VEC, NV>), grid, blk, 0, stream, x, ldx, w, b, q, s, k_pad, M, eps); break;
-    switch (D) {     // the instantiation table of launch_layernorm (kernels.h)
-        VITX_LN_WIDTHS(VITX_LNMX_CASE)
-    default: return hipErrorInvalidValue;
-    }
-#undef VITX_LNMX_CASE
-    return hipGetLastError();
+    const bool ok = ln_for_width(D, [&](auto vec, auto nv) {
+        hipLaunchKernelGGL((layernorm_mx8_kernel<vec(), nv()>), grid, blk, 0, stream, x, ldx, w, b, q, s, k_pad, M, eps);
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_quantize_mx8(const float *x, int rows, int K, int k_pad, uint8_t *q, uint8_t *s, hipStream_t stream) {

@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "device_common.h"
+#include "ln_row.h"
 #include "kernels.h"
 #include "epilogue16.h"
 
@@ -86,7 +87,7 @@ __device__ __forceinline__ void pp_barrier() { asm volatile("s_barrier" ::: "mem
 template <int EPI> __host__ __device__ constexpr int pp_epi_stores() { return (EPI == EPI_BIAS || epi_is_act(EPI)) ? 16 : 32; }      // (EPI_BIAS_HILO: two 16-bit planes = 32)
 
 // ---- EPI_BIAS_RESID + LayerNorm of the finished rows (GemmLn, kernels.h), for one full 256 x 256 tile of the persistent kernel.
-// Statistics follow device_common.h "LayerNorm statistics by 256-column tiles": this workgroup's tile is tile c = n0 / 256 of its rows;
+// Statistics follow ln_row.h "LayerNorm statistics by 256-column tiles": this workgroup's tile is tile c = n0 / 256 of its rows;
 // wave column w = the 64-column chunk, accumulator half j and 16-byte piece k = lane & 7 of the staged row layout name the pieces.
 //   passes   the staged f32 epilogue (bias, + residual; 16 passes of 16 rows x 32 columns) into row layout; the final values stay in the
 //            accumulator registers and are stored as whole lines at the very end

@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/vitx.h"
 
 namespace vitx {
@@ -77,7 +79,7 @@ inline GemmArgs dense_gemm(const void *A, const void *W, const float *bias, void
 // All M (padded) rows are computed and stored: the buffers are padded to the row tile, pad rows stay finite and are never read
 // for real rows.  A peer that does not answer within `timeout` (two such GEMMs on two streams can each hold CUs the other's
 // workgroups wait for) makes the workgroup skip its tile and set todo[row block] = epoch; launch_layernorm_fixup() then
-// normalises exactly those row blocks from X with the stand-alone arithmetic -- the same bits (device_common.h "LayerNorm statistics").
+// normalises exactly those row blocks from X with the stand-alone arithmetic -- the same bits (ln_row.h "LayerNorm statistics").
 struct GemmLn {
     const float *w, *b;           // [N]
     const float *x;               // consumer-side fix only (GemmArgs::fix): the f32 rows [M][N] the statistics are recomputed from
@@ -215,11 +217,20 @@ hipError_t launch_pos_resample(const float *pos, int gy_in, int gx_in, int D, in
 bool attention_supports(int N, int D, int H);     // any token count; head_dim 64 (tuned kernels) or any other multiple of 8 up to 128 (generic kernel)
 bool attention_single_pass_supports(int N);       // instantiation table of the register-resident kernel
 bool layernorm_supports(int D);
-// The LayerNorm instantiation table (hidden size D, columns per lane VEC, pieces NV; D = 64 VEC NV), ONE list for layernorm_supports, launch_layernorm
-// and launch_layernorm_mx8: widths of the timm ViTs (SO400M 1152, ViT-g 1408, ViT-G 1664, ...) and of small test models
+// The LayerNorm instantiation table (hidden size D, columns per lane VEC, pieces NV; D = 64 VEC NV: LnRow<VEC, NV> of ln_row.h), ONE list for every
+// kernel that normalises a row: widths of the timm ViTs (SO400M 1152, ViT-g 1408, ViT-G 1664, ...) and of small test models
 #define VITX_LN_WIDTHS(X)                                                                                                  \
     X(64, 1, 1) X(128, 2, 1) X(192, 1, 3) X(256, 4, 1) X(384, 2, 3) X(512, 4, 2) X(768, 4, 3) X(1024, 4, 4) X(1280, 4, 5) X(1536, 4, 6) \
     X(320, 1, 5) X(448, 1, 7) X(576, 1, 9) X(640, 2, 5) X(896, 2, 7) X(1152, 2, 9) X(1408, 2, 11) X(1664, 2, 13) X(2048, 4, 8)
+// The table's one dispatcher: f(integral_constant<int, VEC>, integral_constant<int, NV>) for D's row; false, and f not called, if D has none
+template <typename F> bool ln_for_width(int D, F &&f) {
+    switch (D) {
+#define VITX_LN_CASE(DD, VEC, NV) case DD: f(std::integral_constant<int, VEC>{}, std::integral_constant<int, NV>{}); return true;
+        VITX_LN_WIDTHS(VITX_LN_CASE)
+#undef VITX_LN_CASE
+    default: return false;
+    }
+}
 // class softmax with the reference's fp16 (or bf16) exp rounding (softmax_topk.hip; vit.cpp:931)
 hipError_t launch_softmax(int dtype, const float *logits, float *probs, int rows, int cols, int ld, hipStream_t stream);
 // u8 HWC [n][ny][nx][3] -> f32 HWC [n][S][S][3], resized and normalised (image_preprocess.hip; bit for bit the host version in preprocess.cpp)

@@ -15,7 +15,7 @@ namespace {
 
 // One wave per row, four rows per workgroup.  Lane l owns the 16-byte pieces l, l + 64, ... of the row: the sum of squares is taken per lane in
 // ascending column order, then over the lanes by a butterfly (the same bits in every lane) -- an order that depends on E only.  The rule is
-// VITX_FEAT_L2's (FeatRow::l2, feat_row.h); that one walks the LayerNorm tables' column ownership and exists only for their widths, this one
+// VITX_FEAT_L2's (LnRow::l2, ln_row.h); that one walks the LayerNorm tables' column ownership and exists only for their widths, this one
 // takes any E that is a multiple of 64 (a CLIP projection width need not be a hidden size), so the two stay separate functions.
 template <typename T16>
 __global__ __launch_bounds__(256) void zs_embed_kernel(const float *__restrict__ z, long z_stride, T16 *__restrict__ a, int n, int m_pad, int E) {
