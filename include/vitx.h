@@ -728,6 +728,70 @@ int vitx_zeroshot_max_classes(int E);                /* the bound on K for width
 int vitx_op_zeroshot(int dtype, const void *d_z, long z_stride, const void *d_bank /* dtype, [K_pad][E], zero rows beyond K */,
                      void *d_a_scratch, void *d_acc_scratch, void *d_probs, void *d_logits, int n, int K, int E, int kind, float scale, float bias, void *stream);
 
+/* ---- the text tower (CLIP, SigLIP): token ids in, text embeddings out ---------------
+ * The text half of a contrastive checkpoint is a second model file in the same container.  Header: hidden_size D, num_hidden_layers L,
+ * num_attention_heads H, num_classes = E (the width of the projected embedding), patch_size = 0 (THE mark of a text file: no image file
+ * has it), img_size = T (context length = rows of the position table).  Tensors: token_embed.weight [V][D] (f16 for ftype >= 1, f32 for
+ * ftype 0; never block-quantised), pos_embed [T][D] f32, blocks.{i}.* exactly as in an image file, norm.weight / norm.bias (the tower's
+ * final LayerNorm), head.weight [E][D] + head.bias [E] (CLIP: text_projection with a zero bias; SigLIP: head), and -- always present in
+ * a text file --
+ *     arch f32 [4] = {activation, eps, causal, eos + 1}
+ * causal: 1 = row t attends keys 0 .. t (CLIP), 0 = no mask (SigLIP).  Slot 3: 0 = pool the last position (SigLIP); otherwise the
+ * EOS token id plus one: pool the FIRST position whose id is EOS (CLIP).  Optional zs f32 [4] = {kind, scale, bias, 0}: the
+ * checkpoint's enum vitx_zs_kind, exp(logit_scale) and logit_bias, so that a bank made from this file carries its scoring constants.
+ * Loader errors (VITX_ERR_FORMAT): a wrong shape, a missing tensor, eos >= V, causal or kind outside its enum.
+ *
+ * There is no tokenizer and no attention mask in the engine: ids in, embeddings out.  Under CLIP's causal mask nothing behind the pooled
+ * (EOS) row reaches it, so the pad ids after EOS do not matter; SigLIP is trained and served without a mask on padded rows.
+ *
+ * A text model takes no image context, group or resize (VITX_ERR_ARG before any device call), an image model no text context.
+ *
+ * vitx_text_create: dtype VITX_F16 or VITX_BF16 (VITX_MXFP8: VITX_ERR_UNSUPPORTED).  VITX_F16 here is PLAIN fp16 operands with the
+ * ordinary attention: the hi / lo parity planes of an image context exist to match ggml's f32 q, k, v, and ggml has no text tower to
+ * match.  T > 128, a head dim that is not a multiple of 8 up to 128, or a D outside the LayerNorm widths: VITX_ERR_UNSUPPORTED at
+ * creation.  Weights upload once per (model, device, dtype) and are shared by the text contexts of a model; block-quantised matrices
+ * are expanded once at upload.  One stream, no sub-batches, no graph cache, no LayerNorm fusion.
+ *
+ * vitx_text_embed: ids host int32 [n][T]; out host f32 [n][E]; flags 0 or VITX_TEXT_L2 (e / sqrt(sum e^2), f32).  VITX_ERR_ARG, checked
+ * on the host before any device call: an id < 0 or >= V, a row without the EOS id (files with eos), n outside 1 .. max_prompts.
+ * vitx_text_embed_device: the same with d_out on the device; ids stay a HOST pointer (they are checked, and the pooled positions are
+ * computed, on the host, then copied: the caller's array is free when the call returns); only enqueues on `stream`, after waiting for the
+ * previous call's upload of ids -- not for its forward -- to leave the context's staging buffer.
+ * Forward: X = f32(tok[id]) + pos; per layer LayerNorm, qkv, attention (attention_text.hip), proj + residual, LayerNorm, fc1 with the
+ * file's activation, fc2 + residual; the pooled row through the final LayerNorm; the head GEMM in f32.
+ * Determinism: a prompt's embedding is a function of its own ids only -- the same bits at any n and any position in the batch.  The
+ * GEMM dispatcher picks a kernel family by row count, so a text context PINS the family of each of its GEMMs at creation, from
+ * max_prompts * T rows, to one of the two ring tilings (128 x 256, or 64 x 128 for few rows); the wide persistent kernels are not
+ * used.  This is the "one kernel per token count" rule of the attention dispatcher.  The guarantee holds within a context: contexts
+ * created with different max_prompts may pin different tilings. */
+#define VITX_KIND_IMAGE 0
+#define VITX_KIND_TEXT 1
+#define VITX_TEXT_L2 1
+#define VITX_TEXT_MAX_TOKENS 128
+typedef struct vitx_text vitx_text;
+int vitx_model_kind(const vitx_model *m);            /* VITX_KIND_IMAGE / VITX_KIND_TEXT (0 for NULL) */
+/* V, T, causal (0 / 1), eos (the token id, or -1: pool the last position); any out pointer may be NULL.  VITX_ERR_ARG for an image model. */
+int vitx_model_text_info(const vitx_model *m, int *V, int *T, int *causal, int *eos);
+/* kind, scale, bias of the file's `zs` tensor; returns 1 when the file has one, 0 (outputs untouched) otherwise */
+int vitx_model_text_zs(const vitx_model *m, int *kind, float *scale, float *bias);
+int vitx_text_create(const vitx_model *m, int device, int max_prompts, int dtype, vitx_text **out);
+void vitx_text_free(vitx_text *t);
+int vitx_text_embed(vitx_text *t, const int32_t *ids /* host [n][T] */, int n, int flags /* 0 | VITX_TEXT_L2 */, float *out /* host [n][E] */);
+int vitx_text_embed_device(vitx_text *t, const int32_t *ids /* host [n][T] */, int n, int flags, void *d_out /* [n][E] f32 */, void *stream);
+/* Host only, no device call: the id checks of vitx_text_embed on ids [n][T] of text model m (VITX_ERR_ARG: an id < 0 or >= V, a row without the
+ * EOS id in a file with eos) and, pooled != NULL, the position each prompt is pooled at. */
+int vitx_text_check_ids(const vitx_model *m, const int32_t *ids, int n, int32_t *pooled /* [n] or NULL */);
+int vitx_text_shares_weights(const vitx_text *t);    /* 1 when this context found its model's weights already on the device */
+/* The three text kernels on the caller's device buffers (only enqueue).  text_embed: d_tok [V][D] f16 (table_f16 != 0) or f32, d_pos [T][D] f32,
+ * d_ids int32 [n][T] (NOT checked: the caller guarantees 0 <= id < V), d_x f32 [n * T][D]; D a multiple of 8.  text_pool: d_z [n][D] (dtype) =
+ * the rounded LayerNorm of row i * T + d_pooled[i] of d_x -- vitx_op_layernorm's bits for that row.  attention_text: d_qkv [n * T][3 D] ->
+ * d_out [n * T][D]; 1 <= T <= 128, head dim a multiple of 8 up to 128 (else VITX_ERR_UNSUPPORTED); causal != 0: row t is attention over keys 0 .. t. */
+int vitx_op_text_embed(int table_f16, const void *d_tok, const void *d_pos, const void *d_ids, void *d_x, int n, int T, int D, void *stream);
+int vitx_op_text_pool(int dtype, const void *d_x, const void *d_pooled, const void *d_w, const void *d_b, void *d_z, int n, int T, int D, float eps, void *stream);
+int vitx_op_attention_text(int dtype, const void *d_qkv, void *d_out, int n, int T, int D, int H, int causal, void *stream);
+/* attention_generic.hip at any head dim it takes, 64 included (vitx_op_attention prefers the tuned families there): the yardstick of tools/text_cost.py */
+int vitx_op_attention_generic(int dtype, const void *d_qkv, void *d_out, int n_img, int N, int D, int H, void *stream);
+
 /* ---- MXFP8 operands (VITX_MXFP8, encoding above) ------------------------------- */
 /* Host encoder: x f32 [rows][K] -> q [rows][k_pad] e4m3 bytes + scales [rows][k_pad / 32] (k_pad >= K, a multiple of 32; columns
  * K .. k_pad are zero elements, whole padding blocks get scale 127).  VITX_ERR_ARG on NULL or a bad size. */

@@ -32,6 +32,8 @@ GEMM_AUTO, GEMM_PP, GEMM_AUTO_SPLIT = 0, 1, 2          # vitx_op_gemm_ex `kernel
 ATTN_AUTO, ATTN_SINGLE, ATTN_FLOW, ATTN_PERSIST, ATTN_STREAM = 0, 1, 3, 4, 5   # vitx_op_attention_ex `kernel`
 ATTN_ROLLOUT = 1                # vitx_attn_enable flag
 FEAT_CLS, FEAT_MEAN, FEAT_TOKENS, FEAT_L2 = 1, 2, 4, 8      # vitx_feat_enable flags
+KIND_IMAGE, KIND_TEXT = 0, 1            # vitx_model_kind
+TEXT_L2 = 1                             # vitx_text_embed flag
 POS_BICUBIC, POS_BICUBIC_AA = 0, 1      # vitx_pos_interp: F.interpolate(mode="bicubic") without / with antialias=True (include/vitx.h)
 
 EXPORTS = [
@@ -51,6 +53,8 @@ EXPORTS = [
     "vitx_model_preproc", "vitx_model_has_preproc", "vitx_preproc_at_size", "vitx_preprocess_ex", "vitx_preprocess_ex_device", "vitx_preprocess_ex_device_supports",
     "vitx_model_num_prefix", "vitx_model_pool_query", "vitx_op_attention_pool",
     "vitx_zeroshot_set", "vitx_zeroshot_classes", "vitx_zeroshot_images", "vitx_zeroshot_read", "vitx_zeroshot_device", "vitx_zeroshot_max_classes", "vitx_op_zeroshot",
+    "vitx_model_kind", "vitx_model_text_info", "vitx_model_text_zs", "vitx_text_create", "vitx_text_free", "vitx_text_embed", "vitx_text_embed_device", "vitx_text_shares_weights", "vitx_text_check_ids",
+    "vitx_op_text_embed", "vitx_op_text_pool", "vitx_op_attention_text", "vitx_op_attention_generic",
 ]
 
 
@@ -222,6 +226,21 @@ def lib():
             L.vitx_zeroshot_read.argtypes = [vp, fp, fp, C.c_size_t]
             L.vitx_zeroshot_device.restype = C.c_void_p; L.vitx_zeroshot_device.argtypes = [vp]
             L.vitx_op_zeroshot.argtypes = [ip, vp, C.c_long, vp, vp, vp, vp, vp, ip, ip, ip, ip, C.c_float, C.c_float, vp]
+        if hasattr(L, "vitx_text_create"):
+            i32p = C.POINTER(C.c_int32)
+            L.vitx_model_kind.argtypes = [vp]
+            L.vitx_model_text_info.argtypes = [vp, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]
+            L.vitx_model_text_zs.argtypes = [vp, C.POINTER(ip), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+            L.vitx_text_create.argtypes = [vp, ip, ip, ip, C.POINTER(vp)]
+            L.vitx_text_free.argtypes = [vp]
+            L.vitx_text_embed.argtypes = [vp, i32p, ip, ip, C.POINTER(C.c_float)]
+            L.vitx_text_embed_device.argtypes = [vp, i32p, ip, ip, vp, vp]
+            L.vitx_text_shares_weights.argtypes = [vp]
+            L.vitx_text_check_ids.argtypes = [vp, i32p, ip, i32p]
+            L.vitx_op_text_embed.argtypes = [ip, vp, vp, vp, vp, ip, ip, ip, vp]
+            L.vitx_op_text_pool.argtypes = [ip, vp, vp, vp, vp, vp, ip, ip, ip, C.c_float, vp]
+            L.vitx_op_attention_text.argtypes = [ip, vp, vp, ip, ip, ip, ip, ip, vp]
+            L.vitx_op_attention_generic.argtypes = [ip, vp, vp, ip, ip, ip, ip, vp]
         _lib = L
     return _lib
 
@@ -253,6 +272,22 @@ class Model:
             self.close()
         except Exception:       # interpreter shutdown: module globals may already be gone
             pass
+
+    @property
+    def kind(self) -> int: return lib().vitx_model_kind(self._h)                    # KIND_IMAGE, or KIND_TEXT for a text-tower file (patch_size 0)
+
+    @property
+    def text_info(self) -> dict:
+        """{"vocab", "tokens", "causal", "eos"} of a text-tower file (eos -1: the last position is pooled); VitxError for an image file."""
+        v = [C.c_int() for _ in range(4)]
+        check(lib().vitx_model_text_info(self._h, *[C.byref(x) for x in v]), "vitx_model_text_info")
+        return dict(vocab=v[0].value, tokens=v[1].value, causal=v[2].value, eos=v[3].value)
+
+    @property
+    def text_zs(self):
+        """(kind, scale, bias) of a text-tower file's `zs` tensor, or None."""
+        k, s, b = C.c_int(), C.c_float(), C.c_float()
+        return (k.value, s.value, b.value) if lib().vitx_model_text_zs(self._h, C.byref(k), C.byref(s), C.byref(b)) else None
 
     @property
     def in_channels(self) -> int: return lib().vitx_model_in_channels(self._h)      # 3, or 1 for a ViTSTR file
@@ -680,6 +715,89 @@ class Context:
         return [dict(name=arr[i].name.decode(), launches=arr[i].launches, total_ms=arr[i].total_ms, flops=arr[i].flops, bytes=arr[i].bytes, busy_ms=arr[i].busy_ms) for i in range(n.value)]
 
 
+class TextContext:
+    """A text tower on one GPU (include/vitx.h "the text tower"): token ids [n][T] in, projected embeddings [n][E] out.  No tokenizer, no mask."""
+
+    def __init__(self, model: Model, max_prompts: int = 1, dtype: int = F16, device: int = 0):
+        self._h = C.c_void_p()
+        self.model = model
+        check(lib().vitx_text_create(model._h, device, max_prompts, dtype, C.byref(self._h)), "vitx_text_create")
+        self.max_prompts = max_prompts
+        self.tokens = model.hparams.img_size
+        self.width = model.hparams.num_classes
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h:
+            lib().vitx_text_free(self._h); self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ids(self, ids) -> np.ndarray:
+        a = np.asarray(ids)
+        if a.ndim != 2 or a.shape[1] != self.tokens or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"ids must be integers [prompts][{self.tokens}], got {a.dtype} {a.shape}")
+        if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+            raise ValueError("ids do not fit int32")
+        return np.ascontiguousarray(a, np.int32)
+
+    def embed(self, ids, l2: bool = False) -> np.ndarray:
+        """[n][E] f32; l2: every row divided by its norm (VITX_TEXT_L2).  More than max_prompts rows run as several calls: a prompt's bits do not
+        depend on its batch."""
+        a = self._ids(ids)
+        out = np.empty((a.shape[0], self.width), np.float32)
+        for i in range(0, a.shape[0], self.max_prompts):
+            part = a[i:i + self.max_prompts]
+            check(lib().vitx_text_embed(self._h, part.ctypes.data_as(C.POINTER(C.c_int32)), part.shape[0], TEXT_L2 if l2 else 0,
+                                        out[i:].ctypes.data_as(C.POINTER(C.c_float))), "vitx_text_embed")
+        return out
+
+    def embed_device(self, ids, d_out: int, l2: bool = False, stream: int = 0) -> None:
+        a = self._ids(ids)
+        check(lib().vitx_text_embed_device(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), a.shape[0], TEXT_L2 if l2 else 0, d_out, stream), "vitx_text_embed_device")
+
+    @property
+    def shares_weights(self) -> bool:
+        return bool(lib().vitx_text_shares_weights(self._h))
+
+
+def text_check_ids(model: Model, ids) -> np.ndarray:
+    """The id checks of vitx_text_embed on the host (no device): the pooled position of every prompt, or VitxError (ERR_ARG) for an id outside the
+    vocabulary or a prompt without the EOS id."""
+    a = np.ascontiguousarray(ids, np.int32)
+    pooled = np.empty(a.shape[0], np.int32)
+    i32p = C.POINTER(C.c_int32)
+    check(lib().vitx_text_check_ids(model._h, a.ctypes.data_as(i32p), a.shape[0], pooled.ctypes.data_as(i32p)), "vitx_text_check_ids")
+    return pooled
+
+
+def text_bank(text_ctx: "TextContext", ids, groups=None, embeds=None):
+    """The zero-shot bank of the prompts `ids` [P][T] made by the engine: (embeds [K][E] float64, kind, scale, bias) -- what convert.save_bank and
+    Context.zeroshot_set take.  The prompt-ensembling rule is convert.zeroshot_bank's, float64 past the tower: every embedding is normalised;
+    with groups [P] of class ids 0 .. K-1 the normalised rows of a class are averaged and the mean is normalised again.  kind, scale and bias
+    are the text file's `zs` tensor; a file without one (a tower converted alone) gives (ZS_SOFTMAX, 1.0, 0.0).  embeds: text_ctx.embed(ids) where
+    the caller already has it (the tower is then not run again)."""
+    e = (text_ctx.embed(ids) if embeds is None else np.asarray(embeds)).astype(np.float64)
+    l2 = lambda x: x / np.sqrt((x * x).sum(axis=1, keepdims=True))
+    e = l2(e)
+    if groups is not None:
+        g = np.asarray(groups, dtype=np.int64)
+        if g.shape != (e.shape[0],) or g.min() < 0:
+            raise ValueError("text_bank: groups must give one class id >= 0 per prompt")
+        K = int(g.max()) + 1
+        counts = np.bincount(g, minlength=K)
+        if (counts == 0).any():
+            raise ValueError(f"text_bank: class {int(np.flatnonzero(counts == 0)[0])} has no prompt")
+        mean = np.zeros((K, e.shape[1]), np.float64)
+        np.add.at(mean, g, e)
+        e = l2(mean / counts[:, None])
+    kind, scale, bias = text_ctx.model.text_zs or (0, 1.0, 0.0)
+    return e, kind, scale, bias
+
+
 class Group:
     """Several GPUs in one process: batch shards + one RCCL all-gather of the probabilities (vitx_group_*)."""
 
@@ -760,6 +878,18 @@ def op_attention_pool(d_x: int, row_stride: int, img_stride: int, d_ln_w: int, d
     """vitx_op_attention_pool: the pooling kernel of the attention-pooling head (device pointers, strides in floats): M [n_img, H, D] f32 and,
     with d_p, the probabilities [n_img, H, N] f32."""
     check(lib().vitx_op_attention_pool(d_x, row_stride, img_stride, d_ln_w, d_ln_b, eps, d_u, d_M, d_p or None, n_img, N, D, H, stream or None), "vitx_op_attention_pool")
+
+
+def op_text_embed(table_f16: bool, d_tok: int, d_pos: int, d_ids: int, d_x: int, n: int, T: int, D: int, stream: int = 0) -> None:
+    check(lib().vitx_op_text_embed(1 if table_f16 else 0, d_tok, d_pos, d_ids, d_x, n, T, D, stream), "vitx_op_text_embed")
+
+
+def op_text_pool(dtype: int, d_x: int, d_pooled: int, d_w: int, d_b: int, d_z: int, n: int, T: int, D: int, eps: float = 1e-6, stream: int = 0) -> None:
+    check(lib().vitx_op_text_pool(dtype, d_x, d_pooled, d_w, d_b, d_z, n, T, D, eps, stream), "vitx_op_text_pool")
+
+
+def op_attention_text(dtype: int, d_qkv: int, d_out: int, n: int, T: int, D: int, H: int, causal: bool, stream: int = 0) -> None:
+    check(lib().vitx_op_attention_text(dtype, d_qkv, d_out, n, T, D, H, 1 if causal else 0, stream), "vitx_op_attention_text")
 
 
 def zeroshot_max_classes(E: int) -> int:

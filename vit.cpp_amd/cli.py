@@ -8,6 +8,8 @@ directory-walk accuracy harness:
     python vit_cli.py -m model.gguf ... --img-size 384 [--pos-interp bicubic|bicubic-aa]   # run at another input size than the file's
     python vit_cli.py -m model.gguf ... [--preprocess model|reference]   # the file's own preprocessing (default) or the reference's for any file
     python vit_cli.py -m clip.gguf -i image.jpg -k 5 --zero-shot bank.npz   # zero-shot classes of a CLIP / SigLIP file (bank: convert.py --zero-shot-out)
+    python vit_cli.py -m clip.gguf -i image.jpg --text-model text.gguf --zero-shot-ids ids.npy [--zero-shot-labels labels.txt]   # the bank made by the engine, same run
+    python vit_cli.py --text-model text.gguf --zero-shot-ids ids.npy --text-embed out.npy   # the text embeddings of tokenised prompts (no image, no -m)
 
 --preprocess model follows the file's `preproc` tensor (include/vitx.h "each model's own preprocessing": what convert.py reads from a
 HuggingFace preprocessor_config.json -- CLIP: Pillow-bicubic shortest edge 224, centre crop 224, CLIP's mean / std; DINOv2: shortest edge 256,
@@ -81,7 +83,37 @@ def make_parser() -> argparse.ArgumentParser:
     ap.add_argument("--zero-shot", default=None, metavar="BANK.npz",
                     help="with -i, a CLIP or SigLIP file: classify against the bank of text embeddings in BANK.npz (convert.py --zero-shot-out) instead of the "
                          "file's own head; the ' > label : 0.xx' lines are the bank's labels and the zero-shot probabilities (softmax for CLIP, sigmoid for SigLIP)")
+    ap.add_argument("--text-model", default=None, metavar="TEXT.gguf",
+                    help="the checkpoint's text-tower file (convert.py --text-out): with --zero-shot-ids the zero-shot bank is made by the engine in this run")
+    ap.add_argument("--zero-shot-ids", default=None, metavar="IDS.npy",
+                    help="with --text-model: token ids, an integer array [prompts][tokens], one class per prompt (there is no tokenizer in the engine)")
+    ap.add_argument("--zero-shot-labels", default=None, metavar="LABELS.txt", help="with --zero-shot-ids: one class name per line (default: class_<k>)")
+    ap.add_argument("--text-embed", default=None, metavar="OUT.npy", help="with --text-model and --zero-shot-ids: write the prompts' text embeddings [prompts][E] and stop "
+                                                                          "unless -m names an image model to classify with")
     return ap
+
+
+def text_side(binding, a, dt):
+    """--text-model: the embeddings and the bank of --zero-shot-ids made by the engine.  Returns the bank (load_bank's dict), or raises
+    VitxError / OSError / ValueError."""
+    ids = np.load(a.zero_shot_ids)
+    tmodel = binding.Model(a.text_model)
+    if tmodel.kind != binding.KIND_TEXT:
+        raise ValueError(f"'{a.text_model}' is an image model, not a text-tower file")
+    tctx = binding.TextContext(tmodel, max_prompts=max(1, min(int(np.shape(ids)[0]), 256)), dtype=dt, device=a.device)
+    raw = tctx.embed(ids)                                                 # the tower runs once: the file and the bank are made of the same rows
+    if a.text_embed:
+        np.save(a.text_embed, raw)
+        print(f"main: wrote {np.shape(ids)[0]} text embeddings to '{a.text_embed}'", file=sys.stderr)
+    embeds, kind, scale, bias = binding.text_bank(tctx, ids, embeds=raw)
+    tctx.close(); tmodel.close()
+    labels = [f"class_{k}" for k in range(embeds.shape[0])]
+    if a.zero_shot_labels:
+        with open(a.zero_shot_labels) as f:
+            labels = [l.rstrip("\n") for l in f if l.strip()]
+        if len(labels) != embeds.shape[0]:
+            raise ValueError(f"{len(labels)} labels in '{a.zero_shot_labels}' for {embeds.shape[0]} prompts")
+    return dict(embeds=embeds.astype(np.float32), labels=labels, kind=kind, scale=scale, bias=bias)
 
 
 def main(argv: List[str] | None = None) -> int:
@@ -90,6 +122,16 @@ def main(argv: List[str] | None = None) -> int:
     a = ap.parse_args(argv)
     if a.zero_shot and a.dir is not None:
         ap.error("--zero-shot takes the single image of -i, not --dir")
+    if (a.text_model is None) != (a.zero_shot_ids is None):
+        ap.error("--text-model and --zero-shot-ids come together")
+    if (a.zero_shot_labels or a.text_embed) and not a.text_model:
+        ap.error("--zero-shot-labels and --text-embed need --text-model TEXT.gguf --zero-shot-ids IDS.npy")
+    if a.text_model and a.zero_shot:
+        ap.error("--zero-shot BANK.npz and --text-model are two sources of one bank: give one")
+    if a.text_model and a.dir is not None:
+        ap.error("--text-model takes the single image of -i, not --dir")
+    if a.text_model and a.dtype == "mxfp8":
+        ap.error("--text-model: a text context takes --dtype f16 or bf16")
     if a.attn_map and a.dir is not None:
         ap.error("--attn-map takes the single image of -i, not --dir")
     if a.embed is None and (a.embed_l2 or a.embed_kind != "cls"):
@@ -101,6 +143,15 @@ def main(argv: List[str] | None = None) -> int:
 
     t_main = time.perf_counter()
     print(f"main: seed = {a.seed if a.seed >= 0 else int(time.time())}", file=sys.stderr)
+    text_bank = None
+    if a.text_model:
+        try:
+            text_bank = text_side(binding, a, binding.F16 if a.dtype == "f16" else binding.BF16)
+        except (binding.VitxError, OSError, ValueError) as e:
+            print(f"main: the text tower of '{a.text_model}' failed: {e}", file=sys.stderr)
+            return 1
+        if a.text_embed and a.model == ap.get_default("model"):           # embeddings only: no image model was named
+            return 0
     try:
         model = binding.Model(a.model)
     except binding.VitxError as e:
@@ -126,7 +177,7 @@ def main(argv: List[str] | None = None) -> int:
         preprocess = lambda img: binding.preprocess(img, S, interp)
     geometry = dict(img_size=a.img_size, pos_interp=binding.POS_BICUBIC_AA if a.pos_interp == "bicubic-aa" else binding.POS_BICUBIC) if a.img_size else {}
 
-    bank = None
+    bank = text_bank
     if a.zero_shot:
         from .convert import load_bank
         try:
@@ -162,7 +213,7 @@ def main(argv: List[str] | None = None) -> int:
             try:
                 ctx.zeroshot_set(bank["embeds"], bank["kind"], bank["scale"], bank["bias"])
             except binding.VitxError as e:
-                print(f"main: the bank of '{a.zero_shot}' does not fit this model: {e}", file=sys.stderr)
+                print(f"main: the bank of '{a.zero_shot or a.text_model}' does not fit this model: {e}", file=sys.stderr)
                 return 1
         probs = ctx.forward(img1[None])[0]
         if a.embed:

@@ -360,6 +360,49 @@ def siglip_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg) -> Dict[str, np.nd
     return _f32(out)
 
 
+# --------------------------------------------------------------------------- text towers (include/vitx.h "the text tower")
+# (tests/test_cpu_text.py reads the macro out of kernels.h and holds this tuple to it)
+LN_WIDTHS = (64, 128, 192, 256, 384, 512, 768, 1024, 1280, 1536, 320, 448, 576, 640, 896, 1152, 1408, 1664, 2048)     # VITX_LN_WIDTHS (kernels.h)
+TEXT_MAX_TOKENS = 128
+
+
+def _text_prefix(sd) -> str:
+    pre = next((p for p in ("text_model.", "") if p + "embeddings.token_embedding.weight" in sd), None)
+    if pre is None:
+        raise ValueError("not a text-tower state dict: embeddings.token_embedding.weight is missing")
+    return pre
+
+
+def _text_front(sd, cfg, pre: str) -> Dict[str, np.ndarray]:
+    e = pre + "embeddings."
+    D = int(cfg.hidden_size)
+    _require_mlp_4x(cfg, "intermediate_size", 4 * D)
+    out = {"token_embed.weight": sd[e + "token_embedding.weight"], "pos_embed": sd[e + "position_embedding.weight"]}
+    map_blocks(out, sd, CLIP_BLOCKS, cfg.num_hidden_layers, pre)
+    _put(out, "norm", sd, pre + "final_layer_norm")
+    return out
+
+
+def clip_text_state_dict(sd: Dict[str, np.ndarray], cfg, no_head: bool = False) -> Dict[str, np.ndarray]:
+    """An HF CLIPTextModelWithProjection / CLIPModel state dict under a text file's names and order: token_embedding -> token_embed.weight [V][D],
+    position_embedding -> pos_embed [T][D], the blocks through map_blocks, final_layer_norm -> norm, the bias-free text_projection [E][D] ->
+    head.weight with a zero head.bias."""
+    out = _text_front(sd, cfg, _text_prefix(sd))
+    if "text_projection.weight" not in sd:
+        raise ValueError("the model has no text_projection: a text file holds the projected tower (CLIPTextModelWithProjection or CLIPModel)")
+    out["head.weight"] = sd["text_projection.weight"]
+    out["head.bias"] = np.zeros((int(np.shape(out["head.weight"])[0]),), np.float32)
+    return _f32(out)
+
+
+def siglip_text_state_dict(sd: Dict[str, np.ndarray], cfg, no_head: bool = False) -> Dict[str, np.ndarray]:
+    """An HF SiglipTextModel / SiglipModel state dict under a text file's names and order; the tower's own `head` (a Linear with bias) is the projection."""
+    pre = _text_prefix(sd)
+    out = _text_front(sd, cfg, pre)
+    _put(out, "head", sd, pre + "head")
+    return _f32(out)
+
+
 # --------------------------------------------------------------------------- one write path for every HuggingFace family
 def _config_labels(cfg, num_classes: int):
     return {int(k): str(v) for k, v in (getattr(cfg, "id2label", None) or {}).items()} or None
@@ -376,9 +419,23 @@ _VIT = Family("ViT", lambda sd, cfg, no_head: state_dict_to_timm(sd, cfg.num_hid
 _DINOV2 = Family("DINOv2", dinov2_state_dict_to_timm, 1, _config_labels, "optional", ("AutoModelForImageClassification", "AutoModel"))
 _CLIP = Family("CLIP", clip_state_dict_to_timm, 1, lambda cfg, E: {i: f"dim_{i}" for i in range(E)}, "optional", ("CLIPVisionModelWithProjection", "CLIPVisionModel"))
 _SIGLIP = Family("SigLIP", lambda sd, cfg, no_head: siglip_state_dict_to_timm(sd, cfg), 0, None, "never", ("SiglipVisionModel",) * 2)
-_TWO_TOWERS = ("clip", "siglip")          # converted as their vision tower (config.vision_config)
+# text towers (convert_hf_text_model): no patch grid (prefix_rows is not read), no labels -- the "classes" are the projection's columns --, always with the projection
+_CLIP_TEXT = Family("CLIP text", clip_text_state_dict, 0, lambda cfg, E: {}, "always", ("CLIPTextModelWithProjection",) * 2)
+_SIGLIP_TEXT = Family("SigLIP text", siglip_text_state_dict, 0, lambda cfg, E: {}, "always", ("SiglipTextModel",) * 2)
+_TWO_TOWERS = ("clip", "siglip")          # converted as their vision tower (config.vision_config); convert_hf_text_model takes config.text_config
 # by model_type, the vision tower's or, for main(), the checkpoint's; any other model_type is taken for a ViT
-FAMILIES = {"vit": _VIT, "dinov2": _DINOV2, "dinov2_with_registers": _DINOV2, "clip_vision_model": _CLIP, "clip": _CLIP, "siglip_vision_model": _SIGLIP, "siglip": _SIGLIP}
+FAMILIES = {"vit": _VIT, "dinov2": _DINOV2, "dinov2_with_registers": _DINOV2, "clip_vision_model": _CLIP, "clip": _CLIP, "siglip_vision_model": _SIGLIP, "siglip": _SIGLIP,
+            "clip_text_model": _CLIP_TEXT, "siglip_text_model": _SIGLIP_TEXT}
+
+
+def _family_tensors(model, cfg, fam, no_head: bool, head_dim_note: str = ""):
+    """The front both converters share: the head-dim refusal, the state dict as numpy arrays, the config's activation and epsilon, and the
+    family's mapper.  Returns (the file's tensors in its order, activation, eps); each converter then states its header and calls write_model."""
+    hd = cfg.hidden_size // cfg.num_attention_heads
+    if cfg.hidden_size % cfg.num_attention_heads or hd % 8 or not 8 <= hd <= 128:
+        raise ValueError(f"head_dim {hd}: the forward path takes multiples of 8 up to 128{head_dim_note}")
+    sd = {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
+    return fam.mapper(sd, cfg, no_head), hf_activation(cfg), float(getattr(cfg, "layer_norm_eps", 1e-6))
 
 
 def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_head: bool = False, preprocessor_config: dict | None = None) -> HParams:
@@ -399,21 +456,18 @@ def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_
     if getattr(cfg, "model_type", "") in _TWO_TOWERS:
         cfg = cfg.vision_config
     fam = FAMILIES.get(getattr(cfg, "model_type", ""), _VIT)
+    if fam in (_CLIP_TEXT, _SIGLIP_TEXT):
+        raise ValueError(f"{cls_name} is a text tower: convert it with convert_hf_text_model (--text-out)")
     if vitstr and preprocessor_config is not None:
         raise ValueError("a ViTSTR model's preprocessing is fixed: convert it without a preprocessor_config")
     if vitstr and getattr(cfg, "num_channels", 3) != 1:
         raise ValueError("a ViTSTR model takes one (grey) input channel")
-    hd = cfg.hidden_size // cfg.num_attention_heads
-    if cfg.hidden_size % cfg.num_attention_heads or hd % 8 or not 8 <= hd <= 128:
-        raise ValueError(f"head_dim {hd}: the forward path takes multiples of 8 up to 128 (64 runs the tuned attention kernels)")
     if vitstr and fam.name != "ViT":
         raise ValueError(f"a {fam.name} model is not a ViTSTR model")
     if no_head and fam.head == "always":
         raise ValueError("no_head converts a DINOv2 backbone (Dinov2Model, Dinov2WithRegistersModel), a CLIPVisionModel or a SigLIP tower")
     headless = fam.head == "never" or no_head
-    sd = {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
-    act, eps = hf_activation(cfg), float(getattr(cfg, "layer_norm_eps", 1e-6))
-    tensors = fam.mapper(sd, cfg, no_head)
+    tensors, act, eps = _family_tensors(model, cfg, fam, no_head, " (64 runs the tuned attention kernels)")
     g = grid_side(tensors["pos_embed"], fam.prefix_rows)          # the checkpoint's own grid (config.image_size states it too)
     hp = HParams(cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, int(tensors["head.weight"].shape[0]), cfg.patch_size, g * cfg.patch_size, ftype)
     id2label = NO_HEAD_LABELS if headless else fam.labels(cfg, hp.num_classes)
@@ -424,6 +478,54 @@ def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_
         id2label = dict(VITSTR_LABELS)
     write_model(path, hp, with_arch(tensors, act, eps), id2label=id2label, ftype=ftype,
                 preproc=hf_preproc(preprocessor_config, hp.img_size) if preprocessor_config is not None else None)
+    return hp
+
+
+def convert_hf_text_model(model, path: str, ftype: int = 1) -> HParams:
+    """The text tower of a transformers CLIPTextModelWithProjection, CLIPModel, SiglipTextModel or SiglipModel as a text-tower file (include/vitx.h
+    "the text tower"): header hidden D, layers L, heads H, num_classes = E (the projected width), patch_size = 0 (the mark of a text file),
+    img_size = T (max_position_embeddings); tensors token_embed.weight, pos_embed, blocks.*, norm.*, head.*, and always
+    `arch` = {activation, eps, causal, eos + 1}: causal 1 for CLIP, 0 for SigLIP; SigLIP pools the last position (slot 3 = 0), CLIP pools as
+    transformers does today: the FIRST position whose id equals config.eos_token_id.  Legacy CLIP configs (eos_token_id == 2) pool at
+    argmax(ids) instead; for those the file names eos = vocab_size - 1, the id for which both rules agree on tokenised input (CLIP's tokenizer
+    gives <|endoftext|> the highest id, and pads with it).  A two-tower model also writes `zs` = {kind, exp(logit_scale), logit_bias, 0}.
+    The token table is never block-quantised (ggml_file.write_model).  Writes `path`; returns the hparams written."""
+    cfg = model.config
+    mt = getattr(cfg, "model_type", "")
+    zs = None
+    if mt in _TWO_TOWERS:
+        sd_all = model.state_dict()
+        scale = float(np.exp(np.float64(sd_all["logit_scale"].detach().double().reshape(-1)[0].item())))
+        bias = float(sd_all["logit_bias"].detach().double().reshape(-1)[0].item()) if mt == "siglip" else 0.0
+        zs = np.array([ZS_SIGMOID if mt == "siglip" else ZS_SOFTMAX, scale, bias, 0.0], np.float32)
+        cfg = cfg.text_config
+    fam = FAMILIES.get(getattr(cfg, "model_type", ""))
+    if fam not in (_CLIP_TEXT, _SIGLIP_TEXT):
+        raise ValueError(f"convert_hf_text_model: model_type '{getattr(cfg, 'model_type', '')}' is no CLIP or SigLIP text tower")
+    D, T = int(cfg.hidden_size), int(cfg.max_position_embeddings)
+    if D not in LN_WIDTHS:
+        raise ValueError(f"hidden_size {D} has no LayerNorm instantiation ({', '.join(str(w) for w in sorted(LN_WIDTHS))})")
+    if not 1 <= T <= TEXT_MAX_TOKENS:
+        raise ValueError(f"max_position_embeddings {T}: the text attention takes 1 .. {TEXT_MAX_TOKENS} tokens")
+    tensors, act, eps = _family_tensors(model, cfg, fam, False)
+    V, E = int(tensors["token_embed.weight"].shape[0]), int(tensors["head.weight"].shape[0])
+    if tuple(tensors["pos_embed"].shape) != (T, D):
+        raise ValueError(f"position_embedding {tuple(tensors['pos_embed'].shape)}: expected [{T}][{D}]")
+    if fam is _CLIP_TEXT:
+        eos = int(getattr(cfg, "eos_token_id", 2))
+        if eos == 2:
+            eos = V - 1
+        if not 0 <= eos < V:
+            raise ValueError(f"eos_token_id {eos} is outside the vocabulary of {V}")
+        causal, slot = 1, eos + 1
+    else:
+        causal, slot = 0, 0
+    out = {"arch": np.array([act, np.float32(eps), causal, slot], np.float32)}
+    if zs is not None:
+        out["zs"] = zs
+    out.update(tensors)
+    hp = HParams(D, cfg.num_hidden_layers, cfg.num_attention_heads, E, 0, T, ftype)
+    write_model(path, hp, out, id2label=fam.labels(cfg, E), ftype=ftype)
     return hp
 
 
@@ -656,7 +758,11 @@ def main(argv=None) -> int:
                          "the token ids is the tested --zero-shot-ids path")
     ap.add_argument("--zero-shot-labels", default=None, metavar="LABELS.txt", help="one class name per line (default: the prompts themselves, or class_<k>)")
     ap.add_argument("--zero-shot-out", default=None, metavar="BANK.npz", help="where the bank goes (embeds, labels, kind, scale, bias)")
+    ap.add_argument("--text-out", default=None, metavar="TEXT.gguf", help="CLIPModel / SiglipModel (or a text tower alone): also write the text tower as a text-tower file "
+                                                                          "(convert_hf_text_model; vit_cli.py --text-model)")
     a = ap.parse_args(argv)
+    if a.text_out and a.timm_state_dict:
+        ap.error("--text-out needs a HuggingFace CLIP / SigLIP checkpoint, not a timm state dict")
     if (a.zero_shot_ids is None) == (a.zero_shot_prompts is None) and a.zero_shot_out:
         ap.error("--zero-shot-out needs exactly one of --zero-shot-ids and --zero-shot-prompts")
     if (a.zero_shot_ids or a.zero_shot_prompts or a.zero_shot_labels) and not a.zero_shot_out:
@@ -678,6 +784,14 @@ def main(argv=None) -> int:
             if model_type not in _TWO_TOWERS:
                 ap.error(f"a zero-shot bank needs a CLIPModel or SiglipModel checkpoint (both towers), not model_type '{model_type}'")
             _main_bank(a, transformers, model_type)
+        if a.text_out:
+            if model_type not in _TWO_TOWERS + ("clip_text_model", "siglip_text_model"):
+                ap.error(f"--text-out needs a CLIP or SigLIP checkpoint, not model_type '{model_type}'")
+            tcls = {"clip": "CLIPModel", "siglip": "SiglipModel"}.get(model_type) or FAMILIES[model_type].loaders[0]
+            thp = convert_hf_text_model(getattr(transformers, tcls).from_pretrained(a.model).eval(), a.text_out, a.ftype)
+            print(f"wrote {a.text_out}: text tower, hidden {thp.hidden_size}, layers {thp.num_hidden_layers}, heads {thp.num_attention_heads}, width {thp.num_classes}, tokens {thp.img_size}, ftype {a.ftype}")
+            if model_type not in _TWO_TOWERS:
+                return 0                                   # a text tower alone: there is no vision file to write
         fam = FAMILIES.get(model_type, _VIT)
         m = getattr(transformers, fam.loaders[1 if a.no_head and fam.head == "optional" else 0]).from_pretrained(a.model).eval()
         pc, pc_path = None, os.path.join(a.model, "preprocessor_config.json")

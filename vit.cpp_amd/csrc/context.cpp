@@ -216,6 +216,40 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
     return VITX_OK;
 }
 
+// The transformer blocks blocks.{i}.* of a model file into the context's weight set: the same twelve tensors per layer in an image file and a text file
+int upload_blocks(vitx_ctx *c) {
+    const vitx_model *m = c->model;
+    const int D = c->D, tn = c->tn;
+    int rc;
+    auto T = [&](const std::string &n) { return m->find(n); };
+    vitx_ctx::WeightSet &ws = *c->wset;
+    ws.layers.resize(c->L);
+    for (int i = 0; i < c->L; ++i) {
+        const std::string p = "blocks." + std::to_string(i) + ".";
+        LayerW &w = ws.layers[i];
+        if ((rc = upload_f32(c, T(p + "norm1.weight"), &w.ln1_w))) return rc;
+        if ((rc = upload_f32(c, T(p + "norm1.bias"), &w.ln1_b))) return rc;
+        if ((rc = upload_f32(c, T(p + "norm2.weight"), &w.ln2_w))) return rc;
+        if ((rc = upload_f32(c, T(p + "norm2.bias"), &w.ln2_b))) return rc;
+        if ((rc = upload_f32(c, T(p + "attn.qkv.bias"), &w.qkv_b, round_up(3 * D, tn)))) return rc;
+        if ((rc = upload_f32(c, T(p + "attn.proj.bias"), &w.proj_b, round_up(D, tn)))) return rc;
+        if ((rc = upload_f32(c, T(p + "mlp.fc1.bias"), &w.fc1_b, round_up(4 * D, tn)))) return rc;
+        if ((rc = upload_f32(c, T(p + "mlp.fc2.bias"), &w.fc2_b, round_up(D, tn)))) return rc;
+        w.qkv_w = w.fc1_w = w.fc2_w = nullptr;
+        if (c->mx) {
+            if ((rc = upload_mx(c, T(p + "attn.qkv.weight"), 3 * D, D, round_up(3 * D, 128), &w.mx[W_QKV]))) return rc;
+            if ((rc = upload_mx(c, T(p + "mlp.fc1.weight"), 4 * D, D, round_up(4 * D, 128), &w.mx[W_FC1]))) return rc;
+            if ((rc = upload_mx(c, T(p + "mlp.fc2.weight"), D, 4 * D, round_up(D, 128), &w.mx[W_FC2]))) return rc;
+        } else {
+            if ((rc = upload_weight(c, T(p + "attn.qkv.weight"), 3 * D, D, round_up(3 * D, tn), &w.qkv_w, &w.q[W_QKV]))) return rc;
+            if ((rc = upload_weight(c, T(p + "mlp.fc1.weight"), 4 * D, D, round_up(4 * D, tn), &w.fc1_w, &w.q[W_FC1]))) return rc;
+            if ((rc = upload_weight(c, T(p + "mlp.fc2.weight"), D, 4 * D, round_up(D, tn), &w.fc2_w, &w.q[W_FC2]))) return rc;
+        }
+        if ((rc = upload_weight(c, T(p + "attn.proj.weight"), D, D, round_up(D, tn), &w.proj_w, &w.q[W_PROJ]))) return rc;
+    }
+    return VITX_OK;
+}
+
 // Step 2: the device copies of the weights, found in the registry or uploaded.  `dtype`: the type the caller asked for (the key tells MXFP8 from BF16)
 int obtain_weights(vitx_ctx *c, int dtype) {
     const vitx_model *m = c->model;
@@ -230,6 +264,23 @@ int obtain_weights(vitx_ctx *c, int dtype) {
     for (auto it = wreg.begin(); it != wreg.end();) it = it->second.expired() ? wreg.erase(it) : std::next(it);      // sets whose last context is gone
     if (auto have = wreg[wkey].lock()) {
         c->wset = have; c->weights_shared = true;
+    } else if (m->kind == VITX_KIND_TEXT) {
+        // a text tower (text_forward.cpp): the token table as filed (a gather reads it), the position table, the same blocks, final norm, projection
+        c->wset = std::make_shared<vitx_ctx::WeightSet>();
+        vitx_ctx::WeightSet &ws = *c->wset;
+        ws.device = device;
+        const HostTensor *tok = T("token_embed.weight");
+        ws.tok_f16 = tok->type == T_F16;
+        if ((rc = c->wmalloc(&ws.tok, tok->raw.size()))) return rc;
+        HIP_TRY(hipMemcpy(ws.tok, tok->raw.data(), tok->raw.size(), hipMemcpyHostToDevice));
+        ws.weight_bytes += tok->raw.size();
+        if ((rc = upload_f32(c, T("pos_embed"), &ws.pos))) return rc;
+        if ((rc = upload_blocks(c))) return rc;
+        if ((rc = upload_f32(c, T("norm.weight"), &ws.norm_w))) return rc;
+        if ((rc = upload_f32(c, T("norm.bias"), &ws.norm_b))) return rc;
+        if ((rc = upload_f32(c, T("head.bias"), &ws.head_b, c->C_pad))) return rc;
+        if ((rc = upload_weight(c, T("head.weight"), c->C, D, c->C_pad, &ws.head_w, &ws.head_q))) return rc;
+        wreg[wkey] = c->wset;
     } else {
         c->wset = std::make_shared<vitx_ctx::WeightSet>();
         vitx_ctx::WeightSet &ws = *c->wset;
@@ -240,30 +291,7 @@ int obtain_weights(vitx_ctx *c, int dtype) {
         if (m->has_pre_norm && ((rc = upload_f32(c, T("pre_norm.weight"), &ws.pre_w)) || (rc = upload_f32(c, T("pre_norm.bias"), &ws.pre_b)))) return rc;
         if ((rc = upload_f32(c, T("patch_embed.proj.bias"), &ws.pe_b, round_up(D, tn)))) return rc;
         if ((rc = upload_matrix(c, T("patch_embed.proj.weight"), D, c->Kpe, round_up(D, tn), c->Kpe_pad, &ws.pe_w, c->P, c->Cin))) return rc;
-        ws.layers.resize(c->L);
-        for (int i = 0; i < c->L; ++i) {
-            const std::string p = "blocks." + std::to_string(i) + ".";
-            LayerW &w = ws.layers[i];
-            if ((rc = upload_f32(c, T(p + "norm1.weight"), &w.ln1_w))) return rc;
-            if ((rc = upload_f32(c, T(p + "norm1.bias"), &w.ln1_b))) return rc;
-            if ((rc = upload_f32(c, T(p + "norm2.weight"), &w.ln2_w))) return rc;
-            if ((rc = upload_f32(c, T(p + "norm2.bias"), &w.ln2_b))) return rc;
-            if ((rc = upload_f32(c, T(p + "attn.qkv.bias"), &w.qkv_b, round_up(3 * D, tn)))) return rc;
-            if ((rc = upload_f32(c, T(p + "attn.proj.bias"), &w.proj_b, round_up(D, tn)))) return rc;
-            if ((rc = upload_f32(c, T(p + "mlp.fc1.bias"), &w.fc1_b, round_up(4 * D, tn)))) return rc;
-            if ((rc = upload_f32(c, T(p + "mlp.fc2.bias"), &w.fc2_b, round_up(D, tn)))) return rc;
-            w.qkv_w = w.fc1_w = w.fc2_w = nullptr;
-            if (c->mx) {
-                if ((rc = upload_mx(c, T(p + "attn.qkv.weight"), 3 * D, D, round_up(3 * D, 128), &w.mx[W_QKV]))) return rc;
-                if ((rc = upload_mx(c, T(p + "mlp.fc1.weight"), 4 * D, D, round_up(4 * D, 128), &w.mx[W_FC1]))) return rc;
-                if ((rc = upload_mx(c, T(p + "mlp.fc2.weight"), D, 4 * D, round_up(D, 128), &w.mx[W_FC2]))) return rc;
-            } else {
-                if ((rc = upload_weight(c, T(p + "attn.qkv.weight"), 3 * D, D, round_up(3 * D, tn), &w.qkv_w, &w.q[W_QKV]))) return rc;
-                if ((rc = upload_weight(c, T(p + "mlp.fc1.weight"), 4 * D, D, round_up(4 * D, tn), &w.fc1_w, &w.q[W_FC1]))) return rc;
-                if ((rc = upload_weight(c, T(p + "mlp.fc2.weight"), D, 4 * D, round_up(D, tn), &w.fc2_w, &w.q[W_FC2]))) return rc;
-            }
-            if ((rc = upload_weight(c, T(p + "attn.proj.weight"), D, D, round_up(D, tn), &w.proj_w, &w.q[W_PROJ]))) return rc;
-        }
+        if ((rc = upload_blocks(c))) return rc;
         if ((rc = upload_f32(c, T("norm.weight"), &ws.norm_w))) return rc;
         if ((rc = upload_f32(c, T("norm.bias"), &ws.norm_b))) return rc;
         if (c->map && (rc = upload_map_head(c))) return rc;
@@ -328,6 +356,10 @@ int alloc_slice(vitx_ctx *c, vitx_ctx::Slice &sl, size_t hcols, bool internal) {
 
 }  // namespace
 
+// The weight set of a text context (text_forward.cpp): `shell` is a vitx_ctx that carries only what the upload reads (model, device, dtype, D, L, C,
+// C_pad, tn, quant_on_device = false) and receives wset -- the registry, the sharing rule and every upload function are the image contexts'.
+int vitx::obtain_text_weights(vitx_ctx *shell) { return obtain_weights(shell, shell->dtype); }
+
 extern "C" {
 
 int vitx_ctx_create(const vitx_model *m, int device, int max_batch, int dtype, vitx_ctx **out) { return vitx_ctx_create_ex(m, device, max_batch, dtype, nullptr, out); }
@@ -335,6 +367,7 @@ int vitx_ctx_create(const vitx_model *m, int device, int max_batch, int dtype, v
 int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype, const vitx_ctx_options *opt_in, vitx_ctx **out) {
     if (!m || !out || max_batch <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16 && dtype != VITX_MXFP8)) { set_error("vitx_ctx_create: invalid argument"); return VITX_ERR_ARG; }
     *out = nullptr;
+    if (m->kind != VITX_KIND_IMAGE) { set_error("vitx_ctx_create: a text-tower model takes a text context (vitx_text_create), not an image context"); return VITX_ERR_ARG; }
     vitx_ctx_options opt{};                   // all zero = every default
     std::unique_ptr<vitx_ctx> c;
     int rc;

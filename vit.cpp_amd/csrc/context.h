@@ -1,5 +1,6 @@
-// context.h -- the execution context (struct vitx_ctx) as context.cpp, forward.cpp, outputs.cpp and ops.cpp share it.  Internal: nothing
-// outside those four files includes it; callers see the opaque vitx_ctx of include/vitx.h.
+// context.h -- the execution context (struct vitx_ctx) as context.cpp, forward.cpp, outputs.cpp and ops.cpp share it, and the text context
+// (struct vitx_text) of text_forward.cpp.  Internal: nothing outside those five files includes it; callers see the opaque vitx_ctx and vitx_text
+// of include/vitx.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -99,6 +100,8 @@ struct vitx_ctx {
         float *cls = nullptr, *reg = nullptr, *pos = nullptr, *pe_b = nullptr, *norm_w = nullptr, *norm_b = nullptr, *head_b = nullptr;
         void *pe_w = nullptr, *head_w = nullptr;
         QuantW head_q;
+        void *tok = nullptr;             // a text tower's token table [V][D] as filed: f16 (tok_f16) or f32
+        bool tok_f16 = false;
         // VITX_POOL_MAP (attn_pool.*): u [H][D] f32 (the folded probe, vitx_model_pool_query); the V half of kv.weight / kv.bias, padded by 128 rows so that
         // every head's [d][D] block can be read as a whole column tile; proj, norm, fc1, fc2 like a block's
         float *map_u = nullptr, *map_v_b = nullptr, *map_proj_b = nullptr, *map_ln_w = nullptr, *map_ln_b = nullptr, *map_fc1_b = nullptr, *map_fc2_b = nullptr;
@@ -292,6 +295,34 @@ struct vitx_ctx {
     hipEvent_t next_event() {
         if (ev_used == ev_pool.size()) { hipEvent_t e; (void)hipEventCreate(&e); ev_pool.push_back(e); }
         return ev_pool[ev_used++];
+    }
+};
+
+namespace vitx { int obtain_text_weights(vitx_ctx *shell); }      // context.cpp
+
+// The text context (text_forward.cpp; include/vitx.h "the text tower"): one stream, no sub-batches, no graph cache, no LayerNorm fusion.
+struct vitx_text {
+    vitx_ctx shell;                      // the weight holder (obtain_text_weights): model, device, dtype, D, L, H, C = E, wset; no scratch, no stream of its own
+    int V = 0, T = 0, E = 0, E_pad = 0, causal = 0, eos = -1, max_prompts = 0;
+    int fc1_epi = EPI_BIAS_GELU;
+    float eps = 1e-6f;
+    Tuning tune_qkv, tune_proj, tune_fc1, tune_fc2, tune_head;      // the device's tuning with ONE ring family pinned per GEMM, chosen at creation from max_prompts * T rows
+    hipStream_t stream = nullptr;        // of vitx_text_embed (the host entry point)
+    std::vector<void *> allocs;
+    int *pooled = nullptr, *ids = nullptr;      // [max_prompts] pooled positions, then [max_prompts][T] ids: one buffer, one upload of its front
+    std::vector<int> host;               // the same on the host: the staging buffer of the upload
+    std::vector<int32_t> pooled_host;    // the positions of the call being checked (stage_ids), before they may enter `host`
+    hipEvent_t uploaded = nullptr;       // recorded behind the upload of a call: the next call waits for it before it overwrites `host`
+    bool uploaded_pending = false;
+    float *X = nullptr;                  // [Mpad][D] f32 residual stream
+    void *U = nullptr, *QKV = nullptr, *Hbuf = nullptr, *Z = nullptr;      // [Mpad][D], [Mpad][3 D], [Mpad][4 D], [Bpad][D] operand type
+    float *out = nullptr;                // [Bpad][E] f32 embeddings of the host entry point
+    float *raw = nullptr;                // [Bpad][E] f32: the head's output in front of VITX_TEXT_L2
+    ~vitx_text() {
+        (void)hipSetDevice(shell.device);
+        for (void *p : allocs) (void)hipFree(p);
+        if (uploaded) (void)hipEventDestroy(uploaded);
+        if (stream) (void)hipStreamDestroy(stream);
     }
 };
 

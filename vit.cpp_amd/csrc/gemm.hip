@@ -211,6 +211,16 @@ static hipError_t launch_wide(const Tuning &t, int dtype, int epi, const GemmArg
     return launch_gemm_ring(t, dtype, epi, a, wide_ring_cfg(a), stream);
 }
 
+// The ring tiling of a shape that is not wide (0: none): 128 x 256 tiles, or the skinny 64 x 128 ones when those would leave half of the CUs idle.
+// A column count that is a multiple of 128 but not of 256 takes the 64 x 128 tiles at any row count (the v1 128 x 128 kernel used to take
+// these; it now exists only in its q4_0 form, launch_gemm_q4).  launch_gemm's rule, stated once: a text context pins it per GEMM (text_forward.cpp).
+int gemm_ring_cfg(const Tuning &t, const GemmArgs &a) {
+    int cfg = 245;
+    if ((long)(a.M / 128) * (a.N_pad / 256) < t.skinny_tiles && gemm_ring_supports(a, 122)) cfg = 122;
+    if (gemm_ring_supports(a, cfg)) return cfg;
+    return gemm_ring_supports(a, 122) ? 122 : 0;
+}
+
 hipError_t launch_gemm(const Tuning &t, int dtype, int epi, const GemmArgs &a, hipStream_t stream) {
     if (a.M <= 0) return hipErrorInvalidValue;
     if (a.ln && !gemm_ln_fusable(t, a)) return hipErrorInvalidValue;      // the caller asks gemm_ln_fusable first
@@ -241,13 +251,8 @@ hipError_t launch_gemm(const Tuning &t, int dtype, int epi, const GemmArgs &a, h
         }
         return launch_wide(t, dtype, epi, a, stream);
     }
-    cfg = 245;
-    if ((long)(a.M / 128) * (a.N_pad / 256) < t.skinny_tiles && gemm_ring_supports(a, 122)) cfg = 122;
-    if (gemm_ring_supports(a, cfg)) return launch_gemm_ring(t, dtype, epi, a, cfg, stream);
-    // a column count that is a multiple of 128 but not of 256: the 64 x 128 ring tiles at any row count (the v1 128 x 128 kernel used to
-    // take these; it now exists only in its q4_0 form, launch_gemm_q4)
-    if (gemm_ring_supports(a, 122)) return launch_gemm_ring(t, dtype, epi, a, 122, stream);
-    return hipErrorInvalidValue;
+    cfg = gemm_ring_cfg(t, a);
+    return cfg ? launch_gemm_ring(t, dtype, epi, a, cfg, stream) : hipErrorInvalidValue;
 }
 
 bool gemm_q4_supports(const GemmArgs &a) { return a.Wscale && a.M > 0 && a.M % GBM == 0 && a.N_pad % GBN == 0 && a.K % GBK == 0; }

@@ -141,6 +141,7 @@ bool gemm_fix_capable(const Tuning &t, const GemmArgs &a);
 int gemm_ln_grid(int n_cu, int M, int N);
 // normalises the row blocks a fused GEMM left behind (todo[rb] == epoch) from x (layernorm.hip); a few microseconds when there are none
 hipError_t launch_layernorm_fixup(int dtype, const float *x, const float *w, const float *b, void *y, int M, int D, float eps, const unsigned *todo, unsigned epoch, hipStream_t stream);
+int gemm_ring_cfg(const Tuning &t, const GemmArgs &a);   // the ring configuration (245 or 122; 0: none) launch_gemm gives a shape that is not wide
 int gemm_tile_m();   // M granularity the GEMM needs (buffer row padding)
 int gemm_tile_n();
 
@@ -211,7 +212,17 @@ hipError_t launch_pool_embed(const float *e, void *z, int dtype, float *cls, lon
 //             the sigmoid (VITX_ZS_SIGMOID); columns K .. ld are never read.  One workgroup per image.
 // hipErrorInvalidValue for a shape outside that.
 hipError_t launch_zs_embed(int dtype, const float *z, long z_stride, void *a, int n, int m_pad, int E, hipStream_t stream);
+// zs_embed with an f32 result, unrounded (VITX_TEXT_L2): a[i][0 .. E) = z / sqrt(sum z^2), dense rows of E floats, a != z; the same kernel text, one more instantiation
+hipError_t launch_zs_embed_f32(const float *z, long z_stride, float *a, int n, int E, hipStream_t stream);
 hipError_t launch_zs_score(const float *acc, int ld, float *probs, float *logits, long out_img_stride, int n, int K, int kind, float scale, float bias, hipStream_t stream);
+// The text tower (include/vitx.h "the text tower"; text_embed.hip, attention_text.hip).
+//   text_embed: X[i][t][:] (f32) = f32(tok[ids[i * T + t]][:]) + pos[t][:]; tok [V][D] f16 (table_f16) or f32, ids checked by the caller; D % 8 == 0
+//   text_pool:  z[i][:] (dtype) = RNE(final LayerNorm of X row i * T + pooled[i]), LnRow's bits; rows n .. m_pad zeros; every width of VITX_LN_WIDTHS
+//   attention_text: qkv [n * T][3 D] -> out [n * T][D] (dtype), 1 <= T <= 128, head dim a multiple of 8 up to 128; causal != 0: row t attends keys 0 .. t
+hipError_t launch_text_embed(bool table_f16, const void *tok, const float *pos, const int *ids, float *X, int n, int T, int D, hipStream_t stream);
+hipError_t launch_text_pool(int dtype, const float *X, const int *pooled, const float *w, const float *b, void *z, int n, int m_pad, int T, int D, float eps, hipStream_t stream);
+hipError_t launch_attention_text(int dtype, const void *qkv, void *out, int n, int T, int D, int H, int causal, hipStream_t stream);
+bool attention_text_supports(int T, int D, int H);
 // pos [1 + gy_in * gx_in][D] f32 -> out [1 + gy_out * gx_out][D] f32 (pos_resample.hip; the arithmetic: pos_resample.h); only enqueues
 hipError_t launch_pos_resample(const float *pos, int gy_in, int gx_in, int D, int gy_out, int gx_out, int interp, float *out, hipStream_t stream);
 bool attention_supports(int N, int D, int H);     // any token count; head_dim 64 (tuned kernels) or any other multiple of 8 up to 128 (generic kernel)
@@ -294,6 +305,7 @@ hipError_t prepare_attention_single();
 hipError_t prepare_attention_flow();
 hipError_t prepare_attention_persist();
 hipError_t prepare_attention_stream();
+hipError_t prepare_attention_text();                   // attention_text.hip
 #pragma GCC visibility pop
 
 }  // namespace vitx

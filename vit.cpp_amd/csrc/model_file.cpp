@@ -13,9 +13,13 @@
 // `pre_norm.bias` f32 [D] (CLIP's pre_layrnorm).  Without `arch` a file means tanh-GELU and eps 1e-6, the reference's arithmetic.
 // One more (include/vitx.h "no class token and the attention-pooling head"): the thirteen `attn_pool.*` tensors of a SigLIP-class model, which
 // come without cls_token / reg_token and with a pos_embed of g^2 rows (VITX_POOL_MAP).
+// A text-tower file (include/vitx.h "the text tower") is told by patch_size == 0: token_embed.weight [V][D] (f16 or f32) and pos_embed [T][D]
+// in place of the image front, the same blocks, norm.* and head.* [E][D]; `arch` is then required and its last two slots are {causal, eos + 1};
+// `zs` f32 [4] = {kind, scale, bias, 0} is optional.  cls_token, reg_token, pre_norm.*, preproc and attn_pool.* do not belong in one.
 #include "model_file.h"
 
 #include <math.h>
+#include <cmath>
 #include <stdarg.h>
 #include <stdio.h>
 #include <atomic>
@@ -105,11 +109,17 @@ void HostTensor::decode_f32(float *out) const {
 struct Expect { int64_t ne[4]; int cls; };
 static std::map<std::string, Expect> expected_tensors(const vitx_hparams &hp) {
     std::map<std::string, Expect> e;
-    const int64_t D = hp.hidden_size, C = hp.num_classes, P = hp.patch_size, g = hp.img_size / hp.patch_size, N = g * g + 1;
-    e["pos_embed"] = {{D, N, 1, 1}, 0};
-    e["cls_token"] = {{D, 1, 1, 1}, 0};
-    e["patch_embed.proj.weight"] = {{P, P, 3, D}, 2};
-    e["patch_embed.proj.bias"] = {{1, 1, D, 1}, 0};
+    const int64_t D = hp.hidden_size, C = hp.num_classes, P = hp.patch_size;
+    if (P == 0) {                                                    // a text tower (include/vitx.h "the text tower"): img_size = T; V is token_embed.weight's row count
+        e["pos_embed"] = {{D, hp.img_size, 1, 1}, 0};
+        e["token_embed.weight"] = {{D, 0, 1, 1}, 2};
+    } else {
+        const int64_t g = hp.img_size / P, N = g * g + 1;
+        e["pos_embed"] = {{D, N, 1, 1}, 0};
+        e["cls_token"] = {{D, 1, 1, 1}, 0};
+        e["patch_embed.proj.weight"] = {{P, P, 3, D}, 2};
+        e["patch_embed.proj.bias"] = {{1, 1, D, 1}, 0};
+    }
     for (int i = 0; i < hp.num_hidden_layers; ++i) {
         const std::string p = "blocks." + std::to_string(i) + ".";
         e[p + "norm1.weight"] = {{D, 1, 1, 1}, 0}; e[p + "norm1.bias"] = {{D, 1, 1, 1}, 0};
@@ -152,8 +162,10 @@ static int load_impl(const char *path, vitx_model &m) {
     vitx_hparams &hp = m.hp;
     hp.hidden_size = hv[0]; hp.num_hidden_layers = hv[1]; hp.num_attention_heads = hv[2]; hp.num_classes = hv[3];
     hp.patch_size = hv[4]; hp.img_size = hv[5]; hp.ftype = hv[6] % 1000 /* GGML_QNT_VERSION_FACTOR */; hp.eps = 1e-6f;
-    if (hp.hidden_size <= 0 || hp.num_hidden_layers <= 0 || hp.num_attention_heads <= 0 || hp.num_classes <= 0 || hp.patch_size <= 0 ||
-        hp.img_size <= 0 || hp.img_size % hp.patch_size || hp.hidden_size % hp.num_attention_heads || hp.num_hidden_layers > 4096) {
+    const bool text = hp.patch_size == 0;                            // THE mark of a text-tower file: no image file has it
+    m.kind = text ? VITX_KIND_TEXT : VITX_KIND_IMAGE;
+    if (hp.hidden_size <= 0 || hp.num_hidden_layers <= 0 || hp.num_attention_heads <= 0 || hp.num_classes <= 0 || hp.patch_size < 0 ||
+        hp.img_size <= 0 || (!text && hp.img_size % hp.patch_size) || hp.hidden_size % hp.num_attention_heads || hp.num_hidden_layers > 4096) {
         set_error("vitx_model_load: implausible hparams in '%s'", path); return VITX_ERR_FORMAT;
     }
     if (!type_block_bytes(hp.ftype)) { set_error("vitx_model_load: invalid model file '%s' (bad ftype value %d)", path, hp.ftype); return VITX_ERR_FORMAT; }
@@ -167,7 +179,7 @@ static int load_impl(const char *path, vitx_model &m) {
         m.id2label[key] = v;
     }
     const auto expect = expected_tensors(hp);
-    const auto pool_expect = pool_tensors(hp);
+    const auto pool_expect = text ? std::map<std::string, Expect>() : pool_tensors(hp);
     int n_optional = 0;                                              // `arch`, `preproc`, `pre_norm.*` records seen
     int n_pool = 0;                                                  // `attn_pool.*` records seen
     bool pos_no_cls = false;                                         // pos_embed has g^2 rows (no class row)
@@ -208,8 +220,27 @@ static int load_impl(const char *path, vitx_model &m) {
                 set_error("vitx_model_load: tensor 'arch' names activation %g: 0 tanh-GELU, 1 erf-GELU and 2 QuickGELU exist", (double)a[0]); return VITX_ERR_FORMAT;
             }
             if (!(a[1] > 0.0f) || !(a[1] <= 3.402823466e38f)) { set_error("vitx_model_load: tensor 'arch' carries LayerNorm eps %g: it must be finite and positive", (double)a[1]); return VITX_ERR_FORMAT; }
-            if (a[2] != 0.0f || a[3] != 0.0f) { set_error("vitx_model_load: tensor 'arch' has reserved slots {%g, %g}: they must be 0", (double)a[2], (double)a[3]); return VITX_ERR_FORMAT; }
+            if (!text && (a[2] != 0.0f || a[3] != 0.0f)) { set_error("vitx_model_load: tensor 'arch' has reserved slots {%g, %g}: they must be 0", (double)a[2], (double)a[3]); return VITX_ERR_FORMAT; }
+            if (text) {                                              // {.., causal, eos + 1}
+                if (a[2] != 0.0f && a[2] != 1.0f) { set_error("vitx_model_load: tensor 'arch' of a text file names causal %g: 0 (no mask) and 1 (causal) exist", (double)a[2]); return VITX_ERR_FORMAT; }
+                if (!(a[3] >= 0.0f) || a[3] > 16777216.0f || a[3] != floorf(a[3])) { set_error("vitx_model_load: tensor 'arch' of a text file carries eos + 1 = %g: it must be a whole number, 0 for none", (double)a[3]); return VITX_ERR_FORMAT; }
+                m.causal = (int)a[2]; m.eos = (int)a[3] - 1;
+            }
             m.activation = (int)a[0]; hp.eps = a[1];
+            m.index[t.name] = (int)m.tensors.size();
+            m.tensors.push_back(std::move(t));
+            ++n_optional;
+            continue;
+        }
+        if (t.name == "zs" && text) {                                // optional, text files: f32 [4] = {kind, scale, bias, 0}
+            if (m.index.count(t.name)) { set_error("vitx_model_load: duplicate tensor '%s'", t.name.c_str()); return VITX_ERR_FORMAT; }
+            if (ttype != T_F32 || n_dims != 1 || t.ne[0] != 4) { set_error("vitx_model_load: tensor 'zs' must be f32 [4] = {kind, scale, bias, 0}: got type %d, %d dims [%lld, ..]", ttype, n_dims, (long long)t.ne[0]); return VITX_ERR_FORMAT; }
+            t.raw.resize(16);
+            if (fread(t.raw.data(), 1, 16, f) != 16) { set_error("vitx_model_load: tensor '%s' is truncated", t.name.c_str()); return VITX_ERR_IO; }
+            float a[4]; memcpy(a, t.raw.data(), 16);
+            if (a[0] != (float)VITX_ZS_SOFTMAX && a[0] != (float)VITX_ZS_SIGMOID) { set_error("vitx_model_load: tensor 'zs' names kind %g: 0 softmax and 1 sigmoid exist", (double)a[0]); return VITX_ERR_FORMAT; }
+            if (!std::isfinite(a[1]) || !std::isfinite(a[2]) || a[3] != 0.0f) { set_error("vitx_model_load: tensor 'zs' needs a finite scale and bias and a zero last slot"); return VITX_ERR_FORMAT; }
+            m.has_zs = true; m.zs_kind = (int)a[0]; m.zs_scale = a[1]; m.zs_bias = a[2];
             m.index[t.name] = (int)m.tensors.size();
             m.tensors.push_back(std::move(t));
             ++n_optional;
@@ -256,11 +287,12 @@ static int load_impl(const char *path, vitx_model &m) {
         Expect ex = *known;
         if (is_pool) ++n_pool;
         // attn_pool.latent is [1][1][D] (ggml dims [D, 1, 1]); a model without a class token has a pos_embed of g^2 rows (checked against attn_pool.* below)
-        if (t.name == "pos_embed" && t.ne[1] == ex.ne[1] - 1 && t.ne[1] >= 1) { ex.ne[1] -= 1; pos_no_cls = true; }
+        if (t.name == "token_embed.weight" && n_dims == 2) { ex.ne[1] = t.ne[1]; m.vocab = (int)t.ne[1]; }      // V: any row count
+        if (!text && t.name == "pos_embed" && t.ne[1] == ex.ne[1] - 1 && t.ne[1] >= 1) { ex.ne[1] -= 1; pos_no_cls = true; }
         // ViTSTR files (extensions/vitstr.cpp/vitstr.cpp:482) carry a ONE-channel patch kernel [P, P, 1, D]: same format otherwise
         if (t.name == "patch_embed.proj.weight" && t.ne[2] == 1 && t.ne[0] == ex.ne[0] && t.ne[1] == ex.ne[1] && t.ne[3] == ex.ne[3]) { ex.ne[2] = 1; m.in_chans = 1; }
         // a head over concat(cls, mean of the patch tokens) has rows of 2 D (VITX_POOL_CLS_MEAN); any other row length fails the shape check below
-        if (t.name == "head.weight" && t.ne[0] == 2 * ex.ne[0] && t.ne[1] == ex.ne[1] && t.ne[2] == 1 && t.ne[3] == 1) { ex.ne[0] *= 2; m.head_pool = VITX_POOL_CLS_MEAN; }
+        if (!text && t.name == "head.weight" && t.ne[0] == 2 * ex.ne[0] && t.ne[1] == ex.ne[1] && t.ne[2] == 1 && t.ne[3] == 1) { ex.ne[0] *= 2; m.head_pool = VITX_POOL_CLS_MEAN; }
         const int64_t want = ex.ne[0] * ex.ne[1] * ex.ne[2] * ex.ne[3];
         if (t.nelements() != want) { set_error("vitx_model_load: tensor '%s' has wrong size in model file: got %lld, expected %lld", t.name.c_str(), (long long)t.nelements(), (long long)want); return VITX_ERR_FORMAT; }
         if (t.ne[0] != ex.ne[0] || t.ne[1] != ex.ne[1] || t.ne[2] != ex.ne[2] || t.ne[3] != ex.ne[3]) {
@@ -285,6 +317,17 @@ static int load_impl(const char *path, vitx_model &m) {
         return VITX_ERR_FORMAT;
     }
     m.has_pre_norm = m.find("pre_norm.weight") != nullptr;
+    if (text) {
+        // a text tower: every expected tensor and `arch`; nothing an image front or head brings
+        for (const auto &kv : expect)
+            if (!m.find(kv.first)) { set_error("vitx_model_load: text-tower file: tensor '%s' is missing", kv.first.c_str()); return VITX_ERR_FORMAT; }
+        if (!m.find("arch")) { set_error("vitx_model_load: text-tower file: tensor 'arch' = {activation, eps, causal, eos + 1} is missing"); return VITX_ERR_FORMAT; }
+        for (const char *n : {"pre_norm.weight", "preproc", "reg_token"})
+            if (m.find(n)) { set_error("vitx_model_load: text-tower file: tensor '%s' belongs to image files", n); return VITX_ERR_FORMAT; }
+        if (m.eos >= m.vocab) { set_error("vitx_model_load: text-tower file: eos token %d is not below the vocabulary size %d", m.eos, m.vocab); return VITX_ERR_FORMAT; }
+        if (m.tensors.size() != expect.size() + (size_t)n_optional) { set_error("vitx_model_load: model file has %d tensors, but %d tensors were expected", (int)m.tensors.size(), (int)(expect.size() + (size_t)n_optional)); return VITX_ERR_FORMAT; }
+        return VITX_OK;
+    }
     if (m.has_preproc && m.in_chans == 1) { set_error("vitx_model_load: tensor 'preproc' in a one-channel (ViTSTR) file: its preprocessing is fixed"); return VITX_ERR_FORMAT; }
     if (!m.has_preproc) m.preproc = pp_default(hp.img_size);
     // the attention-pooling head: all thirteen tensors, no class or register token, a position table without a class row -- or none of it
@@ -338,6 +381,22 @@ uint64_t vitx_model_uid(const vitx_model *m) { return m ? m->uid : 0; }
 int vitx_model_hparams(const vitx_model *m, vitx_hparams *out) {
     if (!m || !out) return VITX_ERR_ARG;
     *out = m->hp; return VITX_OK;
+}
+int vitx_model_kind(const vitx_model *m) { return m ? m->kind : 0; }
+int vitx_model_text_info(const vitx_model *m, int *V, int *T, int *causal, int *eos) {
+    if (!m || m->kind != VITX_KIND_TEXT) { vitx::set_error("vitx_model_text_info: not a text-tower model"); return VITX_ERR_ARG; }
+    if (V) *V = m->vocab;
+    if (T) *T = m->hp.img_size;
+    if (causal) *causal = m->causal;
+    if (eos) *eos = m->eos;
+    return VITX_OK;
+}
+int vitx_model_text_zs(const vitx_model *m, int *kind, float *scale, float *bias) {
+    if (!m || !m->has_zs) return 0;
+    if (kind) *kind = m->zs_kind;
+    if (scale) *scale = m->zs_scale;
+    if (bias) *bias = m->zs_bias;
+    return 1;
 }
 int vitx_model_num_labels(const vitx_model *m) { return m ? (int)m->id2label.size() : 0; }
 int vitx_model_in_channels(const vitx_model *m) { return m ? m->in_chans : 0; }

@@ -38,6 +38,14 @@ struct vitx_model {
     bool has_pre_norm = false;                        // `pre_norm.weight` / `pre_norm.bias` [D]: LayerNorm of every token row in front of layer 0
     bool has_preproc = false;                         // `preproc` [16]: the model's own preprocessing (include/vitx.h); without it `preproc` is the reference default
     vitx_preproc preproc;
+    // a text-tower file (patch_size == 0; include/vitx.h "the text tower"): hp.img_size = T, hp.num_classes = E
+    int kind = VITX_KIND_IMAGE;
+    int vocab = 0;                                    // V, token_embed.weight's row count
+    int causal = 0;                                   // arch[2]
+    int eos = -1;                                     // arch[3] - 1: the EOS token id whose first position is pooled; -1: the last position
+    bool has_zs = false;                              // `zs` [4] = {kind, scale, bias, 0}
+    int zs_kind = 0;
+    float zs_scale = 1.0f, zs_bias = 0.0f;
     std::map<int, std::string> id2label;
     std::vector<vitx::HostTensor> tensors;            // file order
     std::map<std::string, int> index;                 // name -> position

@@ -305,6 +305,32 @@ int vitx_op_zeroshot(int dtype, const void *d_z, long z_stride, const void *d_ba
     return op_rc("vitx_op_zeroshot", e, VITX_ERR_UNSUPPORTED);
 }
 
+// The text tower's three kernels on their own (include/vitx.h "the text tower").  Every argument check comes before the first device call.
+int vitx_op_text_embed(int table_f16, const void *d_tok, const void *d_pos, const void *d_ids, void *d_x, int n, int T, int D, void *stream) {
+    if (!d_tok || !d_pos || !d_ids || !d_x || n <= 0 || T <= 0 || D <= 0 || D % 8) { set_error("vitx_op_text_embed: invalid argument (D %% 8 == 0)"); return VITX_ERR_ARG; }
+    for (const void *p : {d_tok, d_pos, (const void *)d_x})
+        if ((uintptr_t)p % 16) { set_error("vitx_op_text_embed: pointers must be 16-byte aligned"); return VITX_ERR_ARG; }
+    return op_rc("vitx_op_text_embed", launch_text_embed(table_f16 != 0, d_tok, (const float *)d_pos, (const int *)d_ids, (float *)d_x, n, T, D, (hipStream_t)stream), VITX_ERR_ARG);
+}
+int vitx_op_text_pool(int dtype, const void *d_x, const void *d_pooled, const void *d_w, const void *d_b, void *d_z, int n, int T, int D, float eps, void *stream) {
+    if (!d_x || !d_pooled || !d_w || !d_b || !d_z || n <= 0 || T <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_text_pool: invalid argument"); return VITX_ERR_ARG; }
+    if (!layernorm_supports(D)) { set_error("vitx_op_text_pool: hidden size %d has no LayerNorm instantiation", D); return VITX_ERR_UNSUPPORTED; }
+    return op_rc("vitx_op_text_pool", launch_text_pool(dtype, (const float *)d_x, (const int *)d_pooled, (const float *)d_w, (const float *)d_b, d_z, n, n, T, D, eps, (hipStream_t)stream));
+}
+// The generic head-dim kernel at ANY head dim, 64 included (where the dispatcher prefers the tuned families): tools/text_cost.py measures the text
+// attention against it.  Only enqueues.
+int vitx_op_attention_generic(int dtype, const void *d_qkv, void *d_out, int n_img, int N, int D, int H, void *stream) {
+    if (!d_qkv || !d_out || n_img <= 0 || N <= 0 || D <= 0 || H <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_attention_generic: invalid argument"); return VITX_ERR_ARG; }
+    if (!attention_generic_supports(D, H)) { set_error("vitx_op_attention_generic: head_dim must be a multiple of 8 up to 128 (D %d, H %d)", D, H); return VITX_ERR_UNSUPPORTED; }
+    return op_rc("vitx_op_attention_generic", launch_attention_generic(dtype, d_qkv, d_out, n_img, N, D, H, (hipStream_t)stream));
+}
+int vitx_op_attention_text(int dtype, const void *d_qkv, void *d_out, int n, int T, int D, int H, int causal, void *stream) {
+    if (!d_qkv || !d_out || n <= 0 || T <= 0 || D <= 0 || H <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_attention_text: invalid argument"); return VITX_ERR_ARG; }
+    if (!attention_text_supports(T, D, H)) { set_error("vitx_op_attention_text: 1 <= T <= %d and a head dim that is a multiple of 8 up to 128 (T %d, D %d, H %d)", VITX_TEXT_MAX_TOKENS, T, D, H); return VITX_ERR_UNSUPPORTED; }
+    if (!tuning_for_device(-1)) { set_error("vitx_op_attention_text: kernel bring-up failed"); return VITX_ERR_HIP; }
+    return op_rc("vitx_op_attention_text", launch_attention_text(dtype, d_qkv, d_out, n, T, D, H, causal, (hipStream_t)stream));
+}
+
 int vitx_preprocess_ex_device_supports(const vitx_preproc *pp, int nx, int ny) { return pp && preprocess_ex_supports(*pp, nx, ny) ? 1 : 0; }
 int vitx_preprocess_ex_device(const vitx_preproc *pp, const void *d_hwc, int n, int nx, int ny, void *d_out, void *stream) {
     if (!pp || !d_hwc || !d_out || n <= 0) { set_error("vitx_preprocess_ex_device: invalid argument"); return VITX_ERR_ARG; }

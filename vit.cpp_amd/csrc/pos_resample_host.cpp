@@ -50,6 +50,7 @@ extern "C" int vitx_model_resize_file(const char *path_in, const char *path_out,
     vitx_model *m = nullptr;
     int rc = vitx_model_load(path_in, &m);
     if (rc != VITX_OK) return rc;
+    if (m->kind != VITX_KIND_IMAGE) { vitx_model_free(m); set_error("vitx_model_resize_file: '%s' is a text-tower file: it has no image size", path_in); return VITX_ERR_ARG; }
     const vitx_hparams hp = m->hp;
     const int in_chans = m->in_chans;
     const bool map_head = m->head_pool == VITX_POOL_MAP;

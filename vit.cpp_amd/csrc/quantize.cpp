@@ -89,8 +89,9 @@ static bool ends_with(const std::string &s, const char *suffix) {
     return s.size() >= n && s.compare(s.size() - n, n, suffix) == 0;
 }
 // the reference's selection (quantize.cpp:207-223) over the tensors it knows; the attention-pooling head (attn_pool.*, about 5 % of a base
-// model) is no tensor of the reference's and is copied through byte for byte
-static bool is_quantised(const HostTensor &t) { return t.n_dims == 2 && ends_with(t.name, "weight") && t.name.compare(0, 10, "attn_pool.") != 0; }
+// model) is no tensor of the reference's and is copied through byte for byte; so is a text tower's token table (token_embed.weight: a gather
+// reads it, no GEMM), with its pos_embed, arch and zs
+static bool is_quantised(const HostTensor &t) { return t.n_dims == 2 && ends_with(t.name, "weight") && t.name.compare(0, 10, "attn_pool.") != 0 && t.name != "token_embed.weight"; }
 
 }  // namespace vitx
 

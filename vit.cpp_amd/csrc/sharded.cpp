@@ -140,6 +140,7 @@ extern "C" {
 int vitx_group_create(const vitx_model *m, const int *devices, int n_devices, int max_batch_per_device, int dtype, vitx_group **out) {
     if (!m || !devices || !out || n_devices <= 0 || max_batch_per_device <= 0) { set_error("vitx_group_create: invalid argument"); return VITX_ERR_ARG; }
     *out = nullptr;
+    if (m->kind != VITX_KIND_IMAGE) { set_error("vitx_group_create: a text-tower model takes a text context (vitx_text_create), not a group"); return VITX_ERR_ARG; }
     for (int i = 0; i < n_devices; ++i)
         for (int j = 0; j < i; ++j)
             if (devices[i] == devices[j]) { set_error("vitx_group_create: device %d listed twice", devices[i]); return VITX_ERR_ARG; }

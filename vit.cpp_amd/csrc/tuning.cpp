@@ -16,6 +16,7 @@ static hipError_t prepare_device_kernels(const Tuning &t) {
     hipError_t e = prepare_gemm(t);
     if (e == hipSuccess) e = prepare_patch_embed();
     if (e == hipSuccess) e = prepare_attention();
+    if (e == hipSuccess) e = prepare_attention_text();
     return e;
 }
 

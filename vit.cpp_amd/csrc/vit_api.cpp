@@ -6,6 +6,7 @@
 
 vit_model::~vit_model() { vitx_model_free(handle); }
 vit_state::~vit_state() { vitx_ctx_free(ctx); }
+vit_text_state::~vit_text_state() { vitx_text_free(ctx); }
 
 // vit.cpp:109-127 -- false + message on stderr when the file cannot be read or decoded
 bool load_image_from_file(const std::string &fname, image_u8 &img) {
@@ -189,6 +190,25 @@ int vit_zeroshot_batch(const vit_model &model, vit_state &state, const image_f32
         if (vitx_topk(probs.data() + (size_t)i * K, K, k, idx.data(), pr.data()) != VITX_OK) { fprintf(stderr, "%s: %s\n", __func__, vitx_last_error()); out.clear(); return 1; }
         for (int j = 0; j < k; ++j) out[i].push_back(std::make_pair(pr[j], (int)idx[j]));
     }
+    return 0;
+}
+
+// No counterpart in the reference: the text embeddings of n tokenised prompts (include/vitx.h "the text tower")
+int vit_text_embed_batch(const vit_model &model, vit_text_state &state, const int32_t *ids, int n, int flags, std::vector<std::vector<float>> &out) {
+    out.clear();
+    if (!model.handle || !ids || n <= 0) { fprintf(stderr, "%s: invalid argument\n", __func__); return 1; }
+    if (vitx_model_kind(model.handle) != VITX_KIND_TEXT) { fprintf(stderr, "%s: this is an image model: it has no text tower\n", __func__); return 1; }
+    if (!state.ctx || state.ctx_model_uid != vitx_model_uid(model.handle) || state.max_prompts < n) {
+        vitx_text_free(state.ctx); state.ctx = nullptr; state.ctx_model_uid = 0;
+        state.max_prompts = std::max(state.max_prompts, n);
+        if (vitx_text_create(model.handle, state.device, state.max_prompts, state.dtype, &state.ctx) != VITX_OK) { fprintf(stderr, "%s: failed to create the context: %s\n", __func__, vitx_last_error()); return 1; }
+        state.ctx_model_uid = vitx_model_uid(model.handle);
+    }
+    const int E = model.hparams.num_classes;
+    std::vector<float> flat((size_t)n * E);
+    if (vitx_text_embed(state.ctx, ids, n, flags, flat.data()) != VITX_OK) { fprintf(stderr, "%s: %s\n", __func__, vitx_last_error()); return 1; }
+    out.resize(n);
+    for (int i = 0; i < n; ++i) out[i].assign(flat.begin() + (size_t)i * E, flat.begin() + (size_t)(i + 1) * E);
     return 0;
 }
 

@@ -17,9 +17,12 @@ namespace {
 // ascending column order, then over the lanes by a butterfly (the same bits in every lane) -- an order that depends on E only.  The rule is
 // VITX_FEAT_L2's (LnRow::l2, ln_row.h); that one walks the LayerNorm tables' column ownership and exists only for their widths, this one
 // takes any E that is a multiple of 64 (a CLIP projection width need not be a hidden size), so the two stay separate functions.
+// (T16 = float: the same rule with the quotient stored as it is -- VITX_TEXT_L2 of a text context, launch_zs_embed_f32)
+template <typename T16> struct ZsVec { typedef typename Elem<T16>::v4 v4; };
+template <> struct ZsVec<float> { typedef f32x4 v4; };
 template <typename T16>
 __global__ __launch_bounds__(256) void zs_embed_kernel(const float *__restrict__ z, long z_stride, T16 *__restrict__ a, int n, int m_pad, int E) {
-    typedef typename Elem<T16>::v4 v4;
+    typedef typename ZsVec<T16>::v4 v4;
     const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= m_pad) return;
     T16 *ar = a + (size_t)row * E;
@@ -106,6 +109,12 @@ hipError_t launch_zs_embed(int dtype, const float *z, long z_stride, void *a, in
     const dim3 grid((m_pad + 3) / 4), blk(256);
     if (dtype == DT_F16) hipLaunchKernelGGL(zs_embed_kernel<_Float16>, grid, blk, 0, stream, z, z_stride, (_Float16 *)a, n, m_pad, E);
     else hipLaunchKernelGGL(zs_embed_kernel<__bf16>, grid, blk, 0, stream, z, z_stride, (__bf16 *)a, n, m_pad, E);
+    return hipGetLastError();
+}
+
+hipError_t launch_zs_embed_f32(const float *z, long z_stride, float *a, int n, int E, hipStream_t stream) {
+    if (n <= 0 || E <= 0 || E % 64 || z_stride < E || z_stride % 4 || (const void *)z == (const void *)a) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(zs_embed_kernel<float>, dim3((n + 3) / 4), dim3(256), 0, stream, z, z_stride, a, n, n, E);
     return hipGetLastError();
 }
 

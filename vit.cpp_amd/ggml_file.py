@@ -308,7 +308,7 @@ def write_model(path: str, hp: HParams, tensors: Dict[str, np.ndarray], id2label
             if ftype == 0 and not (patch_f16 and name == "patch_embed.proj.weight"):
                 keep_f32 = True
             ttype = F32 if keep_f32 else F16
-            if not keep_f32 and ftype in QUANTIZERS and data.ndim == 2 and name.endswith("weight") and not name.startswith("attn_pool."):
+            if not keep_f32 and ftype in QUANTIZERS and data.ndim == 2 and name.endswith("weight") and not name.startswith("attn_pool.") and name != "token_embed.weight":
                 ttype = ftype
             nb = name.encode("utf-8")
             f.write(struct.pack("<iii", data.ndim, len(nb), ttype))

@@ -117,6 +117,21 @@ struct vit_zeroshot_bank {
 // returning; state.prediction holds the file's own class "probabilities" of the same forward.  0 ok / 1 failure.
 int vit_zeroshot_batch(const vit_model &model, vit_state &state, const image_f32 *imgs, int n, const vit_zeroshot_bank &bank,
                        std::vector<std::vector<std::pair<float, int>>> &out, int topk = 5);
+// NEW, no counterpart in the reference: the text tower of a CLIP / SigLIP checkpoint (include/vitx.h "the text tower").  `model` is a text-tower
+// file (vitx_model_kind == VITX_KIND_TEXT; hparams.img_size is its context length T, hparams.num_classes its embedding width E).  ids: n
+// tokenised prompts [n][T] -- there is no tokenizer in the engine; out[i] = prompt i's E floats; flags 0 or VITX_TEXT_L2.  0 ok / 1 failure.
+struct vit_text_state {                   // per-caller mutable scratch of the text tower, the analogue of vit_state
+    vitx_text *ctx = nullptr;             // created lazily on `device`, grown on demand
+    uint64_t ctx_model_uid = 0;
+    int device = 0;
+    int max_prompts = 1;
+    int dtype = VITX_F16;                 // VITX_F16 or VITX_BF16
+    vit_text_state() = default;
+    vit_text_state(const vit_text_state &) = delete;
+    vit_text_state &operator=(const vit_text_state &) = delete;
+    ~vit_text_state();
+};
+int vit_text_embed_batch(const vit_model &model, vit_text_state &state, const int32_t *ids, int n, int flags, std::vector<std::vector<float>> &out);
 // ---- the ViTSTR scene-text extension (extensions/vitstr.cpp).  It is a separate program in the reference that re-uses the names
 // vit_image_preprocess / vit_predict with different bodies (vitstr.h:115-119); here both programs live in one library, so the
 // extension's two functions carry a vitstr_ prefix.  vit_model_load is shared: a file whose patch kernel has ONE input channel is
