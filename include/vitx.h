@@ -391,6 +391,39 @@ int vitx_pos_embed_resample(const float *pos, int gy_in, int gx_in, int D, int g
 int vitx_op_pos_embed_resample(const void *d_pos, int gy_in, int gx_in, int D, int gy_out, int gx_out, int interp, void *d_out, void *stream);
 int vitx_model_resize_file(const char *path_in, const char *path_out, int img_size, int interp);
 
+/* ---- rotary position embeddings (DINOv3-class models) ---------------------------- */
+/* A file may carry `rope`, f32 [4] = {kind, theta, 0, 0}: the position signal is then a rotation of q and k of the patch tokens in every layer, a
+ * function of the grid and not a table.  kind 1 (VITX_ROPE_DINOV3_AXIAL, the only one) is DINOv3's: normalised patch-centre coordinates, half-split
+ * rotation, prefix tokens (class token, registers) not rotated; theta is the base (100 for the published models).  The loader refuses
+ * (VITX_ERR_FORMAT) any other kind, a theta that is not finite and positive, non-zero reserved slots, a head dim that is no multiple of 4, `rope` in
+ * a text-tower file and `rope` together with attn_pool.*.  Such a file still carries a pos_embed of 1 + g^2 rows, ALL ZERO: the patch embedding, the
+ * resampler and vitx_model_resize_file stay as they are (a resampled zero table is a zero table), at the price of 0.6 MB in a ViT-B file.
+ * vitx_quantize_file and vitx_model_resize_file copy `rope` byte for byte.  A file without `rope` loads, runs and hashes exactly as before.
+ * The table (host, double, once per context), hd = head dim, outputs [gh * gw][hd / 2], row-major over (y, x):
+ *   cy = 2 (y + 0.5) / gh - 1, cx = 2 (x + 0.5) / gw - 1;  inv_j = theta^(-4 j / hd) for j < hd / 4;
+ *   angle of column j < hd / 4: 2 pi cy inv_j;  of column hd / 4 + j: 2 pi cx inv_j;  cos / sin rounded once to f32.
+ * (HuggingFace tiles these hd / 2 angles twice: columns j and j + hd / 2 of a head share one cos / sin.)  Grids may be rectangular here, as in the two
+ * resampler entry points; contexts stay square.  A context of such a file builds the table for ITS grid (vitx_ctx_options::img_size) at creation and
+ * keeps it with the context, not in the shared weight set; so a context at another img_size is exact.  pos_interp is validated but has no effect.
+ * The rotation (rope.hip), in place on the qkv GEMM's output, after that GEMM and before everything that reads q or k (attention, the class-row tail,
+ * attention maps and rollout): for token t >= T (patch p = t - T), s in {q, k}, head h, j < hd / 2, a = element h hd + j, b = element h hd + hd / 2 + j,
+ *   a' = a cos[p][j] - b sin[p][j];  b' = b cos[p][j] + a sin[p][j]
+ * each product rounded to f32, then the sum (no FMA), the result rounded RNE to the operand type: bf16, one fp16 plane (f16_fast_attention), or the
+ * parity mode's two fp16 planes (read as f32(hi) + f32(lo) / 2048, split again as the qkv GEMM splits: hi = RNE(v), lo = RNE((v - hi) 2048)).
+ * v columns, prefix rows and rows beyond n_img * N keep their bits; every element has one writer, so the bits do not depend on the batch.
+ * VITX_MXFP8 contexts of such a file: VITX_ERR_UNSUPPORTED at creation.  ViTSTR does not apply.  A context of a file without `rope` launches and
+ * allocates nothing new.
+ *   vitx_model_rope        1 and *kind / *theta (either may be NULL) for a file with `rope`, 0 without (and for NULL)
+ *   vitx_model_rope_table  cos, sin f32 [gh * gw][hd / 2]; VITX_ERR_ARG for NULL, a file without `rope` or a non-positive grid
+ *   vitx_op_rope           the gfx950 kernel on device pointers: d_qkv [n_img * N][3 D] of `dtype` (VITX_F16 / VITX_BF16), lo_off != 0: the lo plane that
+ *                          many ELEMENTS behind (VITX_F16 only, a multiple of 8, at least n_img * N * 3 * D), d_cos / d_sin f32 [N - prefix][hd / 2].
+ *                          Every check comes before the launch: NULL, non-positive sizes, prefix outside 0 .. N, a bad lo plane, both planes beyond
+ *                          0xf0000000 bytes: VITX_ERR_ARG; D no multiple of H or an odd head dim: VITX_ERR_UNSUPPORTED.  Only enqueues on `stream`. */
+enum vitx_rope_kind { VITX_ROPE_NONE = 0, VITX_ROPE_DINOV3_AXIAL = 1 };
+int vitx_model_rope(const vitx_model *m, int *kind, float *theta);
+int vitx_model_rope_table(const vitx_model *m, int gh, int gw, float *cos_out, float *sin_out);
+int vitx_op_rope(int dtype, void *d_qkv, long lo_off, const void *d_cos, const void *d_sin, int n_img, int N, int prefix, int D, int H, void *stream);
+
 /* ---- several GPUs in one process (north_star: batch shards + one RCCL gather) -- */
 /* One context (replicated weights) and one PERSISTENT host thread per listed device (created here, parked between calls).  Images are
  * cut into contiguous shards, run concurrently, and the results are all-gathered with ONE ncclAllGather over RCCL.
@@ -425,7 +458,7 @@ int vitx_topk(const float *probs, int num_classes, int k, int32_t *out_idx, floa
  * events on the launch stream and the sub-batches run back to back on that one
  * stream (exclusive per-kernel durations); vitx_profile_read() synchronises, folds
  * the event pairs into per-kernel-class totals and clears the pool. */
-#define VITX_PROF_MAX_CLASSES 16
+#define VITX_PROF_MAX_CLASSES 24
 typedef struct vitx_prof_entry {
     const char *name;     /* kernel class, e.g. "gemm_fc1_gelu" */
     int32_t launches;

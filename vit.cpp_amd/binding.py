@@ -55,6 +55,7 @@ EXPORTS = [
     "vitx_zeroshot_set", "vitx_zeroshot_classes", "vitx_zeroshot_images", "vitx_zeroshot_read", "vitx_zeroshot_device", "vitx_zeroshot_max_classes", "vitx_op_zeroshot",
     "vitx_model_kind", "vitx_model_text_info", "vitx_model_text_zs", "vitx_text_create", "vitx_text_free", "vitx_text_embed", "vitx_text_embed_device", "vitx_text_shares_weights", "vitx_text_check_ids",
     "vitx_op_text_embed", "vitx_op_text_pool", "vitx_op_attention_text", "vitx_op_attention_generic",
+    "vitx_model_rope", "vitx_model_rope_table", "vitx_op_rope",
 ]
 
 
@@ -241,6 +242,10 @@ def lib():
             L.vitx_op_text_pool.argtypes = [ip, vp, vp, vp, vp, vp, ip, ip, ip, C.c_float, vp]
             L.vitx_op_attention_text.argtypes = [ip, vp, vp, ip, ip, ip, ip, ip, vp]
             L.vitx_op_attention_generic.argtypes = [ip, vp, vp, ip, ip, ip, ip, vp]
+        if hasattr(L, "vitx_op_rope"):
+            L.vitx_model_rope.argtypes = [vp, C.POINTER(ip), C.POINTER(C.c_float)]
+            L.vitx_model_rope_table.argtypes = [vp, ip, ip, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+            L.vitx_op_rope.argtypes = [ip, vp, C.c_long, vp, vp, ip, ip, ip, ip, ip, vp]
         _lib = L
     return _lib
 
@@ -309,6 +314,22 @@ class Model:
         u = np.empty((hp.num_attention_heads, hp.hidden_size), np.float32)
         check(lib().vitx_model_pool_query(self._h, u.ctypes.data_as(C.POINTER(C.c_float))), "vitx_model_pool_query")
         return u
+
+    @property
+    def rope(self):
+        """(kind, theta) of a file with a `rope` tensor (rotary position embeddings on q and k of the patch tokens), or None."""
+        k, t = C.c_int(), C.c_float()
+        return (k.value, t.value) if lib().vitx_model_rope(self._h, C.byref(k), C.byref(t)) else None
+
+    def rope_table(self, grid) -> Tuple[np.ndarray, np.ndarray]:
+        """vitx_model_rope_table: (cos, sin), each f32 [gh * gw, head_dim / 2], for a grid g or (gh, gw); row-major over (y, x)."""
+        gh, gw = _grid(grid)
+        hp = self.hparams
+        half = hp.hidden_size // hp.num_attention_heads // 2
+        fp = C.POINTER(C.c_float)
+        cos = np.empty((max(gh, 0) * max(gw, 0), half), np.float32); sin = np.empty_like(cos)
+        check(lib().vitx_model_rope_table(self._h, gh, gw, cos.ctypes.data_as(fp), sin.ctypes.data_as(fp)), "vitx_model_rope_table")
+        return cos, sin
 
     @property
     def activation(self) -> int:                                                    # ACT_GELU_TANH / ACT_GELU_ERF / ACT_QUICK_GELU (the file's `arch`)
@@ -710,8 +731,8 @@ class Context:
         return float(v.value)
 
     def profile_read(self):
-        arr = (ProfEntry * 16)(); n = C.c_int()
-        check(lib().vitx_profile_read(self._h, arr, 16, C.byref(n)), "vitx_profile_read")
+        arr = (ProfEntry * 24)(); n = C.c_int()      # VITX_PROF_MAX_CLASSES
+        check(lib().vitx_profile_read(self._h, arr, len(arr), C.byref(n)), "vitx_profile_read")
         return [dict(name=arr[i].name.decode(), launches=arr[i].launches, total_ms=arr[i].total_ms, flops=arr[i].flops, bytes=arr[i].bytes, busy_ms=arr[i].busy_ms) for i in range(n.value)]
 
 
@@ -878,6 +899,11 @@ def op_attention_pool(d_x: int, row_stride: int, img_stride: int, d_ln_w: int, d
     """vitx_op_attention_pool: the pooling kernel of the attention-pooling head (device pointers, strides in floats): M [n_img, H, D] f32 and,
     with d_p, the probabilities [n_img, H, N] f32."""
     check(lib().vitx_op_attention_pool(d_x, row_stride, img_stride, d_ln_w, d_ln_b, eps, d_u, d_M, d_p or None, n_img, N, D, H, stream or None), "vitx_op_attention_pool")
+
+
+def op_rope(dtype: int, d_qkv: int, d_cos: int, d_sin: int, n_img: int, N: int, prefix: int, D: int, H: int, lo_off: int = 0, stream: int = 0) -> None:
+    """vitx_op_rope: rotary position embeddings in place on d_qkv [n_img * N, 3 D] (lo_off: the parity mode's lo plane); cos / sin f32 [N - prefix, head_dim / 2].  Only enqueues."""
+    check(lib().vitx_op_rope(dtype, d_qkv, lo_off, d_cos, d_sin, n_img, N, prefix, D, H, stream), "vitx_op_rope")
 
 
 def op_text_embed(table_f16: bool, d_tok: int, d_pos: int, d_ids: int, d_x: int, n: int, T: int, D: int, stream: int = 0) -> None:

@@ -14,6 +14,8 @@ What is converted
            Dinov2WithRegistersModel.  Register tokens, folded LayerScale, the head over concat(cls, mean of the patch tokens).
   CLIP     CLIPVisionModelWithProjection, CLIPModel (its vision tower and visual_projection); with --no-head a CLIPVisionModel.
   SigLIP   SiglipVisionModel, SiglipModel (its vision tower): no class token, the attention-pooling head.
+  DINOv3   DINOv3ViTModel (ViT-S/B/L): class token, register tokens, folded LayerScale, and rotary position embeddings -- the `rope` tensor,
+           f32 [4] = {1, rope_theta, 0, 0}, beside an all-zero pos_embed (include/vitx.h "rotary position embeddings").  A backbone: the zero head.
   timm     a VisionTransformer state_dict (--timm-state-dict model.pth, no `timm` import): convert_timm_state_dict.
 
 Every model's settings travel with it.  The MLP activation (`hidden_act`: gelu -> erf-GELU, gelu_pytorch_tanh / gelu_new -> tanh-GELU, quick_gelu ->
@@ -29,7 +31,7 @@ f32(255.0 * mean).  --no-preproc writes the file without it: the reference's str
 processor: the --pp-* options state one (cli_preproc); with none of them no tensor is written and the file keeps the reference's bytes.
 
 What is refused, by name: an activation the forward path does not evaluate; an MLP that is not 4 x hidden (SigLIP SO400M's 4304); a head_dim that
-is no multiple of 8 up to 128; qkv_bias=False; SwiGLU, qk-norm, fc_norm and distillation tokens; a SigLIP tower without its pooling head
+is no multiple of 8 up to 128; qkv_bias=False; SwiGLU, DINOv3's gated MLP (use_gated_mlp, ViT-H+ and 7B), qk-norm, fc_norm and distillation tokens; a SigLIP tower without its pooling head
 (vision_use_head = False), SiglipForImageClassification (a mean-pool classifier: no slot), Siglip2VisionModel (NaFlex: its patch embedding is a
 Linear); --no-head on a ViT, and a model without classifier or projection converted without it; --vitstr on anything but a one-channel ViT; in a
 preprocessor_config whatever the engine's preprocess cannot honour -- another resample code, do_resize off, padding, a channel flip, a final size
@@ -196,6 +198,8 @@ VIT_BLOCKS_V4 = BlockNames("vit.encoder.layer.{i}.", _HF_QKV, "layernorm_before"
 VIT_BLOCKS_V5 = BlockNames("vit.layers.{i}.", ("attention.q_proj", "attention.k_proj", "attention.v_proj"), "layernorm_before", "attention.o_proj", "layernorm_after",
                            "mlp.fc1", "mlp.fc2")
 DINOV2_BLOCKS = BlockNames("encoder.layer.{i}.", _HF_QKV, "norm1", "attention.output.dense", "norm2", "mlp.fc1", "mlp.fc2", "layer_scale1.lambda1", "layer_scale2.lambda1")
+DINOV3_BLOCKS = BlockNames("layer.{i}.", ("attention.q_proj", "attention.k_proj", "attention.v_proj"), "norm1", "attention.o_proj", "norm2", "mlp.up_proj", "mlp.down_proj",
+                           "layer_scale1.lambda1", "layer_scale2.lambda1")
 CLIP_BLOCKS = BlockNames("encoder.layers.{i}.", ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"), "layer_norm1", "self_attn.out_proj", "layer_norm2",
                          "mlp.fc1", "mlp.fc2")          # SigLIP's too
 
@@ -323,6 +327,46 @@ def clip_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, no_head: bool = Fals
     return _f32(out)
 
 
+def dinov3_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg) -> Dict[str, np.ndarray]:
+    """An HF DINOv3ViTModel state dict (numpy arrays) under the file's names and order.  The position signal is rotary (include/vitx.h "rotary
+    position embeddings"): `rope` = {1, rope_theta, 0, 0} in front, and a pos_embed [1][1 + g^2][D] of zeros at the config's image_size, so that the
+    patch embedding and the resampler stay what they are.  register_tokens -> `reg_token`; LayerScale is folded; key_bias=False (the published
+    models) becomes a zero k bias; mask_token is dropped.  The blocks live under `model.layer.N.` (transformers 5.15; `layer.N.` is accepted too).
+    The gated MLP of ViT-H+ / 7B (use_gated_mlp) and an MLP that is not 4 x hidden are refused.  A backbone: the zero head, whose VITX_FEAT_CLS
+    is HF's pooler_output."""
+    if getattr(cfg, "use_gated_mlp", False):
+        raise ValueError("use_gated_mlp: the gated (SwiGLU) MLP of DINOv3 ViT-H+ / 7B is not supported (the forward path has the GELU MLP only)")
+    D = int(cfg.hidden_size)
+    _require_mlp_4x(cfg, "intermediate_size", 4 * D)
+    if "embeddings.cls_token" not in sd:
+        raise ValueError("not a DINOv3 state dict: embeddings.cls_token is missing")
+    pre = next((p for p in ("model.", "") if p + "layer.0.attention.q_proj.weight" in sd), None)
+    if pre is None:
+        raise ValueError("not a DINOv3 state dict: layer.0.attention.q_proj.weight is missing")
+    theta = np.float32(getattr(cfg, "rope_theta", 100.0))
+    if not np.isfinite(theta) or not theta > 0:
+        raise ValueError(f"rope_theta {theta}: it must be finite and positive")
+    if (D // cfg.num_attention_heads) % 4:
+        raise ValueError(f"head_dim {D // cfg.num_attention_heads}: rotary position embeddings need a multiple of 4")
+    sd = dict(sd)
+    for i in range(cfg.num_hidden_layers):                            # a projection without bias (key_bias=False) has a zero bias
+        for n in DINOV3_BLOCKS.qkv:
+            k = f"{pre}layer.{i}.{n}"
+            if k + ".weight" in sd and k + ".bias" not in sd:
+                sd[k + ".bias"] = np.zeros((int(np.shape(sd[k + ".weight"])[0]),), np.float32)
+    g = int(cfg.image_size) // int(cfg.patch_size)
+    e = "embeddings."
+    out = {"rope": np.array([1, theta, 0, 0], np.float32), "cls_token": sd[e + "cls_token"]}
+    if e + "register_tokens" in sd and int(np.shape(sd[e + "register_tokens"])[1]) > 0:
+        out["reg_token"] = sd[e + "register_tokens"]
+    out["pos_embed"] = np.zeros((1, 1 + g * g, D), np.float32)
+    _put(out, "patch_embed.proj", sd, e + "patch_embeddings")
+    map_blocks(out, sd, DINOV3_BLOCKS, cfg.num_hidden_layers, pre)
+    _put(out, "norm", sd, "norm")
+    _zero_head(out, D)
+    return _f32(out)
+
+
 _POOL_ORDER = ("latent", "q.weight", "q.bias", "kv.weight", "kv.bias", "proj.weight", "proj.bias", "norm.weight", "norm.bias",
                "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")
 
@@ -419,13 +463,14 @@ _VIT = Family("ViT", lambda sd, cfg, no_head: state_dict_to_timm(sd, cfg.num_hid
 _DINOV2 = Family("DINOv2", dinov2_state_dict_to_timm, 1, _config_labels, "optional", ("AutoModelForImageClassification", "AutoModel"))
 _CLIP = Family("CLIP", clip_state_dict_to_timm, 1, lambda cfg, E: {i: f"dim_{i}" for i in range(E)}, "optional", ("CLIPVisionModelWithProjection", "CLIPVisionModel"))
 _SIGLIP = Family("SigLIP", lambda sd, cfg, no_head: siglip_state_dict_to_timm(sd, cfg), 0, None, "never", ("SiglipVisionModel",) * 2)
+_DINOV3 = Family("DINOv3", lambda sd, cfg, no_head: dinov3_state_dict_to_timm(sd, cfg), 1, None, "never", ("DINOv3ViTModel",) * 2)
 # text towers (convert_hf_text_model): no patch grid (prefix_rows is not read), no labels -- the "classes" are the projection's columns --, always with the projection
 _CLIP_TEXT = Family("CLIP text", clip_text_state_dict, 0, lambda cfg, E: {}, "always", ("CLIPTextModelWithProjection",) * 2)
 _SIGLIP_TEXT = Family("SigLIP text", siglip_text_state_dict, 0, lambda cfg, E: {}, "always", ("SiglipTextModel",) * 2)
 _TWO_TOWERS = ("clip", "siglip")          # converted as their vision tower (config.vision_config); convert_hf_text_model takes config.text_config
 # by model_type, the vision tower's or, for main(), the checkpoint's; any other model_type is taken for a ViT
 FAMILIES = {"vit": _VIT, "dinov2": _DINOV2, "dinov2_with_registers": _DINOV2, "clip_vision_model": _CLIP, "clip": _CLIP, "siglip_vision_model": _SIGLIP, "siglip": _SIGLIP,
-            "clip_text_model": _CLIP_TEXT, "siglip_text_model": _SIGLIP_TEXT}
+            "dinov3_vit": _DINOV3, "clip_text_model": _CLIP_TEXT, "siglip_text_model": _SIGLIP_TEXT}
 
 
 def _family_tensors(model, cfg, fam, no_head: bool, head_dim_note: str = ""):

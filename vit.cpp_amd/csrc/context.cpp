@@ -159,6 +159,8 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
         set_error("vitx_ctx_create_ex: a model with the attention-pooling head stays at the file's img_size (%d): its position table has no class row and no resampling path yet", m->hp.img_size);
         return VITX_ERR_UNSUPPORTED;
     }
+    if (m->rope_kind && dtype == VITX_MXFP8) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts do not take models with rotary position embeddings"); return VITX_ERR_UNSUPPORTED; }
+    if (m->rope_kind && m->in_chans == 1) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes no rotary position embeddings"); return VITX_ERR_UNSUPPORTED; }
     if (m->in_chans == 1 && (m->has_pre_norm || m->activation != VITX_ACT_GELU_TANH)) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes neither a pre-norm nor an activation other than tanh-GELU"); return VITX_ERR_UNSUPPORTED; }
     if (dtype == VITX_MXFP8 && m->activation != VITX_ACT_GELU_TANH) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts evaluate tanh-GELU only (this model's activation: %d)", m->activation); return VITX_ERR_UNSUPPORTED; }
     if (m->in_chans == 1 && img_size != m->hp.img_size) { set_error("vitx_ctx_create_ex: a ViTSTR context stays at the file's img_size (%d)", m->hp.img_size); return VITX_ERR_UNSUPPORTED; }
@@ -382,6 +384,15 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
         if ((rc = c->dmalloc((void **)&c->pos_own, (size_t)(c->g * c->g + 1) * D * 4, false))) return rc;      // (never a VITX_POOL_MAP model: configure refuses it)
         HIP_TRY(launch_pos_resample(c->wset->pos, g_in, g_in, D, c->g, c->g, opt.pos_interp, c->pos_own, c->stream));
         c->pos = c->pos_own;                 // (the hipDeviceSynchronize at the end of the creation covers the launch)
+    }
+    // rotary position embeddings: the table of THIS context's grid, built on the host in double and uploaded once (cos, then sin)
+    if (m->rope_kind) {
+        const size_t tab = (size_t)c->g * c->g * (D / c->H / 2);
+        std::vector<float> h(2 * tab);
+        if ((rc = vitx_model_rope_table(m, c->g, c->g, h.data(), h.data() + tab))) return rc;
+        if ((rc = c->dmalloc((void **)&c->rope_cos, 2 * tab * 4, false))) return rc;
+        c->rope_sin = c->rope_cos + tab;
+        HIP_TRY(hipMemcpy(c->rope_cos, h.data(), 2 * tab * 4, hipMemcpyHostToDevice));
     }
 
     // sub-batch slices (vitx_ctx_options::streams; 1 = single stream).  Small contexts stay single-slice.

@@ -23,11 +23,11 @@ namespace vitx {
 
 enum ProfClass {
     PC_GEMM_PATCH = 0, PC_LAYERNORM, PC_GEMM_QKV, PC_ATTENTION, PC_GEMM_PROJ, PC_GEMM_FC1, PC_GEMM_FC2,
-    PC_GEMM_HEAD, PC_SOFTMAX, PC_DEQUANT, PC_ATTENTION_CLS, PC_GEMM_TAIL, PC_ATTN_MAP, PC_FEATURES, PC_HEAD_POOL, PC_ZEROSHOT, PC_COUNT
+    PC_GEMM_HEAD, PC_SOFTMAX, PC_DEQUANT, PC_ATTENTION_CLS, PC_GEMM_TAIL, PC_ATTN_MAP, PC_FEATURES, PC_HEAD_POOL, PC_ZEROSHOT, PC_ROPE, PC_COUNT
 };
 inline const char *const kProfNames[PC_COUNT] = {"patch_embed", "layernorm", "gemm_qkv_bias", "attention", "gemm_proj_resid",
                                     "gemm_fc1_gelu", "gemm_fc2_resid", "gemm_head", "softmax", "dequant_weights", "attention_cls", "gemm_cls_tail", "attention_map",
-                                    "features", "head_pool", "zeroshot"};
+                                    "features", "head_pool", "zeroshot", "rope"};
 static_assert(PC_COUNT <= VITX_PROF_MAX_CLASSES, "vitx_profile_read callers size their arrays by VITX_PROF_MAX_CLASSES");
 
 // A weight matrix kept in the file's block form on the device (quant.hip): `blocks` = N rows of K/32 blocks in the file's byte
@@ -117,6 +117,9 @@ struct vitx_ctx {
     std::shared_ptr<WeightSet> wset;     // never null once the context exists
     const float *pos = nullptr;          // [1 + g * g][D] position table the patch embedding adds: wset->pos, or pos_own when img_size differs from the file's
     float *pos_own = nullptr;            // the table resampled to this context's grid (vitx_ctx_options::img_size, pos_interp); in `allocs`
+    // rotary position embeddings of a file with `rope` (include/vitx.h): cos and sin [g * g][hd / 2] f32 for THIS context's grid, one allocation in
+    // `allocs` (the table depends on the context's size, not on the weights); nullptr for every other file: nothing is allocated or launched
+    float *rope_cos = nullptr, *rope_sin = nullptr;
     bool weights_shared = false;         // this context found the set already uploaded (vitx_ctx_shares_weights)
     // quantised files: vitx_ctx_options::quant_on_host restores the r01 behaviour (expand once on the host at upload, 16 bits per weight in HBM)
     bool quant_on_device = true;

@@ -238,7 +238,7 @@ struct SliceForward {
         return VITX_OK;
     }
     // The front of layer il, shared by the dense and the MX tail: just-in-time dequant, (norm1 of the first layer,) the qkv projection, the
-    // attention maps, then the attention -- or, tail_now, the class token's attention alone
+    // (rotary position embeddings,) attention maps, then the attention -- or, tail_now, the class token's attention alone
     int layer_front(int il, const LayerW &w, bool tail_now, const Rows &r) {
         int rc;
         const void *Wfile[W_PER_LAYER] = {w.qkv_w, w.proj_w, w.fc1_w, w.fc2_w};
@@ -262,6 +262,11 @@ struct SliceForward {
             // qkv projection (vit.cpp:820-821); `fix_u`: row blocks of U the previous layer's fc2 left to the fix-up are normalised in its prologue
             if ((rc = gemm(c, st, PC_GEMM_QKV, c->prec_attn ? EPI_BIAS_HILO : EPI_BIAS, dense_gemm(sl.U, Wl[W_QKV], w.qkv_b, sl.QKV, M, M_real, 3 * D, round_up(3 * D, tn), D),
                            Fl[W_QKV], nullptr, fix_u.todo ? &fix_u : nullptr, lo_off))) return rc;
+        }
+        // rotary position embeddings of a file with `rope`: q and k of the patch rows, in place, before anything reads them
+        if (c->rope_cos) {
+            ProfScope ps(c, st, PC_ROPE, 6.0 * n * (N - c->Tp) * (double)D, (double)n * (N - c->Tp) * 2 * D * eb * 2 * (c->prec_attn ? 2 : 1));
+            HIP_TRY(launch_rope(dt, sl.QKV, lo_off, c->rope_cos, c->rope_sin, n, N, c->Tp, D, c->H, st));
         }
         if (c->attn_on() && (rc = attention_maps(c, st, sl.QKV, lo_off, il, first_img, n))) return rc;
         if (tail_now) {   // attention of token 0 (vit.cpp:848-858 for the one row vit.cpp:910-911 keeps) -> compact rows U[b]; class rows of X -> Xc[b]

@@ -223,6 +223,11 @@ hipError_t launch_text_embed(bool table_f16, const void *tok, const float *pos, 
 hipError_t launch_text_pool(int dtype, const float *X, const int *pooled, const float *w, const float *b, void *z, int n, int m_pad, int T, int D, float eps, hipStream_t stream);
 hipError_t launch_attention_text(int dtype, const void *qkv, void *out, int n, int T, int D, int H, int causal, hipStream_t stream);
 bool attention_text_supports(int T, int D, int H);
+// Rotary position embeddings (rope.hip; include/vitx.h "rotary position embeddings"), in place on qkv [n_img * N][3 D] (lo_off != 0: the parity mode's
+// lo plane, F16 only): q and k of every token t >= prefix rotated by cos / sin [N - prefix][hd / 2] f32, half-split pairs (j, j + hd / 2) of each head;
+// v columns, prefix rows and everything behind row n_img * N untouched.  Any even head dim; 16-byte accesses where hd / 2 is a multiple of 8.
+hipError_t launch_rope(int dtype, void *qkv, long lo_off, const float *cos, const float *sin, int n_img, int N, int prefix, int D, int H, hipStream_t stream);
+bool rope_supports(int D, int H);
 // pos [1 + gy_in * gx_in][D] f32 -> out [1 + gy_out * gx_out][D] f32 (pos_resample.hip; the arithmetic: pos_resample.h); only enqueues
 hipError_t launch_pos_resample(const float *pos, int gy_in, int gx_in, int D, int gy_out, int gx_out, int interp, float *out, hipStream_t stream);
 bool attention_supports(int N, int D, int H);     // any token count; head_dim 64 (tuned kernels) or any other multiple of 8 up to 128 (generic kernel)

@@ -13,6 +13,7 @@
 // `pre_norm.bias` f32 [D] (CLIP's pre_layrnorm).  Without `arch` a file means tanh-GELU and eps 1e-6, the reference's arithmetic.
 // One more (include/vitx.h "no class token and the attention-pooling head"): the thirteen `attn_pool.*` tensors of a SigLIP-class model, which
 // come without cls_token / reg_token and with a pos_embed of g^2 rows (VITX_POOL_MAP).
+// One more (include/vitx.h "rotary position embeddings"): `rope` f32 [4] = {kind, theta, 0, 0} of a DINOv3-class model; its pos_embed is all zero.
 // A text-tower file (include/vitx.h "the text tower") is told by patch_size == 0: token_embed.weight [V][D] (f16 or f32) and pos_embed [T][D]
 // in place of the image front, the same blocks, norm.* and head.* [E][D]; `arch` is then required and its last two slots are {causal, eos + 1};
 // `zs` f32 [4] = {kind, scale, bias, 0} is optional.  cls_token, reg_token, pre_norm.*, preproc and attn_pool.* do not belong in one.
@@ -246,6 +247,26 @@ static int load_impl(const char *path, vitx_model &m) {
             ++n_optional;
             continue;
         }
+        if (t.name == "rope") {                                      // optional: f32 [4] = {kind, theta, 0, 0} (include/vitx.h "rotary position embeddings")
+            if (m.index.count(t.name)) { set_error("vitx_model_load: duplicate tensor '%s'", t.name.c_str()); return VITX_ERR_FORMAT; }
+            if (text) { set_error("vitx_model_load: text-tower file: tensor 'rope' belongs to image files"); return VITX_ERR_FORMAT; }
+            if (ttype != T_F32 || n_dims != 1 || t.ne[0] != 4) {
+                set_error("vitx_model_load: tensor 'rope' must be f32 [4] = {kind, theta, 0, 0}: got type %d, %d dims [%lld, ..]", ttype, n_dims, (long long)t.ne[0]);
+                return VITX_ERR_FORMAT;
+            }
+            t.raw.resize(16);
+            if (fread(t.raw.data(), 1, 16, f) != 16) { set_error("vitx_model_load: tensor '%s' is truncated", t.name.c_str()); return VITX_ERR_IO; }
+            float a[4]; memcpy(a, t.raw.data(), 16);
+            if (a[0] != (float)VITX_ROPE_DINOV3_AXIAL) { set_error("vitx_model_load: tensor 'rope' names kind %g: only 1 (DINOv3 axial) exists", (double)a[0]); return VITX_ERR_FORMAT; }
+            if (!(a[1] > 0.0f) || !(a[1] <= 3.402823466e38f)) { set_error("vitx_model_load: tensor 'rope' carries theta %g: it must be finite and positive", (double)a[1]); return VITX_ERR_FORMAT; }
+            if (a[2] != 0.0f || a[3] != 0.0f) { set_error("vitx_model_load: tensor 'rope' has reserved slots {%g, %g}: they must be 0", (double)a[2], (double)a[3]); return VITX_ERR_FORMAT; }
+            if ((hp.hidden_size / hp.num_attention_heads) % 4) { set_error("vitx_model_load: tensor 'rope' needs a head dim that is a multiple of 4 (this file: %d)", hp.hidden_size / hp.num_attention_heads); return VITX_ERR_FORMAT; }
+            m.rope_kind = (int)a[0]; m.rope_theta = a[1];
+            m.index[t.name] = (int)m.tensors.size();
+            m.tensors.push_back(std::move(t));
+            ++n_optional;
+            continue;
+        }
         if (t.name == "preproc") {                                   // optional: f32 [16], the model's own preprocessing (include/vitx.h "each model's own preprocessing")
             if (m.index.count(t.name)) { set_error("vitx_model_load: duplicate tensor '%s'", t.name.c_str()); return VITX_ERR_FORMAT; }
             if (ttype != T_F32 || n_dims != 1 || t.ne[0] != 16) {
@@ -333,6 +354,7 @@ static int load_impl(const char *path, vitx_model &m) {
     // the attention-pooling head: all thirteen tensors, no class or register token, a position table without a class row -- or none of it
     const bool has_cls = m.find("cls_token") != nullptr;
     if (n_pool) {
+        if (m.rope_kind) { set_error("vitx_model_load: tensor 'rope' together with attn_pool.*: the attention-pooling head has no rotary form"); return VITX_ERR_FORMAT; }
         for (const auto &kv : pool_expect)
             if (!m.find(kv.first)) { set_error("vitx_model_load: the attention-pooling head is incomplete: tensor '%s' is missing (%d of %d attn_pool.* tensors)", kv.first.c_str(), n_pool, (int)pool_expect.size()); return VITX_ERR_FORMAT; }
         if (has_cls || m.num_registers) { set_error("vitx_model_load: attn_pool.* together with '%s': a model with the attention-pooling head has no class or register token", has_cls ? "cls_token" : "reg_token"); return VITX_ERR_FORMAT; }
@@ -418,6 +440,33 @@ int vitx_model_pool_query(const vitx_model *m, float *out) {
             double s = 0.0;
             for (int j = 0; j < d; ++j) s += (double)wkv[(size_t)(h * d + j) * D + k] * q[h * d + j];      // the K half: rows 0 .. D-1 of kv.weight
             out[(size_t)h * D + k] = (float)(s * scale);
+        }
+    return VITX_OK;
+}
+int vitx_model_rope(const vitx_model *m, int *kind, float *theta) {
+    if (!m || !m->rope_kind) return 0;
+    if (kind) *kind = m->rope_kind;
+    if (theta) *theta = m->rope_theta;
+    return 1;
+}
+// DINOv3's axial table (include/vitx.h "rotary position embeddings"): double throughout, cos / sin rounded once to f32
+int vitx_model_rope_table(const vitx_model *m, int gh, int gw, float *cos_out, float *sin_out) {
+    if (!m || !cos_out || !sin_out) { vitx::set_error("vitx_model_rope_table: NULL argument"); return VITX_ERR_ARG; }
+    if (!m->rope_kind) { vitx::set_error("vitx_model_rope_table: the model has no `rope` tensor"); return VITX_ERR_ARG; }
+    if (gh <= 0 || gw <= 0 || (int64_t)gh * gw > (1 << 24)) { vitx::set_error("vitx_model_rope_table: grid %d x %d is not a positive size", gh, gw); return VITX_ERR_ARG; }
+    const int hd = m->hp.hidden_size / m->hp.num_attention_heads, q = hd / 4, half = hd / 2;
+    const double two_pi = 6.283185307179586476925286766559;
+    std::vector<double> inv((size_t)q);
+    for (int j = 0; j < q; ++j) inv[j] = pow((double)m->rope_theta, -4.0 * j / hd);
+    for (int y = 0; y < gh; ++y)
+        for (int x = 0; x < gw; ++x) {
+            const double cy = 2.0 * (y + 0.5) / gh - 1.0, cx = 2.0 * (x + 0.5) / gw - 1.0;
+            float *co = cos_out + ((size_t)y * gw + x) * half, *so = sin_out + ((size_t)y * gw + x) * half;
+            for (int j = 0; j < q; ++j) {
+                const double ay = two_pi * cy * inv[j], ax = two_pi * cx * inv[j];
+                co[j] = (float)cos(ay); so[j] = (float)sin(ay);
+                co[q + j] = (float)cos(ax); so[q + j] = (float)sin(ax);
+            }
         }
     return VITX_OK;
 }

@@ -36,6 +36,8 @@ struct vitx_model {
                                                       // VITX_POOL_MAP: the thirteen attn_pool.* tensors, no cls_token, pos_embed of g^2 rows
     int activation = VITX_ACT_GELU_TANH;              // MLP activation, from an optional `arch` [4] = {activation, eps, 0, 0}; hp.eps carries its eps
     bool has_pre_norm = false;                        // `pre_norm.weight` / `pre_norm.bias` [D]: LayerNorm of every token row in front of layer 0
+    int rope_kind = VITX_ROPE_NONE;                   // `rope` [4] = {kind, theta, 0, 0}: rotary position embeddings on q and k of the patch tokens (include/vitx.h)
+    float rope_theta = 0.0f;
     bool has_preproc = false;                         // `preproc` [16]: the model's own preprocessing (include/vitx.h); without it `preproc` is the reference default
     vitx_preproc preproc;
     // a text-tower file (patch_size == 0; include/vitx.h "the text tower"): hp.img_size = T, hp.num_classes = E

@@ -173,6 +173,16 @@ int vitx_op_attention_cls(int dtype, const void *d_qkv, long lo_off, void *out, 
     if (!attention_cls_supports(N, D, H)) { set_error("vitx_op_attention_cls: head_dim must be 8, 16, 32, 64 or 128 and N at most 15360 (head_dim %d, N %d)", D / H, N); return VITX_ERR_UNSUPPORTED; }
     return op_rc("vitx_op_attention_cls", launch_attention_cls(dtype, d_qkv, lo_off, out, nullptr, nullptr, n_img, N, D, H, (hipStream_t)stream));
 }
+// Rotary position embeddings in place on d_qkv (rope.hip; include/vitx.h "rotary position embeddings").  Every check comes before the launch; only enqueues.
+int vitx_op_rope(int dtype, void *d_qkv, long lo_off, const void *d_cos, const void *d_sin, int n_img, int N, int prefix, int D, int H, void *stream) {
+    if (!d_qkv || !d_cos || !d_sin || n_img <= 0 || N <= 0 || D <= 0 || H <= 0 || prefix < 0 || prefix > N || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_rope: invalid argument (0 <= prefix <= N)"); return VITX_ERR_ARG; }
+    if ((size_t)n_img * N * 3 * D >= ((size_t)1 << 40)) { set_error("vitx_op_rope: n_img * N * 3 * D is out of range"); return VITX_ERR_ARG; }
+    if (!lo_plane_ok("vitx_op_rope", dtype, lo_off, (long)n_img * N * 3 * D)) return VITX_ERR_ARG;
+    if (lo_off && (size_t)lo_off * 2 + (size_t)n_img * N * 3 * D * 2 > 0xf0000000u) { set_error("vitx_op_rope: both planes must lie below 0xf0000000 bytes"); return VITX_ERR_ARG; }
+    if ((uintptr_t)d_qkv % 2 || (uintptr_t)d_cos % 4 || (uintptr_t)d_sin % 4) { set_error("vitx_op_rope: misaligned pointer"); return VITX_ERR_ARG; }
+    if (!rope_supports(D, H)) { set_error("vitx_op_rope: D must be a multiple of H and the head dim even (D %d, H %d)", D, H); return VITX_ERR_UNSUPPORTED; }
+    return op_rc("vitx_op_rope", launch_rope(dtype, d_qkv, lo_off, (const float *)d_cos, (const float *)d_sin, n_img, N, prefix, D, H, (hipStream_t)stream), VITX_ERR_UNSUPPORTED);
+}
 // The parity mode's attention on f32 q, k, v (what the reference multiplies, vit.cpp:848,858): splits the rows into the two fp16 planes the
 // QKV GEMM's EPI_BIAS_HILO epilogue emits, then runs the precise streaming kernel.  Synchronous (allocates its own scratch).
 int vitx_op_attention_f32(const float *qkv_f32, void *out, int n_img, int N, int D, int H, void *stream) {
