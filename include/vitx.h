@@ -424,6 +424,35 @@ int vitx_model_rope(const vitx_model *m, int *kind, float *theta);
 int vitx_model_rope_table(const vitx_model *m, int gh, int gw, float *cos_out, float *sin_out);
 int vitx_op_rope(int dtype, void *d_qkv, long lo_off, const void *d_cos, const void *d_sin, int n_img, int N, int prefix, int D, int H, void *stream);
 
+/* ---- gated MLP (DINOv2 ViT-g/14, DINOv3 ViT-H+) ---------------------------------- */
+/* A file may carry `glu`, f32 [4] = {kind, F, 0, 0}: the MLP of every block is then fc2( act(gate(x)) . up(x) ) with hidden width F instead of
+ * fc2( act(fc1(x)) ) with hidden width 4 D.  kind 1 (VITX_GLU_SWIGLU, the only one): h = silu(gate) . up, silu(g) = g / (1 + exp(-g)).  With it every
+ * blocks.i.mlp.fc1.weight is [2 F][D] -- rows 0 .. F-1 the gate projection, rows F .. 2F-1 the up projection: cat(gate_proj, up_proj), the order of
+ * HuggingFace's weights_in.chunk(2) --, mlp.fc1.bias is [2 F] and mlp.fc2.weight is [D][F].  F is fc2's K: it must be a whole number, at least 64 and a
+ * multiple of 64 -- the rule every GEMM family puts on K (the ring kernels step K in pairs of 32-deep slots, gemm_ring_supports; the ping-pong kernel
+ * takes multiples of 128 and leaves the others to the ring), the same rule context creation puts on hidden_size.
+ * The loader refuses (VITX_ERR_FORMAT) any other kind, such an F, non-zero reserved slots, a second `glu`, `glu` in a text-tower file and `glu`
+ * together with attn_pool.*.  `glu` stands IN FRONT of the first blocks.* record (the loader sizes the records from the expected shapes as it reads;
+ * the converter writes it directly after `arch` / `rope`); behind one it is VITX_ERR_FORMAT.  The activation slot of such a file's `arch` is carried
+ * and not applied in the blocks.  vitx_quantize_file and vitx_model_resize_file copy `glu` byte for byte; fc1 and fc2 quantise like any matrix.
+ * A file without `glu` loads, runs and hashes exactly as before.
+ * The forward of such a file: fc1 with the plain bias epilogue into [rows][2 F], one launch of the gate kernel (swiglu.hip) into a compact [rows][F],
+ * fc2 from that -- so fc2 sees lda == K and keeps whatever kernel family and LayerNorm fusion any other model's fc2 gets.  The class-rows-only last
+ * layer takes the same three steps on the class rows.  The gate kernel widens g and u to f32, evaluates the sigmoid and both products in f32 and
+ * rounds the product once (RNE) to the operand type.  Only STORED values are rounded, in both operand types: the fc1 output and the product.  The
+ * reference has no gated MLP, so the F16 parity mode has no ggml rounding point (the fp16 activation table's argument) to honour here.  The result is
+ * finite for every finite operand pair with a finite product: a large negative g gives -0, a large positive g gives g u.
+ * VITX_MXFP8 contexts and ViTSTR (one-channel) contexts of such a file: VITX_ERR_UNSUPPORTED at creation.  A context of a file without `glu`
+ * allocates and launches nothing new.
+ *   vitx_model_glu   1 and *kind / *width (either may be NULL) for a file with `glu`, 0 without (and for NULL)
+ *   vitx_op_swiglu   the gfx950 kernel on device pointers: d_in [rows][ld_in] of `dtype` (VITX_F16 / VITX_BF16), gate in columns 0 .. F-1, up in
+ *                    F .. 2F-1; d_out [rows][ld_out], written in columns 0 .. F-1 and nowhere else.  Every check comes before the launch:
+ *                    NULL, non-positive sizes, another dtype, F % 8, a leading dimension that is no multiple of 8, ld_in < 2 F, ld_out < F, a
+ *                    pointer off a 16-byte boundary: VITX_ERR_ARG.  Only enqueues on `stream`. */
+enum vitx_glu_kind { VITX_GLU_NONE = 0, VITX_GLU_SWIGLU = 1 };
+int vitx_model_glu(const vitx_model *m, int *kind, int *width);
+int vitx_op_swiglu(int dtype, const void *d_in, long ld_in, void *d_out, long ld_out, long rows, int F, void *stream);
+
 /* ---- several GPUs in one process (north_star: batch shards + one RCCL gather) -- */
 /* One context (replicated weights) and one PERSISTENT host thread per listed device (created here, parked between calls).  Images are
  * cut into contiguous shards, run concurrently, and the results are all-gathered with ONE ncclAllGather over RCCL.

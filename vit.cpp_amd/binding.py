@@ -56,6 +56,7 @@ EXPORTS = [
     "vitx_model_kind", "vitx_model_text_info", "vitx_model_text_zs", "vitx_text_create", "vitx_text_free", "vitx_text_embed", "vitx_text_embed_device", "vitx_text_shares_weights", "vitx_text_check_ids",
     "vitx_op_text_embed", "vitx_op_text_pool", "vitx_op_attention_text", "vitx_op_attention_generic",
     "vitx_model_rope", "vitx_model_rope_table", "vitx_op_rope",
+    "vitx_model_glu", "vitx_op_swiglu",
 ]
 
 
@@ -246,6 +247,9 @@ def lib():
             L.vitx_model_rope.argtypes = [vp, C.POINTER(ip), C.POINTER(C.c_float)]
             L.vitx_model_rope_table.argtypes = [vp, ip, ip, C.POINTER(C.c_float), C.POINTER(C.c_float)]
             L.vitx_op_rope.argtypes = [ip, vp, C.c_long, vp, vp, ip, ip, ip, ip, ip, vp]
+        if hasattr(L, "vitx_op_swiglu"):
+            L.vitx_model_glu.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
+            L.vitx_op_swiglu.argtypes = [ip, vp, C.c_long, vp, C.c_long, C.c_long, ip, vp]
         _lib = L
     return _lib
 
@@ -320,6 +324,12 @@ class Model:
         """(kind, theta) of a file with a `rope` tensor (rotary position embeddings on q and k of the patch tokens), or None."""
         k, t = C.c_int(), C.c_float()
         return (k.value, t.value) if lib().vitx_model_rope(self._h, C.byref(k), C.byref(t)) else None
+
+    @property
+    def glu(self):
+        """(kind, F) of a file with a `glu` tensor (a gated MLP of hidden width F: fc1 is [2 F][D], fc2 [D][F]), or None."""
+        k, w = C.c_int(), C.c_int()
+        return (k.value, w.value) if lib().vitx_model_glu(self._h, C.byref(k), C.byref(w)) else None
 
     def rope_table(self, grid) -> Tuple[np.ndarray, np.ndarray]:
         """vitx_model_rope_table: (cos, sin), each f32 [gh * gw, head_dim / 2], for a grid g or (gh, gw); row-major over (y, x)."""
@@ -904,6 +914,11 @@ def op_attention_pool(d_x: int, row_stride: int, img_stride: int, d_ln_w: int, d
 def op_rope(dtype: int, d_qkv: int, d_cos: int, d_sin: int, n_img: int, N: int, prefix: int, D: int, H: int, lo_off: int = 0, stream: int = 0) -> None:
     """vitx_op_rope: rotary position embeddings in place on d_qkv [n_img * N, 3 D] (lo_off: the parity mode's lo plane); cos / sin f32 [N - prefix, head_dim / 2].  Only enqueues."""
     check(lib().vitx_op_rope(dtype, d_qkv, lo_off, d_cos, d_sin, n_img, N, prefix, D, H, stream), "vitx_op_rope")
+
+
+def op_swiglu(dtype: int, d_in: int, ld_in: int, d_out: int, ld_out: int, rows: int, F: int, stream: int = 0) -> None:
+    """vitx_op_swiglu: d_out[r][j] = RNE(silu(d_in[r][j]) * d_in[r][F + j]), j < F, rows of ld_in / ld_out elements of `dtype`.  Only enqueues."""
+    check(lib().vitx_op_swiglu(dtype, d_in, ld_in, d_out, ld_out, rows, F, stream or None), "vitx_op_swiglu")
 
 
 def op_text_embed(table_f16: bool, d_tok: int, d_pos: int, d_ids: int, d_x: int, n: int, T: int, D: int, stream: int = 0) -> None:

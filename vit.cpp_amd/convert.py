@@ -16,6 +16,11 @@ What is converted
   SigLIP   SiglipVisionModel, SiglipModel (its vision tower): no class token, the attention-pooling head.
   DINOv3   DINOv3ViTModel (ViT-S/B/L): class token, register tokens, folded LayerScale, and rotary position embeddings -- the `rope` tensor,
            f32 [4] = {1, rope_theta, 0, 0}, beside an all-zero pos_embed (include/vitx.h "rotary position embeddings").  A backbone: the zero head.
+  gated    DINOv2 ViT-g/14 (use_swiglu_ffn) and DINOv3 ViT-H+ (use_gated_mlp), OPT-IN: convert_hf_model(..., gated_mlp=True) / --gated-mlp.  The MLP is
+           fc2(silu(gate(x)) . up(x)) with a hidden width F that is not 4 x hidden: the `glu` tensor, f32 [4] = {1, F, 0, 0}, directly after `arch` /
+           `rope`; mlp.fc1 = [2 F][D], gate rows then up rows (DINOv2's weights_in as it is; DINOv3's cat(gate_proj, up_proj)), mlp.fc2 = [D][F]
+           (include/vitx.h "gated MLP").  Without the switch such a model is refused: the file cannot be read by the reference or by an engine build
+           before the `glu` tensor existed.
   timm     a VisionTransformer state_dict (--timm-state-dict model.pth, no `timm` import): convert_timm_state_dict.
 
 Every model's settings travel with it.  The MLP activation (`hidden_act`: gelu -> erf-GELU, gelu_pytorch_tanh / gelu_new -> tanh-GELU, quick_gelu ->
@@ -31,7 +36,8 @@ f32(255.0 * mean).  --no-preproc writes the file without it: the reference's str
 processor: the --pp-* options state one (cli_preproc); with none of them no tensor is written and the file keeps the reference's bytes.
 
 What is refused, by name: an activation the forward path does not evaluate; an MLP that is not 4 x hidden (SigLIP SO400M's 4304); a head_dim that
-is no multiple of 8 up to 128; qkv_bias=False; SwiGLU, DINOv3's gated MLP (use_gated_mlp, ViT-H+ and 7B), qk-norm, fc_norm and distillation tokens; a SigLIP tower without its pooling head
+is no multiple of 8 up to 128; qkv_bias=False; SwiGLU (use_swiglu_ffn) and DINOv3's gated MLP (use_gated_mlp) unless gated_mlp=True / --gated-mlp opts in, a gate
+activation other than silu and a gated width that is no multiple of 64; qk-norm, fc_norm and distillation tokens; a SigLIP tower without its pooling head
 (vision_use_head = False), SiglipForImageClassification (a mean-pool classifier: no slot), Siglip2VisionModel (NaFlex: its patch embedding is a
 Linear); --no-head on a ViT, and a model without classifier or projection converted without it; --vitstr on anything but a one-channel ViT; in a
 preprocessor_config whatever the engine's preprocess cannot honour -- another resample code, do_resize off, padding, a channel flip, a final size
@@ -200,6 +206,10 @@ VIT_BLOCKS_V5 = BlockNames("vit.layers.{i}.", ("attention.q_proj", "attention.k_
 DINOV2_BLOCKS = BlockNames("encoder.layer.{i}.", _HF_QKV, "norm1", "attention.output.dense", "norm2", "mlp.fc1", "mlp.fc2", "layer_scale1.lambda1", "layer_scale2.lambda1")
 DINOV3_BLOCKS = BlockNames("layer.{i}.", ("attention.q_proj", "attention.k_proj", "attention.v_proj"), "norm1", "attention.o_proj", "norm2", "mlp.up_proj", "mlp.down_proj",
                            "layer_scale1.lambda1", "layer_scale2.lambda1")
+# the gated MLPs (gated_mlp=True): DINOv2's weights_in is already gate rows then up rows; DINOv3's gate_proj / up_proj are concatenated under the
+# name `mlp.gate_up` by dinov3_state_dict_to_timm before the blocks are mapped
+DINOV2_GLU_BLOCKS = DINOV2_BLOCKS._replace(fc1="mlp.weights_in", fc2="mlp.weights_out")
+DINOV3_GLU_BLOCKS = DINOV3_BLOCKS._replace(fc1="mlp.gate_up")
 CLIP_BLOCKS = BlockNames("encoder.layers.{i}.", ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"), "layer_norm1", "self_attn.out_proj", "layer_norm2",
                          "mlp.fc1", "mlp.fc2")          # SigLIP's too
 
@@ -238,6 +248,17 @@ def _require_mlp_4x(cfg, field: str, want: int, note: str = "") -> None:
         raise ValueError(f"{field} {have}: the file format holds a 4 x hidden MLP{note}")
 
 
+_GATED_HOWTO = ("pass gated_mlp=True (convert.py --gated-mlp) to write it with the `glu` tensor: such a file cannot be read by the reference or by an engine "
+                "build before the gated MLP")
+
+
+def _glu_tensor(F: int) -> np.ndarray:
+    """The `glu` tensor {1 = SwiGLU, F, 0, 0} of a gated MLP of hidden width F (include/vitx.h "gated MLP")."""
+    if F < 64 or F % 64:
+        raise ValueError(f"gated MLP of hidden width {F}: the forward path takes multiples of 64 (the GEMMs' K step)")
+    return np.array([1, F, 0, 0], np.float32)
+
+
 def _f32(tensors: dict) -> Dict[str, np.ndarray]:
     """Every tensor (a numpy array or a torch tensor) as a contiguous f32 array, in the order given."""
     return {k: np.ascontiguousarray(np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, np.float32)) for k, v in tensors.items()}
@@ -265,28 +286,40 @@ def state_dict_to_timm(sd: Dict[str, np.ndarray], num_layers: int) -> Dict[str, 
     return _f32(out)
 
 
-def dinov2_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, no_head: bool = False) -> Dict[str, np.ndarray]:
+def dinov2_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, no_head: bool = False, gated_mlp: bool = False) -> Dict[str, np.ndarray]:
     """An HF Dinov2[WithRegisters]{ForImageClassification, Model} state dict (numpy arrays) under the file's names and order.  register_tokens ->
     `reg_token` [1][R][D] directly after cls_token; the classifier is the [C][2 D] head over concat(cls, mean of the patch tokens) (include/vitx.h
     "register tokens and the pooled head": the reference's loader cannot read such a file); LayerScale is folded (fold_layer_scale); mask_token is
-    dropped.  SwiGLU, qk-norm, fc_norm and distillation tokens are refused by name.  no_head: a backbone, which gets the zero head."""
-    if getattr(cfg, "use_swiglu_ffn", False):
-        raise ValueError("use_swiglu_ffn: the SwiGLU MLP of the DINOv2 giant models is not supported (the forward path has the GELU MLP only)")
+    dropped.  qk-norm, fc_norm and distillation tokens are refused by name.  no_head: a backbone, which gets the zero head.
+    use_swiglu_ffn (ViT-g/14) is refused by name unless gated_mlp: then mlp.weights_in -> mlp.fc1 ([2 F][D]: HF chunks it into gate, up in that
+    order), mlp.weights_out -> mlp.fc2 with LayerScale folded as ever, and `glu` = {1, F, 0, 0} in front, F read off weights_out's shape."""
+    swiglu = bool(getattr(cfg, "use_swiglu_ffn", False))
+    if swiglu and not gated_mlp:
+        raise ValueError("use_swiglu_ffn: the SwiGLU MLP of the DINOv2 giant models is not converted by default; " + _GATED_HOWTO)
+    if gated_mlp and not swiglu:
+        raise ValueError("gated_mlp=True, but the model has the plain MLP (use_swiglu_ffn is off)")
     for k in sd:
         for bad, what in (("q_norm", "qk-norm"), ("k_norm", "qk-norm"), ("fc_norm", "fc_norm"), ("dist_token", "a distillation token"), ("distillation", "a distillation token")):
             if bad in k:
                 raise ValueError(f"tensor {k!r}: {what} is not supported")
-    _require_mlp_4x(cfg, "mlp_ratio", 4)
+    if not swiglu:
+        _require_mlp_4x(cfg, "mlp_ratio", 4)
     pre = next((p for p in ("dinov2_with_registers.", "dinov2.", "") if p + "embeddings.cls_token" in sd), None)
     if pre is None:
         raise ValueError("not a DINOv2 state dict: embeddings.cls_token is missing")
     e = pre + "embeddings."
-    out = {"cls_token": sd[e + "cls_token"]}
+    out = {}
+    if swiglu:
+        w_out = pre + DINOV2_GLU_BLOCKS.layer.format(i=0) + "mlp.weights_out.weight"
+        if w_out not in sd:
+            raise ValueError(f"use_swiglu_ffn, but {w_out} is missing")
+        out["glu"] = _glu_tensor(int(np.shape(sd[w_out])[1]))
+    out["cls_token"] = sd[e + "cls_token"]
     if e + "register_tokens" in sd:
         out["reg_token"] = sd[e + "register_tokens"]
     out["pos_embed"] = sd[e + "position_embeddings"]
     _put(out, "patch_embed.proj", sd, e + "patch_embeddings.projection")
-    map_blocks(out, sd, DINOV2_BLOCKS, cfg.num_hidden_layers, pre)
+    map_blocks(out, sd, DINOV2_GLU_BLOCKS if swiglu else DINOV2_BLOCKS, cfg.num_hidden_layers, pre)
     _put(out, "norm", sd, pre + "layernorm")
     if no_head:
         _zero_head(out, int(np.shape(out["cls_token"])[-1]))
@@ -327,17 +360,25 @@ def clip_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, no_head: bool = Fals
     return _f32(out)
 
 
-def dinov3_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg) -> Dict[str, np.ndarray]:
+def dinov3_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, gated_mlp: bool = False) -> Dict[str, np.ndarray]:
     """An HF DINOv3ViTModel state dict (numpy arrays) under the file's names and order.  The position signal is rotary (include/vitx.h "rotary
     position embeddings"): `rope` = {1, rope_theta, 0, 0} in front, and a pos_embed [1][1 + g^2][D] of zeros at the config's image_size, so that the
     patch embedding and the resampler stay what they are.  register_tokens -> `reg_token`; LayerScale is folded; key_bias=False (the published
     models) becomes a zero k bias; mask_token is dropped.  The blocks live under `model.layer.N.` (transformers 5.15; `layer.N.` is accepted too).
-    The gated MLP of ViT-H+ / 7B (use_gated_mlp) and an MLP that is not 4 x hidden are refused.  A backbone: the zero head, whose VITX_FEAT_CLS
-    is HF's pooler_output."""
-    if getattr(cfg, "use_gated_mlp", False):
-        raise ValueError("use_gated_mlp: the gated (SwiGLU) MLP of DINOv3 ViT-H+ / 7B is not supported (the forward path has the GELU MLP only)")
+    A plain MLP that is not 4 x hidden is refused.  A backbone: the zero head, whose VITX_FEAT_CLS is HF's pooler_output.
+    use_gated_mlp (ViT-H+) is refused by name unless gated_mlp: then mlp.fc1 = cat(gate_proj, up_proj) ([2 F][D], F = intermediate_size),
+    down_proj -> mlp.fc2 with LayerScale folded, zero biases where mlp_bias=False, and `glu` = {1, F, 0, 0} directly after `rope`.  The gate is
+    silu: any other hidden_act of a gated model is refused."""
+    gated = bool(getattr(cfg, "use_gated_mlp", False))
+    if gated and not gated_mlp:
+        raise ValueError("use_gated_mlp: the gated (SwiGLU) MLP of DINOv3 ViT-H+ / 7B is not converted by default; " + _GATED_HOWTO)
+    if gated_mlp and not gated:
+        raise ValueError("gated_mlp=True, but the model has the plain MLP (use_gated_mlp is off)")
+    if gated and getattr(cfg, "hidden_act", "silu") != "silu":
+        raise ValueError(f"hidden_act {getattr(cfg, 'hidden_act', None)!r}: the gate of a gated MLP is silu (SwiGLU); other gate functions are not supported")
     D = int(cfg.hidden_size)
-    _require_mlp_4x(cfg, "intermediate_size", 4 * D)
+    if not gated:
+        _require_mlp_4x(cfg, "intermediate_size", 4 * D)
     if "embeddings.cls_token" not in sd:
         raise ValueError("not a DINOv3 state dict: embeddings.cls_token is missing")
     pre = next((p for p in ("model.", "") if p + "layer.0.attention.q_proj.weight" in sd), None)
@@ -354,14 +395,25 @@ def dinov3_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg) -> Dict[str, np.nd
             k = f"{pre}layer.{i}.{n}"
             if k + ".weight" in sd and k + ".bias" not in sd:
                 sd[k + ".bias"] = np.zeros((int(np.shape(sd[k + ".weight"])[0]),), np.float32)
+    if gated:
+        for i in range(cfg.num_hidden_layers):                        # fc1 = gate rows, then up rows; a projection without bias (mlp_bias=False) has a zero bias
+            q = f"{pre}layer.{i}.mlp."
+            for n in ("gate_proj", "up_proj", "down_proj"):
+                if q + n + ".bias" not in sd:
+                    sd[q + n + ".bias"] = np.zeros((int(np.shape(sd[q + n + ".weight"])[0]),), np.float32)
+            sd[q + "gate_up.weight"] = np.concatenate([sd[q + "gate_proj.weight"], sd[q + "up_proj.weight"]], 0)
+            sd[q + "gate_up.bias"] = np.concatenate([sd[q + "gate_proj.bias"], sd[q + "up_proj.bias"]], 0)
     g = int(cfg.image_size) // int(cfg.patch_size)
     e = "embeddings."
-    out = {"rope": np.array([1, theta, 0, 0], np.float32), "cls_token": sd[e + "cls_token"]}
+    out = {"rope": np.array([1, theta, 0, 0], np.float32)}
+    if gated:
+        out["glu"] = _glu_tensor(int(np.shape(sd[f"{pre}layer.0.mlp.down_proj.weight"])[1]))
+    out["cls_token"] = sd[e + "cls_token"]
     if e + "register_tokens" in sd and int(np.shape(sd[e + "register_tokens"])[1]) > 0:
         out["reg_token"] = sd[e + "register_tokens"]
     out["pos_embed"] = np.zeros((1, 1 + g * g, D), np.float32)
     _put(out, "patch_embed.proj", sd, e + "patch_embeddings")
-    map_blocks(out, sd, DINOV3_BLOCKS, cfg.num_hidden_layers, pre)
+    map_blocks(out, sd, DINOV3_GLU_BLOCKS if gated else DINOV3_BLOCKS, cfg.num_hidden_layers, pre)
     _put(out, "norm", sd, "norm")
     _zero_head(out, D)
     return _f32(out)
@@ -463,7 +515,7 @@ _VIT = Family("ViT", lambda sd, cfg, no_head: state_dict_to_timm(sd, cfg.num_hid
 _DINOV2 = Family("DINOv2", dinov2_state_dict_to_timm, 1, _config_labels, "optional", ("AutoModelForImageClassification", "AutoModel"))
 _CLIP = Family("CLIP", clip_state_dict_to_timm, 1, lambda cfg, E: {i: f"dim_{i}" for i in range(E)}, "optional", ("CLIPVisionModelWithProjection", "CLIPVisionModel"))
 _SIGLIP = Family("SigLIP", lambda sd, cfg, no_head: siglip_state_dict_to_timm(sd, cfg), 0, None, "never", ("SiglipVisionModel",) * 2)
-_DINOV3 = Family("DINOv3", lambda sd, cfg, no_head: dinov3_state_dict_to_timm(sd, cfg), 1, None, "never", ("DINOv3ViTModel",) * 2)
+_DINOV3 = Family("DINOv3", lambda sd, cfg, no_head, gated_mlp=False: dinov3_state_dict_to_timm(sd, cfg, gated_mlp), 1, None, "never", ("DINOv3ViTModel",) * 2)
 # text towers (convert_hf_text_model): no patch grid (prefix_rows is not read), no labels -- the "classes" are the projection's columns --, always with the projection
 _CLIP_TEXT = Family("CLIP text", clip_text_state_dict, 0, lambda cfg, E: {}, "always", ("CLIPTextModelWithProjection",) * 2)
 _SIGLIP_TEXT = Family("SigLIP text", siglip_text_state_dict, 0, lambda cfg, E: {}, "always", ("SiglipTextModel",) * 2)
@@ -473,22 +525,31 @@ FAMILIES = {"vit": _VIT, "dinov2": _DINOV2, "dinov2_with_registers": _DINOV2, "c
             "dinov3_vit": _DINOV3, "clip_text_model": _CLIP_TEXT, "siglip_text_model": _SIGLIP_TEXT}
 
 
-def _family_tensors(model, cfg, fam, no_head: bool, head_dim_note: str = ""):
+def _family_tensors(model, cfg, fam, no_head: bool, head_dim_note: str = "", gated_mlp: bool = False):
     """The front both converters share: the head-dim refusal, the state dict as numpy arrays, the config's activation and epsilon, and the
     family's mapper.  Returns (the file's tensors in its order, activation, eps); each converter then states its header and calls write_model."""
     hd = cfg.hidden_size // cfg.num_attention_heads
     if cfg.hidden_size % cfg.num_attention_heads or hd % 8 or not 8 <= hd <= 128:
         raise ValueError(f"head_dim {hd}: the forward path takes multiples of 8 up to 128{head_dim_note}")
     sd = {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
-    return fam.mapper(sd, cfg, no_head), hf_activation(cfg), float(getattr(cfg, "layer_norm_eps", 1e-6))
+    if gated_mlp and fam not in (_DINOV2, _DINOV3):
+        raise ValueError(f"gated_mlp=True: a {fam.name} model has no gated MLP this converter knows (DINOv2 use_swiglu_ffn, DINOv3 use_gated_mlp)")
+    tensors = fam.mapper(sd, cfg, no_head, gated_mlp=True) if gated_mlp else fam.mapper(sd, cfg, no_head)
+    # a gated DINOv3 model states its GATE function in hidden_act (silu, checked by the mapper): the file's activation slot is carried and not
+    # applied in such a file (include/vitx.h "gated MLP") and says tanh-GELU, the slot's zero
+    act = ACT_TANH if "glu" in tensors and fam is _DINOV3 else hf_activation(cfg)
+    return tensors, act, float(getattr(cfg, "layer_norm_eps", 1e-6))
 
 
-def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_head: bool = False, preprocessor_config: dict | None = None) -> HParams:
+def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_head: bool = False, preprocessor_config: dict | None = None,
+                     gated_mlp: bool = False) -> HParams:
     """model: a transformers model of one of FAMILIES, in eval mode (the module docstring lists the classes); no_head=True converts a model
     without classifier or projection, whose file gets the zero head labelled "(no head)" (a SigLIP tower always does).  The activation and the
     LayerNorm epsilon are the config's (with_arch); the class count and the image size are read off head.weight and pos_embed.
     preprocessor_config: the checkpoint's preprocessor_config.json as a dict -- its preprocessing is written as the `preproc` tensor (hf_preproc);
     None writes the file without one.  Writes `path`; returns the hparams written.
+    gated_mlp=True opts in to the gated (SwiGLU) MLP of a Dinov2* model with use_swiglu_ffn or a DINOv3ViTModel with use_gated_mlp: the file carries
+    the `glu` tensor, which neither the reference nor an engine build before it can read; without it such a model is refused by name.
     vitstr=True: the model is a ViTSTR scene-text recogniser (the reference's extensions/vitstr.cpp/convert-pth-to-ggml.py: a ViT with ONE input
     channel whose classifier is applied to the first 25 tokens); the file then carries the character set as labels, and the one-channel patch
     kernel is what makes vit_model_load / vitx_model_load treat it as a ViTSTR model (vitstr.cpp:482)."""
@@ -512,7 +573,7 @@ def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_
     if no_head and fam.head == "always":
         raise ValueError("no_head converts a DINOv2 backbone (Dinov2Model, Dinov2WithRegistersModel), a CLIPVisionModel or a SigLIP tower")
     headless = fam.head == "never" or no_head
-    tensors, act, eps = _family_tensors(model, cfg, fam, no_head, " (64 runs the tuned attention kernels)")
+    tensors, act, eps = _family_tensors(model, cfg, fam, no_head, " (64 runs the tuned attention kernels)", gated_mlp)
     g = grid_side(tensors["pos_embed"], fam.prefix_rows)          # the checkpoint's own grid (config.image_size states it too)
     hp = HParams(cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, int(tensors["head.weight"].shape[0]), cfg.patch_size, g * cfg.patch_size, ftype)
     id2label = NO_HEAD_LABELS if headless else fam.labels(cfg, hp.num_classes)
@@ -776,6 +837,8 @@ def main(argv=None) -> int:
     ap.add_argument("--vitstr", action="store_true", help="one-channel ViTSTR scene-text model: write the character set as labels")
     ap.add_argument("--no-head", action="store_true", help="a DINOv2 backbone (Dinov2Model / Dinov2WithRegistersModel): the file gets a one-class head of zeros "
                                                            "labelled '(no head)'; read the embeddings with --embed / vitx_feat_*")
+    ap.add_argument("--gated-mlp", action="store_true", help="opt in to the gated (SwiGLU) MLP of DINOv2 ViT-g/14 (use_swiglu_ffn) / DINOv3 ViT-H+ (use_gated_mlp): the file "
+                                                            "carries the `glu` tensor, which the reference and engine builds before it cannot read")
     ap.add_argument("--timm-state-dict", action="store_true", help="`model` is a torch-saved timm VisionTransformer state_dict (.pth); no timm import needed")
     ap.add_argument("--heads", type=int, default=0, help="attention heads of a timm checkpoint (inferred only for the widths of released timm ViTs; required otherwise)")
     ap.add_argument("--act", default="tanh", choices=sorted(_ACT_NAMES), help="MLP activation of a timm checkpoint (a state dict carries no config): tanh = ggml's GELU, the "
@@ -846,7 +909,7 @@ def main(argv=None) -> int:
                     pc = json.load(f)
             else:
                 print(f"note: no preprocessor_config.json beside '{a.model}': the file is written without a `preproc` tensor")
-        hp = convert_hf_model(m, a.out, a.ftype, vitstr=a.vitstr, no_head=a.no_head, preprocessor_config=pc)
+        hp = convert_hf_model(m, a.out, a.ftype, vitstr=a.vitstr, no_head=a.no_head, preprocessor_config=pc, gated_mlp=a.gated_mlp)
     if a.img_size and a.img_size != hp.img_size:           # written at the checkpoint's size first, then replaced by its --img-size version
         from . import binding
         tmp = a.out + f".src{os.getpid()}"

@@ -161,6 +161,8 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
     }
     if (m->rope_kind && dtype == VITX_MXFP8) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts do not take models with rotary position embeddings"); return VITX_ERR_UNSUPPORTED; }
     if (m->rope_kind && m->in_chans == 1) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes no rotary position embeddings"); return VITX_ERR_UNSUPPORTED; }
+    if (m->glu_kind && dtype == VITX_MXFP8) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts do not take models with a gated MLP"); return VITX_ERR_UNSUPPORTED; }
+    if (m->glu_kind && m->in_chans == 1) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes no gated MLP"); return VITX_ERR_UNSUPPORTED; }
     if (m->in_chans == 1 && (m->has_pre_norm || m->activation != VITX_ACT_GELU_TANH)) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes neither a pre-norm nor an activation other than tanh-GELU"); return VITX_ERR_UNSUPPORTED; }
     if (dtype == VITX_MXFP8 && m->activation != VITX_ACT_GELU_TANH) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts evaluate tanh-GELU only (this model's activation: %d)", m->activation); return VITX_ERR_UNSUPPORTED; }
     if (m->in_chans == 1 && img_size != m->hp.img_size) { set_error("vitx_ctx_create_ex: a ViTSTR context stays at the file's img_size (%d)", m->hp.img_size); return VITX_ERR_UNSUPPORTED; }
@@ -179,7 +181,8 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
     c->mx = dtype == VITX_MXFP8; c->dtype = c->mx ? VITX_BF16 : dtype;      // everything but the MX GEMMs runs as in a VITX_BF16 context
     c->D = hp.hidden_size; c->L = hp.num_hidden_layers; c->H = hp.num_attention_heads; c->C = hp.num_classes; c->P = hp.patch_size; c->S = img_size;
     c->Cin = m->in_chans; c->R = m->in_chans == 1 ? VITX_VITSTR_SEQ_LEN : 1;
-    c->fc1_epi = act_epi(m->activation);
+    c->glu = m->glu_kind != VITX_GLU_NONE; c->F = m->mlp_hidden(); c->F1 = m->mlp_fc1_rows();
+    c->fc1_epi = c->glu ? EPI_BIAS : act_epi(m->activation);       // a gated MLP: the plain bias epilogue, the gate is a launch of its own
     c->nreg = m->num_registers; c->pool = m->head_pool == VITX_POOL_CLS_MEAN; c->map = m->head_pool == VITX_POOL_MAP;
     c->Tp = c->map ? 0 : 1 + c->nreg;
     if (c->map && c->H > kPoolMaxHeads) { set_error("vitx_ctx_create: the attention-pooling kernel takes at most %d heads (this model: %d)", kPoolMaxHeads, c->H); return VITX_ERR_UNSUPPORTED; }
@@ -222,6 +225,7 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
 int upload_blocks(vitx_ctx *c) {
     const vitx_model *m = c->model;
     const int D = c->D, tn = c->tn;
+    const int F = m->mlp_hidden(), F1 = m->mlp_fc1_rows();      // (from the model: a text context's shell sets neither c->F nor c->F1)
     int rc;
     auto T = [&](const std::string &n) { return m->find(n); };
     vitx_ctx::WeightSet &ws = *c->wset;
@@ -235,17 +239,17 @@ int upload_blocks(vitx_ctx *c) {
         if ((rc = upload_f32(c, T(p + "norm2.bias"), &w.ln2_b))) return rc;
         if ((rc = upload_f32(c, T(p + "attn.qkv.bias"), &w.qkv_b, round_up(3 * D, tn)))) return rc;
         if ((rc = upload_f32(c, T(p + "attn.proj.bias"), &w.proj_b, round_up(D, tn)))) return rc;
-        if ((rc = upload_f32(c, T(p + "mlp.fc1.bias"), &w.fc1_b, round_up(4 * D, tn)))) return rc;
+        if ((rc = upload_f32(c, T(p + "mlp.fc1.bias"), &w.fc1_b, round_up(F1, tn)))) return rc;
         if ((rc = upload_f32(c, T(p + "mlp.fc2.bias"), &w.fc2_b, round_up(D, tn)))) return rc;
         w.qkv_w = w.fc1_w = w.fc2_w = nullptr;
         if (c->mx) {
             if ((rc = upload_mx(c, T(p + "attn.qkv.weight"), 3 * D, D, round_up(3 * D, 128), &w.mx[W_QKV]))) return rc;
-            if ((rc = upload_mx(c, T(p + "mlp.fc1.weight"), 4 * D, D, round_up(4 * D, 128), &w.mx[W_FC1]))) return rc;
-            if ((rc = upload_mx(c, T(p + "mlp.fc2.weight"), D, 4 * D, round_up(D, 128), &w.mx[W_FC2]))) return rc;
+            if ((rc = upload_mx(c, T(p + "mlp.fc1.weight"), F1, D, round_up(F1, 128), &w.mx[W_FC1]))) return rc;
+            if ((rc = upload_mx(c, T(p + "mlp.fc2.weight"), D, F, round_up(D, 128), &w.mx[W_FC2]))) return rc;
         } else {
             if ((rc = upload_weight(c, T(p + "attn.qkv.weight"), 3 * D, D, round_up(3 * D, tn), &w.qkv_w, &w.q[W_QKV]))) return rc;
-            if ((rc = upload_weight(c, T(p + "mlp.fc1.weight"), 4 * D, D, round_up(4 * D, tn), &w.fc1_w, &w.q[W_FC1]))) return rc;
-            if ((rc = upload_weight(c, T(p + "mlp.fc2.weight"), D, 4 * D, round_up(D, tn), &w.fc2_w, &w.q[W_FC2]))) return rc;
+            if ((rc = upload_weight(c, T(p + "mlp.fc1.weight"), F1, D, round_up(F1, tn), &w.fc1_w, &w.q[W_FC1]))) return rc;
+            if ((rc = upload_weight(c, T(p + "mlp.fc2.weight"), D, F, round_up(D, tn), &w.fc2_w, &w.q[W_FC2]))) return rc;
         }
         if ((rc = upload_weight(c, T(p + "attn.proj.weight"), D, D, round_up(D, tn), &w.proj_w, &w.q[W_PROJ]))) return rc;
     }
@@ -321,13 +325,14 @@ int alloc_slice(vitx_ctx *c, vitx_ctx::Slice &sl, size_t hcols, bool internal) {
     if ((rc = c->dmalloc(&sl.QKV, Mpad * 3 * D * 2 * (c->prec_attn ? 2 : 1), true))) return rc;
     sl.qkv_lo_off = c->prec_attn ? (long)(Mpad * 3 * D) : 0;       // capacity; a forward places the lo plane right behind ITS rows (SliceForward)
     if ((rc = c->dmalloc(&sl.Hbuf, Mpad * hcols * 2, true))) return rc;
+    if (c->glu && (rc = c->dmalloc(&sl.Hg, Mpad * (size_t)c->F * 2, true))) return rc;
     if ((rc = c->dmalloc(&sl.Z, Bpad * D * 2 * (c->pool ? 2 : 1), true))) return rc;
     if (c->mx) {
-        const size_t kp = (size_t)mx_k_pad(D), kh = (size_t)mx_k_pad(4 * D);
+        const size_t kp = (size_t)mx_k_pad(D), kh = (size_t)mx_k_pad(c->F);
         if ((rc = c->dmalloc((void **)&sl.Umx, Mpad * kp * 33 / 32, true))) return rc;
         if ((rc = c->dmalloc((void **)&sl.U2mx, Mpad * kp * 33 / 32, true))) return rc;
         sl.Umx_s = sl.Umx + Mpad * kp; sl.U2mx_s = sl.U2mx + Mpad * kp;
-        sl.Hmx = (uint8_t *)sl.Hbuf; sl.Hmx_s = sl.Hmx + Mpad * kh;             // Mpad * kh * 33 / 32 <= Mpad * 4 D * 2 bytes of Hbuf
+        sl.Hmx = (uint8_t *)sl.Hbuf; sl.Hmx_s = sl.Hmx + Mpad * kh;             // Mpad * kh * 33 / 32 <= Mpad * F * 2 bytes of Hbuf
     }
     if ((c->cls_tail || c->map) && (rc = c->dmalloc((void **)&sl.Xc, Bpad * D * 4, true))) return rc;
     if (c->map && (rc = c->dmalloc(&sl.Mp, Bpad * c->H * D * 2, true))) return rc;
@@ -402,7 +407,7 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
     if (max_batch < 8 * ns) ns = 1;
     c->nslices = ns;
     c->slices.resize(ns);
-    const size_t hcols = std::max<size_t>((size_t)4 * D, (size_t)c->Kpe_pad);
+    const size_t hcols = std::max<size_t>((size_t)c->F1, (size_t)c->Kpe_pad);
     {
         // The kernels address every activation buffer with 32-bit BYTE offsets (buffer instructions): a sub-batch must keep its largest buffer --
         // the MLP hidden tensor, or the two QKV planes of the F16 parity mode -- below 0xf0000000 bytes (ViT-B: 3326 images per sub-batch, 2217 in

@@ -23,11 +23,11 @@ namespace vitx {
 
 enum ProfClass {
     PC_GEMM_PATCH = 0, PC_LAYERNORM, PC_GEMM_QKV, PC_ATTENTION, PC_GEMM_PROJ, PC_GEMM_FC1, PC_GEMM_FC2,
-    PC_GEMM_HEAD, PC_SOFTMAX, PC_DEQUANT, PC_ATTENTION_CLS, PC_GEMM_TAIL, PC_ATTN_MAP, PC_FEATURES, PC_HEAD_POOL, PC_ZEROSHOT, PC_ROPE, PC_COUNT
+    PC_GEMM_HEAD, PC_SOFTMAX, PC_DEQUANT, PC_ATTENTION_CLS, PC_GEMM_TAIL, PC_ATTN_MAP, PC_FEATURES, PC_HEAD_POOL, PC_ZEROSHOT, PC_ROPE, PC_SWIGLU, PC_COUNT
 };
 inline const char *const kProfNames[PC_COUNT] = {"patch_embed", "layernorm", "gemm_qkv_bias", "attention", "gemm_proj_resid",
                                     "gemm_fc1_gelu", "gemm_fc2_resid", "gemm_head", "softmax", "dequant_weights", "attention_cls", "gemm_cls_tail", "attention_map",
-                                    "features", "head_pool", "zeroshot", "rope"};
+                                    "features", "head_pool", "zeroshot", "rope", "swiglu"};
 static_assert(PC_COUNT <= VITX_PROF_MAX_CLASSES, "vitx_profile_read callers size their arrays by VITX_PROF_MAX_CLASSES");
 
 // A weight matrix kept in the file's block form on the device (quant.hip): `blocks` = N rows of K/32 blocks in the file's byte
@@ -80,7 +80,11 @@ struct vitx_ctx {
     // Token layout of an image (include/vitx.h "Register tokens and the pooled head"): row 0 = class token, rows 1 .. nreg = register tokens,
     // rows Tp .. N - 1 = patches in raster order; N = g * g + Tp
     int nreg = 0, Tp = 1;                // register tokens of the model (reg_token), prefix tokens 1 + nreg (0 for a VITX_POOL_MAP model: no class token)
-    int fc1_epi = EPI_BIAS_GELU;         // the fc1 epilogue of the model's activation (vitx_model_activation), taken once at creation
+    int fc1_epi = EPI_BIAS_GELU;         // the fc1 epilogue of the model's activation (vitx_model_activation), taken once at creation; EPI_BIAS in a `glu` context
+    // The MLP widths of the blocks: F = the hidden width, fc2's K; F1 = fc1's N.  4 D both, or -- a file with `glu` (include/vitx.h "gated MLP") --
+    // the file's F and 2 F: fc1 writes gate | up into Hbuf [Mpad][2 F], the gate kernel (swiglu.hip) the compact Hg [Mpad][F] that fc2 reads
+    int F = 0, F1 = 0;
+    bool glu = false;
     bool pool = false;                   // VITX_POOL_CLS_MEAN: the head reads concat(cls, mean of the patch tokens) of the final norm, K = 2 D
     bool map = false;                    // VITX_POOL_MAP: no class token; the head reads the attention-pooled embedding e (SliceForward::pooled_tail)
     int tm = 128, tn = 128;
@@ -169,7 +173,8 @@ struct vitx_ctx {
         int ln_blocks = 0;                       // Mpad / 256 of the slice's capacity
         void *QKV = nullptr;         // [Mpad][3D]; the parity mode's lo plane follows at qkv_lo_off elements
         long qkv_lo_off = 0;
-        void *Hbuf = nullptr;        // [Mpad][4D]  (also the im2col rows of the patch-embed GEMM)
+        void *Hbuf = nullptr;        // [Mpad][F1]: the fc1 output (4 D columns, or gate | up of a `glu` context)
+        void *Hg = nullptr;          // `glu` contexts only: [Mpad][F] = silu(gate) . up, the A operand of fc2 (nullptr otherwise: nothing is allocated)
         float *Xc = nullptr;         // [Bpad][D] f32 class-token rows of the residual stream through the last layer's tail (cls_tail)
         void *Z = nullptr;           // [Bpad][D] final-LN output of the cls rows; pooled head: [Bpad][2 D] = RNE(cls) ‖ RNE(mean of the patch rows); MAP head: RNE(e)
         void *Mp = nullptr;          // VITX_POOL_MAP: [Bpad][H][D] RNE(M), the A operand of the value projection (Xc holds a, then e, in f32)

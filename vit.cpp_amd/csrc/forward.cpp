@@ -94,6 +94,7 @@ struct SliceForward {
     vitx_ctx *c; vitx_ctx::Slice &sl; hipStream_t st; int first_img, n;
     const vitx_ctx::WeightSet &ws = *c->wset;
     const int D = c->D, N = c->N, tm = c->tm, tn = c->tn, dt = c->dtype;
+    const int F = c->F, F1 = c->F1;                                 // MLP widths: fc2's K and fc1's N (4 D both, or F and 2 F of a `glu` context)
     static constexpr double eb = 2.0;                               // operand bytes
     const int M_real = n * N, M = round_up(M_real, tm);            // token rows
     const long lo_off = c->prec_attn ? (long)M * 3 * D : 0;         // F16 parity mode: the lo plane of q, k, v right behind this sub-batch's hi plane (elements)
@@ -286,7 +287,7 @@ struct SliceForward {
         int rc;
         if ((rc = gemm(c, st, r.pc_proj, EPI_BIAS_RESID, dense_gemm(sl.U, Wl[W_PROJ], w.proj_b, r.X, r.M, r.M_real, D, round_up(D, tn), D), Fl[W_PROJ]))) return rc;
         if ((rc = layernorm_mx(r.X, w.ln2_w, w.ln2_b, sl.U2mx, sl.U2mx_s, r.M_real))) return rc;
-        if ((rc = gemm_mx(c, st, r.pc_fc1, EPI_BIAS_GELU, sl.U2mx, sl.U2mx_s, w.mx[W_FC1], w.fc1_b, sl.Hmx, sl.Hmx_s, r.M_real, mx_k_pad(4 * D)))) return rc;
+        if ((rc = gemm_mx(c, st, r.pc_fc1, EPI_BIAS_GELU, sl.U2mx, sl.U2mx_s, w.mx[W_FC1], w.fc1_b, sl.Hmx, sl.Hmx_s, r.M_real, mx_k_pad(F)))) return rc;
         if ((rc = gemm_mx(c, st, r.pc_fc2, EPI_BIAS_RESID, sl.Hmx, sl.Hmx_s, w.mx[W_FC2], w.fc2_b, r.X, nullptr, r.M_real, D))) return rc;
         if (nx && (rc = layernorm_mx(r.X, nx->ln1_w, nx->ln1_b, sl.Umx, sl.Umx_s, r.M_real))) return rc;
         if (!c->trace_ids.empty() && (rc = trace(il + 1))) return rc;
@@ -298,9 +299,15 @@ struct SliceForward {
         // output projection + residual (vit.cpp:868-873), then norm2 (vit.cpp:881-885) -> U2
         if ((rc = resid_gemm_ln(r, r.pc_proj, sl.U, Wl[W_PROJ], w.proj_b, D, Fl[W_PROJ], w.ln2_w, w.ln2_b, sl.U2, &fix_u2))) return rc;
         // MLP (vit.cpp:889-900), then the NEXT layer's norm1 (vit.cpp:808-812) -> U; the last layer is followed by the final norm instead
-        if ((rc = gemm(c, st, r.pc_fc1, c->fc1_epi, dense_gemm(sl.U2, Wl[W_FC1], w.fc1_b, sl.Hbuf, r.M, r.M_real, 4 * D, round_up(4 * D, tn), D), Fl[W_FC1], nullptr,
+        // a `glu` context (include/vitx.h "gated MLP"): fc1 with the plain bias epilogue -> gate | up [M][2 F]; the gate kernel -> the compact
+        // Hg [M][F] = silu(gate) . up; fc2 from that, lda == K as in any other model
+        if ((rc = gemm(c, st, r.pc_fc1, c->fc1_epi, dense_gemm(sl.U2, Wl[W_FC1], w.fc1_b, sl.Hbuf, r.M, r.M_real, F1, round_up(F1, tn), D), Fl[W_FC1], nullptr,
                        fix_u2.todo ? &fix_u2 : nullptr))) return rc;
-        if ((rc = resid_gemm_ln(r, r.pc_fc2, sl.Hbuf, Wl[W_FC2], w.fc2_b, 4 * D, Fl[W_FC2], nx ? nx->ln1_w : nullptr, nx ? nx->ln1_b : nullptr, sl.U, &fix_u))) return rc;
+        if (c->glu) {
+            ProfScope ps(c, st, PC_SWIGLU, 0, (double)r.M_real * 3 * F * eb);
+            HIP_TRY(launch_swiglu(dt, sl.Hbuf, F1, sl.Hg, F, r.M_real, F, st));
+        }
+        if ((rc = resid_gemm_ln(r, r.pc_fc2, c->glu ? sl.Hg : sl.Hbuf, Wl[W_FC2], w.fc2_b, F, Fl[W_FC2], nx ? nx->ln1_w : nullptr, nx ? nx->ln1_b : nullptr, sl.U, &fix_u))) return rc;
         if (!c->trace_ids.empty() && (rc = trace(il + 1))) return rc;
         return features(il, tail_now, c->pool && il + 1 == c->L ? sl.Z : nullptr);
     }
@@ -325,7 +332,7 @@ struct SliceForward {
             hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
             if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
             fuse = cs == hipStreamCaptureStatusNone && gemm_ln_fusable(*c->tune, dense_gemm(nullptr, nullptr, nullptr, nullptr, M, M, D, round_up(D, tn), D)) &&
-                   gemm_ln_fusable(*c->tune, dense_gemm(nullptr, nullptr, nullptr, nullptr, M, M, D, round_up(D, tn), 4 * D));
+                   gemm_ln_fusable(*c->tune, dense_gemm(nullptr, nullptr, nullptr, nullptr, M, M, D, round_up(D, tn), F));
         }
         const Rows all_rows{sl.X, M, M_real, PC_GEMM_PROJ, PC_GEMM_FC1, PC_GEMM_FC2, fuse};
         const Rows cls_rows{sl.Xc, round_up(n, tm), n, PC_GEMM_TAIL, PC_GEMM_TAIL, PC_GEMM_TAIL, false};
@@ -397,7 +404,7 @@ static void split_batch(const vitx_ctx *c, int n, int ns, int *m) {
     if (c->split_first > 0 && ns == 2 && c->split_first < n) { m[0] = c->split_first; m[1] = n - c->split_first; return; }
     if (ns != 2) return;
     const int n_cu = c->tune->n_cu;
-    const int D = c->D;
+    const int D = c->D, F = c->F, F1 = c->F1;
     const bool ln = c->ln_fuse && c->slices[0].ln_sync;
     if (ln) {
         // LayerNorm-fusing residual GEMMs run rounds of (CUs / 8 / ntn) * ntn workgroups per XCD: the first sub-batch takes as many images as
@@ -410,8 +417,8 @@ static void split_batch(const vitx_ctx *c, int n, int ns, int *m) {
     auto layer = [&](int imgs) {
         const long rows = (long)imgs * c->N;
         const bool fl = ln && ((rows + 255) / 256) * (D / 256) >= 128;        // the fused kernel needs the wide path (is_wide, gemm.hip)
-        return gemm_round_cost(rows, 3 * D, D, n_cu) + gemm_round_cost(rows, 4 * D, D, n_cu) +
-               (fl ? gemm_round_cost_ln(rows, D, D, n_cu) + gemm_round_cost_ln(rows, D, 4 * D, n_cu) : gemm_round_cost(rows, D, D, n_cu) + gemm_round_cost(rows, D, 4 * D, n_cu));
+        return gemm_round_cost(rows, 3 * D, D, n_cu) + gemm_round_cost(rows, F1, D, n_cu) +
+               (fl ? gemm_round_cost_ln(rows, D, D, n_cu) + gemm_round_cost_ln(rows, D, F, n_cu) : gemm_round_cost(rows, D, D, n_cu) + gemm_round_cost(rows, D, F, n_cu));
     };
     double best = layer(m[0]) + layer(m[1]);
     for (int s1 = std::max(8, n / 4); s1 <= n / 2; ++s1) {

@@ -228,6 +228,10 @@ bool attention_text_supports(int T, int D, int H);
 // v columns, prefix rows and everything behind row n_img * N untouched.  Any even head dim; 16-byte accesses where hd / 2 is a multiple of 8.
 hipError_t launch_rope(int dtype, void *qkv, long lo_off, const float *cos, const float *sin, int n_img, int N, int prefix, int D, int H, hipStream_t stream);
 bool rope_supports(int D, int H);
+// The gate of a gated MLP (swiglu.hip; include/vitx.h "gated MLP"): in [rows][ld_in] of `dtype`, gate in columns 0 .. F-1, up in F .. 2F-1 ->
+// out[r][j] = RNE(silu(f32 gate) * f32 up), j < F, rows of ld_out elements; nothing else of `out` is touched.  hipErrorInvalidValue, before any
+// launch, for F % 8 != 0, a pointer off a 16-byte boundary, a leading dimension that is no multiple of 8, ld_in < 2 F or ld_out < F.
+hipError_t launch_swiglu(int dtype, const void *in, long ld_in, void *out, long ld_out, long rows, int F, hipStream_t stream);
 // pos [1 + gy_in * gx_in][D] f32 -> out [1 + gy_out * gx_out][D] f32 (pos_resample.hip; the arithmetic: pos_resample.h); only enqueues
 hipError_t launch_pos_resample(const float *pos, int gy_in, int gx_in, int D, int gy_out, int gx_out, int interp, float *out, hipStream_t stream);
 bool attention_supports(int N, int D, int H);     // any token count; head_dim 64 (tuned kernels) or any other multiple of 8 up to 128 (generic kernel)

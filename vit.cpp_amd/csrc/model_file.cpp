@@ -14,6 +14,8 @@
 // One more (include/vitx.h "no class token and the attention-pooling head"): the thirteen `attn_pool.*` tensors of a SigLIP-class model, which
 // come without cls_token / reg_token and with a pos_embed of g^2 rows (VITX_POOL_MAP).
 // One more (include/vitx.h "rotary position embeddings"): `rope` f32 [4] = {kind, theta, 0, 0} of a DINOv3-class model; its pos_embed is all zero.
+// One more (include/vitx.h "gated MLP"): `glu` f32 [4] = {kind, F, 0, 0} in front of the first blocks.* record; mlp.fc1.* then has 2 F rows and
+// mlp.fc2.weight rows of F.
 // A text-tower file (include/vitx.h "the text tower") is told by patch_size == 0: token_embed.weight [V][D] (f16 or f32) and pos_embed [T][D]
 // in place of the image front, the same blocks, norm.* and head.* [E][D]; `arch` is then required and its last two slots are {causal, eos + 1};
 // `zs` f32 [4] = {kind, scale, bias, 0} is optional.  cls_token, reg_token, pre_norm.*, preproc and attn_pool.* do not belong in one.
@@ -179,11 +181,12 @@ static int load_impl(const char *path, vitx_model &m) {
         if (len && fread(&v[0], 1, (size_t)len, f) != (size_t)len) { set_error("vitx_model_load: truncated id2label"); return VITX_ERR_IO; }
         m.id2label[key] = v;
     }
-    const auto expect = expected_tensors(hp);
+    auto expect = expected_tensors(hp);                              // (`glu` rewrites the MLP shapes of every block: it stands in front of them)
     const auto pool_expect = text ? std::map<std::string, Expect>() : pool_tensors(hp);
     int n_optional = 0;                                              // `arch`, `preproc`, `pre_norm.*` records seen
     int n_pool = 0;                                                  // `attn_pool.*` records seen
     bool pos_no_cls = false;                                         // pos_embed has g^2 rows (no class row)
+    bool seen_block = false;                                         // a blocks.* record has been read
     for (;;) {
         int32_t n_dims, name_len, ttype;
         if (!rd_i32(n_dims)) break;                                  // clean EOF (vit.cpp:600-603)
@@ -267,6 +270,35 @@ static int load_impl(const char *path, vitx_model &m) {
             ++n_optional;
             continue;
         }
+        if (t.name == "glu") {                                       // optional: f32 [4] = {kind, F, 0, 0} (include/vitx.h "gated MLP")
+            if (m.index.count(t.name)) { set_error("vitx_model_load: duplicate tensor '%s'", t.name.c_str()); return VITX_ERR_FORMAT; }
+            if (text) { set_error("vitx_model_load: text-tower file: tensor 'glu' belongs to image files"); return VITX_ERR_FORMAT; }
+            if (ttype != T_F32 || n_dims != 1 || t.ne[0] != 4) {
+                set_error("vitx_model_load: tensor 'glu' must be f32 [4] = {kind, F, 0, 0}: got type %d, %d dims [%lld, ..]", ttype, n_dims, (long long)t.ne[0]);
+                return VITX_ERR_FORMAT;
+            }
+            if (seen_block) { set_error("vitx_model_load: tensor 'glu' stands behind a blocks.* record: it sets their shapes and must come in front of the first one"); return VITX_ERR_FORMAT; }
+            t.raw.resize(16);
+            if (fread(t.raw.data(), 1, 16, f) != 16) { set_error("vitx_model_load: tensor '%s' is truncated", t.name.c_str()); return VITX_ERR_IO; }
+            float a[4]; memcpy(a, t.raw.data(), 16);
+            if (a[0] != (float)VITX_GLU_SWIGLU) { set_error("vitx_model_load: tensor 'glu' names kind %g: only 1 (SwiGLU) exists", (double)a[0]); return VITX_ERR_FORMAT; }
+            if (!(a[1] >= 64.0f) || a[1] > 16777216.0f || a[1] != floorf(a[1]) || (int64_t)a[1] % 64) {
+                set_error("vitx_model_load: tensor 'glu' carries the hidden width %g: it must be a whole number, at least 64 and a multiple of 64 (the GEMMs' K step)", (double)a[1]);
+                return VITX_ERR_FORMAT;
+            }
+            if (a[2] != 0.0f || a[3] != 0.0f) { set_error("vitx_model_load: tensor 'glu' has reserved slots {%g, %g}: they must be 0", (double)a[2], (double)a[3]); return VITX_ERR_FORMAT; }
+            m.glu_kind = (int)a[0]; m.glu_width = (int)a[1];
+            const int64_t D = hp.hidden_size, F = m.glu_width;
+            for (int i = 0; i < hp.num_hidden_layers; ++i) {
+                const std::string p = "blocks." + std::to_string(i) + ".mlp.";
+                expect[p + "fc1.weight"] = {{D, 2 * F, 1, 1}, 1}; expect[p + "fc1.bias"] = {{2 * F, 1, 1, 1}, 0};
+                expect[p + "fc2.weight"] = {{F, D, 1, 1}, 1};
+            }
+            m.index[t.name] = (int)m.tensors.size();
+            m.tensors.push_back(std::move(t));
+            ++n_optional;
+            continue;
+        }
         if (t.name == "preproc") {                                   // optional: f32 [16], the model's own preprocessing (include/vitx.h "each model's own preprocessing")
             if (m.index.count(t.name)) { set_error("vitx_model_load: duplicate tensor '%s'", t.name.c_str()); return VITX_ERR_FORMAT; }
             if (ttype != T_F32 || n_dims != 1 || t.ne[0] != 16) {
@@ -307,6 +339,7 @@ static int load_impl(const char *path, vitx_model &m) {
         if (m.index.count(t.name)) { set_error("vitx_model_load: duplicate tensor '%s'", t.name.c_str()); return VITX_ERR_FORMAT; }
         Expect ex = *known;
         if (is_pool) ++n_pool;
+        if (t.name.compare(0, 7, "blocks.") == 0) seen_block = true;
         // attn_pool.latent is [1][1][D] (ggml dims [D, 1, 1]); a model without a class token has a pos_embed of g^2 rows (checked against attn_pool.* below)
         if (t.name == "token_embed.weight" && n_dims == 2) { ex.ne[1] = t.ne[1]; m.vocab = (int)t.ne[1]; }      // V: any row count
         if (!text && t.name == "pos_embed" && t.ne[1] == ex.ne[1] - 1 && t.ne[1] >= 1) { ex.ne[1] -= 1; pos_no_cls = true; }
@@ -355,6 +388,7 @@ static int load_impl(const char *path, vitx_model &m) {
     const bool has_cls = m.find("cls_token") != nullptr;
     if (n_pool) {
         if (m.rope_kind) { set_error("vitx_model_load: tensor 'rope' together with attn_pool.*: the attention-pooling head has no rotary form"); return VITX_ERR_FORMAT; }
+        if (m.glu_kind) { set_error("vitx_model_load: tensor 'glu' together with attn_pool.*: the attention-pooling head's MLP has no gated form"); return VITX_ERR_FORMAT; }
         for (const auto &kv : pool_expect)
             if (!m.find(kv.first)) { set_error("vitx_model_load: the attention-pooling head is incomplete: tensor '%s' is missing (%d of %d attn_pool.* tensors)", kv.first.c_str(), n_pool, (int)pool_expect.size()); return VITX_ERR_FORMAT; }
         if (has_cls || m.num_registers) { set_error("vitx_model_load: attn_pool.* together with '%s': a model with the attention-pooling head has no class or register token", has_cls ? "cls_token" : "reg_token"); return VITX_ERR_FORMAT; }
@@ -447,6 +481,12 @@ int vitx_model_rope(const vitx_model *m, int *kind, float *theta) {
     if (!m || !m->rope_kind) return 0;
     if (kind) *kind = m->rope_kind;
     if (theta) *theta = m->rope_theta;
+    return 1;
+}
+int vitx_model_glu(const vitx_model *m, int *kind, int *width) {
+    if (!m || !m->glu_kind) return 0;
+    if (kind) *kind = m->glu_kind;
+    if (width) *width = m->glu_width;
     return 1;
 }
 // DINOv3's axial table (include/vitx.h "rotary position embeddings"): double throughout, cos / sin rounded once to f32

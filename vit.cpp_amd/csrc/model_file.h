@@ -38,6 +38,10 @@ struct vitx_model {
     bool has_pre_norm = false;                        // `pre_norm.weight` / `pre_norm.bias` [D]: LayerNorm of every token row in front of layer 0
     int rope_kind = VITX_ROPE_NONE;                   // `rope` [4] = {kind, theta, 0, 0}: rotary position embeddings on q and k of the patch tokens (include/vitx.h)
     float rope_theta = 0.0f;
+    int glu_kind = VITX_GLU_NONE;                     // `glu` [4] = {kind, F, 0, 0}: a gated MLP (include/vitx.h "gated MLP"); fc1 is then [2 F][D], fc2 [D][F]
+    int glu_width = 0;                                // F, the MLP hidden width of such a file (fc2's K); 0 without `glu`: the width is 4 D
+    int mlp_hidden() const { return glu_kind ? glu_width : 4 * hp.hidden_size; }          // F: fc2's K
+    int mlp_fc1_rows() const { return glu_kind ? 2 * glu_width : 4 * hp.hidden_size; }    // F1: fc1's N
     bool has_preproc = false;                         // `preproc` [16]: the model's own preprocessing (include/vitx.h); without it `preproc` is the reference default
     vitx_preproc preproc;
     // a text-tower file (patch_size == 0; include/vitx.h "the text tower"): hp.img_size = T, hp.num_classes = E

@@ -183,6 +183,15 @@ int vitx_op_rope(int dtype, void *d_qkv, long lo_off, const void *d_cos, const v
     if (!rope_supports(D, H)) { set_error("vitx_op_rope: D must be a multiple of H and the head dim even (D %d, H %d)", D, H); return VITX_ERR_UNSUPPORTED; }
     return op_rc("vitx_op_rope", launch_rope(dtype, d_qkv, lo_off, (const float *)d_cos, (const float *)d_sin, n_img, N, prefix, D, H, (hipStream_t)stream), VITX_ERR_UNSUPPORTED);
 }
+// The gate of a gated MLP (swiglu.hip; include/vitx.h "gated MLP").  Every check comes before the launch; only enqueues.
+int vitx_op_swiglu(int dtype, const void *d_in, long ld_in, void *d_out, long ld_out, long rows, int F, void *stream) {
+    if (!d_in || !d_out || rows <= 0 || F <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_swiglu: invalid argument"); return VITX_ERR_ARG; }
+    if (F % 8 || ld_in % 8 || ld_out % 8 || ld_in < 2L * F || ld_out < F || (uintptr_t)d_in % 16 || (uintptr_t)d_out % 16) {
+        set_error("vitx_op_swiglu: F, ld_in and ld_out must be multiples of 8, ld_in >= 2 F, ld_out >= F and both pointers on 16-byte boundaries (F %d, ld_in %ld, ld_out %ld)", F, ld_in, ld_out);
+        return VITX_ERR_ARG;
+    }
+    return op_rc("vitx_op_swiglu", launch_swiglu(dtype, d_in, ld_in, d_out, ld_out, rows, F, (hipStream_t)stream), VITX_ERR_ARG);
+}
 // The parity mode's attention on f32 q, k, v (what the reference multiplies, vit.cpp:848,858): splits the rows into the two fp16 planes the
 // QKV GEMM's EPI_BIAS_HILO epilogue emits, then runs the precise streaming kernel.  Synchronous (allocates its own scratch).
 int vitx_op_attention_f32(const float *qkv_f32, void *out, int n_img, int N, int D, int H, void *stream) {

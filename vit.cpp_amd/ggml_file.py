@@ -21,6 +21,8 @@ One more ("each model's own preprocessing"): `preproc` f32 [16] = {resize_mode, 
 r g b, 0, 0, 0, 0}, directly after `arch` (first without it): preproc_slots builds it, write_model(preproc=) places it, ModelFile.preproc reads it.
 One more ("no class token and the attention-pooling head"): the thirteen `attn_pool.*` tensors after norm.bias, in a file without cls_token whose
 pos_embed has g^2 rows.  `attn_pool.latent` [1][1][D] stays f32; the matrices are f16 under every ftype >= 1: they are never block-quantised.
+One more ("gated MLP"): `glu` f32 [4] = {1, F, 0, 0}, in front of the first blocks.* tensor (directly after `arch` / `rope`): every mlp.fc1.weight is
+then [2 F][D] (gate rows, then up rows), mlp.fc1.bias [2 F] and mlp.fc2.weight [D][F]; write_model checks those shapes and the tensor's place.
 """
 from __future__ import annotations
 
@@ -290,6 +292,19 @@ def write_model(path: str, hp: HParams, tensors: Dict[str, np.ndarray], id2label
             raise ValueError(f"head.weight must be [C][{D}] (class-token head) or [C][{2 * D}] (cls + mean head), got {hw}")
         if head_pool is not None and hw[1] != (2 * D if head_pool else D):
             raise ValueError(f"head_pool={head_pool}, but head.weight is {hw}")
+    if "glu" in tensors:
+        glu = np.asarray(tensors["glu"], np.float32).reshape(-1)
+        F = int(glu[1]) if glu.shape == (4,) else 0
+        if glu.shape != (4,) or glu[0] != 1 or glu[1] != F or F < 64 or F % 64 or glu[2] != 0 or glu[3] != 0:
+            raise ValueError(f"glu must be [1, F, 0, 0] with F a multiple of 64, got {glu}")
+        names = list(tensors)
+        if any(k.startswith("blocks.") for k in names[:names.index("glu")]):
+            raise ValueError("glu is written in front of the first blocks.* tensor")
+        for i in range(hp.num_hidden_layers):
+            p = f"blocks.{i}.mlp."
+            have = tuple(tuple(np.shape(tensors[p + k])) for k in ("fc1.weight", "fc1.bias", "fc2.weight"))
+            if have != ((2 * F, D), (2 * F,), (D, F)):
+                raise ValueError(f"glu = {F}: {p}fc1.weight / fc1.bias / fc2.weight must be {(2 * F, D)}, {(2 * F,)}, {(D, F)}, got {have}")
     id2label = id2label if id2label is not None else {i: f"LABEL_{i}" for i in range(hp.num_classes)}
     with open(path, "wb") as f:
         f.write(struct.pack("<i", GGML_MAGIC))

@@ -50,20 +50,23 @@ def hparams_for(name: str, ftype: int = 1) -> HParams:
     return HParams(*CONFIGS[name], ftype=ftype)
 
 
-def gflop_per_image(hp: HParams) -> float:
-    """2 x MACs of every GEMM in the graph (elementwise excluded)."""
+def gflop_per_image(hp: HParams, glu: int = 0) -> float:
+    """2 x MACs of every GEMM in the graph (elementwise excluded).  glu = F: a file with the `glu` tensor (a gated MLP of hidden
+    width F: fc1 is [2 F][D], fc2 [D][F]); 0: the 4 x hidden MLP."""
     D, L, h, C, P = hp.hidden_size, hp.num_hidden_layers, hp.num_attention_heads, hp.num_classes, hp.patch_size
     g = hp.img_size // P
     N = g * g + 1
     d = D // h
-    per_layer = N * D * 3 * D + 2 * h * N * N * d + N * D * D + 2 * N * D * 4 * D
+    per_layer = N * D * 3 * D + 2 * h * N * N * d + N * D * D + (3 * N * D * glu if glu else 2 * N * D * 4 * D)
     return 2.0 * (g * g * 3 * P * P * D + L * per_layer + D * C) / 1e9
 
 
 def make_weights(hp: HParams, seed: int = 1234, head_scale: float = 8.0, in_chans: int = 3, registers: int = 0, head_pool: int = 0,
-                 reg_scale: float = 1.0) -> Dict[str, np.ndarray]:
+                 reg_scale: float = 1.0, glu: int = 0) -> Dict[str, np.ndarray]:
     """registers > 0 adds `reg_token` [1][R][D] (x reg_scale), head_pool = 1 widens head.weight to [C][2 D] (cls ‖ mean of the patch tokens).
-    Both are drawn AFTER every draw of the plain model, so files without them keep their bytes (tests/golden/weights_sha1.json)."""
+    Both are drawn AFTER every draw of the plain model, so files without them keep their bytes (tests/golden/weights_sha1.json).
+    glu = F > 0: a gated MLP of hidden width F (include/vitx.h "gated MLP") -- `glu` = {1, F, 0, 0} in front, mlp.fc1 [2 F][D] / [2 F] (gate rows, then
+    up rows) and mlp.fc2.weight [D][F]; such a file draws other numbers than the plain one from the first block on."""
     rng = np.random.default_rng(seed)
     D, L, C, P = hp.hidden_size, hp.num_hidden_layers, hp.num_classes, hp.patch_size
     N = hp.n_tokens
@@ -74,7 +77,10 @@ def make_weights(hp: HParams, seed: int = 1234, head_scale: float = 8.0, in_chan
     def vec(n, mean=0.0):
         return (np.float32(mean) + rng.standard_normal(n, dtype=np.float32) * np.float32(0.02)).astype(np.float32)
 
+    F1, Fh = (2 * glu, glu) if glu else (4 * D, 4 * D)          # fc1's rows, fc2's row length
     t: Dict[str, np.ndarray] = {}
+    if glu:
+        t["glu"] = np.array([1, glu, 0, 0], np.float32)
     t["cls_token"] = mat(1, 1, D)
     t["pos_embed"] = mat(1, N, D)
     t["patch_embed.proj.weight"] = mat(D, in_chans, P, P)
@@ -85,8 +91,8 @@ def make_weights(hp: HParams, seed: int = 1234, head_scale: float = 8.0, in_chan
         t[p + "attn.qkv.weight"] = mat(3 * D, D); t[p + "attn.qkv.bias"] = vec(3 * D)
         t[p + "attn.proj.weight"] = mat(D, D); t[p + "attn.proj.bias"] = vec(D)
         t[p + "norm2.weight"] = vec(D, 1.0); t[p + "norm2.bias"] = vec(D)
-        t[p + "mlp.fc1.weight"] = mat(4 * D, D); t[p + "mlp.fc1.bias"] = vec(4 * D)
-        t[p + "mlp.fc2.weight"] = mat(D, 4 * D); t[p + "mlp.fc2.bias"] = vec(D)
+        t[p + "mlp.fc1.weight"] = mat(F1, D); t[p + "mlp.fc1.bias"] = vec(F1)
+        t[p + "mlp.fc2.weight"] = mat(D, Fh); t[p + "mlp.fc2.bias"] = vec(D)
     t["norm.weight"] = vec(D, 1.0); t["norm.bias"] = vec(D)
     t["head.weight"] = (mat(C, D) * np.float32(head_scale)).astype(np.float32)
     t["head.bias"] = vec(C)
