@@ -22,6 +22,7 @@ CONFIGS = {
     "vit_micro_patch16_64": (128, 2, 2, 10, 16, 64),       # test-only toy (N=17)
     "vit_nano_patch16_32": (64, 2, 1, 10, 16, 32),         # test-only toy of the preprocessing tests: 2 x 2 patches (N = 5), one head of 64
     "vit_micro_patch14_56": (128, 2, 2, 10, 14, 56),       # test-only toy at DINOv2's patch size (16 patches: N = 17, or 21 with 4 register tokens)
+    "vit_wide_patch16_32": (512, 3, 8, 10, 16, 32),        # test-only toy of the LayerNorm-fusing GEMMs: two 256-column tiles per row block, 2 x 2 patches (N = 5, 9 with 4 registers, 4 without a class token)
     "vit_base_patch14_224": (768, 12, 12, 1000, 14, 224),  # DINOv2 ViT-B/14 (257 tokens, 261 with 4 register tokens)
     "vit_micro_c37_patch16_64": (128, 2, 2, 37, 16, 64),   # test-only toy with an ODD class count (the head GEMM's last column group is ragged)
     "vit_micro_c21843_patch16_64": (128, 2, 2, 21843, 16, 64),   # test-only toy with ImageNet-21k's class count (timm *_in21k heads): 86 column tiles of the head GEMM, a 21843-wide class softmax
