@@ -649,13 +649,26 @@ int vitx_trace_read(vitx_ctx *c, float *out, size_t n_floats);
  * vitx_op_attention_map: the kernels on their own (device pointers; only enqueues): d_cls [n_img][H][N] class-token maps, d_mean
  *   [n_img][N][N] mean_h A_h (N <= 1024); either may be NULL.  d_qkv [n_img * N][3 D] as the qkv projection writes it; lo_off != 0: the lo
  *   plane of the F16 parity mode lies lo_off elements behind (VITX_F16 only, a multiple of 8, at least n_img * N * 3 D).  head_dim: any
- *   multiple of 8 up to 128. */
+ *   multiple of 8 up to 128.
+ * The three rollout kernels on their own (device pointers, f32 matrices; only enqueue; every check comes before the launch; N <= 1024, above
+ * it VITX_ERR_UNSUPPORTED; a null pointer or n_img, N, H <= 0: VITX_ERR_ARG):
+ *   vitx_op_rollout_factor: d_out [n_img][N][N] = A^ = 0.5 mean_h A_h + 0.5 I of d_qkv (arguments and checks of vitx_op_attention_map).  An
+ *     entry is float(0.5) * m + float(0.5) * [i == j] in f32 with no contraction, m the entry vitx_op_attention_map's d_mean holds.
+ *   vitx_op_rollout_step: d_a [n_img][N][N] <- d_a . d_r per image, in place over d_a (the forward's R_l = A^_l R_(l-1), f32 products and
+ *     sums in an unspecified order).  d_r [n_img][N][N] is only read; ranges of d_a and d_r that overlap are VITX_ERR_ARG.
+ *   vitx_op_rollout_row: d_out[b * out_stride + k] = sum_j w_j d_r[b][j][k] for k < N, with w_j = 0.5 mean_h d_cls[b * cls_stride + h * N + j]
+ *     + 0.5 [j == 0] (row 0 of the last factor from that layer's class-token maps; the head sum in ascending h, times float(1 / H)); d_r NULL
+ *     (a one-layer model): d_out = w.  Strides in floats; cls_stride < H * N or out_stride < N: VITX_ERR_ARG.  Nothing is written beyond
+ *     the N floats of each output row. */
 #define VITX_ATTN_ROLLOUT 1
 int vitx_attn_enable(vitx_ctx *c, uint64_t layer_mask, int flags);
 int vitx_attn_floats(const vitx_ctx *c);
 int vitx_attn_images(const vitx_ctx *c);
 int vitx_attn_read(vitx_ctx *c, float *out, size_t n_floats);
 int vitx_op_attention_map(int dtype, const void *d_qkv, long lo_off, void *d_cls, void *d_mean, int n_img, int N, int D, int H, void *stream);
+int vitx_op_rollout_factor(int dtype, const void *d_qkv, long lo_off, void *d_out, int n_img, int N, int D, int H, void *stream);
+int vitx_op_rollout_step(void *d_a, const void *d_r, int n_img, int N, void *stream);
+int vitx_op_rollout_row(const void *d_cls, long cls_stride, const void *d_r, void *d_out, long out_stride, int n_img, int N, int H, void *stream);
 
 /* ---- image embeddings and token features (what retrieval, probes and dense heads read) --------- */
 /* Opt-in outputs of the forward, for classifier contexts of every operand type (the residual stream is f32 in all of them).

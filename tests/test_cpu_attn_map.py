@@ -22,6 +22,24 @@ def test_attention_map_calls_without_a_context_are_argument_errors(binding):
     assert L.vitx_op_attention_map(0, None, 0, None, None, 1, 197, 768, 12, None) == 3
 
 
+def test_rollout_entry_points_refuse_bad_arguments_before_any_device_call(binding):
+    """The refusals need no device: they come first (pointers that are never dereferenced)."""
+    L = binding.lib()
+    for s in ("vitx_op_rollout_factor", "vitx_op_rollout_step", "vitx_op_rollout_row"):
+        assert s in binding.EXPORTS and hasattr(L, s)
+    a, r = 0x100000, 0x200000
+    assert L.vitx_op_rollout_factor(0, None, 0, a, 1, 197, 768, 12, None) == 3 and L.vitx_op_rollout_factor(0, a, 0, None, 1, 197, 768, 12, None) == 3
+    assert L.vitx_op_rollout_factor(0, a, 0, r, 1, 1025, 768, 12, None) == 5 and L.vitx_op_rollout_factor(0, a, 0, r, 1, 197, 800, 32, None) == 5
+    assert L.vitx_op_rollout_step(None, r, 1, 8, None) == 3 and L.vitx_op_rollout_step(a, None, 1, 8, None) == 3
+    assert L.vitx_op_rollout_step(a, r, 0, 8, None) == 3 and L.vitx_op_rollout_step(a, r, 1, 0, None) == 3 and L.vitx_op_rollout_step(a, r, 1, 1025, None) == 5
+    for aa, rr in ((a, a), (a, a + 4 * 63), (a + 4 * 63, a)):               # one image of 8 x 8 floats: 256 bytes
+        assert L.vitx_op_rollout_step(aa, rr, 1, 8, None) == 3
+        assert b"overlap" in L.vitx_last_error()
+    assert L.vitx_op_rollout_row(None, 16, None, a, 8, 1, 8, 2, None) == 3 and L.vitx_op_rollout_row(a, 16, None, None, 8, 1, 8, 2, None) == 3
+    assert L.vitx_op_rollout_row(a, 15, None, r, 8, 1, 8, 2, None) == 3 and L.vitx_op_rollout_row(a, 16, None, r, 7, 1, 8, 2, None) == 3
+    assert L.vitx_op_rollout_row(a, 16, None, r, 8, 1, 8, 0, None) == 3 and L.vitx_op_rollout_row(a, 2050, None, r, 1025, 1, 1025, 2, None) == 5
+
+
 def test_attn_pgm_upsamples_by_nearest_neighbour_and_scales_to_255(pkg):
     from vitcpp_amd import cli
     grid = np.arange(16, dtype=np.float32).reshape(4, 4)[::-1].copy()

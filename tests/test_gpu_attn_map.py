@@ -39,13 +39,15 @@ def _maps64(q, k, H):
 
 
 # ------------------------------------------------------------------------------------------------ op level
-OP_SHAPES = [(7, 197, 768, 12), (3, 577, 1024, 16), (5, 50, 192, 3), (4, 65, 256, 8), (2, 197, 256, 2), (3, 17, 64, 4), (9, 1, 128, 2)]
+OP_SHAPES = [(7, 197, 768, 12), (3, 577, 1024, 16), (5, 50, 192, 3), (4, 65, 256, 8), (2, 197, 256, 2), (3, 17, 64, 4), (9, 1, 128, 2),
+             # head dims 24, 40, 56, 72: hd / 8 = 3, 5, 7, 9 pieces of 16 bytes per key row, the class-token map's lane groups of 4, 8, 8, 16 with idle lanes
+             (3, 50, 72, 3), (2, 65, 80, 2), (2, 33, 112, 2), (2, 197, 144, 2)]
 
 
 @pytest.mark.parametrize("mode", ["bf16", "f16", "f16_planes"])
 @pytest.mark.parametrize("n_img,N,D,H,mean", [s + (True,) for s in OP_SHAPES] + [(2, 785, 64, 8, False)])
 def test_op_attention_map_against_float64(binding, torch_gpu, mode, n_img, N, D, H, mean):
-    """Head dims 8 .. 128, 1 .. 785 tokens.  Scores drawn with a spread of several units: peaked rows, not uniform ones."""
+    """Head dims 8 .. 128 (1, 2, 3, 4, 5, 7, 8, 9 and 16 pieces of 16 bytes per key row), 1 .. 785 tokens.  Scores drawn with a spread of several units: peaked rows, not uniform ones."""
     torch = torch_gpu
     rows = n_img * N
     rng = np.random.default_rng(n_img * 7 + N * 13 + D + H)
@@ -105,13 +107,18 @@ MODES = {"bf16": (1, {}), "f16": (0, {}), "f16_fast": (0, {"f16_fast_attention":
 # test-only toys (registered at run time): three layers, so that rollout runs its in-place step (layers 1 .. L-2), at 401 and 785 tokens
 # (the step's and the head mean's 8- and 16-tile builds); and one beyond rollout's 1024 tokens
 EXTRA_CONFIGS = {"vit_micro3_patch8_160": (128, 3, 2, 10, 8, 160), "vit_micro3_patch8_224": (128, 3, 2, 10, 8, 224),
-                 "vit_micro_patch4_128": (128, 2, 2, 10, 4, 128)}
+                 "vit_micro_patch4_128": (128, 2, 2, 10, 4, 128),
+                 # 122 tokens: the step's 2-tile build, N % 4 == 2;  26 tokens in one layer: rollout is the row kernel without r;  in two
+                 # layers: head mean, then the row kernel, no step;  25 patches + class token + 2 registers = 28 tokens: N % 4 == 0
+                 "vit_micro3_patch8_88": (128, 3, 2, 10, 8, 88), "vit_micro1_patch16_80": (128, 1, 2, 10, 16, 80),
+                 "vit_micro_patch16_80": (128, 2, 2, 10, 16, 80), "vit_micro3_patch8_40": (128, 3, 2, 10, 8, 40)}
+EXTRA_REGISTERS = {"vit_micro3_patch8_40": 2}
 
 
 def _synthetic(pkg, name):
     if name in EXTRA_CONFIGS:
         pkg.synth.CONFIGS.setdefault(name, EXTRA_CONFIGS[name])
-    return pkg.synth.cached_synthetic(name, head_scale=4.0)
+    return pkg.synth.cached_synthetic(name, head_scale=4.0, registers=EXTRA_REGISTERS.get(name, 0))
 
 
 def _round(torch, a, dtype):
@@ -144,7 +151,8 @@ def _layer_maps_from_trace(torch, model, trace, dtype, round_qkv, n_img):
 
 
 @pytest.mark.parametrize("mode", list(MODES))
-@pytest.mark.parametrize("name,n_img", [("vit_tiny_patch16_224", 3), ("vit_base_patch16_224", 2), ("vit_micro3_patch8_160", 3), ("vit_micro3_patch8_224", 2)])
+@pytest.mark.parametrize("name,n_img", [("vit_tiny_patch16_224", 3), ("vit_base_patch16_224", 2), ("vit_micro3_patch8_160", 3), ("vit_micro3_patch8_224", 2),
+                                        ("vit_micro3_patch8_88", 3), ("vit_micro1_patch16_80", 3), ("vit_micro_patch16_80", 3), ("vit_micro3_patch8_40", 3)])
 def test_maps_and_rollout_match_a_float64_recompute_from_the_trace(pkg, binding, torch_gpu, mode, name, n_img):
     torch = torch_gpu
     dtype, opts = MODES[mode]
@@ -170,7 +178,8 @@ def test_maps_and_rollout_match_a_float64_recompute_from_the_trace(pkg, binding,
             err = np.abs(g - refc[l]).max(axis=1)
             assert (err <= tol * refc[l].max(axis=1)).all(), (b, l, err.tolist())
             others = [np.abs(g - refc[m]).max() for m in range(L) if m != l]
-            assert np.abs(g - refc[l]).max() <= 0.1 * min(others), (b, l, float(np.abs(g - refc[l]).max()), min(others))
+            if others:                                                  # a one-layer model has no other layer to be confused with
+                assert np.abs(g - refc[l]).max() <= 0.1 * min(others), (b, l, float(np.abs(g - refc[l]).max()), min(others))
         N = refc[0].shape[1]
         eye = np.eye(N)
         fac = [0.5 * ref[l][b].mean(axis=0) + 0.5 * eye for l in range(L)]
@@ -181,7 +190,8 @@ def test_maps_and_rollout_match_a_float64_recompute_from_the_trace(pkg, binding,
         r = roll[b].astype(np.float64)
         assert (r >= 0).all() and abs(r.sum() - 1.0) <= 1e-4, float(r.sum())
         assert np.abs(r - R[0]).max() <= tol * R[0].max(), (b, float(np.abs(r - R[0]).max()), float(R[0].max()))
-        assert np.abs(r - R[0]).max() <= 0.1 * np.abs(r - Rrev[0]).max()       # the factors are chained in layer order
+        if L > 1:
+            assert np.abs(r - R[0]).max() <= 0.1 * np.abs(r - Rrev[0]).max()   # the factors are chained in layer order
     ctx.close(); model.close()
 
 

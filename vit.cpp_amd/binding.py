@@ -44,6 +44,7 @@ EXPORTS = [
     "vitx_op_dequant", "vitx_op_gemm_q4", "vitx_ctx_weight_bytes", "vitx_ctx_shares_weights", "vitx_probe_mfma", "vitx_op_gemm_ln", "vitx_ctx_ln_fallbacks", "vitx_ctx_stream_retries",
     "vitx_model_in_channels", "vitx_model_seq_len", "vitx_ctx_out_rows", "vitx_ctx_split", "vitx_ctx_ln_fusion_active", "vitx_op_attention_f32", "vitx_op_attention_planes", "vitx_op_attention_cls", "vitx_preprocess_vitstr_u8", "vitx_vitstr_decode",
     "vitx_attn_enable", "vitx_attn_floats", "vitx_attn_images", "vitx_attn_read", "vitx_op_attention_map", "vitx_ctx_graph_launches",
+    "vitx_op_rollout_factor", "vitx_op_rollout_step", "vitx_op_rollout_row",
     "vitx_mxfp8_quantize", "vitx_op_quantize_mxfp8", "vitx_op_layernorm_mxfp8", "vitx_op_gemm_mxfp8",
     "vitx_feat_enable", "vitx_feat_floats", "vitx_feat_images", "vitx_feat_read", "vitx_feat_device", "vitx_op_features",
     "vitx_ctx_img_size", "vitx_ctx_tokens", "vitx_pos_embed_resample", "vitx_op_pos_embed_resample", "vitx_model_resize_file",
@@ -183,6 +184,10 @@ def lib():
             L.vitx_ctx_graph_launches.restype = C.c_longlong; L.vitx_ctx_graph_launches.argtypes = [vp]
             L.vitx_attn_read.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t]
             L.vitx_op_attention_map.argtypes = [ip, vp, C.c_long, vp, vp, ip, ip, ip, ip, vp]
+        if hasattr(L, "vitx_op_rollout_step"):
+            L.vitx_op_rollout_factor.argtypes = [ip, vp, C.c_long, vp, ip, ip, ip, ip, vp]
+            L.vitx_op_rollout_step.argtypes = [vp, vp, ip, ip, vp]
+            L.vitx_op_rollout_row.argtypes = [vp, C.c_long, vp, vp, C.c_long, ip, ip, ip, vp]
         if hasattr(L, "vitx_mxfp8_quantize"):
             L.vitx_mxfp8_quantize.argtypes = [C.POINTER(C.c_float), ip, ip, ip, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]
             L.vitx_op_quantize_mxfp8.argtypes = [vp, ip, ip, ip, vp, vp, vp]
@@ -879,6 +884,21 @@ def probe_mfma(device: int = 0, dtype: int = BF16, fill: int = 2, target_ms: flo
 def op_attention_map(dtype: int, d_qkv: int, d_cls: int, d_mean: int, n_img: int, N: int, D: int, H: int, lo_off: int = 0, stream: int = 0) -> None:
     """vitx_op_attention_map: class-token maps [n_img, H, N] and / or the head mean [n_img, N, N] (f32, device pointers; 0 = not wanted)."""
     check(lib().vitx_op_attention_map(dtype, d_qkv, lo_off, d_cls or None, d_mean or None, n_img, N, D, H, stream or None), "vitx_op_attention_map")
+
+
+def op_rollout_factor(dtype: int, d_qkv: int, d_out: int, n_img: int, N: int, D: int, H: int, lo_off: int = 0, stream: int = 0) -> None:
+    """vitx_op_rollout_factor: the rollout factor 0.5 mean_h A_h + 0.5 I [n_img, N, N] (f32, device pointers)."""
+    check(lib().vitx_op_rollout_factor(dtype, d_qkv, lo_off, d_out, n_img, N, D, H, stream or None), "vitx_op_rollout_factor")
+
+
+def op_rollout_step(d_a: int, d_r: int, n_img: int, N: int, stream: int = 0) -> None:
+    """vitx_op_rollout_step: a[b] <- a[b] . r[b] in place over a ([n_img, N, N] f32 each, device pointers)."""
+    check(lib().vitx_op_rollout_step(d_a, d_r, n_img, N, stream or None), "vitx_op_rollout_step")
+
+
+def op_rollout_row(d_cls: int, cls_stride: int, d_r: int, d_out: int, out_stride: int, n_img: int, N: int, H: int, stream: int = 0) -> None:
+    """vitx_op_rollout_row: row 0 of the last rollout factor (from class-token maps [H, N] per image) times r [n_img, N, N]; d_r 0: that row itself."""
+    check(lib().vitx_op_rollout_row(d_cls, cls_stride, d_r or None, d_out, out_stride, n_img, N, H, stream or None), "vitx_op_rollout_row")
 
 
 def op_features(d_x: int, row_stride: int, img_stride: int, d_w: int, d_b: int, d_cls: int, d_mean: int, d_tokens: int, out_img_stride: int,

@@ -294,6 +294,29 @@ int vitx_op_attention_map(int dtype, const void *d_qkv, long lo_off, void *d_cls
     if (e == hipSuccess && d_mean) e = launch_attention_head_mean(dtype, d_qkv, lo_off, (float *)d_mean, n_img, N, D, H, false, st);
     return op_rc("vitx_op_attention_map", e);
 }
+// The rollout kernels on their own (include/vitx.h).  Every argument check comes before the launch; all three only enqueue.
+// The rollout factor A^ = 0.5 mean_h A_h + 0.5 I: the head-mean kernel in its half_identity form, under vitx_op_attention_map's own checks.
+int vitx_op_rollout_factor(int dtype, const void *d_qkv, long lo_off, void *d_out, int n_img, int N, int D, int H, void *stream) {
+    if (!d_qkv || !d_out || n_img <= 0 || N <= 0 || D <= 0 || H <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_rollout_factor: invalid argument"); return VITX_ERR_ARG; }
+    if (!lo_plane_ok("vitx_op_rollout_factor", dtype, lo_off, (long)n_img * N * 3 * D)) return VITX_ERR_ARG;
+    if (!attention_map_supports(N, D, H)) { set_error("vitx_op_rollout_factor: head_dim must be a multiple of 8 up to 128 (D %d, H %d)", D, H); return VITX_ERR_UNSUPPORTED; }
+    if (!attention_mean_supports(N, D, H)) { set_error("vitx_op_rollout_factor: the head mean takes at most %d tokens (N %d)", kAttnMeanMaxTokens, N); return VITX_ERR_UNSUPPORTED; }
+    return op_rc("vitx_op_rollout_factor", launch_attention_head_mean(dtype, d_qkv, lo_off, (float *)d_out, n_img, N, D, H, true, (hipStream_t)stream));
+}
+// d_a <- d_a . d_r per image.  The kernel reads r while it overwrites a: ranges that overlap are refused.
+int vitx_op_rollout_step(void *d_a, const void *d_r, int n_img, int N, void *stream) {
+    if (!d_a || !d_r || n_img <= 0 || N <= 0) { set_error("vitx_op_rollout_step: invalid argument"); return VITX_ERR_ARG; }
+    if (N > kAttnMeanMaxTokens) { set_error("vitx_op_rollout_step: rollout takes at most %d tokens (N %d)", kAttnMeanMaxTokens, N); return VITX_ERR_UNSUPPORTED; }
+    const uintptr_t a0 = (uintptr_t)d_a, r0 = (uintptr_t)d_r, bytes = (uintptr_t)n_img * N * N * sizeof(float);
+    if (a0 < r0 + bytes && r0 < a0 + bytes) { set_error("vitx_op_rollout_step: d_a and d_r overlap (the step is in place over d_a and reads all of d_r)"); return VITX_ERR_ARG; }
+    return op_rc("vitx_op_rollout_step", launch_rollout_step((float *)d_a, (const float *)d_r, n_img, N, (hipStream_t)stream));
+}
+int vitx_op_rollout_row(const void *d_cls, long cls_stride, const void *d_r, void *d_out, long out_stride, int n_img, int N, int H, void *stream) {
+    if (!d_cls || !d_out || n_img <= 0 || N <= 0 || H <= 0) { set_error("vitx_op_rollout_row: invalid argument"); return VITX_ERR_ARG; }
+    if (cls_stride < (long)H * N || out_stride < N) { set_error("vitx_op_rollout_row: cls_stride %ld must be at least H * N = %ld and out_stride %ld at least N = %d", cls_stride, (long)H * N, out_stride, N); return VITX_ERR_ARG; }
+    if (N > kAttnMeanMaxTokens) { set_error("vitx_op_rollout_row: rollout takes at most %d tokens (N %d)", kAttnMeanMaxTokens, N); return VITX_ERR_UNSUPPORTED; }
+    return op_rc("vitx_op_rollout_row", launch_rollout_row((const float *)d_cls, cls_stride, (const float *)d_r, (float *)d_out, out_stride, n_img, N, H, (hipStream_t)stream));
+}
 
 // Zero-shot classification on the caller's buffers: the three launches the forward of a context with a bank makes (SliceForward::zeroshot), the
 // bank GEMM through the dispatcher.  Every argument check comes before the first device call.  The GEMM's bias is the row of zeros the call
