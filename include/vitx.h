@@ -187,8 +187,8 @@ int vitx_model_has_pre_norm(const vitx_model *m);    /* 1 when the file carries 
  * reference's vit_image_preprocess (vitx_preprocess_u8), which is what a file without a description has always meant.
  *   SHORTEST_EDGE: the short side becomes resize_a, the long side (int)((double)(resize_a * long_src) / (double)short_src) -- truncated, as
  *     transformers and torchvision do (500 x 375 at 224 -> 298 x 224); the width is the short side when nx <= ny.
- *   Output: crop x crop, or resize_a x resize_b when crop == 0.  Outputs are square: STRETCH without a crop needs resize_a == resize_b, and
- *     SHORTEST_EDGE needs a crop.
+ *   Output: crop x crop, or resize_a x resize_b when crop == 0.  The outputs of a description are square: STRETCH without a crop needs resize_a == resize_b, and
+ *     SHORTEST_EDGE needs a crop (vitx_preprocess_rect, "rectangular contexts" below, stretches to any out_w x out_h).
  *   Crop offset per axis, d = resized - crop: d / 2 for even d; odd d: (d - 1) / 2 with crop_round 0 (transformers' floor), d / 2.0 rounded half
  *     to even with crop_round 1 (torchvision CenterCrop).
  *   VITX_ERR_ARG: a crop larger than either resized side of the given source (padding is not offered), non-positive sizes (or any side above
@@ -327,7 +327,7 @@ int vitx_ctx_max_batch(const vitx_ctx *c);
 /* The geometry of THIS context (vitx_ctx_options::img_size): what vitx_forward expects is [n][img_size][img_size][3] (ViTSTR: one plane), and
  * N = (img_size / patch_size)^2 + 1 + R tokens (R = vitx_ctx_registers, the model's register tokens) size the trace and the attention maps;
  * the token features have N - 1 - R rows.  0 for NULL. */
-int vitx_ctx_img_size(const vitx_ctx *c);
+int vitx_ctx_img_size(const vitx_ctx *c);      /* 0 also for a non-square context of vitx_ctx_create_rect (vitx_ctx_img_shape) */
 int vitx_ctx_tokens(const vitx_ctx *c);
 int vitx_ctx_registers(const vitx_ctx *c);
 /* Probability rows per image that vitx_forward / vitx_forward_device write: 1 for a classifier ([n][num_classes]), 25 for a ViTSTR
@@ -359,7 +359,8 @@ int vitx_ctx_synchronize(vitx_ctx *c);
  * fastest).  A context created with vitx_ctx_options::img_size keeps the model's weight matrices (contexts of one loaded model at different
  * sizes share ONE device copy: vitx_ctx_shares_weights, vitx_ctx_weight_bytes unchanged) and owns a table resampled to its own grid, computed
  * by the device kernel at creation from the f32 table already uploaded; the file's table is left as it is.  vitx_group_* has no options argument:
- * a group stays at the file's size.  Contexts are square; a size per call on one context is not offered.
+ * a group stays at the file's size.  Contexts of vitx_ctx_create_ex are square, those of
+ * vitx_ctx_create_rect ("rectangular contexts" below) take any img_h x img_w; a size per call on one context is not offered.
  * Two conventions are in use and differ by 1e-3 .. 5e-2 on a trained table, so both are offered, each equal to CPU torch:
  *   VITX_POS_BICUBIC     torch.nn.functional.interpolate(mode="bicubic", align_corners=False, antialias=False) -- HuggingFace
  *                        interpolate_pos_encoding, DINO: cubic convolution with A = -0.75 on 4 x 4 taps, border indices clamped;
@@ -391,6 +392,43 @@ int vitx_pos_embed_resample(const float *pos, int gy_in, int gx_in, int D, int g
 int vitx_op_pos_embed_resample(const void *d_pos, int gy_in, int gx_in, int D, int gy_out, int gx_out, int interp, void *d_out, void *stream);
 int vitx_model_resize_file(const char *path_in, const char *path_out, int img_size, int interp);
 
+/* ---- rectangular contexts: images of any height and width --------------------------- */
+/* vitx_ctx_create_rect makes a context for [n][img_h][img_w][Cin] f32 HWC images: img_h and img_w positive multiples of patch_size (anything else:
+ * VITX_ERR_ARG, before any device is touched), gh = img_h / patch_size, gw = img_w / patch_size, N = gh * gw + prefix tokens (vitx_ctx_tokens).  Patches
+ * are in raster order, x fastest; the token features have gh * gw rows in that order, attention maps and rollout N columns, the trace N rows.
+ *   Position table: the file's, resampled by the device kernel from (g_in, g_in) to (gh, gw) whenever the grids differ -- vitx_op_pos_embed_resample with
+ *   its rectangular arguments, which is F.interpolate(size=(gh, gw), mode="bicubic", align_corners=False) for VITX_POS_BICUBIC (HuggingFace
+ *   interpolate_pos_encoding); options->pos_interp as in a square context.  A file with `rope` builds vitx_model_rope_table(m, gh, gw, ..).
+ *   `options` may be NULL; options->img_size must be 0 (VITX_ERR_ARG otherwise: the shape is the two arguments).  Every other option, quantised files,
+ *   VITX_MXFP8 where a square context takes it, vitx_attn_enable, vitx_feat_enable, vitx_zeroshot_set, the trace and batches beyond the 32-bit buffer
+ *   window work by the rules of a square context at another img_size.
+ *   img_h == img_w == S is the context vitx_ctx_create_ex makes with img_size = S: the same launches, the same bits; at the file's own size nothing is
+ *   resampled and the weight set is shared (vitx_ctx_shares_weights).
+ *   A ViTSTR file, or a file with the attention-pooling head, at any shape other than the file's own: VITX_ERR_UNSUPPORTED.  vitx_group_* and
+ *   vitx_model_resize_file stay square (the file format has one img_size).
+ *   vitx_ctx_img_shape  img_h, img_w of any context;  vitx_ctx_grid  gh, gw of any context (VITX_ERR_ARG for NULL).
+ *   vitx_ctx_img_size   the side of a square context and 0 for a non-square one: a caller that sizes S * S buffers fails loudly.
+ * Preprocessing to a rectangle (the arithmetic is "each model's own preprocessing" above, per axis with in = nx, out = out_w and in = ny, out = out_h):
+ *   vitx_rect_shape     the aspect-preserving shape, in integers: short_side a positive multiple of patch; with s = min(nx, ny), l = max(nx, ny):
+ *                       long = ((int64)short_side * l / s) / patch * patch, capped at max_long when max_long != 0 (a multiple of patch, at least
+ *                       short_side); the width is the short side when nx <= ny.  500 x 375, patch 16, short 224 -> 288 x 224 (an 18 x 14 grid).
+ *                       Anything else, or a long side above 16384: VITX_ERR_ARG.
+ *   vitx_preprocess_rect   host: the source stretched to out_w x out_h with the description's filter, mean255 and std255; no crop: resize_* and crop are
+ *                       ignored, but the description must be valid.  out f32 [out_h][out_w][3].  out_w == out_h == S equals vitx_preprocess_ex with
+ *                       {STRETCH, S, S, filter, 0, 0} bit for bit.  A REF filter: VITX_ERR_UNSUPPORTED (the reference's resize is defined for squares
+ *                       only); sides outside 1 .. 16384 (source: 1 .. 2^20): VITX_ERR_ARG.
+ *   vitx_preprocess_rect_device   the same for n images of one source size on device pointers, bit for bit: ONE launch of the PIL kernel with a
+ *                       rectangular output window, the LDS bound of vitx_preprocess_ex_device (VITX_ERR_UNSUPPORTED beyond it, before any launch).
+ *   vitx_preprocess_rect_device_supports   1 / 0 for that bound (0 also for an invalid description, a REF filter or bad sizes); no device call. */
+int vitx_ctx_create_rect(const vitx_model *m, int device, int max_batch, int dtype, const vitx_ctx_options *options /* may be NULL; options->img_size must be 0 */,
+                         int img_h, int img_w, vitx_ctx **out);
+int vitx_ctx_img_shape(const vitx_ctx *c, int *img_h, int *img_w);
+int vitx_ctx_grid(const vitx_ctx *c, int *gh, int *gw);
+int vitx_rect_shape(int nx, int ny, int patch, int short_side, int max_long, int *out_w, int *out_h);
+int vitx_preprocess_rect(const vitx_preproc *pp, const uint8_t *hwc, int nx, int ny, int out_w, int out_h, float *out_hwc);
+int vitx_preprocess_rect_device(const vitx_preproc *pp, const void *d_hwc, int n, int nx, int ny, int out_w, int out_h, void *d_out_hwc, void *stream);
+int vitx_preprocess_rect_device_supports(const vitx_preproc *pp, int nx, int ny, int out_w, int out_h);
+
 /* ---- rotary position embeddings (DINOv3-class models) ---------------------------- */
 /* A file may carry `rope`, f32 [4] = {kind, theta, 0, 0}: the position signal is then a rotation of q and k of the patch tokens in every layer, a
  * function of the grid and not a table.  kind 1 (VITX_ROPE_DINOV3_AXIAL, the only one) is DINOv3's: normalised patch-centre coordinates, half-split
@@ -403,7 +441,8 @@ int vitx_model_resize_file(const char *path_in, const char *path_out, int img_si
  *   cy = 2 (y + 0.5) / gh - 1, cx = 2 (x + 0.5) / gw - 1;  inv_j = theta^(-4 j / hd) for j < hd / 4;
  *   angle of column j < hd / 4: 2 pi cy inv_j;  of column hd / 4 + j: 2 pi cx inv_j;  cos / sin rounded once to f32.
  * (HuggingFace tiles these hd / 2 angles twice: columns j and j + hd / 2 of a head share one cos / sin.)  Grids may be rectangular here, as in the two
- * resampler entry points; contexts stay square.  A context of such a file builds the table for ITS grid (vitx_ctx_options::img_size) at creation and
+ * resampler entry points, and a rectangular context (vitx_ctx_create_rect) uses that.  A context of such a file builds the table for ITS grid (vitx_ctx_options::img_size,
+ * or gh x gw of a rectangular context) at creation and
  * keeps it with the context, not in the shared weight set; so a context at another img_size is exact.  pos_interp is validated but has no effect.
  * The rotation (rope.hip), in place on the qkv GEMM's output, after that GEMM and before everything that reads q or k (attention, the class-row tail,
  * attention maps and rollout): for token t >= T (patch p = t - T), s in {q, k}, head h, j < hd / 2, a = element h hd + j, b = element h hd + hd / 2 + j,
@@ -742,6 +781,8 @@ int vitx_op_features(const void *d_x, long row_stride, long img_stride, const vo
 int vitx_op_features_ex(const void *d_x, long row_stride, long img_stride, const void *d_w, const void *d_b,
                         void *d_cls, void *d_mean, void *d_tokens, long out_img_stride,
                         int n_img, int N, int first, int D, float eps, int l2, void *d_z, int dtype, void *stream);
+int vitx_op_patch_embed_rect(int dtype, const void *d_img /* [n][img_h][img_w][Cin] */, const void *d_w, const void *d_bias, const void *d_pos, const void *d_cls,
+                             const void *d_reg, int R, int n_img, int img_h, int img_w, int P, int Cin, int D, void *d_X);   /* the same kernel on rectangular images (null stream) */
 int vitx_op_patch_embed(int dtype, const void *d_img, const void *d_w, const void *d_bias, const void *d_pos, const void *d_cls, const void *d_reg, int R,
                         void *d_X, int n_img, int S, int P, int Cin, int D, void *stream);
 int vitx_op_attention_pool(const void *d_x, long row_stride, long img_stride, const void *d_ln_w, const void *d_ln_b, float eps, const void *d_u, void *d_M,

@@ -58,6 +58,8 @@ EXPORTS = [
     "vitx_op_text_embed", "vitx_op_text_pool", "vitx_op_attention_text", "vitx_op_attention_generic",
     "vitx_model_rope", "vitx_model_rope_table", "vitx_op_rope",
     "vitx_model_glu", "vitx_op_swiglu",
+    "vitx_ctx_create_rect", "vitx_ctx_img_shape", "vitx_ctx_grid", "vitx_op_patch_embed_rect",
+    "vitx_rect_shape", "vitx_preprocess_rect", "vitx_preprocess_rect_device", "vitx_preprocess_rect_device_supports",
 ]
 
 
@@ -255,6 +257,16 @@ def lib():
         if hasattr(L, "vitx_op_swiglu"):
             L.vitx_model_glu.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
             L.vitx_op_swiglu.argtypes = [ip, vp, C.c_long, vp, C.c_long, C.c_long, ip, vp]
+        if hasattr(L, "vitx_ctx_create_rect"):
+            pp = C.POINTER(Preproc)
+            L.vitx_ctx_create_rect.argtypes = [vp, ip, ip, ip, C.POINTER(CtxOptions), ip, ip, C.POINTER(vp)]
+            L.vitx_ctx_img_shape.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
+            L.vitx_ctx_grid.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
+            L.vitx_op_patch_embed_rect.argtypes = [ip, vp, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, ip, vp]
+            L.vitx_rect_shape.argtypes = [ip, ip, ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
+            L.vitx_preprocess_rect.argtypes = [pp, C.POINTER(C.c_uint8), ip, ip, ip, ip, C.POINTER(C.c_float)]
+            L.vitx_preprocess_rect_device.argtypes = [pp, vp, ip, ip, ip, ip, ip, vp, vp]
+            L.vitx_preprocess_rect_device_supports.argtypes = [pp, ip, ip, ip, ip]
         _lib = L
     return _lib
 
@@ -476,6 +488,32 @@ def preprocess_ex_device_supports(pp: Preproc, nx: int, ny: int) -> bool:
     return bool(lib().vitx_preprocess_ex_device_supports(C.byref(pp), nx, ny))
 
 
+def rect_shape(nx: int, ny: int, patch: int, short_side: int, max_long: int = 0) -> Tuple[int, int]:
+    """vitx_rect_shape: the aspect-preserving (out_w, out_h) for an nx x ny source: the short side becomes short_side, the long side the largest
+    multiple of patch that keeps the aspect (capped at max_long when that is not 0).  500 x 375, patch 16, short 224 -> (288, 224)."""
+    w, h = C.c_int(), C.c_int()
+    check(lib().vitx_rect_shape(nx, ny, patch, short_side, max_long, C.byref(w), C.byref(h)), "vitx_rect_shape")
+    return w.value, h.value
+
+
+def preprocess_rect(img_u8: np.ndarray, pp: Preproc, out_w: int, out_h: int) -> np.ndarray:
+    """vitx_preprocess_rect: HWC u8 any size -> HWC f32 [out_h, out_w, 3], stretched with the description's PIL filter, mean / std; no crop."""
+    img = np.ascontiguousarray(img_u8, np.uint8); ny, nx = img.shape[:2]
+    out = np.empty((max(int(out_h), 1), max(int(out_w), 1), 3), np.float32)
+    check(lib().vitx_preprocess_rect(C.byref(pp), img.ctypes.data_as(C.POINTER(C.c_uint8)), nx, ny, out_w, out_h, out.ctypes.data_as(C.POINTER(C.c_float))), "vitx_preprocess_rect")
+    return out
+
+
+def preprocess_rect_device(pp: Preproc, d_u8: int, n: int, nx: int, ny: int, out_w: int, out_h: int, d_out: int, stream: int = 0) -> None:
+    """vitx_preprocess_rect_device: the same on the GPU for n images of one source size (device pointers; one launch, enqueue only)."""
+    check(lib().vitx_preprocess_rect_device(C.byref(pp), d_u8, n, nx, ny, out_w, out_h, d_out, stream or None), "vitx_preprocess_rect_device")
+
+
+def preprocess_rect_device_supports(pp: Preproc, nx: int, ny: int, out_w: int, out_h: int) -> bool:
+    """vitx_preprocess_rect_device_supports: whether the device kernel's LDS tile covers this down-scale (no device call)."""
+    return bool(lib().vitx_preprocess_rect_device_supports(C.byref(pp), nx, ny, out_w, out_h))
+
+
 def preprocess_vitstr(img_u8: np.ndarray, img_size: int) -> np.ndarray:
     """vit_image_preprocess of extensions/vitstr.cpp (vitstr.cpp:135-201): HWC u8 RGB -> [S,S] f32 grey in [-1, 1]."""
     img = np.ascontiguousarray(img_u8, np.uint8); ny, nx = img.shape[:2]
@@ -497,11 +535,11 @@ def preprocess_device(d_u8: int, n: int, nx: int, ny: int, img_size: int, d_out:
     check(lib().vitx_preprocess_u8_device(d_u8, n, nx, ny, img_size, interp, d_out, stream or None), "vitx_preprocess_u8_device")
 
 
-def _check_image_shape(model: "Model", x: np.ndarray, img_size: Optional[int] = None) -> None:
-    """[n, S, S, 3] for a classifier, [n, S, S] (one grey plane) for a ViTSTR file: the C ABI reads n * S * S * in_channels floats.
-    S is the context's img_size (a Group runs at the file's)."""
-    S = model.img_size if img_size is None else img_size
-    want = (S, S, 3) if model.in_channels == 3 else (S, S)
+def _check_image_shape(model: "Model", x: np.ndarray, img_size=None) -> None:
+    """[n, h, w, 3] for a classifier, [n, S, S] (one grey plane) for a ViTSTR file: the C ABI reads n * h * w * in_channels floats.
+    img_size is the context's side S (h = w = S) or its (h, w) shape (a Group runs at the file's)."""
+    h, w = _grid(model.img_size if img_size is None else img_size)
+    want = (h, w, 3) if model.in_channels == 3 else (h, w)
     if x.ndim != 1 + len(want) or tuple(x.shape[1:]) != want:
         raise ValueError(f"images must be [n, {', '.join(map(str, want))}] for this model, got {tuple(x.shape)}")
 
@@ -509,9 +547,12 @@ def _check_image_shape(model: "Model", x: np.ndarray, img_size: Optional[int] = 
 class Context:
     """Per-(thread, GPU) execution context (vit_state): weights in HBM + activation scratch."""
 
-    def __init__(self, model: Model, device: int = 0, max_batch: int = 1, dtype: int = F16, **options):
+    def __init__(self, model: Model, device: int = 0, max_batch: int = 1, dtype: int = F16, img_shape=None, **options):
         """options: the fields of vitx_ctx_options (streams, graph, quant_on_host, q4_fused_rows, split_first, no_ln_fusion, ...,
-        img_size, pos_interp: a context at another input size than the file's, on the position table resampled to its grid)."""
+        img_size, pos_interp: a context at another input size than the file's, on the position table resampled to its grid).
+        img_shape = (h, w): a rectangular context (vitx_ctx_create_rect) for [n, h, w, 3] images; not together with img_size."""
+        if img_shape is not None and options.get("img_size"):
+            raise ValueError("img_shape and img_size cannot both be given")
         self.model = model; self.device = device; self.max_batch = max_batch; self.dtype = dtype
         self._h = C.c_void_p()
         opt = CtxOptions(struct_size=C.sizeof(CtxOptions))
@@ -524,12 +565,22 @@ class Context:
         names = [f for f, _ in CtxOptions._fields_]
         last = max([i for i, f in enumerate(names) if f != "struct_size" and getattr(opt, f) != 0] + [names.index("f16_fast_attention")])
         opt.struct_size = 4 * (last + 1)
-        check(lib().vitx_ctx_create_ex(model._h, device, max_batch, dtype, C.byref(opt), C.byref(self._h)), "vitx_ctx_create_ex")
+        if img_shape is not None:
+            ih, iw = (int(v) for v in img_shape)
+            check(lib().vitx_ctx_create_rect(model._h, device, max_batch, dtype, C.byref(opt), ih, iw, C.byref(self._h)), "vitx_ctx_create_rect")
+        else:
+            check(lib().vitx_ctx_create_ex(model._h, device, max_batch, dtype, C.byref(opt), C.byref(self._h)), "vitx_ctx_create_ex")
         # the geometry of THIS context (vitx_ctx_options::img_size); a build that predates the option runs at the file's
         L = lib()
         self.img_size = int(L.vitx_ctx_img_size(self._h)) if hasattr(L, "vitx_ctx_img_size") else model.img_size
         self.tokens = int(L.vitx_ctx_tokens(self._h)) if hasattr(L, "vitx_ctx_tokens") else (model.img_size // model.hparams.patch_size) ** 2 + 1
-        self.grid = self.img_size // model.hparams.patch_size
+        self.grid = self.img_size // model.hparams.patch_size      # the side of a square context's grid; 0 for a non-square context (grid_hw)
+        # img_shape = (h, w) and grid_hw = (gh, gw) of any context; img_size is 0 for a non-square one
+        self.img_shape = (self.img_size, self.img_size); self.grid_hw = (self.grid, self.grid)
+        if hasattr(L, "vitx_ctx_img_shape"):
+            a, b = C.c_int(), C.c_int()
+            check(L.vitx_ctx_img_shape(self._h, C.byref(a), C.byref(b)), "vitx_ctx_img_shape"); self.img_shape = (a.value, b.value)
+            check(L.vitx_ctx_grid(self._h, C.byref(a), C.byref(b)), "vitx_ctx_grid"); self.grid_hw = (a.value, b.value)
         self.registers = int(L.vitx_ctx_registers(self._h)) if hasattr(L, "vitx_ctx_registers") else 0
         self.prefix = model.num_prefix                # tokens in front of the patches: the class token and the registers (0 for a POOL_MAP model)
 
@@ -544,9 +595,9 @@ class Context:
             pass
 
     def forward(self, imgs_hwc: np.ndarray, want_logits: bool = False):
-        """Host arrays in/out (copies + sync): [n,S,S,3] f32 -> probs [n,C] (and logits)."""
+        """Host arrays in/out (copies + sync): [n,h,w,3] f32 (the context's img_shape) -> probs [n,C] (and logits)."""
         x = np.ascontiguousarray(imgs_hwc, np.float32); n = x.shape[0]
-        _check_image_shape(self.model, x, self.img_size)
+        _check_image_shape(self.model, x, self.img_shape)
         R = self.model.seq_len                      # ViTSTR: [n, S, S] grey in, [n, 25, C] out
         probs = np.empty((n, self.model.num_classes) if R == 0 else (n, R, self.model.num_classes), np.float32)
         logits = np.empty_like(probs) if want_logits else None
@@ -609,9 +660,9 @@ class Context:
         return cls, (out[:, len(sel) * H * N:].copy() if roll else None)
 
     def attn_grid(self, m: np.ndarray) -> np.ndarray:
-        """[..., N] map -> [..., g, g] patch grid (g = the context's img_size / patch_size): drops the class token and the register tokens."""
-        g = self.grid
-        return np.asarray(m)[..., self.prefix:].reshape(*np.shape(m)[:-1], g, g)
+        """[..., N] map -> [..., gh, gw] patch grid (the context's grid_hw; g x g for a square context): drops the class token and the register tokens."""
+        gh, gw = self.grid_hw
+        return np.asarray(m)[..., self.prefix:].reshape(*np.shape(m)[:-1], gh, gw)
 
     def feat_enable(self, cls: bool = True, mean: bool = False, tokens: bool = False, l2: bool = False, layers=None) -> None:
         """Embeddings and token features of every later forward (vitx_feat_enable): the final-norm class embedding, the mean of the patch
@@ -922,6 +973,12 @@ def op_patch_embed(dtype: int, d_img: int, d_w: int, d_bias: int, d_pos: int, d_
     kernel [D, Cin * P * P] in the file's order; every pointer is a device pointer to f32.  d_cls = 0 (R = 0): a model without a class token --
     no prefix row, d_pos [(S/P)^2, D]."""
     check(lib().vitx_op_patch_embed(dtype, d_img, d_w, d_bias, d_pos, d_cls or None, d_reg or None, R, d_X, n_img, S, P, Cin, D, stream or None), "vitx_op_patch_embed")
+
+
+def op_patch_embed_rect(dtype: int, d_img: int, d_w: int, d_bias: int, d_pos: int, d_cls: int, d_reg: int, R: int, d_X: int, n_img: int, img_h: int, img_w: int,
+                        P: int, Cin: int, D: int) -> None:
+    """vitx_op_patch_embed_rect (test only; synchronous): vitx_op_patch_embed on [n, img_h, img_w, Cin] images; d_pos [prefix rows + (img_h/P)(img_w/P), D]."""
+    check(lib().vitx_op_patch_embed_rect(dtype, d_img, d_w, d_bias, d_pos, d_cls or None, d_reg or None, R, n_img, img_h, img_w, P, Cin, D, d_X), "vitx_op_patch_embed_rect")
 
 
 def op_attention_pool(d_x: int, row_stride: int, img_stride: int, d_ln_w: int, d_ln_b: int, eps: float, d_u: int, d_M: int, d_p: int,

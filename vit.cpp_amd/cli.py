@@ -6,6 +6,7 @@ directory-walk accuracy harness:
     python vit_cli.py -m model.gguf -i image.jpg --attn-map map.pgm [--attn-kind rollout|last]   # + where the model looked (P5 picture)
     python vit_cli.py -m model.gguf (-i image.jpg | --dir DIR) --embed out.npy [--embed-kind cls|mean|tokens] [--embed-l2]   # + the embeddings
     python vit_cli.py -m model.gguf ... --img-size 384 [--pos-interp bicubic|bicubic-aa]   # run at another input size than the file's
+    python vit_cli.py -m model.gguf ... --img-shape 224x448 | --img-fit 224   # a rectangular context: HxW, or the aspect-preserving shape of the input image
     python vit_cli.py -m model.gguf ... [--preprocess model|reference]   # the file's own preprocessing (default) or the reference's for any file
     python vit_cli.py -m clip.gguf -i image.jpg -k 5 --zero-shot bank.npz   # zero-shot classes of a CLIP / SigLIP file (bank: convert.py --zero-shot-out)
     python vit_cli.py -m clip.gguf -i image.jpg --text-model text.gguf --zero-shot-ids ids.npy [--zero-shot-labels labels.txt]   # the bank made by the engine, same run
@@ -37,14 +38,16 @@ def _decode(path: str) -> np.ndarray:
     return np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8)
 
 
-def attn_pgm(grid: np.ndarray, img_size: int) -> bytes:
-    """[g, g] patch map -> binary PGM (P5) of img_size^2 bytes: nearest-neighbour upsampling, scaled to 0..255 (the maximum is 255)."""
-    g = grid.shape[0]
+def attn_pgm(grid: np.ndarray, img_size) -> bytes:
+    """[gh, gw] patch map -> binary PGM (P5) of img_w x img_h bytes (img_size: a side, or (img_h, img_w)): nearest-neighbour upsampling, scaled to
+    0..255 (the maximum is 255)."""
+    gh, gw = grid.shape
+    ih, iw = (int(img_size), int(img_size)) if np.isscalar(img_size) else (int(img_size[0]), int(img_size[1]))
     m = np.asarray(grid, np.float64)
     lo, hi = float(m.min()), float(m.max())
     u8 = np.zeros_like(m, np.uint8) if hi <= lo else np.rint((m - lo) / (hi - lo) * 255.0).astype(np.uint8)
-    idx = np.arange(img_size) * g // img_size                  # source patch of every output pixel
-    return f"P5\n{img_size} {img_size}\n255\n".encode() + u8[idx][:, idx].tobytes()
+    iy, ix = np.arange(ih) * gh // ih, np.arange(iw) * gw // iw      # source patch of every output pixel
+    return f"P5\n{iw} {ih}\n255\n".encode() + u8[iy][:, ix].tobytes()
 
 
 def make_parser() -> argparse.ArgumentParser:
@@ -77,8 +80,15 @@ def make_parser() -> argparse.ArgumentParser:
     ap.add_argument("--img-size", type=int, default=0, metavar="N",
                     help="run at N x N instead of the file's img_size (a multiple of the patch size): the position table is resampled to the new grid; "
                          "the preprocess, the --attn-map picture and the --embed shapes follow")
+    ap.add_argument("--img-shape", default=None, metavar="HxW",
+                    help="run on H x W images (both multiples of the patch size) in a rectangular context: the image is STRETCHED to that shape by the "
+                         "file's own filter, mean and std, without a crop (a file without a `preproc` tensor, or one with the reference's filter: Pillow "
+                         "bicubic with the file's default mean / std); --attn-map then writes a W x H picture, --embed-kind tokens (H/P)(W/P) rows")
+    ap.add_argument("--img-fit", type=int, default=0, metavar="SHORT",
+                    help="with -i: like --img-shape, with the shape taken from the input image: its short side becomes SHORT (a multiple of the patch size), "
+                         "the long side the largest multiple of the patch size that keeps the aspect (vitx_rect_shape; 500 x 375 at 224, patch 16: 288 x 224)")
     ap.add_argument("--pos-interp", default="bicubic", choices=["bicubic", "bicubic-aa"],
-                    help="with --img-size: bicubic = F.interpolate(mode='bicubic') (HuggingFace interpolate_pos_encoding, DINO); "
+                    help="with --img-size, --img-shape or --img-fit: bicubic = F.interpolate(mode='bicubic') (HuggingFace interpolate_pos_encoding, DINO); "
                          "bicubic-aa = the same with antialias=True (timm resample_abs_pos_embed)")
     ap.add_argument("--zero-shot", default=None, metavar="BANK.npz",
                     help="with -i, a CLIP or SigLIP file: classify against the bank of text embeddings in BANK.npz (convert.py --zero-shot-out) instead of the "
@@ -138,6 +148,19 @@ def main(argv: List[str] | None = None) -> int:
         ap.error("--embed-kind and --embed-l2 need --embed OUT.npy")
     if a.embed_l2 and a.embed_kind == "tokens":
         ap.error("--embed-l2 normalises the cls / mean embedding; token features are never normalised")
+    if sum(bool(v) for v in (a.img_size, a.img_shape, a.img_fit)) > 1:
+        ap.error("--img-size, --img-shape and --img-fit are three ways to say one thing: give one")
+    if a.img_fit and a.dir is not None:
+        ap.error("--img-fit takes its shape from the single image of -i, not --dir (use --img-shape HxW)")
+    if (a.img_shape or a.img_fit) and a.preprocess == "reference":
+        ap.error("--preprocess reference resizes to squares only: not with --img-shape / --img-fit")
+    rect = None                                          # (img_h, img_w) of a rectangular context
+    if a.img_shape:
+        try:
+            rect = tuple(int(v) for v in a.img_shape.lower().split("x"))
+            assert len(rect) == 2
+        except (ValueError, AssertionError):
+            ap.error(f"--img-shape takes HxW, e.g. 224x448 (got '{a.img_shape}')")
     feat = dict(cls=a.embed_kind == "cls", mean=a.embed_kind == "mean", tokens=a.embed_kind == "tokens", l2=a.embed_l2)
     last = lambda ctx: ctx.feat_read()[model.hparams.num_hidden_layers - 1][a.embed_kind]
 
@@ -176,6 +199,14 @@ def main(argv: List[str] | None = None) -> int:
     else:
         preprocess = lambda img: binding.preprocess(img, S, interp)
     geometry = dict(img_size=a.img_size, pos_interp=binding.POS_BICUBIC_AA if a.pos_interp == "bicubic-aa" else binding.POS_BICUBIC) if a.img_size else {}
+    if rect or a.img_fit:
+        # a rectangular context: the whole image stretched to img_w x img_h by the file's PIL filter, mean and std (vitx_preprocess_rect); a file
+        # without a description, or with the reference's filter, takes Pillow bicubic with its default mean / std
+        pp_rect = model.preproc()
+        if pp_rect.filter not in (binding.PP_PIL_BILINEAR, binding.PP_PIL_BICUBIC):
+            pp_rect.filter = binding.PP_PIL_BICUBIC
+        preprocess = lambda img: binding.preprocess_rect(img, pp_rect, rect[1], rect[0])
+        geometry = dict(pos_interp=binding.POS_BICUBIC_AA if a.pos_interp == "bicubic-aa" else binding.POS_BICUBIC)
 
     bank = text_bank
     if a.zero_shot:
@@ -194,13 +225,16 @@ def main(argv: List[str] | None = None) -> int:
             return 1
         print(f"main: loaded image '{a.inp}' ({img0.shape[1]} x {img0.shape[0]})", file=sys.stderr)
         try:
+            if a.img_fit:
+                w_fit, h_fit = binding.rect_shape(img0.shape[1], img0.shape[0], model.hparams.patch_size, a.img_fit)
+                rect = (h_fit, w_fit)
             img1 = preprocess(img0)
         except binding.VitxError as e:
             print(f"main: failed to preprocess '{a.inp}': {e}", file=sys.stderr)
             return 1
-        print(f"processed, out dims : ({S} x {S})", file=sys.stderr)
+        print(f"processed, out dims : ({rect[1]} x {rect[0]})" if rect else f"processed, out dims : ({S} x {S})", file=sys.stderr)
         try:
-            ctx = binding.Context(model, device=a.device, max_batch=1, dtype=dt, **geometry)
+            ctx = binding.Context(model, device=a.device, max_batch=1, dtype=dt, img_shape=rect, **geometry)
         except binding.VitxError as e:
             print(f"main: failed to create the context: {e}", file=sys.stderr)
             return 1
@@ -223,7 +257,7 @@ def main(argv: List[str] | None = None) -> int:
             cls, roll = ctx.attn_read()
             m = roll[0] if a.attn_kind == "rollout" else cls[0, 0].mean(axis=0)
             with open(a.attn_map, "wb") as f:
-                f.write(attn_pgm(ctx.attn_grid(m), S))
+                f.write(attn_pgm(ctx.attn_grid(m), rect or S))
             print(f"main: wrote the {a.attn_kind} attention map to '{a.attn_map}'", file=sys.stderr)
         label = model.label
         if bank:                                                            # the bank's classes in place of the file's own head
@@ -252,7 +286,7 @@ def main(argv: List[str] | None = None) -> int:
         print(f"main: no <label>/<image> files under '{a.dir}' match the model's labels", file=sys.stderr)
         return 1
     try:
-        ctx = binding.Context(model, device=a.device, max_batch=min(a.batch, len(files)), dtype=dt, **geometry)
+        ctx = binding.Context(model, device=a.device, max_batch=min(a.batch, len(files)), dtype=dt, img_shape=rect, **geometry)
     except binding.VitxError as e:
         print(f"main: failed to create the context: {e}", file=sys.stderr)
         return 1

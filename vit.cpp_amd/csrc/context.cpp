@@ -139,9 +139,10 @@ int upload_map_head(vitx_ctx *c) {
     return VITX_OK;
 }
 
-// vitx_ctx_create_ex, step 1: the options (all zero = every default) and the geometry they ask for are validated, then the context is made and
-// its fields are derived from them.  Every check keeps its place: the first one that fails is the one reported.
-int configure(const vitx_model *m, int device, int max_batch, int dtype, const vitx_ctx_options *opt_in, vitx_ctx_options &opt, std::unique_ptr<vitx_ctx> &c) {
+// vitx_ctx_create_ex / vitx_ctx_create_rect, step 1: the options (all zero = every default) and the geometry they ask for are validated, then the
+// context is made and its fields are derived from them.  Every check keeps its place: the first one that fails is the one reported.
+// rect: the caller is vitx_ctx_create_rect and the geometry is rect_h x rect_w; otherwise it is the square of options.img_size (0: the file's).
+int configure(const vitx_model *m, int device, int max_batch, int dtype, const vitx_ctx_options *opt_in, bool rect, int rect_h, int rect_w, vitx_ctx_options &opt, std::unique_ptr<vitx_ctx> &c) {
     if (opt_in) {
         if (opt_in->struct_size < 8 || opt_in->struct_size > (int)sizeof(vitx_ctx_options)) { set_error("vitx_ctx_create_ex: options.struct_size %d is not a size this library knows", opt_in->struct_size); return VITX_ERR_ARG; }
         memcpy(&opt, opt_in, (size_t)opt_in->struct_size);
@@ -152,10 +153,18 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
     if (opt.img_size < 0 || (opt.img_size > 0 && (m->hp.patch_size <= 0 || opt.img_size % m->hp.patch_size))) {
         set_error("vitx_ctx_create_ex: img_size %d is not a positive multiple of the patch size %d", opt.img_size, m->hp.patch_size); return VITX_ERR_ARG;
     }
+    if (rect) {
+        if (opt.img_size != 0) { set_error("vitx_ctx_create_rect: options.img_size must be 0 (the shape is img_h x img_w; it is %d)", opt.img_size); return VITX_ERR_ARG; }
+        if (m->hp.patch_size <= 0 || rect_h <= 0 || rect_w <= 0 || rect_h % m->hp.patch_size || rect_w % m->hp.patch_size) {
+            set_error("vitx_ctx_create_rect: img_h %d and img_w %d must be positive multiples of the patch size %d", rect_h, rect_w, m->hp.patch_size); return VITX_ERR_ARG;
+        }
+    }
     const int img_size = opt.img_size > 0 ? opt.img_size : m->hp.img_size;
+    const int img_h = rect ? rect_h : img_size, img_w = rect ? rect_w : img_size;
+    const bool own_shape = img_h == m->hp.img_size && img_w == m->hp.img_size;      // the file's own geometry
     if (m->in_chans == 1 && (m->num_registers || m->head_pool != VITX_POOL_CLS)) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes neither register tokens nor a pooled or attention-pooling head"); return VITX_ERR_UNSUPPORTED; }
     if (dtype == VITX_MXFP8 && (m->num_registers || m->head_pool != VITX_POOL_CLS)) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts do not take models with register tokens, the pooled head or the attention-pooling head"); return VITX_ERR_UNSUPPORTED; }
-    if (m->head_pool == VITX_POOL_MAP && img_size != m->hp.img_size) {
+    if (m->head_pool == VITX_POOL_MAP && !own_shape) {
         set_error("vitx_ctx_create_ex: a model with the attention-pooling head stays at the file's img_size (%d): its position table has no class row and no resampling path yet", m->hp.img_size);
         return VITX_ERR_UNSUPPORTED;
     }
@@ -165,7 +174,7 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
     if (m->glu_kind && m->in_chans == 1) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes no gated MLP"); return VITX_ERR_UNSUPPORTED; }
     if (m->in_chans == 1 && (m->has_pre_norm || m->activation != VITX_ACT_GELU_TANH)) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes neither a pre-norm nor an activation other than tanh-GELU"); return VITX_ERR_UNSUPPORTED; }
     if (dtype == VITX_MXFP8 && m->activation != VITX_ACT_GELU_TANH) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts evaluate tanh-GELU only (this model's activation: %d)", m->activation); return VITX_ERR_UNSUPPORTED; }
-    if (m->in_chans == 1 && img_size != m->hp.img_size) { set_error("vitx_ctx_create_ex: a ViTSTR context stays at the file's img_size (%d)", m->hp.img_size); return VITX_ERR_UNSUPPORTED; }
+    if (m->in_chans == 1 && !own_shape) { set_error("vitx_ctx_create_ex: a ViTSTR context stays at the file's img_size (%d)", m->hp.img_size); return VITX_ERR_UNSUPPORTED; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("vitx_ctx_create: no HIP device available (this engine has no CPU fallback)"); return VITX_ERR_HIP; }
     if (device < 0 || device >= ndev) { set_error("vitx_ctx_create: device %d out of range (%d devices)", device, ndev); return VITX_ERR_ARG; }
@@ -179,20 +188,23 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
     if (!c) return VITX_ERR_NOMEM;
     c->model = m; c->hp = hp; c->device = device; c->max_batch = max_batch;
     c->mx = dtype == VITX_MXFP8; c->dtype = c->mx ? VITX_BF16 : dtype;      // everything but the MX GEMMs runs as in a VITX_BF16 context
-    c->D = hp.hidden_size; c->L = hp.num_hidden_layers; c->H = hp.num_attention_heads; c->C = hp.num_classes; c->P = hp.patch_size; c->S = img_size;
+    c->D = hp.hidden_size; c->L = hp.num_hidden_layers; c->H = hp.num_attention_heads; c->C = hp.num_classes; c->P = hp.patch_size;
+    c->Sh = img_h; c->Sw = img_w; c->S = img_h == img_w ? img_h : 0;
     c->Cin = m->in_chans; c->R = m->in_chans == 1 ? VITX_VITSTR_SEQ_LEN : 1;
     c->glu = m->glu_kind != VITX_GLU_NONE; c->F = m->mlp_hidden(); c->F1 = m->mlp_fc1_rows();
     c->fc1_epi = c->glu ? EPI_BIAS : act_epi(m->activation);       // a gated MLP: the plain bias epilogue, the gate is a launch of its own
     c->nreg = m->num_registers; c->pool = m->head_pool == VITX_POOL_CLS_MEAN; c->map = m->head_pool == VITX_POOL_MAP;
     c->Tp = c->map ? 0 : 1 + c->nreg;
     if (c->map && c->H > kPoolMaxHeads) { set_error("vitx_ctx_create: the attention-pooling kernel takes at most %d heads (this model: %d)", kPoolMaxHeads, c->H); return VITX_ERR_UNSUPPORTED; }
-    c->g = c->S / c->P; c->N = c->g * c->g + c->Tp; c->Kpe = c->Cin * c->P * c->P; c->Kpe_pad = round_up(c->Kpe, 64);
-    if (c->N < c->R) { set_error("vitx_ctx_create: a ViTSTR head reads %d tokens, this model has %d (img_size %d, patch_size %d)", c->R, c->N, c->S, c->P); return VITX_ERR_UNSUPPORTED; }
+    c->gh = c->Sh / c->P; c->gw = c->Sw / c->P;
+    if ((long)c->gh * c->gw + c->Tp > 0x7fffffffl / 4) { set_error("vitx_ctx_create: %d x %d patches are more tokens than a context takes", c->gh, c->gw); return VITX_ERR_UNSUPPORTED; }
+    c->N = c->gh * c->gw + c->Tp; c->Kpe = c->Cin * c->P * c->P; c->Kpe_pad = round_up(c->Kpe, 64);
+    if (c->N < c->R) { set_error("vitx_ctx_create: a ViTSTR head reads %d tokens, this model has %d (image %d x %d, patch_size %d)", c->R, c->N, c->Sh, c->Sw, c->P); return VITX_ERR_UNSUPPORTED; }
     c->tm = gemm_tile_m(); c->tn = gemm_tile_n();
     c->C_pad = round_up(c->C, c->tn);
     // validate against what the kernels are actually instantiated for (a context that would fail on its first forward is refused here)
     if (!attention_supports(c->N, c->D, c->H)) {
-        set_error("vitx_ctx_create: attention needs a head_dim that is a multiple of 8 up to 128 (this model: %d) and at least one token (%d tokens, img_size %d, patch_size %d)", c->D / c->H, c->N, c->S, c->P);
+        set_error("vitx_ctx_create: attention needs a head_dim that is a multiple of 8 up to 128 (this model: %d) and at least one token (%d tokens, image %d x %d, patch_size %d)", c->D / c->H, c->N, c->Sh, c->Sw, c->P);
         return VITX_ERR_UNSUPPORTED;
     }
     if (!layernorm_supports(c->D)) { set_error("vitx_ctx_create: hidden_size %d has no LayerNorm instantiation (64, 128, 192, 256, 320, 384, 448, 512, 576, 640, 768, 896, 1024, 1152, 1280, 1408, 1536, 1664, 2048)", c->D); return VITX_ERR_UNSUPPORTED; }
@@ -371,30 +383,32 @@ extern "C" {
 
 int vitx_ctx_create(const vitx_model *m, int device, int max_batch, int dtype, vitx_ctx **out) { return vitx_ctx_create_ex(m, device, max_batch, dtype, nullptr, out); }
 
-int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype, const vitx_ctx_options *opt_in, vitx_ctx **out) {
+// One creation path for both entry points (rect: vitx_ctx_create_rect with img_h x img_w).  A rect call with img_h == img_w == S does what
+// vitx_ctx_create_ex does with img_size = S: the same fields, the same launches.
+static int ctx_create(const vitx_model *m, int device, int max_batch, int dtype, const vitx_ctx_options *opt_in, bool rect, int img_h, int img_w, vitx_ctx **out) {
     if (!m || !out || max_batch <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16 && dtype != VITX_MXFP8)) { set_error("vitx_ctx_create: invalid argument"); return VITX_ERR_ARG; }
     *out = nullptr;
     if (m->kind != VITX_KIND_IMAGE) { set_error("vitx_ctx_create: a text-tower model takes a text context (vitx_text_create), not an image context"); return VITX_ERR_ARG; }
     vitx_ctx_options opt{};                   // all zero = every default
     std::unique_ptr<vitx_ctx> c;
     int rc;
-    if ((rc = configure(m, device, max_batch, dtype, opt_in, opt, c))) return rc;
+    if ((rc = configure(m, device, max_batch, dtype, opt_in, rect, img_h, img_w, opt, c))) return rc;
     if ((rc = obtain_weights(c.get(), dtype))) return rc;
     const vitx_hparams &hp = m->hp;
     const int D = c->D;
     // the position table of THIS context: the set's (the file's) at the file's size, else resampled on the device into scratch the context owns
     c->pos = c->wset->pos;
-    if (c->S != hp.img_size) {
-        const int g_in = hp.img_size / hp.patch_size;
-        if ((rc = c->dmalloc((void **)&c->pos_own, (size_t)(c->g * c->g + 1) * D * 4, false))) return rc;      // (never a VITX_POOL_MAP model: configure refuses it)
-        HIP_TRY(launch_pos_resample(c->wset->pos, g_in, g_in, D, c->g, c->g, opt.pos_interp, c->pos_own, c->stream));
+    const int g_in = hp.img_size / hp.patch_size;
+    if (c->gh != g_in || c->gw != g_in) {
+        if ((rc = c->dmalloc((void **)&c->pos_own, ((size_t)c->gh * c->gw + 1) * D * 4, false))) return rc;      // (never a VITX_POOL_MAP model: configure refuses it)
+        HIP_TRY(launch_pos_resample(c->wset->pos, g_in, g_in, D, c->gh, c->gw, opt.pos_interp, c->pos_own, c->stream));
         c->pos = c->pos_own;                 // (the hipDeviceSynchronize at the end of the creation covers the launch)
     }
     // rotary position embeddings: the table of THIS context's grid, built on the host in double and uploaded once (cos, then sin)
     if (m->rope_kind) {
-        const size_t tab = (size_t)c->g * c->g * (D / c->H / 2);
+        const size_t tab = (size_t)c->gh * c->gw * (D / c->H / 2);
         std::vector<float> h(2 * tab);
-        if ((rc = vitx_model_rope_table(m, c->g, c->g, h.data(), h.data() + tab))) return rc;
+        if ((rc = vitx_model_rope_table(m, c->gh, c->gw, h.data(), h.data() + tab))) return rc;
         if ((rc = c->dmalloc((void **)&c->rope_cos, 2 * tab * 4, false))) return rc;
         c->rope_sin = c->rope_cos + tab;
         HIP_TRY(hipMemcpy(c->rope_cos, h.data(), 2 * tab * 4, hipMemcpyHostToDevice));
@@ -423,7 +437,7 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
     if (ns > 1) HIP_TRY(hipEventCreateWithFlags(&c->fork, hipEventDisableTiming));
     HIP_TRY(hipHostMalloc((void **)&c->ln_fb_host, sizeof(unsigned) * 4, hipHostMallocDefault));
     for (int i = 0; i < 4; ++i) c->ln_fb_host[i] = 0;
-    if ((rc = c->dmalloc((void **)&c->img, (size_t)max_batch * c->S * c->S * c->Cin * 4, false))) return rc;
+    if ((rc = c->dmalloc((void **)&c->img, (size_t)max_batch * c->img_floats() * 4, false))) return rc;
     if ((rc = c->dmalloc((void **)&c->probs, (size_t)max_batch * c->R * c->C * 4, true))) return rc;
     if ((rc = c->dmalloc((void **)&c->logits_all, (size_t)max_batch * c->R * c->C * 4, true))) return rc;
     HIP_TRY(hipDeviceSynchronize());
@@ -431,9 +445,26 @@ int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype
     return VITX_OK;
 }
 
+int vitx_ctx_create_ex(const vitx_model *m, int device, int max_batch, int dtype, const vitx_ctx_options *opt_in, vitx_ctx **out) {
+    return ctx_create(m, device, max_batch, dtype, opt_in, false, 0, 0, out);
+}
+int vitx_ctx_create_rect(const vitx_model *m, int device, int max_batch, int dtype, const vitx_ctx_options *opt_in, int img_h, int img_w, vitx_ctx **out) {
+    return ctx_create(m, device, max_batch, dtype, opt_in, true, img_h, img_w, out);
+}
+
 void vitx_ctx_free(vitx_ctx *c) { delete c; }
 int vitx_ctx_max_batch(const vitx_ctx *c) { return c ? c->max_batch : 0; }
 int vitx_ctx_img_size(const vitx_ctx *c) { return c ? c->S : 0; }
+int vitx_ctx_img_shape(const vitx_ctx *c, int *img_h, int *img_w) {
+    if (!c || !img_h || !img_w) { set_error("vitx_ctx_img_shape: NULL argument"); return VITX_ERR_ARG; }
+    *img_h = c->Sh; *img_w = c->Sw;
+    return VITX_OK;
+}
+int vitx_ctx_grid(const vitx_ctx *c, int *gh, int *gw) {
+    if (!c || !gh || !gw) { set_error("vitx_ctx_grid: NULL argument"); return VITX_ERR_ARG; }
+    *gh = c->gh; *gw = c->gw;
+    return VITX_OK;
+}
 int vitx_ctx_tokens(const vitx_ctx *c) { return c ? c->N : 0; }
 int vitx_ctx_registers(const vitx_ctx *c) { return c ? c->nreg : 0; }
 int vitx_ctx_out_rows(const vitx_ctx *c) { return c ? c->R : 0; }

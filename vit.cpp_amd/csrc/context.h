@@ -74,11 +74,15 @@ struct vitx_ctx {
     vitx_hparams hp{};
     int device = 0, dtype = VITX_F16, max_batch = 0;   // dtype: the type of every bf16 / f16 kernel (VITX_BF16 in an MXFP8 context)
     bool mx = false;                     // VITX_MXFP8: qkv, fc1 and fc2 take MX operands (norm1, norm2 and the fc1 output are encoded)
-    int D = 0, L = 0, H = 0, C = 0, P = 0, S = 0, g = 0, N = 0, Kpe = 0, Kpe_pad = 0, C_pad = 0;
+    int D = 0, L = 0, H = 0, C = 0, P = 0, N = 0, Kpe = 0, Kpe_pad = 0, C_pad = 0;
+    // geometry of THIS context (include/vitx.h "rectangular contexts"): images are [Sh][Sw][Cin], the patch grid is gh x gw, x fastest; a context of
+    // vitx_ctx_create_ex has Sh == Sw.  S = the side of a square context, 0 for any other (vitx_ctx_img_size): nothing sizes a buffer with it
+    int Sh = 0, Sw = 0, gh = 0, gw = 0, S = 0;
+    size_t img_floats() const { return (size_t)Sh * Sw * Cin; }      // one input image
     int Cin = 3;                         // input channels: 3 (RGB classifier) or 1 (ViTSTR, grey)
     int R = 1;                           // probability rows per image: 1 (cls token) or 25 (ViTSTR: tokens 0..24, vitstr.cpp:864-904)
     // Token layout of an image (include/vitx.h "Register tokens and the pooled head"): row 0 = class token, rows 1 .. nreg = register tokens,
-    // rows Tp .. N - 1 = patches in raster order; N = g * g + Tp
+    // rows Tp .. N - 1 = patches in raster order; N = gh * gw + Tp
     int nreg = 0, Tp = 1;                // register tokens of the model (reg_token), prefix tokens 1 + nreg (0 for a VITX_POOL_MAP model: no class token)
     int fc1_epi = EPI_BIAS_GELU;         // the fc1 epilogue of the model's activation (vitx_model_activation), taken once at creation; EPI_BIAS in a `glu` context
     // The MLP widths of the blocks: F = the hidden width, fc2's K; F1 = fc1's N.  4 D both, or -- a file with `glu` (include/vitx.h "gated MLP") --
@@ -119,9 +123,9 @@ struct vitx_ctx {
         }
     };
     std::shared_ptr<WeightSet> wset;     // never null once the context exists
-    const float *pos = nullptr;          // [1 + g * g][D] position table the patch embedding adds: wset->pos, or pos_own when img_size differs from the file's
+    const float *pos = nullptr;          // [1 + gh * gw][D] position table the patch embedding adds: wset->pos, or pos_own when the grid differs from the file's
     float *pos_own = nullptr;            // the table resampled to this context's grid (vitx_ctx_options::img_size, pos_interp); in `allocs`
-    // rotary position embeddings of a file with `rope` (include/vitx.h): cos and sin [g * g][hd / 2] f32 for THIS context's grid, one allocation in
+    // rotary position embeddings of a file with `rope` (include/vitx.h): cos and sin [gh * gw][hd / 2] f32 for THIS context's grid, one allocation in
     // `allocs` (the table depends on the context's size, not on the weights); nullptr for every other file: nothing is allocated or launched
     float *rope_cos = nullptr, *rope_sin = nullptr;
     bool weights_shared = false;         // this context found the set already uploaded (vitx_ctx_shares_weights)
@@ -192,7 +196,7 @@ struct vitx_ctx {
     std::vector<hipStream_t> probed_streams;   // caller streams the internal streams were already checked against (ensure_concurrent): never re-probed
     int stream_retries = 0;               // internal streams re-created because they did not run beside the caller's stream
     hipEvent_t probe_a = nullptr, probe_b = nullptr;
-    float *img = nullptr;        // [max_batch][S][S][3] staging for the host entry point
+    float *img = nullptr;        // [max_batch][Sh][Sw][Cin] staging for the host entry point
     float *probs = nullptr;      // [max_batch][C]
     float *logits_all = nullptr; // [max_batch][C] staging for the host entry point
     // residual-stream trace (vitx_trace_enable)

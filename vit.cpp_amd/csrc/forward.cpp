@@ -312,12 +312,12 @@ struct SliceForward {
         return features(il, tail_now, c->pool && il + 1 == c->L ? sl.Z : nullptr);
     }
     int run(const void *d_imgs, void *d_probs, void *d_logits) {
-        const int Mp_real = n * c->g * c->g;                           // patch rows
+        const int Mp_real = n * c->gh * c->gw;                          // patch rows
         // patch embedding (vit.cpp:747-797) in one launch: im2col gather, GEMM, + bias + pos, token scatter, class rows (patch_embed.hip)
         int rc;
         {
-            ProfScope ps(c, st, PC_GEMM_PATCH, 2.0 * Mp_real * (double)D * c->Kpe, (double)n * c->S * c->S * c->Cin * 4 + (double)M_real * D * 4);
-            HIP_TRY(launch_patch_embed(dt, (const float *)d_imgs, ws.pe_w, ws.pe_b, c->pos, ws.cls, ws.reg, c->nreg, sl.X, n, c->S, c->P, c->Cin, D, round_up(D, tn), c->Kpe_pad, st));
+            ProfScope ps(c, st, PC_GEMM_PATCH, 2.0 * Mp_real * (double)D * c->Kpe, (double)n * c->img_floats() * 4 + (double)M_real * D * 4);
+            HIP_TRY(launch_patch_embed(dt, (const float *)d_imgs, ws.pe_w, ws.pe_b, c->pos, ws.cls, ws.reg, c->nreg, sl.X, n, c->Sh, c->Sw, c->P, c->Cin, D, round_up(D, tn), c->Kpe_pad, st));
         }
         // pre-norm of a file with pre_norm.* (CLIP's pre_layrnorm): every token row, in place, before layer 0 -- trace stage 0 is the stream that enters it
         if (ws.pre_w) {
@@ -567,7 +567,7 @@ static int forward_pass(vitx_ctx *c, const void *d_imgs, int n, void *d_probs, v
         vitx_ctx::Slice &sl = c->slices[i];
         hipStream_t ss = (serial || i == 0) ? st : sl.stream;
         if (!serial && i > 0) HIP_TRY(hipStreamWaitEvent(sl.stream, c->fork, 0));
-        int rc = SliceForward{c, sl, ss, off[i], m[i]}.run((const float *)d_imgs + (size_t)off[i] * c->S * c->S * c->Cin, (float *)d_probs + (size_t)off[i] * c->R * c->C,
+        int rc = SliceForward{c, sl, ss, off[i], m[i]}.run((const float *)d_imgs + (size_t)off[i] * c->img_floats(), (float *)d_probs + (size_t)off[i] * c->R * c->C,
                                                            d_logits ? (float *)d_logits + (size_t)off[i] * c->R * c->C : nullptr);
         if (rc) return rc;
         if (!serial && i > 0) HIP_TRY(hipEventRecord(sl.done, sl.stream));
@@ -603,7 +603,7 @@ int vitx_forward_device(vitx_ctx *c, const void *d_imgs, int n, void *d_probs, v
     if (n > c->call_limit && c->zs_on()) { set_error("vitx_forward_device: zero-shot classification takes one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
     for (int i0 = 0; i0 < n; i0 += c->call_limit) {
         const int ni = std::min(c->call_limit, n - i0);
-        const int rc = forward_pass(c, (const float *)d_imgs + (size_t)i0 * c->S * c->S * c->Cin, ni, (float *)d_probs + (size_t)i0 * c->R * c->C,
+        const int rc = forward_pass(c, (const float *)d_imgs + (size_t)i0 * c->img_floats(), ni, (float *)d_probs + (size_t)i0 * c->R * c->C,
                                     d_logits ? (float *)d_logits + (size_t)i0 * c->R * c->C : nullptr, st);
         if (rc) return rc;
     }
@@ -616,7 +616,7 @@ int vitx_forward(vitx_ctx *c, const float *imgs, int n, float *probs, float *log
     if (!c || !imgs || !probs) { set_error("vitx_forward: NULL argument"); return VITX_ERR_ARG; }
     if (n <= 0 || n > c->max_batch) { set_error("vitx_forward: batch %d outside 1..%d", n, c->max_batch); return VITX_ERR_ARG; }
     HIP_TRY(hipSetDevice(c->device));
-    const size_t img_bytes = (size_t)n * c->S * c->S * c->Cin * 4;
+    const size_t img_bytes = (size_t)n * c->img_floats() * 4;
     HIP_TRY(hipMemcpyAsync(c->img, imgs, img_bytes, hipMemcpyHostToDevice, c->stream));
     int rc = vitx_forward_device(c, c->img, n, c->probs, logits ? c->logits_all : nullptr, c->stream);
     if (rc) return rc;

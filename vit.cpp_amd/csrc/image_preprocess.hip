@@ -96,7 +96,8 @@ hipError_t launch_preprocess(const void *u8, float *out, int n, int nx, int ny, 
 
 // ------------------------------------------------------------------------------------------------
 // Pillow's Image.resize on u8 + centre crop + mean / std (include/vitx.h "each model's own preprocessing"; the arithmetic: preproc_resample.h,
-// shared with the host loop in preprocess.cpp, so both give Pillow's bits).  u8 HWC [n][ny][nx][3] -> f32 HWC [n][S][S][3] in ONE launch.
+// shared with the host loop in preprocess.cpp, so both give Pillow's bits).  u8 HWC [n][ny][nx][3] -> f32 HWC [n][SH][SW][3] in ONE launch (the window is SW x SH: square for a description,
+// any pair for vitx_preprocess_rect_device).
 // A workgroup of 4 waves owns a PP_TW x PP_TH (32 x 8) tile of one image's output window:
 //   A  lanes 0 .. 39 (32 columns, then 8 rows; indices past the window's edge repeat its last one) find first / n of their target index and
 //      the weight total ww, in double;
@@ -111,7 +112,7 @@ hipError_t launch_preprocess(const void *u8, float *out, int n, int nx, int ny, 
 // ------------------------------------------------------------------------------------------------
 struct PpPilArgs {
     const unsigned char *src; float *dst;
-    int nx, ny, S, left, top, tiles_x;
+    int nx, ny, SW, SH, left, top, tiles_x;
     PilAxis ax, ay;
     int kx, ky, rows, span, stage;
     PpMeanStd nm;
@@ -131,8 +132,8 @@ __global__ __launch_bounds__(256) void pp_pil_kernel(const PpPilArgs a) {
     const int bx = blockIdx.x % a.tiles_x, by = blockIdx.x / a.tiles_x, b = blockIdx.y;
     const int ox0 = bx * PP_TW, oy0 = by * PP_TH;
     auto target = [&](int p) {                                // the resized image's index of table row p
-        if (p < PP_TW) { const int o = ox0 + p; return a.left + (o < a.S ? o : a.S - 1); }
-        const int o = oy0 + p - PP_TW; return a.top + (o < a.S ? o : a.S - 1);
+        if (p < PP_TW) { const int o = ox0 + p; return a.left + (o < a.SW ? o : a.SW - 1); }
+        const int o = oy0 + p - PP_TW; return a.top + (o < a.SH ? o : a.SH - 1);
     };
     if (tid < NP) {
         const PilAxis &ax = tid < PP_TW ? a.ax : a.ay;
@@ -183,19 +184,21 @@ __global__ __launch_bounds__(256) void pp_pil_kernel(const PpPilArgs a) {
         __syncthreads();
     }
 
-    float *out = a.dst + (size_t)b * a.S * a.S * 3;
+    float *out = a.dst + (size_t)b * a.SH * a.SW * 3;
     for (int item = tid; item < PP_TH * LINE; item += 256) {
         const int ty = item / LINE, e = item - ty * LINE, tx = e / 3, ch = e - tx * 3;
         const int oy = oy0 + ty, ox = ox0 + tx;
-        if (oy >= a.S || ox >= a.S) continue;
+        if (oy >= a.SH || ox >= a.SW) continue;
         const int rel = min(s_first[PP_TW + ty] - y0, R), nt = min(s_n[PP_TW + ty], R - rel);
         const unsigned char *m = s_h + rel * LINE + e;
         const int32_t *k = s_ky + ty * a.ky;
         int32_t acc = 1 << (PIL_PRECISION_BITS - 1);
         for (int i = 0; i < nt; ++i) acc += (int32_t)m[i * LINE] * k[i];
-        out[((size_t)oy * a.S + ox) * 3 + ch] = ((float)pil_clip8(acc) - a.nm.mean(ch)) / a.nm.sd(ch);
+        out[((size_t)oy * a.SW + ox) * 3 + ch] = ((float)pil_clip8(acc) - a.nm.mean(ch)) / a.nm.sd(ch);
     }
 }
+
+static hipError_t launch_pp_pil(const vitx_preproc &p, const PpGeom &g, const PpMeanStd &nm, const void *u8, float *out, int n, int nx, int ny, hipStream_t stream);
 
 bool preprocess_ex_supports(const vitx_preproc &p, int nx, int ny) {
     PpGeom g;
@@ -210,35 +213,54 @@ hipError_t launch_preprocess_ex(const vitx_preproc &p, const void *u8, float *ou
     if (n <= 0 || pp_check(p) || pp_geometry(p, nx, ny, g)) return hipErrorInvalidValue;
     const PpMeanStd nm = {p.mean255[0], p.mean255[1], p.mean255[2], p.std255[0], p.std255[1], p.std255[2]};
     if (!pp_filter_is_pil(p.filter)) {
-        const vitx_preproc d = pp_default(g.S);
+        const vitx_preproc d = pp_default(g.SW);
         bool imagenet = true;
         for (int c = 0; c < 3; ++c) imagenet = imagenet && p.mean255[c] == d.mean255[c] && p.std255[c] == d.std255[c];
         const int bicubic = p.filter == VITX_PP_REF_BICUBIC;
-        if (imagenet) return launch_preprocess(u8, out, n, nx, ny, g.S, bicubic, stream);
-        const long total = (long)n * g.S * g.S;
+        if (imagenet) return launch_preprocess(u8, out, n, nx, ny, g.SW, bicubic, stream);
+        const long total = (long)n * g.SW * g.SW;
         const int blocks = (int)std::min<long>((total + 255) / 256, 256L * 64);
-        if (bicubic) hipLaunchKernelGGL(preprocess_ms_kernel<true>, dim3(blocks), dim3(256), 0, stream, (const unsigned char *)u8, out, n, nx, ny, g.S, nm);
-        else hipLaunchKernelGGL(preprocess_ms_kernel<false>, dim3(blocks), dim3(256), 0, stream, (const unsigned char *)u8, out, n, nx, ny, g.S, nm);
+        if (bicubic) hipLaunchKernelGGL(preprocess_ms_kernel<true>, dim3(blocks), dim3(256), 0, stream, (const unsigned char *)u8, out, n, nx, ny, g.SW, nm);
+        else hipLaunchKernelGGL(preprocess_ms_kernel<false>, dim3(blocks), dim3(256), 0, stream, (const unsigned char *)u8, out, n, nx, ny, g.SW, nm);
         return hipGetLastError();
     }
+    return launch_pp_pil(p, g, nm, u8, out, n, nx, ny, stream);
+}
+
+// pp_pil_kernel on the window of g: the one launch of both the description's geometry and vitx_preprocess_rect_device's
+static hipError_t launch_pp_pil(const vitx_preproc &p, const PpGeom &g, const PpMeanStd &nm, const void *u8, float *out, int n, int nx, int ny, hipStream_t stream) {
     PpPilArgs a;
     const int bicubic = p.filter == VITX_PP_PIL_BICUBIC;
     a.ax = pil_axis(bicubic, nx, g.W); a.ay = pil_axis(bicubic, ny, g.H);
     const PpTiling t = pp_tiling(g, a.ax, a.ay);
     if (t.lds > (size_t)PP_LDS_LIMIT) return hipErrorInvalidValue;
-    a.nx = nx; a.ny = ny; a.S = g.S; a.left = g.left; a.top = g.top;
-    a.tiles_x = (g.S + PP_TW - 1) / PP_TW;
+    a.nx = nx; a.ny = ny; a.SW = g.SW; a.SH = g.SH; a.left = g.left; a.top = g.top;
+    a.tiles_x = (g.SW + PP_TW - 1) / PP_TW;
     a.kx = t.kx; a.ky = t.ky; a.rows = t.rows; a.span = t.span; a.stage = t.stage; a.nm = nm;
-    const int tiles = a.tiles_x * ((g.S + PP_TH - 1) / PP_TH);
+    const int tiles = a.tiles_x * ((g.SH + PP_TH - 1) / PP_TH);
     for (int i0 = 0; i0 < n; i0 += 65535) {                   // gridDim.y: images
         const int ni = std::min(n - i0, 65535);
         a.src = (const unsigned char *)u8 + (size_t)i0 * nx * ny * 3;
-        a.dst = out + (size_t)i0 * g.S * g.S * 3;
+        a.dst = out + (size_t)i0 * g.SH * g.SW * 3;
         hipLaunchKernelGGL(pp_pil_kernel, dim3(tiles, ni), dim3(256), t.lds, stream, a);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+bool preprocess_rect_supports(const vitx_preproc &p, int nx, int ny, int out_w, int out_h) {
+    PpGeom g;
+    if (pp_check(p) || !pp_filter_is_pil(p.filter) || pp_geometry_rect(nx, ny, out_w, out_h, g)) return false;
+    const int bicubic = p.filter == VITX_PP_PIL_BICUBIC;
+    return pp_tiling(g, pil_axis(bicubic, nx, g.W), pil_axis(bicubic, ny, g.H)).lds <= (size_t)PP_LDS_LIMIT;
+}
+
+hipError_t launch_preprocess_rect(const vitx_preproc &p, const void *u8, float *out, int n, int nx, int ny, int out_w, int out_h, hipStream_t stream) {
+    PpGeom g;
+    if (n <= 0 || pp_check(p) || !pp_filter_is_pil(p.filter) || pp_geometry_rect(nx, ny, out_w, out_h, g)) return hipErrorInvalidValue;
+    const PpMeanStd nm = {p.mean255[0], p.mean255[1], p.mean255[2], p.std255[0], p.std255[1], p.std255[2]};
+    return launch_pp_pil(p, g, nm, u8, out, n, nx, ny, stream);
 }
 
 }  // namespace vitx

@@ -147,12 +147,12 @@ int gemm_tile_n();
 
 // Patch embedding in one launch (patch_embed.hip; vit.cpp:747-797): with T = 1 + n_reg prefix tokens and N = T + patches rows per image,
 // X[b * N + T + t][:] = W . patch(b, t) + bias + pos[1 + t], X[b * N][:] = cls + pos[0], X[b * N + 1 + r][:] = reg[r] (no position term).
-// img: f32 HWC [n_img][S][S][Cin] (Cin = 3: RGB classifier input; 1: the grey ViTSTR input, extensions/vitstr.cpp/vitstr.cpp:713-731);
+// img: f32 HWC [n_img][img_h][img_w][Cin], both sides multiples of P, patches in raster order with img_w / P per row (Cin = 3: RGB classifier input; 1: the grey ViTSTR input, extensions/vitstr.cpp/vitstr.cpp:713-731);
 // w_perm: the [n_pad][k_pad] operand-type kernel with its K axis permuted by patch_embed_permute_k (host side, at upload); pos [1 + patches][D],
 // cls [D], reg [n_reg][D] (nullptr when n_reg == 0).  cls == nullptr (n_reg == 0): no prefix token at all -- N = patches, X[b * N + t][:] = W . patch(b, t) + bias + pos[t],
 // pos [patches][D] (a VITX_POOL_MAP model).
 hipError_t launch_patch_embed(int dtype, const float *img, const void *w_perm, const float *bias, const float *pos, const float *cls, const float *reg, int n_reg,
-                              float *X, int n_img, int S, int P, int Cin, int D, int n_pad, int k_pad, hipStream_t stream);
+                              float *X, int n_img, int img_h, int img_w, int P, int Cin, int D, int n_pad, int k_pad, hipStream_t stream);
 void patch_embed_permute_k(const uint16_t *w, uint16_t *w_perm, int N, int Cin, int P, int k_pad);
 // y[r][:] (dtype) = LN(x[r*ldx ...]) * w + b   (layernorm.hip; vit.cpp:808-812)
 // group > 1: input row r = x + (r / group) * gstride + (r % group) * ldx (the first `group` tokens of every image: ViTSTR head)
@@ -259,6 +259,10 @@ hipError_t launch_preprocess(const void *u8, float *out, int n, int nx, int ny, 
 // hipErrorInvalidValue for an invalid description or source, or a down-scale whose tile does not fit the LDS (preprocess_ex_supports)
 hipError_t launch_preprocess_ex(const vitx_preproc &p, const void *u8, float *out, int n, int nx, int ny, hipStream_t stream);
 bool preprocess_ex_supports(const vitx_preproc &p, int nx, int ny);
+// the PIL kernel with a rectangular output window: the whole source stretched to out_w x out_h with the description's filter and mean / std
+// (vitx_preprocess_rect_device); hipErrorInvalidValue also for a REF filter
+hipError_t launch_preprocess_rect(const vitx_preproc &p, const void *u8, float *out, int n, int nx, int ny, int out_w, int out_h, hipStream_t stream);
+bool preprocess_rect_supports(const vitx_preproc &p, int nx, int ny, int out_w, int out_h);
 // out[row][k] = {f32 probability, i32 class} of the k largest entries of probs[row][0..cols), descending, ties by the lower class index
 // (softmax_topk.hip; the sort of vit_predict, vit.cpp:1043-1057, on the device: the multi-GPU gather then moves 8 k bytes per row instead of 4 cols)
 hipError_t launch_topk(const float *probs, int rows, int cols, int k, void *out_pairs, hipStream_t stream);

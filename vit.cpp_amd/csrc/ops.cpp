@@ -248,11 +248,12 @@ int vitx_op_features_ex(const void *d_x, long row_stride, long img_stride, const
 }
 // The product's patch-embedding kernel on its own (TEST ONLY: allocates, uploads and synchronises).  d_w: the f32 kernel [D][Cin * P * P] in the
 // file's order (channel-major); it is rounded (RNE) to the operand type, K-permuted and padded exactly as the context does at upload.
-int vitx_op_patch_embed(int dtype, const void *d_img, const void *d_w, const void *d_bias, const void *d_pos, const void *d_cls, const void *d_reg, int R, void *d_X,
-                        int n_img, int S, int P, int Cin, int D, void *stream) {
-    if (!d_img || !d_w || !d_bias || !d_pos || (!d_cls && R != 0) || !d_X || R < 0 || (R > 0 && !d_reg) || n_img <= 0 || S <= 0 || P <= 0 || S % P || Cin <= 0 || D <= 0 || D % 4 ||
-        (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_patch_embed: invalid argument"); return VITX_ERR_ARG; }
-    if (!tuning_for_device(-1)) { set_error("vitx_op_patch_embed: kernel bring-up failed"); return VITX_ERR_HIP; }
+// vitx_op_patch_embed_rect: the same on [n][img_h][img_w][Cin] images (one body; the square entry point passes S twice).
+static int op_patch_embed(const char *name, int dtype, const void *d_img, const void *d_w, const void *d_bias, const void *d_pos, const void *d_cls, const void *d_reg, int R, void *d_X,
+                          int n_img, int img_h, int img_w, int P, int Cin, int D, void *stream) {
+    if (!d_img || !d_w || !d_bias || !d_pos || (!d_cls && R != 0) || !d_X || R < 0 || (R > 0 && !d_reg) || n_img <= 0 || img_h <= 0 || img_w <= 0 || P <= 0 || img_h % P || img_w % P ||
+        Cin <= 0 || D <= 0 || D % 4 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("%s: invalid argument", name); return VITX_ERR_ARG; }
+    if (!tuning_for_device(-1)) { set_error("%s: kernel bring-up failed", name); return VITX_ERR_HIP; }
     const int K = Cin * P * P, k_pad = round_up(K, 64), n_pad = round_up(D, gemm_tile_n());
     std::vector<float> wf((size_t)D * K);
     HIP_TRY(hipMemcpy(wf.data(), d_w, wf.size() * 4, hipMemcpyDeviceToHost));
@@ -267,9 +268,17 @@ int vitx_op_patch_embed(int dtype, const void *d_img, const void *d_w, const voi
     if (e == hipSuccess) e = hipMemset(bias, 0, (size_t)n_pad * 4);
     if (e == hipSuccess) e = hipMemcpy(bias, d_bias, (size_t)D * 4, hipMemcpyDeviceToDevice);
     if (e == hipSuccess) e = launch_patch_embed(dtype, (const float *)d_img, w_perm, bias, (const float *)d_pos, (const float *)d_cls, (const float *)d_reg, R,
-                                                (float *)d_X, n_img, S, P, Cin, D, n_pad, k_pad, st);
+                                                (float *)d_X, n_img, img_h, img_w, P, Cin, D, n_pad, k_pad, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return op_rc("vitx_op_patch_embed", e, VITX_ERR_UNSUPPORTED);
+    return op_rc(name, e, VITX_ERR_UNSUPPORTED);
+}
+int vitx_op_patch_embed(int dtype, const void *d_img, const void *d_w, const void *d_bias, const void *d_pos, const void *d_cls, const void *d_reg, int R, void *d_X,
+                        int n_img, int S, int P, int Cin, int D, void *stream) {
+    return op_patch_embed("vitx_op_patch_embed", dtype, d_img, d_w, d_bias, d_pos, d_cls, d_reg, R, d_X, n_img, S, S, P, Cin, D, stream);
+}
+int vitx_op_patch_embed_rect(int dtype, const void *d_img, const void *d_w, const void *d_bias, const void *d_pos, const void *d_cls, const void *d_reg, int R,
+                             int n_img, int img_h, int img_w, int P, int Cin, int D, void *d_X) {
+    return op_patch_embed("vitx_op_patch_embed_rect", dtype, d_img, d_w, d_bias, d_pos, d_cls, d_reg, R, d_X, n_img, img_h, img_w, P, Cin, D, nullptr);
 }
 // The pooling kernel of the attention-pooling head on its own.  Every argument check comes before the first device call.
 int vitx_op_attention_pool(const void *d_x, long row_stride, long img_stride, const void *d_ln_w, const void *d_ln_b, float eps, const void *d_u, void *d_M, void *d_p,
@@ -385,6 +394,20 @@ int vitx_preprocess_ex_device(const vitx_preproc *pp, const void *d_hwc, int n, 
         return VITX_ERR_UNSUPPORTED;
     }
     return op_rc("vitx_preprocess_ex_device", launch_preprocess_ex(*pp, d_hwc, (float *)d_out, n, nx, ny, (hipStream_t)stream));
+}
+int vitx_preprocess_rect_device_supports(const vitx_preproc *pp, int nx, int ny, int out_w, int out_h) { return pp && preprocess_rect_supports(*pp, nx, ny, out_w, out_h) ? 1 : 0; }
+int vitx_preprocess_rect_device(const vitx_preproc *pp, const void *d_hwc, int n, int nx, int ny, int out_w, int out_h, void *d_out, void *stream) {
+    if (!pp || !d_hwc || !d_out || n <= 0) { set_error("vitx_preprocess_rect_device: invalid argument"); return VITX_ERR_ARG; }
+    PpGeom g;
+    const char *bad = pp_check(*pp);
+    if (!bad) bad = pp_geometry_rect(nx, ny, out_w, out_h, g);
+    if (bad) { set_error("vitx_preprocess_rect_device: %s", bad); return VITX_ERR_ARG; }
+    if (!pp_filter_is_pil(pp->filter)) { set_error("vitx_preprocess_rect_device: the reference's filters resize to squares only (use a PIL filter)"); return VITX_ERR_UNSUPPORTED; }
+    if (!preprocess_rect_supports(*pp, nx, ny, out_w, out_h)) {
+        set_error("vitx_preprocess_rect_device: a %d x %d source resized to %d x %d needs more than 64 KiB of LDS per tile (use vitx_preprocess_rect)", nx, ny, out_w, out_h);
+        return VITX_ERR_UNSUPPORTED;
+    }
+    return op_rc("vitx_preprocess_rect_device", launch_preprocess_rect(*pp, d_hwc, (float *)d_out, n, nx, ny, out_w, out_h, (hipStream_t)stream));
 }
 int vitx_preprocess_u8_device(const void *d_hwc, int n, int nx, int ny, int img_size, int interp, void *d_out, void *stream) {
     if (!d_hwc || !d_out || n <= 0 || nx <= 0 || ny <= 0 || img_size <= 0) { set_error("vitx_preprocess_u8_device: invalid argument"); return VITX_ERR_ARG; }

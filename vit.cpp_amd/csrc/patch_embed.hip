@@ -28,7 +28,7 @@ constexpr int TILE = BM * BK * 2, STAGE = 2 * TILE, LDS_BYTES = 2 * STAGE;      
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void patch_embed_kernel(GemmArgs g, const float *__restrict__ img, const float *__restrict__ cls, const float *__restrict__ reg, int S, int P, int Cin, int gsz /* patches per image row */) {
+__global__ __launch_bounds__(256) void patch_embed_kernel(GemmArgs g, const float *__restrict__ img, const float *__restrict__ cls, const float *__restrict__ reg, int IH, int IW /* the image's height and width */, int P, int Cin, int gw /* patches per image row */) {
     using namespace pe;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef typename Elem<T>::v8 v8;
@@ -59,10 +59,12 @@ __global__ __launch_bounds__(256) void patch_embed_kernel(GemmArgs g, const floa
     const bool row_ok = m < g.M_real;
     const float *prow;                  // first float of the patch: pixel (py * P, px * P), channel 0
     {
-        const int b = m / tpi, t = m - b * tpi, py = t / gsz, px = t - py * gsz;
-        prow = img + (((size_t)b * S + (size_t)py * P) * S + (size_t)px * P) * Cin;
+        const int b = m / tpi, t = m - b * tpi, py = t / gw, px = t - py * gw;
+        prow = img + (((size_t)b * IH + (size_t)py * P) * IW + (size_t)px * P) * Cin;      // row pitch IW * Cin floats, image stride IH * IW * Cin
     }
-    const bool fast = (PC & 15) == 0;   // a 16-float group never straddles an image row
+    // a 16-float group never straddles an image row; with P * Cin a multiple of 16 every patch row starts at px * P * Cin and every image row at
+    // a multiple of IW * Cin = gw * P * Cin floats, both multiples of 16 at ANY gw: the f32x4 loads stay aligned on a rectangular image
+    const bool fast = (PC & 15) == 0;
     f32x4 areg[2][4];
     auto load_a = [&](int kt) {
 #pragma unroll
@@ -70,7 +72,7 @@ __global__ __launch_bounds__(256) void patch_embed_kernel(GemmArgs g, const floa
             const int k0 = kt * BK + (a_h * 2 + q) * 16;
             if (fast) {
                 const int ky = k0 / PC, r0 = k0 - ky * PC;
-                const f32x4 *src = (const f32x4 *)(prow + (size_t)ky * S * Cin + r0);
+                const f32x4 *src = (const f32x4 *)(prow + (size_t)ky * IW * Cin + r0);
                 const bool ok = row_ok && k0 < K;            // K is a multiple of 16 here: a group is all inside or all padding
 #pragma unroll
                 for (int e = 0; e < 4; ++e) areg[q][e] = ok ? src[e] : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
@@ -78,7 +80,7 @@ __global__ __launch_bounds__(256) void patch_embed_kernel(GemmArgs g, const floa
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     const int k = k0 + e, ky = k / PC, r = k - ky * PC;
-                    areg[q][e >> 2][e & 3] = (row_ok && k < K) ? prow[(size_t)ky * S * Cin + r] : 0.0f;
+                    areg[q][e >> 2][e & 3] = (row_ok && k < K) ? prow[(size_t)ky * IW * Cin + r] : 0.0f;
                 }
             }
         }
@@ -177,15 +179,16 @@ hipError_t prepare_patch_embed() {       // device bring-up
 }
 
 hipError_t launch_patch_embed(int dtype, const float *img, const void *w_perm, const float *bias, const float *pos, const float *cls, const float *reg, int n_reg,
-                              float *X, int n_img, int S, int P, int Cin, int D, int n_pad, int k_pad, hipStream_t stream) {
-    const int gsz = S / P, tpi = gsz * gsz;
-    if (n_img <= 0 || P <= 0 || S % P || n_pad % pe::BN || k_pad % pe::BK || k_pad < Cin * P * P || D % 4 || n_reg < 0 || (n_reg > 0 && (!reg || !cls))) return hipErrorInvalidValue;
+                              float *X, int n_img, int img_h, int img_w, int P, int Cin, int D, int n_pad, int k_pad, hipStream_t stream) {
+    if (n_img <= 0 || P <= 0 || img_h <= 0 || img_w <= 0 || img_h % P || img_w % P || n_pad % pe::BN || k_pad % pe::BK || k_pad < Cin * P * P || D % 4 || n_reg < 0 || (n_reg > 0 && (!reg || !cls))) return hipErrorInvalidValue;
+    const int gh = img_h / P, gw = img_w / P, tpi = gh * gw;
+    if ((long)n_img * tpi > 0x7fffff00l) return hipErrorInvalidValue;            // patch rows are 32-bit in the kernel
     GemmArgs g{};
     g.W = w_perm; g.bias = bias; g.out = X; g.pos = pos;
     g.M_real = n_img * tpi; g.M = (g.M_real + pe::BM - 1) / pe::BM * pe::BM; g.N = D; g.N_pad = n_pad; g.K = k_pad; g.ldw = k_pad; g.ldo = D; g.tpi = tpi; g.prefix = cls ? 1 + n_reg : 0;
     const int grid = (g.M / pe::BM) * (n_pad / pe::BN);
-    if (dtype == DT_F16) hipLaunchKernelGGL(patch_embed_kernel<_Float16>, dim3(grid), dim3(256), pe::LDS_BYTES, stream, g, img, cls, reg, S, P, Cin, gsz);
-    else hipLaunchKernelGGL(patch_embed_kernel<__bf16>, dim3(grid), dim3(256), pe::LDS_BYTES, stream, g, img, cls, reg, S, P, Cin, gsz);
+    if (dtype == DT_F16) hipLaunchKernelGGL(patch_embed_kernel<_Float16>, dim3(grid), dim3(256), pe::LDS_BYTES, stream, g, img, cls, reg, img_h, img_w, P, Cin, gw);
+    else hipLaunchKernelGGL(patch_embed_kernel<__bf16>, dim3(grid), dim3(256), pe::LDS_BYTES, stream, g, img, cls, reg, img_h, img_w, P, Cin, gw);
     return hipGetLastError();
 }
 

@@ -92,7 +92,7 @@ VITX_HD int pil_clip8(int32_t acc) {
 struct PpGeom {
     int W, H;          // the resized image
     int left, top;     // the crop window's corner in it
-    int S;             // the output side
+    int SW, SH;        // the output window's width and height (equal for a description: pp_check; any pair for vitx_preprocess_rect)
 };
 
 enum { PP_MAX_SIDE = 16384, PP_MAX_SRC = 1 << 20 };
@@ -135,10 +135,32 @@ inline const char *pp_geometry(const vitx_preproc &p, int nx, int ny, PpGeom &g)
         const int le = (int)lv;
         if (nx <= ny) { g.W = p.resize_a; g.H = le; } else { g.W = le; g.H = p.resize_a; }
     }
-    g.S = p.crop ? p.crop : p.resize_a;
+    g.SW = g.SH = p.crop ? p.crop : p.resize_a;
     if (p.crop > g.W || p.crop > g.H) return "the crop is larger than the resized image (padding is not offered)";
     g.left = p.crop ? pp_crop_offset(g.W - p.crop, p.crop_round) : 0;
     g.top = p.crop ? pp_crop_offset(g.H - p.crop, p.crop_round) : 0;
+    return nullptr;
+}
+
+// vitx_preprocess_rect (include/vitx.h "rectangular contexts"): the whole source stretched to out_w x out_h, no crop; the description gives the
+// filter and mean / std only.  nullptr = fine and g filled, else what is wrong.  pp_check(p) has passed.
+inline const char *pp_geometry_rect(int nx, int ny, int out_w, int out_h, PpGeom &g) {
+    if (nx <= 0 || ny <= 0 || nx > PP_MAX_SRC || ny > PP_MAX_SRC) return "the source sides must be in 1 .. 2^20";
+    if (out_w <= 0 || out_h <= 0 || out_w > PP_MAX_SIDE || out_h > PP_MAX_SIDE) return "the output sides must be in 1 .. 16384";
+    g.W = g.SW = out_w; g.H = g.SH = out_h; g.left = g.top = 0;
+    return nullptr;
+}
+
+// The aspect-preserving shape of vitx_rect_shape, in integers only; nullptr = fine, else what is wrong
+inline const char *pp_rect_shape(int nx, int ny, int patch, int short_side, int max_long, int &out_w, int &out_h) {
+    if (nx <= 0 || ny <= 0 || nx > PP_MAX_SRC || ny > PP_MAX_SRC) return "the source sides must be in 1 .. 2^20";
+    if (patch <= 0 || short_side <= 0 || short_side % patch || short_side > PP_MAX_SIDE) return "short_side must be a positive multiple of patch, at most 16384";
+    if (max_long != 0 && (max_long < short_side || max_long % patch || max_long > PP_MAX_SIDE)) return "max_long must be 0 or a multiple of patch in short_side .. 16384";
+    const int s = nx <= ny ? nx : ny, l = nx <= ny ? ny : nx;
+    int64_t lg = (int64_t)short_side * l / s / patch * patch;          // >= short_side: l >= s and short_side is a multiple of patch
+    if (max_long != 0 && lg > max_long) lg = max_long;
+    if (lg > PP_MAX_SIDE) return "the long side exceeds 16384 (set max_long)";
+    if (nx <= ny) { out_w = short_side; out_h = (int)lg; } else { out_w = (int)lg; out_h = short_side; }
     return nullptr;
 }
 
@@ -156,16 +178,16 @@ struct PpTiling {
 inline PpTiling pp_tiling(const PpGeom &g, const PilAxis &ax, const PilAxis &ay) {
     PpTiling t;
     t.kx = ax.ksize; t.ky = ay.ksize; t.rows = 1; t.span = 1;
-    for (int o0 = 0; o0 < g.S; o0 += PP_TW) {
-        const int o1 = (o0 + PP_TW < g.S ? o0 + PP_TW : g.S) - 1;
+    for (int o0 = 0; o0 < g.SW; o0 += PP_TW) {                // each axis is walked to its own length
+        const int o1 = (o0 + PP_TW < g.SW ? o0 + PP_TW : g.SW) - 1;
         int f0, n0, f1, n1;
         pil_bounds(ax, g.left + o0, f0, n0); pil_bounds(ax, g.left + o1, f1, n1);
         // first and first + n never decrease with o, so the tile's span runs from its first column's first tap to its last column's last
         const int s = (f1 + n1 > f0 + n0 ? f1 + n1 : f0 + n0) - f0;
         if (s > t.span) t.span = s;
     }
-    for (int o0 = 0; o0 < g.S; o0 += PP_TH) {
-        const int o1 = (o0 + PP_TH < g.S ? o0 + PP_TH : g.S) - 1;
+    for (int o0 = 0; o0 < g.SH; o0 += PP_TH) {
+        const int o1 = (o0 + PP_TH < g.SH ? o0 + PP_TH : g.SH) - 1;
         int f0, n0, f1, n1;
         pil_bounds(ay, g.top + o0, f0, n0); pil_bounds(ay, g.top + o1, f1, n1);
         const int s = (f1 + n1 > f0 + n0 ? f1 + n1 : f0 + n0) - f0;

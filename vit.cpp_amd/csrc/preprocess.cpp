@@ -94,7 +94,7 @@ void reference_resize(const uint8_t *hwc, int nx, int ny, int S, bool bicubic, c
     parallel_rows(S, [&](int r0, int r1) { if (bicubic) bicubic_rows(hwc, nx, ny, S, mean, sd, out, r0, r1); else bilinear_rows(hwc, nx, ny, S, mean, sd, out, r0, r1); });
 }
 
-// One axis of the crop window: first tap, tap count and the fixed-point coefficients of its S target indices (preproc_resample.h)
+// One axis of the output window: first tap, tap count and the fixed-point coefficients of its S target indices (preproc_resample.h)
 struct PilTable {
     std::vector<int> first, n;
     std::vector<int32_t> k;
@@ -111,18 +111,18 @@ struct PilTable {
 };
 
 // Pillow's Image.resize on u8, the crop window only: horizontal pass over the source rows the window's vertical taps need into a u8
-// intermediate [rows][S][3], then the vertical pass, clamp and normalise
+// intermediate [rows][SW][3], then the vertical pass, clamp and normalise.  The window is SW x SH (square for a description's geometry)
 void pil_resize(const vitx_preproc &p, const vitx::PpGeom &g, const uint8_t *src, int nx, int ny, float *out) {
-    const int bicubic = p.filter == VITX_PP_PIL_BICUBIC, S = g.S;
-    const PilTable tx(vitx::pil_axis(bicubic, nx, g.W), g.left, S), ty(vitx::pil_axis(bicubic, ny, g.H), g.top, S);
+    const int bicubic = p.filter == VITX_PP_PIL_BICUBIC, SW = g.SW, SH = g.SH;
+    const PilTable tx(vitx::pil_axis(bicubic, nx, g.W), g.left, SW), ty(vitx::pil_axis(bicubic, ny, g.H), g.top, SH);
     const int y0 = ty.lo, rows = ty.hi - ty.lo;
-    const size_t line = (size_t)S * 3;
+    const size_t line = (size_t)SW * 3;
     std::vector<uint8_t> mid((size_t)rows * line);
     parallel_rows(rows, [&](int r0, int r1) {
         for (int r = r0; r < r1; ++r) {
             const uint8_t *row = src + (size_t)(y0 + r) * nx * 3;
             uint8_t *m = mid.data() + (size_t)r * line;
-            for (int c = 0; c < S; ++c) {
+            for (int c = 0; c < SW; ++c) {
                 const int32_t *k = tx.k.data() + (size_t)c * tx.ksize;
                 const uint8_t *px = row + (size_t)tx.first[c] * 3;
                 for (int ch = 0; ch < 3; ++ch) {
@@ -133,7 +133,7 @@ void pil_resize(const vitx_preproc &p, const vitx::PpGeom &g, const uint8_t *src
             }
         }
     });
-    parallel_rows(S, [&](int r0, int r1) {
+    parallel_rows(SH, [&](int r0, int r1) {
         for (int oy = r0; oy < r1; ++oy) {
             const int32_t *k = ty.k.data() + (size_t)oy * ty.ksize;
             const uint8_t *m = mid.data() + (size_t)(ty.first[oy] - y0) * line;
@@ -194,8 +194,28 @@ extern "C" int vitx_preprocess_ex(const vitx_preproc *pp, const uint8_t *hwc, in
     const char *bad = vitx::pp_check(*pp);
     if (!bad) bad = vitx::pp_geometry(*pp, nx, ny, g);
     if (bad) { vitx::set_error("vitx_preprocess_ex: %s", bad); return VITX_ERR_ARG; }
-    if (!vitx::pp_filter_is_pil(pp->filter)) reference_resize(hwc, nx, ny, g.S, pp->filter == VITX_PP_REF_BICUBIC, pp->mean255, pp->std255, out);
+    if (!vitx::pp_filter_is_pil(pp->filter)) reference_resize(hwc, nx, ny, g.SW, pp->filter == VITX_PP_REF_BICUBIC, pp->mean255, pp->std255, out);
     else pil_resize(*pp, g, hwc, nx, ny, out);
+    return VITX_OK;
+}
+
+// ---- rectangular outputs (include/vitx.h "rectangular contexts") ---------------------------------------------------------
+extern "C" int vitx_rect_shape(int nx, int ny, int patch, int short_side, int max_long, int *out_w, int *out_h) {
+    if (!out_w || !out_h) { vitx::set_error("vitx_rect_shape: NULL argument"); return VITX_ERR_ARG; }
+    int w = 0, h = 0;
+    if (const char *bad = vitx::pp_rect_shape(nx, ny, patch, short_side, max_long, w, h)) { vitx::set_error("vitx_rect_shape: %s", bad); return VITX_ERR_ARG; }
+    *out_w = w; *out_h = h;
+    return VITX_OK;
+}
+
+extern "C" int vitx_preprocess_rect(const vitx_preproc *pp, const uint8_t *hwc, int nx, int ny, int out_w, int out_h, float *out) {
+    if (!pp || !hwc || !out) { vitx::set_error("vitx_preprocess_rect: NULL argument"); return VITX_ERR_ARG; }
+    vitx::PpGeom g;
+    const char *bad = vitx::pp_check(*pp);
+    if (!bad) bad = vitx::pp_geometry_rect(nx, ny, out_w, out_h, g);
+    if (bad) { vitx::set_error("vitx_preprocess_rect: %s", bad); return VITX_ERR_ARG; }
+    if (!vitx::pp_filter_is_pil(pp->filter)) { vitx::set_error("vitx_preprocess_rect: the reference's filters resize to squares only (use a PIL filter)"); return VITX_ERR_UNSUPPORTED; }
+    pil_resize(*pp, g, hwc, nx, ny, out);
     return VITX_OK;
 }
 

@@ -70,20 +70,54 @@ bool vit_image_preprocess_model(const image_u8 &img, image_f32 &res, const vit_m
     return true;
 }
 
+// No counterpart in the reference: the whole image stretched to w x h for a rectangular state (vitx_preprocess_rect)
+bool vit_image_preprocess_rect(const image_u8 &img, image_f32 &res, const vit_model &model, int w, int h) {
+    vitx_preproc pp;
+    if (!model.handle || vitx_model_preproc(model.handle, &pp) != VITX_OK) { fprintf(stderr, "%s: no model is loaded\n", __func__); return false; }
+    if (pp.filter != VITX_PP_PIL_BILINEAR && pp.filter != VITX_PP_PIL_BICUBIC) pp.filter = VITX_PP_PIL_BICUBIC;
+    if (w <= 0 || h <= 0) { fprintf(stderr, "%s: the shape %d x %d is not positive\n", __func__, w, h); return false; }
+    res.nx = w; res.ny = h;
+    res.data.resize((size_t)3 * w * h);
+    if (vitx_preprocess_rect(&pp, img.data.data(), img.nx, img.ny, w, h, res.data.data()) != VITX_OK) { fprintf(stderr, "%s: %s\n", __func__, vitx_last_error()); return false; }
+    return true;
+}
+
 // The reference's vit_state carries no weights and can be reused with any model; ours caches a context that does, so the cache
 // is keyed on the unique id of the parsed model it was built from (vit_model_load frees and replaces that handle on every call).
 // The input side a state's context takes: vit_state::img_size, or the file's when that is 0
 static int state_img_size(const vit_model &model, const vit_state &state) { return state.img_size > 0 ? state.img_size : model.hparams.img_size; }
 
+// ... and the shape: img_h x img_w of a rectangular state, the square of state_img_size otherwise.  false (and a message): img_h / img_w half set, or set beside img_size
+static bool state_shape(const vit_model &model, const vit_state &state, int &h, int &w, const char *who) {
+    const bool rect = state.img_h != 0 || state.img_w != 0;
+    if (rect && (state.img_h <= 0 || state.img_w <= 0 || state.img_size != 0)) {
+        fprintf(stderr, "%s: vit_state::img_h and img_w are set together, with img_size == 0 (img_h %d, img_w %d, img_size %d)\n", who, state.img_h, state.img_w, state.img_size);
+        return false;
+    }
+    h = rect ? state.img_h : state_img_size(model, state);
+    w = rect ? state.img_w : h;
+    return true;
+}
+// n images of the state's shape?  -1 or the index of the first that is not
+static int first_bad_image(const image_f32 *imgs, int n, int h, int w) {
+    for (int i = 0; i < n; ++i) if (imgs[i].nx != w || imgs[i].ny != h || imgs[i].data.size() != (size_t)3 * h * w) return i;
+    return -1;
+}
+
 static int ensure_ctx(const vit_model &model, vit_state &state, int n) {
-    const int S = state_img_size(model, state);
-    const bool same_geometry = state.ctx && vitx_ctx_img_size(state.ctx) == S && (S == model.hparams.img_size || state.ctx_pos_interp == state.pos_interp);
+    int Sh = 0, Sw = 0, ch = -1, cw = -1;
+    if (!state_shape(model, state, Sh, Sw, __func__)) return VITX_ERR_ARG;
+    const bool rect = state.img_h != 0;
+    if (state.ctx) (void)vitx_ctx_img_shape(state.ctx, &ch, &cw);
+    const bool own = Sh == model.hparams.img_size && Sw == model.hparams.img_size;
+    const bool same_geometry = state.ctx && ch == Sh && cw == Sw && (own || state.ctx_pos_interp == state.pos_interp);
     if (same_geometry && state.ctx_model_uid == vitx_model_uid(model.handle) && vitx_ctx_max_batch(state.ctx) >= n) return VITX_OK;
     vitx_ctx_free(state.ctx); state.ctx = nullptr; state.ctx_model_uid = 0;
     state.max_batch = std::max(state.max_batch, n);
     vitx_ctx_options opt{};
     opt.struct_size = (int32_t)sizeof(opt); opt.img_size = state.img_size; opt.pos_interp = state.pos_interp;
-    const int rc = vitx_ctx_create_ex(model.handle, state.device, state.max_batch, state.dtype, &opt, &state.ctx);
+    const int rc = rect ? vitx_ctx_create_rect(model.handle, state.device, state.max_batch, state.dtype, &opt, Sh, Sw, &state.ctx)
+                        : vitx_ctx_create_ex(model.handle, state.device, state.max_batch, state.dtype, &opt, &state.ctx);
     if (rc == VITX_OK) { state.ctx_model_uid = vitx_model_uid(model.handle); state.ctx_pos_interp = state.pos_interp; }
     return rc;
 }
@@ -93,18 +127,20 @@ int vit_predict_batch(const vit_model &model, vit_state &state, const image_f32 
     predictions.clear();
     if (!model.handle || !imgs || n <= 0) { fprintf(stderr, "%s: invalid argument\n", __func__); return 1; }
     if (vitx_model_seq_len(model.handle) > 0) { fprintf(stderr, "%s: this is a ViTSTR model (one-channel patch kernel): use vitstr_predict\n", __func__); return 1; }
-    const int S = state_img_size(model, state), C = model.hparams.num_classes;
-    for (int i = 0; i < n; ++i)
-        if (imgs[i].nx != S || imgs[i].ny != S || imgs[i].data.size() != (size_t)3 * S * S) {      // GGML_ASSERT at vit.cpp:757
-            fprintf(stderr, "%s: image %d is %dx%d, this state expects %dx%d\n", __func__, i, imgs[i].nx, imgs[i].ny, S, S);
-            abort();
-        }
+    const int C = model.hparams.num_classes;
+    int Sh = 0, Sw = 0;
+    if (!state_shape(model, state, Sh, Sw, __func__)) return 1;
+    const size_t img_floats = (size_t)3 * Sh * Sw;
+    if (const int i = first_bad_image(imgs, n, Sh, Sw); i >= 0) {                                  // GGML_ASSERT at vit.cpp:757
+        fprintf(stderr, "%s: image %d is %dx%d, this state expects %dx%d\n", __func__, i, imgs[i].nx, imgs[i].ny, Sw, Sh);
+        abort();
+    }
     if (ensure_ctx(model, state, n) != VITX_OK) { fprintf(stderr, "%s: failed to encode image: %s\n", __func__, vitx_last_error()); return 1; }
     std::vector<float> batch;
     const float *src = imgs[0].data.data();
     if (n > 1) {
-        batch.resize((size_t)n * 3 * S * S);
-        for (int i = 0; i < n; ++i) std::copy(imgs[i].data.begin(), imgs[i].data.end(), batch.begin() + (size_t)i * 3 * S * S);
+        batch.resize((size_t)n * img_floats);
+        for (int i = 0; i < n; ++i) std::copy(imgs[i].data.begin(), imgs[i].data.end(), batch.begin() + (size_t)i * img_floats);
         src = batch.data();
     }
     state.prediction.resize((size_t)n * C);
@@ -132,16 +168,18 @@ int vit_embed_batch(const vit_model &model, vit_state &state, const image_f32 *i
     out.clear();
     if (!model.handle || !imgs || n <= 0 || !flags) { fprintf(stderr, "%s: invalid argument\n", __func__); return 1; }
     if (vitx_model_seq_len(model.handle) > 0) { fprintf(stderr, "%s: this is a ViTSTR model: it has no image embedding\n", __func__); return 1; }
-    const int S = state_img_size(model, state), C = model.hparams.num_classes;
-    for (int i = 0; i < n; ++i)
-        if (imgs[i].nx != S || imgs[i].ny != S || imgs[i].data.size() != (size_t)3 * S * S) {
-            fprintf(stderr, "%s: image %d is %dx%d, this state expects %dx%d\n", __func__, i, imgs[i].nx, imgs[i].ny, S, S);
-            return 1;
-        }
+    const int C = model.hparams.num_classes;
+    int Sh = 0, Sw = 0;
+    if (!state_shape(model, state, Sh, Sw, __func__)) return 1;
+    const size_t img_floats = (size_t)3 * Sh * Sw;
+    if (const int i = first_bad_image(imgs, n, Sh, Sw); i >= 0) {
+        fprintf(stderr, "%s: image %d is %dx%d, this state expects %dx%d\n", __func__, i, imgs[i].nx, imgs[i].ny, Sw, Sh);
+        return 1;
+    }
     if (ensure_ctx(model, state, n) != VITX_OK) { fprintf(stderr, "%s: failed to create the context: %s\n", __func__, vitx_last_error()); return 1; }
     if (vitx_feat_enable(state.ctx, flags, 0) != VITX_OK) { fprintf(stderr, "%s: %s\n", __func__, vitx_last_error()); return 1; }
-    std::vector<float> batch((size_t)n * 3 * S * S);
-    for (int i = 0; i < n; ++i) std::copy(imgs[i].data.begin(), imgs[i].data.end(), batch.begin() + (size_t)i * 3 * S * S);
+    std::vector<float> batch((size_t)n * img_floats);
+    for (int i = 0; i < n; ++i) std::copy(imgs[i].data.begin(), imgs[i].data.end(), batch.begin() + (size_t)i * img_floats);
     state.prediction.resize((size_t)n * C);
     const size_t fpi = (size_t)vitx_feat_floats(state.ctx);
     std::vector<float> all((size_t)n * fpi);
@@ -167,16 +205,18 @@ int vit_zeroshot_batch(const vit_model &model, vit_state &state, const image_f32
     out.clear();
     if (!model.handle || !imgs || n <= 0 || bank.K <= 0 || bank.E <= 0 || bank.embeds.size() != (size_t)bank.K * bank.E) { fprintf(stderr, "%s: invalid argument\n", __func__); return 1; }
     if (vitx_model_seq_len(model.handle) > 0) { fprintf(stderr, "%s: this is a ViTSTR model: it has no image embedding\n", __func__); return 1; }
-    const int S = state_img_size(model, state), C = model.hparams.num_classes, K = bank.K;
-    for (int i = 0; i < n; ++i)
-        if (imgs[i].nx != S || imgs[i].ny != S || imgs[i].data.size() != (size_t)3 * S * S) {
-            fprintf(stderr, "%s: image %d is %dx%d, this state expects %dx%d\n", __func__, i, imgs[i].nx, imgs[i].ny, S, S);
-            return 1;
-        }
+    const int C = model.hparams.num_classes, K = bank.K;
+    int Sh = 0, Sw = 0;
+    if (!state_shape(model, state, Sh, Sw, __func__)) return 1;
+    const size_t img_floats = (size_t)3 * Sh * Sw;
+    if (const int i = first_bad_image(imgs, n, Sh, Sw); i >= 0) {
+        fprintf(stderr, "%s: image %d is %dx%d, this state expects %dx%d\n", __func__, i, imgs[i].nx, imgs[i].ny, Sw, Sh);
+        return 1;
+    }
     if (ensure_ctx(model, state, n) != VITX_OK) { fprintf(stderr, "%s: failed to create the context: %s\n", __func__, vitx_last_error()); return 1; }
     if (vitx_zeroshot_set(state.ctx, bank.embeds.data(), K, bank.E, bank.kind, bank.scale, bank.bias) != VITX_OK) { fprintf(stderr, "%s: %s\n", __func__, vitx_last_error()); return 1; }
-    std::vector<float> batch((size_t)n * 3 * S * S);
-    for (int i = 0; i < n; ++i) std::copy(imgs[i].data.begin(), imgs[i].data.end(), batch.begin() + (size_t)i * 3 * S * S);
+    std::vector<float> batch((size_t)n * img_floats);
+    for (int i = 0; i < n; ++i) std::copy(imgs[i].data.begin(), imgs[i].data.end(), batch.begin() + (size_t)i * img_floats);
     state.prediction.resize((size_t)n * C);
     std::vector<float> probs((size_t)n * K);
     const bool ok = vitx_forward(state.ctx, batch.data(), n, state.prediction.data(), nullptr) == VITX_OK && vitx_zeroshot_read(state.ctx, probs.data(), nullptr, probs.size()) == VITX_OK;

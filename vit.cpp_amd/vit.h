@@ -63,6 +63,9 @@ struct vit_state {                        // vit.h:72-80: per-caller mutable scr
                                           // runs on the file's position table resampled to that grid (vitx_ctx_options::img_size).  vit_predict, vit_predict_batch
                                           // and vit_embed_batch check their images against this size; preprocess to it by passing vit_image_preprocess a copy of
                                           // the hparams with img_size set.  Changing it (or pos_interp) replaces the context on the next call.  Not for ViTSTR.
+    int img_h = 0, img_w = 0;             // both 0, or both set with img_size == 0: THIS state takes img_h x img_w images (positive multiples of the patch size) in a
+                                          // rectangular context (vitx_ctx_create_rect; include/vitx.h "rectangular contexts"): res.nx == img_w, res.ny == img_h, as
+                                          // vit_image_preprocess_rect emits.  Changing them replaces the context on the next call, as img_size does.  Not for ViTSTR.
     int pos_interp = VITX_POS_BICUBIC;    // enum vitx_pos_interp: which bicubic convention resamples the table (include/vitx.h)
     int ctx_pos_interp = 0;               // the pos_interp `ctx` was created with
     std::vector<float> prediction;        // class probabilities of the last call ([n][num_classes])
@@ -93,6 +96,9 @@ bool vit_image_preprocess(const image_u8 &img, image_f32 &res, const vit_hparams
 // without a description gets vit_image_preprocess with bicubic interpolation: the reference's own files are preprocessed as always.
 // img_size 0 = the file's; else the side of the images a state with that vit_state::img_size takes (vitx_preproc_at_size).
 bool vit_image_preprocess_model(const image_u8 &img, image_f32 &res, const vit_model &model, int img_size = 0);
+// NEW: the whole image stretched to w x h for a state with img_w = w, img_h = h (vitx_preprocess_rect): the file's PIL filter, mean and std, no crop; a file
+// without a description, or with the reference's filter, takes Pillow bicubic with its default mean / std.
+bool vit_image_preprocess_rect(const image_u8 &img, image_f32 &res, const vit_model &model, int w, int h);
 int vit_predict(const vit_model &model, vit_state &state, const image_f32 img1, const vit_params &params,
                 std::vector<std::pair<float, int>> &predictions);                                      // vit.h:122
 int vit_predict_batch(const vit_model &model, vit_state &state, const image_f32 *imgs, int n, const vit_params &params,
