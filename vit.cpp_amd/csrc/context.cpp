@@ -1,146 +1,19 @@
-// context.cpp -- creation of the execution context of the MI355X ViT engine: weight upload, scratch, streams.
+// context.cpp -- creation of the execution context of the MI355X ViT engine: its configuration, the tables of its grid, scratch, streams.
 // Replaces vit_state + the set-up half of vit_predict of the reference (vit.cpp:718-941, 1004-1040).  Differences by design: the batch is
-// n images (the reference hard-wires 1, vit.cpp:747), weights live in HBM in the MFMA operand type, all activation scratch is allocated
-// once per context (the reference builds the graph twice and reallocates per call, vit.cpp:1009-1035), and the ~90 launches of a
+// n images (the reference hard-wires 1, vit.cpp:747), weights live in HBM in the MFMA operand type (weights.cpp), all activation scratch is
+// allocated once per context (the reference builds the graph twice and reallocates per call, vit.cpp:1009-1035), and the ~90 launches of a
 // forward are enqueued on one HIP stream without host synchronisation (forward.cpp).
 #include <stdlib.h>
 #include <string.h>
 
-#include <map>
-#include <mutex>
 #include <new>
-#include <string>
-#include <tuple>
 
 #include "context.h"
 
-std::vector<uint16_t> vitx::operand_matrix_host(int dtype, const float *f, const uint16_t *bits, int Nrows, int K, int n_pad, int k_pad, int patch_P, int patch_Cin) {
-    std::vector<uint16_t> h((size_t)n_pad * k_pad, 0);
-    for (int n = 0; n < Nrows; ++n) {
-        if (bits) { memcpy(&h[(size_t)n * k_pad], bits + (size_t)n * K, (size_t)K * 2); continue; }
-        for (int k = 0; k < K; ++k) h[(size_t)n * k_pad + k] = dtype == VITX_F16 ? f32_to_f16_bits(f[(size_t)n * K + k]) : f32_to_bf16_bits(f[(size_t)n * K + k]);
-    }
-    if (patch_P > 0) { std::vector<uint16_t> hp(h.size(), 0); patch_embed_permute_k(h.data(), hp.data(), Nrows, patch_Cin, patch_P, k_pad); h.swap(hp); }
-    return h;
-}
-
 namespace {
 
-// f32 vector -> device f32 (padded with zeros to n_pad)
-int upload_f32(vitx_ctx *c, const HostTensor *t, float **out, size_t n_pad = 0) {
-    std::vector<float> h((size_t)t->nelements());
-    t->decode_f32(h.data());
-    if (n_pad > h.size()) h.resize(n_pad, 0.0f);
-    int rc = c->wmalloc((void **)out, h.size() * 4);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(*out, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-    return VITX_OK;
-}
-
-// [N][K] matrix -> operand type, rows padded to n_pad, cols to k_pad (zeros).  f16 file data is
-// forwarded bit-exact in F16 mode; everything else is decoded to f32 and rounded once (RNE).
-// patch_P > 0: the patch-embedding kernel [D][Cin * P * P]: its K axis is permuted to the image's memory order (patch_embed.hip)
-int upload_matrix(vitx_ctx *c, const HostTensor *t, int Nrows, int K, int n_pad, int k_pad, void **out, int patch_P = 0, int patch_Cin = 0) {
-    const bool exact = t->type == T_F16 && c->dtype == VITX_F16;
-    std::vector<float> f(exact ? 0 : (size_t)Nrows * K);
-    if (!exact) t->decode_f32(f.data());
-    const std::vector<uint16_t> h = operand_matrix_host(c->dtype, f.data(), exact ? (const uint16_t *)t->raw.data() : nullptr, Nrows, K, n_pad, k_pad, patch_P, patch_Cin);
-    int rc = c->wmalloc(out, h.size() * 2);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(*out, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-    c->wset->weight_bytes += h.size() * 2;
-    return VITX_OK;
-}
-int upload_quant(vitx_ctx *c, const HostTensor *t, int Nrows, int K, int n_pad, QuantW *q);
-// A 2-D "*weight" tensor: block types stay quantised on the device (q), everything else is uploaded expanded (dense).
-int upload_weight(vitx_ctx *c, const HostTensor *t, int Nrows, int K, int n_pad, void **dense, QuantW *q) {
-    *dense = nullptr;
-    if (c->quant_on_device) { int rc = upload_quant(c, t, Nrows, K, n_pad, q); if (rc) return rc; }
-    if (q->blocks) return VITX_OK;
-    return upload_matrix(c, t, Nrows, K, n_pad, K, dense);
-}
-
-// [N][K] matrix -> MX operand (VITX_MXFP8): the f32 decode of any file type, encoded once on the host; rows N..n_pad are zero blocks
-int upload_mx(vitx_ctx *c, const HostTensor *t, int Nrows, int K, int n_pad, MxW *w) {
-    w->N = Nrows; w->K = K; w->n_pad = n_pad; w->k_pad = mx_k_pad(K);
-    std::vector<float> f((size_t)n_pad * K, 0.0f);
-    t->decode_f32(f.data());
-    std::vector<uint8_t> q((size_t)n_pad * w->k_pad), sc((size_t)n_pad * (w->k_pad / kMxBlock));
-    mxfp8_encode_rows(f.data(), n_pad, K, w->k_pad, q.data(), sc.data());
-    int rc;
-    if ((rc = c->wmalloc((void **)&w->q, q.size()))) return rc;
-    if ((rc = c->wmalloc((void **)&w->s, sc.size()))) return rc;
-    HIP_TRY(hipMemcpy(w->q, q.data(), q.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(w->s, sc.data(), sc.size(), hipMemcpyHostToDevice));
-    c->wset->weight_bytes += q.size() + sc.size();
-    return VITX_OK;
-}
-
-// Quantised [N][K] matrix -> device, still in block form.  Returns VITX_OK with q->blocks == nullptr when the tensor is not a
-// block type (the caller then uploads the expanded matrix).
-int upload_quant(vitx_ctx *c, const HostTensor *t, int Nrows, int K, int n_pad, QuantW *q) {
-    const int bb = type_block_bytes(t->type);
-    if (t->type == T_F32 || t->type == T_F16 || !bb || K % 32) return VITX_OK;
-    const size_t nbk = (size_t)K / 32;
-    q->type = t->type; q->N = Nrows; q->K = K; q->n_pad = n_pad;
-    int rc;
-    if (t->type == T_Q4_0) {        // split planes, rows padded (zero scales -> the pad rows expand to zeros)
-        std::vector<uint8_t> qs((size_t)n_pad * nbk * 16, 0);
-        std::vector<uint16_t> ds((size_t)n_pad * nbk, 0);
-        const uint8_t *src = t->raw.data();
-        for (size_t b = 0; b < (size_t)Nrows * nbk; ++b) { memcpy(&ds[b], src + b * 18, 2); memcpy(&qs[b * 16], src + b * 18 + 2, 16); }
-        if ((rc = c->wmalloc(&q->blocks, qs.size()))) return rc;
-        if ((rc = c->wmalloc((void **)&q->scales, ds.size() * 2))) return rc;
-        HIP_TRY(hipMemcpy(q->blocks, qs.data(), qs.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(q->scales, ds.data(), ds.size() * 2, hipMemcpyHostToDevice));
-        c->wset->weight_bytes += qs.size() + ds.size() * 2;
-    } else {
-        const size_t bytes = (size_t)Nrows * nbk * bb;
-        if ((rc = c->wmalloc(&q->blocks, bytes))) return rc;
-        HIP_TRY(hipMemcpy(q->blocks, t->raw.data(), bytes, hipMemcpyHostToDevice));
-        c->wset->weight_bytes += bytes;
-    }
-    return VITX_OK;
-}
-
-// The attention-pooling head (VITX_POOL_MAP; include/vitx.h): the folded probe u, the V half of kv.*, proj, norm, fc1, fc2.  The matrices are f32
-// or f16 in the file, never blocks.
-int upload_map_head(vitx_ctx *c) {
-    const vitx_model *m = c->model;
-    vitx_ctx::WeightSet &ws = *c->wset;
-    const int D = c->D, tn = c->tn;
-    int rc;
-    std::vector<float> u((size_t)c->H * D);
-    if ((rc = vitx_model_pool_query(m, u.data()))) return rc;
-    if ((rc = c->wmalloc((void **)&ws.map_u, u.size() * 4))) return rc;
-    HIP_TRY(hipMemcpy(ws.map_u, u.data(), u.size() * 4, hipMemcpyHostToDevice));
-    // V: rows D .. 2 D of kv.weight, elements D .. 2 D of kv.bias; 128 zero rows behind them: the value projection of the last head reads a whole column tile
-    const HostTensor *kvw = m->find("attn_pool.kv.weight"), *kvb = m->find("attn_pool.kv.bias");
-    std::vector<float> f((size_t)2 * D * D), fb((size_t)2 * D);
-    kvw->decode_f32(f.data()); kvb->decode_f32(fb.data());
-    const int v_pad = round_up(D, tn) + 128;
-    const std::vector<uint16_t> hv = operand_matrix_host(c->dtype, f.data() + (size_t)D * D, nullptr, D, D, v_pad, D, 0, 0);
-    if ((rc = c->wmalloc(&ws.map_v_w, hv.size() * 2))) return rc;
-    HIP_TRY(hipMemcpy(ws.map_v_w, hv.data(), hv.size() * 2, hipMemcpyHostToDevice));
-    ws.weight_bytes += hv.size() * 2;
-    std::vector<float> vb((size_t)v_pad, 0.0f);
-    std::copy(fb.begin() + D, fb.end(), vb.begin());
-    if ((rc = c->wmalloc((void **)&ws.map_v_b, vb.size() * 4))) return rc;
-    HIP_TRY(hipMemcpy(ws.map_v_b, vb.data(), vb.size() * 4, hipMemcpyHostToDevice));
-    auto T = [&](const char *n) { return m->find(n); };
-    if ((rc = upload_f32(c, T("attn_pool.proj.bias"), &ws.map_proj_b, round_up(D, tn)))) return rc;
-    if ((rc = upload_f32(c, T("attn_pool.norm.weight"), &ws.map_ln_w))) return rc;
-    if ((rc = upload_f32(c, T("attn_pool.norm.bias"), &ws.map_ln_b))) return rc;
-    if ((rc = upload_f32(c, T("attn_pool.mlp.fc1.bias"), &ws.map_fc1_b, round_up(4 * D, tn)))) return rc;
-    if ((rc = upload_f32(c, T("attn_pool.mlp.fc2.bias"), &ws.map_fc2_b, round_up(D, tn)))) return rc;
-    if ((rc = upload_matrix(c, T("attn_pool.proj.weight"), D, D, round_up(D, tn), D, &ws.map_proj_w))) return rc;
-    if ((rc = upload_matrix(c, T("attn_pool.mlp.fc1.weight"), 4 * D, D, round_up(4 * D, tn), D, &ws.map_fc1_w))) return rc;
-    if ((rc = upload_matrix(c, T("attn_pool.mlp.fc2.weight"), D, 4 * D, round_up(D, tn), 4 * D, &ws.map_fc2_w))) return rc;
-    return VITX_OK;
-}
-
 // vitx_ctx_create_ex / vitx_ctx_create_rect, step 1: the options (all zero = every default) and the geometry they ask for are validated, then the
-// context is made and its fields are derived from them.  Every check keeps its place: the first one that fails is the one reported.
+// context is made and its fields are derived from them.  The first check that fails is the one reported; the device is opened behind those of the options.
 // rect: the caller is vitx_ctx_create_rect and the geometry is rect_h x rect_w; otherwise it is the square of options.img_size (0: the file's).
 int configure(const vitx_model *m, int device, int max_batch, int dtype, const vitx_ctx_options *opt_in, bool rect, int rect_h, int rect_w, vitx_ctx_options &opt, std::unique_ptr<vitx_ctx> &c) {
     if (opt_in) {
@@ -175,18 +48,16 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
     if (m->in_chans == 1 && (m->has_pre_norm || m->activation != VITX_ACT_GELU_TANH)) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes neither a pre-norm nor an activation other than tanh-GELU"); return VITX_ERR_UNSUPPORTED; }
     if (dtype == VITX_MXFP8 && m->activation != VITX_ACT_GELU_TANH) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts evaluate tanh-GELU only (this model's activation: %d)", m->activation); return VITX_ERR_UNSUPPORTED; }
     if (m->in_chans == 1 && !own_shape) { set_error("vitx_ctx_create_ex: a ViTSTR context stays at the file's img_size (%d)", m->hp.img_size); return VITX_ERR_UNSUPPORTED; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("vitx_ctx_create: no HIP device available (this engine has no CPU fallback)"); return VITX_ERR_HIP; }
-    if (device < 0 || device >= ndev) { set_error("vitx_ctx_create: device %d out of range (%d devices)", device, ndev); return VITX_ERR_ARG; }
+    const Tuning *tune = nullptr;
+    if (int rc = open_device("vitx_ctx_create", device, &tune)) return rc;
     const vitx_hparams &hp = m->hp;
     if (hp.num_attention_heads <= 0 || hp.hidden_size % hp.num_attention_heads) { set_error("vitx_ctx_create: hidden_size %d is not a multiple of %d heads", hp.hidden_size, hp.num_attention_heads); return VITX_ERR_UNSUPPORTED; }
     if (hp.hidden_size % 64) { set_error("vitx_ctx_create: hidden_size must be a multiple of 64"); return VITX_ERR_UNSUPPORTED; }
     // (VITX_MXFP8 needs whole 32-element blocks per row: the multiple of 64 above already guarantees it, so no check of its own)
     static_assert(64 % kMxBlock == 0, "the hidden-size rule above must cover the MX block");
-    HIP_TRY(hipSetDevice(device));
     c.reset(new (std::nothrow) vitx_ctx());
     if (!c) return VITX_ERR_NOMEM;
-    c->model = m; c->hp = hp; c->device = device; c->max_batch = max_batch;
+    c->model = m; c->hp = hp; c->device = device; c->max_batch = max_batch; c->tune = tune;
     c->mx = dtype == VITX_MXFP8; c->dtype = c->mx ? VITX_BF16 : dtype;      // everything but the MX GEMMs runs as in a VITX_BF16 context
     c->D = hp.hidden_size; c->L = hp.num_hidden_layers; c->H = hp.num_attention_heads; c->C = hp.num_classes; c->P = hp.patch_size;
     c->Sh = img_h; c->Sw = img_w; c->S = img_h == img_w ? img_h : 0;
@@ -198,18 +69,16 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
     if (c->map && c->H > kPoolMaxHeads) { set_error("vitx_ctx_create: the attention-pooling kernel takes at most %d heads (this model: %d)", kPoolMaxHeads, c->H); return VITX_ERR_UNSUPPORTED; }
     c->gh = c->Sh / c->P; c->gw = c->Sw / c->P;
     if ((long)c->gh * c->gw + c->Tp > 0x7fffffffl / 4) { set_error("vitx_ctx_create: %d x %d patches are more tokens than a context takes", c->gh, c->gw); return VITX_ERR_UNSUPPORTED; }
-    c->N = c->gh * c->gw + c->Tp; c->Kpe = c->Cin * c->P * c->P; c->Kpe_pad = round_up(c->Kpe, 64);
+    c->N = c->gh * c->gw + c->Tp; c->Kpe = patch_k(m); c->Kpe_pad = patch_k_pad(m);
     if (c->N < c->R) { set_error("vitx_ctx_create: a ViTSTR head reads %d tokens, this model has %d (image %d x %d, patch_size %d)", c->R, c->N, c->Sh, c->Sw, c->P); return VITX_ERR_UNSUPPORTED; }
     c->tm = gemm_tile_m(); c->tn = gemm_tile_n();
-    c->C_pad = round_up(c->C, c->tn);
+    c->C_pad = head_cols_pad(m);
     // validate against what the kernels are actually instantiated for (a context that would fail on its first forward is refused here)
     if (!attention_supports(c->N, c->D, c->H)) {
         set_error("vitx_ctx_create: attention needs a head_dim that is a multiple of 8 up to 128 (this model: %d) and at least one token (%d tokens, image %d x %d, patch_size %d)", c->D / c->H, c->N, c->Sh, c->Sw, c->P);
         return VITX_ERR_UNSUPPORTED;
     }
     if (!layernorm_supports(c->D)) { set_error("vitx_ctx_create: hidden_size %d has no LayerNorm instantiation (64, 128, 192, 256, 320, 384, 448, 512, 576, 640, 768, 896, 1024, 1152, 1280, 1408, 1536, 1664, 2048)", c->D); return VITX_ERR_UNSUPPORTED; }
-    c->tune = tuning_for_device(device);
-    if (!c->tune) { set_error("vitx_ctx_create: kernel bring-up on device %d failed: %s", device, hipGetErrorString(hipGetLastError())); return VITX_ERR_HIP; }
     c->split_first = opt.split_first;
     c->prec_attn = dtype == VITX_F16 && c->D == c->H * 64 && !opt.f16_fast_attention;
     c->quant_on_device = !opt.quant_on_host;
@@ -233,94 +102,7 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
     return VITX_OK;
 }
 
-// The transformer blocks blocks.{i}.* of a model file into the context's weight set: the same twelve tensors per layer in an image file and a text file
-int upload_blocks(vitx_ctx *c) {
-    const vitx_model *m = c->model;
-    const int D = c->D, tn = c->tn;
-    const int F = m->mlp_hidden(), F1 = m->mlp_fc1_rows();      // (from the model: a text context's shell sets neither c->F nor c->F1)
-    int rc;
-    auto T = [&](const std::string &n) { return m->find(n); };
-    vitx_ctx::WeightSet &ws = *c->wset;
-    ws.layers.resize(c->L);
-    for (int i = 0; i < c->L; ++i) {
-        const std::string p = "blocks." + std::to_string(i) + ".";
-        LayerW &w = ws.layers[i];
-        if ((rc = upload_f32(c, T(p + "norm1.weight"), &w.ln1_w))) return rc;
-        if ((rc = upload_f32(c, T(p + "norm1.bias"), &w.ln1_b))) return rc;
-        if ((rc = upload_f32(c, T(p + "norm2.weight"), &w.ln2_w))) return rc;
-        if ((rc = upload_f32(c, T(p + "norm2.bias"), &w.ln2_b))) return rc;
-        if ((rc = upload_f32(c, T(p + "attn.qkv.bias"), &w.qkv_b, round_up(3 * D, tn)))) return rc;
-        if ((rc = upload_f32(c, T(p + "attn.proj.bias"), &w.proj_b, round_up(D, tn)))) return rc;
-        if ((rc = upload_f32(c, T(p + "mlp.fc1.bias"), &w.fc1_b, round_up(F1, tn)))) return rc;
-        if ((rc = upload_f32(c, T(p + "mlp.fc2.bias"), &w.fc2_b, round_up(D, tn)))) return rc;
-        w.qkv_w = w.fc1_w = w.fc2_w = nullptr;
-        if (c->mx) {
-            if ((rc = upload_mx(c, T(p + "attn.qkv.weight"), 3 * D, D, round_up(3 * D, 128), &w.mx[W_QKV]))) return rc;
-            if ((rc = upload_mx(c, T(p + "mlp.fc1.weight"), F1, D, round_up(F1, 128), &w.mx[W_FC1]))) return rc;
-            if ((rc = upload_mx(c, T(p + "mlp.fc2.weight"), D, F, round_up(D, 128), &w.mx[W_FC2]))) return rc;
-        } else {
-            if ((rc = upload_weight(c, T(p + "attn.qkv.weight"), 3 * D, D, round_up(3 * D, tn), &w.qkv_w, &w.q[W_QKV]))) return rc;
-            if ((rc = upload_weight(c, T(p + "mlp.fc1.weight"), F1, D, round_up(F1, tn), &w.fc1_w, &w.q[W_FC1]))) return rc;
-            if ((rc = upload_weight(c, T(p + "mlp.fc2.weight"), D, F, round_up(D, tn), &w.fc2_w, &w.q[W_FC2]))) return rc;
-        }
-        if ((rc = upload_weight(c, T(p + "attn.proj.weight"), D, D, round_up(D, tn), &w.proj_w, &w.q[W_PROJ]))) return rc;
-    }
-    return VITX_OK;
-}
-
-// Step 2: the device copies of the weights, found in the registry or uploaded.  `dtype`: the type the caller asked for (the key tells MXFP8 from BF16)
-int obtain_weights(vitx_ctx *c, int dtype) {
-    const vitx_model *m = c->model;
-    const int device = c->device, D = c->D, tn = c->tn;
-    int rc;
-    auto T = [&](const std::string &n) { return m->find(n); };
-    // device copies of the weights: one set per (loaded model, device, operand type, block mode), shared by every context that asks for it
-    static std::mutex wreg_mu;
-    static std::map<std::tuple<uint64_t, int, int, int>, std::weak_ptr<vitx_ctx::WeightSet>> wreg;
-    const auto wkey = std::make_tuple(m->uid, device, dtype, c->quant_on_device ? 1 : 0);
-    std::unique_lock<std::mutex> wlock(wreg_mu);           // held through the upload: a second context of the same model waits for the first
-    for (auto it = wreg.begin(); it != wreg.end();) it = it->second.expired() ? wreg.erase(it) : std::next(it);      // sets whose last context is gone
-    if (auto have = wreg[wkey].lock()) {
-        c->wset = have; c->weights_shared = true;
-    } else if (m->kind == VITX_KIND_TEXT) {
-        // a text tower (text_forward.cpp): the token table as filed (a gather reads it), the position table, the same blocks, final norm, projection
-        c->wset = std::make_shared<vitx_ctx::WeightSet>();
-        vitx_ctx::WeightSet &ws = *c->wset;
-        ws.device = device;
-        const HostTensor *tok = T("token_embed.weight");
-        ws.tok_f16 = tok->type == T_F16;
-        if ((rc = c->wmalloc(&ws.tok, tok->raw.size()))) return rc;
-        HIP_TRY(hipMemcpy(ws.tok, tok->raw.data(), tok->raw.size(), hipMemcpyHostToDevice));
-        ws.weight_bytes += tok->raw.size();
-        if ((rc = upload_f32(c, T("pos_embed"), &ws.pos))) return rc;
-        if ((rc = upload_blocks(c))) return rc;
-        if ((rc = upload_f32(c, T("norm.weight"), &ws.norm_w))) return rc;
-        if ((rc = upload_f32(c, T("norm.bias"), &ws.norm_b))) return rc;
-        if ((rc = upload_f32(c, T("head.bias"), &ws.head_b, c->C_pad))) return rc;
-        if ((rc = upload_weight(c, T("head.weight"), c->C, D, c->C_pad, &ws.head_w, &ws.head_q))) return rc;
-        wreg[wkey] = c->wset;
-    } else {
-        c->wset = std::make_shared<vitx_ctx::WeightSet>();
-        vitx_ctx::WeightSet &ws = *c->wset;
-        ws.device = device;
-        if (!c->map && (rc = upload_f32(c, T("cls_token"), &ws.cls))) return rc;
-        if (c->nreg && (rc = upload_f32(c, T("reg_token"), &ws.reg))) return rc;
-        if ((rc = upload_f32(c, T("pos_embed"), &ws.pos))) return rc;
-        if (m->has_pre_norm && ((rc = upload_f32(c, T("pre_norm.weight"), &ws.pre_w)) || (rc = upload_f32(c, T("pre_norm.bias"), &ws.pre_b)))) return rc;
-        if ((rc = upload_f32(c, T("patch_embed.proj.bias"), &ws.pe_b, round_up(D, tn)))) return rc;
-        if ((rc = upload_matrix(c, T("patch_embed.proj.weight"), D, c->Kpe, round_up(D, tn), c->Kpe_pad, &ws.pe_w, c->P, c->Cin))) return rc;
-        if ((rc = upload_blocks(c))) return rc;
-        if ((rc = upload_f32(c, T("norm.weight"), &ws.norm_w))) return rc;
-        if ((rc = upload_f32(c, T("norm.bias"), &ws.norm_b))) return rc;
-        if (c->map && (rc = upload_map_head(c))) return rc;
-        if ((rc = upload_f32(c, T("head.bias"), &ws.head_b, c->C_pad))) return rc;
-        if ((rc = upload_weight(c, T("head.weight"), c->C, c->pool ? 2 * D : D, c->C_pad, &ws.head_w, &ws.head_q))) return rc;
-        wreg[wkey] = c->wset;
-    }
-    return VITX_OK;               // (the lock is released here: held through the upload)
-}
-
-// Step 3: the scratch of one sub-batch slice; `internal`: a slice that runs on a stream of its own (every slice but the first of several)
+// Step 2: the scratch of one sub-batch slice; `internal`: a slice that runs on a stream of its own (every slice but the first of several)
 int alloc_slice(vitx_ctx *c, vitx_ctx::Slice &sl, size_t hcols, bool internal) {
     const int D = c->D;
     int rc;
@@ -375,10 +157,6 @@ int alloc_slice(vitx_ctx *c, vitx_ctx::Slice &sl, size_t hcols, bool internal) {
 
 }  // namespace
 
-// The weight set of a text context (text_forward.cpp): `shell` is a vitx_ctx that carries only what the upload reads (model, device, dtype, D, L, C,
-// C_pad, tn, quant_on_device = false) and receives wset -- the registry, the sharing rule and every upload function are the image contexts'.
-int vitx::obtain_text_weights(vitx_ctx *shell) { return obtain_weights(shell, shell->dtype); }
-
 extern "C" {
 
 int vitx_ctx_create(const vitx_model *m, int device, int max_batch, int dtype, vitx_ctx **out) { return vitx_ctx_create_ex(m, device, max_batch, dtype, nullptr, out); }
@@ -393,7 +171,7 @@ static int ctx_create(const vitx_model *m, int device, int max_batch, int dtype,
     std::unique_ptr<vitx_ctx> c;
     int rc;
     if ((rc = configure(m, device, max_batch, dtype, opt_in, rect, img_h, img_w, opt, c))) return rc;
-    if ((rc = obtain_weights(c.get(), dtype))) return rc;
+    if ((rc = obtain_weights({m, device, dtype, c->quant_on_device}, &c->wset, &c->weights_shared))) return rc;
     const vitx_hparams &hp = m->hp;
     const int D = c->D;
     // the position table of THIS context: the set's (the file's) at the file's size, else resampled on the device into scratch the context owns
@@ -415,9 +193,7 @@ static int ctx_create(const vitx_model *m, int device, int max_batch, int dtype,
     }
 
     // sub-batch slices (vitx_ctx_options::streams; 1 = single stream).  Small contexts stay single-slice.
-    int ns = opt.streams > 0 ? opt.streams : 2;
-    if (ns < 1) ns = 1;
-    if (ns > 4) ns = 4;
+    int ns = opt.streams > 0 ? opt.streams : 2;      // (configure: 0 .. 4)
     if (max_batch < 8 * ns) ns = 1;
     c->nslices = ns;
     c->slices.resize(ns);

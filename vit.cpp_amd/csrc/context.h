@@ -1,5 +1,5 @@
-// context.h -- the execution context (struct vitx_ctx) as context.cpp, forward.cpp, outputs.cpp and ops.cpp share it, and the text context
-// (struct vitx_text) of text_forward.cpp.  Internal: nothing outside those five files includes it; callers see the opaque vitx_ctx and vitx_text
+// context.h -- the execution context (struct vitx_ctx) as context.cpp, forward.cpp, outputs.cpp and ops.cpp share it: what a forward uses.
+// The weights it reads are a WeightSet (weights.h).  Internal: nothing outside those four files includes it; callers see the opaque vitx_ctx
 // of include/vitx.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -9,15 +9,7 @@
 #include <memory>
 #include <vector>
 
-#include "kernels.h"
-#include "model_file.h"
-#include "mxfp8.h"
-
-#define HIP_TRY(expr)                                                                                      \
-    do {                                                                                                   \
-        hipError_t e__ = (expr);                                                                           \
-        if (e__ != hipSuccess) { set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); return VITX_ERR_HIP; } \
-    } while (0)
+#include "weights.h"
 
 namespace vitx {
 
@@ -30,33 +22,9 @@ inline const char *const kProfNames[PC_COUNT] = {"patch_embed", "layernorm", "ge
                                     "features", "head_pool", "zeroshot", "rope", "swiglu"};
 static_assert(PC_COUNT <= VITX_PROF_MAX_CLASSES, "vitx_profile_read callers size their arrays by VITX_PROF_MAX_CLASSES");
 
-// A weight matrix kept in the file's block form on the device (quant.hip): `blocks` = N rows of K/32 blocks in the file's byte
-// layout -- except q4_0, which is split into a nibble plane (`blocks`, 16 B per block, rows padded to n_pad) and an f16 scale
-// plane (`scales`) so both the dequant kernel and the fused small-batch GEMM read aligned 16-byte pieces.  Same bits, same size.
-struct QuantW {
-    void *blocks = nullptr; uint16_t *scales = nullptr;
-    int type = 0, N = 0, K = 0, n_pad = 0;
-};
-enum { W_QKV = 0, W_PROJ, W_FC1, W_FC2, W_PER_LAYER };
-// A weight matrix of a VITX_MXFP8 context (mxfp8.h): elements [n_pad][k_pad] e4m3 and scales [n_pad][k_pad / 32], encoded on the host at upload
-struct MxW {
-    uint8_t *q = nullptr, *s = nullptr;
-    int N = 0, K = 0, n_pad = 0, k_pad = 0;
-};
-struct LayerW {
-    float *ln1_w, *ln1_b, *ln2_w, *ln2_b, *qkv_b, *proj_b, *fc1_b, *fc2_b;
-    void *qkv_w, *proj_w, *fc1_w, *fc2_w;      // expanded operand-type matrices; nullptr where the blocks stay quantised (q[]) or are MX (mx[])
-    QuantW q[W_PER_LAYER];
-    MxW mx[W_PER_LAYER];                       // VITX_MXFP8: qkv, fc1 and fc2 (proj stays bf16)
-};
-
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 static_assert(VITX_F16 == DT_F16 && VITX_BF16 == DT_BF16, "the API's dtype values are handed to the launchers as they are");
 // selected layers of an output's layer mask (attention maps, features) below layer il: the slot of il's block in the per-image layout; il = L: their number
 inline int layer_slot(uint64_t mask, int il) { return __builtin_popcountll(il < 64 ? mask & ((1ull << il) - 1) : mask); }
-// [Nrows][K] -> operand type, rows padded to n_pad, cols to k_pad (zeros): f32 `f` rounded once (RNE), or -- `bits` != nullptr -- operand-type rows
-// forwarded bit-exact.  patch_P > 0: a patch-embedding kernel [D][Cin * P * P], its K axis permuted to the image's memory order (patch_embed.hip)
-std::vector<uint16_t> operand_matrix_host(int dtype, const float *f, const uint16_t *bits, int Nrows, int K, int n_pad, int k_pad, int patch_P, int patch_Cin);
 
 // Temporary device scratch of one call: owns the pointer it is given and frees it on every way out.  Move-only.
 struct DevMem {
@@ -99,29 +67,7 @@ struct vitx_ctx {
 #endif
     hipStream_t stream = nullptr;
     std::vector<void *> allocs;          // scratch of THIS context
-    // weights: device copies are shared by every context of the same loaded model, device, operand type and quantisation mode
-    // (WeightSet below; e.g. the two contexts of INTEGRATION.md's "two forwards in flight"): uploaded by the first, freed with the last
-    struct WeightSet {
-        int device = 0;
-        std::vector<void *> allocs;
-        float *pre_w = nullptr, *pre_b = nullptr;      // pre_norm.* (nullptr without them): LayerNorm of the token rows in front of layer 0
-        float *cls = nullptr, *reg = nullptr, *pos = nullptr, *pe_b = nullptr, *norm_w = nullptr, *norm_b = nullptr, *head_b = nullptr;
-        void *pe_w = nullptr, *head_w = nullptr;
-        QuantW head_q;
-        void *tok = nullptr;             // a text tower's token table [V][D] as filed: f16 (tok_f16) or f32
-        bool tok_f16 = false;
-        // VITX_POOL_MAP (attn_pool.*): u [H][D] f32 (the folded probe, vitx_model_pool_query); the V half of kv.weight / kv.bias, padded by 128 rows so that
-        // every head's [d][D] block can be read as a whole column tile; proj, norm, fc1, fc2 like a block's
-        float *map_u = nullptr, *map_v_b = nullptr, *map_proj_b = nullptr, *map_ln_w = nullptr, *map_ln_b = nullptr, *map_fc1_b = nullptr, *map_fc2_b = nullptr;
-        void *map_v_w = nullptr, *map_proj_w = nullptr, *map_fc1_w = nullptr, *map_fc2_w = nullptr;
-        std::vector<LayerW> layers;
-        size_t weight_bytes = 0;         // device bytes held by weight matrices (vitx_ctx_weight_bytes)
-        ~WeightSet() {       // may run on any thread (the last context of the set): leave the caller's current device as it was
-            int cur = -1; (void)hipGetDevice(&cur);
-            (void)hipSetDevice(device); for (void *p : allocs) (void)hipFree(p);
-            if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
-        }
-    };
+    // weights: the device copies, shared by every context of the same loaded model, device, requested dtype and block mode (weights.h)
     std::shared_ptr<WeightSet> wset;     // never null once the context exists
     const float *pos = nullptr;          // [1 + gh * gw][D] position table the patch embedding adds: wset->pos, or pos_own when the grid differs from the file's
     float *pos_own = nullptr;            // the table resampled to this context's grid (vitx_ctx_options::img_size, pos_interp); in `allocs`
@@ -299,42 +245,9 @@ struct vitx_ctx {
         if (zero) HIP_TRY(hipMemset(*p, 0, bytes ? bytes : 16));
         return VITX_OK;
     }
-    int wmalloc(void **p, size_t bytes) {      // weight storage: owned by the shared set
-        HIP_TRY(hipMalloc(p, bytes ? bytes : 16));
-        wset->allocs.push_back(*p);
-        return VITX_OK;
-    }
     hipEvent_t next_event() {
         if (ev_used == ev_pool.size()) { hipEvent_t e; (void)hipEventCreate(&e); ev_pool.push_back(e); }
         return ev_pool[ev_used++];
-    }
-};
-
-namespace vitx { int obtain_text_weights(vitx_ctx *shell); }      // context.cpp
-
-// The text context (text_forward.cpp; include/vitx.h "the text tower"): one stream, no sub-batches, no graph cache, no LayerNorm fusion.
-struct vitx_text {
-    vitx_ctx shell;                      // the weight holder (obtain_text_weights): model, device, dtype, D, L, H, C = E, wset; no scratch, no stream of its own
-    int V = 0, T = 0, E = 0, E_pad = 0, causal = 0, eos = -1, max_prompts = 0;
-    int fc1_epi = EPI_BIAS_GELU;
-    float eps = 1e-6f;
-    Tuning tune_qkv, tune_proj, tune_fc1, tune_fc2, tune_head;      // the device's tuning with ONE ring family pinned per GEMM, chosen at creation from max_prompts * T rows
-    hipStream_t stream = nullptr;        // of vitx_text_embed (the host entry point)
-    std::vector<void *> allocs;
-    int *pooled = nullptr, *ids = nullptr;      // [max_prompts] pooled positions, then [max_prompts][T] ids: one buffer, one upload of its front
-    std::vector<int> host;               // the same on the host: the staging buffer of the upload
-    std::vector<int32_t> pooled_host;    // the positions of the call being checked (stage_ids), before they may enter `host`
-    hipEvent_t uploaded = nullptr;       // recorded behind the upload of a call: the next call waits for it before it overwrites `host`
-    bool uploaded_pending = false;
-    float *X = nullptr;                  // [Mpad][D] f32 residual stream
-    void *U = nullptr, *QKV = nullptr, *Hbuf = nullptr, *Z = nullptr;      // [Mpad][D], [Mpad][3 D], [Mpad][4 D], [Bpad][D] operand type
-    float *out = nullptr;                // [Bpad][E] f32 embeddings of the host entry point
-    float *raw = nullptr;                // [Bpad][E] f32: the head's output in front of VITX_TEXT_L2
-    ~vitx_text() {
-        (void)hipSetDevice(shell.device);
-        for (void *p : allocs) (void)hipFree(p);
-        if (uploaded) (void)hipEventDestroy(uploaded);
-        if (stream) (void)hipStreamDestroy(stream);
     }
 };
 

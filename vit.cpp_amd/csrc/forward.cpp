@@ -92,7 +92,7 @@ static int attention_maps(vitx_ctx *c, hipStream_t st, const void *qkv, long lo_
 // functions are the steps, each one launch (or one group of launches) + its profile record.  run() enqueues them in order.
 struct SliceForward {
     vitx_ctx *c; vitx_ctx::Slice &sl; hipStream_t st; int first_img, n;
-    const vitx_ctx::WeightSet &ws = *c->wset;
+    const WeightSet &ws = *c->wset;
     const int D = c->D, N = c->N, tm = c->tm, tn = c->tn, dt = c->dtype;
     const int F = c->F, F1 = c->F1;                                 // MLP widths: fc2's K and fc1's N (4 D both, or F and 2 F of a `glu` context)
     static constexpr double eb = 2.0;                               // operand bytes

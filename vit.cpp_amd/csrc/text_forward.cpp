@@ -8,12 +8,13 @@
 
 #include <new>
 
-#include "context.h"
+#include "text_context.h"
+#include "weights.h"
 
 namespace {
 
 int text_gemm(const vitx_text *t, const Tuning &tune, int epi, const GemmArgs &a, hipStream_t st) {
-    HIP_TRY(launch_gemm(tune, t->shell.dtype, epi, a, st));
+    HIP_TRY(launch_gemm(tune, t->dtype, epi, a, st));
     return VITX_OK;
 }
 
@@ -22,17 +23,17 @@ int text_gemm(const vitx_text *t, const Tuning &tune, int epi, const GemmArgs &a
 // still be reading the buffer (vitx_text_embed_device only enqueues) -- for the upload, not for its forward.
 int stage_ids(vitx_text *t, const int32_t *ids, int n) {
     t->pooled_host.resize((size_t)n);
-    const int rc = vitx_text_check_ids(t->shell.model, ids, n, t->pooled_host.data());
+    const int rc = vitx_text_check_ids(t->model, ids, n, t->pooled_host.data());
     if (rc) return rc;
-    if (t->uploaded_pending) { HIP_TRY(hipSetDevice(t->shell.device)); HIP_TRY(hipEventSynchronize(t->uploaded)); t->uploaded_pending = false; }
+    if (t->uploaded_pending) { HIP_TRY(hipSetDevice(t->device)); HIP_TRY(hipEventSynchronize(t->uploaded)); t->uploaded_pending = false; }
     memcpy(t->host.data(), t->pooled_host.data(), (size_t)n * 4);
     memcpy(t->host.data() + t->max_prompts, ids, (size_t)n * t->T * 4);
     return VITX_OK;
 }
 
 int text_forward(vitx_text *t, int n, int flags, float *d_out, hipStream_t st) {
-    const vitx_ctx::WeightSet &ws = *t->shell.wset;
-    const int T = t->T, D = t->shell.D, H = t->shell.H, tn = t->shell.tn, tm = t->shell.tm, dtype = t->shell.dtype;
+    const WeightSet &ws = *t->wset;
+    const int T = t->T, D = t->D, H = t->H, tn = t->tn, tm = t->tm, dtype = t->dtype;
     const int rows = n * T, M = round_up(rows, tm), Mh = round_up(n, tm);
     int rc;
     // pooled positions and ids: ONE upload of the staging buffer's front (the ids sit at their fixed place behind max_prompts positions)
@@ -82,32 +83,27 @@ int vitx_text_create(const vitx_model *m, int device, int max_prompts, int dtype
     if (!layernorm_supports(D)) { set_error("vitx_text_create: hidden_size %d has no LayerNorm instantiation", D); return VITX_ERR_UNSUPPORTED; }
     if (E % 64) { set_error("vitx_text_create: embedding width %d is not a multiple of 64", E); return VITX_ERR_UNSUPPORTED; }
     if ((long)max_prompts * T > (long)(0xf0000000u / ((size_t)4 * D * 2)) / 256 * 256) { set_error("vitx_text_create: max_prompts %d x %d tokens exceed the kernels' 32-bit buffer window", max_prompts, T); return VITX_ERR_UNSUPPORTED; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("vitx_text_create: no HIP device available (this engine has no CPU fallback)"); return VITX_ERR_HIP; }
-    if (device < 0 || device >= ndev) { set_error("vitx_text_create: device %d out of range (%d devices)", device, ndev); return VITX_ERR_ARG; }
-    HIP_TRY(hipSetDevice(device));
+    const Tuning *tune = nullptr;
+    int rc;
+    if ((rc = open_device("vitx_text_create", device, &tune))) return rc;
     std::unique_ptr<vitx_text> t(new (std::nothrow) vitx_text());
     if (!t) return VITX_ERR_NOMEM;
-    vitx_ctx &s = t->shell;
-    s.model = m; s.hp = hp; s.device = device; s.dtype = dtype; s.max_batch = max_prompts;
-    s.D = D; s.L = hp.num_hidden_layers; s.H = H; s.C = E;
-    s.tm = gemm_tile_m(); s.tn = gemm_tile_n(); s.C_pad = round_up(E, s.tn);
-    s.quant_on_device = false;
-    t->V = m->vocab; t->T = T; t->E = E; t->E_pad = s.C_pad; t->causal = m->causal; t->eos = m->eos; t->max_prompts = max_prompts;
+    t->model = m; t->device = device; t->dtype = dtype; t->tune = tune;
+    t->D = D; t->L = hp.num_hidden_layers; t->H = H;
+    t->tm = gemm_tile_m(); t->tn = gemm_tile_n();
+    t->V = m->vocab; t->T = T; t->E = E; t->E_pad = head_cols_pad(m); t->causal = m->causal; t->eos = m->eos; t->max_prompts = max_prompts;
     t->fc1_epi = act_epi(m->activation); t->eps = hp.eps;
-    s.tune = tuning_for_device(device);
-    if (!s.tune) { set_error("vitx_text_create: kernel bring-up on device %d failed: %s", device, hipGetErrorString(hipGetLastError())); return VITX_ERR_HIP; }
-    const int Mcap = round_up(max_prompts * T, s.tm), Bcap = round_up(max_prompts, s.tm), tn = s.tn;
+    const int Mcap = round_up(max_prompts * T, t->tm), Bcap = round_up(max_prompts, t->tm), tn = t->tn;
     struct { Tuning *tune; int M, N, K; } pins[] = {{&t->tune_qkv, Mcap, 3 * D, D}, {&t->tune_proj, Mcap, D, D}, {&t->tune_fc1, Mcap, 4 * D, D}, {&t->tune_fc2, Mcap, D, 4 * D}, {&t->tune_head, Bcap, E, D}};
     for (auto &p : pins) {
-        *p.tune = *s.tune;
+        *p.tune = *tune;
         // the dispatcher's own rule between its two ring tilings (gemm_ring_cfg, gemm.hip), at the rows of a full batch: never the wide persistent
         // kernels, whose choice depends on the row count of a call
-        p.tune->gemm_cfg = gemm_ring_cfg(*s.tune, dense_gemm(nullptr, nullptr, nullptr, nullptr, p.M, p.M, p.N, round_up(p.N, tn), p.K));
+        p.tune->gemm_cfg = gemm_ring_cfg(*tune, dense_gemm(nullptr, nullptr, nullptr, nullptr, p.M, p.M, p.N, round_up(p.N, tn), p.K));
         if (!p.tune->gemm_cfg) { set_error("vitx_text_create: no GEMM tiling for %d x %d x %d", p.M, p.N, p.K); return VITX_ERR_UNSUPPORTED; }
     }
-    int rc;
-    if ((rc = obtain_text_weights(&s))) return rc;
+    // quantised block matrices are expanded at upload (the comment at the top): block mode 0
+    if ((rc = obtain_weights({m, device, dtype, false}, &t->wset, &t->weights_shared))) return rc;
     auto dmalloc = [&](void **p, size_t bytes) -> int {
         HIP_TRY(hipMalloc(p, bytes));
         t->allocs.push_back(*p);
@@ -150,13 +146,13 @@ int vitx_text_check_ids(const vitx_model *m, const int32_t *ids, int n, int32_t 
 }
 
 void vitx_text_free(vitx_text *t) { delete t; }
-int vitx_text_shares_weights(const vitx_text *t) { return t && t->shell.weights_shared ? 1 : 0; }
+int vitx_text_shares_weights(const vitx_text *t) { return t && t->weights_shared ? 1 : 0; }
 
 int vitx_text_embed_device(vitx_text *t, const int32_t *ids, int n, int flags, void *d_out, void *stream) {
     int rc = check_call(t, ids, n, flags, d_out);
     if (rc) return rc;
     if ((rc = stage_ids(t, ids, n))) return rc;
-    HIP_TRY(hipSetDevice(t->shell.device));
+    HIP_TRY(hipSetDevice(t->device));
     return text_forward(t, n, flags, (float *)d_out, (hipStream_t)stream);
 }
 
@@ -164,7 +160,7 @@ int vitx_text_embed(vitx_text *t, const int32_t *ids, int n, int flags, float *o
     int rc = check_call(t, ids, n, flags, out);
     if (rc) return rc;
     if ((rc = stage_ids(t, ids, n))) return rc;
-    HIP_TRY(hipSetDevice(t->shell.device));
+    HIP_TRY(hipSetDevice(t->device));
     if ((rc = text_forward(t, n, flags, t->out, t->stream))) return rc;
     HIP_TRY(hipMemcpyAsync(out, t->out, (size_t)n * t->E * 4, hipMemcpyDeviceToHost, t->stream));
     HIP_TRY(hipStreamSynchronize(t->stream));
