@@ -844,6 +844,72 @@ int vitx_zeroshot_max_classes(int E);                /* the bound on K for width
 int vitx_op_zeroshot(int dtype, const void *d_z, long z_stride, const void *d_bank /* dtype, [K_pad][E], zero rows beyond K */,
                      void *d_a_scratch, void *d_acc_scratch, void *d_probs, void *d_logits, int n, int K, int E, int kind, float scale, float bias, void *stream);
 
+/* ---- nearest neighbours in a gallery: device retrieval and weighted k-NN --------- */
+/* An opt-in output of the forward, in the manner of the maps, the features and the bank.  A context is given a GALLERY: G embeddings of width E
+ * (and, optionally, a label per row); every forward then also writes, per image, the k gallery rows with the best scores and -- with labels -- the
+ * temperature-weighted vote of their labels (the DINO k-NN protocol: k = 20, T = 0.07).  Nothing else the forward writes changes; with no gallery
+ * nothing is launched or allocated.  The gallery is walked in chunks: the scratch does not grow with G, and G is not bound by the GEMMs' 32-bit
+ * operand window (only one chunk of it is).  For one image:
+ *   source embedding z, width E = vitx_nn_width(ctx, source), a multiple of 64 (the GEMMs' K step):
+ *     VITX_NN_LOGITS  the f32 logits row of the head GEMM, the z of the zero-shot path of a context without the attention-pooling head; E = C
+ *                     (image_embeds of a CLIP file).
+ *     VITX_NN_EMBED   the head GEMM's own operand row Z[i] widened to f32: RNE of the final-norm class embedding (class-token head, E = D), RNE(e) of
+ *                     the pooled embedding (VITX_POOL_MAP, E = D), RNE(cls) ‖ RNE(patch mean) (VITX_POOL_CLS_MEAN, E = 2 D) -- the values the
+ *                     "RNE(feature) == the head operand" rules above pin.  Z exists in every classifier forward: this source costs no feature pass
+ *                     and leaves the class-rows-only last layer alone.  It is what a backbone converted without a head is searched by.
+ *   query operand  a = RNE_dtype(z / sqrtf(ss)): the zero-shot rule unchanged (the same kernel text: the same sum-of-squares order, an all-zero row
+ *     stays zero, a VITX_MXFP8 context uses bf16).
+ *   gallery        host [G][E] f32 rows, uploaded RNE to the operand type, padded with zero rows to a multiple of 128.  The engine does NOT
+ *     renormalise them (as for the bank); every entry must be finite.  labels: [G] i32 in [0, n_labels), or NULL.
+ *   scores         s_g = sum_i a_i * t_{g,i}, f32 accumulation on the MFMA, through the head's GEMM dispatcher with a zero bias, one GEMM per chunk of
+ *     Gc = 32768 gallery rows, each with its own base pointer into the gallery.  The bits of s_g depend on the image's a and on row g only.
+ *   selection      the k best of the G scores in vitx_topk's total order: score descending, then gallery index ascending; +0 and -0 tie; NaN last, by
+ *     index.  1 <= k <= 64, k <= G.  Output idx[k] i32 and score[k] f32, best first.  The result is a function of the G scores alone: not of the
+ *     chunk size, nor of how a chunk is cut among wavefronts.  A score is returned as its place in the order names it: either zero as +0, any NaN as
+ *     the quiet NaN 0x7fc00000, every other value bit for bit.  Pad rows of the gallery never reach the selection.
+ *   vote (labels only)  T > 0 finite; w_j = expf((score_j - score_0) / T), f32 subtract, IEEE division; W = sum_j w_j serially over rank j = 0 .. k-1;
+ *     vote[c] = (sum of w_j over the ranks j with label[idx_j] == c, serially in rank order) / W: a row of n_labels f32.  One writer per element.
+ * Determinism: an image's outputs are the same bits at any batch size, position in the batch, sub-batch cut and stream count; the forward's
+ *   probabilities and logits are the same bits with a gallery set and without; a bank and a gallery may both be set, neither changes the other.
+ * vitx_nn_set: uploads the gallery (and labels), allocates per sub-batch slice the operand rows, one chunk's score scratch and the running top-k
+ *   state -- none of them depends on G (vitx_nn_scratch_bytes) -- and the output buffers for the images one pass takes; synchronises the device.
+ *   Setting again replaces the gallery; gallery NULL and G 0 turn the output off and free everything.
+ *   VITX_ERR_ARG: NULL gallery with G > 0; an unknown source; k < 1 or k > G; E different from vitx_nn_width; a gallery entry that is not finite; a
+ *     label outside [0, n_labels); labels with n_labels < 1 or with a temperature that is not finite and positive.  VITX_ERR_UNSUPPORTED: k > 64; E
+ *     not a multiple of 64; a ViTSTR context; G >= 2^31 - 128; a context whose pass takes more than 30720 images (one chunk's score rows must lie
+ *     inside the GEMM's 32-bit byte window).  VITX_ERR_NOMEM: an allocation fails (the gallery is then off).  All but the last
+ *     are raised before any device call.
+ * While a gallery is set, a forward of more than one pass is VITX_ERR_ARG and forwards do not use the hipGraph cache; profiling reports the
+ *   2 ceil(G / Gc) + 2 launches per sub-batch (the operand rows, per chunk the GEMM and the selection, the final merge) as class "nn".
+ * vitx_nn_read: synchronises and copies the last such forward's idx [n][k], score [n][k] and, unless NULL, vote [n][n_labels]; VITX_ERR_ARG before
+ *   any such forward, or for a vote without labels.  vitx_nn_device: the device buffer, [capacity][k] {f32 score, i32 index} pairs (the layout
+ *   vitx_op_topk writes), NULL while off.  vitx_group_* has no gallery.
+ * The kernels on their own (device pointers; only enqueue):
+ *   vitx_op_nn_select: merges columns 0 .. cols of d_scores [n][ld] f32 (column j = gallery row base_index + j; columns cols .. ld are never read)
+ *     into d_state (vitx_op_nn_state_bytes(n, k) bytes, 8-byte aligned); first != 0: the state is initialised by this launch, not read.
+ *   vitx_op_nn_finish: d_state -> d_pairs [n][k] and, d_labels != NULL, d_vote [n][n_labels]; d_labels must cover every index in the state.
+ *   vitx_op_nn: the forward's launches without the vote.  Row i of z at d_z + i * z_stride elements: f32 (z_is_operand 0) or `dtype` (1); z_stride
+ *     >= E, a multiple of 4.  d_gallery [G_pad][E] in `dtype`, G_pad = G rounded up to 128, zero rows beyond G; d_a_scratch [n_pad][E] `dtype`,
+ *     d_acc_scratch [n_pad + 1][chunk] f32 with n_pad = n rounded up to 256 (the last row becomes the zero bias).
+ *     VITX_ERR_ARG: NULL or misaligned (16 bytes) pointers, n, G, E < 1, k < 1 or k > G, a bad z_stride, chunk not a positive multiple of 128;
+ *     VITX_ERR_UNSUPPORTED: k > 64, E not a multiple of 64, G >= 2^31 - 128, a chunk beyond the GEMM's operand window. */
+enum vitx_nn_source { VITX_NN_LOGITS = 0, VITX_NN_EMBED = 1 };
+int vitx_nn_width(const vitx_ctx *c, int source);     /* E of that source for this context; 0 for NULL / an unknown source */
+int vitx_nn_set(vitx_ctx *c, const float *gallery /* host [G][E] */, long G, int E, int k, int source,
+                const int32_t *labels /* [G] or NULL */, int n_labels, float temperature);   /* gallery NULL && G == 0: off, frees */
+long vitx_nn_rows(const vitx_ctx *c);                 /* G; 0 while off */
+int vitx_nn_k(const vitx_ctx *c);
+int vitx_nn_labels(const vitx_ctx *c);                /* n_labels; 0 without labels */
+int vitx_nn_images(const vitx_ctx *c);
+int vitx_nn_read(vitx_ctx *c, int32_t *idx /* [n][k] */, float *score /* [n][k] */, float *vote /* [n][n_labels] or NULL */);
+const void *vitx_nn_device(const vitx_ctx *c);        /* [capacity][k] {f32 score, i32 index}; NULL while off */
+size_t vitx_nn_scratch_bytes(const vitx_ctx *c);      /* device bytes of score scratch + running state over all slices; 0 while off */
+int vitx_op_nn_select(const void *d_scores /* [n][ld] f32 */, long ld, int n, int cols, long base_index, void *d_state, int k, int first, void *stream);
+int vitx_op_nn_finish(const void *d_state, int n, int k, const void *d_labels, int n_labels, float temperature, void *d_pairs, void *d_vote, void *stream);
+size_t vitx_op_nn_state_bytes(int n, int k);
+int vitx_op_nn(int dtype, const void *d_z, long z_stride, int z_is_operand, int n, const void *d_gallery /* dtype [G_pad][E] */, long G, int E, int k, int chunk,
+               void *d_a_scratch, void *d_acc_scratch /* [n_pad + 1][chunk] */, void *d_state, void *d_pairs, void *stream);
+
 /* ---- the text tower (CLIP, SigLIP): token ids in, text embeddings out ---------------
  * The text half of a contrastive checkpoint is a second model file in the same container.  Header: hidden_size D, num_hidden_layers L,
  * num_attention_heads H, num_classes = E (the width of the projected embedding), patch_size = 0 (THE mark of a text file: no image file

@@ -34,6 +34,7 @@ ATTN_ROLLOUT = 1                # vitx_attn_enable flag
 FEAT_CLS, FEAT_MEAN, FEAT_TOKENS, FEAT_L2 = 1, 2, 4, 8      # vitx_feat_enable flags
 KIND_IMAGE, KIND_TEXT = 0, 1            # vitx_model_kind
 TEXT_L2 = 1                             # vitx_text_embed flag
+NN_LOGITS, NN_EMBED = 0, 1              # vitx_nn_source
 POS_BICUBIC, POS_BICUBIC_AA = 0, 1      # vitx_pos_interp: F.interpolate(mode="bicubic") without / with antialias=True (include/vitx.h)
 
 EXPORTS = [
@@ -54,6 +55,8 @@ EXPORTS = [
     "vitx_model_preproc", "vitx_model_has_preproc", "vitx_preproc_at_size", "vitx_preprocess_ex", "vitx_preprocess_ex_device", "vitx_preprocess_ex_device_supports",
     "vitx_model_num_prefix", "vitx_model_pool_query", "vitx_op_attention_pool",
     "vitx_zeroshot_set", "vitx_zeroshot_classes", "vitx_zeroshot_images", "vitx_zeroshot_read", "vitx_zeroshot_device", "vitx_zeroshot_max_classes", "vitx_op_zeroshot",
+    "vitx_nn_width", "vitx_nn_set", "vitx_nn_rows", "vitx_nn_k", "vitx_nn_labels", "vitx_nn_images", "vitx_nn_read", "vitx_nn_device", "vitx_nn_scratch_bytes",
+    "vitx_op_nn_select", "vitx_op_nn_finish", "vitx_op_nn_state_bytes", "vitx_op_nn",
     "vitx_model_kind", "vitx_model_text_info", "vitx_model_text_zs", "vitx_text_create", "vitx_text_free", "vitx_text_embed", "vitx_text_embed_device", "vitx_text_shares_weights", "vitx_text_check_ids",
     "vitx_op_text_embed", "vitx_op_text_pool", "vitx_op_attention_text", "vitx_op_attention_generic",
     "vitx_model_rope", "vitx_model_rope_table", "vitx_op_rope",
@@ -235,6 +238,19 @@ def lib():
             L.vitx_zeroshot_read.argtypes = [vp, fp, fp, C.c_size_t]
             L.vitx_zeroshot_device.restype = C.c_void_p; L.vitx_zeroshot_device.argtypes = [vp]
             L.vitx_op_zeroshot.argtypes = [ip, vp, C.c_long, vp, vp, vp, vp, vp, ip, ip, ip, ip, C.c_float, C.c_float, vp]
+        if hasattr(L, "vitx_nn_set"):
+            fp, i32p = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+            L.vitx_nn_width.argtypes = [vp, ip]
+            L.vitx_nn_set.argtypes = [vp, fp, C.c_long, ip, ip, ip, i32p, ip, C.c_float]
+            L.vitx_nn_rows.restype = C.c_long; L.vitx_nn_rows.argtypes = [vp]
+            L.vitx_nn_k.argtypes = [vp]; L.vitx_nn_labels.argtypes = [vp]; L.vitx_nn_images.argtypes = [vp]
+            L.vitx_nn_read.argtypes = [vp, i32p, fp, fp]
+            L.vitx_nn_device.restype = C.c_void_p; L.vitx_nn_device.argtypes = [vp]
+            L.vitx_nn_scratch_bytes.restype = C.c_size_t; L.vitx_nn_scratch_bytes.argtypes = [vp]
+            L.vitx_op_nn_select.argtypes = [vp, C.c_long, ip, ip, C.c_long, vp, ip, ip, vp]
+            L.vitx_op_nn_finish.argtypes = [vp, ip, ip, vp, ip, C.c_float, vp, vp, vp]
+            L.vitx_op_nn_state_bytes.restype = C.c_size_t; L.vitx_op_nn_state_bytes.argtypes = [ip, ip]
+            L.vitx_op_nn.argtypes = [ip, vp, C.c_long, ip, ip, vp, C.c_long, ip, ip, ip, vp, vp, vp, vp, vp]
         if hasattr(L, "vitx_text_create"):
             i32p = C.POINTER(C.c_int32)
             L.vitx_model_kind.argtypes = [vp]
@@ -744,6 +760,48 @@ class Context:
         stay on the GPU (vitx_zeroshot_device).  Ordered after the forward's stream, like d_probs."""
         return int(lib().vitx_zeroshot_device(self._h) or 0), int(lib().vitx_zeroshot_classes(self._h))
 
+    def nn_width(self, source: int) -> int:
+        """vitx_nn_width: the width E of the source embedding (NN_LOGITS: num_classes; NN_EMBED: the head operand's, D or 2 D)."""
+        return int(lib().vitx_nn_width(self._h, int(source)))
+
+    def nn_set(self, gallery: Optional[np.ndarray], k: int = 1, source: int = NN_EMBED, labels=None, n_labels: int = 0, temperature: float = 0.07) -> None:
+        """The k nearest rows of `gallery` [G, E] f32 (unit rows: the engine does not renormalise them) for every image of every later forward, and --
+        labels [G] i32 in [0, n_labels) -- the temperature-weighted vote of their labels (vitx_nn_set).  None turns the output off and frees its buffers."""
+        if gallery is None:
+            check(lib().vitx_nn_set(self._h, None, 0, 0, 0, 0, None, 0, 0.0), "vitx_nn_set")
+            return
+        g = np.ascontiguousarray(gallery, dtype=np.float32)
+        if g.ndim != 2:
+            raise ValueError("nn_set: gallery must be [G, E]")
+        lab = None
+        if labels is not None:
+            lab = np.ascontiguousarray(labels, dtype=np.int32)
+            if lab.shape != (g.shape[0],):
+                raise ValueError("nn_set: labels must be [G]")
+        check(lib().vitx_nn_set(self._h, g.ctypes.data_as(C.POINTER(C.c_float)), g.shape[0], g.shape[1], int(k), int(source),
+                                lab.ctypes.data_as(C.POINTER(C.c_int32)) if lab is not None else None, int(n_labels), float(temperature)), "vitx_nn_set")
+
+    def nn_read(self, n: Optional[int] = None):
+        """(idx [n, k] i32, score [n, k] f32, vote [n, n_labels] f32 or None) of the last forward made with a gallery set, best first.  `n`, if given,
+        must be that batch."""
+        L = lib()
+        k, nl, have = L.vitx_nn_k(self._h), L.vitx_nn_labels(self._h), L.vitx_nn_images(self._h)
+        if n is not None and n != have:
+            raise ValueError(f"nn_read: the last forward with a gallery set had {have} images, not {n}")
+        idx = np.empty((max(have, 1), max(k, 1)), np.int32)
+        score = np.empty(idx.shape, np.float32)
+        vote = np.empty((max(have, 1), nl), np.float32) if nl else None
+        check(L.vitx_nn_read(self._h, idx.ctypes.data_as(C.POINTER(C.c_int32)), score.ctypes.data_as(C.POINTER(C.c_float)),
+                             vote.ctypes.data_as(C.POINTER(C.c_float)) if nl else None), "vitx_nn_read")
+        return idx, score, vote
+
+    def nn_device(self) -> Tuple[int, int]:
+        """(device pointer of the result [capacity][k] {f32 score, i32 index}, k) for callers that stay on the GPU (vitx_nn_device); (0, 0) while off."""
+        return int(lib().vitx_nn_device(self._h) or 0), int(lib().vitx_nn_k(self._h))
+
+    def nn_scratch_bytes(self) -> int:
+        return int(lib().vitx_nn_scratch_bytes(self._h))
+
     def synchronize(self) -> None:
         check(lib().vitx_ctx_synchronize(self._h), "vitx_ctx_synchronize")
 
@@ -1022,6 +1080,67 @@ def op_zeroshot(dtype: int, d_z: int, z_stride: int, d_bank: int, d_a: int, d_ac
     d_probs and d_logits [n, K] f32."""
     check(lib().vitx_op_zeroshot(dtype, d_z or None, z_stride, d_bank or None, d_a or None, d_acc or None, d_probs or None, d_logits or None, n, K, E,
                                  int(kind), float(scale), float(bias), stream or None), "vitx_op_zeroshot")
+
+
+def op_nn_state_bytes(n: int, k: int) -> int:
+    return int(lib().vitx_op_nn_state_bytes(n, k))
+
+
+def op_nn_select(d_scores: int, ld: int, n: int, cols: int, base_index: int, d_state: int, k: int, first: bool, stream: int = 0) -> None:
+    """vitx_op_nn_select: merge columns 0 .. cols of the f32 score rows [n, ld] (column j = gallery row base_index + j) into the running top-k state."""
+    check(lib().vitx_op_nn_select(d_scores or None, ld, n, cols, base_index, d_state or None, k, int(bool(first)), stream or None), "vitx_op_nn_select")
+
+
+def op_nn_finish(d_state: int, n: int, k: int, d_pairs: int, d_labels: int = 0, n_labels: int = 0, temperature: float = 0.0, d_vote: int = 0, stream: int = 0) -> None:
+    """vitx_op_nn_finish: the state -> pairs [n, k] {f32 score, i32 index} best first and, with labels, the vote [n, n_labels]."""
+    check(lib().vitx_op_nn_finish(d_state or None, n, k, d_labels or None, n_labels, float(temperature), d_pairs or None, d_vote or None, stream or None), "vitx_op_nn_finish")
+
+
+def op_nn(dtype: int, d_z: int, z_stride: int, z_is_operand: bool, n: int, d_gallery: int, G: int, E: int, k: int, chunk: int, d_a: int, d_acc: int,
+          d_state: int, d_pairs: int, stream: int = 0) -> None:
+    """vitx_op_nn: the nearest-neighbour launches of a forward on their own (device pointers; z_stride in elements of z's type).  d_gallery [G_pad, E]
+    in `dtype` (G_pad = G rounded up to 128, zero rows beyond G), d_a [n_pad, E] `dtype`, d_acc [n_pad + 1, chunk] f32 with n_pad = n rounded up to 256."""
+    check(lib().vitx_op_nn(dtype, d_z or None, z_stride, int(bool(z_is_operand)), n, d_gallery or None, G, E, k, chunk, d_a or None, d_acc or None,
+                           d_state or None, d_pairs or None, stream or None), "vitx_op_nn")
+
+
+def round_operand(x: np.ndarray, dtype: int) -> np.ndarray:
+    """x rounded (RNE) to a context's operand type, as f32: fp16 for F16, bf16 for BF16 and MXFP8 (finite values)."""
+    x = np.ascontiguousarray(x, np.float32)
+    if dtype == F16:
+        return x.astype(np.float16).astype(np.float32)
+    b = x.view(np.uint32).astype(np.uint64)
+    b = ((b + 0x7fff + ((b >> 16) & 1)) >> 16) << 16
+    return b.astype(np.uint32).view(np.float32)
+
+
+def nn_gallery(ctx: "Context", images: np.ndarray, source: int = NN_EMBED) -> np.ndarray:
+    """Gallery rows [n, E] f32 of unit length for Context.nn_set, from forwards of `images` [n, h, w, 3] through ctx: the logits rows (NN_LOGITS), or
+    (NN_EMBED) the head GEMM's operand rows -- RNE of the last layer's FEAT_CLS feature (and of FEAT_MEAN behind it for a cls + mean head), which the
+    header pins to the operand bit for bit.  Normalised in float64, rounded once to f32.  Runs in batches of ctx.max_batch; leaves the features off."""
+    x = np.ascontiguousarray(images, np.float32)
+    pooled = source == NN_EMBED and ctx.model.head_pool == POOL_CLS_MEAN
+    if source == NN_EMBED:
+        ctx.feat_enable(cls=True, mean=pooled)
+    elif source != NN_LOGITS:
+        raise ValueError(f"nn_gallery: unknown source {source}")
+    rows = []
+    try:
+        for i0 in range(0, x.shape[0], ctx.max_batch):
+            xb = x[i0:i0 + ctx.max_batch]
+            _, lg = ctx.forward(xb, want_logits=True)
+            if source == NN_LOGITS:
+                rows.append(lg.astype(np.float64))
+                continue
+            f = ctx.feat_read(xb.shape[0])[ctx.model.hparams.num_hidden_layers - 1]
+            z = np.concatenate([f["cls"], f["mean"]], axis=1) if pooled else f["cls"]
+            rows.append(round_operand(z, ctx.dtype).astype(np.float64))
+    finally:
+        if source == NN_EMBED:
+            ctx.feat_disable()
+    z = np.concatenate(rows, axis=0)
+    nrm = np.sqrt((z * z).sum(-1, keepdims=True))
+    return np.divide(z, nrm, out=np.zeros_like(z), where=nrm > 0).astype(np.float32)
 
 
 def mx_k_pad(K: int) -> int:

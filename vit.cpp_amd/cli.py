@@ -11,6 +11,8 @@ directory-walk accuracy harness:
     python vit_cli.py -m clip.gguf -i image.jpg -k 5 --zero-shot bank.npz   # zero-shot classes of a CLIP / SigLIP file (bank: convert.py --zero-shot-out)
     python vit_cli.py -m clip.gguf -i image.jpg --text-model text.gguf --zero-shot-ids ids.npy [--zero-shot-labels labels.txt]   # the bank made by the engine, same run
     python vit_cli.py --text-model text.gguf --zero-shot-ids ids.npy --text-embed out.npy   # the text embeddings of tokenised prompts (no image, no -m)
+    python vit_cli.py -m model.gguf --gallery-build DIR --gallery-out g.npz [--nn-source embed|logits]   # embed DIR/<label>/* into a gallery
+    python vit_cli.py -m model.gguf -i image.jpg --gallery g.npz -k 5 [--nn-temperature 0.07]   # the k nearest gallery images and the k-NN vote of their labels
 
 --preprocess model follows the file's `preproc` tensor (include/vitx.h "each model's own preprocessing": what convert.py reads from a
 HuggingFace preprocessor_config.json -- CLIP: Pillow-bicubic shortest edge 224, centre crop 224, CLIP's mean / std; DINOv2: shortest edge 256,
@@ -100,7 +102,37 @@ def make_parser() -> argparse.ArgumentParser:
     ap.add_argument("--zero-shot-labels", default=None, metavar="LABELS.txt", help="with --zero-shot-ids: one class name per line (default: class_<k>)")
     ap.add_argument("--text-embed", default=None, metavar="OUT.npy", help="with --text-model and --zero-shot-ids: write the prompts' text embeddings [prompts][E] and stop "
                                                                           "unless -m names an image model to classify with")
+    ap.add_argument("--gallery-build", default=None, metavar="DIR",
+                    help="embed every image under DIR/<label>/* and write the gallery to --gallery-out: unit rows `embeds`, `labels`, `label_names`, `paths` (and `source`)")
+    ap.add_argument("--gallery-out", default=None, metavar="G.npz", help="with --gallery-build: the file to write")
+    ap.add_argument("--nn-source", default="embed", choices=["embed", "logits"],
+                    help="with --gallery-build: what a gallery row is: embed = the head's operand row (any backbone, also one converted without a head), "
+                         "logits = the logits row (image_embeds of a CLIP file)")
+    ap.add_argument("--gallery", default=None, metavar="G.npz",
+                    help="with -i: print the -k nearest gallery images with their scores and, when the gallery has labels, the ' > label : 0.xx' lines of the "
+                         "temperature-weighted k-NN vote (vitx_nn_set) instead of the file's own head")
+    ap.add_argument("--nn-temperature", type=float, default=0.07, help="with --gallery: the vote's temperature (DINO: 0.07)")
     return ap
+
+
+def gallery_build(binding, a, model, ctx, preprocess):
+    """--gallery-build: DIR/<label>/<image> -> G.npz.  The label of an image is its sub-directory's name."""
+    names = [d for d in sorted(os.listdir(a.gallery_build)) if os.path.isdir(os.path.join(a.gallery_build, d))]
+    paths, labels = [], []
+    for li, d in enumerate(names):
+        for f in sorted(os.listdir(os.path.join(a.gallery_build, d))):
+            paths.append(os.path.join(a.gallery_build, d, f)); labels.append(li)
+    if not paths:
+        print(f"main: no <label>/<image> files under '{a.gallery_build}'", file=sys.stderr)
+        return 1
+    source = binding.NN_EMBED if a.nn_source == "embed" else binding.NN_LOGITS
+    rows = []
+    for lo in range(0, len(paths), ctx.max_batch):
+        rows.append(binding.nn_gallery(ctx, np.stack([preprocess(_decode(f)) for f in paths[lo:lo + ctx.max_batch]]), source))
+    np.savez(a.gallery_out, embeds=np.concatenate(rows), labels=np.asarray(labels, np.int32), label_names=np.asarray(names), paths=np.asarray(paths),
+             source=np.int32(source))
+    print(f"main: wrote {len(paths)} {a.nn_source} rows of {len(names)} labels to '{a.gallery_out}'", file=sys.stderr)
+    return 0
 
 
 def text_side(binding, a, dt):
@@ -148,6 +180,10 @@ def main(argv: List[str] | None = None) -> int:
         ap.error("--embed-kind and --embed-l2 need --embed OUT.npy")
     if a.embed_l2 and a.embed_kind == "tokens":
         ap.error("--embed-l2 normalises the cls / mean embedding; token features are never normalised")
+    if bool(a.gallery_build) != bool(a.gallery_out):
+        ap.error("--gallery-build DIR and --gallery-out G.npz go together")
+    if a.gallery and (a.dir is not None or a.gallery_build):
+        ap.error("--gallery searches for the single image of -i")
     if sum(bool(v) for v in (a.img_size, a.img_shape, a.img_fit)) > 1:
         ap.error("--img-size, --img-shape and --img-fit are three ways to say one thing: give one")
     if a.img_fit and a.dir is not None:
@@ -217,6 +253,23 @@ def main(argv: List[str] | None = None) -> int:
             print(f"main: failed to load the zero-shot bank from '{a.zero_shot}': {e}", file=sys.stderr)
             return 1
 
+    if a.gallery_build:
+        n_files = sum(len(fs) for _, _, fs in os.walk(a.gallery_build))
+        try:
+            ctx = binding.Context(model, device=a.device, max_batch=max(1, min(a.batch, n_files)), dtype=dt, img_shape=rect, **geometry)
+            return gallery_build(binding, a, model, ctx, preprocess)
+        except (binding.VitxError, OSError, ValueError) as e:
+            print(f"main: failed to build the gallery of '{a.gallery_build}': {e}", file=sys.stderr)
+            return 1
+    gallery = None
+    if a.gallery:
+        try:
+            with np.load(a.gallery) as z:
+                gallery = {k: z[k] for k in z.files}
+        except (OSError, ValueError) as e:
+            print(f"main: failed to load the gallery from '{a.gallery}': {e}", file=sys.stderr)
+            return 1
+
     if a.dir is None:
         try:
             img0 = _decode(a.inp)
@@ -249,7 +302,25 @@ def main(argv: List[str] | None = None) -> int:
             except binding.VitxError as e:
                 print(f"main: the bank of '{a.zero_shot or a.text_model}' does not fit this model: {e}", file=sys.stderr)
                 return 1
+        if gallery:
+            try:
+                labels = gallery["labels"] if "labels" in gallery and len(gallery.get("label_names", ())) else None
+                ctx.nn_set(gallery["embeds"], min(a.topk, len(gallery["embeds"])), int(gallery["source"]) if "source" in gallery else binding.NN_EMBED, labels,
+                           len(gallery["label_names"]) if labels is not None else 0, a.nn_temperature)
+            except binding.VitxError as e:
+                print(f"main: the gallery of '{a.gallery}' does not fit this model: {e}", file=sys.stderr)
+                return 1
         probs = ctx.forward(img1[None])[0]
+        if gallery:
+            idx, score, vote = ctx.nn_read(1)
+            print("", file=sys.stderr)
+            for g, s in zip(idx[0], score[0]):
+                print(f" ~ {gallery['paths'][g] if 'paths' in gallery else g} : {s:.4f}")
+            if vote is not None:
+                names = gallery["label_names"]
+                for i, p in zip(*binding.topk(vote[0], min(a.topk, len(names)))):
+                    print(f" > {names[i]} : {p:.2f}")
+            return 0
         if a.embed:
             np.save(a.embed, last(ctx))
             print(f"main: wrote the {a.embed_kind} embedding to '{a.embed}'", file=sys.stderr)

@@ -15,11 +15,11 @@ namespace vitx {
 
 enum ProfClass {
     PC_GEMM_PATCH = 0, PC_LAYERNORM, PC_GEMM_QKV, PC_ATTENTION, PC_GEMM_PROJ, PC_GEMM_FC1, PC_GEMM_FC2,
-    PC_GEMM_HEAD, PC_SOFTMAX, PC_DEQUANT, PC_ATTENTION_CLS, PC_GEMM_TAIL, PC_ATTN_MAP, PC_FEATURES, PC_HEAD_POOL, PC_ZEROSHOT, PC_ROPE, PC_SWIGLU, PC_COUNT
+    PC_GEMM_HEAD, PC_SOFTMAX, PC_DEQUANT, PC_ATTENTION_CLS, PC_GEMM_TAIL, PC_ATTN_MAP, PC_FEATURES, PC_HEAD_POOL, PC_ZEROSHOT, PC_ROPE, PC_SWIGLU, PC_NN, PC_COUNT
 };
 inline const char *const kProfNames[PC_COUNT] = {"patch_embed", "layernorm", "gemm_qkv_bias", "attention", "gemm_proj_resid",
                                     "gemm_fc1_gelu", "gemm_fc2_resid", "gemm_head", "softmax", "dequant_weights", "attention_cls", "gemm_cls_tail", "attention_map",
-                                    "features", "head_pool", "zeroshot", "rope", "swiglu"};
+                                    "features", "head_pool", "zeroshot", "rope", "swiglu", "nn"};
 static_assert(PC_COUNT <= VITX_PROF_MAX_CLASSES, "vitx_profile_read callers size their arrays by VITX_PROF_MAX_CLASSES");
 
 static_assert(VITX_F16 == DT_F16 && VITX_BF16 == DT_BF16, "the API's dtype values are handed to the launchers as they are");
@@ -204,6 +204,36 @@ struct vitx_ctx {
         zs_bank = nullptr; zs_zero = nullptr; zs_out = nullptr;
         zs_K = zs_Kpad = zs_cap = zs_n = 0;
     }
+    // nearest neighbours in a gallery (vitx_nn_set): nothing is allocated or launched while nn_G == 0
+    static constexpr int kNnChunk = 32768;  // Gc: gallery rows one chunk GEMM scores (a multiple of the GEMM's column tile; tools/nn_cost.py sweeps it)
+    long nn_G = 0, nn_Gpad = 0;  // rows of the gallery; its rows on the device (G rounded up to the column tile, zero rows beyond G)
+    int nn_k = 0, nn_source = 0, nn_E = 0;
+    int nn_nlabels = 0;          // 0: no labels, no vote
+    float nn_T = 0.0f;
+    int nn_cap = 0;              // images the buffers hold (= the images one pass takes)
+    int nn_n = 0;                // images of the last forward made with a gallery set (0: none since vitx_nn_set)
+    void *nn_gallery = nullptr;  // [nn_Gpad][nn_E] operand type
+    int *nn_labels = nullptr;    // [nn_G]
+    float *nn_zero = nullptr;    // [kNnChunk] zeros: the chunk GEMMs' bias
+    float *nn_out = nullptr;     // [nn_cap][nn_k] {f32 score, i32 index}
+    float *nn_vote = nullptr;    // [nn_cap][nn_nlabels]
+    std::vector<void *> nn_a;    // per slice: [round_up(nn_cap, tm)][nn_E] operand type, the normalised queries (the GEMMs' A rows)
+    std::vector<float *> nn_acc; // per slice: [round_up(nn_cap, tm)][kNnChunk] f32, one chunk's scores
+    std::vector<void *> nn_state;// per slice: the running top-k (nn_state_bytes)
+    size_t nn_scratch = 0;       // bytes of nn_acc + nn_state over all slices
+    bool nn_on() const { return nn_G != 0; }
+    int nn_width(int source) const {       // E of a source: the logits row, or the head GEMM's operand row Z
+        if (source == VITX_NN_LOGITS) return C;
+        return source == VITX_NN_EMBED ? (pool ? 2 * D : D) : 0;
+    }
+    void nn_free() {
+        for (void *p : nn_a) if (p) (void)hipFree(p);
+        for (float *p : nn_acc) if (p) (void)hipFree(p);
+        for (void *p : nn_state) if (p) (void)hipFree(p);
+        nn_a.clear(); nn_acc.clear(); nn_state.clear();
+        for (void **p : {&nn_gallery, (void **)&nn_labels, (void **)&nn_zero, (void **)&nn_out, (void **)&nn_vote}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+        nn_G = nn_Gpad = 0; nn_k = nn_source = nn_E = nn_nlabels = nn_cap = nn_n = 0; nn_T = 0.0f; nn_scratch = 0;
+    }
     // hipGraph cache of the single-stream (small-batch) forward, opt-in (vitx_ctx_options::graph).  Key = (images, batch, outputs): the graph
     // bakes the pointers in.  An entry is captured the second time in a row its key is seen (one-off calls are never captured).
     // Measured (profiles/r02f/hipgraph_small_batch.txt): replaying the ~100 dependent launches as a graph takes the enqueue work off
@@ -236,6 +266,7 @@ struct vitx_ctx {
         attn_free();
         feat_free();
         zs_free();
+        nn_free();
         for (void *p : allocs) (void)hipFree(p);
         if (stream) (void)hipStreamDestroy(stream);
     }

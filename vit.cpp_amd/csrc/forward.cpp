@@ -186,6 +186,33 @@ struct SliceForward {
         HIP_TRY(launch_zs_score(acc, Kpad, out, out + K, 2L * K, n, K, c->zs_kind, c->zs_scale, c->zs_bias, st));
         return VITX_OK;
     }
+    // Nearest neighbours in a gallery (vitx_nn_set), after the head: the query rows of this sub-batch -- the f32 logits rows, or the head GEMM's
+    // operand rows Z -- become unit rows in the operand type (zero-shot's rule); then the gallery passes by in chunks of kNnChunk rows, each one
+    // dispatcher GEMM into the slice's score scratch (its own base pointer into the gallery: only a chunk has to fit the GEMM's operand window) and
+    // one selection launch that merges the chunk's real columns into the slice's running state; the last launch writes the k best (and the vote)
+    // at the images' global positions.  2 ceil(G / Gc) + 2 launches.
+    int nearest(const float *lg, long ldl) {
+        int rc;
+        const int E = c->nn_E, k = c->nn_k, Mz = round_up(n, tm), Gc = vitx_ctx::kNnChunk;
+        const long G = c->nn_G;
+        const size_t si = &sl - &c->slices[0];
+        void *a = c->nn_a[si]; float *acc = c->nn_acc[si]; void *state = c->nn_state[si];
+        {
+            ProfScope ps(c, st, PC_NN, 0, (double)n * E * (c->nn_source == VITX_NN_LOGITS ? 4 : eb) + (double)Mz * E * eb);
+            if (c->nn_source == VITX_NN_LOGITS) HIP_TRY(launch_zs_embed(dt, lg, ldl, a, n, Mz, E, st));
+            else HIP_TRY(launch_zs_embed_operand(dt, sl.Z, E, a, n, Mz, E, st));
+        }
+        for (long g0 = 0; g0 < G; g0 += Gc) {
+            const int cols = (int)std::min<long>(Gc, G - g0);
+            if ((rc = gemm(c, st, PC_NN, EPI_BIAS_F32, dense_gemm(a, (const char *)c->nn_gallery + (size_t)g0 * E * 2, c->nn_zero, acc, Mz, n, cols, round_up(cols, tn), E, Gc)))) return rc;
+            ProfScope ps(c, st, PC_NN, 0, (double)n * cols * 4);
+            HIP_TRY(launch_nn_select(acc, Gc, n, cols, g0, state, k, g0 == 0, st));
+        }
+        ProfScope ps(c, st, PC_NN, 0, (double)n * kNnSegs * k * 8 + (double)n * (k * 8 + c->nn_nlabels * 4));
+        HIP_TRY(launch_nn_finish(state, n, k, c->nn_labels, c->nn_nlabels, c->nn_T, c->nn_out + (size_t)first_img * k * 2,
+                                 c->nn_vote ? c->nn_vote + (size_t)first_img * c->nn_nlabels : nullptr, st));
+        return VITX_OK;
+    }
     // Quantised matrices (block form in HBM): a q4_0 GEMM with few rows expands the blocks in its own LDS-fill path; everything else
     // is expanded just in time, one launch per layer, into the slice's scratch and then streamed by the wide-tile kernels.
     bool fused_ok(const QuantW &q, int rows) const { return q.blocks && q.type == T_Q4_0 && rows <= c->q4_fused_rows && rows % 128 == 0 && q.n_pad % 128 == 0 && q.K % 64 == 0; }
@@ -370,6 +397,7 @@ struct SliceForward {
         }
         // zero-shot logits and probabilities of a context with a bank: from the pooled embedding e (attention-pooling head), else from the logits row
         if (c->zs_on() && (rc = c->map ? zeroshot(sl.Xc, D) : zeroshot(lg, ldl))) return rc;
+        if (c->nn_on() && (rc = nearest(lg, ldl))) return rc;
         if (fuse && c->ln_fb_host) HIP_TRY(hipMemcpyAsync(c->ln_fb_host + (&sl - &c->slices[0]), sl.ln_todo + sl.ln_blocks, sizeof(unsigned), hipMemcpyDeviceToHost, st));       // fall-back budget
         return VITX_OK;
     }
@@ -547,7 +575,7 @@ static int forward_pass(vitx_ctx *c, const void *d_imgs, int n, void *d_probs, v
     const bool serial = c->prof_on;
     const int ns = (c->nslices > 1 && n >= 8 * c->nslices) ? c->nslices : 1;
     if (ns == 1) {
-        if (c->graphs_on && !c->prof_on && c->trace_ids.empty() && !c->attn_on() && !c->feat_on() && !c->zs_on()) {
+        if (c->graphs_on && !c->prof_on && c->trace_ids.empty() && !c->attn_on() && !c->feat_on() && !c->zs_on() && !c->nn_on()) {
             bool done = false;
             const int rc = forward_graph(c, st, d_imgs, n, d_probs, d_logits, &done);
             if (rc != VITX_OK || done) return rc;
@@ -601,6 +629,7 @@ int vitx_forward_device(vitx_ctx *c, const void *d_imgs, int n, void *d_probs, v
     if (n > c->call_limit && c->attn_on()) { set_error("vitx_forward_device: attention maps take one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
     if (n > c->call_limit && c->feat_on()) { set_error("vitx_forward_device: features take one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
     if (n > c->call_limit && c->zs_on()) { set_error("vitx_forward_device: zero-shot classification takes one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
+    if (n > c->call_limit && c->nn_on()) { set_error("vitx_forward_device: nearest neighbours take one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
     for (int i0 = 0; i0 < n; i0 += c->call_limit) {
         const int ni = std::min(c->call_limit, n - i0);
         const int rc = forward_pass(c, (const float *)d_imgs + (size_t)i0 * c->img_floats(), ni, (float *)d_probs + (size_t)i0 * c->R * c->C,
@@ -610,6 +639,7 @@ int vitx_forward_device(vitx_ctx *c, const void *d_imgs, int n, void *d_probs, v
     if (c->attn_on()) c->attn_n = n;
     if (c->feat_on()) c->feat_n = n;
     if (c->zs_on()) c->zs_n = n;
+    if (c->nn_on()) c->nn_n = n;
     return VITX_OK;
 }
 int vitx_forward(vitx_ctx *c, const float *imgs, int n, float *probs, float *logits) {

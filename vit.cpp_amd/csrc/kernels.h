@@ -215,6 +215,19 @@ hipError_t launch_zs_embed(int dtype, const float *z, long z_stride, void *a, in
 // zs_embed with an f32 result, unrounded (VITX_TEXT_L2): a[i][0 .. E) = z / sqrt(sum z^2), dense rows of E floats, a != z; the same kernel text, one more instantiation
 hipError_t launch_zs_embed_f32(const float *z, long z_stride, float *a, int n, int E, hipStream_t stream);
 hipError_t launch_zs_score(const float *acc, int ld, float *probs, float *logits, long out_img_stride, int n, int K, int kind, float scale, float bias, hipStream_t stream);
+// zs_embed on rows that are already in the operand type (the head GEMM's operand Z; z_stride in elements, a multiple of 4): every element widened to
+// f32 first, then the same kernel text -- one more instantiation, not a second rule
+hipError_t launch_zs_embed_operand(int dtype, const void *z, long z_stride, void *a, int n, int m_pad, int E, hipStream_t stream);
+// Nearest neighbours in a gallery (nn_select.hip; include/vitx.h "nearest neighbours in a gallery"): the streaming selection around the chunk GEMMs.
+//   nn_select: scores [n][ld] f32, columns 0 .. cols of one chunk (columns cols .. ld never read), column j = gallery row base_index + j (below 2^31)
+//              -> merged into state [n][kNnSegs][k] 64-bit keys (nn_state_bytes); first: the state is initialised by this launch, not read.
+//   nn_finish: state -> pairs [n][k] {f32 score, i32 index} best first (launch_topk's layout); labels != nullptr ([every index in the state] i32 in
+//              [0, n_labels)): also vote [n][n_labels] f32 with temperature T > 0.
+// 1 <= k <= kNnMaxK.  hipErrorInvalidValue for a shape outside that.
+constexpr int kNnSegs = 8, kNnMaxK = 64;
+size_t nn_state_bytes(int n, int k);
+hipError_t launch_nn_select(const float *scores, long ld, int n, int cols, long base_index, void *state, int k, bool first, hipStream_t stream);
+hipError_t launch_nn_finish(const void *state, int n, int k, const int *labels, int n_labels, float temperature, void *pairs, float *vote, hipStream_t stream);
 // The text tower (include/vitx.h "the text tower"; text_embed.hip, attention_text.hip).
 //   text_embed: X[i][t][:] (f32) = f32(tok[ids[i * T + t]][:]) + pos[t][:]; tok [V][D] f16 (table_f16) or f32, ids checked by the caller; D % 8 == 0
 //   text_pool:  z[i][:] (dtype) = RNE(final LayerNorm of X row i * T + pooled[i]), LnRow's bits; rows n .. m_pad zeros; every width of VITX_LN_WIDTHS

@@ -356,6 +356,51 @@ int vitx_op_zeroshot(int dtype, const void *d_z, long z_stride, const void *d_ba
     return op_rc("vitx_op_zeroshot", e, VITX_ERR_UNSUPPORTED);
 }
 
+// Nearest neighbours on the caller's buffers (include/vitx.h "nearest neighbours in a gallery").  Every argument check comes before the first device
+// call; all of them only enqueue.
+size_t vitx_op_nn_state_bytes(int n, int k) { return nn_state_bytes(n, k); }
+int vitx_op_nn_select(const void *d_scores, long ld, int n, int cols, long base_index, void *d_state, int k, int first, void *stream) {
+    if (!d_scores || !d_state || n <= 0 || cols <= 0 || ld < cols || k < 1 || base_index < 0 || (uintptr_t)d_scores % 4 || (uintptr_t)d_state % 8) { set_error("vitx_op_nn_select: invalid argument"); return VITX_ERR_ARG; }
+    if (k > kNnMaxK) { set_error("vitx_op_nn_select: k = %d above %d", k, kNnMaxK); return VITX_ERR_UNSUPPORTED; }
+    if (base_index + cols > 0x7fffffffL) { set_error("vitx_op_nn_select: gallery indices are 31 bits (base_index %ld + %d columns)", base_index, cols); return VITX_ERR_UNSUPPORTED; }
+    return op_rc("vitx_op_nn_select", launch_nn_select((const float *)d_scores, ld, n, cols, base_index, d_state, k, first != 0, (hipStream_t)stream), VITX_ERR_ARG);
+}
+int vitx_op_nn_finish(const void *d_state, int n, int k, const void *d_labels, int n_labels, float temperature, void *d_pairs, void *d_vote, void *stream) {
+    if (!d_state || !d_pairs || n <= 0 || k < 1 || (uintptr_t)d_state % 8 || (uintptr_t)d_pairs % 4) { set_error("vitx_op_nn_finish: invalid argument"); return VITX_ERR_ARG; }
+    if (d_labels && (n_labels < 1 || !d_vote || !(std::isfinite(temperature) && temperature > 0.0f))) { set_error("vitx_op_nn_finish: labels need n_labels >= 1, d_vote and a finite positive temperature"); return VITX_ERR_ARG; }
+    if (k > kNnMaxK) { set_error("vitx_op_nn_finish: k = %d above %d", k, kNnMaxK); return VITX_ERR_UNSUPPORTED; }
+    return op_rc("vitx_op_nn_finish", launch_nn_finish(d_state, n, k, (const int *)d_labels, n_labels, temperature, d_pairs, (float *)d_vote, (hipStream_t)stream), VITX_ERR_ARG);
+}
+// The launches the forward of a context with a gallery makes (SliceForward::nearest) without the vote: the operand rows, per chunk the GEMM through
+// the dispatcher and the selection, then the final merge.  The GEMMs' bias is the row of zeros the call writes behind the score rows.
+int vitx_op_nn(int dtype, const void *d_z, long z_stride, int z_is_operand, int n, const void *d_gallery, long G, int E, int k, int chunk,
+               void *d_a_scratch, void *d_acc_scratch, void *d_state, void *d_pairs, void *stream) {
+    if (!d_z || !d_gallery || !d_a_scratch || !d_acc_scratch || !d_state || !d_pairs || n <= 0 || G <= 0 || E <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_nn: invalid argument"); return VITX_ERR_ARG; }
+    if (k < 1 || k > G) { set_error("vitx_op_nn: k = %d outside 1 .. G = %ld", k, G); return VITX_ERR_ARG; }
+    if (chunk <= 0 || chunk % gemm_tile_n()) { set_error("vitx_op_nn: chunk = %d is not a positive multiple of %d", chunk, gemm_tile_n()); return VITX_ERR_ARG; }
+    if (z_stride < E || z_stride % 4) { set_error("vitx_op_nn: z_stride %ld must be at least E = %d and a multiple of 4 elements", z_stride, E); return VITX_ERR_ARG; }
+    for (const void *p : {d_z, d_gallery, (const void *)d_a_scratch, (const void *)d_acc_scratch, (const void *)d_state})
+        if ((uintptr_t)p % 16) { set_error("vitx_op_nn: d_z, d_gallery, the scratch buffers and the state must be 16-byte aligned"); return VITX_ERR_ARG; }
+    if (k > kNnMaxK) { set_error("vitx_op_nn: k = %d above %d", k, kNnMaxK); return VITX_ERR_UNSUPPORTED; }
+    if (E % 64) { set_error("vitx_op_nn: E = %d is not a multiple of 64 (the GEMMs' K step)", E); return VITX_ERR_UNSUPPORTED; }
+    if (G >= 0x7fffffffL - 127) { set_error("vitx_op_nn: %ld gallery rows: indices are 31 bits", G); return VITX_ERR_UNSUPPORTED; }
+    if ((size_t)chunk * E * 2 > 0xf0000000u) { set_error("vitx_op_nn: a chunk of %d rows of width %d exceeds the GEMM's 32-bit operand window", chunk, E); return VITX_ERR_UNSUPPORTED; }
+    const Tuning *t = tuning_for_device(-1);
+    if (!t) { set_error("vitx_op_nn: kernel bring-up failed"); return VITX_ERR_HIP; }
+    const int M = round_up(n, gemm_tile_m());
+    hipStream_t st = (hipStream_t)stream;
+    float *acc = (float *)d_acc_scratch, *zero = acc + (size_t)M * chunk;
+    hipError_t e = hipMemsetAsync(zero, 0, (size_t)chunk * 4, st);
+    if (e == hipSuccess) e = z_is_operand ? launch_zs_embed_operand(dtype, d_z, z_stride, d_a_scratch, n, M, E, st) : launch_zs_embed(dtype, (const float *)d_z, z_stride, d_a_scratch, n, M, E, st);
+    for (long g0 = 0; g0 < G && e == hipSuccess; g0 += chunk) {
+        const int cols = (int)std::min<long>(chunk, G - g0);
+        e = launch_gemm(*t, dtype, EPI_BIAS_F32, dense_gemm(d_a_scratch, (const char *)d_gallery + (size_t)g0 * E * 2, zero, acc, M, n, cols, round_up(cols, gemm_tile_n()), E, chunk), st);
+        if (e == hipSuccess) e = launch_nn_select(acc, chunk, n, cols, g0, d_state, k, g0 == 0, st);
+    }
+    if (e == hipSuccess) e = launch_nn_finish(d_state, n, k, nullptr, 0, 0.0f, d_pairs, nullptr, st);
+    return op_rc("vitx_op_nn", e, VITX_ERR_UNSUPPORTED);
+}
+
 // The text tower's three kernels on their own (include/vitx.h "the text tower").  Every argument check comes before the first device call.
 int vitx_op_text_embed(int table_f16, const void *d_tok, const void *d_pos, const void *d_ids, void *d_x, int n, int T, int D, void *stream) {
     if (!d_tok || !d_pos || !d_ids || !d_x || n <= 0 || T <= 0 || D <= 0 || D % 8) { set_error("vitx_op_text_embed: invalid argument (D %% 8 == 0)"); return VITX_ERR_ARG; }

@@ -251,4 +251,77 @@ int vitx_zeroshot_read(vitx_ctx *c, float *probs, float *logits, size_t n_floats
     return VITX_OK;
 }
 
+// Nearest neighbours: the gallery of a context (include/vitx.h).  Every argument check comes before the first device call.
+int vitx_nn_width(const vitx_ctx *c, int source) { return c ? c->nn_width(source) : 0; }
+int vitx_nn_set(vitx_ctx *c, const float *gallery, long G, int E, int k, int source, const int32_t *labels, int n_labels, float temperature) {
+    if (!c) return VITX_ERR_ARG;
+    const bool off = !gallery && G == 0;
+    if (!off) {
+        if (!gallery) { set_error("vitx_nn_set: NULL gallery with G = %ld", G); return VITX_ERR_ARG; }
+        if (source != VITX_NN_LOGITS && source != VITX_NN_EMBED) { set_error("vitx_nn_set: unknown source %d (0 logits, 1 embed)", source); return VITX_ERR_ARG; }
+        if (k < 1 || k > G) { set_error("vitx_nn_set: k = %d outside 1 .. G = %ld", k, G); return VITX_ERR_ARG; }
+        if (labels && n_labels < 1) { set_error("vitx_nn_set: labels with n_labels = %d", n_labels); return VITX_ERR_ARG; }
+        if (labels && !(std::isfinite(temperature) && temperature > 0.0f)) { set_error("vitx_nn_set: the vote's temperature must be finite and positive"); return VITX_ERR_ARG; }
+        if (c->R != 1) { set_error("vitx_nn_set: nearest neighbours are not available for ViTSTR contexts"); return VITX_ERR_UNSUPPORTED; }
+        if (E != c->nn_width(source)) { set_error("vitx_nn_set: the gallery's width %d is not this context's width %d of source %d", E, c->nn_width(source), source); return VITX_ERR_ARG; }
+        if (k > kNnMaxK) { set_error("vitx_nn_set: k = %d above %d", k, kNnMaxK); return VITX_ERR_UNSUPPORTED; }
+        if (E % 64) { set_error("vitx_nn_set: the embedding width %d is not a multiple of 64 (the GEMMs' K step)", E); return VITX_ERR_UNSUPPORTED; }
+        if (G >= 0x7fffffffL - 127) { set_error("vitx_nn_set: %ld gallery rows: indices are 31 bits (at most 2^31 - 129 rows)", G); return VITX_ERR_UNSUPPORTED; }
+        if ((size_t)round_up(c->pass_cap(), c->tm) * vitx_ctx::kNnChunk * 4 > 0xf0000000u) {       // the chunk GEMM addresses its output inside a 32-bit byte window
+            set_error("vitx_nn_set: the score scratch of %d images exceeds the chunk GEMM's 32-bit window (at most %d images per pass)", c->pass_cap(), (int)(0xf0000000u / 4 / vitx_ctx::kNnChunk / c->tm * c->tm));
+            return VITX_ERR_UNSUPPORTED;
+        }
+        for (size_t i = 0, nb = (size_t)G * E; i < nb; ++i)
+            if (!std::isfinite(gallery[i])) { set_error("vitx_nn_set: gallery entry [%zu][%zu] is not finite", i / E, i % E); return VITX_ERR_ARG; }
+        if (labels) for (long g = 0; g < G; ++g)
+            if (labels[g] < 0 || labels[g] >= n_labels) { set_error("vitx_nn_set: label %d of gallery row %ld outside 0 .. %d", labels[g], g, n_labels - 1); return VITX_ERR_ARG; }
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());          // no forward in flight reads or writes the buffers about to be freed
+    c->nn_free();
+    if (off) return VITX_OK;
+    constexpr int Gc = vitx_ctx::kNnChunk;
+    const long Gpad = (G + c->tn - 1) / c->tn * c->tn;
+    const int cap = c->pass_cap();
+    const size_t rows = (size_t)round_up(cap, c->tm), state_bytes = nn_state_bytes((int)rows, k);
+    auto alloc = [](void **p, size_t bytes) { if (hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; } return true; };
+    bool ok = alloc(&c->nn_gallery, (size_t)Gpad * E * 2) && alloc((void **)&c->nn_zero, (size_t)Gc * 4) && alloc((void **)&c->nn_out, (size_t)cap * k * 8);
+    if (ok && labels) ok = alloc((void **)&c->nn_labels, (size_t)G * 4) && alloc((void **)&c->nn_vote, (size_t)cap * n_labels * 4);
+    c->nn_a.assign(c->nslices, nullptr); c->nn_acc.assign(c->nslices, nullptr); c->nn_state.assign(c->nslices, nullptr);
+    for (int i = 0; ok && i < c->nslices; ++i) ok = alloc(&c->nn_a[i], rows * E * 2) && alloc((void **)&c->nn_acc[i], rows * Gc * 4) && alloc(&c->nn_state[i], state_bytes);
+    if (!ok) { c->nn_free(); set_error("vitx_nn_set: cannot allocate the buffers for %ld gallery rows and %d images", G, cap); return VITX_ERR_NOMEM; }
+    // the gallery goes up in blocks of rows, rounded (RNE) to the operand type; the zero rows beyond G come from the memset
+    hipError_t e = hipMemset(c->nn_gallery, 0, (size_t)Gpad * E * 2);
+    if (e == hipSuccess) e = hipMemset(c->nn_zero, 0, (size_t)Gc * 4);
+    for (long g0 = 0; g0 < G && e == hipSuccess; g0 += 65536) {
+        const int nr = (int)std::min<long>(65536, G - g0);
+        const std::vector<uint16_t> hb = operand_matrix_host(c->dtype, gallery + (size_t)g0 * E, nullptr, nr, E, nr, E, 0, 0);
+        e = hipMemcpy((char *)c->nn_gallery + (size_t)g0 * E * 2, hb.data(), hb.size() * 2, hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess && labels) e = hipMemcpy(c->nn_labels, labels, (size_t)G * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { c->nn_free(); set_error("vitx_nn_set: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
+    c->nn_G = G; c->nn_Gpad = Gpad; c->nn_k = k; c->nn_source = source; c->nn_E = E; c->nn_nlabels = labels ? n_labels : 0; c->nn_T = labels ? temperature : 0.0f; c->nn_cap = cap;
+    c->nn_scratch = (size_t)c->nslices * (rows * Gc * 4 + state_bytes);
+    return VITX_OK;
+}
+long vitx_nn_rows(const vitx_ctx *c) { return c ? c->nn_G : 0; }
+int vitx_nn_k(const vitx_ctx *c) { return c ? c->nn_k : 0; }
+int vitx_nn_labels(const vitx_ctx *c) { return c ? c->nn_nlabels : 0; }
+int vitx_nn_images(const vitx_ctx *c) { return c ? c->nn_n : 0; }
+const void *vitx_nn_device(const vitx_ctx *c) { return c ? c->nn_out : nullptr; }
+size_t vitx_nn_scratch_bytes(const vitx_ctx *c) { return c ? c->nn_scratch : 0; }
+int vitx_nn_read(vitx_ctx *c, int32_t *idx, float *score, float *vote) {
+    if (!c || !idx || !score) return VITX_ERR_ARG;
+    const int n = c->nn_on() ? c->nn_n : 0, k = c->nn_k;
+    if (n == 0) { set_error("vitx_nn_read: no forward has run with a gallery set since vitx_nn_set"); return VITX_ERR_ARG; }
+    if (vote && !c->nn_nlabels) { set_error("vitx_nn_read: the gallery has no labels: there is no vote"); return VITX_ERR_ARG; }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy2D(score, 4, c->nn_out, 8, 4, (size_t)n * k, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy2D(idx, 4, c->nn_out + 1, 8, 4, (size_t)n * k, hipMemcpyDeviceToHost));
+    if (vote) HIP_TRY(hipMemcpy(vote, c->nn_vote, (size_t)n * c->nn_nlabels * 4, hipMemcpyDeviceToHost));
+    return VITX_OK;
+}
+
 }  // extern "C"

@@ -2,6 +2,7 @@
 #include "kernels.h"
 #include "epilogue16.h"
 #include "device_common.h"
+#include "topk_rank.h"
 
 namespace vitx {
 
@@ -43,11 +44,7 @@ hipError_t launch_softmax(int dtype, const float *logits, float *probs, int rows
 // a NaN, below -inf's) and an entry to rank << 32 | ~index, so with k <= cols every pass finds an entry and every class written lies
 // in [0, cols) and is written once -- also for a row of NaNs, which float comparisons alone would answer with no entry at all.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned topk_rank(float v) {
-    if (v != v) return 0u;
-    const unsigned b = __builtin_bit_cast(unsigned, v + 0.0f);            // -0 + 0 = +0: the two zeros share a rank
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
+// (topk_rank: topk_rank.h, shared with nn_select.hip)
 __global__ __launch_bounds__(256) void topk_kernel(const float *__restrict__ probs, int rows, int cols, int k, float *__restrict__ out) {
     const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;

@@ -233,6 +233,39 @@ int vit_zeroshot_batch(const vit_model &model, vit_state &state, const image_f32
     return 0;
 }
 
+// No counterpart in the reference: the nearest gallery rows of n images, and the vote of their labels (include/vitx.h "nearest neighbours in a gallery")
+int vit_nn_batch(const vit_model &model, vit_state &state, const image_f32 *imgs, int n, const vit_nn_gallery &g, std::vector<vit_nn_result> &out) {
+    out.clear();
+    const bool voting = !g.labels.empty();
+    if (!model.handle || !imgs || n <= 0 || g.G <= 0 || g.E <= 0 || g.embeds.size() != (size_t)g.G * g.E || (voting && g.labels.size() != (size_t)g.G)) { fprintf(stderr, "%s: invalid argument\n", __func__); return 1; }
+    if (vitx_model_seq_len(model.handle) > 0) { fprintf(stderr, "%s: this is a ViTSTR model: it has no image embedding\n", __func__); return 1; }
+    const int C = model.hparams.num_classes, k = g.k;
+    int Sh = 0, Sw = 0;
+    if (!state_shape(model, state, Sh, Sw, __func__)) return 1;
+    const size_t img_floats = (size_t)3 * Sh * Sw;
+    if (const int i = first_bad_image(imgs, n, Sh, Sw); i >= 0) {
+        fprintf(stderr, "%s: image %d is %dx%d, this state expects %dx%d\n", __func__, i, imgs[i].nx, imgs[i].ny, Sw, Sh);
+        return 1;
+    }
+    if (ensure_ctx(model, state, n) != VITX_OK) { fprintf(stderr, "%s: failed to create the context: %s\n", __func__, vitx_last_error()); return 1; }
+    if (vitx_nn_set(state.ctx, g.embeds.data(), g.G, g.E, k, g.source, voting ? g.labels.data() : nullptr, g.n_labels, g.temperature) != VITX_OK) { fprintf(stderr, "%s: %s\n", __func__, vitx_last_error()); return 1; }
+    std::vector<float> batch((size_t)n * img_floats);
+    for (int i = 0; i < n; ++i) std::copy(imgs[i].data.begin(), imgs[i].data.end(), batch.begin() + (size_t)i * img_floats);
+    state.prediction.resize((size_t)n * C);
+    std::vector<int32_t> idx((size_t)n * k); std::vector<float> score((size_t)n * k), vote(voting ? (size_t)n * g.n_labels : 0);
+    const bool ok = vitx_forward(state.ctx, batch.data(), n, state.prediction.data(), nullptr) == VITX_OK &&
+                    vitx_nn_read(state.ctx, idx.data(), score.data(), voting ? vote.data() : nullptr) == VITX_OK;
+    if (!ok) fprintf(stderr, "%s: failed to encode image: %s\n", __func__, vitx_last_error());
+    (void)vitx_nn_set(state.ctx, nullptr, 0, 0, 0, 0, nullptr, 0, 0.0f);
+    if (!ok) return 1;
+    out.resize(n);
+    for (int i = 0; i < n; ++i) {
+        for (int j = 0; j < k; ++j) out[i].neighbours.push_back(std::make_pair(score[(size_t)i * k + j], (int)idx[(size_t)i * k + j]));
+        if (voting) out[i].vote.assign(vote.begin() + (size_t)i * g.n_labels, vote.begin() + (size_t)(i + 1) * g.n_labels);
+    }
+    return 0;
+}
+
 // No counterpart in the reference: the text embeddings of n tokenised prompts (include/vitx.h "the text tower")
 int vit_text_embed_batch(const vit_model &model, vit_text_state &state, const int32_t *ids, int n, int flags, std::vector<std::vector<float>> &out) {
     out.clear();

@@ -20,8 +20,13 @@ namespace {
 // (T16 = float: the same rule with the quotient stored as it is -- VITX_TEXT_L2 of a text context, launch_zs_embed_f32)
 template <typename T16> struct ZsVec { typedef typename Elem<T16>::v4 v4; };
 template <> struct ZsVec<float> { typedef f32x4 v4; };
-template <typename T16>
-__global__ __launch_bounds__(256) void zs_embed_kernel(const float *__restrict__ z, long z_stride, T16 *__restrict__ a, int n, int m_pad, int E) {
+// (Tin = the type z is read in: float, or -- launch_zs_embed_operand -- an operand type, every element widened to f32 as it is loaded)
+template <typename Tin> __device__ __forceinline__ f32x4 zs_load4(const Tin *p) {
+    if constexpr (std::is_same<Tin, float>::value) return *(const f32x4 *)p;
+    else { const typename Elem<Tin>::v4 x = *(const typename Elem<Tin>::v4 *)p; return f32x4{(float)x[0], (float)x[1], (float)x[2], (float)x[3]}; }
+}
+template <typename T16, typename Tin = float>
+__global__ __launch_bounds__(256) void zs_embed_kernel(const Tin *__restrict__ z, long z_stride, T16 *__restrict__ a, int n, int m_pad, int E) {
     typedef typename ZsVec<T16>::v4 v4;
     const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= m_pad) return;
@@ -31,10 +36,10 @@ __global__ __launch_bounds__(256) void zs_embed_kernel(const float *__restrict__
         for (int v = lane; v < nv; v += 64) *(v4 *)(ar + 4 * v) = v4{(T16)0.0f, (T16)0.0f, (T16)0.0f, (T16)0.0f};
         return;
     }
-    const float *zr = z + (size_t)row * z_stride;
+    const Tin *zr = z + (size_t)row * z_stride;
     float ss = 0.0f;
     for (int v = lane; v < nv; v += 64) {
-        const f32x4 x = *(const f32x4 *)(zr + 4 * v);
+        const f32x4 x = zs_load4(zr + 4 * v);
 #pragma unroll
         for (int e = 0; e < 4; ++e) ss += x[e] * x[e];
     }
@@ -42,7 +47,7 @@ __global__ __launch_bounds__(256) void zs_embed_kernel(const float *__restrict__
     for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
     const float nrm = sqrtf(ss);
     for (int v = lane; v < nv; v += 64) {
-        f32x4 x = *(const f32x4 *)(zr + 4 * v);       // the row again: it is a few KiB and still in the cache
+        f32x4 x = zs_load4(zr + 4 * v);       // the row again: it is a few KiB and still in the cache
         if (nrm > 0.0f) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) x[e] = x[e] / nrm;
@@ -109,6 +114,14 @@ hipError_t launch_zs_embed(int dtype, const float *z, long z_stride, void *a, in
     const dim3 grid((m_pad + 3) / 4), blk(256);
     if (dtype == DT_F16) hipLaunchKernelGGL(zs_embed_kernel<_Float16>, grid, blk, 0, stream, z, z_stride, (_Float16 *)a, n, m_pad, E);
     else hipLaunchKernelGGL(zs_embed_kernel<__bf16>, grid, blk, 0, stream, z, z_stride, (__bf16 *)a, n, m_pad, E);
+    return hipGetLastError();
+}
+
+hipError_t launch_zs_embed_operand(int dtype, const void *z, long z_stride, void *a, int n, int m_pad, int E, hipStream_t stream) {
+    if (n <= 0 || m_pad < n || E <= 0 || E % 64 || z_stride < E || z_stride % 4 || z == a) return hipErrorInvalidValue;
+    const dim3 grid((m_pad + 3) / 4), blk(256);
+    if (dtype == DT_F16) hipLaunchKernelGGL((zs_embed_kernel<_Float16, _Float16>), grid, blk, 0, stream, (const _Float16 *)z, z_stride, (_Float16 *)a, n, m_pad, E);
+    else hipLaunchKernelGGL((zs_embed_kernel<__bf16, __bf16>), grid, blk, 0, stream, (const __bf16 *)z, z_stride, (__bf16 *)a, n, m_pad, E);
     return hipGetLastError();
 }
 

@@ -10,7 +10,8 @@
 //     descending and prints the top-k lines to stdout (vit.cpp:1043-1067);
 //   * vit_predict_batch is NEW (the reference has no batched call): n images per launch;
 //   * vit_embed / vit_embed_batch are NEW (the reference returns class probabilities only): the image embedding;
-//   * vit_zeroshot_batch is NEW: zero-shot classes of a CLIP / SigLIP file against a bank of text embeddings.
+//   * vit_zeroshot_batch is NEW: zero-shot classes of a CLIP / SigLIP file against a bank of text embeddings;
+//   * vit_nn_batch is NEW: the nearest rows of a gallery of embeddings, and the weighted k-NN vote of their labels.
 // Everything below is a thin wrapper over the C ABI in include/vitx.h.
 #pragma once
 
@@ -123,6 +124,24 @@ struct vit_zeroshot_bank {
 // returning; state.prediction holds the file's own class "probabilities" of the same forward.  0 ok / 1 failure.
 int vit_zeroshot_batch(const vit_model &model, vit_state &state, const image_f32 *imgs, int n, const vit_zeroshot_bank &bank,
                        std::vector<std::vector<std::pair<float, int>>> &out, int topk = 5);
+// NEW, no counterpart in the reference: nearest neighbours in a gallery of embeddings (include/vitx.h "nearest neighbours in a gallery") -- retrieval,
+// and with labels the temperature-weighted k-NN vote a headless DINOv2 / DINOv3 backbone is evaluated with.
+struct vit_nn_gallery {
+    std::vector<float> embeds;            // [G][E], rows of unit length (the engine does not renormalise them); E = vitx_nn_width of `source`
+    long G = 0;
+    int E = 0, k = 5;
+    int source = VITX_NN_EMBED;           // VITX_NN_EMBED (the head's operand row) or VITX_NN_LOGITS (the logits row: image_embeds of a CLIP file)
+    std::vector<int32_t> labels;          // G labels in [0, n_labels), or empty: no vote
+    int n_labels = 0;
+    float temperature = 0.07f;
+};
+struct vit_nn_result {
+    std::vector<std::pair<float, int>> neighbours;   // k (score, gallery row) pairs, best first
+    std::vector<float> vote;                         // n_labels weights that sum to 1, or empty
+};
+// out[i] = image i's result.  The gallery is set for this call and switched off again before returning; state.prediction holds the file's own class
+// probabilities of the same forward.  0 ok / 1 failure.
+int vit_nn_batch(const vit_model &model, vit_state &state, const image_f32 *imgs, int n, const vit_nn_gallery &gallery, std::vector<vit_nn_result> &out);
 // NEW, no counterpart in the reference: the text tower of a CLIP / SigLIP checkpoint (include/vitx.h "the text tower").  `model` is a text-tower
 // file (vitx_model_kind == VITX_KIND_TEXT; hparams.img_size is its context length T, hparams.num_classes its embedding width E).  ids: n
 // tokenised prompts [n][T] -- there is no tokenizer in the engine; out[i] = prompt i's E floats; flags 0 or VITX_TEXT_L2.  0 ok / 1 failure.
