@@ -910,6 +910,70 @@ size_t vitx_op_nn_state_bytes(int n, int k);
 int vitx_op_nn(int dtype, const void *d_z, long z_stride, int z_is_operand, int n, const void *d_gallery /* dtype [G_pad][E] */, long G, int E, int k, int chunk,
                void *d_a_scratch, void *d_acc_scratch /* [n_pad + 1][chunk] */, void *d_state, void *d_pairs, void *stream);
 
+/* ---- dense prediction: a linear head over the patch tokens, label maps on the device --------- */
+/* An opt-in output of the forward, in the manner of the bank and the gallery, with one result per PIXEL.  A context is given a linear HEAD over its
+ * patch tokens (the form DINOv2's segmentation heads are published in: a 1 x 1 convolution over the final-norm tokens of the last layer, or of four
+ * layers concatenated); every forward then also writes, per image, an [out_h][out_w] u8 label map and -- optionally -- the winner's score and the
+ * patch-level logits.  Nothing else the forward writes changes; with no head nothing is launched or allocated.  For one image with grid gh x gw,
+ * Np = gh gw patches, first patch row T, and the selected layers l_1 < ... < l_m (1 <= m <= 4; mask 0 = the last layer):
+ *   operand      A[t] = RNE_dtype(F_{l_1}[T + t]) ‖ ... ‖ RNE_dtype(F_{l_m}[T + t]), width Dc = m D; F_l is the F_l of the features section above (the
+ *     final norm applied, the engine's own statistics): RNE of the VITX_FEAT_TOKENS feature of the same forward, bit for bit.  Written by the stand-alone
+ *     LayerNorm as each selected layer finishes, into compact rows [n Np][Dc] of the sub-batch (zero rows up to the GEMM's row tile).  dtype = the
+ *     context's operand type; a VITX_MXFP8 context uses bf16, as its head does.  A selected last layer makes the context evaluate EVERY row of the last
+ *     layer while the head is set (the rule of VITX_FEAT_TOKENS, with its consequence: probabilities and logits are those of a last_layer_all_rows = 1
+ *     context, bit for bit).
+ *   patch logits c[t][k] = bias_k + sum_i A[t][i] RNE_dtype(W[k][i]), f32 accumulation on the MFMA, through the head's GEMM dispatcher into [M_pad][K_pad]
+ *     f32; K_pad = K rounded up to 128, weight rows beyond K are zero.  Profile class "dense".
+ *   label map    the K planes c[.][k] resampled from gh x gw to out_h x out_w as F.interpolate(mode="bilinear", align_corners=False) does (mmseg's
+ *     resize), then the arg-max over k < K.  Per axis (g source cells, out target cells, o the target index), all f32:
+ *       scale = (float)g / (float)out (IEEE division);  s = ((float)o + 0.5f) * scale - 0.5f (one multiply, one subtract), clamped below at 0;
+ *       i0 = (int)s;  i1 = i0 + (i0 < g - 1);  l = s - (float)i0;  h = 1.0f - l.
+ *     Value, with a, b the taps (y0, x0), (y0, x1) and c, d the taps (y1, x0), (y1, x1):  top = hx a + lx b;  bot = hx c + lx d;  v = hy top + ly bot;
+ *     every product and every sum rounded on its own, no FMA contraction (so 0 * inf is a NaN, as written).  The winner is the first entry of
+ *     vitx_topk's total order: value descending, then class index ascending; +0 and -0 tie; a NaN ranks last (a pixel of NaNs only gets class 0).
+ *     label[y][x] u8 = the winner;  VITX_DENSE_SCORE: score[y][x] f32 = the winner's v bit for bit (a NaN as the quiet NaN 0x7fc00000: the payload of
+ *     a computed NaN is the processor's choice);  VITX_DENSE_LOGITS: the patch logits [Np][K] f32 are kept for vitx_dense_read.
+ *     The weights and the value are ONE definition (csrc/dense_resample.h) for the device kernel and for vitx_dense_labels_host: the same bits on any data.
+ * Determinism: an image's outputs are the same bits at any batch size, position in the batch, sub-batch cut and stream count; the forward's
+ *   probabilities and logits are the bits of the same context with last_layer_all_rows = 1 and no head (of the same context, when the last layer is
+ *   not selected); a bank, a gallery and a dense head may all be set, none changes another.
+ * vitx_dense_set: W host [K][Dc] f32, bias [K] or NULL (zeros); uploads W rounded (RNE) to the operand type and padded, allocates per sub-batch slice
+ *   the operand rows and the logit scratch (vitx_dense_scratch_bytes) and the output buffers for the images one pass takes; synchronises the device.
+ *   Setting again replaces the head; W NULL and K 0 turn the output off and free everything.  out_h = out_w = 0: the context's own img_h x img_w.
+ *   VITX_ERR_ARG: NULL W with K > 0; K < 1; Dc != popcount(mask) D; mask bits at or beyond L, or more than 4 of them; a W or bias entry that is not
+ *     finite; unknown flags; a negative output side, or one side 0.  VITX_ERR_UNSUPPORTED: K > 256; a ViTSTR context; out_h < gh, out_w < gw or either
+ *     above 8192 (upsampling only); a pass whose operand rows capacity Np Dc 2 or logit rows capacity Np K_pad 4 leave the GEMMs' 32-bit byte window
+ *     (0xf0000000), or of more than 65535 images.  VITX_ERR_NOMEM: an allocation fails (the head is then off).  All but the last are raised before any
+ *     device call.
+ * While a head is set, a forward of more than one pass is VITX_ERR_ARG and forwards do not use the hipGraph cache; profiling reports the m operand
+ *   launches, the GEMM and the label kernel of a sub-batch as class "dense".  vitx_group_* has no dense head.
+ * vitx_dense_read: synchronises and copies the last such forward's labels [n][out_h][out_w] and, unless NULL, score (VITX_DENSE_SCORE) and logits
+ *   [n][Np][K] (VITX_DENSE_LOGITS); VITX_ERR_ARG before any such forward or for an output the flags did not ask for.  vitx_dense_device: the labels
+ *   on the device, [capacity][out_h][out_w] u8, NULL while off.
+ * The kernel on its own (device pointers; only enqueues; every check before any device call):
+ *   vitx_op_dense_labels: d_logits [n gh gw][ld] f32 (image, then patch in raster order; columns K .. ld are never compared: they may hold anything)
+ *     -> d_labels [n][out_h][out_w] u8 and, unless NULL, d_score [n][..][..] f32.  VITX_ERR_ARG: NULL d_logits or d_labels, n, gh, gw, K < 1, d_logits
+ *     off a 16-byte or d_score off a 4-byte boundary, ld below K rounded up to 4 or no multiple of 4; VITX_ERR_UNSUPPORTED: K > 256, an output smaller
+ *     than the grid or above 8192, n > 65535.
+ *   vitx_dense_labels_host: the same arguments on host pointers, the same bits; makes no device call (any alignment).
+ *   vitx_op_dense: the forward's launches on a given operand: d_a [M_pad][Dc] in `dtype` with the n gh gw operand rows (M_pad = that rounded up to 256;
+ *     the call zeroes the rows beyond them), d_w [K_pad][Dc] `dtype` (zero rows beyond K), d_bias [K_pad] f32 -> d_logits [M_pad][K_pad] f32 (scratch and
+ *     output: the patch logits in its first K columns), then the labels as above.  VITX_ERR_ARG also for a dtype other than VITX_F16 / VITX_BF16 and any
+ *     pointer off a 16-byte boundary; VITX_ERR_UNSUPPORTED also for Dc not a multiple of 64 and rows beyond the GEMM's byte window. */
+enum vitx_dense_flags { VITX_DENSE_SCORE = 1, VITX_DENSE_LOGITS = 2 };
+int vitx_dense_set(vitx_ctx *c, const float *W /* host [K][Dc] */, const float *bias /* [K] or NULL */, int K, int Dc, uint64_t layer_mask,
+                   int out_h, int out_w, int flags);  /* W NULL && K == 0: off, frees */
+int vitx_dense_classes(const vitx_ctx *c);            /* K; 0 while off */
+int vitx_dense_shape(const vitx_ctx *c, int *out_h, int *out_w);   /* 0 x 0 while off */
+int vitx_dense_images(const vitx_ctx *c);
+int vitx_dense_read(vitx_ctx *c, uint8_t *labels /* [n][out_h][out_w] */, float *score /* or NULL */, float *logits /* [n][Np][K] or NULL */);
+const void *vitx_dense_device(const vitx_ctx *c);     /* [capacity][out_h][out_w] u8; NULL while off */
+size_t vitx_dense_scratch_bytes(const vitx_ctx *c);   /* device bytes of operand rows + logit scratch over all slices; 0 while off */
+int vitx_op_dense_labels(const void *d_logits /* [n gh gw][ld] f32 */, long ld, int n, int gh, int gw, int K, int out_h, int out_w, void *d_labels, void *d_score, void *stream);
+int vitx_dense_labels_host(const float *logits, long ld, int n, int gh, int gw, int K, int out_h, int out_w, uint8_t *labels, float *score);
+int vitx_op_dense(int dtype, void *d_a /* [M_pad][Dc] */, const void *d_w /* [K_pad][Dc] */, const void *d_bias /* [K_pad] f32 */, void *d_logits /* [M_pad][K_pad] f32 */,
+                  int n, int gh, int gw, int K, int Dc, int out_h, int out_w, void *d_labels, void *d_score, void *stream);
+
 /* ---- the text tower (CLIP, SigLIP): token ids in, text embeddings out ---------------
  * The text half of a contrastive checkpoint is a second model file in the same container.  Header: hidden_size D, num_hidden_layers L,
  * num_attention_heads H, num_classes = E (the width of the projected embedding), patch_size = 0 (THE mark of a text file: no image file

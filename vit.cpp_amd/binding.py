@@ -35,6 +35,7 @@ FEAT_CLS, FEAT_MEAN, FEAT_TOKENS, FEAT_L2 = 1, 2, 4, 8      # vitx_feat_enable f
 KIND_IMAGE, KIND_TEXT = 0, 1            # vitx_model_kind
 TEXT_L2 = 1                             # vitx_text_embed flag
 NN_LOGITS, NN_EMBED = 0, 1              # vitx_nn_source
+DENSE_SCORE, DENSE_LOGITS = 1, 2        # vitx_dense_flags
 POS_BICUBIC, POS_BICUBIC_AA = 0, 1      # vitx_pos_interp: F.interpolate(mode="bicubic") without / with antialias=True (include/vitx.h)
 
 EXPORTS = [
@@ -57,6 +58,8 @@ EXPORTS = [
     "vitx_zeroshot_set", "vitx_zeroshot_classes", "vitx_zeroshot_images", "vitx_zeroshot_read", "vitx_zeroshot_device", "vitx_zeroshot_max_classes", "vitx_op_zeroshot",
     "vitx_nn_width", "vitx_nn_set", "vitx_nn_rows", "vitx_nn_k", "vitx_nn_labels", "vitx_nn_images", "vitx_nn_read", "vitx_nn_device", "vitx_nn_scratch_bytes",
     "vitx_op_nn_select", "vitx_op_nn_finish", "vitx_op_nn_state_bytes", "vitx_op_nn",
+    "vitx_dense_set", "vitx_dense_classes", "vitx_dense_shape", "vitx_dense_images", "vitx_dense_read", "vitx_dense_device", "vitx_dense_scratch_bytes",
+    "vitx_op_dense_labels", "vitx_dense_labels_host", "vitx_op_dense",
     "vitx_model_kind", "vitx_model_text_info", "vitx_model_text_zs", "vitx_text_create", "vitx_text_free", "vitx_text_embed", "vitx_text_embed_device", "vitx_text_shares_weights", "vitx_text_check_ids",
     "vitx_op_text_embed", "vitx_op_text_pool", "vitx_op_attention_text", "vitx_op_attention_generic",
     "vitx_model_rope", "vitx_model_rope_table", "vitx_op_rope",
@@ -251,6 +254,17 @@ def lib():
             L.vitx_op_nn_finish.argtypes = [vp, ip, ip, vp, ip, C.c_float, vp, vp, vp]
             L.vitx_op_nn_state_bytes.restype = C.c_size_t; L.vitx_op_nn_state_bytes.argtypes = [ip, ip]
             L.vitx_op_nn.argtypes = [ip, vp, C.c_long, ip, ip, vp, C.c_long, ip, ip, ip, vp, vp, vp, vp, vp]
+        if hasattr(L, "vitx_dense_set"):
+            fp, u8p, intp = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int)
+            L.vitx_dense_set.argtypes = [vp, fp, fp, ip, ip, C.c_uint64, ip, ip, ip]
+            L.vitx_dense_classes.argtypes = [vp]; L.vitx_dense_images.argtypes = [vp]
+            L.vitx_dense_shape.argtypes = [vp, intp, intp]
+            L.vitx_dense_read.argtypes = [vp, u8p, fp, fp]
+            L.vitx_dense_device.restype = C.c_void_p; L.vitx_dense_device.argtypes = [vp]
+            L.vitx_dense_scratch_bytes.restype = C.c_size_t; L.vitx_dense_scratch_bytes.argtypes = [vp]
+            L.vitx_op_dense_labels.argtypes = [vp, C.c_long, ip, ip, ip, ip, ip, ip, vp, vp, vp]
+            L.vitx_dense_labels_host.argtypes = [vp, C.c_long, ip, ip, ip, ip, ip, ip, vp, vp]
+            L.vitx_op_dense.argtypes = [ip, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, ip, vp, vp, vp]
         if hasattr(L, "vitx_text_create"):
             i32p = C.POINTER(C.c_int32)
             L.vitx_model_kind.argtypes = [vp]
@@ -802,6 +816,63 @@ class Context:
     def nn_scratch_bytes(self) -> int:
         return int(lib().vitx_nn_scratch_bytes(self._h))
 
+    def dense_set(self, weight: Optional[np.ndarray], bias: Optional[np.ndarray] = None, layers=None, out_shape: Optional[Tuple[int, int]] = None,
+                  score: bool = False, logits: bool = False) -> None:
+        """A linear head `weight` [K, Dc] f32 (+ `bias` [K]) over the patch tokens of `layers` (indices; None: the last layer) for every later forward:
+        per image a label map [out_h, out_w] u8 (`out_shape` None: the context's image shape), with `score` the winner's value, with `logits` the patch
+        logits (vitx_dense_set).  weight None turns the output off and frees its buffers."""
+        if weight is None:
+            check(lib().vitx_dense_set(self._h, None, None, 0, 0, 0, 0, 0, 0), "vitx_dense_set")
+            return
+        w = np.ascontiguousarray(weight, dtype=np.float32)
+        if w.ndim != 2:
+            raise ValueError("dense_set: weight must be [K, Dc]")
+        b = None
+        if bias is not None:
+            b = np.ascontiguousarray(bias, dtype=np.float32)
+            if b.shape != (w.shape[0],):
+                raise ValueError("dense_set: bias must be [K]")
+        mask = 0
+        for l in ([] if layers is None else layers):
+            if not 0 <= int(l) < 64:
+                raise ValueError(f"dense_set: layer {l} outside 0 .. 63")
+            mask |= 1 << int(l)
+        oh, ow = (0, 0) if out_shape is None else (int(out_shape[0]), int(out_shape[1]))
+        fp = C.POINTER(C.c_float)
+        check(lib().vitx_dense_set(self._h, w.ctypes.data_as(fp), b.ctypes.data_as(fp) if b is not None else None, w.shape[0], w.shape[1], mask, oh, ow,
+                                   (DENSE_SCORE if score else 0) | (DENSE_LOGITS if logits else 0)), "vitx_dense_set")
+        self._dense_flags = (bool(score), bool(logits))
+
+    def dense_shape(self) -> Tuple[int, int]:
+        oh, ow = C.c_int(0), C.c_int(0)
+        check(lib().vitx_dense_shape(self._h, C.byref(oh), C.byref(ow)), "vitx_dense_shape")
+        return oh.value, ow.value
+
+    def dense_read(self, n: Optional[int] = None):
+        """(labels [n, out_h, out_w] u8, score [n, out_h, out_w] f32 or None, logits [n, Np, K] f32 or None) of the last forward made with a dense head
+        set.  `n`, if given, must be that batch."""
+        L = lib()
+        have, K = L.vitx_dense_images(self._h), L.vitx_dense_classes(self._h)
+        if n is not None and n != have:
+            raise ValueError(f"dense_read: the last forward with a dense head set had {have} images, not {n}")
+        oh, ow = self.dense_shape()
+        gh, gw = self.grid_hw
+        want_score, want_logits = getattr(self, "_dense_flags", (False, False)) if K else (False, False)
+        labels = np.empty((max(have, 1), max(oh, 1), max(ow, 1)), np.uint8)
+        score = np.empty(labels.shape, np.float32) if want_score else None
+        logits = np.empty((max(have, 1), gh * gw, max(K, 1)), np.float32) if want_logits else None
+        fp = C.POINTER(C.c_float)
+        check(L.vitx_dense_read(self._h, labels.ctypes.data_as(C.POINTER(C.c_uint8)), score.ctypes.data_as(fp) if want_score else None,
+                                logits.ctypes.data_as(fp) if want_logits else None), "vitx_dense_read")
+        return labels, score, logits
+
+    def dense_device(self) -> Tuple[int, Tuple[int, int]]:
+        """(device pointer of the labels [capacity][out_h][out_w] u8, (out_h, out_w)) for callers that stay on the GPU; (0, (0, 0)) while off."""
+        return int(lib().vitx_dense_device(self._h) or 0), self.dense_shape()
+
+    def dense_scratch_bytes(self) -> int:
+        return int(lib().vitx_dense_scratch_bytes(self._h))
+
     def synchronize(self) -> None:
         check(lib().vitx_ctx_synchronize(self._h), "vitx_ctx_synchronize")
 
@@ -1102,6 +1173,47 @@ def op_nn(dtype: int, d_z: int, z_stride: int, z_is_operand: bool, n: int, d_gal
     in `dtype` (G_pad = G rounded up to 128, zero rows beyond G), d_a [n_pad, E] `dtype`, d_acc [n_pad + 1, chunk] f32 with n_pad = n rounded up to 256."""
     check(lib().vitx_op_nn(dtype, d_z or None, z_stride, int(bool(z_is_operand)), n, d_gallery or None, G, E, k, chunk, d_a or None, d_acc or None,
                            d_state or None, d_pairs or None, stream or None), "vitx_op_nn")
+
+
+def op_dense_labels(d_logits: int, ld: int, n: int, gh: int, gw: int, K: int, out_h: int, out_w: int, d_labels: int, d_score: int = 0, stream: int = 0) -> None:
+    """vitx_op_dense_labels: logits [n gh gw, ld] f32 on the device -> labels [n, out_h, out_w] u8 (and scores f32): bilinear resampling + arg-max."""
+    check(lib().vitx_op_dense_labels(d_logits or None, ld, n, gh, gw, K, out_h, out_w, d_labels or None, d_score or None, stream or None), "vitx_op_dense_labels")
+
+
+def dense_labels_host(logits: np.ndarray, n: int, gh: int, gw: int, K: int, out_h: int, out_w: int, want_score: bool = True):
+    """vitx_dense_labels_host: the label kernel's arithmetic on the host.  logits [n gh gw, ld] f32 -> (labels [n, out_h, out_w] u8, score or None)."""
+    lg = np.ascontiguousarray(logits, np.float32)
+    if lg.ndim != 2 or lg.shape[0] != n * gh * gw:
+        raise ValueError("dense_labels_host: logits must be [n gh gw, ld]")
+    labels = np.empty((n, out_h, out_w), np.uint8)
+    score = np.empty((n, out_h, out_w), np.float32) if want_score else None
+    check(lib().vitx_dense_labels_host(lg.ctypes.data, lg.shape[1], n, gh, gw, K, out_h, out_w, labels.ctypes.data, score.ctypes.data if want_score else None),
+          "vitx_dense_labels_host")
+    return labels, score
+
+
+def op_dense(dtype: int, d_a: int, d_w: int, d_bias: int, d_logits: int, n: int, gh: int, gw: int, K: int, Dc: int, out_h: int, out_w: int,
+             d_labels: int, d_score: int = 0, stream: int = 0) -> None:
+    """vitx_op_dense: the dense head's launches on a given operand (device pointers): d_a [M_pad, Dc] `dtype` (M_pad = n gh gw rounded up to 256), d_w
+    [K_pad, Dc] (K_pad = K rounded up to 128, zero rows beyond K), d_bias [K_pad] f32 -> d_logits [M_pad, K_pad] f32, d_labels, d_score."""
+    check(lib().vitx_op_dense(dtype, d_a or None, d_w or None, d_bias or None, d_logits or None, n, gh, gw, K, Dc, out_h, out_w, d_labels or None, d_score or None,
+                              stream or None), "vitx_op_dense")
+
+
+def dense_head(path: str) -> dict:
+    """A dense head file (convert.dense_head / convert.py --dense-head-out): an .npz with weight [K, Dc] f32, bias [K] f32, layers (indices) and,
+    optionally, names [K].  Returns {"weight", "bias", "layers", "names"} (names None when absent)."""
+    with np.load(path, allow_pickle=False) as z:
+        if "weight" not in z or "bias" not in z or "layers" not in z:
+            raise ValueError(f"{path}: a dense head file holds weight, bias and layers")
+        w, b = np.ascontiguousarray(z["weight"], np.float32), np.ascontiguousarray(z["bias"], np.float32)
+        layers = [int(l) for l in np.asarray(z["layers"]).reshape(-1)]
+        names = [str(s) for s in z["names"]] if "names" in z else None
+    if w.ndim != 2 or b.shape != (w.shape[0],):
+        raise ValueError(f"{path}: weight must be [K, Dc] and bias [K]")
+    if names is not None and len(names) != w.shape[0]:
+        raise ValueError(f"{path}: {len(names)} names for {w.shape[0]} classes")
+    return {"weight": w, "bias": b, "layers": layers, "names": names}
 
 
 def round_operand(x: np.ndarray, dtype: int) -> np.ndarray:

@@ -13,6 +13,7 @@ directory-walk accuracy harness:
     python vit_cli.py --text-model text.gguf --zero-shot-ids ids.npy --text-embed out.npy   # the text embeddings of tokenised prompts (no image, no -m)
     python vit_cli.py -m model.gguf --gallery-build DIR --gallery-out g.npz [--nn-source embed|logits]   # embed DIR/<label>/* into a gallery
     python vit_cli.py -m model.gguf -i image.jpg --gallery g.npz -k 5 [--nn-temperature 0.07]   # the k nearest gallery images and the k-NN vote of their labels
+    python vit_cli.py -m backbone.gguf -i image.jpg --dense-head head.npz --dense-out labels.pgm [--img-shape HxW | --img-fit SHORT]   # a label per pixel (P5 picture of class bytes)
 
 --preprocess model follows the file's `preproc` tensor (include/vitx.h "each model's own preprocessing": what convert.py reads from a
 HuggingFace preprocessor_config.json -- CLIP: Pillow-bicubic shortest edge 224, centre crop 224, CLIP's mean / std; DINOv2: shortest edge 256,
@@ -112,6 +113,10 @@ def make_parser() -> argparse.ArgumentParser:
                     help="with -i: print the -k nearest gallery images with their scores and, when the gallery has labels, the ' > label : 0.xx' lines of the "
                          "temperature-weighted k-NN vote (vitx_nn_set) instead of the file's own head")
     ap.add_argument("--nn-temperature", type=float, default=0.07, help="with --gallery: the vote's temperature (DINO: 0.07)")
+    ap.add_argument("--dense-head", default=None, metavar="HEAD.npz",
+                    help="with -i: a linear head over the patch tokens (convert.py --dense-head-out: weight, bias, layers, names): the label of every pixel of the "
+                         "preprocessed image goes to --dense-out, the share of every class is printed as ' > name : 0.xx'")
+    ap.add_argument("--dense-out", default=None, metavar="PATH", help="with --dense-head: the label map as a binary PGM (P5) of class bytes, img_w x img_h")
     return ap
 
 
@@ -182,6 +187,10 @@ def main(argv: List[str] | None = None) -> int:
         ap.error("--embed-l2 normalises the cls / mean embedding; token features are never normalised")
     if bool(a.gallery_build) != bool(a.gallery_out):
         ap.error("--gallery-build DIR and --gallery-out G.npz go together")
+    if bool(a.dense_head) != bool(a.dense_out):
+        ap.error("--dense-head HEAD.npz and --dense-out PATH go together")
+    if a.dense_head and (a.dir is not None or a.gallery_build or a.gallery):
+        ap.error("--dense-head labels the single image of -i")
     if a.gallery and (a.dir is not None or a.gallery_build):
         ap.error("--gallery searches for the single image of -i")
     if sum(bool(v) for v in (a.img_size, a.img_shape, a.img_fit)) > 1:
@@ -270,6 +279,14 @@ def main(argv: List[str] | None = None) -> int:
             print(f"main: failed to load the gallery from '{a.gallery}': {e}", file=sys.stderr)
             return 1
 
+    dense = None
+    if a.dense_head:
+        try:
+            dense = binding.dense_head(a.dense_head)
+        except (OSError, ValueError, KeyError) as e:
+            print(f"main: failed to load the dense head from '{a.dense_head}': {e}", file=sys.stderr)
+            return 1
+
     if a.dir is None:
         try:
             img0 = _decode(a.inp)
@@ -310,7 +327,24 @@ def main(argv: List[str] | None = None) -> int:
             except binding.VitxError as e:
                 print(f"main: the gallery of '{a.gallery}' does not fit this model: {e}", file=sys.stderr)
                 return 1
+        if dense:
+            try:
+                ctx.dense_set(dense["weight"], dense["bias"], dense["layers"])
+            except binding.VitxError as e:
+                print(f"main: the head of '{a.dense_head}' does not fit this model: {e}", file=sys.stderr)
+                return 1
         probs = ctx.forward(img1[None])[0]
+        if dense:
+            lab = ctx.dense_read(1)[0][0]
+            with open(a.dense_out, "wb") as f:
+                f.write(f"P5\n{lab.shape[1]} {lab.shape[0]}\n255\n".encode() + lab.tobytes())
+            print(f"main: wrote the {lab.shape[1]} x {lab.shape[0]} label map to '{a.dense_out}'", file=sys.stderr)
+            print("", file=sys.stderr)
+            share = np.bincount(lab.reshape(-1), minlength=dense["weight"].shape[0]) / lab.size
+            for k in np.argsort(-share, kind="stable")[:a.topk]:
+                if share[k] > 0:
+                    print(f" > {dense['names'][k] if dense['names'] else f'class_{k}'} : {share[k]:.2f}")
+            return 0
         if gallery:
             idx, score, vote = ctx.nn_read(1)
             print("", file=sys.stderr)

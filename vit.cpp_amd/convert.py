@@ -59,6 +59,7 @@ from __future__ import annotations
 import argparse
 import json
 import os
+import sys
 from collections import namedtuple
 from typing import Dict
 
@@ -831,7 +832,82 @@ def _main_bank(a, transformers, model_type: str) -> None:
     print(f"wrote {a.zero_shot_out}: {embeds.shape[0]} classes of width {embeds.shape[1]}, {'sigmoid' if kind == ZS_SIGMOID else 'softmax'}, scale {scale:.6g}, bias {bias:.6g}")
 
 
+# ---- dense heads (include/vitx.h "dense prediction"): an mmseg BNHead state dict -> the .npz binding.dense_head reads -----------------------
+_BN_KEYS = ("weight", "bias", "running_mean", "running_var")
+
+
+def dense_head(state_dict, layers, hidden_size=None, eps=1e-5, names=None):
+    """The linear segmentation head of an mmseg BNHead checkpoint (the form DINOv2's linear heads are published in) as {"weight" [K, Dc] f32, "bias"
+    [K] f32, "layers", "names"}: decode_head.conv_seg.weight [K, Dc, 1, 1] and .bias [K], with the evaluation-mode SyncBN decode_head.bn.* in front of
+    the convolution folded in, in float64:  g = gamma / sqrt(var + eps);  W' = W diag(g);  b' = b + W (beta - mean g).  A plain weight [K, Dc] / bias
+    [K] pair is taken as it is.  `layers`: the backbone layers (indices, ascending) whose tokens the head was trained on, Dc = len(layers) * D;
+    hidden_size, when given, is the backbone's D and a head of another width is refused by name.  No mmseg import, no download."""
+    sd = state_dict.get("state_dict", state_dict)
+    get = lambda k: np.asarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], np.float64)
+    layers = [int(l) for l in layers]
+    if not layers or len(layers) > 4 or sorted(set(layers)) != layers or layers[0] < 0:
+        raise ValueError(f"dense_head: layers {layers} must be 1 to 4 ascending, distinct layer indices")
+    if "decode_head.conv_seg.weight" in sd:
+        wkey, bkey = "decode_head.conv_seg.weight", "decode_head.conv_seg.bias"
+    elif "weight" in sd and "bias" in sd:
+        wkey, bkey = "weight", "bias"
+    else:
+        raise ValueError("dense_head: neither decode_head.conv_seg.weight nor a plain weight / bias pair in the state dict")
+    W, b = get(wkey), get(bkey)
+    if W.ndim == 4 and W.shape[2:] == (1, 1):
+        W = W[:, :, 0, 0]
+    if W.ndim != 2 or b.shape != (W.shape[0],):
+        raise ValueError(f"dense_head: {wkey} {tuple(get(wkey).shape)} is not [K, Dc, 1, 1] or [K, Dc] with {bkey} [K]")
+    K, Dc = W.shape
+    if hidden_size is not None and Dc != len(layers) * int(hidden_size):
+        raise ValueError(f"dense_head: {wkey} has width {Dc}, the backbone gives {len(layers)} layers x hidden size {int(hidden_size)} = {len(layers) * int(hidden_size)}")
+    if Dc % len(layers):
+        raise ValueError(f"dense_head: {wkey} has width {Dc}, not a multiple of the {len(layers)} layers")
+    if wkey.startswith("decode_head") and all(f"decode_head.bn.{k}" in sd for k in _BN_KEYS):
+        gamma, beta, mean, var = (get(f"decode_head.bn.{k}") for k in _BN_KEYS)
+        for k, v in zip(_BN_KEYS, (gamma, beta, mean, var)):
+            if v.shape != (Dc,):
+                raise ValueError(f"dense_head: decode_head.bn.{k} {tuple(v.shape)} does not match the head's width {Dc}")
+        g = gamma / np.sqrt(var + float(eps))
+        b = b + W @ (beta - mean * g)
+        W = W * g[None, :]
+    if not (np.isfinite(W).all() and np.isfinite(b).all()):
+        raise ValueError("dense_head: the folded head is not finite")
+    if names is not None and len(names) != K:
+        raise ValueError(f"dense_head: {len(names)} names for {K} classes")
+    return {"weight": W.astype(np.float32), "bias": b.astype(np.float32), "layers": layers, "names": None if names is None else [str(s) for s in names]}
+
+
+def write_dense_head(path, head) -> None:
+    """The .npz binding.dense_head reads: weight, bias, layers and -- when the head has them -- names (a unicode array: no pickle)."""
+    arrays = dict(weight=np.asarray(head["weight"], np.float32), bias=np.asarray(head["bias"], np.float32), layers=np.asarray(head["layers"], np.int32))
+    if head.get("names"):
+        arrays["names"] = np.asarray(head["names"], dtype=np.str_)
+    with open(path, "wb") as f:
+        np.savez(f, **arrays)
+
+
+def _main_dense_head(argv) -> int:
+    ap = argparse.ArgumentParser(description="an mmseg BNHead checkpoint (.pth) -> a dense head file (.npz) for vit_cli.py --dense-head")
+    ap.add_argument("--dense-head-in", required=True, metavar="CKPT.pth", help="torch-saved state dict with decode_head.conv_seg.* (and decode_head.bn.*), or a plain weight / bias pair")
+    ap.add_argument("--dense-head-out", required=True, metavar="HEAD.npz")
+    ap.add_argument("--dense-layers", required=True, metavar="L1,L2,..", help="the backbone layers (0-based, ascending) whose tokens the head reads, e.g. 8,9,10,11")
+    ap.add_argument("--dense-hidden", type=int, default=0, metavar="D", help="the backbone's hidden size: a head of another width is refused")
+    ap.add_argument("--dense-eps", type=float, default=1e-5, help="epsilon of the head's BatchNorm (default 1e-5, torch's)")
+    ap.add_argument("--dense-names", default=None, metavar="NAMES.txt", help="one class name per line")
+    a = ap.parse_args(argv)
+    import torch
+    sd = torch.load(a.dense_head_in, map_location="cpu", weights_only=True)
+    names = [l.rstrip("\n") for l in open(a.dense_names)] if a.dense_names else None
+    head = dense_head(sd, [int(x) for x in a.dense_layers.split(",")], a.dense_hidden or None, a.dense_eps, names)
+    write_dense_head(a.dense_head_out, head)
+    print(f"wrote {a.dense_head_out}: {head['weight'].shape[0]} classes, width {head['weight'].shape[1]}, layers {head['layers']}")
+    return 0
+
+
 def main(argv=None) -> int:
+    if any(str(x).split("=")[0] == "--dense-head-in" for x in (sys.argv[1:] if argv is None else argv)):
+        return _main_dense_head(argv)          # a head is a file of its own: no model file is read or written
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("model"); ap.add_argument("out"); ap.add_argument("--ftype", type=int, default=1, help="0 f32, 1 f16 (default), 2/3/6/7/8 q4_0/q4_1/q5_0/q5_1/q8_0")
     ap.add_argument("--vitstr", action="store_true", help="one-channel ViTSTR scene-text model: write the character set as labels")

@@ -15,11 +15,11 @@ namespace vitx {
 
 enum ProfClass {
     PC_GEMM_PATCH = 0, PC_LAYERNORM, PC_GEMM_QKV, PC_ATTENTION, PC_GEMM_PROJ, PC_GEMM_FC1, PC_GEMM_FC2,
-    PC_GEMM_HEAD, PC_SOFTMAX, PC_DEQUANT, PC_ATTENTION_CLS, PC_GEMM_TAIL, PC_ATTN_MAP, PC_FEATURES, PC_HEAD_POOL, PC_ZEROSHOT, PC_ROPE, PC_SWIGLU, PC_NN, PC_COUNT
+    PC_GEMM_HEAD, PC_SOFTMAX, PC_DEQUANT, PC_ATTENTION_CLS, PC_GEMM_TAIL, PC_ATTN_MAP, PC_FEATURES, PC_HEAD_POOL, PC_ZEROSHOT, PC_ROPE, PC_SWIGLU, PC_NN, PC_DENSE, PC_COUNT
 };
 inline const char *const kProfNames[PC_COUNT] = {"patch_embed", "layernorm", "gemm_qkv_bias", "attention", "gemm_proj_resid",
                                     "gemm_fc1_gelu", "gemm_fc2_resid", "gemm_head", "softmax", "dequant_weights", "attention_cls", "gemm_cls_tail", "attention_map",
-                                    "features", "head_pool", "zeroshot", "rope", "swiglu", "nn"};
+                                    "features", "head_pool", "zeroshot", "rope", "swiglu", "nn", "dense"};
 static_assert(PC_COUNT <= VITX_PROF_MAX_CLASSES, "vitx_profile_read callers size their arrays by VITX_PROF_MAX_CLASSES");
 
 static_assert(VITX_F16 == DT_F16 && VITX_BF16 == DT_BF16, "the API's dtype values are handed to the launchers as they are");
@@ -234,6 +234,32 @@ struct vitx_ctx {
         for (void **p : {&nn_gallery, (void **)&nn_labels, (void **)&nn_zero, (void **)&nn_out, (void **)&nn_vote}) { if (*p) (void)hipFree(*p); *p = nullptr; }
         nn_G = nn_Gpad = 0; nn_k = nn_source = nn_E = nn_nlabels = nn_cap = nn_n = 0; nn_T = 0.0f; nn_scratch = 0;
     }
+    // the dense head (vitx_dense_set): nothing is allocated or launched while dn_K == 0
+    int dn_K = 0, dn_Kpad = 0;   // classes of the head; its rows on the device (K rounded up to the GEMM's column tile `tn`, zero rows beyond K)
+    int dn_Dc = 0;               // the operand's width: popcount(dn_mask) * D
+    uint64_t dn_mask = 0;        // selected layers (never 0 while on: "the last layer" is resolved at vitx_dense_set)
+    int dn_oh = 0, dn_ow = 0;    // the label map's shape
+    int dn_flags = 0;            // VITX_DENSE_*
+    int dn_cap = 0;              // images the output buffers hold (= the images one pass takes)
+    int dn_n = 0;                // images of the last forward made with a head set (0: none since vitx_dense_set)
+    void *dn_W = nullptr;        // [dn_Kpad][dn_Dc] operand type
+    float *dn_bias = nullptr;    // [dn_Kpad] f32, zeros beyond K
+    uint8_t *dn_labels = nullptr;// [dn_cap][dn_oh][dn_ow]
+    float *dn_score = nullptr;   // VITX_DENSE_SCORE: [dn_cap][dn_oh][dn_ow]
+    float *dn_logits = nullptr;  // VITX_DENSE_LOGITS: [dn_cap][gh * gw][dn_K], the patch logits kept for vitx_dense_read
+    std::vector<void *> dn_a;    // per slice: [round_up(slice cap * gh * gw, tm)][dn_Dc] operand type, the GEMM's A rows
+    std::vector<float *> dn_acc; // per slice: [round_up(slice cap * gh * gw, tm)][dn_Kpad] f32, the patch logits
+    size_t dn_scratch = 0;       // bytes of dn_a + dn_acc over all slices
+    bool dense_on() const { return dn_K != 0; }
+    // a selected last layer needs every row of it: no class-rows-only tail while the head is set (as with VITX_FEAT_TOKENS of the last layer)
+    bool dense_last_all_rows() const { return dense_on() && ((dn_mask >> (L - 1)) & 1); }
+    void dense_free() {
+        for (void *p : dn_a) if (p) (void)hipFree(p);
+        for (float *p : dn_acc) if (p) (void)hipFree(p);
+        dn_a.clear(); dn_acc.clear();
+        for (void **p : {&dn_W, (void **)&dn_bias, (void **)&dn_labels, (void **)&dn_score, (void **)&dn_logits}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+        dn_K = dn_Kpad = dn_Dc = dn_oh = dn_ow = dn_flags = dn_cap = dn_n = 0; dn_mask = 0; dn_scratch = 0;
+    }
     // hipGraph cache of the single-stream (small-batch) forward, opt-in (vitx_ctx_options::graph).  Key = (images, batch, outputs): the graph
     // bakes the pointers in.  An entry is captured the second time in a row its key is seen (one-off calls are never captured).
     // Measured (profiles/r02f/hipgraph_small_batch.txt): replaying the ~100 dependent launches as a graph takes the enqueue work off
@@ -267,6 +293,7 @@ struct vitx_ctx {
         feat_free();
         zs_free();
         nn_free();
+        dense_free();
         for (void *p : allocs) (void)hipFree(p);
         if (stream) (void)hipStreamDestroy(stream);
     }

@@ -213,6 +213,33 @@ struct SliceForward {
                                  c->nn_vote ? c->nn_vote + (size_t)first_img * c->nn_nlabels : nullptr, st));
         return VITX_OK;
     }
+    // The dense head (vitx_dense_set).  dense_rows, as layer il finishes (where features(il, ..) is called): the final norm of the patch rows of this
+    // sub-batch, rounded to the operand type, into columns slot * D .. of the slice's compact operand rows [n * Np][Dc] -- the stand-alone LayerNorm
+    // with the patch rows as its groups, no kernel of its own.  dense_head, after the classifier: the pad rows zeroed, the patch logits through
+    // the dispatcher, the label kernel into the images' global positions, and (VITX_DENSE_LOGITS) the real columns kept.
+    int dense_rows(int il) {
+        if (!c->dense_on() || !((c->dn_mask >> il) & 1)) return VITX_OK;
+        const int Np = N - c->Tp, Dc = c->dn_Dc, rows = n * Np;
+        const size_t si = &sl - &c->slices[0];
+        ProfScope ps(c, st, PC_DENSE, 0, (double)rows * D * (4 + eb));
+        HIP_TRY(launch_layernorm(dt, sl.X + (size_t)c->Tp * D, D, ws.norm_w, ws.norm_b, (char *)c->dn_a[si] + (size_t)layer_slot(c->dn_mask, il) * D * 2, Dc, rows, D, c->hp.eps, st, Np, (long)N * D));
+        return VITX_OK;
+    }
+    int dense_head() {
+        int rc;
+        const int Np = N - c->Tp, Dc = c->dn_Dc, K = c->dn_K, Kpad = c->dn_Kpad, rows = n * Np, Mr = round_up(rows, tm);
+        const size_t si = &sl - &c->slices[0], px = (size_t)c->dn_oh * c->dn_ow;
+        void *a = c->dn_a[si]; float *acc = c->dn_acc[si];
+        if (Mr > rows) HIP_TRY(hipMemsetAsync((char *)a + (size_t)rows * Dc * 2, 0, (size_t)(Mr - rows) * Dc * 2, st));
+        if ((rc = gemm(c, st, PC_DENSE, EPI_BIAS_F32, dense_gemm(a, c->dn_W, c->dn_bias, acc, Mr, rows, K, Kpad, Dc, Kpad)))) return rc;
+        {
+            ProfScope ps(c, st, PC_DENSE, 9.0 * n * (double)px * K, (double)rows * Kpad * 4 + (double)n * px * (c->dn_score ? 5 : 1));
+            HIP_TRY(launch_dense_labels(acc, Kpad, n, c->gh, c->gw, K, c->dn_oh, c->dn_ow, c->dn_labels + (size_t)first_img * px,
+                                        c->dn_score ? c->dn_score + (size_t)first_img * px : nullptr, st));
+        }
+        if (c->dn_logits) HIP_TRY(hipMemcpy2DAsync(c->dn_logits + (size_t)first_img * Np * K, (size_t)K * 4, acc, (size_t)Kpad * 4, (size_t)K * 4, rows, hipMemcpyDeviceToDevice, st));
+        return VITX_OK;
+    }
     // Quantised matrices (block form in HBM): a q4_0 GEMM with few rows expands the blocks in its own LDS-fill path; everything else
     // is expanded just in time, one launch per layer, into the slice's scratch and then streamed by the wide-tile kernels.
     bool fused_ok(const QuantW &q, int rows) const { return q.blocks && q.type == T_Q4_0 && rows <= c->q4_fused_rows && rows % 128 == 0 && q.n_pad % 128 == 0 && q.K % 64 == 0; }
@@ -318,7 +345,8 @@ struct SliceForward {
         if ((rc = gemm_mx(c, st, r.pc_fc2, EPI_BIAS_RESID, sl.Hmx, sl.Hmx_s, w.mx[W_FC2], w.fc2_b, r.X, nullptr, r.M_real, D))) return rc;
         if (nx && (rc = layernorm_mx(r.X, nx->ln1_w, nx->ln1_b, sl.Umx, sl.Umx_s, r.M_real))) return rc;
         if (!c->trace_ids.empty() && (rc = trace(il + 1))) return rc;
-        return c->feat_on() ? features(il, tail_now) : VITX_OK;
+        if (c->feat_on() && (rc = features(il, tail_now))) return rc;
+        return dense_rows(il);
     }
     // Dense tail of a layer
     int dense_tail(int il, const LayerW &w, const LayerW *nx, bool tail_now, const Rows &r) {
@@ -336,7 +364,8 @@ struct SliceForward {
         }
         if ((rc = resid_gemm_ln(r, r.pc_fc2, c->glu ? sl.Hg : sl.Hbuf, Wl[W_FC2], w.fc2_b, F, Fl[W_FC2], nx ? nx->ln1_w : nullptr, nx ? nx->ln1_b : nullptr, sl.U, &fix_u))) return rc;
         if (!c->trace_ids.empty() && (rc = trace(il + 1))) return rc;
-        return features(il, tail_now, c->pool && il + 1 == c->L ? sl.Z : nullptr);
+        if ((rc = features(il, tail_now, c->pool && il + 1 == c->L ? sl.Z : nullptr))) return rc;
+        return dense_rows(il);
     }
     int run(const void *d_imgs, void *d_probs, void *d_logits) {
         const int Mp_real = n * c->gh * c->gw;                          // patch rows
@@ -363,7 +392,7 @@ struct SliceForward {
         }
         const Rows all_rows{sl.X, M, M_real, PC_GEMM_PROJ, PC_GEMM_FC1, PC_GEMM_FC2, fuse};
         const Rows cls_rows{sl.Xc, round_up(n, tm), n, PC_GEMM_TAIL, PC_GEMM_TAIL, PC_GEMM_TAIL, false};
-        const bool tail = c->cls_tail && c->trace_ids.empty() && !c->feat_last_all_rows();      // the last layer carries only the class-token rows past its qkv projection (vitx_ctx::cls_tail)
+        const bool tail = c->cls_tail && c->trace_ids.empty() && !c->feat_last_all_rows() && !c->dense_last_all_rows();      // the last layer carries only the class-token rows past its qkv projection (vitx_ctx::cls_tail)
         for (int il = 0; il < c->L; ++il) {
             const LayerW &w = ws.layers[il], *nx = il + 1 < c->L ? &ws.layers[il + 1] : nullptr;
             const bool tail_now = tail && il + 1 == c->L;
@@ -398,6 +427,7 @@ struct SliceForward {
         // zero-shot logits and probabilities of a context with a bank: from the pooled embedding e (attention-pooling head), else from the logits row
         if (c->zs_on() && (rc = c->map ? zeroshot(sl.Xc, D) : zeroshot(lg, ldl))) return rc;
         if (c->nn_on() && (rc = nearest(lg, ldl))) return rc;
+        if (c->dense_on() && (rc = dense_head())) return rc;
         if (fuse && c->ln_fb_host) HIP_TRY(hipMemcpyAsync(c->ln_fb_host + (&sl - &c->slices[0]), sl.ln_todo + sl.ln_blocks, sizeof(unsigned), hipMemcpyDeviceToHost, st));       // fall-back budget
         return VITX_OK;
     }
@@ -575,7 +605,7 @@ static int forward_pass(vitx_ctx *c, const void *d_imgs, int n, void *d_probs, v
     const bool serial = c->prof_on;
     const int ns = (c->nslices > 1 && n >= 8 * c->nslices) ? c->nslices : 1;
     if (ns == 1) {
-        if (c->graphs_on && !c->prof_on && c->trace_ids.empty() && !c->attn_on() && !c->feat_on() && !c->zs_on() && !c->nn_on()) {
+        if (c->graphs_on && !c->prof_on && c->trace_ids.empty() && !c->attn_on() && !c->feat_on() && !c->zs_on() && !c->nn_on() && !c->dense_on()) {
             bool done = false;
             const int rc = forward_graph(c, st, d_imgs, n, d_probs, d_logits, &done);
             if (rc != VITX_OK || done) return rc;
@@ -630,6 +660,7 @@ int vitx_forward_device(vitx_ctx *c, const void *d_imgs, int n, void *d_probs, v
     if (n > c->call_limit && c->feat_on()) { set_error("vitx_forward_device: features take one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
     if (n > c->call_limit && c->zs_on()) { set_error("vitx_forward_device: zero-shot classification takes one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
     if (n > c->call_limit && c->nn_on()) { set_error("vitx_forward_device: nearest neighbours take one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
+    if (n > c->call_limit && c->dense_on()) { set_error("vitx_forward_device: the dense head takes one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
     for (int i0 = 0; i0 < n; i0 += c->call_limit) {
         const int ni = std::min(c->call_limit, n - i0);
         const int rc = forward_pass(c, (const float *)d_imgs + (size_t)i0 * c->img_floats(), ni, (float *)d_probs + (size_t)i0 * c->R * c->C,
@@ -640,6 +671,7 @@ int vitx_forward_device(vitx_ctx *c, const void *d_imgs, int n, void *d_probs, v
     if (c->feat_on()) c->feat_n = n;
     if (c->zs_on()) c->zs_n = n;
     if (c->nn_on()) c->nn_n = n;
+    if (c->dense_on()) c->dn_n = n;
     return VITX_OK;
 }
 int vitx_forward(vitx_ctx *c, const float *imgs, int n, float *probs, float *logits) {

@@ -228,6 +228,13 @@ constexpr int kNnSegs = 8, kNnMaxK = 64;
 size_t nn_state_bytes(int n, int k);
 hipError_t launch_nn_select(const float *scores, long ld, int n, int cols, long base_index, void *state, int k, bool first, hipStream_t stream);
 hipError_t launch_nn_finish(const void *state, int n, int k, const int *labels, int n_labels, float temperature, void *pairs, float *vote, hipStream_t stream);
+// The label map of the dense head (dense_label.hip; include/vitx.h "dense prediction"): logits [n * gh * gw][ld] f32 (ld a multiple of 4, at least K rounded
+// up to 4; columns K .. ld never compared; 16-byte aligned) -> labels [n][out_h][out_w] u8 and, score != nullptr, score [n][out_h][out_w] f32: the K
+// planes resampled bilinearly (dense_resample.h) and arg-maxed in vitx_topk's order.  1 <= K <= kDenseMaxK, gh <= out_h <= kDenseMaxOut (and w),
+// n <= 65535.  hipErrorInvalidValue for a shape outside that (dense_labels_supports).
+constexpr int kDenseMaxK = 256, kDenseMaxOut = 8192;
+bool dense_labels_supports(long ld, int n, int gh, int gw, int K, int out_h, int out_w);
+hipError_t launch_dense_labels(const float *logits, long ld, int n, int gh, int gw, int K, int out_h, int out_w, uint8_t *labels, float *score, hipStream_t stream);
 // The text tower (include/vitx.h "the text tower"; text_embed.hip, attention_text.hip).
 //   text_embed: X[i][t][:] (f32) = f32(tok[ids[i * T + t]][:]) + pos[t][:]; tok [V][D] f16 (table_f16) or f32, ids checked by the caller; D % 8 == 0
 //   text_pool:  z[i][:] (dtype) = RNE(final LayerNorm of X row i * T + pooled[i]), LnRow's bits; rows n .. m_pad zeros; every width of VITX_LN_WIDTHS
@@ -332,6 +339,7 @@ hipError_t prepare_attention_flow();
 hipError_t prepare_attention_persist();
 hipError_t prepare_attention_stream();
 hipError_t prepare_attention_text();                   // attention_text.hip
+hipError_t prepare_dense();                            // dense_label.hip
 #pragma GCC visibility pop
 
 }  // namespace vitx

@@ -5,6 +5,7 @@
 
 #include "context.h"
 #include "preproc_resample.h"
+#include "dense_resample.h"
 
 // A launcher's hipError_t -> the entry point's return code, with "<name>: <hip string>" as the error text.  `invalid`: the code that
 // hipErrorInvalidValue (the launchers' "no instantiation for this shape") maps to -- each entry point keeps the mapping it always had
@@ -399,6 +400,66 @@ int vitx_op_nn(int dtype, const void *d_z, long z_stride, int z_is_operand, int 
     }
     if (e == hipSuccess) e = launch_nn_finish(d_state, n, k, nullptr, 0, 0.0f, d_pairs, nullptr, st);
     return op_rc("vitx_op_nn", e, VITX_ERR_UNSUPPORTED);
+}
+
+// The dense head on the caller's buffers (include/vitx.h "dense prediction").  dense_label_args: the checks the device entry point and its host twin
+// share -- none needs a device.
+static int dense_label_args(const char *name, const void *logits, long ld, int n, int gh, int gw, int K, int out_h, int out_w, const void *labels) {
+    if (!logits || !labels || n < 1 || gh < 1 || gw < 1 || K < 1) { set_error("%s: invalid argument", name); return VITX_ERR_ARG; }
+    if (ld < ((K + 3) & ~3) || ld % 4) { set_error("%s: ld = %ld must be a multiple of 4 and at least K = %d rounded up to 4", name, ld, K); return VITX_ERR_ARG; }
+    if (K > kDenseMaxK) { set_error("%s: K = %d classes above %d (labels are bytes)", name, K, kDenseMaxK); return VITX_ERR_UNSUPPORTED; }
+    if (out_h < gh || out_w < gw || out_h > kDenseMaxOut || out_w > kDenseMaxOut) { set_error("%s: output %d x %d outside the grid %d x %d .. %d (upsampling only)", name, out_h, out_w, gh, gw, kDenseMaxOut); return VITX_ERR_UNSUPPORTED; }
+    if (n > 65535 || (size_t)n * gh * gw > 0x7fffffffu) { set_error("%s: %d images of %d x %d patches in one launch", name, n, gh, gw); return VITX_ERR_UNSUPPORTED; }
+    return VITX_OK;
+}
+int vitx_op_dense_labels(const void *d_logits, long ld, int n, int gh, int gw, int K, int out_h, int out_w, void *d_labels, void *d_score, void *stream) {
+    if (const int rc = dense_label_args("vitx_op_dense_labels", d_logits, ld, n, gh, gw, K, out_h, out_w, d_labels)) return rc;
+    if ((uintptr_t)d_logits % 16 || (uintptr_t)d_score % 4) { set_error("vitx_op_dense_labels: d_logits must be 16-byte, d_score 4-byte aligned"); return VITX_ERR_ARG; }
+    return op_rc("vitx_op_dense_labels", launch_dense_labels((const float *)d_logits, ld, n, gh, gw, K, out_h, out_w, (uint8_t *)d_labels, (float *)d_score, (hipStream_t)stream), VITX_ERR_UNSUPPORTED);
+}
+// The host twin: dense_resample.h's arithmetic in plain loops, the classes of a pixel walked upwards.  No device call.
+int vitx_dense_labels_host(const float *logits, long ld, int n, int gh, int gw, int K, int out_h, int out_w, uint8_t *labels, float *score) {
+    if (const int rc = dense_label_args("vitx_dense_labels_host", logits, ld, n, gh, gw, K, out_h, out_w, labels)) return rc;
+    const float sy = dense_scale(gh, out_h), sx = dense_scale(gw, out_w);
+    std::vector<DenseAxis> axs(out_w);
+    for (int x = 0; x < out_w; ++x) axs[x] = dense_axis(gw, sx, x);
+    for (int i = 0; i < n; ++i) {
+        const float *lg = logits + (size_t)i * gh * gw * ld;
+        for (int y = 0; y < out_h; ++y) {
+            const DenseAxis ay = dense_axis(gh, sy, y);
+            for (int x = 0; x < out_w; ++x) {
+                const DenseAxis &ax = axs[x];
+                const float *a = lg + ((size_t)ay.i0 * gw + ax.i0) * ld, *b = lg + ((size_t)ay.i0 * gw + ax.i1) * ld;
+                const float *c = lg + ((size_t)ay.i1 * gw + ax.i0) * ld, *d = lg + ((size_t)ay.i1 * gw + ax.i1) * ld;
+                DenseBest best = dense_best_init();
+                for (int k = 0; k < K; ++k) dense_offer(best, dense_value(ax.h, ax.l, ay.h, ay.l, a[k], b[k], c[k], d[k]), k);
+                const size_t pix = ((size_t)i * out_h + y) * out_w + x;
+                labels[pix] = (uint8_t)best.cls;
+                if (score) score[pix] = dense_score(best);
+            }
+        }
+    }
+    return VITX_OK;
+}
+// The launches the forward of a context with a dense head makes after its operand rows are written (SliceForward::dense_head): the pad rows
+// zeroed, the GEMM through the dispatcher, the label kernel.
+int vitx_op_dense(int dtype, void *d_a, const void *d_w, const void *d_bias, void *d_logits, int n, int gh, int gw, int K, int Dc, int out_h, int out_w,
+                  void *d_labels, void *d_score, void *stream) {
+    if (!d_a || !d_w || !d_bias || Dc < 1 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_dense: invalid argument"); return VITX_ERR_ARG; }
+    const int Kpad = K > 0 ? round_up(K, gemm_tile_n()) : 0;
+    if (const int rc = dense_label_args("vitx_op_dense", d_logits, Kpad, n, gh, gw, K, out_h, out_w, d_labels)) return rc;
+    for (const void *p : {(const void *)d_a, d_w, d_bias, (const void *)d_logits, (const void *)d_score})
+        if ((uintptr_t)p % 16) { set_error("vitx_op_dense: every pointer but d_labels must be 16-byte aligned"); return VITX_ERR_ARG; }
+    if (Dc % 64) { set_error("vitx_op_dense: Dc = %d is not a multiple of 64 (the GEMMs' K step)", Dc); return VITX_ERR_UNSUPPORTED; }
+    const int rows = n * gh * gw, M = round_up(rows, gemm_tile_m());
+    if ((size_t)M * Dc * 2 > 0xf0000000u || (size_t)M * Kpad * 4 > 0xf0000000u || (size_t)Kpad * Dc * 2 > 0xf0000000u) { set_error("vitx_op_dense: %d rows of width %d leave the GEMM's 32-bit byte window", M, Dc); return VITX_ERR_UNSUPPORTED; }
+    const Tuning *t = tuning_for_device(-1);
+    if (!t) { set_error("vitx_op_dense: kernel bring-up failed"); return VITX_ERR_HIP; }
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = M > rows ? hipMemsetAsync((char *)d_a + (size_t)rows * Dc * 2, 0, (size_t)(M - rows) * Dc * 2, st) : hipSuccess;
+    if (e == hipSuccess) e = launch_gemm(*t, dtype, EPI_BIAS_F32, dense_gemm(d_a, d_w, (const float *)d_bias, d_logits, M, rows, K, Kpad, Dc, Kpad), st);
+    if (e == hipSuccess) e = launch_dense_labels((const float *)d_logits, Kpad, n, gh, gw, K, out_h, out_w, (uint8_t *)d_labels, (float *)d_score, st);
+    return op_rc("vitx_op_dense", e, VITX_ERR_UNSUPPORTED);
 }
 
 // The text tower's three kernels on their own (include/vitx.h "the text tower").  Every argument check comes before the first device call.

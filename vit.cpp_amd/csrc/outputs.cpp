@@ -324,4 +324,95 @@ int vitx_nn_read(vitx_ctx *c, int32_t *idx, float *score, float *vote) {
     return VITX_OK;
 }
 
+// The dense head of a context (include/vitx.h "dense prediction").  Every argument check comes before the first device call.
+int vitx_dense_set(vitx_ctx *c, const float *W, const float *bias, int K, int Dc, uint64_t layer_mask, int out_h, int out_w, int flags) {
+    if (!c) return VITX_ERR_ARG;
+    const bool off = !W && K == 0;
+    uint64_t mask = layer_mask;
+    int m = 0, oh = out_h, ow = out_w;
+    if (!off) {
+        if (!W) { set_error("vitx_dense_set: NULL weights with K = %d", K); return VITX_ERR_ARG; }
+        if (K < 1) { set_error("vitx_dense_set: K = %d classes", K); return VITX_ERR_ARG; }
+        if (flags & ~(VITX_DENSE_SCORE | VITX_DENSE_LOGITS)) { set_error("vitx_dense_set: unknown flags 0x%x", flags); return VITX_ERR_ARG; }
+        if (mask == 0) mask = 1ull << (c->L - 1);
+        if (c->L < 64 && (mask >> c->L)) { set_error("vitx_dense_set: layer mask selects a layer at or beyond L = %d", c->L); return VITX_ERR_ARG; }
+        m = __builtin_popcountll(mask);
+        if (m > 4) { set_error("vitx_dense_set: %d layers selected, at most 4", m); return VITX_ERR_ARG; }
+        if (Dc != m * c->D) { set_error("vitx_dense_set: the head's width %d is not %d layers x D = %d", Dc, m, m * c->D); return VITX_ERR_ARG; }
+        if (out_h < 0 || out_w < 0 || ((out_h == 0) != (out_w == 0))) { set_error("vitx_dense_set: output shape %d x %d (0 x 0: the context's image shape)", out_h, out_w); return VITX_ERR_ARG; }
+        if (out_h == 0) { oh = c->Sh; ow = c->Sw; }
+        for (size_t i = 0, nb = (size_t)K * Dc; i < nb; ++i)
+            if (!std::isfinite(W[i])) { set_error("vitx_dense_set: weight [%zu][%zu] is not finite", i / Dc, i % Dc); return VITX_ERR_ARG; }
+        if (bias) for (int k = 0; k < K; ++k)
+            if (!std::isfinite(bias[k])) { set_error("vitx_dense_set: bias [%d] is not finite", k); return VITX_ERR_ARG; }
+        if (K > kDenseMaxK) { set_error("vitx_dense_set: K = %d classes above %d (labels are bytes)", K, kDenseMaxK); return VITX_ERR_UNSUPPORTED; }
+        if (c->R != 1) { set_error("vitx_dense_set: the dense head is not available for ViTSTR contexts"); return VITX_ERR_UNSUPPORTED; }
+        if (oh < c->gh || ow < c->gw || oh > kDenseMaxOut || ow > kDenseMaxOut) {
+            set_error("vitx_dense_set: output %d x %d outside the patch grid %d x %d .. %d (upsampling only)", oh, ow, c->gh, c->gw, kDenseMaxOut);
+            return VITX_ERR_UNSUPPORTED;
+        }
+        const size_t rows = (size_t)c->pass_cap() * c->gh * c->gw;
+        if (rows * Dc * 2 > 0xf0000000u || rows * round_up(K, c->tn) * 4 > 0xf0000000u || c->pass_cap() > 65535) {
+            set_error("vitx_dense_set: the operand or logit rows of a pass of %d images leave the GEMM's 32-bit byte window", c->pass_cap());
+            return VITX_ERR_UNSUPPORTED;
+        }
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());          // no forward in flight reads or writes the buffers about to be freed
+    c->dense_free();
+    if (off) return VITX_OK;
+    const int Kpad = round_up(K, c->tn), cap = c->pass_cap(), Np = c->gh * c->gw;
+    const size_t px = (size_t)oh * ow;
+    auto alloc = [](void **p, size_t bytes) { if (hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; } return true; };
+    bool ok = alloc(&c->dn_W, (size_t)Kpad * Dc * 2) && alloc((void **)&c->dn_bias, (size_t)Kpad * 4) && alloc((void **)&c->dn_labels, (size_t)cap * px);
+    if (ok && (flags & VITX_DENSE_SCORE)) ok = alloc((void **)&c->dn_score, (size_t)cap * px * 4);
+    if (ok && (flags & VITX_DENSE_LOGITS)) ok = alloc((void **)&c->dn_logits, (size_t)cap * Np * K * 4);
+    c->dn_a.assign(c->nslices, nullptr); c->dn_acc.assign(c->nslices, nullptr);
+    size_t scratch = 0;
+    hipError_t e = hipSuccess;
+    for (int i = 0; ok && i < c->nslices; ++i) {
+        const size_t rows = (size_t)round_up(std::min(c->slices[i].cap, cap) * Np, c->tm);
+        ok = alloc(&c->dn_a[i], rows * Dc * 2) && alloc((void **)&c->dn_acc[i], rows * Kpad * 4);
+        if (ok) e = hipMemset(c->dn_a[i], 0, rows * Dc * 2);
+        if (e != hipSuccess) break;
+        scratch += rows * Dc * 2 + rows * Kpad * 4;
+    }
+    if (!ok) { c->dense_free(); set_error("vitx_dense_set: cannot allocate the buffers for %d classes, %d x %d labels and %d images", K, oh, ow, cap); return VITX_ERR_NOMEM; }
+    // the head goes up rounded (RNE) to the operand type; the zero rows beyond K come from operand_matrix_host, the zero biases from the memset
+    if (e == hipSuccess) {
+        const std::vector<uint16_t> hw = operand_matrix_host(c->dtype, W, nullptr, K, Dc, Kpad, Dc, 0, 0);
+        e = hipMemcpy(c->dn_W, hw.data(), hw.size() * 2, hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = hipMemset(c->dn_bias, 0, (size_t)Kpad * 4);
+    if (e == hipSuccess && bias) e = hipMemcpy(c->dn_bias, bias, (size_t)K * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { c->dense_free(); set_error("vitx_dense_set: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
+    c->dn_K = K; c->dn_Kpad = Kpad; c->dn_Dc = Dc; c->dn_mask = mask; c->dn_oh = oh; c->dn_ow = ow; c->dn_flags = flags; c->dn_cap = cap; c->dn_scratch = scratch;
+    return VITX_OK;
+}
+int vitx_dense_classes(const vitx_ctx *c) { return c ? c->dn_K : 0; }
+int vitx_dense_shape(const vitx_ctx *c, int *out_h, int *out_w) {
+    if (!c) return VITX_ERR_ARG;
+    if (out_h) *out_h = c->dn_oh;
+    if (out_w) *out_w = c->dn_ow;
+    return VITX_OK;
+}
+int vitx_dense_images(const vitx_ctx *c) { return c ? c->dn_n : 0; }
+const void *vitx_dense_device(const vitx_ctx *c) { return c ? c->dn_labels : nullptr; }
+size_t vitx_dense_scratch_bytes(const vitx_ctx *c) { return c ? c->dn_scratch : 0; }
+int vitx_dense_read(vitx_ctx *c, uint8_t *labels, float *score, float *logits) {
+    if (!c || !labels) return VITX_ERR_ARG;
+    const int n = c->dense_on() ? c->dn_n : 0;
+    if (n == 0) { set_error("vitx_dense_read: no forward has run with a dense head set since vitx_dense_set"); return VITX_ERR_ARG; }
+    if (score && !c->dn_score) { set_error("vitx_dense_read: the head was set without VITX_DENSE_SCORE"); return VITX_ERR_ARG; }
+    if (logits && !c->dn_logits) { set_error("vitx_dense_read: the head was set without VITX_DENSE_LOGITS"); return VITX_ERR_ARG; }
+    const size_t px = (size_t)c->dn_oh * c->dn_ow;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(labels, c->dn_labels, (size_t)n * px, hipMemcpyDeviceToHost));
+    if (score) HIP_TRY(hipMemcpy(score, c->dn_score, (size_t)n * px * 4, hipMemcpyDeviceToHost));
+    if (logits) HIP_TRY(hipMemcpy(logits, c->dn_logits, (size_t)n * c->gh * c->gw * c->dn_K * 4, hipMemcpyDeviceToHost));
+    return VITX_OK;
+}
+
 }  // extern "C"

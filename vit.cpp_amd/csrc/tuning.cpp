@@ -17,6 +17,7 @@ static hipError_t prepare_device_kernels(const Tuning &t) {
     if (e == hipSuccess) e = prepare_patch_embed();
     if (e == hipSuccess) e = prepare_attention();
     if (e == hipSuccess) e = prepare_attention_text();
+    if (e == hipSuccess) e = prepare_dense();
     return e;
 }
 

@@ -11,7 +11,8 @@
 //   * vit_predict_batch is NEW (the reference has no batched call): n images per launch;
 //   * vit_embed / vit_embed_batch are NEW (the reference returns class probabilities only): the image embedding;
 //   * vit_zeroshot_batch is NEW: zero-shot classes of a CLIP / SigLIP file against a bank of text embeddings;
-//   * vit_nn_batch is NEW: the nearest rows of a gallery of embeddings, and the weighted k-NN vote of their labels.
+//   * vit_nn_batch is NEW: the nearest rows of a gallery of embeddings, and the weighted k-NN vote of their labels;
+//   * vit_dense_batch is NEW: a linear head over the patch tokens, a class label for every pixel.
 // Everything below is a thin wrapper over the C ABI in include/vitx.h.
 #pragma once
 
@@ -142,6 +143,25 @@ struct vit_nn_result {
 // out[i] = image i's result.  The gallery is set for this call and switched off again before returning; state.prediction holds the file's own class
 // probabilities of the same forward.  0 ok / 1 failure.
 int vit_nn_batch(const vit_model &model, vit_state &state, const image_f32 *imgs, int n, const vit_nn_gallery &gallery, std::vector<vit_nn_result> &out);
+// NEW, no counterpart in the reference: dense prediction (include/vitx.h "dense prediction") -- a linear head over the final-norm patch tokens of up to
+// four layers (the form DINOv2's segmentation heads are published in; convert.py --dense-head-in writes one from an mmseg checkpoint).
+struct vit_dense_head {
+    std::vector<float> weight;            // [K][Dc], Dc = layers.size() * hidden_size
+    std::vector<float> bias;              // K, or empty: zeros
+    int K = 0, Dc = 0;
+    std::vector<int> layers;              // the layers whose tokens are concatenated, ascending; empty: the last layer
+    int out_h = 0, out_w = 0;             // the label map's shape; 0 x 0: the state's image shape
+    bool want_score = false;              // also the winner's resampled logit per pixel
+    std::vector<std::string> names;       // K names, or empty
+};
+struct vit_dense_result {
+    int h = 0, w = 0;
+    std::vector<uint8_t> labels;          // [h][w]
+    std::vector<float> score;             // [h][w], or empty
+};
+// out[i] = image i's label map.  The head is set for this call and switched off again before returning; state.prediction holds the file's own class
+// probabilities of the same forward.  0 ok / 1 failure.
+int vit_dense_batch(const vit_model &model, vit_state &state, const image_f32 *imgs, int n, const vit_dense_head &head, std::vector<vit_dense_result> &out);
 // NEW, no counterpart in the reference: the text tower of a CLIP / SigLIP checkpoint (include/vitx.h "the text tower").  `model` is a text-tower
 // file (vitx_model_kind == VITX_KIND_TEXT; hparams.img_size is its context length T, hparams.num_classes its embedding width E).  ids: n
 // tokenised prompts [n][T] -- there is no tokenizer in the engine; out[i] = prompt i's E floats; flags 0 or VITX_TEXT_L2.  0 ok / 1 failure.
