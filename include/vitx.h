@@ -974,6 +974,86 @@ int vitx_dense_labels_host(const float *logits, long ld, int n, int gh, int gw, 
 int vitx_op_dense(int dtype, void *d_a /* [M_pad][Dc] */, const void *d_w /* [K_pad][Dc] */, const void *d_bias /* [K_pad] f32 */, void *d_logits /* [M_pad][K_pad] f32 */,
                   int n, int gh, int gw, int K, int Dc, int out_h, int out_w, void *d_labels, void *d_score, void *stream);
 
+/* ---- depth estimation: a binned linear head over patch and class tokens, depth maps on the device --------- */
+/* An opt-in output of the forward beside the dense head, for the other family of linear heads DINOv2 is published with (mmseg's BNHead-style depth
+ * head with classify = True, norm_strategy = "linear": a 1 x 1 convolution to K depth BINS over concat(patch token, class token) of one or four
+ * layers, the tokens upsampled x 4 first).  Every forward then also writes, per image, an [out_h][out_w] f32 depth map.  Nothing else the forward
+ * writes changes; with no head nothing is launched or allocated.  For one image with grid gh x gw, Np = gh gw patches, first patch row T, and the
+ * selected layers l_1 < ... < l_m (1 <= m <= 4; mask 0 = the last layer):
+ *   operand rows  A[t] = RNE_dtype(G_{l_1}[T + t]) ‖ ... ‖ RNE_dtype(G_{l_m}[T + t]), width Dc = m D, compact rows [n Np][Dc] of the sub-batch; with a
+ *     class half Wc also a_cls = RNE(G_{l_1}[0]) ‖ ... ‖ RNE(G_{l_m}[0]), one row per image.  G_l = X_l, the raw f32 residual stream after layer l (what
+ *     vitx_trace_read returns as stage l + 1), written by a streaming conversion kernel; under VITX_DEPTH_NORM G_l = F_l, the features section's
+ *     final-norm value bit for bit, written by the stand-alone LayerNorm as the dense head's rows are.  dtype = the context's operand type; a
+ *     VITX_MXFP8 context uses bf16.  A selected last layer makes the context evaluate EVERY row of the last layer while the head is set (the rule of
+ *     VITX_FEAT_TOKENS, with its consequence: probabilities and logits are those of a last_layer_all_rows = 1 context, bit for bit).
+ *   patch logits  c[t][k] = sum_i A[t][i] RNE_dtype(Wp[k][i]), f32 accumulation on the MFMA, through the head's GEMM dispatcher into [M_pad][K_pad] f32
+ *     with a bias of zeros; K <= 256, K_pad = K rounded up to 128, weight rows beyond K are zero.
+ *   offsets       o[img][k] = bias_k + sum_i a_cls[i] RNE_dtype(Wc[k][i]): one GEMM of the n class rows through the same dispatcher.  Without Wc
+ *     o[img] = bias for every image and no GEMM is launched.
+ *   fine plane    fh = u gh, fw = u gw, u = `upsample` in {1, 2, 4}.  For the fine cell (y, x): the axes and the value v_k of the dense-prediction
+ *     section (scale = g / (u g)), its four taps being c[cell][k] + o[img][k] (one rounded add per tap); then for k ascending from 0, S = Tm = 0
+ *     before the first, all f32, every operation rounded on its own:
+ *       r = v_k < 0 ? 0 : v_k (a NaN stays a NaN);  p = r + 0.1f;  S = S + p;  q = p * bins[k];  Tm = Tm + q;      fine[y][x] = Tm / S (IEEE division).
+ *     This is relu, + 0.1, the division by the sum and the expectation over the bin centres, with the division moved behind the sums and the
+ *     upsampling moved behind the convolution (both linear, the weights sum to 1: equal in real arithmetic).
+ *   depth map     d = the value of `fine` resampled from fh x fw to out_h x out_w with the same axis arithmetic, then
+ *     d < min_depth ? min_depth : (d > max_depth ? max_depth : d).  A NaN -- in the fine plane and in the depth map -- is written as the quiet NaN
+ *     0x7fc00000.  Output [n][out_h][out_w] f32.  The step, the quotient and the clamp are ONE definition (csrc/depth_bins.h) for the device kernels
+ *     and for vitx_depth_host: the same bits on any data.
+ * Determinism: an image's outputs are the same bits at any batch size, position in the batch, sub-batch cut and stream count; the forward's
+ *   probabilities and logits are the bits of the same context with last_layer_all_rows = 1 and no head (of the same context, when the last layer is
+ *   not selected); a bank, a gallery, a dense head and a depth head may all be set, none changes another.
+ * vitx_depth_set: Wp host [K][Dc] f32, Wc [K][Dc] or NULL (no class half), bias [K] or NULL (zeros), bins [K] the bin centres; uploads the matrices
+ *   rounded (RNE) to the operand type and padded, allocates per sub-batch slice the operand rows and the logit scratch (vitx_depth_scratch_bytes) and
+ *   the output buffers for the images one pass takes; synchronises the device.  Setting again replaces the head; Wp NULL and K 0 turn the output off
+ *   and free everything.  out_h = out_w = 0: the context's own img_h x img_w.  flags: VITX_DEPTH_NORM (above); VITX_DEPTH_LOGITS: the patch logits
+ *   [Np][K] and the offsets [K] of every image are kept for vitx_depth_read; VITX_DEPTH_FINE: vitx_depth_read may return the fine plane.
+ *   VITX_ERR_ARG: NULL Wp with K > 0, NULL bins; K < 1; Dc != popcount(mask) D; mask bits at or beyond L, or more than 4 of them; a Wp, Wc, bias or
+ *     bins entry that is not finite; a bin <= 0; min_depth > max_depth or either not finite; unknown flags; a negative output side, or one side 0.
+ *   VITX_ERR_UNSUPPORTED: K > 256; upsample not 1, 2 or 4; out_h < fh, out_w < fw or either above 8192; Wc on a context without a class token
+ *     (VITX_POOL_MAP); a ViTSTR context; a pass whose operand rows or logit rows leave the GEMMs' 32-bit byte window (0xf0000000), or of more than
+ *     65535 images.  VITX_ERR_NOMEM: an allocation fails (the head is then off).  All but the last are raised before any device call.
+ * While a head is set, a forward of more than one pass is VITX_ERR_ARG and forwards do not use the hipGraph cache; profiling reports every launch
+ *   of the feature as class "depth".  vitx_group_* has no depth head.
+ * vitx_depth_read: synchronises and copies the last such forward's depth [n][out_h][out_w] and, unless NULL, fine [n][fh][fw] (VITX_DEPTH_FINE),
+ *   logits [n][Np][K] and offsets [n][K] (VITX_DEPTH_LOGITS); VITX_ERR_ARG before any such forward or for an output the flags did not ask for.
+ *   vitx_depth_device: the depth maps on the device, [capacity][out_h][out_w] f32, NULL while off.
+ * The kernels on their own (device pointers; only enqueue; every check before any device call):
+ *   vitx_op_depth_fine: d_logits [n gh gw][ld] f32 (image, then patch in raster order; columns K .. ld never reach a sum: they may hold anything),
+ *     d_offsets [n][ld] f32 or NULL (nothing is added), d_bins [K] -> d_fine [n][u gh][u gw] f32.  VITX_ERR_ARG: a NULL pointer but d_offsets, n, gh, gw,
+ *     K < 1, d_logits or d_offsets off a 16-byte boundary, ld below K rounded up to 4 or no multiple of 4; VITX_ERR_UNSUPPORTED: K > 256, u not in
+ *     {1, 2, 4}, n > 65535, a fine side above 8192.
+ *   vitx_op_depth_resize: d_fine [n][fh][fw] -> d_out [n][out_h][out_w] f32 (any 4-byte alignment), clamped.  VITX_ERR_ARG: a NULL pointer, a side
+ *     < 1, a range that is not finite or not ordered; VITX_ERR_UNSUPPORTED: an output smaller than the plane or above 8192, n > 65535.
+ *   vitx_depth_host: the two on host pointers (offsets [n][ld] or NULL), the same bits; fine unless NULL; makes no device call (any alignment).
+ *   vitx_op_depth: the forward's launches on given operands: d_a [M_pad][Dc] in `dtype` with the n gh gw patch rows (M_pad = that rounded up to 256;
+ *     the call zeroes the rows beyond them), d_wp [K_pad][Dc] (zero rows beyond K); d_acls [n_pad][Dc] (n_pad = n rounded up to 256) and d_wc
+ *     [K_pad][Dc], both or neither; d_bias [K_pad] f32, d_bins [K] -> d_logits [M_pad + 1][K_pad] f32 (scratch and output: the patch logits in its first
+ *     K columns; the last row is the zero bias the call writes), d_offsets [n_pad][K_pad] f32 (class half only), d_fine, d_depth.  VITX_ERR_ARG also for a
+ *     dtype other than VITX_F16 / VITX_BF16 and a pointer off a 16-byte boundary (d_depth: 4); VITX_ERR_UNSUPPORTED also for Dc not a multiple of 64 and
+ *     rows beyond the GEMM's byte window.
+ *   vitx_op_depth_rows: the raw operand rows: d_y[row][0 .. D) in `dtype` (row stride ldy elements) = RNE(d_x[row][0 .. D)) (f32, row stride ldx). */
+enum vitx_depth_flags { VITX_DEPTH_NORM = 1, VITX_DEPTH_LOGITS = 2, VITX_DEPTH_FINE = 4 };
+int vitx_depth_set(vitx_ctx *c, const float *Wp /* host [K][Dc] */, const float *Wc /* host [K][Dc] or NULL */, const float *bias /* [K] or NULL */,
+                   const float *bins /* [K] */, int K, int Dc, uint64_t layer_mask, int upsample, float min_depth, float max_depth,
+                   int out_h, int out_w, int flags);  /* Wp NULL && K == 0: off, frees */
+int vitx_depth_bins(const vitx_ctx *c);               /* K; 0 while off */
+int vitx_depth_shape(const vitx_ctx *c, int *out_h, int *out_w, int *fine_h, int *fine_w);   /* 0 while off */
+int vitx_depth_images(const vitx_ctx *c);
+int vitx_depth_read(vitx_ctx *c, float *depth /* [n][out_h][out_w] */, float *fine /* [n][fh][fw] or NULL */, float *logits /* [n][Np][K] or NULL */,
+                    float *offsets /* [n][K] or NULL */);
+const void *vitx_depth_device(const vitx_ctx *c);     /* [capacity][out_h][out_w] f32; NULL while off */
+size_t vitx_depth_scratch_bytes(const vitx_ctx *c);   /* device bytes of operand rows + logit scratch over all slices; 0 while off */
+int vitx_op_depth_fine(const void *d_logits /* [n gh gw][ld] f32 */, long ld, const void *d_offsets /* [n][ld] or NULL */, const void *d_bins /* [K] */,
+                       int n, int gh, int gw, int K, int upsample, void *d_fine, void *stream);
+int vitx_op_depth_resize(const void *d_fine, int n, int fh, int fw, int out_h, int out_w, float min_depth, float max_depth, void *d_out, void *stream);
+int vitx_depth_host(const float *logits, long ld, const float *offsets, const float *bins, int n, int gh, int gw, int K, int upsample, int out_h, int out_w,
+                    float min_depth, float max_depth, float *depth, float *fine /* or NULL */);
+int vitx_op_depth(int dtype, void *d_a /* [M_pad][Dc] */, const void *d_wp /* [K_pad][Dc] */, void *d_acls /* [n_pad][Dc] or NULL */, const void *d_wc /* or NULL */,
+                  const void *d_bias /* [K_pad] f32 */, const void *d_bins /* [K] */, void *d_logits /* [M_pad + 1][K_pad] f32 */, void *d_offsets /* [n_pad][K_pad] */,
+                  int n, int gh, int gw, int K, int Dc, int upsample, int out_h, int out_w, float min_depth, float max_depth, void *d_fine, void *d_depth, void *stream);
+int vitx_op_depth_rows(int dtype, const void *d_x, long ldx, void *d_y, long ldy, int rows, int D, void *stream);
+
 /* ---- the text tower (CLIP, SigLIP): token ids in, text embeddings out ---------------
  * The text half of a contrastive checkpoint is a second model file in the same container.  Header: hidden_size D, num_hidden_layers L,
  * num_attention_heads H, num_classes = E (the width of the projected embedding), patch_size = 0 (THE mark of a text file: no image file

@@ -36,6 +36,7 @@ KIND_IMAGE, KIND_TEXT = 0, 1            # vitx_model_kind
 TEXT_L2 = 1                             # vitx_text_embed flag
 NN_LOGITS, NN_EMBED = 0, 1              # vitx_nn_source
 DENSE_SCORE, DENSE_LOGITS = 1, 2        # vitx_dense_flags
+DEPTH_NORM, DEPTH_LOGITS, DEPTH_FINE = 1, 2, 4      # vitx_depth_flags
 POS_BICUBIC, POS_BICUBIC_AA = 0, 1      # vitx_pos_interp: F.interpolate(mode="bicubic") without / with antialias=True (include/vitx.h)
 
 EXPORTS = [
@@ -60,6 +61,8 @@ EXPORTS = [
     "vitx_op_nn_select", "vitx_op_nn_finish", "vitx_op_nn_state_bytes", "vitx_op_nn",
     "vitx_dense_set", "vitx_dense_classes", "vitx_dense_shape", "vitx_dense_images", "vitx_dense_read", "vitx_dense_device", "vitx_dense_scratch_bytes",
     "vitx_op_dense_labels", "vitx_dense_labels_host", "vitx_op_dense",
+    "vitx_depth_set", "vitx_depth_bins", "vitx_depth_shape", "vitx_depth_images", "vitx_depth_read", "vitx_depth_device", "vitx_depth_scratch_bytes",
+    "vitx_op_depth_fine", "vitx_op_depth_resize", "vitx_depth_host", "vitx_op_depth", "vitx_op_depth_rows",
     "vitx_model_kind", "vitx_model_text_info", "vitx_model_text_zs", "vitx_text_create", "vitx_text_free", "vitx_text_embed", "vitx_text_embed_device", "vitx_text_shares_weights", "vitx_text_check_ids",
     "vitx_op_text_embed", "vitx_op_text_pool", "vitx_op_attention_text", "vitx_op_attention_generic",
     "vitx_model_rope", "vitx_model_rope_table", "vitx_op_rope",
@@ -265,6 +268,19 @@ def lib():
             L.vitx_op_dense_labels.argtypes = [vp, C.c_long, ip, ip, ip, ip, ip, ip, vp, vp, vp]
             L.vitx_dense_labels_host.argtypes = [vp, C.c_long, ip, ip, ip, ip, ip, ip, vp, vp]
             L.vitx_op_dense.argtypes = [ip, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, ip, vp, vp, vp]
+        if hasattr(L, "vitx_depth_set"):
+            fp, intp, cf = C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_float
+            L.vitx_depth_set.argtypes = [vp, fp, fp, fp, fp, ip, ip, C.c_uint64, ip, cf, cf, ip, ip, ip]
+            L.vitx_depth_bins.argtypes = [vp]; L.vitx_depth_images.argtypes = [vp]
+            L.vitx_depth_shape.argtypes = [vp, intp, intp, intp, intp]
+            L.vitx_depth_read.argtypes = [vp, fp, fp, fp, fp]
+            L.vitx_depth_device.restype = C.c_void_p; L.vitx_depth_device.argtypes = [vp]
+            L.vitx_depth_scratch_bytes.restype = C.c_size_t; L.vitx_depth_scratch_bytes.argtypes = [vp]
+            L.vitx_op_depth_fine.argtypes = [vp, C.c_long, vp, vp, ip, ip, ip, ip, ip, vp, vp]
+            L.vitx_op_depth_resize.argtypes = [vp, ip, ip, ip, ip, ip, cf, cf, vp, vp]
+            L.vitx_depth_host.argtypes = [vp, C.c_long, vp, vp, ip, ip, ip, ip, ip, ip, ip, cf, cf, vp, vp]
+            L.vitx_op_depth.argtypes = [ip, vp, vp, vp, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, ip, ip, cf, cf, vp, vp, vp]
+            L.vitx_op_depth_rows.argtypes = [ip, vp, C.c_long, vp, C.c_long, ip, ip, vp]
         if hasattr(L, "vitx_text_create"):
             i32p = C.POINTER(C.c_int32)
             L.vitx_model_kind.argtypes = [vp]
@@ -873,6 +889,76 @@ class Context:
     def dense_scratch_bytes(self) -> int:
         return int(lib().vitx_dense_scratch_bytes(self._h))
 
+    def depth_set(self, wp: Optional[np.ndarray], wc: Optional[np.ndarray] = None, bias: Optional[np.ndarray] = None, bins: Optional[np.ndarray] = None,
+                  layers=None, upsample: int = 4, min_depth: float = 0.001, max_depth: float = 10.0, out_shape: Optional[Tuple[int, int]] = None,
+                  norm: bool = False, logits: bool = False, fine: bool = False) -> None:
+        """A binned depth head for every later forward (vitx_depth_set): `wp` [K, Dc] f32 over the patch tokens of `layers` (indices; None: the last
+        layer), `wc` [K, Dc] over the class tokens (None: no class half), `bias` [K], `bins` [K] the bin centres; per image a depth map [out_h, out_w]
+        f32 (`out_shape` None: the context's image shape).  `norm`: the rows are the final-norm features, not the raw residual stream; `logits` /
+        `fine`: the patch logits and offsets / the fine plane are kept for depth_read.  wp None turns the output off and frees its buffers."""
+        fp = C.POINTER(C.c_float)
+        if wp is None:
+            check(lib().vitx_depth_set(self._h, None, None, None, None, 0, 0, 0, 0, 0.0, 0.0, 0, 0, 0), "vitx_depth_set")
+            return
+        w = np.ascontiguousarray(wp, dtype=np.float32)
+        if w.ndim != 2:
+            raise ValueError("depth_set: wp must be [K, Dc]")
+        K = w.shape[0]
+
+        def opt(a, shape, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != shape:
+                raise ValueError(f"depth_set: {name} must be {list(shape)}")
+            return a
+        c, b, bn = opt(wc, w.shape, "wc"), opt(bias, (K,), "bias"), opt(bins, (K,), "bins")
+        if bn is None:
+            raise ValueError("depth_set: bins [K] are required")
+        mask = 0
+        for l in ([] if layers is None else layers):
+            if not 0 <= int(l) < 64:
+                raise ValueError(f"depth_set: layer {l} outside 0 .. 63")
+            mask |= 1 << int(l)
+        oh, ow = (0, 0) if out_shape is None else (int(out_shape[0]), int(out_shape[1]))
+        ptr = lambda a: a.ctypes.data_as(fp) if a is not None else None
+        check(lib().vitx_depth_set(self._h, ptr(w), ptr(c), ptr(b), ptr(bn), K, w.shape[1], mask, int(upsample), float(min_depth), float(max_depth), oh, ow,
+                                   (DEPTH_NORM if norm else 0) | (DEPTH_LOGITS if logits else 0) | (DEPTH_FINE if fine else 0)), "vitx_depth_set")
+        self._depth_flags = (bool(logits), bool(fine))
+
+    def depth_shape(self) -> Tuple[int, int, int, int]:
+        """(out_h, out_w, fine_h, fine_w); zeros while off."""
+        v = [C.c_int(0) for _ in range(4)]
+        check(lib().vitx_depth_shape(self._h, *[C.byref(x) for x in v]), "vitx_depth_shape")
+        return tuple(x.value for x in v)
+
+    def depth_read(self, n: Optional[int] = None):
+        """(depth [n, out_h, out_w] f32, fine [n, fh, fw] or None, logits [n, Np, K] or None, offsets [n, K] or None) of the last forward made with a
+        depth head set.  `n`, if given, must be that batch."""
+        L = lib()
+        have, K = L.vitx_depth_images(self._h), L.vitx_depth_bins(self._h)
+        if n is not None and n != have:
+            raise ValueError(f"depth_read: the last forward with a depth head set had {have} images, not {n}")
+        oh, ow, fh, fw = self.depth_shape()
+        gh, gw = self.grid_hw
+        want_logits, want_fine = getattr(self, "_depth_flags", (False, False)) if K else (False, False)
+        m = max(have, 1)
+        depth = np.empty((m, max(oh, 1), max(ow, 1)), np.float32)
+        fine = np.empty((m, max(fh, 1), max(fw, 1)), np.float32) if want_fine else None
+        logits = np.empty((m, gh * gw, max(K, 1)), np.float32) if want_logits else None
+        offsets = np.empty((m, max(K, 1)), np.float32) if want_logits else None
+        fp = C.POINTER(C.c_float)
+        ptr = lambda a: a.ctypes.data_as(fp) if a is not None else None
+        check(L.vitx_depth_read(self._h, ptr(depth), ptr(fine), ptr(logits), ptr(offsets)), "vitx_depth_read")
+        return depth, fine, logits, offsets
+
+    def depth_device(self) -> Tuple[int, Tuple[int, int]]:
+        """(device pointer of the depth maps [capacity][out_h][out_w] f32, (out_h, out_w)) for callers that stay on the GPU; (0, (0, 0)) while off."""
+        return int(lib().vitx_depth_device(self._h) or 0), self.depth_shape()[:2]
+
+    def depth_scratch_bytes(self) -> int:
+        return int(lib().vitx_depth_scratch_bytes(self._h))
+
     def synchronize(self) -> None:
         check(lib().vitx_ctx_synchronize(self._h), "vitx_ctx_synchronize")
 
@@ -1214,6 +1300,78 @@ def dense_head(path: str) -> dict:
     if names is not None and len(names) != w.shape[0]:
         raise ValueError(f"{path}: {len(names)} names for {w.shape[0]} classes")
     return {"weight": w, "bias": b, "layers": layers, "names": names}
+
+
+def op_depth_fine(d_logits: int, ld: int, d_offsets: int, d_bins: int, n: int, gh: int, gw: int, K: int, upsample: int, d_fine: int, stream: int = 0) -> None:
+    """vitx_op_depth_fine: logits [n gh gw, ld] f32 (+ offsets [n, ld] or 0) and bins [K] on the device -> fine [n, u gh, u gw] f32."""
+    check(lib().vitx_op_depth_fine(d_logits or None, ld, d_offsets or None, d_bins or None, n, gh, gw, K, upsample, d_fine or None, stream or None), "vitx_op_depth_fine")
+
+
+def op_depth_resize(d_fine: int, n: int, fh: int, fw: int, out_h: int, out_w: int, min_depth: float, max_depth: float, d_out: int, stream: int = 0) -> None:
+    """vitx_op_depth_resize: fine [n, fh, fw] f32 on the device -> depth [n, out_h, out_w] f32, resampled bilinearly and clamped."""
+    check(lib().vitx_op_depth_resize(d_fine or None, n, fh, fw, out_h, out_w, min_depth, max_depth, d_out or None, stream or None), "vitx_op_depth_resize")
+
+
+def depth_host(logits: np.ndarray, offsets: Optional[np.ndarray], bins: np.ndarray, n: int, gh: int, gw: int, K: int, upsample: int, out_h: int, out_w: int,
+               min_depth: float, max_depth: float):
+    """vitx_depth_host: the two depth kernels' arithmetic on the host.  logits [n gh gw, ld] f32, offsets [n, ld] or None, bins [K] ->
+    (depth [n, out_h, out_w] f32, fine [n, u gh, u gw] f32)."""
+    lg = np.ascontiguousarray(logits, np.float32)
+    if lg.ndim != 2 or lg.shape[0] != n * gh * gw:
+        raise ValueError("depth_host: logits must be [n gh gw, ld]")
+    off = None if offsets is None else np.ascontiguousarray(offsets, np.float32)
+    if off is not None and off.shape != (n, lg.shape[1]):
+        raise ValueError("depth_host: offsets must be [n, ld]")
+    bn = np.ascontiguousarray(bins, np.float32)
+    if bn.ndim != 1 or bn.shape[0] < K:
+        raise ValueError("depth_host: bins must be [K]")
+    depth = np.empty((n, max(out_h, 1), max(out_w, 1)), np.float32)
+    fine = np.empty((n, max(upsample * gh, 1), max(upsample * gw, 1)), np.float32)
+    check(lib().vitx_depth_host(lg.ctypes.data, lg.shape[1], off.ctypes.data if off is not None else None, bn.ctypes.data, n, gh, gw, K, upsample, out_h, out_w,
+                                min_depth, max_depth, depth.ctypes.data, fine.ctypes.data), "vitx_depth_host")
+    return depth, fine
+
+
+def op_depth(dtype: int, d_a: int, d_wp: int, d_acls: int, d_wc: int, d_bias: int, d_bins: int, d_logits: int, d_offsets: int, n: int, gh: int, gw: int, K: int,
+             Dc: int, upsample: int, out_h: int, out_w: int, min_depth: float, max_depth: float, d_fine: int, d_depth: int, stream: int = 0) -> None:
+    """vitx_op_depth: the depth head's launches on given operands (device pointers): d_a [M_pad, Dc] `dtype` (M_pad = n gh gw rounded up to 256), d_wp and
+    d_wc [K_pad, Dc], d_acls [n_pad, Dc] (d_acls = d_wc = 0: no class half), d_bias [K_pad] f32, d_bins [K] -> d_logits [M_pad + 1, K_pad] f32, d_offsets
+    [n_pad, K_pad] f32, d_fine, d_depth."""
+    check(lib().vitx_op_depth(dtype, d_a or None, d_wp or None, d_acls or None, d_wc or None, d_bias or None, d_bins or None, d_logits or None, d_offsets or None,
+                              n, gh, gw, K, Dc, upsample, out_h, out_w, min_depth, max_depth, d_fine or None, d_depth or None, stream or None), "vitx_op_depth")
+
+
+def op_depth_rows(dtype: int, d_x: int, ldx: int, d_y: int, ldy: int, rows: int, D: int, stream: int = 0) -> None:
+    """vitx_op_depth_rows: f32 rows (stride ldx) -> rows of `dtype` (stride ldy elements), rounded to nearest even."""
+    check(lib().vitx_op_depth_rows(dtype, d_x or None, ldx, d_y or None, ldy, rows, D, stream or None), "vitx_op_depth_rows")
+
+
+def depth_bins(K: int, lo: float, hi: float, kind: str = "UD") -> np.ndarray:
+    """The K bin centres of a depth head between lo and hi: "UD" linspace, "SID" logspace (mmseg's bins_strategy), computed in float64 and
+    rounded once to f32."""
+    if K < 1 or not (0.0 < lo <= hi) or not np.isfinite(hi):
+        raise ValueError("depth_bins: K >= 1 and 0 < lo <= hi")
+    if kind == "UD":
+        return np.linspace(np.float64(lo), np.float64(hi), K).astype(np.float32)
+    if kind == "SID":
+        return np.logspace(np.log10(np.float64(lo)), np.log10(np.float64(hi)), K).astype(np.float32)
+    raise ValueError(f"depth_bins: kind {kind!r} is neither 'UD' nor 'SID'")
+
+
+def depth_head(path: str) -> dict:
+    """A depth head file (convert.depth_head / convert.py --depth-head-out): an .npz with wp [K, Dc] f32, optionally wc [K, Dc], bias [K], bins [K],
+    layers (indices), upsample, min_depth, max_depth and norm.  Returns a dict with those keys (wc None when absent)."""
+    with np.load(path, allow_pickle=False) as z:
+        for k in ("wp", "bias", "bins", "layers", "upsample", "min_depth", "max_depth", "norm"):
+            if k not in z:
+                raise ValueError(f"{path}: a depth head file holds wp, bias, bins, layers, upsample, min_depth, max_depth and norm (no {k})")
+        wp, b, bn = (np.ascontiguousarray(z[k], np.float32) for k in ("wp", "bias", "bins"))
+        wc = np.ascontiguousarray(z["wc"], np.float32) if "wc" in z else None
+        layers = [int(l) for l in np.asarray(z["layers"]).reshape(-1)]
+        u, lo, hi, norm = int(z["upsample"]), float(z["min_depth"]), float(z["max_depth"]), bool(z["norm"])
+    if wp.ndim != 2 or b.shape != (wp.shape[0],) or bn.shape != (wp.shape[0],) or (wc is not None and wc.shape != wp.shape):
+        raise ValueError(f"{path}: wp (and wc) must be [K, Dc], bias and bins [K]")
+    return {"wp": wp, "wc": wc, "bias": b, "bins": bn, "layers": layers, "upsample": u, "min_depth": lo, "max_depth": hi, "norm": norm}
 
 
 def round_operand(x: np.ndarray, dtype: int) -> np.ndarray:

@@ -14,6 +14,7 @@ directory-walk accuracy harness:
     python vit_cli.py -m model.gguf --gallery-build DIR --gallery-out g.npz [--nn-source embed|logits]   # embed DIR/<label>/* into a gallery
     python vit_cli.py -m model.gguf -i image.jpg --gallery g.npz -k 5 [--nn-temperature 0.07]   # the k nearest gallery images and the k-NN vote of their labels
     python vit_cli.py -m backbone.gguf -i image.jpg --dense-head head.npz --dense-out labels.pgm [--img-shape HxW | --img-fit SHORT]   # a label per pixel (P5 picture of class bytes)
+    python vit_cli.py -m backbone.gguf -i image.jpg --depth-head head.npz --depth-out depth.npy [--img-shape HxW | --img-fit SHORT]   # a depth per pixel (float32 .npy)
 
 --preprocess model follows the file's `preproc` tensor (include/vitx.h "each model's own preprocessing": what convert.py reads from a
 HuggingFace preprocessor_config.json -- CLIP: Pillow-bicubic shortest edge 224, centre crop 224, CLIP's mean / std; DINOv2: shortest edge 256,
@@ -117,6 +118,9 @@ def make_parser() -> argparse.ArgumentParser:
                     help="with -i: a linear head over the patch tokens (convert.py --dense-head-out: weight, bias, layers, names): the label of every pixel of the "
                          "preprocessed image goes to --dense-out, the share of every class is printed as ' > name : 0.xx'")
     ap.add_argument("--dense-out", default=None, metavar="PATH", help="with --dense-head: the label map as a binary PGM (P5) of class bytes, img_w x img_h")
+    ap.add_argument("--depth-head", default=None, metavar="HEAD.npz",
+                    help="with -i: a binned linear depth head (convert.py --depth-head-out): the depth of every pixel of the preprocessed image goes to --depth-out")
+    ap.add_argument("--depth-out", default=None, metavar="PATH.npy", help="with --depth-head: the depth map as a float32 .npy array [img_h, img_w]")
     return ap
 
 
@@ -191,6 +195,10 @@ def main(argv: List[str] | None = None) -> int:
         ap.error("--dense-head HEAD.npz and --dense-out PATH go together")
     if a.dense_head and (a.dir is not None or a.gallery_build or a.gallery):
         ap.error("--dense-head labels the single image of -i")
+    if bool(a.depth_head) != bool(a.depth_out):
+        ap.error("--depth-head HEAD.npz and --depth-out PATH.npy go together")
+    if a.depth_head and (a.dir is not None or a.gallery_build or a.gallery or a.dense_head):
+        ap.error("--depth-head measures the single image of -i (and not together with --dense-head)")
     if a.gallery and (a.dir is not None or a.gallery_build):
         ap.error("--gallery searches for the single image of -i")
     if sum(bool(v) for v in (a.img_size, a.img_shape, a.img_fit)) > 1:
@@ -287,6 +295,14 @@ def main(argv: List[str] | None = None) -> int:
             print(f"main: failed to load the dense head from '{a.dense_head}': {e}", file=sys.stderr)
             return 1
 
+    depth = None
+    if a.depth_head:
+        try:
+            depth = binding.depth_head(a.depth_head)
+        except (OSError, ValueError, KeyError) as e:
+            print(f"main: failed to load the depth head from '{a.depth_head}': {e}", file=sys.stderr)
+            return 1
+
     if a.dir is None:
         try:
             img0 = _decode(a.inp)
@@ -333,7 +349,22 @@ def main(argv: List[str] | None = None) -> int:
             except binding.VitxError as e:
                 print(f"main: the head of '{a.dense_head}' does not fit this model: {e}", file=sys.stderr)
                 return 1
+        if depth:
+            try:
+                ctx.depth_set(depth["wp"], depth["wc"], depth["bias"], depth["bins"], depth["layers"], depth["upsample"], depth["min_depth"], depth["max_depth"],
+                              norm=depth["norm"])
+            except binding.VitxError as e:
+                print(f"main: the head of '{a.depth_head}' does not fit this model: {e}", file=sys.stderr)
+                return 1
         probs = ctx.forward(img1[None])[0]
+        if depth:
+            dm = ctx.depth_read(1)[0][0]
+            with open(a.depth_out, "wb") as f:
+                np.save(f, dm)
+            print(f"main: wrote the {dm.shape[1]} x {dm.shape[0]} depth map to '{a.depth_out}'", file=sys.stderr)
+            print("", file=sys.stderr)
+            print(f" > depth : min {float(np.nanmin(dm)):.3f} median {float(np.nanmedian(dm)):.3f} max {float(np.nanmax(dm)):.3f}")
+            return 0
         if dense:
             lab = ctx.dense_read(1)[0][0]
             with open(a.dense_out, "wb") as f:

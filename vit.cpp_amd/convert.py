@@ -905,7 +905,77 @@ def _main_dense_head(argv) -> int:
     return 0
 
 
+# ---- depth heads (include/vitx.h "depth estimation"): an mmseg-style binned depth head's state dict -> the .npz binding.depth_head reads ------
+def depth_head(state_dict, layers, hidden_size, min_depth=0.001, max_depth=10.0, bins="UD", upsample=4, norm=False):
+    """The binned linear depth head of a DINOv2-style depther checkpoint as {"wp" [K, m D], "wc" [K, m D] or None, "bias" [K], "bins" [K], "layers",
+    "upsample", "min_depth", "max_depth", "norm"}: decode_head.conv_depth.weight [K, 2 m D, 1, 1] (or [K, 2 m D]) and .bias [K].  Per layer the D patch
+    columns come first, then the D class columns (the class token is concatenated to every patch token); they are split into wp and wc.  A width of
+    m D is a head without a class half (wc None); any other width is refused by name.  bins: "UD" / "SID" centres between min_depth and max_depth."""
+    from . import binding
+    sd = state_dict.get("state_dict", state_dict)
+    get = lambda k: np.asarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], np.float64)
+    layers = [int(l) for l in layers]
+    if not layers or len(layers) > 4 or sorted(set(layers)) != layers or layers[0] < 0:
+        raise ValueError(f"depth_head: layers {layers} must be 1 to 4 ascending, distinct layer indices")
+    wkey, bkey = "decode_head.conv_depth.weight", "decode_head.conv_depth.bias"
+    if wkey not in sd or bkey not in sd:
+        raise ValueError(f"depth_head: no {wkey} / {bkey} in the state dict")
+    W, b = get(wkey), get(bkey)
+    if W.ndim == 4 and W.shape[2:] == (1, 1):
+        W = W[:, :, 0, 0]
+    if W.ndim != 2 or b.shape != (W.shape[0],):
+        raise ValueError(f"depth_head: {wkey} {tuple(get(wkey).shape)} is not [K, C, 1, 1] or [K, C] with {bkey} [K]")
+    K, width = W.shape
+    m, D = len(layers), int(hidden_size)
+    if width == 2 * m * D:
+        blocks = W.reshape(K, m, 2, D)
+        wp, wc = blocks[:, :, 0, :].reshape(K, m * D), blocks[:, :, 1, :].reshape(K, m * D)
+    elif width == m * D:
+        wp, wc = W, None
+    else:
+        raise ValueError(f"depth_head: {wkey} has width {width}, the backbone gives {m} layers x hidden size {D}: {2 * m * D} with the class token, {m * D} without")
+    if not (np.isfinite(W).all() and np.isfinite(b).all()):
+        raise ValueError("depth_head: the head is not finite")
+    if int(upsample) not in (1, 2, 4):
+        raise ValueError(f"depth_head: upsample {upsample} is not 1, 2 or 4")
+    return {"wp": np.ascontiguousarray(wp, np.float32), "wc": None if wc is None else np.ascontiguousarray(wc, np.float32), "bias": b.astype(np.float32),
+            "bins": binding.depth_bins(K, float(min_depth), float(max_depth), bins), "layers": layers, "upsample": int(upsample),
+            "min_depth": float(min_depth), "max_depth": float(max_depth), "norm": bool(norm)}
+
+
+def write_depth_head(path, head) -> None:
+    """The .npz binding.depth_head reads."""
+    arrays = dict(wp=np.asarray(head["wp"], np.float32), bias=np.asarray(head["bias"], np.float32), bins=np.asarray(head["bins"], np.float32),
+                  layers=np.asarray(head["layers"], np.int32), upsample=np.int32(head["upsample"]), min_depth=np.float64(head["min_depth"]),
+                  max_depth=np.float64(head["max_depth"]), norm=np.bool_(head["norm"]))
+    if head.get("wc") is not None:
+        arrays["wc"] = np.asarray(head["wc"], np.float32)
+    with open(path, "wb") as f:
+        np.savez(f, **arrays)
+
+
+def _main_depth_head(argv) -> int:
+    ap = argparse.ArgumentParser(description="a binned linear depth head checkpoint (.pth) -> a depth head file (.npz) for vit_cli.py --depth-head")
+    ap.add_argument("--depth-head-in", required=True, metavar="CKPT.pth", help="torch-saved state dict with decode_head.conv_depth.weight / .bias")
+    ap.add_argument("--depth-head-out", required=True, metavar="HEAD.npz")
+    ap.add_argument("--depth-layers", required=True, metavar="L1,L2,..", help="the backbone layers (0-based, ascending) whose tokens the head reads, e.g. 2,5,8,11")
+    ap.add_argument("--depth-hidden", type=int, required=True, metavar="D", help="the backbone's hidden size: it splits the head into its patch and class halves")
+    ap.add_argument("--depth-min", type=float, default=0.001); ap.add_argument("--depth-max", type=float, default=10.0)
+    ap.add_argument("--depth-bins", default="UD", choices=["UD", "SID"], help="bin centres: uniform (default) or log-spaced")
+    ap.add_argument("--depth-upsample", type=int, default=4, choices=[1, 2, 4])
+    ap.add_argument("--depth-norm", action="store_true", help="the head was trained on final-norm tokens (default: the raw residual stream)")
+    a = ap.parse_args(argv)
+    import torch
+    sd = torch.load(a.depth_head_in, map_location="cpu", weights_only=True)
+    head = depth_head(sd, [int(x) for x in a.depth_layers.split(",")], a.depth_hidden, a.depth_min, a.depth_max, a.depth_bins, a.depth_upsample, a.depth_norm)
+    write_depth_head(a.depth_head_out, head)
+    print(f"wrote {a.depth_head_out}: {head['wp'].shape[0]} bins, width {head['wp'].shape[1]}, layers {head['layers']}, class half: {'yes' if head['wc'] is not None else 'no'}")
+    return 0
+
+
 def main(argv=None) -> int:
+    if any(str(x).split("=")[0] == "--depth-head-in" for x in (sys.argv[1:] if argv is None else argv)):
+        return _main_depth_head(argv)
     if any(str(x).split("=")[0] == "--dense-head-in" for x in (sys.argv[1:] if argv is None else argv)):
         return _main_dense_head(argv)          # a head is a file of its own: no model file is read or written
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])

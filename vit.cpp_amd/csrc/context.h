@@ -1,5 +1,6 @@
 // context.h -- the execution context (struct vitx_ctx) as context.cpp, forward.cpp, outputs.cpp and ops.cpp share it: what a forward uses.
-// The weights it reads are a WeightSet (weights.h).  Internal: nothing outside those four files includes it; callers see the opaque vitx_ctx
+// The weights it reads are a WeightSet (weights.h).  Internal: nothing outside those four files includes it (depth_host.cpp does, for the
+// argument checks it shares with ops.cpp and the error text); callers see the opaque vitx_ctx
 // of include/vitx.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -15,11 +16,11 @@ namespace vitx {
 
 enum ProfClass {
     PC_GEMM_PATCH = 0, PC_LAYERNORM, PC_GEMM_QKV, PC_ATTENTION, PC_GEMM_PROJ, PC_GEMM_FC1, PC_GEMM_FC2,
-    PC_GEMM_HEAD, PC_SOFTMAX, PC_DEQUANT, PC_ATTENTION_CLS, PC_GEMM_TAIL, PC_ATTN_MAP, PC_FEATURES, PC_HEAD_POOL, PC_ZEROSHOT, PC_ROPE, PC_SWIGLU, PC_NN, PC_DENSE, PC_COUNT
+    PC_GEMM_HEAD, PC_SOFTMAX, PC_DEQUANT, PC_ATTENTION_CLS, PC_GEMM_TAIL, PC_ATTN_MAP, PC_FEATURES, PC_HEAD_POOL, PC_ZEROSHOT, PC_ROPE, PC_SWIGLU, PC_NN, PC_DENSE, PC_DEPTH, PC_COUNT
 };
 inline const char *const kProfNames[PC_COUNT] = {"patch_embed", "layernorm", "gemm_qkv_bias", "attention", "gemm_proj_resid",
                                     "gemm_fc1_gelu", "gemm_fc2_resid", "gemm_head", "softmax", "dequant_weights", "attention_cls", "gemm_cls_tail", "attention_map",
-                                    "features", "head_pool", "zeroshot", "rope", "swiglu", "nn", "dense"};
+                                    "features", "head_pool", "zeroshot", "rope", "swiglu", "nn", "dense", "depth"};
 static_assert(PC_COUNT <= VITX_PROF_MAX_CLASSES, "vitx_profile_read callers size their arrays by VITX_PROF_MAX_CLASSES");
 
 static_assert(VITX_F16 == DT_F16 && VITX_BF16 == DT_BF16, "the API's dtype values are handed to the launchers as they are");
@@ -260,6 +261,41 @@ struct vitx_ctx {
         for (void **p : {&dn_W, (void **)&dn_bias, (void **)&dn_labels, (void **)&dn_score, (void **)&dn_logits}) { if (*p) (void)hipFree(*p); *p = nullptr; }
         dn_K = dn_Kpad = dn_Dc = dn_oh = dn_ow = dn_flags = dn_cap = dn_n = 0; dn_mask = 0; dn_scratch = 0;
     }
+    // the depth head (vitx_depth_set): nothing is allocated or launched while dp_K == 0
+    int dp_K = 0, dp_Kpad = 0;   // bins of the head; its rows on the device (K rounded up to the GEMM's column tile `tn`, zero rows beyond K)
+    int dp_Dc = 0;               // the operand's width: popcount(dp_mask) * D
+    uint64_t dp_mask = 0;        // selected layers (never 0 while on)
+    int dp_u = 0;                // the fine plane is dp_u gh x dp_u gw
+    int dp_oh = 0, dp_ow = 0;    // the depth map's shape
+    float dp_lo = 0.0f, dp_hi = 0.0f;    // the clamp
+    int dp_flags = 0;            // VITX_DEPTH_*
+    int dp_cap = 0;              // images the output buffers hold (= the images one pass takes)
+    int dp_n = 0;                // images of the last forward made with a head set (0: none since vitx_depth_set)
+    void *dp_Wp = nullptr;       // [dp_Kpad][dp_Dc] operand type: the patch half
+    void *dp_Wc = nullptr;       // the class half, or nullptr: the offsets are the bias then, and no class rows are written
+    float *dp_bias = nullptr;    // [dp_Kpad] f32, zeros beyond K: the class GEMM's bias, or every image's offsets
+    float *dp_zero = nullptr;    // [dp_Kpad] zeros: the patch GEMM's bias
+    float *dp_bins = nullptr;    // [dp_Kpad] f32 bin centres
+    std::vector<float> dp_bias_host;     // [dp_K]: what vitx_depth_read returns as offsets of a head without a class half
+    float *dp_depth = nullptr;   // [dp_cap][dp_oh][dp_ow]
+    float *dp_fine = nullptr;    // [dp_cap][dp_u gh][dp_u gw]: the resize reads it; vitx_depth_read returns it under VITX_DEPTH_FINE
+    float *dp_logits = nullptr;  // VITX_DEPTH_LOGITS: [dp_cap][gh * gw][dp_K], the patch logits kept for vitx_depth_read
+    float *dp_off = nullptr;     // VITX_DEPTH_LOGITS with a class half: [dp_cap][dp_K], the offsets kept
+    std::vector<void *> dp_a;    // per slice: [round_up(slice cap * gh * gw, tm)][dp_Dc] operand type, the patch GEMM's A rows
+    std::vector<float *> dp_acc; // per slice: [the same rows][dp_Kpad] f32, the patch logits
+    std::vector<void *> dp_ac;   // per slice, class half only: [round_up(slice cap, tm)][dp_Dc] operand type, the class rows
+    std::vector<float *> dp_o;   // per slice, class half only: [round_up(slice cap, tm)][dp_Kpad] f32, the offsets
+    size_t dp_scratch = 0;       // bytes of dp_a + dp_acc + dp_ac + dp_o over all slices
+    bool depth_on() const { return dp_K != 0; }
+    // a selected last layer needs every row of it (as with the dense head)
+    bool depth_last_all_rows() const { return depth_on() && ((dp_mask >> (L - 1)) & 1); }
+    void depth_free() {
+        for (auto *v : {&dp_a, &dp_ac}) { for (void *p : *v) if (p) (void)hipFree(p); v->clear(); }
+        for (auto *v : {&dp_acc, &dp_o}) { for (float *p : *v) if (p) (void)hipFree(p); v->clear(); }
+        for (void **p : {&dp_Wp, &dp_Wc, (void **)&dp_bias, (void **)&dp_zero, (void **)&dp_bins, (void **)&dp_depth, (void **)&dp_fine, (void **)&dp_logits, (void **)&dp_off}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+        dp_bias_host.clear();
+        dp_K = dp_Kpad = dp_Dc = dp_u = dp_oh = dp_ow = dp_flags = dp_cap = dp_n = 0; dp_mask = 0; dp_scratch = 0; dp_lo = dp_hi = 0.0f;
+    }
     // hipGraph cache of the single-stream (small-batch) forward, opt-in (vitx_ctx_options::graph).  Key = (images, batch, outputs): the graph
     // bakes the pointers in.  An entry is captured the second time in a row its key is seen (one-off calls are never captured).
     // Measured (profiles/r02f/hipgraph_small_batch.txt): replaying the ~100 dependent launches as a graph takes the enqueue work off
@@ -294,6 +330,7 @@ struct vitx_ctx {
         zs_free();
         nn_free();
         dense_free();
+        depth_free();
         for (void *p : allocs) (void)hipFree(p);
         if (stream) (void)hipStreamDestroy(stream);
     }
@@ -308,6 +345,12 @@ struct vitx_ctx {
         return ev_pool[ev_used++];
     }
 };
+
+namespace vitx {
+// the argument checks vitx_op_depth_fine / vitx_op_depth_resize / vitx_op_depth (ops.cpp) share with vitx_depth_host (depth_host.cpp): none needs a device
+int depth_fine_args(const char *name, const void *logits, long ld, const void *bins, int n, int gh, int gw, int K, int u, const void *fine);
+int depth_resize_args(const char *name, const void *fine, int n, int fh, int fw, int out_h, int out_w, float lo, float hi, const void *out);
+}  // namespace vitx
 
 struct ProfScope {
     vitx_ctx *c; hipStream_t s; size_t idx = 0; bool on;

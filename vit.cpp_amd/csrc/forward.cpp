@@ -240,6 +240,52 @@ struct SliceForward {
         if (c->dn_logits) HIP_TRY(hipMemcpy2DAsync(c->dn_logits + (size_t)first_img * Np * K, (size_t)K * 4, acc, (size_t)Kpad * 4, (size_t)K * 4, rows, hipMemcpyDeviceToDevice, st));
         return VITX_OK;
     }
+    // The depth head (vitx_depth_set).  depth_rows, where dense_rows is called: the patch rows of layer il -- raw f32 residual stream through the
+    // streaming conversion, or (VITX_DEPTH_NORM) the final norm through the stand-alone LayerNorm as dense_rows does -- into columns slot * D .. of the
+    // slice's compact operand rows, and with a class half the class-token row of every image the same way (one row per group).  depth_head, after
+    // the classifier: the patch logits (zero bias) and the offsets (the head's bias) through the dispatcher, the fine plane, the depth map.
+    int depth_rows(int il) {
+        if (!c->depth_on() || !((c->dp_mask >> il) & 1)) return VITX_OK;
+        const int Np = N - c->Tp, Dc = c->dp_Dc, rows = n * Np;
+        const size_t si = &sl - &c->slices[0], col = (size_t)layer_slot(c->dp_mask, il) * D * 2;
+        const bool norm = (c->dp_flags & VITX_DEPTH_NORM) != 0;
+        {
+            ProfScope ps(c, st, PC_DEPTH, 0, (double)rows * D * (4 + eb));
+            if (norm) HIP_TRY(launch_layernorm(dt, sl.X + (size_t)c->Tp * D, D, ws.norm_w, ws.norm_b, (char *)c->dp_a[si] + col, Dc, rows, D, c->hp.eps, st, Np, (long)N * D));
+            else HIP_TRY(launch_depth_rows(dt, sl.X + (size_t)c->Tp * D, D, (char *)c->dp_a[si] + col, Dc, rows, D, st, Np, (long)N * D));
+        }
+        if (!c->dp_Wc) return VITX_OK;
+        ProfScope ps(c, st, PC_DEPTH, 0, (double)n * D * (4 + eb));
+        if (norm) HIP_TRY(launch_layernorm(dt, sl.X, (long)N * D, ws.norm_w, ws.norm_b, (char *)c->dp_ac[si] + col, Dc, n, D, c->hp.eps, st));
+        else HIP_TRY(launch_depth_rows(dt, sl.X, (long)N * D, (char *)c->dp_ac[si] + col, Dc, n, D, st));
+        return VITX_OK;
+    }
+    int depth_head() {
+        int rc;
+        const int Np = N - c->Tp, Dc = c->dp_Dc, K = c->dp_K, Kpad = c->dp_Kpad, rows = n * Np, Mr = round_up(rows, tm), Mc = round_up(n, tm), u = c->dp_u;
+        const size_t si = &sl - &c->slices[0], px = (size_t)c->dp_oh * c->dp_ow, fpx = (size_t)u * c->gh * u * c->gw;
+        void *a = c->dp_a[si]; float *acc = c->dp_acc[si];
+        if (Mr > rows) HIP_TRY(hipMemsetAsync((char *)a + (size_t)rows * Dc * 2, 0, (size_t)(Mr - rows) * Dc * 2, st));
+        if ((rc = gemm(c, st, PC_DEPTH, EPI_BIAS_F32, dense_gemm(a, c->dp_Wp, c->dp_zero, acc, Mr, rows, K, Kpad, Dc, Kpad)))) return rc;
+        const float *off = c->dp_bias; long ldo = 0;
+        if (c->dp_Wc) {
+            if (Mc > n) HIP_TRY(hipMemsetAsync((char *)c->dp_ac[si] + (size_t)n * Dc * 2, 0, (size_t)(Mc - n) * Dc * 2, st));
+            if ((rc = gemm(c, st, PC_DEPTH, EPI_BIAS_F32, dense_gemm(c->dp_ac[si], c->dp_Wc, c->dp_bias, c->dp_o[si], Mc, n, K, Kpad, Dc, Kpad)))) return rc;
+            off = c->dp_o[si]; ldo = Kpad;
+        }
+        float *fine = c->dp_fine + (size_t)first_img * fpx;
+        {
+            ProfScope ps(c, st, PC_DEPTH, 11.0 * n * (double)fpx * K, (double)rows * Kpad * 4 + (double)n * fpx * 4);
+            HIP_TRY(launch_depth_fine(acc, Kpad, off, ldo, c->dp_bins, n, c->gh, c->gw, K, u, fine, st));
+        }
+        {
+            ProfScope ps(c, st, PC_DEPTH, 7.0 * n * (double)px, (double)n * (fpx + px) * 4);
+            HIP_TRY(launch_depth_resize(fine, n, u * c->gh, u * c->gw, c->dp_oh, c->dp_ow, c->dp_lo, c->dp_hi, c->dp_depth + (size_t)first_img * px, st));
+        }
+        if (c->dp_logits) HIP_TRY(hipMemcpy2DAsync(c->dp_logits + (size_t)first_img * Np * K, (size_t)K * 4, acc, (size_t)Kpad * 4, (size_t)K * 4, rows, hipMemcpyDeviceToDevice, st));
+        if (c->dp_off) HIP_TRY(hipMemcpy2DAsync(c->dp_off + (size_t)first_img * K, (size_t)K * 4, c->dp_o[si], (size_t)Kpad * 4, (size_t)K * 4, n, hipMemcpyDeviceToDevice, st));
+        return VITX_OK;
+    }
     // Quantised matrices (block form in HBM): a q4_0 GEMM with few rows expands the blocks in its own LDS-fill path; everything else
     // is expanded just in time, one launch per layer, into the slice's scratch and then streamed by the wide-tile kernels.
     bool fused_ok(const QuantW &q, int rows) const { return q.blocks && q.type == T_Q4_0 && rows <= c->q4_fused_rows && rows % 128 == 0 && q.n_pad % 128 == 0 && q.K % 64 == 0; }
@@ -346,7 +392,8 @@ struct SliceForward {
         if (nx && (rc = layernorm_mx(r.X, nx->ln1_w, nx->ln1_b, sl.Umx, sl.Umx_s, r.M_real))) return rc;
         if (!c->trace_ids.empty() && (rc = trace(il + 1))) return rc;
         if (c->feat_on() && (rc = features(il, tail_now))) return rc;
-        return dense_rows(il);
+        if ((rc = dense_rows(il))) return rc;
+        return depth_rows(il);
     }
     // Dense tail of a layer
     int dense_tail(int il, const LayerW &w, const LayerW *nx, bool tail_now, const Rows &r) {
@@ -365,7 +412,8 @@ struct SliceForward {
         if ((rc = resid_gemm_ln(r, r.pc_fc2, c->glu ? sl.Hg : sl.Hbuf, Wl[W_FC2], w.fc2_b, F, Fl[W_FC2], nx ? nx->ln1_w : nullptr, nx ? nx->ln1_b : nullptr, sl.U, &fix_u))) return rc;
         if (!c->trace_ids.empty() && (rc = trace(il + 1))) return rc;
         if ((rc = features(il, tail_now, c->pool && il + 1 == c->L ? sl.Z : nullptr))) return rc;
-        return dense_rows(il);
+        if ((rc = dense_rows(il))) return rc;
+        return depth_rows(il);
     }
     int run(const void *d_imgs, void *d_probs, void *d_logits) {
         const int Mp_real = n * c->gh * c->gw;                          // patch rows
@@ -392,7 +440,7 @@ struct SliceForward {
         }
         const Rows all_rows{sl.X, M, M_real, PC_GEMM_PROJ, PC_GEMM_FC1, PC_GEMM_FC2, fuse};
         const Rows cls_rows{sl.Xc, round_up(n, tm), n, PC_GEMM_TAIL, PC_GEMM_TAIL, PC_GEMM_TAIL, false};
-        const bool tail = c->cls_tail && c->trace_ids.empty() && !c->feat_last_all_rows() && !c->dense_last_all_rows();      // the last layer carries only the class-token rows past its qkv projection (vitx_ctx::cls_tail)
+        const bool tail = c->cls_tail && c->trace_ids.empty() && !c->feat_last_all_rows() && !c->dense_last_all_rows() && !c->depth_last_all_rows();      // the last layer carries only the class-token rows past its qkv projection (vitx_ctx::cls_tail)
         for (int il = 0; il < c->L; ++il) {
             const LayerW &w = ws.layers[il], *nx = il + 1 < c->L ? &ws.layers[il + 1] : nullptr;
             const bool tail_now = tail && il + 1 == c->L;
@@ -428,6 +476,7 @@ struct SliceForward {
         if (c->zs_on() && (rc = c->map ? zeroshot(sl.Xc, D) : zeroshot(lg, ldl))) return rc;
         if (c->nn_on() && (rc = nearest(lg, ldl))) return rc;
         if (c->dense_on() && (rc = dense_head())) return rc;
+        if (c->depth_on() && (rc = depth_head())) return rc;
         if (fuse && c->ln_fb_host) HIP_TRY(hipMemcpyAsync(c->ln_fb_host + (&sl - &c->slices[0]), sl.ln_todo + sl.ln_blocks, sizeof(unsigned), hipMemcpyDeviceToHost, st));       // fall-back budget
         return VITX_OK;
     }
@@ -605,7 +654,7 @@ static int forward_pass(vitx_ctx *c, const void *d_imgs, int n, void *d_probs, v
     const bool serial = c->prof_on;
     const int ns = (c->nslices > 1 && n >= 8 * c->nslices) ? c->nslices : 1;
     if (ns == 1) {
-        if (c->graphs_on && !c->prof_on && c->trace_ids.empty() && !c->attn_on() && !c->feat_on() && !c->zs_on() && !c->nn_on() && !c->dense_on()) {
+        if (c->graphs_on && !c->prof_on && c->trace_ids.empty() && !c->attn_on() && !c->feat_on() && !c->zs_on() && !c->nn_on() && !c->dense_on() && !c->depth_on()) {
             bool done = false;
             const int rc = forward_graph(c, st, d_imgs, n, d_probs, d_logits, &done);
             if (rc != VITX_OK || done) return rc;
@@ -661,6 +710,7 @@ int vitx_forward_device(vitx_ctx *c, const void *d_imgs, int n, void *d_probs, v
     if (n > c->call_limit && c->zs_on()) { set_error("vitx_forward_device: zero-shot classification takes one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
     if (n > c->call_limit && c->nn_on()) { set_error("vitx_forward_device: nearest neighbours take one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
     if (n > c->call_limit && c->dense_on()) { set_error("vitx_forward_device: the dense head takes one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
+    if (n > c->call_limit && c->depth_on()) { set_error("vitx_forward_device: the depth head takes one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
     for (int i0 = 0; i0 < n; i0 += c->call_limit) {
         const int ni = std::min(c->call_limit, n - i0);
         const int rc = forward_pass(c, (const float *)d_imgs + (size_t)i0 * c->img_floats(), ni, (float *)d_probs + (size_t)i0 * c->R * c->C,
@@ -672,6 +722,7 @@ int vitx_forward_device(vitx_ctx *c, const void *d_imgs, int n, void *d_probs, v
     if (c->zs_on()) c->zs_n = n;
     if (c->nn_on()) c->nn_n = n;
     if (c->dense_on()) c->dn_n = n;
+    if (c->depth_on()) c->dp_n = n;
     return VITX_OK;
 }
 int vitx_forward(vitx_ctx *c, const float *imgs, int n, float *probs, float *logits) {

@@ -235,6 +235,17 @@ hipError_t launch_nn_finish(const void *state, int n, int k, const int *labels, 
 constexpr int kDenseMaxK = 256, kDenseMaxOut = 8192;
 bool dense_labels_supports(long ld, int n, int gh, int gw, int K, int out_h, int out_w);
 hipError_t launch_dense_labels(const float *logits, long ld, int n, int gh, int gw, int K, int out_h, int out_w, uint8_t *labels, float *score, hipStream_t stream);
+// The tail of the depth head (depth_map.hip; include/vitx.h "depth estimation"; the arithmetic: dense_resample.h + depth_bins.h).
+//   depth_fine:   logits [n * gh * gw][ld] f32 (ld a multiple of 4, at least K rounded up to 4; columns K .. ld never summed; 16-byte aligned) + offsets
+//                 (row img * ldo, ldo floats apart -- ldo == 0: one row for every image; nullptr: nothing is added), bins [K] -> fine [n][u gh][u gw] f32
+//   depth_resize: fine [n][fh][fw] -> out [n][out_h][out_w] f32 (any 4-byte alignment), clamped to lo .. hi; fh <= out_h <= kDepthMaxOut (and w)
+//   depth_rows:   y[row][0 .. D) (dtype, row stride ldy elements) = RNE(x row), row = g * group + r read at x + g * gstride + r * ldx; D % 8 == 0
+// 1 <= K <= kDepthMaxK, u in {1, 2, 4}, n <= 65535.  hipErrorInvalidValue for a shape outside that (depth_*_supports).
+bool depth_fine_supports(long ld, long ldo, int n, int gh, int gw, int K, int u);
+bool depth_resize_supports(int n, int fh, int fw, int out_h, int out_w);
+hipError_t launch_depth_fine(const float *logits, long ld, const float *offsets, long ldo, const float *bins, int n, int gh, int gw, int K, int u, float *fine, hipStream_t stream);
+hipError_t launch_depth_resize(const float *fine, int n, int fh, int fw, int out_h, int out_w, float lo, float hi, float *out, hipStream_t stream);
+hipError_t launch_depth_rows(int dtype, const float *x, long ldx, void *y, long ldy, long rows, int D, hipStream_t stream, int group = 1, long gstride = 0);
 // The text tower (include/vitx.h "the text tower"; text_embed.hip, attention_text.hip).
 //   text_embed: X[i][t][:] (f32) = f32(tok[ids[i * T + t]][:]) + pos[t][:]; tok [V][D] f16 (table_f16) or f32, ids checked by the caller; D % 8 == 0
 //   text_pool:  z[i][:] (dtype) = RNE(final LayerNorm of X row i * T + pooled[i]), LnRow's bits; rows n .. m_pad zeros; every width of VITX_LN_WIDTHS
@@ -340,6 +351,7 @@ hipError_t prepare_attention_persist();
 hipError_t prepare_attention_stream();
 hipError_t prepare_attention_text();                   // attention_text.hip
 hipError_t prepare_dense();                            // dense_label.hip
+hipError_t prepare_depth();                            // depth_map.hip
 #pragma GCC visibility pop
 
 }  // namespace vitx

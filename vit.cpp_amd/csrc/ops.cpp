@@ -462,6 +462,54 @@ int vitx_op_dense(int dtype, void *d_a, const void *d_w, const void *d_bias, voi
     return op_rc("vitx_op_dense", e, VITX_ERR_UNSUPPORTED);
 }
 
+// The depth head on the caller's buffers (include/vitx.h "depth estimation"); depth_fine_args / depth_resize_args: depth_host.cpp.
+int vitx_op_depth_fine(const void *d_logits, long ld, const void *d_offsets, const void *d_bins, int n, int gh, int gw, int K, int upsample, void *d_fine, void *stream) {
+    if (const int rc = depth_fine_args("vitx_op_depth_fine", d_logits, ld, d_bins, n, gh, gw, K, upsample, d_fine)) return rc;
+    if ((uintptr_t)d_logits % 16 || (uintptr_t)d_offsets % 16 || (uintptr_t)d_bins % 4 || (uintptr_t)d_fine % 4) { set_error("vitx_op_depth_fine: d_logits and d_offsets must be 16-byte, d_bins and d_fine 4-byte aligned"); return VITX_ERR_ARG; }
+    return op_rc("vitx_op_depth_fine", launch_depth_fine((const float *)d_logits, ld, (const float *)d_offsets, ld, (const float *)d_bins, n, gh, gw, K, upsample, (float *)d_fine, (hipStream_t)stream), VITX_ERR_UNSUPPORTED);
+}
+int vitx_op_depth_resize(const void *d_fine, int n, int fh, int fw, int out_h, int out_w, float min_depth, float max_depth, void *d_out, void *stream) {
+    if (const int rc = depth_resize_args("vitx_op_depth_resize", d_fine, n, fh, fw, out_h, out_w, min_depth, max_depth, d_out)) return rc;
+    if ((uintptr_t)d_fine % 4 || (uintptr_t)d_out % 4) { set_error("vitx_op_depth_resize: d_fine and d_out must be 4-byte aligned"); return VITX_ERR_ARG; }
+    return op_rc("vitx_op_depth_resize", launch_depth_resize((const float *)d_fine, n, fh, fw, out_h, out_w, min_depth, max_depth, (float *)d_out, (hipStream_t)stream), VITX_ERR_UNSUPPORTED);
+}
+// The launches the forward of a context with a depth head makes after its operand rows are written (SliceForward::depth_head): the pad rows zeroed,
+// the patch GEMM with a zero bias (the row of zeros the call writes behind the logit rows), the class GEMM with the head's bias, the two kernels.
+int vitx_op_depth(int dtype, void *d_a, const void *d_wp, void *d_acls, const void *d_wc, const void *d_bias, const void *d_bins, void *d_logits, void *d_offsets,
+                  int n, int gh, int gw, int K, int Dc, int upsample, int out_h, int out_w, float min_depth, float max_depth, void *d_fine, void *d_depth, void *stream) {
+    if (!d_a || !d_wp || !d_bias || Dc < 1 || (dtype != VITX_F16 && dtype != VITX_BF16) || (!d_wc) != (!d_acls) || (d_wc && !d_offsets)) { set_error("vitx_op_depth: invalid argument"); return VITX_ERR_ARG; }
+    const int Kpad = K > 0 ? round_up(K, gemm_tile_n()) : 0;
+    if (const int rc = depth_fine_args("vitx_op_depth", d_logits, Kpad, d_bins, n, gh, gw, K, upsample, d_fine)) return rc;
+    const int fh = upsample * gh, fw = upsample * gw;
+    if (const int rc = depth_resize_args("vitx_op_depth", d_fine, n, fh, fw, out_h, out_w, min_depth, max_depth, d_depth)) return rc;
+    for (const void *p : {(const void *)d_a, d_wp, (const void *)d_acls, d_wc, d_bias, d_bins, (const void *)d_logits, (const void *)d_offsets, (const void *)d_fine})
+        if ((uintptr_t)p % 16) { set_error("vitx_op_depth: every pointer but d_depth must be 16-byte aligned"); return VITX_ERR_ARG; }
+    if ((uintptr_t)d_depth % 4) { set_error("vitx_op_depth: d_depth must be 4-byte aligned"); return VITX_ERR_ARG; }
+    if (Dc % 64) { set_error("vitx_op_depth: Dc = %d is not a multiple of 64 (the GEMMs' K step)", Dc); return VITX_ERR_UNSUPPORTED; }
+    const int rows = n * gh * gw, M = round_up(rows, gemm_tile_m()), Mc = round_up(n, gemm_tile_m());
+    if ((size_t)M * Dc * 2 > 0xf0000000u || (size_t)(M + 1) * Kpad * 4 > 0xf0000000u || (size_t)Kpad * Dc * 2 > 0xf0000000u) { set_error("vitx_op_depth: %d rows of width %d leave the GEMM's 32-bit byte window", M, Dc); return VITX_ERR_UNSUPPORTED; }
+    const Tuning *t = tuning_for_device(-1);
+    if (!t) { set_error("vitx_op_depth: kernel bring-up failed"); return VITX_ERR_HIP; }
+    hipStream_t st = (hipStream_t)stream;
+    float *acc = (float *)d_logits, *zero = acc + (size_t)M * Kpad;
+    hipError_t e = hipMemsetAsync(zero, 0, (size_t)Kpad * 4, st);
+    if (e == hipSuccess && M > rows) e = hipMemsetAsync((char *)d_a + (size_t)rows * Dc * 2, 0, (size_t)(M - rows) * Dc * 2, st);
+    if (e == hipSuccess) e = launch_gemm(*t, dtype, EPI_BIAS_F32, dense_gemm(d_a, d_wp, zero, acc, M, rows, K, Kpad, Dc, Kpad), st);
+    if (d_wc) {
+        if (e == hipSuccess && Mc > n) e = hipMemsetAsync((char *)d_acls + (size_t)n * Dc * 2, 0, (size_t)(Mc - n) * Dc * 2, st);
+        if (e == hipSuccess) e = launch_gemm(*t, dtype, EPI_BIAS_F32, dense_gemm(d_acls, d_wc, (const float *)d_bias, d_offsets, Mc, n, K, Kpad, Dc, Kpad), st);
+    }
+    if (e == hipSuccess) e = launch_depth_fine(acc, Kpad, d_wc ? (const float *)d_offsets : (const float *)d_bias, d_wc ? Kpad : 0, (const float *)d_bins, n, gh, gw, K, upsample, (float *)d_fine, st);
+    if (e == hipSuccess) e = launch_depth_resize((const float *)d_fine, n, fh, fw, out_h, out_w, min_depth, max_depth, (float *)d_depth, st);
+    return op_rc("vitx_op_depth", e, VITX_ERR_UNSUPPORTED);
+}
+// The raw operand rows on their own: y[row][0 .. D) (dtype, row stride ldy elements) = RNE(x[row][0 .. D)) (f32, row stride ldx floats)
+int vitx_op_depth_rows(int dtype, const void *d_x, long ldx, void *d_y, long ldy, int rows, int D, void *stream) {
+    if (!d_x || !d_y || rows < 1 || D < 1 || ldx < D || ldy < D || (dtype != VITX_F16 && dtype != VITX_BF16) || (uintptr_t)d_x % 16 || (uintptr_t)d_y % 16) { set_error("vitx_op_depth_rows: invalid argument"); return VITX_ERR_ARG; }
+    if (D % 8 || ldx % 4 || ldy % 8) { set_error("vitx_op_depth_rows: D %% 8, ldx %% 4 and ldy %% 8 must be 0"); return VITX_ERR_UNSUPPORTED; }
+    return op_rc("vitx_op_depth_rows", launch_depth_rows(dtype, (const float *)d_x, ldx, d_y, ldy, rows, D, (hipStream_t)stream), VITX_ERR_UNSUPPORTED);
+}
+
 // The text tower's three kernels on their own (include/vitx.h "the text tower").  Every argument check comes before the first device call.
 int vitx_op_text_embed(int table_f16, const void *d_tok, const void *d_pos, const void *d_ids, void *d_x, int n, int T, int D, void *stream) {
     if (!d_tok || !d_pos || !d_ids || !d_x || n <= 0 || T <= 0 || D <= 0 || D % 8) { set_error("vitx_op_text_embed: invalid argument (D %% 8 == 0)"); return VITX_ERR_ARG; }

@@ -4,6 +4,7 @@
 #include <utility>
 
 #include "context.h"
+#include "depth_bins.h"
 
 // Synchronise and copy the n x fpi floats of an opt-in output to the host, or say why not.  `api`: "vitx_attn" / "vitx_feat"; n: the images
 // of the last forward made with the output on (0: it is off, or no forward since <api>_enable)
@@ -412,6 +413,120 @@ int vitx_dense_read(vitx_ctx *c, uint8_t *labels, float *score, float *logits) {
     HIP_TRY(hipMemcpy(labels, c->dn_labels, (size_t)n * px, hipMemcpyDeviceToHost));
     if (score) HIP_TRY(hipMemcpy(score, c->dn_score, (size_t)n * px * 4, hipMemcpyDeviceToHost));
     if (logits) HIP_TRY(hipMemcpy(logits, c->dn_logits, (size_t)n * c->gh * c->gw * c->dn_K * 4, hipMemcpyDeviceToHost));
+    return VITX_OK;
+}
+
+// The depth head of a context (include/vitx.h "depth estimation").  Every argument check comes before the first device call.
+int vitx_depth_set(vitx_ctx *c, const float *Wp, const float *Wc, const float *bias, const float *bins, int K, int Dc, uint64_t layer_mask, int upsample,
+                   float min_depth, float max_depth, int out_h, int out_w, int flags) {
+    if (!c) return VITX_ERR_ARG;
+    const bool off = !Wp && K == 0;
+    uint64_t mask = layer_mask;
+    int m = 0, oh = out_h, ow = out_w;
+    const int fh = upsample * c->gh, fw = upsample * c->gw;
+    if (!off) {
+        if (!Wp || !bins) { set_error("vitx_depth_set: NULL weights or bins with K = %d", K); return VITX_ERR_ARG; }
+        if (K < 1) { set_error("vitx_depth_set: K = %d bins", K); return VITX_ERR_ARG; }
+        if (flags & ~(VITX_DEPTH_NORM | VITX_DEPTH_LOGITS | VITX_DEPTH_FINE)) { set_error("vitx_depth_set: unknown flags 0x%x", flags); return VITX_ERR_ARG; }
+        if (mask == 0) mask = 1ull << (c->L - 1);
+        if (c->L < 64 && (mask >> c->L)) { set_error("vitx_depth_set: layer mask selects a layer at or beyond L = %d", c->L); return VITX_ERR_ARG; }
+        m = __builtin_popcountll(mask);
+        if (m > 4) { set_error("vitx_depth_set: %d layers selected, at most 4", m); return VITX_ERR_ARG; }
+        if (Dc != m * c->D) { set_error("vitx_depth_set: the head's width %d is not %d layers x D = %d", Dc, m, m * c->D); return VITX_ERR_ARG; }
+        if (out_h < 0 || out_w < 0 || ((out_h == 0) != (out_w == 0))) { set_error("vitx_depth_set: output shape %d x %d (0 x 0: the context's image shape)", out_h, out_w); return VITX_ERR_ARG; }
+        if (out_h == 0) { oh = c->Sh; ow = c->Sw; }
+        if (!std::isfinite(min_depth) || !std::isfinite(max_depth) || min_depth > max_depth) { set_error("vitx_depth_set: the depth range %g .. %g must be finite and ordered", (double)min_depth, (double)max_depth); return VITX_ERR_ARG; }
+        for (const float *W : {Wp, Wc})
+            if (W) for (size_t i = 0, nb = (size_t)K * Dc; i < nb; ++i)
+                if (!std::isfinite(W[i])) { set_error("vitx_depth_set: %s weight [%zu][%zu] is not finite", W == Wp ? "patch" : "class", i / Dc, i % Dc); return VITX_ERR_ARG; }
+        for (int k = 0; k < K; ++k) {
+            if (bias && !std::isfinite(bias[k])) { set_error("vitx_depth_set: bias [%d] is not finite", k); return VITX_ERR_ARG; }
+            if (!std::isfinite(bins[k]) || !(bins[k] > 0.0f)) { set_error("vitx_depth_set: bin [%d] = %g is not a finite positive depth", k, (double)bins[k]); return VITX_ERR_ARG; }
+        }
+        if (K > kDepthMaxK) { set_error("vitx_depth_set: K = %d bins above %d", K, kDepthMaxK); return VITX_ERR_UNSUPPORTED; }
+        if (upsample != 1 && upsample != 2 && upsample != 4) { set_error("vitx_depth_set: upsample = %d, not 1, 2 or 4", upsample); return VITX_ERR_UNSUPPORTED; }
+        if (c->R != 1) { set_error("vitx_depth_set: the depth head is not available for ViTSTR contexts"); return VITX_ERR_UNSUPPORTED; }
+        if (Wc && c->map) { set_error("vitx_depth_set: a class half on a context without a class token (VITX_POOL_MAP)"); return VITX_ERR_UNSUPPORTED; }
+        if (oh < fh || ow < fw || oh > kDepthMaxOut || ow > kDepthMaxOut) {
+            set_error("vitx_depth_set: output %d x %d outside the fine plane %d x %d .. %d (upsampling only)", oh, ow, fh, fw, kDepthMaxOut);
+            return VITX_ERR_UNSUPPORTED;
+        }
+        const size_t rows = (size_t)c->pass_cap() * c->gh * c->gw;
+        if (rows * Dc * 2 > 0xf0000000u || rows * round_up(K, c->tn) * 4 > 0xf0000000u || c->pass_cap() > 65535) {
+            set_error("vitx_depth_set: the operand or logit rows of a pass of %d images leave the GEMM's 32-bit byte window", c->pass_cap());
+            return VITX_ERR_UNSUPPORTED;
+        }
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());          // no forward in flight reads or writes the buffers about to be freed
+    c->depth_free();
+    if (off) return VITX_OK;
+    const int Kpad = round_up(K, c->tn), cap = c->pass_cap(), Np = c->gh * c->gw;
+    const size_t px = (size_t)oh * ow, fpx = (size_t)fh * fw;
+    auto alloc = [](void **p, size_t bytes) { if (hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; } return true; };
+    bool ok = alloc(&c->dp_Wp, (size_t)Kpad * Dc * 2) && (!Wc || alloc(&c->dp_Wc, (size_t)Kpad * Dc * 2)) && alloc((void **)&c->dp_bias, (size_t)Kpad * 4) &&
+              alloc((void **)&c->dp_zero, (size_t)Kpad * 4) && alloc((void **)&c->dp_bins, (size_t)Kpad * 4) && alloc((void **)&c->dp_depth, (size_t)cap * px * 4) &&
+              alloc((void **)&c->dp_fine, (size_t)cap * fpx * 4);
+    if (ok && (flags & VITX_DEPTH_LOGITS)) ok = alloc((void **)&c->dp_logits, (size_t)cap * Np * K * 4) && (!Wc || alloc((void **)&c->dp_off, (size_t)cap * K * 4));
+    c->dp_a.assign(c->nslices, nullptr); c->dp_acc.assign(c->nslices, nullptr); c->dp_ac.assign(c->nslices, nullptr); c->dp_o.assign(c->nslices, nullptr);
+    size_t scratch = 0;
+    hipError_t e = hipSuccess;
+    for (int i = 0; ok && i < c->nslices; ++i) {
+        const int imgs = std::min(c->slices[i].cap, cap);
+        const size_t rows = (size_t)round_up(imgs * Np, c->tm), crows = (size_t)round_up(imgs, c->tm);
+        ok = alloc(&c->dp_a[i], rows * Dc * 2) && alloc((void **)&c->dp_acc[i], rows * Kpad * 4);
+        if (ok) e = hipMemset(c->dp_a[i], 0, rows * Dc * 2);
+        scratch += rows * Dc * 2 + rows * Kpad * 4;
+        if (ok && Wc && e == hipSuccess) {
+            ok = alloc(&c->dp_ac[i], crows * Dc * 2) && alloc((void **)&c->dp_o[i], crows * Kpad * 4);
+            if (ok) e = hipMemset(c->dp_ac[i], 0, crows * Dc * 2);
+            scratch += crows * Dc * 2 + crows * Kpad * 4;
+        }
+        if (e != hipSuccess) break;
+    }
+    if (!ok) { c->depth_free(); set_error("vitx_depth_set: cannot allocate the buffers for %d bins, %d x %d maps and %d images", K, oh, ow, cap); return VITX_ERR_NOMEM; }
+    // the halves go up rounded (RNE) to the operand type; the zero rows beyond K come from operand_matrix_host, the zero biases from the memset
+    for (int h = 0; h < 2 && e == hipSuccess; ++h) {
+        if (h && !Wc) break;
+        const std::vector<uint16_t> hw = operand_matrix_host(c->dtype, h ? Wc : Wp, nullptr, K, Dc, Kpad, Dc, 0, 0);
+        e = hipMemcpy(h ? c->dp_Wc : c->dp_Wp, hw.data(), hw.size() * 2, hipMemcpyHostToDevice);
+    }
+    for (float *p : {c->dp_bias, c->dp_zero, c->dp_bins}) if (e == hipSuccess) e = hipMemset(p, 0, (size_t)Kpad * 4);
+    if (e == hipSuccess && bias) e = hipMemcpy(c->dp_bias, bias, (size_t)K * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(c->dp_bins, bins, (size_t)K * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { c->depth_free(); set_error("vitx_depth_set: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
+    c->dp_bias_host.assign(K, 0.0f);
+    if (bias) std::copy(bias, bias + K, c->dp_bias_host.begin());
+    c->dp_K = K; c->dp_Kpad = Kpad; c->dp_Dc = Dc; c->dp_mask = mask; c->dp_u = upsample; c->dp_oh = oh; c->dp_ow = ow; c->dp_lo = min_depth; c->dp_hi = max_depth;
+    c->dp_flags = flags; c->dp_cap = cap; c->dp_scratch = scratch;
+    return VITX_OK;
+}
+int vitx_depth_bins(const vitx_ctx *c) { return c ? c->dp_K : 0; }
+int vitx_depth_shape(const vitx_ctx *c, int *out_h, int *out_w, int *fine_h, int *fine_w) {
+    if (!c) return VITX_ERR_ARG;
+    if (out_h) *out_h = c->dp_oh;
+    if (out_w) *out_w = c->dp_ow;
+    if (fine_h) *fine_h = c->dp_u * c->gh;
+    if (fine_w) *fine_w = c->dp_u * c->gw;
+    return VITX_OK;
+}
+int vitx_depth_images(const vitx_ctx *c) { return c ? c->dp_n : 0; }
+const void *vitx_depth_device(const vitx_ctx *c) { return c ? c->dp_depth : nullptr; }
+size_t vitx_depth_scratch_bytes(const vitx_ctx *c) { return c ? c->dp_scratch : 0; }
+int vitx_depth_read(vitx_ctx *c, float *depth, float *fine, float *logits, float *offsets) {
+    if (!c || !depth) return VITX_ERR_ARG;
+    const int n = c->depth_on() ? c->dp_n : 0, K = c->dp_K;
+    if (n == 0) { set_error("vitx_depth_read: no forward has run with a depth head set since vitx_depth_set"); return VITX_ERR_ARG; }
+    if (fine && !(c->dp_flags & VITX_DEPTH_FINE)) { set_error("vitx_depth_read: the head was set without VITX_DEPTH_FINE"); return VITX_ERR_ARG; }
+    if ((logits || offsets) && !c->dp_logits) { set_error("vitx_depth_read: the head was set without VITX_DEPTH_LOGITS"); return VITX_ERR_ARG; }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(depth, c->dp_depth, (size_t)n * c->dp_oh * c->dp_ow * 4, hipMemcpyDeviceToHost));
+    if (fine) HIP_TRY(hipMemcpy(fine, c->dp_fine, (size_t)n * c->dp_u * c->gh * c->dp_u * c->gw * 4, hipMemcpyDeviceToHost));
+    if (logits) HIP_TRY(hipMemcpy(logits, c->dp_logits, (size_t)n * c->gh * c->gw * K * 4, hipMemcpyDeviceToHost));
+    if (offsets && c->dp_off) HIP_TRY(hipMemcpy(offsets, c->dp_off, (size_t)n * K * 4, hipMemcpyDeviceToHost));
+    if (offsets && !c->dp_off) for (int i = 0; i < n; ++i) std::copy(c->dp_bias_host.begin(), c->dp_bias_host.end(), offsets + (size_t)i * K);
     return VITX_OK;
 }
 

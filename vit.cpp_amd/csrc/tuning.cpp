@@ -18,6 +18,7 @@ static hipError_t prepare_device_kernels(const Tuning &t) {
     if (e == hipSuccess) e = prepare_attention();
     if (e == hipSuccess) e = prepare_attention_text();
     if (e == hipSuccess) e = prepare_dense();
+    if (e == hipSuccess) e = prepare_depth();
     return e;
 }
 

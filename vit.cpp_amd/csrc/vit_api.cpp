@@ -308,6 +308,52 @@ int vit_dense_batch(const vit_model &model, vit_state &state, const image_f32 *i
     return 0;
 }
 
+// No counterpart in the reference: a depth for every pixel of n images (include/vitx.h "depth estimation")
+int vit_depth_batch(const vit_model &model, vit_state &state, const image_f32 *imgs, int n, const vit_depth_head &head, std::vector<vit_depth_result> &out) {
+    out.clear();
+    const size_t wsz = (size_t)std::max(head.K, 0) * std::max(head.Dc, 0);
+    if (!model.handle || !imgs || n <= 0 || head.K <= 0 || head.Dc <= 0 || head.wp.size() != wsz || (!head.wc.empty() && head.wc.size() != wsz) ||
+        (!head.bias.empty() && head.bias.size() != (size_t)head.K) || head.bins.size() != (size_t)head.K) { fprintf(stderr, "%s: invalid argument\n", __func__); return 1; }
+    if (vitx_model_seq_len(model.handle) > 0) { fprintf(stderr, "%s: this is a ViTSTR model: it has no depth head\n", __func__); return 1; }
+    uint64_t mask = 0;
+    for (const int l : head.layers) {
+        if (l < 0 || l >= 64) { fprintf(stderr, "%s: layer %d outside 0 .. 63\n", __func__, l); return 1; }
+        mask |= 1ull << l;
+    }
+    const int C = model.hparams.num_classes;
+    int Sh = 0, Sw = 0;
+    if (!state_shape(model, state, Sh, Sw, __func__)) return 1;
+    const size_t img_floats = (size_t)3 * Sh * Sw;
+    if (const int i = first_bad_image(imgs, n, Sh, Sw); i >= 0) {
+        fprintf(stderr, "%s: image %d is %dx%d, this state expects %dx%d\n", __func__, i, imgs[i].nx, imgs[i].ny, Sw, Sh);
+        return 1;
+    }
+    if (ensure_ctx(model, state, n) != VITX_OK) { fprintf(stderr, "%s: failed to create the context: %s\n", __func__, vitx_last_error()); return 1; }
+    if (vitx_depth_set(state.ctx, head.wp.data(), head.wc.empty() ? nullptr : head.wc.data(), head.bias.empty() ? nullptr : head.bias.data(), head.bins.data(), head.K, head.Dc,
+                       mask, head.upsample, head.min_depth, head.max_depth, head.out_h, head.out_w, head.norm ? VITX_DEPTH_NORM : 0) != VITX_OK) {
+        fprintf(stderr, "%s: %s\n", __func__, vitx_last_error());
+        return 1;
+    }
+    int oh = 0, ow = 0;
+    (void)vitx_depth_shape(state.ctx, &oh, &ow, nullptr, nullptr);
+    const size_t px = (size_t)oh * ow;
+    std::vector<float> batch((size_t)n * img_floats);
+    for (int i = 0; i < n; ++i) std::copy(imgs[i].data.begin(), imgs[i].data.end(), batch.begin() + (size_t)i * img_floats);
+    state.prediction.resize((size_t)n * C);
+    std::vector<float> depth((size_t)n * px);
+    const bool ok = vitx_forward(state.ctx, batch.data(), n, state.prediction.data(), nullptr) == VITX_OK &&
+                    vitx_depth_read(state.ctx, depth.data(), nullptr, nullptr, nullptr) == VITX_OK;
+    if (!ok) fprintf(stderr, "%s: failed to encode image: %s\n", __func__, vitx_last_error());
+    (void)vitx_depth_set(state.ctx, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0.0f, 0.0f, 0, 0, 0);
+    if (!ok) return 1;
+    out.resize(n);
+    for (int i = 0; i < n; ++i) {
+        out[i].h = oh; out[i].w = ow;
+        out[i].depth.assign(depth.begin() + (size_t)i * px, depth.begin() + (size_t)(i + 1) * px);
+    }
+    return 0;
+}
+
 // No counterpart in the reference: the text embeddings of n tokenised prompts (include/vitx.h "the text tower")
 int vit_text_embed_batch(const vit_model &model, vit_text_state &state, const int32_t *ids, int n, int flags, std::vector<std::vector<float>> &out) {
     out.clear();

@@ -162,6 +162,27 @@ struct vit_dense_result {
 // out[i] = image i's label map.  The head is set for this call and switched off again before returning; state.prediction holds the file's own class
 // probabilities of the same forward.  0 ok / 1 failure.
 int vit_dense_batch(const vit_model &model, vit_state &state, const image_f32 *imgs, int n, const vit_dense_head &head, std::vector<vit_dense_result> &out);
+// NEW, no counterpart in the reference: depth estimation (include/vitx.h "depth estimation") -- a binned linear head over the patch and class tokens of
+// up to four layers (the form DINOv2's linear depth heads are published in; convert.py --depth-head-in writes one from a checkpoint).
+struct vit_depth_head {
+    std::vector<float> wp;                // [K][Dc] over the patch tokens, Dc = layers.size() * hidden_size
+    std::vector<float> wc;                // [K][Dc] over the class tokens, or empty: no class half
+    std::vector<float> bias;              // K, or empty: zeros
+    std::vector<float> bins;              // K bin centres, all > 0
+    int K = 0, Dc = 0;
+    std::vector<int> layers;              // the layers whose tokens are concatenated, ascending; empty: the last layer
+    int upsample = 4;                     // 1, 2 or 4: the bins are reduced on a grid this many times finer than the patch grid
+    float min_depth = 0.001f, max_depth = 10.0f;
+    bool norm = false;                    // the head reads final-norm tokens, not the raw residual stream
+    int out_h = 0, out_w = 0;             // the depth map's shape; 0 x 0: the state's image shape
+};
+struct vit_depth_result {
+    int h = 0, w = 0;
+    std::vector<float> depth;             // [h][w]
+};
+// out[i] = image i's depth map.  The head is set for this call and switched off again before returning; state.prediction holds the file's own class
+// probabilities of the same forward.  0 ok / 1 failure.
+int vit_depth_batch(const vit_model &model, vit_state &state, const image_f32 *imgs, int n, const vit_depth_head &head, std::vector<vit_depth_result> &out);
 // NEW, no counterpart in the reference: the text tower of a CLIP / SigLIP checkpoint (include/vitx.h "the text tower").  `model` is a text-tower
 // file (vitx_model_kind == VITX_KIND_TEXT; hparams.img_size is its context length T, hparams.num_classes its embedding width E).  ids: n
 // tokenised prompts [n][T] -- there is no tokenizer in the engine; out[i] = prompt i's E floats; flags 0 or VITX_TEXT_L2.  0 ok / 1 failure.
