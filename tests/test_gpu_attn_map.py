@@ -392,3 +392,21 @@ def test_cli_writes_the_attention_map_as_pgm(pkg, binding, torch_gpu, tmp_path, 
     gi, gj = np.unravel_index(int(np.argmax(grid)), grid.shape)
     assert pic[gi * 16:(gi + 1) * 16, gj * 16:(gj + 1) * 16].min() == 255 == pic.max()
     ctx.close(); model.close()
+
+
+def test_a_refused_enable_leaves_the_maps_on(pkg, binding, torch_gpu):
+    """A vitx_attn_enable that is refused for its arguments (unknown flags) leaves the maps as they were enabled: the next forward gives the same bits."""
+    L = binding.lib()
+    model = binding.Model(pkg.synth.cached_synthetic("vit_tiny_patch16_224", head_scale=4.0))
+    imgs = pkg.synth.normalize_u8(pkg.synth.synthetic_images_u8(4, 224, seed=10))
+    ctx = binding.Context(model, device=0, max_batch=4, dtype=binding.F16)
+    ctx.attn_enable([2, 11], rollout=True)
+    ctx.forward(imgs)
+    cls, roll = ctx.attn_read(4)
+    fpi = L.vitx_attn_floats(ctx._h)
+    assert L.vitx_attn_enable(ctx._h, 1, 0x100) == binding.ERR_ARG
+    ctx.forward(imgs)
+    assert L.vitx_attn_images(ctx._h) == 4 and L.vitx_attn_floats(ctx._h) == fpi
+    cls2, roll2 = ctx.attn_read(4)
+    assert np.array_equal(cls2.view(np.uint32), cls.view(np.uint32)) and np.array_equal(roll2.view(np.uint32), roll.view(np.uint32))
+    ctx.close(); model.close()

@@ -417,3 +417,25 @@ def test_errors(pkg, binding, torch_gpu):
         cs.dense_set(np.zeros((2, 192), np.float32), None, None)
     assert ei.value.code == U and "ViTSTR" in str(ei.value)
     cs.close(); st.close()
+
+
+def test_a_refused_set_leaves_the_head_in_place(pkg, binding, torch_gpu):
+    """A vitx_dense_set that is refused for its arguments (a NaN weight) leaves the head that was set: the next forward gives the same bits."""
+    L = binding.lib()
+    imgs = Z.images()[:5]
+    model = binding.Model(Z.model_file(pkg, "clip"))
+    D = model.hparams.hidden_size
+    W, b = _head(K_E2E, D, seed=11)
+    ctx = binding.Context(model, device=0, max_batch=5, dtype=1)
+    ctx.dense_set(W, b, [1], score=True, logits=True)
+    ctx.forward(imgs)
+    labels, score, logits = ctx.dense_read(5)
+    bad = W.copy(); bad[3, 5] = np.nan
+    with pytest.raises(binding.VitxError) as ei:
+        ctx.dense_set(bad, b, [1], score=True, logits=True)
+    assert ei.value.code == binding.ERR_ARG
+    ctx.forward(imgs)
+    assert L.vitx_dense_images(ctx._h) == 5 and L.vitx_dense_classes(ctx._h) == K_E2E
+    labels2, score2, logits2 = ctx.dense_read(5)
+    assert np.array_equal(labels2, labels) and np.array_equal(_bits(score2), _bits(score)) and np.array_equal(_bits(logits2), _bits(logits))
+    ctx.close(); model.close()

@@ -544,3 +544,25 @@ def test_errors(pkg, binding, torch_gpu):
         cs.depth_set(np.zeros((2, 192), np.float32), None, None, np.ones(2, np.float32))
     assert ei.value.code == U and "ViTSTR" in str(ei.value)
     cs.close(); st.close()
+
+
+def test_a_refused_set_leaves_the_head_in_place(pkg, binding, torch_gpu):
+    """A vitx_depth_set that is refused for its arguments (upsample = 3) leaves the head that was set: the next forward gives the same bits."""
+    L = binding.lib()
+    imgs = Z.images()[:5]
+    model = binding.Model(Z.model_file(pkg, "clip"))
+    D = model.hparams.hidden_size
+    wp, wc, bias, bins = _head(K_E2E, D, seed=11)
+    ctx = binding.Context(model, device=0, max_batch=5, dtype=1)
+    ctx.depth_set(wp, wc, bias, bins, [1], 4, 3.0, 7.0, logits=True, fine=True)
+    ctx.forward(imgs)
+    first = ctx.depth_read(5)
+    with pytest.raises(binding.VitxError) as ei:
+        ctx.depth_set(wp, wc, bias, bins, [1], 3, 3.0, 7.0, logits=True, fine=True)
+    assert ei.value.code == binding.ERR_UNSUPPORTED
+    ctx.forward(imgs)
+    assert L.vitx_depth_images(ctx._h) == 5 and L.vitx_depth_bins(ctx._h) == K_E2E
+    again = ctx.depth_read(5)
+    for a, b in zip(first, again):
+        assert np.array_equal(_bits(a), _bits(b))
+    ctx.close(); model.close()

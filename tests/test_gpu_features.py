@@ -667,3 +667,24 @@ def test_cpp_example_embed_main_prints_cosine_similarities(pkg, binding, torch_g
     assert cosine(a, a) == "1.000000"
     v = float(cosine(a, b))
     assert -1.0 < v < 1.0, v
+
+
+def test_a_refused_enable_leaves_the_features_on(pkg, binding, torch_gpu):
+    """A vitx_feat_enable that is refused for its arguments (unknown flags) leaves the features as they were enabled: the next forward gives the same bits."""
+    L = binding.lib()
+    model = binding.Model(_synthetic(pkg, "vit_micro_patch16_64"))
+    imgs = _images(pkg, 9, 64, seed=3)
+    ctx = binding.Context(model, device=0, max_batch=9, dtype=binding.BF16)
+    last = model.hparams.num_hidden_layers - 1
+    ctx.feat_enable(cls=True, mean=True, tokens=True, l2=True, layers=[0, last])
+    _forward_dev(torch_gpu, ctx, imgs)
+    first = ctx.feat_read(9)
+    fpi = L.vitx_feat_floats(ctx._h)
+    assert L.vitx_feat_enable(ctx._h, 0x100 | binding.FEAT_CLS, 0) == binding.ERR_ARG
+    _forward_dev(torch_gpu, ctx, imgs)
+    assert L.vitx_feat_images(ctx._h) == 9 and L.vitx_feat_floats(ctx._h) == fpi
+    again = ctx.feat_read(9)
+    for l in (0, last):
+        for k in ("cls", "mean", "tokens"):
+            assert np.array_equal(_bits(again[l][k]), _bits(first[l][k])), (l, k)
+    ctx.close(); model.close()

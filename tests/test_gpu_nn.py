@@ -486,3 +486,25 @@ def test_nearest_neighbours_take_one_pass(pkg, binding, torch_gpu):
     assert L.vitx_forward_device(ctx._h, x.data_ptr(), n, p.data_ptr(), None, None) == binding.ERR_ARG
     assert "one pass" in L.vitx_last_error().decode() and L.vitx_nn_images(ctx._h) == 0
     ctx.close(); model.close()
+
+
+def test_a_refused_set_leaves_the_gallery_in_place(pkg, binding, torch_gpu):
+    """A vitx_nn_set that is refused for its arguments (a NaN in the gallery) leaves the gallery that was set: the next forward gives the same bits."""
+    L = binding.lib()
+    imgs = Z.images()[:5]
+    model = binding.Model(Z.model_file(pkg, "clip"))
+    ctx = binding.Context(model, device=0, max_batch=5, dtype=1)
+    g = Z.unit_rows(np.random.default_rng(8).standard_normal((50, Z.CLIP_E)))
+    labels = np.arange(50, dtype=np.int32) % 4
+    ctx.nn_set(g, 3, binding.NN_LOGITS, labels, 4)
+    ctx.forward(imgs)
+    idx, score, vote = ctx.nn_read(5)
+    bad = g.copy(); bad[7, 1] = np.nan
+    with pytest.raises(binding.VitxError) as ei:
+        ctx.nn_set(bad, 3, binding.NN_LOGITS, labels, 4)
+    assert ei.value.code == binding.ERR_ARG
+    ctx.forward(imgs)
+    assert L.vitx_nn_images(ctx._h) == 5 and L.vitx_nn_rows(ctx._h) == 50
+    idx2, score2, vote2 = ctx.nn_read(5)
+    assert np.array_equal(idx2, idx) and np.array_equal(_bits(score2), _bits(score)) and np.array_equal(_bits(vote2), _bits(vote))
+    ctx.close(); model.close()

@@ -417,3 +417,24 @@ def test_zero_shot_takes_one_pass(pkg, binding, torch_gpu):
     assert L.vitx_forward_device(ctx._h, x.data_ptr(), n, p.data_ptr(), None, None) == binding.ERR_ARG
     assert "one pass" in L.vitx_last_error().decode() and L.vitx_zeroshot_images(ctx._h) == 0
     ctx.close(); model.close()
+
+
+def test_a_refused_set_leaves_the_bank_in_place(pkg, binding, torch_gpu):
+    """A vitx_zeroshot_set that is refused for its arguments (a NaN in the bank) leaves the bank that was set: the next forward gives the same bits."""
+    L = binding.lib()
+    t, kind, scale, bias = _bank(pkg, "clip")
+    imgs = Z.images()[:5]
+    model = binding.Model(Z.model_file(pkg, "clip"))
+    ctx = binding.Context(model, device=0, max_batch=5, dtype=1)
+    ctx.zeroshot_set(t, kind, scale, bias)
+    ctx.forward(imgs)
+    zp, zl = ctx.zeroshot_read(5, want_logits=True)
+    bad = t.copy(); bad[1, 2] = np.nan
+    with pytest.raises(binding.VitxError) as ei:
+        ctx.zeroshot_set(bad, kind, scale, bias)
+    assert ei.value.code == binding.ERR_ARG
+    ctx.forward(imgs)
+    assert L.vitx_zeroshot_images(ctx._h) == 5 and L.vitx_zeroshot_classes(ctx._h) == t.shape[0]
+    zp2, zl2 = ctx.zeroshot_read(5, want_logits=True)
+    assert np.array_equal(_bits(zp2), _bits(zp)) and np.array_equal(_bits(zl2), _bits(zl))
+    ctx.close(); model.close()

@@ -1,7 +1,6 @@
-// context.h -- the execution context (struct vitx_ctx) as context.cpp, forward.cpp, outputs.cpp and ops.cpp share it: what a forward uses.
-// The weights it reads are a WeightSet (weights.h).  Internal: nothing outside those four files includes it (depth_host.cpp does, for the
-// argument checks it shares with ops.cpp and the error text); callers see the opaque vitx_ctx
-// of include/vitx.h.
+// context.h -- the execution context (struct vitx_ctx) as context.cpp, forward.cpp, outputs.cpp, heads.cpp and ops.cpp share it: what a forward
+// uses.  The weights it reads are a WeightSet (weights.h), its opt-in outputs the structs of heads.h.  Internal: nothing outside those five files
+// includes it (depth_host.cpp shares its argument checks with ops.cpp through heads.h); callers see the opaque vitx_ctx of include/vitx.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -10,6 +9,7 @@
 #include <memory>
 #include <vector>
 
+#include "heads.h"
 #include "weights.h"
 
 namespace vitx {
@@ -24,17 +24,6 @@ inline const char *const kProfNames[PC_COUNT] = {"patch_embed", "layernorm", "ge
 static_assert(PC_COUNT <= VITX_PROF_MAX_CLASSES, "vitx_profile_read callers size their arrays by VITX_PROF_MAX_CLASSES");
 
 static_assert(VITX_F16 == DT_F16 && VITX_BF16 == DT_BF16, "the API's dtype values are handed to the launchers as they are");
-// selected layers of an output's layer mask (attention maps, features) below layer il: the slot of il's block in the per-image layout; il = L: their number
-inline int layer_slot(uint64_t mask, int il) { return __builtin_popcountll(il < 64 ? mask & ((1ull << il) - 1) : mask); }
-
-// Temporary device scratch of one call: owns the pointer it is given and frees it on every way out.  Move-only.
-struct DevMem {
-    void *p;
-    explicit DevMem(void *p_ = nullptr) : p(p_) {}
-    DevMem(DevMem &&o) : p(o.p) { o.p = nullptr; }
-    ~DevMem() { (void)hipFree(p); }
-};
-
 }  // namespace vitx
 using namespace vitx;
 
@@ -149,152 +138,26 @@ struct vitx_ctx {
     // residual-stream trace (vitx_trace_enable)
     std::vector<int> trace_ids;
     float *trace_buf = nullptr;  // [L + 1][n_ids][N][D]
-    // attention maps (vitx_attn_enable): nothing is allocated or launched while attn_mask == 0 and attn_flags == 0
-    uint64_t attn_mask = 0;
-    int attn_flags = 0;
-    int attn_fpi = 0;            // floats per image: popcount(mask) * H * N (+ N with VITX_ATTN_ROLLOUT)
-    int attn_cap = 0;            // images the buffers hold (= the images one pass takes)
-    int attn_n = 0;              // images of the last forward made with maps on (0: none since vitx_attn_enable)
-    float *attn_out = nullptr;   // [attn_cap][attn_fpi]: per image the selected layers' [H][N] class-token maps in ascending order, then the rollout row [N]
-    float *attn_roll[2] = {nullptr, nullptr};   // rollout: [attn_cap][N][N] x 2, A^_l written into one, the product R_l in place of it (ping-pong)
-    float *attn_cls_last = nullptr;             // rollout without the last layer in the mask: its class-token maps [attn_cap][H][N]
-    bool attn_on() const { return attn_mask != 0 || attn_flags != 0; }
-    void attn_free() {
-        for (float **p : {&attn_out, &attn_roll[0], &attn_roll[1], &attn_cls_last}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    // The opt-in outputs (heads.h), each built by its vitx_*_enable / vitx_*_set (outputs.cpp).  nullptr: off -- nothing is allocated or launched;
+    // dropping the object frees its buffers.  They are released after ~vitx_ctx's body, with the context's device still current.
+    std::unique_ptr<AttnMaps> attn;
+    std::unique_ptr<Features> feat;
+    std::unique_ptr<ZeroShot> zs;
+    std::unique_ptr<Gallery> nn;
+    std::unique_ptr<DenseHead> dense;
+    std::unique_ptr<DepthHead> depth;
+    // f(Output &) for every output that is set, in the order above
+    template <typename F> void each_output(F &&f) const {
+        Output *const all[] = {attn.get(), feat.get(), zs.get(), nn.get(), dense.get(), depth.get()};
+        for (Output *o : all) if (o) f(*o);
     }
-    // embeddings and token features (vitx_feat_enable): nothing is allocated or launched while feat_flags == 0
-    int feat_flags = 0;          // VITX_FEAT_*
-    uint64_t feat_mask = 0;      // selected layers (never 0 while on: "the last layer" is resolved at vitx_feat_enable)
-    int feat_fpi = 0;            // floats per image: popcount(mask) * feat_layer_floats()
-    int feat_cap = 0;            // images the buffer holds (= the images one pass takes)
-    int feat_n = 0;              // images of the last forward made with features on (0: none since vitx_feat_enable)
-    float *feat_out = nullptr;   // [feat_cap][feat_fpi]: per image the selected layers in ascending order, each [cls D][mean D][tokens (N-Tp) D] (selected parts only)
-    bool feat_on() const { return feat_flags != 0; }
-    int feat_layer_floats() const { return D * ((feat_flags & VITX_FEAT_CLS ? 1 : 0) + (feat_flags & VITX_FEAT_MEAN ? 1 : 0) + (feat_flags & VITX_FEAT_TOKENS ? N - Tp : 0)); }
-    // the slots of layer il in image first_img's block of feat_out (nullptr: not selected), in the layout's order cls, mean, tokens
-    void feat_slots(int first_img, int il, int flags, float **o_cls, float **o_mean, float **o_tok) const {
-        float *o = feat_out + (size_t)first_img * feat_fpi + (size_t)layer_slot(feat_mask, il) * feat_layer_floats();
-        *o_cls = *o_mean = *o_tok = nullptr;
-        if (flags & VITX_FEAT_CLS) { *o_cls = o; o += D; }
-        if (flags & VITX_FEAT_MEAN) { *o_mean = o; o += D; }
-        if (flags & VITX_FEAT_TOKENS) *o_tok = o;
-    }
-    // MEAN or TOKENS of the last layer need every row of it: no class-rows-only tail while they are on (as while the trace is)
-    bool feat_last_all_rows() const { return (feat_flags & (VITX_FEAT_MEAN | VITX_FEAT_TOKENS)) && ((feat_mask >> (L - 1)) & 1); }
-    void feat_free() { if (feat_out) (void)hipFree(feat_out); feat_out = nullptr; }
-    // zero-shot classification (vitx_zeroshot_set): nothing is allocated or launched while zs_K == 0
-    int zs_K = 0, zs_Kpad = 0;   // classes of the bank; its rows on the device (K rounded up to the GEMM's column tile `tn`, zero rows beyond K)
-    int zs_kind = 0;             // enum vitx_zs_kind
-    float zs_scale = 1.0f, zs_bias = 0.0f;
-    int zs_cap = 0;              // images the buffers hold (= the images one pass takes)
-    int zs_n = 0;                // images of the last forward made with a bank set (0: none since vitx_zeroshot_set)
-    void *zs_bank = nullptr;     // [zs_Kpad][zs_width()] operand type
-    float *zs_zero = nullptr;    // [zs_Kpad] zeros: the bank GEMM's bias
-    float *zs_out = nullptr;     // [zs_cap][2][zs_K]: per image the probabilities, then the logits
-    std::vector<void *> zs_a;    // per slice: [round_up(zs_cap, tm)][zs_width()] operand type, the normalised embeddings (the GEMM's A rows)
-    std::vector<float *> zs_acc; // per slice: [round_up(zs_cap, tm)][zs_Kpad] f32, the GEMM's output
-    bool zs_on() const { return zs_K != 0; }
+    bool any_output() const { bool any = false; each_output([&](Output &) { any = true; }); return any; }
+    bool outputs_need_last_rows() const { bool need = false; each_output([&](Output &o) { need |= o.last_all_rows; }); return need; }
+    // The widths a bank and a gallery must have are the context's own: they are asked for before either exists (vitx_nn_width)
     int zs_width() const { return map ? D : C; }      // E: the pooled embedding e, or the head GEMM's logits row (CLIP: image_embeds)
-    void zs_free() {
-        for (void *p : zs_a) if (p) (void)hipFree(p);
-        for (float *p : zs_acc) if (p) (void)hipFree(p);
-        zs_a.clear(); zs_acc.clear();
-        if (zs_bank) (void)hipFree(zs_bank);
-        if (zs_zero) (void)hipFree(zs_zero);
-        if (zs_out) (void)hipFree(zs_out);
-        zs_bank = nullptr; zs_zero = nullptr; zs_out = nullptr;
-        zs_K = zs_Kpad = zs_cap = zs_n = 0;
-    }
-    // nearest neighbours in a gallery (vitx_nn_set): nothing is allocated or launched while nn_G == 0
-    static constexpr int kNnChunk = 32768;  // Gc: gallery rows one chunk GEMM scores (a multiple of the GEMM's column tile; tools/nn_cost.py sweeps it)
-    long nn_G = 0, nn_Gpad = 0;  // rows of the gallery; its rows on the device (G rounded up to the column tile, zero rows beyond G)
-    int nn_k = 0, nn_source = 0, nn_E = 0;
-    int nn_nlabels = 0;          // 0: no labels, no vote
-    float nn_T = 0.0f;
-    int nn_cap = 0;              // images the buffers hold (= the images one pass takes)
-    int nn_n = 0;                // images of the last forward made with a gallery set (0: none since vitx_nn_set)
-    void *nn_gallery = nullptr;  // [nn_Gpad][nn_E] operand type
-    int *nn_labels = nullptr;    // [nn_G]
-    float *nn_zero = nullptr;    // [kNnChunk] zeros: the chunk GEMMs' bias
-    float *nn_out = nullptr;     // [nn_cap][nn_k] {f32 score, i32 index}
-    float *nn_vote = nullptr;    // [nn_cap][nn_nlabels]
-    std::vector<void *> nn_a;    // per slice: [round_up(nn_cap, tm)][nn_E] operand type, the normalised queries (the GEMMs' A rows)
-    std::vector<float *> nn_acc; // per slice: [round_up(nn_cap, tm)][kNnChunk] f32, one chunk's scores
-    std::vector<void *> nn_state;// per slice: the running top-k (nn_state_bytes)
-    size_t nn_scratch = 0;       // bytes of nn_acc + nn_state over all slices
-    bool nn_on() const { return nn_G != 0; }
     int nn_width(int source) const {       // E of a source: the logits row, or the head GEMM's operand row Z
         if (source == VITX_NN_LOGITS) return C;
         return source == VITX_NN_EMBED ? (pool ? 2 * D : D) : 0;
-    }
-    void nn_free() {
-        for (void *p : nn_a) if (p) (void)hipFree(p);
-        for (float *p : nn_acc) if (p) (void)hipFree(p);
-        for (void *p : nn_state) if (p) (void)hipFree(p);
-        nn_a.clear(); nn_acc.clear(); nn_state.clear();
-        for (void **p : {&nn_gallery, (void **)&nn_labels, (void **)&nn_zero, (void **)&nn_out, (void **)&nn_vote}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-        nn_G = nn_Gpad = 0; nn_k = nn_source = nn_E = nn_nlabels = nn_cap = nn_n = 0; nn_T = 0.0f; nn_scratch = 0;
-    }
-    // the dense head (vitx_dense_set): nothing is allocated or launched while dn_K == 0
-    int dn_K = 0, dn_Kpad = 0;   // classes of the head; its rows on the device (K rounded up to the GEMM's column tile `tn`, zero rows beyond K)
-    int dn_Dc = 0;               // the operand's width: popcount(dn_mask) * D
-    uint64_t dn_mask = 0;        // selected layers (never 0 while on: "the last layer" is resolved at vitx_dense_set)
-    int dn_oh = 0, dn_ow = 0;    // the label map's shape
-    int dn_flags = 0;            // VITX_DENSE_*
-    int dn_cap = 0;              // images the output buffers hold (= the images one pass takes)
-    int dn_n = 0;                // images of the last forward made with a head set (0: none since vitx_dense_set)
-    void *dn_W = nullptr;        // [dn_Kpad][dn_Dc] operand type
-    float *dn_bias = nullptr;    // [dn_Kpad] f32, zeros beyond K
-    uint8_t *dn_labels = nullptr;// [dn_cap][dn_oh][dn_ow]
-    float *dn_score = nullptr;   // VITX_DENSE_SCORE: [dn_cap][dn_oh][dn_ow]
-    float *dn_logits = nullptr;  // VITX_DENSE_LOGITS: [dn_cap][gh * gw][dn_K], the patch logits kept for vitx_dense_read
-    std::vector<void *> dn_a;    // per slice: [round_up(slice cap * gh * gw, tm)][dn_Dc] operand type, the GEMM's A rows
-    std::vector<float *> dn_acc; // per slice: [round_up(slice cap * gh * gw, tm)][dn_Kpad] f32, the patch logits
-    size_t dn_scratch = 0;       // bytes of dn_a + dn_acc over all slices
-    bool dense_on() const { return dn_K != 0; }
-    // a selected last layer needs every row of it: no class-rows-only tail while the head is set (as with VITX_FEAT_TOKENS of the last layer)
-    bool dense_last_all_rows() const { return dense_on() && ((dn_mask >> (L - 1)) & 1); }
-    void dense_free() {
-        for (void *p : dn_a) if (p) (void)hipFree(p);
-        for (float *p : dn_acc) if (p) (void)hipFree(p);
-        dn_a.clear(); dn_acc.clear();
-        for (void **p : {&dn_W, (void **)&dn_bias, (void **)&dn_labels, (void **)&dn_score, (void **)&dn_logits}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-        dn_K = dn_Kpad = dn_Dc = dn_oh = dn_ow = dn_flags = dn_cap = dn_n = 0; dn_mask = 0; dn_scratch = 0;
-    }
-    // the depth head (vitx_depth_set): nothing is allocated or launched while dp_K == 0
-    int dp_K = 0, dp_Kpad = 0;   // bins of the head; its rows on the device (K rounded up to the GEMM's column tile `tn`, zero rows beyond K)
-    int dp_Dc = 0;               // the operand's width: popcount(dp_mask) * D
-    uint64_t dp_mask = 0;        // selected layers (never 0 while on)
-    int dp_u = 0;                // the fine plane is dp_u gh x dp_u gw
-    int dp_oh = 0, dp_ow = 0;    // the depth map's shape
-    float dp_lo = 0.0f, dp_hi = 0.0f;    // the clamp
-    int dp_flags = 0;            // VITX_DEPTH_*
-    int dp_cap = 0;              // images the output buffers hold (= the images one pass takes)
-    int dp_n = 0;                // images of the last forward made with a head set (0: none since vitx_depth_set)
-    void *dp_Wp = nullptr;       // [dp_Kpad][dp_Dc] operand type: the patch half
-    void *dp_Wc = nullptr;       // the class half, or nullptr: the offsets are the bias then, and no class rows are written
-    float *dp_bias = nullptr;    // [dp_Kpad] f32, zeros beyond K: the class GEMM's bias, or every image's offsets
-    float *dp_zero = nullptr;    // [dp_Kpad] zeros: the patch GEMM's bias
-    float *dp_bins = nullptr;    // [dp_Kpad] f32 bin centres
-    std::vector<float> dp_bias_host;     // [dp_K]: what vitx_depth_read returns as offsets of a head without a class half
-    float *dp_depth = nullptr;   // [dp_cap][dp_oh][dp_ow]
-    float *dp_fine = nullptr;    // [dp_cap][dp_u gh][dp_u gw]: the resize reads it; vitx_depth_read returns it under VITX_DEPTH_FINE
-    float *dp_logits = nullptr;  // VITX_DEPTH_LOGITS: [dp_cap][gh * gw][dp_K], the patch logits kept for vitx_depth_read
-    float *dp_off = nullptr;     // VITX_DEPTH_LOGITS with a class half: [dp_cap][dp_K], the offsets kept
-    std::vector<void *> dp_a;    // per slice: [round_up(slice cap * gh * gw, tm)][dp_Dc] operand type, the patch GEMM's A rows
-    std::vector<float *> dp_acc; // per slice: [the same rows][dp_Kpad] f32, the patch logits
-    std::vector<void *> dp_ac;   // per slice, class half only: [round_up(slice cap, tm)][dp_Dc] operand type, the class rows
-    std::vector<float *> dp_o;   // per slice, class half only: [round_up(slice cap, tm)][dp_Kpad] f32, the offsets
-    size_t dp_scratch = 0;       // bytes of dp_a + dp_acc + dp_ac + dp_o over all slices
-    bool depth_on() const { return dp_K != 0; }
-    // a selected last layer needs every row of it (as with the dense head)
-    bool depth_last_all_rows() const { return depth_on() && ((dp_mask >> (L - 1)) & 1); }
-    void depth_free() {
-        for (auto *v : {&dp_a, &dp_ac}) { for (void *p : *v) if (p) (void)hipFree(p); v->clear(); }
-        for (auto *v : {&dp_acc, &dp_o}) { for (float *p : *v) if (p) (void)hipFree(p); v->clear(); }
-        for (void **p : {&dp_Wp, &dp_Wc, (void **)&dp_bias, (void **)&dp_zero, (void **)&dp_bins, (void **)&dp_depth, (void **)&dp_fine, (void **)&dp_logits, (void **)&dp_off}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-        dp_bias_host.clear();
-        dp_K = dp_Kpad = dp_Dc = dp_u = dp_oh = dp_ow = dp_flags = dp_cap = dp_n = 0; dp_mask = 0; dp_scratch = 0; dp_lo = dp_hi = 0.0f;
     }
     // hipGraph cache of the single-stream (small-batch) forward, opt-in (vitx_ctx_options::graph).  Key = (images, batch, outputs): the graph
     // bakes the pointers in.  An entry is captured the second time in a row its key is seen (one-off calls are never captured).
@@ -325,12 +188,6 @@ struct vitx_ctx {
         if (prof_base) (void)hipEventDestroy(prof_base);
         if (ln_fb_host) (void)hipHostFree(ln_fb_host);
         if (trace_buf) (void)hipFree(trace_buf);
-        attn_free();
-        feat_free();
-        zs_free();
-        nn_free();
-        dense_free();
-        depth_free();
         for (void *p : allocs) (void)hipFree(p);
         if (stream) (void)hipStreamDestroy(stream);
     }
@@ -346,15 +203,10 @@ struct vitx_ctx {
     }
 };
 
-namespace vitx {
-// the argument checks vitx_op_depth_fine / vitx_op_depth_resize / vitx_op_depth (ops.cpp) share with vitx_depth_host (depth_host.cpp): none needs a device
-int depth_fine_args(const char *name, const void *logits, long ld, const void *bins, int n, int gh, int gw, int K, int u, const void *fine);
-int depth_resize_args(const char *name, const void *fine, int n, int fh, int fw, int out_h, int out_w, float lo, float hi, const void *out);
-}  // namespace vitx
-
+// The profile record around one launch on stream s.  A null context (a vitx_op_* call through heads.cpp) records nothing.
 struct ProfScope {
     vitx_ctx *c; hipStream_t s; size_t idx = 0; bool on;
-    ProfScope(vitx_ctx *c_, hipStream_t s_, int cls, double flops, double bytes) : c(c_), s(s_), on(c_->prof_on) {
+    ProfScope(vitx_ctx *c_, hipStream_t s_, int cls, double flops, double bytes) : c(c_), s(s_), on(c_ && c_->prof_on) {
         if (!on) return;
         vitx_ctx::Rec r{cls, c->next_event(), c->next_event(), flops, bytes};
         idx = c->recs.size(); c->recs.push_back(r);

@@ -4,9 +4,9 @@
 #include <cmath>
 #include <vector>
 
-#include "context.h"
 #include "dense_resample.h"
 #include "depth_bins.h"
+#include "heads.h"
 
 namespace vitx {
 
@@ -31,6 +31,7 @@ int depth_resize_args(const char *name, const void *fine, int n, int fh, int fw,
 }
 
 }  // namespace vitx
+using namespace vitx;
 
 extern "C" int vitx_depth_host(const float *logits, long ld, const float *offsets, const float *bins, int n, int gh, int gw, int K, int upsample, int out_h, int out_w,
                                float min_depth, float max_depth, float *depth, float *fine_out) {

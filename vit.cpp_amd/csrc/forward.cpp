@@ -21,12 +21,9 @@ int gemm(vitx_ctx *c, hipStream_t st, int pc, int epi, GemmArgs a, const QuantW 
     }
     // algorithmic work of the launch: the REAL rows (a LayerNorm-fusing launch computes and stores its pad rows too -- GemmLn -- but they are not work
     // the forward asked for: r03 counted them, +0.46 % on the fc2 figure)
-    const int M_alg = rows_alg > 0 ? rows_alg : a.M_real, N = a.N, K = a.K, esz = epi_out_bytes(epi);
-    double bytes = (double)M_alg * K * 2 + (double)N * K * (fused ? 0.5625 : 2.0) + (double)M_alg * N * esz;
-    if (epi == EPI_BIAS_RESID) bytes += (double)M_alg * N * 4;
-    if (epi == EPI_BIAS_HILO) bytes += (double)M_alg * N * esz;        // the second plane
-    if (ln) bytes += (double)M_alg * N * 2;
-    ProfScope ps(c, st, pc, 2.0 * M_alg * (double)N * K, bytes);
+    double flops, bytes;
+    gemm_work(epi, rows_alg > 0 ? rows_alg : a.M_real, a.N, a.K, fused != nullptr, ln != nullptr, &flops, &bytes);
+    ProfScope ps(c, st, pc, flops, bytes);
     if (fused) {
         a.W = fused->blocks; a.Wscale = fused->scales;
         HIP_TRY(launch_gemm_q4(c->dtype, epi, a, st));
@@ -50,20 +47,22 @@ int gemm_mx(vitx_ctx *c, hipStream_t st, int pc, int epi, const uint8_t *A, cons
 
 // Attention maps of layer il (vitx_attn_enable) for the n images first_img .. of a sub-batch, from the QKV its qkv projection has just written
 // (lo_off: the parity mode's lo plane).  The kernels only read QKV and write the context's map buffers at the images' global positions.
-// Rollout: A^_l goes to attn_roll[l & 1] and becomes R_l = A^_l R_(l-1) in place; the last layer contributes row 0 of its factor only,
+// Rollout: A^_l goes to roll[l & 1] and becomes R_l = A^_l R_(l-1) in place; the last layer contributes row 0 of its factor only,
 // built from its class-token maps -- the rows a cls_tail context still has.
 static int attention_maps(vitx_ctx *c, hipStream_t st, const void *qkv, long lo_off, int il, int first_img, int n) {
-    const int N = c->N, D = c->D, H = c->H, L = c->L, fpi = c->attn_fpi;
+    const AttnMaps &am = *c->attn;
+    const int N = c->N, D = c->D, H = c->H, L = c->L, fpi = am.fpi;
     const size_t NN = (size_t)N * N;
-    const bool rollout = (c->attn_flags & VITX_ATTN_ROLLOUT) != 0;
+    const bool rollout = (am.flags & VITX_ATTN_ROLLOUT) != 0;
+    float *const roll[2] = {am.roll[0].as<float>(), am.roll[1].as<float>()};
     const double qk_bytes = (double)n * N * 2 * D * 2 * (lo_off ? 2 : 1);        // q and k of every token (both planes in the parity mode)
-    float *out_img = c->attn_out + (size_t)first_img * fpi;
+    float *out_img = am.out.as<float>() + (size_t)first_img * fpi;
     float *cls = nullptr;
     long cls_stride = 0;
-    if ((c->attn_mask >> il) & 1) {
-        cls = out_img + (size_t)layer_slot(c->attn_mask, il) * H * N; cls_stride = fpi;
+    if ((am.mask >> il) & 1) {
+        cls = out_img + (size_t)layer_slot(am.mask, il) * H * N; cls_stride = fpi;
     } else if (rollout && il + 1 == L) {
-        cls = c->attn_cls_last + (size_t)first_img * H * N; cls_stride = (long)H * N;
+        cls = am.cls_last.as<float>() + (size_t)first_img * H * N; cls_stride = (long)H * N;
     }
     if (cls) {
         ProfScope ps(c, st, PC_ATTN_MAP, 2.0 * n * (double)N * D, qk_bytes / 2 + (double)n * H * N * 4);
@@ -71,18 +70,18 @@ static int attention_maps(vitx_ctx *c, hipStream_t st, const void *qkv, long lo_
     }
     if (!rollout) return VITX_OK;
     if (il + 1 < L) {
-        float *a = c->attn_roll[il & 1] + (size_t)first_img * NN;
+        float *a = roll[il & 1] + (size_t)first_img * NN;
         {
             ProfScope ps(c, st, PC_ATTN_MAP, 2.0 * n * (double)NN * D, qk_bytes + (double)n * NN * 4);
             HIP_TRY(launch_attention_head_mean(c->dtype, qkv, lo_off, a, n, N, D, H, true, st));
         }
         if (il > 0) {
             ProfScope ps(c, st, PC_ATTN_MAP, 2.0 * n * (double)NN * N, (double)n * NN * 12);
-            HIP_TRY(launch_rollout_step(a, c->attn_roll[(il + 1) & 1] + (size_t)first_img * NN, n, N, st));
+            HIP_TRY(launch_rollout_step(a, roll[(il + 1) & 1] + (size_t)first_img * NN, n, N, st));
         }
         return VITX_OK;
     }
-    const float *r = L > 1 ? c->attn_roll[(L - 2) & 1] + (size_t)first_img * NN : nullptr;
+    const float *r = L > 1 ? roll[(L - 2) & 1] + (size_t)first_img * NN : nullptr;
     ProfScope ps(c, st, PC_ATTN_MAP, 2.0 * n * (double)NN, (double)n * NN * 4);
     HIP_TRY(launch_rollout_row(cls, cls_stride, r, out_img + (fpi - N), fpi, n, N, H, st));
     return VITX_OK;
@@ -93,6 +92,8 @@ static int attention_maps(vitx_ctx *c, hipStream_t st, const void *qkv, long lo_
 struct SliceForward {
     vitx_ctx *c; vitx_ctx::Slice &sl; hipStream_t st; int first_img, n;
     const WeightSet &ws = *c->wset;
+    const size_t si = &sl - &c->slices[0];                          // the slice's index: the per-slice buffers of the opt-in outputs
+    const HeadLaunch head{*c->tune, c->dtype, st, c};               // how the head sequences (heads.cpp) launch, recorded in this context's profile
     const int D = c->D, N = c->N, tm = c->tm, tn = c->tn, dt = c->dtype;
     const int F = c->F, F1 = c->F1;                                 // MLP widths: fc2's K and fc1's N (4 D both, or F and 2 F of a `glu` context)
     static constexpr double eb = 2.0;                               // operand bytes
@@ -126,18 +127,19 @@ struct SliceForward {
     // z != nullptr (the last layer of a pooled-head context): the same launch also writes the head's operand rows RNE(cls) ‖ RNE(mean), with or
     // without features of that layer selected -- one pass over the residual stream serves both.
     int features(int il, bool cls_rows, void *z = nullptr) {
-        const bool sel = c->feat_on() && ((c->feat_mask >> il) & 1);
+        const Features *ft = c->feat.get();
+        const bool sel = ft && ft->selects(il);
         if (!sel && !z) return VITX_OK;
-        const int fl = sel ? c->feat_flags : 0, Tp = c->Tp;
-        float *o_cls, *o_mean, *o_tok;
-        c->feat_slots(first_img, il, fl, &o_cls, &o_mean, &o_tok);
+        const int fl = sel ? ft->flags : 0, Tp = c->Tp;
+        float *o_cls = nullptr, *o_mean = nullptr, *o_tok = nullptr;
+        if (sel) ft->slots(first_img, il, &o_cls, &o_mean, &o_tok);
         if (c->map) {        // no class row: VITX_FEAT_CLS of such a context is the pooled embedding, written by pooled_tail
             o_cls = nullptr;
             if (!o_mean && !o_tok) return VITX_OK;
         }
         const double rows = (double)n * ((o_cls || z ? 1 : 0) + (o_mean || o_tok || z ? N - Tp : 0));
         ProfScope ps(c, st, sel ? PC_FEATURES : PC_HEAD_POOL, 0, rows * D * 4 + (double)n * D * 4 * ((o_cls ? 1 : 0) + (o_mean ? 1 : 0) + (o_tok ? N - Tp : 0)) + (z ? (double)n * 2 * D * eb : 0.0));
-        HIP_TRY(launch_features(cls_rows ? sl.Xc : sl.X, D, cls_rows ? (long)D : (long)N * D, ws.norm_w, ws.norm_b, o_cls, o_mean, o_tok, c->feat_fpi,
+        HIP_TRY(launch_features(cls_rows ? sl.Xc : sl.X, D, cls_rows ? (long)D : (long)N * D, ws.norm_w, ws.norm_b, o_cls, o_mean, o_tok, ft ? ft->fpi : 0,
                                 n, cls_rows ? 1 : N, D, c->hp.eps, (fl & VITX_FEAT_L2) != 0, st, cls_rows ? 1 : Tp, z, dt));
         return VITX_OK;
     }
@@ -163,128 +165,69 @@ struct SliceForward {
         if ((rc = gemm(c, st, PC_GEMM_TAIL, c->fc1_epi, dense_gemm(sl.U2, ws.map_fc1_w, ws.map_fc1_b, sl.Hbuf, Mc, n, 4 * D, round_up(4 * D, tn), D)))) return rc;
         if ((rc = gemm(c, st, PC_GEMM_TAIL, EPI_BIAS_RESID, dense_gemm(sl.Hbuf, ws.map_fc2_w, ws.map_fc2_b, sl.Xc, Mc, n, D, round_up(D, tn), 4 * D)))) return rc;
         float *o_cls = nullptr, *o_mean, *o_tok;
-        const bool sel = c->feat_on() && ((c->feat_mask >> (c->L - 1)) & 1);
-        if (sel) c->feat_slots(first_img, c->L - 1, c->feat_flags, &o_cls, &o_mean, &o_tok);
+        const Features *ft = c->feat.get();
+        const bool sel = ft && ft->selects(c->L - 1);
+        if (sel) ft->slots(first_img, c->L - 1, &o_cls, &o_mean, &o_tok);
         ProfScope ps(c, st, sel && o_cls ? PC_FEATURES : PC_HEAD_POOL, 0, (double)n * D * (4 + eb + (o_cls ? 4 : 0)));
-        HIP_TRY(launch_pool_embed(sl.Xc, sl.Z, dt, o_cls, c->feat_fpi, (c->feat_flags & VITX_FEAT_L2) != 0, n, D, st));
+        HIP_TRY(launch_pool_embed(sl.Xc, sl.Z, dt, o_cls, ft ? ft->fpi : 0, ft && (ft->flags & VITX_FEAT_L2), n, D, st));
         return VITX_OK;
     }
-    // Zero-shot classification (vitx_zeroshot_set), after the head: z = the f32 embedding rows of this sub-batch (row stride ldz floats) -> unit rows in
-    // the operand type, the bank GEMM through the dispatcher as the head's goes, then logits and probabilities at the images' global positions
-    int zeroshot(const float *z, long ldz) {
+    // The four heads after the classifier, each one sequence of heads.cpp on this slice's buffers, its results at the images' global positions.
+    // lg: this sub-batch's f32 logits rows (row stride ldl).  Zero-shot (vitx_zeroshot_set) embeds the pooled embedding e of an attention-pooling
+    // head, else the logits row; nearest neighbours (vitx_nn_set) the logits row, or the head GEMM's operand rows Z.
+    int heads(const float *lg, long ldl) {
+        if (const ZeroShot *zs = c->zs.get()) {
+            float *out = zs->out.as<float>() + (size_t)first_img * 2 * zs->K;
+            HIP_TRY(head_zeroshot(head, c->map ? sl.Xc : lg, c->map ? (long)D : ldl, zs->a[si].p, zs->bank.p, zs->zero.as<float>(), zs->acc[si].as<float>(), out, out + zs->K,
+                                  2L * zs->K, n, zs->K, zs->E, zs->kind, zs->scale, zs->bias));
+        }
+        if (const Gallery *nn = c->nn.get()) {
+            const bool operand = nn->source != VITX_NN_LOGITS;
+            HIP_TRY(head_nearest(head, operand ? (const void *)sl.Z : lg, operand ? (long)nn->E : ldl, operand, nn->a[si].p, nn->gallery.p, nn->zero.as<float>(), nn->acc[si].as<float>(),
+                                 nn->state[si].p, nn->G, nn->E, nn->k, Gallery::kChunk, nn->labels.as<int>(), nn->nlabels, nn->T, nn->out.as<float>() + (size_t)first_img * nn->k * 2,
+                                 nn->vote ? nn->vote.as<float>() + (size_t)first_img * nn->nlabels : nullptr, n));
+        }
+        const size_t Np = N - c->Tp;
+        if (const DenseHead *dn = c->dense.get()) {
+            const size_t px = (size_t)dn->oh * dn->ow;
+            HIP_TRY(head_dense(head, dn->a[si].p, dn->W.p, dn->bias.as<float>(), dn->acc[si].as<float>(), n, c->gh, c->gw, dn->K, dn->Dc, dn->oh, dn->ow,
+                               dn->labels.as<uint8_t>() + (size_t)first_img * px, dn->score ? dn->score.as<float>() + (size_t)first_img * px : nullptr,
+                               dn->logits ? dn->logits.as<float>() + (size_t)first_img * Np * dn->K : nullptr));
+        }
+        if (const DepthHead *dp = c->depth.get()) {
+            const size_t px = (size_t)dp->oh * dp->ow, fpx = (size_t)dp->u * c->gh * dp->u * c->gw;
+            const bool cls = (bool)dp->Wc;
+            HIP_TRY(head_depth(head, dp->a[si].p, dp->Wp.p, dp->zero.as<float>(), dp->acc[si].as<float>(), cls ? dp->ac[si].p : nullptr, dp->Wc.p, dp->bias.as<float>(),
+                               cls ? dp->o[si].as<float>() : nullptr, dp->bins.as<float>(), n, c->gh, c->gw, dp->K, dp->Dc, dp->u, dp->oh, dp->ow, dp->lo, dp->hi,
+                               dp->fine.as<float>() + (size_t)first_img * fpx, dp->depth.as<float>() + (size_t)first_img * px,
+                               dp->logits ? dp->logits.as<float>() + (size_t)first_img * Np * dp->K : nullptr, dp->off ? dp->off.as<float>() + (size_t)first_img * dp->K : nullptr));
+        }
+        return VITX_OK;
+    }
+    // The operand rows of the dense and the depth head, as layer il finishes (where features(il, ..) is called).  head_rows, the one step: `rows` rows of
+    // the f32 residual stream (x, ldx, group, gstride as launch_layernorm reads them) -- their final norm through the stand-alone LayerNorm (no kernel
+    // of its own), or, raw, through the streaming conversion -- rounded to the operand type into y, rows of Dc elements: a column slot of compact rows.
+    int head_rows(int pc, bool norm, const float *x, long ldx, void *y, int Dc, int rows, int group = 1, long gstride = 0) {
+        ProfScope ps(c, st, pc, 0, (double)rows * D * (4 + eb));
+        if (norm) HIP_TRY(launch_layernorm(dt, x, ldx, ws.norm_w, ws.norm_b, y, Dc, rows, D, c->hp.eps, st, group, gstride));
+        else HIP_TRY(launch_depth_rows(dt, x, ldx, y, Dc, rows, D, st, group, gstride));
+        return VITX_OK;
+    }
+    // the patch rows of this sub-batch's images into columns slot * D .. of h's operand rows [n * Np][Dc]
+    int patch_rows(const PatchHead &h, int il, int pc, bool norm) {
+        const int Np = N - c->Tp;
+        return head_rows(pc, norm, sl.X + (size_t)c->Tp * D, D, h.a[si].as<char>() + h.col(il, D) * 2, h.Dc, n * Np, Np, (long)N * D);
+    }
+    // the dense head (vitx_dense_set) reads the final norm; the depth head (vitx_depth_set) the raw stream or (VITX_DEPTH_NORM) the final norm, and
+    // with a class half the class-token row of every image the same way (one row per image)
+    int patch_head_rows(int il) {
         int rc;
-        const int K = c->zs_K, Kpad = c->zs_Kpad, E = c->zs_width(), Mz = round_up(n, tm);
-        const size_t si = &sl - &c->slices[0];
-        void *a = c->zs_a[si]; float *acc = c->zs_acc[si];
-        {
-            ProfScope ps(c, st, PC_ZEROSHOT, 0, (double)n * E * 4 + (double)Mz * E * eb);
-            HIP_TRY(launch_zs_embed(dt, z, ldz, a, n, Mz, E, st));
-        }
-        if ((rc = gemm(c, st, PC_ZEROSHOT, EPI_BIAS_F32, dense_gemm(a, c->zs_bank, c->zs_zero, acc, Mz, n, K, Kpad, E, Kpad)))) return rc;
-        float *out = c->zs_out + (size_t)first_img * 2 * K;
-        ProfScope ps(c, st, PC_ZEROSHOT, 0, (double)n * K * 4 * (c->zs_kind == VITX_ZS_SOFTMAX ? 7 : 3));
-        HIP_TRY(launch_zs_score(acc, Kpad, out, out + K, 2L * K, n, K, c->zs_kind, c->zs_scale, c->zs_bias, st));
-        return VITX_OK;
-    }
-    // Nearest neighbours in a gallery (vitx_nn_set), after the head: the query rows of this sub-batch -- the f32 logits rows, or the head GEMM's
-    // operand rows Z -- become unit rows in the operand type (zero-shot's rule); then the gallery passes by in chunks of kNnChunk rows, each one
-    // dispatcher GEMM into the slice's score scratch (its own base pointer into the gallery: only a chunk has to fit the GEMM's operand window) and
-    // one selection launch that merges the chunk's real columns into the slice's running state; the last launch writes the k best (and the vote)
-    // at the images' global positions.  2 ceil(G / Gc) + 2 launches.
-    int nearest(const float *lg, long ldl) {
-        int rc;
-        const int E = c->nn_E, k = c->nn_k, Mz = round_up(n, tm), Gc = vitx_ctx::kNnChunk;
-        const long G = c->nn_G;
-        const size_t si = &sl - &c->slices[0];
-        void *a = c->nn_a[si]; float *acc = c->nn_acc[si]; void *state = c->nn_state[si];
-        {
-            ProfScope ps(c, st, PC_NN, 0, (double)n * E * (c->nn_source == VITX_NN_LOGITS ? 4 : eb) + (double)Mz * E * eb);
-            if (c->nn_source == VITX_NN_LOGITS) HIP_TRY(launch_zs_embed(dt, lg, ldl, a, n, Mz, E, st));
-            else HIP_TRY(launch_zs_embed_operand(dt, sl.Z, E, a, n, Mz, E, st));
-        }
-        for (long g0 = 0; g0 < G; g0 += Gc) {
-            const int cols = (int)std::min<long>(Gc, G - g0);
-            if ((rc = gemm(c, st, PC_NN, EPI_BIAS_F32, dense_gemm(a, (const char *)c->nn_gallery + (size_t)g0 * E * 2, c->nn_zero, acc, Mz, n, cols, round_up(cols, tn), E, Gc)))) return rc;
-            ProfScope ps(c, st, PC_NN, 0, (double)n * cols * 4);
-            HIP_TRY(launch_nn_select(acc, Gc, n, cols, g0, state, k, g0 == 0, st));
-        }
-        ProfScope ps(c, st, PC_NN, 0, (double)n * kNnSegs * k * 8 + (double)n * (k * 8 + c->nn_nlabels * 4));
-        HIP_TRY(launch_nn_finish(state, n, k, c->nn_labels, c->nn_nlabels, c->nn_T, c->nn_out + (size_t)first_img * k * 2,
-                                 c->nn_vote ? c->nn_vote + (size_t)first_img * c->nn_nlabels : nullptr, st));
-        return VITX_OK;
-    }
-    // The dense head (vitx_dense_set).  dense_rows, as layer il finishes (where features(il, ..) is called): the final norm of the patch rows of this
-    // sub-batch, rounded to the operand type, into columns slot * D .. of the slice's compact operand rows [n * Np][Dc] -- the stand-alone LayerNorm
-    // with the patch rows as its groups, no kernel of its own.  dense_head, after the classifier: the pad rows zeroed, the patch logits through
-    // the dispatcher, the label kernel into the images' global positions, and (VITX_DENSE_LOGITS) the real columns kept.
-    int dense_rows(int il) {
-        if (!c->dense_on() || !((c->dn_mask >> il) & 1)) return VITX_OK;
-        const int Np = N - c->Tp, Dc = c->dn_Dc, rows = n * Np;
-        const size_t si = &sl - &c->slices[0];
-        ProfScope ps(c, st, PC_DENSE, 0, (double)rows * D * (4 + eb));
-        HIP_TRY(launch_layernorm(dt, sl.X + (size_t)c->Tp * D, D, ws.norm_w, ws.norm_b, (char *)c->dn_a[si] + (size_t)layer_slot(c->dn_mask, il) * D * 2, Dc, rows, D, c->hp.eps, st, Np, (long)N * D));
-        return VITX_OK;
-    }
-    int dense_head() {
-        int rc;
-        const int Np = N - c->Tp, Dc = c->dn_Dc, K = c->dn_K, Kpad = c->dn_Kpad, rows = n * Np, Mr = round_up(rows, tm);
-        const size_t si = &sl - &c->slices[0], px = (size_t)c->dn_oh * c->dn_ow;
-        void *a = c->dn_a[si]; float *acc = c->dn_acc[si];
-        if (Mr > rows) HIP_TRY(hipMemsetAsync((char *)a + (size_t)rows * Dc * 2, 0, (size_t)(Mr - rows) * Dc * 2, st));
-        if ((rc = gemm(c, st, PC_DENSE, EPI_BIAS_F32, dense_gemm(a, c->dn_W, c->dn_bias, acc, Mr, rows, K, Kpad, Dc, Kpad)))) return rc;
-        {
-            ProfScope ps(c, st, PC_DENSE, 9.0 * n * (double)px * K, (double)rows * Kpad * 4 + (double)n * px * (c->dn_score ? 5 : 1));
-            HIP_TRY(launch_dense_labels(acc, Kpad, n, c->gh, c->gw, K, c->dn_oh, c->dn_ow, c->dn_labels + (size_t)first_img * px,
-                                        c->dn_score ? c->dn_score + (size_t)first_img * px : nullptr, st));
-        }
-        if (c->dn_logits) HIP_TRY(hipMemcpy2DAsync(c->dn_logits + (size_t)first_img * Np * K, (size_t)K * 4, acc, (size_t)Kpad * 4, (size_t)K * 4, rows, hipMemcpyDeviceToDevice, st));
-        return VITX_OK;
-    }
-    // The depth head (vitx_depth_set).  depth_rows, where dense_rows is called: the patch rows of layer il -- raw f32 residual stream through the
-    // streaming conversion, or (VITX_DEPTH_NORM) the final norm through the stand-alone LayerNorm as dense_rows does -- into columns slot * D .. of the
-    // slice's compact operand rows, and with a class half the class-token row of every image the same way (one row per group).  depth_head, after
-    // the classifier: the patch logits (zero bias) and the offsets (the head's bias) through the dispatcher, the fine plane, the depth map.
-    int depth_rows(int il) {
-        if (!c->depth_on() || !((c->dp_mask >> il) & 1)) return VITX_OK;
-        const int Np = N - c->Tp, Dc = c->dp_Dc, rows = n * Np;
-        const size_t si = &sl - &c->slices[0], col = (size_t)layer_slot(c->dp_mask, il) * D * 2;
-        const bool norm = (c->dp_flags & VITX_DEPTH_NORM) != 0;
-        {
-            ProfScope ps(c, st, PC_DEPTH, 0, (double)rows * D * (4 + eb));
-            if (norm) HIP_TRY(launch_layernorm(dt, sl.X + (size_t)c->Tp * D, D, ws.norm_w, ws.norm_b, (char *)c->dp_a[si] + col, Dc, rows, D, c->hp.eps, st, Np, (long)N * D));
-            else HIP_TRY(launch_depth_rows(dt, sl.X + (size_t)c->Tp * D, D, (char *)c->dp_a[si] + col, Dc, rows, D, st, Np, (long)N * D));
-        }
-        if (!c->dp_Wc) return VITX_OK;
-        ProfScope ps(c, st, PC_DEPTH, 0, (double)n * D * (4 + eb));
-        if (norm) HIP_TRY(launch_layernorm(dt, sl.X, (long)N * D, ws.norm_w, ws.norm_b, (char *)c->dp_ac[si] + col, Dc, n, D, c->hp.eps, st));
-        else HIP_TRY(launch_depth_rows(dt, sl.X, (long)N * D, (char *)c->dp_ac[si] + col, Dc, n, D, st));
-        return VITX_OK;
-    }
-    int depth_head() {
-        int rc;
-        const int Np = N - c->Tp, Dc = c->dp_Dc, K = c->dp_K, Kpad = c->dp_Kpad, rows = n * Np, Mr = round_up(rows, tm), Mc = round_up(n, tm), u = c->dp_u;
-        const size_t si = &sl - &c->slices[0], px = (size_t)c->dp_oh * c->dp_ow, fpx = (size_t)u * c->gh * u * c->gw;
-        void *a = c->dp_a[si]; float *acc = c->dp_acc[si];
-        if (Mr > rows) HIP_TRY(hipMemsetAsync((char *)a + (size_t)rows * Dc * 2, 0, (size_t)(Mr - rows) * Dc * 2, st));
-        if ((rc = gemm(c, st, PC_DEPTH, EPI_BIAS_F32, dense_gemm(a, c->dp_Wp, c->dp_zero, acc, Mr, rows, K, Kpad, Dc, Kpad)))) return rc;
-        const float *off = c->dp_bias; long ldo = 0;
-        if (c->dp_Wc) {
-            if (Mc > n) HIP_TRY(hipMemsetAsync((char *)c->dp_ac[si] + (size_t)n * Dc * 2, 0, (size_t)(Mc - n) * Dc * 2, st));
-            if ((rc = gemm(c, st, PC_DEPTH, EPI_BIAS_F32, dense_gemm(c->dp_ac[si], c->dp_Wc, c->dp_bias, c->dp_o[si], Mc, n, K, Kpad, Dc, Kpad)))) return rc;
-            off = c->dp_o[si]; ldo = Kpad;
-        }
-        float *fine = c->dp_fine + (size_t)first_img * fpx;
-        {
-            ProfScope ps(c, st, PC_DEPTH, 11.0 * n * (double)fpx * K, (double)rows * Kpad * 4 + (double)n * fpx * 4);
-            HIP_TRY(launch_depth_fine(acc, Kpad, off, ldo, c->dp_bins, n, c->gh, c->gw, K, u, fine, st));
-        }
-        {
-            ProfScope ps(c, st, PC_DEPTH, 7.0 * n * (double)px, (double)n * (fpx + px) * 4);
-            HIP_TRY(launch_depth_resize(fine, n, u * c->gh, u * c->gw, c->dp_oh, c->dp_ow, c->dp_lo, c->dp_hi, c->dp_depth + (size_t)first_img * px, st));
-        }
-        if (c->dp_logits) HIP_TRY(hipMemcpy2DAsync(c->dp_logits + (size_t)first_img * Np * K, (size_t)K * 4, acc, (size_t)Kpad * 4, (size_t)K * 4, rows, hipMemcpyDeviceToDevice, st));
-        if (c->dp_off) HIP_TRY(hipMemcpy2DAsync(c->dp_off + (size_t)first_img * K, (size_t)K * 4, c->dp_o[si], (size_t)Kpad * 4, (size_t)K * 4, n, hipMemcpyDeviceToDevice, st));
-        return VITX_OK;
+        if (c->dense && c->dense->selects(il) && (rc = patch_rows(*c->dense, il, PC_DENSE, true))) return rc;
+        const DepthHead *dp = c->depth.get();
+        if (!dp || !dp->selects(il)) return VITX_OK;
+        const bool norm = (dp->flags & VITX_DEPTH_NORM) != 0;
+        if ((rc = patch_rows(*dp, il, PC_DEPTH, norm))) return rc;
+        return dp->Wc ? head_rows(PC_DEPTH, norm, sl.X, (long)N * D, dp->ac[si].as<char>() + dp->col(il, D) * 2, dp->Dc, n) : VITX_OK;
     }
     // Quantised matrices (block form in HBM): a q4_0 GEMM with few rows expands the blocks in its own LDS-fill path; everything else
     // is expanded just in time, one launch per layer, into the slice's scratch and then streamed by the wide-tile kernels.
@@ -369,7 +312,7 @@ struct SliceForward {
             ProfScope ps(c, st, PC_ROPE, 6.0 * n * (N - c->Tp) * (double)D, (double)n * (N - c->Tp) * 2 * D * eb * 2 * (c->prec_attn ? 2 : 1));
             HIP_TRY(launch_rope(dt, sl.QKV, lo_off, c->rope_cos, c->rope_sin, n, N, c->Tp, D, c->H, st));
         }
-        if (c->attn_on() && (rc = attention_maps(c, st, sl.QKV, lo_off, il, first_img, n))) return rc;
+        if (c->attn && (rc = attention_maps(c, st, sl.QKV, lo_off, il, first_img, n))) return rc;
         if (tail_now) {   // attention of token 0 (vit.cpp:848-858 for the one row vit.cpp:910-911 keeps) -> compact rows U[b]; class rows of X -> Xc[b]
             ProfScope ps(c, st, PC_ATTENTION_CLS, 4.0 * n * c->H * (double)N * (D / c->H), (double)M_real * 2 * D * eb * (c->prec_attn ? 2 : 1) + (double)n * D * (eb + 8));
             HIP_TRY(launch_attention_cls(dt, sl.QKV, lo_off, sl.U, sl.X, sl.Xc, n, N, D, c->H, st));
@@ -391,9 +334,8 @@ struct SliceForward {
         if ((rc = gemm_mx(c, st, r.pc_fc2, EPI_BIAS_RESID, sl.Hmx, sl.Hmx_s, w.mx[W_FC2], w.fc2_b, r.X, nullptr, r.M_real, D))) return rc;
         if (nx && (rc = layernorm_mx(r.X, nx->ln1_w, nx->ln1_b, sl.Umx, sl.Umx_s, r.M_real))) return rc;
         if (!c->trace_ids.empty() && (rc = trace(il + 1))) return rc;
-        if (c->feat_on() && (rc = features(il, tail_now))) return rc;
-        if ((rc = dense_rows(il))) return rc;
-        return depth_rows(il);
+        if (c->feat && (rc = features(il, tail_now))) return rc;
+        return patch_head_rows(il);
     }
     // Dense tail of a layer
     int dense_tail(int il, const LayerW &w, const LayerW *nx, bool tail_now, const Rows &r) {
@@ -412,8 +354,7 @@ struct SliceForward {
         if ((rc = resid_gemm_ln(r, r.pc_fc2, c->glu ? sl.Hg : sl.Hbuf, Wl[W_FC2], w.fc2_b, F, Fl[W_FC2], nx ? nx->ln1_w : nullptr, nx ? nx->ln1_b : nullptr, sl.U, &fix_u))) return rc;
         if (!c->trace_ids.empty() && (rc = trace(il + 1))) return rc;
         if ((rc = features(il, tail_now, c->pool && il + 1 == c->L ? sl.Z : nullptr))) return rc;
-        if ((rc = dense_rows(il))) return rc;
-        return depth_rows(il);
+        return patch_head_rows(il);
     }
     int run(const void *d_imgs, void *d_probs, void *d_logits) {
         const int Mp_real = n * c->gh * c->gw;                          // patch rows
@@ -440,7 +381,7 @@ struct SliceForward {
         }
         const Rows all_rows{sl.X, M, M_real, PC_GEMM_PROJ, PC_GEMM_FC1, PC_GEMM_FC2, fuse};
         const Rows cls_rows{sl.Xc, round_up(n, tm), n, PC_GEMM_TAIL, PC_GEMM_TAIL, PC_GEMM_TAIL, false};
-        const bool tail = c->cls_tail && c->trace_ids.empty() && !c->feat_last_all_rows() && !c->dense_last_all_rows() && !c->depth_last_all_rows();      // the last layer carries only the class-token rows past its qkv projection (vitx_ctx::cls_tail)
+        const bool tail = c->cls_tail && c->trace_ids.empty() && !c->outputs_need_last_rows();      // the last layer carries only the class-token rows past its qkv projection (vitx_ctx::cls_tail)
         for (int il = 0; il < c->L; ++il) {
             const LayerW &w = ws.layers[il], *nx = il + 1 < c->L ? &ws.layers[il + 1] : nullptr;
             const bool tail_now = tail && il + 1 == c->L;
@@ -472,12 +413,8 @@ struct SliceForward {
             ProfScope ps(c, st, PC_SOFTMAX, 0, (double)nR * c->C * 8);
             HIP_TRY(launch_softmax(dt, lg, (float *)d_probs, nR, c->C, ldl, st));
         }
-        // zero-shot logits and probabilities of a context with a bank: from the pooled embedding e (attention-pooling head), else from the logits row
-        if (c->zs_on() && (rc = c->map ? zeroshot(sl.Xc, D) : zeroshot(lg, ldl))) return rc;
-        if (c->nn_on() && (rc = nearest(lg, ldl))) return rc;
-        if (c->dense_on() && (rc = dense_head())) return rc;
-        if (c->depth_on() && (rc = depth_head())) return rc;
-        if (fuse && c->ln_fb_host) HIP_TRY(hipMemcpyAsync(c->ln_fb_host + (&sl - &c->slices[0]), sl.ln_todo + sl.ln_blocks, sizeof(unsigned), hipMemcpyDeviceToHost, st));       // fall-back budget
+        if ((rc = heads(lg, ldl))) return rc;
+        if (fuse && c->ln_fb_host) HIP_TRY(hipMemcpyAsync(c->ln_fb_host + si, sl.ln_todo + sl.ln_blocks, sizeof(unsigned), hipMemcpyDeviceToHost, st));       // fall-back budget
         return VITX_OK;
     }
 };
@@ -654,7 +591,7 @@ static int forward_pass(vitx_ctx *c, const void *d_imgs, int n, void *d_probs, v
     const bool serial = c->prof_on;
     const int ns = (c->nslices > 1 && n >= 8 * c->nslices) ? c->nslices : 1;
     if (ns == 1) {
-        if (c->graphs_on && !c->prof_on && c->trace_ids.empty() && !c->attn_on() && !c->feat_on() && !c->zs_on() && !c->nn_on() && !c->dense_on() && !c->depth_on()) {
+        if (c->graphs_on && !c->prof_on && c->trace_ids.empty() && !c->any_output()) {
             bool done = false;
             const int rc = forward_graph(c, st, d_imgs, n, d_probs, d_logits, &done);
             if (rc != VITX_OK || done) return rc;
@@ -705,24 +642,18 @@ int vitx_forward_device(vitx_ctx *c, const void *d_imgs, int n, void *d_probs, v
     // one pass of the kernels takes call_limit images (32-bit buffer window, vitx_ctx_create_ex); a larger batch is several passes, back to back on the
     // caller's stream through the same scratch -- images are independent, so the results are the ones a single pass would give
     if (n > c->call_limit && !c->trace_ids.empty()) { set_error("vitx_forward_device: the residual-stream trace takes one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
-    if (n > c->call_limit && c->attn_on()) { set_error("vitx_forward_device: attention maps take one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
-    if (n > c->call_limit && c->feat_on()) { set_error("vitx_forward_device: features take one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
-    if (n > c->call_limit && c->zs_on()) { set_error("vitx_forward_device: zero-shot classification takes one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
-    if (n > c->call_limit && c->nn_on()) { set_error("vitx_forward_device: nearest neighbours take one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
-    if (n > c->call_limit && c->dense_on()) { set_error("vitx_forward_device: the dense head takes one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
-    if (n > c->call_limit && c->depth_on()) { set_error("vitx_forward_device: the depth head takes one pass (at most %d images)", c->call_limit); return VITX_ERR_ARG; }
+    if (n > c->call_limit) {
+        const char *who = nullptr;
+        c->each_output([&](const Output &o) { if (!who) who = o.one_pass; });
+        if (who) { set_error("vitx_forward_device: %s one pass (at most %d images)", who, c->call_limit); return VITX_ERR_ARG; }
+    }
     for (int i0 = 0; i0 < n; i0 += c->call_limit) {
         const int ni = std::min(c->call_limit, n - i0);
         const int rc = forward_pass(c, (const float *)d_imgs + (size_t)i0 * c->img_floats(), ni, (float *)d_probs + (size_t)i0 * c->R * c->C,
                                     d_logits ? (float *)d_logits + (size_t)i0 * c->R * c->C : nullptr, st);
         if (rc) return rc;
     }
-    if (c->attn_on()) c->attn_n = n;
-    if (c->feat_on()) c->feat_n = n;
-    if (c->zs_on()) c->zs_n = n;
-    if (c->nn_on()) c->nn_n = n;
-    if (c->dense_on()) c->dn_n = n;
-    if (c->depth_on()) c->dp_n = n;
+    c->each_output([n](Output &o) { o.n = n; });
     return VITX_OK;
 }
 int vitx_forward(vitx_ctx *c, const float *imgs, int n, float *probs, float *logits) {

@@ -1,0 +1,86 @@
+// heads.cpp -- the launch sequences of the zero-shot bank, the gallery, the dense head and the depth head (heads.h): what a forward runs after
+// its classifier (SliceForward, forward.cpp) and what vitx_op_zeroshot / _nn / _dense / _depth run on the caller's buffers (ops.cpp) -- one text.
+#include "context.h"
+
+namespace vitx {
+
+namespace {
+
+constexpr double eb = 2.0;                               // operand bytes
+
+// the first HIP error of a sequence ends it
+#define HEAD_TRY(expr) do { const hipError_t e__ = (expr); if (e__ != hipSuccess) return e__; } while (0)
+
+// One dispatcher GEMM with an f32 output (+ its profile record)
+hipError_t gemm_f32(const HeadLaunch &l, int pc, const GemmArgs &a) {
+    double flops, bytes;
+    gemm_work(EPI_BIAS_F32, a.M_real, a.N, a.K, false, false, &flops, &bytes);
+    ProfScope ps(l.prof, l.st, pc, flops, bytes);
+    return launch_gemm(l.tune, l.dtype, EPI_BIAS_F32, a, l.st);
+}
+
+}  // namespace
+
+hipError_t head_zeroshot(const HeadLaunch &l, const float *z, long ldz, void *a, const void *bank, const float *zero, float *acc, float *probs, float *logits,
+                         long out_stride, int n, int K, int E, int kind, float scale, float bias) {
+    const int Kpad = round_up(K, gemm_tile_n()), Mz = round_up(n, gemm_tile_m());
+    {
+        ProfScope ps(l.prof, l.st, PC_ZEROSHOT, 0, (double)n * E * 4 + (double)Mz * E * eb);
+        HEAD_TRY(launch_zs_embed(l.dtype, z, ldz, a, n, Mz, E, l.st));
+    }
+    HEAD_TRY(gemm_f32(l, PC_ZEROSHOT, dense_gemm(a, bank, zero, acc, Mz, n, K, Kpad, E, Kpad)));
+    ProfScope ps(l.prof, l.st, PC_ZEROSHOT, 0, (double)n * K * 4 * (kind == VITX_ZS_SOFTMAX ? 7 : 3));
+    return launch_zs_score(acc, Kpad, probs, logits, out_stride, n, K, kind, scale, bias, l.st);
+}
+
+hipError_t head_nearest(const HeadLaunch &l, const void *z, long ldz, bool z_is_operand, void *a, const void *gallery, const float *zero, float *acc, void *state,
+                        long G, int E, int k, int chunk, const int *labels, int nlabels, float T, void *pairs, float *vote, int n) {
+    const int Mz = round_up(n, gemm_tile_m());
+    {
+        ProfScope ps(l.prof, l.st, PC_NN, 0, (double)n * E * (z_is_operand ? eb : 4) + (double)Mz * E * eb);
+        if (z_is_operand) HEAD_TRY(launch_zs_embed_operand(l.dtype, z, ldz, a, n, Mz, E, l.st));
+        else HEAD_TRY(launch_zs_embed(l.dtype, (const float *)z, ldz, a, n, Mz, E, l.st));
+    }
+    for (long g0 = 0; g0 < G; g0 += chunk) {
+        const int cols = (int)std::min<long>(chunk, G - g0);
+        HEAD_TRY(gemm_f32(l, PC_NN, dense_gemm(a, (const char *)gallery + (size_t)g0 * E * 2, zero, acc, Mz, n, cols, round_up(cols, gemm_tile_n()), E, chunk)));
+        ProfScope ps(l.prof, l.st, PC_NN, 0, (double)n * cols * 4);
+        HEAD_TRY(launch_nn_select(acc, chunk, n, cols, g0, state, k, g0 == 0, l.st));
+    }
+    ProfScope ps(l.prof, l.st, PC_NN, 0, (double)n * kNnSegs * k * 8 + (double)n * (k * 8 + nlabels * 4));
+    return launch_nn_finish(state, n, k, labels, nlabels, T, pairs, vote, l.st);
+}
+
+hipError_t head_linear(const HeadLaunch &l, int pc, void *a, const void *W, const float *bias, float *acc, int rows, int K, int Dc, float *keep) {
+    const int Kpad = round_up(K, gemm_tile_n()), Mr = round_up(rows, gemm_tile_m());
+    if (Mr > rows) HEAD_TRY(hipMemsetAsync((char *)a + (size_t)rows * Dc * 2, 0, (size_t)(Mr - rows) * Dc * 2, l.st));
+    HEAD_TRY(gemm_f32(l, pc, dense_gemm(a, W, bias, acc, Mr, rows, K, Kpad, Dc, Kpad)));
+    if (keep) HEAD_TRY(hipMemcpy2DAsync(keep, (size_t)K * 4, acc, (size_t)Kpad * 4, (size_t)K * 4, rows, hipMemcpyDeviceToDevice, l.st));
+    return hipSuccess;
+}
+
+hipError_t head_dense(const HeadLaunch &l, void *a, const void *W, const float *bias, float *acc, int n, int gh, int gw, int K, int Dc, int oh, int ow,
+                      uint8_t *labels, float *score, float *keep) {
+    const int rows = n * gh * gw, Kpad = round_up(K, gemm_tile_n());
+    const size_t px = (size_t)oh * ow;
+    HEAD_TRY(head_linear(l, PC_DENSE, a, W, bias, acc, rows, K, Dc, keep));
+    ProfScope ps(l.prof, l.st, PC_DENSE, 9.0 * n * (double)px * K, (double)rows * Kpad * 4 + (double)n * px * (score ? 5 : 1));
+    return launch_dense_labels(acc, Kpad, n, gh, gw, K, oh, ow, labels, score, l.st);
+}
+
+hipError_t head_depth(const HeadLaunch &l, void *a, const void *Wp, const float *zero, float *acc, void *ac, const void *Wc, const float *bias, float *o,
+                      const float *bins, int n, int gh, int gw, int K, int Dc, int u, int oh, int ow, float lo, float hi, float *fine, float *depth,
+                      float *keep, float *keep_off) {
+    const int rows = n * gh * gw, Kpad = round_up(K, gemm_tile_n());
+    const size_t px = (size_t)oh * ow, fpx = (size_t)u * gh * u * gw;
+    HEAD_TRY(head_linear(l, PC_DEPTH, a, Wp, zero, acc, rows, K, Dc, keep));
+    if (Wc) HEAD_TRY(head_linear(l, PC_DEPTH, ac, Wc, bias, o, n, K, Dc, keep_off));
+    {
+        ProfScope ps(l.prof, l.st, PC_DEPTH, 11.0 * n * (double)fpx * K, (double)rows * Kpad * 4 + (double)n * fpx * 4);
+        HEAD_TRY(launch_depth_fine(acc, Kpad, Wc ? o : bias, Wc ? Kpad : 0, bins, n, gh, gw, K, u, fine, l.st));
+    }
+    ProfScope ps(l.prof, l.st, PC_DEPTH, 7.0 * n * (double)px, (double)n * (fpx + px) * 4);
+    return launch_depth_resize(fine, n, u * gh, u * gw, oh, ow, lo, hi, depth, l.st);
+}
+
+}  // namespace vitx

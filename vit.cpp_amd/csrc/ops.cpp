@@ -328,9 +328,9 @@ int vitx_op_rollout_row(const void *d_cls, long cls_stride, const void *d_r, voi
     return op_rc("vitx_op_rollout_row", launch_rollout_row((const float *)d_cls, cls_stride, (const float *)d_r, (float *)d_out, out_stride, n_img, N, H, (hipStream_t)stream));
 }
 
-// Zero-shot classification on the caller's buffers: the three launches the forward of a context with a bank makes (SliceForward::zeroshot), the
-// bank GEMM through the dispatcher.  Every argument check comes before the first device call.  The GEMM's bias is the row of zeros the call
-// writes behind the accumulator rows (d_acc_scratch holds round_up(n, 256) + 1 rows of K_pad floats).
+// Zero-shot classification on the caller's buffers: the sequence the forward of a context with a bank runs (head_zeroshot, heads.cpp).  Every
+// argument check comes before the first device call.  The GEMM's bias is the row of zeros the call writes behind the accumulator rows
+// (d_acc_scratch holds round_up(n, 256) + 1 rows of K_pad floats).
 int vitx_zeroshot_max_classes(int E) {
     if (E <= 0 || E % 64) return 0;
     return (int)std::min<size_t>((size_t)0xf0000000u / ((size_t)E * 2) / gemm_tile_n() * gemm_tile_n(), (size_t)0x7fffff80);
@@ -351,9 +351,7 @@ int vitx_op_zeroshot(int dtype, const void *d_z, long z_stride, const void *d_ba
     hipStream_t st = (hipStream_t)stream;
     float *acc = (float *)d_acc_scratch, *zero = acc + (size_t)M * Kpad;
     hipError_t e = hipMemsetAsync(zero, 0, (size_t)Kpad * 4, st);
-    if (e == hipSuccess) e = launch_zs_embed(dtype, (const float *)d_z, z_stride, d_a_scratch, n, M, E, st);
-    if (e == hipSuccess) e = launch_gemm(*t, dtype, EPI_BIAS_F32, dense_gemm(d_a_scratch, d_bank, zero, acc, M, n, K, Kpad, E, Kpad), st);
-    if (e == hipSuccess) e = launch_zs_score(acc, Kpad, (float *)d_probs, (float *)d_logits, K, n, K, kind, scale, bias, st);
+    if (e == hipSuccess) e = head_zeroshot(HeadLaunch{*t, dtype, st, nullptr}, (const float *)d_z, z_stride, d_a_scratch, d_bank, zero, acc, (float *)d_probs, (float *)d_logits, K, n, K, E, kind, scale, bias);
     return op_rc("vitx_op_zeroshot", e, VITX_ERR_UNSUPPORTED);
 }
 
@@ -372,8 +370,8 @@ int vitx_op_nn_finish(const void *d_state, int n, int k, const void *d_labels, i
     if (k > kNnMaxK) { set_error("vitx_op_nn_finish: k = %d above %d", k, kNnMaxK); return VITX_ERR_UNSUPPORTED; }
     return op_rc("vitx_op_nn_finish", launch_nn_finish(d_state, n, k, (const int *)d_labels, n_labels, temperature, d_pairs, (float *)d_vote, (hipStream_t)stream), VITX_ERR_ARG);
 }
-// The launches the forward of a context with a gallery makes (SliceForward::nearest) without the vote: the operand rows, per chunk the GEMM through
-// the dispatcher and the selection, then the final merge.  The GEMMs' bias is the row of zeros the call writes behind the score rows.
+// The sequence the forward of a context with a gallery runs (head_nearest, heads.cpp), without the vote.  The GEMMs' bias is the row of zeros the
+// call writes behind the score rows.
 int vitx_op_nn(int dtype, const void *d_z, long z_stride, int z_is_operand, int n, const void *d_gallery, long G, int E, int k, int chunk,
                void *d_a_scratch, void *d_acc_scratch, void *d_state, void *d_pairs, void *stream) {
     if (!d_z || !d_gallery || !d_a_scratch || !d_acc_scratch || !d_state || !d_pairs || n <= 0 || G <= 0 || E <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_nn: invalid argument"); return VITX_ERR_ARG; }
@@ -392,13 +390,7 @@ int vitx_op_nn(int dtype, const void *d_z, long z_stride, int z_is_operand, int 
     hipStream_t st = (hipStream_t)stream;
     float *acc = (float *)d_acc_scratch, *zero = acc + (size_t)M * chunk;
     hipError_t e = hipMemsetAsync(zero, 0, (size_t)chunk * 4, st);
-    if (e == hipSuccess) e = z_is_operand ? launch_zs_embed_operand(dtype, d_z, z_stride, d_a_scratch, n, M, E, st) : launch_zs_embed(dtype, (const float *)d_z, z_stride, d_a_scratch, n, M, E, st);
-    for (long g0 = 0; g0 < G && e == hipSuccess; g0 += chunk) {
-        const int cols = (int)std::min<long>(chunk, G - g0);
-        e = launch_gemm(*t, dtype, EPI_BIAS_F32, dense_gemm(d_a_scratch, (const char *)d_gallery + (size_t)g0 * E * 2, zero, acc, M, n, cols, round_up(cols, gemm_tile_n()), E, chunk), st);
-        if (e == hipSuccess) e = launch_nn_select(acc, chunk, n, cols, g0, d_state, k, g0 == 0, st);
-    }
-    if (e == hipSuccess) e = launch_nn_finish(d_state, n, k, nullptr, 0, 0.0f, d_pairs, nullptr, st);
+    if (e == hipSuccess) e = head_nearest(HeadLaunch{*t, dtype, st, nullptr}, d_z, z_stride, z_is_operand != 0, d_a_scratch, d_gallery, zero, acc, d_state, G, E, k, chunk, nullptr, 0, 0.0f, d_pairs, nullptr, n);
     return op_rc("vitx_op_nn", e, VITX_ERR_UNSUPPORTED);
 }
 
@@ -441,8 +433,7 @@ int vitx_dense_labels_host(const float *logits, long ld, int n, int gh, int gw, 
     }
     return VITX_OK;
 }
-// The launches the forward of a context with a dense head makes after its operand rows are written (SliceForward::dense_head): the pad rows
-// zeroed, the GEMM through the dispatcher, the label kernel.
+// The sequence the forward of a context with a dense head runs after its operand rows are written (head_dense, heads.cpp).
 int vitx_op_dense(int dtype, void *d_a, const void *d_w, const void *d_bias, void *d_logits, int n, int gh, int gw, int K, int Dc, int out_h, int out_w,
                   void *d_labels, void *d_score, void *stream) {
     if (!d_a || !d_w || !d_bias || Dc < 1 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_dense: invalid argument"); return VITX_ERR_ARG; }
@@ -455,14 +446,11 @@ int vitx_op_dense(int dtype, void *d_a, const void *d_w, const void *d_bias, voi
     if ((size_t)M * Dc * 2 > 0xf0000000u || (size_t)M * Kpad * 4 > 0xf0000000u || (size_t)Kpad * Dc * 2 > 0xf0000000u) { set_error("vitx_op_dense: %d rows of width %d leave the GEMM's 32-bit byte window", M, Dc); return VITX_ERR_UNSUPPORTED; }
     const Tuning *t = tuning_for_device(-1);
     if (!t) { set_error("vitx_op_dense: kernel bring-up failed"); return VITX_ERR_HIP; }
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = M > rows ? hipMemsetAsync((char *)d_a + (size_t)rows * Dc * 2, 0, (size_t)(M - rows) * Dc * 2, st) : hipSuccess;
-    if (e == hipSuccess) e = launch_gemm(*t, dtype, EPI_BIAS_F32, dense_gemm(d_a, d_w, (const float *)d_bias, d_logits, M, rows, K, Kpad, Dc, Kpad), st);
-    if (e == hipSuccess) e = launch_dense_labels((const float *)d_logits, Kpad, n, gh, gw, K, out_h, out_w, (uint8_t *)d_labels, (float *)d_score, st);
-    return op_rc("vitx_op_dense", e, VITX_ERR_UNSUPPORTED);
+    return op_rc("vitx_op_dense", head_dense(HeadLaunch{*t, dtype, (hipStream_t)stream, nullptr}, d_a, d_w, (const float *)d_bias, (float *)d_logits, n, gh, gw, K, Dc, out_h, out_w,
+                                             (uint8_t *)d_labels, (float *)d_score, nullptr), VITX_ERR_UNSUPPORTED);
 }
 
-// The depth head on the caller's buffers (include/vitx.h "depth estimation"); depth_fine_args / depth_resize_args: depth_host.cpp.
+// The depth head on the caller's buffers (include/vitx.h "depth estimation"); depth_fine_args / depth_resize_args: heads.h, depth_host.cpp.
 int vitx_op_depth_fine(const void *d_logits, long ld, const void *d_offsets, const void *d_bins, int n, int gh, int gw, int K, int upsample, void *d_fine, void *stream) {
     if (const int rc = depth_fine_args("vitx_op_depth_fine", d_logits, ld, d_bins, n, gh, gw, K, upsample, d_fine)) return rc;
     if ((uintptr_t)d_logits % 16 || (uintptr_t)d_offsets % 16 || (uintptr_t)d_bins % 4 || (uintptr_t)d_fine % 4) { set_error("vitx_op_depth_fine: d_logits and d_offsets must be 16-byte, d_bins and d_fine 4-byte aligned"); return VITX_ERR_ARG; }
@@ -473,8 +461,8 @@ int vitx_op_depth_resize(const void *d_fine, int n, int fh, int fw, int out_h, i
     if ((uintptr_t)d_fine % 4 || (uintptr_t)d_out % 4) { set_error("vitx_op_depth_resize: d_fine and d_out must be 4-byte aligned"); return VITX_ERR_ARG; }
     return op_rc("vitx_op_depth_resize", launch_depth_resize((const float *)d_fine, n, fh, fw, out_h, out_w, min_depth, max_depth, (float *)d_out, (hipStream_t)stream), VITX_ERR_UNSUPPORTED);
 }
-// The launches the forward of a context with a depth head makes after its operand rows are written (SliceForward::depth_head): the pad rows zeroed,
-// the patch GEMM with a zero bias (the row of zeros the call writes behind the logit rows), the class GEMM with the head's bias, the two kernels.
+// The sequence the forward of a context with a depth head runs after its operand rows are written (head_depth, heads.cpp).  The patch GEMM's zero
+// bias is the row of zeros the call writes behind the logit rows.
 int vitx_op_depth(int dtype, void *d_a, const void *d_wp, void *d_acls, const void *d_wc, const void *d_bias, const void *d_bins, void *d_logits, void *d_offsets,
                   int n, int gh, int gw, int K, int Dc, int upsample, int out_h, int out_w, float min_depth, float max_depth, void *d_fine, void *d_depth, void *stream) {
     if (!d_a || !d_wp || !d_bias || Dc < 1 || (dtype != VITX_F16 && dtype != VITX_BF16) || (!d_wc) != (!d_acls) || (d_wc && !d_offsets)) { set_error("vitx_op_depth: invalid argument"); return VITX_ERR_ARG; }
@@ -486,21 +474,15 @@ int vitx_op_depth(int dtype, void *d_a, const void *d_wp, void *d_acls, const vo
         if ((uintptr_t)p % 16) { set_error("vitx_op_depth: every pointer but d_depth must be 16-byte aligned"); return VITX_ERR_ARG; }
     if ((uintptr_t)d_depth % 4) { set_error("vitx_op_depth: d_depth must be 4-byte aligned"); return VITX_ERR_ARG; }
     if (Dc % 64) { set_error("vitx_op_depth: Dc = %d is not a multiple of 64 (the GEMMs' K step)", Dc); return VITX_ERR_UNSUPPORTED; }
-    const int rows = n * gh * gw, M = round_up(rows, gemm_tile_m()), Mc = round_up(n, gemm_tile_m());
+    const int rows = n * gh * gw, M = round_up(rows, gemm_tile_m());
     if ((size_t)M * Dc * 2 > 0xf0000000u || (size_t)(M + 1) * Kpad * 4 > 0xf0000000u || (size_t)Kpad * Dc * 2 > 0xf0000000u) { set_error("vitx_op_depth: %d rows of width %d leave the GEMM's 32-bit byte window", M, Dc); return VITX_ERR_UNSUPPORTED; }
     const Tuning *t = tuning_for_device(-1);
     if (!t) { set_error("vitx_op_depth: kernel bring-up failed"); return VITX_ERR_HIP; }
     hipStream_t st = (hipStream_t)stream;
     float *acc = (float *)d_logits, *zero = acc + (size_t)M * Kpad;
     hipError_t e = hipMemsetAsync(zero, 0, (size_t)Kpad * 4, st);
-    if (e == hipSuccess && M > rows) e = hipMemsetAsync((char *)d_a + (size_t)rows * Dc * 2, 0, (size_t)(M - rows) * Dc * 2, st);
-    if (e == hipSuccess) e = launch_gemm(*t, dtype, EPI_BIAS_F32, dense_gemm(d_a, d_wp, zero, acc, M, rows, K, Kpad, Dc, Kpad), st);
-    if (d_wc) {
-        if (e == hipSuccess && Mc > n) e = hipMemsetAsync((char *)d_acls + (size_t)n * Dc * 2, 0, (size_t)(Mc - n) * Dc * 2, st);
-        if (e == hipSuccess) e = launch_gemm(*t, dtype, EPI_BIAS_F32, dense_gemm(d_acls, d_wc, (const float *)d_bias, d_offsets, Mc, n, K, Kpad, Dc, Kpad), st);
-    }
-    if (e == hipSuccess) e = launch_depth_fine(acc, Kpad, d_wc ? (const float *)d_offsets : (const float *)d_bias, d_wc ? Kpad : 0, (const float *)d_bins, n, gh, gw, K, upsample, (float *)d_fine, st);
-    if (e == hipSuccess) e = launch_depth_resize((const float *)d_fine, n, fh, fw, out_h, out_w, min_depth, max_depth, (float *)d_depth, st);
+    if (e == hipSuccess) e = head_depth(HeadLaunch{*t, dtype, st, nullptr}, d_a, d_wp, zero, acc, d_acls, d_wc, (const float *)d_bias, (float *)d_offsets, (const float *)d_bins,
+                                        n, gh, gw, K, Dc, upsample, out_h, out_w, min_depth, max_depth, (float *)d_fine, (float *)d_depth, nullptr, nullptr);
     return op_rc("vitx_op_depth", e, VITX_ERR_UNSUPPORTED);
 }
 // The raw operand rows on their own: y[row][0 .. D) (dtype, row stride ldy elements) = RNE(x[row][0 .. D)) (f32, row stride ldx floats)

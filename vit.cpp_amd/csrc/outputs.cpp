@@ -1,5 +1,6 @@
 // outputs.cpp -- what a context gives besides probabilities: the per-kernel profile, the residual-stream trace, attention maps, features,
-// and the diagnostics counters.  All opt-in; the forward (forward.cpp) launches nothing for an output that is off.
+// the zero-shot bank, the gallery, the dense and the depth head (their state: heads.h), and the diagnostics counters.  All opt-in; the forward
+// (forward.cpp) launches nothing for an output that is off.
 #include <cmath>
 #include <utility>
 
@@ -17,6 +18,63 @@ static int read_output(vitx_ctx *c, const char *api, const char *what, int n, in
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, buf, need * 4, hipMemcpyDeviceToHost));
     return VITX_OK;
+}
+
+// How every vitx_*_enable / vitx_*_set goes: its argument checks (before the first device call: a refused call leaves the output that was set in
+// place); quiesce(); the old object dropped, so that its buffers are free before the new ones are asked for; the new object built in a local, and
+// moved into the context only when every allocation and upload succeeded -- any earlier return frees the local and leaves the output off.
+// quiesce: the context's device is current and no forward in flight reads or writes the buffers about to be freed
+static int quiesce(vitx_ctx *c) {
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());
+    return VITX_OK;
+}
+static int hip_failed(const char *api, hipError_t e) {
+    set_error("%s: %s", api, hipGetErrorString(e));
+    return VITX_ERR_HIP;
+}
+// W [K][Dc] f32 -> dst [Kpad][Dc], rounded (RNE) to the context's operand type, zero rows beyond K
+static hipError_t upload_operand(const vitx_ctx *c, const DevMem &dst, const float *W, int K, int Kpad, int Dc) {
+    const std::vector<uint16_t> hw = operand_matrix_host(c->dtype, W, nullptr, K, Dc, Kpad, Dc, 0, 0);
+    return hipMemcpy(dst.p, hw.data(), hw.size() * 2, hipMemcpyHostToDevice);
+}
+
+// What vitx_dense_set and vitx_depth_set (`api`) share.  The argument checks come in two pieces because each head's own checks sit between them:
+// patch_head_layers: the layer mask (0: the last layer), at most 4 layers, Dc = layers x D, the output shape (0 x 0: the context's image shape)
+static int patch_head_layers(const vitx_ctx *c, const char *api, int Dc, uint64_t *mask, int *oh, int *ow) {
+    if (*mask == 0) *mask = 1ull << (c->L - 1);
+    if (c->L < 64 && (*mask >> c->L)) { set_error("%s: layer mask selects a layer at or beyond L = %d", api, c->L); return VITX_ERR_ARG; }
+    const int m = __builtin_popcountll(*mask);
+    if (m > 4) { set_error("%s: %d layers selected, at most 4", api, m); return VITX_ERR_ARG; }
+    if (Dc != m * c->D) { set_error("%s: the head's width %d is not %d layers x D = %d", api, Dc, m, m * c->D); return VITX_ERR_ARG; }
+    if (*oh < 0 || *ow < 0 || ((*oh == 0) != (*ow == 0))) { set_error("%s: output shape %d x %d (0 x 0: the context's image shape)", api, *oh, *ow); return VITX_ERR_ARG; }
+    if (*oh == 0) { *oh = c->Sh; *ow = c->Sw; }
+    return VITX_OK;
+}
+// patch_head_window: the operand and logit rows of a pass lie inside the 32-bit byte window the GEMM addresses
+static int patch_head_window(const vitx_ctx *c, const char *api, int K, int Dc) {
+    const size_t rows = (size_t)c->pass_cap() * c->gh * c->gw;
+    if (rows * Dc * 2 > 0xf0000000u || rows * round_up(K, c->tn) * 4 > 0xf0000000u || c->pass_cap() > 65535) {
+        set_error("%s: the operand or logit rows of a pass of %d images leave the GEMM's 32-bit byte window", api, c->pass_cap());
+        return VITX_ERR_UNSUPPORTED;
+    }
+    return VITX_OK;
+}
+static void patch_head_init(const vitx_ctx *c, PatchHead *h, int K, int Dc, uint64_t mask, int oh, int ow, int flags) {
+    h->K = K; h->Kpad = round_up(K, c->tn); h->Dc = Dc; h->mask = mask; h->oh = oh; h->ow = ow; h->flags = flags; h->cap = c->pass_cap();
+    h->last_all_rows = (mask >> (c->L - 1)) & 1;       // a selected last layer needs every row of it (as VITX_FEAT_TOKENS of the last layer does)
+}
+// patch_head_scratch: the per-slice operand rows -- zero-filled once: a forward writes the real rows of its batch and zeroes the pad rows behind
+// them -- and patch logits, counted into h->scratch.  false: the device has no room; *e: the zero fill failed
+static bool patch_head_scratch(const vitx_ctx *c, PatchHead *h, hipError_t *e) {
+    h->a.resize(c->nslices); h->acc.resize(c->nslices);
+    for (int i = 0; i < c->nslices && *e == hipSuccess; ++i) {
+        const size_t rows = (size_t)round_up(std::min(c->slices[i].cap, h->cap) * c->gh * c->gw, c->tm);
+        if (!h->a[i].alloc(rows * h->Dc * 2) || !h->acc[i].alloc(rows * h->Kpad * 4)) return false;
+        *e = hipMemset(h->a[i].p, 0, rows * h->Dc * 2);
+        h->scratch += rows * h->Dc * 2 + rows * h->Kpad * 4;
+    }
+    return true;
 }
 
 extern "C" {
@@ -145,25 +203,26 @@ int vitx_attn_enable(vitx_ctx *c, uint64_t layer_mask, int flags) {
     if (on && c->map) { set_error("vitx_attn_enable: the maps are defined by the class-token row, and a model with the attention-pooling head has no class token"); return VITX_ERR_UNSUPPORTED; }
     if (on && !attention_map_supports(c->N, c->D, c->H)) { set_error("vitx_attn_enable: head_dim %d is not covered by the map kernels", c->D / c->H); return VITX_ERR_UNSUPPORTED; }
     if (rollout && !attention_mean_supports(c->N, c->D, c->H)) { set_error("vitx_attn_enable: rollout keeps two N x N matrices per image and takes at most %d tokens (this model: %d)", kAttnMeanMaxTokens, c->N); return VITX_ERR_UNSUPPORTED; }
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipDeviceSynchronize());          // no forward in flight writes the buffers about to be freed
-    c->attn_free();
-    c->attn_mask = 0; c->attn_flags = 0; c->attn_fpi = 0; c->attn_cap = 0; c->attn_n = 0;
+    if (const int rc = quiesce(c)) return rc;
+    c->attn.reset();
     if (!on) return VITX_OK;
-    const int cap = c->pass_cap(), N = c->N, H = c->H;
-    const int fpi = layer_slot(layer_mask, c->L) * H * N + (rollout ? N : 0);
-    auto alloc = [&](float **p, size_t floats) { if (hipMalloc((void **)p, floats * 4) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; } return true; };
-    bool ok = alloc(&c->attn_out, (size_t)cap * fpi);
-    if (ok && rollout) ok = alloc(&c->attn_roll[0], (size_t)cap * N * N) && alloc(&c->attn_roll[1], (size_t)cap * N * N);
-    if (ok && rollout && !((layer_mask >> (c->L - 1)) & 1)) ok = alloc(&c->attn_cls_last, (size_t)cap * H * N);
-    if (!ok) { c->attn_free(); set_error("vitx_attn_enable: cannot allocate the map buffers for %d images", cap); return VITX_ERR_NOMEM; }
-    c->attn_mask = layer_mask; c->attn_flags = flags; c->attn_fpi = fpi; c->attn_cap = cap;
+    auto am = std::make_unique<AttnMaps>();
+    const size_t cap = c->pass_cap(), N = c->N, H = c->H;
+    am->mask = layer_mask; am->flags = flags; am->cap = (int)cap;
+    am->fpi = layer_slot(layer_mask, c->L) * c->H * c->N + (rollout ? c->N : 0);
+    bool ok = am->out.alloc(cap * am->fpi * 4);
+    if (ok && rollout) ok = am->roll[0].alloc(cap * N * N * 4) && am->roll[1].alloc(cap * N * N * 4);
+    if (ok && rollout && !((layer_mask >> (c->L - 1)) & 1)) ok = am->cls_last.alloc(cap * H * N * 4);
+    if (!ok) { set_error("vitx_attn_enable: cannot allocate the map buffers for %d images", am->cap); return VITX_ERR_NOMEM; }
+    c->attn = std::move(am);
     return VITX_OK;
 }
-int vitx_attn_floats(const vitx_ctx *c) { return c ? c->attn_fpi : 0; }
-int vitx_attn_images(const vitx_ctx *c) { return c ? c->attn_n : 0; }
+int vitx_attn_floats(const vitx_ctx *c) { return c && c->attn ? c->attn->fpi : 0; }
+int vitx_attn_images(const vitx_ctx *c) { return c && c->attn ? c->attn->n : 0; }
 int vitx_attn_read(vitx_ctx *c, float *out, size_t n_floats) {
-    return c ? read_output(c, "vitx_attn", "attention maps", c->attn_on() ? c->attn_n : 0, c->attn_fpi, c->attn_out, out, n_floats) : VITX_ERR_ARG;
+    if (!c) return VITX_ERR_ARG;
+    const AttnMaps *a = c->attn.get();
+    return read_output(c, "vitx_attn", "attention maps", a ? a->n : 0, a ? a->fpi : 0, a ? a->out.as<float>() : nullptr, out, n_floats);
 }
 
 int vitx_feat_enable(vitx_ctx *c, int flags, uint64_t layer_mask) {
@@ -173,32 +232,32 @@ int vitx_feat_enable(vitx_ctx *c, int flags, uint64_t layer_mask) {
     if (flags && !(flags & kinds)) { set_error("vitx_feat_enable: VITX_FEAT_L2 modifies VITX_FEAT_CLS / VITX_FEAT_MEAN and selects nothing on its own"); return VITX_ERR_ARG; }
     if (c->L < 64 && (layer_mask >> c->L)) { set_error("vitx_feat_enable: layer mask 0x%llx names layers beyond the model's %d", (unsigned long long)layer_mask, c->L); return VITX_ERR_ARG; }
     if (flags && c->R != 1) { set_error("vitx_feat_enable: features are not available for ViTSTR contexts"); return VITX_ERR_UNSUPPORTED; }
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipDeviceSynchronize());          // no forward in flight writes the buffer about to be freed
-    c->feat_free();
-    c->feat_flags = 0; c->feat_mask = 0; c->feat_fpi = 0; c->feat_cap = 0; c->feat_n = 0;
+    if (const int rc = quiesce(c)) return rc;
+    c->feat.reset();
     if (!flags) return VITX_OK;
     if (!layer_mask) layer_mask = 1ull << (c->L - 1);
-    if (c->map && (flags & VITX_FEAT_CLS) && layer_mask != 1ull << (c->L - 1)) {
+    if (c->map && (flags & VITX_FEAT_CLS) && layer_mask != 1ull << (c->L - 1)) {      // the one refusal that comes after the free: the features are off now
         set_error("vitx_feat_enable: VITX_FEAT_CLS of a model with the attention-pooling head is the pooled embedding: it exists for the last layer only (mask 0x%llx)", (unsigned long long)layer_mask);
         return VITX_ERR_ARG;
     }
-    c->feat_flags = flags;                    // feat_layer_floats() reads it
-    const int cap = c->pass_cap();
-    const size_t fpi = (size_t)layer_slot(layer_mask, c->L) * c->feat_layer_floats();
-    if (fpi > 0x7fffffff || hipMalloc((void **)&c->feat_out, (size_t)cap * fpi * 4) != hipSuccess) {
-        (void)hipGetLastError(); c->feat_out = nullptr; c->feat_flags = 0;
-        set_error("vitx_feat_enable: cannot allocate the feature buffer for %d images of %zu floats", cap, fpi);
+    auto ft = std::make_unique<Features>(flags, layer_mask, c->D, c->N - c->Tp, c->L);
+    ft->cap = c->pass_cap();
+    const size_t fpi = (size_t)layer_slot(layer_mask, c->L) * ft->layer_floats();
+    if (fpi > 0x7fffffff || !ft->out.alloc((size_t)ft->cap * fpi * 4)) {
+        set_error("vitx_feat_enable: cannot allocate the feature buffer for %d images of %zu floats", ft->cap, fpi);
         return VITX_ERR_NOMEM;
     }
-    c->feat_mask = layer_mask; c->feat_fpi = (int)fpi; c->feat_cap = cap;
+    ft->fpi = (int)fpi;
+    c->feat = std::move(ft);
     return VITX_OK;
 }
-int vitx_feat_floats(const vitx_ctx *c) { return c ? c->feat_fpi : 0; }
-int vitx_feat_images(const vitx_ctx *c) { return c ? c->feat_n : 0; }
-const void *vitx_feat_device(const vitx_ctx *c) { return c ? c->feat_out : nullptr; }
+int vitx_feat_floats(const vitx_ctx *c) { return c && c->feat ? c->feat->fpi : 0; }
+int vitx_feat_images(const vitx_ctx *c) { return c && c->feat ? c->feat->n : 0; }
+const void *vitx_feat_device(const vitx_ctx *c) { return c && c->feat ? c->feat->out.p : nullptr; }
 int vitx_feat_read(vitx_ctx *c, float *out, size_t n_floats) {
-    return c ? read_output(c, "vitx_feat", "features", c->feat_on() ? c->feat_n : 0, c->feat_fpi, c->feat_out, out, n_floats) : VITX_ERR_ARG;
+    if (!c) return VITX_ERR_ARG;
+    const Features *f = c->feat.get();
+    return read_output(c, "vitx_feat", "features", f ? f->n : 0, f ? f->fpi : 0, f ? f->out.as<float>() : nullptr, out, n_floats);
 }
 
 // Zero-shot classification: the bank of a context (include/vitx.h).  Every argument check comes before the first device call.
@@ -217,38 +276,39 @@ int vitx_zeroshot_set(vitx_ctx *c, const float *bank, int K, int E, int kind, fl
         for (size_t i = 0, nb = (size_t)K * E; i < nb; ++i)
             if (!std::isfinite(bank[i])) { set_error("vitx_zeroshot_set: bank entry [%zu][%zu] is not finite", i / E, i % E); return VITX_ERR_ARG; }
     }
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipDeviceSynchronize());          // no forward in flight reads or writes the buffers about to be freed
-    c->zs_free();
+    if (const int rc = quiesce(c)) return rc;
+    c->zs.reset();
     if (off) return VITX_OK;
-    const int Kpad = round_up(K, c->tn), cap = c->pass_cap();
-    const size_t rows = (size_t)round_up(cap, c->tm);
-    const std::vector<uint16_t> hb = operand_matrix_host(c->dtype, bank, nullptr, K, E, Kpad, E, 0, 0);
-    auto alloc = [](void **p, size_t bytes) { if (hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; } return true; };
-    bool ok = alloc(&c->zs_bank, hb.size() * 2) && alloc((void **)&c->zs_zero, (size_t)Kpad * 4) && alloc((void **)&c->zs_out, (size_t)cap * 2 * K * 4);
-    c->zs_a.assign(c->nslices, nullptr); c->zs_acc.assign(c->nslices, nullptr);
-    for (int i = 0; ok && i < c->nslices; ++i) ok = alloc(&c->zs_a[i], rows * E * 2) && alloc((void **)&c->zs_acc[i], rows * Kpad * 4);
-    if (!ok) { c->zs_free(); set_error("vitx_zeroshot_set: cannot allocate the buffers for %d classes and %d images", K, cap); return VITX_ERR_NOMEM; }
-    hipError_t e = hipMemcpy(c->zs_bank, hb.data(), hb.size() * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(c->zs_zero, 0, (size_t)Kpad * 4);
+    auto zs = std::make_unique<ZeroShot>();
+    zs->K = K; zs->Kpad = round_up(K, c->tn); zs->E = E; zs->kind = kind; zs->scale = scale; zs->bias = bias; zs->cap = c->pass_cap();
+    const size_t Kpad = zs->Kpad, rows = (size_t)round_up(zs->cap, c->tm);
+    const std::vector<uint16_t> hb = operand_matrix_host(c->dtype, bank, nullptr, K, E, zs->Kpad, E, 0, 0);
+    bool ok = zs->bank.alloc(hb.size() * 2) && zs->zero.alloc(Kpad * 4) && zs->out.alloc((size_t)zs->cap * 2 * K * 4);
+    zs->a.resize(c->nslices); zs->acc.resize(c->nslices);
+    for (int i = 0; ok && i < c->nslices; ++i) ok = zs->a[i].alloc(rows * E * 2) && zs->acc[i].alloc(rows * Kpad * 4);
+    if (!ok) { set_error("vitx_zeroshot_set: cannot allocate the buffers for %d classes and %d images", K, zs->cap); return VITX_ERR_NOMEM; }
+    hipError_t e = hipMemcpy(zs->bank.p, hb.data(), hb.size() * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(zs->zero.p, 0, Kpad * 4);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { c->zs_free(); set_error("vitx_zeroshot_set: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
-    c->zs_K = K; c->zs_Kpad = Kpad; c->zs_kind = kind; c->zs_scale = scale; c->zs_bias = bias; c->zs_cap = cap;
+    if (e != hipSuccess) return hip_failed("vitx_zeroshot_set", e);
+    c->zs = std::move(zs);
     return VITX_OK;
 }
-int vitx_zeroshot_classes(const vitx_ctx *c) { return c ? c->zs_K : 0; }
-int vitx_zeroshot_images(const vitx_ctx *c) { return c ? c->zs_n : 0; }
-const void *vitx_zeroshot_device(const vitx_ctx *c) { return c ? c->zs_out : nullptr; }
+int vitx_zeroshot_classes(const vitx_ctx *c) { return c && c->zs ? c->zs->K : 0; }
+int vitx_zeroshot_images(const vitx_ctx *c) { return c && c->zs ? c->zs->n : 0; }
+const void *vitx_zeroshot_device(const vitx_ctx *c) { return c && c->zs ? c->zs->out.p : nullptr; }
 int vitx_zeroshot_read(vitx_ctx *c, float *probs, float *logits, size_t n_floats_each) {
     if (!c || !probs) return VITX_ERR_ARG;
-    const int n = c->zs_on() ? c->zs_n : 0, K = c->zs_K;
+    const ZeroShot *zs = c->zs.get();
+    const int n = zs ? zs->n : 0;
     if (n == 0) { set_error("vitx_zeroshot_read: no forward has run with a bank set since vitx_zeroshot_set"); return VITX_ERR_ARG; }
+    const int K = zs->K;
     const size_t need = (size_t)n * K;
     if (n_floats_each < need) { set_error("vitx_zeroshot_read: buffer too small (%zu floats needed for %d images of %d classes)", need, n, K); return VITX_ERR_ARG; }
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy2D(probs, (size_t)K * 4, c->zs_out, (size_t)2 * K * 4, (size_t)K * 4, n, hipMemcpyDeviceToHost));
-    if (logits) HIP_TRY(hipMemcpy2D(logits, (size_t)K * 4, c->zs_out + K, (size_t)2 * K * 4, (size_t)K * 4, n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy2D(probs, (size_t)K * 4, zs->out.p, (size_t)2 * K * 4, (size_t)K * 4, n, hipMemcpyDeviceToHost));
+    if (logits) HIP_TRY(hipMemcpy2D(logits, (size_t)K * 4, zs->out.as<float>() + K, (size_t)2 * K * 4, (size_t)K * 4, n, hipMemcpyDeviceToHost));
     return VITX_OK;
 }
 
@@ -256,6 +316,7 @@ int vitx_zeroshot_read(vitx_ctx *c, float *probs, float *logits, size_t n_floats
 int vitx_nn_width(const vitx_ctx *c, int source) { return c ? c->nn_width(source) : 0; }
 int vitx_nn_set(vitx_ctx *c, const float *gallery, long G, int E, int k, int source, const int32_t *labels, int n_labels, float temperature) {
     if (!c) return VITX_ERR_ARG;
+    constexpr int Gc = Gallery::kChunk;
     const bool off = !gallery && G == 0;
     if (!off) {
         if (!gallery) { set_error("vitx_nn_set: NULL gallery with G = %ld", G); return VITX_ERR_ARG; }
@@ -268,8 +329,8 @@ int vitx_nn_set(vitx_ctx *c, const float *gallery, long G, int E, int k, int sou
         if (k > kNnMaxK) { set_error("vitx_nn_set: k = %d above %d", k, kNnMaxK); return VITX_ERR_UNSUPPORTED; }
         if (E % 64) { set_error("vitx_nn_set: the embedding width %d is not a multiple of 64 (the GEMMs' K step)", E); return VITX_ERR_UNSUPPORTED; }
         if (G >= 0x7fffffffL - 127) { set_error("vitx_nn_set: %ld gallery rows: indices are 31 bits (at most 2^31 - 129 rows)", G); return VITX_ERR_UNSUPPORTED; }
-        if ((size_t)round_up(c->pass_cap(), c->tm) * vitx_ctx::kNnChunk * 4 > 0xf0000000u) {       // the chunk GEMM addresses its output inside a 32-bit byte window
-            set_error("vitx_nn_set: the score scratch of %d images exceeds the chunk GEMM's 32-bit window (at most %d images per pass)", c->pass_cap(), (int)(0xf0000000u / 4 / vitx_ctx::kNnChunk / c->tm * c->tm));
+        if ((size_t)round_up(c->pass_cap(), c->tm) * Gc * 4 > 0xf0000000u) {       // the chunk GEMM addresses its output inside a 32-bit byte window
+            set_error("vitx_nn_set: the score scratch of %d images exceeds the chunk GEMM's 32-bit window (at most %d images per pass)", c->pass_cap(), (int)(0xf0000000u / 4 / Gc / c->tm * c->tm));
             return VITX_ERR_UNSUPPORTED;
         }
         for (size_t i = 0, nb = (size_t)G * E; i < nb; ++i)
@@ -277,51 +338,50 @@ int vitx_nn_set(vitx_ctx *c, const float *gallery, long G, int E, int k, int sou
         if (labels) for (long g = 0; g < G; ++g)
             if (labels[g] < 0 || labels[g] >= n_labels) { set_error("vitx_nn_set: label %d of gallery row %ld outside 0 .. %d", labels[g], g, n_labels - 1); return VITX_ERR_ARG; }
     }
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipDeviceSynchronize());          // no forward in flight reads or writes the buffers about to be freed
-    c->nn_free();
+    if (const int rc = quiesce(c)) return rc;
+    c->nn.reset();
     if (off) return VITX_OK;
-    constexpr int Gc = vitx_ctx::kNnChunk;
-    const long Gpad = (G + c->tn - 1) / c->tn * c->tn;
-    const int cap = c->pass_cap();
-    const size_t rows = (size_t)round_up(cap, c->tm), state_bytes = nn_state_bytes((int)rows, k);
-    auto alloc = [](void **p, size_t bytes) { if (hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; } return true; };
-    bool ok = alloc(&c->nn_gallery, (size_t)Gpad * E * 2) && alloc((void **)&c->nn_zero, (size_t)Gc * 4) && alloc((void **)&c->nn_out, (size_t)cap * k * 8);
-    if (ok && labels) ok = alloc((void **)&c->nn_labels, (size_t)G * 4) && alloc((void **)&c->nn_vote, (size_t)cap * n_labels * 4);
-    c->nn_a.assign(c->nslices, nullptr); c->nn_acc.assign(c->nslices, nullptr); c->nn_state.assign(c->nslices, nullptr);
-    for (int i = 0; ok && i < c->nslices; ++i) ok = alloc(&c->nn_a[i], rows * E * 2) && alloc((void **)&c->nn_acc[i], rows * Gc * 4) && alloc(&c->nn_state[i], state_bytes);
-    if (!ok) { c->nn_free(); set_error("vitx_nn_set: cannot allocate the buffers for %ld gallery rows and %d images", G, cap); return VITX_ERR_NOMEM; }
+    auto nn = std::make_unique<Gallery>();
+    nn->G = G; nn->Gpad = (G + c->tn - 1) / c->tn * c->tn; nn->k = k; nn->source = source; nn->E = E; nn->cap = c->pass_cap();
+    nn->nlabels = labels ? n_labels : 0; nn->T = labels ? temperature : 0.0f;
+    const size_t gallery_bytes = (size_t)nn->Gpad * E * 2, rows = (size_t)round_up(nn->cap, c->tm), state_bytes = nn_state_bytes((int)rows, k);
+    bool ok = nn->gallery.alloc(gallery_bytes) && nn->zero.alloc((size_t)Gc * 4) && nn->out.alloc((size_t)nn->cap * k * 8);
+    if (ok && labels) ok = nn->labels.alloc((size_t)G * 4) && nn->vote.alloc((size_t)nn->cap * n_labels * 4);
+    nn->a.resize(c->nslices); nn->acc.resize(c->nslices); nn->state.resize(c->nslices);
+    for (int i = 0; ok && i < c->nslices; ++i) ok = nn->a[i].alloc(rows * E * 2) && nn->acc[i].alloc(rows * Gc * 4) && nn->state[i].alloc(state_bytes);
+    if (!ok) { set_error("vitx_nn_set: cannot allocate the buffers for %ld gallery rows and %d images", G, nn->cap); return VITX_ERR_NOMEM; }
+    nn->scratch = (size_t)c->nslices * (rows * Gc * 4 + state_bytes);
     // the gallery goes up in blocks of rows, rounded (RNE) to the operand type; the zero rows beyond G come from the memset
-    hipError_t e = hipMemset(c->nn_gallery, 0, (size_t)Gpad * E * 2);
-    if (e == hipSuccess) e = hipMemset(c->nn_zero, 0, (size_t)Gc * 4);
+    hipError_t e = hipMemset(nn->gallery.p, 0, gallery_bytes);
+    if (e == hipSuccess) e = hipMemset(nn->zero.p, 0, (size_t)Gc * 4);
     for (long g0 = 0; g0 < G && e == hipSuccess; g0 += 65536) {
         const int nr = (int)std::min<long>(65536, G - g0);
         const std::vector<uint16_t> hb = operand_matrix_host(c->dtype, gallery + (size_t)g0 * E, nullptr, nr, E, nr, E, 0, 0);
-        e = hipMemcpy((char *)c->nn_gallery + (size_t)g0 * E * 2, hb.data(), hb.size() * 2, hipMemcpyHostToDevice);
+        e = hipMemcpy(nn->gallery.as<char>() + (size_t)g0 * E * 2, hb.data(), hb.size() * 2, hipMemcpyHostToDevice);
     }
-    if (e == hipSuccess && labels) e = hipMemcpy(c->nn_labels, labels, (size_t)G * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && labels) e = hipMemcpy(nn->labels.p, labels, (size_t)G * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { c->nn_free(); set_error("vitx_nn_set: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
-    c->nn_G = G; c->nn_Gpad = Gpad; c->nn_k = k; c->nn_source = source; c->nn_E = E; c->nn_nlabels = labels ? n_labels : 0; c->nn_T = labels ? temperature : 0.0f; c->nn_cap = cap;
-    c->nn_scratch = (size_t)c->nslices * (rows * Gc * 4 + state_bytes);
+    if (e != hipSuccess) return hip_failed("vitx_nn_set", e);
+    c->nn = std::move(nn);
     return VITX_OK;
 }
-long vitx_nn_rows(const vitx_ctx *c) { return c ? c->nn_G : 0; }
-int vitx_nn_k(const vitx_ctx *c) { return c ? c->nn_k : 0; }
-int vitx_nn_labels(const vitx_ctx *c) { return c ? c->nn_nlabels : 0; }
-int vitx_nn_images(const vitx_ctx *c) { return c ? c->nn_n : 0; }
-const void *vitx_nn_device(const vitx_ctx *c) { return c ? c->nn_out : nullptr; }
-size_t vitx_nn_scratch_bytes(const vitx_ctx *c) { return c ? c->nn_scratch : 0; }
+long vitx_nn_rows(const vitx_ctx *c) { return c && c->nn ? c->nn->G : 0; }
+int vitx_nn_k(const vitx_ctx *c) { return c && c->nn ? c->nn->k : 0; }
+int vitx_nn_labels(const vitx_ctx *c) { return c && c->nn ? c->nn->nlabels : 0; }
+int vitx_nn_images(const vitx_ctx *c) { return c && c->nn ? c->nn->n : 0; }
+const void *vitx_nn_device(const vitx_ctx *c) { return c && c->nn ? c->nn->out.p : nullptr; }
+size_t vitx_nn_scratch_bytes(const vitx_ctx *c) { return c && c->nn ? c->nn->scratch : 0; }
 int vitx_nn_read(vitx_ctx *c, int32_t *idx, float *score, float *vote) {
     if (!c || !idx || !score) return VITX_ERR_ARG;
-    const int n = c->nn_on() ? c->nn_n : 0, k = c->nn_k;
+    const Gallery *nn = c->nn.get();
+    const int n = nn ? nn->n : 0;
     if (n == 0) { set_error("vitx_nn_read: no forward has run with a gallery set since vitx_nn_set"); return VITX_ERR_ARG; }
-    if (vote && !c->nn_nlabels) { set_error("vitx_nn_read: the gallery has no labels: there is no vote"); return VITX_ERR_ARG; }
+    if (vote && !nn->nlabels) { set_error("vitx_nn_read: the gallery has no labels: there is no vote"); return VITX_ERR_ARG; }
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy2D(score, 4, c->nn_out, 8, 4, (size_t)n * k, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy2D(idx, 4, c->nn_out + 1, 8, 4, (size_t)n * k, hipMemcpyDeviceToHost));
-    if (vote) HIP_TRY(hipMemcpy(vote, c->nn_vote, (size_t)n * c->nn_nlabels * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy2D(score, 4, nn->out.p, 8, 4, (size_t)n * nn->k, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy2D(idx, 4, nn->out.as<float>() + 1, 8, 4, (size_t)n * nn->k, hipMemcpyDeviceToHost));
+    if (vote) HIP_TRY(hipMemcpy(vote, nn->vote.p, (size_t)n * nn->nlabels * 4, hipMemcpyDeviceToHost));
     return VITX_OK;
 }
 
@@ -330,18 +390,12 @@ int vitx_dense_set(vitx_ctx *c, const float *W, const float *bias, int K, int Dc
     if (!c) return VITX_ERR_ARG;
     const bool off = !W && K == 0;
     uint64_t mask = layer_mask;
-    int m = 0, oh = out_h, ow = out_w;
+    int oh = out_h, ow = out_w;
     if (!off) {
         if (!W) { set_error("vitx_dense_set: NULL weights with K = %d", K); return VITX_ERR_ARG; }
         if (K < 1) { set_error("vitx_dense_set: K = %d classes", K); return VITX_ERR_ARG; }
         if (flags & ~(VITX_DENSE_SCORE | VITX_DENSE_LOGITS)) { set_error("vitx_dense_set: unknown flags 0x%x", flags); return VITX_ERR_ARG; }
-        if (mask == 0) mask = 1ull << (c->L - 1);
-        if (c->L < 64 && (mask >> c->L)) { set_error("vitx_dense_set: layer mask selects a layer at or beyond L = %d", c->L); return VITX_ERR_ARG; }
-        m = __builtin_popcountll(mask);
-        if (m > 4) { set_error("vitx_dense_set: %d layers selected, at most 4", m); return VITX_ERR_ARG; }
-        if (Dc != m * c->D) { set_error("vitx_dense_set: the head's width %d is not %d layers x D = %d", Dc, m, m * c->D); return VITX_ERR_ARG; }
-        if (out_h < 0 || out_w < 0 || ((out_h == 0) != (out_w == 0))) { set_error("vitx_dense_set: output shape %d x %d (0 x 0: the context's image shape)", out_h, out_w); return VITX_ERR_ARG; }
-        if (out_h == 0) { oh = c->Sh; ow = c->Sw; }
+        if (const int rc = patch_head_layers(c, "vitx_dense_set", Dc, &mask, &oh, &ow)) return rc;
         for (size_t i = 0, nb = (size_t)K * Dc; i < nb; ++i)
             if (!std::isfinite(W[i])) { set_error("vitx_dense_set: weight [%zu][%zu] is not finite", i / Dc, i % Dc); return VITX_ERR_ARG; }
         if (bias) for (int k = 0; k < K; ++k)
@@ -352,67 +406,51 @@ int vitx_dense_set(vitx_ctx *c, const float *W, const float *bias, int K, int Dc
             set_error("vitx_dense_set: output %d x %d outside the patch grid %d x %d .. %d (upsampling only)", oh, ow, c->gh, c->gw, kDenseMaxOut);
             return VITX_ERR_UNSUPPORTED;
         }
-        const size_t rows = (size_t)c->pass_cap() * c->gh * c->gw;
-        if (rows * Dc * 2 > 0xf0000000u || rows * round_up(K, c->tn) * 4 > 0xf0000000u || c->pass_cap() > 65535) {
-            set_error("vitx_dense_set: the operand or logit rows of a pass of %d images leave the GEMM's 32-bit byte window", c->pass_cap());
-            return VITX_ERR_UNSUPPORTED;
-        }
+        if (const int rc = patch_head_window(c, "vitx_dense_set", K, Dc)) return rc;
     }
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipDeviceSynchronize());          // no forward in flight reads or writes the buffers about to be freed
-    c->dense_free();
+    if (const int rc = quiesce(c)) return rc;
+    c->dense.reset();
     if (off) return VITX_OK;
-    const int Kpad = round_up(K, c->tn), cap = c->pass_cap(), Np = c->gh * c->gw;
-    const size_t px = (size_t)oh * ow;
-    auto alloc = [](void **p, size_t bytes) { if (hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; } return true; };
-    bool ok = alloc(&c->dn_W, (size_t)Kpad * Dc * 2) && alloc((void **)&c->dn_bias, (size_t)Kpad * 4) && alloc((void **)&c->dn_labels, (size_t)cap * px);
-    if (ok && (flags & VITX_DENSE_SCORE)) ok = alloc((void **)&c->dn_score, (size_t)cap * px * 4);
-    if (ok && (flags & VITX_DENSE_LOGITS)) ok = alloc((void **)&c->dn_logits, (size_t)cap * Np * K * 4);
-    c->dn_a.assign(c->nslices, nullptr); c->dn_acc.assign(c->nslices, nullptr);
-    size_t scratch = 0;
+    auto dn = std::make_unique<DenseHead>();
+    patch_head_init(c, dn.get(), K, Dc, mask, oh, ow, flags);
+    const size_t Kpad = dn->Kpad, cap = dn->cap, px = (size_t)oh * ow, Np = (size_t)c->gh * c->gw;
+    bool ok = dn->W.alloc(Kpad * Dc * 2) && dn->bias.alloc(Kpad * 4) && dn->labels.alloc(cap * px);
+    if (ok && (flags & VITX_DENSE_SCORE)) ok = dn->score.alloc(cap * px * 4);
+    if (ok && (flags & VITX_DENSE_LOGITS)) ok = dn->logits.alloc(cap * Np * K * 4);
     hipError_t e = hipSuccess;
-    for (int i = 0; ok && i < c->nslices; ++i) {
-        const size_t rows = (size_t)round_up(std::min(c->slices[i].cap, cap) * Np, c->tm);
-        ok = alloc(&c->dn_a[i], rows * Dc * 2) && alloc((void **)&c->dn_acc[i], rows * Kpad * 4);
-        if (ok) e = hipMemset(c->dn_a[i], 0, rows * Dc * 2);
-        if (e != hipSuccess) break;
-        scratch += rows * Dc * 2 + rows * Kpad * 4;
-    }
-    if (!ok) { c->dense_free(); set_error("vitx_dense_set: cannot allocate the buffers for %d classes, %d x %d labels and %d images", K, oh, ow, cap); return VITX_ERR_NOMEM; }
+    if (!ok || !patch_head_scratch(c, dn.get(), &e)) { set_error("vitx_dense_set: cannot allocate the buffers for %d classes, %d x %d labels and %d images", K, oh, ow, dn->cap); return VITX_ERR_NOMEM; }
     // the head goes up rounded (RNE) to the operand type; the zero rows beyond K come from operand_matrix_host, the zero biases from the memset
-    if (e == hipSuccess) {
-        const std::vector<uint16_t> hw = operand_matrix_host(c->dtype, W, nullptr, K, Dc, Kpad, Dc, 0, 0);
-        e = hipMemcpy(c->dn_W, hw.data(), hw.size() * 2, hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess) e = hipMemset(c->dn_bias, 0, (size_t)Kpad * 4);
-    if (e == hipSuccess && bias) e = hipMemcpy(c->dn_bias, bias, (size_t)K * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = upload_operand(c, dn->W, W, K, dn->Kpad, Dc);
+    if (e == hipSuccess) e = hipMemset(dn->bias.p, 0, Kpad * 4);
+    if (e == hipSuccess && bias) e = hipMemcpy(dn->bias.p, bias, (size_t)K * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { c->dense_free(); set_error("vitx_dense_set: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
-    c->dn_K = K; c->dn_Kpad = Kpad; c->dn_Dc = Dc; c->dn_mask = mask; c->dn_oh = oh; c->dn_ow = ow; c->dn_flags = flags; c->dn_cap = cap; c->dn_scratch = scratch;
+    if (e != hipSuccess) return hip_failed("vitx_dense_set", e);
+    c->dense = std::move(dn);
     return VITX_OK;
 }
-int vitx_dense_classes(const vitx_ctx *c) { return c ? c->dn_K : 0; }
+int vitx_dense_classes(const vitx_ctx *c) { return c && c->dense ? c->dense->K : 0; }
 int vitx_dense_shape(const vitx_ctx *c, int *out_h, int *out_w) {
     if (!c) return VITX_ERR_ARG;
-    if (out_h) *out_h = c->dn_oh;
-    if (out_w) *out_w = c->dn_ow;
+    if (out_h) *out_h = c->dense ? c->dense->oh : 0;
+    if (out_w) *out_w = c->dense ? c->dense->ow : 0;
     return VITX_OK;
 }
-int vitx_dense_images(const vitx_ctx *c) { return c ? c->dn_n : 0; }
-const void *vitx_dense_device(const vitx_ctx *c) { return c ? c->dn_labels : nullptr; }
-size_t vitx_dense_scratch_bytes(const vitx_ctx *c) { return c ? c->dn_scratch : 0; }
+int vitx_dense_images(const vitx_ctx *c) { return c && c->dense ? c->dense->n : 0; }
+const void *vitx_dense_device(const vitx_ctx *c) { return c && c->dense ? c->dense->labels.p : nullptr; }
+size_t vitx_dense_scratch_bytes(const vitx_ctx *c) { return c && c->dense ? c->dense->scratch : 0; }
 int vitx_dense_read(vitx_ctx *c, uint8_t *labels, float *score, float *logits) {
     if (!c || !labels) return VITX_ERR_ARG;
-    const int n = c->dense_on() ? c->dn_n : 0;
+    const DenseHead *dn = c->dense.get();
+    const int n = dn ? dn->n : 0;
     if (n == 0) { set_error("vitx_dense_read: no forward has run with a dense head set since vitx_dense_set"); return VITX_ERR_ARG; }
-    if (score && !c->dn_score) { set_error("vitx_dense_read: the head was set without VITX_DENSE_SCORE"); return VITX_ERR_ARG; }
-    if (logits && !c->dn_logits) { set_error("vitx_dense_read: the head was set without VITX_DENSE_LOGITS"); return VITX_ERR_ARG; }
-    const size_t px = (size_t)c->dn_oh * c->dn_ow;
+    if (score && !dn->score) { set_error("vitx_dense_read: the head was set without VITX_DENSE_SCORE"); return VITX_ERR_ARG; }
+    if (logits && !dn->logits) { set_error("vitx_dense_read: the head was set without VITX_DENSE_LOGITS"); return VITX_ERR_ARG; }
+    const size_t px = (size_t)dn->oh * dn->ow;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(labels, c->dn_labels, (size_t)n * px, hipMemcpyDeviceToHost));
-    if (score) HIP_TRY(hipMemcpy(score, c->dn_score, (size_t)n * px * 4, hipMemcpyDeviceToHost));
-    if (logits) HIP_TRY(hipMemcpy(logits, c->dn_logits, (size_t)n * c->gh * c->gw * c->dn_K * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(labels, dn->labels.p, (size_t)n * px, hipMemcpyDeviceToHost));
+    if (score) HIP_TRY(hipMemcpy(score, dn->score.p, (size_t)n * px * 4, hipMemcpyDeviceToHost));
+    if (logits) HIP_TRY(hipMemcpy(logits, dn->logits.p, (size_t)n * c->gh * c->gw * dn->K * 4, hipMemcpyDeviceToHost));
     return VITX_OK;
 }
 
@@ -422,19 +460,13 @@ int vitx_depth_set(vitx_ctx *c, const float *Wp, const float *Wc, const float *b
     if (!c) return VITX_ERR_ARG;
     const bool off = !Wp && K == 0;
     uint64_t mask = layer_mask;
-    int m = 0, oh = out_h, ow = out_w;
+    int oh = out_h, ow = out_w;
     const int fh = upsample * c->gh, fw = upsample * c->gw;
     if (!off) {
         if (!Wp || !bins) { set_error("vitx_depth_set: NULL weights or bins with K = %d", K); return VITX_ERR_ARG; }
         if (K < 1) { set_error("vitx_depth_set: K = %d bins", K); return VITX_ERR_ARG; }
         if (flags & ~(VITX_DEPTH_NORM | VITX_DEPTH_LOGITS | VITX_DEPTH_FINE)) { set_error("vitx_depth_set: unknown flags 0x%x", flags); return VITX_ERR_ARG; }
-        if (mask == 0) mask = 1ull << (c->L - 1);
-        if (c->L < 64 && (mask >> c->L)) { set_error("vitx_depth_set: layer mask selects a layer at or beyond L = %d", c->L); return VITX_ERR_ARG; }
-        m = __builtin_popcountll(mask);
-        if (m > 4) { set_error("vitx_depth_set: %d layers selected, at most 4", m); return VITX_ERR_ARG; }
-        if (Dc != m * c->D) { set_error("vitx_depth_set: the head's width %d is not %d layers x D = %d", Dc, m, m * c->D); return VITX_ERR_ARG; }
-        if (out_h < 0 || out_w < 0 || ((out_h == 0) != (out_w == 0))) { set_error("vitx_depth_set: output shape %d x %d (0 x 0: the context's image shape)", out_h, out_w); return VITX_ERR_ARG; }
-        if (out_h == 0) { oh = c->Sh; ow = c->Sw; }
+        if (const int rc = patch_head_layers(c, "vitx_depth_set", Dc, &mask, &oh, &ow)) return rc;
         if (!std::isfinite(min_depth) || !std::isfinite(max_depth) || min_depth > max_depth) { set_error("vitx_depth_set: the depth range %g .. %g must be finite and ordered", (double)min_depth, (double)max_depth); return VITX_ERR_ARG; }
         for (const float *W : {Wp, Wc})
             if (W) for (size_t i = 0, nb = (size_t)K * Dc; i < nb; ++i)
@@ -451,83 +483,73 @@ int vitx_depth_set(vitx_ctx *c, const float *Wp, const float *Wc, const float *b
             set_error("vitx_depth_set: output %d x %d outside the fine plane %d x %d .. %d (upsampling only)", oh, ow, fh, fw, kDepthMaxOut);
             return VITX_ERR_UNSUPPORTED;
         }
-        const size_t rows = (size_t)c->pass_cap() * c->gh * c->gw;
-        if (rows * Dc * 2 > 0xf0000000u || rows * round_up(K, c->tn) * 4 > 0xf0000000u || c->pass_cap() > 65535) {
-            set_error("vitx_depth_set: the operand or logit rows of a pass of %d images leave the GEMM's 32-bit byte window", c->pass_cap());
-            return VITX_ERR_UNSUPPORTED;
-        }
+        if (const int rc = patch_head_window(c, "vitx_depth_set", K, Dc)) return rc;
     }
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipDeviceSynchronize());          // no forward in flight reads or writes the buffers about to be freed
-    c->depth_free();
+    if (const int rc = quiesce(c)) return rc;
+    c->depth.reset();
     if (off) return VITX_OK;
-    const int Kpad = round_up(K, c->tn), cap = c->pass_cap(), Np = c->gh * c->gw;
-    const size_t px = (size_t)oh * ow, fpx = (size_t)fh * fw;
-    auto alloc = [](void **p, size_t bytes) { if (hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; } return true; };
-    bool ok = alloc(&c->dp_Wp, (size_t)Kpad * Dc * 2) && (!Wc || alloc(&c->dp_Wc, (size_t)Kpad * Dc * 2)) && alloc((void **)&c->dp_bias, (size_t)Kpad * 4) &&
-              alloc((void **)&c->dp_zero, (size_t)Kpad * 4) && alloc((void **)&c->dp_bins, (size_t)Kpad * 4) && alloc((void **)&c->dp_depth, (size_t)cap * px * 4) &&
-              alloc((void **)&c->dp_fine, (size_t)cap * fpx * 4);
-    if (ok && (flags & VITX_DEPTH_LOGITS)) ok = alloc((void **)&c->dp_logits, (size_t)cap * Np * K * 4) && (!Wc || alloc((void **)&c->dp_off, (size_t)cap * K * 4));
-    c->dp_a.assign(c->nslices, nullptr); c->dp_acc.assign(c->nslices, nullptr); c->dp_ac.assign(c->nslices, nullptr); c->dp_o.assign(c->nslices, nullptr);
-    size_t scratch = 0;
+    auto dp = std::make_unique<DepthHead>();
+    patch_head_init(c, dp.get(), K, Dc, mask, oh, ow, flags);
+    dp->u = upsample; dp->lo = min_depth; dp->hi = max_depth;
+    dp->bias_host.assign(K, 0.0f);
+    if (bias) std::copy(bias, bias + K, dp->bias_host.begin());
+    const size_t Kpad = dp->Kpad, cap = dp->cap, px = (size_t)oh * ow, fpx = (size_t)fh * fw, Np = (size_t)c->gh * c->gw;
+    bool ok = dp->Wp.alloc(Kpad * Dc * 2) && (!Wc || dp->Wc.alloc(Kpad * Dc * 2)) && dp->bias.alloc(Kpad * 4) && dp->zero.alloc(Kpad * 4) && dp->bins.alloc(Kpad * 4) &&
+              dp->depth.alloc(cap * px * 4) && dp->fine.alloc(cap * fpx * 4);
+    if (ok && (flags & VITX_DEPTH_LOGITS)) ok = dp->logits.alloc(cap * Np * K * 4) && (!Wc || dp->off.alloc(cap * K * 4));
     hipError_t e = hipSuccess;
-    for (int i = 0; ok && i < c->nslices; ++i) {
-        const int imgs = std::min(c->slices[i].cap, cap);
-        const size_t rows = (size_t)round_up(imgs * Np, c->tm), crows = (size_t)round_up(imgs, c->tm);
-        ok = alloc(&c->dp_a[i], rows * Dc * 2) && alloc((void **)&c->dp_acc[i], rows * Kpad * 4);
-        if (ok) e = hipMemset(c->dp_a[i], 0, rows * Dc * 2);
-        scratch += rows * Dc * 2 + rows * Kpad * 4;
-        if (ok && Wc && e == hipSuccess) {
-            ok = alloc(&c->dp_ac[i], crows * Dc * 2) && alloc((void **)&c->dp_o[i], crows * Kpad * 4);
-            if (ok) e = hipMemset(c->dp_ac[i], 0, crows * Dc * 2);
-            scratch += crows * Dc * 2 + crows * Kpad * 4;
+    ok = ok && patch_head_scratch(c, dp.get(), &e);
+    if (Wc) {        // the class rows and the offsets, per slice: zero-filled once like the patch rows
+        dp->ac.resize(c->nslices); dp->o.resize(c->nslices);
+        for (int i = 0; ok && e == hipSuccess && i < c->nslices; ++i) {
+            const size_t crows = (size_t)round_up(std::min(c->slices[i].cap, dp->cap), c->tm);
+            ok = dp->ac[i].alloc(crows * Dc * 2) && dp->o[i].alloc(crows * Kpad * 4);
+            if (ok) e = hipMemset(dp->ac[i].p, 0, crows * Dc * 2);
+            dp->scratch += crows * Dc * 2 + crows * Kpad * 4;
         }
-        if (e != hipSuccess) break;
     }
-    if (!ok) { c->depth_free(); set_error("vitx_depth_set: cannot allocate the buffers for %d bins, %d x %d maps and %d images", K, oh, ow, cap); return VITX_ERR_NOMEM; }
+    if (!ok) { set_error("vitx_depth_set: cannot allocate the buffers for %d bins, %d x %d maps and %d images", K, oh, ow, dp->cap); return VITX_ERR_NOMEM; }
     // the halves go up rounded (RNE) to the operand type; the zero rows beyond K come from operand_matrix_host, the zero biases from the memset
-    for (int h = 0; h < 2 && e == hipSuccess; ++h) {
-        if (h && !Wc) break;
-        const std::vector<uint16_t> hw = operand_matrix_host(c->dtype, h ? Wc : Wp, nullptr, K, Dc, Kpad, Dc, 0, 0);
-        e = hipMemcpy(h ? c->dp_Wc : c->dp_Wp, hw.data(), hw.size() * 2, hipMemcpyHostToDevice);
-    }
-    for (float *p : {c->dp_bias, c->dp_zero, c->dp_bins}) if (e == hipSuccess) e = hipMemset(p, 0, (size_t)Kpad * 4);
-    if (e == hipSuccess && bias) e = hipMemcpy(c->dp_bias, bias, (size_t)K * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(c->dp_bins, bins, (size_t)K * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = upload_operand(c, dp->Wp, Wp, K, dp->Kpad, Dc);
+    if (e == hipSuccess && Wc) e = upload_operand(c, dp->Wc, Wc, K, dp->Kpad, Dc);
+    for (const DevMem *m : {&dp->bias, &dp->zero, &dp->bins}) if (e == hipSuccess) e = hipMemset(m->p, 0, Kpad * 4);
+    if (e == hipSuccess && bias) e = hipMemcpy(dp->bias.p, bias, (size_t)K * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dp->bins.p, bins, (size_t)K * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { c->depth_free(); set_error("vitx_depth_set: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
-    c->dp_bias_host.assign(K, 0.0f);
-    if (bias) std::copy(bias, bias + K, c->dp_bias_host.begin());
-    c->dp_K = K; c->dp_Kpad = Kpad; c->dp_Dc = Dc; c->dp_mask = mask; c->dp_u = upsample; c->dp_oh = oh; c->dp_ow = ow; c->dp_lo = min_depth; c->dp_hi = max_depth;
-    c->dp_flags = flags; c->dp_cap = cap; c->dp_scratch = scratch;
+    if (e != hipSuccess) return hip_failed("vitx_depth_set", e);
+    c->depth = std::move(dp);
     return VITX_OK;
 }
-int vitx_depth_bins(const vitx_ctx *c) { return c ? c->dp_K : 0; }
+int vitx_depth_bins(const vitx_ctx *c) { return c && c->depth ? c->depth->K : 0; }
 int vitx_depth_shape(const vitx_ctx *c, int *out_h, int *out_w, int *fine_h, int *fine_w) {
     if (!c) return VITX_ERR_ARG;
-    if (out_h) *out_h = c->dp_oh;
-    if (out_w) *out_w = c->dp_ow;
-    if (fine_h) *fine_h = c->dp_u * c->gh;
-    if (fine_w) *fine_w = c->dp_u * c->gw;
+    const DepthHead *dp = c->depth.get();
+    if (out_h) *out_h = dp ? dp->oh : 0;
+    if (out_w) *out_w = dp ? dp->ow : 0;
+    if (fine_h) *fine_h = dp ? dp->u * c->gh : 0;
+    if (fine_w) *fine_w = dp ? dp->u * c->gw : 0;
     return VITX_OK;
 }
-int vitx_depth_images(const vitx_ctx *c) { return c ? c->dp_n : 0; }
-const void *vitx_depth_device(const vitx_ctx *c) { return c ? c->dp_depth : nullptr; }
-size_t vitx_depth_scratch_bytes(const vitx_ctx *c) { return c ? c->dp_scratch : 0; }
+int vitx_depth_images(const vitx_ctx *c) { return c && c->depth ? c->depth->n : 0; }
+const void *vitx_depth_device(const vitx_ctx *c) { return c && c->depth ? c->depth->depth.p : nullptr; }
+size_t vitx_depth_scratch_bytes(const vitx_ctx *c) { return c && c->depth ? c->depth->scratch : 0; }
 int vitx_depth_read(vitx_ctx *c, float *depth, float *fine, float *logits, float *offsets) {
     if (!c || !depth) return VITX_ERR_ARG;
-    const int n = c->depth_on() ? c->dp_n : 0, K = c->dp_K;
+    const DepthHead *dp = c->depth.get();
+    const int n = dp ? dp->n : 0;
     if (n == 0) { set_error("vitx_depth_read: no forward has run with a depth head set since vitx_depth_set"); return VITX_ERR_ARG; }
-    if (fine && !(c->dp_flags & VITX_DEPTH_FINE)) { set_error("vitx_depth_read: the head was set without VITX_DEPTH_FINE"); return VITX_ERR_ARG; }
-    if ((logits || offsets) && !c->dp_logits) { set_error("vitx_depth_read: the head was set without VITX_DEPTH_LOGITS"); return VITX_ERR_ARG; }
+    if (fine && !(dp->flags & VITX_DEPTH_FINE)) { set_error("vitx_depth_read: the head was set without VITX_DEPTH_FINE"); return VITX_ERR_ARG; }
+    if ((logits || offsets) && !dp->logits) { set_error("vitx_depth_read: the head was set without VITX_DEPTH_LOGITS"); return VITX_ERR_ARG; }
+    const int K = dp->K;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(depth, c->dp_depth, (size_t)n * c->dp_oh * c->dp_ow * 4, hipMemcpyDeviceToHost));
-    if (fine) HIP_TRY(hipMemcpy(fine, c->dp_fine, (size_t)n * c->dp_u * c->gh * c->dp_u * c->gw * 4, hipMemcpyDeviceToHost));
-    if (logits) HIP_TRY(hipMemcpy(logits, c->dp_logits, (size_t)n * c->gh * c->gw * K * 4, hipMemcpyDeviceToHost));
-    if (offsets && c->dp_off) HIP_TRY(hipMemcpy(offsets, c->dp_off, (size_t)n * K * 4, hipMemcpyDeviceToHost));
-    if (offsets && !c->dp_off) for (int i = 0; i < n; ++i) std::copy(c->dp_bias_host.begin(), c->dp_bias_host.end(), offsets + (size_t)i * K);
+    HIP_TRY(hipMemcpy(depth, dp->depth.p, (size_t)n * dp->oh * dp->ow * 4, hipMemcpyDeviceToHost));
+    if (fine) HIP_TRY(hipMemcpy(fine, dp->fine.p, (size_t)n * dp->u * c->gh * dp->u * c->gw * 4, hipMemcpyDeviceToHost));
+    if (logits) HIP_TRY(hipMemcpy(logits, dp->logits.p, (size_t)n * c->gh * c->gw * K * 4, hipMemcpyDeviceToHost));
+    if (offsets && dp->off) HIP_TRY(hipMemcpy(offsets, dp->off.p, (size_t)n * K * 4, hipMemcpyDeviceToHost));
+    if (offsets && !dp->off) for (int i = 0; i < n; ++i) std::copy(dp->bias_host.begin(), dp->bias_host.end(), offsets + (size_t)i * K);
     return VITX_OK;
 }
 
 }  // extern "C"
+
