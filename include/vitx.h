@@ -1118,6 +1118,74 @@ int vitx_op_attention_text(int dtype, const void *d_qkv, void *d_out, int n, int
 /* attention_generic.hip at any head dim it takes, 64 included (vitx_op_attention prefers the tuned families there): the yardstick of tools/text_cost.py */
 int vitx_op_attention_generic(int dtype, const void *d_qkv, void *d_out, int n_img, int N, int D, int H, void *stream);
 
+/* ---- packed batches: images of different shapes in one forward ---------------------
+ * A rectangular context runs one shape.  A PACKED context takes n images, each with its own h_i x w_i (positive multiples of the patch
+ * size), lays their tokens end to end in one [sum N_i][D] residual stream (N_i = T + (h_i / P)(w_i / P), T = 1 + the register tokens;
+ * image i = rows row0[i] .. row0[i + 1] - 1) and runs ONE forward: a caller whose images have their own aspect ratios needs neither a
+ * context per shape nor buckets.  GEMMs, LayerNorm, activation, gate and pre-norm work on rows and do not care where an image ends; the
+ * patch embedding (the rectangular context's kernel, one launch per run of consecutive images of one shape, so a caller who sorts by shape
+ * pays one launch per distinct shape), the rotary embeddings, the attention and the class-row gather go by the segment table.
+ *
+ * vitx_pack_create: scratch for max_tokens token rows and max_images images; dtype VITX_F16 or VITX_BF16.  VITX_F16 here is PLAIN fp16
+ * operands with the ordinary attention (the text tower's rule: no hi / lo parity planes).  One stream, no sub-batches, no graph cache, no
+ * LayerNorm fusion, no class-token tail; block-quantised matrices are expanded once at upload; the GEMMs go through the dispatcher with the
+ * device's own tuning (every GEMM family gives the same bits).  options (NULL = all zero): pos_interp as in vitx_ctx_options; max_grids = the
+ * grids whose tables the context caches (0 = 32).  VITX_ERR_UNSUPPORTED at creation, before any device call: a ViTSTR file, a
+ * VITX_POOL_CLS_MEAN or VITX_POOL_MAP head, VITX_MXFP8, a head dim that is no multiple of 8 up to 128, a D outside the LayerNorm widths, a
+ * max_tokens beyond the kernels' 32-bit buffer window.  VITX_ERR_ARG: a text model.
+ *
+ * Tables: the position table of a grid (the file's at the file's grid, else resampled on the device, pos_interp) and, for a file with
+ * `rope`, its rotary table (vitx_model_rope_table, uploaded) are built the first time a call names the grid -- that call allocates -- and
+ * cached; beyond max_grids the least recently used grid the current call does not name is dropped.  A table is freed or overwritten only
+ * after the context's previous forward has finished (an event the call waits for on the host: such a call does not merely enqueue).
+ *
+ * vitx_pack_forward: imgs = the images' f32 HWC pixels end to end (image i: h_i * w_i * 3 floats), shapes host int32 [n][2] = h, w; probs and
+ * logits host [n][C].  vitx_pack_forward_device: the same on device pointers; shapes stay a HOST pointer, free when the call returns; only
+ * enqueues on `stream` (0 = the context's own), after waiting for the previous call's upload of the segment tables -- not for its forward.
+ * Forwards of one context share its scratch: the caller orders them, as with any context.  VITX_ERR_ARG, checked on the host before the first
+ * device call (vitx_pack_check is that text): a shape that is not a positive multiple of the patch size, n outside 1 .. max_images, more than
+ * max_tokens tokens, more distinct grids in one call than max_grids (vitx_pack_distinct_grids counts them).
+ *
+ * Features of the last layer (vitx_pack_feat_enable, flags VITX_FEAT_CLS | VITX_FEAT_TOKENS, 0 = off; with nothing enabled nothing is launched
+ * or allocated): the f32 final norm of every row of the pack (vitx_op_layernorm_f32's bits), gathered by vitx_pack_feat_read: cls [n][D] = the
+ * class rows, tokens [sum gh_i gw_i][D] = the patch rows, images end to end.
+ *
+ * Determinism: within a context an image's logits, probabilities and features are a function of its own pixels and shape -- the same bits
+ * alone, at any position in a pack and beside any neighbours (NaN pixels included).  A pack of one shape gives the bits of a rectangular
+ * context of that shape created with last_layer_all_rows = 1 wherever both run the same attention arithmetic (any head dim but 64, where an
+ * image context prefers its tuned kernels and, in VITX_F16, the parity planes).
+ *
+ * The kernels on the caller's device buffers (only enqueue, but see below):
+ *   vitx_op_attention_packed   d_qkv [rows][3 D] -> d_out [rows][D], d_row0 int32 [n + 1]; any N_i >= 1, head dim a multiple of 8 up to 128.  Image
+ *                              i's rows have exactly the bits vitx_op_attention_generic(dtype, qkv + row0[i] * 3 D, .., 1, N_i, D, H) writes; nothing
+ *                              outside rows row0[0] .. row0[n] - 1 is written.  A work item is (image, head, 64 queries): H * sum ceil(N_i / 64)
+ *                              workgroups, found by a binary search of the workgroup index in the running count of query blocks.  TEST entry
+ *                              point: it reads d_row0 back to build that count (synchronises); a packed context uploads both with one copy.
+ *   vitx_op_rope_packed        vitx_op_rope on a pack: token t >= prefix of image i rotates by row t - prefix of the table that starts
+ *                              d_table_off[i] floats into d_cos and d_sin; one launch for the pack; reads both tables back to check them (synchronises).
+ * Not offered on packed contexts (each a later step): the opt-in heads (attention maps, zero-shot bank, gallery, dense, depth), the pooled
+ * and attention-pooling heads, the F16 parity planes, LayerNorm fusion and sub-batch streams, a packed patch-embedding kernel, vitx_group_*. */
+typedef struct vitx_pack vitx_pack;
+typedef struct { int pos_interp, max_grids, reserved[6]; } vitx_pack_options;
+int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_images, int dtype, const vitx_pack_options *opt, vitx_pack **out);
+void vitx_pack_free(vitx_pack *p);
+int vitx_pack_shares_weights(const vitx_pack *p);
+/* host only: every refusal of a forward call but the grid count, and row0 [n + 1] (may be NULL) */
+int vitx_pack_check(const vitx_model *m, const int32_t *shapes /* [n][2] = h, w */, int n, int max_tokens, int max_images, int32_t *row0);
+/* host only: the distinct grids among shapes [n][2] -- what a forward call compares with max_grids (0 for NULL arguments) */
+int vitx_pack_distinct_grids(const vitx_model *m, const int32_t *shapes, int n);
+int vitx_pack_forward(vitx_pack *p, const float *imgs, const int32_t *shapes, int n, float *probs, float *logits /* or NULL */);
+int vitx_pack_forward_device(vitx_pack *p, const void *d_imgs, const int32_t *shapes /* host */, int n, void *d_probs, void *d_logits, void *stream);
+int vitx_pack_feat_enable(vitx_pack *p, int flags /* VITX_FEAT_CLS | VITX_FEAT_TOKENS, 0 = off */);
+int vitx_pack_feat_read(vitx_pack *p, float *cls /* [n][D] or NULL */, float *tokens /* [sum gh_i gw_i][D], images end to end, or NULL */);
+size_t vitx_pack_scratch_bytes(const vitx_pack *p);        /* device bytes of activation scratch and cached tables held now (weights not counted) */
+int vitx_pack_launches(const vitx_pack *p, int *patch_embed);      /* kernel launches of the last forward call; *patch_embed: the patch embeddings among them */
+int vitx_op_attention_packed(int dtype, const void *d_qkv, void *d_out, const void *d_row0 /* int32 [n + 1] */, int n, int D, int H, void *stream);
+/* the same launch on tables the caller built and vouches for: d_qb0 int32 [n + 1] = the running count of ceil(N_i / 64), qblocks = d_qb0[n]; only enqueues */
+int vitx_op_attention_packed_tables(int dtype, const void *d_qkv, void *d_out, const void *d_row0, const void *d_qb0, int n, long qblocks, int D, int H, void *stream);
+int vitx_op_rope_packed(int dtype, void *d_qkv, long lo_off /* must be 0 */, const void *d_cos, const void *d_sin, const void *d_row0 /* int32 [n + 1] */,
+                        const void *d_table_off /* int32 [n] */, int n, int prefix, int D, int H, void *stream);
+
 /* ---- MXFP8 operands (VITX_MXFP8, encoding above) ------------------------------- */
 /* Host encoder: x f32 [rows][K] -> q [rows][k_pad] e4m3 bytes + scales [rows][k_pad / 32] (k_pad >= K, a multiple of 32; columns
  * K .. k_pad are zero elements, whole padding blocks get scale 127).  VITX_ERR_ARG on NULL or a bad size. */

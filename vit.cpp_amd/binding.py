@@ -69,6 +69,8 @@ EXPORTS = [
     "vitx_model_glu", "vitx_op_swiglu",
     "vitx_ctx_create_rect", "vitx_ctx_img_shape", "vitx_ctx_grid", "vitx_op_patch_embed_rect",
     "vitx_rect_shape", "vitx_preprocess_rect", "vitx_preprocess_rect_device", "vitx_preprocess_rect_device_supports",
+    "vitx_pack_create", "vitx_pack_free", "vitx_pack_shares_weights", "vitx_pack_check", "vitx_pack_distinct_grids", "vitx_pack_forward", "vitx_pack_forward_device",
+    "vitx_pack_feat_enable", "vitx_pack_feat_read", "vitx_pack_scratch_bytes", "vitx_pack_launches", "vitx_op_attention_packed", "vitx_op_attention_packed_tables", "vitx_op_rope_packed",
 ]
 
 
@@ -81,6 +83,10 @@ class CtxOptions(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("streams", C.c_int32), ("graph", C.c_int32), ("quant_on_host", C.c_int32), ("q4_fused_rows", C.c_int32),
                 ("split_first", C.c_int32), ("no_ln_fusion", C.c_int32), ("ln_test", C.c_int32), ("f16_fast_attention", C.c_int32), ("last_layer_all_rows", C.c_int32),
                 ("img_size", C.c_int32), ("pos_interp", C.c_int32)]
+
+
+class PackOptions(C.Structure):
+    _fields_ = [("pos_interp", C.c_int), ("max_grids", C.c_int), ("reserved", C.c_int * 6)]
 
 
 class Preproc(C.Structure):
@@ -313,6 +319,22 @@ def lib():
             L.vitx_preprocess_rect.argtypes = [pp, C.POINTER(C.c_uint8), ip, ip, ip, ip, C.POINTER(C.c_float)]
             L.vitx_preprocess_rect_device.argtypes = [pp, vp, ip, ip, ip, ip, ip, vp, vp]
             L.vitx_preprocess_rect_device_supports.argtypes = [pp, ip, ip, ip, ip]
+        if hasattr(L, "vitx_pack_create"):
+            i32p, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+            L.vitx_pack_create.argtypes = [vp, ip, ip, ip, ip, C.POINTER(PackOptions), C.POINTER(vp)]
+            L.vitx_pack_free.argtypes = [vp]
+            L.vitx_pack_shares_weights.argtypes = [vp]
+            L.vitx_pack_check.argtypes = [vp, i32p, ip, ip, ip, i32p]
+            L.vitx_pack_distinct_grids.argtypes = [vp, i32p, ip]
+            L.vitx_pack_forward.argtypes = [vp, fp, i32p, ip, fp, fp]
+            L.vitx_pack_forward_device.argtypes = [vp, vp, i32p, ip, vp, vp, vp]
+            L.vitx_pack_feat_enable.argtypes = [vp, ip]
+            L.vitx_pack_feat_read.argtypes = [vp, fp, fp]
+            L.vitx_pack_scratch_bytes.restype = C.c_size_t; L.vitx_pack_scratch_bytes.argtypes = [vp]
+            L.vitx_pack_launches.argtypes = [vp, C.POINTER(ip)]
+            L.vitx_op_attention_packed.argtypes = [ip, vp, vp, vp, ip, ip, ip, vp]
+            L.vitx_op_attention_packed_tables.argtypes = [ip, vp, vp, vp, vp, ip, C.c_long, ip, ip, vp]
+            L.vitx_op_rope_packed.argtypes =[ip, vp, C.c_long, vp, vp, vp, vp, ip, ip, ip, ip, vp]
         _lib = L
     return _lib
 
@@ -1098,6 +1120,133 @@ def text_bank(text_ctx: "TextContext", ids, groups=None, embeds=None):
         e = l2(mean / counts[:, None])
     kind, scale, bias = text_ctx.model.text_zs or (0, 1.0, 0.0)
     return e, kind, scale, bias
+
+
+def _pack_shapes(shapes) -> np.ndarray:
+    a = np.ascontiguousarray(shapes, np.int32)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError(f"shapes must be [n][2] = (h, w), got {a.shape}")
+    return a
+
+
+def pack_check(model: Model, shapes, max_tokens: int, max_images: int) -> np.ndarray:
+    """vitx_pack_check (host only): row0 [n + 1] of a pack of images of `shapes` [n][2] = (h, w), or VitxError (ERR_ARG) for what a packed forward refuses."""
+    a = _pack_shapes(shapes)
+    row0 = np.empty(a.shape[0] + 1, np.int32)
+    i32p = C.POINTER(C.c_int32)
+    check(lib().vitx_pack_check(model._h, a.ctypes.data_as(i32p), a.shape[0], max_tokens, max_images, row0.ctypes.data_as(i32p)), "vitx_pack_check")
+    return row0
+
+
+def pack_distinct_grids(model: Model, shapes) -> int:
+    """vitx_pack_distinct_grids (host only): the distinct grids among `shapes` -- what a packed forward compares with its context's max_grids."""
+    a = _pack_shapes(shapes)
+    return int(lib().vitx_pack_distinct_grids(model._h, a.ctypes.data_as(C.POINTER(C.c_int32)), a.shape[0]))
+
+
+def pack_images(imgs_u8, pp: Preproc, short_side: int, max_long: int = 0, *, patch: int):
+    """Every u8 HWC image at its own aspect-preserving shape (rect_shape, then preprocess_rect): (pixels, shapes) -- pixels the f32 HWC images end to
+    end in one flat array, shapes int32 [n][2] = (h, w): what PackContext.forward_flat takes."""
+    shapes, flat = [], []
+    for img in imgs_u8:
+        ny, nx = np.asarray(img).shape[:2]
+        w, h = rect_shape(nx, ny, patch, short_side, max_long)
+        shapes.append((h, w)); flat.append(preprocess_rect(img, pp, w, h).ravel())
+    return np.concatenate(flat), np.asarray(shapes, np.int32)
+
+
+class PackContext:
+    """A packed context (include/vitx.h "packed batches"): images of different shapes, their tokens end to end, in one forward."""
+
+    def __init__(self, model: Model, device: int = 0, max_tokens: int = 1024, max_images: int = 16, dtype: int = F16, pos_interp: int = POS_BICUBIC, max_grids: int = 0):
+        self._h = C.c_void_p()
+        self.model = model; self.max_tokens = max_tokens; self.max_images = max_images; self.dtype = dtype
+        opt = PackOptions(pos_interp=pos_interp, max_grids=max_grids)
+        check(lib().vitx_pack_create(model._h, device, max_tokens, max_images, dtype, C.byref(opt), C.byref(self._h)), "vitx_pack_create")
+        self._shapes = None; self._feat = 0
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h:
+            lib().vitx_pack_free(self._h); self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def forward_flat(self, pixels: np.ndarray, shapes):
+        """pixels: the images' f32 HWC pixels end to end; shapes [n][2] = (h, w).  Returns (probs, logits), each [n, C]."""
+        s = _pack_shapes(shapes); n = s.shape[0]
+        x = np.ascontiguousarray(pixels, np.float32).ravel()
+        if x.size != int((s[:, 0].astype(np.int64) * s[:, 1]).sum()) * 3:
+            raise ValueError(f"pixels hold {x.size} floats, the shapes {int((s[:, 0].astype(np.int64) * s[:, 1]).sum()) * 3}")
+        probs = np.empty((n, self.model.num_classes), np.float32); logits = np.empty_like(probs)
+        fp = C.POINTER(C.c_float)
+        check(lib().vitx_pack_forward(self._h, x.ctypes.data_as(fp), s.ctypes.data_as(C.POINTER(C.c_int32)), n, probs.ctypes.data_as(fp), logits.ctypes.data_as(fp)), "vitx_pack_forward")
+        self._shapes = s
+        return probs, logits
+
+    def forward(self, imgs):
+        """A list of f32 HWC arrays [h_i, w_i, 3], each of its own shape -> (probs, logits), each [n, C]."""
+        arrs = [np.ascontiguousarray(a, np.float32) for a in imgs]
+        for a in arrs:
+            if a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError(f"every image must be [h, w, 3], got {a.shape}")
+        return self.forward_flat(np.concatenate([a.ravel() for a in arrs]) if arrs else np.empty(0, np.float32), [a.shape[:2] for a in arrs])
+
+    def forward_device(self, d_imgs: int, shapes, d_probs: int, d_logits: int = 0, stream: int = 0) -> None:
+        """Device pointers, host shapes; only enqueues on `stream` (0 = the context's own stream)."""
+        s = _pack_shapes(shapes)
+        check(lib().vitx_pack_forward_device(self._h, d_imgs, s.ctypes.data_as(C.POINTER(C.c_int32)), s.shape[0], d_probs, d_logits or None, stream or None), "vitx_pack_forward_device")
+        self._shapes = s
+
+    def feat_enable(self, cls: bool = True, tokens: bool = False) -> None:
+        """Last-layer features of every later forward (vitx_pack_feat_enable); neither: off."""
+        self._feat = (FEAT_CLS if cls else 0) | (FEAT_TOKENS if tokens else 0)
+        check(lib().vitx_pack_feat_enable(self._h, self._feat), "vitx_pack_feat_enable")
+
+    def feat_read(self):
+        """(cls [n, D] or None, tokens: a list of per-image [gh_i, gw_i, D] arrays or None) of the last forward."""
+        if self._shapes is None:
+            raise VitxError("feat_read: no forward has run")
+        D, P = self.model.hparams.hidden_size, self.model.hparams.patch_size
+        grids = [(int(h) // P, int(w) // P) for h, w in self._shapes]
+        flags = getattr(self, "_feat", 0)
+        cls = np.empty((len(grids), D), np.float32) if flags & FEAT_CLS else None
+        tok = np.empty((sum(a * b for a, b in grids), D), np.float32) if flags & FEAT_TOKENS else None
+        fp = C.POINTER(C.c_float)
+        check(lib().vitx_pack_feat_read(self._h, cls.ctypes.data_as(fp) if cls is not None else None, tok.ctypes.data_as(fp) if tok is not None else None), "vitx_pack_feat_read")
+        if tok is None:
+            return cls, None
+        out, at = [], 0
+        for a, b in grids:
+            out.append(tok[at:at + a * b].reshape(a, b, D)); at += a * b
+        return cls, out
+
+    @property
+    def shares_weights(self) -> bool:
+        return bool(lib().vitx_pack_shares_weights(self._h))
+
+    @property
+    def scratch_bytes(self) -> int:
+        return int(lib().vitx_pack_scratch_bytes(self._h))
+
+    @property
+    def launches(self) -> Tuple[int, int]:
+        """(kernel launches, patch-embedding launches among them) of the last forward call."""
+        pe = C.c_int()
+        return int(lib().vitx_pack_launches(self._h, C.byref(pe))), pe.value
+
+
+def op_attention_packed(dtype: int, d_qkv: int, d_out: int, d_row0: int, n: int, D: int, H: int, stream: int = 0) -> None:
+    """vitx_op_attention_packed: attention over a pack, image i = rows row0[i] .. row0[i + 1] - 1 (d_row0 int32 [n + 1] on the device)."""
+    check(lib().vitx_op_attention_packed(dtype, d_qkv, d_out, d_row0, n, D, H, stream or None), "vitx_op_attention_packed")
+
+
+def op_rope_packed(dtype: int, d_qkv: int, d_cos: int, d_sin: int, d_row0: int, d_table_off: int, n: int, prefix: int, D: int, H: int, stream: int = 0) -> None:
+    """vitx_op_rope_packed: vitx_op_rope on a pack; image i's table starts d_table_off[i] floats into d_cos and d_sin."""
+    check(lib().vitx_op_rope_packed(dtype, d_qkv, 0, d_cos, d_sin, d_row0, d_table_off, n, prefix, D, H, stream or None), "vitx_op_rope_packed")
 
 
 class Group:

@@ -7,6 +7,7 @@ directory-walk accuracy harness:
     python vit_cli.py -m model.gguf (-i image.jpg | --dir DIR) --embed out.npy [--embed-kind cls|mean|tokens] [--embed-l2]   # + the embeddings
     python vit_cli.py -m model.gguf ... --img-size 384 [--pos-interp bicubic|bicubic-aa]   # run at another input size than the file's
     python vit_cli.py -m model.gguf ... --img-shape 224x448 | --img-fit 224   # a rectangular context: HxW, or the aspect-preserving shape of the input image
+    python vit_cli.py -m model.gguf -i a.jpg,b.jpg,c.jpg --pack --img-fit 224   # several images, each at its own aspect-preserving shape, in one packed forward
     python vit_cli.py -m model.gguf ... [--preprocess model|reference]   # the file's own preprocessing (default) or the reference's for any file
     python vit_cli.py -m clip.gguf -i image.jpg -k 5 --zero-shot bank.npz   # zero-shot classes of a CLIP / SigLIP file (bank: convert.py --zero-shot-out)
     python vit_cli.py -m clip.gguf -i image.jpg --text-model text.gguf --zero-shot-ids ids.npy [--zero-shot-labels labels.txt]   # the bank made by the engine, same run
@@ -91,6 +92,9 @@ def make_parser() -> argparse.ArgumentParser:
     ap.add_argument("--img-fit", type=int, default=0, metavar="SHORT",
                     help="with -i: like --img-shape, with the shape taken from the input image: its short side becomes SHORT (a multiple of the patch size), "
                          "the long side the largest multiple of the patch size that keeps the aspect (vitx_rect_shape; 500 x 375 at 224, patch 16: 288 x 224)")
+    ap.add_argument("--pack", action="store_true",
+                    help="with --img-fit SHORT and -i A.jpg,B.jpg,...: every image at its own aspect-preserving shape in ONE forward of a packed context "
+                         "(include/vitx.h \"packed batches\"); prints each image's ' > label : 0.xx' lines, image after image")
     ap.add_argument("--pos-interp", default="bicubic", choices=["bicubic", "bicubic-aa"],
                     help="with --img-size, --img-shape or --img-fit: bicubic = F.interpolate(mode='bicubic') (HuggingFace interpolate_pos_encoding, DINO); "
                          "bicubic-aa = the same with antialias=True (timm resample_abs_pos_embed)")
@@ -205,6 +209,9 @@ def main(argv: List[str] | None = None) -> int:
         ap.error("--img-size, --img-shape and --img-fit are three ways to say one thing: give one")
     if a.img_fit and a.dir is not None:
         ap.error("--img-fit takes its shape from the single image of -i, not --dir (use --img-shape HxW)")
+    if a.pack and (not a.img_fit or a.dir is not None or a.dtype == "mxfp8" or a.attn_map or a.embed or a.zero_shot or a.text_model or a.gallery or a.gallery_build
+                   or a.dense_head or a.depth_head):
+        ap.error("--pack takes --img-fit SHORT, the images of -i A.jpg,B.jpg,... and --dtype f16 or bf16; a packed context has no opt-in outputs")
     if (a.img_shape or a.img_fit) and a.preprocess == "reference":
         ap.error("--preprocess reference resizes to squares only: not with --img-shape / --img-fit")
     rect = None                                          # (img_h, img_w) of a rectangular context
@@ -302,6 +309,28 @@ def main(argv: List[str] | None = None) -> int:
         except (OSError, ValueError, KeyError) as e:
             print(f"main: failed to load the depth head from '{a.depth_head}': {e}", file=sys.stderr)
             return 1
+
+    if a.pack:
+        # several images, each at its own aspect-preserving shape, in ONE forward of a packed context; the lines of the per-image --img-fit path, image after image
+        files = [f for f in a.inp.split(",") if f]
+        try:
+            imgs = [_decode(f) for f in files]
+        except Exception as e:
+            print(f"main: failed to load an image of '{a.inp}': {e}", file=sys.stderr)
+            return 1
+        try:
+            pixels, shapes = binding.pack_images(imgs, pp_rect, a.img_fit, patch=model.hparams.patch_size)
+            tokens = int(binding.pack_check(model, shapes, 2 ** 31 - 1, len(files))[-1])
+            ctx = binding.PackContext(model, device=a.device, max_tokens=tokens, max_images=len(files), dtype=dt, pos_interp=geometry["pos_interp"])
+            probs, _ = ctx.forward_flat(pixels, shapes)
+        except binding.VitxError as e:
+            print(f"main: the packed forward failed: {e}", file=sys.stderr)
+            return 1
+        for f, (h, w), p in zip(files, shapes, probs):
+            print(f"main: '{f}' at ({w} x {h})", file=sys.stderr)
+            for i, v in zip(*binding.topk(p, a.topk)):
+                print(f" > {model.label(i)} : {v:.2f}")
+        return 0
 
     if a.dir is None:
         try:

@@ -259,6 +259,18 @@ bool attention_text_supports(int T, int D, int H);
 // v columns, prefix rows and everything behind row n_img * N untouched.  Any even head dim; 16-byte accesses where hd / 2 is a multiple of 8.
 hipError_t launch_rope(int dtype, void *qkv, long lo_off, const float *cos, const float *sin, int n_img, int N, int prefix, int D, int H, hipStream_t stream);
 bool rope_supports(int D, int H);
+// Packed batches (include/vitx.h "packed batches"): images of different token counts end to end, image i = rows row0[i] .. row0[i + 1] - 1 (device
+// int32 [n + 1]); the three kernels that must know where an image begins.
+//   attention_packed: qkv [rows][3 D] -> out [rows][D], image i's rows with the bits of launch_attention_generic on that image alone (attention_packed.hip);
+//                     qb0 [n + 1] device: the running count of 64-query blocks, qblocks = qb0[n] on the host
+//   rope_packed:      launch_rope's kernel text; image i's table ([N_i - prefix][hd / 2]) starts toff[i] floats into cos and sin; patch_rows = all patch
+//                     rows of the pack, toff_aligned = every toff[i] is a multiple of 4 (the 16-byte form needs it)
+//   pool_rows:        launch_text_pool's kernel text on absolute rows: z[i][:] = RNE(final LayerNorm of X row rows[i]); rows n .. m_pad zeros
+hipError_t launch_attention_packed(int dtype, const void *qkv, void *out, const int *row0, const int *qb0, int n, long qblocks, int D, int H, hipStream_t stream);
+bool attention_packed_supports(int D, int H);      // attention_generic_supports
+hipError_t launch_rope_packed(int dtype, void *qkv, const float *cos, const float *sin, const int *row0, const int *toff, int n, long patch_rows, bool toff_aligned, int prefix, int D,
+                              int H, hipStream_t stream);
+hipError_t launch_pool_rows(int dtype, const float *X, const int *rows, const float *w, const float *b, void *z, int n, int m_pad, int D, float eps, hipStream_t stream);
 // The gate of a gated MLP (swiglu.hip; include/vitx.h "gated MLP"): in [rows][ld_in] of `dtype`, gate in columns 0 .. F-1, up in F .. 2F-1 ->
 // out[r][j] = RNE(silu(f32 gate) * f32 up), j < F, rows of ld_out elements; nothing else of `out` is touched.  hipErrorInvalidValue, before any
 // launch, for F % 8 != 0, a pointer off a 16-byte boundary, a leading dimension that is no multiple of 8, ld_in < 2 F or ld_out < F.

@@ -193,6 +193,54 @@ int vitx_op_swiglu(int dtype, const void *d_in, long ld_in, void *d_out, long ld
     }
     return op_rc("vitx_op_swiglu", launch_swiglu(dtype, d_in, ld_in, d_out, ld_out, rows, F, (hipStream_t)stream), VITX_ERR_ARG);
 }
+// The two packed kernels on the caller's buffers (include/vitx.h "packed batches").  TEST entry points: they read the device tables back (a
+// synchronous copy) to check them -- a table that lies would send the kernel out of bounds -- and, the attention, to build the count of query blocks.
+static int read_row0(const char *name, const void *d_row0, int n, int min_rows, std::vector<int32_t> &row0) {
+    row0.resize((size_t)n + 1);
+    HIP_TRY(hipMemcpy(row0.data(), d_row0, row0.size() * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i)
+        if (row0[0] < 0 || (long)row0[i + 1] - row0[i] < min_rows) { set_error("%s: d_row0 must start at 0 or above and give every image at least %d rows (image %d)", name, min_rows, i); return VITX_ERR_ARG; }
+    return VITX_OK;
+}
+int vitx_op_attention_packed(int dtype, const void *d_qkv, void *d_out, const void *d_row0, int n, int D, int H, void *stream) {
+    if (!d_qkv || !d_out || !d_row0 || n <= 0 || D <= 0 || H <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_attention_packed: invalid argument"); return VITX_ERR_ARG; }
+    if (!attention_packed_supports(D, H)) { set_error("vitx_op_attention_packed: head_dim must be a multiple of 8 up to 128 (D %d, H %d)", D, H); return VITX_ERR_UNSUPPORTED; }
+    std::vector<int32_t> row0, qb0((size_t)n + 1);
+    if (const int rc = read_row0("vitx_op_attention_packed", d_row0, n, 1, row0)) return rc;
+    long qblocks = 0;
+    for (int i = 0; i < n; ++i) { qb0[i] = (int32_t)qblocks; qblocks += (row0[i + 1] - row0[i] + 63) / 64; }
+    qb0[n] = (int32_t)qblocks;
+    int *d_qb0 = nullptr;
+    HIP_TRY(hipMalloc((void **)&d_qb0, qb0.size() * 4));
+    const DevMem qb_own(d_qb0);
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemcpy(d_qb0, qb0.data(), qb0.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_attention_packed(dtype, d_qkv, d_out, (const int *)d_row0, d_qb0, n, qblocks, D, H, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);       // d_qb0 is freed on return
+    return op_rc("vitx_op_attention_packed", e, VITX_ERR_UNSUPPORTED);
+}
+// The same launch on tables the caller has built and vouches for (d_qb0 [n + 1]: the running count of 64-query blocks; qblocks = d_qb0[n]): only
+// enqueues, reads nothing back -- what a packed context does per layer, and what tools/pack_cost.py times.
+int vitx_op_attention_packed_tables(int dtype, const void *d_qkv, void *d_out, const void *d_row0, const void *d_qb0, int n, long qblocks, int D, int H, void *stream) {
+    if (!d_qkv || !d_out || !d_row0 || !d_qb0 || n <= 0 || qblocks < n || D <= 0 || H <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_attention_packed_tables: invalid argument"); return VITX_ERR_ARG; }
+    return op_rc("vitx_op_attention_packed_tables", launch_attention_packed(dtype, d_qkv, d_out, (const int *)d_row0, (const int *)d_qb0, n, qblocks, D, H, (hipStream_t)stream), VITX_ERR_UNSUPPORTED);
+}
+int vitx_op_rope_packed(int dtype, void *d_qkv, long lo_off, const void *d_cos, const void *d_sin, const void *d_row0, const void *d_table_off, int n, int prefix, int D, int H, void *stream) {
+    if (!d_qkv || !d_cos || !d_sin || !d_row0 || !d_table_off || n <= 0 || D <= 0 || H <= 0 || prefix < 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_rope_packed: invalid argument"); return VITX_ERR_ARG; }
+    if (lo_off) { set_error("vitx_op_rope_packed: a pack has one operand plane (lo_off must be 0)"); return VITX_ERR_ARG; }
+    if ((uintptr_t)d_qkv % 2 || (uintptr_t)d_cos % 4 || (uintptr_t)d_sin % 4) { set_error("vitx_op_rope_packed: misaligned pointer"); return VITX_ERR_ARG; }
+    if (!rope_supports(D, H)) { set_error("vitx_op_rope_packed: D must be a multiple of H and the head dim even (D %d, H %d)", D, H); return VITX_ERR_UNSUPPORTED; }
+    std::vector<int32_t> row0, toff((size_t)n);
+    if (const int rc = read_row0("vitx_op_rope_packed", d_row0, n, std::max(prefix, 1), row0)) return rc;
+    HIP_TRY(hipMemcpy(toff.data(), d_table_off, toff.size() * 4, hipMemcpyDeviceToHost));
+    bool aligned = true;
+    for (int i = 0; i < n; ++i) {
+        if (toff[i] < 0) { set_error("vitx_op_rope_packed: d_table_off[%d] is negative", i); return VITX_ERR_ARG; }
+        aligned = aligned && toff[i] % 4 == 0;
+    }
+    return op_rc("vitx_op_rope_packed", launch_rope_packed(dtype, d_qkv, (const float *)d_cos, (const float *)d_sin, (const int *)d_row0, (const int *)d_table_off, n,
+                                                           (long)row0[n] - row0[0] - (long)n * prefix, aligned, prefix, D, H, (hipStream_t)stream), VITX_ERR_UNSUPPORTED);
+}
 // The parity mode's attention on f32 q, k, v (what the reference multiplies, vit.cpp:848,858): splits the rows into the two fp16 planes the
 // QKV GEMM's EPI_BIAS_HILO epilogue emits, then runs the precise streaming kernel.  Synchronous (allocates its own scratch).
 int vitx_op_attention_f32(const float *qkv_f32, void *out, int n_img, int N, int D, int H, void *stream) {

@@ -9,6 +9,9 @@
 // A streaming pass: one thread owns VEC consecutive j of a head's first half and the matching VEC of its second half -- VEC = 8: 16-byte loads and
 // stores of the operands, the table rows as f32x4 (the table is a few hundred KB at most and stays in cache); VEC = 1: head dims whose half is no
 // multiple of 8.  No LDS, no atomics; every element has exactly one writer, so an image's bits depend on nothing but its own rows.
+// PACKED (launch_rope_packed; include/vitx.h "packed batches"): the same kernel text on a pack of images of different grids laid end to end,
+// image i = rows row0[i] .. row0[i + 1] - 1 with `prefix` rows in front of its patches; its table starts toff[i] floats into cs and sn (one arena
+// each).  Patch row q of the pack belongs to the last image with row0[i] - row0[0] - i prefix <= q: a binary search per thread.
 #include "device_common.h"
 #include "kernels.h"
 
@@ -18,9 +21,9 @@ namespace {
 
 template <typename T, int VEC> struct RopeVec { T e[VEC]; };
 
-template <typename T, int VEC, bool PLANES>
+template <typename T, int VEC, bool PLANES, bool PACKED>
 __global__ __launch_bounds__(256) void rope_kernel(T *__restrict__ qkv, long lo_off, const float *__restrict__ cs, const float *__restrict__ sn, long units, int N, int prefix,
-                                                   int D, int hd) {
+                                                   int D, int hd, const int *__restrict__ row0, const int *__restrict__ toff, int n) {
     typedef RopeVec<T, VEC> __attribute__((aligned(VEC * 2))) V;
     const int half = hd >> 1, uph = half / VEC, ups = (D >> 1) / VEC;      // units per head half, per q (or k) of a row
     const long gi = (long)blockIdx.x * 256 + threadIdx.x;
@@ -28,15 +31,27 @@ __global__ __launch_bounds__(256) void rope_kernel(T *__restrict__ qkv, long lo_
     const int P = N - prefix;
     long pr, img;                                                         // patch row over all images, its image
     int w, p;                                                             // unit within the row, patch within the image
-    if (units <= 0x7fffffffL) {                                           // (uniform) 32-bit divisions wherever the launch allows them
+    long row, tab = 0;                                                    // the token row in qkv; the image's table offset
+    if constexpr (PACKED) {
+        pr = gi / (2 * ups); w = (int)(gi - pr * (2 * ups));
+        const long first = row0[0];                                       // patch rows in front of image i: row0[i] - first - i prefix
+        int lo = 0, hi = n;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if ((long)row0[mid] - first - (long)mid * prefix <= pr) lo = mid; else hi = mid;
+        }
+        img = lo; p = (int)(pr - ((long)row0[lo] - first - (long)lo * prefix));
+        row = (long)row0[lo] + prefix + p; tab = toff[lo];
+    } else if (units <= 0x7fffffffL) {                                           // (uniform) 32-bit divisions wherever the launch allows them
         const unsigned g = (unsigned)gi, q = g / (unsigned)(2 * ups), i = q / (unsigned)P;
         pr = q; w = (int)(g - q * (unsigned)(2 * ups)); img = i; p = (int)(q - i * (unsigned)P);
     } else {
         pr = gi / (2 * ups); w = (int)(gi - pr * (2 * ups)); img = pr / P; p = (int)(pr - img * P);
     }
+    if constexpr (!PACKED) row = img * N + prefix + p;
     const int s = w / ups, x = w - s * ups, h = x / uph, j0 = (x - h * uph) * VEC;
-    T *pa = qkv + ((size_t)(img * N + prefix + p) * 3 + s) * D + h * hd + j0, *pb = pa + half;
-    const float *pc = cs + (size_t)p * half + j0, *ps = sn + (size_t)p * half + j0;
+    T *pa = qkv + ((size_t)row * 3 + s) * D + h * hd + j0, *pb = pa + half;
+    const float *pc = cs + tab + (size_t)p * half + j0, *ps = sn + tab + (size_t)p * half + j0;
     float a[VEC], b[VEC], c[VEC], t[VEC];
     {
         const V va = *(const V *)pa, vb = *(const V *)pb;
@@ -74,9 +89,16 @@ template <typename T, int VEC>
 hipError_t launch_rope_t(void *qkv, long lo_off, const float *cs, const float *sn, long units, int N, int prefix, int D, int hd, hipStream_t stream) {
     const dim3 grid((unsigned)((units + 255) / 256)), blk(256);
     if constexpr (std::is_same<T, _Float16>::value) {
-        if (lo_off) { hipLaunchKernelGGL((rope_kernel<T, VEC, true>), grid, blk, 0, stream, (T *)qkv, lo_off, cs, sn, units, N, prefix, D, hd); return hipGetLastError(); }
+        if (lo_off) { hipLaunchKernelGGL((rope_kernel<T, VEC, true, false>), grid, blk, 0, stream, (T *)qkv, lo_off, cs, sn, units, N, prefix, D, hd, nullptr, nullptr, 0); return hipGetLastError(); }
     }
-    hipLaunchKernelGGL((rope_kernel<T, VEC, false>), grid, blk, 0, stream, (T *)qkv, 0L, cs, sn, units, N, prefix, D, hd);
+    hipLaunchKernelGGL((rope_kernel<T, VEC, false, false>), grid, blk, 0, stream, (T *)qkv, 0L, cs, sn, units, N, prefix, D, hd, nullptr, nullptr, 0);
+    return hipGetLastError();
+}
+// the packed form: one operand plane (a packed context has no parity planes)
+template <typename T, int VEC>
+hipError_t launch_rope_packed_t(void *qkv, const float *cs, const float *sn, long units, int prefix, int D, int hd, const int *row0, const int *toff, int n, hipStream_t stream) {
+    const dim3 grid((unsigned)((units + 255) / 256)), blk(256);
+    hipLaunchKernelGGL((rope_kernel<T, VEC, false, true>), grid, blk, 0, stream, (T *)qkv, 0L, cs, sn, units, 0, prefix, D, hd, row0, toff, n);
     return hipGetLastError();
 }
 
@@ -94,6 +116,19 @@ hipError_t launch_rope(int dtype, void *qkv, long lo_off, const float *cs, const
     if (units > 0x7fffffffL * 256) return hipErrorInvalidValue;
     if (wide) return VITX_BY_DTYPE2(dtype, launch_rope_t, 8, qkv, lo_off, cs, sn, units, N, prefix, D, hd, stream);
     return VITX_BY_DTYPE2(dtype, launch_rope_t, 1, qkv, lo_off, cs, sn, units, N, prefix, D, hd, stream);
+}
+
+// patch_rows = row0[n] - row0[0] - n * prefix, toff_aligned = every toff[i] is a multiple of 4 floats: both known to the caller, who built the tables
+hipError_t launch_rope_packed(int dtype, void *qkv, const float *cs, const float *sn, const int *row0, const int *toff, int n, long patch_rows, bool toff_aligned, int prefix, int D,
+                              int H, hipStream_t stream) {
+    if (!rope_supports(D, H) || n <= 0 || prefix < 0 || patch_rows < 0 || !row0 || !toff) return hipErrorInvalidValue;
+    if (patch_rows == 0) return hipSuccess;
+    const int hd = D / H;
+    const bool wide = (hd / 2) % 8 == 0 && (uintptr_t)qkv % 16 == 0 && (uintptr_t)cs % 16 == 0 && (uintptr_t)sn % 16 == 0 && toff_aligned;
+    const long units = patch_rows * (wide ? D / 8 : D);
+    if (units > 0x7fffffffL * 256) return hipErrorInvalidValue;
+    if (wide) return VITX_BY_DTYPE2(dtype, launch_rope_packed_t, 8, qkv, cs, sn, units, prefix, D, hd, row0, toff, n, stream);
+    return VITX_BY_DTYPE2(dtype, launch_rope_packed_t, 1, qkv, cs, sn, units, prefix, D, hd, row0, toff, n, stream);
 }
 
 }  // namespace vitx

@@ -2,6 +2,7 @@
 //   text_embed_kernel   X[i][t][:] = f32(tok[ids[i][t]][:]) + pos[t][:]: one f32 add per element, the table held as filed (f16 or f32);
 //   text_pool_kernel    the pooled row of every prompt through the final LayerNorm (LnRow: the project's one row definition), rounded to the
 //                       operand type: the head GEMM's A rows; rows n .. m_pad are written as zeros (the GEMM multiplies whole row tiles);
+//                       launch_pool_rows is the same kernel on absolute row indices (the class rows of a packed context);
 // (VITX_TEXT_L2 is zs_embed_kernel's f32 instantiation, zeroshot.hip.)
 // No atomics; a prompt's bits depend on its own ids only.
 #include "device_common.h"
@@ -77,6 +78,11 @@ static hipError_t launch_text_pool_t(const float *X, const int *pooled, const fl
 hipError_t launch_text_pool(int dtype, const float *X, const int *pooled, const float *w, const float *b, void *z, int n, int m_pad, int T, int D, float eps, hipStream_t stream) {
     if (n <= 0 || m_pad < n || T <= 0) return hipErrorInvalidValue;
     return VITX_BY_DTYPE(dtype, launch_text_pool_t, X, pooled, w, b, z, n, m_pad, T, D, eps, stream);
+}
+// the same kernel with absolute row indices (T = 0: row i * 0 + rows[i]): the class rows of a packed context
+hipError_t launch_pool_rows(int dtype, const float *X, const int *rows, const float *w, const float *b, void *z, int n, int m_pad, int D, float eps, hipStream_t stream) {
+    if (n <= 0 || m_pad < n) return hipErrorInvalidValue;
+    return VITX_BY_DTYPE(dtype, launch_text_pool_t, X, rows, w, b, z, n, m_pad, 0, D, eps, stream);
 }
 
 }  // namespace vitx

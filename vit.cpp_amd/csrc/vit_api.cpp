@@ -5,7 +5,7 @@
 #include <stdlib.h>
 
 vit_model::~vit_model() { vitx_model_free(handle); }
-vit_state::~vit_state() { vitx_ctx_free(ctx); }
+vit_state::~vit_state() { vitx_ctx_free(ctx); vitx_pack_free(pack); }
 vit_text_state::~vit_text_state() { vitx_text_free(ctx); }
 
 // vit.cpp:109-127 -- false + message on stderr when the file cannot be read or decoded
@@ -159,6 +159,48 @@ int vit_predict_batch(const vit_model &model, vit_state &state, const image_f32 
             for (int i = 0; i < params.topk && i < (int)p.size(); ++i)                                        // vit.cpp:1062-1067
                 printf(" > %s : %.2f\n", model.hparams.id2label.at(p[i].second).c_str(), p[i].first);
         }
+    }
+    return 0;
+}
+
+// No counterpart in the reference: images of different shapes in one forward of a packed context (include/vitx.h "packed batches")
+int vit_pack_batch(const vit_model &model, vit_state &state, const image_f32 *imgs, int n, std::vector<std::vector<std::pair<float, int>>> &predictions) {
+    predictions.clear();
+    if (!model.handle || !imgs || n <= 0) { fprintf(stderr, "%s: invalid argument\n", __func__); return 1; }
+    std::vector<int32_t> shapes((size_t)2 * n), row0((size_t)n + 1);
+    size_t floats = 0;
+    for (int i = 0; i < n; ++i) {
+        if (imgs[i].nx <= 0 || imgs[i].ny <= 0 || imgs[i].data.size() != (size_t)3 * imgs[i].nx * imgs[i].ny) { fprintf(stderr, "%s: image %d does not hold nx * ny * 3 floats\n", __func__, i); return 1; }
+        shapes[2 * i] = imgs[i].ny; shapes[2 * i + 1] = imgs[i].nx;
+        floats += imgs[i].data.size();
+    }
+    if (vitx_pack_check(model.handle, shapes.data(), n, 0x7fffffff, n, row0.data()) != VITX_OK) { fprintf(stderr, "%s: %s\n", __func__, vitx_last_error()); return 1; }
+    const bool fits = state.pack && state.pack_model_uid == vitx_model_uid(model.handle) && state.pack_tokens >= row0[n] && state.pack_images >= n &&
+                      state.pack_dtype == state.dtype && state.pack_pos_interp == state.pos_interp;
+    if (!fits) {
+        vitx_pack_free(state.pack); state.pack = nullptr;
+        vitx_pack_options opt{};
+        opt.pos_interp = state.pos_interp;
+        state.pack_tokens = std::max(state.pack_tokens, (int)row0[n]); state.pack_images = std::max(state.pack_images, n);
+        if (vitx_pack_create(model.handle, state.device, state.pack_tokens, state.pack_images, state.dtype, &opt, &state.pack) != VITX_OK) {
+            fprintf(stderr, "%s: failed to create the packed context: %s\n", __func__, vitx_last_error());
+            state.pack_tokens = state.pack_images = 0;
+            return 1;
+        }
+        state.pack_model_uid = vitx_model_uid(model.handle); state.pack_dtype = state.dtype; state.pack_pos_interp = state.pos_interp;
+    }
+    std::vector<float> pixels;
+    pixels.reserve(floats);
+    for (int i = 0; i < n; ++i) pixels.insert(pixels.end(), imgs[i].data.begin(), imgs[i].data.end());
+    const int C = model.hparams.num_classes;
+    state.prediction.resize((size_t)n * C);
+    if (vitx_pack_forward(state.pack, pixels.data(), shapes.data(), n, state.prediction.data(), nullptr) != VITX_OK) { fprintf(stderr, "%s: failed to encode the pack: %s\n", __func__, vitx_last_error()); return 1; }
+    predictions.resize(n);
+    for (int b = 0; b < n; ++b) {
+        auto &p = predictions[b];
+        p.reserve(C);
+        for (int i = 0; i < C; ++i) p.push_back(std::make_pair(state.prediction[(size_t)b * C + i], i));
+        std::sort(p.begin(), p.end(), [](const std::pair<float, int> &a, const std::pair<float, int> &b2) { return a.first > b2.first; });
     }
     return 0;
 }

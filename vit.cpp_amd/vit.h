@@ -71,6 +71,9 @@ struct vit_state {                        // vit.h:72-80: per-caller mutable scr
     int pos_interp = VITX_POS_BICUBIC;    // enum vitx_pos_interp: which bicubic convention resamples the table (include/vitx.h)
     int ctx_pos_interp = 0;               // the pos_interp `ctx` was created with
     std::vector<float> prediction;        // class probabilities of the last call ([n][num_classes])
+    vitx_pack *pack = nullptr;            // the packed context of vit_pack_batch, created lazily on `device` with `dtype` and `pos_interp`; grown on demand
+    uint64_t pack_model_uid = 0;
+    int pack_tokens = 0, pack_images = 0, pack_dtype = 0, pack_pos_interp = 0;      // what `pack` was created with
     vit_state() = default;
     vit_state(const vit_state &) = delete;
     vit_state &operator=(const vit_state &) = delete;
@@ -105,6 +108,11 @@ int vit_predict(const vit_model &model, vit_state &state, const image_f32 img1, 
                 std::vector<std::pair<float, int>> &predictions);                                      // vit.h:122
 int vit_predict_batch(const vit_model &model, vit_state &state, const image_f32 *imgs, int n, const vit_params &params,
                       std::vector<std::vector<std::pair<float, int>>> &predictions, bool print = false);
+// NEW, no counterpart in the reference: n preprocessed images, each of its OWN shape (vit_image_preprocess_rect at any w x h that are multiples of the
+// patch size), in ONE forward of a packed context (include/vitx.h "packed batches"; VITX_F16 is plain fp16 there).  predictions[i] = image i's class
+// probabilities, sorted as vit_predict_batch sorts them; state.prediction holds them unsorted.  An image's result does not depend on the others.
+// state.img_size / img_h / img_w are not consulted.  0 ok / 1 failure.
+int vit_pack_batch(const vit_model &model, vit_state &state, const image_f32 *imgs, int n, std::vector<std::vector<std::pair<float, int>>> &predictions);
 // NEW, no counterpart in the reference: the embeddings of n preprocessed images -- the f32 final-norm features of the last layer
 // (include/vitx.h, "image embeddings and token features").  flags = VITX_FEAT_CLS, VITX_FEAT_MEAN, VITX_FEAT_TOKENS, optionally | VITX_FEAT_L2;
 // out[i] = image i's floats in the order [cls D][mean D][tokens (N-T) * D] (the selected parts; T = 1 + the model's register tokens, 0 for a model with the attention-pooling head, whose cls part is the pooled embedding).  state.prediction holds the class
