@@ -290,6 +290,7 @@ int vitx_vitstr_decode(const float *probs, int seq_len, int num_classes, int32_t
  * internal HIP streams; the cut is placed where the GEMM tile counts of both parts fill whole
  * rounds of CUs (110 + 146 for 256 ViT-B images on 256 CUs).
  * Results do not depend on the split: images are independent in every kernel.
+ * A non-finite value (NaN, Inf) in one image stays in that image's outputs: its batch neighbours keep the bits of a batch without it.
  * The library reads NO environment variable: everything tunable is in vitx_ctx_options. */
 int vitx_ctx_create(const vitx_model *m, int device, int max_batch, int dtype, vitx_ctx **out);
 /* Options of a context; every field 0 = the default.  Set struct_size = sizeof(vitx_ctx_options) (lets the struct grow).

@@ -19,9 +19,10 @@ namespace vitx {
 //     i of keys 0..3, which is the k-slot order of the P registers -- tools/tr_probe.hip prints the mapping);
 //   * 32 KiB of LDS and <= 128 VGPRs: four workgroups = 16 waves per CU, so the MFMA work of one wave runs under the VALU work
 //     of the others (the single-pass kernel holds every score in registers: one wave per SIMD at 577 tokens).
-// Pass 1 streams K for the row maxima, pass 2 streams K and V.  Keys past N inside the last chunk read the next image's rows
-// (finite values; their scores are masked to -inf and their probabilities are exactly 0) or, past the end of the tensor, the
-// zeros a buffer load returns out of range.
+// Pass 1 streams K for the row maxima, pass 2 streams K and V.  Keys past N inside the last chunk are never fetched: the buffer
+// descriptor of the K / V DMA ends at the last row of the item's image, so they arrive as the zeros a buffer load returns out of range,
+// whatever the next image holds (their scores are masked to -inf and their probabilities are exactly 0, but 0 . NaN and 0 . Inf are NaN
+// in the PV product: tests/test_gpu_poison.py).
 // ------------------------------------------------------------------------------------------------
 // ONLINE (r04, bf16 only): ONE pass.  The reference's softmax goes through fp16 tables relative to the TRUE row maximum, which is why the F16
 // builds take the maximum first; bf16 has no rounding point of the reference to reproduce there, and softmax is invariant under the per-row
@@ -31,7 +32,7 @@ namespace vitx {
 // during the first chunks only -- and then the accumulators and the running sum of every lane are rescaled by exp2 of its own shift.
 // Rounding: P is rounded to bf16 at whatever scale it has (a relative rounding), O / sum once at the end, as before.
 template <typename T, int FLAGS, bool ONLINE = false>      // FLAGS: ablation builds of tools/attn_bench.py (1 no re-staging, 2 no barriers, 4 no exp/convert, 8 no PV, 16 no pass 1); 0 = product
-__global__ __launch_bounds__(256, 4) void attention_flow_kernel(const T *__restrict__ qkv, T *__restrict__ out, int N, int D, int H, int qblocks, int items, int n_img) {
+__global__ __launch_bounds__(256, 4) void attention_flow_kernel(const T *__restrict__ qkv, T *__restrict__ out, int N, int D, int H, int qblocks, int items) {
     static_assert(!ONLINE || std::is_same<T, __bf16>::value, "the running-maximum schedule is the bf16 build's");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int CK = 64, KBYTES = CK * 128, VBYTES = CK * 128, BUF = KBYTES + VBYTES;
@@ -59,7 +60,7 @@ __global__ __launch_bounds__(256, 4) void attention_flow_kernel(const T *__restr
     }
 
     // ---- LDS-DMA: physical 16-B piece p = it*256 + tid of a chunk image <-> (key row, 16-B slot) of the K / V column block
-    const unsigned remaining = (unsigned)min((size_t)0xf0000000u, ((size_t)(n_img - b) * N * 3 * D - h * 64) * 2);
+    const unsigned remaining = (unsigned)min((size_t)0xf0000000u, ((size_t)N * 3 * D - h * 64) * 2);      // from this head's column block to the end of the IMAGE
     __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, (int)remaining, 0x00020000);
     int koff[2], voff[2];
 #pragma unroll
@@ -246,7 +247,7 @@ static hipError_t launch_attention_flow_inst(const void *qkv, void *out, int n_i
     if (prepare) return hipFuncSetAttribute((const void *)attention_flow_kernel<T, FLAGS, ONLINE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);   // device bring-up
     const int qblocks = ((N + 31) / 32 + 3) / 4, items = n_img * H;
     const int grid = ((items + 7) / 8) * 8 * qblocks;
-    hipLaunchKernelGGL((attention_flow_kernel<T, FLAGS, ONLINE>), dim3(grid), dim3(256), lds, stream, (const T *)qkv, (T *)out, N, D, H, qblocks, items, n_img);
+    hipLaunchKernelGGL((attention_flow_kernel<T, FLAGS, ONLINE>), dim3(grid), dim3(256), lds, stream, (const T *)qkv, (T *)out, N, D, H, qblocks, items);
     return hipGetLastError();
 }
 template <typename T>

@@ -42,14 +42,16 @@ namespace vitx {
 //   * one barrier per item; vector-memory operations retire in issue order, so the wait in front of it counts what was issued AFTER
 //     the loads it needs: the DMA pieces of item i + 2 and this item's stores stay in flight.
 // exp follows AttnExp<T> (device_common.h): F16 = ggml_soft_max's table semantics, BF16 = one f32 exp2 per key.
-// Keys N .. 16 NT16V - 1 read the next image's rows (finite; masked to -inf) or the zeros a buffer load returns out of range.
+// Keys N .. 16 NT16V - 1 are never fetched: an item's K / V DMA goes through a buffer descriptor that ends at the last row of the item's image,
+// so the rows behind it arrive as the zeros a buffer load returns out of range, whatever the next image holds (a masked key has probability
+// exactly 0, but 0 . NaN and 0 . Inf are NaN in the PV product: tests/test_gpu_poison.py).
 // ------------------------------------------------------------------------------------------------
 // QT = 1 for a wave that computes, 0 for one that only moves data; NT16V = 16-key tiles that hold a real key (13 for 193..208 tokens,
 // 14 above).  FLAGS: 0 in the product; ablation builds under -DVITX_LAB only (tools/attn_bench.py, garbage results by design): 1 = no
 // softmax arithmetic, 2 = no K / V DMA after the first items, 4 = no output stores, 8 = no QK^T products, 16 = no PV products, 32 = no Q
 // loads, 64 = shader-clock stamps per phase behind the output rows.
 template <typename T, int NT16V, int QT, int FLAGS>
-__device__ __forceinline__ void attention_persist_loop(const T *__restrict__ qkv, T *__restrict__ out, char *smem, int N, int D, int H, int items, unsigned total_bytes, unsigned out_bytes) {
+__device__ __forceinline__ void attention_persist_loop(const T *__restrict__ qkv, T *__restrict__ out, char *smem, int N, int D, int H, int items, unsigned out_bytes) {
     constexpr int NROW = NT16V * 16, KB = NROW * 128, BUF = 2 * KB;    // one item: K image + V image
     constexpr int NBUF = NT16V <= 13 ? 3 : 2, AHEAD = NBUF - 1;         // ring of item buffers, items requested ahead
     constexpr int NTHR = 1024, PIECES = NROW * 8, OPS = (PIECES + NTHR - 1) / NTHR;   // 16-byte pieces per image, DMA instructions per thread and image
@@ -66,7 +68,6 @@ __device__ __forceinline__ void attention_persist_loop(const T *__restrict__ qkv
     const int row_bytes = 3 * D * 2;
     const bool second = NTHR + wave * 64 < PIECES;      // wave-uniform: this wave also issues the second (partial) DMA instruction of an image
 
-    __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)qkv, 0, (int)total_bytes, 0x00020000);
     __amdgpu_buffer_rsrc_t rsrc_o = __builtin_amdgcn_make_buffer_rsrc((void *)out, 0, (int)out_bytes, 0x00020000);
     // bytes (< 4 GiB: launcher) -- UNSIGNED: as an int it went negative beyond 2 GiB and load_q's pointer arithmetic sign-extended it (r04: wrong
     // results from 2366 ViT-B images per launch on, a fault beyond; found by the chunked-launch test)
@@ -82,6 +83,9 @@ __device__ __forceinline__ void attention_persist_loop(const T *__restrict__ qkv
     }
     auto stage = [&](int item, char *buf) {
         const int so = __builtin_amdgcn_readfirstlane((int)item_base(item));          // the buffer unit takes the SGPR offset as 32 unsigned bits
+        // the descriptor ENDS with the item's image: rows N .. NROW - 1 of the item are out of range and land as zeros
+        const int end = __builtin_amdgcn_readfirstlane((int)((unsigned)(item / H + 1) * (unsigned)(N * row_bytes)));
+        __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)qkv, 0, end, 0x00020000);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)(buf + wave * 1024), 16, koff0, so, 0, ATT_AUX);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)(buf + KB + wave * 1024), 16, voff0, so, 0, ATT_AUX);
         if (second) {
@@ -312,13 +316,13 @@ __device__ __forceinline__ void attention_persist_loop(const T *__restrict__ qkv
 }
 
 template <typename T, int NT16V, int FLAGS = 0>
-__global__ __launch_bounds__(1024) void attention_persist_kernel(const T *__restrict__ qkv, T *__restrict__ out, int N, int D, int H, int items, unsigned total_bytes, unsigned out_bytes) {
+__global__ __launch_bounds__(1024) void attention_persist_kernel(const T *__restrict__ qkv, T *__restrict__ out, int N, int D, int H, int items, unsigned out_bytes) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if ((int)blockIdx.x >= items) return;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // every wave runs the same number of items and barriers, whichever build of the loop it takes
-    if (wave < NT16V) attention_persist_loop<T, NT16V, 1, FLAGS>(qkv, out, smem, N, D, H, items, total_bytes, out_bytes);
-    else attention_persist_loop<T, NT16V, 0, FLAGS>(qkv, out, smem, N, D, H, items, total_bytes, out_bytes);
+    if (wave < NT16V) attention_persist_loop<T, NT16V, 1, FLAGS>(qkv, out, smem, N, D, H, items, out_bytes);
+    else attention_persist_loop<T, NT16V, 0, FLAGS>(qkv, out, smem, N, D, H, items, out_bytes);
 }
 template <int NT16V> constexpr int attention_persist_lds() { return (NT16V <= 13 ? 3 : 2) * 2 * NT16V * 16 * 128; }      // 156 KiB / 112 KiB
 template <typename T>
@@ -337,14 +341,14 @@ static hipError_t launch_attention_persist_t(const void *qkv, void *out, int n_i
     const int grid = (items + rounds - 1) / rounds;
 #ifdef VITX_LAB
 #define VITX_PERSIST_LAB(F) case F: { static bool once = false; if (!once) { once = true; (void)hipFuncSetAttribute((const void *)attention_persist_kernel<T, 13, F>, hipFuncAttributeMaxDynamicSharedMemorySize, attention_persist_lds<13>()); } \
-        hipLaunchKernelGGL((attention_persist_kernel<T, 13, F>), dim3(grid), dim3(1024), attention_persist_lds<13>(), stream, (const T *)qkv, (T *)out, N, D, H, items, (unsigned)total, (unsigned)(total / 3)); return hipGetLastError(); }
+        hipLaunchKernelGGL((attention_persist_kernel<T, 13, F>), dim3(grid), dim3(1024), attention_persist_lds<13>(), stream, (const T *)qkv, (T *)out, N, D, H, items, (unsigned)(total / 3)); return hipGetLastError(); }
     if (flags && N <= 208) switch (flags) {
         VITX_PERSIST_LAB(1) VITX_PERSIST_LAB(2) VITX_PERSIST_LAB(4) VITX_PERSIST_LAB(8) VITX_PERSIST_LAB(16) VITX_PERSIST_LAB(32) VITX_PERSIST_LAB(25) VITX_PERSIST_LAB(38) VITX_PERSIST_LAB(64)
         default: return hipErrorInvalidValue; }
 #undef VITX_PERSIST_LAB
 #endif
-    if (N <= 208) hipLaunchKernelGGL((attention_persist_kernel<T, 13>), dim3(grid), dim3(1024), attention_persist_lds<13>(), stream, (const T *)qkv, (T *)out, N, D, H, items, (unsigned)total, (unsigned)(total / 3));
-    else hipLaunchKernelGGL((attention_persist_kernel<T, 14>), dim3(grid), dim3(1024), attention_persist_lds<14>(), stream, (const T *)qkv, (T *)out, N, D, H, items, (unsigned)total, (unsigned)(total / 3));
+    if (N <= 208) hipLaunchKernelGGL((attention_persist_kernel<T, 13>), dim3(grid), dim3(1024), attention_persist_lds<13>(), stream, (const T *)qkv, (T *)out, N, D, H, items, (unsigned)(total / 3));
+    else hipLaunchKernelGGL((attention_persist_kernel<T, 14>), dim3(grid), dim3(1024), attention_persist_lds<14>(), stream, (const T *)qkv, (T *)out, N, D, H, items, (unsigned)(total / 3));
     return hipGetLastError();
 }
 

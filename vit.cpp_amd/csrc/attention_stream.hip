@@ -17,8 +17,9 @@
 // Every build claims the whole register file of its SIMDs (AS_CLAIM below): a foreign wave beside this MFMA stream computed wrong DPP sums.
 // Both: pass 1 streams K for the row maxima of the raw scores, pass 2 streams K and V: e = AttnExp<T>(s, max) (F16: ggml_soft_max's
 // table semantics), row sum of the rounded numerators, O^T = V^T . P^T, O / sum rounded once to the operand type.
-// Keys past N inside the last chunk read the next image's rows (finite; masked to -inf, probability exactly 0) or the zeros a buffer
-// load returns out of range.
+// Keys past N inside the last chunk are never fetched: the buffer descriptors end at the last row of the item's image, so those rows arrive
+// as the zeros a buffer load returns out of range, whatever the next image holds (masked to -inf, probability exactly 0 -- but 0 . NaN and
+// 0 . Inf are NaN in the PV product: tests/test_gpu_poison.py).
 #include <type_traits>
 
 #include "device_common.h"
@@ -99,7 +100,7 @@ template <int CNT> __device__ __forceinline__ void wait_lgkm8(s4 &a, s4 &b, s4 &
 }  // namespace as
 
 template <typename T, int QT, bool PREC, int W, int NSLOT>
-__global__ __launch_bounds__(W * 64, W == 16 ? 4 : 2) void attention_stream_kernel(const T *__restrict__ qkv, T *__restrict__ out, int N, int D, int H, int items, int qblocks, int n_img, long lo_off) {
+__global__ __launch_bounds__(W * 64, W == 16 ? 4 : 2) void attention_stream_kernel(const T *__restrict__ qkv, T *__restrict__ out, int N, int D, int H, int items, int qblocks, long lo_off) {
     using namespace as;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // a plane image is 512 pieces of 16 bytes: moved by the first DT = min(NT, 512) threads, OPS pieces each (waves past them only compute)
@@ -133,7 +134,7 @@ __global__ __launch_bounds__(W * 64, W == 16 ? 4 : 2) void attention_stream_kern
     const int nch = (N + CK - 1) / CK, nstage = 2 * nch;
 
     // ---- LDS-DMA: physical 16-B piece tid of a plane image <-> (key row, 16-B piece) of the K / V column block of this head
-    const unsigned remaining = (unsigned)min((size_t)0xf0000000u, ((size_t)(n_img - b) * N * 3 * D - h * 64) * 2);
+    const unsigned remaining = (unsigned)min((size_t)0xf0000000u, ((size_t)N * 3 * D - h * 64) * 2);      // from this head's column block to the end of the IMAGE
     __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, (int)remaining, 0x00020000);
     __amdgpu_buffer_rsrc_t rsrc_lo = __builtin_amdgcn_make_buffer_rsrc((void *)(base + (PREC ? lo_off : 0)), 0, (int)remaining, 0x00020000);
     int koff[2], voff[2];           // (fixed bound, OPS <= 2: hipcc 7.2 silently drops the host-side instantiation of a kernel whose lambda captures an array sized by a constexpr LOCAL that depends on a template parameter)
@@ -534,8 +535,8 @@ __global__ __launch_bounds__(W * 64, W == 16 ? 4 : 2) void attention_stream_kern
 //     (the Q region is free once every wave has taken its fragments in step 0).  The counted wait in front of a barrier names exactly the
 //     operations younger than the chunk the next step reads (wait_cnt below) -- four to eight stay in flight across every barrier;
 //   * the item's output (two 16-byte stores per lane) is issued at the end of step 7 and counted the same way.
-// Keys past N: chunk rows beyond the item are the next item's rows or the zeros a buffer load returns out of range -- finite; their scores are
-// masked to -inf (probability exactly 0).
+// Keys past N: the fourth chunk of an operand goes through a descriptor that ends at the last row of the item's image, so its rows N .. 255 are
+// the zeros a buffer load returns out of range, whatever the next image holds; their scores are masked to -inf (probability exactly 0).
 // ------------------------------------------------------------------------------------------------
 template <int RES>
 __global__ __launch_bounds__(1024, 4) void attention_precise_kernel(const _Float16 *__restrict__ qkv, _Float16 *__restrict__ out, int N, int D, int H, int items, unsigned plane_bytes, long lo_off) {
@@ -571,26 +572,27 @@ __global__ __launch_bounds__(1024, 4) void attention_precise_kernel(const _Float
     // (readfirstlane: the division runs on the VALU; its result must not sit in a vector register for the length of an item)
     auto item_base = [&](int item) -> unsigned { const int b = __builtin_amdgcn_readfirstlane(item / H), h = item - b * H; return (unsigned)(((size_t)b * N * 3 * D + h * 64) * 2); };
     int ring_in = 0, ring_out = 0;                       // slot the next ring chunk is written to / the current step reads
-    // The fourth chunk of an operand covers rows 192..255 of the item; only rows < 16 RES (208 or 224) can hold a token.  Its DMA goes through a
-    // descriptor that ENDS at row 16 RES of the item: the rows behind it are out of range -- the buffer unit returns zeros and fetches nothing
-    // (a fifth of the launch's traffic; the zero rows are keys past N: masked, probability 0).
+    // The fourth chunk of an operand covers rows 192..255 of the item; only rows < N hold a token.  Its DMA goes through a descriptor that ENDS
+    // with the item's image: the rows behind it are out of range -- the buffer unit returns zeros and fetches nothing (a fifth of the launch's
+    // traffic; the zero rows are keys past N: masked, probability 0, and 0 . 0 = 0 where the next image's NaN or Inf would give NaN).
     const void *plane_ptr = (const void *)(qkv + ((wave >> 3) ? lo_off : 0));
-    const unsigned tail_bytes = (unsigned)(RES * 16 * row_bytes);      // (a run-time value on purpose: hipcc 7.2 drops the host-side instantiation of a kernel whose lambda names the template parameter here)
-    auto tail_end = [&](unsigned jb) -> int { const unsigned end = jb + tail_bytes; return (int)(end < plane_bytes ? end : plane_bytes); };     // (the descriptor itself is built at the use: a lambda RETURNING one makes hipcc 7.2 drop the kernel's host-side instantiation)
-    auto stage_ring = [&](unsigned jb, int s) {          // chunk s of the item at byte offset jb: 0..3 = K, 4..7 = V
+    const unsigned image_bytes = (unsigned)(N * row_bytes);
+    auto item_end = [&](int item) -> unsigned { const int b = __builtin_amdgcn_readfirstlane(item / H); return (unsigned)(b + 1) * image_bytes; };      // byte offset behind the item's image, <= plane_bytes
+    // (the descriptor itself is built at the use: a lambda RETURNING one makes hipcc 7.2 drop the kernel's host-side instantiation)
+    auto stage_ring = [&](unsigned jb, unsigned je, int s) {          // chunk s of the item at byte offset jb, whose image ends at je: 0..3 = K, 4..7 = V
         const int so = __builtin_amdgcn_readfirstlane((int)(jb + (unsigned)((s & 3) * CK * row_bytes + (s < 4 ? D * 2 : 2 * D * 2))));
         const bool skip = AP_DROP && (s < 4 ? skip_k : skip_v);
         {
-            __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc((void *)plane_ptr, 0, skip ? 0 : ((s & 3) == 3 ? tail_end(jb) : (int)plane_bytes), 0x00020000);
+            __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc((void *)plane_ptr, 0, skip ? 0 : ((s & 3) == 3 ? (int)je : (int)plane_bytes), 0x00020000);
             if (AP_DROP || (s & 3) == 3) __builtin_amdgcn_raw_ptr_buffer_load_lds(rt, LPTR(smem + QB + ring_in * SLOT + dst_w), 16, s < 4 ? koff : voff, so, 0, AP_AUX);
             else __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, LPTR(smem + QB + ring_in * SLOT + dst_w), 16, s < 4 ? koff : voff, so, 0, AP_AUX);
         }
         ring_in = ring_in == NSL - 1 ? 0 : ring_in + 1;
     };
-    auto stage_q = [&](unsigned jb, int q) {
+    auto stage_q = [&](unsigned jb, unsigned je, int q) {
         const int so = __builtin_amdgcn_readfirstlane((int)(jb + (unsigned)(q * CK * row_bytes)));
         {
-            __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc((void *)plane_ptr, 0, (AP_DROP && skip_q) ? 0 : (q == 3 ? tail_end(jb) : (int)plane_bytes), 0x00020000);
+            __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc((void *)plane_ptr, 0, (AP_DROP && skip_q) ? 0 : (q == 3 ? (int)je : (int)plane_bytes), 0x00020000);
             if (AP_DROP || q == 3) __builtin_amdgcn_raw_ptr_buffer_load_lds(rt, LPTR(smem + q * SLOT + dst_w), 16, koff, so, 0, AP_AUX);
             else __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, LPTR(smem + q * SLOT + dst_w), 16, koff, so, 0, AP_AUX);
         }
@@ -672,11 +674,11 @@ __global__ __launch_bounds__(1024, 4) void attention_precise_kernel(const _Float
     int item = blockIdx.x;
     if (item >= items) return;
     {
-        const unsigned jb = item_base(item);
+        const unsigned jb = item_base(item), je = item_end(item);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) stage_q(jb, q);
+        for (int q = 0; q < 4; ++q) stage_q(jb, je, q);
 #pragma unroll
-        for (int s2 = 0; s2 < 5; ++s2) stage_ring(jb, s2);
+        for (int s2 = 0; s2 < 5; ++s2) stage_ring(jb, je, s2);
     }
     wait_vm<4>();
     __builtin_amdgcn_s_barrier();
@@ -690,19 +692,19 @@ __global__ __launch_bounds__(1024, 4) void attention_precise_kernel(const _Float
     bool first = true;
 
     for (; item < items; item += gridDim.x) {
-        const unsigned jb = item_base(item);
+        const unsigned jb = item_base(item), je = item_end(item);
         const int nitem = item + (int)gridDim.x;
         const bool hn = nitem < items;
-        const unsigned jbn = hn ? item_base(nitem) : 0u;
+        const unsigned jbn = hn ? item_base(nitem) : 0u, jen = hn ? item_end(nitem) : 0u;
         const int hn1 = hn ? 1 : 0, pst = first ? 0 : nst;
         f32x4 sres[RES], o[4], oc[4];
         float mx = -INFINITY, nmx = 0.0f, sum = 0.0f;
         static_for<0, 8>([&](auto c_) {
             constexpr int c = decltype(c_)::value;
             // ---- top of the step: the slot the previous step read is free
-            if constexpr (c <= 2) stage_ring(jb, 5 + c);
-            else { if (hn) stage_ring(jbn, c - 3); }
-            if constexpr (c >= 1 && c <= 4) { if (hn) stage_q(jbn, c - 1); }
+            if constexpr (c <= 2) stage_ring(jb, je, 5 + c);
+            else { if (hn) stage_ring(jbn, jen, c - 3); }
+            if constexpr (c >= 1 && c <= 4) { if (hn) stage_q(jbn, jen, c - 1); }
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (ACTIVE) {
                 const unsigned sb = lds0 + (unsigned)(QB + ring_out * SLOT);
@@ -833,7 +835,7 @@ static hipError_t launch_stream_inst(const void *qkv, void *out, int n_img, int 
     }
     const int tasks = (N + 16 * QT - 1) / (16 * QT), qblocks = (tasks + W - 1) / W, items = n_img * H;
     const unsigned grid = (unsigned)(((items + 7) / 8) * 8 * qblocks);
-    hipLaunchKernelGGL((attention_stream_kernel<T, QT, PREC, W, NSLOT>), dim3(grid), dim3(W * 64), lds, stream, (const T *)qkv, (T *)out, N, D, H, items, qblocks, n_img, lo_off);
+    hipLaunchKernelGGL((attention_stream_kernel<T, QT, PREC, W, NSLOT>), dim3(grid), dim3(W * 64), lds, stream, (const T *)qkv, (T *)out, N, D, H, items, qblocks, lo_off);
     return hipGetLastError();
 }
 
