@@ -1,15 +1,12 @@
-"""Float64 restatement of the forward parametrised by MLP activation, LayerNorm epsilon and pre-norm (include/vitx.h "activation, epsilon and
-pre-norm"), shared by tests/test_cpu_arch.py -- which pins it to transformers' ViT, DINOv2 and CLIP -- and tests/test_gpu_arch.py.
-
-It is tests/prefix_data.py::forward64 (same token layout, same rounding points: `around` on the pixels, `wround` on every matrix, `uround` on
-the activations that enter a GEMM) with three things read from the file's tensors instead of being fixed:
+"""What the activation / epsilon / pre-norm family (include/vitx.h "activation, epsilon and pre-norm") owns of the float64 restatement
+tests/ref64.py: the three activations and the LayerNorm in float64, what a file's `arch` tensor states, the bound and the grid of the exact epilogue
+test, and the synthetic files of the three model classes.  Shared by tests/test_cpu_arch.py -- which pins the restatement to transformers' ViT,
+DINOv2 and CLIP -- and tests/test_gpu_arch.py.
     activation   t["arch"][0]: 0 tanh-GELU, 1 erf-GELU x Phi(x), 2 QuickGELU x sigmoid(1.702 x)      (absent: 0)
     eps          t["arch"][1], the epsilon of EVERY LayerNorm                                          (absent: 1e-6)
     pre-norm     t["pre_norm.weight"], t["pre_norm.bias"]: a LayerNorm of every token row after the patch embedding and before layer 0; trace
                  stage 0 is the stream AFTER it (what enters layer 0), `embed` the rows in front of it
-`activation=`, `eps=` and `pre_norm=False` override the file: the mutants the GPU tests must be able to tell from the real thing."""
-import os
-
+ref64.forward64's `activation=`, `eps=` and `pre_norm=False` override the file: the mutants the GPU tests must be able to tell from the real thing."""
 import numpy as np
 
 import prefix_data as PD
@@ -85,60 +82,6 @@ def layernorm64(x, w, b, eps):
     return (x - mu) / np.sqrt(var + eps) * w + b
 
 
-def forward64(t, imgs, heads, pos=None, activation=None, eps=None, pre_norm=None, around=None, wround=None, uround=None):
-    """t: {name: f32 array, torch shapes} (prefix_data.file_tensors); imgs [n][S][S][3] f32; pos: another [1 + g^2][D] table than the file's.
-    activation / eps / pre_norm: None = the file's own (arch_of).  Returns dict(embed [n][N][D] (the rows in front of the pre-norm), trace
-    [L + 1][n][N][D], final [n][N][D], mean [n][D], logits [n][C], probs [n][C])."""
-    f8 = lambda a: np.asarray(a, np.float64)
-    W = (lambda a: f8(wround(a))) if wround else f8
-    U = (lambda a: f8(uround(a))) if uround else f8
-    f_act, f_eps, f_pre = arch_of(t)
-    activation = f_act if activation is None else activation
-    eps = float(np.float32(f_eps if eps is None else eps))
-    pre_norm = f_pre if pre_norm is None else pre_norm
-    D = t["cls_token"].shape[-1]
-    R = t["reg_token"].shape[1] if "reg_token" in t else 0
-    T = 1 + R
-    L = 1 + max(int(k.split(".")[1]) for k in t if k.startswith("blocks."))
-    P = t["patch_embed.proj.weight"].shape[-1]
-    n, S = imgs.shape[0], imgs.shape[1]
-    g = S // P
-    pos = f8(t["pos_embed"][0] if pos is None else pos)
-    assert pos.shape == (1 + g * g, D)
-    px = f8(around(imgs) if around else imgs)
-    patches = px.reshape(n, g, P, g, P, 3).transpose(0, 1, 3, 5, 2, 4).reshape(n, g * g, 3 * P * P)      # [c][ky][kx], the kernel's order
-    emb = patches @ W(t["patch_embed.proj.weight"]).reshape(D, -1).T + f8(t["patch_embed.proj.bias"]).reshape(-1)
-    x = np.empty((n, g * g + T, D))
-    x[:, 0] = f8(t["cls_token"]).reshape(D) + pos[0]
-    if R:
-        x[:, 1:T] = f8(t["reg_token"][0])
-    x[:, T:] = emb + pos[1:]
-    embed = x.copy()
-    if pre_norm:
-        x = layernorm64(x, f8(t["pre_norm.weight"]), f8(t["pre_norm.bias"]), eps)
-    trace = [x.copy()]
-    hd = D // heads
-    for i in range(L):
-        p = f"blocks.{i}."
-        v = lambda name: f8(t[p + name])
-        qkv = U(layernorm64(x, v("norm1.weight"), v("norm1.bias"), eps)) @ W(t[p + "attn.qkv.weight"]).T + v("attn.qkv.bias")
-        q, k, vv = (qkv[..., j * D:(j + 1) * D].reshape(n, -1, heads, hd).transpose(0, 2, 1, 3) for j in range(3))
-        s = q @ k.transpose(0, 1, 3, 2) / np.sqrt(hd)
-        a = np.exp(s - s.max(-1, keepdims=True)); a /= a.sum(-1, keepdims=True)
-        o = U((a @ vv).transpose(0, 2, 1, 3).reshape(n, -1, D))
-        x = x + o @ W(t[p + "attn.proj.weight"]).T + v("attn.proj.bias")
-        h = U(act64(U(layernorm64(x, v("norm2.weight"), v("norm2.bias"), eps)) @ W(t[p + "mlp.fc1.weight"]).T + v("mlp.fc1.bias"), activation))
-        x = x + h @ W(t[p + "mlp.fc2.weight"]).T + v("mlp.fc2.bias")
-        trace.append(x.copy())
-    F = layernorm64(x, f8(t["norm.weight"]), f8(t["norm.bias"]), eps)
-    mean = PD.pooled64(F, T)
-    hw = W(t["head.weight"])
-    z = U(F[:, 0] if hw.shape[1] == D else np.concatenate([F[:, 0], mean], 1))
-    logits = z @ hw.T + f8(t["head.bias"])
-    e = np.exp(logits - logits.max(1, keepdims=True))
-    return dict(embed=embed, trace=np.stack(trace), final=F, mean=mean, logits=logits, probs=e / e.sum(1, keepdims=True))
-
-
 # ------------------------------------------------------------------------------------------------ synthetic files of the three model classes
 # name: (activation, eps, pre-norm, head_pool, CLIP-style zero biases and MLP scale)
 FIXTURES = {
@@ -184,12 +127,7 @@ def fixture_tensors(pkg, kind, name=MICRO, in_chans=3):
 
 def fixture_file(pkg, kind, ftype=1, name=MICRO, in_chans=3):
     """Path of the (cached) model file of a fixture."""
-    cache_dir = os.environ.get("VITX_CACHE", "/tmp/vitx_cache")
-    os.makedirs(cache_dir, exist_ok=True)
-    path = os.path.join(cache_dir, f"arch-{name}-c{in_chans}-{kind}-ft{ftype}.gguf")
-    if not os.path.exists(path):
-        hp, t = fixture_tensors(pkg, kind, name, in_chans)
-        tmp = path + f".tmp{os.getpid()}"
-        pkg.ggml_file.write_model(tmp, hp, t, ftype=ftype, id2label=dict(pkg.synth.VITSTR_LABELS) if in_chans == 1 else None)
-        os.replace(tmp, path)
-    return path
+    from ref64 import cached_file
+    labels = dict(pkg.synth.VITSTR_LABELS) if in_chans == 1 else None
+    return cached_file(f"arch-{name}-c{in_chans}-{kind}-ft{ftype}",
+                       lambda tmp: pkg.ggml_file.write_model(tmp, *fixture_tensors(pkg, kind, name, in_chans), ftype=ftype, id2label=labels))

@@ -1,15 +1,13 @@
-"""Float64 restatement of a model without a class token whose embedding comes from a multi-head attention-pooling (MAP) head (include/vitx.h
-"no class token and the attention-pooling head": SigLIP), shared by tests/test_cpu_map_head.py -- which pins it to transformers'
+"""Models without a class token whose embedding comes from a multi-head attention-pooling (MAP) head (include/vitx.h "no class token and the
+attention-pooling head": SigLIP), shared by tests/test_cpu_map_head.py -- which pins the restatement of such a file to transformers'
 SiglipVisionModel -- and tests/test_gpu_map_head.py.
 
-It is tests/arch_data.py::forward64 with T = 0 prefix tokens (an image is its g^2 patch rows, patch t takes pos_embed[t]) and the head in two
-forms that are identical in exact arithmetic:
+What the family owns of the float64 restatement tests/ref64.py (T = 0 prefix tokens there: an image is its patch rows, patch t takes pos_embed[t]):
+the gates on the pooled embedding, the micro fixture, and the head (head64, u64, pool64) in two forms that are identical in exact arithmetic:
     textbook   q = Wq latent + bq; k_t = Wk F[t] + bk; v_t = Wv F[t] + bv; p_h = softmax_t(q_h . k_{t,h} / sqrt(d)); o_h = sum_t p_{h,t} v_{t,h}
     folded     u_h = Wk_h^T q_h / sqrt(d); s_{h,t} = u_h . F[t]; p_h = softmax_t(s_h); M_h = sum_t p_{h,t} F[t]; o_h = Wv_h M_h + bv_h
 then a = Wproj o + bproj and e = a + fc2(act(fc1(LN(a)))).  The folded form carries the engine's rounding points (`uround` on M, o, LN(a), the fc1
 output and e as the head operand; `wround` on every matrix; u is rounded to f32 as vitx_model_pool_query stores it)."""
-import os
-
 import numpy as np
 
 import arch_data as AD
@@ -36,7 +34,6 @@ COS_GPU = {0: 1.12e-7, 1: 1.54e-5}
 COS_CPU = {0: 9.2e-8, 1: 1.75e-5}
 LEN_GPU = {0: 1.3e-5, 1: 4.26e-4}
 LEN_CPU = {0: 8.4e-6, 1: 3.45e-4}
-PROB_TOL = {0: 1e-3, 1: 2e-2}                       # tests/test_gpu_registers.py PROB_TOL
 
 
 def cos_gate(dtype):
@@ -98,15 +95,9 @@ def fixture_tensors(pkg, name=MICRO, head=True, activation=AD.ACT_TANH, eps=1e-6
 
 
 def fixture_file(pkg, ftype=1, name=MICRO, head=True, activation=AD.ACT_TANH):
-    cache_dir = os.environ.get("VITX_CACHE", "/tmp/vitx_cache")
-    os.makedirs(cache_dir, exist_ok=True)
-    path = os.path.join(cache_dir, f"map-{name}-h{int(head)}-a{activation}-ft{ftype}.gguf")
-    if not os.path.exists(path):
-        hp, t = fixture_tensors(pkg, name, head, activation)
-        tmp = path + f".tmp{os.getpid()}"
-        pkg.ggml_file.write_model(tmp, hp, t, ftype=ftype, id2label=None if head else {0: "(no head)"})
-        os.replace(tmp, path)
-    return path
+    from ref64 import cached_file
+    return cached_file(f"map-{name}-h{int(head)}-a{activation}-ft{ftype}",
+                       lambda tmp: pkg.ggml_file.write_model(tmp, *fixture_tensors(pkg, name, head, activation), ftype=ftype, id2label=None if head else {0: "(no head)"}))
 
 
 def u64(t, heads):
@@ -169,46 +160,6 @@ def head64(t, F, heads, folded=True, flat=False, activation=None, eps=None, wrou
     hdn = U(AD.act64(U(AD.layernorm64(a, f8(g("norm.weight")), f8(g("norm.bias")), eps)) @ W(g("mlp.fc1.weight")).T + f8(g("mlp.fc1.bias")), activation))
     e = a + hdn @ W(g("mlp.fc2.weight")).T + f8(g("mlp.fc2.bias"))
     return dict(e=e, M=M, p=p, a=a)
-
-
-def forward64(t, imgs, heads, folded=True, flat=False, activation=None, eps=None, around=None, wround=None, uround=None):
-    """t: {name: f32 array, torch shapes}; imgs [n][S][S][3] f32.  Returns dict(trace [L + 1][n][N][D], final [n][N][D], mean [n][D], e [n][D],
-    M, p, logits [n][C], probs [n][C]); N = g^2: no prefix token.  flat / activation: the mutants (activation is applied to the blocks AND the head)."""
-    f8 = lambda a: np.asarray(a, np.float64)
-    W = (lambda a: f8(wround(a))) if wround else f8
-    U = (lambda a: f8(uround(a))) if uround else f8
-    f_act, f_eps, _ = AD.arch_of(t)
-    act = f_act if activation is None else activation
-    eps_ = float(np.float32(f_eps if eps is None else eps))
-    D = t["pos_embed"].shape[-1]
-    L = 1 + max(int(k.split(".")[1]) for k in t if k.startswith("blocks."))
-    P = t["patch_embed.proj.weight"].shape[-1]
-    n, S = imgs.shape[0], imgs.shape[1]
-    g = S // P
-    pos = f8(t["pos_embed"][0])
-    assert pos.shape == (g * g, D)
-    px = f8(around(imgs) if around else imgs)
-    patches = px.reshape(n, g, P, g, P, 3).transpose(0, 1, 3, 5, 2, 4).reshape(n, g * g, 3 * P * P)
-    x = patches @ W(t["patch_embed.proj.weight"]).reshape(D, -1).T + f8(t["patch_embed.proj.bias"]).reshape(-1) + pos
-    trace = [x.copy()]
-    hd = D // heads
-    for i in range(L):
-        p = f"blocks.{i}."
-        v = lambda name: f8(t[p + name])
-        qkv = U(AD.layernorm64(x, v("norm1.weight"), v("norm1.bias"), eps_)) @ W(t[p + "attn.qkv.weight"]).T + v("attn.qkv.bias")
-        q, k, vv = (qkv[..., j * D:(j + 1) * D].reshape(n, -1, heads, hd).transpose(0, 2, 1, 3) for j in range(3))
-        s = q @ k.transpose(0, 1, 3, 2) / np.sqrt(hd)
-        a = np.exp(s - s.max(-1, keepdims=True)); a /= a.sum(-1, keepdims=True)
-        o = U((a @ vv).transpose(0, 2, 1, 3).reshape(n, -1, D))
-        x = x + o @ W(t[p + "attn.proj.weight"]).T + v("attn.proj.bias")
-        h = U(AD.act64(U(AD.layernorm64(x, v("norm2.weight"), v("norm2.bias"), eps_)) @ W(t[p + "mlp.fc1.weight"]).T + v("mlp.fc1.bias"), act))
-        x = x + h @ W(t[p + "mlp.fc2.weight"]).T + v("mlp.fc2.bias")
-        trace.append(x.copy())
-    F = AD.layernorm64(x, f8(t["norm.weight"]), f8(t["norm.bias"]), eps_)
-    hd_ = head64(t, F, heads, folded=folded, flat=flat, activation=act, eps=eps_, wround=wround, uround=uround)
-    logits = U(hd_["e"]) @ W(t["head.weight"]).T + f8(t["head.bias"])
-    ex = np.exp(logits - logits.max(1, keepdims=True))
-    return dict(trace=np.stack(trace), final=F, mean=F.mean(1), e=hd_["e"], M=hd_["M"], p=hd_["p"], logits=logits, probs=ex / ex.sum(1, keepdims=True))
 
 
 def one_minus_cos(a, b):

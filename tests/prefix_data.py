@@ -1,17 +1,12 @@
-"""Float64 restatement of the forward with prefix tokens (class token + R register tokens), shared by tests/test_cpu_registers.py and
-tests/test_gpu_registers.py (include/vitx.h "register tokens and the pooled head").
+"""What the prefix-token family (class token + R register tokens, the cls + mean head; include/vitx.h "register tokens and the pooled head") owns
+of the float64 restatement tests/ref64.py, and the helpers every family shares: the operand roundings, file_tensors, tanh-GELU, the pooled
+mean, the class-token attention rows and the exact images.  Shared by tests/test_cpu_registers.py and tests/test_gpu_registers.py.
 
-Token layout of an image, T = 1 + R, N = g^2 + T:
-    row 0          cls_token + pos_embed[0]
-    rows 1 .. R    reg_token[r]                    (no position embedding)
-    rows T .. N-1  patch p + pos_embed[1 + p]      (raster order)
-Pre-norm blocks, fused qkv with biases, softmax(q k^T / sqrt(hd)) v, tanh-GELU MLP, LayerNorm eps 1e-6 (LayerScale is already folded into
-attn.proj / mlp.fc2 of a file).  Head: logits = W . F[0] + b (head.weight [C][D]) or W . concat(F[0], mean of F[T .. N-1]) + b ([C][2 D]),
-F = the final norm of the last residual stream.  Everything is float64 on the f32 values it is given; `around` / `wround` / `uround` place
-the operand type's rounding where the engine places it -- on the patch pixels, on every matrix, and on the activations that enter a GEMM
-(LayerNorm outputs, attention output, GELU output, the head operand).  All None: no rounding anywhere.
-
-MUTANTS are the mistakes the GPU tests must be able to see; forward64(..., mutant=name) makes one of them."""
+MUTANTS are the layout mistakes the GPU tests must be able to see; ref64.forward64(..., mutant=name) makes one of them:
+    pos_on_registers     the register rows take pos_embed[1 .. R]
+    patch_pos_shifted    patch p takes the position row of patch p + R (wrapping)
+    registers_in_mean    the pooled mean runs over the register rows too
+    mean_over_n_minus_1  the pooled sum is divided by N - 1"""
 import numpy as np
 
 EPS = 1e-6
@@ -35,11 +30,6 @@ def file_tensors(pkg, path):
     return {t.name: pkg.ggml_file.dequantize(t.ttype, t.raw, int(np.prod(t.ne))).reshape(tuple(reversed(t.ne))) for t in mf.tensors}
 
 
-def layernorm64(x, w, b):
-    mu = x.mean(-1, keepdims=True); var = ((x - mu) ** 2).mean(-1, keepdims=True)
-    return (x - mu) / np.sqrt(var + EPS) * w + b
-
-
 def gelu64(x):
     return 0.5 * x * (1.0 + np.tanh(np.sqrt(2.0 / np.pi) * x * (1.0 + 0.044715 * x * x)))
 
@@ -51,63 +41,6 @@ def pooled64(F, T, mutant=None):
     if mutant == "mean_over_n_minus_1":
         return F[:, T:].sum(1) / (F.shape[1] - 1)
     return F[:, T:].mean(1)
-
-
-def qk64(t, x, i, heads, wround=None, uround=None):
-    """q, k, v [n][H][N][hd] of layer i from the residual stream x [n][N][D] that enters it."""
-    f8 = lambda a: np.asarray(a, np.float64)
-    W = (lambda a: f8(wround(a))) if wround else f8
-    U = (lambda a: f8(uround(a))) if uround else f8
-    p = f"blocks.{i}."
-    n, _, D = x.shape
-    qkv = U(layernorm64(f8(x), f8(t[p + "norm1.weight"]), f8(t[p + "norm1.bias"]))) @ W(t[p + "attn.qkv.weight"]).T + f8(t[p + "attn.qkv.bias"])
-    return tuple(qkv[..., j * D:(j + 1) * D].reshape(n, -1, heads, D // heads).transpose(0, 2, 1, 3) for j in range(3))
-
-
-def forward64(t, imgs, heads, pos=None, mutant=None, around=None, wround=None, uround=None):
-    """t: {name: f32 array, torch shapes} (file_tensors); imgs [n][S][S][3] f32; pos: another [1 + g^2][D] table than the file's.
-    Returns dict(trace [L + 1][n][N][D], final [n][N][D], mean [n][D], q / k [L][n][H][N][hd], logits [n][C], probs [n][C])."""
-    f8 = lambda a: np.asarray(a, np.float64)
-    W = (lambda a: f8(wround(a))) if wround else f8
-    U = (lambda a: f8(uround(a))) if uround else f8
-    D = t["cls_token"].shape[-1]
-    R = t["reg_token"].shape[1] if "reg_token" in t else 0
-    T = 1 + R
-    L = 1 + max(int(k.split(".")[1]) for k in t if k.startswith("blocks."))
-    P = t["patch_embed.proj.weight"].shape[-1]
-    n, S = imgs.shape[0], imgs.shape[1]
-    g = S // P
-    pos = f8(t["pos_embed"][0] if pos is None else pos)
-    assert pos.shape == (1 + g * g, D)
-    px = f8(around(imgs) if around else imgs)
-    patches = px.reshape(n, g, P, g, P, 3).transpose(0, 1, 3, 5, 2, 4).reshape(n, g * g, 3 * P * P)      # [c][ky][kx], the kernel's order
-    emb = patches @ W(t["patch_embed.proj.weight"]).reshape(D, -1).T + f8(t["patch_embed.proj.bias"]).reshape(-1)
-    ppos = pos[1:] if mutant != "patch_pos_shifted" else pos[(1 + R + np.arange(g * g)) % (1 + g * g)]
-    x = np.empty((n, g * g + T, D))
-    x[:, 0] = f8(t["cls_token"]).reshape(D) + pos[0]
-    if R:
-        x[:, 1:T] = f8(t["reg_token"][0]) + (pos[1:T] if mutant == "pos_on_registers" else 0.0)
-    x[:, T:] = emb + ppos
-    trace, qs, ks = [x.copy()], [], []
-    hd = D // heads
-    for i in range(L):
-        p = f"blocks.{i}."
-        v = lambda name: f8(t[p + name])
-        q, k, vv = qk64(t, x, i, heads, wround, uround)
-        s = q @ k.transpose(0, 1, 3, 2) / np.sqrt(hd)
-        a = np.exp(s - s.max(-1, keepdims=True)); a /= a.sum(-1, keepdims=True)
-        o = U((a @ vv).transpose(0, 2, 1, 3).reshape(n, -1, D))
-        x = x + o @ W(t[p + "attn.proj.weight"]).T + v("attn.proj.bias")
-        h = U(gelu64(U(layernorm64(x, v("norm2.weight"), v("norm2.bias"))) @ W(t[p + "mlp.fc1.weight"]).T + v("mlp.fc1.bias")))
-        x = x + h @ W(t[p + "mlp.fc2.weight"]).T + v("mlp.fc2.bias")
-        trace.append(x.copy()); qs.append(q); ks.append(k)
-    F = layernorm64(x, f8(t["norm.weight"]), f8(t["norm.bias"]))
-    mean = pooled64(F, T, mutant)
-    hw = W(t["head.weight"])
-    z = U(F[:, 0] if hw.shape[1] == D else np.concatenate([F[:, 0], mean], 1))
-    logits = z @ hw.T + f8(t["head.bias"])
-    e = np.exp(logits - logits.max(1, keepdims=True))
-    return dict(trace=np.stack(trace), final=F, mean=mean, q=np.stack(qs), k=np.stack(ks), logits=logits, probs=e / e.sum(1, keepdims=True))
 
 
 def cls_maps64(q, k):

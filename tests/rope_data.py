@@ -1,15 +1,15 @@
-"""Float64 restatement of the forward of a file with rotary position embeddings (include/vitx.h "rotary position embeddings"), shared by
-tests/test_cpu_rope.py -- which pins it to transformers' DINOv3ViTModel -- and tests/test_gpu_rope.py.
+"""Files with rotary position embeddings (include/vitx.h "rotary position embeddings"), shared by tests/test_cpu_rope.py -- which pins the
+restatement of such a file to transformers' DINOv3ViTModel -- and tests/test_gpu_rope.py.
 
-It is tests/arch_data.py::forward64 (class token + register tokens, the file's activation and epsilon, the same `around` / `wround` / `uround`
-rounding points) plus the rotation of q and k of the patch rows in every layer.  With T = 1 + registers, patch p = (y, x) of a gh x gw grid, hd the
-head dim, theta the file's rope[1]:
+What the family owns of the float64 restatement tests/ref64.py: the rotation of q and k of the patch rows in every layer (table64, rotate64), the
+operation order of rope.hip in numpy f32, and the micro fixture.  With T = 1 + registers, patch p = (y, x) of a gh x gw grid, hd the head dim, theta
+the file's rope[1]:
     cy = 2 (y + 0.5) / gh - 1, cx = 2 (x + 0.5) / gw - 1, inv_j = theta^(-4 j / hd) for j < hd / 4
     angle[p][j] = 2 pi cy inv_j, angle[p][hd / 4 + j] = 2 pi cx inv_j                                  (hd / 2 columns)
     a = q[.., j], b = q[.., hd / 2 + j]:  a' = a cos - b sin,  b' = b cos + a sin                        (k alike; rows 0 .. T - 1 untouched)
 The position table of such a file is all zero; the restatement adds it like any other.
 
-MUTANTS are the mistakes the tests must be able to see; forward64(..., mutant=name) makes one of them:
+MUTANTS are the mistakes the tests must be able to see; ref64.forward64(..., mutant=name) makes one of them:
     no_rope         nothing is rotated
     xy_swapped      the first quarter of the columns takes cx, the second cy
     sin_negated     the rotation runs the other way
@@ -20,15 +20,12 @@ The micro fixture (fixture_tensors; D 128, 2 layers, 2 heads of 64, patch 14, im
 pkg.synth.make_weights with the q and k rows of every attn.qkv.weight and attn.qkv.bias multiplied by QK_SCALE.  make_weights draws every matrix at
 0.02: q . k / sqrt(hd) then stays within a few hundredths, every softmax is nearly uniform and position information of any kind moves the stream by
 less than the operand rounding does.  The factor makes the scores of unit size.  It is chosen so that BOTH of these hold, computed by
-tests/test_cpu_rope.py::test_fixture_separates_the_mutants_from_operand_rounding and not assumed (the gates are tests/test_gpu_arch.py's; the chosen
+tests/test_cpu_rope.py::test_fixture_separates_the_mutants_from_operand_rounding and not assumed (the gates are tests/ref64.py's; the chosen
 value and the measured distances stand at QK_SCALE below):
     the operand-rounded restatement lies inside HALF a gate of the unrounded one, and every mutant more than TWICE a gate away."""
-import os
-
 import numpy as np
 
 import arch_data as AD
-import prefix_data as PD
 
 MUTANTS = ("no_rope", "xy_swapped", "sin_negated", "rope_on_prefix", "wrong_grid")
 MICRO = AD.MICRO
@@ -86,71 +83,6 @@ def rope_of(t):
     r = np.asarray(t["rope"], np.float32).reshape(-1)
     assert r[0] == 1 and r[2] == 0 and r[3] == 0
     return float(r[1])
-
-
-def qk64(t, x, i, heads, cos, sin, mutant=None, wround=None, uround=None):
-    """q, k (rotated by cos / sin [N - T][hd / 2]) and v, each [n][H][N][hd], of layer i from the residual stream x [n][N][D] that enters it."""
-    f8 = lambda a: np.asarray(a, np.float64)
-    W = (lambda a: f8(wround(a))) if wround else f8
-    U = (lambda a: f8(uround(a))) if uround else f8
-    _, eps, _ = AD.arch_of(t)
-    p = f"blocks.{i}."
-    n, N, D = x.shape
-    T = N - cos.shape[0]
-    qkv = U(AD.layernorm64(f8(x), f8(t[p + "norm1.weight"]), f8(t[p + "norm1.bias"]), float(np.float32(eps)))) @ W(t[p + "attn.qkv.weight"]).T + f8(t[p + "attn.qkv.bias"])
-    q, k, v = (qkv[..., j * D:(j + 1) * D].reshape(n, -1, heads, D // heads).transpose(0, 2, 1, 3) for j in range(3))
-    return rotate64(q, cos, sin, T, mutant), rotate64(k, cos, sin, T, mutant), v
-
-
-def forward64(t, imgs, heads, pos=None, mutant=None, around=None, wround=None, uround=None):
-    """t: {name: f32 array, torch shapes} (prefix_data.file_tensors) with a `rope` tensor; imgs [n][S][S][3] f32; pos: another [1 + g^2][D] table than
-    the file's (zeros at another grid).  Returns dict(trace [L + 1][n][N][D], final [n][N][D], mean [n][D], q / k [L][n][H][N][hd] AFTER the
-    rotation, logits [n][C], probs [n][C])."""
-    f8 = lambda a: np.asarray(a, np.float64)
-    W = (lambda a: f8(wround(a))) if wround else f8
-    U = (lambda a: f8(uround(a))) if uround else f8
-    activation, eps, pre_norm = AD.arch_of(t)
-    assert not pre_norm
-    eps = float(np.float32(eps))
-    theta = rope_of(t)
-    D = t["cls_token"].shape[-1]
-    R = t["reg_token"].shape[1] if "reg_token" in t else 0
-    T = 1 + R
-    L = 1 + max(int(k.split(".")[1]) for k in t if k.startswith("blocks."))
-    P = t["patch_embed.proj.weight"].shape[-1]
-    n, S = imgs.shape[0], imgs.shape[1]
-    g = S // P
-    pos = f8(t["pos_embed"][0] if pos is None else pos)
-    assert pos.shape == (1 + g * g, D)
-    hd = D // heads
-    cos, sin = table64(theta, hd, g, g, mutant)
-    px = f8(around(imgs) if around else imgs)
-    patches = px.reshape(n, g, P, g, P, 3).transpose(0, 1, 3, 5, 2, 4).reshape(n, g * g, 3 * P * P)      # [c][ky][kx], the kernel's order
-    emb = patches @ W(t["patch_embed.proj.weight"]).reshape(D, -1).T + f8(t["patch_embed.proj.bias"]).reshape(-1)
-    x = np.empty((n, g * g + T, D))
-    x[:, 0] = f8(t["cls_token"]).reshape(D) + pos[0]
-    if R:
-        x[:, 1:T] = f8(t["reg_token"][0])
-    x[:, T:] = emb + pos[1:]
-    trace, qs, ks = [x.copy()], [], []
-    for i in range(L):
-        p = f"blocks.{i}."
-        v = lambda name: f8(t[p + name])
-        q, k, vv = qk64(t, x, i, heads, cos, sin, mutant, wround, uround)
-        s = q @ k.transpose(0, 1, 3, 2) / np.sqrt(hd)
-        a = np.exp(s - s.max(-1, keepdims=True)); a /= a.sum(-1, keepdims=True)
-        o = U((a @ vv).transpose(0, 2, 1, 3).reshape(n, -1, D))
-        x = x + o @ W(t[p + "attn.proj.weight"]).T + v("attn.proj.bias")
-        h = U(AD.act64(U(AD.layernorm64(x, v("norm2.weight"), v("norm2.bias"), eps)) @ W(t[p + "mlp.fc1.weight"]).T + v("mlp.fc1.bias"), activation))
-        x = x + h @ W(t[p + "mlp.fc2.weight"]).T + v("mlp.fc2.bias")
-        trace.append(x.copy()); qs.append(q); ks.append(k)
-    F = AD.layernorm64(x, f8(t["norm.weight"]), f8(t["norm.bias"]), eps)
-    mean = PD.pooled64(F, T)
-    hw = W(t["head.weight"])
-    z = U(F[:, 0] if hw.shape[1] == D else np.concatenate([F[:, 0], mean], 1))
-    logits = z @ hw.T + f8(t["head.bias"])
-    e = np.exp(logits - logits.max(1, keepdims=True))
-    return dict(trace=np.stack(trace), final=F, mean=mean, q=np.stack(qs), k=np.stack(ks), logits=logits, probs=e / e.sum(1, keepdims=True))
 
 
 # ------------------------------------------------------------------------------------------------ the operation order of rope.hip in numpy f32
@@ -225,12 +157,6 @@ def fixture_tensors(pkg, name=MICRO, qk_scale=QK_SCALE, rope=True):
 
 
 def fixture_file(pkg, ftype=1, name=MICRO, rope=True):
-    cache_dir = os.environ.get("VITX_CACHE", "/tmp/vitx_cache")
-    os.makedirs(cache_dir, exist_ok=True)
-    path = os.path.join(cache_dir, f"rope-{name}-s{QK_SCALE:g}-r{int(rope)}-ft{ftype}.gguf")
-    if not os.path.exists(path):
-        hp, t = fixture_tensors(pkg, name, rope=rope)
-        tmp = path + f".tmp{os.getpid()}"
-        pkg.ggml_file.write_model(tmp, hp, t, ftype=ftype)
-        os.replace(tmp, path)
-    return path
+    from ref64 import cached_file
+    return cached_file(f"rope-{name}-s{QK_SCALE:g}-r{int(rope)}-ft{ftype}",
+                       lambda tmp: pkg.ggml_file.write_model(tmp, *fixture_tensors(pkg, name, rope=rope), ftype=ftype))

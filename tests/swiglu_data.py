@@ -1,16 +1,16 @@
-"""Float64 restatement of the forward of a file with a gated (SwiGLU) MLP (include/vitx.h "gated MLP"), shared by tests/test_cpu_swiglu.py -- which
-pins it to transformers' Dinov2Model (use_swiglu_ffn) and DINOv3ViTModel (use_gated_mlp) -- and tests/test_gpu_swiglu.py.
+"""Files with a gated (SwiGLU) MLP (include/vitx.h "gated MLP"), shared by tests/test_cpu_swiglu.py -- which pins the restatement of such a file to
+transformers' Dinov2Model (use_swiglu_ffn) and DINOv3ViTModel (use_gated_mlp) -- and tests/test_gpu_swiglu.py.
 
-It is tests/rope_data.py::forward64 (class token + register tokens, the file's epsilon, the same `around` / `wround` / `uround` rounding points, q and
-k of the patch rows rotated -- here only when the file has a `rope` tensor) with the MLP of every block replaced by the gated one.  With F = glu[1],
-y = uround(norm2(x)), fc1.weight [2 F][D], fc1.bias [2 F]:
+What the family owns of the float64 restatement tests/ref64.py: the gate (swiglu64, silu64), the exact grid of the kernel test and the micro
+fixtures.  ref64.blocks64 puts the gated MLP in place of every block's plain one.  With F = glu[1], y = uround(norm2(x)), fc1.weight [2 F][D],
+fc1.bias [2 F]:
     a = uround(y fc1.weight^T + fc1.bias)          the STORED fc1 output, [.., 2 F]
     g = a[.., :F], u = a[.., F:]                   gate rows first, then up rows: HuggingFace's weights_in.chunk(2), cat(gate_proj, up_proj)
     h = uround(silu(g) u), silu(g) = g / (1 + exp(-g))     the STORED product; nothing between the two is rounded
     x = x + h fc2.weight^T + fc2.bias
 The `arch` activation of such a file is not applied.
 
-MUTANTS are the mistakes the tests must be able to see; forward64(..., mutant=name) and swiglu64(..., mutant=name) make one of them:
+MUTANTS are the mistakes the tests must be able to see; ref64.forward64(..., mutant=name) and swiglu64(..., mutant=name) make one of them:
     gate_up_swapped      h = silu(u) g
     gate_is_sigmoid      h = sigmoid(g) u: the g factor is lost
     gelu_gate            h = erf-GELU(g) u
@@ -25,15 +25,12 @@ the wide tiles):
     hplus   DINOv3-H+-like: 4 registers, `rope` {1, 100}, a zero pos_embed, rope_data.QK_SCALE on q and k, `arch` {tanh, 1e-5}       N = 21
 pkg.synth.make_weights draws every matrix at 0.02: the gate arguments then stay near 0, where silu(g) ~ g / 2 and silu(g) u ~ silu(u) g -- the
 swapped halves are invisible.  So mlp.fc1.weight, mlp.fc1.bias and mlp.fc2.weight are multiplied by the factors GLU_SCALE, chosen so that BOTH of
-these hold on the 17 images of the GPU tests and against tests/test_gpu_arch.py's gates (_stage_ok, PROB_TOL), computed by
+these hold on the 17 images of the GPU tests and against tests/ref64.py's gates (stage_ok, PROB_TOL), computed by
 tests/test_cpu_swiglu.py::test_fixtures_separate_the_mutants_from_operand_rounding and not assumed:
     the operand-rounded restatement lies inside HALF a gate of the unrounded one, and every mutant more than TWICE a gate away."""
-import os
-
 import numpy as np
 
 import arch_data as AD
-import prefix_data as PD
 import rope_data as RD
 
 MUTANTS = ("gate_up_swapped", "gate_is_sigmoid", "gelu_gate", "no_up", "halves_interleaved", "up_bias_dropped")
@@ -95,66 +92,6 @@ def glu_of(t):
     return int(r[1])
 
 
-def forward64(t, imgs, heads, pos=None, mutant=None, around=None, wround=None, uround=None):
-    """t: {name: f32 array, torch shapes} (prefix_data.file_tensors) with a `glu` tensor, with or without `rope`; imgs [n][S][S][3] f32; pos: another
-    [1 + g^2][D] table than the file's.  Returns dict(trace [L + 1][n][N][D], final [n][N][D], mean [n][D], logits [n][C], probs [n][C])."""
-    f8 = lambda a: np.asarray(a, np.float64)
-    W = (lambda a: f8(wround(a))) if wround else f8
-    U = (lambda a: f8(uround(a))) if uround else f8
-    _, eps, pre_norm = AD.arch_of(t)
-    assert not pre_norm
-    eps = float(np.float32(eps))
-    Fw = glu_of(t)
-    theta = RD.rope_of(t)
-    D = t["cls_token"].shape[-1]
-    R = t["reg_token"].shape[1] if "reg_token" in t else 0
-    T = 1 + R
-    L = 1 + max(int(k.split(".")[1]) for k in t if k.startswith("blocks."))
-    P = t["patch_embed.proj.weight"].shape[-1]
-    n, S = imgs.shape[0], imgs.shape[1]
-    g = S // P
-    pos = f8(t["pos_embed"][0] if pos is None else pos)
-    assert pos.shape == (1 + g * g, D)
-    hd = D // heads
-    if theta is not None:
-        cos, sin = RD.table64(theta, hd, g, g)
-    px = f8(around(imgs) if around else imgs)
-    patches = px.reshape(n, g, P, g, P, 3).transpose(0, 1, 3, 5, 2, 4).reshape(n, g * g, 3 * P * P)      # [c][ky][kx], the kernel's order
-    emb = patches @ W(t["patch_embed.proj.weight"]).reshape(D, -1).T + f8(t["patch_embed.proj.bias"]).reshape(-1)
-    x = np.empty((n, g * g + T, D))
-    x[:, 0] = f8(t["cls_token"]).reshape(D) + pos[0]
-    if R:
-        x[:, 1:T] = f8(t["reg_token"][0])
-    x[:, T:] = emb + pos[1:]
-    trace = [x.copy()]
-    for i in range(L):
-        p = f"blocks.{i}."
-        v = lambda name: f8(t[p + name])
-        qkv = U(AD.layernorm64(x, v("norm1.weight"), v("norm1.bias"), eps)) @ W(t[p + "attn.qkv.weight"]).T + v("attn.qkv.bias")
-        q, k, vv = (qkv[..., j * D:(j + 1) * D].reshape(n, -1, heads, hd).transpose(0, 2, 1, 3) for j in range(3))
-        if theta is not None:
-            q, k = RD.rotate64(q, cos, sin, T), RD.rotate64(k, cos, sin, T)
-        s = q @ k.transpose(0, 1, 3, 2) / np.sqrt(hd)
-        a = np.exp(s - s.max(-1, keepdims=True)); a /= a.sum(-1, keepdims=True)
-        o = U((a @ vv).transpose(0, 2, 1, 3).reshape(n, -1, D))
-        x = x + o @ W(t[p + "attn.proj.weight"]).T + v("attn.proj.bias")
-        b1 = v("mlp.fc1.bias").copy()
-        assert b1.shape == (2 * Fw,) and t[p + "mlp.fc2.weight"].shape == (D, Fw)
-        if mutant == "up_bias_dropped":
-            b1[Fw:] = 0.0
-        a1 = U(U(AD.layernorm64(x, v("norm2.weight"), v("norm2.bias"), eps)) @ W(t[p + "mlp.fc1.weight"]).T + b1)
-        h = U(swiglu64(a1, Fw, mutant))
-        x = x + h @ W(t[p + "mlp.fc2.weight"]).T + v("mlp.fc2.bias")
-        trace.append(x.copy())
-    Fn = AD.layernorm64(x, f8(t["norm.weight"]), f8(t["norm.bias"]), eps)
-    mean = PD.pooled64(Fn, T)
-    hw = W(t["head.weight"])
-    z = U(Fn[:, 0] if hw.shape[1] == D else np.concatenate([Fn[:, 0], mean], 1))
-    logits = z @ hw.T + f8(t["head.bias"])
-    e = np.exp(logits - logits.max(1, keepdims=True))
-    return dict(trace=np.stack(trace), final=Fn, mean=mean, logits=logits, probs=e / e.sum(1, keepdims=True))
-
-
 # ------------------------------------------------------------------------------------------------ the exact grid of the kernel test
 def grid_operands(rows, Fw, dtype):
     """(g, u) [rows][Fw] float64 as the operand type holds them: g walks arch_data.grid() (k / 64, |g| <= 8) over the elements in row-major order,
@@ -203,12 +140,6 @@ def fixture_tensors(pkg, kind, name=MICRO, scale=GLU_SCALE, Fw=F, glu=True):
 
 
 def fixture_file(pkg, kind, ftype=1, name=MICRO):
-    cache_dir = os.environ.get("VITX_CACHE", "/tmp/vitx_cache")
-    os.makedirs(cache_dir, exist_ok=True)
-    path = os.path.join(cache_dir, f"glu-{name}-{kind}-F{F}-s{'x'.join(f'{s:g}' for s in GLU_SCALE)}-ft{ftype}.gguf")
-    if not os.path.exists(path):
-        hp, t = fixture_tensors(pkg, kind, name)
-        tmp = path + f".tmp{os.getpid()}"
-        pkg.ggml_file.write_model(tmp, hp, t, ftype=ftype)
-        os.replace(tmp, path)
-    return path
+    from ref64 import cached_file
+    return cached_file(f"glu-{name}-{kind}-F{F}-s{'x'.join(f'{s:g}' for s in GLU_SCALE)}-ft{ftype}",
+                       lambda tmp: pkg.ggml_file.write_model(tmp, *fixture_tensors(pkg, kind, name), ftype=ftype))

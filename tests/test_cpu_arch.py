@@ -10,6 +10,7 @@ import pytest
 
 import arch_data as AD
 import prefix_data as PD
+import ref64 as R64
 
 ERR_FORMAT = 2
 HF_TOL = 2e-4                        # tests/test_cpu_oracle.py:115 (test_oracle_vs_transformers_vit_f32), as tests/test_cpu_registers.py
@@ -66,7 +67,7 @@ WANT = {"vit": (AD.ACT_ERF, 1e-12, False), "dinov2": (AD.ACT_ERF, 1e-6, False), 
 @pytest.mark.parametrize("kind", ["vit", "dinov2", "clip"])
 def test_restatement_and_converter_against_transformers(pkg, binding, tmp_path, kind):
     """convert_hf_model at ftype 0 of a model with the settings its released checkpoints have (HF ViT: erf, 1e-12; DINOv2: erf, 1e-6; CLIP:
-    QuickGELU, 1e-5, pre_layrnorm, bias-free convolution and projection), then arch_data.forward64 on the file's tensors against the model
+    QuickGELU, 1e-5, pre_layrnorm, bias-free convolution and projection), then ref64.forward64 on the file's tensors against the model
     itself: every hidden state and the logits (CLIP: image_embeds) to f32 noise.  The file reports its settings through the loader."""
     torch, m = _hf_model(kind)
     path = str(tmp_path / f"{kind}.gguf")
@@ -90,7 +91,7 @@ def test_restatement_and_converter_against_transformers(pkg, binding, tmp_path, 
     px = torch.from_numpy(imgs).permute(0, 3, 1, 2).contiguous()
     with torch.no_grad():
         out = m(pixel_values=px, output_hidden_states=True)
-    r = AD.forward64(t, imgs, heads=2)
+    r = R64.forward64(t, imgs, heads=2)
     want_logits = (out.image_embeds if kind == "clip" else out.logits).numpy()
     # every hidden state, stage 0 included: with a pre-norm it is the stream that enters layer 0 (transformers' CLIP encoder starts from the normalised rows)
     assert r["trace"].shape == (3, 2, 17, 128) and len(out.hidden_states) == 3
@@ -108,7 +109,7 @@ def test_restatement_and_converter_against_transformers(pkg, binding, tmp_path, 
     print(f"{kind} logits: max|restatement - transformers| = {d:.3e}  (max|logit| {np.abs(want_logits).max():.3f})")
     assert d <= HF_TOL, d
     # the comparison sees the settings: the reference's arithmetic (tanh, 1e-6, no pre-norm) on the same tensors is NOT the model
-    wrong = AD.forward64(t, imgs, heads=2, activation=AD.ACT_TANH, eps=1e-6, pre_norm=False)
+    wrong = R64.forward64(t, imgs, heads=2, activation=AD.ACT_TANH, eps=1e-6, pre_norm=False)
     dw = float(np.abs(wrong["logits"] - want_logits).max())
     print(f"{kind} logits with tanh / 1e-6 / no pre-norm: max|d| = {dw:.3e}")
     if kind == "clip":              # erf against tanh alone moves these logits by about the gate itself (max |tanh - erf| = 4.7e-4 per element): printed, not asserted

@@ -10,6 +10,7 @@ import pytest
 import arch_data as AD
 import map_data as MD
 import prefix_data as PD
+import ref64 as R64
 from test_cpu_arch import HF_TOL, KW, _redraw
 
 ERR_FORMAT, ERR_ARG, ERR_UNSUPPORTED = 2, 3, 5
@@ -59,7 +60,7 @@ def _load_fails(binding, path, code=ERR_FORMAT, word=None):
 
 @pytest.mark.parametrize("full", [False, True], ids=["SiglipVisionModel", "SiglipModel"])
 def test_converter_and_restatement_against_transformers(pkg, binding, tmp_path, full):
-    """convert_hf_model at ftype 0 of a SiglipVisionModel (and of a SiglipModel: its vision tower), then map_data.forward64 on the file's tensors
+    """convert_hf_model at ftype 0 of a SiglipVisionModel (and of a SiglipModel: its vision tower), then ref64.forward64 on the file's tensors
     against the model itself: last_hidden_state and pooler_output to f32 noise, textbook and folded."""
     torch, m = _siglip(full=full)
     vis = m.vision_model if full else m
@@ -83,7 +84,7 @@ def test_converter_and_restatement_against_transformers(pkg, binding, tmp_path, 
     with torch.no_grad():
         out = vis(pixel_values=px) if full else m(pixel_values=px)
     for folded in (False, True):
-        r = MD.forward64(t, imgs, heads=2, folded=folded)
+        r = R64.forward64(t, imgs, heads=2, folded=folded)
         d_h = float(np.abs(r["final"] - out.last_hidden_state.numpy()).max())
         d_e = float(np.abs(r["e"] - out.pooler_output.numpy()).max())
         print(f"{'folded' if folded else 'textbook'}: max|restatement - transformers|  last_hidden_state {d_h:.3e}  pooler_output {d_e:.3e}  (max|e| {np.abs(r['e']).max():.3f})")
@@ -105,7 +106,7 @@ def test_fold_identity_and_fixture_separates_the_mutants(pkg):
     hp, t = MD.fixture_tensors(pkg)
     assert np.abs(t["attn_pool.kv.bias"][:128]).max() > 0.01
     imgs = PD.exact_images(17, 56, seed=1)              # the images of tests/test_gpu_map_head.py
-    a, b = MD.forward64(t, imgs, heads=2, folded=False), MD.forward64(t, imgs, heads=2, folded=True)
+    a, b = R64.forward64(t, imgs, heads=2, folded=False), R64.forward64(t, imgs, heads=2, folded=True)
     rel = float(np.abs(a["e"] - b["e"]).max() / np.abs(a["e"]).max())
     print(f"fold identity: max|e_folded - e_textbook| / max|e| = {rel:.3e};  max|p_folded - p_textbook| = {np.abs(a['p'] - b['p']).max():.3e}")
     assert rel <= 1e-12
@@ -115,12 +116,12 @@ def test_fold_identity_and_fixture_separates_the_mutants(pkg):
     print(f"score spread (max - min over tokens, smallest over images and heads): {spread:.2f};  largest p: {b['p'].max():.3f}")
     assert spread > 2.0
     t = PD.file_tensors(pkg, MD.fixture_file(pkg))          # the file the GPU test runs (f16 matrices): the figures recorded in map_data.py are its
-    b = MD.forward64(t, imgs, heads=2)
-    flat, quick = MD.forward64(t, imgs, heads=2, flat=True), MD.forward64(t, imgs, heads=2, activation=AD.ACT_QUICK)
+    b = R64.forward64(t, imgs, heads=2)
+    flat, quick = R64.forward64(t, imgs, heads=2, flat=True), R64.forward64(t, imgs, heads=2, activation=AD.ACT_QUICK)
     for dtype in (0, 1):
         gate, lgate = MD.cos_gate(dtype), MD.len_gate(dtype)
         rnd = PD.f16_round if dtype == 0 else PD.bf16_round
-        r = MD.forward64(t, imgs, heads=2, wround=rnd, uround=rnd)
+        r = R64.forward64(t, imgs, heads=2, wround=rnd, uround=rnd)
         noise, lnoise = float(MD.one_minus_cos(r["e"], b["e"]).max()), MD.mean_length(r["e"], b["e"])
         c_flat, l_quick = float(MD.one_minus_cos(flat["e"], b["e"]).min()), MD.mean_length(quick["e"], b["e"])
         print(f"dtype {dtype}: operand rounding: 1 - cos(e) {noise:.3e} (recorded {MD.COS_CPU[dtype]:.2e}, gate {gate:.3e}), mean length {lnoise:+.3e} (recorded "

@@ -1,4 +1,4 @@
-"""Rectangular contexts without a GPU (include/vitx.h "rectangular contexts"): the float64 restatement of tests/rect_data.py and the converter against
+"""Rectangular contexts without a GPU (include/vitx.h "rectangular contexts"): the float64 restatement (tests/ref64.py) and the converter against
 transformers' ViTModel (interpolate_pos_encoding=True), Dinov2Model and DINOv3ViTModel on non-square inputs, the separation of the fixtures'
 mutants from operand rounding, vitx_rect_shape, vitx_preprocess_rect against Pillow bit for bit, and the argument errors of vitx_ctx_create_rect
 that are decided before a device is touched."""
@@ -10,7 +10,9 @@ import pytest
 import preproc_data as PPD
 import prefix_data as PD
 import rect_data as XD
-from test_gpu_arch import PROB_TOL, ROUND, _apart, _stage_errors, _stage_ok
+import ref64 as R64
+from ref64 import PROB_TOL, stage_errors, stage_ok
+from test_gpu_arch import ROUND, _apart
 
 ERR_ARG, ERR_HIP, ERR_UNSUPPORTED = 3, 4, 5
 MICRO16 = "vit_micro_patch16_64"
@@ -24,33 +26,33 @@ def _bits(a):
 @pytest.mark.parametrize("kind,shape", XD.CASES, ids=[f"{k}-{h}x{w}" for k, (h, w) in XD.CASES])
 def test_fixture_separates_the_mutants_from_operand_rounding(pkg, binding, kind, shape):
     """Computed, not assumed (rect_data.POS_SCALE, QK_SCALE): on every fixture, shape and image of the GPU forward tests the operand-rounded
-    restatement lies inside HALF of tests/test_gpu_arch.py's stage and probability gates of the unrounded one, and every mutant lies more than TWICE
+    restatement lies inside HALF of tests/ref64.py's stage and probability gates of the unrounded one, and every mutant lies more than TWICE
     a gate from the real thing -- so a GPU result inside the gates of the restatement is outside those of every mutant."""
     h, w = shape
     t = PD.file_tensors(pkg, XD.fixture_file(pkg, kind))
     imgs = XD.images(17, h, w)
-    exact = XD.forward64(t, imgs, binding=binding)
+    exact = R64.forward64(t, imgs, XD.HEADS, binding=binding)
     assert exact["trace"].shape[2] == (h // t["patch_embed.proj.weight"].shape[-1]) * (w // t["patch_embed.proj.weight"].shape[-1]) + 1 + XD.FIXTURES[kind][1]
     for dtype in (0, 1):
-        ref = XD.forward64(t, imgs, wround=ROUND[dtype], uround=ROUND[dtype], binding=binding)
-        se = _stage_errors(ref["trace"], exact["trace"])
+        ref = R64.forward64(t, imgs, XD.HEADS, wround=ROUND[dtype], uround=ROUND[dtype], binding=binding)
+        se = stage_errors(ref["trace"], exact["trace"])
         dp = float(np.abs(ref["probs"] - exact["probs"]).max())
         print(f"{kind} {h}x{w} dtype {dtype}: rounded against unrounded: stages (e_max, e_rms) {[(round(a, 5), round(b, 5)) for a, b in se]}, max|dprob| {dp:.2e}")
-        assert all(_stage_ok(a, b, dtype, 0.5) for a, b in se) and dp <= 0.5 * PROB_TOL[dtype]
+        assert all(stage_ok(a, b, dtype, 0.5) for a, b in se) and dp <= 0.5 * PROB_TOL[dtype]
         for mut in XD.mutants_of(t):
-            m = XD.forward64(t, imgs, mutant=mut, wround=ROUND[dtype], uround=ROUND[dtype], binding=binding)
-            sm = _stage_errors(m["trace"], ref["trace"])
+            m = R64.forward64(t, imgs, XD.HEADS, mutant=mut, wround=ROUND[dtype], uround=ROUND[dtype], binding=binding)
+            sm = stage_errors(m["trace"], ref["trace"])
             dm = float(np.abs(ref["probs"] - m["probs"]).max())
             print(f"{kind} {h}x{w} dtype {dtype}: mutant {mut}: stages {[(round(a, 4), round(b, 4)) for a, b in sm]}, max|dprob| {dm:.3f}")
             assert _apart(ref, m, dtype), (kind, shape, dtype, mut)
 
 
 def test_square_input_is_the_square_restatement(pkg, binding):
-    """On a square image at the file's size rect_data.forward64 is arch_data.forward64 (no resampling, the same patchify), to the last bit."""
-    import arch_data as AD
+    """On a square image at the file's size the table ref64.forward64 makes (rect_data.pos_table: no resampling) is the file's own handed in as it
+    is, to the last bit."""
     t = PD.file_tensors(pkg, XD.fixture_file(pkg, "p14r4"))
     imgs = PD.exact_images(2, 56, seed=5)
-    a, b = XD.forward64(t, imgs, binding=binding), AD.forward64(t, imgs, 2)
+    a, b = R64.forward64(t, imgs, XD.HEADS, binding=binding), R64.forward64(t, imgs, 2, pos=t["pos_embed"][0])
     assert np.array_equal(a["trace"], b["trace"]) and np.array_equal(a["probs"], b["probs"])
 
 
@@ -58,7 +60,7 @@ def test_square_input_is_the_square_restatement(pkg, binding):
 @pytest.mark.parametrize("shape", [(28, 70), (70, 28), (56, 56)])
 @pytest.mark.parametrize("kind", ["vit", "dinov2"])
 def test_converter_and_restatement_against_transformers(pkg, binding, tmp_path, kind, shape):
-    """convert_hf_model at ftype 0, then rect_data.forward64 on the file's tensors against the model's f32 last_hidden_state on a non-square input:
+    """convert_hf_model at ftype 0, then ref64.forward64 on the file's tensors against the model's f32 last_hidden_state on a non-square input:
     HuggingFace ViT with interpolate_pos_encoding=True and DINOv2 (which always interpolates), both F.interpolate(size=(gh, gw), mode="bicubic",
     align_corners=False) -- the host resampler at (gh, gw).  The bound is tests/test_cpu_rope.py::test_converter_and_restatement_against_transformers':
     1e-4 for the restatement, every mutant further than 0.1."""
@@ -72,14 +74,14 @@ def test_converter_and_restatement_against_transformers(pkg, binding, tmp_path, 
     px = torch.from_numpy(imgs).permute(0, 3, 1, 2).contiguous()
     with torch.no_grad():
         want = (m.vit(pixel_values=px, interpolate_pos_encoding=True) if kind == "vit" else m.dinov2(pixel_values=px)).last_hidden_state.numpy()
-    r = XD.forward64(t, imgs, heads=2, binding=binding)
+    r = R64.forward64(t, imgs, heads=2, binding=binding)
     assert r["final"].shape == want.shape == (2, 1 + (h // 14) * (w // 14), 128)
     d = float(np.abs(r["final"] - want).max())
     print(f"{kind} {h}x{w}: max|restatement - transformers| = {d:.3e} on features of magnitude {np.abs(want).max():.2f}")
     assert d <= 1e-4, d
     if h != w:
         for mut in XD.MUTANTS:
-            dm = float(np.abs(XD.forward64(t, imgs, heads=2, mutant=mut, binding=binding)["final"] - want).max())
+            dm = float(np.abs(R64.forward64(t, imgs, heads=2, mutant=mut, binding=binding)["final"] - want).max())
             print(f"{kind} {h}x{w}: mutant {mut}: max|d| = {dm:.3f}")
             assert dm > 0.1, (mut, dm)
 
@@ -96,13 +98,13 @@ def test_converter_and_restatement_against_transformers_dinov3(pkg, binding, tmp
     imgs = pkg.synth.normalize_u8(np.random.default_rng(3).integers(0, 256, (2, h, w, 3), dtype=np.uint8))
     with torch.no_grad():
         want = m(pixel_values=torch.from_numpy(imgs).permute(0, 3, 1, 2).contiguous()).last_hidden_state.numpy()
-    r = XD.forward64(t, imgs, heads=2, binding=binding)
+    r = R64.forward64(t, imgs, heads=2, binding=binding)
     assert r["final"].shape == want.shape == (2, 5 + (h // 14) * (w // 14), 128)
     d = float(np.abs(r["final"] - want).max())
     print(f"dinov3 {h}x{w}: max|restatement - transformers| = {d:.3e} on features of magnitude {np.abs(want).max():.2f}")
     assert d <= 1e-4, d
     for mut in XD.ROPE_MUTANTS:
-        dm = float(np.abs(XD.forward64(t, imgs, heads=2, mutant=mut, binding=binding)["final"] - want).max())
+        dm = float(np.abs(R64.forward64(t, imgs, heads=2, mutant=mut, binding=binding)["final"] - want).max())
         print(f"dinov3 {h}x{w}: mutant {mut}: max|d| = {dm:.3f}")
         assert dm > 0.1, (mut, dm)
 

@@ -10,6 +10,7 @@ import pytest
 
 import feature_data as FD
 import prefix_data as PD
+import ref64 as R64
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 ERR_FORMAT = 2
@@ -64,7 +65,7 @@ def test_restatement_and_converter_against_transformers_dinov2(pkg, tmp_path, re
     imgs = pkg.synth.normalize_u8(pkg.synth.synthetic_images_u8(2, 56, seed=3))
     with torch.no_grad():
         out = m(pixel_values=torch.from_numpy(imgs).permute(0, 3, 1, 2).contiguous(), output_hidden_states=True)
-    r = PD.forward64(t, imgs, heads=2)
+    r = R64.forward64(t, imgs, heads=2)
     N = 17 + registers
     assert r["trace"].shape == (3, 2, N, 128) and len(out.hidden_states) == 3 and tuple(out.hidden_states[0].shape) == (2, N, 128)
     for s in range(3):
@@ -268,11 +269,11 @@ def test_each_layout_mistake_moves_its_quantity_by_100_gates(pkg):
     images the GPU tests use: otherwise a GPU test could pass on a wrong layout."""
     t = PD.file_tensors(pkg, pkg.synth.cached_synthetic(NAME, head_scale=4.0, registers=4, head_pool=1))
     imgs = PD.exact_images(3, 56, seed=1)
-    good = PD.forward64(t, imgs, heads=2)
+    good = R64.forward64(t, imgs, heads=2)
     g0, gm, gl = gpu_gates(pkg, t, good, 5)
     moved = {}
     for mut in PD.MUTANTS:
-        bad = PD.forward64(t, imgs, heads=2, mutant=mut)
+        bad = R64.forward64(t, imgs, heads=2, mutant=mut)
         moved[mut] = (float(np.abs(bad["trace"][0] - good["trace"][0]).max()), float(np.abs(bad["mean"] - good["mean"]).max()),
                       float(np.abs(bad["logits"] - good["logits"]).max()))
         print(f"{mut}: stage 0 moves {moved[mut][0]:.3e} (gate {g0:.1e}), mean {moved[mut][1]:.3e} (gate {gm:.1e}), logits {moved[mut][2]:.3e} (gate {gl:.1e})")

@@ -1,5 +1,5 @@
 """Rotary position embeddings without a GPU (include/vitx.h "rotary position embeddings"): the host table against transformers'
-DINOv3ViTRopePositionEmbedding, the converter and the float64 restatement of tests/rope_data.py against DINOv3ViTModel, the separation of the micro
+DINOv3ViTRopePositionEmbedding, the converter and the float64 restatement of tests/ref64.py against DINOv3ViTModel, the separation of the micro
 fixture's mutants from operand rounding, and the loader's rules for the `rope` tensor."""
 import ctypes as C
 import hashlib
@@ -13,9 +13,11 @@ import pytest
 import arch_data as AD
 import map_data as MD
 import prefix_data as PD
+import ref64 as R64
 import rope_data as RD
 import text_data as TD
-from test_gpu_arch import PROB_TOL, ROUND, _apart, _stage_errors, _stage_ok
+from ref64 import PROB_TOL, stage_errors, stage_ok
+from test_gpu_arch import ROUND, _apart
 
 ERR_FORMAT, ERR_ARG = 2, 3
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -114,7 +116,7 @@ def _hf_dinov3(seed=31, factor=QK_FACTOR, **over):
 
 @pytest.mark.parametrize("S", [56, 84])
 def test_converter_and_restatement_against_transformers(pkg, binding, tmp_path, S):
-    """convert_hf_model at ftype 0, then rope_data.forward64 on the file's tensors against the model's f32 last_hidden_state, at the file's size and on
+    """convert_hf_model at ftype 0, then ref64.forward64 on the file's tensors against the model's f32 last_hidden_state, at the file's size and on
     an 84 x 84 image (6 x 6 grid, the table from the new grid: nothing is resampled).  The issue's gates: 1e-4 for the restatement, every mutant
     further than 0.1 (it measured 2.5e-6 on features of magnitude 3.9, and 0.58 / 0.51 / 0.68 for no_rope / xy_swapped / sin_negated)."""
     torch, m = _hf_dinov3()
@@ -142,14 +144,14 @@ def test_converter_and_restatement_against_transformers(pkg, binding, tmp_path, 
     want = out.last_hidden_state.numpy()
     g = S // 14
     pos = None if S == 56 else np.zeros((1 + g * g, 128), np.float32)
-    r = RD.forward64(t, imgs, heads=2, pos=pos)
+    r = R64.forward64(t, imgs, heads=2, pos=pos)
     assert r["final"].shape == want.shape == (2, 5 + g * g, 128)
     d = float(np.abs(r["final"] - want).max())
     print(f"S {S}: max|restatement - transformers| = {d:.3e} on features of magnitude {np.abs(want).max():.2f}")
     assert d <= 1e-4, d
     assert np.abs(r["final"][:, 0] - out.pooler_output.numpy()).max() <= 1e-4
     for mut in RD.MUTANTS:
-        dm = float(np.abs(RD.forward64(t, imgs, heads=2, pos=pos, mutant=mut)["final"] - want).max())
+        dm = float(np.abs(R64.forward64(t, imgs, heads=2, pos=pos, mutant=mut)["final"] - want).max())
         print(f"S {S}: mutant {mut}: max|d| = {dm:.3f}")
         assert dm > 0.1, (mut, dm)
 
@@ -169,21 +171,21 @@ def test_converter_refusals(pkg, tmp_path):
 # ------------------------------------------------------------------------------------------------ the micro fixture
 def test_fixture_separates_the_mutants_from_operand_rounding(pkg):
     """Computed, not assumed (rope_data.QK_SCALE): on the micro fixture and the images of the GPU tests, the operand-rounded restatement lies inside
-    HALF of tests/test_gpu_arch.py's stage and probability gates of the unrounded one, and every mutant lies more than TWICE a gate from the real
+    HALF of tests/ref64.py's stage and probability gates of the unrounded one, and every mutant lies more than TWICE a gate from the real
     thing -- so a GPU result inside the gates of the restatement is outside those of every mutant."""
     imgs = PD.exact_images(17, 56, seed=1)
     t = PD.file_tensors(pkg, RD.fixture_file(pkg))
     assert RD.rope_of(t) == RD.THETA and t["reg_token"].shape[1] == RD.REGISTERS and not t["pos_embed"].any()
-    exact = RD.forward64(t, imgs, 2)
+    exact = R64.forward64(t, imgs, 2)
     for dtype in (0, 1):
-        ref = RD.forward64(t, imgs, 2, wround=ROUND[dtype], uround=ROUND[dtype])
-        se = _stage_errors(ref["trace"], exact["trace"])
+        ref = R64.forward64(t, imgs, 2, wround=ROUND[dtype], uround=ROUND[dtype])
+        se = stage_errors(ref["trace"], exact["trace"])
         dp = float(np.abs(ref["probs"] - exact["probs"]).max())
         print(f"dtype {dtype}: rounded against unrounded: stages (e_max, e_rms) {[(round(a, 5), round(b, 5)) for a, b in se]}, max|dprob| {dp:.2e}")
-        assert all(_stage_ok(a, b, dtype, 0.5) for a, b in se) and dp <= 0.5 * PROB_TOL[dtype]
+        assert all(stage_ok(a, b, dtype, 0.5) for a, b in se) and dp <= 0.5 * PROB_TOL[dtype]
         for mut in RD.MUTANTS:
-            m = RD.forward64(t, imgs, 2, mutant=mut, wround=ROUND[dtype], uround=ROUND[dtype])
-            sm = _stage_errors(m["trace"], ref["trace"])
+            m = R64.forward64(t, imgs, 2, mutant=mut, wround=ROUND[dtype], uround=ROUND[dtype])
+            sm = stage_errors(m["trace"], ref["trace"])
             dm = float(np.abs(ref["probs"] - m["probs"]).max())
             print(f"dtype {dtype}: mutant {mut}: stages {[(round(a, 4), round(b, 4)) for a, b in sm]}, max|dprob| {dm:.3f}")
             assert _apart(ref, m, dtype), (dtype, mut)

@@ -1,5 +1,5 @@
 """The gated (SwiGLU) MLP without a GPU (include/vitx.h "gated MLP"): the loader's rules for the `glu` tensor, the file tools, the converter's opt-in
-path and the float64 restatement of tests/swiglu_data.py against transformers' Dinov2Model (use_swiglu_ffn) and DINOv3ViTModel (use_gated_mlp), the
+path and the float64 restatement of tests/ref64.py against transformers' Dinov2Model (use_swiglu_ffn) and DINOv3ViTModel (use_gated_mlp), the
 separation of the micro fixtures' mutants from operand rounding, and the share of the kernel test's exact grid at which each mutant shows."""
 import ctypes as C
 import hashlib
@@ -13,11 +13,13 @@ import pytest
 import arch_data as AD
 import map_data as MD
 import prefix_data as PD
+import ref64 as R64
 import rope_data as RD
 import swiglu_data as SD
 import text_data as TD
 from test_cpu_rope import _hf_dinov3
-from test_gpu_arch import PROB_TOL, ROUND, _apart, _stage_errors, _stage_ok
+from ref64 import PROB_TOL, stage_errors, stage_ok
+from test_gpu_arch import ROUND, _apart
 
 ERR_FORMAT = 2
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -244,14 +246,14 @@ def _against_transformers(pkg, binding, tmp_path, torch, m, heads, what, mutants
     with torch.no_grad():
         out = m(pixel_values=torch.from_numpy(imgs).permute(0, 3, 1, 2).contiguous())
     want = out.last_hidden_state.numpy()
-    r = SD.forward64(t, imgs, heads=heads)
+    r = R64.forward64(t, imgs, heads=heads)
     assert r["final"].shape == want.shape
     d = float(np.abs(r["final"] - want).max())
     print(f"{what}: max|restatement - transformers| = {d:.3e} on features of magnitude {np.abs(want).max():.2f}")
     assert d <= 1e-4, d                                                  # tests/test_cpu_rope.py's bound for the same comparison
     assert np.abs(r["final"][:, 0] - out.pooler_output.numpy()).max() <= 1e-4
     for mut in mutants:
-        dm = float(np.abs(SD.forward64(t, imgs, heads=heads, mutant=mut)["final"] - want).max())
+        dm = float(np.abs(R64.forward64(t, imgs, heads=heads, mutant=mut)["final"] - want).max())
         print(f"{what}: mutant {mut}: max|d| = {dm:.3f}")
         assert dm > 0.1, (mut, dm)
     mdl = binding.Model(path)
@@ -328,21 +330,21 @@ def test_default_refusals_and_the_switch(pkg, tmp_path):
 @pytest.mark.parametrize("kind", SD.FIXTURES)
 def test_fixtures_separate_the_mutants_from_operand_rounding(pkg, kind):
     """Computed, not assumed (swiglu_data.GLU_SCALE): on each micro fixture and the images of the GPU tests, the operand-rounded restatement lies
-    inside HALF of tests/test_gpu_arch.py's stage and probability gates of the unrounded one, and every mutant lies more than TWICE a gate from the
+    inside HALF of tests/ref64.py's stage and probability gates of the unrounded one, and every mutant lies more than TWICE a gate from the
     real thing -- so a GPU result inside the gates of the restatement is outside those of every mutant."""
     imgs = PD.exact_images(17, 56, seed=1)
     t = PD.file_tensors(pkg, SD.fixture_file(pkg, kind))
     assert SD.glu_of(t) == SD.F and (RD.rope_of(t) is not None) == (kind == "hplus")
-    exact = SD.forward64(t, imgs, SD.HEADS)
+    exact = R64.forward64(t, imgs, SD.HEADS)
     for dtype in (0, 1):
-        ref = SD.forward64(t, imgs, SD.HEADS, wround=ROUND[dtype], uround=ROUND[dtype])
-        se = _stage_errors(ref["trace"], exact["trace"])
+        ref = R64.forward64(t, imgs, SD.HEADS, wround=ROUND[dtype], uround=ROUND[dtype])
+        se = stage_errors(ref["trace"], exact["trace"])
         dp = float(np.abs(ref["probs"] - exact["probs"]).max())
         print(f"{kind} dtype {dtype}: rounded against unrounded: stages (e_max, e_rms) {[(round(a, 5), round(b, 5)) for a, b in se]}, max|dprob| {dp:.2e}")
-        assert all(_stage_ok(a, b, dtype, 0.5) for a, b in se) and dp <= 0.5 * PROB_TOL[dtype]
+        assert all(stage_ok(a, b, dtype, 0.5) for a, b in se) and dp <= 0.5 * PROB_TOL[dtype]
         for mut in SD.MUTANTS:
-            m = SD.forward64(t, imgs, SD.HEADS, mutant=mut, wround=ROUND[dtype], uround=ROUND[dtype])
-            sm = _stage_errors(m["trace"], ref["trace"])
+            m = R64.forward64(t, imgs, SD.HEADS, mutant=mut, wround=ROUND[dtype], uround=ROUND[dtype])
+            sm = stage_errors(m["trace"], ref["trace"])
             dm = float(np.abs(ref["probs"] - m["probs"]).max())
             print(f"{kind} dtype {dtype}: mutant {mut}: stages {[(round(a, 4), round(b, 4)) for a, b in sm]}, max|dprob| {dm:.3f}")
             assert _apart(ref, m, dtype), (kind, dtype, mut)

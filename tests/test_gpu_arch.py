@@ -1,6 +1,6 @@
 """Activation, LayerNorm epsilon and pre-norm on the GPU (include/vitx.h "activation, epsilon and pre-norm"): the two new fc1 epilogues on every
 GEMM family, the f32 LayerNorm, and the forward of the three model classes (HuggingFace ViT: erf-GELU, eps 1e-12; DINOv2: erf-GELU, cls + mean
-head; CLIP: QuickGELU, eps 1e-5, pre-norm) against the float64 restatement of tests/arch_data.py, which tests/test_cpu_arch.py pins to transformers.
+head; CLIP: QuickGELU, eps 1e-5, pre-norm) against the float64 restatement of tests/ref64.py, which tests/test_cpu_arch.py pins to transformers.
 
 What pins each activation.  The exact epilogue tests: their inputs make acc + bias an exact fp16 number on the grid x = k / 64 (+ 1 / 128 on odd rows),
 the bound is one ulp of the output type + 1e-6, and tests/test_cpu_arch.py shows that the float64 references themselves lie more than two such
@@ -17,6 +17,8 @@ import pytest
 import arch_data as AD
 import feature_data as FD
 import prefix_data as PD
+import ref64 as R64
+from ref64 import PROB_TOL, stage_errors, stage_ok
 
 pytestmark = pytest.mark.gpu
 
@@ -25,7 +27,6 @@ ROUND = {0: PD.f16_round, 1: PD.bf16_round}
 KERNELS = [1, 945, 445, 245, 122, 0, 2]            # tests/test_gpu_parity_r02.py KERNELS: vitx_op_gemm_ex kernel ids
 ERR_UNSUPPORTED = 5
 F16_ULP, BF16_ULP = 2.0 ** -10, 2.0 ** -7
-PROB_TOL = {0: 1e-3, 1: 2e-2}                      # tests/test_gpu_registers.py PROB_TOL
 SENT = 7.0
 
 
@@ -243,21 +244,8 @@ def _ref(pkg, kind, dtype, **mutant):
     key = (kind, dtype, tuple(sorted(mutant.items())))
     if key not in _REF:
         t = PD.file_tensors(pkg, AD.fixture_file(pkg, kind))
-        _REF[key] = (t, AD.forward64(t, _images(), H, wround=ROUND[dtype], uround=ROUND[dtype], **mutant))
+        _REF[key] = (t, R64.forward64(t, _images(), H, wround=ROUND[dtype], uround=ROUND[dtype], **mutant))
     return _REF[key]
-
-
-def _stage_errors(x, ref):
-    out = []
-    for il in range(1, x.shape[0]):
-        rms = float(np.sqrt((ref[il] ** 2).mean()))
-        out.append((float(np.abs(x[il] - ref[il]).max()) / rms, float(np.sqrt(((x[il] - ref[il]) ** 2).mean())) / rms))
-    return out
-
-
-def _stage_ok(e_max, e_rms, dtype, scale=1.0):
-    """tests/test_gpu_registers.py:65-67: F16 e_max <= 2.5e-2 and e_rms <= 2e-3; BF16 e_rms <= 2.5e-2."""
-    return (e_max <= scale * 2.5e-2 and e_rms <= scale * 2e-3) if dtype == 0 else e_rms <= scale * 2.5e-2
 
 
 def _check_trace(x, ref, dtype, where, stage0=True):
@@ -265,23 +253,23 @@ def _check_trace(x, ref, dtype, where, stage0=True):
         d0 = float(np.abs(x[0] - ref[0]).max()); g0 = 2e-5 * max(1.0, float(np.abs(ref[0]).max()))      # tests/test_gpu_registers.py:56
         print(f"{where} stage 0: max|d| {d0:.3e} (gate {g0:.3e})")
         assert d0 <= g0, (where, d0, g0)
-    for il, (e_max, e_rms) in enumerate(_stage_errors(x, ref), 1):
+    for il, (e_max, e_rms) in enumerate(stage_errors(x, ref), 1):
         print(f"{where} stage {il}: max|d| / rms {e_max:.3e}, rms(d) / rms {e_rms:.3e}")
-        assert _stage_ok(e_max, e_rms, dtype), (where, il, e_max, e_rms)
+        assert stage_ok(e_max, e_rms, dtype), (where, il, e_max, e_rms)
 
 
 def _outside(x, p, mut, dtype, ids):
     """The GPU result (trace x of images `ids`, probabilities p of the first len(p) images) fails at least one gate against the restatement `mut`."""
     if np.abs(p - mut["probs"][:len(p)]).max() > PROB_TOL[dtype]:
         return True
-    return any(not _stage_ok(a, b, dtype) for a, b in _stage_errors(x, mut["trace"][:, ids]))
+    return any(not stage_ok(a, b, dtype) for a, b in stage_errors(x, mut["trace"][:, ids]))
 
 
 def _apart(ref, mut, dtype):
     """The two restatements lie more than TWICE a gate apart: a result inside the gates of `ref` is then outside those of `mut`, whatever it is."""
     if np.abs(ref["probs"] - mut["probs"]).max() > 2 * PROB_TOL[dtype]:
         return True
-    return any(not _stage_ok(a, b, dtype, 2.0) for a, b in _stage_errors(mut["trace"], ref["trace"]))
+    return any(not stage_ok(a, b, dtype, 2.0) for a, b in stage_errors(mut["trace"], ref["trace"]))
 
 
 MUTANT = {"vit_erf": dict(activation=AD.ACT_TANH), "dinov2_erf": dict(activation=AD.ACT_TANH), "clip": dict(activation=AD.ACT_TANH), "eps_1e-2": dict(eps=1e-6)}
@@ -376,7 +364,7 @@ def test_q8_0_erf_file_matches_the_restatement_on_dequantised_weights(pkg, bindi
     t = PD.file_tensors(pkg, q8)
     assert AD.arch_of(t) == (AD.ACT_ERF, float(np.float32(1e-12)), False)
     imgs = _images()[:3]
-    ref = AD.forward64(t, imgs, H, wround=PD.f16_round, uround=PD.f16_round)
+    ref = R64.forward64(t, imgs, H, wround=PD.f16_round, uround=PD.f16_round)
     model = binding.Model(q8)
     assert model.activation == AD.ACT_ERF
     ctx = binding.Context(model, device=0, max_batch=3, dtype=0)
@@ -394,7 +382,7 @@ def test_clip_file_at_another_image_size(pkg, binding, torch_gpu):
     t = PD.file_tensors(pkg, path)
     imgs = PD.exact_images(n, 84, seed=84)
     pos = binding.pos_embed_resample(t["pos_embed"][0], 6, binding.POS_BICUBIC)
-    ref = AD.forward64(t, imgs, H, pos=pos, wround=ROUND[dtype], uround=ROUND[dtype])
+    ref = R64.forward64(t, imgs, H, pos=pos, wround=ROUND[dtype], uround=ROUND[dtype])
     model = binding.Model(path)
     ctx = binding.Context(model, device=0, max_batch=n, dtype=dtype, img_size=84)
     assert (ctx.tokens, ctx.grid) == (37, 6)

@@ -1,6 +1,6 @@
 """The attention-pooling (MAP) head of a model without a class token on the MI355X (include/vitx.h "no class token and the attention-pooling
 head"): the pooling kernel against float64, its leaks and drops, batch invariance, the patch embedding without a prefix row, and the forward end
-to end against tests/map_data.py's restatement (pinned to transformers' SiglipVisionModel in tests/test_cpu_map_head.py)."""
+to end against tests/ref64.py's restatement (pinned to transformers' SiglipVisionModel in tests/test_cpu_map_head.py)."""
 import functools
 
 import numpy as np
@@ -9,12 +9,14 @@ import pytest
 import arch_data as AD
 import map_data as MD
 import prefix_data as PD
+import ref64 as R64
+from ref64 import PROB_TOL, stage_errors, stage_ok
 
 pytestmark = pytest.mark.gpu
 
 D, L, H, P, S, N = 128, 2, 2, 14, 56, 16            # arch_data.MICRO without its class token
 ROUND = {0: PD.f16_round, 1: PD.bf16_round}
-PROB_TOL, COS_GPU, COS_CPU = MD.PROB_TOL, MD.COS_GPU, MD.COS_CPU      # the gates on e and their provenance: tests/map_data.py
+COS_GPU, COS_CPU = MD.COS_GPU, MD.COS_CPU      # the gates on e and their provenance: tests/map_data.py
 
 
 def _bits(a):
@@ -178,21 +180,8 @@ def _ref(pkg, dtype, path=None, **mutant):
     if key not in _REF:
         t = PD.file_tensors(pkg, path or MD.fixture_file(pkg))
         rnd = {} if dtype is None else dict(wround=ROUND[dtype], uround=ROUND[dtype])
-        _REF[key] = (t, MD.forward64(t, _images(), H, **rnd, **mutant))
+        _REF[key] = (t, R64.forward64(t, _images(), H, **rnd, **mutant))
     return _REF[key]
-
-
-def _stage_errors(x, ref):
-    out = []
-    for il in range(1, x.shape[0]):
-        rms = float(np.sqrt((ref[il] ** 2).mean()))
-        out.append((float(np.abs(x[il] - ref[il]).max()) / rms, float(np.sqrt(((x[il] - ref[il]) ** 2).mean())) / rms))
-    return out
-
-
-def _stage_ok(e_max, e_rms, dtype):
-    """tests/test_gpu_arch.py _stage_ok: F16 e_max <= 2.5e-2 and e_rms <= 2e-3; BF16 e_rms <= 2.5e-2."""
-    return (e_max <= 2.5e-2 and e_rms <= 2e-3) if dtype == 0 else e_rms <= 2.5e-2
 
 
 @pytest.mark.parametrize("dtype", [0, 1])
@@ -222,9 +211,9 @@ def test_forward_against_the_restatement(pkg, binding, torch_gpu, dtype):
     d0 = float(np.abs(x[0] - ref["trace"][0][ids]).max()); g0 = 2e-5 * max(1.0, float(np.abs(ref["trace"][0]).max()))
     print(f"dtype {dtype} stage 0: max|d| {d0:.3e} (gate {g0:.3e})")
     assert d0 <= g0                                                    # row b * N is patch 0 + pos[0]
-    for il, (e_max, e_rms) in enumerate(_stage_errors(x, ref["trace"][:, ids]), 1):
+    for il, (e_max, e_rms) in enumerate(stage_errors(x, ref["trace"][:, ids]), 1):
         print(f"dtype {dtype} stage {il}: max|d| / rms {e_max:.3e}, rms(d) / rms {e_rms:.3e}")
-        assert _stage_ok(e_max, e_rms, dtype), (il, e_max, e_rms)
+        assert stage_ok(e_max, e_rms, dtype), (il, e_max, e_rms)
     # the pooled embedding
     ctx.feat_enable(cls=True, mean=True, tokens=True)
     p17, lg17 = ctx.forward(imgs, want_logits=True)

@@ -16,8 +16,10 @@ import map_data as MD
 import pack_data as KD
 import prefix_data as PD
 import rect_data as XD
+import ref64 as R64
 import text_data as TD
-from test_gpu_arch import PROB_TOL, ROUND
+from ref64 import PROB_TOL
+from test_gpu_arch import ROUND
 
 pytestmark = pytest.mark.gpu
 
@@ -26,7 +28,7 @@ SENT = -12345.5            # f32 buffers
 SENT16 = -640.0             # 16-bit buffers: exact in fp16 and bf16
 COUNTS = (1, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 129, 197, 260, 577)
 GATE = PROB_TOL[1]          # the bf16 gate for both operand types: plain fp16 carries three more mantissa bits than bf16, so that gate bounds it
-TOKEN_GATE = 2.5e-2         # rms(d) <= 2.5e-2 rms on the final norm's patch rows: the bf16 stage gate of tests/test_gpu_arch.py, as test_gpu_rect.py applies it
+TOKEN_GATE = 2.5e-2         # rms(d) <= 2.5e-2 rms on the final norm's patch rows: the bf16 stage gate of tests/ref64.py, as test_gpu_rect.py applies it
 
 
 def _bits(a):
@@ -203,7 +205,7 @@ def _ref(pkg, binding, kind, dtype, mutant=None):
         T = 1 + (t["reg_token"].shape[1] if "reg_token" in t else 0)
         out = []
         for im in _pack(t["patch_embed.proj.weight"].shape[-1])[1]:
-            r = XD.forward64(t, im[None], mutant=mutant, wround=ROUND[dtype], uround=ROUND[dtype], binding=binding)
+            r = R64.forward64(t, im[None], XD.HEADS, mutant=mutant, wround=ROUND[dtype], uround=ROUND[dtype], binding=binding)
             out.append((r["probs"][0], r["final"][0, T:]))
         _REF[key] = out
     return _REF[key]
@@ -229,7 +231,7 @@ def _run_pack(binding, model, dtype, shapes, imgs, max_grids=0):
 @pytest.mark.parametrize("dtype", [0, 1])
 @pytest.mark.parametrize("kind", ["p16", "p14r4", "p14rope"])
 def test_mixed_pack_against_the_restatement_and_every_mutant(pkg, binding, torch_gpu, kind, dtype):
-    """Seven images of five grids in one forward (head dim 64).  Every image against rect_data.forward64 of its own shape: probabilities inside the
+    """Seven images of five grids in one forward (head dim 64).  Every image against ref64.forward64 of its own shape: probabilities inside the
     bf16 gate (both operand types) and the final norm's patch rows inside the bf16 stage gate; every mutant of rect_data fails one of the two for at
     least one image.  (Probabilities alone do not separate every mutant on shapes this small -- pos_transposed moves them by 0.016 at most on
     p14r4, computed on the restatement -- the patch rows do: 0.35 of their rms and more, 0.049 for rope_transposed.)"""

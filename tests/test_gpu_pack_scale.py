@@ -144,7 +144,7 @@ def _ref64(pkg, binding, key, dtype, i, mutant=None):
 @pytest.mark.parametrize("key,dtype", CASES)
 def test_probes_against_float64(pkg, binding, states, key, dtype):
     """The probes' bits are those of every rung (the test above), so the reference call's outputs stand for all of them: each probe against
-    rect_data.forward64 at its own shape (glu_hplus: its 2 x 2 probe against wide_data.forward64) inside GATE and TOKEN_GATE; every mutant of
+    ref64.forward64 at its own shape (glu_hplus: its 2 x 2 probe against wide_data.forward64) inside GATE and TOKEN_GATE; every mutant of
     pack_data.SCALE_MUTANTS outside one of them on at least one probe.  The preconditions are tests/test_cpu_pack.py::test_scale_probe_preconditions."""
     assert (GATE, TOKEN_GATE) == (KD.GATE, KD.TOKEN_GATE)
     s = states(key, dtype)

@@ -1,5 +1,5 @@
 """Rectangular contexts on the GPU (include/vitx.h "rectangular contexts"): the patch-embedding kernel bit for bit on exact data at rectangular
-grids, the forward of vitx_ctx_create_rect against the float64 restatement of tests/rect_data.py under the gates of tests/test_gpu_arch.py with
+grids, the forward of vitx_ctx_create_rect against the float64 restatement of tests/ref64.py under its gates with
 every mutant outside them, bit-equality with the square path, the persistent attention band, batch invariance, the outputs, the device
 preprocessing against the host's, the refusals, and vit_cli.py --img-fit and examples/embed_main.cpp --img-shape against the binding path."""
 import ctypes as C
@@ -8,12 +8,15 @@ import functools
 import numpy as np
 import pytest
 
+import arch_data as AD
 import feature_data as FD
 import prefix_data as PD
 import preproc_data as PPD
 import rect_data as XD
+import ref64 as R64
 import rope_data as RD
-from test_gpu_arch import PROB_TOL, ROUND, _check_trace, _outside
+from ref64 import PROB_TOL
+from test_gpu_arch import ROUND, _check_trace, _outside
 
 pytestmark = pytest.mark.gpu
 
@@ -124,7 +127,7 @@ def _ref(pkg, binding, kind, shape, dtype, mutant=None, n=17):
     """The restatement of the images of a (fixture, shape), once per (operand type, mutant)."""
     key = (kind, shape, dtype, mutant, n)
     if key not in _REF:
-        _REF[key] = XD.forward64(_tensors(pkg, kind), _images(*shape, n), mutant=mutant, wround=ROUND[dtype], uround=ROUND[dtype], binding=binding)
+        _REF[key] = R64.forward64(_tensors(pkg, kind), _images(*shape, n), XD.HEADS, mutant=mutant, wround=ROUND[dtype], uround=ROUND[dtype], binding=binding)
     return _REF[key]
 
 
@@ -270,7 +273,7 @@ def test_token_features_and_class_token_maps(pkg, binding, torch_gpu, kind, mode
     assert cls.shape == (n, L, H, N) and roll.shape == (n, N) and f["tokens"].shape == (n, gh * gw, D)
     assert np.abs(cls.sum(-1) - 1).max() <= 1e-5 and np.abs(roll.sum(-1) - 1).max() <= 1e-4
     assert ctx.attn_grid(cls).shape == (n, L, H, gh, gw) and np.array_equal(ctx.attn_grid(roll)[:, 1, 2], roll[:, T + gw + 2])
-    _, eps, _ = XD.AD.arch_of(t)
+    _, eps, _ = AD.arch_of(t)
     y64, bound = FD.features64(trace[L], t["norm.weight"], t["norm.bias"], eps)
     assert (np.abs(f["cls"] - y64[:, 0]) <= bound[:, 0]).all() and (np.abs(f["tokens"] - y64[:, T:]) <= bound[:, T:]).all()
     want = ref["final"][:n, T:]
@@ -286,7 +289,7 @@ def test_token_features_and_class_token_maps(pkg, binding, torch_gpu, kind, mode
     hd = D // H
     cos, sin = RD.table64(RD.rope_of(t), hd, gh, gw) if "rope" in t else (np.ones((gh * gw, hd // 2)), np.zeros((gh * gw, hd // 2)))
     for l in range(L):
-        q, k, _ = RD.qk64(t, trace[l], l, H, cos, sin, None, wround=rnd, uround=rnd)
+        q, k, _ = R64.qk64(t, trace[l], l, H, cos, sin, None, wround=rnd, uround=rnd)
         if not two_planes:
             q, k = rnd(q).astype(np.float64), rnd(k).astype(np.float64)
         m = PD.cls_maps64(q, k)

@@ -1,7 +1,7 @@
 """Rotary position embeddings on the GPU (include/vitx.h "rotary position embeddings"): vitx_op_rope bit for bit against the numpy-f32 restatement
 of its operation order (tests/rope_data.py::rope_bits) on the three operand forms, exact tables that name a fault, batch invariance, and the
 forward of the micro RoPE fixture (N = 21) against the float64 restatement that tests/test_cpu_rope.py pins to transformers' DINOv3ViTModel, under
-the gates of tests/test_gpu_arch.py -- with every mutant of rope_data.MUTANTS outside them."""
+the gates of tests/ref64.py -- with every mutant of rope_data.MUTANTS outside them."""
 import ctypes as C
 import functools
 
@@ -10,8 +10,10 @@ import pytest
 
 import feature_data as FD
 import prefix_data as PD
+import ref64 as R64
 import rope_data as RD
-from test_gpu_arch import PROB_TOL, ROUND, _check_trace, _outside
+from ref64 import PROB_TOL
+from test_gpu_arch import ROUND, _check_trace, _outside
 
 pytestmark = pytest.mark.gpu
 
@@ -181,7 +183,7 @@ def _ref(pkg, dtype, mutant=None):
     """The restatement of all 17 images, once per (operand type, mutant)."""
     if (dtype, mutant) not in _REF:
         t = PD.file_tensors(pkg, RD.fixture_file(pkg))
-        _REF[(dtype, mutant)] = (t, RD.forward64(t, _images(), H, mutant=mutant, wround=ROUND[dtype], uround=ROUND[dtype]))
+        _REF[(dtype, mutant)] = (t, R64.forward64(t, _images(), H, mutant=mutant, wround=ROUND[dtype], uround=ROUND[dtype]))
     return _REF[(dtype, mutant)]
 
 
@@ -249,7 +251,7 @@ def test_features_and_class_token_maps_read_rotated_q_and_k(pkg, binding, torch_
     for l in range(L):
         worst = {}
         for mut in (None, "no_rope"):
-            q, k, _ = RD.qk64(t, trace[l], l, H, cos, sin, mut, wround=rnd, uround=rnd)
+            q, k, _ = R64.qk64(t, trace[l], l, H, cos, sin, mut, wround=rnd, uround=rnd)
             if not two_planes:
                 q, k = rnd(q).astype(np.float64), rnd(k).astype(np.float64)
             ref = PD.cls_maps64(q, k)
@@ -283,8 +285,8 @@ def test_q8_0_file_matches_the_restatement_on_dequantised_weights(pkg, binding, 
     t = PD.file_tensors(pkg, q8)
     assert RD.rope_of(t) == RD.THETA
     imgs = _images()[:3]
-    ref = RD.forward64(t, imgs, H, wround=PD.f16_round, uround=PD.f16_round)
-    unrotated = RD.forward64(t, imgs, H, mutant="no_rope", wround=PD.f16_round, uround=PD.f16_round)
+    ref = R64.forward64(t, imgs, H, wround=PD.f16_round, uround=PD.f16_round)
+    unrotated = R64.forward64(t, imgs, H, mutant="no_rope", wround=PD.f16_round, uround=PD.f16_round)
     model = binding.Model(q8)
     assert model.rope == (1, RD.THETA)
     ctx = binding.Context(model, device=0, max_batch=3, dtype=0)
@@ -303,7 +305,7 @@ def test_context_at_another_image_size(pkg, binding, torch_gpu, tmp_path):
     path = RD.fixture_file(pkg)
     t = PD.file_tensors(pkg, path)
     imgs = PD.exact_images(n, 84, seed=84)
-    ref = RD.forward64(t, imgs, H, pos=np.zeros((37, D), np.float32), wround=ROUND[dtype], uround=ROUND[dtype])
+    ref = R64.forward64(t, imgs, H, pos=np.zeros((37, D), np.float32), wround=ROUND[dtype], uround=ROUND[dtype])
     big = str(tmp_path / "84.gguf")
     binding.resize_file(path, big, 84, binding.POS_BICUBIC)
     got = {}
@@ -318,7 +320,7 @@ def test_context_at_another_image_size(pkg, binding, torch_gpu, tmp_path):
     p, x = got["ctx"]
     _check_trace(x, ref["trace"], dtype, "rope at img_size 84")
     assert np.abs(p - ref["probs"]).max() <= PROB_TOL[dtype]
-    wrong = RD.forward64(t, imgs, H, pos=np.zeros((37, D), np.float32), mutant="wrong_grid", wround=ROUND[dtype], uround=ROUND[dtype])
+    wrong = R64.forward64(t, imgs, H, pos=np.zeros((37, D), np.float32), mutant="wrong_grid", wround=ROUND[dtype], uround=ROUND[dtype])
     assert _outside(x, p, wrong, dtype, list(range(n)))
     assert np.array_equal(_bits(p), _bits(got["file"][0])) and np.array_equal(_bits(x), _bits(got["file"][1]))
 

@@ -11,9 +11,11 @@ import pytest
 import arch_data as AD
 import feature_data as FD
 import prefix_data as PD
+import ref64 as R64
 import rope_data as RD
 import swiglu_data as SD
-from test_gpu_arch import PROB_TOL, ROUND, _check_trace, _outside
+from ref64 import PROB_TOL
+from test_gpu_arch import ROUND, _check_trace, _outside
 
 pytestmark = pytest.mark.gpu
 
@@ -140,7 +142,7 @@ def _ref(pkg, kind, dtype, mutant=None):
     key = (kind, dtype, mutant)
     if key not in _REF:
         t = PD.file_tensors(pkg, SD.fixture_file(pkg, kind))
-        _REF[key] = (t, SD.forward64(t, _images(), H, mutant=mutant, wround=ROUND[dtype], uround=ROUND[dtype]))
+        _REF[key] = (t, R64.forward64(t, _images(), H, mutant=mutant, wround=ROUND[dtype], uround=ROUND[dtype]))
     return _REF[key]
 
 
@@ -232,8 +234,8 @@ def test_q8_0_file_matches_the_restatement_on_dequantised_weights(pkg, binding, 
     t = PD.file_tensors(pkg, q8)
     assert SD.glu_of(t) == F
     imgs = _images()[:3]
-    ref = SD.forward64(t, imgs, H, wround=PD.f16_round, uround=PD.f16_round)
-    swapped = SD.forward64(t, imgs, H, mutant="gate_up_swapped", wround=PD.f16_round, uround=PD.f16_round)
+    ref = R64.forward64(t, imgs, H, wround=PD.f16_round, uround=PD.f16_round)
+    swapped = R64.forward64(t, imgs, H, mutant="gate_up_swapped", wround=PD.f16_round, uround=PD.f16_round)
     model = binding.Model(q8)
     assert model.glu == (1, F)
     ctx = binding.Context(model, device=0, max_batch=3, dtype=0)
@@ -269,7 +271,7 @@ def test_context_at_another_image_size(pkg, binding, torch_gpu):
     t = PD.file_tensors(pkg, path)
     imgs = PD.exact_images(n, 84, seed=84)
     pos = binding.pos_embed_resample(t["pos_embed"][0], 6, binding.POS_BICUBIC)
-    ref = SD.forward64(t, imgs, H, pos=pos, wround=ROUND[dtype], uround=ROUND[dtype])
+    ref = R64.forward64(t, imgs, H, pos=pos, wround=ROUND[dtype], uround=ROUND[dtype])
     model = binding.Model(path)
     ctx = binding.Context(model, device=0, max_batch=n, dtype=dtype, img_size=84)
     assert (ctx.tokens, ctx.grid) == (37, 6)
@@ -279,7 +281,7 @@ def test_context_at_another_image_size(pkg, binding, torch_gpu):
     ctx.close(); model.close()
     _check_trace(x, ref["trace"], dtype, "fixture g at img_size 84")
     assert np.abs(p - ref["probs"]).max() <= PROB_TOL[dtype]
-    wrong = SD.forward64(t, imgs, H, pos=pos, mutant="gate_up_swapped", wround=ROUND[dtype], uround=ROUND[dtype])
+    wrong = R64.forward64(t, imgs, H, pos=pos, mutant="gate_up_swapped", wround=ROUND[dtype], uround=ROUND[dtype])
     assert _outside(x, p, wrong, dtype, list(range(n)))
 
 

@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 
 import prefix_data as PD
+import ref64 as R64
 import wide_data as WD
 
 pytestmark = pytest.mark.gpu
@@ -154,8 +155,8 @@ def test_wide_batch_of_every_family(pkg, binding, torch_gpu, key, mode):
     # ---- the high-precision anchor: the fusing context's trace and probabilities of the boundary images against the float64 restatement
     ref = _ref(pkg, key, dtype)
     d = float(np.abs(probs[ids] - ref["probs"]).max())          # the untraced forward (class rows only in the last layer, where the model keeps that)
-    print(f"{where}: untraced forward: max|dprob| / gate {d / WD.PROB_TOL[dtype]:.3f}")
-    assert d <= WD.PROB_TOL[dtype]
+    print(f"{where}: untraced forward: max|dprob| / gate {d / R64.PROB_TOL[dtype]:.3f}")
+    assert d <= R64.PROB_TOL[dtype]
     ctx = ctxs["fused"]
     ctx.trace_enable(ids)
     p, _ = _run(torch, ctx, d_imgs, n)

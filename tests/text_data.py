@@ -4,20 +4,19 @@
 forward64(t, ids) restates the forward of a text-tower file in float64:
     X = tok[ids] + pos;  per layer: x += proj(attention(qkv(LN1 x))), x += fc2(act(fc1(LN2 x)));  e = head(LN_final(x[pooled]))
 with the file's activation, eps, causal mask and pooling rule (arch = {activation, eps, causal, eos + 1}: the FIRST position whose id is eos, or
-the last position).  `wround` is applied to every matrix, `uround` to every activation that enters a GEMM (and the attention operands), as in
-arch_data.forward64; `tround` to the token table (the f16 table of an ftype 1 file).
+the last position): the token-embedding front, the layer stack of ref64.blocks64, the pooling and the head.  `wround` is applied to every matrix,
+`uround` to every activation that enters a GEMM and to the stored qkv (the attention operands), `tround` to the token table (the f16 table of an
+ftype 1 file).
 
 The attention data: the cases of the issue, the causal staircase (every key of an (item, head) the same vector: every numerator exactly 1;
 v[j][d] = (2 j + 1) u_d, u_d a power of two: row t of the causal output is exactly (t + 1) u_d, every row of the unmasked output T u_d), and
 masked versions of exact_data's float64 reference and f32 emulation, made of exact_data's own functions row by row (row t of a causal
 attention IS the unmasked attention of query t over keys 0 .. t)."""
-import os
-
 import numpy as np
 
 import arch_data as AD
 import exact_data as X
-import prefix_data as PD
+import ref64 as R64
 import zs_data as Z
 
 ATTN_CASES = [(3, 1, 2, 64), (3, 15, 2, 64), (3, 16, 2, 64), (3, 17, 2, 64), (2, 33, 2, 72), (2, 64, 3, 64), (2, 77, 2, 64), (2, 128, 1, 128), (2, 77, 2, 8)]
@@ -127,14 +126,7 @@ def hf_model(family):
 
 def text_file(pkg, family, ftype=1):
     """Path of the (cached) text-tower file of a family's micro model."""
-    cache_dir = os.environ.get("VITX_CACHE", "/tmp/vitx_cache")
-    os.makedirs(cache_dir, exist_ok=True)
-    path = os.path.join(cache_dir, f"text-{family}-micro-ft{ftype}.gguf")
-    if not os.path.exists(path):
-        tmp = path + f".tmp{os.getpid()}"
-        pkg.convert.convert_hf_text_model(hf_model(family), tmp, ftype)
-        os.replace(tmp, path)
-    return path
+    return R64.cached_file(f"text-{family}-micro-ft{ftype}", lambda tmp: pkg.convert.convert_hf_text_model(hf_model(family), tmp, ftype))
 
 
 def prompts(family, n=N_PROMPTS, seed=PROMPT_SEED):
@@ -178,21 +170,9 @@ def forward64(t, ids, heads=HEADS, wround=None, uround=None, tround=None):
     n, T = ids.shape
     tok = f8(tround(t["token_embed.weight"]) if tround else t["token_embed.weight"])
     D = tok.shape[1]
-    L = 1 + max(int(k.split(".")[1]) for k in t if k.startswith("blocks."))
-    hd = D // heads
     x = tok[ids] + f8(t["pos_embed"]).reshape(T, D)
-    mask = np.where(np.arange(T)[None, :] > np.arange(T)[:, None], -np.inf, 0.0) if causal else np.zeros((T, T))
-    for i in range(L):
-        p = f"blocks.{i}."
-        v = lambda name: f8(t[p + name])
-        qkv = U(U(AD.layernorm64(x, v("norm1.weight"), v("norm1.bias"), eps)) @ W(t[p + "attn.qkv.weight"]).T + v("attn.qkv.bias"))
-        q, k, vv = (qkv[..., j * D:(j + 1) * D].reshape(n, T, heads, hd).transpose(0, 2, 1, 3) for j in range(3))
-        s = q @ k.transpose(0, 1, 3, 2) / np.sqrt(hd) + mask
-        a = np.exp(s - s.max(-1, keepdims=True)); a /= a.sum(-1, keepdims=True)
-        o = U((a @ vv).transpose(0, 2, 1, 3).reshape(n, T, D))
-        x = x + o @ W(t[p + "attn.proj.weight"]).T + v("attn.proj.bias")
-        h = U(AD.act64(U(AD.layernorm64(x, v("norm2.weight"), v("norm2.bias"), eps)) @ W(t[p + "mlp.fc1.weight"]).T + v("mlp.fc1.bias"), act))
-        x = x + h @ W(t[p + "mlp.fc2.weight"]).T + v("mlp.fc2.bias")
+    mask = np.where(np.arange(T)[None, :] > np.arange(T)[:, None], -np.inf, 0.0) if causal else None
+    x = R64.blocks64(t, x, heads, act, eps, mask=mask, wround=wround, uround=uround, round_qkv=True)[0]
     rows = x[np.arange(n), pooled_positions(ids, eos)]
     z = U(AD.layernorm64(rows, f8(t["norm.weight"]), f8(t["norm.bias"]), eps))
     return z @ W(t["head.weight"]).T + f8(t["head.bias"])

@@ -5,10 +5,10 @@ Shared by tests/test_cpu_wide_data.py, which checks without a GPU what tests/tes
 D = 512 is the smallest width at which a row block has a column-tile peer (two tiles exchange their statistics; D = 256 has one tile), three layers
 the smallest depth with a layer whose proj and fc2 are both fused and whose qkv and fc1 both consume a fused output: the last layer of a class-token
 model carries the class rows only (cls_tail) and is never fused.  Every fixture is built by its family's own fixture_tensors on that geometry
-(fixture_tensors below), with the q / k and head factors that D = 512 asks for (QK_WIDE, HEAD_WIDE, HEAD_WIDE_MAP); the float64 restatement and
-the mutants are that family's.
+(fixture_tensors below), with the q / k and head factors that D = 512 asks for (QK_WIDE, HEAD_WIDE, HEAD_WIDE_MAP); the mutants are
+that family's, the float64 restatement is tests/ref64.py.
 
-    key          family (restatement)         what it puts on the fused path
+    key          family (fixture builder)     what it puts on the fused path
     vit_erf      arch_data                    fc1 epilogue 6 (erf-GELU), eps 1e-12
     clip         arch_data                    fc1 epilogue 7 (QuickGELU), eps 1e-5, the pre-norm in place on X in front of layer 0
     dinov2_reg   prefix_data, 4 registers     5 prefix rows, the cls + mean head fed by the last layer's feature launch, never cls_tail
@@ -23,13 +23,13 @@ Mutants that no end-to-end gate can see are not listed: erf- against tanh-GELU (
 away (tests/test_gpu_arch.py asserts it in F16 alone as well; the families' builders take no other MLP scale).  The eps mutant of the two arch_data
 fixtures is 1e-2, as that file's `eps_1e-2` fixture has it the other way round.  rope_data's `rope_on_prefix` needs a patch row per prefix row."""
 import functools
-import os
 
 import numpy as np
 
 import arch_data as AD
 import map_data as MD
 import prefix_data as PD
+import ref64 as R64
 import rope_data as RD
 import swiglu_data as SD
 
@@ -37,7 +37,6 @@ NAME = "vit_wide_patch16_32"
 D, L, H, P, S = 512, 3, 8, 16, 32
 G2 = (S // P) ** 2                                  # patch rows of an image
 ROUND = {0: PD.f16_round, 1: PD.bf16_round}
-PROB_TOL = {0: 1e-3, 1: 2e-2}                       # tests/test_gpu_arch.py PROB_TOL
 F_WIDE, F_ODD = 1408, 1344
 # The q / k factor of the two rope fixtures.  rope_data.QK_SCALE = 12 makes the scores of unit size at D 128; q and k grow with sqrt(D), so at D 512
 # the same factor makes the softmaxes four times as peaked and F16 operand rounding alone moves the probabilities by 7 gates (measured by
@@ -60,7 +59,7 @@ class Fixture:
         self.cls_tail = not pool and not pooled_map      # context.cpp: the class-rows-only last layer of a class-token head
 
     def mutants(self, dtype):
-        """{name: forward64 arguments} of the mutants listed for operand type `dtype`."""
+        """{name: ref64.forward64 arguments} of the mutants listed for operand type `dtype`."""
         return {k: v for k, v in self._mutants.items() if dtype == 0 or k not in self._f16_only}
 
 
@@ -77,7 +76,6 @@ FIXTURES = {
     "glu_hplus": Fixture("glu", 5 + G2, 5, _GLU_MUTANTS, glu=F_WIDE, kind="hplus"),
     "glu_odd": Fixture("glu", 1 + G2, 1, _GLU_MUTANTS, pool=True, glu=F_ODD, kind="g", fusable=False),
 }
-FORWARD64 = {"arch": AD.forward64, "prefix": PD.forward64, "map": MD.forward64, "rope": RD.forward64, "glu": SD.forward64}
 
 
 # ------------------------------------------------------------------------------------------------ the files
@@ -106,21 +104,14 @@ def fixture_tensors(pkg, key):
 
 def fixture_file(pkg, key):
     """Path of the (cached) ftype-1 file of a wide fixture."""
-    cache_dir = os.environ.get("VITX_CACHE", "/tmp/vitx_cache")
-    os.makedirs(cache_dir, exist_ok=True)
-    path = os.path.join(cache_dir, f"wide-{NAME}-{key}-qk{QK_WIDE:g}-h{HEAD_WIDE_MAP if FIXTURES[key].map else HEAD_WIDE:g}-ft1.gguf")
-    if not os.path.exists(path):
-        hp, t = fixture_tensors(pkg, key)
-        tmp = path + f".tmp{os.getpid()}"
-        pkg.ggml_file.write_model(tmp, hp, t, ftype=1)
-        os.replace(tmp, path)
-    return path
+    return R64.cached_file(f"wide-{NAME}-{key}-qk{QK_WIDE:g}-h{HEAD_WIDE_MAP if FIXTURES[key].map else HEAD_WIDE:g}-ft1",
+                           lambda tmp: pkg.ggml_file.write_model(tmp, *fixture_tensors(pkg, key), ftype=1))
 
 
 def forward64(key, t, imgs, dtype=None, **mutant):
-    """The family's restatement of `imgs`; dtype 0 / 1: with that operand type's rounding on matrices and GEMM operands, None: without any."""
+    """ref64.forward64 of `imgs`; dtype 0 / 1: with that operand type's rounding on matrices and GEMM operands, None: without any."""
     rnd = {} if dtype is None else dict(wround=ROUND[dtype], uround=ROUND[dtype])
-    return FORWARD64[FIXTURES[key].family](t, imgs, H, **rnd, **mutant)
+    return R64.forward64(t, imgs, H, **rnd, **mutant)
 
 
 # ------------------------------------------------------------------------------------------------ the batch
@@ -189,30 +180,21 @@ def forced_tiles(key, tokens, traced=False):
     return launches(key, traced=traced)["fused"] // 2 * per_launch
 
 
-# ------------------------------------------------------------------------------------------------ the gates (tests/test_gpu_arch.py, tests/test_gpu_map_head.py)
-def stage_errors(x, ref):
-    """[(max|d| / rms, rms(d) / rms)] of stages 1 .. of x, ref [L + 1][n][N][D]: tests/test_gpu_arch.py _stage_errors."""
-    out = []
-    for il in range(1, x.shape[0]):
-        rms = float(np.sqrt((ref[il] ** 2).mean()))
-        out.append((float(np.abs(x[il] - ref[il]).max()) / rms, float(np.sqrt(((x[il] - ref[il]) ** 2).mean())) / rms))
-    return out
-
-
+# ------------------------------------------------------------------------------------------------ the gates (tests/ref64.py, tests/test_gpu_map_head.py)
 def stage_ratio(e_max, e_rms, dtype):
-    """Worst figure / gate of tests/test_gpu_arch.py _stage_ok: F16 e_max <= 2.5e-2 and e_rms <= 2e-3; BF16 e_rms <= 2.5e-2."""
-    return max(e_max / 2.5e-2, e_rms / 2e-3) if dtype == 0 else e_rms / 2.5e-2
+    """Worst figure / gate of ref64.stage_ok."""
+    return max(e_max / R64.F16_STAGE[0], e_rms / R64.F16_STAGE[1]) if dtype == 0 else e_rms / R64.BF16_STAGE_RMS
 
 
 def distance(key, got, ref, dtype, exact=None):
     """How far `got` (dict: trace [L + 1][n][N][D], probs [n][C]; the attention-pooling family: e [n][D] too) lies from the restatement `ref` of the
     same images, as the LARGEST figure / gate over the gates of that family's GPU test: <= 1 inside every gate, > 1 outside at least one.
-    trace stages and probabilities: tests/test_gpu_arch.py (_check_trace, _stage_ok, PROB_TOL); the attention-pooling family adds tests/test_gpu_map_head.py's two
+    trace stages and probabilities: tests/test_gpu_arch.py _check_trace (ref64.stage_ok, PROB_TOL); the attention-pooling family adds tests/test_gpu_map_head.py's two
     gates on e, which that test takes against the UNROUNDED restatement (`exact`; ref when None).  Returns (worst, {gate name: ratio})."""
-    r = {"probs": float(np.abs(got["probs"] - ref["probs"]).max()) / PROB_TOL[dtype]}
+    r = {"probs": float(np.abs(got["probs"] - ref["probs"]).max()) / R64.PROB_TOL[dtype]}
     if not FIXTURES[key].pre:       # stage 0, the patch embedding (tests/test_gpu_arch.py _check_trace; behind a pre-norm that test leaves it out)
         r["stage0"] = float(np.abs(got["trace"][0] - ref["trace"][0]).max()) / (2e-5 * max(1.0, float(np.abs(ref["trace"][0]).max())))
-    for il, (e_max, e_rms) in enumerate(stage_errors(got["trace"], ref["trace"]), 1):
+    for il, (e_max, e_rms) in enumerate(R64.stage_errors(got["trace"], ref["trace"]), 1):
         r[f"stage{il}"] = stage_ratio(e_max, e_rms, dtype)
     if FIXTURES[key].map:
         ex = ref if exact is None else exact

@@ -8,13 +8,12 @@ restate() takes the operands AS THE DEVICE MULTIPLIES THEM -- a and t already ro
 device is the f32 accumulation order of the products and expf.  device_operand() is the device's own arithmetic for a, operation for operation in
 f32 (zs_embed_kernel: lane l of a wave owns the 16-byte pieces l, l + 64, ... of the row and adds its squares in column order; the 64 partial sums
 meet in a butterfly; IEEE square root and division; RNE to the operand type)."""
-import os
-
 import numpy as np
 
 import arch_data as AD
 import map_data as MD
 import prefix_data as PD
+import ref64 as R64
 
 SOFTMAX, SIGMOID = 0, 1
 ROUND = {0: PD.f16_round, 1: PD.bf16_round}
@@ -113,15 +112,7 @@ def clip_tensors(pkg, name=AD.MICRO):
 
 
 def clip_file(pkg, ftype=1, name=AD.MICRO):
-    cache_dir = os.environ.get("VITX_CACHE", "/tmp/vitx_cache")
-    os.makedirs(cache_dir, exist_ok=True)
-    path = os.path.join(cache_dir, f"zs-clip-{name}-e{CLIP_E}-ft{ftype}.gguf")
-    if not os.path.exists(path):
-        hp, t = clip_tensors(pkg, name)
-        tmp = path + f".tmp{os.getpid()}"
-        pkg.ggml_file.write_model(tmp, hp, t, ftype=ftype)
-        os.replace(tmp, path)
-    return path
+    return R64.cached_file(f"zs-clip-{name}-e{CLIP_E}-ft{ftype}", lambda tmp: pkg.ggml_file.write_model(tmp, *clip_tensors(pkg, name), ftype=ftype))
 
 
 def model_file(pkg, family):
@@ -135,7 +126,7 @@ def images():
 def embedding64(pkg, family):
     """The float64 embedding of the 17 images under the file's restatement: the logits row (CLIP-class) or the pooled embedding e (SigLIP-class)."""
     t = PD.file_tensors(pkg, model_file(pkg, family))
-    return AD.forward64(t, images(), 2)["logits"] if family == "clip" else MD.forward64(t, images(), 2)["e"]
+    return R64.forward64(t, images(), 2)["logits" if family == "clip" else "e"]
 
 
 def bank(family, emb):
