@@ -1164,8 +1164,37 @@ int vitx_op_attention_generic(int dtype, const void *d_qkv, void *d_out, int n_i
  *                              point: it reads d_row0 back to build that count (synchronises); a packed context uploads both with one copy.
  *   vitx_op_rope_packed        vitx_op_rope on a pack: token t >= prefix of image i rotates by row t - prefix of the table that starts
  *                              d_table_off[i] floats into d_cos and d_sin; one launch for the pack; reads both tables back to check them (synchronises).
- * Not offered on packed contexts (each a later step): the opt-in heads (attention maps, zero-shot bank, gallery, dense, depth), the pooled
- * and attention-pooling heads, the F16 parity planes, LayerNorm fusion and sub-batch streams, a packed patch-embedding kernel, vitx_group_*. */
+ *
+ * The dense head on a pack (vitx_pack_dense_set): "dense prediction" above, word for word and per image -- the operand is RNE of the final-norm
+ * patch tokens of the selected layers, the logits come from the dispatcher GEMM with f32 accumulation, labels and scores from
+ * csrc/dense_resample.h -- with one label map per image AT ITS OWN SIZE, the maps end to end.  vitx_pack_dense_set has vitx_dense_set's
+ * meaning and checks (K <= 256, one to four layers, Dc = popcount(layer_mask) D, 0 = the last layer, finite W and bias, flags
+ * VITX_DENSE_SCORE | VITX_DENSE_LOGITS; W == NULL && K == 0: off, everything freed); max_pixels sizes the label and score buffers.
+ * VITX_ERR_UNSUPPORTED before any device call when the operand or logit rows of max_tokens rows leave the GEMMs' 32-bit byte window.  A
+ * refused set leaves the head that was set in place.  With no head set nothing is allocated or launched and the forward is unchanged.
+ * Per forward: as each selected layer finishes, ONE stand-alone LayerNorm over all rows of the pack writes that layer's column slot of the
+ * operand (the prefix rows are normalised too and never used); after the forward one GEMM over the pack's rows and ONE label launch
+ * (vitx_op_dense_labels_packed's kernel): m + 2 kernel launches more, counted by vitx_pack_launches.  The tables of the label launch ride in
+ * the call's one table upload.  By default image i's maps are h_i x w_i; vitx_pack_dense_out gives the NEXT forward call other shapes
+ * [n][2] = (out_h, out_w), e.g. the sizes of the originals before an aspect-preserving resize (NULL / n = 0 withdraws them); that call
+ * consumes them whether it runs or is refused.  VITX_ERR_ARG before the call's first device call, nothing launched or written, the context
+ * usable: an n that differs from the call's, a side below the image's grid or above 8192 (upsampling only), more than max_pixels output
+ * pixels in the call.  vitx_pack_dense_check is that text, host only; it returns pix0 [n + 1] (image i's maps are elements pix0[i] ..
+ * pix0[i + 1] - 1) and tile0 [n + 1] (the running count of the label launch's 64 x 16 tiles); either may be NULL.
+ * vitx_pack_dense_read (waits for the forward): labels [sum oh_i ow_i] u8 and score f32 the images end to end, logits [sum gh_i gw_i][K]
+ * the kept patch logits (VITX_DENSE_LOGITS).  vitx_pack_dense_device: the device label buffer (NULL while off).  vitx_pack_dense_scratch_bytes:
+ * the head's operand and logit scratch; all of the head's buffers count in vitx_pack_scratch_bytes.  An image's logits, labels and scores
+ * are a function of its own pixels, shape and output shape: the same bits alone, at any position and beside any neighbours; a pack of one
+ * shape gives the labels and kept logits of a rectangular context with the same head.
+ *   vitx_op_dense_labels_packed   the label kernel on a pack: d_logits [rows][ld], HOST grids [n][2] = (gh, gw), outs [n][2] = (oh, ow) and
+ *                              lrow [n] = image i's first logit row (its gh gw rows follow; rows between images are never read) -> d_labels u8
+ *                              and (or NULL) d_score f32, image i's maps with the bits of vitx_op_dense_labels on that image alone, the maps end
+ *                              to end; nothing else is written.  A work item is (image, 64 x 16 output tile), found by a binary search of the
+ *                              workgroup index in the running tile count.  vitx_op_dense_labels's checks per image.  TEST entry point: it builds
+ *                              and uploads the tables and frees them after the launch (synchronises).
+ * Not offered on packed contexts (each a later step): the other opt-in heads (attention maps, zero-shot bank, gallery, depth), the pooled
+ * and attention-pooling heads, the F16 parity planes, LayerNorm fusion and sub-batch streams, a packed patch-embedding kernel, vitx_group_*;
+ * of the dense head: downsampling, and a vit.h wrapper. */
 typedef struct vitx_pack vitx_pack;
 typedef struct { int pos_interp, max_grids, reserved[6]; } vitx_pack_options;
 int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_images, int dtype, const vitx_pack_options *opt, vitx_pack **out);
@@ -1186,6 +1215,20 @@ int vitx_op_attention_packed(int dtype, const void *d_qkv, void *d_out, const vo
 int vitx_op_attention_packed_tables(int dtype, const void *d_qkv, void *d_out, const void *d_row0, const void *d_qb0, int n, long qblocks, int D, int H, void *stream);
 int vitx_op_rope_packed(int dtype, void *d_qkv, long lo_off /* must be 0 */, const void *d_cos, const void *d_sin, const void *d_row0 /* int32 [n + 1] */,
                         const void *d_table_off /* int32 [n] */, int n, int prefix, int D, int H, void *stream);
+int vitx_pack_dense_set(vitx_pack *p, const float *W /* [K][Dc] */, const float *bias /* [K] or NULL */, int K, int Dc, uint64_t layer_mask, long max_pixels, int flags);
+int vitx_pack_dense_out(vitx_pack *p, const int32_t *out_shapes /* [n][2] = out_h, out_w; NULL: the images' own */, int n);
+/* host only: every refusal a forward call adds while a dense head of K classes and max_pixels is set */
+int vitx_pack_dense_check(const vitx_model *m, const int32_t *shapes, const int32_t *out_shapes /* or NULL */, int n, int K, long max_pixels,
+                          int64_t *pix0 /* [n + 1] or NULL */, int32_t *tile0 /* [n + 1] or NULL */);
+int vitx_pack_dense_read(vitx_pack *p, uint8_t *labels, float *score /* or NULL */, float *logits /* or NULL */);
+const void *vitx_pack_dense_device(const vitx_pack *p);
+size_t vitx_pack_dense_scratch_bytes(const vitx_pack *p);
+int vitx_op_dense_labels_packed(const void *d_logits, long ld, const int32_t *grids /* host [n][2] */, const int32_t *outs /* host [n][2] */,
+                                const int32_t *lrow /* host [n] */, int n, int K, void *d_labels, void *d_score /* or NULL */, void *stream);
+/* the same in two steps, for callers that keep the tables: host only, tab int32 [n + 1 + 10 n] (the running tile count, then a row per image), its
+ * tile count and widest window; then the launch on a table the caller uploaded and vouches for (only enqueues) */
+int vitx_dense_pack_tables(const int32_t *grids, const int32_t *outs, const int32_t *lrow, int n, int32_t *tab, int *tiles, int *cells);
+int vitx_op_dense_labels_packed_tables(const void *d_logits, long ld, const void *d_tab, int n, int tiles, int cells, int K, void *d_labels, void *d_score, void *stream);
 
 /* ---- MXFP8 operands (VITX_MXFP8, encoding above) ------------------------------- */
 /* Host encoder: x f32 [rows][K] -> q [rows][k_pad] e4m3 bytes + scales [rows][k_pad / 32] (k_pad >= K, a multiple of 32; columns

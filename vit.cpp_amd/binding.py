@@ -71,6 +71,8 @@ EXPORTS = [
     "vitx_rect_shape", "vitx_preprocess_rect", "vitx_preprocess_rect_device", "vitx_preprocess_rect_device_supports",
     "vitx_pack_create", "vitx_pack_free", "vitx_pack_shares_weights", "vitx_pack_check", "vitx_pack_distinct_grids", "vitx_pack_forward", "vitx_pack_forward_device",
     "vitx_pack_feat_enable", "vitx_pack_feat_read", "vitx_pack_scratch_bytes", "vitx_pack_launches", "vitx_op_attention_packed", "vitx_op_attention_packed_tables", "vitx_op_rope_packed",
+    "vitx_pack_dense_set", "vitx_pack_dense_out", "vitx_pack_dense_check", "vitx_pack_dense_read", "vitx_pack_dense_device", "vitx_pack_dense_scratch_bytes", "vitx_op_dense_labels_packed",
+    "vitx_dense_pack_tables", "vitx_op_dense_labels_packed_tables",
 ]
 
 
@@ -335,6 +337,17 @@ def lib():
             L.vitx_op_attention_packed.argtypes = [ip, vp, vp, vp, ip, ip, ip, vp]
             L.vitx_op_attention_packed_tables.argtypes = [ip, vp, vp, vp, vp, ip, C.c_long, ip, ip, vp]
             L.vitx_op_rope_packed.argtypes =[ip, vp, C.c_long, vp, vp, vp, vp, ip, ip, ip, ip, vp]
+        if hasattr(L, "vitx_pack_dense_set"):
+            i32p, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+            L.vitx_pack_dense_set.argtypes = [vp, fp, fp, ip, ip, C.c_uint64, C.c_long, ip]
+            L.vitx_pack_dense_out.argtypes = [vp, i32p, ip]
+            L.vitx_pack_dense_check.argtypes = [vp, i32p, i32p, ip, ip, C.c_long, C.POINTER(C.c_int64), i32p]
+            L.vitx_pack_dense_read.argtypes = [vp, C.POINTER(C.c_uint8), fp, fp]
+            L.vitx_pack_dense_device.restype = C.c_void_p; L.vitx_pack_dense_device.argtypes = [vp]
+            L.vitx_pack_dense_scratch_bytes.restype = C.c_size_t; L.vitx_pack_dense_scratch_bytes.argtypes = [vp]
+            L.vitx_op_dense_labels_packed.argtypes = [vp, C.c_long, i32p, i32p, i32p, ip, ip, vp, vp, vp]
+            L.vitx_dense_pack_tables.argtypes = [i32p, i32p, i32p, ip, i32p, C.POINTER(ip), C.POINTER(ip)]
+            L.vitx_op_dense_labels_packed_tables.argtypes = [vp, C.c_long, vp, ip, ip, ip, ip, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -1164,6 +1177,7 @@ class PackContext:
         opt = PackOptions(pos_interp=pos_interp, max_grids=max_grids)
         check(lib().vitx_pack_create(model._h, device, max_tokens, max_images, dtype, C.byref(opt), C.byref(self._h)), "vitx_pack_create")
         self._shapes = None; self._feat = 0
+        self._dense = self._dense_out = self._dense_shapes = None
 
     def close(self):
         if getattr(self, "_h", None) and self._h:
@@ -1183,7 +1197,9 @@ class PackContext:
             raise ValueError(f"pixels hold {x.size} floats, the shapes {int((s[:, 0].astype(np.int64) * s[:, 1]).sum()) * 3}")
         probs = np.empty((n, self.model.num_classes), np.float32); logits = np.empty_like(probs)
         fp = C.POINTER(C.c_float)
-        check(lib().vitx_pack_forward(self._h, x.ctypes.data_as(fp), s.ctypes.data_as(C.POINTER(C.c_int32)), n, probs.ctypes.data_as(fp), logits.ctypes.data_as(fp)), "vitx_pack_forward")
+        rc = lib().vitx_pack_forward(self._h, x.ctypes.data_as(fp), s.ctypes.data_as(C.POINTER(C.c_int32)), n, probs.ctypes.data_as(fp), logits.ctypes.data_as(fp))
+        self._dense_forward(s, rc == 0)
+        check(rc, "vitx_pack_forward")
         self._shapes = s
         return probs, logits
 
@@ -1198,7 +1214,9 @@ class PackContext:
     def forward_device(self, d_imgs: int, shapes, d_probs: int, d_logits: int = 0, stream: int = 0) -> None:
         """Device pointers, host shapes; only enqueues on `stream` (0 = the context's own stream)."""
         s = _pack_shapes(shapes)
-        check(lib().vitx_pack_forward_device(self._h, d_imgs, s.ctypes.data_as(C.POINTER(C.c_int32)), s.shape[0], d_probs, d_logits or None, stream or None), "vitx_pack_forward_device")
+        rc = lib().vitx_pack_forward_device(self._h, d_imgs, s.ctypes.data_as(C.POINTER(C.c_int32)), s.shape[0], d_probs, d_logits or None, stream or None)
+        self._dense_forward(s, rc == 0)
+        check(rc, "vitx_pack_forward_device")
         self._shapes = s
 
     def feat_enable(self, cls: bool = True, tokens: bool = False) -> None:
@@ -1224,6 +1242,88 @@ class PackContext:
             out.append(tok[at:at + a * b].reshape(a, b, D)); at += a * b
         return cls, out
 
+    def dense_set(self, weight: Optional[np.ndarray], bias: Optional[np.ndarray] = None, layers=None, max_pixels: int = 0, score: bool = False,
+                  logits: bool = False) -> None:
+        """A linear head `weight` [K, Dc] f32 (+ `bias` [K]) over the patch tokens of `layers` (indices; None: the last layer) for every later forward:
+        per image a label map u8 at the image's own shape (or dense_out's), with `score` the winner's value, with `logits` the patch logits
+        (vitx_pack_dense_set).  max_pixels: the output pixels one forward may hold (0: max_tokens x patch x patch, every image at its own shape).
+        weight None turns the output off and frees its buffers."""
+        if weight is None:
+            check(lib().vitx_pack_dense_set(self._h, None, None, 0, 0, 0, 0, 0), "vitx_pack_dense_set")
+            self._dense = None
+            return
+        w = np.ascontiguousarray(weight, dtype=np.float32)
+        if w.ndim != 2:
+            raise ValueError("dense_set: weight must be [K, Dc]")
+        b = None
+        if bias is not None:
+            b = np.ascontiguousarray(bias, dtype=np.float32)
+            if b.shape != (w.shape[0],):
+                raise ValueError("dense_set: bias must be [K]")
+        mask = 0
+        for l in ([] if layers is None else layers):
+            if not 0 <= int(l) < 64:
+                raise ValueError(f"dense_set: layer {l} outside 0 .. 63")
+            mask |= 1 << int(l)
+        P = self.model.hparams.patch_size
+        fp = C.POINTER(C.c_float)
+        check(lib().vitx_pack_dense_set(self._h, w.ctypes.data_as(fp), b.ctypes.data_as(fp) if b is not None else None, w.shape[0], w.shape[1], mask,
+                                        int(max_pixels) or self.max_tokens * P * P, (DENSE_SCORE if score else 0) | (DENSE_LOGITS if logits else 0)), "vitx_pack_dense_set")
+        self._dense = (w.shape[0], bool(score), bool(logits))
+        self._dense_out = self._dense_shapes = None
+
+    def dense_out(self, shapes) -> None:
+        """Output shapes [n][2] = (out_h, out_w) of the NEXT forward's label maps (vitx_pack_dense_out), e.g. the sizes of the originals; that forward
+        consumes them.  None withdraws them."""
+        if shapes is None:
+            check(lib().vitx_pack_dense_out(self._h, None, 0), "vitx_pack_dense_out")
+            self._dense_out = None
+            return
+        s = _pack_shapes(shapes)
+        check(lib().vitx_pack_dense_out(self._h, s.ctypes.data_as(C.POINTER(C.c_int32)), s.shape[0]), "vitx_pack_dense_out")
+        self._dense_out = s
+
+    def _dense_forward(self, s, ok: bool) -> None:
+        """Book-keeping of a forward call for dense_read: the call consumed dense_out's shapes; a call that ran fixed the shapes of its maps."""
+        out, self._dense_out = getattr(self, "_dense_out", None), None
+        if ok and getattr(self, "_dense", None):
+            self._dense_shapes = (s.copy(), (out if out is not None else s).copy())
+
+    def dense_read(self):
+        """(labels: a list of per-image [out_h_i, out_w_i] u8 arrays, scores: the same in f32 or None, logits: a list of [gh_i gw_i, K] f32 or None) of the
+        last forward made with the dense head set (vitx_pack_dense_read)."""
+        if not getattr(self, "_dense", None) or getattr(self, "_dense_shapes", None) is None:
+            e = VitxError("dense_read: no forward has run with a dense head set")
+            e.code = ERR_ARG
+            raise e
+        K, want_score, want_logits = self._dense
+        shapes, outs = self._dense_shapes
+        P = self.model.hparams.patch_size
+        px = [int(h) * int(w) for h, w in outs]
+        npatch = [(int(h) // P) * (int(w) // P) for h, w in shapes]
+        labels = np.empty(sum(px), np.uint8)
+        score = np.empty(sum(px), np.float32) if want_score else None
+        logits = np.empty((sum(npatch), K), np.float32) if want_logits else None
+        fp = C.POINTER(C.c_float)
+        check(lib().vitx_pack_dense_read(self._h, labels.ctypes.data_as(C.POINTER(C.c_uint8)), score.ctypes.data_as(fp) if want_score else None,
+                                         logits.ctypes.data_as(fp) if want_logits else None), "vitx_pack_dense_read")
+        lab, sc, lg, at, ar = [], [], [], 0, 0
+        for (oh, ow), p_, r_ in zip(outs, px, npatch):
+            lab.append(labels[at:at + p_].reshape(int(oh), int(ow)))
+            if want_score:
+                sc.append(score[at:at + p_].reshape(int(oh), int(ow)))
+            if want_logits:
+                lg.append(logits[ar:ar + r_])
+            at += p_; ar += r_
+        return lab, (sc if want_score else None), (lg if want_logits else None)
+
+    def dense_device(self) -> int:
+        """Device pointer of the label buffer (the maps of a forward end to end, u8), 0 while off."""
+        return int(lib().vitx_pack_dense_device(self._h) or 0)
+
+    def dense_scratch_bytes(self) -> int:
+        return int(lib().vitx_pack_dense_scratch_bytes(self._h))
+
     @property
     def shares_weights(self) -> bool:
         return bool(lib().vitx_pack_shares_weights(self._h))
@@ -1242,6 +1342,58 @@ class PackContext:
 def op_attention_packed(dtype: int, d_qkv: int, d_out: int, d_row0: int, n: int, D: int, H: int, stream: int = 0) -> None:
     """vitx_op_attention_packed: attention over a pack, image i = rows row0[i] .. row0[i + 1] - 1 (d_row0 int32 [n + 1] on the device)."""
     check(lib().vitx_op_attention_packed(dtype, d_qkv, d_out, d_row0, n, D, H, stream or None), "vitx_op_attention_packed")
+
+
+def pack_dense_check(model: Model, shapes, out_shapes, K: int, max_pixels: int):
+    """vitx_pack_dense_check (host only): (pix0 int64 [n + 1], tile0 int32 [n + 1]) of a packed forward of `shapes` [n][2] with a dense head of K classes and
+    max_pixels set -- image i's maps are elements pix0[i] .. pix0[i + 1] - 1, tile0 the running count of the label launch's 64 x 16 tiles -- or
+    VitxError for what such a forward refuses.  out_shapes [n][2] = (out_h, out_w), None: the images' own shapes."""
+    a = _pack_shapes(shapes)
+    o = None if out_shapes is None else _pack_shapes(out_shapes)
+    # the C call takes one n: a list of another length is refused there as a forward refuses it, through the n the head would see
+    n = a.shape[0]
+    if o is not None and o.shape[0] != n:
+        e = VitxError(f"vitx_pack_dense_check: output shapes were given for {o.shape[0]} images, the call has {n}")
+        e.code = ERR_ARG
+        raise e
+    pix0, tile0 = np.empty(n + 1, np.int64), np.empty(n + 1, np.int32)
+    i32p = C.POINTER(C.c_int32)
+    check(lib().vitx_pack_dense_check(model._h, a.ctypes.data_as(i32p), o.ctypes.data_as(i32p) if o is not None else None, n, K, max_pixels,
+                                      pix0.ctypes.data_as(C.POINTER(C.c_int64)), tile0.ctypes.data_as(i32p)), "vitx_pack_dense_check")
+    return pix0, tile0
+
+
+def op_dense_labels_packed(d_logits: int, ld: int, grids, outs, lrow, K: int, d_labels: int, d_score: int = 0, stream: int = 0) -> None:
+    """vitx_op_dense_labels_packed: the label kernel on a pack.  d_logits [rows, ld] f32 on the device; host grids [n][2] = (gh, gw), outs [n][2] =
+    (out_h, out_w), lrow [n] = each image's first logit row -> d_labels u8 (and d_score f32), the images' maps end to end."""
+    g, o = _pack_shapes(grids), _pack_shapes(outs)
+    r = np.ascontiguousarray(lrow, np.int32)
+    if o.shape != g.shape or r.shape != (g.shape[0],):
+        raise ValueError("op_dense_labels_packed: grids and outs are [n][2], lrow is [n]")
+    i32p = C.POINTER(C.c_int32)
+    check(lib().vitx_op_dense_labels_packed(d_logits or None, ld, g.ctypes.data_as(i32p), o.ctypes.data_as(i32p), r.ctypes.data_as(i32p), g.shape[0], K, d_labels or None,
+                                            d_score or None, stream or None), "vitx_op_dense_labels_packed")
+
+
+def dense_pack_tables(grids, outs, lrow):
+    """vitx_dense_pack_tables (host only): (tab int32 [n + 1 + 10 n], tiles, cells) -- the device table of the packed label launch, to be uploaded by
+    the caller for op_dense_labels_packed_tables."""
+    g, o = _pack_shapes(grids), _pack_shapes(outs)
+    r = np.ascontiguousarray(lrow, np.int32)
+    if o.shape != g.shape or r.shape != (g.shape[0],):
+        raise ValueError("dense_pack_tables: grids and outs are [n][2], lrow is [n]")
+    n = g.shape[0]
+    tab, tiles, cells = np.zeros(n + 1 + 10 * n, np.int32), C.c_int(), C.c_int()
+    i32p = C.POINTER(C.c_int32)
+    check(lib().vitx_dense_pack_tables(g.ctypes.data_as(i32p), o.ctypes.data_as(i32p), r.ctypes.data_as(i32p), n, tab.ctypes.data_as(i32p), C.byref(tiles), C.byref(cells)),
+          "vitx_dense_pack_tables")
+    return tab, tiles.value, cells.value
+
+
+def op_dense_labels_packed_tables(d_logits: int, ld: int, d_tab: int, n: int, tiles: int, cells: int, K: int, d_labels: int, d_score: int = 0, stream: int = 0) -> None:
+    """vitx_op_dense_labels_packed_tables: the packed label launch on a table of dense_pack_tables already on the device; only enqueues."""
+    check(lib().vitx_op_dense_labels_packed_tables(d_logits or None, ld, d_tab or None, n, tiles, cells, K, d_labels or None, d_score or None, stream or None),
+          "vitx_op_dense_labels_packed_tables")
 
 
 def op_rope_packed(dtype: int, d_qkv: int, d_cos: int, d_sin: int, d_row0: int, d_table_off: int, n: int, prefix: int, D: int, H: int, stream: int = 0) -> None:

@@ -15,6 +15,7 @@ directory-walk accuracy harness:
     python vit_cli.py -m model.gguf --gallery-build DIR --gallery-out g.npz [--nn-source embed|logits]   # embed DIR/<label>/* into a gallery
     python vit_cli.py -m model.gguf -i image.jpg --gallery g.npz -k 5 [--nn-temperature 0.07]   # the k nearest gallery images and the k-NN vote of their labels
     python vit_cli.py -m backbone.gguf -i image.jpg --dense-head head.npz --dense-out labels.pgm [--img-shape HxW | --img-fit SHORT]   # a label per pixel (P5 picture of class bytes)
+    python vit_cli.py -m backbone.gguf -i a.jpg,b.jpg --pack --img-fit SHORT --dense-head head.npz --dense-out PREFIX   # PREFIX.<i>.pgm per image, at each ORIGINAL's size
     python vit_cli.py -m backbone.gguf -i image.jpg --depth-head head.npz --depth-out depth.npy [--img-shape HxW | --img-fit SHORT]   # a depth per pixel (float32 .npy)
 
 --preprocess model follows the file's `preproc` tensor (include/vitx.h "each model's own preprocessing": what convert.py reads from a
@@ -198,7 +199,7 @@ def main(argv: List[str] | None = None) -> int:
     if bool(a.dense_head) != bool(a.dense_out):
         ap.error("--dense-head HEAD.npz and --dense-out PATH go together")
     if a.dense_head and (a.dir is not None or a.gallery_build or a.gallery):
-        ap.error("--dense-head labels the single image of -i")
+        ap.error("--dense-head labels the single image of -i (or, with --pack, each image of -i A.jpg,B.jpg,...)")
     if bool(a.depth_head) != bool(a.depth_out):
         ap.error("--depth-head HEAD.npz and --depth-out PATH.npy go together")
     if a.depth_head and (a.dir is not None or a.gallery_build or a.gallery or a.dense_head):
@@ -210,8 +211,9 @@ def main(argv: List[str] | None = None) -> int:
     if a.img_fit and a.dir is not None:
         ap.error("--img-fit takes its shape from the single image of -i, not --dir (use --img-shape HxW)")
     if a.pack and (not a.img_fit or a.dir is not None or a.dtype == "mxfp8" or a.attn_map or a.embed or a.zero_shot or a.text_model or a.gallery or a.gallery_build
-                   or a.dense_head or a.depth_head):
-        ap.error("--pack takes --img-fit SHORT, the images of -i A.jpg,B.jpg,... and --dtype f16 or bf16; a packed context has no opt-in outputs")
+                   or a.depth_head):
+        ap.error("--pack takes --img-fit SHORT, the images of -i A.jpg,B.jpg,... and --dtype f16 or bf16; of the opt-in outputs a packed context has the dense head "
+                 "(--dense-head HEAD.npz --dense-out PREFIX) only")
     if (a.img_shape or a.img_fit) and a.preprocess == "reference":
         ap.error("--preprocess reference resizes to squares only: not with --img-shape / --img-fit")
     rect = None                                          # (img_h, img_w) of a rectangular context
@@ -322,12 +324,29 @@ def main(argv: List[str] | None = None) -> int:
             pixels, shapes = binding.pack_images(imgs, pp_rect, a.img_fit, patch=model.hparams.patch_size)
             tokens = int(binding.pack_check(model, shapes, 2 ** 31 - 1, len(files))[-1])
             ctx = binding.PackContext(model, device=a.device, max_tokens=tokens, max_images=len(files), dtype=dt, pos_interp=geometry["pos_interp"])
+            if dense:
+                # a label map per image at the ORIGINAL's size (never below the patch grid: a tiny original keeps the preprocessed shape's side)
+                P = model.hparams.patch_size
+                outs = [(max(im.shape[0], h // P), max(im.shape[1], w // P)) for im, (h, w) in zip(imgs, shapes)]
+                ctx.dense_set(dense["weight"], dense["bias"], dense["layers"], max_pixels=sum(h * w for h, w in outs))
+                ctx.dense_out(outs)
             probs, _ = ctx.forward_flat(pixels, shapes)
+            maps = ctx.dense_read()[0] if dense else None
         except binding.VitxError as e:
             print(f"main: the packed forward failed: {e}", file=sys.stderr)
             return 1
-        for f, (h, w), p in zip(files, shapes, probs):
+        for k, (f, (h, w), p) in enumerate(zip(files, shapes, probs)):
             print(f"main: '{f}' at ({w} x {h})", file=sys.stderr)
+            if dense:
+                lab, path = maps[k], f"{a.dense_out}.{k}.pgm"
+                with open(path, "wb") as fo:
+                    fo.write(f"P5\n{lab.shape[1]} {lab.shape[0]}\n255\n".encode() + lab.tobytes())
+                print(f"main: wrote the {lab.shape[1]} x {lab.shape[0]} label map to '{path}'", file=sys.stderr)
+                share = np.bincount(lab.reshape(-1), minlength=dense["weight"].shape[0]) / lab.size
+                for c in np.argsort(-share, kind="stable")[:a.topk]:
+                    if share[c] > 0:
+                        print(f" > {dense['names'][c] if dense['names'] else f'class_{c}'} : {share[c]:.2f}")
+                continue
             for i, v in zip(*binding.topk(p, a.topk)):
                 print(f" > {model.label(i)} : {v:.2f}")
         return 0

@@ -1,112 +1,76 @@
-// dense_label.hip -- the label map of the dense head (vitx_dense_set, vitx_op_dense_labels; the contract: include/vitx.h "dense prediction"):
-// the K logit planes of an image's gh x gw patch grid resampled bilinearly to out_h x out_w (dense_resample.h: ONE definition of the weights and
-// of the value, shared with the host function) and arg-maxed over k < K in vitx_topk's order.
-//   logits [n * gh * gw][ld] f32 (row = image, then patch in raster order; columns K .. ld are never compared)
-//   -> labels [n][out_h][out_w] u8 and, score != nullptr, score [n][out_h][out_w] f32 = the winner's value.
-// A workgroup owns a kDenseTileW x kDenseTileH tile of one image's output.  The grid cells its pixels touch form a window of ncx x ncy cells
-// (upsampling only: at most one cell more than the tile's pixels per axis; at the usual scale 16 a 64 x 16 tile touches about 6 x 3); the window's
-// logits go to LDS as [cell][KCp] rows -- every logit loaded ONCE per workgroup, 16 bytes per lane, non-temporal (the GEMM wrote them one launch ago
-// and nothing reads them again) -- in chunks of KC classes when window x K does not fit the LDS budget; a lane keeps the running winner of its
-// 4 pixels (class, value) across chunks.  A lane reads the taps of 4 classes per ds_read_b128 and computes them as one vector (packed f32
-// multiplies and adds); KCp / 4 is odd, so the rows of neighbouring cells start in different 16-byte slots of the bank row.  Where the 4 pixels of
-// every lane of a wave share their two source columns -- always at the usual scales, 4 | 16 -- the four taps are read once for the 4 pixels.
-// Labels leave as one 4-byte store per lane, scores as one 16-byte store, where the row allows it (compact rows of out_w: a row whose start is
-// off the pack's boundary, and the last columns of a width that is no multiple of 4, go element by element).  No atomics; one writer per element.
-#include "device_common.h"
+// dense_label.hip -- the label map of the dense head (vitx_dense_set, vitx_op_dense_labels, vitx_pack_dense_set, vitx_op_dense_labels_packed; the
+// contract: include/vitx.h "dense prediction"): the K logit planes of an image's gh x gw patch grid resampled bilinearly to out_h x out_w
+// (dense_resample.h: ONE definition of the weights and of the value, shared with the host function) and arg-maxed over k < K in vitx_topk's order.
+// A workgroup owns a kDenseTileW x kDenseTileH tile of one image's output; what it does there is dense_tile (dense_tile.h), one text for both kernels:
+//   dense_label_kernel          images of ONE shape: logits [n * gh * gw][ld] f32 (row = image, then patch in raster order) -> labels [n][out_h][out_w]
+//                               u8 and, score != nullptr, score [n][out_h][out_w] f32 = the winner's value.  The grid is tiles x tiles x images.
+//   dense_label_packed_kernel   a PACK: image i has its own first logit row lrow_i, grid (gh_i, gw_i), output (oh_i, ow_i) and first output element
+//                               pix0_i (the maps end to end).  A work item is (image, tile) and the grid is sum_i tiles_i workgroups, so one 4096 x 4096
+//                               output beside two hundred 224 x 224 ones balances itself.  A workgroup finds its image by a wave-uniform binary search
+//                               of blockIdx.x in tile0 [n + 1], the running tile count, as attention_packed_kernel does with qb0: every load of the
+//                               search and of the image's table row has a uniform address.  The LDS of the launch and the class chunk come from the
+//                               largest window of any image of the call; an image's bits do not depend on them (dense_tile.h).  Only the rows
+//                               lrow_i .. lrow_i + gh_i gw_i - 1 are read, columns below K rounded up to 4; nothing outside elements pix0_0 .. pix0_n - 1
+//                               is written.
 #include "kernels.h"
-#include "dense_resample.h"
+#include "dense_tile.h"
 
 namespace vitx {
 
 namespace {
 
 constexpr int kDenseLds = 64 * 1024;           // dynamic LDS of one workgroup at most: two and more workgroups per CU inside gfx950's 160 KiB
-constexpr int kDensePack = 4;                  // pixels per lane: one row, consecutive x
-static_assert(kDenseTileW == 16 * kDensePack && kDenseTileH == 16, "256 lanes: 16 x 16, each with kDensePack pixels of a row");
 
 __global__ __launch_bounds__(256) void dense_label_kernel(const float *__restrict__ logits, long ld, int gh, int gw, int K, int out_h, int out_w,
                                                           float sy, float sx, uint8_t *__restrict__ labels, float *__restrict__ score,
                                                           int KC, int KCp, int cells_max) {
-    extern __shared__ f32x4 dense_lds[];       // [cell][KCp / 4] groups of 4 classes
-    const int KCq = KCp >> 2;
-    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    const int img = blockIdx.z, X0 = blockIdx.x * kDenseTileW, Y0 = blockIdx.y * kDenseTileH;
-    const int X1 = min(X0 + kDenseTileW - 1, out_w - 1), Y1 = min(Y0 + kDenseTileH - 1, out_h - 1);
-    // the window of grid cells: the source index grows with the target index, so the first pixel's i0 and the last pixel's i1 bound it
-    const int cx0 = dense_axis(gw, sx, X0).i0, cy0 = dense_axis(gh, sy, Y0).i0;
-    const int ncx = dense_axis(gw, sx, X1).i1 - cx0 + 1, ncy = dense_axis(gh, sy, Y1).i1 - cy0 + 1;
-    if (ncx * ncy > cells_max) return;         // workgroup-uniform; the launcher's bound on the window says never -- and nothing is written past the LDS if it were wrong
-    const int y = min(Y0 + ty, out_h - 1);     // lanes past the edge compute a pixel of the edge and store nothing
-    const DenseAxis ay = dense_axis(gh, sy, y);
-    const int r0 = (ay.i0 - cy0) * ncx - cx0, r1 = (ay.i1 - cy0) * ncx - cx0;
-    int o_a[kDensePack], o_b[kDensePack], o_c[kDensePack], o_d[kDensePack];        // the four taps' rows in the LDS image (in groups of 4 floats)
-    float hx[kDensePack], lx[kDensePack];
-    DenseBest best[kDensePack];
-#pragma unroll
-    for (int p = 0; p < kDensePack; ++p) {
-        const DenseAxis ax = dense_axis(gw, sx, min(X0 + tx * kDensePack + p, out_w - 1));
-        o_a[p] = (r0 + ax.i0) * KCq; o_b[p] = (r0 + ax.i1) * KCq; o_c[p] = (r1 + ax.i0) * KCq; o_d[p] = (r1 + ax.i1) * KCq;
-        hx[p] = ax.h; lx[p] = ax.l;
-        best[p] = dense_best_init();
+    const size_t img = blockIdx.z, px = (size_t)out_h * out_w;
+    dense_tile(logits + img * gh * gw * ld, ld, gh, gw, K, out_h, out_w, sy, sx, labels + img * px, score ? score + img * px : nullptr,
+               blockIdx.x * kDenseTileW, blockIdx.y * kDenseTileH, KC, KCp, cells_max);
+}
+
+// seg [n][kDenseSegInts]: dense_pack_seg's rows.  The scales are the host's dense_scale values, carried as bits.
+__global__ __launch_bounds__(256) void dense_label_packed_kernel(const float *__restrict__ logits, long ld, const int *__restrict__ tile0, const int *__restrict__ seg,
+                                                                 int n, int K, uint8_t *__restrict__ labels, float *__restrict__ score, int KC, int KCp, int cells_max) {
+    const int wg = blockIdx.x;
+    int lo = 0, hi = n;                        // the image: tile0[lo] <= wg < tile0[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (tile0[mid] <= wg) lo = mid; else hi = mid;
     }
-    // wave-uniform: the 4 pixels of every lane share the cell pair of pixel 0 (the taps are then read once per lane, not once per pixel)
-    const bool shared = __all(o_a[1] == o_a[0] && o_b[1] == o_b[0] && o_a[2] == o_a[0] && o_b[2] == o_b[0] && o_a[3] == o_a[0] && o_b[3] == o_b[0]);
-    const float *lg = logits + (size_t)img * gh * gw * ld;
-    const int K4 = (K + 3) & ~3, cells = ncx * ncy;
-    for (int k0 = 0; k0 < K4; k0 += KC) {
-        const int q4 = min(KC, K4 - k0) >> 2, total = cells * q4;
-        if (k0) __syncthreads();               // every lane has read the previous chunk
-        for (int idx = tid; idx < total; idx += 256) {
-            const int cell = idx / q4, q = idx - cell * q4, cy = cell / ncx, cx = cell - cy * ncx;
-            const f32x4 v = __builtin_nontemporal_load((const f32x4 *)(lg + ((size_t)(cy0 + cy) * gw + (cx0 + cx)) * ld + k0 + 4 * q));
-            dense_lds[cell * KCq + q] = v;
-        }
-        __syncthreads();
-        // 4 classes of one pixel: the value as a vector, then the classes in ascending order; a pad column never reaches the comparison
-        auto offer4 = [&](int p, int q, f32x4 a, f32x4 b, f32x4 c, f32x4 d) {
-            const f32x4 v = dense_value(hx[p], lx[p], ay.h, ay.l, a, b, c, d);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int k = k0 + 4 * q + e;
-                if (k < K) dense_offer(best[p], v[e], k);
-            }
-        };
-        if (shared) {
-            for (int q = 0; q < q4; ++q) {
-                const f32x4 a = dense_lds[o_a[0] + q], b = dense_lds[o_b[0] + q], c = dense_lds[o_c[0] + q], d = dense_lds[o_d[0] + q];
-#pragma unroll
-                for (int p = 0; p < kDensePack; ++p) offer4(p, q, a, b, c, d);
-            }
-        } else {
-            for (int q = 0; q < q4; ++q) {
-#pragma unroll
-                for (int p = 0; p < kDensePack; ++p)
-                    offer4(p, q, dense_lds[o_a[p] + q], dense_lds[o_b[p] + q], dense_lds[o_c[p] + q], dense_lds[o_d[p] + q]);
-            }
-        }
+    const int *s = seg + (size_t)lo * kDenseSegInts;
+    const int lrow = s[0], gh = s[1], gw = s[2], out_h = s[3], out_w = s[4];
+    const size_t pix0 = (size_t)(uint32_t)s[5] | ((size_t)(uint32_t)s[6] << 32);
+    const float sy = __int_as_float(s[7]), sx = __int_as_float(s[8]);
+    const int item = wg - tile0[lo], tw = (out_w + kDenseTileW - 1) / kDenseTileW, tyi = item / tw, txi = item - tyi * tw;
+    dense_tile(logits + (size_t)lrow * ld, ld, gh, gw, K, out_h, out_w, sy, sx, labels + pix0, score ? score + pix0 : nullptr,
+               txi * kDenseTileW, tyi * kDenseTileH, KC, KCp, cells_max);
+}
+
+// the window of a tile: the source positions of its first and last pixel lie (T - 1) * scale apart, so their cells at most floor of that + 1,
+// the second tap one more; one cell of margin for the rounding of the float positions.  The kernel checks its own window against the product.
+int dense_window(int gh, int gw, int out_h, int out_w) {
+    const float sy = dense_scale(gh, out_h), sx = dense_scale(gw, out_w);
+    return std::min(gw, (int)((kDenseTileW - 1) * sx) + 4) * std::min(gh, (int)((kDenseTileH - 1) * sy) + 4);
+}
+
+// the class chunk KC and the row stride KCp of the LDS image (an odd number of 16-byte slots) for a window of `cells`; false: nothing fits
+bool dense_chunk(int cells, int K, int *KC_out, int *KCp_out) {
+    int KC = (K + 3) & ~3, KCp = 0;
+    for (; KC >= 4; KC -= 4) {
+        KCp = KC + (((KC >> 2) & 1) ? 0 : 4);
+        if ((size_t)cells * KCp * 4 <= (size_t)kDenseLds) break;
     }
-    const int yy = Y0 + ty, x0 = X0 + tx * kDensePack;
-    if (yy >= out_h || x0 >= out_w) return;
-    const size_t pix = ((size_t)img * out_h + yy) * out_w + x0;
-    const bool whole = x0 + kDensePack <= out_w;
-    if (whole && ((uintptr_t)(labels + pix) & 3) == 0) {
-        *(uint32_t *)(labels + pix) = (uint32_t)best[0].cls | ((uint32_t)best[1].cls << 8) | ((uint32_t)best[2].cls << 16) | ((uint32_t)best[3].cls << 24);
-    } else {
-#pragma unroll
-        for (int p = 0; p < kDensePack; ++p) if (x0 + p < out_w) labels[pix + p] = (uint8_t)best[p].cls;
-    }
-    if (!score) return;
-    if (whole && ((uintptr_t)(score + pix) & 15) == 0) {
-        *(f32x4 *)(score + pix) = f32x4{dense_score(best[0]), dense_score(best[1]), dense_score(best[2]), dense_score(best[3])};
-    } else {
-#pragma unroll
-        for (int p = 0; p < kDensePack; ++p) if (x0 + p < out_w) score[pix + p] = dense_score(best[p]);
-    }
+    *KC_out = KC; *KCp_out = KCp;
+    return KC >= 4;                            // 67 x 19 cells x 12 floats fit: always
 }
 
 }  // namespace
 
-hipError_t prepare_dense() { return hipFuncSetAttribute((const void *)dense_label_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kDenseLds); }
+hipError_t prepare_dense() {
+    const hipError_t e = hipFuncSetAttribute((const void *)dense_label_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kDenseLds);
+    return e != hipSuccess ? e : hipFuncSetAttribute((const void *)dense_label_packed_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kDenseLds);
+}
 
 bool dense_labels_supports(long ld, int n, int gh, int gw, int K, int out_h, int out_w) {
     return n >= 1 && n <= 65535 && gh >= 1 && gw >= 1 && K >= 1 && K <= kDenseMaxK && out_h >= gh && out_w >= gw && out_h <= kDenseMaxOut && out_w <= kDenseMaxOut &&
@@ -116,18 +80,49 @@ bool dense_labels_supports(long ld, int n, int gh, int gw, int K, int out_h, int
 hipError_t launch_dense_labels(const float *logits, long ld, int n, int gh, int gw, int K, int out_h, int out_w, uint8_t *labels, float *score, hipStream_t stream) {
     if (!dense_labels_supports(ld, n, gh, gw, K, out_h, out_w) || ((uintptr_t)logits & 15)) return hipErrorInvalidValue;
     const float sy = dense_scale(gh, out_h), sx = dense_scale(gw, out_w);
-    // the window of a tile: the source positions of its first and last pixel lie (T - 1) * scale apart, so their cells at most floor of that + 1,
-    // the second tap one more; one cell of margin for the rounding of the float positions.  The kernel checks its own window against the product.
-    const int wx = std::min(gw, (int)((kDenseTileW - 1) * sx) + 4), wy = std::min(gh, (int)((kDenseTileH - 1) * sy) + 4), cells = wx * wy;
-    const int K4 = (K + 3) & ~3;
-    int KC = K4, KCp = 0;
-    for (; KC >= 4; KC -= 4) {
-        KCp = KC + (((KC >> 2) & 1) ? 0 : 4);          // row stride of the LDS image: an odd number of 16-byte slots
-        if ((size_t)cells * KCp * 4 <= (size_t)kDenseLds) break;
-    }
-    if (KC < 4) return hipErrorInvalidValue;           // 67 x 19 cells x 12 floats fit: not reached
+    const int cells = dense_window(gh, gw, out_h, out_w);
+    int KC, KCp;
+    if (!dense_chunk(cells, K, &KC, &KCp)) return hipErrorInvalidValue;
     const dim3 grid((out_w + kDenseTileW - 1) / kDenseTileW, (out_h + kDenseTileH - 1) / kDenseTileH, n);
     hipLaunchKernelGGL(dense_label_kernel, grid, dim3(256), (size_t)cells * KCp * 4, stream, logits, ld, gh, gw, K, out_h, out_w, sy, sx, labels, score, KC, KCp, cells);
+    return hipGetLastError();
+}
+
+bool dense_pack_tables(const int32_t *grids, const int32_t *outs, int n, int64_t *pix0, int32_t *tile0, int *cells) {
+    int64_t px = 0, tiles = 0;
+    int widest = 0;
+    for (int i = 0; i < n; ++i) {
+        const int gh = grids[2 * i], gw = grids[2 * i + 1], oh = outs[2 * i], ow = outs[2 * i + 1];
+        if (gh < 1 || gw < 1 || oh < gh || ow < gw || oh > kDenseMaxOut || ow > kDenseMaxOut) return false;
+        if (pix0) pix0[i] = px;
+        if (tile0) tile0[i] = (int32_t)tiles;
+        px += (int64_t)oh * ow;
+        tiles += (int64_t)((ow + kDenseTileW - 1) / kDenseTileW) * ((oh + kDenseTileH - 1) / kDenseTileH);
+        if (tiles > 0x7fffffff) return false;
+        widest = std::max(widest, dense_window(gh, gw, oh, ow));
+    }
+    if (pix0) pix0[n] = px;
+    if (tile0) tile0[n] = (int32_t)tiles;
+    if (cells) *cells = widest;
+    return true;
+}
+
+void dense_pack_seg(const int32_t *grids, const int32_t *outs, const int32_t *lrow, const int64_t *pix0, int n, int32_t *seg) {
+    for (int i = 0; i < n; ++i) {
+        int32_t *s = seg + (size_t)i * kDenseSegInts;
+        s[0] = lrow[i]; s[1] = grids[2 * i]; s[2] = grids[2 * i + 1]; s[3] = outs[2 * i]; s[4] = outs[2 * i + 1];
+        s[5] = (int32_t)(uint32_t)((uint64_t)pix0[i] & 0xffffffffu); s[6] = (int32_t)(uint32_t)((uint64_t)pix0[i] >> 32);
+        s[7] = __builtin_bit_cast(int32_t, dense_scale(s[1], s[3])); s[8] = __builtin_bit_cast(int32_t, dense_scale(s[2], s[4]));
+        s[9] = 0;
+    }
+}
+
+hipError_t launch_dense_labels_packed(const float *logits, long ld, const int *tile0, const int *seg, int n, int tiles, int cells, int K, uint8_t *labels, float *score,
+                                      hipStream_t stream) {
+    if (n < 1 || tiles < n || cells < 1 || K < 1 || K > kDenseMaxK || ld < ((K + 3) & ~3) || ld % 4 || ((uintptr_t)logits & 15) || !tile0 || !seg || !labels) return hipErrorInvalidValue;
+    int KC, KCp;
+    if (!dense_chunk(cells, K, &KC, &KCp)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dense_label_packed_kernel, dim3((unsigned)tiles), dim3(256), (size_t)cells * KCp * 4, stream, logits, ld, tile0, seg, n, K, labels, score, KC, KCp, cells);
     return hipGetLastError();
 }
 

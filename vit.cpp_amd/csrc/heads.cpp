@@ -68,6 +68,14 @@ hipError_t head_dense(const HeadLaunch &l, void *a, const void *W, const float *
     return launch_dense_labels(acc, Kpad, n, gh, gw, K, oh, ow, labels, score, l.st);
 }
 
+hipError_t head_dense_packed(const HeadLaunch &l, void *a, const void *W, const float *bias, float *acc, int rows, int K, int Dc, const int *tile0, const int *seg,
+                             int n, int tiles, int cells, long pixels, uint8_t *labels, float *score, float *keep) {
+    const int Kpad = round_up(K, gemm_tile_n());
+    HEAD_TRY(head_linear(l, PC_DENSE, a, W, bias, acc, rows, K, Dc, keep));
+    ProfScope ps(l.prof, l.st, PC_DENSE, 9.0 * (double)pixels * K, (double)rows * Kpad * 4 + (double)pixels * (score ? 5 : 1));
+    return launch_dense_labels_packed(acc, Kpad, tile0, seg, n, tiles, cells, K, labels, score, l.st);
+}
+
 hipError_t head_depth(const HeadLaunch &l, void *a, const void *Wp, const float *zero, float *acc, void *ac, const void *Wc, const float *bias, float *o,
                       const float *bins, int n, int gh, int gw, int K, int Dc, int u, int oh, int ow, float lo, float hi, float *fine, float *depth,
                       float *keep, float *keep_off) {

@@ -137,6 +137,18 @@ struct DenseHead : PatchHead {
     DevMem logits;               // VITX_DENSE_LOGITS: [cap][gh * gw][K] f32, the patch logits kept for vitx_dense_read
 };
 
+// the dense head of a packed context (vitx_pack_dense_set): the same linear map over ALL rows of the pack -- a[0] [round_up(max_tokens, tm)][Dc],
+// acc[0] the same rows x Kpad, the prefix rows computed and never used -- and one label map per image at its own size, the maps end to end
+struct PackDense : DenseHead {
+    long max_pixels = 0;         // elements of labels (and score); logits: [max_tokens][K], every row of the pack
+    size_t bytes = 0;            // device bytes of everything above: what the head adds to vitx_pack_scratch_bytes
+    std::vector<int32_t> next_out;       // vitx_pack_dense_out: the output shapes [n][2] of the next forward (empty: the images' own shapes)
+    std::vector<int32_t> grids, outs;    // [n][2] each, of the call being checked / the last forward made with the head set
+    std::vector<int64_t> pix0;   // [n + 1], the same
+    std::vector<int32_t> tile0;  // [n + 1], the same
+    int cells = 0;               // the widest tile window of that call
+};
+
 // the depth head (vitx_depth_set)
 struct DepthHead : PatchHead {
     DepthHead() : PatchHead("the depth head takes") {}
@@ -189,6 +201,10 @@ hipError_t head_linear(const HeadLaunch &l, int pc, void *a, const void *W, cons
 // The dense head after its operand rows are written: the patch logits (head_linear), then the label kernel
 hipError_t head_dense(const HeadLaunch &l, void *a, const void *W, const float *bias, float *acc, int n, int gh, int gw, int K, int Dc, int oh, int ow,
                       uint8_t *labels, float *score, float *keep);
+// The dense head of a pack after its operand rows are written: the logits of all `rows` rows of the pack (head_linear; keep: [rows][K]), then the
+// packed label kernel on the device tables tile0 / seg (kernels.h dense_pack_tables, dense_pack_seg).  2 launches.
+hipError_t head_dense_packed(const HeadLaunch &l, void *a, const void *W, const float *bias, float *acc, int rows, int K, int Dc, const int *tile0, const int *seg,
+                             int n, int tiles, int cells, long pixels, uint8_t *labels, float *score, float *keep);
 // The depth head after its operand rows are written: the patch logits with the zero bias, with a class half (Wc) the offsets from the class rows ac
 // with the head's bias (without: the bias is every image's offsets), the fine plane, the depth map
 hipError_t head_depth(const HeadLaunch &l, void *a, const void *Wp, const float *zero, float *acc, void *ac, const void *Wc, const float *bias, float *o,

@@ -235,6 +235,19 @@ hipError_t launch_nn_finish(const void *state, int n, int k, const int *labels, 
 constexpr int kDenseMaxK = 256, kDenseMaxOut = 8192;
 bool dense_labels_supports(long ld, int n, int gh, int gw, int K, int out_h, int out_w);
 hipError_t launch_dense_labels(const float *logits, long ld, int n, int gh, int gw, int K, int out_h, int out_w, uint8_t *labels, float *score, hipStream_t stream);
+// The same on a PACK (include/vitx.h "packed batches", the dense head): image i has its own first logit row lrow[i], grid grids[i] = (gh, gw) and output
+// outs[i] = (oh, ow); its maps start pix0[i] elements into labels and score (the maps end to end), bit for bit what launch_dense_labels writes for it alone.
+//   dense_pack_tables   host only, the one place the tables are built (the launch, vitx_pack_dense_check and a later head on packs): pix0 [n + 1] = the
+//                       running pixel count, tile0 [n + 1] = the running count of kDenseTileW x kDenseTileH tiles, *cells = the widest tile window of any
+//                       image (it sizes the LDS and the class chunk of the launch); any of the three may be NULL.  false: a grid below 1, an output
+//                       outside grid .. kDenseMaxOut, or more than 2^31 - 1 tiles.
+//   dense_pack_seg      the device table's rows seg [n][kDenseSegInts]: lrow, gh, gw, oh, ow, pix0 (low, high word), the bits of dense_scale for y and x, 0
+//   launch_dense_labels_packed   tile0 and seg on the device; tiles = tile0[n] and cells from dense_pack_tables: the caller built the tables
+constexpr int kDenseSegInts = 10;
+bool dense_pack_tables(const int32_t *grids, const int32_t *outs, int n, int64_t *pix0, int32_t *tile0, int *cells);
+void dense_pack_seg(const int32_t *grids, const int32_t *outs, const int32_t *lrow, const int64_t *pix0, int n, int32_t *seg);
+hipError_t launch_dense_labels_packed(const float *logits, long ld, const int *tile0, const int *seg, int n, int tiles, int cells, int K, uint8_t *labels, float *score,
+                                      hipStream_t stream);
 // The tail of the depth head (depth_map.hip; include/vitx.h "depth estimation"; the arithmetic: dense_resample.h + depth_bins.h).
 //   depth_fine:   logits [n * gh * gw][ld] f32 (ld a multiple of 4, at least K rounded up to 4; columns K .. ld never summed; 16-byte aligned) + offsets
 //                 (row img * ldo, ldo floats apart -- ldo == 0: one row for every image; nullptr: nothing is added), bins [K] -> fine [n][u gh][u gw] f32

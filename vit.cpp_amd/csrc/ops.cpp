@@ -457,6 +457,48 @@ int vitx_op_dense_labels(const void *d_logits, long ld, int n, int gh, int gw, i
     if ((uintptr_t)d_logits % 16 || (uintptr_t)d_score % 4) { set_error("vitx_op_dense_labels: d_logits must be 16-byte, d_score 4-byte aligned"); return VITX_ERR_ARG; }
     return op_rc("vitx_op_dense_labels", launch_dense_labels((const float *)d_logits, ld, n, gh, gw, K, out_h, out_w, (uint8_t *)d_labels, (float *)d_score, (hipStream_t)stream), VITX_ERR_UNSUPPORTED);
 }
+// The label kernel on a pack (include/vitx.h "packed batches"): vitx_op_dense_labels's checks image by image, the tables built by the one host
+// function (dense_pack_tables) and uploaded in one copy -- tile0 [n + 1] | seg [n][kDenseSegInts] -- then the launch.  A test entry point: it waits
+// for the launch before it frees the tables.
+int vitx_op_dense_labels_packed(const void *d_logits, long ld, const int32_t *grids, const int32_t *outs, const int32_t *lrow, int n, int K, void *d_labels, void *d_score,
+                                void *stream) {
+    const char *name = "vitx_op_dense_labels_packed";
+    if (!grids || !outs || !lrow || n < 1) { set_error("%s: invalid argument", name); return VITX_ERR_ARG; }
+    for (int i = 0; i < n; ++i) {
+        if (const int rc = dense_label_args(name, d_logits, ld, 1, grids[2 * i], grids[2 * i + 1], K, outs[2 * i], outs[2 * i + 1], d_labels)) return rc;
+        if (lrow[i] < 0 || (size_t)lrow[i] + (size_t)grids[2 * i] * grids[2 * i + 1] > 0x7fffffffu) { set_error("%s: image %d: first logit row %d", name, i, lrow[i]); return VITX_ERR_ARG; }
+    }
+    if ((uintptr_t)d_logits % 16 || (uintptr_t)d_score % 4) { set_error("%s: d_logits must be 16-byte, d_score 4-byte aligned", name); return VITX_ERR_ARG; }
+    std::vector<int64_t> pix0((size_t)n + 1);
+    std::vector<int32_t> tab((size_t)n + 1 + (size_t)n * kDenseSegInts);
+    int cells = 0;
+    if (!dense_pack_tables(grids, outs, n, pix0.data(), tab.data(), &cells)) { set_error("%s: the outputs hold more than 2^31 - 1 tiles", name); return VITX_ERR_UNSUPPORTED; }
+    dense_pack_seg(grids, outs, lrow, pix0.data(), n, tab.data() + n + 1);
+    int *d_tab = nullptr;
+    HIP_TRY(hipMalloc((void **)&d_tab, tab.size() * 4));
+    const DevMem own(d_tab);
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
+    const hipError_t e = launch_dense_labels_packed((const float *)d_logits, ld, d_tab, d_tab + n + 1, n, tab[n], cells, K, (uint8_t *)d_labels, (float *)d_score, st);
+    const hipError_t es = hipStreamSynchronize(st);      // the tables are freed, and the staging vector goes, when this returns
+    if (e == hipSuccess && es != hipSuccess) return op_rc(name, es);
+    return op_rc(name, e, VITX_ERR_UNSUPPORTED);
+}
+// The two halves of the above for callers that keep the tables (tools/pack_dense_cost.py times the launch alone): the host builder -- tab =
+// tile0 [n + 1] | seg [n][kDenseSegInts], *tiles = tile0[n], *cells = the widest window -- and the launch on such a table uploaded by the caller.
+int vitx_dense_pack_tables(const int32_t *grids, const int32_t *outs, const int32_t *lrow, int n, int32_t *tab, int *tiles, int *cells) {
+    if (!grids || !outs || !lrow || !tab || !tiles || !cells || n < 1) { set_error("vitx_dense_pack_tables: invalid argument"); return VITX_ERR_ARG; }
+    std::vector<int64_t> pix0((size_t)n + 1);
+    if (!dense_pack_tables(grids, outs, n, pix0.data(), tab, cells)) { set_error("vitx_dense_pack_tables: an output outside its grid .. %d, or more than 2^31 - 1 tiles", kDenseMaxOut); return VITX_ERR_UNSUPPORTED; }
+    dense_pack_seg(grids, outs, lrow, pix0.data(), n, tab + n + 1);
+    *tiles = tab[n];
+    return VITX_OK;
+}
+int vitx_op_dense_labels_packed_tables(const void *d_logits, long ld, const void *d_tab, int n, int tiles, int cells, int K, void *d_labels, void *d_score, void *stream) {
+    if (!d_logits || !d_tab || !d_labels || (uintptr_t)d_logits % 16 || (uintptr_t)d_score % 4 || (uintptr_t)d_tab % 4) { set_error("vitx_op_dense_labels_packed_tables: invalid argument"); return VITX_ERR_ARG; }
+    return op_rc("vitx_op_dense_labels_packed_tables", launch_dense_labels_packed((const float *)d_logits, ld, (const int *)d_tab, (const int *)d_tab + n + 1, n, tiles, cells, K,
+                                                                                     (uint8_t *)d_labels, (float *)d_score, (hipStream_t)stream), VITX_ERR_UNSUPPORTED);
+}
 // The host twin: dense_resample.h's arithmetic in plain loops, the classes of a pixel walked upwards.  No device call.
 int vitx_dense_labels_host(const float *logits, long ld, int n, int gh, int gw, int K, int out_h, int out_w, uint8_t *labels, float *score) {
     if (const int rc = dense_label_args("vitx_dense_labels_host", logits, ld, n, gh, gw, K, out_h, out_w, labels)) return rc;

@@ -2,7 +2,9 @@
 // h_i x w_i, their tokens end to end in one [sum N_i][D] residual stream, one forward.  Modelled on the text context (text_context.h): its own
 // scratch, one stream, no sub-batches, no graph cache, no LayerNorm fusion.  Internal: callers see the opaque vitx_pack of include/vitx.h.
 #pragma once
-#include "weights.h"
+#include <memory>
+
+#include "heads.h"
 
 using namespace vitx;
 
@@ -36,7 +38,8 @@ struct vitx_pack {
     float *logits = nullptr, *probs = nullptr;      // [Bpad][C_pad], [max_images][C] f32
     float *logits_out = nullptr;         // [max_images][C] f32: the dense logits of the host entry point
     float *img = nullptr;                // the host entry point's pixels on the device (allocated by its first call)
-    // the segment tables of a call: row0 [cap + 1] | qb0 [cap + 1] | toff [cap] (cap = max_images), one buffer, one upload
+    // the segment tables of a call: row0 [cap + 1] | qb0 [cap + 1] | toff [cap] (cap = max_images) and, while a dense head is set, behind them
+    // tile0 [cap + 1] | seg [cap][kDenseSegInts] (kernels.h): one buffer, one upload
     int *tab = nullptr;
     std::vector<int> host;               // the same on the host: the staging buffer of the upload
     std::vector<int32_t> chk, row0;      // [cap + 1] each: the rows of the call being checked; of the last call that passed its checks (vitx_pack_feat_read)
@@ -51,6 +54,7 @@ struct vitx_pack {
     int feat_flags = 0;                  // vitx_pack_feat_enable
     float *feat = nullptr;               // [max_tokens][D] f32 final-norm rows of the last forward (allocated by vitx_pack_feat_enable)
     int feat_n = 0;                      // images of the last forward with features on (0: none)
+    std::unique_ptr<PackDense> dense;    // vitx_pack_dense_set (null: off); its device memory is its own
     int launches = 0, pe_launches = 0;   // kernel launches of the last forward, and how many of them were patch embeddings
     size_t scratch_bytes = 0;            // device bytes of activation scratch and tables held now
     ~vitx_pack() {

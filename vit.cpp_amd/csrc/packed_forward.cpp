@@ -2,12 +2,15 @@
 // to end in one residual stream, one forward.  The blocks are the image forward's row-wise launches through the same dispatchers (GEMMs,
 // LayerNorm, activation, gate, pre-norm do not care where one image ends); new are the three launches that must know: the variable-length
 // attention (attention_packed.hip), the rotary embeddings by a segment table (rope.hip) and the class-row gather (text_embed.hip).  The patch
-// embedding is the rectangular context's kernel, one launch per run of consecutive images of one shape.
+// embedding is the rectangular context's kernel, one launch per run of consecutive images of one shape.  The one opt-in head is the dense head
+// (vitx_pack_dense_set): the stand-alone LayerNorm and the head GEMM over all rows of the pack, then the label launch by its own segment table
+// (dense_label.hip), one map per image at its own size.
 // One stream, no sub-batch split, no hipGraph cache, no LayerNorm fusion, no class-token tail; block matrices are expanded at upload, as in
 // the text context (text_forward.cpp).
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <new>
 
 #include "packed_context.h"
@@ -29,6 +32,35 @@ int check_shapes(const char *api, const vitx_model *m, const int32_t *shapes, in
         if (rows > max_tokens) { set_error("%s: images 0 .. %d hold %ld tokens, above max_tokens = %d", api, i, rows, max_tokens); return VITX_ERR_ARG; }
     }
     if (row0) row0[n] = (int32_t)rows;
+    return VITX_OK;
+}
+
+// What a forward call adds to check_shapes while a dense head of K classes and max_pixels is set (vitx_pack_dense_check's text; `shapes` has passed
+// check_shapes): the output shapes -- out_shapes [n_out][2], or the images' own -- against the grids and the buffers.  On success the call's
+// tables: grids and outs [n][2], pix0 and tile0 [n + 1] (any may be NULL), *cells (dense_pack_tables).
+int check_dense(const char *api, const vitx_model *m, const int32_t *shapes, const int32_t *out_shapes, int n_out, int n, int K, long max_pixels, int32_t *grids,
+                int32_t *outs, int64_t *pix0, int32_t *tile0, int *cells) {
+    if (K < 1) { set_error("%s: K = %d classes", api, K); return VITX_ERR_ARG; }
+    if (K > kDenseMaxK) { set_error("%s: K = %d classes above %d (labels are bytes)", api, K, kDenseMaxK); return VITX_ERR_UNSUPPORTED; }
+    if (max_pixels < 1) { set_error("%s: max_pixels = %ld", api, max_pixels); return VITX_ERR_ARG; }
+    if (out_shapes && n_out != n) { set_error("%s: output shapes were given for %d images, the call has %d", api, n_out, n); return VITX_ERR_ARG; }
+    const int P = m->hp.patch_size;
+    std::vector<int32_t> g((size_t)2 * n), o((size_t)2 * n);
+    std::vector<int64_t> px((size_t)n + 1);
+    for (int i = 0; i < n; ++i) {
+        const int gh = shapes[2 * i] / P, gw = shapes[2 * i + 1] / P;
+        const int oh = out_shapes ? out_shapes[2 * i] : shapes[2 * i], ow = out_shapes ? out_shapes[2 * i + 1] : shapes[2 * i + 1];
+        if (oh < gh || ow < gw || oh > kDenseMaxOut || ow > kDenseMaxOut) {
+            set_error("%s: image %d: output %d x %d outside the patch grid %d x %d .. %d (upsampling only)", api, i, oh, ow, gh, gw, kDenseMaxOut);
+            return VITX_ERR_ARG;
+        }
+        g[2 * i] = gh; g[2 * i + 1] = gw; o[2 * i] = oh; o[2 * i + 1] = ow;
+    }
+    if (!dense_pack_tables(g.data(), o.data(), n, px.data(), tile0, cells)) { set_error("%s: the call's outputs hold more than 2^31 - 1 tiles", api); return VITX_ERR_ARG; }
+    if (px[n] > (int64_t)max_pixels) { set_error("%s: the call's outputs hold %lld pixels, above max_pixels = %ld", api, (long long)px[n], max_pixels); return VITX_ERR_ARG; }
+    if (grids) std::copy(g.begin(), g.end(), grids);
+    if (outs) std::copy(o.begin(), o.end(), outs);
+    if (pix0) std::copy(px.begin(), px.end(), pix0);
     return VITX_OK;
 }
 
@@ -140,6 +172,16 @@ int pack_forward(vitx_pack *p, const float *d_imgs, const int32_t *shapes, int n
         h_toff[i] = (int)find_grid(p, shapes[2 * i] / P, shapes[2 * i + 1] / P)->rope_off;
     }
     h_row0[n] = rows; h_qb0[n] = (int)qblocks;
+    // the dense head's tables (pack_call checked and built them): image i's logit rows start behind its prefix rows
+    PackDense *dn = p->dense.get();
+    const size_t tile0_at = (size_t)3 * cap + 2, seg_at = tile0_at + cap + 1;        // ints into host / tab, there while a head is set
+    if (dn) {
+        int *h_tile0 = p->host.data() + tile0_at, *h_seg = p->host.data() + seg_at;
+        std::vector<int32_t> lrow(n);
+        for (int i = 0; i < n; ++i) lrow[i] = p->row0[i] + Tp;
+        std::copy(dn->tile0.begin(), dn->tile0.end(), h_tile0);
+        dense_pack_seg(dn->grids.data(), dn->outs.data(), lrow.data(), dn->pix0.data(), n, h_seg);
+    }
     HIP_TRY(hipMemcpyAsync(p->tab, p->host.data(), p->host.size() * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(p->uploaded, st));
     p->uploaded_pending = true;
@@ -158,7 +200,9 @@ int pack_forward(vitx_pack *p, const float *d_imgs, const int32_t *shapes, int n
         i = j;
     }
     if (ws.pre_w) { HIP_TRY(launch_layernorm_f32(p->X, ws.pre_w, ws.pre_b, p->X, rows, D, p->eps, st)); ++p->launches; }
+    int il = -1;
     for (const LayerW &w : ws.layers) {
+        ++il;
         HIP_TRY(launch_layernorm(dt, p->X, D, w.ln1_w, w.ln1_b, p->U, D, rows, D, p->eps, st)); ++p->launches;
         if ((rc = pack_gemm(p, EPI_BIAS, dense_gemm(p->U, w.qkv_w, w.qkv_b, p->QKV, M, rows, 3 * D, round_up(3 * D, tn), D), st))) return rc;
         if (p->rope) {
@@ -171,6 +215,12 @@ int pack_forward(vitx_pack *p, const float *d_imgs, const int32_t *shapes, int n
         if ((rc = pack_gemm(p, p->fc1_epi, dense_gemm(p->U, w.fc1_w, w.fc1_b, p->Hbuf, M, rows, p->F1, round_up(p->F1, tn), D), st))) return rc;
         if (p->glu) { HIP_TRY(launch_swiglu(dt, p->Hbuf, p->F1, p->Hg, p->F, rows, p->F, st)); ++p->launches; }
         if ((rc = pack_gemm(p, EPI_BIAS_RESID, dense_gemm(p->glu ? p->Hg : p->Hbuf, w.fc2_w, w.fc2_b, p->X, M, rows, D, round_up(D, tn), p->F), st))) return rc;
+        // the dense head's operand: the final norm of every row of the pack as layer il stands, rounded to the operand type into the layer's column
+        // slot of the compact rows [M][Dc] (the stand-alone LayerNorm: the rows a rectangular context's head reads, and the prefix rows, never used)
+        if (dn && dn->selects(il)) {
+            HIP_TRY(launch_layernorm(dt, p->X, D, ws.norm_w, ws.norm_b, dn->a[0].as<char>() + dn->col(il, D) * 2, dn->Dc, rows, D, p->eps, st));
+            ++p->launches;
+        }
     }
     // the class rows through the final norm (row0[i] is image i's class row), the head GEMM in f32, the class softmax
     HIP_TRY(launch_pool_rows(dt, p->X, d_row0, ws.norm_w, ws.norm_b, p->Z, n, Mh, D, p->eps, st)); ++p->launches;
@@ -180,6 +230,16 @@ int pack_forward(vitx_pack *p, const float *d_imgs, const int32_t *shapes, int n
     HIP_TRY(launch_softmax(dt, lg, d_probs, n, p->C, ldl, st)); ++p->launches;
     // features (vitx_pack_feat_enable): the f32 final norm of every row of the pack; vitx_pack_feat_read gathers the rows it was asked for
     if (p->feat_flags) { HIP_TRY(launch_layernorm_f32(p->X, ws.norm_w, ws.norm_b, p->feat, rows, D, p->eps, st)); ++p->launches; p->feat_n = n; }
+    // the dense head: the logits of every row of the pack, then one label launch over the images' own output shapes (2 launches; the memset of
+    // the operand's pad rows is not a kernel)
+    if (dn) {
+        const hipError_t e = head_dense_packed(HeadLaunch{*p->tune, dt, st, nullptr}, dn->a[0].p, dn->W.p, dn->bias.as<float>(), dn->acc[0].as<float>(), rows, dn->K, dn->Dc,
+                                               p->tab + tile0_at, p->tab + seg_at, n, dn->tile0[n], dn->cells, (long)dn->pix0[n], dn->labels.as<uint8_t>(),
+                                               dn->score ? dn->score.as<float>() : nullptr, dn->logits ? dn->logits.as<float>() : nullptr);
+        if (e != hipSuccess) { set_error("vitx_pack_forward: the dense head: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
+        p->launches += 2;
+        dn->n = n;
+    }
     HIP_TRY(hipEventRecord(p->done, st));
     p->done_pending = true;
     return VITX_OK;
@@ -188,9 +248,20 @@ int pack_forward(vitx_pack *p, const float *d_imgs, const int32_t *shapes, int n
 // Everything a call can be refused for comes before its first device call
 int pack_call(vitx_pack *p, const void *d_imgs, const int32_t *shapes, int n, void *d_probs, void *d_logits, hipStream_t st) {
     int rc;
+    PackDense *dn = p->dense.get();
+    std::vector<int32_t> next_out;              // vitx_pack_dense_out: this call consumes the shapes, run or refused
+    if (dn) next_out.swap(dn->next_out);
     if ((rc = check_shapes("vitx_pack_forward", p->model, shapes, n, p->max_tokens, p->max_images, p->chk.data()))) return rc;
     const std::vector<uint64_t> want = distinct_grids(shapes, n, p->P);
     if (want.size() > (size_t)p->max_grids) { set_error("vitx_pack_forward: the call names %d distinct grids, the table cache holds max_grids = %d", (int)want.size(), p->max_grids); return VITX_ERR_ARG; }
+    if (dn) {       // into locals: a refused call leaves the tables of the last forward (vitx_pack_dense_read) alone
+        std::vector<int32_t> g((size_t)2 * n), o((size_t)2 * n), t0((size_t)n + 1);
+        std::vector<int64_t> px((size_t)n + 1);
+        int cells = 0;
+        if ((rc = check_dense("vitx_pack_forward", p->model, shapes, next_out.empty() ? nullptr : next_out.data(), (int)(next_out.size() / 2), n, dn->K, dn->max_pixels,
+                              g.data(), o.data(), px.data(), t0.data(), &cells))) return rc;
+        dn->grids.swap(g); dn->outs.swap(o); dn->pix0.swap(px); dn->tile0.swap(t0); dn->cells = cells; dn->n = 0;
+    }
     HIP_TRY(hipSetDevice(p->device));
     p->row0 = p->chk; p->feat_n = 0;
     p->launches = p->pe_launches = 0;
@@ -292,7 +363,12 @@ int vitx_pack_forward_device(vitx_pack *p, const void *d_imgs, const int32_t *sh
 int vitx_pack_forward(vitx_pack *p, const float *imgs, const int32_t *shapes, int n, float *probs, float *logits) {
     if (!p || !imgs || !shapes || !probs) { set_error("vitx_pack_forward: NULL argument"); return VITX_ERR_ARG; }
     int rc;
-    if ((rc = check_shapes("vitx_pack_forward", p->model, shapes, n, p->max_tokens, p->max_images, nullptr))) return rc;
+    if ((rc = check_shapes("vitx_pack_forward", p->model, shapes, n, p->max_tokens, p->max_images, nullptr))) { if (p->dense) p->dense->next_out.clear(); return rc; }
+    if (PackDense *dn = p->dense.get()) {       // the head's refusals too come before the pixels go up (pack_call makes the check again and keeps its tables)
+        rc = check_dense("vitx_pack_forward", p->model, shapes, dn->next_out.empty() ? nullptr : dn->next_out.data(), (int)(dn->next_out.size() / 2), n, dn->K, dn->max_pixels,
+                         nullptr, nullptr, nullptr, nullptr, nullptr);
+        if (rc) { dn->next_out.clear(); return rc; }
+    }
     HIP_TRY(hipSetDevice(p->device));
     if (!p->img) {       // the pixels of a full pack: max_tokens patches
         const size_t bytes = (size_t)p->max_tokens * p->P * p->P * 3 * 4;
@@ -337,6 +413,115 @@ int vitx_pack_feat_read(vitx_pack *p, float *cls, float *tokens) {
             const size_t np = (size_t)(p->row0[i + 1] - p->row0[i] - p->Tp), at = (size_t)(p->row0[i] - i * p->Tp);
             HIP_TRY(hipMemcpy(tokens + at * D, src + (size_t)p->Tp * D, np * rowb, hipMemcpyDeviceToHost));
         }
+    }
+    return VITX_OK;
+}
+
+int vitx_pack_dense_check(const vitx_model *m, const int32_t *shapes, const int32_t *out_shapes, int n, int K, long max_pixels, int64_t *pix0, int32_t *tile0) {
+    // max_tokens / max_images: whatever holds the call -- their refusals are vitx_pack_check's
+    if (const int rc = check_shapes("vitx_pack_dense_check", m, shapes, n, 0x7fffffff, n, nullptr)) return rc;
+    return check_dense("vitx_pack_dense_check", m, shapes, out_shapes, n, n, K, max_pixels, nullptr, nullptr, pix0, tile0, nullptr);
+}
+
+// The dense head of a packed context (include/vitx.h "packed batches").  Every argument check comes before the first device call; the head is
+// built in a local and moved in, so a refused or failed set leaves the head that was set.
+int vitx_pack_dense_set(vitx_pack *p, const float *W, const float *bias, int K, int Dc, uint64_t layer_mask, long max_pixels, int flags) {
+    if (!p) { set_error("vitx_pack_dense_set: NULL context"); return VITX_ERR_ARG; }
+    const bool off = !W && K == 0;
+    uint64_t mask = layer_mask;
+    const size_t Mp = (size_t)round_up(p->max_tokens, p->tm), Kpad = K > 0 ? (size_t)round_up(K, p->tn) : 0;
+    if (!off) {
+        if (!W) { set_error("vitx_pack_dense_set: NULL weights with K = %d", K); return VITX_ERR_ARG; }
+        if (K < 1) { set_error("vitx_pack_dense_set: K = %d classes", K); return VITX_ERR_ARG; }
+        if (flags & ~(VITX_DENSE_SCORE | VITX_DENSE_LOGITS)) { set_error("vitx_pack_dense_set: unknown flags 0x%x", flags); return VITX_ERR_ARG; }
+        if (mask == 0) mask = 1ull << (p->L - 1);
+        if (p->L < 64 && (mask >> p->L)) { set_error("vitx_pack_dense_set: layer mask selects a layer at or beyond L = %d", p->L); return VITX_ERR_ARG; }
+        const int m = __builtin_popcountll(mask);
+        if (m > 4) { set_error("vitx_pack_dense_set: %d layers selected, at most 4", m); return VITX_ERR_ARG; }
+        if (Dc != m * p->D) { set_error("vitx_pack_dense_set: the head's width %d is not %d layers x D = %d", Dc, m, m * p->D); return VITX_ERR_ARG; }
+        if (max_pixels < 1) { set_error("vitx_pack_dense_set: max_pixels = %ld", max_pixels); return VITX_ERR_ARG; }
+        for (size_t i = 0, nb = (size_t)K * Dc; i < nb; ++i)
+            if (!std::isfinite(W[i])) { set_error("vitx_pack_dense_set: weight [%zu][%zu] is not finite", i / Dc, i % Dc); return VITX_ERR_ARG; }
+        if (bias) for (int k = 0; k < K; ++k)
+            if (!std::isfinite(bias[k])) { set_error("vitx_pack_dense_set: bias [%d] is not finite", k); return VITX_ERR_ARG; }
+        if (K > kDenseMaxK) { set_error("vitx_pack_dense_set: K = %d classes above %d (labels are bytes)", K, kDenseMaxK); return VITX_ERR_UNSUPPORTED; }
+        if (Mp * Dc * 2 > 0xf0000000u || Mp * Kpad * 4 > 0xf0000000u) {
+            set_error("vitx_pack_dense_set: the operand or logit rows of max_tokens = %d rows leave the GEMM's 32-bit byte window", p->max_tokens);
+            return VITX_ERR_UNSUPPORTED;
+        }
+    }
+    HIP_TRY(hipSetDevice(p->device));
+    // nothing of this context is in flight while buffers and tables change hands
+    if (p->uploaded_pending) { HIP_TRY(hipEventSynchronize(p->uploaded)); p->uploaded_pending = false; }
+    if (const int rc = wait_done(p)) return rc;
+    const size_t cap = (size_t)p->max_images, base_ints = 3 * cap + 2;
+    // the segment tables with (ints > base_ints) or without the head's part behind them: a fresh zeroed buffer in place of the old one
+    auto resize_tables = [&](size_t ints) -> int {
+        if (p->host.size() == ints) return VITX_OK;
+        int *t = nullptr;
+        HIP_TRY(hipMalloc((void **)&t, ints * 4));
+        if (const hipError_t e = hipMemset(t, 0, ints * 4); e != hipSuccess) { (void)hipFree(t); set_error("vitx_pack_dense_set: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
+        std::replace(p->allocs.begin(), p->allocs.end(), (void *)p->tab, (void *)t);
+        (void)hipFree(p->tab);
+        p->scratch_bytes += ints * 4; p->scratch_bytes -= p->host.size() * 4;
+        p->tab = t; p->host.assign(ints, 0);
+        return VITX_OK;
+    };
+    if (off) {
+        if (p->dense) { p->scratch_bytes -= p->dense->bytes; p->dense.reset(); }
+        return resize_tables(base_ints);
+    }
+    auto dn = std::make_unique<PackDense>();
+    dn->K = K; dn->Kpad = (int)Kpad; dn->Dc = Dc; dn->mask = mask; dn->flags = flags; dn->cap = p->max_images; dn->max_pixels = max_pixels;
+    dn->a.resize(1); dn->acc.resize(1);
+    dn->scratch = Mp * Dc * 2 + Mp * Kpad * 4;
+    dn->bytes = dn->scratch + Kpad * Dc * 2 + Kpad * 4 + (size_t)max_pixels;
+    bool ok = dn->W.alloc(Kpad * Dc * 2) && dn->bias.alloc(Kpad * 4) && dn->a[0].alloc(Mp * Dc * 2) && dn->acc[0].alloc(Mp * Kpad * 4) && dn->labels.alloc((size_t)max_pixels);
+    if (ok && (flags & VITX_DENSE_SCORE)) { ok = dn->score.alloc((size_t)max_pixels * 4); dn->bytes += (size_t)max_pixels * 4; }
+    if (ok && (flags & VITX_DENSE_LOGITS)) { ok = dn->logits.alloc((size_t)p->max_tokens * K * 4); dn->bytes += (size_t)p->max_tokens * K * 4; }
+    if (!ok) { set_error("vitx_pack_dense_set: cannot allocate the buffers for %d classes, %ld pixels and %d token rows", K, max_pixels, p->max_tokens); return VITX_ERR_NOMEM; }
+    // the head goes up rounded (RNE) to the operand type, zero rows beyond K; the operand rows start as zeros (a forward writes its rows and zeroes
+    // the pad rows behind them)
+    const std::vector<uint16_t> hw = operand_matrix_host(p->dtype, W, nullptr, K, Dc, (int)Kpad, Dc, 0, 0);
+    HIP_TRY(hipMemcpy(dn->W.p, hw.data(), hw.size() * 2, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(dn->bias.p, 0, Kpad * 4));
+    if (bias) HIP_TRY(hipMemcpy(dn->bias.p, bias, (size_t)K * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(dn->a[0].p, 0, Mp * Dc * 2));
+    HIP_TRY(hipDeviceSynchronize());
+    if (const int rc = resize_tables(base_ints + cap + 1 + cap * kDenseSegInts)) return rc;
+    if (p->dense) p->scratch_bytes -= p->dense->bytes;
+    p->scratch_bytes += dn->bytes;
+    p->dense = std::move(dn);
+    return VITX_OK;
+}
+
+int vitx_pack_dense_out(vitx_pack *p, const int32_t *out_shapes, int n) {
+    if (!p || !p->dense) { set_error("vitx_pack_dense_out: no dense head is set"); return VITX_ERR_ARG; }
+    if (!out_shapes || n == 0) { p->dense->next_out.clear(); return VITX_OK; }
+    if (n < 1 || n > p->max_images) { set_error("vitx_pack_dense_out: n = %d is outside 1 .. max_images = %d", n, p->max_images); return VITX_ERR_ARG; }
+    p->dense->next_out.assign(out_shapes, out_shapes + (size_t)2 * n);
+    return VITX_OK;
+}
+
+const void *vitx_pack_dense_device(const vitx_pack *p) { return p && p->dense ? p->dense->labels.p : nullptr; }
+size_t vitx_pack_dense_scratch_bytes(const vitx_pack *p) { return p && p->dense ? p->dense->scratch : 0; }
+
+// The last forward's maps, the images end to end, and the kept logits of its patch rows (row0[i] + T .. row0[i + 1] - 1 of the pack's rows)
+int vitx_pack_dense_read(vitx_pack *p, uint8_t *labels, float *score, float *logits) {
+    if (!p || !labels) { set_error("vitx_pack_dense_read: NULL argument"); return VITX_ERR_ARG; }
+    const PackDense *dn = p->dense.get();
+    const int n = dn ? dn->n : 0;
+    if (n == 0) { set_error("vitx_pack_dense_read: no forward has run with a dense head set since vitx_pack_dense_set"); return VITX_ERR_ARG; }
+    if (score && !dn->score) { set_error("vitx_pack_dense_read: the head was set without VITX_DENSE_SCORE"); return VITX_ERR_ARG; }
+    if (logits && !dn->logits) { set_error("vitx_pack_dense_read: the head was set without VITX_DENSE_LOGITS"); return VITX_ERR_ARG; }
+    HIP_TRY(hipSetDevice(p->device));
+    if (p->done_pending) HIP_TRY(hipEventSynchronize(p->done));
+    const size_t px = (size_t)dn->pix0[n];
+    HIP_TRY(hipMemcpy(labels, dn->labels.p, px, hipMemcpyDeviceToHost));
+    if (score) HIP_TRY(hipMemcpy(score, dn->score.p, px * 4, hipMemcpyDeviceToHost));
+    if (logits) for (int i = 0; i < n; ++i) {
+        const size_t np = (size_t)(p->row0[i + 1] - p->row0[i] - p->Tp), at = (size_t)(p->row0[i] - i * p->Tp);
+        HIP_TRY(hipMemcpy(logits + at * dn->K, dn->logits.as<float>() + (size_t)(p->row0[i] + p->Tp) * dn->K, np * dn->K * 4, hipMemcpyDeviceToHost));
     }
     return VITX_OK;
 }
