@@ -250,7 +250,7 @@ def pe_runs(shapes):
 
 
 def pack_launches(shapes, L, new_grids, rope=False, glu=False, pre=False, feat=False):
-    """(kernel launches, patch embeddings among them) of one packed forward, counted from packed_forward.cpp:
+    """(kernel launches, patch embeddings among them) of one packed forward, counted from packed_context.cpp (resolve_grids) and packed_forward.cpp (pack_forward):
     resolve_grids  one launch_pos_resample per grid the cache does not hold and that is not the file's own (`new_grids`; rotary tables are host copies)
     pack_forward   the patch-embedding runs; the pre-norm of a file that has one;
                    per layer 7: norm1, qkv, attention, proj, norm2, fc1, fc2 -- + 1 rope.hip with `rope`, + 1 swiglu.hip with `glu`;
@@ -306,7 +306,7 @@ def gates(d):
     return max(d[0] / GATE, d[1] / TOKEN_GATE)
 
 
-# ================================================================================================ the table cache (packed_forward.cpp resolve_grids)
+# ================================================================================================ the table cache (packed_context.cpp resolve_grids)
 def cache_trace(calls, max_tokens, half, max_grids=32):
     """resolve_grids restated.  calls: per call the grids (gh, gw) it names, in order; half: head_dim / 2 of a `rope` file, 0 without rope (no arena).
     Per call: dict(held = the grids in the cache afterwards, in cache order; rope_off = {grid: floats into the arenas}; restarted; evicted).

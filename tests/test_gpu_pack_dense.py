@@ -5,7 +5,8 @@
    dense_data.cases() as a uniform pack against the fixed-shape kernel (the one shared tile body).
 2. The head on a packed context end to end: kept logits under the f32 inner-product bound, labels and scores equal to the host function on the kept
    logits, determinism (alone, another position, a NaN neighbour), a uniform pack against the rectangular context, the forward's own outputs unchanged,
-   launches, scratch, vitx_pack_dense_out, refusals that write nothing."""
+   launches, scratch, vitx_pack_dense_out, refusals that write nothing; the device entry point with a head set against the host entry point, run and
+   refused."""
 import ctypes as C
 
 import numpy as np
@@ -346,4 +347,59 @@ def test_output_shapes_and_refused_calls(pkg, binding, torch_gpu):
         assert L.vitx_pack_dense_set(pack._h, *args) == code, args[2:]
     still = _run(pack, imgs)[0]
     assert all(_same(still[i], own[i]) for i in range(n))
+    pack.close(); model.close()
+
+
+def test_the_device_entry_point_with_a_head_set(pkg, binding, torch_gpu):
+    """vitx_pack_forward_device goes through the same check of a call as vitx_pack_forward.  With a head set (score and logits on) and
+    dense_out(original_like): forward_device + dense_read give the bits of forward + dense_read, probabilities and logits included.  A forward_device
+    refused for its output shapes (given for n - 1 images) is ERR_ARG, leaves the canaries in the label buffer and the probabilities' sentinel,
+    consumes its dense_out shapes -- the following forward_device, at the images' own shapes, equals the host path's."""
+    torch = torch_gpu
+    model = binding.Model(KD.variant_file(pkg, "p14r4h4"))
+    P, D = model.hparams.patch_size, model.hparams.hidden_size
+    shapes = KD.mixed_shapes(P)
+    imgs = KD.pack_of(shapes)
+    n = len(imgs)
+    outs = QD.original_like(shapes, P)
+    px_out = sum(h * w for h, w in outs)
+    W, b = _head(K_E2E, D, seed=3)
+    pack = binding.PackContext(model, device=0, max_tokens=256, max_images=n, dtype=1)
+    pack.dense_set(W, b, None, max_pixels=px_out, score=True, logits=True)
+    own, own_p, own_lg = _run(pack, imgs)
+    pack.dense_out(outs)
+    big, big_p, big_lg = _run(pack, imgs)
+    assert all(big[i][0].shape == tuple(outs[i]) for i in range(n)) and any(big[i][0].shape != own[i][0].shape for i in range(n))
+    d_pix = torch.from_numpy(np.concatenate([a.ravel() for a in imgs])).cuda()
+    SENT = -7.25
+
+    def device_run(out_shapes):
+        d_p = torch.full((n, model.num_classes), SENT, dtype=torch.float32, device="cuda")
+        d_lg = torch.full((n, model.num_classes), SENT, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        if out_shapes is not None:
+            pack.dense_out(out_shapes)
+        pack.forward_device(d_pix.data_ptr(), shapes, d_p.data_ptr(), d_lg.data_ptr())
+        lab, sc, kept = pack.dense_read()
+        torch.cuda.synchronize()
+        return [(lab[i], sc[i], kept[i]) for i in range(n)], d_p.cpu().numpy(), d_lg.cpu().numpy()
+
+    got, p, lg = device_run(outs)
+    assert all(_same(got[i], big[i]) for i in range(n)), "forward_device with dense_out"
+    assert np.array_equal(_bits(p), _bits(big_p)) and np.array_equal(_bits(lg), _bits(big_lg))
+    # refused for its output shapes: nothing is written, the shapes are consumed
+    hip = C.cdll.LoadLibrary("libamdhip64.so")
+    ptr = pack.dense_device()
+    assert hip.hipMemset(C.c_void_p(ptr), CAN_U8, px_out) == 0 and hip.hipDeviceSynchronize() == 0
+    d_p = torch.full((n, model.num_classes), SENT, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    pack.dense_out(outs[:-1])
+    with pytest.raises(binding.VitxError) as ei:
+        pack.forward_device(d_pix.data_ptr(), shapes, d_p.data_ptr())
+    assert ei.value.code == binding.ERR_ARG and "images" in str(ei.value), str(ei.value)
+    assert hip.hipDeviceSynchronize() == 0 and (_device_bytes(ptr, px_out) == CAN_U8).all(), "a refused call wrote labels"
+    assert bool((d_p == SENT).all()), "a refused call wrote probabilities"
+    again, p, lg = device_run(None)
+    assert all(_same(again[i], own[i]) for i in range(n)), "the refused call did not consume its shapes"
+    assert np.array_equal(_bits(p), _bits(own_p)) and np.array_equal(_bits(lg), _bits(own_lg))
     pack.close(); model.close()

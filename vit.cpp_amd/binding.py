@@ -493,6 +493,29 @@ def _grid(g) -> Tuple[int, int]:
     return (int(g), int(g)) if np.isscalar(g) else (int(g[0]), int(g[1]))
 
 
+def _layer_mask(layers, prefix: str = "", span: str = "0 .. 63") -> int:
+    """Layer indices -> the layer mask of the C API (bit l = layer l); `prefix` and `span` are the caller's spelling of the ValueError."""
+    mask = 0
+    for l in layers:
+        if not 0 <= int(l) < 64:
+            raise ValueError(f"{prefix}layer {l} outside {span}")
+        mask |= 1 << int(l)
+    return mask
+
+
+def _head_arrays(prefix: str, weight, bias):
+    """(weight [K, Dc], bias [K] or None) of a linear head as contiguous f32 arrays, or ValueError."""
+    w = np.ascontiguousarray(weight, dtype=np.float32)
+    if w.ndim != 2:
+        raise ValueError(f"{prefix}weight must be [K, Dc]")
+    b = None
+    if bias is not None:
+        b = np.ascontiguousarray(bias, dtype=np.float32)
+        if b.shape != (w.shape[0],):
+            raise ValueError(f"{prefix}bias must be [K]")
+    return w, b
+
+
 def pos_embed_resample(pos: np.ndarray, grid_out, interp: int = POS_BICUBIC, grid_in=None) -> np.ndarray:
     """vitx_pos_embed_resample on the host: pos [1 + gy * gx, D] f32 (row 0 = class token) -> [1 + gy' * gx', D].  grid_out (and grid_in) are a
     side or a (gy, gx) pair; grid_in defaults to the square grid the row count implies."""
@@ -709,11 +732,7 @@ class Context:
         with rollout=True, the attention-rollout row.  attn_enable([]) turns them off and frees the buffers."""
         L = self.model.hparams.num_hidden_layers
         sel = list(range(L)) if layers is None else sorted(set(int(l) for l in layers))
-        mask = 0
-        for l in sel:
-            if l < 0 or l >= 64:
-                raise ValueError(f"layer {l} outside 0..63")
-            mask |= 1 << l
+        mask = _layer_mask(sel, span="0..63")
         check(lib().vitx_attn_enable(self._h, mask, ATTN_ROLLOUT if rollout else 0), "vitx_attn_enable")
         self._attn_layers, self._attn_rollout = sel, bool(rollout)
 
@@ -751,11 +770,7 @@ class Context:
         mean or tokens of the last layer make it compute every row (the probabilities of a last_layer_all_rows=1 context)."""
         L = self.model.hparams.num_hidden_layers
         sel = [L - 1] if layers is None else sorted(set(int(l) for l in layers))
-        mask = 0
-        for l in sel:
-            if l < 0 or l >= 64:
-                raise ValueError(f"layer {l} outside 0..63")
-            mask |= 1 << l
+        mask = _layer_mask(sel, span="0..63")
         flags = (FEAT_CLS if cls else 0) | (FEAT_MEAN if mean else 0) | (FEAT_TOKENS if tokens else 0) | (FEAT_L2 if l2 else 0)
         if not sel:
             raise ValueError("feat_enable: no layer selected (feat_disable() turns the features off)")
@@ -875,19 +890,8 @@ class Context:
         if weight is None:
             check(lib().vitx_dense_set(self._h, None, None, 0, 0, 0, 0, 0, 0), "vitx_dense_set")
             return
-        w = np.ascontiguousarray(weight, dtype=np.float32)
-        if w.ndim != 2:
-            raise ValueError("dense_set: weight must be [K, Dc]")
-        b = None
-        if bias is not None:
-            b = np.ascontiguousarray(bias, dtype=np.float32)
-            if b.shape != (w.shape[0],):
-                raise ValueError("dense_set: bias must be [K]")
-        mask = 0
-        for l in ([] if layers is None else layers):
-            if not 0 <= int(l) < 64:
-                raise ValueError(f"dense_set: layer {l} outside 0 .. 63")
-            mask |= 1 << int(l)
+        w, b = _head_arrays("dense_set: ", weight, bias)
+        mask = _layer_mask([] if layers is None else layers, "dense_set: ")
         oh, ow = (0, 0) if out_shape is None else (int(out_shape[0]), int(out_shape[1]))
         fp = C.POINTER(C.c_float)
         check(lib().vitx_dense_set(self._h, w.ctypes.data_as(fp), b.ctypes.data_as(fp) if b is not None else None, w.shape[0], w.shape[1], mask, oh, ow,
@@ -950,11 +954,7 @@ class Context:
         c, b, bn = opt(wc, w.shape, "wc"), opt(bias, (K,), "bias"), opt(bins, (K,), "bins")
         if bn is None:
             raise ValueError("depth_set: bins [K] are required")
-        mask = 0
-        for l in ([] if layers is None else layers):
-            if not 0 <= int(l) < 64:
-                raise ValueError(f"depth_set: layer {l} outside 0 .. 63")
-            mask |= 1 << int(l)
+        mask = _layer_mask([] if layers is None else layers, "depth_set: ")
         oh, ow = (0, 0) if out_shape is None else (int(out_shape[0]), int(out_shape[1]))
         ptr = lambda a: a.ctypes.data_as(fp) if a is not None else None
         check(lib().vitx_depth_set(self._h, ptr(w), ptr(c), ptr(b), ptr(bn), K, w.shape[1], mask, int(upsample), float(min_depth), float(max_depth), oh, ow,
@@ -1252,19 +1252,8 @@ class PackContext:
             check(lib().vitx_pack_dense_set(self._h, None, None, 0, 0, 0, 0, 0), "vitx_pack_dense_set")
             self._dense = None
             return
-        w = np.ascontiguousarray(weight, dtype=np.float32)
-        if w.ndim != 2:
-            raise ValueError("dense_set: weight must be [K, Dc]")
-        b = None
-        if bias is not None:
-            b = np.ascontiguousarray(bias, dtype=np.float32)
-            if b.shape != (w.shape[0],):
-                raise ValueError("dense_set: bias must be [K]")
-        mask = 0
-        for l in ([] if layers is None else layers):
-            if not 0 <= int(l) < 64:
-                raise ValueError(f"dense_set: layer {l} outside 0 .. 63")
-            mask |= 1 << int(l)
+        w, b = _head_arrays("dense_set: ", weight, bias)
+        mask = _layer_mask([] if layers is None else layers, "dense_set: ")
         P = self.model.hparams.patch_size
         fp = C.POINTER(C.c_float)
         check(lib().vitx_pack_dense_set(self._h, w.ctypes.data_as(fp), b.ctypes.data_as(fp) if b is not None else None, w.shape[0], w.shape[1], mask,

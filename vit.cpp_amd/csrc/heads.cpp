@@ -1,5 +1,8 @@
 // heads.cpp -- the launch sequences of the zero-shot bank, the gallery, the dense head and the depth head (heads.h): what a forward runs after
 // its classifier (SliceForward, forward.cpp) and what vitx_op_zeroshot / _nn / _dense / _depth run on the caller's buffers (ops.cpp) -- one text.
+// Behind them the set path of the patch heads: the argument checks and the upload that an image context and a packed context share.
+#include <cmath>
+
 #include "context.h"
 
 namespace vitx {
@@ -89,6 +92,43 @@ hipError_t head_depth(const HeadLaunch &l, void *a, const void *Wp, const float 
     }
     ProfScope ps(l.prof, l.st, PC_DEPTH, 7.0 * n * (double)px, (double)n * (fpx + px) * 4);
     return launch_depth_resize(fine, n, u * gh, u * gw, oh, ow, lo, hi, depth, l.st);
+}
+
+int patch_head_mask(const char *api, int L, int D, int Dc, uint64_t *mask) {
+    if (*mask == 0) *mask = 1ull << (L - 1);
+    if (L < 64 && (*mask >> L)) { set_error("%s: layer mask selects a layer at or beyond L = %d", api, L); return VITX_ERR_ARG; }
+    const int m = __builtin_popcountll(*mask);
+    if (m > 4) { set_error("%s: %d layers selected, at most 4", api, m); return VITX_ERR_ARG; }
+    if (Dc != m * D) { set_error("%s: the head's width %d is not %d layers x D = %d", api, Dc, m, m * D); return VITX_ERR_ARG; }
+    return VITX_OK;
+}
+
+int dense_head_args(const char *api, const float *W, int K, int Dc, int flags, int L, int D, uint64_t *mask) {
+    if (!W) { set_error("%s: NULL weights with K = %d", api, K); return VITX_ERR_ARG; }
+    if (K < 1) { set_error("%s: K = %d classes", api, K); return VITX_ERR_ARG; }
+    if (flags & ~(VITX_DENSE_SCORE | VITX_DENSE_LOGITS)) { set_error("%s: unknown flags 0x%x", api, flags); return VITX_ERR_ARG; }
+    return patch_head_mask(api, L, D, Dc, mask);
+}
+
+int dense_head_values(const char *api, const float *W, const float *bias, int K, int Dc) {
+    for (size_t i = 0, nb = (size_t)K * Dc; i < nb; ++i)
+        if (!std::isfinite(W[i])) { set_error("%s: weight [%zu][%zu] is not finite", api, i / Dc, i % Dc); return VITX_ERR_ARG; }
+    if (bias) for (int k = 0; k < K; ++k)
+        if (!std::isfinite(bias[k])) { set_error("%s: bias [%d] is not finite", api, k); return VITX_ERR_ARG; }
+    if (K > kDenseMaxK) { set_error("%s: K = %d classes above %d (labels are bytes)", api, K, kDenseMaxK); return VITX_ERR_UNSUPPORTED; }
+    return VITX_OK;
+}
+
+hipError_t upload_operand(int dtype, const DevMem &dst, const float *W, int K, int Kpad, int Dc) {
+    const std::vector<uint16_t> hw = operand_matrix_host(dtype, W, nullptr, K, Dc, Kpad, Dc, 0, 0);
+    return hipMemcpy(dst.p, hw.data(), hw.size() * 2, hipMemcpyHostToDevice);
+}
+
+hipError_t dense_head_upload(const DenseHead &dn, int dtype, const float *W, const float *bias) {
+    HEAD_TRY(upload_operand(dtype, dn.W, W, dn.K, dn.Kpad, dn.Dc));
+    HEAD_TRY(hipMemset(dn.bias.p, 0, (size_t)dn.Kpad * 4));
+    if (bias) HEAD_TRY(hipMemcpy(dn.bias.p, bias, (size_t)dn.K * 4, hipMemcpyHostToDevice));
+    return hipSuccess;
 }
 
 }  // namespace vitx

@@ -1,7 +1,8 @@
 // heads.h -- the opt-in outputs of an execution context (attention maps, features, the zero-shot bank, the gallery, the dense and the depth
 // head): one struct each, owning its parameters and its device memory, held by vitx_ctx (context.h) through a pointer -- null means off,
 // dropping the object frees everything.  outputs.cpp builds them, forward.cpp reads them.  Below them: the launch sequences of the four heads
-// (heads.cpp), on plain pointers, as the forward and the vitx_op_* entry points (ops.cpp) both run them.  Internal; needs no context.
+// (heads.cpp), on plain pointers, as the forward and the vitx_op_* entry points (ops.cpp) both run them, and the part of setting a patch head that an
+// image context and a packed context share.  Internal; needs no context.
 #pragma once
 #include <type_traits>
 #include <vector>
@@ -143,7 +144,7 @@ struct PackDense : DenseHead {
     long max_pixels = 0;         // elements of labels (and score); logits: [max_tokens][K], every row of the pack
     size_t bytes = 0;            // device bytes of everything above: what the head adds to vitx_pack_scratch_bytes
     std::vector<int32_t> next_out;       // vitx_pack_dense_out: the output shapes [n][2] of the next forward (empty: the images' own shapes)
-    std::vector<int32_t> grids, outs;    // [n][2] each, of the call being checked / the last forward made with the head set
+    std::vector<int32_t> grids, outs;    // [n][2] each, of the last call that passed its checks with the head set (PackCall, packed_context.h)
     std::vector<int64_t> pix0;   // [n + 1], the same
     std::vector<int32_t> tile0;  // [n + 1], the same
     int cells = 0;               // the widest tile window of that call
@@ -214,5 +215,19 @@ hipError_t head_depth(const HeadLaunch &l, void *a, const void *Wp, const float 
 // the argument checks vitx_op_depth_fine / vitx_op_depth_resize / vitx_op_depth (ops.cpp) share with vitx_depth_host (depth_host.cpp): none needs a device
 int depth_fine_args(const char *name, const void *logits, long ld, const void *bins, int n, int gh, int gw, int K, int u, const void *fine);
 int depth_resize_args(const char *name, const void *fine, int n, int fh, int fw, int out_h, int out_w, float lo, float hi, const void *out);
+
+// ---- what setting a patch head takes, whichever context it serves (heads.cpp) -----------------------------------------------------------
+// The argument checks need no device and put `api` in front of every refusal.  They come in pieces because each context's and each head's own
+// checks sit between them (outputs.cpp: vitx_dense_set, vitx_depth_set; packed_outputs.cpp: vitx_pack_dense_set).
+// patch_head_mask: the layer mask of a head on a model of L layers of width D (0: the last layer), at most 4 layers, Dc = layers x D
+int patch_head_mask(const char *api, int L, int D, int Dc, uint64_t *mask);
+// dense_head_args: the weights are there, K >= 1, known flags, then patch_head_mask
+int dense_head_args(const char *api, const float *W, int K, int Dc, int flags, int L, int D, uint64_t *mask);
+// dense_head_values: W [K][Dc] and bias [K] (or NULL) are finite, K is at most kDenseMaxK
+int dense_head_values(const char *api, const float *W, const float *bias, int K, int Dc);
+// W [K][Dc] f32 -> dst [Kpad][Dc], rounded (RNE) to the operand type, zero rows beyond K
+hipError_t upload_operand(int dtype, const DevMem &dst, const float *W, int K, int Kpad, int Dc);
+// The parameters of a dense head whose K, Kpad and Dc are set, onto the device: W through upload_operand, bias zero-filled, then `bias` [K] (or NULL) copied
+hipError_t dense_head_upload(const DenseHead &dn, int dtype, const float *W, const float *bias);
 
 }  // namespace vitx

@@ -33,20 +33,11 @@ static int hip_failed(const char *api, hipError_t e) {
     set_error("%s: %s", api, hipGetErrorString(e));
     return VITX_ERR_HIP;
 }
-// W [K][Dc] f32 -> dst [Kpad][Dc], rounded (RNE) to the context's operand type, zero rows beyond K
-static hipError_t upload_operand(const vitx_ctx *c, const DevMem &dst, const float *W, int K, int Kpad, int Dc) {
-    const std::vector<uint16_t> hw = operand_matrix_host(c->dtype, W, nullptr, K, Dc, Kpad, Dc, 0, 0);
-    return hipMemcpy(dst.p, hw.data(), hw.size() * 2, hipMemcpyHostToDevice);
-}
 
-// What vitx_dense_set and vitx_depth_set (`api`) share.  The argument checks come in two pieces because each head's own checks sit between them:
-// patch_head_layers: the layer mask (0: the last layer), at most 4 layers, Dc = layers x D, the output shape (0 x 0: the context's image shape)
-static int patch_head_layers(const vitx_ctx *c, const char *api, int Dc, uint64_t *mask, int *oh, int *ow) {
-    if (*mask == 0) *mask = 1ull << (c->L - 1);
-    if (c->L < 64 && (*mask >> c->L)) { set_error("%s: layer mask selects a layer at or beyond L = %d", api, c->L); return VITX_ERR_ARG; }
-    const int m = __builtin_popcountll(*mask);
-    if (m > 4) { set_error("%s: %d layers selected, at most 4", api, m); return VITX_ERR_ARG; }
-    if (Dc != m * c->D) { set_error("%s: the head's width %d is not %d layers x D = %d", api, Dc, m, m * c->D); return VITX_ERR_ARG; }
+// What vitx_dense_set and vitx_depth_set (`api`) share beyond the checks of the head itself (heads.h: patch_head_mask and its kin).  The argument
+// checks come in two pieces because each head's own checks sit between them:
+// patch_head_shape: the output shape (0 x 0: the context's image shape)
+static int patch_head_shape(const vitx_ctx *c, const char *api, int *oh, int *ow) {
     if (*oh < 0 || *ow < 0 || ((*oh == 0) != (*ow == 0))) { set_error("%s: output shape %d x %d (0 x 0: the context's image shape)", api, *oh, *ow); return VITX_ERR_ARG; }
     if (*oh == 0) { *oh = c->Sh; *ow = c->Sw; }
     return VITX_OK;
@@ -392,15 +383,9 @@ int vitx_dense_set(vitx_ctx *c, const float *W, const float *bias, int K, int Dc
     uint64_t mask = layer_mask;
     int oh = out_h, ow = out_w;
     if (!off) {
-        if (!W) { set_error("vitx_dense_set: NULL weights with K = %d", K); return VITX_ERR_ARG; }
-        if (K < 1) { set_error("vitx_dense_set: K = %d classes", K); return VITX_ERR_ARG; }
-        if (flags & ~(VITX_DENSE_SCORE | VITX_DENSE_LOGITS)) { set_error("vitx_dense_set: unknown flags 0x%x", flags); return VITX_ERR_ARG; }
-        if (const int rc = patch_head_layers(c, "vitx_dense_set", Dc, &mask, &oh, &ow)) return rc;
-        for (size_t i = 0, nb = (size_t)K * Dc; i < nb; ++i)
-            if (!std::isfinite(W[i])) { set_error("vitx_dense_set: weight [%zu][%zu] is not finite", i / Dc, i % Dc); return VITX_ERR_ARG; }
-        if (bias) for (int k = 0; k < K; ++k)
-            if (!std::isfinite(bias[k])) { set_error("vitx_dense_set: bias [%d] is not finite", k); return VITX_ERR_ARG; }
-        if (K > kDenseMaxK) { set_error("vitx_dense_set: K = %d classes above %d (labels are bytes)", K, kDenseMaxK); return VITX_ERR_UNSUPPORTED; }
+        if (const int rc = dense_head_args("vitx_dense_set", W, K, Dc, flags, c->L, c->D, &mask)) return rc;
+        if (const int rc = patch_head_shape(c, "vitx_dense_set", &oh, &ow)) return rc;
+        if (const int rc = dense_head_values("vitx_dense_set", W, bias, K, Dc)) return rc;
         if (c->R != 1) { set_error("vitx_dense_set: the dense head is not available for ViTSTR contexts"); return VITX_ERR_UNSUPPORTED; }
         if (oh < c->gh || ow < c->gw || oh > kDenseMaxOut || ow > kDenseMaxOut) {
             set_error("vitx_dense_set: output %d x %d outside the patch grid %d x %d .. %d (upsampling only)", oh, ow, c->gh, c->gw, kDenseMaxOut);
@@ -420,9 +405,7 @@ int vitx_dense_set(vitx_ctx *c, const float *W, const float *bias, int K, int Dc
     hipError_t e = hipSuccess;
     if (!ok || !patch_head_scratch(c, dn.get(), &e)) { set_error("vitx_dense_set: cannot allocate the buffers for %d classes, %d x %d labels and %d images", K, oh, ow, dn->cap); return VITX_ERR_NOMEM; }
     // the head goes up rounded (RNE) to the operand type; the zero rows beyond K come from operand_matrix_host, the zero biases from the memset
-    if (e == hipSuccess) e = upload_operand(c, dn->W, W, K, dn->Kpad, Dc);
-    if (e == hipSuccess) e = hipMemset(dn->bias.p, 0, Kpad * 4);
-    if (e == hipSuccess && bias) e = hipMemcpy(dn->bias.p, bias, (size_t)K * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = dense_head_upload(*dn, c->dtype, W, bias);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) return hip_failed("vitx_dense_set", e);
     c->dense = std::move(dn);
@@ -466,7 +449,8 @@ int vitx_depth_set(vitx_ctx *c, const float *Wp, const float *Wc, const float *b
         if (!Wp || !bins) { set_error("vitx_depth_set: NULL weights or bins with K = %d", K); return VITX_ERR_ARG; }
         if (K < 1) { set_error("vitx_depth_set: K = %d bins", K); return VITX_ERR_ARG; }
         if (flags & ~(VITX_DEPTH_NORM | VITX_DEPTH_LOGITS | VITX_DEPTH_FINE)) { set_error("vitx_depth_set: unknown flags 0x%x", flags); return VITX_ERR_ARG; }
-        if (const int rc = patch_head_layers(c, "vitx_depth_set", Dc, &mask, &oh, &ow)) return rc;
+        if (const int rc = patch_head_mask("vitx_depth_set", c->L, c->D, Dc, &mask)) return rc;
+        if (const int rc = patch_head_shape(c, "vitx_depth_set", &oh, &ow)) return rc;
         if (!std::isfinite(min_depth) || !std::isfinite(max_depth) || min_depth > max_depth) { set_error("vitx_depth_set: the depth range %g .. %g must be finite and ordered", (double)min_depth, (double)max_depth); return VITX_ERR_ARG; }
         for (const float *W : {Wp, Wc})
             if (W) for (size_t i = 0, nb = (size_t)K * Dc; i < nb; ++i)
@@ -510,8 +494,8 @@ int vitx_depth_set(vitx_ctx *c, const float *Wp, const float *Wc, const float *b
     }
     if (!ok) { set_error("vitx_depth_set: cannot allocate the buffers for %d bins, %d x %d maps and %d images", K, oh, ow, dp->cap); return VITX_ERR_NOMEM; }
     // the halves go up rounded (RNE) to the operand type; the zero rows beyond K come from operand_matrix_host, the zero biases from the memset
-    if (e == hipSuccess) e = upload_operand(c, dp->Wp, Wp, K, dp->Kpad, Dc);
-    if (e == hipSuccess && Wc) e = upload_operand(c, dp->Wc, Wc, K, dp->Kpad, Dc);
+    if (e == hipSuccess) e = upload_operand(c->dtype, dp->Wp, Wp, K, dp->Kpad, Dc);
+    if (e == hipSuccess && Wc) e = upload_operand(c->dtype, dp->Wc, Wc, K, dp->Kpad, Dc);
     for (const DevMem *m : {&dp->bias, &dp->zero, &dp->bins}) if (e == hipSuccess) e = hipMemset(m->p, 0, Kpad * 4);
     if (e == hipSuccess && bias) e = hipMemcpy(dp->bias.p, bias, (size_t)K * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dp->bins.p, bins, (size_t)K * 4, hipMemcpyHostToDevice);

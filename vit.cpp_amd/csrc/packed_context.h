@@ -1,12 +1,36 @@
-// packed_context.h -- the packed context (struct vitx_pack) of packed_forward.cpp; include/vitx.h "packed batches": n images, each with its own
-// h_i x w_i, their tokens end to end in one [sum N_i][D] residual stream, one forward.  Modelled on the text context (text_context.h): its own
-// scratch, one stream, no sub-batches, no graph cache, no LayerNorm fusion.  Internal: callers see the opaque vitx_pack of include/vitx.h.
+// packed_context.h -- the packed context (struct vitx_pack); include/vitx.h "packed batches": n images, each with its own h_i x w_i, their
+// tokens end to end in one [sum N_i][D] residual stream, one forward.  Modelled on the text context (text_context.h): its own scratch, one
+// stream, no sub-batches, no graph cache, no LayerNorm fusion.  Three units stand on it, split like the image context's: packed_context.cpp
+// (creation, counters, the table cache), packed_forward.cpp (the checks of a call, the forward), packed_outputs.cpp (features, the dense head).
+// Internal: callers see the opaque vitx_pack of include/vitx.h.
 #pragma once
 #include <memory>
 
 #include "heads.h"
 
 using namespace vitx;
+
+// The segment tables of a call, in ints into vitx_pack::tab / host (cap = max_images): row0 [cap + 1] | qb0 [cap + 1] | toff [cap] and, while a
+// dense head is set, behind them tile0 [cap + 1] | seg [cap][kDenseSegInts] (kernels.h).  One buffer, one upload; a new table goes in here.
+struct PackLayout {
+    size_t cap;
+    size_t row0() const { return 0; }
+    size_t qb0() const { return row0() + cap + 1; }
+    size_t toff() const { return qb0() + cap + 1; }
+    size_t tile0() const { return toff() + cap; }
+    size_t seg() const { return tile0() + cap + 1; }
+    size_t ints(bool head) const { return head ? seg() + cap * kDenseSegInts : tile0(); }
+};
+
+// What the host-only checks of a forward call (packed_forward.cpp check_call) give the forward: made once per call, before its first device call
+struct PackCall {
+    std::vector<int32_t> row0;           // [n + 1]: image i's rows of the pack are row0[i] .. row0[i + 1] - 1
+    std::vector<uint64_t> want;          // the distinct grids, in order of first appearance, as (gh << 32 | gw)
+    std::vector<int32_t> grids, outs;    // with a dense head set: [n][2] each, the patch grids and the output shapes
+    std::vector<int64_t> pix0;           // [n + 1], the running pixel count of the outputs
+    std::vector<int32_t> tile0;          // [n + 1], the running tile count of the label launch
+    int cells = 0;                       // the widest tile window (kernels.h dense_pack_tables)
+};
 
 // One grid of the table cache: the position table resampled to gh x gw and the grid's place in the rotary arenas
 struct PackGrid {
@@ -38,11 +62,9 @@ struct vitx_pack {
     float *logits = nullptr, *probs = nullptr;      // [Bpad][C_pad], [max_images][C] f32
     float *logits_out = nullptr;         // [max_images][C] f32: the dense logits of the host entry point
     float *img = nullptr;                // the host entry point's pixels on the device (allocated by its first call)
-    // the segment tables of a call: row0 [cap + 1] | qb0 [cap + 1] | toff [cap] (cap = max_images) and, while a dense head is set, behind them
-    // tile0 [cap + 1] | seg [cap][kDenseSegInts] (kernels.h): one buffer, one upload
-    int *tab = nullptr;
+    int *tab = nullptr;                  // the segment tables of a call (PackLayout)
     std::vector<int> host;               // the same on the host: the staging buffer of the upload
-    std::vector<int32_t> chk, row0;      // [cap + 1] each: the rows of the call being checked; of the last call that passed its checks (vitx_pack_feat_read)
+    std::vector<int32_t> row0;           // PackCall::row0 of the last call that passed its checks (vitx_pack_feat_read, vitx_pack_dense_read)
     hipEvent_t uploaded = nullptr;       // recorded behind the upload of a call: the next call waits for it before it overwrites `host`
     bool uploaded_pending = false;
     hipEvent_t done = nullptr;           // recorded behind the last forward: a table is evicted or overwritten only after it
@@ -57,6 +79,10 @@ struct vitx_pack {
     std::unique_ptr<PackDense> dense;    // vitx_pack_dense_set (null: off); its device memory is its own
     int launches = 0, pe_launches = 0;   // kernel launches of the last forward, and how many of them were patch embeddings
     size_t scratch_bytes = 0;            // device bytes of activation scratch and tables held now
+    PackLayout layout() const { return PackLayout{(size_t)max_images}; }
+    // image i of the last call that passed its checks: its patch rows, and where they start in an output that holds every image's patch rows end to end
+    size_t patch_rows(int i) const { return (size_t)(row0[i + 1] - row0[i] - Tp); }
+    size_t patch_at(int i) const { return (size_t)(row0[i] - i * Tp); }
     ~vitx_pack() {
         (void)hipSetDevice(device);
         for (void *p : allocs) (void)hipFree(p);
@@ -68,3 +94,9 @@ struct vitx_pack {
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
+
+// The table cache (packed_context.cpp).  find_grid: the cached grid, or nullptr.  wait_done: before a table is freed or overwritten, the last forward
+// of this context, which may still read it on another stream, is waited for.  resolve_grids: the tables of every grid a call names, on its stream.
+PackGrid *find_grid(vitx_pack *p, int gh, int gw);
+int wait_done(vitx_pack *p);
+int resolve_grids(vitx_pack *p, const std::vector<uint64_t> &want, hipStream_t st);

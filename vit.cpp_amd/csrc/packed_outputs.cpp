@@ -1,0 +1,125 @@
+// packed_outputs.cpp -- what a packed context gives besides probabilities (packed_context.h; include/vitx.h "packed batches"): the last layer's
+// features and the dense head.  Both opt-in; the forward (packed_forward.cpp) launches nothing for an output that is off.  The dense head's own
+// argument checks and its upload are the image context's (heads.h: dense_head_args, dense_head_values, dense_head_upload).
+#include <algorithm>
+
+#include "packed_context.h"
+
+extern "C" {
+
+int vitx_pack_feat_enable(vitx_pack *p, int flags) {
+    if (!p || (flags & ~(VITX_FEAT_CLS | VITX_FEAT_TOKENS))) { set_error("vitx_pack_feat_enable: flags are VITX_FEAT_CLS | VITX_FEAT_TOKENS (0 = off)"); return VITX_ERR_ARG; }
+    HIP_TRY(hipSetDevice(p->device));
+    if (flags && !p->feat) {
+        const size_t bytes = (size_t)p->max_tokens * p->D * 4;
+        HIP_TRY(hipMalloc((void **)&p->feat, bytes));
+        p->scratch_bytes += bytes;
+    }
+    p->feat_flags = flags; p->feat_n = 0;
+    return VITX_OK;
+}
+
+// The last forward's final-norm rows, gathered on the host: cls [n][D] = row row0[i], tokens = image i's patch rows, images end to end
+int vitx_pack_feat_read(vitx_pack *p, float *cls, float *tokens) {
+    if (!p || (!cls && !tokens)) { set_error("vitx_pack_feat_read: NULL argument"); return VITX_ERR_ARG; }
+    if (!p->feat_flags || !p->feat_n) { set_error("vitx_pack_feat_read: no forward has run with features on since vitx_pack_feat_enable"); return VITX_ERR_ARG; }
+    if ((cls && !(p->feat_flags & VITX_FEAT_CLS)) || (tokens && !(p->feat_flags & VITX_FEAT_TOKENS))) { set_error("vitx_pack_feat_read: an output was asked for that vitx_pack_feat_enable did not select"); return VITX_ERR_ARG; }
+    HIP_TRY(hipSetDevice(p->device));
+    if (p->done_pending) HIP_TRY(hipEventSynchronize(p->done));
+    const int n = p->feat_n, D = p->D;
+    const size_t rowb = (size_t)D * 4;
+    for (int i = 0; i < n; ++i) {
+        const float *src = p->feat + (size_t)p->row0[i] * D;
+        if (cls) HIP_TRY(hipMemcpy(cls + (size_t)i * D, src, rowb, hipMemcpyDeviceToHost));
+        if (tokens) HIP_TRY(hipMemcpy(tokens + p->patch_at(i) * D, src + (size_t)p->Tp * D, p->patch_rows(i) * rowb, hipMemcpyDeviceToHost));
+    }
+    return VITX_OK;
+}
+
+// The dense head of a packed context (include/vitx.h "packed batches").  Every argument check comes before the first device call; the head is
+// built in a local and moved in, so a refused or failed set leaves the head that was set.
+int vitx_pack_dense_set(vitx_pack *p, const float *W, const float *bias, int K, int Dc, uint64_t layer_mask, long max_pixels, int flags) {
+    if (!p) { set_error("vitx_pack_dense_set: NULL context"); return VITX_ERR_ARG; }
+    const bool off = !W && K == 0;
+    uint64_t mask = layer_mask;
+    const size_t Mp = (size_t)round_up(p->max_tokens, p->tm), Kpad = K > 0 ? (size_t)round_up(K, p->tn) : 0;
+    if (!off) {
+        if (const int rc = dense_head_args("vitx_pack_dense_set", W, K, Dc, flags, p->L, p->D, &mask)) return rc;
+        if (max_pixels < 1) { set_error("vitx_pack_dense_set: max_pixels = %ld", max_pixels); return VITX_ERR_ARG; }
+        if (const int rc = dense_head_values("vitx_pack_dense_set", W, bias, K, Dc)) return rc;
+        if (Mp * Dc * 2 > 0xf0000000u || Mp * Kpad * 4 > 0xf0000000u) {
+            set_error("vitx_pack_dense_set: the operand or logit rows of max_tokens = %d rows leave the GEMM's 32-bit byte window", p->max_tokens);
+            return VITX_ERR_UNSUPPORTED;
+        }
+    }
+    HIP_TRY(hipSetDevice(p->device));
+    // nothing of this context is in flight while buffers and tables change hands
+    if (p->uploaded_pending) { HIP_TRY(hipEventSynchronize(p->uploaded)); p->uploaded_pending = false; }
+    if (const int rc = wait_done(p)) return rc;
+    // the segment tables with or without the head's part behind them (PackLayout): a fresh zeroed buffer in place of the old one
+    auto resize_tables = [&](bool head) -> int {
+        const size_t ints = p->layout().ints(head);
+        if (p->host.size() == ints) return VITX_OK;
+        int *t = nullptr;
+        HIP_TRY(hipMalloc((void **)&t, ints * 4));
+        if (const hipError_t e = hipMemset(t, 0, ints * 4); e != hipSuccess) { (void)hipFree(t); set_error("vitx_pack_dense_set: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
+        std::replace(p->allocs.begin(), p->allocs.end(), (void *)p->tab, (void *)t);
+        (void)hipFree(p->tab);
+        p->scratch_bytes += ints * 4; p->scratch_bytes -= p->host.size() * 4;
+        p->tab = t; p->host.assign(ints, 0);
+        return VITX_OK;
+    };
+    if (off) {
+        if (p->dense) { p->scratch_bytes -= p->dense->bytes; p->dense.reset(); }
+        return resize_tables(false);
+    }
+    auto dn = std::make_unique<PackDense>();
+    dn->K = K; dn->Kpad = (int)Kpad; dn->Dc = Dc; dn->mask = mask; dn->flags = flags; dn->cap = p->max_images; dn->max_pixels = max_pixels;
+    dn->a.resize(1); dn->acc.resize(1);
+    dn->scratch = Mp * Dc * 2 + Mp * Kpad * 4;
+    dn->bytes = dn->scratch + Kpad * Dc * 2 + Kpad * 4 + (size_t)max_pixels;
+    bool ok = dn->W.alloc(Kpad * Dc * 2) && dn->bias.alloc(Kpad * 4) && dn->a[0].alloc(Mp * Dc * 2) && dn->acc[0].alloc(Mp * Kpad * 4) && dn->labels.alloc((size_t)max_pixels);
+    if (ok && (flags & VITX_DENSE_SCORE)) { ok = dn->score.alloc((size_t)max_pixels * 4); dn->bytes += (size_t)max_pixels * 4; }
+    if (ok && (flags & VITX_DENSE_LOGITS)) { ok = dn->logits.alloc((size_t)p->max_tokens * K * 4); dn->bytes += (size_t)p->max_tokens * K * 4; }
+    if (!ok) { set_error("vitx_pack_dense_set: cannot allocate the buffers for %d classes, %ld pixels and %d token rows", K, max_pixels, p->max_tokens); return VITX_ERR_NOMEM; }
+    // the head goes up as in an image context; the operand rows start as zeros (a forward writes its rows and zeroes the pad rows behind them)
+    HIP_TRY(dense_head_upload(*dn, p->dtype, W, bias));
+    HIP_TRY(hipMemset(dn->a[0].p, 0, Mp * Dc * 2));
+    HIP_TRY(hipDeviceSynchronize());
+    if (const int rc = resize_tables(true)) return rc;
+    if (p->dense) p->scratch_bytes -= p->dense->bytes;
+    p->scratch_bytes += dn->bytes;
+    p->dense = std::move(dn);
+    return VITX_OK;
+}
+
+int vitx_pack_dense_out(vitx_pack *p, const int32_t *out_shapes, int n) {
+    if (!p || !p->dense) { set_error("vitx_pack_dense_out: no dense head is set"); return VITX_ERR_ARG; }
+    if (!out_shapes || n == 0) { p->dense->next_out.clear(); return VITX_OK; }
+    if (n < 1 || n > p->max_images) { set_error("vitx_pack_dense_out: n = %d is outside 1 .. max_images = %d", n, p->max_images); return VITX_ERR_ARG; }
+    p->dense->next_out.assign(out_shapes, out_shapes + (size_t)2 * n);
+    return VITX_OK;
+}
+
+const void *vitx_pack_dense_device(const vitx_pack *p) { return p && p->dense ? p->dense->labels.p : nullptr; }
+size_t vitx_pack_dense_scratch_bytes(const vitx_pack *p) { return p && p->dense ? p->dense->scratch : 0; }
+
+// The last forward's maps, the images end to end, and the kept logits of its patch rows (behind each image's prefix rows in the pack's rows)
+int vitx_pack_dense_read(vitx_pack *p, uint8_t *labels, float *score, float *logits) {
+    if (!p || !labels) { set_error("vitx_pack_dense_read: NULL argument"); return VITX_ERR_ARG; }
+    const PackDense *dn = p->dense.get();
+    const int n = dn ? dn->n : 0;
+    if (n == 0) { set_error("vitx_pack_dense_read: no forward has run with a dense head set since vitx_pack_dense_set"); return VITX_ERR_ARG; }
+    if (score && !dn->score) { set_error("vitx_pack_dense_read: the head was set without VITX_DENSE_SCORE"); return VITX_ERR_ARG; }
+    if (logits && !dn->logits) { set_error("vitx_pack_dense_read: the head was set without VITX_DENSE_LOGITS"); return VITX_ERR_ARG; }
+    HIP_TRY(hipSetDevice(p->device));
+    if (p->done_pending) HIP_TRY(hipEventSynchronize(p->done));
+    const size_t px = (size_t)dn->pix0[n];
+    HIP_TRY(hipMemcpy(labels, dn->labels.p, px, hipMemcpyDeviceToHost));
+    if (score) HIP_TRY(hipMemcpy(score, dn->score.p, px * 4, hipMemcpyDeviceToHost));
+    if (logits) for (int i = 0; i < n; ++i)
+        HIP_TRY(hipMemcpy(logits + p->patch_at(i) * dn->K, dn->logits.as<float>() + (size_t)(p->row0[i] + p->Tp) * dn->K, p->patch_rows(i) * dn->K * 4, hipMemcpyDeviceToHost));
+    return VITX_OK;
+}
+
+}  // extern "C"
