@@ -1192,9 +1192,47 @@ int vitx_op_attention_generic(int dtype, const void *d_qkv, void *d_out, int n_i
  *                              to end; nothing else is written.  A work item is (image, 64 x 16 output tile), found by a binary search of the
  *                              workgroup index in the running tile count.  vitx_op_dense_labels's checks per image.  TEST entry point: it builds
  *                              and uploads the tables and frees them after the launch (synchronises).
- * Not offered on packed contexts (each a later step): the other opt-in heads (attention maps, zero-shot bank, gallery, depth), the pooled
+ *
+ * The depth head on a pack (vitx_pack_depth_set): "depth estimation" above, word for word and per image -- the operand is RNE of the raw or
+ * (VITX_DEPTH_NORM) final-norm tokens of the selected layers, the patch logits and the class half's offsets come from the dispatcher GEMM with
+ * f32 accumulation, the fine plane and the map from csrc/dense_resample.h and csrc/depth_bins.h -- with one fine plane (u gh_i x u gw_i) and one
+ * depth map per image AT ITS OWN SIZE, planes and maps end to end.  vitx_pack_depth_set has vitx_depth_set's meaning, flags (VITX_DEPTH_NORM |
+ * VITX_DEPTH_LOGITS | VITX_DEPTH_FINE) and value checks (K <= 256 finite positive bins, upsample 1, 2 or 4, one to four layers, Dc =
+ * popcount(layer_mask) D, 0 = the last layer, finite halves and bias, a finite ordered depth range; Wp == NULL && K == 0: off, everything freed);
+ * max_pixels sizes the depth buffer, the fine buffer holds upsample^2 max_tokens floats.  VITX_ERR_UNSUPPORTED before any device call when the
+ * operand or logit rows of max_tokens rows leave the GEMMs' 32-bit byte window.  A refused set leaves the head that was set in place.  With no
+ * depth head set nothing is allocated or launched for it.  Per forward: as each selected layer finishes, ONE launch over all rows of the pack
+ * -- the stand-alone LayerNorm, or raw the streaming conversion -- writes that layer's column slot of the operand (prefix rows included);
+ * after the forward the patch GEMM over the pack's rows (image i's first logit row is row0[i] + T), with a class half (Wc) one gather of the n
+ * class rows row0[i] of that operand into compact rows and the short offsets GEMM (without Wc the bias is every image's offsets row and neither
+ * is launched), then ONE fine launch and ONE resize launch (vitx_op_depth_fine_packed's and vitx_op_depth_resize_packed's kernels): m + 3
+ * kernel launches more, m + 5 with a class half, counted by vitx_pack_launches.  The tables of both launches ride in the call's one table
+ * upload.  By default image i's map is h_i x w_i; vitx_pack_depth_out gives the NEXT forward call other shapes, with vitx_pack_dense_out's
+ * meaning: that call consumes them whether it runs or is refused.  Refused before the call's first device call, nothing launched or written,
+ * the context usable: VITX_ERR_ARG for an n that differs from the call's, an output side below the image's fine plane or above 8192
+ * (upsampling only), more than max_pixels output pixels in the call; VITX_ERR_UNSUPPORTED for a fine side above 8192.  vitx_pack_depth_check
+ * is that text, host only; it returns pix0 and fine0 [n + 1] (image i's map is floats pix0[i] .. pix0[i + 1] - 1, its fine plane fine0[i] ..)
+ * and ftile0 / otile0 [n + 1] (the running counts of the fine launch's 16 x 16 and the resize launch's 64 x 16 tiles); any may be NULL.
+ * vitx_pack_depth_read (waits for the forward): depth [sum oh_i ow_i] and fine [sum u^2 gh_i gw_i] (VITX_DEPTH_FINE) f32 the images end to
+ * end, logits [sum gh_i gw_i][K] the kept patch logits and offsets [n][K] (VITX_DEPTH_LOGITS; without a class half the bias n times).
+ * vitx_pack_depth_device: the device depth buffer (NULL while off).  vitx_pack_depth_scratch_bytes: the head's operand, logit, class-row and
+ * offset scratch; all of the head's buffers count in vitx_pack_scratch_bytes.  An image's logits, offsets, fine plane and map are a function
+ * of its own pixels, shape and output shape: the same bits alone, at any position and beside any neighbours (the LDS of the fine launch and
+ * its bin chunk come from the call's widest window; a lane carries its two sums across chunks in bin order, so no bit depends on them); a
+ * pack of one shape gives the maps and kept logits of a rectangular context with the same head.  A dense head and a depth head may both be
+ * set; neither changes the other's bits.
+ *   vitx_op_depth_fine_packed  the fine kernel on a pack: d_logits [rows][ld], d_offsets [.][ld] or NULL, d_bins [K], HOST grids [n][2] = (gh, gw),
+ *                              lrow [n] = image i's first logit row (its gh gw rows follow; rows between images are never read) and orow [n] = its
+ *                              row of d_offsets -> d_fine f32, image i's plane with the bits of vitx_op_depth_fine on that image alone, the planes
+ *                              end to end; nothing else is written.  A work item is (image, 16 x 16 fine tile), found by a binary search of the
+ *                              workgroup index in the running tile count: a 1-D grid, so no bound on n.  vitx_op_depth_fine's checks per image.
+ *   vitx_op_depth_resize_packed  the resize kernel on a pack: d_fine = the fine planes end to end, HOST fines [n][2] = (fh, fw) and outs [n][2] =
+ *                              (oh, ow) -> d_out f32, image i's map with the bits of vitx_op_depth_resize on that image alone, the maps end to
+ *                              end.  A work item is (image, 64 x 16 output tile).  vitx_op_depth_resize's checks per image.
+ *                              Both are TEST entry points: they build and upload the tables and free them after the launch (synchronise).
+ * Not offered on packed contexts (each a later step): the other opt-in heads (attention maps, zero-shot bank, gallery), the pooled
  * and attention-pooling heads, the F16 parity planes, LayerNorm fusion and sub-batch streams, a packed patch-embedding kernel, vitx_group_*;
- * of the dense head: downsampling, and a vit.h wrapper. */
+ * of the dense and the depth head: downsampling, and a vit.h wrapper. */
 typedef struct vitx_pack vitx_pack;
 typedef struct { int pos_interp, max_grids, reserved[6]; } vitx_pack_options;
 int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_images, int dtype, const vitx_pack_options *opt, vitx_pack **out);
@@ -1229,6 +1267,25 @@ int vitx_op_dense_labels_packed(const void *d_logits, long ld, const int32_t *gr
  * tile count and widest window; then the launch on a table the caller uploaded and vouches for (only enqueues) */
 int vitx_dense_pack_tables(const int32_t *grids, const int32_t *outs, const int32_t *lrow, int n, int32_t *tab, int *tiles, int *cells);
 int vitx_op_dense_labels_packed_tables(const void *d_logits, long ld, const void *d_tab, int n, int tiles, int cells, int K, void *d_labels, void *d_score, void *stream);
+int vitx_pack_depth_set(vitx_pack *p, const float *Wp /* [K][Dc] */, const float *Wc /* [K][Dc] or NULL */, const float *bias /* [K] or NULL */, const float *bins /* [K] */,
+                        int K, int Dc, uint64_t layer_mask, int upsample, float min_depth, float max_depth, long max_pixels, int flags);
+int vitx_pack_depth_out(vitx_pack *p, const int32_t *out_shapes /* [n][2] = out_h, out_w; NULL: the images' own */, int n);
+/* host only: every refusal a forward call adds while a depth head of K bins, upsample and max_pixels is set */
+int vitx_pack_depth_check(const vitx_model *m, const int32_t *shapes, const int32_t *out_shapes /* or NULL */, int n, int K, int upsample, long max_pixels,
+                          int64_t *pix0 /* [n + 1] or NULL */, int64_t *fine0 /* [n + 1] or NULL */, int32_t *ftile0 /* [n + 1] or NULL */, int32_t *otile0 /* [n + 1] or NULL */);
+int vitx_pack_depth_read(vitx_pack *p, float *depth, float *fine /* or NULL */, float *logits /* or NULL */, float *offsets /* or NULL */);
+const void *vitx_pack_depth_device(const vitx_pack *p);
+size_t vitx_pack_depth_scratch_bytes(const vitx_pack *p);
+int vitx_op_depth_fine_packed(const void *d_logits, long ld, const void *d_offsets /* or NULL */, const void *d_bins, const int32_t *grids /* host [n][2] */,
+                              const int32_t *lrow /* host [n] */, const int32_t *orow /* host [n]; NULL without d_offsets */, int n, int K, int upsample, void *d_fine, void *stream);
+int vitx_op_depth_resize_packed(const void *d_fine, const int32_t *fines /* host [n][2] */, const int32_t *outs /* host [n][2] */, int n, float min_depth, float max_depth,
+                                void *d_out, void *stream);
+/* the same in two steps, for callers that keep the tables: host only, tab int32 [2 (n + 1) + 16 n] (the running fine and output tile counts, then a row per
+ * image), its tile counts and widest window; then the launches on a table the caller uploaded and vouches for (only enqueue); ldo = 0: one offsets row for all */
+int vitx_depth_pack_tables(const int32_t *grids, const int32_t *outs, const int32_t *lrow, const int32_t *orow, int n, int upsample, int32_t *tab, int *ftiles, int *otiles, int *cells);
+int vitx_op_depth_fine_packed_tables(const void *d_logits, long ld, const void *d_offsets, long ldo, const void *d_bins, const void *d_tab, int n, int tiles, int cells, int K,
+                                     void *d_fine, void *stream);
+int vitx_op_depth_resize_packed_tables(const void *d_fine, const void *d_tab, int n, int tiles, float min_depth, float max_depth, void *d_out, void *stream);
 
 /* ---- MXFP8 operands (VITX_MXFP8, encoding above) ------------------------------- */
 /* Host encoder: x f32 [rows][K] -> q [rows][k_pad] e4m3 bytes + scales [rows][k_pad / 32] (k_pad >= K, a multiple of 32; columns

@@ -73,6 +73,8 @@ EXPORTS = [
     "vitx_pack_feat_enable", "vitx_pack_feat_read", "vitx_pack_scratch_bytes", "vitx_pack_launches", "vitx_op_attention_packed", "vitx_op_attention_packed_tables", "vitx_op_rope_packed",
     "vitx_pack_dense_set", "vitx_pack_dense_out", "vitx_pack_dense_check", "vitx_pack_dense_read", "vitx_pack_dense_device", "vitx_pack_dense_scratch_bytes", "vitx_op_dense_labels_packed",
     "vitx_dense_pack_tables", "vitx_op_dense_labels_packed_tables",
+    "vitx_pack_depth_set", "vitx_pack_depth_out", "vitx_pack_depth_check", "vitx_pack_depth_read", "vitx_pack_depth_device", "vitx_pack_depth_scratch_bytes",
+    "vitx_op_depth_fine_packed", "vitx_op_depth_resize_packed", "vitx_depth_pack_tables", "vitx_op_depth_fine_packed_tables", "vitx_op_depth_resize_packed_tables",
 ]
 
 
@@ -348,6 +350,19 @@ def lib():
             L.vitx_op_dense_labels_packed.argtypes = [vp, C.c_long, i32p, i32p, i32p, ip, ip, vp, vp, vp]
             L.vitx_dense_pack_tables.argtypes = [i32p, i32p, i32p, ip, i32p, C.POINTER(ip), C.POINTER(ip)]
             L.vitx_op_dense_labels_packed_tables.argtypes = [vp, C.c_long, vp, ip, ip, ip, ip, vp, vp, vp]
+        if hasattr(L, "vitx_pack_depth_set"):
+            i32p, i64p, fp, cf = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_float), C.c_float
+            L.vitx_pack_depth_set.argtypes = [vp, fp, fp, fp, fp, ip, ip, C.c_uint64, ip, cf, cf, C.c_long, ip]
+            L.vitx_pack_depth_out.argtypes = [vp, i32p, ip]
+            L.vitx_pack_depth_check.argtypes = [vp, i32p, i32p, ip, ip, ip, C.c_long, i64p, i64p, i32p, i32p]
+            L.vitx_pack_depth_read.argtypes = [vp, fp, fp, fp, fp]
+            L.vitx_pack_depth_device.restype = C.c_void_p; L.vitx_pack_depth_device.argtypes = [vp]
+            L.vitx_pack_depth_scratch_bytes.restype = C.c_size_t; L.vitx_pack_depth_scratch_bytes.argtypes = [vp]
+            L.vitx_op_depth_fine_packed.argtypes = [vp, C.c_long, vp, vp, i32p, i32p, i32p, ip, ip, ip, vp, vp]
+            L.vitx_op_depth_resize_packed.argtypes = [vp, i32p, i32p, ip, cf, cf, vp, vp]
+            L.vitx_depth_pack_tables.argtypes = [i32p, i32p, i32p, i32p, ip, ip, i32p, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]
+            L.vitx_op_depth_fine_packed_tables.argtypes = [vp, C.c_long, vp, C.c_long, vp, vp, ip, ip, ip, ip, vp, vp]
+            L.vitx_op_depth_resize_packed_tables.argtypes = [vp, vp, ip, ip, cf, cf, vp, vp]
         _lib = L
     return _lib
 
@@ -1178,6 +1193,7 @@ class PackContext:
         check(lib().vitx_pack_create(model._h, device, max_tokens, max_images, dtype, C.byref(opt), C.byref(self._h)), "vitx_pack_create")
         self._shapes = None; self._feat = 0
         self._dense = self._dense_out = self._dense_shapes = None
+        self._depth = self._depth_out = self._depth_shapes = None
 
     def close(self):
         if getattr(self, "_h", None) and self._h:
@@ -1273,10 +1289,14 @@ class PackContext:
         self._dense_out = s
 
     def _dense_forward(self, s, ok: bool) -> None:
-        """Book-keeping of a forward call for dense_read: the call consumed dense_out's shapes; a call that ran fixed the shapes of its maps."""
+        """Book-keeping of a forward call for dense_read and depth_read: the call consumed dense_out's and depth_out's shapes; a call that ran fixed the
+        shapes of its maps."""
         out, self._dense_out = getattr(self, "_dense_out", None), None
         if ok and getattr(self, "_dense", None):
             self._dense_shapes = (s.copy(), (out if out is not None else s).copy())
+        out, self._depth_out = getattr(self, "_depth_out", None), None
+        if ok and getattr(self, "_depth", None):
+            self._depth_shapes = (s.copy(), (out if out is not None else s).copy())
 
     def dense_read(self):
         """(labels: a list of per-image [out_h_i, out_w_i] u8 arrays, scores: the same in f32 or None, logits: a list of [gh_i gw_i, K] f32 or None) of the
@@ -1312,6 +1332,89 @@ class PackContext:
 
     def dense_scratch_bytes(self) -> int:
         return int(lib().vitx_pack_dense_scratch_bytes(self._h))
+
+    def depth_set(self, wp: Optional[np.ndarray], wc: Optional[np.ndarray] = None, bias: Optional[np.ndarray] = None, bins: Optional[np.ndarray] = None,
+                  layers=None, upsample: int = 4, min_depth: float = 0.001, max_depth: float = 10.0, max_pixels: int = 0, norm: bool = False,
+                  logits: bool = False, fine: bool = False) -> None:
+        """A binned depth head for every later forward (vitx_pack_depth_set), Context.depth_set's arguments and meaning: per image a depth map f32 at the
+        image's own shape (or depth_out's).  max_pixels: the output pixels one forward may hold (0: max_tokens x patch x patch, every image at its own
+        shape).  wp None turns the output off and frees its buffers."""
+        fp = C.POINTER(C.c_float)
+        if wp is None:
+            check(lib().vitx_pack_depth_set(self._h, None, None, None, None, 0, 0, 0, 0, 0.0, 0.0, 0, 0), "vitx_pack_depth_set")
+            self._depth = None
+            return
+        w = np.ascontiguousarray(wp, dtype=np.float32)
+        if w.ndim != 2:
+            raise ValueError("depth_set: wp must be [K, Dc]")
+        K = w.shape[0]
+
+        def opt(a, shape, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != shape:
+                raise ValueError(f"depth_set: {name} must be {list(shape)}")
+            return a
+        c, b, bn = opt(wc, w.shape, "wc"), opt(bias, (K,), "bias"), opt(bins, (K,), "bins")
+        if bn is None:
+            raise ValueError("depth_set: bins [K] are required")
+        mask = _layer_mask([] if layers is None else layers, "depth_set: ")
+        P = self.model.hparams.patch_size
+        ptr = lambda a: a.ctypes.data_as(fp) if a is not None else None
+        check(lib().vitx_pack_depth_set(self._h, ptr(w), ptr(c), ptr(b), ptr(bn), K, w.shape[1], mask, int(upsample), float(min_depth), float(max_depth),
+                                        int(max_pixels) or self.max_tokens * P * P,
+                                        (DEPTH_NORM if norm else 0) | (DEPTH_LOGITS if logits else 0) | (DEPTH_FINE if fine else 0)), "vitx_pack_depth_set")
+        self._depth = (K, int(upsample), bool(logits), bool(fine))
+        self._depth_out = self._depth_shapes = None
+
+    def depth_out(self, shapes) -> None:
+        """Output shapes [n][2] = (out_h, out_w) of the NEXT forward's depth maps (vitx_pack_depth_out), e.g. the sizes of the originals; that forward
+        consumes them.  None withdraws them."""
+        if shapes is None:
+            check(lib().vitx_pack_depth_out(self._h, None, 0), "vitx_pack_depth_out")
+            self._depth_out = None
+            return
+        s = _pack_shapes(shapes)
+        check(lib().vitx_pack_depth_out(self._h, s.ctypes.data_as(C.POINTER(C.c_int32)), s.shape[0]), "vitx_pack_depth_out")
+        self._depth_out = s
+
+    def depth_read(self):
+        """(depth: a list of per-image [out_h_i, out_w_i] f32 arrays, fine: a list of [u gh_i, u gw_i] f32 or None, logits: a list of [gh_i gw_i, K] f32 or
+        None, offsets [n, K] f32 or None) of the last forward made with the depth head set (vitx_pack_depth_read)."""
+        if not getattr(self, "_depth", None) or getattr(self, "_depth_shapes", None) is None:
+            e = VitxError("depth_read: no forward has run with a depth head set")
+            e.code = ERR_ARG
+            raise e
+        K, u, want_logits, want_fine = self._depth
+        shapes, outs = self._depth_shapes
+        P = self.model.hparams.patch_size
+        grids = [(int(h) // P, int(w) // P) for h, w in shapes]
+        px = [int(h) * int(w) for h, w in outs]
+        npatch = [a * b for a, b in grids]
+        depth = np.empty(sum(px), np.float32)
+        fine = np.empty(u * u * sum(npatch), np.float32) if want_fine else None
+        logits = np.empty((sum(npatch), K), np.float32) if want_logits else None
+        offsets = np.empty((len(grids), K), np.float32) if want_logits else None
+        fp = C.POINTER(C.c_float)
+        ptr = lambda a: a.ctypes.data_as(fp) if a is not None else None
+        check(lib().vitx_pack_depth_read(self._h, ptr(depth), ptr(fine), ptr(logits), ptr(offsets)), "vitx_pack_depth_read")
+        dm, fn, lg, at, af, ar = [], [], [], 0, 0, 0
+        for (oh, ow), (gh, gw), p_, r_ in zip(outs, grids, px, npatch):
+            dm.append(depth[at:at + p_].reshape(int(oh), int(ow)))
+            if want_fine:
+                fn.append(fine[af:af + u * u * r_].reshape(u * gh, u * gw))
+            if want_logits:
+                lg.append(logits[ar:ar + r_])
+            at += p_; af += u * u * r_; ar += r_
+        return dm, (fn if want_fine else None), (lg if want_logits else None), offsets
+
+    def depth_device(self) -> int:
+        """Device pointer of the depth buffer (the maps of a forward end to end, f32), 0 while off."""
+        return int(lib().vitx_pack_depth_device(self._h) or 0)
+
+    def depth_scratch_bytes(self) -> int:
+        return int(lib().vitx_pack_depth_scratch_bytes(self._h))
 
     @property
     def shares_weights(self) -> bool:
@@ -1383,6 +1486,77 @@ def op_dense_labels_packed_tables(d_logits: int, ld: int, d_tab: int, n: int, ti
     """vitx_op_dense_labels_packed_tables: the packed label launch on a table of dense_pack_tables already on the device; only enqueues."""
     check(lib().vitx_op_dense_labels_packed_tables(d_logits or None, ld, d_tab or None, n, tiles, cells, K, d_labels or None, d_score or None, stream or None),
           "vitx_op_dense_labels_packed_tables")
+
+
+def pack_depth_check(model: Model, shapes, out_shapes, K: int, upsample: int, max_pixels: int):
+    """vitx_pack_depth_check (host only): (pix0 int64 [n + 1], fine0 int64 [n + 1], ftile0 int32 [n + 1], otile0 int32 [n + 1]) of a packed forward of
+    `shapes` [n][2] with a depth head of K bins, `upsample` and max_pixels set -- image i's map is floats pix0[i] .. pix0[i + 1] - 1, its fine plane
+    fine0[i] .., ftile0 / otile0 the running counts of the fine launch's 16 x 16 and the resize launch's 64 x 16 tiles -- or VitxError for what such a
+    forward refuses.  out_shapes [n][2] = (out_h, out_w), None: the images' own shapes."""
+    a = _pack_shapes(shapes)
+    o = None if out_shapes is None else _pack_shapes(out_shapes)
+    # the C call takes one n: a list of another length is refused there as a forward refuses it, through the n the head would see
+    n = a.shape[0]
+    if o is not None and o.shape[0] != n:
+        e = VitxError(f"vitx_pack_depth_check: output shapes were given for {o.shape[0]} images, the call has {n}")
+        e.code = ERR_ARG
+        raise e
+    pix0, fine0, ftile0, otile0 = np.empty(n + 1, np.int64), np.empty(n + 1, np.int64), np.empty(n + 1, np.int32), np.empty(n + 1, np.int32)
+    i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    check(lib().vitx_pack_depth_check(model._h, a.ctypes.data_as(i32p), o.ctypes.data_as(i32p) if o is not None else None, n, K, upsample, max_pixels,
+                                      pix0.ctypes.data_as(i64p), fine0.ctypes.data_as(i64p), ftile0.ctypes.data_as(i32p), otile0.ctypes.data_as(i32p)), "vitx_pack_depth_check")
+    return pix0, fine0, ftile0, otile0
+
+
+def op_depth_fine_packed(d_logits: int, ld: int, d_offsets: int, d_bins: int, grids, lrow, orow, K: int, upsample: int, d_fine: int, stream: int = 0) -> None:
+    """vitx_op_depth_fine_packed: the fine kernel on a pack.  d_logits [rows, ld] f32, d_offsets [., ld] f32 (or 0) and d_bins [K] on the device; host grids
+    [n][2] = (gh, gw), lrow [n] = each image's first logit row, orow [n] = its offsets row (None without offsets) -> d_fine f32, the planes end to end."""
+    g = _pack_shapes(grids)
+    r = np.ascontiguousarray(lrow, np.int32)
+    q = None if orow is None else np.ascontiguousarray(orow, np.int32)
+    if r.shape != (g.shape[0],) or (q is not None and q.shape != r.shape):
+        raise ValueError("op_depth_fine_packed: grids is [n][2], lrow and orow are [n]")
+    i32p = C.POINTER(C.c_int32)
+    check(lib().vitx_op_depth_fine_packed(d_logits or None, ld, d_offsets or None, d_bins or None, g.ctypes.data_as(i32p), r.ctypes.data_as(i32p),
+                                          q.ctypes.data_as(i32p) if q is not None else None, g.shape[0], K, upsample, d_fine or None, stream or None), "vitx_op_depth_fine_packed")
+
+
+def op_depth_resize_packed(d_fine: int, fines, outs, min_depth: float, max_depth: float, d_out: int, stream: int = 0) -> None:
+    """vitx_op_depth_resize_packed: the resize kernel on a pack.  d_fine = the fine planes end to end; host fines [n][2] = (fh, fw), outs [n][2] =
+    (out_h, out_w) -> d_out f32, the maps end to end."""
+    f, o = _pack_shapes(fines), _pack_shapes(outs)
+    if o.shape != f.shape:
+        raise ValueError("op_depth_resize_packed: fines and outs are [n][2]")
+    i32p = C.POINTER(C.c_int32)
+    check(lib().vitx_op_depth_resize_packed(d_fine or None, f.ctypes.data_as(i32p), o.ctypes.data_as(i32p), f.shape[0], min_depth, max_depth, d_out or None, stream or None),
+          "vitx_op_depth_resize_packed")
+
+
+def depth_pack_tables(grids, outs, lrow, orow, upsample: int):
+    """vitx_depth_pack_tables (host only): (tab int32 [2 (n + 1) + 16 n], ftiles, otiles, cells) -- the device table of the packed fine and resize
+    launches, to be uploaded by the caller for op_depth_fine_packed_tables / op_depth_resize_packed_tables."""
+    g, o = _pack_shapes(grids), _pack_shapes(outs)
+    r, q = np.ascontiguousarray(lrow, np.int32), np.ascontiguousarray(orow, np.int32)
+    if o.shape != g.shape or r.shape != (g.shape[0],) or q.shape != r.shape:
+        raise ValueError("depth_pack_tables: grids and outs are [n][2], lrow and orow are [n]")
+    n = g.shape[0]
+    tab, ft, ot, cells = np.zeros(2 * (n + 1) + 16 * n, np.int32), C.c_int(), C.c_int(), C.c_int()
+    i32p = C.POINTER(C.c_int32)
+    check(lib().vitx_depth_pack_tables(g.ctypes.data_as(i32p), o.ctypes.data_as(i32p), r.ctypes.data_as(i32p), q.ctypes.data_as(i32p), n, upsample, tab.ctypes.data_as(i32p),
+                                       C.byref(ft), C.byref(ot), C.byref(cells)), "vitx_depth_pack_tables")
+    return tab, ft.value, ot.value, cells.value
+
+
+def op_depth_fine_packed_tables(d_logits: int, ld: int, d_offsets: int, ldo: int, d_bins: int, d_tab: int, n: int, tiles: int, cells: int, K: int, d_fine: int,
+                                stream: int = 0) -> None:
+    """vitx_op_depth_fine_packed_tables: the packed fine launch on a table of depth_pack_tables already on the device; only enqueues."""
+    check(lib().vitx_op_depth_fine_packed_tables(d_logits or None, ld, d_offsets or None, ldo, d_bins or None, d_tab or None, n, tiles, cells, K, d_fine or None, stream or None),
+          "vitx_op_depth_fine_packed_tables")
+
+
+def op_depth_resize_packed_tables(d_fine: int, d_tab: int, n: int, tiles: int, min_depth: float, max_depth: float, d_out: int, stream: int = 0) -> None:
+    """vitx_op_depth_resize_packed_tables: the packed resize launch on a table of depth_pack_tables already on the device; only enqueues."""
+    check(lib().vitx_op_depth_resize_packed_tables(d_fine or None, d_tab or None, n, tiles, min_depth, max_depth, d_out or None, stream or None), "vitx_op_depth_resize_packed_tables")
 
 
 def op_rope_packed(dtype: int, d_qkv: int, d_cos: int, d_sin: int, d_row0: int, d_table_off: int, n: int, prefix: int, D: int, H: int, stream: int = 0) -> None:

@@ -17,6 +17,7 @@ directory-walk accuracy harness:
     python vit_cli.py -m backbone.gguf -i image.jpg --dense-head head.npz --dense-out labels.pgm [--img-shape HxW | --img-fit SHORT]   # a label per pixel (P5 picture of class bytes)
     python vit_cli.py -m backbone.gguf -i a.jpg,b.jpg --pack --img-fit SHORT --dense-head head.npz --dense-out PREFIX   # PREFIX.<i>.pgm per image, at each ORIGINAL's size
     python vit_cli.py -m backbone.gguf -i image.jpg --depth-head head.npz --depth-out depth.npy [--img-shape HxW | --img-fit SHORT]   # a depth per pixel (float32 .npy)
+    python vit_cli.py -m backbone.gguf -i a.jpg,b.jpg --pack --img-fit SHORT --depth-head head.npz --depth-out PREFIX   # PREFIX.<i>.npy per image, at each ORIGINAL's size
 
 --preprocess model follows the file's `preproc` tensor (include/vitx.h "each model's own preprocessing": what convert.py reads from a
 HuggingFace preprocessor_config.json -- CLIP: Pillow-bicubic shortest edge 224, centre crop 224, CLIP's mean / std; DINOv2: shortest edge 256,
@@ -203,17 +204,16 @@ def main(argv: List[str] | None = None) -> int:
     if bool(a.depth_head) != bool(a.depth_out):
         ap.error("--depth-head HEAD.npz and --depth-out PATH.npy go together")
     if a.depth_head and (a.dir is not None or a.gallery_build or a.gallery or a.dense_head):
-        ap.error("--depth-head measures the single image of -i (and not together with --dense-head)")
+        ap.error("--depth-head measures the single image of -i (or, with --pack, each image of -i A.jpg,B.jpg,...), and not together with --dense-head")
     if a.gallery and (a.dir is not None or a.gallery_build):
         ap.error("--gallery searches for the single image of -i")
     if sum(bool(v) for v in (a.img_size, a.img_shape, a.img_fit)) > 1:
         ap.error("--img-size, --img-shape and --img-fit are three ways to say one thing: give one")
     if a.img_fit and a.dir is not None:
         ap.error("--img-fit takes its shape from the single image of -i, not --dir (use --img-shape HxW)")
-    if a.pack and (not a.img_fit or a.dir is not None or a.dtype == "mxfp8" or a.attn_map or a.embed or a.zero_shot or a.text_model or a.gallery or a.gallery_build
-                   or a.depth_head):
+    if a.pack and (not a.img_fit or a.dir is not None or a.dtype == "mxfp8" or a.attn_map or a.embed or a.zero_shot or a.text_model or a.gallery or a.gallery_build):
         ap.error("--pack takes --img-fit SHORT, the images of -i A.jpg,B.jpg,... and --dtype f16 or bf16; of the opt-in outputs a packed context has the dense head "
-                 "(--dense-head HEAD.npz --dense-out PREFIX) only")
+                 "(--dense-head HEAD.npz --dense-out PREFIX) and the depth head (--depth-head HEAD.npz --depth-out PREFIX) only")
     if (a.img_shape or a.img_fit) and a.preprocess == "reference":
         ap.error("--preprocess reference resizes to squares only: not with --img-shape / --img-fit")
     rect = None                                          # (img_h, img_w) of a rectangular context
@@ -330,13 +330,28 @@ def main(argv: List[str] | None = None) -> int:
                 outs = [(max(im.shape[0], h // P), max(im.shape[1], w // P)) for im, (h, w) in zip(imgs, shapes)]
                 ctx.dense_set(dense["weight"], dense["bias"], dense["layers"], max_pixels=sum(h * w for h, w in outs))
                 ctx.dense_out(outs)
+            if depth:
+                # a depth map per image at the ORIGINAL's size (never below the fine plane: a tiny original keeps that side of the fine plane)
+                P, u = model.hparams.patch_size, depth["upsample"]
+                outs = [(max(im.shape[0], u * (h // P)), max(im.shape[1], u * (w // P))) for im, (h, w) in zip(imgs, shapes)]
+                ctx.depth_set(depth["wp"], depth["wc"], depth["bias"], depth["bins"], depth["layers"], u, depth["min_depth"], depth["max_depth"],
+                              max_pixels=sum(h * w for h, w in outs), norm=depth["norm"])
+                ctx.depth_out(outs)
             probs, _ = ctx.forward_flat(pixels, shapes)
             maps = ctx.dense_read()[0] if dense else None
+            dmaps = ctx.depth_read()[0] if depth else None
         except binding.VitxError as e:
             print(f"main: the packed forward failed: {e}", file=sys.stderr)
             return 1
         for k, (f, (h, w), p) in enumerate(zip(files, shapes, probs)):
             print(f"main: '{f}' at ({w} x {h})", file=sys.stderr)
+            if depth:
+                dm, path = dmaps[k], f"{a.depth_out}.{k}.npy"
+                with open(path, "wb") as fo:
+                    np.save(fo, dm)
+                print(f"main: wrote the {dm.shape[1]} x {dm.shape[0]} depth map to '{path}'", file=sys.stderr)
+                print(f" > depth : min {float(np.nanmin(dm)):.3f} median {float(np.nanmedian(dm)):.3f} max {float(np.nanmax(dm)):.3f}")
+                continue
             if dense:
                 lab, path = maps[k], f"{a.dense_out}.{k}.pgm"
                 with open(path, "wb") as fo:

@@ -4,6 +4,7 @@
 #include <cmath>
 
 #include "context.h"
+#include "depth_bins.h"
 
 namespace vitx {
 
@@ -94,6 +95,26 @@ hipError_t head_depth(const HeadLaunch &l, void *a, const void *Wp, const float 
     return launch_depth_resize(fine, n, u * gh, u * gw, oh, ow, lo, hi, depth, l.st);
 }
 
+hipError_t head_depth_packed(const HeadLaunch &l, void *a, const void *Wp, const float *zero, float *acc, void *ac, const void *Wc, const float *bias, float *o,
+                             const float *bins, int rows, int K, int Dc, const int *row0, const int *ftile0, const int *otile0, const int *seg, int n, int ftiles,
+                             int otiles, int cells, long fine_px, long pixels, float lo, float hi, float *fine, float *depth, float *keep, float *keep_off) {
+    const int Kpad = round_up(K, gemm_tile_n());
+    HEAD_TRY(head_linear(l, PC_DEPTH, a, Wp, zero, acc, rows, K, Dc, keep));
+    if (Wc) {
+        {
+            ProfScope ps(l.prof, l.st, PC_DEPTH, 0, 2.0 * n * Dc * eb);
+            HEAD_TRY(launch_depth_gather(a, Dc, row0, ac, n, l.st));
+        }
+        HEAD_TRY(head_linear(l, PC_DEPTH, ac, Wc, bias, o, n, K, Dc, keep_off));
+    }
+    {
+        ProfScope ps(l.prof, l.st, PC_DEPTH, 11.0 * (double)fine_px * K, (double)rows * Kpad * 4 + (double)fine_px * 4);
+        HEAD_TRY(launch_depth_fine_packed(acc, Kpad, Wc ? o : bias, Wc ? Kpad : 0, bins, ftile0, seg, n, ftiles, cells, K, fine, l.st));
+    }
+    ProfScope ps(l.prof, l.st, PC_DEPTH, 7.0 * (double)pixels, (double)(fine_px + pixels) * 4);
+    return launch_depth_resize_packed(fine, otile0, seg, n, otiles, lo, hi, depth, l.st);
+}
+
 int patch_head_mask(const char *api, int L, int D, int Dc, uint64_t *mask) {
     if (*mask == 0) *mask = 1ull << (L - 1);
     if (L < 64 && (*mask >> L)) { set_error("%s: layer mask selects a layer at or beyond L = %d", api, L); return VITX_ERR_ARG; }
@@ -119,6 +140,27 @@ int dense_head_values(const char *api, const float *W, const float *bias, int K,
     return VITX_OK;
 }
 
+int depth_head_args(const char *api, const float *Wp, const float *bins, int K, int Dc, int flags, int L, int D, uint64_t *mask) {
+    if (!Wp || !bins) { set_error("%s: NULL weights or bins with K = %d", api, K); return VITX_ERR_ARG; }
+    if (K < 1) { set_error("%s: K = %d bins", api, K); return VITX_ERR_ARG; }
+    if (flags & ~(VITX_DEPTH_NORM | VITX_DEPTH_LOGITS | VITX_DEPTH_FINE)) { set_error("%s: unknown flags 0x%x", api, flags); return VITX_ERR_ARG; }
+    return patch_head_mask(api, L, D, Dc, mask);
+}
+
+int depth_head_values(const char *api, const float *Wp, const float *Wc, const float *bias, const float *bins, int K, int Dc, float min_depth, float max_depth, int upsample) {
+    if (!std::isfinite(min_depth) || !std::isfinite(max_depth) || min_depth > max_depth) { set_error("%s: the depth range %g .. %g must be finite and ordered", api, (double)min_depth, (double)max_depth); return VITX_ERR_ARG; }
+    for (const float *W : {Wp, Wc})
+        if (W) for (size_t i = 0, nb = (size_t)K * Dc; i < nb; ++i)
+            if (!std::isfinite(W[i])) { set_error("%s: %s weight [%zu][%zu] is not finite", api, W == Wp ? "patch" : "class", i / Dc, i % Dc); return VITX_ERR_ARG; }
+    for (int k = 0; k < K; ++k) {
+        if (bias && !std::isfinite(bias[k])) { set_error("%s: bias [%d] is not finite", api, k); return VITX_ERR_ARG; }
+        if (!std::isfinite(bins[k]) || !(bins[k] > 0.0f)) { set_error("%s: bin [%d] = %g is not a finite positive depth", api, k, (double)bins[k]); return VITX_ERR_ARG; }
+    }
+    if (K > kDepthMaxK) { set_error("%s: K = %d bins above %d", api, K, kDepthMaxK); return VITX_ERR_UNSUPPORTED; }
+    if (upsample != 1 && upsample != 2 && upsample != 4) { set_error("%s: upsample = %d, not 1, 2 or 4", api, upsample); return VITX_ERR_UNSUPPORTED; }
+    return VITX_OK;
+}
+
 hipError_t upload_operand(int dtype, const DevMem &dst, const float *W, int K, int Kpad, int Dc) {
     const std::vector<uint16_t> hw = operand_matrix_host(dtype, W, nullptr, K, Dc, Kpad, Dc, 0, 0);
     return hipMemcpy(dst.p, hw.data(), hw.size() * 2, hipMemcpyHostToDevice);
@@ -129,6 +171,15 @@ hipError_t dense_head_upload(const DenseHead &dn, int dtype, const float *W, con
     HEAD_TRY(hipMemset(dn.bias.p, 0, (size_t)dn.Kpad * 4));
     if (bias) HEAD_TRY(hipMemcpy(dn.bias.p, bias, (size_t)dn.K * 4, hipMemcpyHostToDevice));
     return hipSuccess;
+}
+
+// the halves go up rounded (RNE) to the operand type; the zero rows beyond K come from operand_matrix_host, the zero biases from the memset
+hipError_t depth_head_upload(const DepthHead &dp, int dtype, const float *Wp, const float *Wc, const float *bias, const float *bins) {
+    HEAD_TRY(upload_operand(dtype, dp.Wp, Wp, dp.K, dp.Kpad, dp.Dc));
+    if (Wc) HEAD_TRY(upload_operand(dtype, dp.Wc, Wc, dp.K, dp.Kpad, dp.Dc));
+    for (const DevMem *m : {&dp.bias, &dp.zero, &dp.bins}) HEAD_TRY(hipMemset(m->p, 0, (size_t)dp.Kpad * 4));
+    if (bias) HEAD_TRY(hipMemcpy(dp.bias.p, bias, (size_t)dp.K * 4, hipMemcpyHostToDevice));
+    return hipMemcpy(dp.bins.p, bins, (size_t)dp.K * 4, hipMemcpyHostToDevice);
 }
 
 }  // namespace vitx

@@ -169,6 +169,19 @@ struct DepthHead : PatchHead {
     std::vector<DevMem> o;       // per slice, class half only: [round_up(slice cap, tm)][Kpad] f32, the offsets
 };
 
+// the depth head of a packed context (vitx_pack_depth_set): the same two linear maps over ALL rows of the pack -- a[0] [round_up(max_tokens, tm)][Dc],
+// acc[0] the same rows x Kpad, the prefix rows computed and never used; with a class half ac[0] [round_up(max_images, tm)][Dc], the class rows gathered
+// from a[0], and o[0] their offsets -- and one fine plane and one depth map per image at its own size, planes and maps end to end
+struct PackDepth : DepthHead {
+    long max_pixels = 0;         // floats of depth; fine: u^2 max_tokens floats; logits: [max_tokens][K], every row of the pack; off: [max_images][K]
+    size_t bytes = 0;            // device bytes of everything above: what the head adds to vitx_pack_scratch_bytes
+    std::vector<int32_t> next_out;       // vitx_pack_depth_out: the output shapes [n][2] of the next forward (empty: the images' own shapes)
+    std::vector<int32_t> grids, outs;    // [n][2] each, of the last call that passed its checks with the head set (PackCall, packed_context.h)
+    std::vector<int64_t> pix0, fine0;    // [n + 1] each, the same
+    std::vector<int32_t> ftile0, otile0; // [n + 1] each, the same
+    int cells = 0;               // the widest fine-tile window of that call
+};
+
 // ---- the launch sequences of the four heads (heads.cpp) --------------------------------------------------------------------------------
 // Each only enqueues on `st`, on the caller's buffers: every pointer is a device pointer, rows are padded to the GEMMs' row tile
 // (gemm_tile_m) and the columns of a head to their column tile (gemm_tile_n) as the struct comments above say.  `prof` != nullptr: every launch
@@ -212,19 +225,35 @@ hipError_t head_depth(const HeadLaunch &l, void *a, const void *Wp, const float 
                       const float *bins, int n, int gh, int gw, int K, int Dc, int u, int oh, int ow, float lo, float hi, float *fine, float *depth,
                       float *keep, float *keep_off);
 
+// The depth head of a pack after its operand rows are written: the patch logits of all `rows` rows of the pack with the zero bias (head_linear; keep:
+// [rows][K]); with a class half the class rows gathered from a by row0 (device, [n]) into ac and their offsets with the head's bias (keep_off: [n][K]);
+// then the packed fine and resize kernels on the device tables ftile0 / otile0 / seg (kernels.h depth_pack_tables, depth_pack_seg; seg's offset rows
+// are 0 .. n - 1).  3 launches, 5 with a class half.
+hipError_t head_depth_packed(const HeadLaunch &l, void *a, const void *Wp, const float *zero, float *acc, void *ac, const void *Wc, const float *bias, float *o,
+                             const float *bins, int rows, int K, int Dc, const int *row0, const int *ftile0, const int *otile0, const int *seg, int n, int ftiles,
+                             int otiles, int cells, long fine_px, long pixels, float lo, float hi, float *fine, float *depth, float *keep, float *keep_off);
+
 // the argument checks vitx_op_depth_fine / vitx_op_depth_resize / vitx_op_depth (ops.cpp) share with vitx_depth_host (depth_host.cpp): none needs a device
 int depth_fine_args(const char *name, const void *logits, long ld, const void *bins, int n, int gh, int gw, int K, int u, const void *fine);
 int depth_resize_args(const char *name, const void *fine, int n, int fh, int fw, int out_h, int out_w, float lo, float hi, const void *out);
 
 // ---- what setting a patch head takes, whichever context it serves (heads.cpp) -----------------------------------------------------------
 // The argument checks need no device and put `api` in front of every refusal.  They come in pieces because each context's and each head's own
-// checks sit between them (outputs.cpp: vitx_dense_set, vitx_depth_set; packed_outputs.cpp: vitx_pack_dense_set).
+// checks sit between them (outputs.cpp: vitx_dense_set, vitx_depth_set; packed_outputs.cpp: vitx_pack_dense_set, vitx_pack_depth_set).
 // patch_head_mask: the layer mask of a head on a model of L layers of width D (0: the last layer), at most 4 layers, Dc = layers x D
 int patch_head_mask(const char *api, int L, int D, int Dc, uint64_t *mask);
 // dense_head_args: the weights are there, K >= 1, known flags, then patch_head_mask
 int dense_head_args(const char *api, const float *W, int K, int Dc, int flags, int L, int D, uint64_t *mask);
 // dense_head_values: W [K][Dc] and bias [K] (or NULL) are finite, K is at most kDenseMaxK
 int dense_head_values(const char *api, const float *W, const float *bias, int K, int Dc);
+// depth_head_args: the weights and bins are there, K >= 1, known flags, then patch_head_mask
+int depth_head_args(const char *api, const float *Wp, const float *bins, int K, int Dc, int flags, int L, int D, uint64_t *mask);
+// depth_head_values: the depth range is finite and ordered, Wp and Wc [K][Dc] and bias [K] (each but Wp or NULL) are finite, the bins finite and positive,
+// K is at most kDepthMaxK, upsample is 1, 2 or 4
+int depth_head_values(const char *api, const float *Wp, const float *Wc, const float *bias, const float *bins, int K, int Dc, float min_depth, float max_depth, int upsample);
+// The parameters of a depth head whose K, Kpad and Dc are set and whose Wp, Wc (with a class half), bias, zero and bins are allocated, onto the device:
+// the halves through upload_operand, bias / zero / bins zero-filled, then `bias` [K] (or NULL) and `bins` [K] copied
+hipError_t depth_head_upload(const DepthHead &dp, int dtype, const float *Wp, const float *Wc, const float *bias, const float *bins);
 // W [K][Dc] f32 -> dst [Kpad][Dc], rounded (RNE) to the operand type, zero rows beyond K
 hipError_t upload_operand(int dtype, const DevMem &dst, const float *W, int K, int Kpad, int Dc);
 // The parameters of a dense head whose K, Kpad and Dc are set, onto the device: W through upload_operand, bias zero-filled, then `bias` [K] (or NULL) copied

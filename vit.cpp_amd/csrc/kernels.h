@@ -259,6 +259,24 @@ bool depth_resize_supports(int n, int fh, int fw, int out_h, int out_w);
 hipError_t launch_depth_fine(const float *logits, long ld, const float *offsets, long ldo, const float *bins, int n, int gh, int gw, int K, int u, float *fine, hipStream_t stream);
 hipError_t launch_depth_resize(const float *fine, int n, int fh, int fw, int out_h, int out_w, float lo, float hi, float *out, hipStream_t stream);
 hipError_t launch_depth_rows(int dtype, const float *x, long ldx, void *y, long ldy, long rows, int D, hipStream_t stream, int group = 1, long gstride = 0);
+// The same tail on a PACK (include/vitx.h "packed batches", the depth head): image i has its own first logit row lrow[i], offsets row orow[i] (row
+// orow[i] * ldo of `offsets`), grid grids[i] = (gh, gw), fine plane (u gh, u gw) and output outs[i] = (oh, ow); its fine plane starts fine0[i] floats
+// into `fine`, its map pix0[i] floats into `out` (planes and maps end to end), bit for bit what launch_depth_fine / launch_depth_resize write for it alone.
+//   depth_pack_tables   host only, the one place the tables are built: pix0 / fine0 [n + 1] = the running pixel counts of the maps and the fine planes,
+//                       ftile0 / otile0 [n + 1] = the running counts of kDepthTile x kDepthTile fine tiles and kDepthOutW x kDepthOutH output tiles, *cells =
+//                       the widest fine-tile window of any image (it sizes the LDS and the bin chunk of the launch); any of the five may be NULL.  false:
+//                       u not 1, 2 or 4, a grid below 1, a fine side above kDepthMaxOut, an output outside fine .. kDepthMaxOut, or more than 2^31 - 1 tiles.
+//   depth_pack_seg      the device table's rows seg [n][kDepthSegInts]: lrow, orow, gh, gw, u gh, u gw, oh, ow, fine0 (low, high word), pix0 (low, high
+//                       word), the bits of dense_scale for the fine plane's y and x and for the map's y and x
+//   launch_depth_*_packed   ftile0 / otile0 and seg on the device; tiles = ftile0[n] / otile0[n] and cells from depth_pack_tables: the caller built the tables
+//   depth_gather        dst[i][0 .. Dc) = src[rows[i]][0 .. Dc), operand-type rows of Dc elements (Dc % 8 == 0), rows [n] on the device
+constexpr int kDepthSegInts = 16;
+bool depth_pack_tables(const int32_t *grids, const int32_t *outs, int n, int u, int64_t *pix0, int64_t *fine0, int32_t *ftile0, int32_t *otile0, int *cells);
+void depth_pack_seg(const int32_t *grids, const int32_t *outs, const int32_t *lrow, const int32_t *orow, const int64_t *fine0, const int64_t *pix0, int n, int u, int32_t *seg);
+hipError_t launch_depth_fine_packed(const float *logits, long ld, const float *offsets, long ldo, const float *bins, const int *ftile0, const int *seg, int n, int tiles,
+                                    int cells, int K, float *fine, hipStream_t stream);
+hipError_t launch_depth_resize_packed(const float *fine, const int *otile0, const int *seg, int n, int tiles, float lo, float hi, float *out, hipStream_t stream);
+hipError_t launch_depth_gather(const void *src, int Dc, const int *rows, void *dst, int n, hipStream_t stream);
 // The text tower (include/vitx.h "the text tower"; text_embed.hip, attention_text.hip).
 //   text_embed: X[i][t][:] (f32) = f32(tok[ids[i * T + t]][:]) + pos[t][:]; tok [V][D] f16 (table_f16) or f32, ids checked by the caller; D % 8 == 0
 //   text_pool:  z[i][:] (dtype) = RNE(final LayerNorm of X row i * T + pooled[i]), LnRow's bits; rows n .. m_pad zeros; every width of VITX_LN_WIDTHS

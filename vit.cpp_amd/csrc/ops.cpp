@@ -6,6 +6,7 @@
 #include "context.h"
 #include "preproc_resample.h"
 #include "dense_resample.h"
+#include "depth_bins.h"
 
 // A launcher's hipError_t -> the entry point's return code, with "<name>: <hip string>" as the error text.  `invalid`: the code that
 // hipErrorInvalidValue (the launchers' "no instantiation for this shape") maps to -- each entry point keeps the mapping it always had
@@ -550,6 +551,87 @@ int vitx_op_depth_resize(const void *d_fine, int n, int fh, int fw, int out_h, i
     if (const int rc = depth_resize_args("vitx_op_depth_resize", d_fine, n, fh, fw, out_h, out_w, min_depth, max_depth, d_out)) return rc;
     if ((uintptr_t)d_fine % 4 || (uintptr_t)d_out % 4) { set_error("vitx_op_depth_resize: d_fine and d_out must be 4-byte aligned"); return VITX_ERR_ARG; }
     return op_rc("vitx_op_depth_resize", launch_depth_resize((const float *)d_fine, n, fh, fw, out_h, out_w, min_depth, max_depth, (float *)d_out, (hipStream_t)stream), VITX_ERR_UNSUPPORTED);
+}
+// The two depth kernels on a pack (include/vitx.h "packed batches"): vitx_op_depth_fine's / vitx_op_depth_resize's checks image by image, the tables
+// built by the one host function (depth_pack_tables) and uploaded in one copy -- ftile0 [n + 1] | otile0 [n + 1] | seg [n][kDepthSegInts] -- then the
+// launch.  Test entry points: they wait for the launch before they free the tables.  Image i's offsets are row orow[i] of d_offsets, rows ld floats apart.
+static int depth_packed_run(const char *name, const int32_t *grids, const int32_t *outs, const int32_t *lrow, const int32_t *orow, int n, int u, hipStream_t st,
+                            hipError_t (*launch)(const int *d_tab, int n, int ftiles, int otiles, int cells, void *arg, hipStream_t st), void *arg) {
+    std::vector<int64_t> pix0((size_t)n + 1), fine0((size_t)n + 1);
+    std::vector<int32_t> tab((size_t)2 * (n + 1) + (size_t)n * kDepthSegInts);
+    int cells = 0;
+    if (!depth_pack_tables(grids, outs, n, u, pix0.data(), fine0.data(), tab.data(), tab.data() + n + 1, &cells)) { set_error("%s: the planes hold more than 2^31 - 1 tiles", name); return VITX_ERR_UNSUPPORTED; }
+    depth_pack_seg(grids, outs, lrow, orow, fine0.data(), pix0.data(), n, u, tab.data() + 2 * (n + 1));
+    int *d_tab = nullptr;
+    HIP_TRY(hipMalloc((void **)&d_tab, tab.size() * 4));
+    const DevMem own(d_tab);
+    HIP_TRY(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
+    const hipError_t e = launch(d_tab, n, tab[n], tab[2 * n + 1], cells, arg, st);
+    const hipError_t es = hipStreamSynchronize(st);      // the tables are freed, and the staging vector goes, when this returns
+    if (e == hipSuccess && es != hipSuccess) return op_rc(name, es);
+    return op_rc(name, e, VITX_ERR_UNSUPPORTED);
+}
+int vitx_op_depth_fine_packed(const void *d_logits, long ld, const void *d_offsets, const void *d_bins, const int32_t *grids, const int32_t *lrow, const int32_t *orow, int n, int K,
+                              int upsample, void *d_fine, void *stream) {
+    const char *name = "vitx_op_depth_fine_packed";
+    if (!grids || !lrow || (d_offsets && !orow) || n < 1) { set_error("%s: invalid argument", name); return VITX_ERR_ARG; }
+    std::vector<int32_t> outs((size_t)2 * n), zero((size_t)n, 0);
+    for (int i = 0; i < n; ++i) {
+        if (const int rc = depth_fine_args(name, d_logits, ld, d_bins, 1, grids[2 * i], grids[2 * i + 1], K, upsample, d_fine)) return rc;
+        if (lrow[i] < 0 || (size_t)lrow[i] + (size_t)grids[2 * i] * grids[2 * i + 1] > 0x7fffffffu) { set_error("%s: image %d: first logit row %d", name, i, lrow[i]); return VITX_ERR_ARG; }
+        if (d_offsets && orow[i] < 0) { set_error("%s: image %d: offsets row %d", name, i, orow[i]); return VITX_ERR_ARG; }
+        outs[2 * i] = upsample * grids[2 * i]; outs[2 * i + 1] = upsample * grids[2 * i + 1];
+    }
+    if ((uintptr_t)d_logits % 16 || (uintptr_t)d_offsets % 16 || (uintptr_t)d_bins % 4 || (uintptr_t)d_fine % 4) { set_error("%s: d_logits and d_offsets must be 16-byte, d_bins and d_fine 4-byte aligned", name); return VITX_ERR_ARG; }
+    struct Arg { const float *lg; long ld; const float *off, *bins; int K; float *fine; } a{(const float *)d_logits, ld, (const float *)d_offsets, (const float *)d_bins, K, (float *)d_fine};
+    return depth_packed_run(name, grids, outs.data(), lrow, d_offsets ? orow : zero.data(), n, upsample, (hipStream_t)stream,
+                            [](const int *t, int n_, int ftiles, int, int cells, void *v, hipStream_t st) {
+                                const Arg &g = *(const Arg *)v;
+                                return launch_depth_fine_packed(g.lg, g.ld, g.off, g.ld, g.bins, t, t + 2 * (n_ + 1), n_, ftiles, cells, g.K, g.fine, st);
+                            }, &a);
+}
+int vitx_op_depth_resize_packed(const void *d_fine, const int32_t *fines, const int32_t *outs, int n, float min_depth, float max_depth, void *d_out, void *stream) {
+    const char *name = "vitx_op_depth_resize_packed";
+    if (!fines || !outs || n < 1) { set_error("%s: invalid argument", name); return VITX_ERR_ARG; }
+    for (int i = 0; i < n; ++i)
+        if (const int rc = depth_resize_args(name, d_fine, 1, fines[2 * i], fines[2 * i + 1], outs[2 * i], outs[2 * i + 1], min_depth, max_depth, d_out)) return rc;
+    if ((uintptr_t)d_fine % 4 || (uintptr_t)d_out % 4) { set_error("%s: d_fine and d_out must be 4-byte aligned", name); return VITX_ERR_ARG; }
+    struct Arg { const float *fine; float lo, hi; float *out; } a{(const float *)d_fine, min_depth, max_depth, (float *)d_out};
+    const std::vector<int32_t> zero((size_t)n, 0);
+    // the fine planes stand in for the grids of the table (u = 1): the resize reads the fine shape, the output shape and the two base offsets
+    return depth_packed_run(name, fines, outs, zero.data(), zero.data(), n, 1, (hipStream_t)stream,
+                            [](const int *t, int n_, int, int otiles, int, void *v, hipStream_t st) {
+                                const Arg &g = *(const Arg *)v;
+                                return launch_depth_resize_packed(g.fine, t + n_ + 1, t + 2 * (n_ + 1), n_, otiles, g.lo, g.hi, g.out, st);
+                            }, &a);
+}
+// The halves of the above for callers that keep the tables (tools/pack_depth_cost.py times the launches alone): the host builder -- tab = ftile0 [n + 1] |
+// otile0 [n + 1] | seg [n][kDepthSegInts], *ftiles = ftile0[n], *otiles = otile0[n], *cells = the widest window -- and the launches on such a table
+// uploaded by the caller.
+int vitx_depth_pack_tables(const int32_t *grids, const int32_t *outs, const int32_t *lrow, const int32_t *orow, int n, int upsample, int32_t *tab, int *ftiles, int *otiles, int *cells) {
+    if (!grids || !outs || !lrow || !orow || !tab || !ftiles || !otiles || !cells || n < 1) { set_error("vitx_depth_pack_tables: invalid argument"); return VITX_ERR_ARG; }
+    std::vector<int64_t> pix0((size_t)n + 1), fine0((size_t)n + 1);
+    if (!depth_pack_tables(grids, outs, n, upsample, pix0.data(), fine0.data(), tab, tab + n + 1, cells)) {
+        set_error("vitx_depth_pack_tables: upsample not 1, 2 or 4, an output outside its fine plane .. %d, or more than 2^31 - 1 tiles", kDepthMaxOut);
+        return VITX_ERR_UNSUPPORTED;
+    }
+    depth_pack_seg(grids, outs, lrow, orow, fine0.data(), pix0.data(), n, upsample, tab + 2 * (n + 1));
+    *ftiles = tab[n]; *otiles = tab[2 * n + 1];
+    return VITX_OK;
+}
+int vitx_op_depth_fine_packed_tables(const void *d_logits, long ld, const void *d_offsets, long ldo, const void *d_bins, const void *d_tab, int n, int tiles, int cells, int K,
+                                     void *d_fine, void *stream) {
+    if (!d_logits || !d_bins || !d_tab || !d_fine || (uintptr_t)d_logits % 16 || (uintptr_t)d_offsets % 16 || (uintptr_t)d_bins % 4 || (uintptr_t)d_fine % 4 || (uintptr_t)d_tab % 4) {
+        set_error("vitx_op_depth_fine_packed_tables: invalid argument");
+        return VITX_ERR_ARG;
+    }
+    return op_rc("vitx_op_depth_fine_packed_tables", launch_depth_fine_packed((const float *)d_logits, ld, (const float *)d_offsets, ldo, (const float *)d_bins, (const int *)d_tab,
+                                                                              (const int *)d_tab + 2 * (n + 1), n, tiles, cells, K, (float *)d_fine, (hipStream_t)stream), VITX_ERR_UNSUPPORTED);
+}
+int vitx_op_depth_resize_packed_tables(const void *d_fine, const void *d_tab, int n, int tiles, float min_depth, float max_depth, void *d_out, void *stream) {
+    if (!d_fine || !d_tab || !d_out || (uintptr_t)d_fine % 4 || (uintptr_t)d_out % 4 || (uintptr_t)d_tab % 4) { set_error("vitx_op_depth_resize_packed_tables: invalid argument"); return VITX_ERR_ARG; }
+    return op_rc("vitx_op_depth_resize_packed_tables", launch_depth_resize_packed((const float *)d_fine, (const int *)d_tab + n + 1, (const int *)d_tab + 2 * (n + 1), n, tiles, min_depth,
+                                                                                  max_depth, (float *)d_out, (hipStream_t)stream), VITX_ERR_UNSUPPORTED);
 }
 // The sequence the forward of a context with a depth head runs after its operand rows are written (head_depth, heads.cpp).  The patch GEMM's zero
 // bias is the row of zeros the call writes behind the logit rows.

@@ -446,21 +446,9 @@ int vitx_depth_set(vitx_ctx *c, const float *Wp, const float *Wc, const float *b
     int oh = out_h, ow = out_w;
     const int fh = upsample * c->gh, fw = upsample * c->gw;
     if (!off) {
-        if (!Wp || !bins) { set_error("vitx_depth_set: NULL weights or bins with K = %d", K); return VITX_ERR_ARG; }
-        if (K < 1) { set_error("vitx_depth_set: K = %d bins", K); return VITX_ERR_ARG; }
-        if (flags & ~(VITX_DEPTH_NORM | VITX_DEPTH_LOGITS | VITX_DEPTH_FINE)) { set_error("vitx_depth_set: unknown flags 0x%x", flags); return VITX_ERR_ARG; }
-        if (const int rc = patch_head_mask("vitx_depth_set", c->L, c->D, Dc, &mask)) return rc;
+        if (const int rc = depth_head_args("vitx_depth_set", Wp, bins, K, Dc, flags, c->L, c->D, &mask)) return rc;
         if (const int rc = patch_head_shape(c, "vitx_depth_set", &oh, &ow)) return rc;
-        if (!std::isfinite(min_depth) || !std::isfinite(max_depth) || min_depth > max_depth) { set_error("vitx_depth_set: the depth range %g .. %g must be finite and ordered", (double)min_depth, (double)max_depth); return VITX_ERR_ARG; }
-        for (const float *W : {Wp, Wc})
-            if (W) for (size_t i = 0, nb = (size_t)K * Dc; i < nb; ++i)
-                if (!std::isfinite(W[i])) { set_error("vitx_depth_set: %s weight [%zu][%zu] is not finite", W == Wp ? "patch" : "class", i / Dc, i % Dc); return VITX_ERR_ARG; }
-        for (int k = 0; k < K; ++k) {
-            if (bias && !std::isfinite(bias[k])) { set_error("vitx_depth_set: bias [%d] is not finite", k); return VITX_ERR_ARG; }
-            if (!std::isfinite(bins[k]) || !(bins[k] > 0.0f)) { set_error("vitx_depth_set: bin [%d] = %g is not a finite positive depth", k, (double)bins[k]); return VITX_ERR_ARG; }
-        }
-        if (K > kDepthMaxK) { set_error("vitx_depth_set: K = %d bins above %d", K, kDepthMaxK); return VITX_ERR_UNSUPPORTED; }
-        if (upsample != 1 && upsample != 2 && upsample != 4) { set_error("vitx_depth_set: upsample = %d, not 1, 2 or 4", upsample); return VITX_ERR_UNSUPPORTED; }
+        if (const int rc = depth_head_values("vitx_depth_set", Wp, Wc, bias, bins, K, Dc, min_depth, max_depth, upsample)) return rc;
         if (c->R != 1) { set_error("vitx_depth_set: the depth head is not available for ViTSTR contexts"); return VITX_ERR_UNSUPPORTED; }
         if (Wc && c->map) { set_error("vitx_depth_set: a class half on a context without a class token (VITX_POOL_MAP)"); return VITX_ERR_UNSUPPORTED; }
         if (oh < fh || ow < fw || oh > kDepthMaxOut || ow > kDepthMaxOut) {
@@ -493,12 +481,7 @@ int vitx_depth_set(vitx_ctx *c, const float *Wp, const float *Wc, const float *b
         }
     }
     if (!ok) { set_error("vitx_depth_set: cannot allocate the buffers for %d bins, %d x %d maps and %d images", K, oh, ow, dp->cap); return VITX_ERR_NOMEM; }
-    // the halves go up rounded (RNE) to the operand type; the zero rows beyond K come from operand_matrix_host, the zero biases from the memset
-    if (e == hipSuccess) e = upload_operand(c->dtype, dp->Wp, Wp, K, dp->Kpad, Dc);
-    if (e == hipSuccess && Wc) e = upload_operand(c->dtype, dp->Wc, Wc, K, dp->Kpad, Dc);
-    for (const DevMem *m : {&dp->bias, &dp->zero, &dp->bins}) if (e == hipSuccess) e = hipMemset(m->p, 0, Kpad * 4);
-    if (e == hipSuccess && bias) e = hipMemcpy(dp->bias.p, bias, (size_t)K * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dp->bins.p, bins, (size_t)K * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = depth_head_upload(*dp, c->dtype, Wp, Wc, bias, bins);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) return hip_failed("vitx_depth_set", e);
     c->depth = std::move(dp);

@@ -124,7 +124,7 @@ int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_im
         return VITX_OK;
     };
     const size_t Mp = (size_t)round_up(max_tokens, p->tm), Bp = (size_t)round_up(max_images, p->tm);
-    p->host.assign(p->layout().ints(false), 0);
+    p->host.assign(p->layout().ints(), 0);
     if ((rc = dmalloc((void **)&p->tab, p->host.size() * 4))) return rc;
     if ((rc = dmalloc((void **)&p->X, Mp * D * 4))) return rc;
     if ((rc = dmalloc(&p->U, Mp * D * 2))) return rc;

@@ -1,7 +1,7 @@
 // packed_context.h -- the packed context (struct vitx_pack); include/vitx.h "packed batches": n images, each with its own h_i x w_i, their
 // tokens end to end in one [sum N_i][D] residual stream, one forward.  Modelled on the text context (text_context.h): its own scratch, one
 // stream, no sub-batches, no graph cache, no LayerNorm fusion.  Three units stand on it, split like the image context's: packed_context.cpp
-// (creation, counters, the table cache), packed_forward.cpp (the checks of a call, the forward), packed_outputs.cpp (features, the dense head).
+// (creation, counters, the table cache), packed_forward.cpp (the checks of a call, the forward), packed_outputs.cpp (features, the dense and the depth head).
 // Internal: callers see the opaque vitx_pack of include/vitx.h.
 #pragma once
 #include <memory>
@@ -11,15 +11,20 @@
 using namespace vitx;
 
 // The segment tables of a call, in ints into vitx_pack::tab / host (cap = max_images): row0 [cap + 1] | qb0 [cap + 1] | toff [cap] and, while a
-// dense head is set, behind them tile0 [cap + 1] | seg [cap][kDenseSegInts] (kernels.h).  One buffer, one upload; a new table goes in here.
+// dense head is set, behind them tile0 [cap + 1] | seg [cap][kDenseSegInts] and, while a depth head is set, behind those ftile0 [cap + 1] |
+// otile0 [cap + 1] | dseg [cap][kDepthSegInts] (kernels.h).  One buffer, one upload; a new table goes in here.
 struct PackLayout {
     size_t cap;
+    bool dense, depth;                   // the heads whose tables the buffer holds
     size_t row0() const { return 0; }
     size_t qb0() const { return row0() + cap + 1; }
     size_t toff() const { return qb0() + cap + 1; }
     size_t tile0() const { return toff() + cap; }
     size_t seg() const { return tile0() + cap + 1; }
-    size_t ints(bool head) const { return head ? seg() + cap * kDenseSegInts : tile0(); }
+    size_t ftile0() const { return dense ? seg() + cap * kDenseSegInts : tile0(); }
+    size_t otile0() const { return ftile0() + cap + 1; }
+    size_t dseg() const { return otile0() + cap + 1; }
+    size_t ints() const { return depth ? dseg() + cap * kDepthSegInts : ftile0(); }
 };
 
 // What the host-only checks of a forward call (packed_forward.cpp check_call) give the forward: made once per call, before its first device call
@@ -30,6 +35,12 @@ struct PackCall {
     std::vector<int64_t> pix0;           // [n + 1], the running pixel count of the outputs
     std::vector<int32_t> tile0;          // [n + 1], the running tile count of the label launch
     int cells = 0;                       // the widest tile window (kernels.h dense_pack_tables)
+    // with a depth head set (kernels.h depth_pack_tables): the grids again, the depth maps' shapes, the running pixel counts of the maps and of the
+    // fine planes, the running tile counts of the fine and the resize launch, the widest fine-tile window
+    std::vector<int32_t> dgrids, douts;
+    std::vector<int64_t> dpix0, dfine0;
+    std::vector<int32_t> ftile0, otile0;
+    int dcells = 0;
 };
 
 // One grid of the table cache: the position table resampled to gh x gw and the grid's place in the rotary arenas
@@ -77,9 +88,10 @@ struct vitx_pack {
     float *feat = nullptr;               // [max_tokens][D] f32 final-norm rows of the last forward (allocated by vitx_pack_feat_enable)
     int feat_n = 0;                      // images of the last forward with features on (0: none)
     std::unique_ptr<PackDense> dense;    // vitx_pack_dense_set (null: off); its device memory is its own
+    std::unique_ptr<PackDepth> depth;    // vitx_pack_depth_set (null: off); its device memory is its own
     int launches = 0, pe_launches = 0;   // kernel launches of the last forward, and how many of them were patch embeddings
     size_t scratch_bytes = 0;            // device bytes of activation scratch and tables held now
-    PackLayout layout() const { return PackLayout{(size_t)max_images}; }
+    PackLayout layout() const { return PackLayout{(size_t)max_images, (bool)dense, (bool)depth}; }
     // image i of the last call that passed its checks: its patch rows, and where they start in an output that holds every image's patch rows end to end
     size_t patch_rows(int i) const { return (size_t)(row0[i + 1] - row0[i] - Tp); }
     size_t patch_at(int i) const { return (size_t)(row0[i] - i * Tp); }

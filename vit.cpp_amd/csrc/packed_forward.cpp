@@ -2,11 +2,12 @@
 // the forward.  The blocks are the image forward's row-wise launches through the same dispatchers (GEMMs, LayerNorm, activation, gate, pre-norm
 // do not care where one image ends); new are the three launches that must know: the variable-length attention (attention_packed.hip), the
 // rotary embeddings by a segment table (rope.hip) and the class-row gather (text_embed.hip).  The patch embedding is the rectangular context's
-// kernel, one launch per run of consecutive images of one shape.  The one opt-in head is the dense head (packed_outputs.cpp): the stand-alone
-// LayerNorm and the head GEMM over all rows of the pack, then the label launch by its own segment table (dense_label.hip), one map per image
-// at its own size.  No LayerNorm fusion, no class-token tail.
+// kernel, one launch per run of consecutive images of one shape.  The opt-in heads are the dense and the depth head (packed_outputs.cpp): the operand rows
+// and the head GEMM over all rows of the pack, then the label launch (dense_label.hip) or the fine and resize launches (depth_map.hip) by their own
+// segment tables, one map per image at its own size.  No LayerNorm fusion, no class-token tail.
 #include <algorithm>
 
+#include "depth_bins.h"
 #include "packed_context.h"
 
 namespace {
@@ -53,6 +54,38 @@ int check_dense(const char *api, const vitx_model *m, const int32_t *shapes, con
     return VITX_OK;
 }
 
+// The same for a depth head of K bins, upsampling u and max_pixels (vitx_pack_depth_check's text): the output shapes against the fine planes and the
+// buffers.  On success the head's tables of the call: c->dgrids, douts, dpix0, dfine0, ftile0, otile0, dcells.
+int check_depth(const char *api, const vitx_model *m, const int32_t *shapes, const int32_t *out_shapes, int n_out, int n, int K, int u, long max_pixels, PackCall *c) {
+    if (K < 1) { set_error("%s: K = %d bins", api, K); return VITX_ERR_ARG; }
+    if (K > kDepthMaxK) { set_error("%s: K = %d bins above %d", api, K, kDepthMaxK); return VITX_ERR_UNSUPPORTED; }
+    if (u != 1 && u != 2 && u != 4) { set_error("%s: upsample = %d, not 1, 2 or 4", api, u); return VITX_ERR_UNSUPPORTED; }
+    if (max_pixels < 1) { set_error("%s: max_pixels = %ld", api, max_pixels); return VITX_ERR_ARG; }
+    if (out_shapes && n_out != n) { set_error("%s: output shapes were given for %d images, the call has %d", api, n_out, n); return VITX_ERR_ARG; }
+    const int P = m->hp.patch_size;
+    c->dgrids.resize((size_t)2 * n); c->douts.resize((size_t)2 * n);
+    c->dpix0.resize((size_t)n + 1); c->dfine0.resize((size_t)n + 1); c->ftile0.resize((size_t)n + 1); c->otile0.resize((size_t)n + 1);
+    for (int i = 0; i < n; ++i) {
+        const int gh = shapes[2 * i] / P, gw = shapes[2 * i + 1] / P;
+        const int oh = out_shapes ? out_shapes[2 * i] : shapes[2 * i], ow = out_shapes ? out_shapes[2 * i + 1] : shapes[2 * i + 1];
+        if ((long)u * gh > kDepthMaxOut || (long)u * gw > kDepthMaxOut) {
+            set_error("%s: image %d: fine plane %ld x %ld above %d", api, i, (long)u * gh, (long)u * gw, kDepthMaxOut);
+            return VITX_ERR_UNSUPPORTED;
+        }
+        if (oh < u * gh || ow < u * gw || oh > kDepthMaxOut || ow > kDepthMaxOut) {
+            set_error("%s: image %d: output %d x %d outside the fine plane %d x %d .. %d (upsampling only)", api, i, oh, ow, u * gh, u * gw, kDepthMaxOut);
+            return VITX_ERR_ARG;
+        }
+        c->dgrids[2 * i] = gh; c->dgrids[2 * i + 1] = gw; c->douts[2 * i] = oh; c->douts[2 * i + 1] = ow;
+    }
+    if (!depth_pack_tables(c->dgrids.data(), c->douts.data(), n, u, c->dpix0.data(), c->dfine0.data(), c->ftile0.data(), c->otile0.data(), &c->dcells)) {
+        set_error("%s: the call's outputs hold more than 2^31 - 1 tiles", api);
+        return VITX_ERR_ARG;
+    }
+    if (c->dpix0[n] > (int64_t)max_pixels) { set_error("%s: the call's outputs hold %lld pixels, above max_pixels = %ld", api, (long long)c->dpix0[n], max_pixels); return VITX_ERR_ARG; }
+    return VITX_OK;
+}
+
 // the distinct grids of a call, in order of first appearance, as (gh << 32 | gw)
 std::vector<uint64_t> distinct_grids(const int32_t *shapes, int n, int P) {
     std::vector<uint64_t> g;
@@ -64,18 +97,21 @@ std::vector<uint64_t> distinct_grids(const int32_t *shapes, int n, int P) {
 }
 
 // THE check of a forward call, for both entry points: everything the call can be refused for, before its first device call.  It consumes
-// vitx_pack_dense_out's shapes, passed or refused, and touches nothing else of the context: a refused call leaves row0 and the head's tables of the last
+// vitx_pack_dense_out's and vitx_pack_depth_out's shapes, passed or refused, and touches nothing else of the context: a refused call leaves row0 and the head's tables of the last
 // forward that ran (vitx_pack_feat_read, vitx_pack_dense_read) alone.
 int check_call(vitx_pack *p, const int32_t *shapes, int n, PackCall *c) {
     int rc;
     PackDense *dn = p->dense.get();
-    std::vector<int32_t> next_out;
+    PackDepth *dp = p->depth.get();
+    std::vector<int32_t> next_out, next_depth;
     if (dn) next_out.swap(dn->next_out);
+    if (dp) next_depth.swap(dp->next_out);
     c->row0.resize((size_t)p->max_images + 1);
     if ((rc = check_shapes("vitx_pack_forward", p->model, shapes, n, p->max_tokens, p->max_images, c->row0.data()))) return rc;
     c->want = distinct_grids(shapes, n, p->P);
     if (c->want.size() > (size_t)p->max_grids) { set_error("vitx_pack_forward: the call names %d distinct grids, the table cache holds max_grids = %d", (int)c->want.size(), p->max_grids); return VITX_ERR_ARG; }
-    if (dn) rc = check_dense("vitx_pack_forward", p->model, shapes, next_out.empty() ? nullptr : next_out.data(), (int)(next_out.size() / 2), n, dn->K, dn->max_pixels, c);
+    if (dn && (rc = check_dense("vitx_pack_forward", p->model, shapes, next_out.empty() ? nullptr : next_out.data(), (int)(next_out.size() / 2), n, dn->K, dn->max_pixels, c))) return rc;
+    if (dp) rc = check_depth("vitx_pack_forward", p->model, shapes, next_depth.empty() ? nullptr : next_depth.data(), (int)(next_depth.size() / 2), n, dp->K, dp->u, dp->max_pixels, c);
     return rc;
 }
 
@@ -90,9 +126,14 @@ int pack_gemm(vitx_pack *p, int epi, const GemmArgs &a, hipStream_t st) {
 int pack_forward(vitx_pack *p, PackCall &c, const float *d_imgs, const int32_t *shapes, int n, float *d_probs, float *d_logits, hipStream_t st) {
     int rc;
     PackDense *dn = p->dense.get();
+    PackDepth *dp = p->depth.get();
     HIP_TRY(hipSetDevice(p->device));
     p->row0.swap(c.row0); p->feat_n = 0;
     if (dn) { dn->grids.swap(c.grids); dn->outs.swap(c.outs); dn->pix0.swap(c.pix0); dn->tile0.swap(c.tile0); dn->cells = c.cells; dn->n = 0; }
+    if (dp) {
+        dp->grids.swap(c.dgrids); dp->outs.swap(c.douts); dp->pix0.swap(c.dpix0); dp->fine0.swap(c.dfine0); dp->ftile0.swap(c.ftile0); dp->otile0.swap(c.otile0);
+        dp->cells = c.dcells; dp->n = 0;
+    }
     p->launches = p->pe_launches = 0;
     if ((rc = resolve_grids(p, c.want, st))) return rc;
     const WeightSet &ws = *p->wset;
@@ -115,6 +156,14 @@ int pack_forward(vitx_pack *p, PackCall &c, const float *d_imgs, const int32_t *
         for (int i = 0; i < n; ++i) lrow[i] = p->row0[i] + Tp;
         std::copy(dn->tile0.begin(), dn->tile0.end(), p->host.data() + at.tile0());
         dense_pack_seg(dn->grids.data(), dn->outs.data(), lrow.data(), dn->pix0.data(), n, p->host.data() + at.seg());
+    }
+    // the depth head's: the same logit rows; image i's offsets are row i of the offsets (or, without a class half, the bias for every image)
+    if (dp) {
+        std::vector<int32_t> lrow(n), orow(n);
+        for (int i = 0; i < n; ++i) { lrow[i] = p->row0[i] + Tp; orow[i] = i; }
+        std::copy(dp->ftile0.begin(), dp->ftile0.end(), p->host.data() + at.ftile0());
+        std::copy(dp->otile0.begin(), dp->otile0.end(), p->host.data() + at.otile0());
+        depth_pack_seg(dp->grids.data(), dp->outs.data(), lrow.data(), orow.data(), dp->fine0.data(), dp->pix0.data(), n, dp->u, p->host.data() + at.dseg());
     }
     HIP_TRY(hipMemcpyAsync(p->tab, p->host.data(), p->host.size() * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(p->uploaded, st));
@@ -155,6 +204,14 @@ int pack_forward(vitx_pack *p, PackCall &c, const float *d_imgs, const int32_t *
             HIP_TRY(launch_layernorm(dt, p->X, D, ws.norm_w, ws.norm_b, dn->a[0].as<char>() + dn->col(il, D) * 2, dn->Dc, rows, D, p->eps, st));
             ++p->launches;
         }
+        // the depth head's operand: the same rows raw, through the streaming conversion, or (VITX_DEPTH_NORM) through the final norm; the class rows
+        // of a class half are gathered from them after the forward
+        if (dp && dp->selects(il)) {
+            void *y = dp->a[0].as<char>() + dp->col(il, D) * 2;
+            if (dp->flags & VITX_DEPTH_NORM) HIP_TRY(launch_layernorm(dt, p->X, D, ws.norm_w, ws.norm_b, y, dp->Dc, rows, D, p->eps, st));
+            else HIP_TRY(launch_depth_rows(dt, p->X, D, y, dp->Dc, rows, D, st));
+            ++p->launches;
+        }
     }
     // the class rows through the final norm (row0[i] is image i's class row), the head GEMM in f32, the class softmax
     HIP_TRY(launch_pool_rows(dt, p->X, d_row0, ws.norm_w, ws.norm_b, p->Z, n, Mh, D, p->eps, st)); ++p->launches;
@@ -173,6 +230,19 @@ int pack_forward(vitx_pack *p, PackCall &c, const float *d_imgs, const int32_t *
         if (e != hipSuccess) { set_error("vitx_pack_forward: the dense head: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
         p->launches += 2;
         dn->n = n;
+    }
+    // the depth head: the logits of every row of the pack, with a class half the gathered class rows and their offsets, then the fine planes and the
+    // maps over the images' own shapes (3 launches, 5 with a class half)
+    if (dp) {
+        const bool cls = (bool)dp->Wc;
+        const hipError_t e = head_depth_packed(HeadLaunch{*p->tune, dt, st, nullptr}, dp->a[0].p, dp->Wp.p, dp->zero.as<float>(), dp->acc[0].as<float>(), cls ? dp->ac[0].p : nullptr,
+                                               dp->Wc.p, dp->bias.as<float>(), cls ? dp->o[0].as<float>() : nullptr, dp->bins.as<float>(), rows, dp->K, dp->Dc, d_row0,
+                                               p->tab + at.ftile0(), p->tab + at.otile0(), p->tab + at.dseg(), n, dp->ftile0[n], dp->otile0[n], dp->cells, (long)dp->fine0[n],
+                                               (long)dp->pix0[n], dp->lo, dp->hi, dp->fine.as<float>(), dp->depth.as<float>(), dp->logits ? dp->logits.as<float>() : nullptr,
+                                               dp->off ? dp->off.as<float>() : nullptr);
+        if (e != hipSuccess) { set_error("vitx_pack_forward: the depth head: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
+        p->launches += cls ? 5 : 3;
+        dp->n = n;
     }
     HIP_TRY(hipEventRecord(p->done, st));
     p->done_pending = true;
@@ -197,6 +267,18 @@ int vitx_pack_dense_check(const vitx_model *m, const int32_t *shapes, const int3
     if (const int rc = check_dense("vitx_pack_dense_check", m, shapes, out_shapes, n, n, K, max_pixels, &c)) return rc;
     if (pix0) std::copy(c.pix0.begin(), c.pix0.end(), pix0);
     if (tile0) std::copy(c.tile0.begin(), c.tile0.end(), tile0);
+    return VITX_OK;
+}
+
+int vitx_pack_depth_check(const vitx_model *m, const int32_t *shapes, const int32_t *out_shapes, int n, int K, int upsample, long max_pixels, int64_t *pix0, int64_t *fine0,
+                          int32_t *ftile0, int32_t *otile0) {
+    if (const int rc = check_shapes("vitx_pack_depth_check", m, shapes, n, 0x7fffffff, n, nullptr)) return rc;
+    PackCall c;
+    if (const int rc = check_depth("vitx_pack_depth_check", m, shapes, out_shapes, n, n, K, upsample, max_pixels, &c)) return rc;
+    if (pix0) std::copy(c.dpix0.begin(), c.dpix0.end(), pix0);
+    if (fine0) std::copy(c.dfine0.begin(), c.dfine0.end(), fine0);
+    if (ftile0) std::copy(c.ftile0.begin(), c.ftile0.end(), ftile0);
+    if (otile0) std::copy(c.otile0.begin(), c.otile0.end(), otile0);
     return VITX_OK;
 }
 

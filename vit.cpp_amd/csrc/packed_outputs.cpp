@@ -1,9 +1,33 @@
 // packed_outputs.cpp -- what a packed context gives besides probabilities (packed_context.h; include/vitx.h "packed batches"): the last layer's
-// features and the dense head.  Both opt-in; the forward (packed_forward.cpp) launches nothing for an output that is off.  The dense head's own
-// argument checks and its upload are the image context's (heads.h: dense_head_args, dense_head_values, dense_head_upload).
+// features, the dense head and the depth head.  All opt-in; the forward (packed_forward.cpp) launches nothing for an output that is off.  The heads' own
+// argument checks and their uploads are the image context's (heads.h: dense_head_args, dense_head_values, dense_head_upload and depth_head_*).
 #include <algorithm>
 
 #include "packed_context.h"
+
+namespace {
+
+// nothing of this context is in flight while buffers and tables change hands
+int pack_quiesce(vitx_pack *p) {
+    if (p->uploaded_pending) { HIP_TRY(hipEventSynchronize(p->uploaded)); p->uploaded_pending = false; }
+    return wait_done(p);
+}
+
+// the segment tables with the parts of the heads that will be set behind them (PackLayout): a fresh zeroed buffer in place of the old one
+int resize_tables(vitx_pack *p, const char *api, bool dense, bool depth) {
+    const size_t ints = PackLayout{(size_t)p->max_images, dense, depth}.ints();
+    if (p->host.size() == ints) return VITX_OK;
+    int *t = nullptr;
+    HIP_TRY(hipMalloc((void **)&t, ints * 4));
+    if (const hipError_t e = hipMemset(t, 0, ints * 4); e != hipSuccess) { (void)hipFree(t); set_error("%s: %s", api, hipGetErrorString(e)); return VITX_ERR_HIP; }
+    std::replace(p->allocs.begin(), p->allocs.end(), (void *)p->tab, (void *)t);
+    (void)hipFree(p->tab);
+    p->scratch_bytes += ints * 4; p->scratch_bytes -= p->host.size() * 4;
+    p->tab = t; p->host.assign(ints, 0);
+    return VITX_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -53,25 +77,10 @@ int vitx_pack_dense_set(vitx_pack *p, const float *W, const float *bias, int K, 
         }
     }
     HIP_TRY(hipSetDevice(p->device));
-    // nothing of this context is in flight while buffers and tables change hands
-    if (p->uploaded_pending) { HIP_TRY(hipEventSynchronize(p->uploaded)); p->uploaded_pending = false; }
-    if (const int rc = wait_done(p)) return rc;
-    // the segment tables with or without the head's part behind them (PackLayout): a fresh zeroed buffer in place of the old one
-    auto resize_tables = [&](bool head) -> int {
-        const size_t ints = p->layout().ints(head);
-        if (p->host.size() == ints) return VITX_OK;
-        int *t = nullptr;
-        HIP_TRY(hipMalloc((void **)&t, ints * 4));
-        if (const hipError_t e = hipMemset(t, 0, ints * 4); e != hipSuccess) { (void)hipFree(t); set_error("vitx_pack_dense_set: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
-        std::replace(p->allocs.begin(), p->allocs.end(), (void *)p->tab, (void *)t);
-        (void)hipFree(p->tab);
-        p->scratch_bytes += ints * 4; p->scratch_bytes -= p->host.size() * 4;
-        p->tab = t; p->host.assign(ints, 0);
-        return VITX_OK;
-    };
+    if (const int rc = pack_quiesce(p)) return rc;
     if (off) {
         if (p->dense) { p->scratch_bytes -= p->dense->bytes; p->dense.reset(); }
-        return resize_tables(false);
+        return resize_tables(p, "vitx_pack_dense_set", false, (bool)p->depth);
     }
     auto dn = std::make_unique<PackDense>();
     dn->K = K; dn->Kpad = (int)Kpad; dn->Dc = Dc; dn->mask = mask; dn->flags = flags; dn->cap = p->max_images; dn->max_pixels = max_pixels;
@@ -86,7 +95,7 @@ int vitx_pack_dense_set(vitx_pack *p, const float *W, const float *bias, int K, 
     HIP_TRY(dense_head_upload(*dn, p->dtype, W, bias));
     HIP_TRY(hipMemset(dn->a[0].p, 0, Mp * Dc * 2));
     HIP_TRY(hipDeviceSynchronize());
-    if (const int rc = resize_tables(true)) return rc;
+    if (const int rc = resize_tables(p, "vitx_pack_dense_set", true, (bool)p->depth)) return rc;
     if (p->dense) p->scratch_bytes -= p->dense->bytes;
     p->scratch_bytes += dn->bytes;
     p->dense = std::move(dn);
@@ -119,6 +128,96 @@ int vitx_pack_dense_read(vitx_pack *p, uint8_t *labels, float *score, float *log
     if (score) HIP_TRY(hipMemcpy(score, dn->score.p, px * 4, hipMemcpyDeviceToHost));
     if (logits) for (int i = 0; i < n; ++i)
         HIP_TRY(hipMemcpy(logits + p->patch_at(i) * dn->K, dn->logits.as<float>() + (size_t)(p->row0[i] + p->Tp) * dn->K, p->patch_rows(i) * dn->K * 4, hipMemcpyDeviceToHost));
+    return VITX_OK;
+}
+
+// The depth head of a packed context (include/vitx.h "packed batches").  Every argument check comes before the first device call -- the head's own
+// are the image context's (heads.h: depth_head_args, depth_head_values) --; the head is built in a local and moved in, so a refused or failed set
+// leaves the head that was set.
+int vitx_pack_depth_set(vitx_pack *p, const float *Wp, const float *Wc, const float *bias, const float *bins, int K, int Dc, uint64_t layer_mask, int upsample,
+                        float min_depth, float max_depth, long max_pixels, int flags) {
+    if (!p) { set_error("vitx_pack_depth_set: NULL context"); return VITX_ERR_ARG; }
+    const bool off = !Wp && K == 0;
+    uint64_t mask = layer_mask;
+    const size_t Mp = (size_t)round_up(p->max_tokens, p->tm), Bp = (size_t)round_up(p->max_images, p->tm), Kpad = K > 0 ? (size_t)round_up(K, p->tn) : 0;
+    if (!off) {
+        if (const int rc = depth_head_args("vitx_pack_depth_set", Wp, bins, K, Dc, flags, p->L, p->D, &mask)) return rc;
+        if (max_pixels < 1) { set_error("vitx_pack_depth_set: max_pixels = %ld", max_pixels); return VITX_ERR_ARG; }
+        if (const int rc = depth_head_values("vitx_pack_depth_set", Wp, Wc, bias, bins, K, Dc, min_depth, max_depth, upsample)) return rc;
+        if (Mp * Dc * 2 > 0xf0000000u || Mp * Kpad * 4 > 0xf0000000u) {
+            set_error("vitx_pack_depth_set: the operand or logit rows of max_tokens = %d rows leave the GEMM's 32-bit byte window", p->max_tokens);
+            return VITX_ERR_UNSUPPORTED;
+        }
+    }
+    HIP_TRY(hipSetDevice(p->device));
+    if (const int rc = pack_quiesce(p)) return rc;
+    if (off) {
+        if (p->depth) { p->scratch_bytes -= p->depth->bytes; p->depth.reset(); }
+        return resize_tables(p, "vitx_pack_depth_set", (bool)p->dense, false);
+    }
+    auto dp = std::make_unique<PackDepth>();
+    dp->K = K; dp->Kpad = (int)Kpad; dp->Dc = Dc; dp->mask = mask; dp->flags = flags; dp->cap = p->max_images; dp->max_pixels = max_pixels;
+    dp->u = upsample; dp->lo = min_depth; dp->hi = max_depth;
+    dp->bias_host.assign(K, 0.0f);
+    if (bias) std::copy(bias, bias + K, dp->bias_host.begin());
+    dp->a.resize(1); dp->acc.resize(1);
+    const size_t fine_floats = (size_t)upsample * upsample * p->max_tokens;
+    dp->scratch = Mp * Dc * 2 + Mp * Kpad * 4;
+    dp->bytes = (Wc ? 2 : 1) * Kpad * Dc * 2 + 3 * Kpad * 4 + (size_t)max_pixels * 4 + fine_floats * 4;
+    bool ok = dp->Wp.alloc(Kpad * Dc * 2) && (!Wc || dp->Wc.alloc(Kpad * Dc * 2)) && dp->bias.alloc(Kpad * 4) && dp->zero.alloc(Kpad * 4) && dp->bins.alloc(Kpad * 4) &&
+              dp->a[0].alloc(Mp * Dc * 2) && dp->acc[0].alloc(Mp * Kpad * 4) && dp->depth.alloc((size_t)max_pixels * 4) && dp->fine.alloc(fine_floats * 4);
+    if (ok && Wc) {
+        dp->ac.resize(1); dp->o.resize(1);
+        ok = dp->ac[0].alloc(Bp * Dc * 2) && dp->o[0].alloc(Bp * Kpad * 4);
+        dp->scratch += Bp * Dc * 2 + Bp * Kpad * 4;
+    }
+    dp->bytes += dp->scratch;
+    if (ok && (flags & VITX_DEPTH_LOGITS)) {
+        ok = dp->logits.alloc((size_t)p->max_tokens * K * 4) && (!Wc || dp->off.alloc((size_t)p->max_images * K * 4));
+        dp->bytes += (size_t)p->max_tokens * K * 4 + (Wc ? (size_t)p->max_images * K * 4 : 0);
+    }
+    if (!ok) { set_error("vitx_pack_depth_set: cannot allocate the buffers for %d bins, %ld pixels and %d token rows", K, max_pixels, p->max_tokens); return VITX_ERR_NOMEM; }
+    // the head goes up as in an image context; the operand rows start as zeros (a forward writes its rows and zeroes the pad rows behind them)
+    HIP_TRY(depth_head_upload(*dp, p->dtype, Wp, Wc, bias, bins));
+    HIP_TRY(hipMemset(dp->a[0].p, 0, Mp * Dc * 2));
+    if (Wc) HIP_TRY(hipMemset(dp->ac[0].p, 0, Bp * Dc * 2));
+    HIP_TRY(hipDeviceSynchronize());
+    if (const int rc = resize_tables(p, "vitx_pack_depth_set", (bool)p->dense, true)) return rc;
+    if (p->depth) p->scratch_bytes -= p->depth->bytes;
+    p->scratch_bytes += dp->bytes;
+    p->depth = std::move(dp);
+    return VITX_OK;
+}
+
+int vitx_pack_depth_out(vitx_pack *p, const int32_t *out_shapes, int n) {
+    if (!p || !p->depth) { set_error("vitx_pack_depth_out: no depth head is set"); return VITX_ERR_ARG; }
+    if (!out_shapes || n == 0) { p->depth->next_out.clear(); return VITX_OK; }
+    if (n < 1 || n > p->max_images) { set_error("vitx_pack_depth_out: n = %d is outside 1 .. max_images = %d", n, p->max_images); return VITX_ERR_ARG; }
+    p->depth->next_out.assign(out_shapes, out_shapes + (size_t)2 * n);
+    return VITX_OK;
+}
+
+const void *vitx_pack_depth_device(const vitx_pack *p) { return p && p->depth ? p->depth->depth.p : nullptr; }
+size_t vitx_pack_depth_scratch_bytes(const vitx_pack *p) { return p && p->depth ? p->depth->scratch : 0; }
+
+// The last forward's maps and fine planes, the images end to end, the kept logits of its patch rows (behind each image's prefix rows in the pack's
+// rows) and the kept offsets, one row per image
+int vitx_pack_depth_read(vitx_pack *p, float *depth, float *fine, float *logits, float *offsets) {
+    if (!p || !depth) { set_error("vitx_pack_depth_read: NULL argument"); return VITX_ERR_ARG; }
+    const PackDepth *dp = p->depth.get();
+    const int n = dp ? dp->n : 0;
+    if (n == 0) { set_error("vitx_pack_depth_read: no forward has run with a depth head set since vitx_pack_depth_set"); return VITX_ERR_ARG; }
+    if (fine && !(dp->flags & VITX_DEPTH_FINE)) { set_error("vitx_pack_depth_read: the head was set without VITX_DEPTH_FINE"); return VITX_ERR_ARG; }
+    if ((logits || offsets) && !dp->logits) { set_error("vitx_pack_depth_read: the head was set without VITX_DEPTH_LOGITS"); return VITX_ERR_ARG; }
+    const int K = dp->K;
+    HIP_TRY(hipSetDevice(p->device));
+    if (p->done_pending) HIP_TRY(hipEventSynchronize(p->done));
+    HIP_TRY(hipMemcpy(depth, dp->depth.p, (size_t)dp->pix0[n] * 4, hipMemcpyDeviceToHost));
+    if (fine) HIP_TRY(hipMemcpy(fine, dp->fine.p, (size_t)dp->fine0[n] * 4, hipMemcpyDeviceToHost));
+    if (logits) for (int i = 0; i < n; ++i)
+        HIP_TRY(hipMemcpy(logits + p->patch_at(i) * K, dp->logits.as<float>() + (size_t)(p->row0[i] + p->Tp) * K, p->patch_rows(i) * K * 4, hipMemcpyDeviceToHost));
+    if (offsets && dp->off) HIP_TRY(hipMemcpy(offsets, dp->off.p, (size_t)n * K * 4, hipMemcpyDeviceToHost));
+    if (offsets && !dp->off) for (int i = 0; i < n; ++i) std::copy(dp->bias_host.begin(), dp->bias_host.end(), offsets + (size_t)i * K);
     return VITX_OK;
 }
 
