@@ -1139,6 +1139,11 @@ int vitx_op_attention_generic(int dtype, const void *d_qkv, void *d_out, int n_i
  * `rope`, its rotary table (vitx_model_rope_table, uploaded) are built the first time a call names the grid -- that call allocates -- and
  * cached; beyond max_grids the least recently used grid the current call does not name is dropped.  A table is freed or overwritten only
  * after the context's previous forward has finished (an event the call waits for on the host: such a call does not merely enqueue).
+ * That wait is the only one: the call that builds a table allocates it (or takes over a dropped one), resamples on `stream` and uploads the
+ * rotary table with an asynchronous copy from pinned memory on `stream`; the call that drops a table does not free it -- freeing device
+ * memory waits for everything enqueued on the device, the caller's own stream included -- but keeps it for the next grid it can hold (up to
+ * 2 max_grids such tables, the oldest is freed beyond that; vitx_pack_scratch_bytes counts the tables of cached grids only).  With the
+ * caller's stream stalled in front of it, each kind of call returns while the stall runs (tests/test_gpu_stream_order.py).
  *
  * vitx_pack_forward: imgs = the images' f32 HWC pixels end to end (image i: h_i * w_i * 3 floats), shapes host int32 [n][2] = h, w; probs and
  * logits host [n][C].  vitx_pack_forward_device: the same on device pointers; shapes stay a HOST pointer, free when the call returns; only

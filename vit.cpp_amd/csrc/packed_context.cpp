@@ -16,10 +16,35 @@ int wait_done(vitx_pack *p) {
     return VITX_OK;
 }
 
+// The caller has waited for the last forward (wait_done): nothing reads the table any more.  It is not freed -- hipFree waits for everything
+// enqueued on the device, the caller's own stream included -- but retired for the next grid it can hold; only beyond 2 max_grids retired
+// tables is the oldest really freed.  scratch_bytes counts the tables of cached grids, not the retired ones.
 static void drop_grid(vitx_pack *p, size_t k) {
     PackGrid &g = p->grids[k];
-    if (g.own) { (void)hipFree(g.pos); p->scratch_bytes -= ((size_t)g.gh * g.gw + 1) * p->D * 4; }
+    if (g.own) {
+        p->retired.push_back(vitx_pack::Retired{g.pos, g.pos_bytes});
+        p->scratch_bytes -= ((size_t)g.gh * g.gw + 1) * p->D * 4;
+        if (p->retired.size() > 2 * (size_t)p->max_grids) { (void)hipFree(p->retired.front().pos); p->retired.erase(p->retired.begin()); }
+    }
     p->grids.erase(p->grids.begin() + k);
+}
+// An own position table of at least `bytes`: the smallest retired one that holds it, else a new allocation
+static hipError_t take_table(vitx_pack *p, size_t bytes, float **pos, size_t *cap) {
+    size_t best = p->retired.size();
+    for (size_t k = 0; k < p->retired.size(); ++k)
+        if (p->retired[k].bytes >= bytes && (best == p->retired.size() || p->retired[k].bytes < p->retired[best].bytes)) best = k;
+    if (best < p->retired.size()) {
+        *pos = p->retired[best].pos; *cap = p->retired[best].bytes;
+        p->retired.erase(p->retired.begin() + best);
+        return hipSuccess;
+    }
+    *cap = bytes;
+    return hipMalloc((void **)pos, bytes);
+}
+static void give_back(vitx_pack *p, PackGrid &g) {
+    if (!g.own) return;
+    p->retired.push_back(vitx_pack::Retired{g.pos, g.pos_bytes});
+    p->scratch_bytes -= ((size_t)g.gh * g.gw + 1) * p->D * 4;
 }
 
 // The tables of every grid the call names, built the first time a call names them: the position table by launch_pos_resample on the call's
@@ -57,21 +82,22 @@ int resolve_grids(vitx_pack *p, const std::vector<uint64_t> &want, hipStream_t s
         if (gh == p->g_in && gw == p->g_in) g.pos = p->wset->pos;        // the file's own grid: the file's table, as in a context of the file's size
         else {
             const size_t bytes = ((size_t)gh * gw + 1) * p->D * 4;
-            HIP_TRY(hipMalloc((void **)&g.pos, bytes));
+            HIP_TRY(take_table(p, bytes, &g.pos, &g.pos_bytes));
             g.own = true; p->scratch_bytes += bytes;
             const hipError_t e = launch_pos_resample(p->wset->pos, p->g_in, p->g_in, p->D, gh, gw, p->pos_interp, g.pos, st);
-            if (e != hipSuccess) { (void)hipFree(g.pos); p->scratch_bytes -= bytes; set_error("vitx_pack_forward: launch_pos_resample: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
+            if (e != hipSuccess) { give_back(p, g); set_error("vitx_pack_forward: launch_pos_resample: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
             ++p->launches;
         }
         if (p->rope) {
             const size_t tab = (size_t)gh * gw * half;
-            std::vector<float> h(2 * tab);
-            rc = vitx_model_rope_table(p->model, gh, gw, h.data(), h.data() + tab);
-            // a fresh piece of the arenas: nothing reads it yet, so the (synchronous) upload needs no ordering
-            hipError_t e = rc ? hipSuccess : hipMemcpy(p->rope_cos + p->rope_top, h.data(), tab * 4, hipMemcpyHostToDevice);
-            if (!rc && e == hipSuccess) e = hipMemcpy(p->rope_sin + p->rope_top, h.data() + tab, tab * 4, hipMemcpyHostToDevice);
+            // a fresh piece of the arenas: nothing reads it yet.  The table is computed into the same piece of the pinned mirror and uploaded on the
+            // call's stream, in front of the launches that read it; the host does not wait
+            float *hc = p->rope_host + p->rope_top, *hs = p->rope_host + p->rope_cap + p->rope_top;
+            rc = vitx_model_rope_table(p->model, gh, gw, hc, hs);
+            hipError_t e = rc ? hipSuccess : hipMemcpyAsync(p->rope_cos + p->rope_top, hc, tab * 4, hipMemcpyHostToDevice, st);
+            if (!rc && e == hipSuccess) e = hipMemcpyAsync(p->rope_sin + p->rope_top, hs, tab * 4, hipMemcpyHostToDevice, st);
             if (rc || e != hipSuccess) {
-                if (g.own) { (void)hipFree(g.pos); p->scratch_bytes -= ((size_t)gh * gw + 1) * p->D * 4; }
+                give_back(p, g);
                 if (!rc) { set_error("vitx_pack_forward: rotary table upload: %s", hipGetErrorString(e)); rc = VITX_ERR_HIP; }
                 return rc;
             }
@@ -139,6 +165,7 @@ int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_im
         p->rope_cap = 2L * max_tokens * (D / H / 2);
         if ((rc = dmalloc((void **)&p->rope_cos, (size_t)p->rope_cap * 4))) return rc;
         if ((rc = dmalloc((void **)&p->rope_sin, (size_t)p->rope_cap * 4))) return rc;
+        HIP_TRY(hipHostMalloc((void **)&p->rope_host, (size_t)p->rope_cap * 2 * 4, hipHostMallocDefault));
     }
     HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&p->uploaded, hipEventDisableTiming));

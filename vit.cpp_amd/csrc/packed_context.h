@@ -48,6 +48,7 @@ struct PackGrid {
     int gh = 0, gw = 0;
     float *pos = nullptr;                // [1 + gh gw][D] f32; the weight set's own table (own == false) at the file's grid
     bool own = false;
+    size_t pos_bytes = 0;                // bytes allocated behind an own table (a reused one may be larger than the grid needs)
     long rope_off = 0;                   // floats into rope_cos / rope_sin: the grid's [gh gw][hd / 2] table (files with `rope`)
     uint64_t used = 0;                   // the call (vitx_pack::tick) that named the grid last
 };
@@ -84,6 +85,11 @@ struct vitx_pack {
     uint64_t tick = 0;
     float *rope_cos = nullptr, *rope_sin = nullptr;      // the rotary arenas, rope_cap floats each; rope_top: the first free float
     long rope_cap = 0, rope_top = 0;
+    float *rope_host = nullptr;          // pinned mirror of both arenas, [2][rope_cap]: the staging of the asynchronous table uploads (a piece is
+                                         // rewritten only when the arena restarts, after the forwards that were fed from it)
+    struct Retired { float *pos; size_t bytes; };
+    std::vector<Retired> retired;        // own position tables of dropped grids, kept for the next grid they hold: hipFree would wait for the whole
+                                         // device, and a call that drops a table must not wait for the caller's stream (oldest first)
     int feat_flags = 0;                  // vitx_pack_feat_enable
     float *feat = nullptr;               // [max_tokens][D] f32 final-norm rows of the last forward (allocated by vitx_pack_feat_enable)
     int feat_n = 0;                      // images of the last forward with features on (0: none)
@@ -99,6 +105,8 @@ struct vitx_pack {
         (void)hipSetDevice(device);
         for (void *p : allocs) (void)hipFree(p);
         for (PackGrid &g : grids) if (g.own) (void)hipFree(g.pos);
+        for (Retired &r : retired) (void)hipFree(r.pos);
+        if (rope_host) (void)hipHostFree(rope_host);
         if (img) (void)hipFree(img);
         if (feat) (void)hipFree(feat);
         if (uploaded) (void)hipEventDestroy(uploaded);
