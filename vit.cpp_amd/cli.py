@@ -211,6 +211,8 @@ def main(argv: List[str] | None = None) -> int:
         ap.error("--img-size, --img-shape and --img-fit are three ways to say one thing: give one")
     if a.img_fit and a.dir is not None:
         ap.error("--img-fit takes its shape from the single image of -i, not --dir (use --img-shape HxW)")
+    if a.img_fit and a.gallery_build:
+        ap.error("--img-fit takes its shape from the single image of -i, not --gallery-build (use --img-shape HxW)")
     if a.pack and (not a.img_fit or a.dir is not None or a.dtype == "mxfp8" or a.attn_map or a.embed or a.zero_shot or a.text_model or a.gallery or a.gallery_build):
         ap.error("--pack takes --img-fit SHORT, the images of -i A.jpg,B.jpg,... and --dtype f16 or bf16; of the opt-in outputs a packed context has the dense head "
                  "(--dense-head HEAD.npz --dense-out PREFIX) and the depth head (--depth-head HEAD.npz --depth-out PREFIX) only")

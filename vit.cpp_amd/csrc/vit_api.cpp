@@ -83,7 +83,8 @@ bool vit_image_preprocess_rect(const image_u8 &img, image_f32 &res, const vit_mo
 }
 
 // The reference's vit_state carries no weights and can be reused with any model; ours caches a context that does, so the cache
-// is keyed on the unique id of the parsed model it was built from (vit_model_load frees and replaces that handle on every call).
+// is keyed on the unique id of the parsed model it was built from (vit_model_load frees and replaces that handle on every call),
+// and on everything else of the state the context was created from: geometry, pos_interp, device and dtype.
 // The input side a state's context takes: vit_state::img_size, or the file's when that is 0
 static int state_img_size(const vit_model &model, const vit_state &state) { return state.img_size > 0 ? state.img_size : model.hparams.img_size; }
 
@@ -111,14 +112,15 @@ static int ensure_ctx(const vit_model &model, vit_state &state, int n) {
     if (state.ctx) (void)vitx_ctx_img_shape(state.ctx, &ch, &cw);
     const bool own = Sh == model.hparams.img_size && Sw == model.hparams.img_size;
     const bool same_geometry = state.ctx && ch == Sh && cw == Sw && (own || state.ctx_pos_interp == state.pos_interp);
-    if (same_geometry && state.ctx_model_uid == vitx_model_uid(model.handle) && vitx_ctx_max_batch(state.ctx) >= n) return VITX_OK;
+    if (same_geometry && state.ctx_model_uid == vitx_model_uid(model.handle) && state.ctx_device == state.device && state.ctx_dtype == state.dtype &&
+        vitx_ctx_max_batch(state.ctx) >= n) return VITX_OK;
     vitx_ctx_free(state.ctx); state.ctx = nullptr; state.ctx_model_uid = 0;
     state.max_batch = std::max(state.max_batch, n);
     vitx_ctx_options opt{};
     opt.struct_size = (int32_t)sizeof(opt); opt.img_size = state.img_size; opt.pos_interp = state.pos_interp;
     const int rc = rect ? vitx_ctx_create_rect(model.handle, state.device, state.max_batch, state.dtype, &opt, Sh, Sw, &state.ctx)
                         : vitx_ctx_create_ex(model.handle, state.device, state.max_batch, state.dtype, &opt, &state.ctx);
-    if (rc == VITX_OK) { state.ctx_model_uid = vitx_model_uid(model.handle); state.ctx_pos_interp = state.pos_interp; }
+    if (rc == VITX_OK) { state.ctx_model_uid = vitx_model_uid(model.handle); state.ctx_pos_interp = state.pos_interp; state.ctx_device = state.device; state.ctx_dtype = state.dtype; }
     return rc;
 }
 
@@ -176,7 +178,7 @@ int vit_pack_batch(const vit_model &model, vit_state &state, const image_f32 *im
     }
     if (vitx_pack_check(model.handle, shapes.data(), n, 0x7fffffff, n, row0.data()) != VITX_OK) { fprintf(stderr, "%s: %s\n", __func__, vitx_last_error()); return 1; }
     const bool fits = state.pack && state.pack_model_uid == vitx_model_uid(model.handle) && state.pack_tokens >= row0[n] && state.pack_images >= n &&
-                      state.pack_dtype == state.dtype && state.pack_pos_interp == state.pos_interp;
+                      state.pack_dtype == state.dtype && state.pack_pos_interp == state.pos_interp && state.pack_device == state.device;
     if (!fits) {
         vitx_pack_free(state.pack); state.pack = nullptr;
         vitx_pack_options opt{};
@@ -187,7 +189,7 @@ int vit_pack_batch(const vit_model &model, vit_state &state, const image_f32 *im
             state.pack_tokens = state.pack_images = 0;
             return 1;
         }
-        state.pack_model_uid = vitx_model_uid(model.handle); state.pack_dtype = state.dtype; state.pack_pos_interp = state.pos_interp;
+        state.pack_model_uid = vitx_model_uid(model.handle); state.pack_dtype = state.dtype; state.pack_pos_interp = state.pos_interp; state.pack_device = state.device;
     }
     std::vector<float> pixels;
     pixels.reserve(floats);
@@ -401,11 +403,11 @@ int vit_text_embed_batch(const vit_model &model, vit_text_state &state, const in
     out.clear();
     if (!model.handle || !ids || n <= 0) { fprintf(stderr, "%s: invalid argument\n", __func__); return 1; }
     if (vitx_model_kind(model.handle) != VITX_KIND_TEXT) { fprintf(stderr, "%s: this is an image model: it has no text tower\n", __func__); return 1; }
-    if (!state.ctx || state.ctx_model_uid != vitx_model_uid(model.handle) || state.max_prompts < n) {
+    if (!state.ctx || state.ctx_model_uid != vitx_model_uid(model.handle) || state.ctx_device != state.device || state.ctx_dtype != state.dtype || state.max_prompts < n) {
         vitx_text_free(state.ctx); state.ctx = nullptr; state.ctx_model_uid = 0;
         state.max_prompts = std::max(state.max_prompts, n);
         if (vitx_text_create(model.handle, state.device, state.max_prompts, state.dtype, &state.ctx) != VITX_OK) { fprintf(stderr, "%s: failed to create the context: %s\n", __func__, vitx_last_error()); return 1; }
-        state.ctx_model_uid = vitx_model_uid(model.handle);
+        state.ctx_model_uid = vitx_model_uid(model.handle); state.ctx_device = state.device; state.ctx_dtype = state.dtype;
     }
     const int E = model.hparams.num_classes;
     std::vector<float> flat((size_t)n * E);

@@ -58,9 +58,12 @@ struct vit_state {                        // vit.h:72-80: per-caller mutable scr
     uint64_t ctx_model_uid = 0;           // vitx_model_uid of the parsed file `ctx` holds the weights of: a state reused with another (or a
                                           // reloaded) vit_model gets a fresh context instead of silently running the old weights.  An id,
                                           // not the pointer: `vit_model m; vit_model_load(f, m);` in a loop usually re-allocates the same address
-    int device = 0;
+    int device = 0;                       // the HIP device `ctx` and `pack` live on.  device and dtype may be changed between calls: a cached context that was
+                                          // created with other values is replaced on the next call (ctx_device / ctx_dtype, pack_device / pack_dtype hold what
+                                          // each was created with); a device that does not exist makes that call return 1
     int max_batch = 1;                    // capacity of ctx; grown on demand by vit_predict_batch
     int dtype = VITX_F16;                 // MFMA operand type (VITX_F16 reproduces the reference's rounding); VITX_MXFP8: experimental, slower than bf16
+    int ctx_device = 0, ctx_dtype = 0;    // the device and dtype `ctx` was created with
     int img_size = 0;                     // 0 = the file's; else the side of the images THIS state takes (a positive multiple of the patch size): the context
                                           // runs on the file's position table resampled to that grid (vitx_ctx_options::img_size).  vit_predict, vit_predict_batch
                                           // and vit_embed_batch check their images against this size; preprocess to it by passing vit_image_preprocess a copy of
@@ -73,7 +76,7 @@ struct vit_state {                        // vit.h:72-80: per-caller mutable scr
     std::vector<float> prediction;        // class probabilities of the last call ([n][num_classes])
     vitx_pack *pack = nullptr;            // the packed context of vit_pack_batch, created lazily on `device` with `dtype` and `pos_interp`; grown on demand
     uint64_t pack_model_uid = 0;
-    int pack_tokens = 0, pack_images = 0, pack_dtype = 0, pack_pos_interp = 0;      // what `pack` was created with
+    int pack_tokens = 0, pack_images = 0, pack_dtype = 0, pack_pos_interp = 0, pack_device = 0;      // what `pack` was created with
     vit_state() = default;
     vit_state(const vit_state &) = delete;
     vit_state &operator=(const vit_state &) = delete;
@@ -197,9 +200,10 @@ int vit_depth_batch(const vit_model &model, vit_state &state, const image_f32 *i
 struct vit_text_state {                   // per-caller mutable scratch of the text tower, the analogue of vit_state
     vitx_text *ctx = nullptr;             // created lazily on `device`, grown on demand
     uint64_t ctx_model_uid = 0;
-    int device = 0;
+    int device = 0;                       // device and dtype may be changed between calls, as in vit_state: the context is then replaced on the next call
     int max_prompts = 1;
     int dtype = VITX_F16;                 // VITX_F16 or VITX_BF16
+    int ctx_device = 0, ctx_dtype = 0;    // the device and dtype `ctx` was created with
     vit_text_state() = default;
     vit_text_state(const vit_text_state &) = delete;
     vit_text_state &operator=(const vit_text_state &) = delete;
