@@ -1235,9 +1235,41 @@ int vitx_op_attention_generic(int dtype, const void *d_qkv, void *d_out, int n_i
  *                              (oh, ow) -> d_out f32, image i's map with the bits of vitx_op_depth_resize on that image alone, the maps end to
  *                              end.  A work item is (image, 64 x 16 output tile).  vitx_op_depth_resize's checks per image.
  *                              Both are TEST entry points: they build and upload the tables and free them after the launch (synchronise).
+ *
+ * u8 sources (vitx_pack_u8_set): a pack fed from decoded u8 originals, each of its own size, instead of f32 pixels already resized.  ONE launch per
+ * pack (vitx_op_preprocess_pack's kernel) stretches source i, u8 HWC [ny_i][nx_i][3], to image i's own h_i x w_i with Pillow's arithmetic and the
+ * description's mean / std -- vitx_preprocess_rect's meaning, no crop, the aspect is the caller's (vitx_pack_fit_shapes: vitx_rect_shape per
+ * image) -- into the context's pixel buffer, which the unchanged forward then reads: one kernel launch more, counted by vitx_pack_launches.  Image
+ * i's pixels are the bits of vitx_preprocess_rect (and of vitx_preprocess_rect_device) on it alone, at any position and beside any neighbours:
+ * a workgroup lays out its LDS by its image's own tiling, and no bit depends on the launch's LDS size (the largest tiling of the call).
+ * vitx_pack_u8_set: pp (NULL: the file's, vitx_model_preproc) must pass the description's rules (VITX_ERR_ARG) and name a PIL filter
+ * (VITX_ERR_UNSUPPORTED, vitx_preprocess_rect's rule), before any device call; it allocates the device staging of the host entry point
+ * (max_src_bytes rounded up to 4) and the f32 pixel buffer (max_tokens P^2 3 floats, which vitx_pack_forward otherwise allocates at its first
+ * call); both and the tables count in vitx_pack_scratch_bytes.  A refused set leaves what was set.  max_src_bytes = 0: off, everything the set
+ * allocated is freed and vitx_pack_scratch_bytes returns to its value before.  While off nothing is allocated or launched and the forward is
+ * unchanged.  vitx_pack_u8_sources declares, as vitx_pack_dense_out does for output shapes, that the NEXT forward call's d_imgs holds the u8
+ * sources strictly end to end, no padding, with sizes src_shapes [n][2] = (ny, nx); `shapes` of that call stays the images' (output) shapes.
+ * That call consumes the declaration whether it runs or is refused; the call after it takes f32 pixels again (NULL / n = 0 withdraws it;
+ * VITX_ERR_ARG while u8 is off).  Alignment: sources start at every byte alignment; d_imgs itself must be 4-byte aligned and readable up to
+ * its byte count rounded up to 4 (the kernel stages source rows by aligned dword loads; of a dword that straddles two sources, or the end, only the
+ * row's own bytes are used).  vitx_pack_forward_device in that mode uploads the launch's tables in the call's one table upload and still only
+ * enqueues.  Refused before the call's first device call, nothing launched or written, the context usable: VITX_ERR_ARG for a declaration whose
+ * n differs from the call's, a d_imgs that is not 4-byte aligned, a source side outside 1 .. 2^20, more than max_src_bytes source bytes, more than
+ * 2^31 - 1 tiles (32 x 8 output pixels each); VITX_ERR_UNSUPPORTED for an image whose down-scale needs more than 64 KiB of LDS per tile
+ * (vitx_preprocess_rect_device_supports; the text names the image -- feed that pack through vitx_preprocess_rect).  vitx_pack_u8_check is that text,
+ * host only (pp NULL: the file's; max_src_bytes 0: no bound); it returns src0 [n + 1] (source i is bytes src0[i] .. src0[i + 1] - 1), tile0 [n + 1]
+ * (the running tile count) and *lds (the launch's dynamic LDS); any may be NULL.  vitx_pack_forward_u8 is the host entry point, vitx_pack_forward's
+ * shape on u8: it declares the sources, uploads them (3 bytes per SOURCE pixel, where vitx_pack_forward uploads 12 per output pixel) on the context's
+ * stream, runs the forward and copies the results back.  vitx_pack_forward refuses a call for which sources are declared (VITX_ERR_ARG).
+ *   vitx_op_preprocess_pack    the kernel alone on the caller's device buffers: d_srcs as above, HOST src_shapes [n][2] = (ny, nx) and out_shapes
+ *                              [n][2] = (h, w) -> d_out f32 HWC, the images end to end; nothing else is written.  A work item is (image, 32 x 8
+ *                              output tile), found by a binary search of the workgroup index in the running tile count: a 1-D grid.  The
+ *                              refusals above.  TEST entry point: it runs on the null stream, builds and uploads the tables and frees them after
+ *                              the launch (synchronises).
  * Not offered on packed contexts (each a later step): the other opt-in heads (attention maps, zero-shot bank, gallery), the pooled
  * and attention-pooling heads, the F16 parity planes, LayerNorm fusion and sub-batch streams, a packed patch-embedding kernel, vitx_group_*;
- * of the dense and the depth head: downsampling, and a vit.h wrapper. */
+ * of the dense and the depth head: downsampling, and a vit.h wrapper; of the u8 sources: crops and shortest-edge geometry (a source is stretched
+ * to the given shape), the REF filters, JPEG decode on the device, and a vit.h wrapper. */
 typedef struct vitx_pack vitx_pack;
 typedef struct { int pos_interp, max_grids, reserved[6]; } vitx_pack_options;
 int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_images, int dtype, const vitx_pack_options *opt, vitx_pack **out);
@@ -1291,6 +1323,17 @@ int vitx_depth_pack_tables(const int32_t *grids, const int32_t *outs, const int3
 int vitx_op_depth_fine_packed_tables(const void *d_logits, long ld, const void *d_offsets, long ldo, const void *d_bins, const void *d_tab, int n, int tiles, int cells, int K,
                                      void *d_fine, void *stream);
 int vitx_op_depth_resize_packed_tables(const void *d_fine, const void *d_tab, int n, int tiles, float min_depth, float max_depth, void *d_out, void *stream);
+/* u8 sources */
+int vitx_pack_u8_set(vitx_pack *p, const vitx_preproc *pp /* NULL: the file's, vitx_model_preproc */, size_t max_src_bytes /* 0 = off */);
+int vitx_pack_u8_sources(vitx_pack *p, const int32_t *src_shapes /* [n][2] = ny, nx; NULL: none */, int n);
+int vitx_pack_forward_u8(vitx_pack *p, const uint8_t *srcs, const int32_t *src_shapes, const int32_t *shapes, int n, float *probs, float *logits /* or NULL */);
+/* host only: every refusal a forward call adds while u8 sources are declared for it */
+int vitx_pack_u8_check(const vitx_model *m, const vitx_preproc *pp, const int32_t *src_shapes, const int32_t *shapes, int n, size_t max_src_bytes,
+                       int64_t *src0 /* [n + 1] or NULL */, int32_t *tile0 /* [n + 1] or NULL */, int *lds /* or NULL */);
+/* host only: vitx_rect_shape per image, shapes [n][2] = h, w */
+int vitx_pack_fit_shapes(const vitx_model *m, const int32_t *src_shapes, int n, int short_side, int max_long, int32_t *shapes);
+int vitx_op_preprocess_pack(const vitx_preproc *pp, const void *d_srcs, const int32_t *src_shapes /* host [n][2] */, const int32_t *out_shapes /* host [n][2] */,
+                            int n, void *d_out);
 
 /* ---- MXFP8 operands (VITX_MXFP8, encoding above) ------------------------------- */
 /* Host encoder: x f32 [rows][K] -> q [rows][k_pad] e4m3 bytes + scales [rows][k_pad / 32] (k_pad >= K, a multiple of 32; columns

@@ -75,6 +75,7 @@ EXPORTS = [
     "vitx_dense_pack_tables", "vitx_op_dense_labels_packed_tables",
     "vitx_pack_depth_set", "vitx_pack_depth_out", "vitx_pack_depth_check", "vitx_pack_depth_read", "vitx_pack_depth_device", "vitx_pack_depth_scratch_bytes",
     "vitx_op_depth_fine_packed", "vitx_op_depth_resize_packed", "vitx_depth_pack_tables", "vitx_op_depth_fine_packed_tables", "vitx_op_depth_resize_packed_tables",
+    "vitx_pack_u8_set", "vitx_pack_u8_sources", "vitx_pack_forward_u8", "vitx_pack_u8_check", "vitx_pack_fit_shapes", "vitx_op_preprocess_pack",
 ]
 
 
@@ -363,6 +364,14 @@ def lib():
             L.vitx_depth_pack_tables.argtypes = [i32p, i32p, i32p, i32p, ip, ip, i32p, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]
             L.vitx_op_depth_fine_packed_tables.argtypes = [vp, C.c_long, vp, C.c_long, vp, vp, ip, ip, ip, ip, vp, vp]
             L.vitx_op_depth_resize_packed_tables.argtypes = [vp, vp, ip, ip, cf, cf, vp, vp]
+        if hasattr(L, "vitx_pack_u8_set"):
+            i32p, fp, pp = C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(Preproc)
+            L.vitx_pack_u8_set.argtypes = [vp, pp, C.c_size_t]
+            L.vitx_pack_u8_sources.argtypes = [vp, i32p, ip]
+            L.vitx_pack_forward_u8.argtypes = [vp, C.POINTER(C.c_uint8), i32p, i32p, ip, fp, fp]
+            L.vitx_pack_u8_check.argtypes = [vp, pp, i32p, i32p, ip, C.c_size_t, C.POINTER(C.c_int64), i32p, C.POINTER(ip)]
+            L.vitx_pack_fit_shapes.argtypes = [vp, i32p, ip, ip, ip, i32p]
+            L.vitx_op_preprocess_pack.argtypes = [pp, vp, i32p, i32p, ip, vp]
         _lib = L
     return _lib
 
@@ -1183,6 +1192,42 @@ def pack_images(imgs_u8, pp: Preproc, short_side: int, max_long: int = 0, *, pat
     return np.concatenate(flat), np.asarray(shapes, np.int32)
 
 
+def pack_fit_shapes(model: Model, src_shapes, short_side: int, max_long: int = 0) -> np.ndarray:
+    """vitx_pack_fit_shapes (host only): rect_shape per source of `src_shapes` [n][2] = (ny, nx) -> shapes int32 [n][2] = (h, w)."""
+    a = _pack_shapes(src_shapes)
+    out = np.empty_like(a)
+    i32p = C.POINTER(C.c_int32)
+    check(lib().vitx_pack_fit_shapes(model._h, a.ctypes.data_as(i32p), a.shape[0], short_side, max_long, out.ctypes.data_as(i32p)), "vitx_pack_fit_shapes")
+    return out
+
+
+def pack_u8_check(model: Model, pp: Optional[Preproc], src_shapes, shapes, max_src_bytes: int = 0):
+    """vitx_pack_u8_check (host only): (src0 int64 [n + 1], tile0 int32 [n + 1], lds) of a packed forward of `shapes` [n][2] = (h, w) fed from u8 sources of
+    `src_shapes` [n][2] = (ny, nx) -- source i is bytes src0[i] .. src0[i + 1] - 1, tile0 the running count of the preprocessing launch's 32 x 8 tiles,
+    lds its dynamic LDS -- or VitxError for what such a forward refuses.  pp None: the file's description; max_src_bytes 0: no bound."""
+    a, o = _pack_shapes(src_shapes), _pack_shapes(shapes)
+    n = o.shape[0]
+    if a.shape[0] != n:      # the C call takes one n: a list of another length is refused there as a forward refuses it
+        e = VitxError(f"vitx_pack_u8_check: u8 sources were declared for {a.shape[0]} images, the call has {n}")
+        e.code = ERR_ARG
+        raise e
+    src0, tile0, lds = np.empty(n + 1, np.int64), np.empty(n + 1, np.int32), C.c_int()
+    i32p = C.POINTER(C.c_int32)
+    check(lib().vitx_pack_u8_check(model._h, C.byref(pp) if pp is not None else None, a.ctypes.data_as(i32p), o.ctypes.data_as(i32p), n, max_src_bytes,
+                                   src0.ctypes.data_as(C.POINTER(C.c_int64)), tile0.ctypes.data_as(i32p), C.byref(lds)), "vitx_pack_u8_check")
+    return src0, tile0, lds.value
+
+
+def preprocess_pack(pp: Preproc, d_srcs: int, src_shapes, out_shapes, d_out: int) -> None:
+    """vitx_op_preprocess_pack (test only; null stream, synchronous): u8 HWC sources of `src_shapes` [n][2] = (ny, nx) strictly end to end at d_srcs (4-byte
+    aligned, readable up to the byte count rounded up to 4), each stretched to its own out_shapes [n][2] = (h, w) -> d_out f32 HWC, end to end."""
+    a, o = _pack_shapes(src_shapes), _pack_shapes(out_shapes)
+    if a.shape[0] != o.shape[0]:
+        raise ValueError(f"{a.shape[0]} source shapes, {o.shape[0]} output shapes")
+    i32p = C.POINTER(C.c_int32)
+    check(lib().vitx_op_preprocess_pack(C.byref(pp), d_srcs or None, a.ctypes.data_as(i32p), o.ctypes.data_as(i32p), a.shape[0], d_out or None), "vitx_op_preprocess_pack")
+
+
 class PackContext:
     """A packed context (include/vitx.h "packed batches"): images of different shapes, their tokens end to end, in one forward."""
 
@@ -1234,6 +1279,40 @@ class PackContext:
         self._dense_forward(s, rc == 0)
         check(rc, "vitx_pack_forward_device")
         self._shapes = s
+
+    def u8_set(self, pp: Optional[Preproc] = None, max_src_bytes: int = 0) -> None:
+        """u8 sources for later calls (vitx_pack_u8_set): the description (None: the file's) and the most source bytes forward_u8 may upload; 0: off."""
+        check(lib().vitx_pack_u8_set(self._h, C.byref(pp) if pp is not None else None, int(max_src_bytes)), "vitx_pack_u8_set")
+
+    def u8_sources(self, src_shapes) -> None:
+        """The NEXT forward_device call's d_imgs holds u8 HWC sources of `src_shapes` [n][2] = (ny, nx) end to end (vitx_pack_u8_sources); that call consumes
+        the declaration.  None withdraws it."""
+        if src_shapes is None:
+            check(lib().vitx_pack_u8_sources(self._h, None, 0), "vitx_pack_u8_sources")
+            return
+        s = _pack_shapes(src_shapes)
+        check(lib().vitx_pack_u8_sources(self._h, s.ctypes.data_as(C.POINTER(C.c_int32)), s.shape[0]), "vitx_pack_u8_sources")
+
+    def forward_u8(self, imgs_u8, shapes):
+        """A list of u8 HWC originals [ny_i, nx_i, 3], each stretched on the device to its own shapes[i] = (h, w), in one forward (vitx_pack_forward_u8).
+        Returns (probs, logits), each [n, C]."""
+        arrs = [np.ascontiguousarray(a, np.uint8) for a in imgs_u8]
+        for a in arrs:
+            if a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError(f"every image must be [ny, nx, 3], got {a.shape}")
+        s = _pack_shapes(shapes); n = s.shape[0]
+        src = _pack_shapes([a.shape[:2] for a in arrs]) if arrs else np.empty((0, 2), np.int32)
+        if src.shape[0] != n:
+            raise ValueError(f"{src.shape[0]} images, {n} shapes")
+        flat = np.concatenate([a.ravel() for a in arrs]) if arrs else np.empty(0, np.uint8)
+        probs = np.empty((n, self.model.num_classes), np.float32); logits = np.empty_like(probs)
+        fp, i32p = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        rc = lib().vitx_pack_forward_u8(self._h, flat.ctypes.data_as(C.POINTER(C.c_uint8)), src.ctypes.data_as(i32p), s.ctypes.data_as(i32p), n,
+                                        probs.ctypes.data_as(fp), logits.ctypes.data_as(fp))
+        self._dense_forward(s, rc == 0)
+        check(rc, "vitx_pack_forward_u8")
+        self._shapes = s
+        return probs, logits
 
     def feat_enable(self, cls: bool = True, tokens: bool = False) -> None:
         """Last-layer features of every later forward (vitx_pack_feat_enable); neither: off."""

@@ -8,6 +8,7 @@ directory-walk accuracy harness:
     python vit_cli.py -m model.gguf ... --img-size 384 [--pos-interp bicubic|bicubic-aa]   # run at another input size than the file's
     python vit_cli.py -m model.gguf ... --img-shape 224x448 | --img-fit 224   # a rectangular context: HxW, or the aspect-preserving shape of the input image
     python vit_cli.py -m model.gguf -i a.jpg,b.jpg,c.jpg --pack --img-fit 224   # several images, each at its own aspect-preserving shape, in one packed forward
+    python vit_cli.py -m model.gguf -i a.jpg,b.jpg,c.jpg --pack --img-fit 224 --pack-u8   # the same, resized on the device from the u8 originals in one launch
     python vit_cli.py -m model.gguf ... [--preprocess model|reference]   # the file's own preprocessing (default) or the reference's for any file
     python vit_cli.py -m clip.gguf -i image.jpg -k 5 --zero-shot bank.npz   # zero-shot classes of a CLIP / SigLIP file (bank: convert.py --zero-shot-out)
     python vit_cli.py -m clip.gguf -i image.jpg --text-model text.gguf --zero-shot-ids ids.npy [--zero-shot-labels labels.txt]   # the bank made by the engine, same run
@@ -91,6 +92,9 @@ def make_parser() -> argparse.ArgumentParser:
                     help="run on H x W images (both multiples of the patch size) in a rectangular context: the image is STRETCHED to that shape by the "
                          "file's own filter, mean and std, without a crop (a file without a `preproc` tensor, or one with the reference's filter: Pillow "
                          "bicubic with the file's default mean / std); --attn-map then writes a W x H picture, --embed-kind tokens (H/P)(W/P) rows")
+    ap.add_argument("--pack-u8", action="store_true",
+                    help="with --pack: feed the decoded u8 originals and let ONE device launch stretch each to its own shape (vitx_pack_forward_u8), instead of "
+                         "resizing on the host; the printed lines are the same")
     ap.add_argument("--img-fit", type=int, default=0, metavar="SHORT",
                     help="with -i: like --img-shape, with the shape taken from the input image: its short side becomes SHORT (a multiple of the patch size), "
                          "the long side the largest multiple of the patch size that keeps the aspect (vitx_rect_shape; 500 x 375 at 224, patch 16: 288 x 224)")
@@ -213,6 +217,8 @@ def main(argv: List[str] | None = None) -> int:
         ap.error("--img-fit takes its shape from the single image of -i, not --dir (use --img-shape HxW)")
     if a.img_fit and a.gallery_build:
         ap.error("--img-fit takes its shape from the single image of -i, not --gallery-build (use --img-shape HxW)")
+    if a.pack_u8 and not a.pack:
+        ap.error("--pack-u8 goes with --pack")
     if a.pack and (not a.img_fit or a.dir is not None or a.dtype == "mxfp8" or a.attn_map or a.embed or a.zero_shot or a.text_model or a.gallery or a.gallery_build):
         ap.error("--pack takes --img-fit SHORT, the images of -i A.jpg,B.jpg,... and --dtype f16 or bf16; of the opt-in outputs a packed context has the dense head "
                  "(--dense-head HEAD.npz --dense-out PREFIX) and the depth head (--depth-head HEAD.npz --depth-out PREFIX) only")
@@ -323,7 +329,10 @@ def main(argv: List[str] | None = None) -> int:
             print(f"main: failed to load an image of '{a.inp}': {e}", file=sys.stderr)
             return 1
         try:
-            pixels, shapes = binding.pack_images(imgs, pp_rect, a.img_fit, patch=model.hparams.patch_size)
+            if a.pack_u8:
+                shapes = binding.pack_fit_shapes(model, [im.shape[:2] for im in imgs], a.img_fit)
+            else:
+                pixels, shapes = binding.pack_images(imgs, pp_rect, a.img_fit, patch=model.hparams.patch_size)
             tokens = int(binding.pack_check(model, shapes, 2 ** 31 - 1, len(files))[-1])
             ctx = binding.PackContext(model, device=a.device, max_tokens=tokens, max_images=len(files), dtype=dt, pos_interp=geometry["pos_interp"])
             if dense:
@@ -339,7 +348,11 @@ def main(argv: List[str] | None = None) -> int:
                 ctx.depth_set(depth["wp"], depth["wc"], depth["bias"], depth["bins"], depth["layers"], u, depth["min_depth"], depth["max_depth"],
                               max_pixels=sum(h * w for h, w in outs), norm=depth["norm"])
                 ctx.depth_out(outs)
-            probs, _ = ctx.forward_flat(pixels, shapes)
+            if a.pack_u8:
+                ctx.u8_set(pp_rect, max_src_bytes=sum(im.size for im in imgs))
+                probs, _ = ctx.forward_u8(imgs, shapes)
+            else:
+                probs, _ = ctx.forward_flat(pixels, shapes)
             maps = ctx.dense_read()[0] if dense else None
             dmaps = ctx.depth_read()[0] if depth else None
         except binding.VitxError as e:

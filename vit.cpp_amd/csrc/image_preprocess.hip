@@ -6,6 +6,7 @@
 #include "device_common.h"
 #include "model_file.h"
 #include "preproc_resample.h"
+#include "preproc_tile.h"
 
 namespace vitx {
 
@@ -20,11 +21,6 @@ namespace vitx {
 struct PpImageNet {
     __device__ __forceinline__ float mean(int k) const { return k == 0 ? 123.675f : (k == 1 ? 116.280f : 103.530f); }
     __device__ __forceinline__ float sd(int k) const { return k == 0 ? 58.395f : (k == 1 ? 57.120f : 57.375f); }
-};
-struct PpMeanStd {
-    float m0, m1, m2, s0, s1, s2;
-    __device__ __forceinline__ float mean(int k) const { return k == 0 ? m0 : (k == 1 ? m1 : m2); }
-    __device__ __forceinline__ float sd(int k) const { return k == 0 ? s0 : (k == 1 ? s1 : s2); }
 };
 template <class NORM> __device__ __forceinline__ float pp_norm(float v, int k, const NORM &nm) {
     const unsigned char q = (unsigned char)fminf(fmaxf(roundf(v), 0.0f), 255.0f);
@@ -96,106 +92,48 @@ hipError_t launch_preprocess(const void *u8, float *out, int n, int nx, int ny, 
 
 // ------------------------------------------------------------------------------------------------
 // Pillow's Image.resize on u8 + centre crop + mean / std (include/vitx.h "each model's own preprocessing"; the arithmetic: preproc_resample.h,
-// shared with the host loop in preprocess.cpp, so both give Pillow's bits).  u8 HWC [n][ny][nx][3] -> f32 HWC [n][SH][SW][3] in ONE launch (the window is SW x SH: square for a description,
-// any pair for vitx_preprocess_rect_device).
-// A workgroup of 4 waves owns a PP_TW x PP_TH (32 x 8) tile of one image's output window:
-//   A  lanes 0 .. 39 (32 columns, then 8 rows; indices past the window's edge repeat its last one) find first / n of their target index and
-//      the weight total ww, in double;
-//   B  every lane fills the fixed-point coefficient rows k[32][kx], k[8][ky] (one IEEE divide per tap);
-//   C  horizontal pass: wave w takes source rows y0 + w, y0 + w + 4, ... of the rows [y0, y0 + R) the tile's vertical taps span.  The row's
-//      bytes [3 x0, 3 (x0 + span)) are staged in LDS by aligned dword loads (consecutive lanes, consecutive dwords: the first and the last
-//      dword may reach up to 3 bytes outside the span but never leave a dword that holds a byte of it), then 96 (column, channel) sums per row
-//      read the taps as LDS bytes -- the three channels of a pixel and neighbouring taps share dwords -- and write u8 to h[R][96];
-//   D  vertical pass over h, clamp, normalise, f32 stores: 96 consecutive floats per tile row.
-// Every LDS size comes from pp_tiling() on the host, computed with the same pil_bounds; the kernel clamps its own spans to them, so an index
-// cannot leave the allocation whatever the arithmetic gives.
+// shared with the host loop in preprocess.cpp, so both give Pillow's bits).  A workgroup of 4 waves owns a PP_TW x PP_TH (32 x 8) tile of one
+// image's output window; what it does there is pp_pil_tile (preproc_tile.h), one text for both kernels:
+//   pp_pil_kernel          sources of ONE size: u8 HWC [n][ny][nx][3] -> f32 HWC [n][SH][SW][3] in one launch (the window is SW x SH: square for a
+//                          description, any pair for vitx_preprocess_rect_device).  The grid is tiles x images.
+//   pp_pil_packed_kernel   a PACK: source i is u8 HWC [ny_i][nx_i][3], the sources strictly end to end (so they start at every alignment mod 4),
+//                          stretched to its own h_i x w_i, the f32 outputs end to end, in one launch.  A work item is (image, tile) and the grid is
+//                          sum_i tiles_i workgroups, 1-D; a workgroup finds its image by a wave-uniform binary search of blockIdx.x in tile0 [n + 1],
+//                          the running tile count, as dense_label_packed_kernel does.  The image's table row (pp_pack_tables) gives its offsets, sizes
+//                          and its OWN tiling; the two PilAxis are rebuilt by pil_axis, the VITX_HD function the host sized the tiling with.  The
+//                          launch's LDS is the largest tiling of the call; an image's bits depend neither on it nor on its neighbours.
+// Every LDS size comes from pp_tiling() on the host, computed with the same pil_bounds; the body clamps its own spans to them.
 // ------------------------------------------------------------------------------------------------
 struct PpPilArgs {
     const unsigned char *src; float *dst;
-    int nx, ny, SW, SH, left, top, tiles_x;
-    PilAxis ax, ay;
-    int kx, ky, rows, span, stage;
+    int tiles_x;
+    PpTileGeom g;
     PpMeanStd nm;
 };
 
 __global__ __launch_bounds__(256) void pp_pil_kernel(const PpPilArgs a) {
-    constexpr int NP = PP_TW + PP_TH, LINE = PP_TW * 3;
-    extern __shared__ __attribute__((aligned(16))) unsigned char pp_lds[];
-    double *s_ww = (double *)pp_lds;                          // [NP]
-    int *s_first = (int *)(s_ww + NP), *s_n = s_first + NP;   // [NP] each
-    int32_t *s_kx = (int32_t *)(s_n + NP);                    // [PP_TW][kx]
-    int32_t *s_ky = s_kx + PP_TW * a.kx;                      // [PP_TH][ky]
-    unsigned char *s_h = (unsigned char *)(s_ky + PP_TH * a.ky);      // [rows][LINE]
-    unsigned char *s_stage = s_h + (size_t)a.rows * LINE;     // [PP_WAVES][stage], dword aligned: LINE is a multiple of 4
-
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int bx = blockIdx.x % a.tiles_x, by = blockIdx.x / a.tiles_x, b = blockIdx.y;
-    const int ox0 = bx * PP_TW, oy0 = by * PP_TH;
-    auto target = [&](int p) {                                // the resized image's index of table row p
-        if (p < PP_TW) { const int o = ox0 + p; return a.left + (o < a.SW ? o : a.SW - 1); }
-        const int o = oy0 + p - PP_TW; return a.top + (o < a.SH ? o : a.SH - 1);
-    };
-    if (tid < NP) {
-        const PilAxis &ax = tid < PP_TW ? a.ax : a.ay;
-        int first, n;
-        pil_bounds(ax, target(tid), first, n);
-        s_first[tid] = first; s_n[tid] = n;
-        s_ww[tid] = pil_total(ax, target(tid), first, n);
-    }
-    __syncthreads();
-    for (int idx = tid; idx < PP_TW * a.kx + PP_TH * a.ky; idx += 256) {
-        const bool isx = idx < PP_TW * a.kx;
-        const int rel = isx ? idx : idx - PP_TW * a.kx, ks = isx ? a.kx : a.ky;
-        const int p = rel / ks + (isx ? 0 : PP_TW), j = rel - (rel / ks) * ks;
-        (isx ? s_kx : s_ky)[rel] = j < s_n[p] ? pil_coeff(isx ? a.ax : a.ay, target(p), s_first[p], j, s_ww[p]) : 0;
-    }
-    // the source window of this tile, clamped to what the host sized the LDS for
-    const int x0 = s_first[0], y0 = s_first[PP_TW];
-    int span = 0, R = 0;
-    for (int c = 0; c < PP_TW; ++c) span = max(span, s_first[c] + s_n[c] - x0);
-    for (int r = 0; r < PP_TH; ++r) R = max(R, s_first[PP_TW + r] + s_n[PP_TW + r] - y0);
-    span = min(span, a.span); R = min(R, a.rows);
-    __syncthreads();
+    pp_pil_tile(a.src + (size_t)b * a.g.nx * a.g.ny * 3, a.dst + (size_t)b * a.g.SH * a.g.SW * 3, a.g, a.nm, bx * PP_TW, by * PP_TH);
+}
 
-    const unsigned char *img = a.src + (size_t)b * a.nx * a.ny * 3;
-    unsigned char *stage = s_stage + (size_t)wave * a.stage;
-    for (int r0 = 0; r0 < R; r0 += PP_WAVES) {                // uniform trip count: the barriers are reached by all four waves
-        const int r = r0 + wave;
-        int shift = 0;
-        if (r < R) {
-            const unsigned char *rowp = img + ((size_t)(y0 + r) * a.nx + x0) * 3;
-            shift = (int)((uintptr_t)rowp & 3);
-            const uint32_t *al = (const uint32_t *)(rowp - shift);
-            const int ndw = (shift + 3 * span + 3) >> 2;      // <= stage / 4: stage = 3 * span rounded up to a dword, plus one dword
-            for (int d = lane; d < ndw; d += 64) ((uint32_t *)stage)[d] = al[d];
-        }
-        __syncthreads();
-        if (r < R) {
-            for (int e = lane; e < LINE; e += 64) {
-                const int c = e / 3, ch = e - c * 3;
-                const int rel = min(s_first[c] - x0, span), nt = min(s_n[c], span - rel);
-                const unsigned char *px = stage + shift + rel * 3 + ch;
-                const int32_t *k = s_kx + c * a.kx;
-                int32_t acc = 1 << (PIL_PRECISION_BITS - 1);
-                for (int j = 0; j < nt; ++j) acc += (int32_t)px[j * 3] * k[j];
-                s_h[r * LINE + e] = (unsigned char)pil_clip8(acc);
-            }
-        }
-        __syncthreads();
+// seg [n][kPpSegInts]: pp_pack_tables's rows
+__global__ __launch_bounds__(256) void pp_pil_packed_kernel(const unsigned char *__restrict__ srcs, float *__restrict__ dst, const int *__restrict__ tile0,
+                                                            const int *__restrict__ seg, int n, int bicubic, const PpMeanStd nm) {
+    const int wg = blockIdx.x;
+    int lo = 0, hi = n;                        // the image: tile0[lo] <= wg < tile0[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (tile0[mid] <= wg) lo = mid; else hi = mid;
     }
-
-    float *out = a.dst + (size_t)b * a.SH * a.SW * 3;
-    for (int item = tid; item < PP_TH * LINE; item += 256) {
-        const int ty = item / LINE, e = item - ty * LINE, tx = e / 3, ch = e - tx * 3;
-        const int oy = oy0 + ty, ox = ox0 + tx;
-        if (oy >= a.SH || ox >= a.SW) continue;
-        const int rel = min(s_first[PP_TW + ty] - y0, R), nt = min(s_n[PP_TW + ty], R - rel);
-        const unsigned char *m = s_h + rel * LINE + e;
-        const int32_t *k = s_ky + ty * a.ky;
-        int32_t acc = 1 << (PIL_PRECISION_BITS - 1);
-        for (int i = 0; i < nt; ++i) acc += (int32_t)m[i * LINE] * k[i];
-        out[((size_t)oy * a.SW + ox) * 3 + ch] = ((float)pil_clip8(acc) - a.nm.mean(ch)) / a.nm.sd(ch);
-    }
+    const int *s = seg + (size_t)lo * kPpSegInts;
+    const size_t src0 = (size_t)(uint32_t)s[0] | ((size_t)(uint32_t)s[1] << 32), dst0 = (size_t)(uint32_t)s[2] | ((size_t)(uint32_t)s[3] << 32);
+    PpTileGeom g;
+    g.nx = s[4]; g.ny = s[5]; g.SW = s[6]; g.SH = s[7]; g.left = 0; g.top = 0;
+    const int tiles_x = s[8];
+    g.kx = s[9]; g.ky = s[10]; g.rows = s[11]; g.span = s[12]; g.stage = s[13];
+    g.ax = pil_axis(bicubic, g.nx, g.SW); g.ay = pil_axis(bicubic, g.ny, g.SH);
+    const int item = wg - tile0[lo], by = item / tiles_x, bx = item - by * tiles_x;
+    pp_pil_tile(srcs + src0, dst + dst0, g, nm, bx * PP_TW, by * PP_TH);
 }
 
 static hipError_t launch_pp_pil(const vitx_preproc &p, const PpGeom &g, const PpMeanStd &nm, const void *u8, float *out, int n, int nx, int ny, hipStream_t stream);
@@ -231,12 +169,12 @@ hipError_t launch_preprocess_ex(const vitx_preproc &p, const void *u8, float *ou
 static hipError_t launch_pp_pil(const vitx_preproc &p, const PpGeom &g, const PpMeanStd &nm, const void *u8, float *out, int n, int nx, int ny, hipStream_t stream) {
     PpPilArgs a;
     const int bicubic = p.filter == VITX_PP_PIL_BICUBIC;
-    a.ax = pil_axis(bicubic, nx, g.W); a.ay = pil_axis(bicubic, ny, g.H);
-    const PpTiling t = pp_tiling(g, a.ax, a.ay);
+    a.g.ax = pil_axis(bicubic, nx, g.W); a.g.ay = pil_axis(bicubic, ny, g.H);
+    const PpTiling t = pp_tiling(g, a.g.ax, a.g.ay);
     if (t.lds > (size_t)PP_LDS_LIMIT) return hipErrorInvalidValue;
-    a.nx = nx; a.ny = ny; a.SW = g.SW; a.SH = g.SH; a.left = g.left; a.top = g.top;
+    a.g.nx = nx; a.g.ny = ny; a.g.SW = g.SW; a.g.SH = g.SH; a.g.left = g.left; a.g.top = g.top;
     a.tiles_x = (g.SW + PP_TW - 1) / PP_TW;
-    a.kx = t.kx; a.ky = t.ky; a.rows = t.rows; a.span = t.span; a.stage = t.stage; a.nm = nm;
+    a.g.kx = t.kx; a.g.ky = t.ky; a.g.rows = t.rows; a.g.span = t.span; a.g.stage = t.stage; a.nm = nm;
     const int tiles = a.tiles_x * ((g.SH + PP_TH - 1) / PP_TH);
     for (int i0 = 0; i0 < n; i0 += 65535) {                   // gridDim.y: images
         const int ni = std::min(n - i0, 65535);
@@ -261,6 +199,59 @@ hipError_t launch_preprocess_rect(const vitx_preproc &p, const void *u8, float *
     if (n <= 0 || pp_check(p) || !pp_filter_is_pil(p.filter) || pp_geometry_rect(nx, ny, out_w, out_h, g)) return hipErrorInvalidValue;
     const PpMeanStd nm = {p.mean255[0], p.mean255[1], p.mean255[2], p.std255[0], p.std255[1], p.std255[2]};
     return launch_pp_pil(p, g, nm, u8, out, n, nx, ny, stream);
+}
+
+// ---- a pack of sources (include/vitx.h "packed batches", u8 sources) -------------------------------------------------------------------
+int pp_pack_tables(const char *api, const vitx_preproc &p, const int32_t *src_shapes, const int32_t *out_shapes, int n, int64_t *src0, int64_t *dst0, int32_t *tile0,
+                   int32_t *seg, int *lds) {
+    if (!src_shapes || !out_shapes || n < 1) { set_error("%s: invalid argument", api); return VITX_ERR_ARG; }
+    if (const char *bad = pp_check(p)) { set_error("%s: %s", api, bad); return VITX_ERR_ARG; }
+    if (!pp_filter_is_pil(p.filter)) { set_error("%s: the reference's filters resize to squares only (use a PIL filter)", api); return VITX_ERR_UNSUPPORTED; }
+    const int bicubic = p.filter == VITX_PP_PIL_BICUBIC;
+    int64_t sb = 0, df = 0, tiles = 0;
+    size_t most = 0;
+    PpTiling t{};
+    for (int i = 0; i < n; ++i) {
+        const int ny = src_shapes[2 * i], nx = src_shapes[2 * i + 1], oh = out_shapes[2 * i], ow = out_shapes[2 * i + 1];
+        PpGeom g;
+        if (const char *bad = pp_geometry_rect(nx, ny, ow, oh, g)) { set_error("%s: image %d: %s", api, i, bad); return VITX_ERR_ARG; }
+        // a run of images of one source and output size shares one tiling
+        const bool same = i > 0 && src_shapes[2 * i - 2] == ny && src_shapes[2 * i - 1] == nx && out_shapes[2 * i - 2] == oh && out_shapes[2 * i - 1] == ow;
+        if (!same) t = pp_tiling(g, pil_axis(bicubic, nx, ow), pil_axis(bicubic, ny, oh));
+        if (t.lds > (size_t)PP_LDS_LIMIT) {
+            set_error("%s: image %d: a %d x %d source resized to %d x %d needs more than 64 KiB of LDS per tile (use vitx_preprocess_rect)", api, i, nx, ny, ow, oh);
+            return VITX_ERR_UNSUPPORTED;
+        }
+        const int tiles_x = (ow + PP_TW - 1) / PP_TW;
+        if (src0) src0[i] = sb;
+        if (dst0) dst0[i] = df;
+        if (tile0) tile0[i] = (int32_t)tiles;
+        if (seg) {
+            int32_t *s = seg + (size_t)i * kPpSegInts;
+            s[0] = (int32_t)(uint32_t)((uint64_t)sb & 0xffffffffu); s[1] = (int32_t)(uint32_t)((uint64_t)sb >> 32);
+            s[2] = (int32_t)(uint32_t)((uint64_t)df & 0xffffffffu); s[3] = (int32_t)(uint32_t)((uint64_t)df >> 32);
+            s[4] = nx; s[5] = ny; s[6] = ow; s[7] = oh; s[8] = tiles_x;
+            s[9] = t.kx; s[10] = t.ky; s[11] = t.rows; s[12] = t.span; s[13] = t.stage;
+        }
+        sb += (int64_t)nx * ny * 3;
+        df += (int64_t)ow * oh * 3;
+        tiles += (int64_t)tiles_x * ((oh + PP_TH - 1) / PP_TH);
+        if (tiles > 0x7fffffff) { set_error("%s: the call's outputs hold more than 2^31 - 1 tiles", api); return VITX_ERR_ARG; }
+        most = std::max(most, t.lds);
+    }
+    if (src0) src0[n] = sb;
+    if (dst0) dst0[n] = df;
+    if (tile0) tile0[n] = (int32_t)tiles;
+    if (lds) *lds = (int)most;
+    return VITX_OK;
+}
+
+hipError_t launch_preprocess_pack(const vitx_preproc &p, const void *u8, float *out, const int *tile0, const int *seg, int n, int tiles, int lds, hipStream_t stream) {
+    if (n < 1 || tiles < n || lds < 1 || lds > PP_LDS_LIMIT || pp_check(p) || !pp_filter_is_pil(p.filter) || !u8 || !out || !tile0 || !seg || ((uintptr_t)u8 & 3)) return hipErrorInvalidValue;
+    const PpMeanStd nm = {p.mean255[0], p.mean255[1], p.mean255[2], p.std255[0], p.std255[1], p.std255[2]};
+    hipLaunchKernelGGL(pp_pil_packed_kernel, dim3((unsigned)tiles), dim3(256), (size_t)lds, stream, (const unsigned char *)u8, out, tile0, seg, n,
+                       (int)(p.filter == VITX_PP_PIL_BICUBIC), nm);
+    return hipGetLastError();
 }
 
 }  // namespace vitx

@@ -337,6 +337,21 @@ bool preprocess_ex_supports(const vitx_preproc &p, int nx, int ny);
 // (vitx_preprocess_rect_device); hipErrorInvalidValue also for a REF filter
 hipError_t launch_preprocess_rect(const vitx_preproc &p, const void *u8, float *out, int n, int nx, int ny, int out_w, int out_h, hipStream_t stream);
 bool preprocess_rect_supports(const vitx_preproc &p, int nx, int ny, int out_w, int out_h);
+// The PIL kernel on a PACK (pp_pil_packed_kernel): source i u8 HWC [ny_i][nx_i][3], the sources strictly end to end, stretched to its own oh_i x ow_i, the
+// f32 HWC outputs end to end; image i's floats are the bits of launch_preprocess_rect on it alone.  A work item is (image, 32 x 8 output tile).
+//   pp_pack_tables   host only, the one place the tables are built and the one text of every refusal (the context's forward, vitx_pack_u8_check, the
+//                    op): src_shapes [n][2] = (ny, nx), out_shapes [n][2] = (oh, ow) -> src0 [n + 1] bytes, dst0 [n + 1] floats, tile0 [n + 1] the
+//                    running tile count, seg [n][kPpSegInts] the device table's rows -- source byte offset and destination float offset (low, high
+//                    word each), nx, ny, ow, oh, tiles_x, then the image's own kx, ky, rows, span, stage of pp_tiling -- and *lds, the largest
+//                    pp_tiling().lds of the call; any output may be NULL.  VITX_OK, or the refusal's code with "<api>: ..." as the error text:
+//                    VITX_ERR_ARG for an invalid description or a side out of range, VITX_ERR_UNSUPPORTED for a REF filter and for an image whose
+//                    tiling is above PP_LDS_LIMIT (the text names the image), VITX_ERR_ARG for more than 2^31 - 1 tiles.
+//   launch_preprocess_pack   tile0 and seg on the device; tiles = tile0[n] and lds from pp_pack_tables: the caller built the tables.  u8 is 4-byte
+//                    aligned and readable up to its byte count rounded up to 4 (the staged dword loads).
+constexpr int kPpSegInts = 14;
+int pp_pack_tables(const char *api, const vitx_preproc &p, const int32_t *src_shapes, const int32_t *out_shapes, int n, int64_t *src0, int64_t *dst0, int32_t *tile0,
+                   int32_t *seg, int *lds);
+hipError_t launch_preprocess_pack(const vitx_preproc &p, const void *u8, float *out, const int *tile0, const int *seg, int n, int tiles, int lds, hipStream_t stream);
 // out[row][k] = {f32 probability, i32 class} of the k largest entries of probs[row][0..cols), descending, ties by the lower class index
 // (softmax_topk.hip; the sort of vit_predict, vit.cpp:1043-1057, on the device: the multi-GPU gather then moves 8 k bytes per row instead of 4 cols)
 hipError_t launch_topk(const float *probs, int rows, int cols, int k, void *out_pairs, hipStream_t stream);

@@ -717,6 +717,25 @@ int vitx_preprocess_rect_device(const vitx_preproc *pp, const void *d_hwc, int n
     }
     return op_rc("vitx_preprocess_rect_device", launch_preprocess_rect(*pp, d_hwc, (float *)d_out, n, nx, ny, out_w, out_h, (hipStream_t)stream));
 }
+// The PIL kernel on a pack (include/vitx.h "packed batches", u8 sources): the tables built by the one host function (pp_pack_tables: its refusals) and
+// uploaded in one copy -- tile0 [n + 1] | seg [n][kPpSegInts] -- then the launch, on the null stream.  A test entry point: it waits for the launch
+// before it frees the tables.
+int vitx_op_preprocess_pack(const vitx_preproc *pp, const void *d_srcs, const int32_t *src_shapes, const int32_t *out_shapes, int n, void *d_out) {
+    const char *name = "vitx_op_preprocess_pack";
+    if (!pp || !d_srcs || !src_shapes || !out_shapes || !d_out || n < 1) { set_error("%s: invalid argument", name); return VITX_ERR_ARG; }
+    if ((uintptr_t)d_srcs % 4 || (uintptr_t)d_out % 4) { set_error("%s: d_srcs and d_out must be 4-byte aligned", name); return VITX_ERR_ARG; }
+    std::vector<int32_t> tab((size_t)n + 1 + (size_t)n * kPpSegInts);
+    int lds = 0;
+    if (const int rc = pp_pack_tables(name, *pp, src_shapes, out_shapes, n, nullptr, nullptr, tab.data(), tab.data() + n + 1, &lds)) return rc;
+    int *d_tab = nullptr;
+    HIP_TRY(hipMalloc((void **)&d_tab, tab.size() * 4));
+    const DevMem own(d_tab);
+    HIP_TRY(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, nullptr));
+    const hipError_t e = launch_preprocess_pack(*pp, d_srcs, (float *)d_out, d_tab, d_tab + n + 1, n, tab[n], lds, nullptr);
+    const hipError_t es = hipStreamSynchronize(nullptr);      // the tables are freed, and the staging vector goes, when this returns
+    if (e == hipSuccess && es != hipSuccess) return op_rc(name, es);
+    return op_rc(name, e);
+}
 int vitx_preprocess_u8_device(const void *d_hwc, int n, int nx, int ny, int img_size, int interp, void *d_out, void *stream) {
     if (!d_hwc || !d_out || n <= 0 || nx <= 0 || ny <= 0 || img_size <= 0) { set_error("vitx_preprocess_u8_device: invalid argument"); return VITX_ERR_ARG; }
     if (interp != VITX_BICUBIC && interp != VITX_BILINEAR) { set_error("vitx_preprocess_u8_device: interpolation mode %d is not supported", interp); return VITX_ERR_ARG; }

@@ -108,6 +108,26 @@ int resolve_grids(vitx_pack *p, const std::vector<uint64_t> &want, hipStream_t s
     return VITX_OK;
 }
 
+// nothing of this context is in flight while buffers and tables change hands
+int pack_quiesce(vitx_pack *p) {
+    if (p->uploaded_pending) { HIP_TRY(hipEventSynchronize(p->uploaded)); p->uploaded_pending = false; }
+    return wait_done(p);
+}
+
+// the segment tables with the parts of the heads and of the u8 sources that will be set behind them (PackLayout): a fresh zeroed buffer in place of the old one
+int resize_tables(vitx_pack *p, const char *api, bool dense, bool depth, bool u8) {
+    const size_t ints = PackLayout{(size_t)p->max_images, dense, depth, u8}.ints();
+    if (p->host.size() == ints) return VITX_OK;
+    int *t = nullptr;
+    HIP_TRY(hipMalloc((void **)&t, ints * 4));
+    if (const hipError_t e = hipMemset(t, 0, ints * 4); e != hipSuccess) { (void)hipFree(t); set_error("%s: %s", api, hipGetErrorString(e)); return VITX_ERR_HIP; }
+    std::replace(p->allocs.begin(), p->allocs.end(), (void *)p->tab, (void *)t);
+    (void)hipFree(p->tab);
+    p->scratch_bytes += ints * 4; p->scratch_bytes -= p->host.size() * 4;
+    p->tab = t; p->host.assign(ints, 0);
+    return VITX_OK;
+}
+
 extern "C" {
 
 int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_images, int dtype, const vitx_pack_options *opt, vitx_pack **out) {

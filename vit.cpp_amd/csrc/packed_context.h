@@ -1,7 +1,8 @@
 // packed_context.h -- the packed context (struct vitx_pack); include/vitx.h "packed batches": n images, each with its own h_i x w_i, their
 // tokens end to end in one [sum N_i][D] residual stream, one forward.  Modelled on the text context (text_context.h): its own scratch, one
 // stream, no sub-batches, no graph cache, no LayerNorm fusion.  Three units stand on it, split like the image context's: packed_context.cpp
-// (creation, counters, the table cache), packed_forward.cpp (the checks of a call, the forward), packed_outputs.cpp (features, the dense and the depth head).
+// (creation, counters, the table cache), packed_forward.cpp (the checks of a call, the forward), packed_outputs.cpp (features, the dense and the depth head)
+// and packed_input.cpp (u8 sources).
 // Internal: callers see the opaque vitx_pack of include/vitx.h.
 #pragma once
 #include <memory>
@@ -12,10 +13,12 @@ using namespace vitx;
 
 // The segment tables of a call, in ints into vitx_pack::tab / host (cap = max_images): row0 [cap + 1] | qb0 [cap + 1] | toff [cap] and, while a
 // dense head is set, behind them tile0 [cap + 1] | seg [cap][kDenseSegInts] and, while a depth head is set, behind those ftile0 [cap + 1] |
-// otile0 [cap + 1] | dseg [cap][kDepthSegInts] (kernels.h).  One buffer, one upload; a new table goes in here.
+// otile0 [cap + 1] | dseg [cap][kDepthSegInts] and, while u8 sources are on (vitx_pack_u8_set), behind those ptile0 [cap + 1] | pseg [cap][kPpSegInts]
+// (kernels.h).  One buffer, one upload; a new table goes in here.
 struct PackLayout {
     size_t cap;
     bool dense, depth;                   // the heads whose tables the buffer holds
+    bool u8 = false;                     // the u8 preprocessing's tables too
     size_t row0() const { return 0; }
     size_t qb0() const { return row0() + cap + 1; }
     size_t toff() const { return qb0() + cap + 1; }
@@ -24,7 +27,9 @@ struct PackLayout {
     size_t ftile0() const { return dense ? seg() + cap * kDenseSegInts : tile0(); }
     size_t otile0() const { return ftile0() + cap + 1; }
     size_t dseg() const { return otile0() + cap + 1; }
-    size_t ints() const { return depth ? dseg() + cap * kDepthSegInts : ftile0(); }
+    size_t ptile0() const { return depth ? dseg() + cap * kDepthSegInts : ftile0(); }
+    size_t pseg() const { return ptile0() + cap + 1; }
+    size_t ints() const { return u8 ? pseg() + cap * kPpSegInts : ptile0(); }
 };
 
 // What the host-only checks of a forward call (packed_forward.cpp check_call) give the forward: made once per call, before its first device call
@@ -41,6 +46,23 @@ struct PackCall {
     std::vector<int64_t> dpix0, dfine0;
     std::vector<int32_t> ftile0, otile0;
     int dcells = 0;
+    // with u8 sources declared for the call (kernels.h pp_pack_tables): the running tile count of the preprocessing launch, its table rows, its LDS
+    // and the bytes of the sources
+    bool u8 = false;
+    std::vector<int32_t> ptile0, pseg;
+    int plds = 0;
+    int64_t src_bytes = 0;
+};
+
+// u8 sources (vitx_pack_u8_set): the description, the device staging of the host entry point and the declaration of the next call
+struct PackU8 {
+    vitx_preproc pp;
+    size_t max_src_bytes = 0;
+    DevMem src;                          // max_src_bytes rounded up to 4: the sources of vitx_pack_forward_u8 on the device
+    bool own_img = false;                // vitx_pack::img was allocated by the set (else by an earlier vitx_pack_forward: it stays when u8 goes off)
+    size_t bytes = 0;                    // what the set added to vitx_pack_scratch_bytes besides the tables
+    bool declared = false;               // vitx_pack_u8_sources: the next forward call's d_imgs are u8 sources of next_src [n][2] = (ny, nx)
+    std::vector<int32_t> next_src;
 };
 
 // One grid of the table cache: the position table resampled to gh x gw and the grid's place in the rotary arenas
@@ -73,7 +95,8 @@ struct vitx_pack {
     void *Z = nullptr;                   // [Bpad][D] operand type: the class rows through the final norm, Bpad = max_images rounded up
     float *logits = nullptr, *probs = nullptr;      // [Bpad][C_pad], [max_images][C] f32
     float *logits_out = nullptr;         // [max_images][C] f32: the dense logits of the host entry point
-    float *img = nullptr;                // the host entry point's pixels on the device (allocated by its first call)
+    float *img = nullptr;                // the host entry point's pixels on the device (allocated by its first call, or by vitx_pack_u8_set: the u8
+                                         // preprocessing writes them there)
     int *tab = nullptr;                  // the segment tables of a call (PackLayout)
     std::vector<int> host;               // the same on the host: the staging buffer of the upload
     std::vector<int32_t> row0;           // PackCall::row0 of the last call that passed its checks (vitx_pack_feat_read, vitx_pack_dense_read)
@@ -95,9 +118,10 @@ struct vitx_pack {
     int feat_n = 0;                      // images of the last forward with features on (0: none)
     std::unique_ptr<PackDense> dense;    // vitx_pack_dense_set (null: off); its device memory is its own
     std::unique_ptr<PackDepth> depth;    // vitx_pack_depth_set (null: off); its device memory is its own
+    std::unique_ptr<PackU8> u8;          // vitx_pack_u8_set (null: off)
     int launches = 0, pe_launches = 0;   // kernel launches of the last forward, and how many of them were patch embeddings
     size_t scratch_bytes = 0;            // device bytes of activation scratch and tables held now
-    PackLayout layout() const { return PackLayout{(size_t)max_images, (bool)dense, (bool)depth}; }
+    PackLayout layout() const { return PackLayout{(size_t)max_images, (bool)dense, (bool)depth, (bool)u8}; }
     // image i of the last call that passed its checks: its patch rows, and where they start in an output that holds every image's patch rows end to end
     size_t patch_rows(int i) const { return (size_t)(row0[i + 1] - row0[i] - Tp); }
     size_t patch_at(int i) const { return (size_t)(row0[i] - i * Tp); }
@@ -120,3 +144,7 @@ struct vitx_pack {
 PackGrid *find_grid(vitx_pack *p, int gh, int gw);
 int wait_done(vitx_pack *p);
 int resolve_grids(vitx_pack *p, const std::vector<uint64_t> &want, hipStream_t st);
+// Before buffers and tables change hands (the set calls): nothing of this context is in flight.  resize_tables: the segment tables with the parts
+// that will be set behind them (PackLayout), a fresh zeroed buffer in place of the old one.
+int pack_quiesce(vitx_pack *p);
+int resize_tables(vitx_pack *p, const char *api, bool dense, bool depth, bool u8);

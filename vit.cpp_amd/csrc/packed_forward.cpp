@@ -4,7 +4,8 @@
 // rotary embeddings by a segment table (rope.hip) and the class-row gather (text_embed.hip).  The patch embedding is the rectangular context's
 // kernel, one launch per run of consecutive images of one shape.  The opt-in heads are the dense and the depth head (packed_outputs.cpp): the operand rows
 // and the head GEMM over all rows of the pack, then the label launch (dense_label.hip) or the fine and resize launches (depth_map.hip) by their own
-// segment tables, one map per image at its own size.  No LayerNorm fusion, no class-token tail.
+// segment tables, one map per image at its own size.  With u8 sources declared for a call (packed_input.cpp) one launch in front of the patch embedding
+// stretches every source to its image's shape into the context's pixel buffer (image_preprocess.hip).  No LayerNorm fusion, no class-token tail.
 #include <algorithm>
 
 #include "depth_bins.h"
@@ -86,6 +87,24 @@ int check_depth(const char *api, const vitx_model *m, const int32_t *shapes, con
     return VITX_OK;
 }
 
+// What a forward call adds while u8 sources are declared for it (vitx_pack_u8_check's text; `shapes` has passed check_shapes): the sources' shapes
+// [n_src][2] = (ny, nx) against the call, the tables (pp_pack_tables: its refusals) and the bytes against max_src_bytes (0: no bound).  On success the
+// preprocessing's tables of the call: c->ptile0, pseg, plds, src_bytes.
+int check_u8(const char *api, const vitx_preproc &pp, const int32_t *src_shapes, int n_src, const int32_t *shapes, int n, size_t max_src_bytes, PackCall *c, int64_t *src0) {
+    if (!src_shapes) { set_error("%s: NULL argument", api); return VITX_ERR_ARG; }
+    if (n_src != n) { set_error("%s: u8 sources were declared for %d images, the call has %d", api, n_src, n); return VITX_ERR_ARG; }
+    std::vector<int64_t> s0((size_t)n + 1);
+    c->ptile0.resize((size_t)n + 1); c->pseg.resize((size_t)n * kPpSegInts);
+    if (const int rc = pp_pack_tables(api, pp, src_shapes, shapes, n, s0.data(), nullptr, c->ptile0.data(), c->pseg.data(), &c->plds)) return rc;
+    if (max_src_bytes && (uint64_t)s0[n] > (uint64_t)max_src_bytes) {
+        set_error("%s: the call's sources hold %lld bytes, above max_src_bytes = %zu", api, (long long)s0[n], max_src_bytes);
+        return VITX_ERR_ARG;
+    }
+    c->src_bytes = s0[n]; c->u8 = true;
+    if (src0) std::copy(s0.begin(), s0.end(), src0);
+    return VITX_OK;
+}
+
 // the distinct grids of a call, in order of first appearance, as (gh << 32 | gw)
 std::vector<uint64_t> distinct_grids(const int32_t *shapes, int n, int P) {
     std::vector<uint64_t> g;
@@ -97,21 +116,28 @@ std::vector<uint64_t> distinct_grids(const int32_t *shapes, int n, int P) {
 }
 
 // THE check of a forward call, for both entry points: everything the call can be refused for, before its first device call.  It consumes
-// vitx_pack_dense_out's and vitx_pack_depth_out's shapes, passed or refused, and touches nothing else of the context: a refused call leaves row0 and the head's tables of the last
-// forward that ran (vitx_pack_feat_read, vitx_pack_dense_read) alone.
-int check_call(vitx_pack *p, const int32_t *shapes, int n, PackCall *c) {
+// vitx_pack_dense_out's and vitx_pack_depth_out's shapes and vitx_pack_u8_sources's declaration, passed or refused, and touches nothing else of the context: a refused
+// call leaves row0 and the head's tables of the last forward that ran (vitx_pack_feat_read, vitx_pack_dense_read) alone.  d_imgs is only looked at, never read.
+int check_call(vitx_pack *p, const void *d_imgs, const int32_t *shapes, int n, PackCall *c) {
     int rc;
     PackDense *dn = p->dense.get();
     PackDepth *dp = p->depth.get();
-    std::vector<int32_t> next_out, next_depth;
+    PackU8 *u8 = p->u8.get();
+    std::vector<int32_t> next_out, next_depth, next_src;
     if (dn) next_out.swap(dn->next_out);
     if (dp) next_depth.swap(dp->next_out);
+    const bool from_u8 = u8 && u8->declared;
+    if (from_u8) { next_src.swap(u8->next_src); u8->declared = false; }
     c->row0.resize((size_t)p->max_images + 1);
     if ((rc = check_shapes("vitx_pack_forward", p->model, shapes, n, p->max_tokens, p->max_images, c->row0.data()))) return rc;
     c->want = distinct_grids(shapes, n, p->P);
     if (c->want.size() > (size_t)p->max_grids) { set_error("vitx_pack_forward: the call names %d distinct grids, the table cache holds max_grids = %d", (int)c->want.size(), p->max_grids); return VITX_ERR_ARG; }
     if (dn && (rc = check_dense("vitx_pack_forward", p->model, shapes, next_out.empty() ? nullptr : next_out.data(), (int)(next_out.size() / 2), n, dn->K, dn->max_pixels, c))) return rc;
-    if (dp) rc = check_depth("vitx_pack_forward", p->model, shapes, next_depth.empty() ? nullptr : next_depth.data(), (int)(next_depth.size() / 2), n, dp->K, dp->u, dp->max_pixels, c);
+    if (dp && (rc = check_depth("vitx_pack_forward", p->model, shapes, next_depth.empty() ? nullptr : next_depth.data(), (int)(next_depth.size() / 2), n, dp->K, dp->u, dp->max_pixels, c))) return rc;
+    if (from_u8) {
+        if ((uintptr_t)d_imgs & 3) { set_error("vitx_pack_forward: the u8 sources must be 4-byte aligned"); return VITX_ERR_ARG; }
+        rc = check_u8("vitx_pack_forward", u8->pp, next_src.data(), (int)(next_src.size() / 2), shapes, n, u8->max_src_bytes, c, nullptr);
+    }
     return rc;
 }
 
@@ -123,7 +149,7 @@ int pack_gemm(vitx_pack *p, int epi, const GemmArgs &a, hipStream_t st) {
 
 // A call that passed check_call: its rows and tables take the place of the last forward's, its grids are resolved; then the segment tables go up in
 // one copy, then the launches
-int pack_forward(vitx_pack *p, PackCall &c, const float *d_imgs, const int32_t *shapes, int n, float *d_probs, float *d_logits, hipStream_t st) {
+int pack_forward(vitx_pack *p, PackCall &c, const void *d_imgs, const int32_t *shapes, int n, float *d_probs, float *d_logits, hipStream_t st) {
     int rc;
     PackDense *dn = p->dense.get();
     PackDepth *dp = p->depth.get();
@@ -165,13 +191,25 @@ int pack_forward(vitx_pack *p, PackCall &c, const float *d_imgs, const int32_t *
         std::copy(dp->otile0.begin(), dp->otile0.end(), p->host.data() + at.otile0());
         depth_pack_seg(dp->grids.data(), dp->outs.data(), lrow.data(), orow.data(), dp->fine0.data(), dp->pix0.data(), n, dp->u, p->host.data() + at.dseg());
     }
+    // the u8 preprocessing's (check_call built them)
+    if (c.u8) {
+        std::copy(c.ptile0.begin(), c.ptile0.end(), p->host.data() + at.ptile0());
+        std::copy(c.pseg.begin(), c.pseg.end(), p->host.data() + at.pseg());
+    }
     HIP_TRY(hipMemcpyAsync(p->tab, p->host.data(), p->host.size() * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(p->uploaded, st));
     p->uploaded_pending = true;
     const int *d_row0 = p->tab + at.row0(), *d_qb0 = p->tab + at.qb0(), *d_toff = p->tab + at.toff();
+    // u8 sources: ONE launch stretches every source to its image's own shape into the context's pixel buffer, which the forward below reads
+    const float *px = (const float *)d_imgs;
+    if (c.u8) {
+        const hipError_t e = launch_preprocess_pack(p->u8->pp, d_imgs, p->img, p->tab + at.ptile0(), p->tab + at.pseg(), n, c.ptile0[n], c.plds, st);
+        if (e != hipSuccess) { set_error("vitx_pack_forward: the u8 preprocessing: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
+        ++p->launches;
+        px = p->img;
+    }
     // patch embedding: one launch of the rectangular context's kernel per run of consecutive images of one shape, at the run's rows of X with the
     // position table of its grid -- the rows a rectangular context of that shape computes
-    const float *px = d_imgs;
     for (int i = 0; i < n;) {
         const int h = shapes[2 * i], w = shapes[2 * i + 1];
         int j = i + 1;
@@ -285,15 +323,16 @@ int vitx_pack_depth_check(const vitx_model *m, const int32_t *shapes, const int3
 int vitx_pack_forward_device(vitx_pack *p, const void *d_imgs, const int32_t *shapes, int n, void *d_probs, void *d_logits, void *stream) {
     if (!p || !d_imgs || !shapes || !d_probs) { set_error("vitx_pack_forward_device: NULL argument"); return VITX_ERR_ARG; }
     PackCall c;
-    if (const int rc = check_call(p, shapes, n, &c)) return rc;
-    return pack_forward(p, c, (const float *)d_imgs, shapes, n, (float *)d_probs, (float *)d_logits, stream ? (hipStream_t)stream : p->stream);
+    if (const int rc = check_call(p, d_imgs, shapes, n, &c)) return rc;
+    return pack_forward(p, c, d_imgs, shapes, n, (float *)d_probs, (float *)d_logits, stream ? (hipStream_t)stream : p->stream);
 }
 
 int vitx_pack_forward(vitx_pack *p, const float *imgs, const int32_t *shapes, int n, float *probs, float *logits) {
     if (!p || !imgs || !shapes || !probs) { set_error("vitx_pack_forward: NULL argument"); return VITX_ERR_ARG; }
     int rc;
     PackCall c;
-    if ((rc = check_call(p, shapes, n, &c))) return rc;        // before the pixels go up
+    if ((rc = check_call(p, imgs, shapes, n, &c))) return rc;  // before the pixels go up
+    if (c.u8) { set_error("vitx_pack_forward: u8 sources were declared for this call (vitx_pack_u8_sources): it takes vitx_pack_forward_device or vitx_pack_forward_u8"); return VITX_ERR_ARG; }
     HIP_TRY(hipSetDevice(p->device));
     if (!p->img) {       // the pixels of a full pack: max_tokens patches
         const size_t bytes = (size_t)p->max_tokens * p->P * p->P * 3 * 4;
@@ -307,6 +346,35 @@ int vitx_pack_forward(vitx_pack *p, const float *imgs, const int32_t *shapes, in
     HIP_TRY(hipMemcpyAsync(probs, p->probs, (size_t)n * p->C * 4, hipMemcpyDeviceToHost, p->stream));
     if (logits) HIP_TRY(hipMemcpyAsync(logits, p->logits_out, (size_t)n * p->C * 4, hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
+    return VITX_OK;
+}
+
+// u8 sources: the host entry point -- vitx_pack_forward's shape on u8.  The declaration is made here and consumed by check_call, like any other.
+int vitx_pack_forward_u8(vitx_pack *p, const uint8_t *srcs, const int32_t *src_shapes, const int32_t *shapes, int n, float *probs, float *logits) {
+    if (!p || !srcs || !src_shapes || !shapes || !probs) { set_error("vitx_pack_forward_u8: NULL argument"); return VITX_ERR_ARG; }
+    int rc;
+    if ((rc = vitx_pack_u8_sources(p, src_shapes, n))) return rc;
+    PackCall c;
+    if ((rc = check_call(p, p->u8->src.p, shapes, n, &c))) return rc;        // before the sources go up
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipMemcpyAsync(p->u8->src.p, srcs, (size_t)c.src_bytes, hipMemcpyHostToDevice, p->stream));
+    if ((rc = pack_forward(p, c, p->u8->src.p, shapes, n, p->probs, logits ? p->logits_out : nullptr, p->stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(probs, p->probs, (size_t)n * p->C * 4, hipMemcpyDeviceToHost, p->stream));
+    if (logits) HIP_TRY(hipMemcpyAsync(logits, p->logits_out, (size_t)n * p->C * 4, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return VITX_OK;
+}
+
+int vitx_pack_u8_check(const vitx_model *m, const vitx_preproc *pp, const int32_t *src_shapes, const int32_t *shapes, int n, size_t max_src_bytes, int64_t *src0,
+                       int32_t *tile0, int *lds) {
+    // max_tokens / max_images: whatever holds the call -- their refusals are vitx_pack_check's
+    if (const int rc = check_shapes("vitx_pack_u8_check", m, shapes, n, 0x7fffffff, n, nullptr)) return rc;
+    vitx_preproc own;
+    if (!pp) { if (const int rc = vitx_model_preproc(m, &own)) return rc; pp = &own; }
+    PackCall c;
+    if (const int rc = check_u8("vitx_pack_u8_check", *pp, src_shapes, n, shapes, n, max_src_bytes, &c, src0)) return rc;
+    if (tile0) std::copy(c.ptile0.begin(), c.ptile0.end(), tile0);
+    if (lds) *lds = c.plds;
     return VITX_OK;
 }
 

@@ -5,30 +5,6 @@
 
 #include "packed_context.h"
 
-namespace {
-
-// nothing of this context is in flight while buffers and tables change hands
-int pack_quiesce(vitx_pack *p) {
-    if (p->uploaded_pending) { HIP_TRY(hipEventSynchronize(p->uploaded)); p->uploaded_pending = false; }
-    return wait_done(p);
-}
-
-// the segment tables with the parts of the heads that will be set behind them (PackLayout): a fresh zeroed buffer in place of the old one
-int resize_tables(vitx_pack *p, const char *api, bool dense, bool depth) {
-    const size_t ints = PackLayout{(size_t)p->max_images, dense, depth}.ints();
-    if (p->host.size() == ints) return VITX_OK;
-    int *t = nullptr;
-    HIP_TRY(hipMalloc((void **)&t, ints * 4));
-    if (const hipError_t e = hipMemset(t, 0, ints * 4); e != hipSuccess) { (void)hipFree(t); set_error("%s: %s", api, hipGetErrorString(e)); return VITX_ERR_HIP; }
-    std::replace(p->allocs.begin(), p->allocs.end(), (void *)p->tab, (void *)t);
-    (void)hipFree(p->tab);
-    p->scratch_bytes += ints * 4; p->scratch_bytes -= p->host.size() * 4;
-    p->tab = t; p->host.assign(ints, 0);
-    return VITX_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int vitx_pack_feat_enable(vitx_pack *p, int flags) {
@@ -80,7 +56,7 @@ int vitx_pack_dense_set(vitx_pack *p, const float *W, const float *bias, int K, 
     if (const int rc = pack_quiesce(p)) return rc;
     if (off) {
         if (p->dense) { p->scratch_bytes -= p->dense->bytes; p->dense.reset(); }
-        return resize_tables(p, "vitx_pack_dense_set", false, (bool)p->depth);
+        return resize_tables(p, "vitx_pack_dense_set", false, (bool)p->depth, (bool)p->u8);
     }
     auto dn = std::make_unique<PackDense>();
     dn->K = K; dn->Kpad = (int)Kpad; dn->Dc = Dc; dn->mask = mask; dn->flags = flags; dn->cap = p->max_images; dn->max_pixels = max_pixels;
@@ -95,7 +71,7 @@ int vitx_pack_dense_set(vitx_pack *p, const float *W, const float *bias, int K, 
     HIP_TRY(dense_head_upload(*dn, p->dtype, W, bias));
     HIP_TRY(hipMemset(dn->a[0].p, 0, Mp * Dc * 2));
     HIP_TRY(hipDeviceSynchronize());
-    if (const int rc = resize_tables(p, "vitx_pack_dense_set", true, (bool)p->depth)) return rc;
+    if (const int rc = resize_tables(p, "vitx_pack_dense_set", true, (bool)p->depth, (bool)p->u8)) return rc;
     if (p->dense) p->scratch_bytes -= p->dense->bytes;
     p->scratch_bytes += dn->bytes;
     p->dense = std::move(dn);
@@ -153,7 +129,7 @@ int vitx_pack_depth_set(vitx_pack *p, const float *Wp, const float *Wc, const fl
     if (const int rc = pack_quiesce(p)) return rc;
     if (off) {
         if (p->depth) { p->scratch_bytes -= p->depth->bytes; p->depth.reset(); }
-        return resize_tables(p, "vitx_pack_depth_set", (bool)p->dense, false);
+        return resize_tables(p, "vitx_pack_depth_set", (bool)p->dense, false, (bool)p->u8);
     }
     auto dp = std::make_unique<PackDepth>();
     dp->K = K; dp->Kpad = (int)Kpad; dp->Dc = Dc; dp->mask = mask; dp->flags = flags; dp->cap = p->max_images; dp->max_pixels = max_pixels;
@@ -182,7 +158,7 @@ int vitx_pack_depth_set(vitx_pack *p, const float *Wp, const float *Wc, const fl
     HIP_TRY(hipMemset(dp->a[0].p, 0, Mp * Dc * 2));
     if (Wc) HIP_TRY(hipMemset(dp->ac[0].p, 0, Bp * Dc * 2));
     HIP_TRY(hipDeviceSynchronize());
-    if (const int rc = resize_tables(p, "vitx_pack_depth_set", (bool)p->dense, true)) return rc;
+    if (const int rc = resize_tables(p, "vitx_pack_depth_set", (bool)p->dense, true, (bool)p->u8)) return rc;
     if (p->depth) p->scratch_bytes -= p->depth->bytes;
     p->scratch_bytes += dp->bytes;
     p->depth = std::move(dp);
