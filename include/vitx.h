@@ -1266,10 +1266,46 @@ int vitx_op_attention_generic(int dtype, const void *d_qkv, void *d_out, int n_i
  *                              output tile), found by a binary search of the workgroup index in the running tile count: a 1-D grid.  The
  *                              refusals above.  TEST entry point: it runs on the null stream, builds and uploads the tables and frees them after
  *                              the launch (synchronises).
- * Not offered on packed contexts (each a later step): the other opt-in heads (attention maps, zero-shot bank, gallery), the pooled
+ *
+ * Attention maps on a pack (vitx_pack_attn_enable): "attention maps and attention rollout" above, word for word and per image.  Image i has N_i = T +
+ * gh_i gw_i tokens; its class-token map of a selected layer is [H][N_i], its rollout row [N_i]; index 0 is the class token, then the registers, then
+ * the patches in raster order of ITS OWN grid.  q and k are what the pack's QKV buffer holds after the layer's qkv GEMM (and, for a file with `rope`,
+ * after the rotary launch): the point where an image context reads them.  A packed context has no parity planes.  vitx_pack_attn_enable(p,
+ * layer_mask, flags, max_sq_tokens): vitx_attn_enable's mask and flags; mask 0 with flags 0 = off, the buffers are freed and vitx_pack_scratch_bytes
+ * returns to its value before.  VITX_ATTN_ROLLOUT keeps two matrix arenas of max_sq_tokens floats each -- a call's matrices, N_i x N_i per image, lie
+ * end to end in them -- and needs 1 <= max_sq_tokens <= 2^31 - 1.  VITX_ERR_ARG, before any device call: mask bits at or beyond L, unknown flags, a
+ * bad max_sq_tokens.  Buffers: the maps, max_tokens * vitx_pack_attn_floats f32; with rollout the two arenas and, when the last layer is not
+ * selected, max_tokens * H f32 for its class maps; all count in vitx_pack_scratch_bytes.  A refused or failed enable leaves the maps that were on.
+ * Waits for the context's last forward.  vitx_pack_attn_floats: floats per TOKEN = popcount(mask) * H + (rollout ? 1 : 0).  Per forward, in front of
+ * each layer's attention launch, the image forward's sequence on the packed kernels below: the class maps of a selected layer (1 launch); with
+ * rollout the factor into arena l & 1 (L - 1 launches), the in-place step for 0 < l < L - 1 (max(L - 2, 0)), and on the last layer its class maps
+ * (one launch more when it is not selected) and the row (1): all counted by vitx_pack_launches; the two tables of the rollout launches ride in the
+ * call's one table upload.  With maps off nothing is launched or allocated.  Probabilities, logits, features and both heads keep their bits with
+ * maps on: the kernels only read QKV.  Refused before the call's first device call with rollout on, nothing launched or written, the last forward's
+ * maps still readable: VITX_ERR_UNSUPPORTED for an image above 1024 tokens (the text names the image), VITX_ERR_ARG when the call's sum of N_i^2
+ * exceeds max_sq_tokens.  vitx_pack_attn_check is that text and the enable's argument checks, host only; it returns rblk0 [n + 1] (the running
+ * count of ceil(N_i / 16), the work items of the factor and the step) and sq0 [n + 1] (the running sum of N_i^2: image i's matrix starts at float
+ * sq0[i] of an arena); either may be NULL.  vitx_pack_attn_read (waits for the forward): the last forward's images end to end, image i at float
+ * row0[i] * vitx_pack_attn_floats: the selected layers in ascending order, each [H][N_i], then the rollout row [N_i]; VITX_ERR_ARG before any
+ * forward with maps on or when n_floats is below row0[n] * vitx_pack_attn_floats.  vitx_pack_attn_device: the device buffer in that layout (NULL
+ * while off).  An image's maps and rollout row are a function of its own pixels and shape: the same bits alone, at any position and beside any
+ * neighbours (the launches' register tiles and LDS pitch come from the call's widest image; key tiles beyond N_i are skipped or masked and add exact
+ * zeros, the step's k loop ends at N_i, so no bit depends on them); a pack of one shape gives the maps of a rectangular context of that shape
+ * wherever both hold the same q and k (any head dim but 64, see above).
+ *   The kernels on a pack, TEST entry points: row0 [n + 1] is a HOST table (ascending, N_i >= 1); each call builds and uploads its
+ *   tables, launches on the NULL STREAM and returns after synchronising -- they take no stream.  Image i has the bits of the fixed-shape entry point
+ *   on that image alone.  A null pointer, n <= 0 or a table that does not ascend: VITX_ERR_ARG; an image above 1024 tokens where a matrix is involved:
+ *   VITX_ERR_UNSUPPORTED.
+ *   vitx_op_attention_map_packed  d_qkv [rows][3 D] -> d_cls (or NULL), image i's [H][N_i] class maps at float row0[i] * H, and d_mean (or NULL), its
+ *                              [N_i][N_i] mean_h A_h at float sq0[i] = sum_(j < i) N_j^2; half_identity != 0: the rollout factor instead
+ *                              (vitx_op_rollout_factor's entry).  Nothing else is written.
+ *   vitx_op_rollout_step_packed   d_a <- d_a . d_r per image, both with image i's matrix at float sq0[i]; ranges that overlap: VITX_ERR_ARG.
+ *   vitx_op_rollout_row_packed    d_cls as above, d_r (or NULL) as above -> d_out, image i's row [N_i] at float row0[i].
+ * Not offered on packed contexts (each a later step): the other opt-in heads (zero-shot bank, gallery), the pooled
  * and attention-pooling heads, the F16 parity planes, LayerNorm fusion and sub-batch streams, a packed patch-embedding kernel, vitx_group_*;
  * of the dense and the depth head: downsampling, and a vit.h wrapper; of the u8 sources: crops and shortest-edge geometry (a source is stretched
- * to the given shape), the REF filters, JPEG decode on the device, and a vit.h wrapper. */
+ * to the given shape), the REF filters, JPEG decode on the device, and a vit.h wrapper; of the attention maps: full N x N maps as an output, rollout
+ * above 1024 tokens per image, and a vit.h wrapper. */
 typedef struct vitx_pack vitx_pack;
 typedef struct { int pos_interp, max_grids, reserved[6]; } vitx_pack_options;
 int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_images, int dtype, const vitx_pack_options *opt, vitx_pack **out);
@@ -1334,6 +1370,18 @@ int vitx_pack_u8_check(const vitx_model *m, const vitx_preproc *pp, const int32_
 int vitx_pack_fit_shapes(const vitx_model *m, const int32_t *src_shapes, int n, int short_side, int max_long, int32_t *shapes);
 int vitx_op_preprocess_pack(const vitx_preproc *pp, const void *d_srcs, const int32_t *src_shapes /* host [n][2] */, const int32_t *out_shapes /* host [n][2] */,
                             int n, void *d_out);
+/* attention maps */
+int vitx_pack_attn_enable(vitx_pack *p, uint64_t layer_mask, int flags /* VITX_ATTN_ROLLOUT */, long max_sq_tokens /* rollout: the call's sum of N_i^2 at most */);
+int vitx_pack_attn_floats(const vitx_pack *p);             /* floats per token */
+int vitx_pack_attn_read(vitx_pack *p, float *out, size_t n_floats);
+const void *vitx_pack_attn_device(const vitx_pack *p);
+/* host only: the enable's argument checks and every refusal a forward call adds while maps are on */
+int vitx_pack_attn_check(const vitx_model *m, const int32_t *shapes, int n, uint64_t layer_mask, int flags, long max_sq_tokens,
+                         int32_t *rblk0 /* [n + 1] or NULL */, int32_t *sq0 /* [n + 1] or NULL */);
+int vitx_op_attention_map_packed(int dtype, const void *d_qkv, void *d_cls /* or NULL */, void *d_mean /* or NULL */, const int32_t *row0 /* host [n + 1] */, int n,
+                                 int D, int H, int half_identity);
+int vitx_op_rollout_step_packed(void *d_a, const void *d_r, const int32_t *row0 /* host [n + 1] */, int n);
+int vitx_op_rollout_row_packed(const void *d_cls, const void *d_r /* or NULL */, void *d_out, const int32_t *row0 /* host [n + 1] */, int n, int H);
 
 /* ---- MXFP8 operands (VITX_MXFP8, encoding above) ------------------------------- */
 /* Host encoder: x f32 [rows][K] -> q [rows][k_pad] e4m3 bytes + scales [rows][k_pad / 32] (k_pad >= K, a multiple of 32; columns

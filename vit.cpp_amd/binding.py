@@ -76,6 +76,8 @@ EXPORTS = [
     "vitx_pack_depth_set", "vitx_pack_depth_out", "vitx_pack_depth_check", "vitx_pack_depth_read", "vitx_pack_depth_device", "vitx_pack_depth_scratch_bytes",
     "vitx_op_depth_fine_packed", "vitx_op_depth_resize_packed", "vitx_depth_pack_tables", "vitx_op_depth_fine_packed_tables", "vitx_op_depth_resize_packed_tables",
     "vitx_pack_u8_set", "vitx_pack_u8_sources", "vitx_pack_forward_u8", "vitx_pack_u8_check", "vitx_pack_fit_shapes", "vitx_op_preprocess_pack",
+    "vitx_pack_attn_enable", "vitx_pack_attn_floats", "vitx_pack_attn_read", "vitx_pack_attn_device", "vitx_pack_attn_check",
+    "vitx_op_attention_map_packed", "vitx_op_rollout_step_packed", "vitx_op_rollout_row_packed",
 ]
 
 
@@ -372,6 +374,16 @@ def lib():
             L.vitx_pack_u8_check.argtypes = [vp, pp, i32p, i32p, ip, C.c_size_t, C.POINTER(C.c_int64), i32p, C.POINTER(ip)]
             L.vitx_pack_fit_shapes.argtypes = [vp, i32p, ip, ip, ip, i32p]
             L.vitx_op_preprocess_pack.argtypes = [pp, vp, i32p, i32p, ip, vp]
+        if hasattr(L, "vitx_pack_attn_enable"):
+            i32p = C.POINTER(C.c_int32)
+            L.vitx_pack_attn_enable.argtypes = [vp, C.c_uint64, ip, C.c_long]
+            L.vitx_pack_attn_floats.argtypes = [vp]
+            L.vitx_pack_attn_read.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t]
+            L.vitx_pack_attn_device.restype = C.c_void_p; L.vitx_pack_attn_device.argtypes = [vp]
+            L.vitx_pack_attn_check.argtypes = [vp, i32p, ip, C.c_uint64, ip, C.c_long, i32p, i32p]
+            L.vitx_op_attention_map_packed.argtypes = [ip, vp, vp, vp, i32p, ip, ip, ip, ip]
+            L.vitx_op_rollout_step_packed.argtypes = [vp, vp, i32p, ip]
+            L.vitx_op_rollout_row_packed.argtypes = [vp, vp, vp, i32p, ip, ip]
         _lib = L
     return _lib
 
@@ -1259,7 +1271,7 @@ class PackContext:
         probs = np.empty((n, self.model.num_classes), np.float32); logits = np.empty_like(probs)
         fp = C.POINTER(C.c_float)
         rc = lib().vitx_pack_forward(self._h, x.ctypes.data_as(fp), s.ctypes.data_as(C.POINTER(C.c_int32)), n, probs.ctypes.data_as(fp), logits.ctypes.data_as(fp))
-        self._dense_forward(s, rc == 0)
+        self._dense_forward(s, rc == 0); self._attn_forward(s, rc == 0)
         check(rc, "vitx_pack_forward")
         self._shapes = s
         return probs, logits
@@ -1276,7 +1288,7 @@ class PackContext:
         """Device pointers, host shapes; only enqueues on `stream` (0 = the context's own stream)."""
         s = _pack_shapes(shapes)
         rc = lib().vitx_pack_forward_device(self._h, d_imgs, s.ctypes.data_as(C.POINTER(C.c_int32)), s.shape[0], d_probs, d_logits or None, stream or None)
-        self._dense_forward(s, rc == 0)
+        self._dense_forward(s, rc == 0); self._attn_forward(s, rc == 0)
         check(rc, "vitx_pack_forward_device")
         self._shapes = s
 
@@ -1309,10 +1321,60 @@ class PackContext:
         fp, i32p = C.POINTER(C.c_float), C.POINTER(C.c_int32)
         rc = lib().vitx_pack_forward_u8(self._h, flat.ctypes.data_as(C.POINTER(C.c_uint8)), src.ctypes.data_as(i32p), s.ctypes.data_as(i32p), n,
                                         probs.ctypes.data_as(fp), logits.ctypes.data_as(fp))
-        self._dense_forward(s, rc == 0)
+        self._dense_forward(s, rc == 0); self._attn_forward(s, rc == 0)
         check(rc, "vitx_pack_forward_u8")
         self._shapes = s
         return probs, logits
+
+    def attn_enable(self, layers=None, rollout: bool = False, max_sq_tokens: int = 0) -> None:
+        """Attention maps of every later forward (vitx_pack_attn_enable), Context.attn_enable's arguments and meaning, per image on its own grid: the
+        class-token maps of `layers` (None = every layer, [] = none) and, with rollout=True, the attention-rollout row.  max_sq_tokens: the most
+        floats the rollout matrices of one call may hold, the sum of N_i^2 (0: max_tokens x min(max_tokens, 1024), whatever a call can name).
+        attn_enable([]) turns them off and frees the buffers."""
+        L = self.model.hparams.num_hidden_layers
+        sel = list(range(L)) if layers is None else sorted(set(int(l) for l in layers))
+        mask = _layer_mask(sel, span="0..63")
+        if rollout and not max_sq_tokens:
+            max_sq_tokens = min(self.max_tokens * min(self.max_tokens, 1024), 2 ** 31 - 1)
+        check(lib().vitx_pack_attn_enable(self._h, mask, ATTN_ROLLOUT if rollout else 0, int(max_sq_tokens)), "vitx_pack_attn_enable")
+        self._attn_layers, self._attn_rollout, self._attn_shapes = sel, bool(rollout), None
+
+    def attn_disable(self) -> None:
+        self.attn_enable([], rollout=False)
+
+    def attn_read(self):
+        """Maps of the last forward made with maps on: per image (cls [n_sel, H, N_i] f32, rollout [N_i] f32 or None), N_i = prefix + gh_i gw_i.  Index 0
+        of a map is the class token, then the register tokens, then the patches in raster order of the image's own grid (attn_grid reshapes)."""
+        sel, roll = getattr(self, "_attn_layers", []), getattr(self, "_attn_rollout", False)
+        s = getattr(self, "_attn_shapes", None)
+        hp = self.model.hparams
+        H, P, Tp = hp.num_attention_heads, hp.patch_size, self.model.num_prefix
+        fpt = lib().vitx_pack_attn_floats(self._h)
+        if s is None or fpt == 0:
+            # the library's own text (and its code) for a read before any forward with maps on
+            check(lib().vitx_pack_attn_read(self._h, np.empty(1, np.float32).ctypes.data_as(C.POINTER(C.c_float)), 0), "vitx_pack_attn_read")
+            raise VitxError("attn_read: no forward has run with attention maps on since attn_enable")
+        assert fpt == len(sel) * H + (1 if roll else 0)
+        toks = [Tp + (int(h) // P) * (int(w) // P) for h, w in s]
+        out = np.empty(sum(toks) * fpt, np.float32)
+        check(lib().vitx_pack_attn_read(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size), "vitx_pack_attn_read")
+        res, at = [], 0
+        for N in toks:
+            blk = out[at * fpt:(at + N) * fpt]
+            res.append((blk[:len(sel) * H * N].reshape(len(sel), H, N), blk[len(sel) * H * N:].copy() if roll else None))
+            at += N
+        return res
+
+    def attn_grid(self, i: int, m: np.ndarray) -> np.ndarray:
+        """[..., N_i] map of image i of the last forward with maps on -> [..., gh_i, gw_i]: drops the class token and the register tokens."""
+        P = self.model.hparams.patch_size
+        h, w = self._attn_shapes[i]
+        return np.asarray(m)[..., self.model.num_prefix:].reshape(*np.shape(m)[:-1], int(h) // P, int(w) // P)
+
+    @property
+    def attn_device(self) -> int:
+        """The device buffer of the maps (vitx_pack_attn_device), image i at float row0[i] * floats-per-token; 0 while off."""
+        return int(lib().vitx_pack_attn_device(self._h) or 0)
 
     def feat_enable(self, cls: bool = True, tokens: bool = False) -> None:
         """Last-layer features of every later forward (vitx_pack_feat_enable); neither: off."""
@@ -1366,6 +1428,11 @@ class PackContext:
         s = _pack_shapes(shapes)
         check(lib().vitx_pack_dense_out(self._h, s.ctypes.data_as(C.POINTER(C.c_int32)), s.shape[0]), "vitx_pack_dense_out")
         self._dense_out = s
+
+    def _attn_forward(self, s, ok: bool) -> None:
+        """Book-keeping of a forward call for attn_read: a call that ran with maps on fixed the shapes of its maps."""
+        if ok and (getattr(self, "_attn_layers", None) or getattr(self, "_attn_rollout", False)):
+            self._attn_shapes = s
 
     def _dense_forward(self, s, ok: bool) -> None:
         """Book-keeping of a forward call for dense_read and depth_read: the call consumed dense_out's and depth_out's shapes; a call that ran fixed the
@@ -1513,6 +1580,52 @@ class PackContext:
 def op_attention_packed(dtype: int, d_qkv: int, d_out: int, d_row0: int, n: int, D: int, H: int, stream: int = 0) -> None:
     """vitx_op_attention_packed: attention over a pack, image i = rows row0[i] .. row0[i + 1] - 1 (d_row0 int32 [n + 1] on the device)."""
     check(lib().vitx_op_attention_packed(dtype, d_qkv, d_out, d_row0, n, D, H, stream or None), "vitx_op_attention_packed")
+
+
+def pack_attn_check(model: Model, shapes, layers=None, rollout: bool = False, max_sq_tokens: int = 0, *, layer_mask: Optional[int] = None, flags: Optional[int] = None):
+    """vitx_pack_attn_check (host only): (rblk0 int32 [n + 1], sq0 int32 [n + 1]) of a packed forward of `shapes` [n][2] with attention maps on, or VitxError
+    for what vitx_pack_attn_enable refuses in its arguments (ERR_ARG) and what such a call is refused for (ERR_UNSUPPORTED above 1024 tokens with rollout,
+    ERR_ARG above max_sq_tokens).  layer_mask / flags: the raw arguments, for the refusals the keyword form cannot express."""
+    a = _pack_shapes(shapes)
+    n = a.shape[0]
+    if layer_mask is None:
+        L = model.hparams.num_hidden_layers
+        layer_mask = _layer_mask(list(range(L)) if layers is None else sorted(set(int(l) for l in layers)), span="0..63")
+    if flags is None:
+        flags = ATTN_ROLLOUT if rollout else 0
+    i32p = C.POINTER(C.c_int32)
+    rblk0, sq0 = np.zeros(n + 1, np.int32), np.zeros(n + 1, np.int32)
+    check(lib().vitx_pack_attn_check(model._h, a.ctypes.data_as(i32p), n, layer_mask, flags, int(max_sq_tokens), rblk0.ctypes.data_as(i32p), sq0.ctypes.data_as(i32p)),
+          "vitx_pack_attn_check")
+    return rblk0, sq0
+
+
+def _row0(row0) -> np.ndarray:
+    r = np.ascontiguousarray(row0, np.int32)
+    if r.ndim != 1 or r.size < 2:
+        raise ValueError("row0 is [n + 1]")
+    return r
+
+
+def op_attention_map_packed(dtype: int, d_qkv: int, d_cls: int, d_mean: int, row0, D: int, H: int, half_identity: bool = False) -> None:
+    """vitx_op_attention_map_packed (test only; null stream, synchronous): the class-token maps and / or the head mean (half_identity: the rollout factor) of a
+    pack, host row0 [n + 1].  d_cls: image i's [H, N_i] at float row0[i] * H; d_mean: its [N_i, N_i] at float sum_(j < i) N_j^2; either may be 0."""
+    r = _row0(row0)
+    check(lib().vitx_op_attention_map_packed(dtype, d_qkv or None, d_cls or None, d_mean or None, r.ctypes.data_as(C.POINTER(C.c_int32)), r.size - 1, D, H,
+                                             1 if half_identity else 0), "vitx_op_attention_map_packed")
+
+
+def op_rollout_step_packed(d_a: int, d_r: int, row0) -> None:
+    """vitx_op_rollout_step_packed (test only; synchronous): a_i <- a_i . r_i per image of a pack, image i's matrices at float sum_(j < i) N_j^2 of both."""
+    r = _row0(row0)
+    check(lib().vitx_op_rollout_step_packed(d_a or None, d_r or None, r.ctypes.data_as(C.POINTER(C.c_int32)), r.size - 1), "vitx_op_rollout_step_packed")
+
+
+def op_rollout_row_packed(d_cls: int, d_r: int, d_out: int, row0, H: int) -> None:
+    """vitx_op_rollout_row_packed (test only; synchronous): the last rollout factor's row per image of a pack; d_cls as op_attention_map_packed writes it,
+    d_r as op_rollout_step_packed (0: the row itself), d_out: image i's row [N_i] at float row0[i]."""
+    r = _row0(row0)
+    check(lib().vitx_op_rollout_row_packed(d_cls or None, d_r or None, d_out or None, r.ctypes.data_as(C.POINTER(C.c_int32)), r.size - 1, H), "vitx_op_rollout_row_packed")
 
 
 def pack_dense_check(model: Model, shapes, out_shapes, K: int, max_pixels: int):

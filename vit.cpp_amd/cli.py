@@ -8,6 +8,7 @@ directory-walk accuracy harness:
     python vit_cli.py -m model.gguf ... --img-size 384 [--pos-interp bicubic|bicubic-aa]   # run at another input size than the file's
     python vit_cli.py -m model.gguf ... --img-shape 224x448 | --img-fit 224   # a rectangular context: HxW, or the aspect-preserving shape of the input image
     python vit_cli.py -m model.gguf -i a.jpg,b.jpg,c.jpg --pack --img-fit 224   # several images, each at its own aspect-preserving shape, in one packed forward
+    python vit_cli.py -m model.gguf -i a.jpg,b.jpg,c.jpg --pack --img-fit 224 --attn-map PREFIX [--attn-kind rollout|last]   # + PREFIX.<i>.pgm per image, on its own grid
     python vit_cli.py -m model.gguf -i a.jpg,b.jpg,c.jpg --pack --img-fit 224 --pack-u8   # the same, resized on the device from the u8 originals in one launch
     python vit_cli.py -m model.gguf ... [--preprocess model|reference]   # the file's own preprocessing (default) or the reference's for any file
     python vit_cli.py -m clip.gguf -i image.jpg -k 5 --zero-shot bank.npz   # zero-shot classes of a CLIP / SigLIP file (bank: convert.py --zero-shot-out)
@@ -76,7 +77,8 @@ def make_parser() -> argparse.ArgumentParser:
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--dir", default=None, help="accuracy harness: walk DIR/<label>/* and report top-1 against the directory name")
     ap.add_argument("--batch", type=int, default=256, help="images per forward in --dir mode")
-    ap.add_argument("--attn-map", default=None, metavar="PATH", help="with -i: write the image's attention map as a binary PGM (P5), img_size x img_size")
+    ap.add_argument("--attn-map", default=None, metavar="PATH", help="with -i: write the image's attention map as a binary PGM (P5), img_size x img_size; with --pack: a prefix, "
+                                                                                "PATH.<i>.pgm per image at its own packed shape")
     ap.add_argument("--attn-kind", default="rollout", choices=["rollout", "last"],
                     help="rollout: attention rollout through all layers; last: head mean of the last layer's class-token map")
     ap.add_argument("--embed", default=None, metavar="OUT.npy",
@@ -219,9 +221,9 @@ def main(argv: List[str] | None = None) -> int:
         ap.error("--img-fit takes its shape from the single image of -i, not --gallery-build (use --img-shape HxW)")
     if a.pack_u8 and not a.pack:
         ap.error("--pack-u8 goes with --pack")
-    if a.pack and (not a.img_fit or a.dir is not None or a.dtype == "mxfp8" or a.attn_map or a.embed or a.zero_shot or a.text_model or a.gallery or a.gallery_build):
-        ap.error("--pack takes --img-fit SHORT, the images of -i A.jpg,B.jpg,... and --dtype f16 or bf16; of the opt-in outputs a packed context has the dense head "
-                 "(--dense-head HEAD.npz --dense-out PREFIX) and the depth head (--depth-head HEAD.npz --depth-out PREFIX) only")
+    if a.pack and (not a.img_fit or a.dir is not None or a.dtype == "mxfp8" or a.embed or a.zero_shot or a.text_model or a.gallery or a.gallery_build):
+        ap.error("--pack takes --img-fit SHORT, the images of -i A.jpg,B.jpg,... and --dtype f16 or bf16; of the opt-in outputs a packed context has attention maps "
+                 "(--attn-map PREFIX), the dense head (--dense-head HEAD.npz --dense-out PREFIX) and the depth head (--depth-head HEAD.npz --depth-out PREFIX) only")
     if (a.img_shape or a.img_fit) and a.preprocess == "reference":
         ap.error("--preprocess reference resizes to squares only: not with --img-shape / --img-fit")
     rect = None                                          # (img_h, img_w) of a rectangular context
@@ -348,6 +350,11 @@ def main(argv: List[str] | None = None) -> int:
                 ctx.depth_set(depth["wp"], depth["wc"], depth["bias"], depth["bins"], depth["layers"], u, depth["min_depth"], depth["max_depth"],
                               max_pixels=sum(h * w for h, w in outs), norm=depth["norm"])
                 ctx.depth_out(outs)
+            if a.attn_map:
+                # where the model looked, per image on its own grid: the rollout row, or the head mean of the last layer's class-token maps
+                L, P, Tp = model.hparams.num_hidden_layers, model.hparams.patch_size, model.num_prefix
+                ctx.attn_enable([] if a.attn_kind == "rollout" else [L - 1], rollout=a.attn_kind == "rollout",
+                                max_sq_tokens=sum((Tp + (h // P) * (w // P)) ** 2 for h, w in shapes))
             if a.pack_u8:
                 ctx.u8_set(pp_rect, max_src_bytes=sum(im.size for im in imgs))
                 probs, _ = ctx.forward_u8(imgs, shapes)
@@ -355,11 +362,18 @@ def main(argv: List[str] | None = None) -> int:
                 probs, _ = ctx.forward_flat(pixels, shapes)
             maps = ctx.dense_read()[0] if dense else None
             dmaps = ctx.depth_read()[0] if depth else None
+            amaps = ctx.attn_read() if a.attn_map else None
         except binding.VitxError as e:
             print(f"main: the packed forward failed: {e}", file=sys.stderr)
             return 1
         for k, (f, (h, w), p) in enumerate(zip(files, shapes, probs)):
             print(f"main: '{f}' at ({w} x {h})", file=sys.stderr)
+            if a.attn_map:
+                cls, roll = amaps[k]
+                m, path = roll if a.attn_kind == "rollout" else cls[0].mean(axis=0), f"{a.attn_map}.{k}.pgm"
+                with open(path, "wb") as fo:
+                    fo.write(attn_pgm(ctx.attn_grid(k, m), (int(h), int(w))))
+                print(f"main: wrote the {a.attn_kind} attention map to '{path}'", file=sys.stderr)
             if depth:
                 dm, path = dmaps[k], f"{a.depth_out}.{k}.npy"
                 with open(path, "wb") as fo:

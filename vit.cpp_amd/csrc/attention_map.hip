@@ -11,272 +11,76 @@
 //   attn_rollout_step_kernel  R_l = A^_l R_(l-1) on v_mfma_f32_16x16x4_f32 (exact f32), in place over A^_l: a workgroup owns a block of
 //                          16 rows of A^_l and reads all of them into LDS before it writes any of them;
 //   attn_rollout_row_kernel   the last factor: row 0 of A^_(L-1) R_(L-2) from the last layer's class-token maps (a GEMV).
+// The bodies live in attention_map_tile.h.  Each kernel has a *_packed_kernel twin over the same body for a packed context (vitx_pack_attn_enable),
+// where image i has its own N_i = row0[i + 1] - row0[i]: the class map's and the row's work items are (image, head) and (image); the head mean's
+// and the step's are (image, 16-row block), found by a scalar binary search of the workgroup index in rblk0 [n + 1], the running count of
+// ceil(N_i / 16), and image i's N_i x N_i matrix starts at float sq0[i], the running sum of N_j^2.  1-D grids, no atomics, one writer per element.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
-#include "device_common.h"
+#include "attention_map_tile.h"
 #include "kernels.h"
 
 namespace vitx {
 namespace {
 
-// 8 consecutive operands -> f32 (PLANES: value = hi + lo / 2048 from the F16 parity mode's two planes, lo_off elements apart)
-template <typename T, bool PLANES>
-__device__ __forceinline__ void map_load8(const T *ptr, long lo_off, float (&f)[8]) {
-    typedef typename Elem<T>::v8 v8;
-    const v8 a = *(const v8 *)ptr;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] = (float)a[e];
-    if (PLANES) {
-        const v8 l = *(const v8 *)(ptr + lo_off);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) f[e] = __builtin_fmaf((float)l[e], kHiLoInv, f[e]);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Class-token map.  One workgroup of four waves per (image, head).  A row of the head's k slice is NP = hd / 8 pieces of 16 bytes; lanes are
-// grouped NPP (NP rounded up to a power of two) per row, lanes p >= NP idle, 64 / NPP rows per wave and step.
-//   pass 1: s_j = (q . k_j) * scale -> out[j] (by the group's lane 0), running maximum;
-//   pass 2: the same lane rewrites out[j] = expf(s_j - max) and sums;  pass 3: out[j] /= sum.
-// Each out[j] is written and re-read by one thread only: program order is the only ordering needed.
-// out row of head h of image b: out + b * img_stride + h * N.
-// ------------------------------------------------------------------------------------------------
 template <typename T, int NPP, bool PLANES>
 __global__ __launch_bounds__(256) void attn_cls_map_kernel(const T *__restrict__ qkv, long lo_off, float *__restrict__ out, long img_stride,
                                                           int N, int D, int H, int NP, float scale) {
-    __shared__ float red[8];
-    constexpr int G = 64 / NPP;
-    const int tid = threadIdx.x, lane = tid & 63, p = lane % NPP, g = lane / NPP, wave = tid >> 6;
+    const int item = blockIdx.x, b = item / H, h = item - b * H;      // out row of head h of image b: out + b * img_stride + h * N
+    map_cls_item<T, NPP, PLANES>(qkv + (size_t)b * N * ((size_t)3 * D), lo_off, out + (size_t)b * img_stride + (size_t)h * N, N, D, h, D / H, NP, scale);
+}
+// a pack: image b = rows row0[b] .. of qkv; its [H][N_b] maps start at float row0[b] * fpt + slot * H * N_b of out (fpt floats per token)
+template <typename T, int NPP>
+__global__ __launch_bounds__(256) void attn_cls_map_packed_kernel(const T *__restrict__ qkv, float *__restrict__ out, long fpt, int slot, const int *__restrict__ row0,
+                                                                 int D, int H, int NP, float scale) {
     const int item = blockIdx.x, b = item / H, h = item - b * H;
-    const int hd = D / H;
-    const size_t row_el = (size_t)3 * D;
-    const bool act = p < NP;
-    const T *qp = qkv + (size_t)b * N * row_el + (size_t)h * hd + p * 8;      // this lane's piece of q of token 0; k at + D
-    float *o = out + (size_t)b * img_stride + (size_t)h * N;
-    float q[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    if (act) map_load8<T, PLANES>(qp, lo_off, q);
-    float mx = -INFINITY;
-    for (int r0 = wave * G; r0 < N; r0 += 4 * G) {
-        const int r = r0 + g;
-        float k[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        if (act && r < N) map_load8<T, PLANES>(qp + D + (size_t)r * row_el, lo_off, k);
-        float s = 0.0f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s = __builtin_fmaf(q[e], k[e], s);
-#pragma unroll
-        for (int m = 1; m < NPP; m <<= 1) s += __shfl_xor(s, m);
-        s *= scale;
-        if (r < N) { mx = fmaxf(mx, s); if (p == 0) o[r] = s; }
-    }
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) mx = fmaxf(mx, __shfl_xor(mx, m));
-    if (lane == 0) red[wave] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    float sum = 0.0f;
-    if (p == 0)
-        for (int r = wave * G + g; r < N; r += 4 * G) { const float e = expf(o[r] - mx); o[r] = e; sum += e; }
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) sum += __shfl_xor(sum, m);
-    if (lane == 0) red[4 + wave] = sum;
-    __syncthreads();
-    sum = (red[4] + red[5]) + (red[6] + red[7]);
-    if (p == 0)
-        for (int r = wave * G + g; r < N; r += 4 * G) o[r] = o[r] / sum;
+    const int r0 = row0[b], N = row0[b + 1] - r0;
+    map_cls_item<T, NPP, false>(qkv + (size_t)r0 * ((size_t)3 * D), 0, out + (size_t)r0 * fpt + ((size_t)slot * H + h) * N, N, D, h, D / H, NP, scale);
 }
 
-// ------------------------------------------------------------------------------------------------
-// Head mean of the softmax rows of 16 queries.  One workgroup of four waves per (image, 16-row query block).  Per head: wave w owns the
-// key tiles t * 4 + w (16 keys each); S tile = mfma_16x16x32(A = Q[16 queries][32 dims], B = K^T[32 dims][16 keys]) over hd / 32 dim chunks
-// (dims beyond hd and keys beyond N are zeros), so lane l holds keys 16 tile + (l & 15) of queries 4 (l >> 4) + r, r = 0..3 (C/D map).
-// Row maxima and sums: shuffles over the 16 lanes of a query group, then the four waves through LDS.  The f32 probabilities are added to
-// per-lane accumulators that keep their (query, key) slots over all heads; out = acc / H (+ the rollout's 0.5 I when `half_identity`).
-// NT = key tiles per wave (N <= 64 NT).
-// ------------------------------------------------------------------------------------------------
 template <typename T, int NT, bool PLANES>
 __global__ __launch_bounds__(256) void attn_head_mean_kernel(const T *__restrict__ qkv, long lo_off, float *__restrict__ out, int N, int D, int H,
                                                             float scale, int half_identity) {
-    typedef typename Elem<T>::v8 v8;
-    __shared__ float red[2][4][16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, l4 = lane >> 4;
     const int qblocks = (N + 15) / 16;
     const int b = blockIdx.x / qblocks, q0 = (blockIdx.x - b * qblocks) * 16;
-    const int hd = D / H, nchunk = (hd + 31) / 32;
-    const size_t row_el = (size_t)3 * D;
-    const T *img = qkv + (size_t)b * N * row_el;
-    const v8 zero8 = {};
-    f32x4 acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    const int qrow = q0 + l15;                                   // the query this lane feeds into the A operand
-    for (int h = 0; h < H; ++h) {
-        f32x4 sc[NT];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) sc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        for (int c = 0; c < nchunk; ++c) {
-            const int d = c * 32 + l4 * 8;                       // this lane's 8 dims of the chunk
-            const bool din = d < hd;
-            const size_t col = (size_t)h * hd + d;
-            v8 qh = zero8, ql = zero8;
-            if (din && qrow < N) {
-                qh = *(const v8 *)(img + (size_t)qrow * row_el + col);
-                if (PLANES) ql = *(const v8 *)(img + (size_t)qrow * row_el + col + lo_off);
-            }
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                if ((t * 4 + wave) * 16 >= N) continue;           // a whole tile beyond the keys (wave-uniform): its scores stay masked
-                const int key = (t * 4 + wave) * 16 + l15;
-                v8 kh = zero8, kl = zero8;
-                if (din && key < N) {
-                    kh = *(const v8 *)(img + (size_t)key * row_el + D + col);
-                    if (PLANES) kl = *(const v8 *)(img + (size_t)key * row_el + D + col + lo_off);
-                }
-                sc[t] = Elem<T>::mfma16(qh, kh, sc[t]);
-                if (PLANES) {
-                    f32x4 x = {0.0f, 0.0f, 0.0f, 0.0f};
-                    x = Elem<T>::mfma16(qh, kl, x);
-                    x = Elem<T>::mfma16(ql, kh, x);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) sc[t][r] = __builtin_fmaf(x[r], kHiLoInv, sc[t][r]);
-                }
-            }
-        }
-        // scale, mask, row maxima
-        float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const bool kin = (t * 4 + wave) * 16 + l15 < N;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { sc[t][r] = kin ? sc[t][r] * scale : -INFINITY; mx[r] = fmaxf(mx[r], sc[t][r]); }
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-#pragma unroll
-            for (int m = 1; m < 16; m <<= 1) mx[r] = fmaxf(mx[r], __shfl_xor(mx[r], m));
-        }
-        if (l15 == 0) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) red[0][wave][l4 * 4 + r] = mx[r];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { const int qi = l4 * 4 + r; mx[r] = fmaxf(fmaxf(red[0][0][qi], red[0][1][qi]), fmaxf(red[0][2][qi], red[0][3][qi])); }
-        float sm[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { sc[t][r] = expf(sc[t][r] - mx[r]); sm[r] += sc[t][r]; }     // a masked key: expf(-inf) = 0
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-#pragma unroll
-            for (int m = 1; m < 16; m <<= 1) sm[r] += __shfl_xor(sm[r], m);
-        }
-        if (l15 == 0) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) red[1][wave][l4 * 4 + r] = sm[r];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { const int qi = l4 * 4 + r; sm[r] = (red[1][0][qi] + red[1][1][qi]) + (red[1][2][qi] + red[1][3][qi]); }
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[t][r] += sc[t][r] / sm[r];
-        }
-        __syncthreads();                                         // red[] is rewritten by the next head
-    }
-    const float inv_h = 1.0f / (float)H;
-    float *ob = out + (size_t)b * N * N;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int key = (t * 4 + wave) * 16 + l15;
-        if (key >= N) continue;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int qi = q0 + l4 * 4 + r;
-            if (qi >= N) continue;
-            float v = acc[t][r] * inv_h;
-            if (half_identity) v = 0.5f * v + (qi == key ? 0.5f : 0.0f);
-            ob[(size_t)qi * N + key] = v;
-        }
-    }
+    map_head_mean_block<T, NT, PLANES>(qkv + (size_t)b * N * ((size_t)3 * D), lo_off, out + (size_t)b * N * N, N, D, H, q0, scale, half_identity);
+}
+template <typename T, int NT>
+__global__ __launch_bounds__(256) void attn_head_mean_packed_kernel(const T *__restrict__ qkv, float *__restrict__ out, const int *__restrict__ row0,
+                                                                   const int *__restrict__ rblk0, const int *__restrict__ sq0, int n, int D, int H, float scale,
+                                                                   int half_identity) {
+    const int b = map_find_image(rblk0, n, blockIdx.x);
+    const int r0 = row0[b], N = row0[b + 1] - r0, q0 = (blockIdx.x - rblk0[b]) * 16;
+    map_head_mean_block<T, NT, false>(qkv + (size_t)r0 * ((size_t)3 * D), 0, out + (size_t)sq0[b], N, D, H, q0, scale, half_identity);
 }
 
-// ------------------------------------------------------------------------------------------------
-// Rollout step, in place: a[b] <- a[b] . r[b] ([N][N] f32 each).  One workgroup of four waves per (image, 16-row block of a).  The block's
-// 16 rows of a go to LDS first (zeros beyond N), then each wave computes 64-column groups of the product: four 16x16 tiles with independent
-// accumulators on mfma_f32_16x16x4_f32 (A[i = l & 15][k = l >> 4] from LDS, B[k = l >> 4][j = l & 15] from r), written back over the rows
-// it read.  No other workgroup touches these rows of a, and r is another buffer.  NT: N <= 64 NT.
-// ------------------------------------------------------------------------------------------------
 template <int NT>
 __global__ __launch_bounds__(256) void attn_rollout_step_kernel(float *__restrict__ a, const float *__restrict__ r, int N) {
-    constexpr int NPAD = 64 * NT;
-    __shared__ float as[16][NPAD + 4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, l4 = lane >> 4;
     const int rblocks = (N + 15) / 16;
     const int b = blockIdx.x / rblocks, i0 = (blockIdx.x - b * rblocks) * 16;
-    float *ab = a + (size_t)b * N * N;
-    const float *rb = r + (size_t)b * N * N;
-    for (int e = tid; e < 16 * NPAD; e += 256) {
-        const int i = e / NPAD, k = e - i * NPAD;
-        as[i][k] = (i0 + i < N && k < N) ? ab[(size_t)(i0 + i) * N + k] : 0.0f;
-    }
-    __syncthreads();
-    const int kend = (N + 3) / 4 * 4;
-    for (int j0 = wave * 64; j0 < N; j0 += 256) {
-        f32x4 c[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) c[u] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        for (int k0 = 0; k0 < kend; k0 += 4) {
-            const int k = k0 + l4;
-            const float av = as[l15][k];
-            const float *rr = rb + (size_t)k * N;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int j = j0 + u * 16 + l15;
-                const float bv = (k < N && j < N) ? rr[j] : 0.0f;
-                c[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, c[u], 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int j = j0 + u * 16 + l15;
-            if (j >= N) continue;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int i = i0 + l4 * 4 + q;
-                if (i < N) ab[(size_t)i * N + j] = c[u][q];
-            }
-        }
-    }
+    rollout_step_block<NT>(a + (size_t)b * N * N, r + (size_t)b * N * N, N, i0);
+}
+template <int NT>
+__global__ __launch_bounds__(256) void attn_rollout_step_packed_kernel(float *__restrict__ a, const float *__restrict__ r, const int *__restrict__ row0,
+                                                                      const int *__restrict__ rblk0, const int *__restrict__ sq0, int n) {
+    const int b = map_find_image(rblk0, n, blockIdx.x);
+    const int N = row0[b + 1] - row0[b], i0 = (blockIdx.x - rblk0[b]) * 16;
+    rollout_step_block<NT>(a + (size_t)sq0[b], r + (size_t)sq0[b], N, i0);
 }
 
-// ------------------------------------------------------------------------------------------------
-// Last rollout factor: out[b][k] = sum_j w_j r[b][j][k] with w_j = 0.5 mean_h cls[b][h][j] + 0.5 [j == 0] (row 0 of A^_(L-1)); r == nullptr
-// (a one-layer model): out = w.  One workgroup per image; w in LDS (N <= 1024), thread k walks column k (coalesced rows of r).
-// ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void attn_rollout_row_kernel(const float *__restrict__ cls, long cls_stride, const float *__restrict__ r,
                                                               float *__restrict__ out, long out_stride, int N, int H) {
-    __shared__ float w[1024];
     const int b = blockIdx.x;
-    const float *cb = cls + (size_t)b * cls_stride;
-    const float inv_h = 1.0f / (float)H;
-    for (int j = threadIdx.x; j < N; j += 256) {
-        float s = 0.0f;
-        for (int h = 0; h < H; ++h) s += cb[(size_t)h * N + j];
-        w[j] = 0.5f * (s * inv_h) + (j == 0 ? 0.5f : 0.0f);
-    }
-    __syncthreads();
-    float *ob = out + (size_t)b * out_stride;
-    if (!r) { for (int k = threadIdx.x; k < N; k += 256) ob[k] = w[k]; return; }
-    const float *rb = r + (size_t)b * N * N;
-    for (int k = threadIdx.x; k < N; k += 256) {
-        float s = 0.0f;
-        for (int j = 0; j < N; ++j) s = __builtin_fmaf(w[j], rb[(size_t)j * N + k], s);
-        ob[k] = s;
-    }
+    rollout_row_image(cls + (size_t)b * cls_stride, r ? r + (size_t)b * N * N : nullptr, out + (size_t)b * out_stride, N, H);
+}
+// a pack: image b's class maps [H][N_b] start at float row0[b] * cfpt + cslot * H * N_b of cls, its row at float row0[b] * ofpt + ooff * N_b of out
+__global__ __launch_bounds__(256) void attn_rollout_row_packed_kernel(const float *__restrict__ cls, long cfpt, int cslot, const float *__restrict__ r,
+                                                                     float *__restrict__ out, long ofpt, long ooff, const int *__restrict__ row0,
+                                                                     const int *__restrict__ sq0, int H) {
+    const int b = blockIdx.x;
+    const int r0 = row0[b], N = row0[b + 1] - r0;
+    rollout_row_image(cls + (size_t)r0 * cfpt + (size_t)cslot * H * N, r ? r + (size_t)sq0[b] : nullptr, out + (size_t)r0 * ofpt + (size_t)ooff * N, N, H);
 }
 
 template <typename T, bool PLANES>
@@ -300,6 +104,37 @@ hipError_t launch_head_mean_t(const void *qkv, long lo_off, float *out, int n_im
     const dim3 grid((unsigned)((size_t)n_img * ((N + 15) / 16))), blk(256);
     const int nt = (N + 63) / 64;
 #define VITX_MAPM(NT) hipLaunchKernelGGL((attn_head_mean_kernel<T, NT, PLANES>), grid, blk, 0, st, (const T *)qkv, lo_off, out, N, D, H, scale, half_identity ? 1 : 0)
+    if (nt <= 1) VITX_MAPM(1);
+    else if (nt <= 2) VITX_MAPM(2);
+    else if (nt <= 4) VITX_MAPM(4);
+    else if (nt <= 8) VITX_MAPM(8);
+    else VITX_MAPM(16);
+#undef VITX_MAPM
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_cls_map_packed_t(const void *qkv, float *out, long fpt, int slot, const int *row0, int n, int D, int H, hipStream_t st) {
+    const int np = D / H / 8;
+    const float scale = 1.0f / sqrtf((float)(D / H));
+    const dim3 grid((unsigned)((size_t)n * H)), blk(256);
+#define VITX_MAPC(NPP) hipLaunchKernelGGL((attn_cls_map_packed_kernel<T, NPP>), grid, blk, 0, st, (const T *)qkv, out, fpt, slot, row0, D, H, np, scale)
+    if (np <= 1) VITX_MAPC(1);
+    else if (np <= 2) VITX_MAPC(2);
+    else if (np <= 4) VITX_MAPC(4);
+    else if (np <= 8) VITX_MAPC(8);
+    else VITX_MAPC(16);
+#undef VITX_MAPC
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_head_mean_packed_t(const void *qkv, float *out, const int *row0, const int *rblk0, const int *sq0, int n, int blocks, int n_max, int D, int H,
+                                     bool half_identity, hipStream_t st) {
+    const float scale = 1.0f / sqrtf((float)(D / H));
+    const dim3 grid((unsigned)blocks), blk(256);
+    const int nt = (n_max + 63) / 64;
+#define VITX_MAPM(NT) hipLaunchKernelGGL((attn_head_mean_packed_kernel<T, NT>), grid, blk, 0, st, (const T *)qkv, out, row0, rblk0, sq0, n, D, H, scale, half_identity ? 1 : 0)
     if (nt <= 1) VITX_MAPM(1);
     else if (nt <= 2) VITX_MAPM(2);
     else if (nt <= 4) VITX_MAPM(4);
@@ -343,6 +178,54 @@ hipError_t launch_rollout_step(float *a, const float *r, int n_img, int N, hipSt
 hipError_t launch_rollout_row(const float *cls, long cls_stride, const float *r, float *out, long out_stride, int n_img, int N, int H, hipStream_t st) {
     if (n_img <= 0 || N <= 0 || N > kAttnMeanMaxTokens || H <= 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(attn_rollout_row_kernel, dim3((unsigned)n_img), dim3(256), 0, st, cls, cls_stride, r, out, out_stride, N, H);
+    return hipGetLastError();
+}
+
+// ---- a pack (kernels.h): the tables, then the four launches ----
+bool attn_pack_tables(const int32_t *row0, int n, int32_t *rblk0, int32_t *sq0, int *n_max) {
+    int64_t blk = 0, sq = 0;
+    int widest = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t N = row0[i + 1] - row0[i];
+        rblk0[i] = (int32_t)blk; sq0[i] = (int32_t)sq;
+        blk += (N + 15) / 16; sq += N * N;
+        if (N > widest) widest = (int)N;
+        if (sq > 0x7fffffffLL || blk > 0x7fffffffLL) return false;
+    }
+    rblk0[n] = (int32_t)blk; sq0[n] = (int32_t)sq;
+    if (n_max) *n_max = widest;
+    return true;
+}
+
+hipError_t launch_attention_cls_map_packed(int dtype, const void *qkv, float *out, long fpt, int slot, const int *row0, int n, int D, int H, hipStream_t st) {
+    if (!attention_map_supports(1, D, H) || n <= 0 || fpt < H || slot < 0 || (dtype != DT_F16 && dtype != DT_BF16)) return hipErrorInvalidValue;
+    if (dtype == DT_F16) return launch_cls_map_packed_t<_Float16>(qkv, out, fpt, slot, row0, n, D, H, st);
+    return launch_cls_map_packed_t<__bf16>(qkv, out, fpt, slot, row0, n, D, H, st);
+}
+
+hipError_t launch_attention_head_mean_packed(int dtype, const void *qkv, float *out, const int *row0, const int *rblk0, const int *sq0, int n, int blocks, int n_max,
+                                             int D, int H, bool half_identity, hipStream_t st) {
+    if (!attention_mean_supports(n_max, D, H) || n <= 0 || blocks < n || (dtype != DT_F16 && dtype != DT_BF16)) return hipErrorInvalidValue;
+    if (dtype == DT_F16) return launch_head_mean_packed_t<_Float16>(qkv, out, row0, rblk0, sq0, n, blocks, n_max, D, H, half_identity, st);
+    return launch_head_mean_packed_t<__bf16>(qkv, out, row0, rblk0, sq0, n, blocks, n_max, D, H, half_identity, st);
+}
+
+hipError_t launch_rollout_step_packed(float *a, const float *r, const int *row0, const int *rblk0, const int *sq0, int n, int blocks, int n_max, hipStream_t st) {
+    if (n <= 0 || blocks < n || n_max <= 0 || n_max > kAttnMeanMaxTokens) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks), blk(256);
+    const int nt = (n_max + 63) / 64;
+    if (nt <= 1) hipLaunchKernelGGL((attn_rollout_step_packed_kernel<1>), grid, blk, 0, st, a, r, row0, rblk0, sq0, n);
+    else if (nt <= 2) hipLaunchKernelGGL((attn_rollout_step_packed_kernel<2>), grid, blk, 0, st, a, r, row0, rblk0, sq0, n);
+    else if (nt <= 4) hipLaunchKernelGGL((attn_rollout_step_packed_kernel<4>), grid, blk, 0, st, a, r, row0, rblk0, sq0, n);
+    else if (nt <= 8) hipLaunchKernelGGL((attn_rollout_step_packed_kernel<8>), grid, blk, 0, st, a, r, row0, rblk0, sq0, n);
+    else hipLaunchKernelGGL((attn_rollout_step_packed_kernel<16>), grid, blk, 0, st, a, r, row0, rblk0, sq0, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_rollout_row_packed(const float *cls, long cfpt, int cslot, const float *r, float *out, long ofpt, long ooff, const int *row0, const int *sq0, int n,
+                                     int n_max, int H, hipStream_t st) {
+    if (n <= 0 || n_max <= 0 || n_max > kAttnMeanMaxTokens || H <= 0 || cfpt < H || cslot < 0 || ofpt < 1 || ooff < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(attn_rollout_row_packed_kernel, dim3((unsigned)n), dim3(256), 0, st, cls, cfpt, cslot, r, out, ofpt, ooff, row0, sq0, H);
     return hipGetLastError();
 }
 

@@ -185,6 +185,19 @@ hipError_t launch_attention_cls_map(int dtype, const void *qkv, long lo_off, flo
 hipError_t launch_attention_head_mean(int dtype, const void *qkv, long lo_off, float *out, int n_img, int N, int D, int H, bool half_identity, hipStream_t stream);
 hipError_t launch_rollout_step(float *a, const float *r, int n_img, int N, hipStream_t stream);
 hipError_t launch_rollout_row(const float *cls, long cls_stride, const float *r, float *out, long out_stride, int n_img, int N, int H, hipStream_t stream);
+// The same on a pack (vitx_pack_attn_enable): image i = rows row0[i] .. row0[i + 1] - 1 of qkv, N_i tokens, the fixed-shape launch's bits on that image
+// alone (one body, attention_map_tile.h; no parity planes).  attn_pack_tables (host): rblk0 [n + 1] = the running count of ceil(N_i / 16), the
+// work items of the head mean and the step; sq0 [n + 1] = the running sum of N_i^2, where image i's N_i x N_i matrix starts in out / a / r; *n_max =
+// the widest image (the launches' NT); false when a count leaves 31 bits.  blocks = rblk0[n].  Device tables: row0, rblk0, sq0.
+//   cls_map:  image i's [H][N_i] maps at float row0[i] * fpt + slot * H * N_i of out (fpt floats per token);
+//   row:      its class maps at float row0[i] * cfpt + cslot * H * N_i of cls, its row [N_i] at float row0[i] * ofpt + ooff * N_i of out.
+bool attn_pack_tables(const int32_t *row0, int n, int32_t *rblk0, int32_t *sq0, int *n_max);
+hipError_t launch_attention_cls_map_packed(int dtype, const void *qkv, float *out, long fpt, int slot, const int *row0, int n, int D, int H, hipStream_t stream);
+hipError_t launch_attention_head_mean_packed(int dtype, const void *qkv, float *out, const int *row0, const int *rblk0, const int *sq0, int n, int blocks, int n_max,
+                                             int D, int H, bool half_identity, hipStream_t stream);
+hipError_t launch_rollout_step_packed(float *a, const float *r, const int *row0, const int *rblk0, const int *sq0, int n, int blocks, int n_max, hipStream_t stream);
+hipError_t launch_rollout_row_packed(const float *cls, long cfpt, int cslot, const float *r, float *out, long ofpt, long ooff, const int *row0, const int *sq0, int n,
+                                     int n_max, int H, hipStream_t stream);
 // Image embeddings and token features (features.hip; vitx_feat_enable): F = the f32 LayerNorm of launch_layernorm before its rounding.  Row t of
 // image i is read at x + i * img_stride + t * row_stride; T = `first` is the first patch row (1 + the register tokens): cls[i * out_img_stride ..] =
 // F[0], mean[..] = mean of F[T .. N-1], tokens[..] = F[T .. N-1] ([N-T][D]); any output may be nullptr (row 0 is read only for cls / z, rows T ..

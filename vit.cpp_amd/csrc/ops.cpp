@@ -1,5 +1,6 @@
 // ops.cpp -- single-kernel entry points (vitx_op_*, vitx_preprocess_u8_device): one launcher each, on the caller's buffers, for the
 // parity tests and the kernel benchmarks.  None takes a context.
+#include <algorithm>
 #include <cmath>
 #include <initializer_list>
 
@@ -375,6 +376,77 @@ int vitx_op_rollout_row(const void *d_cls, long cls_stride, const void *d_r, voi
     if (cls_stride < (long)H * N || out_stride < N) { set_error("vitx_op_rollout_row: cls_stride %ld must be at least H * N = %ld and out_stride %ld at least N = %d", cls_stride, (long)H * N, out_stride, N); return VITX_ERR_ARG; }
     if (N > kAttnMeanMaxTokens) { set_error("vitx_op_rollout_row: rollout takes at most %d tokens (N %d)", kAttnMeanMaxTokens, N); return VITX_ERR_UNSUPPORTED; }
     return op_rc("vitx_op_rollout_row", launch_rollout_row((const float *)d_cls, cls_stride, (const float *)d_r, (float *)d_out, out_stride, n_img, N, H, (hipStream_t)stream));
+}
+
+// The map kernels on a pack (include/vitx.h "packed batches"): TEST entry points.  row0 is a HOST table; each call builds rblk0 and sq0
+// (attn_pack_tables), uploads the three tables, launches on the null stream, waits and frees them.  Every argument check comes before the first device call.
+namespace {
+struct PackMapTables {
+    std::vector<int32_t> host;           // row0 [n + 1] | rblk0 [n + 1] | sq0 [n + 1]
+    int n = 0, n_max = 0;
+    int *dev = nullptr;
+    ~PackMapTables() { (void)hipFree(dev); }
+    const int *row0() const { return dev; }
+    const int *rblk0() const { return dev + n + 1; }
+    const int *sq0() const { return dev + 2 * (n + 1); }
+    int blocks() const { return host[2 * (n + 1) - 1]; }
+    size_t sq_floats() const { return (size_t)host[3 * (n + 1) - 1]; }
+    // the checks of the table (need_mean: every image within the rollout kernels' token bound)
+    int check(const char *name, const int32_t *row0, int n_, bool need_mean) {
+        if (!row0 || n_ <= 0 || row0[0] < 0) { set_error("%s: invalid argument", name); return VITX_ERR_ARG; }
+        for (int i = 0; i < n_; ++i) {
+            if (row0[i + 1] <= row0[i]) { set_error("%s: image %d: row0 must ascend (an image has at least one token)", name, i); return VITX_ERR_ARG; }
+            if (need_mean && row0[i + 1] - row0[i] > kAttnMeanMaxTokens) {
+                set_error("%s: image %d: rollout takes at most %d tokens (N %d)", name, i, kAttnMeanMaxTokens, row0[i + 1] - row0[i]);
+                return VITX_ERR_UNSUPPORTED;
+            }
+        }
+        n = n_;
+        host.assign((size_t)3 * (n + 1), 0);
+        std::copy(row0, row0 + n + 1, host.begin());
+        if (!attn_pack_tables(row0, n, host.data() + n + 1, host.data() + 2 * (n + 1), &n_max)) { set_error("%s: the sum of N_i^2 leaves 31 bits", name); return VITX_ERR_ARG; }
+        return VITX_OK;
+    }
+    hipError_t upload() {
+        hipError_t e = hipMalloc((void **)&dev, host.size() * 4);
+        if (e == hipSuccess) e = hipMemcpy(dev, host.data(), host.size() * 4, hipMemcpyHostToDevice);
+        return e;
+    }
+};
+}  // namespace
+// d_cls: image i's [H][N_i] class-token maps at float row0[i] * H; d_mean: its [N_i][N_i] head mean (half_identity: the rollout factor) at float sq0[i]
+int vitx_op_attention_map_packed(int dtype, const void *d_qkv, void *d_cls, void *d_mean, const int32_t *row0, int n, int D, int H, int half_identity) {
+    if (!d_qkv || (!d_cls && !d_mean) || D <= 0 || H <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_attention_map_packed: invalid argument"); return VITX_ERR_ARG; }
+    if (!attention_map_supports(1, D, H)) { set_error("vitx_op_attention_map_packed: head_dim must be a multiple of 8 up to 128 (D %d, H %d)", D, H); return VITX_ERR_UNSUPPORTED; }
+    PackMapTables t;
+    if (const int rc = t.check("vitx_op_attention_map_packed", row0, n, d_mean != nullptr)) return rc;
+    hipError_t e = t.upload();
+    if (e == hipSuccess && d_cls) e = launch_attention_cls_map_packed(dtype, d_qkv, (float *)d_cls, H, 0, t.row0(), n, D, H, nullptr);
+    if (e == hipSuccess && d_mean) e = launch_attention_head_mean_packed(dtype, d_qkv, (float *)d_mean, t.row0(), t.rblk0(), t.sq0(), n, t.blocks(), t.n_max, D, H, half_identity != 0, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    return op_rc("vitx_op_attention_map_packed", e);
+}
+// d_a <- d_a . d_r per image, image i's matrices at float sq0[i] of both
+int vitx_op_rollout_step_packed(void *d_a, const void *d_r, const int32_t *row0, int n) {
+    if (!d_a || !d_r) { set_error("vitx_op_rollout_step_packed: invalid argument"); return VITX_ERR_ARG; }
+    PackMapTables t;
+    if (const int rc = t.check("vitx_op_rollout_step_packed", row0, n, true)) return rc;
+    const uintptr_t a0 = (uintptr_t)d_a, r0 = (uintptr_t)d_r, bytes = (uintptr_t)t.sq_floats() * sizeof(float);
+    if (a0 < r0 + bytes && r0 < a0 + bytes) { set_error("vitx_op_rollout_step_packed: d_a and d_r overlap (the step is in place over d_a and reads all of d_r)"); return VITX_ERR_ARG; }
+    hipError_t e = t.upload();
+    if (e == hipSuccess) e = launch_rollout_step_packed((float *)d_a, (const float *)d_r, t.row0(), t.rblk0(), t.sq0(), n, t.blocks(), t.n_max, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    return op_rc("vitx_op_rollout_step_packed", e);
+}
+// d_cls as vitx_op_attention_map_packed writes it; d_r: image i's matrix at float sq0[i], or NULL; d_out: image i's row [N_i] at float row0[i]
+int vitx_op_rollout_row_packed(const void *d_cls, const void *d_r, void *d_out, const int32_t *row0, int n, int H) {
+    if (!d_cls || !d_out || H <= 0) { set_error("vitx_op_rollout_row_packed: invalid argument"); return VITX_ERR_ARG; }
+    PackMapTables t;
+    if (const int rc = t.check("vitx_op_rollout_row_packed", row0, n, true)) return rc;
+    hipError_t e = t.upload();
+    if (e == hipSuccess) e = launch_rollout_row_packed((const float *)d_cls, H, 0, (const float *)d_r, (float *)d_out, 1, 0, t.row0(), t.sq0(), n, t.n_max, H, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    return op_rc("vitx_op_rollout_row_packed", e);
 }
 
 // Zero-shot classification on the caller's buffers: the sequence the forward of a context with a bank runs (head_zeroshot, heads.cpp).  Every

@@ -114,9 +114,9 @@ int pack_quiesce(vitx_pack *p) {
     return wait_done(p);
 }
 
-// the segment tables with the parts of the heads and of the u8 sources that will be set behind them (PackLayout): a fresh zeroed buffer in place of the old one
-int resize_tables(vitx_pack *p, const char *api, bool dense, bool depth, bool u8) {
-    const size_t ints = PackLayout{(size_t)p->max_images, dense, depth, u8}.ints();
+// the segment tables with the parts of the heads, of the u8 sources and of the attention rollout that will be set behind them (PackLayout): a fresh zeroed buffer in place of the old one
+int resize_tables(vitx_pack *p, const char *api, bool dense, bool depth, bool u8, bool rollout) {
+    const size_t ints = PackLayout{(size_t)p->max_images, dense, depth, u8, rollout}.ints();
     if (p->host.size() == ints) return VITX_OK;
     int *t = nullptr;
     HIP_TRY(hipMalloc((void **)&t, ints * 4));

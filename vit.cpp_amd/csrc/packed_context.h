@@ -1,7 +1,7 @@
 // packed_context.h -- the packed context (struct vitx_pack); include/vitx.h "packed batches": n images, each with its own h_i x w_i, their
 // tokens end to end in one [sum N_i][D] residual stream, one forward.  Modelled on the text context (text_context.h): its own scratch, one
 // stream, no sub-batches, no graph cache, no LayerNorm fusion.  Three units stand on it, split like the image context's: packed_context.cpp
-// (creation, counters, the table cache), packed_forward.cpp (the checks of a call, the forward), packed_outputs.cpp (features, the dense and the depth head)
+// (creation, counters, the table cache), packed_forward.cpp (the checks of a call, the forward), packed_outputs.cpp (features, the dense and the depth head, attention maps)
 // and packed_input.cpp (u8 sources).
 // Internal: callers see the opaque vitx_pack of include/vitx.h.
 #pragma once
@@ -14,11 +14,13 @@ using namespace vitx;
 // The segment tables of a call, in ints into vitx_pack::tab / host (cap = max_images): row0 [cap + 1] | qb0 [cap + 1] | toff [cap] and, while a
 // dense head is set, behind them tile0 [cap + 1] | seg [cap][kDenseSegInts] and, while a depth head is set, behind those ftile0 [cap + 1] |
 // otile0 [cap + 1] | dseg [cap][kDepthSegInts] and, while u8 sources are on (vitx_pack_u8_set), behind those ptile0 [cap + 1] | pseg [cap][kPpSegInts]
-// (kernels.h).  One buffer, one upload; a new table goes in here.
+// (kernels.h) and, while attention rollout is on (vitx_pack_attn_enable), behind those rblk0 [cap + 1] | sq0 [cap + 1] (kernels.h attn_pack_tables).
+// One buffer, one upload; a new table goes in here.
 struct PackLayout {
     size_t cap;
     bool dense, depth;                   // the heads whose tables the buffer holds
     bool u8 = false;                     // the u8 preprocessing's tables too
+    bool rollout = false;                // the attention rollout's tables too
     size_t row0() const { return 0; }
     size_t qb0() const { return row0() + cap + 1; }
     size_t toff() const { return qb0() + cap + 1; }
@@ -29,7 +31,9 @@ struct PackLayout {
     size_t dseg() const { return otile0() + cap + 1; }
     size_t ptile0() const { return depth ? dseg() + cap * kDepthSegInts : ftile0(); }
     size_t pseg() const { return ptile0() + cap + 1; }
-    size_t ints() const { return u8 ? pseg() + cap * kPpSegInts : ptile0(); }
+    size_t rblk0() const { return u8 ? pseg() + cap * kPpSegInts : ptile0(); }
+    size_t sq0() const { return rblk0() + cap + 1; }
+    size_t ints() const { return rollout ? sq0() + cap + 1 : rblk0(); }
 };
 
 // What the host-only checks of a forward call (packed_forward.cpp check_call) give the forward: made once per call, before its first device call
@@ -52,6 +56,27 @@ struct PackCall {
     std::vector<int32_t> ptile0, pseg;
     int plds = 0;
     int64_t src_bytes = 0;
+    // with attention rollout on (kernels.h attn_pack_tables): the running counts of 16-row blocks and of N_i^2, the widest image of the call
+    std::vector<int32_t> rblk0, sq0;
+    int n_max = 0;
+};
+
+// Attention maps (vitx_pack_attn_enable): the image context's AttnMaps per image of a pack.  Image i's floats of `out` start at row0[i] * fpt: the
+// selected layers in ascending order, each [H][N_i], then the rollout row [N_i]
+struct PackAttn {
+    uint64_t mask = 0;
+    int flags = 0;
+    int fpt = 0;                         // floats per token: popcount(mask) * H (+ 1 with VITX_ATTN_ROLLOUT)
+    long max_sq = 0;                     // rollout: the floats of one matrix arena, the bound on a call's sum of N_i^2
+    DevMem out;                          // [max_tokens][fpt] f32
+    DevMem roll[2];                      // rollout: [max_sq] f32 x 2, A^_l written into one, the product R_l in place of it (ping-pong)
+    DevMem cls_last;                     // rollout without the last layer in the mask: its class-token maps, [max_tokens][H] f32
+    size_t bytes = 0;                    // what the enable added to vitx_pack_scratch_bytes besides the tables
+    int n = 0;                           // images of the last forward with maps on (0: none)
+    std::vector<int32_t> rblk0, sq0;     // of that forward (rollout)
+    int n_max = 0;
+    bool rollout() const { return (flags & VITX_ATTN_ROLLOUT) != 0; }
+    bool selects(int il) const { return (mask >> il) & 1; }
 };
 
 // u8 sources (vitx_pack_u8_set): the description, the device staging of the host entry point and the declaration of the next call
@@ -119,9 +144,11 @@ struct vitx_pack {
     std::unique_ptr<PackDense> dense;    // vitx_pack_dense_set (null: off); its device memory is its own
     std::unique_ptr<PackDepth> depth;    // vitx_pack_depth_set (null: off); its device memory is its own
     std::unique_ptr<PackU8> u8;          // vitx_pack_u8_set (null: off)
+    std::unique_ptr<PackAttn> attn;      // vitx_pack_attn_enable (null: off); its device memory is its own
+    bool rollout() const { return attn && attn->rollout(); }
     int launches = 0, pe_launches = 0;   // kernel launches of the last forward, and how many of them were patch embeddings
     size_t scratch_bytes = 0;            // device bytes of activation scratch and tables held now
-    PackLayout layout() const { return PackLayout{(size_t)max_images, (bool)dense, (bool)depth, (bool)u8}; }
+    PackLayout layout() const { return PackLayout{(size_t)max_images, (bool)dense, (bool)depth, (bool)u8, rollout()}; }
     // image i of the last call that passed its checks: its patch rows, and where they start in an output that holds every image's patch rows end to end
     size_t patch_rows(int i) const { return (size_t)(row0[i + 1] - row0[i] - Tp); }
     size_t patch_at(int i) const { return (size_t)(row0[i] - i * Tp); }
@@ -147,4 +174,6 @@ int resolve_grids(vitx_pack *p, const std::vector<uint64_t> &want, hipStream_t s
 // Before buffers and tables change hands (the set calls): nothing of this context is in flight.  resize_tables: the segment tables with the parts
 // that will be set behind them (PackLayout), a fresh zeroed buffer in place of the old one.
 int pack_quiesce(vitx_pack *p);
-int resize_tables(vitx_pack *p, const char *api, bool dense, bool depth, bool u8);
+int resize_tables(vitx_pack *p, const char *api, bool dense, bool depth, bool u8, bool rollout);
+// Attention maps (packed_forward.cpp): what vitx_pack_attn_enable and vitx_pack_attn_check refuse in their arguments, host only
+int pack_attn_args(const char *api, int L, uint64_t layer_mask, int flags, long max_sq_tokens);

@@ -2,7 +2,8 @@
 // the forward.  The blocks are the image forward's row-wise launches through the same dispatchers (GEMMs, LayerNorm, activation, gate, pre-norm
 // do not care where one image ends); new are the three launches that must know: the variable-length attention (attention_packed.hip), the
 // rotary embeddings by a segment table (rope.hip) and the class-row gather (text_embed.hip).  The patch embedding is the rectangular context's
-// kernel, one launch per run of consecutive images of one shape.  The opt-in heads are the dense and the depth head (packed_outputs.cpp): the operand rows
+// kernel, one launch per run of consecutive images of one shape.  Attention maps (vitx_pack_attn_enable) are the
+// image forward's launch sequence on the packed map kernels (attention_map.hip), in front of each layer's attention.  The opt-in heads are the dense and the depth head (packed_outputs.cpp): the operand rows
 // and the head GEMM over all rows of the pack, then the label launch (dense_label.hip) or the fine and resize launches (depth_map.hip) by their own
 // segment tables, one map per image at its own size.  With u8 sources declared for a call (packed_input.cpp) one launch in front of the patch embedding
 // stretches every source to its image's shape into the context's pixel buffer (image_preprocess.hip).  No LayerNorm fusion, no class-token tail.
@@ -105,6 +106,25 @@ int check_u8(const char *api, const vitx_preproc &pp, const int32_t *src_shapes,
     return VITX_OK;
 }
 
+// What a forward call adds while attention rollout is on with arenas of max_sq floats (vitx_pack_attn_check's text; row0 [n + 1] is check_shapes's):
+// every image within the rollout kernels' token bound, the call's matrices within the arenas.  On success the rollout's tables of the call: c->rblk0,
+// sq0, n_max.  (Class maps alone refuse nothing: they live in max_tokens rows.)
+int check_attn(const char *api, const int32_t *row0, int n, long max_sq, PackCall *c) {
+    for (int i = 0; i < n; ++i)
+        if (row0[i + 1] - row0[i] > kAttnMeanMaxTokens) {
+            set_error("%s: image %d: rollout keeps two N x N matrices per image and takes at most %d tokens (this image: %d)", api, i, kAttnMeanMaxTokens, row0[i + 1] - row0[i]);
+            return VITX_ERR_UNSUPPORTED;
+        }
+    c->rblk0.resize((size_t)n + 1); c->sq0.resize((size_t)n + 1);
+    int64_t sq = 0;
+    for (int i = 0; i < n; ++i) { const int64_t N = row0[i + 1] - row0[i]; sq += N * N; }
+    if (sq > (int64_t)max_sq || !attn_pack_tables(row0, n, c->rblk0.data(), c->sq0.data(), &c->n_max)) {
+        set_error("%s: the call's rollout matrices hold %lld floats (the sum of N_i^2), above max_sq_tokens = %ld", api, (long long)sq, max_sq);
+        return VITX_ERR_ARG;
+    }
+    return VITX_OK;
+}
+
 // the distinct grids of a call, in order of first appearance, as (gh << 32 | gw)
 std::vector<uint64_t> distinct_grids(const int32_t *shapes, int n, int P) {
     std::vector<uint64_t> g;
@@ -134,11 +154,40 @@ int check_call(vitx_pack *p, const void *d_imgs, const int32_t *shapes, int n, P
     if (c->want.size() > (size_t)p->max_grids) { set_error("vitx_pack_forward: the call names %d distinct grids, the table cache holds max_grids = %d", (int)c->want.size(), p->max_grids); return VITX_ERR_ARG; }
     if (dn && (rc = check_dense("vitx_pack_forward", p->model, shapes, next_out.empty() ? nullptr : next_out.data(), (int)(next_out.size() / 2), n, dn->K, dn->max_pixels, c))) return rc;
     if (dp && (rc = check_depth("vitx_pack_forward", p->model, shapes, next_depth.empty() ? nullptr : next_depth.data(), (int)(next_depth.size() / 2), n, dp->K, dp->u, dp->max_pixels, c))) return rc;
+    if (p->rollout() && (rc = check_attn("vitx_pack_forward", c->row0.data(), n, p->attn->max_sq, c))) return rc;
     if (from_u8) {
         if ((uintptr_t)d_imgs & 3) { set_error("vitx_pack_forward: the u8 sources must be 4-byte aligned"); return VITX_ERR_ARG; }
         rc = check_u8("vitx_pack_forward", u8->pp, next_src.data(), (int)(next_src.size() / 2), shapes, n, u8->max_src_bytes, c, nullptr);
     }
     return rc;
+}
+
+// Attention maps of layer il (vitx_pack_attn_enable) from the QKV its qkv projection (and launch_rope_packed) has just written: the launch sequence of
+// the image forward's attention_maps, per image of the pack.  The kernels only read QKV and write the maps' own buffers.  Rollout: A^_l goes to arena
+// l & 1 and becomes R_l = A^_l R_(l-1) in place; the last layer contributes row 0 of its factor only, built from its class-token maps.
+int pack_attention_maps(vitx_pack *p, const PackLayout &at, int il, int n, hipStream_t st) {
+    PackAttn &am = *p->attn;
+    const int D = p->D, H = p->H, L = p->L, dt = p->dtype, fpt = am.fpt;
+    const int *d_row0 = p->tab + at.row0();
+    float *const roll[2] = {am.roll[0].as<float>(), am.roll[1].as<float>()};
+    const float *cls = nullptr;
+    long cfpt = 0;
+    int cslot = 0;
+    if (am.selects(il)) { cls = am.out.as<float>(); cfpt = fpt; cslot = layer_slot(am.mask, il); }
+    else if (am.rollout() && il + 1 == L) { cls = am.cls_last.as<float>(); cfpt = H; }
+    if (cls) { HIP_TRY(launch_attention_cls_map_packed(dt, p->QKV, (float *)cls, cfpt, cslot, d_row0, n, D, H, st)); ++p->launches; }
+    if (!am.rollout()) return VITX_OK;
+    const int *d_rblk0 = p->tab + at.rblk0(), *d_sq0 = p->tab + at.sq0();
+    const int blocks = am.rblk0[n];
+    if (il + 1 < L) {
+        float *a = roll[il & 1];
+        HIP_TRY(launch_attention_head_mean_packed(dt, p->QKV, a, d_row0, d_rblk0, d_sq0, n, blocks, am.n_max, D, H, true, st)); ++p->launches;
+        if (il > 0) { HIP_TRY(launch_rollout_step_packed(a, roll[(il + 1) & 1], d_row0, d_rblk0, d_sq0, n, blocks, am.n_max, st)); ++p->launches; }
+        return VITX_OK;
+    }
+    HIP_TRY(launch_rollout_row_packed(cls, cfpt, cslot, L > 1 ? roll[(L - 2) & 1] : nullptr, am.out.as<float>(), fpt, fpt - 1, d_row0, d_sq0, n, am.n_max, H, st));
+    ++p->launches;
+    return VITX_OK;
 }
 
 int pack_gemm(vitx_pack *p, int epi, const GemmArgs &a, hipStream_t st) {
@@ -160,6 +209,8 @@ int pack_forward(vitx_pack *p, PackCall &c, const void *d_imgs, const int32_t *s
         dp->grids.swap(c.dgrids); dp->outs.swap(c.douts); dp->pix0.swap(c.dpix0); dp->fine0.swap(c.dfine0); dp->ftile0.swap(c.ftile0); dp->otile0.swap(c.otile0);
         dp->cells = c.dcells; dp->n = 0;
     }
+    PackAttn *am = p->attn.get();
+    if (am) { am->rblk0.swap(c.rblk0); am->sq0.swap(c.sq0); am->n_max = c.n_max; am->n = 0; }
     p->launches = p->pe_launches = 0;
     if ((rc = resolve_grids(p, c.want, st))) return rc;
     const WeightSet &ws = *p->wset;
@@ -196,6 +247,11 @@ int pack_forward(vitx_pack *p, PackCall &c, const void *d_imgs, const int32_t *s
         std::copy(c.ptile0.begin(), c.ptile0.end(), p->host.data() + at.ptile0());
         std::copy(c.pseg.begin(), c.pseg.end(), p->host.data() + at.pseg());
     }
+    // the attention rollout's (check_call built them)
+    if (at.rollout) {
+        std::copy(am->rblk0.begin(), am->rblk0.end(), p->host.data() + at.rblk0());
+        std::copy(am->sq0.begin(), am->sq0.end(), p->host.data() + at.sq0());
+    }
     HIP_TRY(hipMemcpyAsync(p->tab, p->host.data(), p->host.size() * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(p->uploaded, st));
     p->uploaded_pending = true;
@@ -230,6 +286,7 @@ int pack_forward(vitx_pack *p, PackCall &c, const void *d_imgs, const int32_t *s
             HIP_TRY(launch_rope_packed(dt, p->QKV, p->rope_cos, p->rope_sin, d_row0, d_toff, n, (long)rows - (long)n * Tp, half % 4 == 0, Tp, D, H, st));
             ++p->launches;
         }
+        if (am && (rc = pack_attention_maps(p, at, il, n, st))) return rc;
         HIP_TRY(launch_attention_packed(dt, p->QKV, p->U, d_row0, d_qb0, n, qblocks, D, H, st)); ++p->launches;
         if ((rc = pack_gemm(p, EPI_BIAS_RESID, dense_gemm(p->U, w.proj_w, w.proj_b, p->X, M, rows, D, round_up(D, tn), D), st))) return rc;
         HIP_TRY(launch_layernorm(dt, p->X, D, w.ln2_w, w.ln2_b, p->U, D, rows, D, p->eps, st)); ++p->launches;
@@ -282,12 +339,23 @@ int pack_forward(vitx_pack *p, PackCall &c, const void *d_imgs, const int32_t *s
         p->launches += cls ? 5 : 3;
         dp->n = n;
     }
+    if (am) am->n = n;
     HIP_TRY(hipEventRecord(p->done, st));
     p->done_pending = true;
     return VITX_OK;
 }
 
 }  // namespace
+
+int pack_attn_args(const char *api, int L, uint64_t layer_mask, int flags, long max_sq_tokens) {
+    if (flags & ~VITX_ATTN_ROLLOUT) { set_error("%s: unknown flags 0x%x", api, flags); return VITX_ERR_ARG; }
+    if (L < 64 && (layer_mask >> L)) { set_error("%s: layer mask 0x%llx names layers beyond the model's %d", api, (unsigned long long)layer_mask, L); return VITX_ERR_ARG; }
+    if ((flags & VITX_ATTN_ROLLOUT) && (max_sq_tokens < 1 || max_sq_tokens > 0x7fffffffL)) {
+        set_error("%s: VITX_ATTN_ROLLOUT needs max_sq_tokens (the call's sum of N_i^2) in 1 .. 2^31 - 1, not %ld", api, max_sq_tokens);
+        return VITX_ERR_ARG;
+    }
+    return VITX_OK;
+}
 
 extern "C" {
 
@@ -317,6 +385,25 @@ int vitx_pack_depth_check(const vitx_model *m, const int32_t *shapes, const int3
     if (fine0) std::copy(c.dfine0.begin(), c.dfine0.end(), fine0);
     if (ftile0) std::copy(c.ftile0.begin(), c.ftile0.end(), ftile0);
     if (otile0) std::copy(c.otile0.begin(), c.otile0.end(), otile0);
+    return VITX_OK;
+}
+
+int vitx_pack_attn_check(const vitx_model *m, const int32_t *shapes, int n, uint64_t layer_mask, int flags, long max_sq_tokens, int32_t *rblk0, int32_t *sq0) {
+    if (!m || !shapes) { set_error("vitx_pack_attn_check: NULL argument"); return VITX_ERR_ARG; }
+    if (n < 1) { set_error("vitx_pack_attn_check: n = %d", n); return VITX_ERR_ARG; }
+    // max_tokens / max_images: whatever holds the call -- their refusals are vitx_pack_check's
+    std::vector<int32_t> row0((size_t)n + 1);
+    if (const int rc = check_shapes("vitx_pack_attn_check", m, shapes, n, 0x7fffffff, n, row0.data())) return rc;
+    if (const int rc = pack_attn_args("vitx_pack_attn_check", m->hp.num_hidden_layers, layer_mask, flags, max_sq_tokens)) return rc;
+    PackCall c;
+    if (flags & VITX_ATTN_ROLLOUT) {
+        if (const int rc = check_attn("vitx_pack_attn_check", row0.data(), n, max_sq_tokens, &c)) return rc;
+    } else {           // class maps alone refuse nothing per call; the tables are still the call's
+        c.rblk0.resize((size_t)n + 1); c.sq0.resize((size_t)n + 1);
+        if (!attn_pack_tables(row0.data(), n, c.rblk0.data(), c.sq0.data(), &c.n_max)) { set_error("vitx_pack_attn_check: the sum of N_i^2 leaves 31 bits"); return VITX_ERR_ARG; }
+    }
+    if (rblk0) std::copy(c.rblk0.begin(), c.rblk0.end(), rblk0);
+    if (sq0) std::copy(c.sq0.begin(), c.sq0.end(), sq0);
     return VITX_OK;
 }
 

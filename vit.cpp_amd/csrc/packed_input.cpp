@@ -31,7 +31,7 @@ int vitx_pack_u8_set(vitx_pack *p, const vitx_preproc *pp, size_t max_src_bytes)
         p->u8.reset();
     };
     if (off) {       // the tables first: a failed resize leaves the mode as it was
-        if (const int rc = resize_tables(p, "vitx_pack_u8_set", (bool)p->dense, (bool)p->depth, false)) return rc;
+        if (const int rc = resize_tables(p, "vitx_pack_u8_set", (bool)p->dense, (bool)p->depth, false, p->rollout())) return rc;
         drop();
         return VITX_OK;
     }
@@ -48,7 +48,7 @@ int vitx_pack_u8_set(vitx_pack *p, const vitx_preproc *pp, size_t max_src_bytes)
     DevMem img_own(img);
     HIP_TRY(hipMemset(u->src.p, 0, src_bytes));
     HIP_TRY(hipDeviceSynchronize());
-    if (const int rc = resize_tables(p, "vitx_pack_u8_set", (bool)p->dense, (bool)p->depth, true)) return rc;
+    if (const int rc = resize_tables(p, "vitx_pack_u8_set", (bool)p->dense, (bool)p->depth, true, p->rollout())) return rc;
     drop();
     if (!have_img) { p->img = img; img_own.p = nullptr; u->own_img = true; }
     u->bytes = src_bytes + (u->own_img ? img_bytes : 0);

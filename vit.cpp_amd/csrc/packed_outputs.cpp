@@ -1,5 +1,5 @@
 // packed_outputs.cpp -- what a packed context gives besides probabilities (packed_context.h; include/vitx.h "packed batches"): the last layer's
-// features, the dense head and the depth head.  All opt-in; the forward (packed_forward.cpp) launches nothing for an output that is off.  The heads' own
+// features, attention maps, the dense head and the depth head.  All opt-in; the forward (packed_forward.cpp) launches nothing for an output that is off.  The heads' own
 // argument checks and their uploads are the image context's (heads.h: dense_head_args, dense_head_values, dense_head_upload and depth_head_*).
 #include <algorithm>
 
@@ -36,6 +36,51 @@ int vitx_pack_feat_read(vitx_pack *p, float *cls, float *tokens) {
     return VITX_OK;
 }
 
+// Attention maps of a packed context (include/vitx.h "packed batches").  Every argument check comes before the first device call; the state is built in
+// a local and moved in, so a refused or failed enable leaves the maps that were on.
+int vitx_pack_attn_enable(vitx_pack *p, uint64_t layer_mask, int flags, long max_sq_tokens) {
+    if (!p) { set_error("vitx_pack_attn_enable: NULL context"); return VITX_ERR_ARG; }
+    if (const int rc = pack_attn_args("vitx_pack_attn_enable", p->L, layer_mask, flags, max_sq_tokens)) return rc;
+    const bool on = layer_mask != 0 || flags != 0, rollout = (flags & VITX_ATTN_ROLLOUT) != 0;
+    HIP_TRY(hipSetDevice(p->device));
+    if (const int rc = pack_quiesce(p)) return rc;
+    if (!on) {
+        if (p->attn) { p->scratch_bytes -= p->attn->bytes; p->attn.reset(); }
+        return resize_tables(p, "vitx_pack_attn_enable", (bool)p->dense, (bool)p->depth, (bool)p->u8, false);
+    }
+    auto am = std::make_unique<PackAttn>();
+    const size_t T = (size_t)p->max_tokens, H = (size_t)p->H;
+    am->mask = layer_mask; am->flags = flags; am->max_sq = rollout ? max_sq_tokens : 0;
+    am->fpt = layer_slot(layer_mask, p->L) * p->H + (rollout ? 1 : 0);
+    am->bytes = T * am->fpt * 4;
+    bool ok = am->out.alloc(T * am->fpt * 4);
+    if (ok && rollout) { ok = am->roll[0].alloc((size_t)max_sq_tokens * 4) && am->roll[1].alloc((size_t)max_sq_tokens * 4); am->bytes += (size_t)max_sq_tokens * 8; }
+    if (ok && rollout && !am->selects(p->L - 1)) { ok = am->cls_last.alloc(T * H * 4); am->bytes += T * H * 4; }
+    if (!ok) { set_error("vitx_pack_attn_enable: cannot allocate the map buffers for %d token rows", p->max_tokens); return VITX_ERR_NOMEM; }
+    if (const int rc = resize_tables(p, "vitx_pack_attn_enable", (bool)p->dense, (bool)p->depth, (bool)p->u8, rollout)) return rc;
+    if (p->attn) p->scratch_bytes -= p->attn->bytes;
+    p->scratch_bytes += am->bytes;
+    p->attn = std::move(am);
+    return VITX_OK;
+}
+
+int vitx_pack_attn_floats(const vitx_pack *p) { return p && p->attn ? p->attn->fpt : 0; }
+const void *vitx_pack_attn_device(const vitx_pack *p) { return p && p->attn ? p->attn->out.p : nullptr; }
+
+// The last forward's maps, the images end to end as they lie on the device: image i's floats start at row0[i] * fpt
+int vitx_pack_attn_read(vitx_pack *p, float *out, size_t n_floats) {
+    if (!p || !out) { set_error("vitx_pack_attn_read: NULL argument"); return VITX_ERR_ARG; }
+    const PackAttn *am = p->attn.get();
+    const int n = am ? am->n : 0;
+    if (n == 0) { set_error("vitx_pack_attn_read: no forward has run with attention maps on since vitx_pack_attn_enable"); return VITX_ERR_ARG; }
+    const size_t need = (size_t)p->row0[n] * am->fpt;
+    if (n_floats < need) { set_error("vitx_pack_attn_read: the buffer holds %zu floats, the last forward's maps %zu", n_floats, need); return VITX_ERR_ARG; }
+    HIP_TRY(hipSetDevice(p->device));
+    if (p->done_pending) HIP_TRY(hipEventSynchronize(p->done));
+    HIP_TRY(hipMemcpy(out, am->out.p, need * 4, hipMemcpyDeviceToHost));
+    return VITX_OK;
+}
+
 // The dense head of a packed context (include/vitx.h "packed batches").  Every argument check comes before the first device call; the head is
 // built in a local and moved in, so a refused or failed set leaves the head that was set.
 int vitx_pack_dense_set(vitx_pack *p, const float *W, const float *bias, int K, int Dc, uint64_t layer_mask, long max_pixels, int flags) {
@@ -56,7 +101,7 @@ int vitx_pack_dense_set(vitx_pack *p, const float *W, const float *bias, int K, 
     if (const int rc = pack_quiesce(p)) return rc;
     if (off) {
         if (p->dense) { p->scratch_bytes -= p->dense->bytes; p->dense.reset(); }
-        return resize_tables(p, "vitx_pack_dense_set", false, (bool)p->depth, (bool)p->u8);
+        return resize_tables(p, "vitx_pack_dense_set", false, (bool)p->depth, (bool)p->u8, p->rollout());
     }
     auto dn = std::make_unique<PackDense>();
     dn->K = K; dn->Kpad = (int)Kpad; dn->Dc = Dc; dn->mask = mask; dn->flags = flags; dn->cap = p->max_images; dn->max_pixels = max_pixels;
@@ -71,7 +116,7 @@ int vitx_pack_dense_set(vitx_pack *p, const float *W, const float *bias, int K, 
     HIP_TRY(dense_head_upload(*dn, p->dtype, W, bias));
     HIP_TRY(hipMemset(dn->a[0].p, 0, Mp * Dc * 2));
     HIP_TRY(hipDeviceSynchronize());
-    if (const int rc = resize_tables(p, "vitx_pack_dense_set", true, (bool)p->depth, (bool)p->u8)) return rc;
+    if (const int rc = resize_tables(p, "vitx_pack_dense_set", true, (bool)p->depth, (bool)p->u8, p->rollout())) return rc;
     if (p->dense) p->scratch_bytes -= p->dense->bytes;
     p->scratch_bytes += dn->bytes;
     p->dense = std::move(dn);
@@ -129,7 +174,7 @@ int vitx_pack_depth_set(vitx_pack *p, const float *Wp, const float *Wc, const fl
     if (const int rc = pack_quiesce(p)) return rc;
     if (off) {
         if (p->depth) { p->scratch_bytes -= p->depth->bytes; p->depth.reset(); }
-        return resize_tables(p, "vitx_pack_depth_set", (bool)p->dense, false, (bool)p->u8);
+        return resize_tables(p, "vitx_pack_depth_set", (bool)p->dense, false, (bool)p->u8, p->rollout());
     }
     auto dp = std::make_unique<PackDepth>();
     dp->K = K; dp->Kpad = (int)Kpad; dp->Dc = Dc; dp->mask = mask; dp->flags = flags; dp->cap = p->max_images; dp->max_pixels = max_pixels;
@@ -158,7 +203,7 @@ int vitx_pack_depth_set(vitx_pack *p, const float *Wp, const float *Wc, const fl
     HIP_TRY(hipMemset(dp->a[0].p, 0, Mp * Dc * 2));
     if (Wc) HIP_TRY(hipMemset(dp->ac[0].p, 0, Bp * Dc * 2));
     HIP_TRY(hipDeviceSynchronize());
-    if (const int rc = resize_tables(p, "vitx_pack_depth_set", (bool)p->dense, true, (bool)p->u8)) return rc;
+    if (const int rc = resize_tables(p, "vitx_pack_depth_set", (bool)p->dense, true, (bool)p->u8, p->rollout())) return rc;
     if (p->depth) p->scratch_bytes -= p->depth->bytes;
     p->scratch_bytes += dp->bytes;
     p->depth = std::move(dp);
