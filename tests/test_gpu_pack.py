@@ -1,7 +1,7 @@
 """Packed batches on the GPU (include/vitx.h "packed batches"): the variable-length attention against the generic kernel per image, bit for bit,
 with poisoned neighbours; the packed rotary launch against vitx_op_rope per image; a pack of one shape against the rectangular context, bit for
 bit; mixed packs against the float64 restatement of every image at its own shape (tests/rect_data.py) with every mutant outside the gate; pack
-invariance; the table cache; the refusals; vit_cli.py --pack."""
+invariance; the table cache; the four opt-in parts set, dropped and set again in different orders; the refusals; vit_cli.py --pack."""
 import dataclasses
 import functools
 import os
@@ -12,9 +12,12 @@ import numpy as np
 import pytest
 
 import arch_data as AD
+import depth_data as DD
 import map_data as MD
 import pack_data as KD
+import pack_u8_data as UD
 import prefix_data as PD
+import preproc_data as PPD
 import rect_data as XD
 import ref64 as R64
 import text_data as TD
@@ -303,6 +306,86 @@ def test_table_cache_eviction_and_rebuild(pkg, binding, torch_gpu, kind):
     torch.cuda.synchronize()
     assert bool(torch.isfinite(probs).all())
     small.close(); big.close(); model.close()
+
+
+# ------------------------------------------------------------------------------------------------ 7b. the opt-in parts in any order
+def test_parts_set_in_any_order_make_the_same_context(pkg, binding, torch_gpu):
+    """The four opt-in parts that bring segment tables (dense head, depth head, u8 sources, attention rollout) on two contexts of the 4-head patch-16
+    variant, bf16, the mixed pack fed from u8 originals of seven different sizes.  A turns them on as dense, depth, u8, rollout; B as rollout, u8, depth,
+    dense, then takes depth off and sets it again, then u8 likewise.  The same forward_u8 call, twice, then has equal bits on both -- probabilities,
+    logits, labels, scores, kept logits, depth maps, fine planes, offsets, class maps, rollout rows -- and the bits of its first run (the forward is
+    deterministic), with equal launch counts and scratch bytes; and with the parts taken off in a third order each context is back at the scratch bytes
+    it had before any part was set (its grids' tables built: a device call with no part on does that and allocates nothing else)."""
+    torch = torch_gpu
+    model = binding.Model(KD.variant_file(pkg, "p16h4"))
+    shapes = KD.mixed_shapes(16)
+    imgs = UD.originals()
+    assert len(imgs) == len(shapes) and len({im.shape for im in imgs}) == len(imgs)
+    mean, std = PPD.mean_std255(PPD.IMAGENET)
+    pp = binding.Preproc.make(resize_a=16, resize_b=16, filter=PPD.PP_PIL_BICUBIC, mean255=mean, std255=std)
+    tokens = int(binding.pack_check(model, shapes, 2 ** 31 - 1, len(shapes))[-1])
+    rng = np.random.default_rng(12)
+    W, b = (rng.standard_normal((5, D)) * 0.25).astype(np.float32), rng.standard_normal(5).astype(np.float32)
+    wp, wc = ((rng.standard_normal((21, D)) * 0.05).astype(np.float32) for _ in range(2))
+    db, bins = rng.standard_normal(21).astype(np.float32), DD.bins_ud(21)
+    on = {"dense": lambda c: c.dense_set(W, b, None, score=True, logits=True),
+          "depth": lambda c: c.depth_set(wp, wc, db, bins, None, 2, 3.0, 7.0, logits=True, fine=True),
+          "u8": lambda c: c.u8_set(pp, max_src_bytes=sum(im.size for im in imgs)),
+          "rollout": lambda c: c.attn_enable(None, rollout=True)}
+    off = {"dense": lambda c: c.dense_set(None), "depth": lambda c: c.depth_set(None), "u8": lambda c: c.u8_set(None, 0), "rollout": lambda c: c.attn_disable()}
+    A, B = (binding.PackContext(model, device=0, max_tokens=tokens, max_images=len(shapes), dtype=binding.BF16) for _ in range(2))
+    pix = torch.zeros(sum(3 * h * w for h, w in shapes), dtype=torch.float32, device="cuda")
+    probs = torch.zeros((len(shapes), model.num_classes), dtype=torch.float32, device="cuda")
+    base = []
+    for c in (A, B):
+        c.forward_device(pix.data_ptr(), shapes, probs.data_ptr())
+        torch.cuda.synchronize()
+        base.append(c.scratch_bytes)
+    assert base[0] == base[1]
+    for part in ("dense", "depth", "u8", "rollout"):
+        on[part](A)
+    for part in ("rollout", "u8", "depth", "dense"):
+        on[part](B)
+    assert B.scratch_bytes == A.scratch_bytes > base[0]
+    for part in ("depth", "u8"):
+        off[part](B)
+        assert base[0] < B.scratch_bytes < A.scratch_bytes, part
+        on[part](B)
+        assert B.scratch_bytes == A.scratch_bytes, part
+
+    def run(c):
+        """Every output of one forward_u8 call as a flat list of (name, array), and the counters."""
+        p, lg = c.forward_u8(imgs, shapes)
+        lab, sc, dlg = c.dense_read()
+        dm, fn, plg, offs = c.depth_read()
+        maps = c.attn_read()
+        out = [("probs", p), ("logits", lg), ("offsets", offs)]
+        for name, per_image in (("labels", lab), ("scores", sc), ("dense logits", dlg), ("depth", dm), ("fine", fn), ("depth logits", plg),
+                                ("class maps", [m[0] for m in maps]), ("rollout", [m[1] for m in maps])):
+            out += [(f"{name} of image {i}", a) for i, a in enumerate(per_image)]
+        return out, (c.launches, c.scratch_bytes, c.dense_scratch_bytes(), c.depth_scratch_bytes())
+
+    def same(x, y, what):
+        assert len(x) == len(y)
+        for (name, a), (_, b_) in zip(x, y):
+            a, b_ = np.ascontiguousarray(a), np.ascontiguousarray(b_)
+            assert a.shape == b_.shape and a.size and np.array_equal(a.view(np.uint8), b_.view(np.uint8)), (what, name)
+
+    first = None
+    for call in range(2):
+        (oa, ca), (ob, cb) = run(A), run(B)
+        assert all(np.isfinite(np.asarray(a, np.float64)).all() for _, a in oa)
+        same(oa, ob, f"call {call}: A against B")
+        assert ca == cb, (call, ca, cb)
+        if first is None:
+            first = oa
+        else:
+            same(first, oa, "A: the second call against the first")
+    for c, was in zip((A, B), base):
+        for part in ("u8", "dense", "rollout", "depth"):
+            off[part](c)
+        assert c.scratch_bytes == was
+    A.close(); B.close(); model.close()
 
 
 # ------------------------------------------------------------------------------------------------ 8. refusals at creation

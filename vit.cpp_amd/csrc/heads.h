@@ -138,16 +138,21 @@ struct DenseHead : PatchHead {
     DevMem logits;               // VITX_DENSE_LOGITS: [cap][gh * gw][K] f32, the patch logits kept for vitx_dense_read
 };
 
+// What the checks of a packed forward call give it while a dense head is set (packed_forward.cpp check_dense; kernels.h dense_pack_tables)
+struct PackDenseCall {
+    std::vector<int32_t> grids, outs;    // [n][2] each, the patch grids and the output shapes
+    std::vector<int64_t> pix0;   // [n + 1], the running pixel count of the outputs
+    std::vector<int32_t> tile0;  // [n + 1], the running tile count of the label launch
+    int cells = 0;               // the widest tile window
+};
+
 // the dense head of a packed context (vitx_pack_dense_set): the same linear map over ALL rows of the pack -- a[0] [round_up(max_tokens, tm)][Dc],
 // acc[0] the same rows x Kpad, the prefix rows computed and never used -- and one label map per image at its own size, the maps end to end
 struct PackDense : DenseHead {
     long max_pixels = 0;         // elements of labels (and score); logits: [max_tokens][K], every row of the pack
     size_t bytes = 0;            // device bytes of everything above: what the head adds to vitx_pack_scratch_bytes
     std::vector<int32_t> next_out;       // vitx_pack_dense_out: the output shapes [n][2] of the next forward (empty: the images' own shapes)
-    std::vector<int32_t> grids, outs;    // [n][2] each, of the last call that passed its checks with the head set (PackCall, packed_context.h)
-    std::vector<int64_t> pix0;   // [n + 1], the same
-    std::vector<int32_t> tile0;  // [n + 1], the same
-    int cells = 0;               // the widest tile window of that call
+    PackDenseCall last;          // of the last call that passed its checks with the head set
 };
 
 // the depth head (vitx_depth_set)
@@ -169,6 +174,14 @@ struct DepthHead : PatchHead {
     std::vector<DevMem> o;       // per slice, class half only: [round_up(slice cap, tm)][Kpad] f32, the offsets
 };
 
+// The same while a depth head is set (check_depth; kernels.h depth_pack_tables)
+struct PackDepthCall {
+    std::vector<int32_t> grids, outs;    // [n][2] each, the patch grids and the depth maps' shapes
+    std::vector<int64_t> pix0, fine0;    // [n + 1] each, the running pixel counts of the maps and of the fine planes
+    std::vector<int32_t> ftile0, otile0; // [n + 1] each, the running tile counts of the fine and the resize launch
+    int cells = 0;               // the widest fine-tile window
+};
+
 // the depth head of a packed context (vitx_pack_depth_set): the same two linear maps over ALL rows of the pack -- a[0] [round_up(max_tokens, tm)][Dc],
 // acc[0] the same rows x Kpad, the prefix rows computed and never used; with a class half ac[0] [round_up(max_images, tm)][Dc], the class rows gathered
 // from a[0], and o[0] their offsets -- and one fine plane and one depth map per image at its own size, planes and maps end to end
@@ -176,10 +189,7 @@ struct PackDepth : DepthHead {
     long max_pixels = 0;         // floats of depth; fine: u^2 max_tokens floats; logits: [max_tokens][K], every row of the pack; off: [max_images][K]
     size_t bytes = 0;            // device bytes of everything above: what the head adds to vitx_pack_scratch_bytes
     std::vector<int32_t> next_out;       // vitx_pack_depth_out: the output shapes [n][2] of the next forward (empty: the images' own shapes)
-    std::vector<int32_t> grids, outs;    // [n][2] each, of the last call that passed its checks with the head set (PackCall, packed_context.h)
-    std::vector<int64_t> pix0, fine0;    // [n + 1] each, the same
-    std::vector<int32_t> ftile0, otile0; // [n + 1] each, the same
-    int cells = 0;               // the widest fine-tile window of that call
+    PackDepthCall last;          // of the last call that passed its checks with the head set
 };
 
 // ---- the launch sequences of the four heads (heads.cpp) --------------------------------------------------------------------------------

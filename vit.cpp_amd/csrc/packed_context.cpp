@@ -1,5 +1,7 @@
 // packed_context.cpp -- the life of a packed context (packed_context.h; include/vitx.h "packed batches"): creation with every refusal before the
-// first device call, the counters, and the table cache -- per grid the resampled position table and, for `rope` files, a piece of the rotary arenas.
+// first device call, the counters, the table cache -- per grid the resampled position table and, for `rope` files, a piece of the rotary arenas --
+// and what the set calls of the opt-in parts share: the wait for the context, the segment tables resized for a set of parts, the commit, the
+// declaration of shapes for the next call.
 // One stream, no sub-batch split, no hipGraph cache; block matrices are expanded at upload, as in the text context (text_forward.cpp).
 #include <algorithm>
 #include <new>
@@ -114,9 +116,9 @@ int pack_quiesce(vitx_pack *p) {
     return wait_done(p);
 }
 
-// the segment tables with the parts of the heads, of the u8 sources and of the attention rollout that will be set behind them (PackLayout): a fresh zeroed buffer in place of the old one
-int resize_tables(vitx_pack *p, const char *api, bool dense, bool depth, bool u8, bool rollout) {
-    const size_t ints = PackLayout{(size_t)p->max_images, dense, depth, u8, rollout}.ints();
+// the segment tables for the parts that will be set (PackLayout): a fresh zeroed buffer in place of the old one
+int resize_tables(vitx_pack *p, const char *api, unsigned parts) {
+    const size_t ints = PackLayout{(size_t)p->max_images, parts}.ints();
     if (p->host.size() == ints) return VITX_OK;
     int *t = nullptr;
     HIP_TRY(hipMalloc((void **)&t, ints * 4));
@@ -125,6 +127,20 @@ int resize_tables(vitx_pack *p, const char *api, bool dense, bool depth, bool u8
     (void)hipFree(p->tab);
     p->scratch_bytes += ints * 4; p->scratch_bytes -= p->host.size() * 4;
     p->tab = t; p->host.assign(ints, 0);
+    return VITX_OK;
+}
+
+// the end of a set call: a failed resize leaves the count, and the state the caller is about to replace, as they were
+int pack_commit(vitx_pack *p, const char *api, unsigned parts, size_t old_bytes, size_t new_bytes) {
+    if (const int rc = resize_tables(p, api, parts)) return rc;
+    p->scratch_bytes -= old_bytes; p->scratch_bytes += new_bytes;
+    return VITX_OK;
+}
+
+int pack_next_shapes(const vitx_pack *p, const char *api, const int32_t *shapes, int n, std::vector<int32_t> *next) {
+    if (!shapes || n == 0) { next->clear(); return VITX_OK; }
+    if (n < 1 || n > p->max_images) { set_error("%s: n = %d is outside 1 .. max_images = %d", api, n, p->max_images); return VITX_ERR_ARG; }
+    next->assign(shapes, shapes + (size_t)2 * n);
     return VITX_OK;
 }
 

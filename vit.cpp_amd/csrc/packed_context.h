@@ -1,8 +1,12 @@
 // packed_context.h -- the packed context (struct vitx_pack); include/vitx.h "packed batches": n images, each with its own h_i x w_i, their
 // tokens end to end in one [sum N_i][D] residual stream, one forward.  Modelled on the text context (text_context.h): its own scratch, one
-// stream, no sub-batches, no graph cache, no LayerNorm fusion.  Three units stand on it, split like the image context's: packed_context.cpp
-// (creation, counters, the table cache), packed_forward.cpp (the checks of a call, the forward), packed_outputs.cpp (features, the dense and the depth head, attention maps)
-// and packed_input.cpp (u8 sources).
+// stream, no sub-batches, no graph cache, no LayerNorm fusion.  Four units stand on it: packed_context.cpp (creation, counters, the table
+// cache, what the set calls share), packed_forward.cpp (the checks of a call, the forward, the entry points), packed_outputs.cpp (features,
+// attention maps, the dense and the depth head) and packed_input.cpp (u8 sources).
+// Four opt-in PARTS bring segment tables and state of a call with them: the dense head, the depth head, u8 sources, attention rollout.  Each is
+// one bit (PackPart), one or two lines of kPackTables, one struct of what its check gives a call (PackDenseCall, PackDepthCall in heads.h,
+// PackU8Call, PackRolloutCall here) and one struct of what its set call holds (PackDense, PackDepth in heads.h, PackU8, PackAttn here).
+// DESIGN.md ("Packed batches", Parts) lists the places a new part is added in.
 // Internal: callers see the opaque vitx_pack of include/vitx.h.
 #pragma once
 #include <memory>
@@ -11,54 +15,70 @@
 
 using namespace vitx;
 
-// The segment tables of a call, in ints into vitx_pack::tab / host (cap = max_images): row0 [cap + 1] | qb0 [cap + 1] | toff [cap] and, while a
-// dense head is set, behind them tile0 [cap + 1] | seg [cap][kDenseSegInts] and, while a depth head is set, behind those ftile0 [cap + 1] |
-// otile0 [cap + 1] | dseg [cap][kDepthSegInts] and, while u8 sources are on (vitx_pack_u8_set), behind those ptile0 [cap + 1] | pseg [cap][kPpSegInts]
-// (kernels.h) and, while attention rollout is on (vitx_pack_attn_enable), behind those rblk0 [cap + 1] | sq0 [cap + 1] (kernels.h attn_pack_tables).
-// One buffer, one upload; a new table goes in here.
-struct PackLayout {
-    size_t cap;
-    bool dense, depth;                   // the heads whose tables the buffer holds
-    bool u8 = false;                     // the u8 preprocessing's tables too
-    bool rollout = false;                // the attention rollout's tables too
-    size_t row0() const { return 0; }
-    size_t qb0() const { return row0() + cap + 1; }
-    size_t toff() const { return qb0() + cap + 1; }
-    size_t tile0() const { return toff() + cap; }
-    size_t seg() const { return tile0() + cap + 1; }
-    size_t ftile0() const { return dense ? seg() + cap * kDenseSegInts : tile0(); }
-    size_t otile0() const { return ftile0() + cap + 1; }
-    size_t dseg() const { return otile0() + cap + 1; }
-    size_t ptile0() const { return depth ? dseg() + cap * kDepthSegInts : ftile0(); }
-    size_t pseg() const { return ptile0() + cap + 1; }
-    size_t rblk0() const { return u8 ? pseg() + cap * kPpSegInts : ptile0(); }
-    size_t sq0() const { return rblk0() + cap + 1; }
-    size_t ints() const { return rollout ? sq0() + cap + 1 : rblk0(); }
+enum PackPart : unsigned { kDense = 1u << 0, kDepth = 1u << 1, kU8 = 1u << 2, kRollout = 1u << 3 };
+
+// The segment tables of a call, in their order in vitx_pack::tab / host: `per_image` ints per image the context holds (cap = max_images) and `plus`
+// more.  A table of part 0 is always there, another while its part is on.  One buffer, one upload; a new table goes at the end of this list.
+struct PackTable { unsigned part; int per_image, plus; };
+constexpr PackTable kPackTables[] = {
+    {0, 1, 1}, {0, 1, 1}, {0, 1, 0},                                 // row0 [cap + 1] | qb0 [cap + 1] | toff [cap]
+    {kDense, 1, 1}, {kDense, kDenseSegInts, 0},                      // tile0 [cap + 1] | seg [cap][kDenseSegInts]               (kernels.h dense_pack_tables)
+    {kDepth, 1, 1}, {kDepth, 1, 1}, {kDepth, kDepthSegInts, 0},      // ftile0 [cap + 1] | otile0 [cap + 1] | dseg [cap][kDepthSegInts]  (depth_pack_tables)
+    {kU8, 1, 1}, {kU8, kPpSegInts, 0},                               // ptile0 [cap + 1] | pseg [cap][kPpSegInts]                (pp_pack_tables)
+    {kRollout, 1, 1}, {kRollout, 1, 1},                              // rblk0 [cap + 1] | sq0 [cap + 1]                          (attn_pack_tables)
 };
 
-// What the host-only checks of a forward call (packed_forward.cpp check_call) give the forward: made once per call, before its first device call
+struct PackLayout {
+    size_t cap;
+    unsigned parts;                      // PackPart bits: the parts whose tables the buffer holds
+    enum Table { kRow0, kQb0, kToff, kTile0, kSeg, kFtile0, kOtile0, kDseg, kPtile0, kPseg, kRblk0, kSq0, kTables };
+    static_assert(sizeof(kPackTables) / sizeof(kPackTables[0]) == kTables, "one name per table");
+    // the ints in front of table t: the tables before it whose part is on (a table of a part that is off is placed as if that part alone were on too)
+    size_t at(int t) const {
+        const unsigned on = parts | (t < kTables ? kPackTables[t].part : 0);
+        size_t o = 0;
+        for (int k = 0; k < t; ++k) if (!kPackTables[k].part || (on & kPackTables[k].part)) o += cap * kPackTables[k].per_image + kPackTables[k].plus;
+        return o;
+    }
+    size_t row0() const { return at(kRow0); }
+    size_t qb0() const { return at(kQb0); }
+    size_t toff() const { return at(kToff); }
+    size_t tile0() const { return at(kTile0); }
+    size_t seg() const { return at(kSeg); }
+    size_t ftile0() const { return at(kFtile0); }
+    size_t otile0() const { return at(kOtile0); }
+    size_t dseg() const { return at(kDseg); }
+    size_t ptile0() const { return at(kPtile0); }
+    size_t pseg() const { return at(kPseg); }
+    size_t rblk0() const { return at(kRblk0); }
+    size_t sq0() const { return at(kSq0); }
+    size_t ints() const { return at(kTables); }
+};
+
+// What check_u8 gives a call whose d_imgs are u8 sources (kernels.h pp_pack_tables): the running tile count of the preprocessing launch [n + 1], its
+// table rows, its LDS and the bytes of the sources
+struct PackU8Call {
+    bool on = false;
+    std::vector<int32_t> tile0, seg;
+    int lds = 0;
+    int64_t src_bytes = 0;
+};
+// What check_attn gives a call while attention rollout is on (kernels.h attn_pack_tables): the running counts of 16-row blocks and of N_i^2 [n + 1]
+// each, the widest image of the call
+struct PackRolloutCall {
+    std::vector<int32_t> rblk0, sq0;
+    int n_max = 0;
+};
+
+// What the host-only checks of a forward call (packed_forward.cpp check_call) give the forward: made once per call, before its first device call.
+// pack_forward takes a part's struct over as that part's `last` with one swap.
 struct PackCall {
     std::vector<int32_t> row0;           // [n + 1]: image i's rows of the pack are row0[i] .. row0[i + 1] - 1
     std::vector<uint64_t> want;          // the distinct grids, in order of first appearance, as (gh << 32 | gw)
-    std::vector<int32_t> grids, outs;    // with a dense head set: [n][2] each, the patch grids and the output shapes
-    std::vector<int64_t> pix0;           // [n + 1], the running pixel count of the outputs
-    std::vector<int32_t> tile0;          // [n + 1], the running tile count of the label launch
-    int cells = 0;                       // the widest tile window (kernels.h dense_pack_tables)
-    // with a depth head set (kernels.h depth_pack_tables): the grids again, the depth maps' shapes, the running pixel counts of the maps and of the
-    // fine planes, the running tile counts of the fine and the resize launch, the widest fine-tile window
-    std::vector<int32_t> dgrids, douts;
-    std::vector<int64_t> dpix0, dfine0;
-    std::vector<int32_t> ftile0, otile0;
-    int dcells = 0;
-    // with u8 sources declared for the call (kernels.h pp_pack_tables): the running tile count of the preprocessing launch, its table rows, its LDS
-    // and the bytes of the sources
-    bool u8 = false;
-    std::vector<int32_t> ptile0, pseg;
-    int plds = 0;
-    int64_t src_bytes = 0;
-    // with attention rollout on (kernels.h attn_pack_tables): the running counts of 16-row blocks and of N_i^2, the widest image of the call
-    std::vector<int32_t> rblk0, sq0;
-    int n_max = 0;
+    PackDenseCall dense;                 // with a dense head set
+    PackDepthCall depth;                 // with a depth head set
+    PackU8Call u8;                       // with u8 sources declared for the call
+    PackRolloutCall roll;                // with attention rollout on
 };
 
 // Attention maps (vitx_pack_attn_enable): the image context's AttnMaps per image of a pack.  Image i's floats of `out` start at row0[i] * fpt: the
@@ -71,10 +91,9 @@ struct PackAttn {
     DevMem out;                          // [max_tokens][fpt] f32
     DevMem roll[2];                      // rollout: [max_sq] f32 x 2, A^_l written into one, the product R_l in place of it (ping-pong)
     DevMem cls_last;                     // rollout without the last layer in the mask: its class-token maps, [max_tokens][H] f32
-    size_t bytes = 0;                    // what the enable added to vitx_pack_scratch_bytes besides the tables
+    size_t bytes = 0;                    // device bytes of everything above: what the enable adds to vitx_pack_scratch_bytes besides the tables
     int n = 0;                           // images of the last forward with maps on (0: none)
-    std::vector<int32_t> rblk0, sq0;     // of that forward (rollout)
-    int n_max = 0;
+    PackRolloutCall last;                // of that forward (rollout)
     bool rollout() const { return (flags & VITX_ATTN_ROLLOUT) != 0; }
     bool selects(int il) const { return (mask >> il) & 1; }
 };
@@ -85,9 +104,8 @@ struct PackU8 {
     size_t max_src_bytes = 0;
     DevMem src;                          // max_src_bytes rounded up to 4: the sources of vitx_pack_forward_u8 on the device
     bool own_img = false;                // vitx_pack::img was allocated by the set (else by an earlier vitx_pack_forward: it stays when u8 goes off)
-    size_t bytes = 0;                    // what the set added to vitx_pack_scratch_bytes besides the tables
-    bool declared = false;               // vitx_pack_u8_sources: the next forward call's d_imgs are u8 sources of next_src [n][2] = (ny, nx)
-    std::vector<int32_t> next_src;
+    size_t bytes = 0;                    // device bytes the set allocated: what it adds to vitx_pack_scratch_bytes besides the tables
+    std::vector<int32_t> next_src;       // vitx_pack_u8_sources: the next forward call's d_imgs are u8 sources of these shapes [n][2] = (ny, nx) (empty: f32 pixels)
 };
 
 // One grid of the table cache: the position table resampled to gh x gw and the grid's place in the rotary arenas
@@ -120,7 +138,7 @@ struct vitx_pack {
     void *Z = nullptr;                   // [Bpad][D] operand type: the class rows through the final norm, Bpad = max_images rounded up
     float *logits = nullptr, *probs = nullptr;      // [Bpad][C_pad], [max_images][C] f32
     float *logits_out = nullptr;         // [max_images][C] f32: the dense logits of the host entry point
-    float *img = nullptr;                // the host entry point's pixels on the device (allocated by its first call, or by vitx_pack_u8_set: the u8
+    DevMem img;                          // the host entry point's f32 pixels on the device (allocated by its first call, or by vitx_pack_u8_set: the u8
                                          // preprocessing writes them there)
     int *tab = nullptr;                  // the segment tables of a call (PackLayout)
     std::vector<int> host;               // the same on the host: the staging buffer of the upload
@@ -139,16 +157,17 @@ struct vitx_pack {
     std::vector<Retired> retired;        // own position tables of dropped grids, kept for the next grid they hold: hipFree would wait for the whole
                                          // device, and a call that drops a table must not wait for the caller's stream (oldest first)
     int feat_flags = 0;                  // vitx_pack_feat_enable
-    float *feat = nullptr;               // [max_tokens][D] f32 final-norm rows of the last forward (allocated by vitx_pack_feat_enable)
+    DevMem feat;                         // [max_tokens][D] f32 final-norm rows of the last forward (allocated by vitx_pack_feat_enable)
     int feat_n = 0;                      // images of the last forward with features on (0: none)
     std::unique_ptr<PackDense> dense;    // vitx_pack_dense_set (null: off); its device memory is its own
     std::unique_ptr<PackDepth> depth;    // vitx_pack_depth_set (null: off); its device memory is its own
     std::unique_ptr<PackU8> u8;          // vitx_pack_u8_set (null: off)
     std::unique_ptr<PackAttn> attn;      // vitx_pack_attn_enable (null: off); its device memory is its own
-    bool rollout() const { return attn && attn->rollout(); }
+    bool rollout() const { return attn && attn->rollout(); }         // the rollout tables are there; class maps alone add no table
     int launches = 0, pe_launches = 0;   // kernel launches of the last forward, and how many of them were patch embeddings
     size_t scratch_bytes = 0;            // device bytes of activation scratch and tables held now
-    PackLayout layout() const { return PackLayout{(size_t)max_images, (bool)dense, (bool)depth, (bool)u8, rollout()}; }
+    unsigned parts() const { return (dense ? kDense : 0u) | (depth ? kDepth : 0u) | (u8 ? kU8 : 0u) | (rollout() ? kRollout : 0u); }
+    PackLayout layout() const { return PackLayout{(size_t)max_images, parts()}; }
     // image i of the last call that passed its checks: its patch rows, and where they start in an output that holds every image's patch rows end to end
     size_t patch_rows(int i) const { return (size_t)(row0[i + 1] - row0[i] - Tp); }
     size_t patch_at(int i) const { return (size_t)(row0[i] - i * Tp); }
@@ -158,8 +177,6 @@ struct vitx_pack {
         for (PackGrid &g : grids) if (g.own) (void)hipFree(g.pos);
         for (Retired &r : retired) (void)hipFree(r.pos);
         if (rope_host) (void)hipHostFree(rope_host);
-        if (img) (void)hipFree(img);
-        if (feat) (void)hipFree(feat);
         if (uploaded) (void)hipEventDestroy(uploaded);
         if (done) (void)hipEventDestroy(done);
         if (stream) (void)hipStreamDestroy(stream);
@@ -171,9 +188,20 @@ struct vitx_pack {
 PackGrid *find_grid(vitx_pack *p, int gh, int gw);
 int wait_done(vitx_pack *p);
 int resolve_grids(vitx_pack *p, const std::vector<uint64_t> &want, hipStream_t st);
-// Before buffers and tables change hands (the set calls): nothing of this context is in flight.  resize_tables: the segment tables with the parts
-// that will be set behind them (PackLayout), a fresh zeroed buffer in place of the old one.
+// What the set calls share (packed_context.cpp).  pack_quiesce: before buffers and tables change hands, nothing of this context is in flight.
+// resize_tables: the segment tables for the parts that will be set (PackLayout), a fresh zeroed buffer in place of the old one.  pack_commit:
+// the end of a set call whose new state is built -- the tables for `parts`, then the old state's bytes leave vitx_pack_scratch_bytes and the new
+// state's enter; the caller moves the new state in behind it.  alloc_counted: one device allocation of a part, added to the count it is given, so
+// that what a part adds to vitx_pack_scratch_bytes is what it allocated; false when the device has no room (DevMem::alloc).
 int pack_quiesce(vitx_pack *p);
-int resize_tables(vitx_pack *p, const char *api, bool dense, bool depth, bool u8, bool rollout);
+int resize_tables(vitx_pack *p, const char *api, unsigned parts);
+int pack_commit(vitx_pack *p, const char *api, unsigned parts, size_t old_bytes, size_t new_bytes);
+inline bool alloc_counted(DevMem &m, size_t bytes, size_t *count) {
+    if (!m.alloc(bytes)) return false;
+    *count += bytes;
+    return true;
+}
+// vitx_pack_dense_out, vitx_pack_depth_out, vitx_pack_u8_sources: the shapes [n][2] a part declares for the next forward call (NULL or n = 0: none)
+int pack_next_shapes(const vitx_pack *p, const char *api, const int32_t *shapes, int n, std::vector<int32_t> *next);
 // Attention maps (packed_forward.cpp): what vitx_pack_attn_enable and vitx_pack_attn_check refuse in their arguments, host only
 int pack_attn_args(const char *api, int L, uint64_t layer_mask, int flags, long max_sq_tokens);

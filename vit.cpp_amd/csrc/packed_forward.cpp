@@ -1,12 +1,18 @@
 // packed_forward.cpp -- a call of a packed context (packed_context.h; include/vitx.h "packed batches"): its host-only checks, made once, and
-// the forward.  The blocks are the image forward's row-wise launches through the same dispatchers (GEMMs, LayerNorm, activation, gate, pre-norm
-// do not care where one image ends); new are the three launches that must know: the variable-length attention (attention_packed.hip), the
-// rotary embeddings by a segment table (rope.hip) and the class-row gather (text_embed.hip).  The patch embedding is the rectangular context's
-// kernel, one launch per run of consecutive images of one shape.  Attention maps (vitx_pack_attn_enable) are the
-// image forward's launch sequence on the packed map kernels (attention_map.hip), in front of each layer's attention.  The opt-in heads are the dense and the depth head (packed_outputs.cpp): the operand rows
-// and the head GEMM over all rows of the pack, then the label launch (dense_label.hip) or the fine and resize launches (depth_map.hip) by their own
-// segment tables, one map per image at its own size.  With u8 sources declared for a call (packed_input.cpp) one launch in front of the patch embedding
-// stretches every source to its image's shape into the context's pixel buffer (image_preprocess.hip).  No LayerNorm fusion, no class-token tail.
+// the forward, and the entry points of both.
+// The checks: check_shapes for every call, then one check_* per opt-in part that is on (dense, depth, attention rollout, u8), each filling its
+// part's struct of the PackCall (packed_context.h); check_call runs them for a forward, the vitx_pack_*_check entry points run one each and
+// copy out of the same struct.
+// The forward: pack_forward takes the call's structs over with one swap per part, resolves the grids, has every part write its tables into the
+// staging buffer (*_tables, in layout order) and uploads them in one copy; then the launches.  The blocks are the image forward's row-wise
+// launches through the same dispatchers (GEMMs, LayerNorm, activation, gate, pre-norm do not care where one image ends); new are the three
+// launches that must know: the variable-length attention (attention_packed.hip), the rotary embeddings by a segment table (rope.hip) and the
+// class-row gather (text_embed.hip).  The patch embedding is the rectangular context's kernel, one launch per run of consecutive images of
+// one shape.  With u8 sources declared for the call one launch in front of it stretches every source to its image's shape into the context's
+// pixel buffer (image_preprocess.hip).  Attention maps are the image forward's launch sequence on the packed map kernels (attention_map.hip), in
+// front of each layer's attention.  The dense and the depth head: the operand rows and the head GEMM over all rows of the pack, then the label
+// launch (dense_label.hip) or the fine and resize launches (depth_map.hip) by their own segment tables, one map per image at its own size.
+// No LayerNorm fusion, no class-token tail.
 #include <algorithm>
 
 #include "depth_bins.h"
@@ -34,8 +40,8 @@ int check_shapes(const char *api, const vitx_model *m, const int32_t *shapes, in
 
 // What a forward call adds to check_shapes while a dense head of K classes and max_pixels is set (vitx_pack_dense_check's text; `shapes` has passed
 // check_shapes): the output shapes -- out_shapes [n_out][2], or the images' own -- against the grids and the buffers.  On success the head's
-// tables of the call: c->grids, outs, pix0, tile0, cells.
-int check_dense(const char *api, const vitx_model *m, const int32_t *shapes, const int32_t *out_shapes, int n_out, int n, int K, long max_pixels, PackCall *c) {
+// tables of the call in *c.
+int check_dense(const char *api, const vitx_model *m, const int32_t *shapes, const int32_t *out_shapes, int n_out, int n, int K, long max_pixels, PackDenseCall *c) {
     if (K < 1) { set_error("%s: K = %d classes", api, K); return VITX_ERR_ARG; }
     if (K > kDenseMaxK) { set_error("%s: K = %d classes above %d (labels are bytes)", api, K, kDenseMaxK); return VITX_ERR_UNSUPPORTED; }
     if (max_pixels < 1) { set_error("%s: max_pixels = %ld", api, max_pixels); return VITX_ERR_ARG; }
@@ -57,16 +63,16 @@ int check_dense(const char *api, const vitx_model *m, const int32_t *shapes, con
 }
 
 // The same for a depth head of K bins, upsampling u and max_pixels (vitx_pack_depth_check's text): the output shapes against the fine planes and the
-// buffers.  On success the head's tables of the call: c->dgrids, douts, dpix0, dfine0, ftile0, otile0, dcells.
-int check_depth(const char *api, const vitx_model *m, const int32_t *shapes, const int32_t *out_shapes, int n_out, int n, int K, int u, long max_pixels, PackCall *c) {
+// buffers.  On success the head's tables of the call in *c.
+int check_depth(const char *api, const vitx_model *m, const int32_t *shapes, const int32_t *out_shapes, int n_out, int n, int K, int u, long max_pixels, PackDepthCall *c) {
     if (K < 1) { set_error("%s: K = %d bins", api, K); return VITX_ERR_ARG; }
     if (K > kDepthMaxK) { set_error("%s: K = %d bins above %d", api, K, kDepthMaxK); return VITX_ERR_UNSUPPORTED; }
     if (u != 1 && u != 2 && u != 4) { set_error("%s: upsample = %d, not 1, 2 or 4", api, u); return VITX_ERR_UNSUPPORTED; }
     if (max_pixels < 1) { set_error("%s: max_pixels = %ld", api, max_pixels); return VITX_ERR_ARG; }
     if (out_shapes && n_out != n) { set_error("%s: output shapes were given for %d images, the call has %d", api, n_out, n); return VITX_ERR_ARG; }
     const int P = m->hp.patch_size;
-    c->dgrids.resize((size_t)2 * n); c->douts.resize((size_t)2 * n);
-    c->dpix0.resize((size_t)n + 1); c->dfine0.resize((size_t)n + 1); c->ftile0.resize((size_t)n + 1); c->otile0.resize((size_t)n + 1);
+    c->grids.resize((size_t)2 * n); c->outs.resize((size_t)2 * n);
+    c->pix0.resize((size_t)n + 1); c->fine0.resize((size_t)n + 1); c->ftile0.resize((size_t)n + 1); c->otile0.resize((size_t)n + 1);
     for (int i = 0; i < n; ++i) {
         const int gh = shapes[2 * i] / P, gw = shapes[2 * i + 1] / P;
         const int oh = out_shapes ? out_shapes[2 * i] : shapes[2 * i], ow = out_shapes ? out_shapes[2 * i + 1] : shapes[2 * i + 1];
@@ -78,38 +84,38 @@ int check_depth(const char *api, const vitx_model *m, const int32_t *shapes, con
             set_error("%s: image %d: output %d x %d outside the fine plane %d x %d .. %d (upsampling only)", api, i, oh, ow, u * gh, u * gw, kDepthMaxOut);
             return VITX_ERR_ARG;
         }
-        c->dgrids[2 * i] = gh; c->dgrids[2 * i + 1] = gw; c->douts[2 * i] = oh; c->douts[2 * i + 1] = ow;
+        c->grids[2 * i] = gh; c->grids[2 * i + 1] = gw; c->outs[2 * i] = oh; c->outs[2 * i + 1] = ow;
     }
-    if (!depth_pack_tables(c->dgrids.data(), c->douts.data(), n, u, c->dpix0.data(), c->dfine0.data(), c->ftile0.data(), c->otile0.data(), &c->dcells)) {
+    if (!depth_pack_tables(c->grids.data(), c->outs.data(), n, u, c->pix0.data(), c->fine0.data(), c->ftile0.data(), c->otile0.data(), &c->cells)) {
         set_error("%s: the call's outputs hold more than 2^31 - 1 tiles", api);
         return VITX_ERR_ARG;
     }
-    if (c->dpix0[n] > (int64_t)max_pixels) { set_error("%s: the call's outputs hold %lld pixels, above max_pixels = %ld", api, (long long)c->dpix0[n], max_pixels); return VITX_ERR_ARG; }
+    if (c->pix0[n] > (int64_t)max_pixels) { set_error("%s: the call's outputs hold %lld pixels, above max_pixels = %ld", api, (long long)c->pix0[n], max_pixels); return VITX_ERR_ARG; }
     return VITX_OK;
 }
 
 // What a forward call adds while u8 sources are declared for it (vitx_pack_u8_check's text; `shapes` has passed check_shapes): the sources' shapes
 // [n_src][2] = (ny, nx) against the call, the tables (pp_pack_tables: its refusals) and the bytes against max_src_bytes (0: no bound).  On success the
-// preprocessing's tables of the call: c->ptile0, pseg, plds, src_bytes.
-int check_u8(const char *api, const vitx_preproc &pp, const int32_t *src_shapes, int n_src, const int32_t *shapes, int n, size_t max_src_bytes, PackCall *c, int64_t *src0) {
+// preprocessing's tables of the call in *c.
+int check_u8(const char *api, const vitx_preproc &pp, const int32_t *src_shapes, int n_src, const int32_t *shapes, int n, size_t max_src_bytes, PackU8Call *c, int64_t *src0) {
     if (!src_shapes) { set_error("%s: NULL argument", api); return VITX_ERR_ARG; }
     if (n_src != n) { set_error("%s: u8 sources were declared for %d images, the call has %d", api, n_src, n); return VITX_ERR_ARG; }
     std::vector<int64_t> s0((size_t)n + 1);
-    c->ptile0.resize((size_t)n + 1); c->pseg.resize((size_t)n * kPpSegInts);
-    if (const int rc = pp_pack_tables(api, pp, src_shapes, shapes, n, s0.data(), nullptr, c->ptile0.data(), c->pseg.data(), &c->plds)) return rc;
+    c->tile0.resize((size_t)n + 1); c->seg.resize((size_t)n * kPpSegInts);
+    if (const int rc = pp_pack_tables(api, pp, src_shapes, shapes, n, s0.data(), nullptr, c->tile0.data(), c->seg.data(), &c->lds)) return rc;
     if (max_src_bytes && (uint64_t)s0[n] > (uint64_t)max_src_bytes) {
         set_error("%s: the call's sources hold %lld bytes, above max_src_bytes = %zu", api, (long long)s0[n], max_src_bytes);
         return VITX_ERR_ARG;
     }
-    c->src_bytes = s0[n]; c->u8 = true;
+    c->src_bytes = s0[n]; c->on = true;
     if (src0) std::copy(s0.begin(), s0.end(), src0);
     return VITX_OK;
 }
 
 // What a forward call adds while attention rollout is on with arenas of max_sq floats (vitx_pack_attn_check's text; row0 [n + 1] is check_shapes's):
-// every image within the rollout kernels' token bound, the call's matrices within the arenas.  On success the rollout's tables of the call: c->rblk0,
-// sq0, n_max.  (Class maps alone refuse nothing: they live in max_tokens rows.)
-int check_attn(const char *api, const int32_t *row0, int n, long max_sq, PackCall *c) {
+// every image within the rollout kernels' token bound, the call's matrices within the arenas.  On success the rollout's tables of the call in *c.
+// (Class maps alone refuse nothing: they live in max_tokens rows.)
+int check_attn(const char *api, const int32_t *row0, int n, long max_sq, PackRolloutCall *c) {
     for (int i = 0; i < n; ++i)
         if (row0[i + 1] - row0[i] > kAttnMeanMaxTokens) {
             set_error("%s: image %d: rollout keeps two N x N matrices per image and takes at most %d tokens (this image: %d)", api, i, kAttnMeanMaxTokens, row0[i + 1] - row0[i]);
@@ -136,8 +142,9 @@ std::vector<uint64_t> distinct_grids(const int32_t *shapes, int n, int P) {
 }
 
 // THE check of a forward call, for both entry points: everything the call can be refused for, before its first device call.  It consumes
-// vitx_pack_dense_out's and vitx_pack_depth_out's shapes and vitx_pack_u8_sources's declaration, passed or refused, and touches nothing else of the context: a refused
-// call leaves row0 and the head's tables of the last forward that ran (vitx_pack_feat_read, vitx_pack_dense_read) alone.  d_imgs is only looked at, never read.
+// vitx_pack_dense_out's and vitx_pack_depth_out's shapes and vitx_pack_u8_sources's declaration, passed or refused, and touches nothing else of the
+// context: a refused call leaves row0 and the parts' tables of the last forward that ran (vitx_pack_feat_read, vitx_pack_dense_read) alone.  d_imgs is
+// only looked at, never read.
 int check_call(vitx_pack *p, const void *d_imgs, const int32_t *shapes, int n, PackCall *c) {
     int rc;
     PackDense *dn = p->dense.get();
@@ -146,18 +153,18 @@ int check_call(vitx_pack *p, const void *d_imgs, const int32_t *shapes, int n, P
     std::vector<int32_t> next_out, next_depth, next_src;
     if (dn) next_out.swap(dn->next_out);
     if (dp) next_depth.swap(dp->next_out);
-    const bool from_u8 = u8 && u8->declared;
-    if (from_u8) { next_src.swap(u8->next_src); u8->declared = false; }
+    if (u8) next_src.swap(u8->next_src);
+    const bool from_u8 = !next_src.empty();
     c->row0.resize((size_t)p->max_images + 1);
     if ((rc = check_shapes("vitx_pack_forward", p->model, shapes, n, p->max_tokens, p->max_images, c->row0.data()))) return rc;
     c->want = distinct_grids(shapes, n, p->P);
     if (c->want.size() > (size_t)p->max_grids) { set_error("vitx_pack_forward: the call names %d distinct grids, the table cache holds max_grids = %d", (int)c->want.size(), p->max_grids); return VITX_ERR_ARG; }
-    if (dn && (rc = check_dense("vitx_pack_forward", p->model, shapes, next_out.empty() ? nullptr : next_out.data(), (int)(next_out.size() / 2), n, dn->K, dn->max_pixels, c))) return rc;
-    if (dp && (rc = check_depth("vitx_pack_forward", p->model, shapes, next_depth.empty() ? nullptr : next_depth.data(), (int)(next_depth.size() / 2), n, dp->K, dp->u, dp->max_pixels, c))) return rc;
-    if (p->rollout() && (rc = check_attn("vitx_pack_forward", c->row0.data(), n, p->attn->max_sq, c))) return rc;
+    if (dn && (rc = check_dense("vitx_pack_forward", p->model, shapes, next_out.empty() ? nullptr : next_out.data(), (int)(next_out.size() / 2), n, dn->K, dn->max_pixels, &c->dense))) return rc;
+    if (dp && (rc = check_depth("vitx_pack_forward", p->model, shapes, next_depth.empty() ? nullptr : next_depth.data(), (int)(next_depth.size() / 2), n, dp->K, dp->u, dp->max_pixels, &c->depth))) return rc;
+    if (p->rollout() && (rc = check_attn("vitx_pack_forward", c->row0.data(), n, p->attn->max_sq, &c->roll))) return rc;
     if (from_u8) {
         if ((uintptr_t)d_imgs & 3) { set_error("vitx_pack_forward: the u8 sources must be 4-byte aligned"); return VITX_ERR_ARG; }
-        rc = check_u8("vitx_pack_forward", u8->pp, next_src.data(), (int)(next_src.size() / 2), shapes, n, u8->max_src_bytes, c, nullptr);
+        rc = check_u8("vitx_pack_forward", u8->pp, next_src.data(), (int)(next_src.size() / 2), shapes, n, u8->max_src_bytes, &c->u8, nullptr);
     }
     return rc;
 }
@@ -178,14 +185,14 @@ int pack_attention_maps(vitx_pack *p, const PackLayout &at, int il, int n, hipSt
     if (cls) { HIP_TRY(launch_attention_cls_map_packed(dt, p->QKV, (float *)cls, cfpt, cslot, d_row0, n, D, H, st)); ++p->launches; }
     if (!am.rollout()) return VITX_OK;
     const int *d_rblk0 = p->tab + at.rblk0(), *d_sq0 = p->tab + at.sq0();
-    const int blocks = am.rblk0[n];
+    const int blocks = am.last.rblk0[n], n_max = am.last.n_max;
     if (il + 1 < L) {
         float *a = roll[il & 1];
-        HIP_TRY(launch_attention_head_mean_packed(dt, p->QKV, a, d_row0, d_rblk0, d_sq0, n, blocks, am.n_max, D, H, true, st)); ++p->launches;
-        if (il > 0) { HIP_TRY(launch_rollout_step_packed(a, roll[(il + 1) & 1], d_row0, d_rblk0, d_sq0, n, blocks, am.n_max, st)); ++p->launches; }
+        HIP_TRY(launch_attention_head_mean_packed(dt, p->QKV, a, d_row0, d_rblk0, d_sq0, n, blocks, n_max, D, H, true, st)); ++p->launches;
+        if (il > 0) { HIP_TRY(launch_rollout_step_packed(a, roll[(il + 1) & 1], d_row0, d_rblk0, d_sq0, n, blocks, n_max, st)); ++p->launches; }
         return VITX_OK;
     }
-    HIP_TRY(launch_rollout_row_packed(cls, cfpt, cslot, L > 1 ? roll[(L - 2) & 1] : nullptr, am.out.as<float>(), fpt, fpt - 1, d_row0, d_sq0, n, am.n_max, H, st));
+    HIP_TRY(launch_rollout_row_packed(cls, cfpt, cslot, L > 1 ? roll[(L - 2) & 1] : nullptr, am.out.as<float>(), fpt, fpt - 1, d_row0, d_sq0, n, n_max, H, st));
     ++p->launches;
     return VITX_OK;
 }
@@ -196,21 +203,40 @@ int pack_gemm(vitx_pack *p, int epi, const GemmArgs &a, hipStream_t st) {
     return VITX_OK;
 }
 
-// A call that passed check_call: its rows and tables take the place of the last forward's, its grids are resolved; then the segment tables go up in
-// one copy, then the launches
+// Each part's tables of a call into the staging buffer `host`, where the layout puts them.  lrow [n]: image i's first logit row, behind its prefix rows
+void dense_tables(const PackDenseCall &c, const int32_t *lrow, int n, const PackLayout &at, int *host) {
+    std::copy(c.tile0.begin(), c.tile0.end(), host + at.tile0());
+    dense_pack_seg(c.grids.data(), c.outs.data(), lrow, c.pix0.data(), n, host + at.seg());
+}
+// image i's offsets are row i of the offsets (or, without a class half, the bias for every image)
+void depth_tables(const PackDepthCall &c, const int32_t *lrow, int n, int u, const PackLayout &at, int *host) {
+    std::vector<int32_t> orow(n);
+    for (int i = 0; i < n; ++i) orow[i] = i;
+    std::copy(c.ftile0.begin(), c.ftile0.end(), host + at.ftile0());
+    std::copy(c.otile0.begin(), c.otile0.end(), host + at.otile0());
+    depth_pack_seg(c.grids.data(), c.outs.data(), lrow, orow.data(), c.fine0.data(), c.pix0.data(), n, u, host + at.dseg());
+}
+void u8_tables(const PackU8Call &c, const PackLayout &at, int *host) {
+    std::copy(c.tile0.begin(), c.tile0.end(), host + at.ptile0());
+    std::copy(c.seg.begin(), c.seg.end(), host + at.pseg());
+}
+void rollout_tables(const PackRolloutCall &c, const PackLayout &at, int *host) {
+    std::copy(c.rblk0.begin(), c.rblk0.end(), host + at.rblk0());
+    std::copy(c.sq0.begin(), c.sq0.end(), host + at.sq0());
+}
+
+// A call that passed check_call: its rows and its parts' tables take the place of the last forward's, its grids are resolved; then the segment tables
+// go up in one copy, then the launches
 int pack_forward(vitx_pack *p, PackCall &c, const void *d_imgs, const int32_t *shapes, int n, float *d_probs, float *d_logits, hipStream_t st) {
     int rc;
     PackDense *dn = p->dense.get();
     PackDepth *dp = p->depth.get();
+    PackAttn *am = p->attn.get();
     HIP_TRY(hipSetDevice(p->device));
     p->row0.swap(c.row0); p->feat_n = 0;
-    if (dn) { dn->grids.swap(c.grids); dn->outs.swap(c.outs); dn->pix0.swap(c.pix0); dn->tile0.swap(c.tile0); dn->cells = c.cells; dn->n = 0; }
-    if (dp) {
-        dp->grids.swap(c.dgrids); dp->outs.swap(c.douts); dp->pix0.swap(c.dpix0); dp->fine0.swap(c.dfine0); dp->ftile0.swap(c.ftile0); dp->otile0.swap(c.otile0);
-        dp->cells = c.dcells; dp->n = 0;
-    }
-    PackAttn *am = p->attn.get();
-    if (am) { am->rblk0.swap(c.rblk0); am->sq0.swap(c.sq0); am->n_max = c.n_max; am->n = 0; }
+    if (dn) { std::swap(dn->last, c.dense); dn->n = 0; }
+    if (dp) { std::swap(dp->last, c.depth); dp->n = 0; }
+    if (am) { std::swap(am->last, c.roll); am->n = 0; }
     p->launches = p->pe_launches = 0;
     if ((rc = resolve_grids(p, c.want, st))) return rc;
     const WeightSet &ws = *p->wset;
@@ -219,50 +245,31 @@ int pack_forward(vitx_pack *p, PackCall &c, const void *d_imgs, const int32_t *s
     const int rows = p->row0[n], M = round_up(rows, tm), Mh = round_up(n, tm);
     // staging: the previous call's upload may still be reading the buffer (this call only enqueues) -- wait for the upload, not for its forward
     if (p->uploaded_pending) { HIP_TRY(hipEventSynchronize(p->uploaded)); p->uploaded_pending = false; }
-    int *h_row0 = p->host.data() + at.row0(), *h_qb0 = p->host.data() + at.qb0(), *h_toff = p->host.data() + at.toff();
+    int *host = p->host.data(), *h_row0 = host + at.row0(), *h_qb0 = host + at.qb0(), *h_toff = host + at.toff();
+    std::vector<int32_t> lrow(n);
     long qblocks = 0;
     for (int i = 0; i < n; ++i) {
-        h_row0[i] = p->row0[i]; h_qb0[i] = (int)qblocks;
+        h_row0[i] = p->row0[i]; h_qb0[i] = (int)qblocks; lrow[i] = p->row0[i] + Tp;
         qblocks += (p->row0[i + 1] - p->row0[i] + 63) / 64;
         h_toff[i] = (int)find_grid(p, shapes[2 * i] / P, shapes[2 * i + 1] / P)->rope_off;
     }
     h_row0[n] = rows; h_qb0[n] = (int)qblocks;
-    // the dense head's tables (check_call built them): image i's logit rows start behind its prefix rows
-    if (dn) {
-        std::vector<int32_t> lrow(n);
-        for (int i = 0; i < n; ++i) lrow[i] = p->row0[i] + Tp;
-        std::copy(dn->tile0.begin(), dn->tile0.end(), p->host.data() + at.tile0());
-        dense_pack_seg(dn->grids.data(), dn->outs.data(), lrow.data(), dn->pix0.data(), n, p->host.data() + at.seg());
-    }
-    // the depth head's: the same logit rows; image i's offsets are row i of the offsets (or, without a class half, the bias for every image)
-    if (dp) {
-        std::vector<int32_t> lrow(n), orow(n);
-        for (int i = 0; i < n; ++i) { lrow[i] = p->row0[i] + Tp; orow[i] = i; }
-        std::copy(dp->ftile0.begin(), dp->ftile0.end(), p->host.data() + at.ftile0());
-        std::copy(dp->otile0.begin(), dp->otile0.end(), p->host.data() + at.otile0());
-        depth_pack_seg(dp->grids.data(), dp->outs.data(), lrow.data(), orow.data(), dp->fine0.data(), dp->pix0.data(), n, dp->u, p->host.data() + at.dseg());
-    }
-    // the u8 preprocessing's (check_call built them)
-    if (c.u8) {
-        std::copy(c.ptile0.begin(), c.ptile0.end(), p->host.data() + at.ptile0());
-        std::copy(c.pseg.begin(), c.pseg.end(), p->host.data() + at.pseg());
-    }
-    // the attention rollout's (check_call built them)
-    if (at.rollout) {
-        std::copy(am->rblk0.begin(), am->rblk0.end(), p->host.data() + at.rblk0());
-        std::copy(am->sq0.begin(), am->sq0.end(), p->host.data() + at.sq0());
-    }
+    // the parts' tables (check_call built them), in layout order
+    if (dn) dense_tables(dn->last, lrow.data(), n, at, host);
+    if (dp) depth_tables(dp->last, lrow.data(), n, dp->u, at, host);
+    if (c.u8.on) u8_tables(c.u8, at, host);
+    if (at.parts & kRollout) rollout_tables(am->last, at, host);
     HIP_TRY(hipMemcpyAsync(p->tab, p->host.data(), p->host.size() * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(p->uploaded, st));
     p->uploaded_pending = true;
     const int *d_row0 = p->tab + at.row0(), *d_qb0 = p->tab + at.qb0(), *d_toff = p->tab + at.toff();
     // u8 sources: ONE launch stretches every source to its image's own shape into the context's pixel buffer, which the forward below reads
     const float *px = (const float *)d_imgs;
-    if (c.u8) {
-        const hipError_t e = launch_preprocess_pack(p->u8->pp, d_imgs, p->img, p->tab + at.ptile0(), p->tab + at.pseg(), n, c.ptile0[n], c.plds, st);
+    if (c.u8.on) {
+        const hipError_t e = launch_preprocess_pack(p->u8->pp, d_imgs, p->img.as<float>(), p->tab + at.ptile0(), p->tab + at.pseg(), n, c.u8.tile0[n], c.u8.lds, st);
         if (e != hipSuccess) { set_error("vitx_pack_forward: the u8 preprocessing: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
         ++p->launches;
-        px = p->img;
+        px = p->img.as<float>();
     }
     // patch embedding: one launch of the rectangular context's kernel per run of consecutive images of one shape, at the run's rows of X with the
     // position table of its grid -- the rows a rectangular context of that shape computes
@@ -315,12 +322,12 @@ int pack_forward(vitx_pack *p, PackCall &c, const void *d_imgs, const int32_t *s
     if ((rc = pack_gemm(p, EPI_BIAS_F32, dense_gemm(p->Z, ws.head_w, ws.head_b, lg, Mh, n, p->C, p->C_pad, D, ldl), st))) return rc;
     HIP_TRY(launch_softmax(dt, lg, d_probs, n, p->C, ldl, st)); ++p->launches;
     // features (vitx_pack_feat_enable): the f32 final norm of every row of the pack; vitx_pack_feat_read gathers the rows it was asked for
-    if (p->feat_flags) { HIP_TRY(launch_layernorm_f32(p->X, ws.norm_w, ws.norm_b, p->feat, rows, D, p->eps, st)); ++p->launches; p->feat_n = n; }
+    if (p->feat_flags) { HIP_TRY(launch_layernorm_f32(p->X, ws.norm_w, ws.norm_b, p->feat.as<float>(), rows, D, p->eps, st)); ++p->launches; p->feat_n = n; }
     // the dense head: the logits of every row of the pack, then one label launch over the images' own output shapes (2 launches; the memset of
     // the operand's pad rows is not a kernel)
     if (dn) {
         const hipError_t e = head_dense_packed(HeadLaunch{*p->tune, dt, st, nullptr}, dn->a[0].p, dn->W.p, dn->bias.as<float>(), dn->acc[0].as<float>(), rows, dn->K, dn->Dc,
-                                               p->tab + at.tile0(), p->tab + at.seg(), n, dn->tile0[n], dn->cells, (long)dn->pix0[n], dn->labels.as<uint8_t>(),
+                                               p->tab + at.tile0(), p->tab + at.seg(), n, dn->last.tile0[n], dn->last.cells, (long)dn->last.pix0[n], dn->labels.as<uint8_t>(),
                                                dn->score ? dn->score.as<float>() : nullptr, dn->logits ? dn->logits.as<float>() : nullptr);
         if (e != hipSuccess) { set_error("vitx_pack_forward: the dense head: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
         p->launches += 2;
@@ -332,8 +339,8 @@ int pack_forward(vitx_pack *p, PackCall &c, const void *d_imgs, const int32_t *s
         const bool cls = (bool)dp->Wc;
         const hipError_t e = head_depth_packed(HeadLaunch{*p->tune, dt, st, nullptr}, dp->a[0].p, dp->Wp.p, dp->zero.as<float>(), dp->acc[0].as<float>(), cls ? dp->ac[0].p : nullptr,
                                                dp->Wc.p, dp->bias.as<float>(), cls ? dp->o[0].as<float>() : nullptr, dp->bins.as<float>(), rows, dp->K, dp->Dc, d_row0,
-                                               p->tab + at.ftile0(), p->tab + at.otile0(), p->tab + at.dseg(), n, dp->ftile0[n], dp->otile0[n], dp->cells, (long)dp->fine0[n],
-                                               (long)dp->pix0[n], dp->lo, dp->hi, dp->fine.as<float>(), dp->depth.as<float>(), dp->logits ? dp->logits.as<float>() : nullptr,
+                                               p->tab + at.ftile0(), p->tab + at.otile0(), p->tab + at.dseg(), n, dp->last.ftile0[n], dp->last.otile0[n], dp->last.cells, (long)dp->last.fine0[n],
+                                               (long)dp->last.pix0[n], dp->lo, dp->hi, dp->fine.as<float>(), dp->depth.as<float>(), dp->logits ? dp->logits.as<float>() : nullptr,
                                                dp->off ? dp->off.as<float>() : nullptr);
         if (e != hipSuccess) { set_error("vitx_pack_forward: the depth head: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
         p->launches += cls ? 5 : 3;
@@ -342,6 +349,15 @@ int pack_forward(vitx_pack *p, PackCall &c, const void *d_imgs, const int32_t *s
     if (am) am->n = n;
     HIP_TRY(hipEventRecord(p->done, st));
     p->done_pending = true;
+    return VITX_OK;
+}
+
+// What both host entry points do behind their upload to d_in: the forward on the context's stream, the results down, the stream drained
+int host_forward(vitx_pack *p, PackCall &c, const void *d_in, const int32_t *shapes, int n, float *probs, float *logits) {
+    if (const int rc = pack_forward(p, c, d_in, shapes, n, p->probs, logits ? p->logits_out : nullptr, p->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(probs, p->probs, (size_t)n * p->C * 4, hipMemcpyDeviceToHost, p->stream));
+    if (logits) HIP_TRY(hipMemcpyAsync(logits, p->logits_out, (size_t)n * p->C * 4, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
     return VITX_OK;
 }
 
@@ -369,7 +385,7 @@ int vitx_pack_distinct_grids(const vitx_model *m, const int32_t *shapes, int n) 
 int vitx_pack_dense_check(const vitx_model *m, const int32_t *shapes, const int32_t *out_shapes, int n, int K, long max_pixels, int64_t *pix0, int32_t *tile0) {
     // max_tokens / max_images: whatever holds the call -- their refusals are vitx_pack_check's
     if (const int rc = check_shapes("vitx_pack_dense_check", m, shapes, n, 0x7fffffff, n, nullptr)) return rc;
-    PackCall c;
+    PackDenseCall c;
     if (const int rc = check_dense("vitx_pack_dense_check", m, shapes, out_shapes, n, n, K, max_pixels, &c)) return rc;
     if (pix0) std::copy(c.pix0.begin(), c.pix0.end(), pix0);
     if (tile0) std::copy(c.tile0.begin(), c.tile0.end(), tile0);
@@ -379,10 +395,10 @@ int vitx_pack_dense_check(const vitx_model *m, const int32_t *shapes, const int3
 int vitx_pack_depth_check(const vitx_model *m, const int32_t *shapes, const int32_t *out_shapes, int n, int K, int upsample, long max_pixels, int64_t *pix0, int64_t *fine0,
                           int32_t *ftile0, int32_t *otile0) {
     if (const int rc = check_shapes("vitx_pack_depth_check", m, shapes, n, 0x7fffffff, n, nullptr)) return rc;
-    PackCall c;
+    PackDepthCall c;
     if (const int rc = check_depth("vitx_pack_depth_check", m, shapes, out_shapes, n, n, K, upsample, max_pixels, &c)) return rc;
-    if (pix0) std::copy(c.dpix0.begin(), c.dpix0.end(), pix0);
-    if (fine0) std::copy(c.dfine0.begin(), c.dfine0.end(), fine0);
+    if (pix0) std::copy(c.pix0.begin(), c.pix0.end(), pix0);
+    if (fine0) std::copy(c.fine0.begin(), c.fine0.end(), fine0);
     if (ftile0) std::copy(c.ftile0.begin(), c.ftile0.end(), ftile0);
     if (otile0) std::copy(c.otile0.begin(), c.otile0.end(), otile0);
     return VITX_OK;
@@ -395,7 +411,7 @@ int vitx_pack_attn_check(const vitx_model *m, const int32_t *shapes, int n, uint
     std::vector<int32_t> row0((size_t)n + 1);
     if (const int rc = check_shapes("vitx_pack_attn_check", m, shapes, n, 0x7fffffff, n, row0.data())) return rc;
     if (const int rc = pack_attn_args("vitx_pack_attn_check", m->hp.num_hidden_layers, layer_mask, flags, max_sq_tokens)) return rc;
-    PackCall c;
+    PackRolloutCall c;
     if (flags & VITX_ATTN_ROLLOUT) {
         if (const int rc = check_attn("vitx_pack_attn_check", row0.data(), n, max_sq_tokens, &c)) return rc;
     } else {           // class maps alone refuse nothing per call; the tables are still the call's
@@ -416,40 +432,30 @@ int vitx_pack_forward_device(vitx_pack *p, const void *d_imgs, const int32_t *sh
 
 int vitx_pack_forward(vitx_pack *p, const float *imgs, const int32_t *shapes, int n, float *probs, float *logits) {
     if (!p || !imgs || !shapes || !probs) { set_error("vitx_pack_forward: NULL argument"); return VITX_ERR_ARG; }
-    int rc;
     PackCall c;
-    if ((rc = check_call(p, imgs, shapes, n, &c))) return rc;  // before the pixels go up
-    if (c.u8) { set_error("vitx_pack_forward: u8 sources were declared for this call (vitx_pack_u8_sources): it takes vitx_pack_forward_device or vitx_pack_forward_u8"); return VITX_ERR_ARG; }
+    if (const int rc = check_call(p, imgs, shapes, n, &c)) return rc;  // before the pixels go up
+    if (c.u8.on) { set_error("vitx_pack_forward: u8 sources were declared for this call (vitx_pack_u8_sources): it takes vitx_pack_forward_device or vitx_pack_forward_u8"); return VITX_ERR_ARG; }
     HIP_TRY(hipSetDevice(p->device));
     if (!p->img) {       // the pixels of a full pack: max_tokens patches
         const size_t bytes = (size_t)p->max_tokens * p->P * p->P * 3 * 4;
-        HIP_TRY(hipMalloc((void **)&p->img, bytes));
+        HIP_TRY(hipMalloc(&p->img.p, bytes));
         p->scratch_bytes += bytes;
     }
     size_t floats = 0;
     for (int i = 0; i < n; ++i) floats += (size_t)shapes[2 * i] * shapes[2 * i + 1] * 3;
-    HIP_TRY(hipMemcpyAsync(p->img, imgs, floats * 4, hipMemcpyHostToDevice, p->stream));
-    if ((rc = pack_forward(p, c, p->img, shapes, n, p->probs, logits ? p->logits_out : nullptr, p->stream))) return rc;
-    HIP_TRY(hipMemcpyAsync(probs, p->probs, (size_t)n * p->C * 4, hipMemcpyDeviceToHost, p->stream));
-    if (logits) HIP_TRY(hipMemcpyAsync(logits, p->logits_out, (size_t)n * p->C * 4, hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    return VITX_OK;
+    HIP_TRY(hipMemcpyAsync(p->img.p, imgs, floats * 4, hipMemcpyHostToDevice, p->stream));
+    return host_forward(p, c, p->img.p, shapes, n, probs, logits);
 }
 
 // u8 sources: the host entry point -- vitx_pack_forward's shape on u8.  The declaration is made here and consumed by check_call, like any other.
 int vitx_pack_forward_u8(vitx_pack *p, const uint8_t *srcs, const int32_t *src_shapes, const int32_t *shapes, int n, float *probs, float *logits) {
     if (!p || !srcs || !src_shapes || !shapes || !probs) { set_error("vitx_pack_forward_u8: NULL argument"); return VITX_ERR_ARG; }
-    int rc;
-    if ((rc = vitx_pack_u8_sources(p, src_shapes, n))) return rc;
+    if (const int rc = vitx_pack_u8_sources(p, src_shapes, n)) return rc;
     PackCall c;
-    if ((rc = check_call(p, p->u8->src.p, shapes, n, &c))) return rc;        // before the sources go up
+    if (const int rc = check_call(p, p->u8->src.p, shapes, n, &c)) return rc;        // before the sources go up
     HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipMemcpyAsync(p->u8->src.p, srcs, (size_t)c.src_bytes, hipMemcpyHostToDevice, p->stream));
-    if ((rc = pack_forward(p, c, p->u8->src.p, shapes, n, p->probs, logits ? p->logits_out : nullptr, p->stream))) return rc;
-    HIP_TRY(hipMemcpyAsync(probs, p->probs, (size_t)n * p->C * 4, hipMemcpyDeviceToHost, p->stream));
-    if (logits) HIP_TRY(hipMemcpyAsync(logits, p->logits_out, (size_t)n * p->C * 4, hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    return VITX_OK;
+    HIP_TRY(hipMemcpyAsync(p->u8->src.p, srcs, (size_t)c.u8.src_bytes, hipMemcpyHostToDevice, p->stream));
+    return host_forward(p, c, p->u8->src.p, shapes, n, probs, logits);
 }
 
 int vitx_pack_u8_check(const vitx_model *m, const vitx_preproc *pp, const int32_t *src_shapes, const int32_t *shapes, int n, size_t max_src_bytes, int64_t *src0,
@@ -458,10 +464,10 @@ int vitx_pack_u8_check(const vitx_model *m, const vitx_preproc *pp, const int32_
     if (const int rc = check_shapes("vitx_pack_u8_check", m, shapes, n, 0x7fffffff, n, nullptr)) return rc;
     vitx_preproc own;
     if (!pp) { if (const int rc = vitx_model_preproc(m, &own)) return rc; pp = &own; }
-    PackCall c;
+    PackU8Call c;
     if (const int rc = check_u8("vitx_pack_u8_check", *pp, src_shapes, n, shapes, n, max_src_bytes, &c, src0)) return rc;
-    if (tile0) std::copy(c.ptile0.begin(), c.ptile0.end(), tile0);
-    if (lds) *lds = c.plds;
+    if (tile0) std::copy(c.tile0.begin(), c.tile0.end(), tile0);
+    if (lds) *lds = c.lds;
     return VITX_OK;
 }
 

@@ -1,6 +1,9 @@
 // packed_input.cpp -- how pixels get into a packed context besides f32 (packed_context.h; include/vitx.h "packed batches", u8 sources): decoded u8
 // originals, each of its own size, stretched on the device to each image's own shape by ONE launch per pack (image_preprocess.hip
-// pp_pil_packed_kernel).  Opt-in; the forward (packed_forward.cpp) allocates and launches nothing for it while it is off.
+// pp_pil_packed_kernel).  Opt-in; the forward (packed_forward.cpp) allocates and launches nothing for it while it is off.  The part's state is
+// PackU8 (packed_context.h): vitx_pack_u8_set is a set call like the heads' (alloc_counted, pack_commit), vitx_pack_u8_sources declares the
+// sources' shapes of the next call (pack_next_shapes), which check_call consumes; its tables of a call are a PackU8Call.  The context's f32 pixel
+// buffer is the set's own only where no vitx_pack_forward had allocated it before.
 #include <algorithm>
 
 #include "packed_context.h"
@@ -22,48 +25,34 @@ int vitx_pack_u8_set(vitx_pack *p, const vitx_preproc *pp, size_t max_src_bytes)
     }
     HIP_TRY(hipSetDevice(p->device));
     if (const int rc = pack_quiesce(p)) return rc;
-    const size_t img_bytes = (size_t)p->max_tokens * p->P * p->P * 3 * 4;
-    // what the last set added goes: the staging with its owner, the pixel buffer only where that set allocated it
-    auto drop = [&]() {
-        if (!p->u8) return;
-        if (p->u8->own_img) { (void)hipFree(p->img); p->img = nullptr; }
-        p->scratch_bytes -= p->u8->bytes;
-        p->u8.reset();
-    };
+    const bool owned = p->u8 && p->u8->own_img;                      // the pixel buffer is the last set's: it goes with that set
+    const size_t old_bytes = p->u8 ? p->u8->bytes : 0;
     if (off) {       // the tables first: a failed resize leaves the mode as it was
-        if (const int rc = resize_tables(p, "vitx_pack_u8_set", (bool)p->dense, (bool)p->depth, false, p->rollout())) return rc;
-        drop();
+        if (const int rc = pack_commit(p, "vitx_pack_u8_set", p->parts() & ~kU8, old_bytes, 0)) return rc;
+        if (owned) p->img = DevMem();
+        p->u8.reset();
         return VITX_OK;
     }
     auto u = std::make_unique<PackU8>();
     u->pp = d; u->max_src_bytes = max_src_bytes;
     const size_t src_bytes = (max_src_bytes + 3) / 4 * 4;
-    const bool have_img = p->img && !(p->u8 && p->u8->own_img);      // an earlier vitx_pack_forward's: it stays
-    float *img = nullptr;
-    if (!u->src.alloc(src_bytes) || (!have_img && hipMalloc((void **)&img, img_bytes) != hipSuccess)) {
-        (void)hipGetLastError();
+    u->own_img = !p->img || owned;                                   // else an earlier vitx_pack_forward's: it stays, now and when u8 goes off
+    DevMem img;
+    if (!alloc_counted(u->src, src_bytes, &u->bytes) || (u->own_img && !alloc_counted(img, (size_t)p->max_tokens * p->P * p->P * 3 * 4, &u->bytes))) {
         set_error("vitx_pack_u8_set: cannot allocate %zu source bytes and the pixels of %d tokens", src_bytes, p->max_tokens);
         return VITX_ERR_NOMEM;
     }
-    DevMem img_own(img);
     HIP_TRY(hipMemset(u->src.p, 0, src_bytes));
     HIP_TRY(hipDeviceSynchronize());
-    if (const int rc = resize_tables(p, "vitx_pack_u8_set", (bool)p->dense, (bool)p->depth, true, p->rollout())) return rc;
-    drop();
-    if (!have_img) { p->img = img; img_own.p = nullptr; u->own_img = true; }
-    u->bytes = src_bytes + (u->own_img ? img_bytes : 0);
-    p->scratch_bytes += u->bytes;
+    if (const int rc = pack_commit(p, "vitx_pack_u8_set", p->parts() | kU8, old_bytes, u->bytes)) return rc;
+    if (u->own_img) p->img = std::move(img);                         // (the last set's own buffer is freed by the move)
     p->u8 = std::move(u);
     return VITX_OK;
 }
 
 int vitx_pack_u8_sources(vitx_pack *p, const int32_t *src_shapes, int n) {
     if (!p || !p->u8) { set_error("vitx_pack_u8_sources: u8 sources are off (vitx_pack_u8_set)"); return VITX_ERR_ARG; }
-    if (!src_shapes || n == 0) { p->u8->next_src.clear(); p->u8->declared = false; return VITX_OK; }
-    if (n < 1 || n > p->max_images) { set_error("vitx_pack_u8_sources: n = %d is outside 1 .. max_images = %d", n, p->max_images); return VITX_ERR_ARG; }
-    p->u8->next_src.assign(src_shapes, src_shapes + (size_t)2 * n);
-    p->u8->declared = true;
-    return VITX_OK;
+    return pack_next_shapes(p, "vitx_pack_u8_sources", src_shapes, n, &p->u8->next_src);
 }
 
 int vitx_pack_fit_shapes(const vitx_model *m, const int32_t *src_shapes, int n, int short_side, int max_long, int32_t *shapes) {
