@@ -1131,9 +1131,15 @@ int vitx_op_attention_generic(int dtype, const void *d_qkv, void *d_out, int n_i
  * operands with the ordinary attention (the text tower's rule: no hi / lo parity planes).  One stream, no sub-batches, no graph cache, no
  * LayerNorm fusion, no class-token tail; block-quantised matrices are expanded once at upload; the GEMMs go through the dispatcher with the
  * device's own tuning (every GEMM family gives the same bits).  options (NULL = all zero): pos_interp as in vitx_ctx_options; max_grids = the
- * grids whose tables the context caches (0 = 32).  VITX_ERR_UNSUPPORTED at creation, before any device call: a ViTSTR file, a
- * VITX_POOL_CLS_MEAN or VITX_POOL_MAP head, VITX_MXFP8, a head dim that is no multiple of 8 up to 128, a D outside the LayerNorm widths, a
- * max_tokens beyond the kernels' 32-bit buffer window.  VITX_ERR_ARG: a text model.
+ * grids whose tables the context caches (0 = 32); attn_kernel = the attention kernel of every layer: VITX_PACK_ATTN_AUTO (0) runs the staged
+ * kernel (vitx_op_attention_packed_ex below) where the model's head dim is 64 and the generic one otherwise, VITX_PACK_ATTN_GENERIC and
+ * VITX_PACK_ATTN_STAGED force one; vitx_pack_attn_kernel returns the one the context runs (1 or 2).  The two give an image the same bits, so
+ * the choice changes no output, launch count or scratch byte -- with one exception: where a value row v[N_i - 1] of an (image, head)
+ * holds +-Inf and N_i % 32 != 0, the generic kernel multiplies that row by the zero probabilities of the padding keys (NaN) and the staged
+ * kernel reads zeros there (no NaN from the padding); with NaN in place of Inf both give NaN.  VITX_ERR_UNSUPPORTED at creation, before any
+ * device call: a ViTSTR file, a VITX_POOL_CLS_MEAN or VITX_POOL_MAP head, VITX_MXFP8, a head dim that is no multiple of 8 up to 128,
+ * VITX_PACK_ATTN_STAGED at a head dim other than 64 (the message names D and H), a D outside the LayerNorm widths, a max_tokens beyond the
+ * kernels' 32-bit buffer window.  VITX_ERR_ARG: a text model, an attn_kernel outside 0 .. 2.
  *
  * Tables: the position table of a grid (the file's at the file's grid, else resampled on the device, pos_interp) and, for a file with
  * `rope`, its rotary table (vitx_model_rope_table, uploaded) are built the first time a call names the grid -- that call allocates -- and
@@ -1167,6 +1173,13 @@ int vitx_op_attention_generic(int dtype, const void *d_qkv, void *d_out, int n_i
  *                              outside rows row0[0] .. row0[n] - 1 is written.  A work item is (image, head, 64 queries): H * sum ceil(N_i / 64)
  *                              workgroups, found by a binary search of the workgroup index in the running count of query blocks.  TEST entry
  *                              point: it reads d_row0 back to build that count (synchronises); a packed context uploads both with one copy.
+ *   vitx_op_attention_packed_ex   the same with a kernel id: VITX_PACK_ATTN_GENERIC = vitx_op_attention_packed's kernel, VITX_PACK_ATTN_STAGED = head dim
+ *                              64 only, K and V streamed through LDS in 64-key chunks once per workgroup (csrc/attention_packed_staged.hip) with the
+ *                              generic kernel's arithmetic operation for operation: the same bits, the same grid, the same tables, except that
+ *                              keys past N_i are read as zeros, not as row N_i - 1 (the +-Inf sentence above); VITX_PACK_ATTN_AUTO = STAGED at
+ *                              head dim 64, GENERIC otherwise.  TEST entry point as well: null stream, synchronous.  Before the first device
+ *                              call: VITX_ERR_ARG for a NULL pointer, n <= 0, a bad dtype or kernel id; VITX_ERR_UNSUPPORTED for STAGED at a
+ *                              head dim other than 64 or a head dim the generic kernel refuses.
  *   vitx_op_rope_packed        vitx_op_rope on a pack: token t >= prefix of image i rotates by row t - prefix of the table that starts
  *                              d_table_off[i] floats into d_cos and d_sin; one launch for the pack; reads both tables back to check them (synchronises).
  *
@@ -1307,7 +1320,10 @@ int vitx_op_attention_generic(int dtype, const void *d_qkv, void *d_out, int n_i
  * to the given shape), the REF filters, JPEG decode on the device, and a vit.h wrapper; of the attention maps: full N x N maps as an output, rollout
  * above 1024 tokens per image, and a vit.h wrapper. */
 typedef struct vitx_pack vitx_pack;
-typedef struct { int pos_interp, max_grids, reserved[6]; } vitx_pack_options;
+#define VITX_PACK_ATTN_AUTO 0
+#define VITX_PACK_ATTN_GENERIC 1
+#define VITX_PACK_ATTN_STAGED 2
+typedef struct { int pos_interp, max_grids, attn_kernel, reserved[5]; } vitx_pack_options;
 int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_images, int dtype, const vitx_pack_options *opt, vitx_pack **out);
 void vitx_pack_free(vitx_pack *p);
 int vitx_pack_shares_weights(const vitx_pack *p);
@@ -1321,9 +1337,14 @@ int vitx_pack_feat_enable(vitx_pack *p, int flags /* VITX_FEAT_CLS | VITX_FEAT_T
 int vitx_pack_feat_read(vitx_pack *p, float *cls /* [n][D] or NULL */, float *tokens /* [sum gh_i gw_i][D], images end to end, or NULL */);
 size_t vitx_pack_scratch_bytes(const vitx_pack *p);        /* device bytes of activation scratch and cached tables held now (weights not counted) */
 int vitx_pack_launches(const vitx_pack *p, int *patch_embed);      /* kernel launches of the last forward call; *patch_embed: the patch embeddings among them */
+int vitx_pack_attn_kernel(const vitx_pack *p);             /* VITX_PACK_ATTN_GENERIC or VITX_PACK_ATTN_STAGED: the attention kernel this context runs (0 for NULL) */
 int vitx_op_attention_packed(int dtype, const void *d_qkv, void *d_out, const void *d_row0 /* int32 [n + 1] */, int n, int D, int H, void *stream);
 /* the same launch on tables the caller built and vouches for: d_qb0 int32 [n + 1] = the running count of ceil(N_i / 64), qblocks = d_qb0[n]; only enqueues */
 int vitx_op_attention_packed_tables(int dtype, const void *d_qkv, void *d_out, const void *d_row0, const void *d_qb0, int n, long qblocks, int D, int H, void *stream);
+/* the kernel by id (VITX_PACK_ATTN_*), on the null stream, synchronous: a test entry point like vitx_op_attention_packed */
+int vitx_op_attention_packed_ex(int dtype, int kernel, const void *d_qkv, void *d_out, const void *d_row0 /* int32 [n + 1] */, int n, int D, int H);
+/* vitx_op_attention_packed_tables with a kernel id (GENERIC or STAGED, no AUTO) on the null stream; only enqueues */
+int vitx_op_attention_packed_tables_ex(int dtype, int kernel, const void *d_qkv, void *d_out, const void *d_row0, const void *d_qb0, int n, long qblocks, int D, int H);
 int vitx_op_rope_packed(int dtype, void *d_qkv, long lo_off /* must be 0 */, const void *d_cos, const void *d_sin, const void *d_row0 /* int32 [n + 1] */,
                         const void *d_table_off /* int32 [n] */, int n, int prefix, int D, int H, void *stream);
 int vitx_pack_dense_set(vitx_pack *p, const float *W /* [K][Dc] */, const float *bias /* [K] or NULL */, int K, int Dc, uint64_t layer_mask, long max_pixels, int flags);

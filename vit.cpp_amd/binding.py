@@ -37,6 +37,7 @@ TEXT_L2 = 1                             # vitx_text_embed flag
 NN_LOGITS, NN_EMBED = 0, 1              # vitx_nn_source
 DENSE_SCORE, DENSE_LOGITS = 1, 2        # vitx_dense_flags
 DEPTH_NORM, DEPTH_LOGITS, DEPTH_FINE = 1, 2, 4      # vitx_depth_flags
+PACK_ATTN_AUTO, PACK_ATTN_GENERIC, PACK_ATTN_STAGED = 0, 1, 2      # VITX_PACK_ATTN_*: a packed context's attention kernel (AUTO: staged at head dim 64)
 POS_BICUBIC, POS_BICUBIC_AA = 0, 1      # vitx_pos_interp: F.interpolate(mode="bicubic") without / with antialias=True (include/vitx.h)
 
 EXPORTS = [
@@ -70,7 +71,8 @@ EXPORTS = [
     "vitx_ctx_create_rect", "vitx_ctx_img_shape", "vitx_ctx_grid", "vitx_op_patch_embed_rect",
     "vitx_rect_shape", "vitx_preprocess_rect", "vitx_preprocess_rect_device", "vitx_preprocess_rect_device_supports",
     "vitx_pack_create", "vitx_pack_free", "vitx_pack_shares_weights", "vitx_pack_check", "vitx_pack_distinct_grids", "vitx_pack_forward", "vitx_pack_forward_device",
-    "vitx_pack_feat_enable", "vitx_pack_feat_read", "vitx_pack_scratch_bytes", "vitx_pack_launches", "vitx_op_attention_packed", "vitx_op_attention_packed_tables", "vitx_op_rope_packed",
+    "vitx_pack_feat_enable", "vitx_pack_feat_read", "vitx_pack_scratch_bytes", "vitx_pack_launches", "vitx_pack_attn_kernel", "vitx_op_attention_packed", "vitx_op_attention_packed_tables",
+    "vitx_op_attention_packed_ex", "vitx_op_attention_packed_tables_ex", "vitx_op_rope_packed",
     "vitx_pack_dense_set", "vitx_pack_dense_out", "vitx_pack_dense_check", "vitx_pack_dense_read", "vitx_pack_dense_device", "vitx_pack_dense_scratch_bytes", "vitx_op_dense_labels_packed",
     "vitx_dense_pack_tables", "vitx_op_dense_labels_packed_tables",
     "vitx_pack_depth_set", "vitx_pack_depth_out", "vitx_pack_depth_check", "vitx_pack_depth_read", "vitx_pack_depth_device", "vitx_pack_depth_scratch_bytes",
@@ -93,7 +95,7 @@ class CtxOptions(C.Structure):
 
 
 class PackOptions(C.Structure):
-    _fields_ = [("pos_interp", C.c_int), ("max_grids", C.c_int), ("reserved", C.c_int * 6)]
+    _fields_ = [("pos_interp", C.c_int), ("max_grids", C.c_int), ("attn_kernel", C.c_int), ("reserved", C.c_int * 5)]
 
 
 class Preproc(C.Structure):
@@ -339,6 +341,10 @@ def lib():
             L.vitx_pack_feat_read.argtypes = [vp, fp, fp]
             L.vitx_pack_scratch_bytes.restype = C.c_size_t; L.vitx_pack_scratch_bytes.argtypes = [vp]
             L.vitx_pack_launches.argtypes = [vp, C.POINTER(ip)]
+            if hasattr(L, "vitx_pack_attn_kernel"):
+                L.vitx_pack_attn_kernel.argtypes = [vp]
+                L.vitx_op_attention_packed_ex.argtypes = [ip, ip, vp, vp, vp, ip, ip, ip]
+                L.vitx_op_attention_packed_tables_ex.argtypes = [ip, ip, vp, vp, vp, vp, ip, C.c_long, ip, ip]
             L.vitx_op_attention_packed.argtypes = [ip, vp, vp, vp, ip, ip, ip, vp]
             L.vitx_op_attention_packed_tables.argtypes = [ip, vp, vp, vp, vp, ip, C.c_long, ip, ip, vp]
             L.vitx_op_rope_packed.argtypes =[ip, vp, C.c_long, vp, vp, vp, vp, ip, ip, ip, ip, vp]
@@ -1243,10 +1249,11 @@ def preprocess_pack(pp: Preproc, d_srcs: int, src_shapes, out_shapes, d_out: int
 class PackContext:
     """A packed context (include/vitx.h "packed batches"): images of different shapes, their tokens end to end, in one forward."""
 
-    def __init__(self, model: Model, device: int = 0, max_tokens: int = 1024, max_images: int = 16, dtype: int = F16, pos_interp: int = POS_BICUBIC, max_grids: int = 0):
+    def __init__(self, model: Model, device: int = 0, max_tokens: int = 1024, max_images: int = 16, dtype: int = F16, pos_interp: int = POS_BICUBIC, max_grids: int = 0,
+                 attn_kernel: int = PACK_ATTN_AUTO):
         self._h = C.c_void_p()
         self.model = model; self.max_tokens = max_tokens; self.max_images = max_images; self.dtype = dtype
-        opt = PackOptions(pos_interp=pos_interp, max_grids=max_grids)
+        opt = PackOptions(pos_interp=pos_interp, max_grids=max_grids, attn_kernel=attn_kernel)
         check(lib().vitx_pack_create(model._h, device, max_tokens, max_images, dtype, C.byref(opt), C.byref(self._h)), "vitx_pack_create")
         self._shapes = None; self._feat = 0
         self._dense = self._dense_out = self._dense_shapes = None
@@ -1571,6 +1578,11 @@ class PackContext:
         return int(lib().vitx_pack_scratch_bytes(self._h))
 
     @property
+    def attn_kernel(self) -> int:
+        """PACK_ATTN_GENERIC or PACK_ATTN_STAGED: the attention kernel this context runs."""
+        return int(lib().vitx_pack_attn_kernel(self._h))
+
+    @property
     def launches(self) -> Tuple[int, int]:
         """(kernel launches, patch-embedding launches among them) of the last forward call."""
         pe = C.c_int()
@@ -1580,6 +1592,11 @@ class PackContext:
 def op_attention_packed(dtype: int, d_qkv: int, d_out: int, d_row0: int, n: int, D: int, H: int, stream: int = 0) -> None:
     """vitx_op_attention_packed: attention over a pack, image i = rows row0[i] .. row0[i + 1] - 1 (d_row0 int32 [n + 1] on the device)."""
     check(lib().vitx_op_attention_packed(dtype, d_qkv, d_out, d_row0, n, D, H, stream or None), "vitx_op_attention_packed")
+
+
+def op_attention_packed_ex(dtype: int, kernel: int, d_qkv: int, d_out: int, d_row0: int, n: int, D: int, H: int) -> None:
+    """vitx_op_attention_packed_ex: the same with a kernel id (PACK_ATTN_*), on the null stream, synchronous."""
+    check(lib().vitx_op_attention_packed_ex(dtype, kernel, d_qkv, d_out, d_row0, n, D, H), "vitx_op_attention_packed_ex")
 
 
 def pack_attn_check(model: Model, shapes, layers=None, rollout: bool = False, max_sq_tokens: int = 0, *, layer_mask: Optional[int] = None, flags: Optional[int] = None):

@@ -8,7 +8,8 @@
 // load of the search has a uniform address and is a scalar load.  Key and value rows clamp to the image's own last row, never to a
 // neighbour's.  No atomics, one writer per output element, nothing written outside rows row0[0] .. row0[n] - 1.  32 * DHP * 2 bytes of LDS
 // per wave (at most 32 KiB per workgroup): no dynamic-LDS attribute, no prepare_*.
-// K and V are NOT staged in LDS for the four waves of a workgroup (attention_text.hip does, for its short sequences): profiles/pack_cost.txt.
+// K and V are NOT staged in LDS for the four waves of a workgroup (profiles/pack_cost.txt): attention_packed_staged.hip does that for head dim 64, with
+// this kernel's bits, and is what a packed context runs there; this kernel serves the other head dims and stays the yardstick.
 #include "attention_rows.h"
 
 namespace vitx {

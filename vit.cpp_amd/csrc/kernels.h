@@ -312,6 +312,10 @@ bool rope_supports(int D, int H);
 //   pool_rows:        launch_text_pool's kernel text on absolute rows: z[i][:] = RNE(final LayerNorm of X row rows[i]); rows n .. m_pad zeros
 hipError_t launch_attention_packed(int dtype, const void *qkv, void *out, const int *row0, const int *qb0, int n, long qblocks, int D, int H, hipStream_t stream);
 bool attention_packed_supports(int D, int H);      // attention_generic_supports
+//   attention_packed_staged: the same call for head dim 64 with K and V staged in LDS per workgroup (attention_packed_staged.hip): the same tables, grid
+//                     and bits (but for a value row v[N_i - 1] holding +-Inf where N_i % 32 != 0); hipErrorInvalidValue on another head dim
+hipError_t launch_attention_packed_staged(int dtype, const void *qkv, void *out, const int *row0, const int *qb0, int n, long qblocks, int D, int H, hipStream_t stream);
+bool attention_packed_staged_supports(int D, int H);      // head dim 64
 hipError_t launch_rope_packed(int dtype, void *qkv, const float *cos, const float *sin, const int *row0, const int *toff, int n, long patch_rows, bool toff_aligned, int prefix, int D,
                               int H, hipStream_t stream);
 hipError_t launch_pool_rows(int dtype, const float *X, const int *rows, const float *w, const float *b, void *z, int n, int m_pad, int D, float eps, hipStream_t stream);

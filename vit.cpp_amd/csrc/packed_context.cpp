@@ -155,12 +155,16 @@ int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_im
     const int pos_interp = opt ? opt->pos_interp : VITX_POS_BICUBIC, max_grids = opt && opt->max_grids ? opt->max_grids : 32;
     if (pos_interp != VITX_POS_BICUBIC && pos_interp != VITX_POS_BICUBIC_AA) { set_error("vitx_pack_create: unknown pos_interp %d (0 bicubic, 1 bicubic with antialias)", pos_interp); return VITX_ERR_ARG; }
     if (max_grids < 1) { set_error("vitx_pack_create: max_grids %d is not positive", max_grids); return VITX_ERR_ARG; }
+    int attn_kernel = opt ? opt->attn_kernel : VITX_PACK_ATTN_AUTO;
+    if (attn_kernel < VITX_PACK_ATTN_AUTO || attn_kernel > VITX_PACK_ATTN_STAGED) { set_error("vitx_pack_create: unknown attn_kernel %d (0 auto, 1 generic, 2 staged)", attn_kernel); return VITX_ERR_ARG; }
     // every refusal before the first device call: nothing is launched after one
     if (m->in_chans == 1) { set_error("vitx_pack_create: a ViTSTR (one-channel) model takes no packed context"); return VITX_ERR_UNSUPPORTED; }
     if (m->head_pool != VITX_POOL_CLS) { set_error("vitx_pack_create: packed contexts take the class-token head only, not the pooled (cls + mean) or the attention-pooling head"); return VITX_ERR_UNSUPPORTED; }
     const vitx_hparams &hp = m->hp;
     const int D = hp.hidden_size, H = hp.num_attention_heads, F1 = m->mlp_fc1_rows();
     if (!attention_packed_supports(D, H)) { set_error("vitx_pack_create: attention needs a head_dim that is a multiple of 8 up to 128 (this model: %d / %d)", D, H); return VITX_ERR_UNSUPPORTED; }
+    if (attn_kernel == VITX_PACK_ATTN_STAGED && !attention_packed_staged_supports(D, H)) { set_error("vitx_pack_create: the staged attention kernel needs head_dim 64 (this model: %d / %d)", D, H); return VITX_ERR_UNSUPPORTED; }
+    if (attn_kernel == VITX_PACK_ATTN_AUTO) attn_kernel = attention_packed_staged_supports(D, H) ? VITX_PACK_ATTN_STAGED : VITX_PACK_ATTN_GENERIC;
     if (!layernorm_supports(D)) { set_error("vitx_pack_create: hidden_size %d has no LayerNorm instantiation", D); return VITX_ERR_UNSUPPORTED; }
     if (m->rope_kind && !rope_supports(D, H)) { set_error("vitx_pack_create: rotary position embeddings need an even head dim (D %d, H %d)", D, H); return VITX_ERR_UNSUPPORTED; }
     if (hp.patch_size <= 0 || hp.img_size % hp.patch_size) { set_error("vitx_pack_create: the file's img_size %d is not a multiple of its patch size %d", hp.img_size, hp.patch_size); return VITX_ERR_UNSUPPORTED; }
@@ -176,7 +180,7 @@ int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_im
     p->glu = m->glu_kind != VITX_GLU_NONE; p->F = m->mlp_hidden(); p->F1 = F1; p->rope = m->rope_kind != VITX_ROPE_NONE;
     p->fc1_epi = p->glu ? EPI_BIAS : act_epi(m->activation); p->eps = hp.eps;
     p->tm = gemm_tile_m(); p->tn = gemm_tile_n();
-    p->max_tokens = max_tokens; p->max_images = max_images; p->max_grids = max_grids; p->pos_interp = pos_interp;
+    p->max_tokens = max_tokens; p->max_images = max_images; p->max_grids = max_grids; p->pos_interp = pos_interp; p->attn_kernel = attn_kernel;
     // quantised block matrices are expanded at upload: block mode 0, as in the text context
     if ((rc = obtain_weights({m, device, dtype, false}, &p->wset, &p->weights_shared))) return rc;
     auto dmalloc = [&](void **q, size_t bytes) -> int {
@@ -214,6 +218,7 @@ int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_im
 void vitx_pack_free(vitx_pack *p) { delete p; }
 int vitx_pack_shares_weights(const vitx_pack *p) { return p && p->weights_shared ? 1 : 0; }
 size_t vitx_pack_scratch_bytes(const vitx_pack *p) { return p ? p->scratch_bytes : 0; }
+int vitx_pack_attn_kernel(const vitx_pack *p) { return p ? p->attn_kernel : 0; }
 int vitx_pack_launches(const vitx_pack *p, int *patch_embed) {
     if (!p) return 0;
     if (patch_embed) *patch_embed = p->pe_launches;
