@@ -1137,7 +1137,7 @@ int vitx_op_attention_generic(int dtype, const void *d_qkv, void *d_out, int n_i
  * the choice changes no output, launch count or scratch byte -- with one exception: where a value row v[N_i - 1] of an (image, head)
  * holds +-Inf and N_i % 32 != 0, the generic kernel multiplies that row by the zero probabilities of the padding keys (NaN) and the staged
  * kernel reads zeros there (no NaN from the padding); with NaN in place of Inf both give NaN.  VITX_ERR_UNSUPPORTED at creation, before any
- * device call: a ViTSTR file, a VITX_POOL_CLS_MEAN or VITX_POOL_MAP head, VITX_MXFP8, a head dim that is no multiple of 8 up to 128,
+ * device call: a ViTSTR file, a VITX_POOL_CLS_MEAN head, a VITX_POOL_MAP head without pool_head (below), VITX_MXFP8, a head dim that is no multiple of 8 up to 128,
  * VITX_PACK_ATTN_STAGED at a head dim other than 64 (the message names D and H), a D outside the LayerNorm widths, a max_tokens beyond the
  * kernels' 32-bit buffer window.  VITX_ERR_ARG: a text model, an attn_kernel outside 0 .. 2.
  *
@@ -1314,8 +1314,29 @@ int vitx_op_attention_generic(int dtype, const void *d_qkv, void *d_out, int n_i
  *                              (vitx_op_rollout_factor's entry).  Nothing else is written.
  *   vitx_op_rollout_step_packed   d_a <- d_a . d_r per image, both with image i's matrix at float sq0[i]; ranges that overlap: VITX_ERR_ARG.
  *   vitx_op_rollout_row_packed    d_cls as above, d_r (or NULL) as above -> d_out, image i's row [N_i] at float row0[i].
- * Not offered on packed contexts (each a later step): the other opt-in heads (zero-shot bank, gallery), the pooled
- * and attention-pooling heads, the F16 parity planes, LayerNorm fusion and sub-batch streams, a packed patch-embedding kernel, vitx_group_*;
+ * The attention-pooling head on a pack (options.pool_head = VITX_PACK_POOL_MAP, 1): a packed context of a VITX_POOL_MAP (SigLIP-class) file.  pool_head
+ * = 0 is the default and leaves everything above as it is, such a file refused included.  With pool_head = 1, before any device call: VITX_ERR_ARG for a
+ * file with another head and for any other value of pool_head; VITX_ERR_UNSUPPORTED for more than 16 heads and for a hidden size whose staging
+ * tiles do not fit the pooling kernel's LDS (D above 1152).  Such a context has T = 0: image i is its gh_i gw_i patch rows, and the table cache
+ * resamples the file's position table, which has no class row, to [gh gw][D] with the same arithmetic.  After the last layer the pooling pass runs
+ * as TWO launches over the pack (csrc/attention_pool_packed.hip): a work item of the first is (image, chunk of vitx_pack_pool_chunk_rows() = 128 rows
+ * of it), found by a binary search of the workgroup index in the running chunk count (vitx_pack_pool_chunks: chunk0[i] = sum_(j < i) ceil(rows_j /
+ * 128); VITX_ERR_ARG for a null rows, n <= 0, a count below 1 or more than 2^31 - 1 chunks), with both products -- the scores F u^T and the weighted
+ * sum P^T F -- on v_mfma_f32_16x16x4_f32 in f32 and an online softmax per chunk; the second merges an image's chunks in ascending order and writes
+ * RNE(M).  The chunk table rides in the call's one table upload; the partial scratch (max_tokens / 128 + max_images chunks of H (D + 2) floats) is
+ * allocated at creation and counted in vitx_pack_scratch_bytes.  Then the image context's pooled tail on one row per image through the same GEMM
+ * dispatcher: the H value projections, proj, LayerNorm, fc1 + activation, fc2 + residual = e, Z = RNE(e), the head GEMM and the class softmax: H + 9
+ * launches in place of the class-row gather's 3, counted by vitx_pack_launches.  vitx_pack_feat_enable takes VITX_FEAT_L2 besides on such a context:
+ * cls [n][D] is the pooled embedding e (with VITX_FEAT_L2 divided by its norm: SigLIP's image_embeds), tokens are the final norm of all rows.  u8
+ * sources work unchanged.  vitx_pack_attn_enable, vitx_pack_dense_set and vitx_pack_depth_set return VITX_ERR_UNSUPPORTED on such a context (the text
+ * names the attention-pooling head).  An image's M, e, logits and probabilities are a function of its own pixels and shape: chunks are cut from the
+ * image's own first row, rows behind an image are never read as data, nothing is accumulated atomically.
+ *   vitx_op_attention_pool_packed  the two launches on the caller's buffers: d_x [rows][D] f32, HOST row0 [n + 1] (ascending, N_i >= 1) -> d_M [n][H][D]
+ *                              f32; vitx_op_attention_pool's argument checks and H <= 16, D <= 1152.  TEST entry point: it builds and uploads its
+ *                              tables, allocates its partial scratch, runs on the null stream and returns after synchronising.
+ * Not offered on packed contexts (each a later step): the other opt-in heads (zero-shot bank, gallery), the pooled (cls + mean) head; of the
+ * attention-pooling head: attention maps, the dense and the depth head, VITX_FEAT_MEAN, more than 16 heads, and image contexts of such files away from
+ * the file's own shape; the F16 parity planes, LayerNorm fusion and sub-batch streams, a packed patch-embedding kernel, vitx_group_*;
  * of the dense and the depth head: downsampling, and a vit.h wrapper; of the u8 sources: crops and shortest-edge geometry (a source is stretched
  * to the given shape), the REF filters, JPEG decode on the device, and a vit.h wrapper; of the attention maps: full N x N maps as an output, rollout
  * above 1024 tokens per image, and a vit.h wrapper. */
@@ -1323,7 +1344,8 @@ typedef struct vitx_pack vitx_pack;
 #define VITX_PACK_ATTN_AUTO 0
 #define VITX_PACK_ATTN_GENERIC 1
 #define VITX_PACK_ATTN_STAGED 2
-typedef struct { int pos_interp, max_grids, attn_kernel, reserved[5]; } vitx_pack_options;
+#define VITX_PACK_POOL_MAP 1
+typedef struct { int pos_interp, max_grids, attn_kernel, pool_head, reserved[4]; } vitx_pack_options;
 int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_images, int dtype, const vitx_pack_options *opt, vitx_pack **out);
 void vitx_pack_free(vitx_pack *p);
 int vitx_pack_shares_weights(const vitx_pack *p);
@@ -1338,6 +1360,15 @@ int vitx_pack_feat_read(vitx_pack *p, float *cls /* [n][D] or NULL */, float *to
 size_t vitx_pack_scratch_bytes(const vitx_pack *p);        /* device bytes of activation scratch and cached tables held now (weights not counted) */
 int vitx_pack_launches(const vitx_pack *p, int *patch_embed);      /* kernel launches of the last forward call; *patch_embed: the patch embeddings among them */
 int vitx_pack_attn_kernel(const vitx_pack *p);             /* VITX_PACK_ATTN_GENERIC or VITX_PACK_ATTN_STAGED: the attention kernel this context runs (0 for NULL) */
+/* the attention-pooling head on a pack (pool_head = VITX_PACK_POOL_MAP): the chunk size of the pooling launch, and the running chunk count of row counts [n] */
+int vitx_pack_pool_chunk_rows(void);
+int vitx_pack_pool_chunks(const int *rows, int n, int *chunk0 /* [n + 1] or NULL */);
+int vitx_op_attention_pool_packed(const void *d_x /* [rows][D] f32 */, const int32_t *row0 /* host [n + 1] */, const void *d_ln_w, const void *d_ln_b, float eps,
+                                  const void *d_u /* [H][D] f32 */, void *d_M /* [n][H][D] f32 */, int n, int D, int H);
+/* the same two launches on device tables and a partial scratch [chunks][H][D + 2] f32 the caller built and vouches for; d_M f32 and / or d_m16 = RNE(M) in dtype;
+ * null stream, only enqueues */
+int vitx_op_attention_pool_packed_tables(const void *d_x, const void *d_row0, const void *d_chunk0, int n, int chunks, const void *d_ln_w, const void *d_ln_b, float eps,
+                                         const void *d_u, void *d_part, void *d_M, void *d_m16, int dtype, int D, int H);
 int vitx_op_attention_packed(int dtype, const void *d_qkv, void *d_out, const void *d_row0 /* int32 [n + 1] */, int n, int D, int H, void *stream);
 /* the same launch on tables the caller built and vouches for: d_qb0 int32 [n + 1] = the running count of ceil(N_i / 64), qblocks = d_qb0[n]; only enqueues */
 int vitx_op_attention_packed_tables(int dtype, const void *d_qkv, void *d_out, const void *d_row0, const void *d_qb0, int n, long qblocks, int D, int H, void *stream);

@@ -80,6 +80,7 @@ EXPORTS = [
     "vitx_pack_u8_set", "vitx_pack_u8_sources", "vitx_pack_forward_u8", "vitx_pack_u8_check", "vitx_pack_fit_shapes", "vitx_op_preprocess_pack",
     "vitx_pack_attn_enable", "vitx_pack_attn_floats", "vitx_pack_attn_read", "vitx_pack_attn_device", "vitx_pack_attn_check",
     "vitx_op_attention_map_packed", "vitx_op_rollout_step_packed", "vitx_op_rollout_row_packed",
+    "vitx_pack_pool_chunk_rows", "vitx_pack_pool_chunks", "vitx_op_attention_pool_packed", "vitx_op_attention_pool_packed_tables",
 ]
 
 
@@ -95,7 +96,7 @@ class CtxOptions(C.Structure):
 
 
 class PackOptions(C.Structure):
-    _fields_ = [("pos_interp", C.c_int), ("max_grids", C.c_int), ("attn_kernel", C.c_int), ("reserved", C.c_int * 5)]
+    _fields_ = [("pos_interp", C.c_int), ("max_grids", C.c_int), ("attn_kernel", C.c_int), ("pool_head", C.c_int), ("reserved", C.c_int * 4)]
 
 
 class Preproc(C.Structure):
@@ -338,6 +339,10 @@ def lib():
             L.vitx_pack_forward.argtypes = [vp, fp, i32p, ip, fp, fp]
             L.vitx_pack_forward_device.argtypes = [vp, vp, i32p, ip, vp, vp, vp]
             L.vitx_pack_feat_enable.argtypes = [vp, ip]
+            if hasattr(L, "vitx_op_attention_pool_packed"):
+                L.vitx_pack_pool_chunks.argtypes = [C.POINTER(C.c_int), ip, C.POINTER(C.c_int)]
+                L.vitx_op_attention_pool_packed.argtypes = [vp, C.POINTER(C.c_int32), vp, vp, C.c_float, vp, vp, ip, ip, ip]
+                L.vitx_op_attention_pool_packed_tables.argtypes = [vp, vp, vp, ip, ip, vp, vp, C.c_float, vp, vp, vp, vp, ip, ip, ip]
             L.vitx_pack_feat_read.argtypes = [vp, fp, fp]
             L.vitx_pack_scratch_bytes.restype = C.c_size_t; L.vitx_pack_scratch_bytes.argtypes = [vp]
             L.vitx_pack_launches.argtypes = [vp, C.POINTER(ip)]
@@ -1250,10 +1255,11 @@ class PackContext:
     """A packed context (include/vitx.h "packed batches"): images of different shapes, their tokens end to end, in one forward."""
 
     def __init__(self, model: Model, device: int = 0, max_tokens: int = 1024, max_images: int = 16, dtype: int = F16, pos_interp: int = POS_BICUBIC, max_grids: int = 0,
-                 attn_kernel: int = PACK_ATTN_AUTO):
+                 attn_kernel: int = PACK_ATTN_AUTO, pool_head=False):
+        """pool_head: True (or 1) for a file with the attention-pooling head (a SigLIP-class file); the default refuses such a file."""
         self._h = C.c_void_p()
         self.model = model; self.max_tokens = max_tokens; self.max_images = max_images; self.dtype = dtype
-        opt = PackOptions(pos_interp=pos_interp, max_grids=max_grids, attn_kernel=attn_kernel)
+        opt = PackOptions(pos_interp=pos_interp, max_grids=max_grids, attn_kernel=attn_kernel, pool_head=int(pool_head))
         check(lib().vitx_pack_create(model._h, device, max_tokens, max_images, dtype, C.byref(opt), C.byref(self._h)), "vitx_pack_create")
         self._shapes = None; self._feat = 0
         self._dense = self._dense_out = self._dense_shapes = None
@@ -1383,9 +1389,9 @@ class PackContext:
         """The device buffer of the maps (vitx_pack_attn_device), image i at float row0[i] * floats-per-token; 0 while off."""
         return int(lib().vitx_pack_attn_device(self._h) or 0)
 
-    def feat_enable(self, cls: bool = True, tokens: bool = False) -> None:
-        """Last-layer features of every later forward (vitx_pack_feat_enable); neither: off."""
-        self._feat = (FEAT_CLS if cls else 0) | (FEAT_TOKENS if tokens else 0)
+    def feat_enable(self, cls: bool = True, tokens: bool = False, l2: bool = False) -> None:
+        """Last-layer features of every later forward (vitx_pack_feat_enable); neither: off.  l2 (pool_head contexts): cls divided by its norm."""
+        self._feat = (FEAT_CLS if cls else 0) | (FEAT_TOKENS if tokens else 0) | (FEAT_L2 if l2 else 0)
         check(lib().vitx_pack_feat_enable(self._h, self._feat), "vitx_pack_feat_enable")
 
     def feat_read(self):
@@ -1874,6 +1880,22 @@ def op_attention_pool(d_x: int, row_stride: int, img_stride: int, d_ln_w: int, d
     """vitx_op_attention_pool: the pooling kernel of the attention-pooling head (device pointers, strides in floats): M [n_img, H, D] f32 and,
     with d_p, the probabilities [n_img, H, N] f32."""
     check(lib().vitx_op_attention_pool(d_x, row_stride, img_stride, d_ln_w, d_ln_b, eps, d_u, d_M, d_p or None, n_img, N, D, H, stream or None), "vitx_op_attention_pool")
+
+
+def pack_pool_chunks(rows):
+    """vitx_pack_pool_chunks (host only): (R, chunk0) -- the chunk size of the packed pooling launch and the running count of ceil(rows[i] / R), [n + 1]."""
+    r = np.ascontiguousarray(rows, np.intc).ravel()
+    chunk0 = np.empty(r.size + 1, np.intc)
+    ip = C.POINTER(C.c_int)
+    check(lib().vitx_pack_pool_chunks(r.ctypes.data_as(ip) if r.size else None, r.size, chunk0.ctypes.data_as(ip)), "vitx_pack_pool_chunks")
+    return int(lib().vitx_pack_pool_chunk_rows()), chunk0
+
+
+def op_attention_pool_packed(d_x: int, row0, d_ln_w: int, d_ln_b: int, eps: float, d_u: int, d_M: int, D: int, H: int) -> None:
+    """vitx_op_attention_pool_packed (test entry point; synchronous): the pooling pass on a pack, d_x [rows, D] f32 with image i = rows row0[i] .. row0[i + 1] - 1
+    (row0: host [n + 1]) -> d_M [n, H, D] f32."""
+    r = np.ascontiguousarray(row0, np.int32).ravel()
+    check(lib().vitx_op_attention_pool_packed(d_x, r.ctypes.data_as(C.POINTER(C.c_int32)), d_ln_w, d_ln_b, eps, d_u, d_M, r.size - 1, D, H), "vitx_op_attention_pool_packed")
 
 
 def op_rope(dtype: int, d_qkv: int, d_cos: int, d_sin: int, n_img: int, N: int, prefix: int, D: int, H: int, lo_off: int = 0, stream: int = 0) -> None:

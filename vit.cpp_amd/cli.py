@@ -9,6 +9,7 @@ directory-walk accuracy harness:
     python vit_cli.py -m model.gguf ... --img-shape 224x448 | --img-fit 224   # a rectangular context: HxW, or the aspect-preserving shape of the input image
     python vit_cli.py -m model.gguf -i a.jpg,b.jpg,c.jpg --pack --img-fit 224   # several images, each at its own aspect-preserving shape, in one packed forward
     python vit_cli.py -m model.gguf -i a.jpg,b.jpg,c.jpg --pack --img-fit 224 --attn-map PREFIX [--attn-kind rollout|last]   # + PREFIX.<i>.pgm per image, on its own grid
+    python vit_cli.py -m siglip.gguf -i a.jpg,b.jpg --pack --img-fit 224 [--embed e.npy --embed-kind cls --embed-l2]   # an attention-pooling file: pool_head is set for it
     python vit_cli.py -m model.gguf -i a.jpg,b.jpg,c.jpg --pack --img-fit 224 --pack-u8   # the same, resized on the device from the u8 originals in one launch
     python vit_cli.py -m model.gguf ... [--preprocess model|reference]   # the file's own preprocessing (default) or the reference's for any file
     python vit_cli.py -m clip.gguf -i image.jpg -k 5 --zero-shot bank.npz   # zero-shot classes of a CLIP / SigLIP file (bank: convert.py --zero-shot-out)
@@ -221,7 +222,9 @@ def main(argv: List[str] | None = None) -> int:
         ap.error("--img-fit takes its shape from the single image of -i, not --gallery-build (use --img-shape HxW)")
     if a.pack_u8 and not a.pack:
         ap.error("--pack-u8 goes with --pack")
-    if a.pack and (not a.img_fit or a.dir is not None or a.dtype == "mxfp8" or a.embed or a.zero_shot or a.text_model or a.gallery or a.gallery_build):
+    if a.pack and a.embed and a.embed_kind != "cls":
+        ap.error("--pack --embed writes the pooled embedding of a file with the attention-pooling head: --embed-kind cls only")
+    if a.pack and (not a.img_fit or a.dir is not None or a.dtype == "mxfp8" or a.zero_shot or a.text_model or a.gallery or a.gallery_build):
         ap.error("--pack takes --img-fit SHORT, the images of -i A.jpg,B.jpg,... and --dtype f16 or bf16; of the opt-in outputs a packed context has attention maps "
                  "(--attn-map PREFIX), the dense head (--dense-head HEAD.npz --dense-out PREFIX) and the depth head (--depth-head HEAD.npz --depth-out PREFIX) only")
     if (a.img_shape or a.img_fit) and a.preprocess == "reference":
@@ -336,7 +339,13 @@ def main(argv: List[str] | None = None) -> int:
             else:
                 pixels, shapes = binding.pack_images(imgs, pp_rect, a.img_fit, patch=model.hparams.patch_size)
             tokens = int(binding.pack_check(model, shapes, 2 ** 31 - 1, len(files))[-1])
-            ctx = binding.PackContext(model, device=a.device, max_tokens=tokens, max_images=len(files), dtype=dt, pos_interp=geometry["pos_interp"])
+            # a file without prefix tokens that carries attn_pool.* (SigLIP-class): the packed attention-pooling head
+            pool_head = model.num_prefix == 0 and model.head_pool == binding.POOL_MAP
+            if a.embed and not pool_head:
+                raise binding.VitxError("--pack --embed needs a file with the attention-pooling head")
+            ctx = binding.PackContext(model, device=a.device, max_tokens=tokens, max_images=len(files), dtype=dt, pos_interp=geometry["pos_interp"], pool_head=pool_head)
+            if a.embed:
+                ctx.feat_enable(cls=True, l2=a.embed_l2)
             if dense:
                 # a label map per image at the ORIGINAL's size (never below the patch grid: a tiny original keeps the preprocessed shape's side)
                 P = model.hparams.patch_size
@@ -363,6 +372,9 @@ def main(argv: List[str] | None = None) -> int:
             maps = ctx.dense_read()[0] if dense else None
             dmaps = ctx.depth_read()[0] if depth else None
             amaps = ctx.attn_read() if a.attn_map else None
+            if a.embed:
+                np.save(a.embed, ctx.feat_read()[0])
+                print(f"main: wrote {len(files)} cls embeddings to '{a.embed}'", file=sys.stderr)
         except binding.VitxError as e:
             print(f"main: the packed forward failed: {e}", file=sys.stderr)
             return 1

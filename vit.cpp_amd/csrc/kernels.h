@@ -215,6 +215,21 @@ hipError_t launch_features(const float *x, long row_stride, long img_stride, con
 constexpr int kPoolMaxHeads = 32;
 hipError_t launch_attention_pool(const float *x, long row_stride, long img_stride, const float *w, const float *b, float eps, const float *u, float *M, void *m16, int dtype,
                                  float *p, int n_img, int N, int D, int H, hipStream_t stream);
+// The same pass on a PACK (attention_pool_packed.hip; include/vitx.h "packed batches", pool_head): image i = rows row0[i] .. row0[i + 1] - 1 of x ([rows][D]
+// f32, dense), cut into chunks of kPoolChunkRows rows from its own first row; both products on v_mfma_f32_16x16x4_f32.  Two launches: the part kernel, one
+// workgroup per (image, chunk), writes (m, l, acc[D]) per head to part [chunks][H][D + 2] f32; the combine kernel, one workgroup per (image, head), merges
+// an image's chunks in ascending order into M [n][H][D] f32 and / or m16 = RNE(M) in `dtype` (either may be nullptr).  No atomics; an image's M does not
+// depend on its position or neighbours, and rows behind an image are never read as data.
+//   pool_pack_chunks   host only, the one place the table is built: chunk0 [n + 1] (may be NULL) = the running count of ceil(rows[i] / kPoolChunkRows);
+//                      false for a null `rows`, n <= 0, a row count below 1 or more than 2^31 - 1 chunks
+//   attention_pool_packed_fits   the part kernel's LDS (two [16][D + 16] f32 tiles and 4 KiB) fits the CU's 160 KiB: D <= 1152
+//   launch_attention_pool_packed   row0 and chunk0 on the device, chunks = chunk0[n]: the caller built the tables.  1 <= H <= kPoolPackMaxHeads, D a width of
+//                      VITX_LN_WIDTHS that fits; hipErrorInvalidValue otherwise
+constexpr int kPoolChunkRows = 128, kPoolPackMaxHeads = 16;
+bool pool_pack_chunks(const int32_t *rows, int n, int32_t *chunk0);
+bool attention_pool_packed_fits(int D);
+hipError_t launch_attention_pool_packed(const float *x, const int *row0, const int *chunk0, int n, int chunks, const float *w, const float *b, float eps, const float *u,
+                                        float *part, float *M, void *m16, int dtype, int D, int H, hipStream_t stream);
 // The end of the pooled tail: e [n_img][D] f32 -> z [n_img][D] = RNE(e) in `dtype` (the head GEMM's operand) and, cls != nullptr, the feature
 // cls[i * out_img_stride ..] = e[i] (l2: divided by its norm, VITX_FEAT_L2's arithmetic).  One wave per image.
 hipError_t launch_pool_embed(const float *e, void *z, int dtype, float *cls, long out_img_stride, bool l2, int n_img, int D, hipStream_t stream);
@@ -323,8 +338,9 @@ hipError_t launch_pool_rows(int dtype, const float *X, const int *rows, const fl
 // out[r][j] = RNE(silu(f32 gate) * f32 up), j < F, rows of ld_out elements; nothing else of `out` is touched.  hipErrorInvalidValue, before any
 // launch, for F % 8 != 0, a pointer off a 16-byte boundary, a leading dimension that is no multiple of 8, ld_in < 2 F or ld_out < F.
 hipError_t launch_swiglu(int dtype, const void *in, long ld_in, void *out, long ld_out, long rows, int F, hipStream_t stream);
-// pos [1 + gy_in * gx_in][D] f32 -> out [1 + gy_out * gx_out][D] f32 (pos_resample.hip; the arithmetic: pos_resample.h); only enqueues
-hipError_t launch_pos_resample(const float *pos, int gy_in, int gx_in, int D, int gy_out, int gx_out, int interp, float *out, hipStream_t stream);
+// pos [1 + gy_in * gx_in][D] f32 -> out [1 + gy_out * gx_out][D] f32 (pos_resample.hip; the arithmetic: pos_resample.h); only enqueues.
+// cls_row = false: both tables without the class row, [gy * gx][D] (a VITX_POOL_MAP file's)
+hipError_t launch_pos_resample(const float *pos, int gy_in, int gx_in, int D, int gy_out, int gx_out, int interp, float *out, hipStream_t stream, bool cls_row = true);
 bool attention_supports(int N, int D, int H);     // any token count; head_dim 64 (tuned kernels) or any other multiple of 8 up to 128 (generic kernel)
 bool attention_single_pass_supports(int N);       // instantiation table of the register-resident kernel
 bool layernorm_supports(int D);
@@ -427,6 +443,7 @@ hipError_t prepare_attention_stream();
 hipError_t prepare_attention_text();                   // attention_text.hip
 hipError_t prepare_dense();                            // dense_label.hip
 hipError_t prepare_depth();                            // depth_map.hip
+hipError_t prepare_attention_pool_packed();            // attention_pool_packed.hip
 #pragma GCC visibility pop
 
 }  // namespace vitx

@@ -361,6 +361,51 @@ int vitx_op_attention_pool(const void *d_x, long row_stride, long img_stride, co
     return op_rc("vitx_op_attention_pool", launch_attention_pool((const float *)d_x, row_stride, img_stride, (const float *)d_ln_w, (const float *)d_ln_b, eps, (const float *)d_u,
                                                                  (float *)d_M, nullptr, DT_F16, (float *)d_p, n_img, N, D, H, (hipStream_t)stream), VITX_ERR_UNSUPPORTED);
 }
+// The pooling pass on a pack (include/vitx.h "packed batches", pool_head).  vitx_pack_pool_chunks: host only.  vitx_op_attention_pool_packed: a TEST entry
+// point -- row0 is a HOST table; the call builds chunk0, uploads both tables, allocates the partial scratch, launches on the null stream, waits and frees.
+// Every argument check comes before the first device call.
+int vitx_pack_pool_chunk_rows(void) { return kPoolChunkRows; }
+int vitx_pack_pool_chunks(const int *rows, int n, int *chunk0) {
+    if (!pool_pack_chunks(rows, n, chunk0)) { set_error("vitx_pack_pool_chunks: rows [n] must hold n >= 1 counts >= 1 that make at most 2^31 - 1 chunks of %d rows", kPoolChunkRows); return VITX_ERR_ARG; }
+    return VITX_OK;
+}
+int vitx_op_attention_pool_packed(const void *d_x, const int32_t *row0, const void *d_ln_w, const void *d_ln_b, float eps, const void *d_u, void *d_M, int n, int D, int H) {
+    const char *name = "vitx_op_attention_pool_packed";
+    if (!d_x || !row0 || !d_ln_w || !d_ln_b || !d_u || !d_M || n <= 0 || D <= 0 || H <= 0 || H > kPoolPackMaxHeads || row0[0] < 0) { set_error("%s: invalid argument (1 <= H <= %d)", name, kPoolPackMaxHeads); return VITX_ERR_ARG; }
+    for (const void *p : {d_x, d_ln_w, d_ln_b, d_u, (const void *)d_M})
+        if ((uintptr_t)p % 16) { set_error("%s: pointers must be 16-byte aligned", name); return VITX_ERR_ARG; }
+    if (!layernorm_supports(D)) { set_error("%s: hidden size %d has no LayerNorm instantiation", name, D); return VITX_ERR_UNSUPPORTED; }
+    if (!attention_pool_packed_fits(D)) { set_error("%s: the staging tiles of hidden size %d do not fit the kernel's LDS", name, D); return VITX_ERR_UNSUPPORTED; }
+    std::vector<int32_t> tab((size_t)2 * (n + 1)), rows(n);
+    for (int i = 0; i < n; ++i) {
+        if (row0[i + 1] <= row0[i]) { set_error("%s: image %d: row0 must ascend (an image has at least one row)", name, i); return VITX_ERR_ARG; }
+        rows[i] = row0[i + 1] - row0[i];
+    }
+    std::copy(row0, row0 + n + 1, tab.begin());
+    if (!pool_pack_chunks(rows.data(), n, tab.data() + n + 1)) { set_error("%s: more than 2^31 - 1 chunks", name); return VITX_ERR_ARG; }
+    const int chunks = tab[2 * n + 1];
+    if (!tuning_for_device(-1)) { set_error("%s: the device could not be opened", name); return VITX_ERR_HIP; }
+    int *d_tab = nullptr;
+    float *d_part = nullptr;
+    hipError_t e = hipMalloc((void **)&d_tab, tab.size() * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_part, (size_t)chunks * H * (D + 2) * 4);
+    if (e == hipSuccess) e = hipMemcpy(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_attention_pool_packed((const float *)d_x, d_tab, d_tab + n + 1, n, chunks, (const float *)d_ln_w, (const float *)d_ln_b, eps, (const float *)d_u, d_part,
+                                                          (float *)d_M, nullptr, DT_F16, D, H, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    (void)hipFree(d_tab); (void)hipFree(d_part);
+    return op_rc(name, e, VITX_ERR_UNSUPPORTED);
+}
+// the same two launches on tables and a partial scratch the caller built and vouches for (d_chunk0 from vitx_pack_pool_chunks, d_part [chunks][H][D + 2] f32):
+// null stream, only enqueues -- what a packed context does per forward, and what tools/pack_map_cost.py times
+int vitx_op_attention_pool_packed_tables(const void *d_x, const void *d_row0, const void *d_chunk0, int n, int chunks, const void *d_ln_w, const void *d_ln_b, float eps,
+                                         const void *d_u, void *d_part, void *d_M, void *d_m16, int dtype, int D, int H) {
+    const char *name = "vitx_op_attention_pool_packed_tables";
+    if (!d_x || !d_row0 || !d_chunk0 || !d_ln_w || !d_ln_b || !d_u || !d_part || (!d_M && !d_m16) || n <= 0 || chunks < n || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("%s: invalid argument", name); return VITX_ERR_ARG; }
+    if (!tuning_for_device(-1)) { set_error("%s: the device could not be opened", name); return VITX_ERR_HIP; }
+    return op_rc(name, launch_attention_pool_packed((const float *)d_x, (const int *)d_row0, (const int *)d_chunk0, n, chunks, (const float *)d_ln_w, (const float *)d_ln_b, eps,
+                                                    (const float *)d_u, (float *)d_part, (float *)d_M, d_m16, dtype, D, H, nullptr), VITX_ERR_UNSUPPORTED);
+}
 // The map kernels on their own (the parity tests): d_cls [n_img][H][N] class-token rows, d_mean [n_img][N][N] mean_h A_h (either may be NULL).
 int vitx_op_attention_map(int dtype, const void *d_qkv, long lo_off, void *d_cls, void *d_mean, int n_img, int N, int D, int H, void *stream) {
     if (!d_qkv || (!d_cls && !d_mean) || n_img <= 0 || N <= 0 || D <= 0 || H <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_attention_map: invalid argument"); return VITX_ERR_ARG; }

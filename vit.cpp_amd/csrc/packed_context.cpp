@@ -25,7 +25,7 @@ static void drop_grid(vitx_pack *p, size_t k) {
     PackGrid &g = p->grids[k];
     if (g.own) {
         p->retired.push_back(vitx_pack::Retired{g.pos, g.pos_bytes});
-        p->scratch_bytes -= ((size_t)g.gh * g.gw + 1) * p->D * 4;
+        p->scratch_bytes -= ((size_t)g.gh * g.gw + (p->pool_map ? 0 : 1)) * p->D * 4;
         if (p->retired.size() > 2 * (size_t)p->max_grids) { (void)hipFree(p->retired.front().pos); p->retired.erase(p->retired.begin()); }
     }
     p->grids.erase(p->grids.begin() + k);
@@ -46,7 +46,7 @@ static hipError_t take_table(vitx_pack *p, size_t bytes, float **pos, size_t *ca
 static void give_back(vitx_pack *p, PackGrid &g) {
     if (!g.own) return;
     p->retired.push_back(vitx_pack::Retired{g.pos, g.pos_bytes});
-    p->scratch_bytes -= ((size_t)g.gh * g.gw + 1) * p->D * 4;
+    p->scratch_bytes -= ((size_t)g.gh * g.gw + (p->pool_map ? 0 : 1)) * p->D * 4;
 }
 
 // The tables of every grid the call names, built the first time a call names them: the position table by launch_pos_resample on the call's
@@ -83,10 +83,10 @@ int resolve_grids(vitx_pack *p, const std::vector<uint64_t> &want, hipStream_t s
         g.gh = gh; g.gw = gw; g.used = p->tick;
         if (gh == p->g_in && gw == p->g_in) g.pos = p->wset->pos;        // the file's own grid: the file's table, as in a context of the file's size
         else {
-            const size_t bytes = ((size_t)gh * gw + 1) * p->D * 4;
+            const size_t bytes = ((size_t)gh * gw + (p->pool_map ? 0 : 1)) * p->D * 4;       // an attention-pooling file's table has no class row
             HIP_TRY(take_table(p, bytes, &g.pos, &g.pos_bytes));
             g.own = true; p->scratch_bytes += bytes;
-            const hipError_t e = launch_pos_resample(p->wset->pos, p->g_in, p->g_in, p->D, gh, gw, p->pos_interp, g.pos, st);
+            const hipError_t e = launch_pos_resample(p->wset->pos, p->g_in, p->g_in, p->D, gh, gw, p->pos_interp, g.pos, st, !p->pool_map);
             if (e != hipSuccess) { give_back(p, g); set_error("vitx_pack_forward: launch_pos_resample: %s", hipGetErrorString(e)); return VITX_ERR_HIP; }
             ++p->launches;
         }
@@ -157,11 +157,16 @@ int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_im
     if (max_grids < 1) { set_error("vitx_pack_create: max_grids %d is not positive", max_grids); return VITX_ERR_ARG; }
     int attn_kernel = opt ? opt->attn_kernel : VITX_PACK_ATTN_AUTO;
     if (attn_kernel < VITX_PACK_ATTN_AUTO || attn_kernel > VITX_PACK_ATTN_STAGED) { set_error("vitx_pack_create: unknown attn_kernel %d (0 auto, 1 generic, 2 staged)", attn_kernel); return VITX_ERR_ARG; }
+    const int pool_head = opt ? opt->pool_head : 0;
+    if (pool_head != 0 && pool_head != VITX_PACK_POOL_MAP) { set_error("vitx_pack_create: unknown pool_head %d (0 the class-token head, 1 the attention-pooling head)", pool_head); return VITX_ERR_ARG; }
+    if (pool_head && m->head_pool != VITX_POOL_MAP) { set_error("vitx_pack_create: pool_head = 1 takes a file with the attention-pooling head; this file has another head"); return VITX_ERR_ARG; }
     // every refusal before the first device call: nothing is launched after one
     if (m->in_chans == 1) { set_error("vitx_pack_create: a ViTSTR (one-channel) model takes no packed context"); return VITX_ERR_UNSUPPORTED; }
-    if (m->head_pool != VITX_POOL_CLS) { set_error("vitx_pack_create: packed contexts take the class-token head only, not the pooled (cls + mean) or the attention-pooling head"); return VITX_ERR_UNSUPPORTED; }
+    if (m->head_pool != VITX_POOL_CLS && !pool_head) { set_error("vitx_pack_create: packed contexts take the class-token head only, not the pooled (cls + mean) or the attention-pooling head"); return VITX_ERR_UNSUPPORTED; }
     const vitx_hparams &hp = m->hp;
     const int D = hp.hidden_size, H = hp.num_attention_heads, F1 = m->mlp_fc1_rows();
+    if (pool_head && H > kPoolPackMaxHeads) { set_error("vitx_pack_create: the packed attention-pooling kernel takes at most %d heads (this model: %d)", kPoolPackMaxHeads, H); return VITX_ERR_UNSUPPORTED; }
+    if (pool_head && !attention_pool_packed_fits(D)) { set_error("vitx_pack_create: the staging tiles of hidden size %d do not fit the packed attention-pooling kernel's LDS", D); return VITX_ERR_UNSUPPORTED; }
     if (!attention_packed_supports(D, H)) { set_error("vitx_pack_create: attention needs a head_dim that is a multiple of 8 up to 128 (this model: %d / %d)", D, H); return VITX_ERR_UNSUPPORTED; }
     if (attn_kernel == VITX_PACK_ATTN_STAGED && !attention_packed_staged_supports(D, H)) { set_error("vitx_pack_create: the staged attention kernel needs head_dim 64 (this model: %d / %d)", D, H); return VITX_ERR_UNSUPPORTED; }
     if (attn_kernel == VITX_PACK_ATTN_AUTO) attn_kernel = attention_packed_staged_supports(D, H) ? VITX_PACK_ATTN_STAGED : VITX_PACK_ATTN_GENERIC;
@@ -176,7 +181,8 @@ int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_im
     if (!p) return VITX_ERR_NOMEM;
     p->model = m; p->device = device; p->dtype = dtype; p->tune = tune;
     p->D = D; p->L = hp.num_hidden_layers; p->H = H; p->C = hp.num_classes; p->C_pad = head_cols_pad(m); p->P = hp.patch_size;
-    p->nreg = m->num_registers; p->Tp = 1 + p->nreg; p->g_in = hp.img_size / hp.patch_size; p->Kpe_pad = patch_k_pad(m);
+    p->pool_map = pool_head == VITX_PACK_POOL_MAP;
+    p->nreg = m->num_registers; p->Tp = p->pool_map ? 0 : 1 + p->nreg; p->g_in = hp.img_size / hp.patch_size; p->Kpe_pad = patch_k_pad(m);
     p->glu = m->glu_kind != VITX_GLU_NONE; p->F = m->mlp_hidden(); p->F1 = F1; p->rope = m->rope_kind != VITX_ROPE_NONE;
     p->fc1_epi = p->glu ? EPI_BIAS : act_epi(m->activation); p->eps = hp.eps;
     p->tm = gemm_tile_m(); p->tn = gemm_tile_n();
@@ -201,6 +207,15 @@ int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_im
     if ((rc = dmalloc((void **)&p->logits, Bp * (size_t)p->C_pad * 4))) return rc;
     if ((rc = dmalloc((void **)&p->probs, (size_t)max_images * p->C * 4))) return rc;
     if ((rc = dmalloc((void **)&p->logits_out, (size_t)max_images * p->C * 4))) return rc;
+    if (p->pool_map) {   // the pooling launch's partial scratch (every image adds at most one partly filled chunk) and the pooled tail's rows
+        p->max_chunks = max_tokens / kPoolChunkRows + max_images;
+        if ((rc = dmalloc((void **)&p->pool_part, (size_t)p->max_chunks * H * (D + 2) * 4))) return rc;
+        if ((rc = dmalloc(&p->Mp, Bp * H * D * 2))) return rc;
+        if ((rc = dmalloc(&p->Uv, Bp * D * 2))) return rc;
+        if ((rc = dmalloc((void **)&p->Xc, Bp * D * 4))) return rc;
+        if ((rc = dmalloc(&p->U2, Bp * D * 2))) return rc;
+        if ((rc = dmalloc(&p->Hm, Bp * 4 * D * 2))) return rc;
+    }
     if (p->rope) {       // a call's grids hold at most max_tokens patches; twice that, so that grids of earlier calls stay cached
         p->rope_cap = 2L * max_tokens * (D / H / 2);
         if ((rc = dmalloc((void **)&p->rope_cos, (size_t)p->rope_cap * 4))) return rc;

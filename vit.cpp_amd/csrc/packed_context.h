@@ -15,7 +15,7 @@
 
 using namespace vitx;
 
-enum PackPart : unsigned { kDense = 1u << 0, kDepth = 1u << 1, kU8 = 1u << 2, kRollout = 1u << 3 };
+enum PackPart : unsigned { kDense = 1u << 0, kDepth = 1u << 1, kU8 = 1u << 2, kRollout = 1u << 3, kPoolMap = 1u << 4 };
 
 // The segment tables of a call, in their order in vitx_pack::tab / host: `per_image` ints per image the context holds (cap = max_images) and `plus`
 // more.  A table of part 0 is always there, another while its part is on.  One buffer, one upload; a new table goes at the end of this list.
@@ -26,12 +26,13 @@ constexpr PackTable kPackTables[] = {
     {kDepth, 1, 1}, {kDepth, 1, 1}, {kDepth, kDepthSegInts, 0},      // ftile0 [cap + 1] | otile0 [cap + 1] | dseg [cap][kDepthSegInts]  (depth_pack_tables)
     {kU8, 1, 1}, {kU8, kPpSegInts, 0},                               // ptile0 [cap + 1] | pseg [cap][kPpSegInts]                (pp_pack_tables)
     {kRollout, 1, 1}, {kRollout, 1, 1},                              // rblk0 [cap + 1] | sq0 [cap + 1]                          (attn_pack_tables)
+    {kPoolMap, 1, 1},                                                // chunk0 [cap + 1]                                         (pool_pack_chunks)
 };
 
 struct PackLayout {
     size_t cap;
     unsigned parts;                      // PackPart bits: the parts whose tables the buffer holds
-    enum Table { kRow0, kQb0, kToff, kTile0, kSeg, kFtile0, kOtile0, kDseg, kPtile0, kPseg, kRblk0, kSq0, kTables };
+    enum Table { kRow0, kQb0, kToff, kTile0, kSeg, kFtile0, kOtile0, kDseg, kPtile0, kPseg, kRblk0, kSq0, kChunk0, kTables };
     static_assert(sizeof(kPackTables) / sizeof(kPackTables[0]) == kTables, "one name per table");
     // the ints in front of table t: the tables before it whose part is on (a table of a part that is off is placed as if that part alone were on too)
     size_t at(int t) const {
@@ -52,6 +53,7 @@ struct PackLayout {
     size_t pseg() const { return at(kPseg); }
     size_t rblk0() const { return at(kRblk0); }
     size_t sq0() const { return at(kSq0); }
+    size_t chunk0() const { return at(kChunk0); }
     size_t ints() const { return at(kTables); }
 };
 
@@ -79,6 +81,7 @@ struct PackCall {
     PackDepthCall depth;                 // with a depth head set
     PackU8Call u8;                       // with u8 sources declared for the call
     PackRolloutCall roll;                // with attention rollout on
+    std::vector<int32_t> chunk0;         // a context of an attention-pooling file: the running chunk count of the pooling launch [n + 1] (pool_pack_chunks)
 };
 
 // Attention maps (vitx_pack_attn_enable): the image context's AttnMaps per image of a pack.  Image i's floats of `out` start at row0[i] * fpt: the
@@ -111,7 +114,7 @@ struct PackU8 {
 // One grid of the table cache: the position table resampled to gh x gw and the grid's place in the rotary arenas
 struct PackGrid {
     int gh = 0, gw = 0;
-    float *pos = nullptr;                // [1 + gh gw][D] f32; the weight set's own table (own == false) at the file's grid
+    float *pos = nullptr;                // [1 + gh gw][D] f32 ([gh gw][D] without a class token); the weight set's own table (own == false) at the file's grid
     bool own = false;
     size_t pos_bytes = 0;                // bytes allocated behind an own table (a reused one may be larger than the grid needs)
     long rope_off = 0;                   // floats into rope_cos / rope_sin: the grid's [gh gw][hd / 2] table (files with `rope`)
@@ -124,6 +127,7 @@ struct vitx_pack {
     int D = 0, L = 0, H = 0, C = 0, C_pad = 0, P = 0, Tp = 1, nreg = 0, g_in = 0, Kpe_pad = 0;
     int F = 0, F1 = 0;                   // MLP widths: fc2's K and fc1's N (4 D both, or F and 2 F of a `glu` file)
     bool glu = false, rope = false;
+    bool pool_map = false;               // options.pool_head: an attention-pooling file -- no prefix rows (Tp = 0), the pooled tail in place of the class rows
     int fc1_epi = EPI_BIAS_GELU;
     float eps = 1e-6f;
     int tm = 256, tn = 128;
@@ -139,6 +143,12 @@ struct vitx_pack {
     void *Z = nullptr;                   // [Bpad][D] operand type: the class rows through the final norm, Bpad = max_images rounded up
     float *logits = nullptr, *probs = nullptr;      // [Bpad][C_pad], [max_images][C] f32
     float *logits_out = nullptr;         // [max_images][C] f32: the dense logits of the host entry point
+    // pool_map only, allocated at creation: the pooling launch's partial scratch [max_chunks][H][D + 2] f32, then one row per image -- Mp [Bpad][H][D] =
+    // RNE(M), Uv [Bpad][D] the value projections, Xc [Bpad][D] f32 = a, then e, U2 [Bpad][D] its LayerNorm, Hm [Bpad][4 D] (operand type unless f32)
+    float *pool_part = nullptr, *Xc = nullptr;
+    void *Mp = nullptr, *Uv = nullptr, *U2 = nullptr, *Hm = nullptr;
+    int max_chunks = 0;
+    std::vector<int32_t> chunk0;         // PackCall::chunk0 of the last call that passed its checks
     DevMem img;                          // the host entry point's f32 pixels on the device (allocated by its first call, or by vitx_pack_u8_set: the u8
                                          // preprocessing writes them there)
     int *tab = nullptr;                  // the segment tables of a call (PackLayout)
@@ -160,6 +170,7 @@ struct vitx_pack {
     int feat_flags = 0;                  // vitx_pack_feat_enable
     DevMem feat;                         // [max_tokens][D] f32 final-norm rows of the last forward (allocated by vitx_pack_feat_enable)
     int feat_n = 0;                      // images of the last forward with features on (0: none)
+    DevMem feat_cls;                     // pool_map with VITX_FEAT_CLS: [max_images][D] f32, the pooled embeddings e of the last forward
     std::unique_ptr<PackDense> dense;    // vitx_pack_dense_set (null: off); its device memory is its own
     std::unique_ptr<PackDepth> depth;    // vitx_pack_depth_set (null: off); its device memory is its own
     std::unique_ptr<PackU8> u8;          // vitx_pack_u8_set (null: off)
@@ -167,7 +178,7 @@ struct vitx_pack {
     bool rollout() const { return attn && attn->rollout(); }         // the rollout tables are there; class maps alone add no table
     int launches = 0, pe_launches = 0;   // kernel launches of the last forward, and how many of them were patch embeddings
     size_t scratch_bytes = 0;            // device bytes of activation scratch and tables held now
-    unsigned parts() const { return (dense ? kDense : 0u) | (depth ? kDepth : 0u) | (u8 ? kU8 : 0u) | (rollout() ? kRollout : 0u); }
+    unsigned parts() const { return (dense ? kDense : 0u) | (depth ? kDepth : 0u) | (u8 ? kU8 : 0u) | (rollout() ? kRollout : 0u) | (pool_map ? kPoolMap : 0u); }
     PackLayout layout() const { return PackLayout{(size_t)max_images, parts()}; }
     // image i of the last call that passed its checks: its patch rows, and where they start in an output that holds every image's patch rows end to end
     size_t patch_rows(int i) const { return (size_t)(row0[i + 1] - row0[i] - Tp); }

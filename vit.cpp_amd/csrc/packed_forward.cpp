@@ -161,6 +161,12 @@ int check_call(vitx_pack *p, const void *d_imgs, const int32_t *shapes, int n, P
     if (c->want.size() > (size_t)p->max_grids) { set_error("vitx_pack_forward: the call names %d distinct grids, the table cache holds max_grids = %d", (int)c->want.size(), p->max_grids); return VITX_ERR_ARG; }
     if (dn && (rc = check_dense("vitx_pack_forward", p->model, shapes, next_out.empty() ? nullptr : next_out.data(), (int)(next_out.size() / 2), n, dn->K, dn->max_pixels, &c->dense))) return rc;
     if (dp && (rc = check_depth("vitx_pack_forward", p->model, shapes, next_depth.empty() ? nullptr : next_depth.data(), (int)(next_depth.size() / 2), n, dp->K, dp->u, dp->max_pixels, &c->depth))) return rc;
+    if (p->pool_map) {   // the pooling launch's chunk table; an image's rows are its patches
+        std::vector<int32_t> rows(n);
+        for (int i = 0; i < n; ++i) rows[i] = c->row0[i + 1] - c->row0[i];
+        c->chunk0.resize((size_t)n + 1);
+        if (!pool_pack_chunks(rows.data(), n, c->chunk0.data())) { set_error("vitx_pack_forward: the call's images make more than 2^31 - 1 pooling chunks"); return VITX_ERR_ARG; }
+    }
     if (p->rollout() && (rc = check_attn("vitx_pack_forward", c->row0.data(), n, p->attn->max_sq, &c->roll))) return rc;
     if (from_u8) {
         if ((uintptr_t)d_imgs & 3) { set_error("vitx_pack_forward: the u8 sources must be 4-byte aligned"); return VITX_ERR_ARG; }
@@ -203,6 +209,32 @@ int pack_gemm(vitx_pack *p, int epi, const GemmArgs &a, hipStream_t st) {
     return VITX_OK;
 }
 
+// The attention-pooling head on a pack (options.pool_head), after the last layer: the pooling pass over the pack's rows in two launches
+// (attention_pool_packed.hip) -> Mp = RNE(M) [n][H][D]; then SliceForward::pooled_tail's sequence on one row per image: the value projection, H launches on
+// strided operands (head h reads Mp[:, h, :] and writes columns h d .. (h + 1) d of Uv); proj -> a (f32, Xc); LayerNorm -> U2; fc1 + activation -> Hm;
+// fc2 + residual -> e (Xc, in place); Z = RNE(e) and, with VITX_FEAT_CLS on, the feature.  H + 7 launches.
+int pack_pooled_tail(vitx_pack *p, const PackLayout &at, int n, int Mh, hipStream_t st) {
+    int rc;
+    const WeightSet &ws = *p->wset;
+    const int D = p->D, H = p->H, d = D / H, dt = p->dtype, tn = p->tn;
+    HIP_TRY(launch_attention_pool_packed(p->X, p->tab + at.row0(), p->tab + at.chunk0(), n, p->chunk0[n], ws.norm_w, ws.norm_b, p->eps, ws.map_u, p->pool_part, nullptr, p->Mp, dt,
+                                         D, H, st));
+    p->launches += 2;
+    for (int h = 0; h < H; ++h) {
+        GemmArgs a = dense_gemm((const char *)p->Mp + (size_t)h * D * 2, (const char *)ws.map_v_w + (size_t)h * d * D * 2, ws.map_v_b + h * d, (char *)p->Uv + (size_t)h * d * 2, Mh, n, d,
+                                round_up(d, 128), D, D);
+        a.lda = H * D;
+        if ((rc = pack_gemm(p, EPI_BIAS, a, st))) return rc;
+    }
+    if ((rc = pack_gemm(p, EPI_BIAS_F32, dense_gemm(p->Uv, ws.map_proj_w, ws.map_proj_b, p->Xc, Mh, n, D, round_up(D, tn), D), st))) return rc;
+    HIP_TRY(launch_layernorm(dt, p->Xc, D, ws.map_ln_w, ws.map_ln_b, p->U2, D, n, D, p->eps, st)); ++p->launches;
+    if ((rc = pack_gemm(p, p->fc1_epi, dense_gemm(p->U2, ws.map_fc1_w, ws.map_fc1_b, p->Hm, Mh, n, 4 * D, round_up(4 * D, tn), D), st))) return rc;
+    if ((rc = pack_gemm(p, EPI_BIAS_RESID, dense_gemm(p->Hm, ws.map_fc2_w, ws.map_fc2_b, p->Xc, Mh, n, D, round_up(D, tn), 4 * D), st))) return rc;
+    const bool cls = (p->feat_flags & VITX_FEAT_CLS) != 0;
+    HIP_TRY(launch_pool_embed(p->Xc, p->Z, dt, cls ? p->feat_cls.as<float>() : nullptr, D, (p->feat_flags & VITX_FEAT_L2) != 0, n, D, st)); ++p->launches;
+    return VITX_OK;
+}
+
 // Each part's tables of a call into the staging buffer `host`, where the layout puts them.  lrow [n]: image i's first logit row, behind its prefix rows
 void dense_tables(const PackDenseCall &c, const int32_t *lrow, int n, const PackLayout &at, int *host) {
     std::copy(c.tile0.begin(), c.tile0.end(), host + at.tile0());
@@ -233,7 +265,7 @@ int pack_forward(vitx_pack *p, PackCall &c, const void *d_imgs, const int32_t *s
     PackDepth *dp = p->depth.get();
     PackAttn *am = p->attn.get();
     HIP_TRY(hipSetDevice(p->device));
-    p->row0.swap(c.row0); p->feat_n = 0;
+    p->row0.swap(c.row0); p->chunk0.swap(c.chunk0); p->feat_n = 0;
     if (dn) { std::swap(dn->last, c.dense); dn->n = 0; }
     if (dp) { std::swap(dp->last, c.depth); dp->n = 0; }
     if (am) { std::swap(am->last, c.roll); am->n = 0; }
@@ -259,6 +291,7 @@ int pack_forward(vitx_pack *p, PackCall &c, const void *d_imgs, const int32_t *s
     if (dp) depth_tables(dp->last, lrow.data(), n, dp->u, at, host);
     if (c.u8.on) u8_tables(c.u8, at, host);
     if (at.parts & kRollout) rollout_tables(am->last, at, host);
+    if (p->pool_map) std::copy(p->chunk0.begin(), p->chunk0.end(), host + at.chunk0());
     HIP_TRY(hipMemcpyAsync(p->tab, p->host.data(), p->host.size() * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(p->uploaded, st));
     p->uploaded_pending = true;
@@ -315,14 +348,17 @@ int pack_forward(vitx_pack *p, PackCall &c, const void *d_imgs, const int32_t *s
             ++p->launches;
         }
     }
-    // the class rows through the final norm (row0[i] is image i's class row), the head GEMM in f32, the class softmax
-    HIP_TRY(launch_pool_rows(dt, p->X, d_row0, ws.norm_w, ws.norm_b, p->Z, n, Mh, D, p->eps, st)); ++p->launches;
+    // the class rows through the final norm (row0[i] is image i's class row), the head GEMM in f32, the class softmax; an attention-pooling file has no
+    // class row: its Z comes out of the pooled tail
+    if (p->pool_map) { if ((rc = pack_pooled_tail(p, at, n, Mh, st))) return rc; }
+    else { HIP_TRY(launch_pool_rows(dt, p->X, d_row0, ws.norm_w, ws.norm_b, p->Z, n, Mh, D, p->eps, st)); ++p->launches; }
     float *lg = d_logits ? d_logits : p->logits;
     const int ldl = d_logits ? p->C : p->C_pad;
     if ((rc = pack_gemm(p, EPI_BIAS_F32, dense_gemm(p->Z, ws.head_w, ws.head_b, lg, Mh, n, p->C, p->C_pad, D, ldl), st))) return rc;
     HIP_TRY(launch_softmax(dt, lg, d_probs, n, p->C, ldl, st)); ++p->launches;
     // features (vitx_pack_feat_enable): the f32 final norm of every row of the pack; vitx_pack_feat_read gathers the rows it was asked for
-    if (p->feat_flags) { HIP_TRY(launch_layernorm_f32(p->X, ws.norm_w, ws.norm_b, p->feat.as<float>(), rows, D, p->eps, st)); ++p->launches; p->feat_n = n; }
+    if (p->pool_map ? (p->feat_flags & VITX_FEAT_TOKENS) != 0 : p->feat_flags != 0) { HIP_TRY(launch_layernorm_f32(p->X, ws.norm_w, ws.norm_b, p->feat.as<float>(), rows, D, p->eps, st)); ++p->launches; }
+    if (p->feat_flags) p->feat_n = n;
     // the dense head: the logits of every row of the pack, then one label launch over the images' own output shapes (2 launches; the memset of
     // the operand's pad rows is not a kernel)
     if (dn) {

@@ -36,9 +36,13 @@ int pack_head_window(const char *api, const vitx_pack *p, size_t Mp, int Dc, siz
 extern "C" {
 
 int vitx_pack_feat_enable(vitx_pack *p, int flags) {
-    if (!p || (flags & ~(VITX_FEAT_CLS | VITX_FEAT_TOKENS))) { set_error("vitx_pack_feat_enable: flags are VITX_FEAT_CLS | VITX_FEAT_TOKENS (0 = off)"); return VITX_ERR_ARG; }
+    if (!p || (flags & ~(VITX_FEAT_CLS | VITX_FEAT_TOKENS | (p->pool_map ? VITX_FEAT_L2 : 0)))) { set_error("vitx_pack_feat_enable: flags are VITX_FEAT_CLS | VITX_FEAT_TOKENS (0 = off), and VITX_FEAT_L2 on a context of an attention-pooling file"); return VITX_ERR_ARG; }
     HIP_TRY(hipSetDevice(p->device));
-    if (flags && !p->feat) {
+    if (p->pool_map) {   // cls is the pooled embedding, one row per image; the final-norm rows are kept for the tokens only
+        if (const int rc = pack_quiesce(p)) return rc;
+        if ((flags & VITX_FEAT_CLS) && !p->feat_cls && !alloc_counted(p->feat_cls, (size_t)p->max_images * p->D * 4, &p->scratch_bytes)) { set_error("vitx_pack_feat_enable: cannot allocate the embeddings of %d images", p->max_images); return VITX_ERR_NOMEM; }
+        if ((flags & VITX_FEAT_TOKENS) && !p->feat && !alloc_counted(p->feat, (size_t)p->max_tokens * p->D * 4, &p->scratch_bytes)) { set_error("vitx_pack_feat_enable: cannot allocate the features of %d token rows", p->max_tokens); return VITX_ERR_NOMEM; }
+    } else if (flags && !p->feat) {
         const size_t bytes = (size_t)p->max_tokens * p->D * 4;
         HIP_TRY(hipMalloc(&p->feat.p, bytes));
         p->scratch_bytes += bytes;
@@ -56,13 +60,15 @@ int vitx_pack_feat_read(vitx_pack *p, float *cls, float *tokens) {
     if (p->done_pending) HIP_TRY(hipEventSynchronize(p->done));
     const int n = p->feat_n;
     const size_t D = (size_t)p->D;
-    if (cls) for (int i = 0; i < n; ++i) HIP_TRY(hipMemcpy(cls + i * D, p->feat.as<float>() + p->row0[i] * D, D * 4, hipMemcpyDeviceToHost));
+    if (cls && p->pool_map) HIP_TRY(hipMemcpy(cls, p->feat_cls.p, n * D * 4, hipMemcpyDeviceToHost));
+    else if (cls) for (int i = 0; i < n; ++i) HIP_TRY(hipMemcpy(cls + i * D, p->feat.as<float>() + p->row0[i] * D, D * 4, hipMemcpyDeviceToHost));
     return tokens ? read_patch_rows(p, n, p->feat.as<float>(), D, tokens) : VITX_OK;
 }
 
 // Attention maps of a packed context (include/vitx.h "packed batches")
 int vitx_pack_attn_enable(vitx_pack *p, uint64_t layer_mask, int flags, long max_sq_tokens) {
     if (!p) { set_error("vitx_pack_attn_enable: NULL context"); return VITX_ERR_ARG; }
+    if (p->pool_map) { set_error("vitx_pack_attn_enable: not offered on a packed context of a file with the attention-pooling head"); return VITX_ERR_UNSUPPORTED; }
     if (const int rc = pack_attn_args("vitx_pack_attn_enable", p->L, layer_mask, flags, max_sq_tokens)) return rc;
     const bool on = layer_mask != 0 || flags != 0, rollout = (flags & VITX_ATTN_ROLLOUT) != 0;
     HIP_TRY(hipSetDevice(p->device));
@@ -106,6 +112,7 @@ int vitx_pack_attn_read(vitx_pack *p, float *out, size_t n_floats) {
 int vitx_pack_dense_set(vitx_pack *p, const float *W, const float *bias, int K, int Dc, uint64_t layer_mask, long max_pixels, int flags) {
     const char *api = "vitx_pack_dense_set";
     if (!p) { set_error("vitx_pack_dense_set: NULL context"); return VITX_ERR_ARG; }
+    if (p->pool_map) { set_error("vitx_pack_dense_set: not offered on a packed context of a file with the attention-pooling head"); return VITX_ERR_UNSUPPORTED; }
     const bool off = !W && K == 0;
     uint64_t mask = layer_mask;
     const size_t Mp = (size_t)round_up(p->max_tokens, p->tm), Kpad = K > 0 ? (size_t)round_up(K, p->tn) : 0;
@@ -168,6 +175,7 @@ int vitx_pack_depth_set(vitx_pack *p, const float *Wp, const float *Wc, const fl
                         float min_depth, float max_depth, long max_pixels, int flags) {
     const char *api = "vitx_pack_depth_set";
     if (!p) { set_error("vitx_pack_depth_set: NULL context"); return VITX_ERR_ARG; }
+    if (p->pool_map) { set_error("vitx_pack_depth_set: not offered on a packed context of a file with the attention-pooling head"); return VITX_ERR_UNSUPPORTED; }
     const bool off = !Wp && K == 0;
     uint64_t mask = layer_mask;
     const size_t Mp = (size_t)round_up(p->max_tokens, p->tm), Bp = (size_t)round_up(p->max_images, p->tm), Kpad = K > 0 ? (size_t)round_up(K, p->tn) : 0;

@@ -19,6 +19,7 @@ static hipError_t prepare_device_kernels(const Tuning &t) {
     if (e == hipSuccess) e = prepare_attention_text();
     if (e == hipSuccess) e = prepare_dense();
     if (e == hipSuccess) e = prepare_depth();
+    if (e == hipSuccess) e = prepare_attention_pool_packed();
     return e;
 }
 
