@@ -493,6 +493,23 @@ enum vitx_glu_kind { VITX_GLU_NONE = 0, VITX_GLU_SWIGLU = 1 };
 int vitx_model_glu(const vitx_model *m, int *kind, int *width);
 int vitx_op_swiglu(int dtype, const void *d_in, long ld_in, void *d_out, long ld_out, long rows, int F, void *stream);
 
+/* ---- MLP width --------------------------------------------------------------------
+ * A file may carry `mlp`, f32 [4] = {F, 0, 0, 0}: the plain (ungated) MLP of every block, fc2( act(fc1(x)) ), then has hidden width F instead of 4 D
+ * (SigLIP SO400M: D 1152, F 4304; ViT-g/14: D 1408, F 6144; any mlp_ratio).  blocks.i.mlp.fc1.weight is [F][D], fc1.bias [F], fc2.weight [D][F], and
+ * the attention-pooling head's attn_pool.mlp.* tensors have the same F.  Image and text-tower files take it.  F is a whole number, at least 8 and a
+ * multiple of 8; the reserved slots are 0; `mlp` stands IN FRONT of the first blocks.* record, as `glu` does, and a file has `mlp` or `glu`, never
+ * both: anything else is VITX_ERR_FORMAT.  vitx_model_resize_file and vitx_quantize_file copy the tensor byte for byte; a block-quantised tensor
+ * keeps its rules, and fc2's rows are F long: vitx_quantize_file itself refuses (VITX_ERR_FORMAT, "not a multiple of 32") an F that is no
+ * multiple of 32, and an F with F % 64 == 32 quantises to a file the loader refuses with its "needs ne[0] % 64 == 0".  Only multiples of 64 quantise.
+ * THE PADDING RULE.  The GEMMs step K by 64, so a context runs the width Fp = round_up(F, 64).  The upload zero-fills fc1's rows F .. Fp-1 and their
+ * bias, and fc2's columns F .. Fp-1.  tanh-GELU, erf-GELU and QuickGELU all map 0 to exactly 0, so the pad columns of the hidden buffer hold zeros and
+ * fc2 adds exact zeros: the result has the bits of the same model filed at width Fp with those zeros written out.  No kernel knows about it; an F that
+ * is a multiple of 64 pads nothing.  Image contexts (square, img_size, rectangular), packed contexts and text contexts take such a file.
+ * VITX_MXFP8 contexts and ViTSTR (one-channel) contexts of it: VITX_ERR_UNSUPPORTED at creation.  A file without `mlp` loads, runs and hashes
+ * exactly as before.
+ *   vitx_model_mlp_width   the file's F: the `mlp` tensor's, the `glu` tensor's, or 4 D; 0 for NULL */
+int vitx_model_mlp_width(const vitx_model *m);
+
 /* ---- several GPUs in one process (north_star: batch shards + one RCCL gather) -- */
 /* One context (replicated weights) and one PERSISTENT host thread per listed device (created here, parked between calls).  Images are
  * cut into contiguous shards, run concurrently, and the results are all-gathered with ONE ncclAllGather over RCCL.
@@ -1118,6 +1135,11 @@ int vitx_op_text_pool(int dtype, const void *d_x, const void *d_pooled, const vo
 int vitx_op_attention_text(int dtype, const void *d_qkv, void *d_out, int n, int T, int D, int H, int causal, void *stream);
 /* attention_generic.hip at any head dim it takes, 64 included (vitx_op_attention prefers the tuned families there): the yardstick of tools/text_cost.py */
 int vitx_op_attention_generic(int dtype, const void *d_qkv, void *d_out, int n_img, int N, int D, int H, void *stream);
+/* attention_wide.hip on its own: head dims 72, 80, .., 128 (else VITX_ERR_UNSUPPORTED), the kernel vitx_op_attention runs there.  The same contract
+ * and, per (image, head), the same bits as vitx_op_attention_generic; K and V go through LDS once per workgroup instead of once per wave.  The one
+ * difference: where N % 32 != 0 and v[N - 1] of an (image, head) holds +-Inf, the generic kernel's 0 * Inf = NaN of the masked keys is a 0 here.
+ * TEST ENTRY: null stream (it only enqueues there). */
+int vitx_op_attention_wide(int dtype, const void *d_qkv, void *d_out, int n_img, int N, int D, int H);
 
 /* ---- packed batches: images of different shapes in one forward ---------------------
  * A rectangular context runs one shape.  A PACKED context takes n images, each with its own h_i x w_i (positive multiples of the patch

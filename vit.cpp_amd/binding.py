@@ -65,9 +65,9 @@ EXPORTS = [
     "vitx_depth_set", "vitx_depth_bins", "vitx_depth_shape", "vitx_depth_images", "vitx_depth_read", "vitx_depth_device", "vitx_depth_scratch_bytes",
     "vitx_op_depth_fine", "vitx_op_depth_resize", "vitx_depth_host", "vitx_op_depth", "vitx_op_depth_rows",
     "vitx_model_kind", "vitx_model_text_info", "vitx_model_text_zs", "vitx_text_create", "vitx_text_free", "vitx_text_embed", "vitx_text_embed_device", "vitx_text_shares_weights", "vitx_text_check_ids",
-    "vitx_op_text_embed", "vitx_op_text_pool", "vitx_op_attention_text", "vitx_op_attention_generic",
+    "vitx_op_text_embed", "vitx_op_text_pool", "vitx_op_attention_text", "vitx_op_attention_generic", "vitx_op_attention_wide",
     "vitx_model_rope", "vitx_model_rope_table", "vitx_op_rope",
-    "vitx_model_glu", "vitx_op_swiglu",
+    "vitx_model_glu", "vitx_op_swiglu", "vitx_model_mlp_width",
     "vitx_ctx_create_rect", "vitx_ctx_img_shape", "vitx_ctx_grid", "vitx_op_patch_embed_rect",
     "vitx_rect_shape", "vitx_preprocess_rect", "vitx_preprocess_rect_device", "vitx_preprocess_rect_device_supports",
     "vitx_pack_create", "vitx_pack_free", "vitx_pack_shares_weights", "vitx_pack_check", "vitx_pack_distinct_grids", "vitx_pack_forward", "vitx_pack_forward_device",
@@ -312,6 +312,10 @@ def lib():
             L.vitx_op_text_pool.argtypes = [ip, vp, vp, vp, vp, vp, ip, ip, ip, C.c_float, vp]
             L.vitx_op_attention_text.argtypes = [ip, vp, vp, ip, ip, ip, ip, ip, vp]
             L.vitx_op_attention_generic.argtypes = [ip, vp, vp, ip, ip, ip, ip, vp]
+        if hasattr(L, "vitx_model_mlp_width"):
+            L.vitx_model_mlp_width.argtypes = [vp]
+        if hasattr(L, "vitx_op_attention_wide"):
+            L.vitx_op_attention_wide.argtypes = [ip, vp, vp, ip, ip, ip, ip]
         if hasattr(L, "vitx_op_rope"):
             L.vitx_model_rope.argtypes = [vp, C.POINTER(ip), C.POINTER(C.c_float)]
             L.vitx_model_rope_table.argtypes = [vp, ip, ip, C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -475,6 +479,11 @@ class Model:
         """(kind, F) of a file with a `glu` tensor (a gated MLP of hidden width F: fc1 is [2 F][D], fc2 [D][F]), or None."""
         k, w = C.c_int(), C.c_int()
         return (k.value, w.value) if lib().vitx_model_glu(self._h, C.byref(k), C.byref(w)) else None
+
+    @property
+    def mlp_width(self) -> int:
+        """The file's MLP hidden width F: the `mlp` tensor's (include/vitx.h "MLP width"), the `glu` tensor's, or 4 D.  A context runs round_up(F, 64)."""
+        return int(lib().vitx_model_mlp_width(self._h))
 
     def rope_table(self, grid) -> Tuple[np.ndarray, np.ndarray]:
         """vitx_model_rope_table: (cos, sin), each f32 [gh * gw, head_dim / 2], for a grid g or (gh, gw); row-major over (y, x)."""
@@ -1918,6 +1927,11 @@ def op_text_pool(dtype: int, d_x: int, d_pooled: int, d_w: int, d_b: int, d_z: i
 
 def op_attention_text(dtype: int, d_qkv: int, d_out: int, n: int, T: int, D: int, H: int, causal: bool, stream: int = 0) -> None:
     check(lib().vitx_op_attention_text(dtype, d_qkv, d_out, n, T, D, H, 1 if causal else 0, stream), "vitx_op_attention_text")
+
+
+def op_attention_wide(dtype: int, d_qkv: int, d_out: int, n_img: int, N: int, D: int, H: int) -> None:
+    """vitx_op_attention_wide: the LDS-staged attention of head dims 72 .. 128 on qkv [n_img * N][3 D] -> out [n_img * N][D]; null stream."""
+    check(lib().vitx_op_attention_wide(dtype, d_qkv, d_out, n_img, N, D, H), "vitx_op_attention_wide")
 
 
 def zeroshot_max_classes(E: int) -> int:

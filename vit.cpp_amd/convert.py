@@ -35,7 +35,7 @@ Its preprocessing travels too (include/vitx.h "each model's own preprocessing"):
 f32(255.0 * mean).  --no-preproc writes the file without it: the reference's stretch and ImageNet mean / std then apply.  A timm checkpoint has no
 processor: the --pp-* options state one (cli_preproc); with none of them no tensor is written and the file keeps the reference's bytes.
 
-What is refused, by name: an activation the forward path does not evaluate; an MLP that is not 4 x hidden (SigLIP SO400M's 4304); a head_dim that
+What is refused, by name: an activation the forward path does not evaluate; a plain MLP that is not 4 x hidden (SigLIP SO400M's 4304) unless mlp_width=True / --mlp-width opts in to the `mlp` tensor {F, 0, 0, 0}; a head_dim that
 is no multiple of 8 up to 128; qkv_bias=False; SwiGLU (use_swiglu_ffn) and DINOv3's gated MLP (use_gated_mlp) unless gated_mlp=True / --gated-mlp opts in, a gate
 activation other than silu and a gated width that is no multiple of 64; qk-norm, fc_norm and distillation tokens; a SigLIP tower without its pooling head
 (vision_use_head = False), SiglipForImageClassification (a mean-pool classifier: no slot), Siglip2VisionModel (NaFlex: its patch embedding is a
@@ -243,10 +243,22 @@ def _zero_head(out: dict, D: int) -> None:
     out["head.weight"] = np.zeros((1, D), np.float32); out["head.bias"] = np.zeros((1,), np.float32)
 
 
-def _require_mlp_4x(cfg, field: str, want: int, note: str = "") -> None:
+def _require_mlp_4x(cfg, field: str, want: int, note: str = "", mlp_width: bool = False) -> None:
+    """Refuses a plain MLP that is not 4 x hidden -- unless the caller has opted in to the `mlp` tensor (mlp_width: _with_mlp_width then writes it)."""
     have = getattr(cfg, field, want)
-    if have != want:
+    if have != want and not mlp_width:
         raise ValueError(f"{field} {have}: the file format holds a 4 x hidden MLP{note}")
+
+
+def _with_mlp_width(tensors: dict, D: int) -> dict:
+    """`tensors` with the `mlp` tensor {F, 0, 0, 0} in front where the plain MLP's width F (fc1's rows) is not 4 D (include/vitx.h "MLP width"); a
+    gated file (`glu`) and a 4 x hidden one come back as they are."""
+    F = int(np.shape(tensors["blocks.0.mlp.fc1.weight"])[0])
+    if "glu" in tensors or F == 4 * D:
+        return tensors
+    if F < 8 or F % 8:
+        raise ValueError(f"MLP of hidden width {F}: the `mlp` tensor takes multiples of 8")
+    return {"mlp": np.array([F, 0, 0, 0], np.float32), **tensors}
 
 
 _GATED_HOWTO = ("pass gated_mlp=True (convert.py --gated-mlp) to write it with the `glu` tensor: such a file cannot be read by the reference or by an engine "
@@ -287,7 +299,7 @@ def state_dict_to_timm(sd: Dict[str, np.ndarray], num_layers: int) -> Dict[str, 
     return _f32(out)
 
 
-def dinov2_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, no_head: bool = False, gated_mlp: bool = False) -> Dict[str, np.ndarray]:
+def dinov2_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, no_head: bool = False, gated_mlp: bool = False, mlp_width: bool = False) -> Dict[str, np.ndarray]:
     """An HF Dinov2[WithRegisters]{ForImageClassification, Model} state dict (numpy arrays) under the file's names and order.  register_tokens ->
     `reg_token` [1][R][D] directly after cls_token; the classifier is the [C][2 D] head over concat(cls, mean of the patch tokens) (include/vitx.h
     "register tokens and the pooled head": the reference's loader cannot read such a file); LayerScale is folded (fold_layer_scale); mask_token is
@@ -304,7 +316,7 @@ def dinov2_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, no_head: bool = Fa
             if bad in k:
                 raise ValueError(f"tensor {k!r}: {what} is not supported")
     if not swiglu:
-        _require_mlp_4x(cfg, "mlp_ratio", 4)
+        _require_mlp_4x(cfg, "mlp_ratio", 4, mlp_width=mlp_width)
     pre = next((p for p in ("dinov2_with_registers.", "dinov2.", "") if p + "embeddings.cls_token" in sd), None)
     if pre is None:
         raise ValueError("not a DINOv2 state dict: embeddings.cls_token is missing")
@@ -331,7 +343,7 @@ def dinov2_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, no_head: bool = Fa
     return _f32(out)
 
 
-def clip_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, no_head: bool = False) -> Dict[str, np.ndarray]:
+def clip_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, no_head: bool = False, mlp_width: bool = False) -> Dict[str, np.ndarray]:
     """An HF CLIPVisionModelWithProjection / CLIPModel / CLIPVisionModel state dict (numpy arrays) under the file's names and order.
     class_embedding -> cls_token, position_embedding -> pos_embed, pre_layrnorm -> `pre_norm.*` directly after pos_embed, the bias-free patch
     convolution gets a zero bias, post_layernorm -> norm, and the bias-free visual_projection [E][D] becomes head.weight with a zero head.bias:
@@ -342,7 +354,7 @@ def clip_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, no_head: bool = Fals
         raise ValueError("not a CLIP vision state dict: embeddings.class_embedding is missing")
     e = pre + "embeddings."
     D = int(np.shape(sd[e + "class_embedding"])[-1])
-    _require_mlp_4x(cfg, "intermediate_size", 4 * D)
+    _require_mlp_4x(cfg, "intermediate_size", 4 * D, mlp_width=mlp_width)
     if e + "patch_embedding.bias" in sd:
         raise ValueError("patch_embedding.bias: not a CLIP vision tower (its patch convolution has no bias)")
     out = {"cls_token": np.reshape(sd[e + "class_embedding"], (1, 1, D)), "pos_embed": np.reshape(sd[e + "position_embedding.weight"], (1, -1, D))}
@@ -361,7 +373,7 @@ def clip_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, no_head: bool = Fals
     return _f32(out)
 
 
-def dinov3_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, gated_mlp: bool = False) -> Dict[str, np.ndarray]:
+def dinov3_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, gated_mlp: bool = False, mlp_width: bool = False) -> Dict[str, np.ndarray]:
     """An HF DINOv3ViTModel state dict (numpy arrays) under the file's names and order.  The position signal is rotary (include/vitx.h "rotary
     position embeddings"): `rope` = {1, rope_theta, 0, 0} in front, and a pos_embed [1][1 + g^2][D] of zeros at the config's image_size, so that the
     patch embedding and the resampler stay what they are.  register_tokens -> `reg_token`; LayerScale is folded; key_bias=False (the published
@@ -379,7 +391,7 @@ def dinov3_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, gated_mlp: bool = 
         raise ValueError(f"hidden_act {getattr(cfg, 'hidden_act', None)!r}: the gate of a gated MLP is silu (SwiGLU); other gate functions are not supported")
     D = int(cfg.hidden_size)
     if not gated:
-        _require_mlp_4x(cfg, "intermediate_size", 4 * D)
+        _require_mlp_4x(cfg, "intermediate_size", 4 * D, mlp_width=mlp_width)
     if "embeddings.cls_token" not in sd:
         raise ValueError("not a DINOv3 state dict: embeddings.cls_token is missing")
     pre = next((p for p in ("model.", "") if p + "layer.0.attention.q_proj.weight" in sd), None)
@@ -424,7 +436,7 @@ _POOL_ORDER = ("latent", "q.weight", "q.bias", "kv.weight", "kv.bias", "proj.wei
                "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")
 
 
-def siglip_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg) -> Dict[str, np.ndarray]:
+def siglip_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, mlp_width: bool = False) -> Dict[str, np.ndarray]:
     """An HF SiglipVisionModel / SiglipModel state dict (numpy arrays) under the file's names and order.  There is NO class token:
     position_embedding [g^2][D] -> pos_embed [1][g^2][D]; post_layernorm -> norm; the multi-head attention-pooling head becomes the thirteen
     `attn_pool.*` tensors after norm.bias (include/vitx.h "no class token and the attention-pooling head", timm's AttentionPoolLatent names):
@@ -438,7 +450,7 @@ def siglip_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg) -> Dict[str, np.nd
     if e + "patch_embedding.weight" not in sd or np.ndim(sd[e + "patch_embedding.weight"]) != 4:
         raise ValueError("Siglip2VisionModel (NaFlex) is not supported: its patch embedding is a Linear over flattened patches, not a convolution")
     D = int(cfg.hidden_size)
-    _require_mlp_4x(cfg, "intermediate_size", 4 * D, " (SO400M's 4304 is not supported)")
+    _require_mlp_4x(cfg, "intermediate_size", 4 * D, " (SO400M's 4304 is not supported)", mlp_width)
     if getattr(cfg, "vision_use_head", True) is False or h + "probe" not in sd:
         raise ValueError("vision_use_head = False: the tower has no attention-pooling head, and the file format has no slot for a SigLIP tower without it")
     out = {"pos_embed": np.reshape(sd[e + "position_embedding.weight"], (1, -1, D))}
@@ -470,21 +482,21 @@ def _text_prefix(sd) -> str:
     return pre
 
 
-def _text_front(sd, cfg, pre: str) -> Dict[str, np.ndarray]:
+def _text_front(sd, cfg, pre: str, mlp_width: bool = False) -> Dict[str, np.ndarray]:
     e = pre + "embeddings."
     D = int(cfg.hidden_size)
-    _require_mlp_4x(cfg, "intermediate_size", 4 * D)
+    _require_mlp_4x(cfg, "intermediate_size", 4 * D, mlp_width=mlp_width)
     out = {"token_embed.weight": sd[e + "token_embedding.weight"], "pos_embed": sd[e + "position_embedding.weight"]}
     map_blocks(out, sd, CLIP_BLOCKS, cfg.num_hidden_layers, pre)
     _put(out, "norm", sd, pre + "final_layer_norm")
     return out
 
 
-def clip_text_state_dict(sd: Dict[str, np.ndarray], cfg, no_head: bool = False) -> Dict[str, np.ndarray]:
+def clip_text_state_dict(sd: Dict[str, np.ndarray], cfg, no_head: bool = False, mlp_width: bool = False) -> Dict[str, np.ndarray]:
     """An HF CLIPTextModelWithProjection / CLIPModel state dict under a text file's names and order: token_embedding -> token_embed.weight [V][D],
     position_embedding -> pos_embed [T][D], the blocks through map_blocks, final_layer_norm -> norm, the bias-free text_projection [E][D] ->
     head.weight with a zero head.bias."""
-    out = _text_front(sd, cfg, _text_prefix(sd))
+    out = _text_front(sd, cfg, _text_prefix(sd), mlp_width)
     if "text_projection.weight" not in sd:
         raise ValueError("the model has no text_projection: a text file holds the projected tower (CLIPTextModelWithProjection or CLIPModel)")
     out["head.weight"] = sd["text_projection.weight"]
@@ -492,10 +504,10 @@ def clip_text_state_dict(sd: Dict[str, np.ndarray], cfg, no_head: bool = False) 
     return _f32(out)
 
 
-def siglip_text_state_dict(sd: Dict[str, np.ndarray], cfg, no_head: bool = False) -> Dict[str, np.ndarray]:
+def siglip_text_state_dict(sd: Dict[str, np.ndarray], cfg, no_head: bool = False, mlp_width: bool = False) -> Dict[str, np.ndarray]:
     """An HF SiglipTextModel / SiglipModel state dict under a text file's names and order; the tower's own `head` (a Linear with bias) is the projection."""
     pre = _text_prefix(sd)
-    out = _text_front(sd, cfg, pre)
+    out = _text_front(sd, cfg, pre, mlp_width)
     _put(out, "head", sd, pre + "head")
     return _f32(out)
 
@@ -505,18 +517,18 @@ def _config_labels(cfg, num_classes: int):
     return {int(k): str(v) for k, v in (getattr(cfg, "id2label", None) or {}).items()} or None
 
 
-# name: as the refusals call the family; mapper(sd, cfg, no_head) -> the file's tensors; prefix_rows: rows of pos_embed in front of the patch grid;
+# name: as the refusals call the family; mapper(sd, cfg, no_head, **opt-ins: gated_mlp, mlp_width) -> the file's tensors; prefix_rows: rows of pos_embed in front of the patch grid;
 # labels(cfg, num_classes) -> id2label of a model converted with its head; head: "always" -- no_head is refused --, "optional" -- no_head converts a
 # model without classifier / projection -- or "never" -- the family has no classifier, no_head is accepted and not required; loaders: the
 # transformers classes main() loads a checkpoint with, (with its head, with --no-head).
 Family = namedtuple("Family", "name mapper prefix_rows labels head loaders")
 
 
-_VIT = Family("ViT", lambda sd, cfg, no_head: state_dict_to_timm(sd, cfg.num_hidden_layers), 1, _config_labels, "always", ("ViTForImageClassification",) * 2)
+_VIT = Family("ViT", lambda sd, cfg, no_head, mlp_width=False: state_dict_to_timm(sd, cfg.num_hidden_layers), 1, _config_labels, "always", ("ViTForImageClassification",) * 2)
 _DINOV2 = Family("DINOv2", dinov2_state_dict_to_timm, 1, _config_labels, "optional", ("AutoModelForImageClassification", "AutoModel"))
 _CLIP = Family("CLIP", clip_state_dict_to_timm, 1, lambda cfg, E: {i: f"dim_{i}" for i in range(E)}, "optional", ("CLIPVisionModelWithProjection", "CLIPVisionModel"))
-_SIGLIP = Family("SigLIP", lambda sd, cfg, no_head: siglip_state_dict_to_timm(sd, cfg), 0, None, "never", ("SiglipVisionModel",) * 2)
-_DINOV3 = Family("DINOv3", lambda sd, cfg, no_head, gated_mlp=False: dinov3_state_dict_to_timm(sd, cfg, gated_mlp), 1, None, "never", ("DINOv3ViTModel",) * 2)
+_SIGLIP = Family("SigLIP", lambda sd, cfg, no_head, mlp_width=False: siglip_state_dict_to_timm(sd, cfg, mlp_width), 0, None, "never", ("SiglipVisionModel",) * 2)
+_DINOV3 = Family("DINOv3", lambda sd, cfg, no_head, gated_mlp=False, mlp_width=False: dinov3_state_dict_to_timm(sd, cfg, gated_mlp, mlp_width), 1, None, "never", ("DINOv3ViTModel",) * 2)
 # text towers (convert_hf_text_model): no patch grid (prefix_rows is not read), no labels -- the "classes" are the projection's columns --, always with the projection
 _CLIP_TEXT = Family("CLIP text", clip_text_state_dict, 0, lambda cfg, E: {}, "always", ("CLIPTextModelWithProjection",) * 2)
 _SIGLIP_TEXT = Family("SigLIP text", siglip_text_state_dict, 0, lambda cfg, E: {}, "always", ("SiglipTextModel",) * 2)
@@ -526,7 +538,7 @@ FAMILIES = {"vit": _VIT, "dinov2": _DINOV2, "dinov2_with_registers": _DINOV2, "c
             "dinov3_vit": _DINOV3, "clip_text_model": _CLIP_TEXT, "siglip_text_model": _SIGLIP_TEXT}
 
 
-def _family_tensors(model, cfg, fam, no_head: bool, head_dim_note: str = "", gated_mlp: bool = False):
+def _family_tensors(model, cfg, fam, no_head: bool, head_dim_note: str = "", gated_mlp: bool = False, mlp_width: bool = False):
     """The front both converters share: the head-dim refusal, the state dict as numpy arrays, the config's activation and epsilon, and the
     family's mapper.  Returns (the file's tensors in its order, activation, eps); each converter then states its header and calls write_model."""
     hd = cfg.hidden_size // cfg.num_attention_heads
@@ -535,7 +547,14 @@ def _family_tensors(model, cfg, fam, no_head: bool, head_dim_note: str = "", gat
     sd = {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
     if gated_mlp and fam not in (_DINOV2, _DINOV3):
         raise ValueError(f"gated_mlp=True: a {fam.name} model has no gated MLP this converter knows (DINOv2 use_swiglu_ffn, DINOv3 use_gated_mlp)")
-    tensors = fam.mapper(sd, cfg, no_head, gated_mlp=True) if gated_mlp else fam.mapper(sd, cfg, no_head)
+    # each opt-in is passed only when set: a mapper sees the call it always saw otherwise.  mlp_width: the mappers' refusal of a plain MLP that is not
+    # 4 x hidden stands down, and the file says its width in the `mlp` tensor
+    opt = dict(gated_mlp=True) if gated_mlp else {}
+    if mlp_width:
+        opt["mlp_width"] = True
+    tensors = fam.mapper(sd, cfg, no_head, **opt)
+    if mlp_width:
+        tensors = _with_mlp_width(tensors, int(cfg.hidden_size))
     # a gated DINOv3 model states its GATE function in hidden_act (silu, checked by the mapper): the file's activation slot is carried and not
     # applied in such a file (include/vitx.h "gated MLP") and says tanh-GELU, the slot's zero
     act = ACT_TANH if "glu" in tensors and fam is _DINOV3 else hf_activation(cfg)
@@ -543,7 +562,7 @@ def _family_tensors(model, cfg, fam, no_head: bool, head_dim_note: str = "", gat
 
 
 def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_head: bool = False, preprocessor_config: dict | None = None,
-                     gated_mlp: bool = False) -> HParams:
+                     gated_mlp: bool = False, mlp_width: bool = False) -> HParams:
     """model: a transformers model of one of FAMILIES, in eval mode (the module docstring lists the classes); no_head=True converts a model
     without classifier or projection, whose file gets the zero head labelled "(no head)" (a SigLIP tower always does).  The activation and the
     LayerNorm epsilon are the config's (with_arch); the class count and the image size are read off head.weight and pos_embed.
@@ -551,6 +570,9 @@ def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_
     None writes the file without one.  Writes `path`; returns the hparams written.
     gated_mlp=True opts in to the gated (SwiGLU) MLP of a Dinov2* model with use_swiglu_ffn or a DINOv3ViTModel with use_gated_mlp: the file carries
     the `glu` tensor, which neither the reference nor an engine build before it can read; without it such a model is refused by name.
+    mlp_width=True opts in to a plain MLP whose width is not 4 x hidden (SigLIP SO400M's 4304; any ViT, CLIP, SigLIP, non-gated DINOv2 / DINOv3 model):
+    the file carries the `mlp` tensor {F, 0, 0, 0} (include/vitx.h "MLP width"), which neither the reference nor an engine build before it can read;
+    without it such a model is refused as before.  A ViTSTR model takes none.
     vitstr=True: the model is a ViTSTR scene-text recogniser (the reference's extensions/vitstr.cpp/convert-pth-to-ggml.py: a ViT with ONE input
     channel whose classifier is applied to the first 25 tokens); the file then carries the character set as labels, and the one-channel patch
     kernel is what makes vit_model_load / vitx_model_load treat it as a ViTSTR model (vitstr.cpp:482)."""
@@ -573,8 +595,10 @@ def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_
         raise ValueError(f"a {fam.name} model is not a ViTSTR model")
     if no_head and fam.head == "always":
         raise ValueError("no_head converts a DINOv2 backbone (Dinov2Model, Dinov2WithRegistersModel), a CLIPVisionModel or a SigLIP tower")
+    if vitstr and mlp_width:
+        raise ValueError("mlp_width=True: a ViTSTR model takes no `mlp` width tensor")
     headless = fam.head == "never" or no_head
-    tensors, act, eps = _family_tensors(model, cfg, fam, no_head, " (64 runs the tuned attention kernels)", gated_mlp)
+    tensors, act, eps = _family_tensors(model, cfg, fam, no_head, " (64 runs the tuned attention kernels)", gated_mlp, mlp_width)
     g = grid_side(tensors["pos_embed"], fam.prefix_rows)          # the checkpoint's own grid (config.image_size states it too)
     hp = HParams(cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, int(tensors["head.weight"].shape[0]), cfg.patch_size, g * cfg.patch_size, ftype)
     id2label = NO_HEAD_LABELS if headless else fam.labels(cfg, hp.num_classes)
@@ -588,7 +612,7 @@ def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_
     return hp
 
 
-def convert_hf_text_model(model, path: str, ftype: int = 1) -> HParams:
+def convert_hf_text_model(model, path: str, ftype: int = 1, mlp_width: bool = False) -> HParams:
     """The text tower of a transformers CLIPTextModelWithProjection, CLIPModel, SiglipTextModel or SiglipModel as a text-tower file (include/vitx.h
     "the text tower"): header hidden D, layers L, heads H, num_classes = E (the projected width), patch_size = 0 (the mark of a text file),
     img_size = T (max_position_embeddings); tensors token_embed.weight, pos_embed, blocks.*, norm.*, head.*, and always
@@ -596,7 +620,8 @@ def convert_hf_text_model(model, path: str, ftype: int = 1) -> HParams:
     transformers does today: the FIRST position whose id equals config.eos_token_id.  Legacy CLIP configs (eos_token_id == 2) pool at
     argmax(ids) instead; for those the file names eos = vocab_size - 1, the id for which both rules agree on tokenised input (CLIP's tokenizer
     gives <|endoftext|> the highest id, and pads with it).  A two-tower model also writes `zs` = {kind, exp(logit_scale), logit_bias, 0}.
-    The token table is never block-quantised (ggml_file.write_model).  Writes `path`; returns the hparams written."""
+    The token table is never block-quantised (ggml_file.write_model).  mlp_width=True: an intermediate_size other than 4 x hidden is written with the
+    `mlp` tensor (convert_hf_model says what that means) instead of being refused.  Writes `path`; returns the hparams written."""
     cfg = model.config
     mt = getattr(cfg, "model_type", "")
     zs = None
@@ -614,7 +639,7 @@ def convert_hf_text_model(model, path: str, ftype: int = 1) -> HParams:
         raise ValueError(f"hidden_size {D} has no LayerNorm instantiation ({', '.join(str(w) for w in sorted(LN_WIDTHS))})")
     if not 1 <= T <= TEXT_MAX_TOKENS:
         raise ValueError(f"max_position_embeddings {T}: the text attention takes 1 .. {TEXT_MAX_TOKENS} tokens")
-    tensors, act, eps = _family_tensors(model, cfg, fam, False)
+    tensors, act, eps = _family_tensors(model, cfg, fam, False, mlp_width=mlp_width)
     V, E = int(tensors["token_embed.weight"].shape[0]), int(tensors["head.weight"].shape[0])
     if tuple(tensors["pos_embed"].shape) != (T, D):
         raise ValueError(f"position_embedding {tuple(tensors['pos_embed'].shape)}: expected [{T}][{D}]")
@@ -657,7 +682,8 @@ def _placed_after(t: dict, anchor: str, names) -> dict:
     return out
 
 
-def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2label=None, act: str = "tanh", eps: float = 1e-6, preproc: dict | None = None) -> HParams:
+def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2label=None, act: str = "tanh", eps: float = 1e-6, preproc: dict | None = None,
+                            mlp_width: bool = False) -> HParams:
     """sd: a timm VisionTransformer state_dict (name -> array / tensor), e.g. torch.load("vit_base_patch16_224.pth").  It already carries the names
     the file uses -- the reference's convert-pth-to-ggml.py:96-158 writes `timm_model.state_dict()` verbatim -- so no `timm` is needed: hidden
     size, depth, classes, patch and image size come from the tensor shapes (the reference reads them off the timm module), `norm_pre.*` is skipped
@@ -671,7 +697,8 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
     A state dict carries no config: `act` ("tanh", "erf", "quick") and `eps` state the model's activation and LayerNorm epsilon.  The default
     (tanh, 1e-6) writes the reference's file, without `arch`; timm's VisionTransformer was trained with nn.GELU and wants act="erf" (its eps is 1e-6).
     preproc: the keyword arguments of cli_preproc (resize, crop, filt, mean, std, crop_round) -- the checkpoint's preprocessing, written as the
-    `preproc` tensor; None or all unset: no tensor."""
+    `preproc` tensor; None or all unset: no tensor.  mlp_width=True: a checkpoint whose mlp.fc1 has other than 4 x hidden rows (so400m, so150m, any
+    mlp_ratio) gets the `mlp` tensor {F, 0, 0, 0} in front (include/vitx.h "MLP width"); without it the file is written as ever and does not load."""
     if act not in _ACT_NAMES:
         raise ValueError(f"act {act!r}: one of {sorted(_ACT_NAMES)}")
     if isinstance(sd, dict) and "model" in sd and not hasattr(sd["model"], "shape"):
@@ -736,6 +763,10 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
     expected = 3 + 12 * L + 4 + (len(_POOL_ORDER) if map_head else 1 + ("reg_token" in t))
     if len(t) != expected:
         raise ValueError(f"{len(t)} tensors after filtering, the file format holds exactly {expected} for {L} layers (vit.cpp:512-574)")
+    if mlp_width:
+        if cin == 1:
+            raise ValueError("mlp_width=True: a ViTSTR model takes no `mlp` width tensor")
+        t = _with_mlp_width(t, D)
     slots = cli_preproc(hp.img_size, **preproc) if preproc else None
     if cin == 1 and slots is not None:
         raise ValueError("a ViTSTR model's preprocessing is fixed: the --pp-* options do not apply")
@@ -985,6 +1016,8 @@ def main(argv=None) -> int:
                                                            "labelled '(no head)'; read the embeddings with --embed / vitx_feat_*")
     ap.add_argument("--gated-mlp", action="store_true", help="opt in to the gated (SwiGLU) MLP of DINOv2 ViT-g/14 (use_swiglu_ffn) / DINOv3 ViT-H+ (use_gated_mlp): the file "
                                                             "carries the `glu` tensor, which the reference and engine builds before it cannot read")
+    ap.add_argument("--mlp-width", action="store_true", help="opt in to a plain MLP whose width is not 4 x hidden (SigLIP SO400M's 4304, any mlp_ratio): the file carries the "
+                    "`mlp` tensor, which neither the reference nor an engine build before it can read; applies to --text-out too")
     ap.add_argument("--timm-state-dict", action="store_true", help="`model` is a torch-saved timm VisionTransformer state_dict (.pth); no timm import needed")
     ap.add_argument("--heads", type=int, default=0, help="attention heads of a timm checkpoint (inferred only for the widths of released timm ViTs; required otherwise)")
     ap.add_argument("--act", default="tanh", choices=sorted(_ACT_NAMES), help="MLP activation of a timm checkpoint (a state dict carries no config): tanh = ggml's GELU, the "
@@ -1030,7 +1063,7 @@ def main(argv=None) -> int:
         sd = torch.load(a.model, map_location="cpu", weights_only=True)
         labels = {int(k): str(v) for k, v in json.load(open(a.labels)).items()} if a.labels else None
         pp_cli = dict(resize=a.pp_resize, crop=a.pp_crop, filt=a.pp_filter, mean=a.pp_mean, std=a.pp_std, crop_round=a.pp_crop_round)
-        hp = convert_timm_state_dict(sd, a.out, a.ftype, heads=a.heads, id2label=labels, act=a.act, eps=a.eps, preproc=None if a.no_preproc else pp_cli)
+        hp = convert_timm_state_dict(sd, a.out, a.ftype, heads=a.heads, id2label=labels, act=a.act, eps=a.eps, preproc=None if a.no_preproc else pp_cli, mlp_width=a.mlp_width)
     else:
         import transformers
         model_type = transformers.AutoConfig.from_pretrained(a.model).model_type
@@ -1042,7 +1075,7 @@ def main(argv=None) -> int:
             if model_type not in _TWO_TOWERS + ("clip_text_model", "siglip_text_model"):
                 ap.error(f"--text-out needs a CLIP or SigLIP checkpoint, not model_type '{model_type}'")
             tcls = {"clip": "CLIPModel", "siglip": "SiglipModel"}.get(model_type) or FAMILIES[model_type].loaders[0]
-            thp = convert_hf_text_model(getattr(transformers, tcls).from_pretrained(a.model).eval(), a.text_out, a.ftype)
+            thp = convert_hf_text_model(getattr(transformers, tcls).from_pretrained(a.model).eval(), a.text_out, a.ftype, mlp_width=a.mlp_width)
             print(f"wrote {a.text_out}: text tower, hidden {thp.hidden_size}, layers {thp.num_hidden_layers}, heads {thp.num_attention_heads}, width {thp.num_classes}, tokens {thp.img_size}, ftype {a.ftype}")
             if model_type not in _TWO_TOWERS:
                 return 0                                   # a text tower alone: there is no vision file to write
@@ -1055,7 +1088,7 @@ def main(argv=None) -> int:
                     pc = json.load(f)
             else:
                 print(f"note: no preprocessor_config.json beside '{a.model}': the file is written without a `preproc` tensor")
-        hp = convert_hf_model(m, a.out, a.ftype, vitstr=a.vitstr, no_head=a.no_head, preprocessor_config=pc, gated_mlp=a.gated_mlp)
+        hp = convert_hf_model(m, a.out, a.ftype, vitstr=a.vitstr, no_head=a.no_head, preprocessor_config=pc, gated_mlp=a.gated_mlp, mlp_width=a.mlp_width)
     if a.img_size and a.img_size != hp.img_size:           # written at the checkpoint's size first, then replaced by its --img-size version
         from . import binding
         tmp = a.out + f".src{os.getpid()}"

@@ -14,7 +14,9 @@ bool attention_supports(int N, int D, int H) { return N > 0 && (D == H * 64 || a
 // t.attn_kernel (vitx_op_attention_ex, tests): ATTN_SINGLE / ATTN_FLOW / ATTN_PERSIST force one family.
 hipError_t launch_attention(const Tuning &t, int dtype, const void *qkv, void *out, int n_img, int N, int D, int H, hipStream_t stream) {
     if (!attention_supports(N, D, H) || n_img <= 0) return hipErrorInvalidValue;
-    if (D != H * 64) return launch_attention_generic(dtype, qkv, out, n_img, N, D, H, stream);
+    // head dims 72 .. 128: the generic kernel's arithmetic and bits with K and V staged in LDS per workgroup (attention_wide.hip; profiles/wide_attn_cost.txt);
+    // the generic kernel for head dims 8 .. 56 (and an image beyond a buffer descriptor's 32-bit range)
+    if (D != H * 64) return (attention_wide_supports(N, D, H) ? launch_attention_wide : launch_attention_generic)(dtype, qkv, out, n_img, N, D, H, stream);
     // 193..224 tokens: the persistent single-pass kernel (K/V of the next item by LDS-DMA under the current item's softmax)
     if ((t.attn_kernel == ATTN_PERSIST || t.attn_kernel == ATTN_AUTO) && N > 192 && N <= 224) {
         // 32-bit buffer offsets bound one launch (~4.4 k ViT-B images): a larger sub-batch is cut into several launches of the SAME kernel rather than
@@ -37,7 +39,7 @@ hipError_t launch_attention(const Tuning &t, int dtype, const void *qkv, void *o
     return launch_attention_single(dtype, qkv, out, n_img, N, D, H, stream);
 }
 
-// Device bring-up of the families whose kernels ask for more than 64 KiB of LDS (the generic and the class-token kernel do not)
+// Device bring-up of the families whose kernels ask for more than 64 KiB of LDS (the generic, the wide and the class-token kernel do not)
 hipError_t prepare_attention() {
     hipError_t e = prepare_attention_flow();
     if (e == hipSuccess) e = prepare_attention_stream();

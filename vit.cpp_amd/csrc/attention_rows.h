@@ -16,9 +16,11 @@ namespace vitx {
 
 // The pieces of that arithmetic, shared by the tile that reads K and V from global memory (attention_rows16) and the one that reads them from chunks
 // staged in LDS (attention_packed_staged_kernel, attention_packed_staged.hip, calls the pieces directly): the same operations in the same order, so the same bits.
-template <typename T, int NK2>
+// VROWB / NDV: the V image's row bytes and how many of the ND tiles pv_step runs -- the padded head dim's unless the V image holds unpadded rows
+// (attention_wide.hip: head_dim * 2 bytes, ceil(head_dim / 16) tiles; an output tile is a product of its own, so the stored bits do not depend on either)
+template <typename T, int NK2, int VROWB = NK2 * 64, int NDV = NK2 * 2>
 struct Rows16 {
-    static constexpr int DHP = NK2 * 32, ND = DHP / 16, ROWB = DHP * 2;       // padded head dim, 16-dim output tiles, LDS row bytes
+    static constexpr int DHP = NK2 * 32, ND = DHP / 16, ROWB = VROWB;         // padded head dim, 16-dim output tiles, LDS row bytes
     typedef typename Elem<T>::v8 v8;
     typedef typename Pair<T>::v2 v2;
     typedef short s4 __attribute__((ext_vector_type(4)));
@@ -60,7 +62,7 @@ struct Rows16 {
     // O^T += V^T . P^T for the 32 keys whose row-major image starts at LDS address vimg (va = vimg + tr_off())
     static __device__ __forceinline__ void pv_step(unsigned va0, const v8 &pk, f32x4 (&o)[ND]) {
 #pragma unroll
-        for (int dt = 0; dt < ND; ++dt) {
+        for (int dt = 0; dt < NDV; ++dt) {
             s4 f0, f1;
             const unsigned va = va0 + dt * 32;
             asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(f0) : "v"(va) : "memory");

@@ -44,6 +44,8 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
     if (m->rope_kind && dtype == VITX_MXFP8) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts do not take models with rotary position embeddings"); return VITX_ERR_UNSUPPORTED; }
     if (m->rope_kind && m->in_chans == 1) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes no rotary position embeddings"); return VITX_ERR_UNSUPPORTED; }
     if (m->glu_kind && dtype == VITX_MXFP8) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts do not take models with a gated MLP"); return VITX_ERR_UNSUPPORTED; }
+    if (m->mlp_width && dtype == VITX_MXFP8) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts do not take models with an `mlp` width tensor"); return VITX_ERR_UNSUPPORTED; }
+    if (m->mlp_width && m->in_chans == 1) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes no `mlp` width tensor"); return VITX_ERR_UNSUPPORTED; }
     if (m->glu_kind && m->in_chans == 1) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes no gated MLP"); return VITX_ERR_UNSUPPORTED; }
     if (m->in_chans == 1 && (m->has_pre_norm || m->activation != VITX_ACT_GELU_TANH)) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes neither a pre-norm nor an activation other than tanh-GELU"); return VITX_ERR_UNSUPPORTED; }
     if (dtype == VITX_MXFP8 && m->activation != VITX_ACT_GELU_TANH) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts evaluate tanh-GELU only (this model's activation: %d)", m->activation); return VITX_ERR_UNSUPPORTED; }

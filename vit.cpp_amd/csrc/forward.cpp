@@ -162,8 +162,8 @@ struct SliceForward {
         }
         if ((rc = gemm(c, st, PC_GEMM_TAIL, EPI_BIAS_F32, dense_gemm(sl.U, ws.map_proj_w, ws.map_proj_b, sl.Xc, Mc, n, D, round_up(D, tn), D)))) return rc;
         if ((rc = layernorm(sl.Xc, D, ws.map_ln_w, ws.map_ln_b, sl.U2, n))) return rc;
-        if ((rc = gemm(c, st, PC_GEMM_TAIL, c->fc1_epi, dense_gemm(sl.U2, ws.map_fc1_w, ws.map_fc1_b, sl.Hbuf, Mc, n, 4 * D, round_up(4 * D, tn), D)))) return rc;
-        if ((rc = gemm(c, st, PC_GEMM_TAIL, EPI_BIAS_RESID, dense_gemm(sl.Hbuf, ws.map_fc2_w, ws.map_fc2_b, sl.Xc, Mc, n, D, round_up(D, tn), 4 * D)))) return rc;
+        if ((rc = gemm(c, st, PC_GEMM_TAIL, c->fc1_epi, dense_gemm(sl.U2, ws.map_fc1_w, ws.map_fc1_b, sl.Hbuf, Mc, n, c->F, round_up(c->F, tn), D)))) return rc;
+        if ((rc = gemm(c, st, PC_GEMM_TAIL, EPI_BIAS_RESID, dense_gemm(sl.Hbuf, ws.map_fc2_w, ws.map_fc2_b, sl.Xc, Mc, n, D, round_up(D, tn), c->F)))) return rc;
         float *o_cls = nullptr, *o_mean, *o_tok;
         const Features *ft = c->feat.get();
         const bool sel = ft && ft->selects(c->L - 1);

@@ -418,6 +418,7 @@ hipError_t launch_gemm_w4(int dtype, int epi, const GemmArgs &a, int n_cu, hipSt
 bool gemm_w4_supports(const GemmArgs &a);
 bool attention_persist_supports(int n_img, int N, int D);      // attention_persist.hip: 193..224 tokens, the whole QKV tensor below 0xf0000000 bytes
 bool attention_generic_supports(int D, int H);                 // attention_generic.hip: head_dim any multiple of 8 up to 128
+bool attention_wide_supports(int N, int D, int H);             // attention_wide.hip: head_dim 72, 80, .., 128, an image's qkv rows below 0xf0000000 bytes
 
 // FN<_Float16>(args) for DT_F16, FN<__bf16>(args) for any other dtype: how a launcher that takes `int dtype` enters its per-type template.
 // VITX_BY_DTYPE2: FN has one more template argument X after the type.
@@ -431,6 +432,7 @@ hipError_t launch_attention_single(int dtype, const void *qkv, void *out, int n_
 hipError_t launch_attention_flow(int dtype, const void *qkv, void *out, int n_img, int N, int D, int H, hipStream_t stream, int flags = 0);      // attention_flow.hip: any N
 hipError_t launch_attention_persist(int dtype, const void *qkv, void *out, int n_img, int N, int D, int H, int n_cu, hipStream_t stream, int flags = 0);      // attention_persist.hip
 hipError_t launch_attention_generic(int dtype, const void *qkv, void *out, int n_img, int N, int D, int H, hipStream_t stream);      // attention_generic.hip
+hipError_t launch_attention_wide(int dtype, const void *qkv, void *out, int n_img, int N, int D, int H, hipStream_t stream);      // attention_wide.hip: the generic kernel's contract and bits, K and V staged in LDS
 // Device bring-up: every kernel instantiation that needs more than 64 KiB of LDS gets its dynamic-LDS attribute on the current device, by the
 // file that holds the instantiation table.  tuning_for_device runs these once per device.
 hipError_t prepare_gemm(const Tuning &t);              // gemm.hip: ring, ping-pong and q4_0 GEMMs (laboratory build: gemm_w4 too)

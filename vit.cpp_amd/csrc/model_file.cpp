@@ -182,7 +182,7 @@ static int load_impl(const char *path, vitx_model &m) {
         m.id2label[key] = v;
     }
     auto expect = expected_tensors(hp);                              // (`glu` rewrites the MLP shapes of every block: it stands in front of them)
-    const auto pool_expect = text ? std::map<std::string, Expect>() : pool_tensors(hp);
+    auto pool_expect = text ? std::map<std::string, Expect>() : pool_tensors(hp);       // (`mlp` rewrites the MLP shapes of both maps)
     int n_optional = 0;                                              // `arch`, `preproc`, `pre_norm.*` records seen
     int n_pool = 0;                                                  // `attn_pool.*` records seen
     bool pos_no_cls = false;                                         // pos_embed has g^2 rows (no class row)
@@ -277,6 +277,7 @@ static int load_impl(const char *path, vitx_model &m) {
                 set_error("vitx_model_load: tensor 'glu' must be f32 [4] = {kind, F, 0, 0}: got type %d, %d dims [%lld, ..]", ttype, n_dims, (long long)t.ne[0]);
                 return VITX_ERR_FORMAT;
             }
+            if (m.mlp_width) { set_error("vitx_model_load: tensor 'glu' together with 'mlp': a file has one of them"); return VITX_ERR_FORMAT; }
             if (seen_block) { set_error("vitx_model_load: tensor 'glu' stands behind a blocks.* record: it sets their shapes and must come in front of the first one"); return VITX_ERR_FORMAT; }
             t.raw.resize(16);
             if (fread(t.raw.data(), 1, 16, f) != 16) { set_error("vitx_model_load: tensor '%s' is truncated", t.name.c_str()); return VITX_ERR_IO; }
@@ -293,6 +294,38 @@ static int load_impl(const char *path, vitx_model &m) {
                 const std::string p = "blocks." + std::to_string(i) + ".mlp.";
                 expect[p + "fc1.weight"] = {{D, 2 * F, 1, 1}, 1}; expect[p + "fc1.bias"] = {{2 * F, 1, 1, 1}, 0};
                 expect[p + "fc2.weight"] = {{F, D, 1, 1}, 1};
+            }
+            m.index[t.name] = (int)m.tensors.size();
+            m.tensors.push_back(std::move(t));
+            ++n_optional;
+            continue;
+        }
+        if (t.name == "mlp") {                                       // optional: f32 [4] = {F, 0, 0, 0} (include/vitx.h "MLP width"), image and text files
+            if (m.index.count(t.name)) { set_error("vitx_model_load: duplicate tensor '%s'", t.name.c_str()); return VITX_ERR_FORMAT; }
+            if (ttype != T_F32 || n_dims != 1 || t.ne[0] != 4) {
+                set_error("vitx_model_load: tensor 'mlp' must be f32 [4] = {F, 0, 0, 0}: got type %d, %d dims [%lld, ..]", ttype, n_dims, (long long)t.ne[0]);
+                return VITX_ERR_FORMAT;
+            }
+            if (m.glu_kind) { set_error("vitx_model_load: tensor 'mlp' together with 'glu': a file has one of them"); return VITX_ERR_FORMAT; }
+            if (seen_block) { set_error("vitx_model_load: tensor 'mlp' stands behind a blocks.* record: it sets their shapes and must come in front of the first one"); return VITX_ERR_FORMAT; }
+            t.raw.resize(16);
+            if (fread(t.raw.data(), 1, 16, f) != 16) { set_error("vitx_model_load: tensor '%s' is truncated", t.name.c_str()); return VITX_ERR_IO; }
+            float a[4]; memcpy(a, t.raw.data(), 16);
+            if (!(a[0] >= 8.0f) || a[0] > 16777216.0f || a[0] != floorf(a[0]) || (int64_t)a[0] % 8) {
+                set_error("vitx_model_load: tensor 'mlp' carries the hidden width %g: it must be a whole number, at least 8 and a multiple of 8", (double)a[0]);
+                return VITX_ERR_FORMAT;
+            }
+            if (a[1] != 0.0f || a[2] != 0.0f || a[3] != 0.0f) { set_error("vitx_model_load: tensor 'mlp' has reserved slots {%g, %g, %g}: they must be 0", (double)a[1], (double)a[2], (double)a[3]); return VITX_ERR_FORMAT; }
+            m.mlp_width = (int)a[0];
+            const int64_t D = hp.hidden_size, F = m.mlp_width;
+            for (int i = 0; i < hp.num_hidden_layers; ++i) {
+                const std::string p = "blocks." + std::to_string(i) + ".mlp.";
+                expect[p + "fc1.weight"] = {{D, F, 1, 1}, 1}; expect[p + "fc1.bias"] = {{F, 1, 1, 1}, 0};
+                expect[p + "fc2.weight"] = {{F, D, 1, 1}, 1};
+            }
+            if (!text) {                                             // the attention-pooling head's MLP has the same width
+                pool_expect["attn_pool.mlp.fc1.weight"] = {{D, F, 1, 1}, 3}; pool_expect["attn_pool.mlp.fc1.bias"] = {{F, 1, 1, 1}, 0};
+                pool_expect["attn_pool.mlp.fc2.weight"] = {{F, D, 1, 1}, 3};
             }
             m.index[t.name] = (int)m.tensors.size();
             m.tensors.push_back(std::move(t));
@@ -483,6 +516,7 @@ int vitx_model_rope(const vitx_model *m, int *kind, float *theta) {
     if (theta) *theta = m->rope_theta;
     return 1;
 }
+int vitx_model_mlp_width(const vitx_model *m) { return !m ? 0 : m->glu_kind ? m->glu_width : m->mlp_file_rows(); }      // the file's F (4 D without `mlp` or `glu`)
 int vitx_model_glu(const vitx_model *m, int *kind, int *width) {
     if (!m || !m->glu_kind) return 0;
     if (kind) *kind = m->glu_kind;

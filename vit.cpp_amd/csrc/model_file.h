@@ -40,8 +40,11 @@ struct vitx_model {
     float rope_theta = 0.0f;
     int glu_kind = VITX_GLU_NONE;                     // `glu` [4] = {kind, F, 0, 0}: a gated MLP (include/vitx.h "gated MLP"); fc1 is then [2 F][D], fc2 [D][F]
     int glu_width = 0;                                // F, the MLP hidden width of such a file (fc2's K); 0 without `glu`: the width is 4 D
-    int mlp_hidden() const { return glu_kind ? glu_width : 4 * hp.hidden_size; }          // F: fc2's K
-    int mlp_fc1_rows() const { return glu_kind ? 2 * glu_width : 4 * hp.hidden_size; }    // F1: fc1's N
+    int mlp_width = 0;                                // `mlp` [4] = {F, 0, 0, 0}: a plain MLP of the file's own width (include/vitx.h "MLP width"); 0 without it
+    // What a context runs: F = fc2's K, F1 = fc1's N.  A file with `mlp` runs Fp = round_up(F, 64), the GEMMs' K step: the upload zero-fills the pad
+    int mlp_hidden() const { return glu_kind ? glu_width : mlp_width ? (mlp_width + 63) / 64 * 64 : 4 * hp.hidden_size; }
+    int mlp_fc1_rows() const { return glu_kind ? 2 * glu_width : mlp_hidden(); }
+    int mlp_file_rows() const { return glu_kind ? 2 * glu_width : mlp_width ? mlp_width : 4 * hp.hidden_size; }     // fc1's rows as filed (fc2's columns without `glu`)
     bool has_preproc = false;                         // `preproc` [16]: the model's own preprocessing (include/vitx.h); without it `preproc` is the reference default
     vitx_preproc preproc;
     // a text-tower file (patch_size == 0; include/vitx.h "the text tower"): hp.img_size = T, hp.num_classes = E

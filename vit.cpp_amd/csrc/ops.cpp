@@ -819,6 +819,12 @@ int vitx_op_attention_generic(int dtype, const void *d_qkv, void *d_out, int n_i
     if (!attention_generic_supports(D, H)) { set_error("vitx_op_attention_generic: head_dim must be a multiple of 8 up to 128 (D %d, H %d)", D, H); return VITX_ERR_UNSUPPORTED; }
     return op_rc("vitx_op_attention_generic", launch_attention_generic(dtype, d_qkv, d_out, n_img, N, D, H, (hipStream_t)stream));
 }
+// The staged kernel of head dims 72 .. 128 (attention_wide.hip) on its own, beside the generic one it must match bit for bit.  Null stream, only enqueues.
+int vitx_op_attention_wide(int dtype, const void *d_qkv, void *d_out, int n_img, int N, int D, int H) {
+    if (!d_qkv || !d_out || n_img <= 0 || N <= 0 || D <= 0 || H <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_attention_wide: invalid argument"); return VITX_ERR_ARG; }
+    if (!attention_wide_supports(N, D, H)) { set_error("vitx_op_attention_wide: head_dim must be a multiple of 8 in 72 .. 128 (D %d, H %d) and an image's qkv rows below 0xf0000000 bytes", D, H); return VITX_ERR_UNSUPPORTED; }
+    return op_rc("vitx_op_attention_wide", launch_attention_wide(dtype, d_qkv, d_out, n_img, N, D, H, nullptr));
+}
 int vitx_op_attention_text(int dtype, const void *d_qkv, void *d_out, int n, int T, int D, int H, int causal, void *stream) {
     if (!d_qkv || !d_out || n <= 0 || T <= 0 || D <= 0 || H <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_attention_text: invalid argument"); return VITX_ERR_ARG; }
     if (!attention_text_supports(T, D, H)) { set_error("vitx_op_attention_text: 1 <= T <= %d and a head dim that is a multiple of 8 up to 128 (T %d, D %d, H %d)", VITX_TEXT_MAX_TOKENS, T, D, H); return VITX_ERR_UNSUPPORTED; }

@@ -214,7 +214,7 @@ int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_im
         if ((rc = dmalloc(&p->Uv, Bp * D * 2))) return rc;
         if ((rc = dmalloc((void **)&p->Xc, Bp * D * 4))) return rc;
         if ((rc = dmalloc(&p->U2, Bp * D * 2))) return rc;
-        if ((rc = dmalloc(&p->Hm, Bp * 4 * D * 2))) return rc;
+        if ((rc = dmalloc(&p->Hm, Bp * (size_t)p->F * 2))) return rc;
     }
     if (p->rope) {       // a call's grids hold at most max_tokens patches; twice that, so that grids of earlier calls stay cached
         p->rope_cap = 2L * max_tokens * (D / H / 2);

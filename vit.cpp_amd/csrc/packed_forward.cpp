@@ -228,8 +228,8 @@ int pack_pooled_tail(vitx_pack *p, const PackLayout &at, int n, int Mh, hipStrea
     }
     if ((rc = pack_gemm(p, EPI_BIAS_F32, dense_gemm(p->Uv, ws.map_proj_w, ws.map_proj_b, p->Xc, Mh, n, D, round_up(D, tn), D), st))) return rc;
     HIP_TRY(launch_layernorm(dt, p->Xc, D, ws.map_ln_w, ws.map_ln_b, p->U2, D, n, D, p->eps, st)); ++p->launches;
-    if ((rc = pack_gemm(p, p->fc1_epi, dense_gemm(p->U2, ws.map_fc1_w, ws.map_fc1_b, p->Hm, Mh, n, 4 * D, round_up(4 * D, tn), D), st))) return rc;
-    if ((rc = pack_gemm(p, EPI_BIAS_RESID, dense_gemm(p->Hm, ws.map_fc2_w, ws.map_fc2_b, p->Xc, Mh, n, D, round_up(D, tn), 4 * D), st))) return rc;
+    if ((rc = pack_gemm(p, p->fc1_epi, dense_gemm(p->U2, ws.map_fc1_w, ws.map_fc1_b, p->Hm, Mh, n, p->F, round_up(p->F, tn), D), st))) return rc;
+    if ((rc = pack_gemm(p, EPI_BIAS_RESID, dense_gemm(p->Hm, ws.map_fc2_w, ws.map_fc2_b, p->Xc, Mh, n, D, round_up(D, tn), p->F), st))) return rc;
     const bool cls = (p->feat_flags & VITX_FEAT_CLS) != 0;
     HIP_TRY(launch_pool_embed(p->Xc, p->Z, dt, cls ? p->feat_cls.as<float>() : nullptr, D, (p->feat_flags & VITX_FEAT_L2) != 0, n, D, st)); ++p->launches;
     return VITX_OK;

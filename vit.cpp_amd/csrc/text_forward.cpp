@@ -4,6 +4,7 @@
 // One stream, no sub-batch split, no hipGraph cache, no LayerNorm fusion.  Quantised block matrices are expanded once at upload
 // (quant_on_device = false): the just-in-time expansion of the image forward exists for ITS memory budget -- hundreds of images of
 // activations beside the weights -- and a text tower's batch of short prompts has no such pressure.
+#include <algorithm>
 #include <string.h>
 
 #include <new>
@@ -33,7 +34,7 @@ int stage_ids(vitx_text *t, const int32_t *ids, int n) {
 
 int text_forward(vitx_text *t, int n, int flags, float *d_out, hipStream_t st) {
     const WeightSet &ws = *t->wset;
-    const int T = t->T, D = t->D, H = t->H, tn = t->tn, tm = t->tm, dtype = t->dtype;
+    const int T = t->T, D = t->D, H = t->H, tn = t->tn, tm = t->tm, dtype = t->dtype, F = t->model->mlp_hidden();
     const int rows = n * T, M = round_up(rows, tm), Mh = round_up(n, tm);
     int rc;
     // pooled positions and ids: ONE upload of the staging buffer's front (the ids sit at their fixed place behind max_prompts positions)
@@ -47,8 +48,8 @@ int text_forward(vitx_text *t, int n, int flags, float *d_out, hipStream_t st) {
         HIP_TRY(launch_attention_text(dtype, t->QKV, t->U, n, T, D, H, t->causal, st));
         if ((rc = text_gemm(t, t->tune_proj, EPI_BIAS_RESID, dense_gemm(t->U, w.proj_w, w.proj_b, t->X, M, rows, D, round_up(D, tn), D), st))) return rc;
         HIP_TRY(launch_layernorm(dtype, t->X, D, w.ln2_w, w.ln2_b, t->U, D, rows, D, t->eps, st));
-        if ((rc = text_gemm(t, t->tune_fc1, t->fc1_epi, dense_gemm(t->U, w.fc1_w, w.fc1_b, t->Hbuf, M, rows, 4 * D, round_up(4 * D, tn), D), st))) return rc;
-        if ((rc = text_gemm(t, t->tune_fc2, EPI_BIAS_RESID, dense_gemm(t->Hbuf, w.fc2_w, w.fc2_b, t->X, M, rows, D, round_up(D, tn), 4 * D), st))) return rc;
+        if ((rc = text_gemm(t, t->tune_fc1, t->fc1_epi, dense_gemm(t->U, w.fc1_w, w.fc1_b, t->Hbuf, M, rows, F, round_up(F, tn), D), st))) return rc;
+        if ((rc = text_gemm(t, t->tune_fc2, EPI_BIAS_RESID, dense_gemm(t->Hbuf, w.fc2_w, w.fc2_b, t->X, M, rows, D, round_up(D, tn), F), st))) return rc;
     }
     HIP_TRY(launch_text_pool(dtype, t->X, t->pooled, ws.norm_w, ws.norm_b, t->Z, n, Mh, T, D, t->eps, st));
     // VITX_TEXT_L2: the head writes the scratch rows and zs_embed_kernel's f32 instantiation (zeroshot.hip: THE sum-of-squares rule) writes the output
@@ -76,13 +77,13 @@ int vitx_text_create(const vitx_model *m, int device, int max_prompts, int dtype
     if (dtype == VITX_MXFP8) { set_error("vitx_text_create: VITX_MXFP8 is not supported by text contexts (VITX_F16 or VITX_BF16)"); return VITX_ERR_UNSUPPORTED; }
     if (dtype != VITX_F16 && dtype != VITX_BF16) { set_error("vitx_text_create: unknown dtype %d", dtype); return VITX_ERR_ARG; }
     const vitx_hparams &hp = m->hp;
-    const int D = hp.hidden_size, H = hp.num_attention_heads, T = hp.img_size, E = hp.num_classes;
+    const int D = hp.hidden_size, H = hp.num_attention_heads, T = hp.img_size, E = hp.num_classes, F = m->mlp_hidden();       // F: 4 D, or the padded width of a file with `mlp`
     // every shape check before the first device call: nothing is launched after a refusal
     if (T > VITX_TEXT_MAX_TOKENS) { set_error("vitx_text_create: context length %d exceeds the %d tokens the text attention takes", T, VITX_TEXT_MAX_TOKENS); return VITX_ERR_UNSUPPORTED; }
     if (!attention_text_supports(T, D, H)) { set_error("vitx_text_create: attention needs a head_dim that is a multiple of 8 up to 128 (this model: %d / %d)", D, H); return VITX_ERR_UNSUPPORTED; }
     if (!layernorm_supports(D)) { set_error("vitx_text_create: hidden_size %d has no LayerNorm instantiation", D); return VITX_ERR_UNSUPPORTED; }
     if (E % 64) { set_error("vitx_text_create: embedding width %d is not a multiple of 64", E); return VITX_ERR_UNSUPPORTED; }
-    if ((long)max_prompts * T > (long)(0xf0000000u / ((size_t)4 * D * 2)) / 256 * 256) { set_error("vitx_text_create: max_prompts %d x %d tokens exceed the kernels' 32-bit buffer window", max_prompts, T); return VITX_ERR_UNSUPPORTED; }
+    if ((long)max_prompts * T > (long)(0xf0000000u / ((size_t)std::max(F, 4 * D) * 2)) / 256 * 256) { set_error("vitx_text_create: max_prompts %d x %d tokens exceed the kernels' 32-bit buffer window", max_prompts, T); return VITX_ERR_UNSUPPORTED; }
     const Tuning *tune = nullptr;
     int rc;
     if ((rc = open_device("vitx_text_create", device, &tune))) return rc;
@@ -94,7 +95,7 @@ int vitx_text_create(const vitx_model *m, int device, int max_prompts, int dtype
     t->V = m->vocab; t->T = T; t->E = E; t->E_pad = head_cols_pad(m); t->causal = m->causal; t->eos = m->eos; t->max_prompts = max_prompts;
     t->fc1_epi = act_epi(m->activation); t->eps = hp.eps;
     const int Mcap = round_up(max_prompts * T, t->tm), Bcap = round_up(max_prompts, t->tm), tn = t->tn;
-    struct { Tuning *tune; int M, N, K; } pins[] = {{&t->tune_qkv, Mcap, 3 * D, D}, {&t->tune_proj, Mcap, D, D}, {&t->tune_fc1, Mcap, 4 * D, D}, {&t->tune_fc2, Mcap, D, 4 * D}, {&t->tune_head, Bcap, E, D}};
+    struct { Tuning *tune; int M, N, K; } pins[] = {{&t->tune_qkv, Mcap, 3 * D, D}, {&t->tune_proj, Mcap, D, D}, {&t->tune_fc1, Mcap, F, D}, {&t->tune_fc2, Mcap, D, F}, {&t->tune_head, Bcap, E, D}};
     for (auto &p : pins) {
         *p.tune = *tune;
         // the dispatcher's own rule between its two ring tilings (gemm_ring_cfg, gemm.hip), at the rows of a full batch: never the wide persistent
@@ -117,7 +118,7 @@ int vitx_text_create(const vitx_model *m, int device, int max_prompts, int dtype
     if ((rc = dmalloc((void **)&t->X, Mp * D * 4))) return rc;
     if ((rc = dmalloc(&t->U, Mp * D * 2))) return rc;
     if ((rc = dmalloc(&t->QKV, Mp * 3 * D * 2))) return rc;
-    if ((rc = dmalloc(&t->Hbuf, Mp * 4 * D * 2))) return rc;
+    if ((rc = dmalloc(&t->Hbuf, Mp * (size_t)F * 2))) return rc;
     if ((rc = dmalloc(&t->Z, Bp * D * 2))) return rc;
     if ((rc = dmalloc((void **)&t->out, Bp * (size_t)E * 4))) return rc;
     if ((rc = dmalloc((void **)&t->raw, Bp * (size_t)E * 4))) return rc;

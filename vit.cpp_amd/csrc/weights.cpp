@@ -2,6 +2,7 @@
 // that ask for the same WeightSpec.  Every quantity an upload reads is derived here from the model and the spec: no context type is seen.
 #include <string.h>
 
+#include <algorithm>
 #include <iterator>
 #include <map>
 #include <mutex>
@@ -88,11 +89,14 @@ int upload_quant(const Upload &u, const HostTensor *t, int Nrows, int K, int n_p
 }
 
 // A 2-D "*weight" tensor: block types stay quantised on the device (q), everything else is uploaded expanded (dense).
-int upload_weight(const Upload &u, const HostTensor *t, int Nrows, int K, int n_pad, void **dense, QuantW *q) {
+// k_pad > K: the source has fewer columns than the destination (fc2 of a file with `mlp`, include/vitx.h "MLP width"): zeros behind column K.  A block
+// type never meets it: the loader wants ne[0] % 64 == 0 of a quantised tensor, and then k_pad == K.
+int upload_weight(const Upload &u, const HostTensor *t, int Nrows, int K, int n_pad, void **dense, QuantW *q, int k_pad = 0) {
     *dense = nullptr;
-    if (u.quant_on_device) { int rc = upload_quant(u, t, Nrows, K, n_pad, q); if (rc) return rc; }
+    if (k_pad <= K) k_pad = K;
+    if (u.quant_on_device && k_pad == K) { int rc = upload_quant(u, t, Nrows, K, n_pad, q); if (rc) return rc; }
     if (q->blocks) return VITX_OK;
-    return upload_matrix(u, t, Nrows, K, n_pad, K, dense);
+    return upload_matrix(u, t, Nrows, K, n_pad, k_pad, dense);
 }
 
 // [N][K] matrix -> MX operand (VITX_MXFP8): the f32 decode of any file type, encoded once on the host; rows N..n_pad are zero blocks
@@ -110,7 +114,7 @@ int upload_mx(const Upload &u, const HostTensor *t, int Nrows, int K, int n_pad,
 // or f16 in the file, never blocks.
 int upload_map_head(const Upload &u) {
     WeightSet &ws = u.ws;
-    const int D = u.D, tn = u.tn;
+    const int D = u.D, tn = u.tn, Ff = u.m->mlp_file_rows(), F = u.m->mlp_hidden();       // the MLP as filed; as run (F > Ff: zero rows / columns, "MLP width")
     int rc;
     std::vector<float> pu((size_t)u.m->hp.num_attention_heads * D);
     if ((rc = vitx_model_pool_query(u.m, pu.data()))) return rc;
@@ -127,17 +131,19 @@ int upload_map_head(const Upload &u) {
     if ((rc = upload_f32(u, u.T("attn_pool.proj.bias"), &ws.map_proj_b, round_up(D, tn)))) return rc;
     if ((rc = upload_f32(u, u.T("attn_pool.norm.weight"), &ws.map_ln_w))) return rc;
     if ((rc = upload_f32(u, u.T("attn_pool.norm.bias"), &ws.map_ln_b))) return rc;
-    if ((rc = upload_f32(u, u.T("attn_pool.mlp.fc1.bias"), &ws.map_fc1_b, round_up(4 * D, tn)))) return rc;
+    if ((rc = upload_f32(u, u.T("attn_pool.mlp.fc1.bias"), &ws.map_fc1_b, round_up(F, tn)))) return rc;
     if ((rc = upload_f32(u, u.T("attn_pool.mlp.fc2.bias"), &ws.map_fc2_b, round_up(D, tn)))) return rc;
     if ((rc = upload_matrix(u, u.T("attn_pool.proj.weight"), D, D, round_up(D, tn), D, &ws.map_proj_w))) return rc;
-    if ((rc = upload_matrix(u, u.T("attn_pool.mlp.fc1.weight"), 4 * D, D, round_up(4 * D, tn), D, &ws.map_fc1_w))) return rc;
-    if ((rc = upload_matrix(u, u.T("attn_pool.mlp.fc2.weight"), D, 4 * D, round_up(D, tn), 4 * D, &ws.map_fc2_w))) return rc;
+    if ((rc = upload_matrix(u, u.T("attn_pool.mlp.fc1.weight"), Ff, D, round_up(F, tn), D, &ws.map_fc1_w))) return rc;
+    if ((rc = upload_matrix(u, u.T("attn_pool.mlp.fc2.weight"), D, Ff, round_up(D, tn), F, &ws.map_fc2_w))) return rc;
     return VITX_OK;
 }
 
 // The transformer blocks blocks.{i}.* of a model file: the same twelve tensors per layer in an image file and a text file
 int upload_blocks(const Upload &u) {
-    const int D = u.D, tn = u.tn, F = u.m->mlp_hidden(), F1 = u.m->mlp_fc1_rows();
+    // F1 / F: fc1's N and fc2's K as the contexts run them; F1f / Ff: as filed (smaller in a file with `mlp` whose width is no multiple of 64: the
+    // upload zero-fills fc1's rows and bias and fc2's columns behind them -- include/vitx.h "MLP width")
+    const int D = u.D, tn = u.tn, F = u.m->mlp_hidden(), F1 = u.m->mlp_fc1_rows(), F1f = u.m->mlp_file_rows(), Ff = u.m->glu_kind ? F : F1f;
     int rc;
     u.ws.layers.resize(u.L);
     for (int i = 0; i < u.L; ++i) {
@@ -152,12 +158,12 @@ int upload_blocks(const Upload &u) {
         if ((rc = upload_f32(u, u.T(p + "mlp.fc1.bias"), &w.fc1_b, round_up(F1, tn)))) return rc;
         if ((rc = upload_f32(u, u.T(p + "mlp.fc2.bias"), &w.fc2_b, round_up(D, tn)))) return rc;
         // a block's matrix: an MX operand in an MXFP8 set (but proj, which stays bf16), else blocks or the expanded operand type
-        auto matrix = [&](const char *name, int k, int N, int K, void **dense) {
-            return u.mx && k != W_PROJ ? upload_mx(u, u.T(p + name), N, K, round_up(N, 128), &w.mx[k]) : upload_weight(u, u.T(p + name), N, K, round_up(N, tn), dense, &w.q[k]);
+        auto matrix = [&](const char *name, int k, int N, int K, void **dense, int n_run = 0, int k_run = 0) {
+            return u.mx && k != W_PROJ ? upload_mx(u, u.T(p + name), N, K, round_up(N, 128), &w.mx[k]) : upload_weight(u, u.T(p + name), N, K, round_up(std::max(N, n_run), tn), dense, &w.q[k], k_run);
         };
         if ((rc = matrix("attn.qkv.weight", W_QKV, 3 * D, D, &w.qkv_w))) return rc;
-        if ((rc = matrix("mlp.fc1.weight", W_FC1, F1, D, &w.fc1_w))) return rc;
-        if ((rc = matrix("mlp.fc2.weight", W_FC2, D, F, &w.fc2_w))) return rc;
+        if ((rc = matrix("mlp.fc1.weight", W_FC1, F1f, D, &w.fc1_w, F1))) return rc;
+        if ((rc = matrix("mlp.fc2.weight", W_FC2, D, Ff, &w.fc2_w, 0, F))) return rc;
         if ((rc = matrix("attn.proj.weight", W_PROJ, D, D, &w.proj_w))) return rc;
     }
     return VITX_OK;
