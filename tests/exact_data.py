@@ -226,9 +226,52 @@ ATTN_CASES = {
     "map": [(2, 197, 3, 64), (1, 577, 2, 64), (3, 17, 2, 32), (2, 65, 1, 128), (1, 50, 4, 96), (2, 197, 2, 80)],
 }
 
+# The head dims of Rows16 (attention_rows.h) at the token counts where its kernels change what they do: 16-key tiles (15, 16, 17), 32-key steps
+# (31, 32, 33), the 64-key chunks of attention_wide.hip (63 .. 65, 127 .. 129, 191 .. 193) and one many-chunk count.  72, 88, 104 and 120 have an
+# odd number of 16-byte pieces per key row (a predicated score pad, a half-live last V tile); 72 meets every edge, every other head dim one triple.
+EDGE_COUNTS = (15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 191, 192, 193, 577)
+HEAD_DIM_EDGES = {72: (15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 191, 192, 193, 577), 88: (31, 32, 33, 65), 104: (127, 128, 129), 112: (63, 64, 65, 130),
+                  120: (191, 192, 193, 33), 24: (15, 16, 17), 40: (31, 32, 33), 56: (63, 64, 65), 48: (127, 128, 129),
+                  96: (64,), 128: (64, 192)}
+_EDGE_GENERIC = [(3, n, 2, hd) for hd, ns in HEAD_DIM_EDGES.items() for n in ns] + [(2, 130, 3, 72)]     # three heads: the middle one has a neighbour on each side
+WIDE_MIN_HD = 72               # attention_wide.hip takes head dims 72 .. 128
+# the class-token map builds its own K pieces (NP = 9 and 15 of 16 lanes live): counts either side of 16 and of 64.  vitx_op_attention_cls has no
+# kernel for these head dims (8, 16, 32, 64, 128 only): test_gpu_exact.py pins the refusal.
+_EDGE_MAP = [(3, n, 2, hd) for hd in (72, 120) for n in (15, 17, 63, 65)]
+# image counts of one pack per odd-piece head dim, all different and all from that head dim's list: (counts, H, head dim)
+PACK_MIXED_CASES = [((17, 64, 129), 2, 72), ((127, 128, 129), 2, 104), ((191, 33, 192), 3, 120)]
+
+ATTN_CASES["generic"] += _EDGE_GENERIC
+ATTN_CASES["map"] += _EDGE_MAP
+ATTN_CASES["auto"] += [(3, 65, 2, 72), (2, 129, 3, 128), (3, 33, 2, 32)]          # the dispatcher's choice under exact data: wide, wide, generic
+ATTN_CASES["wide"] = [c for c in ATTN_CASES["generic"] if c[3] >= WIDE_MIN_HD]
+ATTN_CASES["packed"] = list(ATTN_CASES["generic"])
+
 
 def attn_seed(n_img: int, N: int, H: int, hd: int) -> int:
     return N if (n_img, H, hd) == (1, 1, 64) else N + 1000 * n_img + 100000 * H + 7 * hd
+
+
+def pack_parts(counts, H: int, hd: int):
+    """[(N, seed)] of the images of a mixed pack: every image is a one-image case of its own, with its own seed"""
+    return [(N, attn_seed(1, N, H, hd) + 31 * i) for i, N in enumerate(counts)]
+
+
+def map_routed_f32(qkv: np.ndarray, perm: np.ndarray, n_img: int, N: int, H: int, hd: int) -> float:
+    """The largest class-token map entry away from p(0) under the map's DEFINITION (attention_map_tile.h): the raw score is an exact integer,
+    s = fl32(raw * fl32(1 / sqrt(hd))), the entry exp(s - max) -- here with a float64 exponential.  The two f32 roundings of s move it from
+    e^-gap by up to a few 1e-5 of itself at scales that are no power of two; test_gpu_exact.py allows 1e-5."""
+    x = np.asarray(qkv, np.float64).reshape(n_img, N, 3, H, hd)
+    worst = 0.0
+    sc = np.float32(1.0) / np.sqrt(np.float32(hd))
+    for b in range(n_img):
+        for h in range(H):
+            raw = x[b, :, 1, h] @ x[b, 0, 0, h]
+            s32 = (raw.astype(np.float32) * sc).astype(np.float64)
+            keep = np.arange(N) != perm[b, h, 0]
+            if keep.any():
+                worst = max(worst, float(np.exp((s32[keep] - s32[perm[b, h, 0]]).max())))
+    return worst
 
 
 def dominant_qkv(n_img: int, N: int, H: int, hd: int, seed: int) -> np.ndarray:
@@ -324,6 +367,13 @@ FLAT_CASES = {
     "cls": _three((1, 15, 16, 17, 255, 256, 257, 1025)) + _three((63, 64, 65), 4, 32) + _three((127, 128, 129), hd=128) + [(3, 197, 12, 64), (3, 577, 2, 16), (2, 4097, 2, 64)],
     "map": _three((15, 16, 63, 257)) + [(3, 17, 2, 32), (3, 64, 2, 128), (3, 65, 2, 80), (3, 197, 3, 64), (2, 577, 2, 64), (2, 1, 2, 64), (2, 1024, 2, 64)],
 }
+#   wide     the generic cases of head dims 72 .. 128 through vitx_op_attention_wide: 64-key chunks, 16-key tiles and 32-key steps inside them;
+#   packed   every generic case through vitx_op_attention_packed, the images of a case as one pack (PACK_MIXED_CASES: images of different counts).
+FLAT_CASES["generic"] += _EDGE_GENERIC
+FLAT_CASES["map"] += _EDGE_MAP
+FLAT_CASES["auto"] += [(3, 64, 2, 72), (3, 193, 2, 128), (3, 17, 2, 32)]
+FLAT_CASES["wide"] = [c for c in FLAT_CASES["generic"] if c[3] >= WIDE_MIN_HD]
+FLAT_CASES["packed"] = list(FLAT_CASES["generic"])
 # Spread and peaked data run the same lists without the counts below 15 tokens: with one key the softmax is the constant 1, no scale can
 # move it, and condition (c) of test_cpu_exact_data.py (a 2 % scale fault must break a gate) has nothing to act on.  The flat cases keep N = 1.
 SPREAD_MIN_N = 15
@@ -452,11 +502,14 @@ def attention_emu(q, k, v, scale: float, dtype_name: str, schedule: str = "singl
     return rnd(o * (1.0 / tot)).reshape(B, nb * 32, hd)[:, :Nq]
 
 
-def attention_schedule(family: str, dtype_name: str, N: int) -> str:
+def attention_schedule(family: str, dtype_name: str, N: int, hd: int = 64) -> str:
     """Which definition a family follows at a token count: the bf16 pipelined kernel (forced, or the automatic choice outside the
-    single-pass and persistent ranges) keeps a running maximum; `precise` multiplies f32 values; everything else is single-pass."""
+    single-pass and persistent ranges) keeps a running maximum; `precise` multiplies f32 values; everything else is single-pass.
+    Away from head dim 64 every kernel is Rows16's two passes (generic, wide, packed, and what the automatic choice takes there)."""
     if family == "precise":
         return "precise"
+    if hd != 64 or family in ("generic", "wide", "packed"):
+        return "single"
     single = (N + 31) // 32 in (1, 2, 3, 4, 5, 6, 7, 9, 19)
     if dtype_name == "bf16" and (family == "flow" or (family == "auto" and not (192 < N <= 224) and not (single and N <= 288))):
         return "online"

@@ -108,6 +108,23 @@ def test_attention_routing_gap(family):
         assert 4097 * np.exp(-X.MIN_GAP) * 7.0 < 0.25 * 2.0 ** -25
         if N <= 1025 and n_img * H <= 6:                       # the float64 softmax agrees that the output is the routed row
             assert np.abs(X.attention64(qkv, n_img, N, H, hd) - X.routed(qkv, perm, n_img, N, H, hd))[::(1 if family not in ("cls", "map") else N)].max() < 1e-12
+        if family == "map":
+            # the gate of test_attention_map_of_a_routed_class_token, e^-gap (1 + 1e-5), holds for the f32 definition: its largest other entry, with
+            # room for expf's own error, rounded to f32 (to a denormal or to zero at these gaps: at most e^-40)
+            worst = X.map_routed_f32(qkv, perm, n_img, N, H, hd)
+            assert float(np.float32(worst * (1 + 1e-6))) <= np.exp(-gap) * (1 + 1e-5), (n_img, N, H, hd, gap, worst / np.exp(-gap) - 1)
+
+
+def test_mixed_packs_route_with_the_gap():
+    """Every image of a mixed pack (exact_data.PACK_MIXED_CASES) is a one-image routing case of its own: the gap, the operand types, float64."""
+    for counts, H, hd in X.PACK_MIXED_CASES:
+        for N, seed in X.pack_parts(counts, H, hd):
+            qkv, perm, gap = X.routing_qkv(1, N, H, hd, seed)
+            assert gap >= X.MIN_GAP, (counts, N, H, hd, gap)
+            t = torch.from_numpy(qkv)
+            assert torch.equal(t.to(torch.float16).float(), t) and torch.equal(t.to(torch.bfloat16).float(), t)
+            assert np.abs(X.attention64(qkv, 1, N, H, hd) - X.routed(qkv, perm, 1, N, H, hd)).max() < 1e-12
+    assert len({s for c, H, hd in X.PACK_MIXED_CASES for _, s in X.pack_parts(c, H, hd)}) == 9
 
 
 def test_issue_gaps_at_head_dim_64():
@@ -124,7 +141,7 @@ def _flat_moved(q, k, v, c, hd, dn, schedule):
     return ~(out == c).all(dim=2)
 
 
-@pytest.mark.parametrize("hd", [32, 64, 128])
+@pytest.mark.parametrize("hd", [32, 64, 128, 24, 40, 48, 56, 72, 88, 104, 112, 120])
 def test_flat_softmax_data_is_exact_and_sees_a_dropped_or_padded_key(hd):
     """flat_qkv: every value representable in both operand types, z sums to zero per column and is never zero, every raw score of an item
     is one integer; the f32 / operand-type emulation of every definition gives c bit for bit; and the sensitivity the GPU test relies on:
@@ -177,16 +194,41 @@ def test_attention_case_lists_meet_every_edge():
     assert {n % 16 for _, n, _, _ in X.FLAT_CASES["persist"]} >= {15, 0, 1} and all(192 < n <= 224 for _, n, _, _ in X.FLAT_CASES["persist"])
     assert any(208 < N < 224 and H % 2 for fam in (X.FLAT_CASES, X.ATTN_CASES) for _, N, H, _ in fam["persist"])
     assert all((N + 31) // 32 in (1, 2, 3, 4, 5, 6, 7, 9, 19) for _, N, _, _ in X.FLAT_CASES["single"])
-    assert all(hd != 64 for _, _, _, hd in X.FLAT_CASES["generic"]) and {hd for _, _, _, hd in X.FLAT_CASES["generic"]} >= {32, 80, 96, 128}
+    assert all(hd != 64 for _, _, _, hd in X.FLAT_CASES["generic"])
+    # Rows16's head dims: each one in the routing and in the flat list of every family that reaches it, three images at each of its counts, every
+    # edge count used at some head dim, all of them at 72; the chunk edges of the wide kernel at head dims >= 72; one case with a middle head
+    for cases in (X.FLAT_CASES, X.ATTN_CASES):
+        for f in ("generic", "packed", "wide"):
+            want = {8, 16, 32, 24, 40, 48, 56, 72, 80, 88, 96, 104, 112, 120, 128} if cases is X.FLAT_CASES else {32, 24, 40, 48, 56, 72, 80, 88, 96, 104, 112, 120, 128}
+            assert {hd for _, _, _, hd in cases[f]} == {hd for hd in want if f != "wide" or hd >= X.WIDE_MIN_HD}, (f, sorted({c[3] for c in cases[f]}))
+            three = {(N, hd) for n_img, N, H, hd in cases[f] if n_img >= 3 and H >= 2}
+            for hd, ns in X.HEAD_DIM_EDGES.items():
+                assert f == "wide" and hd < X.WIDE_MIN_HD or {(N, hd) for N in ns} <= three, (f, hd)
+            assert {N for N, hd in three if hd == 72} >= set(X.EDGE_COUNTS), f
+            assert f == "wide" or {N for N, hd in three if hd != 72} >= set(X.EDGE_COUNTS) - {577}, f
+            assert {N for N, hd in three if hd >= X.WIDE_MIN_HD} >= {63, 64, 65, 127, 128, 129, 191, 192, 193}, f
+            for hd in (96, 128):
+                assert (64, hd) in three, (f, hd)
+            assert any(hd == 128 and N == 192 for N, hd in three) and any(H == 3 and hd == 72 for _, _, H, hd in cases[f]), f
+        assert cases["wide"] == [c for c in cases["generic"] if c[3] >= X.WIDE_MIN_HD] and cases["packed"] == cases["generic"]
+        for hd in (72, 120):
+            assert {N for n_img, N, H, h in cases["map"] if h == hd and n_img >= 3} >= {15, 17, 63, 65}, hd
+        assert {hd for _, _, _, hd in cases["auto"]} >= {32, 64, 72, 128}
+    for counts, H, hd in X.PACK_MIXED_CASES:          # a pack of different counts, each from that head dim's own list
+        assert len(set(counts)) == len(counts) == 3 and set(counts) <= set(X.HEAD_DIM_EDGES[hd]) and H >= 2 and hd % 16 == 8
+    assert {hd for _, _, hd in X.PACK_MIXED_CASES} == {72, 104, 120} and any(H == 3 for _, H, _ in X.PACK_MIXED_CASES)
     for f, cases in X.SPREAD_CASES.items():
         assert cases == [c for c in X.FLAT_CASES[f] if c[1] >= X.SPREAD_MIN_N] and len(cases) >= len(X.FLAT_CASES[f]) - 1
     # what the emulation's schedule follows: the dispatcher's ranges (launch_attention, attention.hip)
     S = X.attention_schedule
     assert [S("auto", "bf16", n) for n in (192, 193, 224, 225, 256, 257, 288, 289, 577)] == ["single", "single", "single", "online", "online", "single", "single", "online", "online"]
     assert S("auto", "f16", 4097) == "single" and S("flow", "bf16", 197) == "online" and S("precise", "f16", 197) == "precise" and S("stream", "bf16", 577) == "single"
+    # Rows16 is two-pass everywhere: the families that name it at any count, and the automatic choice away from head dim 64
+    assert all(S(f, "bf16", 577, hd) == "single" for f in ("generic", "wide", "packed") for hd in (32, 72, 128)) and S("packed", "bf16", 577) == "single"
+    assert S("auto", "bf16", 577, 72) == "single" and S("auto", "bf16", 577, 64) == "online"
 
 
-SPREAD_DISTINCT = sorted({(c[1], c[2], c[3]) for cs in X.SPREAD_CASES.values() for c in cs})
+SPREAD_DISTINCT = sorted({(c[1], c[2], c[3]) for cs in X.SPREAD_CASES.values() for c in cs} | {(N, H, hd) for counts, H, hd in X.PACK_MIXED_CASES for N in counts})
 
 
 @pytest.mark.parametrize("N,H,hd", SPREAD_DISTINCT, ids=lambda v: str(v))

@@ -79,7 +79,7 @@ def test_attention_spread_softmax_within_the_derived_bound(binding, torch_gpu, f
     n_img, N, H, hd = case
     _, tdt, _ = TE._types(binding, torch, dtype_name)
     scale = 1.0 / np.sqrt(hd)
-    schedule = X.attention_schedule(family, dtype_name, N)
+    schedule = X.attention_schedule(family, dtype_name, N, hd)
     for kind in X.spread_kinds(N):
         x32 = X.spread_qkv(n_img, N, H, hd, X.attn_seed(n_img, N, H, hd), kind)
         x = torch.from_numpy(x32).cuda()
@@ -106,3 +106,53 @@ def test_attention_spread_softmax_within_the_derived_bound(binding, torch_gpu, f
             assert emu_worst <= 0.5, f"{case} {kind} {dtype_name} {schedule}: the emulation needs {emu_worst:.3f} of the bound (k = {X.ATTN_K})"
             assert worst <= 1.0, f"{name} {dtype_name} {case} {kind}: an element lies at {worst:.3f} of its bound"
             assert mean <= X.ATTN_MEAN_FACTOR, f"{name} {dtype_name} {case} {kind}: mean error {mean:.3f} times the emulation's"
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# vitx_op_attention_packed on images of different token counts (exact_data.PACK_MIXED_CASES): the per-image answers laid end to end
+# ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype_name", ["f16", "bf16"])
+@pytest.mark.parametrize("case", X.PACK_MIXED_CASES, ids=TE._mixed_id)
+def test_attention_packed_mixed_pack_flat_softmax_is_exact(binding, torch_gpu, case, dtype_name):
+    """Flat data of the three signs, every image with its own count, kappa and c: the whole NaN-filled buffer equals each image's c in its rows."""
+    torch = torch_gpu
+    counts, H, hd = case
+    _, tdt, _ = TE._types(binding, torch, dtype_name)
+    for sign in X.FLAT_SIGNS:
+        def one(N, seed):
+            qkv, c = X.flat_qkv(1, N, H, hd, sign, seed + 17 * sign)
+            return qkv, X.flat_expected(c, N)
+        qkv, want = TE.pack_mixed(one, counts, H, hd)
+        out = TE.attention_pack_run(binding, torch, dtype_name, torch.from_numpy(qkv).cuda().to(tdt), counts, H, hd)
+        TE._same(torch, out, torch.from_numpy(want).cuda().to(tdt), f"packed {dtype_name} {case} sign {sign}")
+
+
+@pytest.mark.parametrize("dtype_name", ["f16", "bf16"])
+@pytest.mark.parametrize("case", X.PACK_MIXED_CASES, ids=TE._mixed_id)
+def test_attention_packed_mixed_pack_spread_softmax_within_the_derived_bound(binding, torch_gpu, case, dtype_name):
+    """Spread and peaked data: reference, bound and emulation per image at its own count, laid end to end; the gates of
+    test_attention_spread_softmax_within_the_derived_bound on the whole buffer."""
+    torch = torch_gpu
+    counts, H, hd = case
+    _, tdt, _ = TE._types(binding, torch, dtype_name)
+    scale = 1.0 / np.sqrt(hd)
+    for kind in ("spread", "peaked"):
+        x32, _ = TE.pack_mixed(lambda N, seed: (X.spread_qkv(1, N, H, hd, seed, kind), None), counts, H, hd)
+        xq = torch.from_numpy(x32).cuda().to(tdt)
+        ref, bound, emu, r0 = [], [], [], 0
+        for N in counts:
+            q, k, v = X.heads_of(xq[r0:r0 + N].float(), 1, N, H, hd)
+            r, cond = X.attention_ref(q, k, v, scale, want_bound=True)
+            ref.append(X.rows_of(r, 1, N, H, hd)); bound.append(X.rows_of(X.attention_bound(r, cond, dtype_name), 1, N, H, hd))
+            emu.append(X.rows_of(X.attention_emu(q, k, v, scale, dtype_name, "single"), 1, N, H, hd))
+            r0 += N
+        ref, bound, emu = torch.cat(ref), torch.cat(bound), torch.cat(emu)
+        emu_worst, _ = X.attention_gate_ratios(emu, ref, bound, emu)
+        out = TE.attention_pack_run(binding, torch, dtype_name, xq, counts, H, hd)
+        assert bool(torch.isfinite(out.float()).all()), (case, kind)
+        worst, mean = X.attention_gate_ratios(out, ref, bound, emu)
+        print(f"ATTN_GATE packed-mixed {dtype_name} single {TE._mixed_id(case)} {kind}: emulation {emu_worst:.3f} of the bound, kernel {worst:.3f} of the bound, "
+              f"mean error {mean:.3f} of the emulation's")
+        assert emu_worst <= 0.5, f"{case} {kind} {dtype_name}: the emulation needs {emu_worst:.3f} of the bound (k = {X.ATTN_K})"
+        assert worst <= 1.0, f"packed {dtype_name} {case} {kind}: an element lies at {worst:.3f} of its bound"
+        assert mean <= X.ATTN_MEAN_FACTOR, f"packed {dtype_name} {case} {kind}: mean error {mean:.3f} times the emulation's"

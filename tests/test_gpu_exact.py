@@ -262,18 +262,40 @@ def test_patch_embed_exact(pkg, binding, torch_gpu, tmp_path, P, cin, S, n, dtyp
 ATTN_KERNEL = {"single": 1, "flow": 3, "persist": 4, "stream": 5}
 
 
+def attention_pack_run(binding, torch, dtype_name, xq, counts, H, hd):
+    """vitx_op_attention_packed on device rows xq [sum(counts)][3 D] of the operand type, image i = counts[i] rows: the NaN-filled output it wrote."""
+    dt, tdt, _ = _types(binding, torch, dtype_name)
+    row0 = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    assert xq.shape == (int(row0[-1]), 3 * H * hd) and xq.dtype == tdt
+    out = torch.full((int(row0[-1]), H * hd), float("nan"), dtype=tdt, device="cuda")
+    d_row0 = torch.from_numpy(row0).cuda()
+    binding.op_attention_packed(dt, xq.data_ptr(), out.data_ptr(), d_row0.data_ptr(), len(counts), H * hd, H)
+    torch.cuda.synchronize()
+    return out
+
+
 def attention_run(binding, torch, family, dtype_name, qkv32, n_img, N, H, hd):
     """Runs one attention family / entry point on f32 values (rounded to the operand type on upload); returns {name: output tensor}.
-    `precise` (VITX_F16 only) runs both vitx_op_attention_f32 and vitx_op_attention_planes; `cls` returns [n_img][D]."""
+    `precise` (VITX_F16 only) runs both vitx_op_attention_f32 and vitx_op_attention_planes; `cls` returns [n_img][D].  The kernels of Rows16
+    (attention_rows.h) are each named and reached on purpose: `generic` = vitx_op_attention_generic, `wide` = vitx_op_attention_wide, `packed` =
+    vitx_op_attention_packed; `auto` = vitx_op_attention, whatever it picks."""
     dt, tdt, _ = _types(binding, torch, dtype_name)
     L, D, rows = binding.lib(), H * hd, n_img * N
     x = torch.from_numpy(np.ascontiguousarray(qkv32)).cuda()
     xq = x.to(tdt)
     nan = lambda r: torch.full((r, D), float("nan"), dtype=tdt, device="cuda")
     outs = {}
-    if family in ("auto", "generic"):
+    if family == "auto":
         outs[family] = nan(rows)
         binding.check(L.vitx_op_attention(dt, xq.data_ptr(), outs[family].data_ptr(), n_img, N, D, H, None), family)
+    elif family == "generic":         # attention_generic_kernel itself: vitx_op_attention leaves head dims 72 .. 128 to the wide kernel
+        outs[family] = nan(rows)
+        binding.check(L.vitx_op_attention_generic(dt, xq.data_ptr(), outs[family].data_ptr(), n_img, N, D, H, None), family)
+    elif family == "wide":
+        outs[family] = nan(rows)
+        binding.op_attention_wide(dt, xq.data_ptr(), outs[family].data_ptr(), n_img, N, D, H)
+    elif family == "packed":          # the images of the case as one pack
+        outs[family] = attention_pack_run(binding, torch, dtype_name, xq, [N] * n_img, H, hd)
     elif family in ATTN_KERNEL:
         outs[family] = nan(rows)
         binding.check(L.vitx_op_attention_ex(dt, ATTN_KERNEL[family], xq.data_ptr(), outs[family].data_ptr(), n_img, N, D, H, None), family)
@@ -315,6 +337,47 @@ def test_attention_routes_exactly(binding, torch_gpu, family, dtype_name, case):
         want = want[::N].contiguous()
     for name, out in attention_run(binding, torch, family, dtype_name, qkv, n_img, N, H, hd).items():
         _same(torch, out, want, f"{name} {dtype_name} {case} (gap {gap:.0f})")
+
+
+def pack_mixed(make, counts, H, hd):
+    """The images of a mixed pack laid end to end: make(N, seed) -> (qkv rows of one image, its expected rows or None); (qkv, expected)."""
+    parts = [make(N, seed) for N, seed in X.pack_parts(counts, H, hd)]
+    want = None if parts[0][1] is None else np.concatenate([p[1] for p in parts])
+    return np.concatenate([p[0] for p in parts]), want
+
+
+_mixed_id = lambda c: "N%s_H%d_hd%d" % ("_".join(map(str, c[0])), c[1], c[2])
+
+
+@pytest.mark.parametrize("dtype_name", ["f16", "bf16"])
+@pytest.mark.parametrize("case", X.PACK_MIXED_CASES, ids=_mixed_id)
+def test_attention_packed_mixed_pack_routes_exactly(binding, torch_gpu, case, dtype_name):
+    """vitx_op_attention_packed on images of different token counts at an odd-piece head dim: the expected rows are the per-image routed rows laid
+    end to end, so a key clamped to a neighbour's row, an image found by the wrong table entry or a count taken from the next image moves a row."""
+    torch = torch_gpu
+    counts, H, hd = case
+    _, tdt, _ = _types(binding, torch, dtype_name)
+
+    def one(N, seed):
+        qkv, perm, gap = X.routing_qkv(1, N, H, hd, seed)
+        assert gap >= X.MIN_GAP, gap
+        return qkv, X.routed(qkv, perm, 1, N, H, hd)
+    qkv, want = pack_mixed(one, counts, H, hd)
+    out = attention_pack_run(binding, torch, dtype_name, torch.from_numpy(qkv).cuda().to(tdt), counts, H, hd)
+    _same(torch, out, torch.from_numpy(want).cuda().to(tdt), f"packed {dtype_name} {case}")
+
+
+def test_attention_cls_refuses_the_head_dims_without_a_kernel(binding, torch_gpu):
+    """vitx_op_attention_cls has kernels for head dims 8, 16, 32, 64 and 128: at 72 and 120 it answers VITX_ERR_UNSUPPORTED and writes nothing (the
+    engine runs the last layer on all rows there), so no exact case of those head dims can be listed for it."""
+    torch = torch_gpu
+    for hd in (72, 120):
+        n_img, N, H = 3, 17, 2
+        qkv = torch.zeros((n_img * N, 3 * H * hd), dtype=torch.float16, device="cuda")
+        out = torch.full((n_img, H * hd), float("nan"), dtype=torch.float16, device="cuda")
+        assert binding.lib().vitx_op_attention_cls(binding.F16, qkv.data_ptr(), 0, out.data_ptr(), n_img, N, H * hd, H, None) == VITX_ERR_UNSUPPORTED, hd
+        torch.cuda.synchronize()
+        assert bool(torch.isnan(out).all()), hd
 
 
 @pytest.mark.parametrize("dtype_name", ["f16", "bf16"])
