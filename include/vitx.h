@@ -1153,12 +1153,16 @@ int vitx_op_attention_wide(int dtype, const void *d_qkv, void *d_out, int n_img,
  * operands with the ordinary attention (the text tower's rule: no hi / lo parity planes).  One stream, no sub-batches, no graph cache, no
  * LayerNorm fusion, no class-token tail; block-quantised matrices are expanded once at upload; the GEMMs go through the dispatcher with the
  * device's own tuning (every GEMM family gives the same bits).  options (NULL = all zero): pos_interp as in vitx_ctx_options; max_grids = the
- * grids whose tables the context caches (0 = 32); attn_kernel = the attention kernel of every layer: VITX_PACK_ATTN_AUTO (0) runs the staged
- * kernel (vitx_op_attention_packed_ex below) where the model's head dim is 64 and the generic one otherwise, VITX_PACK_ATTN_GENERIC and
- * VITX_PACK_ATTN_STAGED force one; vitx_pack_attn_kernel returns the one the context runs (1 or 2).  The two give an image the same bits, so
+ * grids whose tables the context caches (0 = 32); attn_kernel = the attention kernel of every layer: VITX_PACK_ATTN_AUTO (0) runs a kernel
+ * that stages keys and values in LDS once per workgroup (vitx_op_attention_packed_ex below) where there is one -- head dim 64
+ * (csrc/attention_packed_staged.hip) and head dims 72, 80, .., 128 (csrc/attention_packed_wide.hip) -- and the generic one elsewhere (head dims
+ * 8 .. 56); VITX_PACK_ATTN_GENERIC forces the generic kernel at every head dim; VITX_PACK_ATTN_STAGED, as a REQUEST, means the head-dim-64
+ * kernel and is refused at every other head dim.  vitx_pack_attn_kernel REPORTS what the context runs (1 or 2), and as a report
+ * VITX_PACK_ATTN_STAGED means "keys staged in LDS per workgroup": the head-dim-64 kernel or the one of head dims 72 .. 128;
+ * VITX_PACK_ATTN_GENERIC otherwise.  The kernels give an image the same bits, so
  * the choice changes no output, launch count or scratch byte -- with one exception: where a value row v[N_i - 1] of an (image, head)
  * holds +-Inf and N_i % 32 != 0, the generic kernel multiplies that row by the zero probabilities of the padding keys (NaN) and the staged
- * kernel reads zeros there (no NaN from the padding); with NaN in place of Inf both give NaN.  VITX_ERR_UNSUPPORTED at creation, before any
+ * kernels read zeros there (no NaN from the padding); with NaN in place of Inf all give NaN.  VITX_ERR_UNSUPPORTED at creation, before any
  * device call: a ViTSTR file, a VITX_POOL_CLS_MEAN head, a VITX_POOL_MAP head without pool_head (below), VITX_MXFP8, a head dim that is no multiple of 8 up to 128,
  * VITX_PACK_ATTN_STAGED at a head dim other than 64 (the message names D and H), a D outside the LayerNorm widths, a max_tokens beyond the
  * kernels' 32-bit buffer window.  VITX_ERR_ARG: a text model, an attn_kernel outside 0 .. 2.
@@ -1198,10 +1202,15 @@ int vitx_op_attention_wide(int dtype, const void *d_qkv, void *d_out, int n_img,
  *   vitx_op_attention_packed_ex   the same with a kernel id: VITX_PACK_ATTN_GENERIC = vitx_op_attention_packed's kernel, VITX_PACK_ATTN_STAGED = head dim
  *                              64 only, K and V streamed through LDS in 64-key chunks once per workgroup (csrc/attention_packed_staged.hip) with the
  *                              generic kernel's arithmetic operation for operation: the same bits, the same grid, the same tables, except that
- *                              keys past N_i are read as zeros, not as row N_i - 1 (the +-Inf sentence above); VITX_PACK_ATTN_AUTO = STAGED at
- *                              head dim 64, GENERIC otherwise.  TEST entry point as well: null stream, synchronous.  Before the first device
+ *                              keys past N_i are read as zeros, not as row N_i - 1 (the +-Inf sentence above); VITX_PACK_ATTN_AUTO = that kernel at
+ *                              head dim 64, at head dims 72, 80, .., 128 its twin with attention_wide.hip's data movement
+ *                              (csrc/attention_packed_wide.hip: unpadded rows of 2 DH bytes, 512 DH bytes of LDS, the same bits, grid, tables and
+ *                              exception), the generic kernel elsewhere.  AUTO is the only way to the kernel of head dims 72 .. 128: it has no
+ *                              id of its own.  TEST entry point as well: null stream, synchronous.  Before the first device
  *                              call: VITX_ERR_ARG for a NULL pointer, n <= 0, a bad dtype or kernel id; VITX_ERR_UNSUPPORTED for STAGED at a
  *                              head dim other than 64 or a head dim the generic kernel refuses.
+ *   vitx_op_attention_packed_tables_ex   the kernel by id (AUTO included, resolved as above) on tables the caller built: only enqueues, on the null
+ *                              stream; what tools/pack_staged_cost.py and tools/pack_wide_cost.py time.
  *   vitx_op_rope_packed        vitx_op_rope on a pack: token t >= prefix of image i rotates by row t - prefix of the table that starts
  *                              d_table_off[i] floats into d_cos and d_sin; one launch for the pack; reads both tables back to check them (synchronises).
  *
@@ -1359,6 +1368,7 @@ int vitx_op_attention_wide(int dtype, const void *d_qkv, void *d_out, int n_img,
  * Not offered on packed contexts (each a later step): the other opt-in heads (zero-shot bank, gallery), the pooled (cls + mean) head; of the
  * attention-pooling head: attention maps, the dense and the depth head, VITX_FEAT_MEAN, more than 16 heads, and image contexts of such files away from
  * the file's own shape; the F16 parity planes, LayerNorm fusion and sub-batch streams, a packed patch-embedding kernel, vitx_group_*;
+ * of the attention: a kernel id that forces the staged kernel of head dims 72 .. 128 (AUTO runs it; the ids stay 0 .. 2), staging at head dims 8 .. 56;
  * of the dense and the depth head: downsampling, and a vit.h wrapper; of the u8 sources: crops and shortest-edge geometry (a source is stretched
  * to the given shape), the REF filters, JPEG decode on the device, and a vit.h wrapper; of the attention maps: full N x N maps as an output, rollout
  * above 1024 tokens per image, and a vit.h wrapper. */
@@ -1381,7 +1391,7 @@ int vitx_pack_feat_enable(vitx_pack *p, int flags /* VITX_FEAT_CLS | VITX_FEAT_T
 int vitx_pack_feat_read(vitx_pack *p, float *cls /* [n][D] or NULL */, float *tokens /* [sum gh_i gw_i][D], images end to end, or NULL */);
 size_t vitx_pack_scratch_bytes(const vitx_pack *p);        /* device bytes of activation scratch and cached tables held now (weights not counted) */
 int vitx_pack_launches(const vitx_pack *p, int *patch_embed);      /* kernel launches of the last forward call; *patch_embed: the patch embeddings among them */
-int vitx_pack_attn_kernel(const vitx_pack *p);             /* VITX_PACK_ATTN_GENERIC or VITX_PACK_ATTN_STAGED: the attention kernel this context runs (0 for NULL) */
+int vitx_pack_attn_kernel(const vitx_pack *p);             /* a report: VITX_PACK_ATTN_STAGED = keys staged in LDS per workgroup (head dim 64 or 72 .. 128), else VITX_PACK_ATTN_GENERIC (0 for NULL) */
 /* the attention-pooling head on a pack (pool_head = VITX_PACK_POOL_MAP): the chunk size of the pooling launch, and the running chunk count of row counts [n] */
 int vitx_pack_pool_chunk_rows(void);
 int vitx_pack_pool_chunks(const int *rows, int n, int *chunk0 /* [n + 1] or NULL */);
@@ -1396,7 +1406,7 @@ int vitx_op_attention_packed(int dtype, const void *d_qkv, void *d_out, const vo
 int vitx_op_attention_packed_tables(int dtype, const void *d_qkv, void *d_out, const void *d_row0, const void *d_qb0, int n, long qblocks, int D, int H, void *stream);
 /* the kernel by id (VITX_PACK_ATTN_*), on the null stream, synchronous: a test entry point like vitx_op_attention_packed */
 int vitx_op_attention_packed_ex(int dtype, int kernel, const void *d_qkv, void *d_out, const void *d_row0 /* int32 [n + 1] */, int n, int D, int H);
-/* vitx_op_attention_packed_tables with a kernel id (GENERIC or STAGED, no AUTO) on the null stream; only enqueues */
+/* vitx_op_attention_packed_tables with a kernel id (VITX_PACK_ATTN_*, AUTO resolved as vitx_pack_create resolves it) on the null stream; only enqueues */
 int vitx_op_attention_packed_tables_ex(int dtype, int kernel, const void *d_qkv, void *d_out, const void *d_row0, const void *d_qb0, int n, long qblocks, int D, int H);
 int vitx_op_rope_packed(int dtype, void *d_qkv, long lo_off /* must be 0 */, const void *d_cos, const void *d_sin, const void *d_row0 /* int32 [n + 1] */,
                         const void *d_table_off /* int32 [n] */, int n, int prefix, int D, int H, void *stream);

@@ -9,7 +9,8 @@
 // neighbour's.  No atomics, one writer per output element, nothing written outside rows row0[0] .. row0[n] - 1.  32 * DHP * 2 bytes of LDS
 // per wave (at most 32 KiB per workgroup): no dynamic-LDS attribute, no prepare_*.
 // K and V are NOT staged in LDS for the four waves of a workgroup (profiles/pack_cost.txt): attention_packed_staged.hip does that for head dim 64, with
-// this kernel's bits, and is what a packed context runs there; this kernel serves the other head dims and stays the yardstick.
+// this kernel's bits, attention_packed_wide.hip for head dims 72 .. 128, and they are what a packed context runs there (resolve_attention_packed below);
+// this kernel serves the other head dims and stays the yardstick.
 #include "attention_rows.h"
 
 namespace vitx {
@@ -53,6 +54,18 @@ static hipError_t launch_attention_packed_t(const void *qkv, void *out, const in
 hipError_t launch_attention_packed(int dtype, const void *qkv, void *out, const int *row0, const int *qb0, int n, long qblocks, int D, int H, hipStream_t stream) {
     if (!attention_packed_supports(D, H) || n <= 0 || qblocks < n || qblocks * H > 0x7fffffffL) return hipErrorInvalidValue;
     return VITX_BY_DTYPE(dtype, launch_attention_packed_t, qkv, out, row0, qb0, n, qblocks, D, H, stream);
+}
+
+// The one rule of the packed family (kernels.h): which of its three kernels a request runs at this shape, and what a context reports for it.
+PackedAttnRefusal resolve_attention_packed(int request, int D, int H, PackedAttn *out) {
+    *out = PackedAttn();
+    if (request < VITX_PACK_ATTN_AUTO || request > VITX_PACK_ATTN_STAGED) return PACKED_ATTN_BAD_ID;
+    if (request == VITX_PACK_ATTN_STAGED && !attention_packed_staged_supports(D, H)) return PACKED_ATTN_STAGED_NOT_64;
+    if (!attention_packed_supports(D, H)) return PACKED_ATTN_NO_KERNEL;
+    if (request != VITX_PACK_ATTN_GENERIC && attention_packed_staged_supports(D, H)) *out = {launch_attention_packed_staged, VITX_PACK_ATTN_STAGED};
+    else if (request == VITX_PACK_ATTN_AUTO && attention_packed_wide_supports(D, H)) *out = {launch_attention_packed_wide, VITX_PACK_ATTN_STAGED};
+    else *out = {launch_attention_packed, VITX_PACK_ATTN_GENERIC};
+    return PACKED_ATTN_OK;
 }
 
 }  // namespace vitx

@@ -37,18 +37,9 @@
 //   waves / SIMD       4       4       3       3       3       2       2       2   = workgroups per CU, bound by LDS (the VGPRs would allow 5)
 // Numbers: profiles/wide_attn_cost.txt.
 #include "attention_rows.h"
+#include "attention_wide_shape.h"
 
 namespace vitx {
-
-template <int DH>
-struct WideShape {
-    static constexpr int P = DH / 8, NK2 = DH <= 96 ? 3 : 4, NDV = (DH + 15) / 16, ROWB = DH * 2;
-    static constexpr int G = (P & -P) > 16 ? 16 : (P & -P);                    // gcd(P, 16)
-    static constexpr int CK = 64, KBYTES = CK * ROWB, BUF = 2 * KBYTES;         // a chunk buffer: K image, then V image
-    static constexpr int LDS = 2 * BUF + (DH % 16 ? 16 : 0);
-    static constexpr int WAVES = 160 * 1024 / LDS > 4 ? 4 : 160 * 1024 / LDS;   // workgroups (= waves per SIMD) the LDS lets a CU hold
-    static __device__ __forceinline__ int rot(int r) { return ((r & 15) * G) >> 4; }
-};
 
 template <typename T, int DH>
 __global__ __launch_bounds__(256, WideShape<DH>::WAVES) void attention_wide_kernel(const T *__restrict__ qkv, T *__restrict__ out, int N, int D, int H, float scale, int qblocks) {

@@ -331,6 +331,23 @@ bool attention_packed_supports(int D, int H);      // attention_generic_supports
 //                     and bits (but for a value row v[N_i - 1] holding +-Inf where N_i % 32 != 0); hipErrorInvalidValue on another head dim
 hipError_t launch_attention_packed_staged(int dtype, const void *qkv, void *out, const int *row0, const int *qb0, int n, long qblocks, int D, int H, hipStream_t stream);
 bool attention_packed_staged_supports(int D, int H);      // head dim 64
+//   attention_packed_wide: the same call for head dims 72, 80, .., 128 (attention_packed_wide.hip): K and V staged in LDS as attention_wide.hip stages them,
+//                     the same tables, grid and bits with the same one exception; hipErrorInvalidValue on another head dim
+hipError_t launch_attention_packed_wide(int dtype, const void *qkv, void *out, const int *row0, const int *qb0, int n, long qblocks, int D, int H, hipStream_t stream);
+bool attention_packed_wide_supports(int D, int H);        // head dim 72, 80, .., 128
+//   resolve_attention_packed: THE rule from a request (VITX_PACK_ATTN_*) and a shape to the kernel that runs -- a packed context, its per-layer launch and
+//                     the vitx_op_attention_packed*_ex entries all ask here.  AUTO: the staged kernel at head dim 64, the wide one at 72 .. 128, the
+//                     generic one elsewhere; GENERIC: the generic one at every head dim; STAGED, as a request: the head-dim-64 kernel or a refusal.
+//                     `report` is what vitx_pack_attn_kernel says: VITX_PACK_ATTN_STAGED wherever keys are staged in LDS per workgroup (both staged
+//                     kernels), VITX_PACK_ATTN_GENERIC otherwise.  Refusals in this order, nothing launched: an id outside 0 .. 2; STAGED at a head dim
+//                     other than 64; a head dim no packed kernel takes
+typedef hipError_t (*attention_packed_launch_t)(int dtype, const void *qkv, void *out, const int *row0, const int *qb0, int n, long qblocks, int D, int H, hipStream_t stream);
+struct PackedAttn {
+    attention_packed_launch_t launch = nullptr;
+    int report = 0;
+};
+enum PackedAttnRefusal { PACKED_ATTN_OK = 0, PACKED_ATTN_BAD_ID, PACKED_ATTN_STAGED_NOT_64, PACKED_ATTN_NO_KERNEL };
+PackedAttnRefusal resolve_attention_packed(int request, int D, int H, PackedAttn *out);
 hipError_t launch_rope_packed(int dtype, void *qkv, const float *cos, const float *sin, const int *row0, const int *toff, int n, long patch_rows, bool toff_aligned, int prefix, int D,
                               int H, hipStream_t stream);
 hipError_t launch_pool_rows(int dtype, const float *X, const int *rows, const float *w, const float *b, void *z, int n, int m_pad, int D, float eps, hipStream_t stream);

@@ -204,8 +204,8 @@ static int read_row0(const char *name, const void *d_row0, int n, int min_rows, 
         if (row0[0] < 0 || (long)row0[i + 1] - row0[i] < min_rows) { set_error("%s: d_row0 must start at 0 or above and give every image at least %d rows (image %d)", name, min_rows, i); return VITX_ERR_ARG; }
     return VITX_OK;
 }
-// kernel: VITX_PACK_ATTN_GENERIC or VITX_PACK_ATTN_STAGED, resolved and checked by the caller
-static int attention_packed_by(const char *name, int dtype, int kernel, const void *d_qkv, void *d_out, const void *d_row0, int n, int D, int H, void *stream) {
+// launch: the kernel, resolved and checked by the caller (resolve_attention_packed, kernels.h)
+static int attention_packed_by(const char *name, int dtype, attention_packed_launch_t launch, const void *d_qkv, void *d_out, const void *d_row0, int n, int D, int H, void *stream) {
     std::vector<int32_t> row0, qb0((size_t)n + 1);
     if (const int rc = read_row0(name, d_row0, n, 1, row0)) return rc;
     long qblocks = 0;
@@ -216,23 +216,26 @@ static int attention_packed_by(const char *name, int dtype, int kernel, const vo
     const DevMem qb_own(d_qb0);
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemcpy(d_qb0, qb0.data(), qb0.size() * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = (kernel == VITX_PACK_ATTN_STAGED ? launch_attention_packed_staged : launch_attention_packed)(dtype, d_qkv, d_out, (const int *)d_row0, d_qb0, n, qblocks, D, H, st);
+    if (e == hipSuccess) e = launch(dtype, d_qkv, d_out, (const int *)d_row0, d_qb0, n, qblocks, D, H, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);       // d_qb0 is freed on return
     return op_rc(name, e, VITX_ERR_UNSUPPORTED);
 }
 int vitx_op_attention_packed(int dtype, const void *d_qkv, void *d_out, const void *d_row0, int n, int D, int H, void *stream) {
     if (!d_qkv || !d_out || !d_row0 || n <= 0 || D <= 0 || H <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_attention_packed: invalid argument"); return VITX_ERR_ARG; }
     if (!attention_packed_supports(D, H)) { set_error("vitx_op_attention_packed: head_dim must be a multiple of 8 up to 128 (D %d, H %d)", D, H); return VITX_ERR_UNSUPPORTED; }
-    return attention_packed_by("vitx_op_attention_packed", dtype, VITX_PACK_ATTN_GENERIC, d_qkv, d_out, d_row0, n, D, H, stream);
+    return attention_packed_by("vitx_op_attention_packed", dtype, launch_attention_packed, d_qkv, d_out, d_row0, n, D, H, stream);
 }
 // The kernel by id, on the null stream.  Every refusal comes before the first device call.
 int vitx_op_attention_packed_ex(int dtype, int kernel, const void *d_qkv, void *d_out, const void *d_row0, int n, int D, int H) {
     if (!d_qkv || !d_out || !d_row0 || n <= 0 || D <= 0 || H <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_attention_packed_ex: invalid argument"); return VITX_ERR_ARG; }
-    if (kernel < VITX_PACK_ATTN_AUTO || kernel > VITX_PACK_ATTN_STAGED) { set_error("vitx_op_attention_packed_ex: unknown kernel id %d (0 auto, 1 generic, 2 staged)", kernel); return VITX_ERR_ARG; }
-    if (kernel == VITX_PACK_ATTN_STAGED && !attention_packed_staged_supports(D, H)) { set_error("vitx_op_attention_packed_ex: the staged kernel needs head_dim 64 (D %d, H %d)", D, H); return VITX_ERR_UNSUPPORTED; }
-    if (!attention_packed_supports(D, H)) { set_error("vitx_op_attention_packed_ex: head_dim must be a multiple of 8 up to 128 (D %d, H %d)", D, H); return VITX_ERR_UNSUPPORTED; }
-    if (kernel == VITX_PACK_ATTN_AUTO) kernel = attention_packed_staged_supports(D, H) ? VITX_PACK_ATTN_STAGED : VITX_PACK_ATTN_GENERIC;
-    return attention_packed_by("vitx_op_attention_packed_ex", dtype, kernel, d_qkv, d_out, d_row0, n, D, H, nullptr);
+    PackedAttn attn;
+    switch (resolve_attention_packed(kernel, D, H, &attn)) {
+    case PACKED_ATTN_BAD_ID: set_error("vitx_op_attention_packed_ex: unknown kernel id %d (0 auto, 1 generic, 2 staged)", kernel); return VITX_ERR_ARG;
+    case PACKED_ATTN_STAGED_NOT_64: set_error("vitx_op_attention_packed_ex: the staged kernel needs head_dim 64 (D %d, H %d)", D, H); return VITX_ERR_UNSUPPORTED;
+    case PACKED_ATTN_NO_KERNEL: set_error("vitx_op_attention_packed_ex: head_dim must be a multiple of 8 up to 128 (D %d, H %d)", D, H); return VITX_ERR_UNSUPPORTED;
+    case PACKED_ATTN_OK: break;
+    }
+    return attention_packed_by("vitx_op_attention_packed_ex", dtype, attn.launch, d_qkv, d_out, d_row0, n, D, H, nullptr);
 }
 // The same launch on tables the caller has built and vouches for (d_qb0 [n + 1]: the running count of 64-query blocks; qblocks = d_qb0[n]): only
 // enqueues, reads nothing back -- what a packed context does per layer, and what tools/pack_cost.py times.
@@ -240,11 +243,14 @@ int vitx_op_attention_packed_tables(int dtype, const void *d_qkv, void *d_out, c
     if (!d_qkv || !d_out || !d_row0 || !d_qb0 || n <= 0 || qblocks < n || D <= 0 || H <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_attention_packed_tables: invalid argument"); return VITX_ERR_ARG; }
     return op_rc("vitx_op_attention_packed_tables", launch_attention_packed(dtype, d_qkv, d_out, (const int *)d_row0, (const int *)d_qb0, n, qblocks, D, H, (hipStream_t)stream), VITX_ERR_UNSUPPORTED);
 }
-// The staged or the generic kernel (no AUTO) on the caller's tables, enqueued on the null stream: what tools/pack_staged_cost.py times.
+// The kernel by id (AUTO included) on the caller's tables, enqueued on the null stream: what tools/pack_staged_cost.py and tools/pack_wide_cost.py time.
+// A shape the requested kernel does not take is refused as that kernel's launcher refuses it.
 int vitx_op_attention_packed_tables_ex(int dtype, int kernel, const void *d_qkv, void *d_out, const void *d_row0, const void *d_qb0, int n, long qblocks, int D, int H) {
+    PackedAttn attn;
+    PackedAttnRefusal no = PACKED_ATTN_BAD_ID;
     if (!d_qkv || !d_out || !d_row0 || !d_qb0 || n <= 0 || qblocks < n || D <= 0 || H <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16) ||
-        (kernel != VITX_PACK_ATTN_GENERIC && kernel != VITX_PACK_ATTN_STAGED)) { set_error("vitx_op_attention_packed_tables_ex: invalid argument"); return VITX_ERR_ARG; }
-    return op_rc("vitx_op_attention_packed_tables_ex", (kernel == VITX_PACK_ATTN_STAGED ? launch_attention_packed_staged : launch_attention_packed)(dtype, d_qkv, d_out, (const int *)d_row0, (const int *)d_qb0, n, qblocks, D, H, nullptr), VITX_ERR_UNSUPPORTED);
+        (no = resolve_attention_packed(kernel, D, H, &attn)) == PACKED_ATTN_BAD_ID) { set_error("vitx_op_attention_packed_tables_ex: invalid argument"); return VITX_ERR_ARG; }
+    return op_rc("vitx_op_attention_packed_tables_ex", no ? hipErrorInvalidValue : attn.launch(dtype, d_qkv, d_out, (const int *)d_row0, (const int *)d_qb0, n, qblocks, D, H, nullptr), VITX_ERR_UNSUPPORTED);
 }
 int vitx_op_rope_packed(int dtype, void *d_qkv, long lo_off, const void *d_cos, const void *d_sin, const void *d_row0, const void *d_table_off, int n, int prefix, int D, int H, void *stream) {
     if (!d_qkv || !d_cos || !d_sin || !d_row0 || !d_table_off || n <= 0 || D <= 0 || H <= 0 || prefix < 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_rope_packed: invalid argument"); return VITX_ERR_ARG; }

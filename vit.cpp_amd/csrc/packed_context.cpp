@@ -168,8 +168,8 @@ int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_im
     if (pool_head && H > kPoolPackMaxHeads) { set_error("vitx_pack_create: the packed attention-pooling kernel takes at most %d heads (this model: %d)", kPoolPackMaxHeads, H); return VITX_ERR_UNSUPPORTED; }
     if (pool_head && !attention_pool_packed_fits(D)) { set_error("vitx_pack_create: the staging tiles of hidden size %d do not fit the packed attention-pooling kernel's LDS", D); return VITX_ERR_UNSUPPORTED; }
     if (!attention_packed_supports(D, H)) { set_error("vitx_pack_create: attention needs a head_dim that is a multiple of 8 up to 128 (this model: %d / %d)", D, H); return VITX_ERR_UNSUPPORTED; }
-    if (attn_kernel == VITX_PACK_ATTN_STAGED && !attention_packed_staged_supports(D, H)) { set_error("vitx_pack_create: the staged attention kernel needs head_dim 64 (this model: %d / %d)", D, H); return VITX_ERR_UNSUPPORTED; }
-    if (attn_kernel == VITX_PACK_ATTN_AUTO) attn_kernel = attention_packed_staged_supports(D, H) ? VITX_PACK_ATTN_STAGED : VITX_PACK_ATTN_GENERIC;
+    PackedAttn attn;
+    if (resolve_attention_packed(attn_kernel, D, H, &attn) != PACKED_ATTN_OK) { set_error("vitx_pack_create: the staged attention kernel needs head_dim 64 (this model: %d / %d)", D, H); return VITX_ERR_UNSUPPORTED; }
     if (!layernorm_supports(D)) { set_error("vitx_pack_create: hidden_size %d has no LayerNorm instantiation", D); return VITX_ERR_UNSUPPORTED; }
     if (m->rope_kind && !rope_supports(D, H)) { set_error("vitx_pack_create: rotary position embeddings need an even head dim (D %d, H %d)", D, H); return VITX_ERR_UNSUPPORTED; }
     if (hp.patch_size <= 0 || hp.img_size % hp.patch_size) { set_error("vitx_pack_create: the file's img_size %d is not a multiple of its patch size %d", hp.img_size, hp.patch_size); return VITX_ERR_UNSUPPORTED; }
@@ -186,7 +186,7 @@ int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_im
     p->glu = m->glu_kind != VITX_GLU_NONE; p->F = m->mlp_hidden(); p->F1 = F1; p->rope = m->rope_kind != VITX_ROPE_NONE;
     p->fc1_epi = p->glu ? EPI_BIAS : act_epi(m->activation); p->eps = hp.eps;
     p->tm = gemm_tile_m(); p->tn = gemm_tile_n();
-    p->max_tokens = max_tokens; p->max_images = max_images; p->max_grids = max_grids; p->pos_interp = pos_interp; p->attn_kernel = attn_kernel;
+    p->max_tokens = max_tokens; p->max_images = max_images; p->max_grids = max_grids; p->pos_interp = pos_interp; p->attn_kernel = attn.report; p->attn_launch = attn.launch;
     // quantised block matrices are expanded at upload: block mode 0, as in the text context
     if ((rc = obtain_weights({m, device, dtype, false}, &p->wset, &p->weights_shared))) return rc;
     auto dmalloc = [&](void **q, size_t bytes) -> int {

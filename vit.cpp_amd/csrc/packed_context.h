@@ -132,7 +132,8 @@ struct vitx_pack {
     float eps = 1e-6f;
     int tm = 256, tn = 128;
     int max_tokens = 0, max_images = 0, max_grids = 32, pos_interp = 0;
-    int attn_kernel = VITX_PACK_ATTN_GENERIC;      // the kernel every layer's attention runs: GENERIC or STAGED, never AUTO
+    int attn_kernel = VITX_PACK_ATTN_GENERIC;      // what vitx_pack_attn_kernel reports: STAGED where keys go through LDS per workgroup, else GENERIC, never AUTO
+    attention_packed_launch_t attn_launch = nullptr;      // the kernel every layer's attention runs (resolve_attention_packed, kernels.h)
     const Tuning *tune = nullptr;        // per-device launch parameters, immutable: the GEMMs go through launch_gemm with the device's own tuning
     std::shared_ptr<WeightSet> wset;
     bool weights_shared = false;

@@ -327,7 +327,7 @@ int pack_forward(vitx_pack *p, PackCall &c, const void *d_imgs, const int32_t *s
             ++p->launches;
         }
         if (am && (rc = pack_attention_maps(p, at, il, n, st))) return rc;
-        HIP_TRY((p->attn_kernel == VITX_PACK_ATTN_STAGED ? launch_attention_packed_staged : launch_attention_packed)(dt, p->QKV, p->U, d_row0, d_qb0, n, qblocks, D, H, st)); ++p->launches;
+        HIP_TRY(p->attn_launch(dt, p->QKV, p->U, d_row0, d_qb0, n, qblocks, D, H, st)); ++p->launches;
         if ((rc = pack_gemm(p, EPI_BIAS_RESID, dense_gemm(p->U, w.proj_w, w.proj_b, p->X, M, rows, D, round_up(D, tn), D), st))) return rc;
         HIP_TRY(launch_layernorm(dt, p->X, D, w.ln2_w, w.ln2_b, p->U, D, rows, D, p->eps, st)); ++p->launches;
         if ((rc = pack_gemm(p, p->fc1_epi, dense_gemm(p->U, w.fc1_w, w.fc1_b, p->Hbuf, M, rows, p->F1, round_up(p->F1, tn), D), st))) return rc;
