@@ -1163,7 +1163,7 @@ int vitx_op_attention_wide(int dtype, const void *d_qkv, void *d_out, int n_img,
  * the choice changes no output, launch count or scratch byte -- with one exception: where a value row v[N_i - 1] of an (image, head)
  * holds +-Inf and N_i % 32 != 0, the generic kernel multiplies that row by the zero probabilities of the padding keys (NaN) and the staged
  * kernels read zeros there (no NaN from the padding); with NaN in place of Inf all give NaN.  VITX_ERR_UNSUPPORTED at creation, before any
- * device call: a ViTSTR file, a VITX_POOL_CLS_MEAN head, a VITX_POOL_MAP head without pool_head (below), VITX_MXFP8, a head dim that is no multiple of 8 up to 128,
+ * device call: a ViTSTR file, a VITX_POOL_CLS_MEAN head without pool_head = 2 (below), a VITX_POOL_MAP head without pool_head = 1 (below), VITX_MXFP8, a head dim that is no multiple of 8 up to 128,
  * VITX_PACK_ATTN_STAGED at a head dim other than 64 (the message names D and H), a D outside the LayerNorm widths, a max_tokens beyond the
  * kernels' 32-bit buffer window.  VITX_ERR_ARG: a text model, an attn_kernel outside 0 .. 2.
  *
@@ -1186,7 +1186,9 @@ int vitx_op_attention_wide(int dtype, const void *d_qkv, void *d_out, int n_img,
  *
  * Features of the last layer (vitx_pack_feat_enable, flags VITX_FEAT_CLS | VITX_FEAT_TOKENS, 0 = off; with nothing enabled nothing is launched
  * or allocated): the f32 final norm of every row of the pack (vitx_op_layernorm_f32's bits), gathered by vitx_pack_feat_read: cls [n][D] = the
- * class rows, tokens [sum gh_i gw_i][D] = the patch rows, images end to end.
+ * class rows, tokens [sum gh_i gw_i][D] = the patch rows, images end to end.  VITX_FEAT_MEAN (and VITX_FEAT_L2 with it, never alone; L2 divides the
+ * mean by its norm and leaves cls and tokens as they are) is taken on every context but one of an attention-pooling file: the mean of an image's
+ * final-norm patch rows, read by vitx_pack_feat_read_mean -- its arithmetic and its order stand under "The cls + mean head on a pack" below.
  *
  * Determinism: within a context an image's logits, probabilities and features are a function of its own pixels and shape -- the same bits
  * alone, at any position in a pack and beside any neighbours (NaN pixels included).  A pack of one shape gives the bits of a rectangular
@@ -1365,7 +1367,43 @@ int vitx_op_attention_wide(int dtype, const void *d_qkv, void *d_out, int n_img,
  *   vitx_op_attention_pool_packed  the two launches on the caller's buffers: d_x [rows][D] f32, HOST row0 [n + 1] (ascending, N_i >= 1) -> d_M [n][H][D]
  *                              f32; vitx_op_attention_pool's argument checks and H <= 16, D <= 1152.  TEST entry point: it builds and uploads its
  *                              tables, allocates its partial scratch, runs on the null stream and returns after synchronising.
- * Not offered on packed contexts (each a later step): the other opt-in heads (zero-shot bank, gallery), the pooled (cls + mean) head; of the
+ * The cls + mean head on a pack (options.pool_head = VITX_PACK_POOL_CLS_MEAN, 2): a packed context of a VITX_POOL_CLS_MEAN file (DINOv2 with its linear
+ * classifier).  pool_head = 0 stays the default and keeps refusing such a file (VITX_ERR_UNSUPPORTED); pool_head = 2 on a file with another head, like
+ * pool_head = 1 on one, is VITX_ERR_ARG.  Such a context is a class-token pack in everything but its head: registers, `rope`, `glu` files, u8 sources,
+ * attention maps, the dense and the depth head work unchanged.  After the last layer TWO launches (csrc/features_packed.hip) stand in place of the
+ * class-row gather and write the head operand Z [n][2 D] = RNE(F[row0[i]]) | RNE(mean_i), F the f32 final-norm row (vitx_op_layernorm_f32's bits); the
+ * head GEMM then runs with K = 2 D: one launch more than a class-token pack, counted by vitx_pack_launches.  The class half has launch_pool_rows' bits,
+ * those of a class-token pack.  The mean has THE PACK'S OWN summation order, fixed by D alone:
+ *   - an image's patch rows are cut into chunks of R = 128 consecutive rows from its own first patch row (vitx_pack_mean_chunks: pc0[i] = sum_(j < i)
+ *     ceil((N_j - T) / R), the table a workgroup searches for its image; it rides in the call's one table upload);
+ *   - in a chunk, wave w of W (16 up to D = 768, 8 above; a function of D only) adds rows w, w + W, w + 2 W, .. in ascending order into per-column f32
+ *     sums; the W partial sums are added in wave order, ((p_0 + p_1) + p_2) + ..;
+ *   - the chunk sums of an image are added in ascending chunk order and divided ONCE by N_i - T: mean_i.  RNE(mean_i) is the operand's second half; with
+ *     VITX_FEAT_MEAN on, vitx_pack_feat_read_mean returns mean_i (VITX_FEAT_L2: divided by its norm, behind the rounding) from the same registers, so
+ *     RNE(feature) == the operand bit for bit, as on an image context.
+ * No atomics: an image's cls, mean, Z, logits and probabilities are a function of its own rows, N_i, T and D -- the same bits alone, at any position
+ * in a pack, beside NaN neighbours.  The mean is NOT bit-equal to an image context's VITX_FEAT_MEAN (one workgroup per image there, another order); both
+ * lie within the f32 bound of a fixed-order sum.  The scratch (max_tokens / 128 + max_images chunk rows of D floats) is allocated at creation with
+ * pool_head = 2, else by the first vitx_pack_feat_enable with VITX_FEAT_MEAN, and counted (turning the flag off keeps both buffers, allocated and counted,
+ * as the other feature buffers are kept; only the chunk table leaves); with VITX_FEAT_MEAN off and pool_head != 2 nothing is
+ * launched or allocated.  On a pool_head = 0 pack VITX_FEAT_MEAN costs the same two launches behind the class softmax.
+ *   vitx_pack_mean_chunks      host only: pc0 [n + 1] (or NULL) from row0 [n + 1] and T; *chunk_rows = R, *waves = W of hidden size D (each may be NULL; D
+ *                              is read only for waves: VITX_ERR_UNSUPPORTED outside the LayerNorm widths).  VITX_ERR_ARG: a null row0, n <= 0, T < 0, an
+ *                              image with N_i <= T.
+ *   vitx_op_feat_pool_packed   the two launches on the caller's buffers: d_x [rows][D] f32, d_row0 device int32 [n + 1] -> d_cls [n][D] f32, d_mean [n][D]
+ *                              f32, d_z [n rounded up to 8][2 D] in dtype (rows n .. written as zeros); each may be NULL, not all; flags 0 or
+ *                              VITX_FEAT_L2 (cls and mean divided by their norm, d_z unchanged).  TEST entry point: it reads d_row0 back, builds and
+ *                              uploads the chunk table, allocates the scratch, runs on the null stream and returns after synchronising.  VITX_ERR_ARG: a
+ *                              NULL or misaligned (16 bytes) pointer, n <= 0, T < 1 with d_cls or d_z (T = 0: the mean alone), an image with N_i <= T
+ *                              while d_mean or d_z is asked for (d_cls alone reads no patch row); VITX_ERR_UNSUPPORTED: a D outside the LayerNorm widths.
+ *   vitx_op_feat_pool_packed_tables   the same launches on tables and a scratch the caller built: only enqueues, on the null stream; what
+ *                              tools/pack_mean_cost.py times.
+ * Measured (profiles/pack_mean_cost.txt; tools/pack_mean_cost.py, D 768, 7 interleaved rounds): on a uniform 256 x 197 pack the two launches take 42 us
+ * against 34 us for the class-row gather and vitx_op_features (slower, x1.24); on one 4001-row image beside 200 of 197 rows 61 us against 460 us.  The
+ * expectation that the skewed pack costs no more per row than a uniform one is NOT met (1.41 against 0.92 ns per row); the cause was not profiled.
+ * Not measured: whether two rows in flight per wave is the best depth; the combine launch's cost at many chunks per image; the whole forward of a
+ * pool_head = 2 pack against a class-token pack.
+ * Not offered on packed contexts (each a later step): the other opt-in heads (zero-shot bank, gallery); of the
  * attention-pooling head: attention maps, the dense and the depth head, VITX_FEAT_MEAN, more than 16 heads, and image contexts of such files away from
  * the file's own shape; the F16 parity planes, LayerNorm fusion and sub-batch streams, a packed patch-embedding kernel, vitx_group_*;
  * of the attention: a kernel id that forces the staged kernel of head dims 72 .. 128 (AUTO runs it; the ids stay 0 .. 2), staging at head dims 8 .. 56;
@@ -1377,6 +1415,7 @@ typedef struct vitx_pack vitx_pack;
 #define VITX_PACK_ATTN_GENERIC 1
 #define VITX_PACK_ATTN_STAGED 2
 #define VITX_PACK_POOL_MAP 1
+#define VITX_PACK_POOL_CLS_MEAN 2
 typedef struct { int pos_interp, max_grids, attn_kernel, pool_head, reserved[4]; } vitx_pack_options;
 int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_images, int dtype, const vitx_pack_options *opt, vitx_pack **out);
 void vitx_pack_free(vitx_pack *p);
@@ -1387,8 +1426,17 @@ int vitx_pack_check(const vitx_model *m, const int32_t *shapes /* [n][2] = h, w 
 int vitx_pack_distinct_grids(const vitx_model *m, const int32_t *shapes, int n);
 int vitx_pack_forward(vitx_pack *p, const float *imgs, const int32_t *shapes, int n, float *probs, float *logits /* or NULL */);
 int vitx_pack_forward_device(vitx_pack *p, const void *d_imgs, const int32_t *shapes /* host */, int n, void *d_probs, void *d_logits, void *stream);
-int vitx_pack_feat_enable(vitx_pack *p, int flags /* VITX_FEAT_CLS | VITX_FEAT_TOKENS, 0 = off */);
+int vitx_pack_feat_enable(vitx_pack *p, int flags /* VITX_FEAT_CLS | VITX_FEAT_TOKENS | VITX_FEAT_MEAN (| VITX_FEAT_L2), 0 = off */);
 int vitx_pack_feat_read(vitx_pack *p, float *cls /* [n][D] or NULL */, float *tokens /* [sum gh_i gw_i][D], images end to end, or NULL */);
+int vitx_pack_feat_read_mean(vitx_pack *p, float *mean /* [n][D] */);
+/* the cls + mean head on a pack (pool_head = VITX_PACK_POOL_CLS_MEAN) and VITX_FEAT_MEAN: the chunk table of the mean's first launch, and the two launches */
+int vitx_pack_mean_chunks(const int32_t *row0 /* host [n + 1] */, int n, int T, int D, int32_t *pc0 /* [n + 1] or NULL */, int *chunk_rows, int *waves);
+int vitx_op_feat_pool_packed(int dtype, const void *d_x /* [rows][D] f32 */, const void *d_row0 /* device int32 [n + 1] */, int n, int T, int D, const void *d_w,
+                             const void *d_b, float eps, void *d_cls, void *d_mean, void *d_z, int flags);
+/* the same two launches on device tables (d_pc0 from vitx_pack_mean_chunks, chunks = pc0[n]) and a partial scratch [chunks][D] f32 the caller built and vouches
+ * for; d_z holds m_pad >= n rows; null stream, only enqueues */
+int vitx_op_feat_pool_packed_tables(int dtype, const void *d_x, const void *d_row0, const void *d_pc0, int n, int chunks, int T, int D, const void *d_w, const void *d_b,
+                                    float eps, void *d_part, void *d_cls, void *d_mean, void *d_z, int m_pad, int flags);
 size_t vitx_pack_scratch_bytes(const vitx_pack *p);        /* device bytes of activation scratch and cached tables held now (weights not counted) */
 int vitx_pack_launches(const vitx_pack *p, int *patch_embed);      /* kernel launches of the last forward call; *patch_embed: the patch embeddings among them */
 int vitx_pack_attn_kernel(const vitx_pack *p);             /* a report: VITX_PACK_ATTN_STAGED = keys staged in LDS per workgroup (head dim 64 or 72 .. 128), else VITX_PACK_ATTN_GENERIC (0 for NULL) */

@@ -38,6 +38,7 @@ NN_LOGITS, NN_EMBED = 0, 1              # vitx_nn_source
 DENSE_SCORE, DENSE_LOGITS = 1, 2        # vitx_dense_flags
 DEPTH_NORM, DEPTH_LOGITS, DEPTH_FINE = 1, 2, 4      # vitx_depth_flags
 PACK_ATTN_AUTO, PACK_ATTN_GENERIC, PACK_ATTN_STAGED = 0, 1, 2      # VITX_PACK_ATTN_*: a packed context's attention kernel (AUTO: staged at head dim 64)
+PACK_POOL_MAP, PACK_POOL_CLS_MEAN = 1, 2      # VITX_PACK_POOL_*: PackContext(pool_head=): the attention-pooling head, the cls + mean head
 POS_BICUBIC, POS_BICUBIC_AA = 0, 1      # vitx_pos_interp: F.interpolate(mode="bicubic") without / with antialias=True (include/vitx.h)
 
 EXPORTS = [
@@ -81,6 +82,7 @@ EXPORTS = [
     "vitx_pack_attn_enable", "vitx_pack_attn_floats", "vitx_pack_attn_read", "vitx_pack_attn_device", "vitx_pack_attn_check",
     "vitx_op_attention_map_packed", "vitx_op_rollout_step_packed", "vitx_op_rollout_row_packed",
     "vitx_pack_pool_chunk_rows", "vitx_pack_pool_chunks", "vitx_op_attention_pool_packed", "vitx_op_attention_pool_packed_tables",
+    "vitx_pack_feat_read_mean", "vitx_pack_mean_chunks", "vitx_op_feat_pool_packed", "vitx_op_feat_pool_packed_tables",
 ]
 
 
@@ -348,6 +350,11 @@ def lib():
                 L.vitx_op_attention_pool_packed.argtypes = [vp, C.POINTER(C.c_int32), vp, vp, C.c_float, vp, vp, ip, ip, ip]
                 L.vitx_op_attention_pool_packed_tables.argtypes = [vp, vp, vp, ip, ip, vp, vp, C.c_float, vp, vp, vp, vp, ip, ip, ip]
             L.vitx_pack_feat_read.argtypes = [vp, fp, fp]
+            if hasattr(L, "vitx_op_feat_pool_packed"):
+                L.vitx_pack_feat_read_mean.argtypes = [vp, fp]
+                L.vitx_pack_mean_chunks.argtypes = [i32p, ip, ip, ip, i32p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+                L.vitx_op_feat_pool_packed.argtypes = [ip, vp, vp, ip, ip, ip, vp, vp, C.c_float, vp, vp, vp, ip]
+                L.vitx_op_feat_pool_packed_tables.argtypes = [ip, vp, vp, vp, ip, ip, ip, ip, vp, vp, C.c_float, vp, vp, vp, vp, ip, ip]
             L.vitx_pack_scratch_bytes.restype = C.c_size_t; L.vitx_pack_scratch_bytes.argtypes = [vp]
             L.vitx_pack_launches.argtypes = [vp, C.POINTER(ip)]
             if hasattr(L, "vitx_pack_attn_kernel"):
@@ -1265,7 +1272,8 @@ class PackContext:
 
     def __init__(self, model: Model, device: int = 0, max_tokens: int = 1024, max_images: int = 16, dtype: int = F16, pos_interp: int = POS_BICUBIC, max_grids: int = 0,
                  attn_kernel: int = PACK_ATTN_AUTO, pool_head=False):
-        """pool_head: True (or 1) for a file with the attention-pooling head (a SigLIP-class file); the default refuses such a file."""
+        """pool_head: True (or 1) for a file with the attention-pooling head (a SigLIP-class file), PACK_POOL_CLS_MEAN (2) for a file with the cls + mean
+        head (DINOv2 with its linear classifier); the default refuses both."""
         self._h = C.c_void_p()
         self.model = model; self.max_tokens = max_tokens; self.max_images = max_images; self.dtype = dtype
         opt = PackOptions(pos_interp=pos_interp, max_grids=max_grids, attn_kernel=attn_kernel, pool_head=int(pool_head))
@@ -1398,10 +1406,20 @@ class PackContext:
         """The device buffer of the maps (vitx_pack_attn_device), image i at float row0[i] * floats-per-token; 0 while off."""
         return int(lib().vitx_pack_attn_device(self._h) or 0)
 
-    def feat_enable(self, cls: bool = True, tokens: bool = False, l2: bool = False) -> None:
-        """Last-layer features of every later forward (vitx_pack_feat_enable); neither: off.  l2 (pool_head contexts): cls divided by its norm."""
-        self._feat = (FEAT_CLS if cls else 0) | (FEAT_TOKENS if tokens else 0) | (FEAT_L2 if l2 else 0)
-        check(lib().vitx_pack_feat_enable(self._h, self._feat), "vitx_pack_feat_enable")
+    def feat_enable(self, cls: bool = True, tokens: bool = False, l2: bool = False, mean: bool = False) -> None:
+        """Last-layer features of every later forward (vitx_pack_feat_enable); none: off.  l2: cls divided by its norm on an attention-pooling context, the
+        mean divided by its norm elsewhere (only with mean).  mean: the mean patch embedding per image (feat_read_mean); not on attention-pooling contexts."""
+        flags = (FEAT_CLS if cls else 0) | (FEAT_TOKENS if tokens else 0) | (FEAT_L2 if l2 else 0) | (FEAT_MEAN if mean else 0)
+        check(lib().vitx_pack_feat_enable(self._h, flags), "vitx_pack_feat_enable")
+        self._feat = flags
+
+    def feat_read_mean(self) -> np.ndarray:
+        """[n, D] f32: the mean of each image's final-norm patch rows in the last forward (vitx_pack_feat_read_mean; feat_enable(mean=True))."""
+        if self._shapes is None:
+            raise VitxError("feat_read_mean: no forward has run")
+        mean = np.empty((len(self._shapes), self.model.hparams.hidden_size), np.float32)
+        check(lib().vitx_pack_feat_read_mean(self._h, mean.ctypes.data_as(C.POINTER(C.c_float))), "vitx_pack_feat_read_mean")
+        return mean
 
     def feat_read(self):
         """(cls [n, D] or None, tokens: a list of per-image [gh_i, gw_i, D] arrays or None) of the last forward."""
@@ -1413,7 +1431,8 @@ class PackContext:
         cls = np.empty((len(grids), D), np.float32) if flags & FEAT_CLS else None
         tok = np.empty((sum(a * b for a, b in grids), D), np.float32) if flags & FEAT_TOKENS else None
         fp = C.POINTER(C.c_float)
-        check(lib().vitx_pack_feat_read(self._h, cls.ctypes.data_as(fp) if cls is not None else None, tok.ctypes.data_as(fp) if tok is not None else None), "vitx_pack_feat_read")
+        if cls is not None or tok is not None or not flags & FEAT_MEAN:      # the mean alone: feat_read_mean
+            check(lib().vitx_pack_feat_read(self._h, cls.ctypes.data_as(fp) if cls is not None else None, tok.ctypes.data_as(fp) if tok is not None else None), "vitx_pack_feat_read")
         if tok is None:
             return cls, None
         out, at = [], 0
@@ -1905,6 +1924,23 @@ def op_attention_pool_packed(d_x: int, row0, d_ln_w: int, d_ln_b: int, eps: floa
     (row0: host [n + 1]) -> d_M [n, H, D] f32."""
     r = np.ascontiguousarray(row0, np.int32).ravel()
     check(lib().vitx_op_attention_pool_packed(d_x, r.ctypes.data_as(C.POINTER(C.c_int32)), d_ln_w, d_ln_b, eps, d_u, d_M, r.size - 1, D, H), "vitx_op_attention_pool_packed")
+
+
+def pack_mean_chunks(row0, T: int, D: int = 0):
+    """vitx_pack_mean_chunks (host only): (R, W, pc0) -- the chunk size of the packed mean's first launch, its waves per workgroup at hidden size D (None
+    for D = 0) and the running count of ceil((N_i - T) / R), [n + 1]."""
+    r = np.ascontiguousarray(row0, np.int32).ravel()
+    pc0 = np.empty(r.size, np.int32)
+    R, W = C.c_int(0), C.c_int(0)
+    i32p = C.POINTER(C.c_int32)
+    check(lib().vitx_pack_mean_chunks(r.ctypes.data_as(i32p) if r.size else None, r.size - 1, T, D, pc0.ctypes.data_as(i32p), C.byref(R), C.byref(W) if D else None), "vitx_pack_mean_chunks")
+    return R.value, (W.value if D else None), pc0
+
+
+def op_feat_pool_packed(dtype: int, d_x: int, d_row0: int, n: int, T: int, D: int, d_w: int, d_b: int, eps: float, d_cls: int, d_mean: int, d_z: int, l2: bool = False) -> None:
+    """vitx_op_feat_pool_packed (test entry point; synchronous): the class rows and mean patch embeddings of a pack, d_x [rows, D] f32 with image i = rows
+    row0[i] .. row0[i + 1] - 1 (d_row0: device int32 [n + 1]) -> d_cls [n, D] f32, d_mean [n, D] f32, d_z [n rounded up to 8, 2 D] in dtype (0: not asked for)."""
+    check(lib().vitx_op_feat_pool_packed(dtype, d_x, d_row0, n, T, D, d_w, d_b, eps, d_cls or None, d_mean or None, d_z or None, FEAT_L2 if l2 else 0), "vitx_op_feat_pool_packed")
 
 
 def op_rope(dtype: int, d_qkv: int, d_cos: int, d_sin: int, n_img: int, N: int, prefix: int, D: int, H: int, lo_off: int = 0, stream: int = 0) -> None:

@@ -343,7 +343,9 @@ def main(argv: List[str] | None = None) -> int:
             pool_head = model.num_prefix == 0 and model.head_pool == binding.POOL_MAP
             if a.embed and not pool_head:
                 raise binding.VitxError("--pack --embed needs a file with the attention-pooling head")
-            ctx = binding.PackContext(model, device=a.device, max_tokens=tokens, max_images=len(files), dtype=dt, pos_interp=geometry["pos_interp"], pool_head=pool_head)
+            # a file whose classifier reads cls | mean (DINOv2 with its linear classifier): the packed cls + mean head
+            pack_head = binding.PACK_POOL_CLS_MEAN if model.head_pool == binding.POOL_CLS_MEAN else int(pool_head)
+            ctx = binding.PackContext(model, device=a.device, max_tokens=tokens, max_images=len(files), dtype=dt, pos_interp=geometry["pos_interp"], pool_head=pack_head)
             if a.embed:
                 ctx.feat_enable(cls=True, l2=a.embed_l2)
             if dense:

@@ -230,6 +230,22 @@ bool pool_pack_chunks(const int32_t *rows, int n, int32_t *chunk0);
 bool attention_pool_packed_fits(int D);
 hipError_t launch_attention_pool_packed(const float *x, const int *row0, const int *chunk0, int n, int chunks, const float *w, const float *b, float eps, const float *u,
                                         float *part, float *M, void *m16, int dtype, int D, int H, hipStream_t stream);
+// The class row and the mean patch embedding of every image of a PACK (features_packed.hip; include/vitx.h "packed batches", pool_head =
+// VITX_PACK_POOL_CLS_MEAN and VITX_FEAT_MEAN): image i = rows row0[i] .. row0[i + 1] - 1 of x ([rows][D] f32, dense), its first T rows the class and
+// register rows; F = launch_features' F.  Two launches: the part kernel, one workgroup of feat_pool_waves(D) waves per (image, chunk of kFeatPoolChunkRows
+// PATCH rows), writes the chunk's column sums to part [chunks][D] f32 and, in an image's chunk 0, z[i][0 .. D) = RNE(F[0]) and cls[i] = F[0]; the combine
+// kernel adds an image's chunks in ascending order, divides once by N_i - T and writes z[i][D .. 2 D) = RNE(mean), mean[i] [D] f32 and zeros to rows
+// n .. m_pad - 1 of z ([m_pad][2 D] in `dtype`).  l2: cls and mean (not z) divided by their norm.  cls, mean, z: each may be nullptr, not all; with cls
+// alone no patch row is read and nothing else is launched.  No atomics; an image's outputs do not depend on its position or neighbours.
+//   feat_pool_chunks   host only, the one place the table is built: pc0 [n + 1] (may be NULL) = the running count of ceil((N_i - T) / kFeatPoolChunkRows);
+//                      false for a null row0, n <= 0, T < 0, an image without a patch row or more than 2^31 - 1 chunks
+//   launch_feat_pool_packed   row0 and pc0 on the device, chunks = pc0[n]: the caller built the tables.  Every width of VITX_LN_WIDTHS; T >= 1 with cls or z;
+//                      hipErrorInvalidValue otherwise
+constexpr int kFeatPoolChunkRows = 128, kFeatPoolMaxD = 2048;
+constexpr int feat_pool_waves(int D) { return D <= 768 ? 16 : 8; }
+bool feat_pool_chunks(const int32_t *row0, int n, int T, int32_t *pc0);
+hipError_t launch_feat_pool_packed(const float *x, const int *row0, const int *pc0, int n, int chunks, int T, const float *w, const float *b, float eps, float *part, float *cls,
+                                   float *mean, void *z, int dtype, int m_pad, int D, bool l2, hipStream_t stream);
 // The end of the pooled tail: e [n_img][D] f32 -> z [n_img][D] = RNE(e) in `dtype` (the head GEMM's operand) and, cls != nullptr, the feature
 // cls[i * out_img_stride ..] = e[i] (l2: divided by its norm, VITX_FEAT_L2's arithmetic).  One wave per image.
 hipError_t launch_pool_embed(const float *e, void *z, int dtype, float *cls, long out_img_stride, bool l2, int n_img, int D, hipStream_t stream);

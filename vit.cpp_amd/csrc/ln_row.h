@@ -4,6 +4,8 @@
 // head (attention_pool.hip).  A row gets the same bits whichever of them produced it (-ffp-contract=off, as for every kernel of the library);
 // the epilogue of the LayerNorm-fusing GEMM, which works from accumulators, follows the same definition in its own text (gemm_pp.hip).
 #pragma once
+#include <type_traits>
+
 #include "device_common.h"
 
 namespace vitx {
@@ -51,11 +53,16 @@ __device__ __forceinline__ void ln_combine(const float (&mc)[LN_MAX_TILES], cons
 
 // The values of one row of NT * 256 columns (v[c] = columns c * 256 + 4 lane ..) and their statistics, the tiled definition above: lane l holds
 // piece l of each tile (w = l >> 4, j = (l >> 3) & 1, k = l & 7): one fully coalesced 1 KiB load per tile.
+// The load is a function of its own (ln_tiled_load), so that a kernel can issue the loads of several rows before the first row's statistics
+// (features_packed.hip); ln_tiled_stats is load + ln_tiled_stats_of, as it always was.
 template <int NT>
-__device__ __forceinline__ void ln_tiled_stats(const float *__restrict__ xr, float eps, int lane, f32x4 (&v)[NT], float &mean, float &rstd) {
-    float mc[LN_MAX_TILES] = {0.0f, 0.0f, 0.0f, 0.0f}, m2[LN_MAX_TILES] = {0.0f, 0.0f, 0.0f, 0.0f};
+__device__ __forceinline__ void ln_tiled_load(const float *__restrict__ xr, int lane, f32x4 (&v)[NT]) {
 #pragma unroll
     for (int c = 0; c < NT; ++c) v[c] = *(const f32x4 *)(xr + c * 256 + lane * 4);
+}
+template <int NT>
+__device__ __forceinline__ void ln_tiled_stats_of(float eps, int lane, const f32x4 (&v)[NT], float &mean, float &rstd) {
+    float mc[LN_MAX_TILES] = {0.0f, 0.0f, 0.0f, 0.0f}, m2[LN_MAX_TILES] = {0.0f, 0.0f, 0.0f, 0.0f};
     auto tile_total = [&](float a) {       // a = this lane's piece value -> S_c (uniform)
         const float s = a + __shfl_xor(a, 8);                      // s(w, k) = a(w, 0, k) + a(w, 1, k)
         const float p = ln_sum8(s);                                // P(w), the same bits in the 16 lanes of wave column w
@@ -69,22 +76,33 @@ __device__ __forceinline__ void ln_tiled_stats(const float *__restrict__ xr, flo
     }
     ln_combine(mc, m2, NT, NT * 256, eps, mean, rstd);
 }
+template <int NT>
+__device__ __forceinline__ void ln_tiled_stats(const float *__restrict__ xr, float eps, int lane, f32x4 (&v)[NT], float &mean, float &rstd) {
+    ln_tiled_load<NT>(xr, lane, v);
+    ln_tiled_stats_of<NT>(eps, lane, v, mean, rstd);
+}
 
 // Hidden sizes the tiled definition does not cover (launch_layernorm): lane l holds VEC consecutive columns idx = (i * 64 + l) * VEC of
 // each of NV pieces; sum and sum of squared deviations over the whole wave.  Returns v[i][j] = x - mean and scale = 1 / sqrt(var + eps).
+// As for the tiled widths, the load stands apart (ln_flat_load): ln_flat_stats is load + ln_flat_stats_of, the sums in the order they always had.
 template <int VEC, int NV>
-__device__ __forceinline__ void ln_flat_stats(const float *__restrict__ xr, float eps, int lane, float (&v)[NV][VEC], float &scale) {
-    constexpr int D = 64 * VEC * NV;
-    float sum = 0.0f;
+__device__ __forceinline__ void ln_flat_load(const float *__restrict__ xr, int lane, float (&v)[NV][VEC]) {
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         const int idx = (i * 64 + lane) * VEC;
         if constexpr (VEC == 4) { const float4 t = *(const float4 *)(xr + idx); v[i][0] = t.x; v[i][1] = t.y; v[i][2] = t.z; v[i][3] = t.w; }
         else if constexpr (VEC == 2) { const float2 t = *(const float2 *)(xr + idx); v[i][0] = t.x; v[i][1] = t.y; }
         else v[i][0] = xr[idx];
+    }
+}
+template <int VEC, int NV>
+__device__ __forceinline__ void ln_flat_stats_of(float eps, float (&v)[NV][VEC], float &scale) {
+    constexpr int D = 64 * VEC * NV;
+    float sum = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
 #pragma unroll
         for (int j = 0; j < VEC; ++j) sum += v[i][j];
-    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
     const float mean = sum / (float)D;
@@ -97,6 +115,11 @@ __device__ __forceinline__ void ln_flat_stats(const float *__restrict__ xr, floa
     for (int o = 32; o > 0; o >>= 1) sum2 += __shfl_xor(sum2, o);
     scale = 1.0f / sqrtf(sum2 / (float)D + eps);
 }
+template <int VEC, int NV>
+__device__ __forceinline__ void ln_flat_stats(const float *__restrict__ xr, float eps, int lane, float (&v)[NV][VEC], float &scale) {
+    ln_flat_load<VEC, NV>(xr, lane, v);
+    ln_flat_stats_of<VEC, NV>(eps, v, scale);
+}
 
 // One row of D = 64 VEC NV columns (a row of VITX_LN_WIDTHS, kernels.h) by one wave.  Lane l holds columns c * 256 + 4 l .. + 3 of tile c (tiled
 // widths: VEC 4, up to LN_MAX_TILES pieces) or (i * 64 + l) * VEC .. of piece i (flat widths): 16-, 8- or 4-byte loads and stores.
@@ -106,12 +129,18 @@ template <int VEC, int NV> struct LnRow {
     // THE output arithmetic, the only place it is written: sink(i, idx, o) for every piece i in turn, idx = col(i), o[j] = F at column idx + j of the
     // row xr, f32, unrounded.  The whole row is read (its statistics) before the first call, so a sink may store over xr; a sink that stores its
     // piece at once keeps one piece of F live, not the row (the widest one-wave-per-row kernels lose an occupancy step otherwise).
+    // A row as it was loaded, before any arithmetic: one f32x4 per tile (tiled widths) or the pieces' columns (flat widths).  load() only issues the
+    // loads; each_loaded() is everything behind them, so a kernel may load several rows first (features_packed.hip).  each() = load() + each_loaded().
+    typedef std::conditional_t<kTiled, f32x4[NV], float[NV][VEC]> Raw;
+    static __device__ __forceinline__ void load(const float *__restrict__ xr, int lane, Raw &r) {
+        if constexpr (kTiled) ln_tiled_load<NV>(xr, lane, r);
+        else ln_flat_load<VEC, NV>(xr, lane, r);
+    }
     template <typename S>
-    static __device__ __forceinline__ void each(const float *__restrict__ xr, const float *__restrict__ w, const float *__restrict__ b, float eps, int lane, S &&sink) {
+    static __device__ __forceinline__ void each_loaded(Raw &v, const float *__restrict__ w, const float *__restrict__ b, float eps, int lane, S &&sink) {
         if constexpr (kTiled) {
-            f32x4 v[NV];
             float mean, rstd;
-            ln_tiled_stats<NV>(xr, eps, lane, v, mean, rstd);
+            ln_tiled_stats_of<NV>(eps, lane, v, mean, rstd);
 #pragma unroll
             for (int c = 0; c < NV; ++c) {
                 const int idx = col(c, lane);
@@ -122,9 +151,8 @@ template <int VEC, int NV> struct LnRow {
                 sink(c, idx, o);
             }
         } else {
-            float v[NV][VEC];                                        // x - mean
-            float scale;
-            ln_flat_stats<VEC, NV>(xr, eps, lane, v, scale);
+            float scale;                                             // v becomes x - mean
+            ln_flat_stats_of<VEC, NV>(eps, v, scale);
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
                 const int idx = col(i, lane);
@@ -135,9 +163,21 @@ template <int VEC, int NV> struct LnRow {
             }
         }
     }
+    template <typename S>
+    static __device__ __forceinline__ void each(const float *__restrict__ xr, const float *__restrict__ w, const float *__restrict__ b, float eps, int lane, S &&sink) {
+        Raw v;
+        load(xr, lane, v);
+        each_loaded(v, w, b, eps, lane, sink);
+    }
     // the whole row in registers: f[i][j] = F at column col(i) + j
     static __device__ __forceinline__ void norm(const float *__restrict__ xr, const float *__restrict__ w, const float *__restrict__ b, float eps, int lane, float (&f)[NV][VEC]) {
         each(xr, w, b, eps, lane, [&](int i, int, const float (&o)[VEC]) {
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) f[i][j] = o[j];
+        });
+    }
+    static __device__ __forceinline__ void norm_loaded(Raw &v, const float *__restrict__ w, const float *__restrict__ b, float eps, int lane, float (&f)[NV][VEC]) {
+        each_loaded(v, w, b, eps, lane, [&](int i, int, const float (&o)[VEC]) {
 #pragma unroll
             for (int j = 0; j < VEC; ++j) f[i][j] = o[j];
         });

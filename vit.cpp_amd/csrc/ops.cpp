@@ -412,6 +412,63 @@ int vitx_op_attention_pool_packed_tables(const void *d_x, const void *d_row0, co
     return op_rc(name, launch_attention_pool_packed((const float *)d_x, (const int *)d_row0, (const int *)d_chunk0, n, chunks, (const float *)d_ln_w, (const float *)d_ln_b, eps,
                                                     (const float *)d_u, (float *)d_part, (float *)d_M, d_m16, dtype, D, H, nullptr), VITX_ERR_UNSUPPORTED);
 }
+// The class rows and mean patch embeddings of a pack (include/vitx.h "packed batches", pool_head = VITX_PACK_POOL_CLS_MEAN).  vitx_pack_mean_chunks: host
+// only.  vitx_op_feat_pool_packed: a TEST entry point -- it reads d_row0 back, builds and uploads the chunk table, allocates the partial scratch, launches on
+// the null stream, waits and frees.  Every argument check comes before the first device call.
+int vitx_pack_mean_chunks(const int32_t *row0, int n, int T, int D, int32_t *pc0, int *chunk_rows, int *waves) {
+    if (waves && !layernorm_supports(D)) { set_error("vitx_pack_mean_chunks: hidden size %d has no LayerNorm instantiation", D); return VITX_ERR_UNSUPPORTED; }
+    if (!feat_pool_chunks(row0, n, T, pc0)) {
+        set_error("vitx_pack_mean_chunks: row0 [n + 1] must hold n >= 1 images of more than T = %d rows each that make at most 2^31 - 1 chunks of %d rows", T, kFeatPoolChunkRows);
+        return VITX_ERR_ARG;
+    }
+    if (chunk_rows) *chunk_rows = kFeatPoolChunkRows;
+    if (waves) *waves = feat_pool_waves(D);
+    return VITX_OK;
+}
+int vitx_op_feat_pool_packed(int dtype, const void *d_x, const void *d_row0, int n, int T, int D, const void *d_w, const void *d_b, float eps, void *d_cls, void *d_mean,
+                             void *d_z, int flags) {
+    const char *name = "vitx_op_feat_pool_packed";
+    if (!d_x || !d_row0 || !d_w || !d_b || (!d_cls && !d_mean && !d_z) || n <= 0 || T < 0 || (T == 0 && (d_cls || d_z)) || D <= 0 || (flags & ~VITX_FEAT_L2) ||
+        (dtype != VITX_F16 && dtype != VITX_BF16)) {
+        set_error("%s: invalid argument (n >= 1, T >= 1 -- T >= 0 for the mean alone --, flags 0 or VITX_FEAT_L2, VITX_F16 or VITX_BF16)", name);
+        return VITX_ERR_ARG;
+    }
+    for (const void *p : {d_x, d_w, d_b, (const void *)d_cls, (const void *)d_mean, (const void *)d_z})
+        if ((uintptr_t)p % 16) { set_error("%s: pointers must be 16-byte aligned", name); return VITX_ERR_ARG; }
+    if ((uintptr_t)d_row0 % 4) { set_error("%s: d_row0 must be 4-byte aligned", name); return VITX_ERR_ARG; }
+    if (!layernorm_supports(D)) { set_error("%s: hidden size %d has no LayerNorm instantiation", name, D); return VITX_ERR_UNSUPPORTED; }
+    if (!tuning_for_device(-1)) { set_error("%s: the device could not be opened", name); return VITX_ERR_HIP; }
+    std::vector<int32_t> row0((size_t)n + 1), pc0((size_t)n + 1);
+    HIP_TRY(hipMemcpy(row0.data(), d_row0, row0.size() * 4, hipMemcpyDeviceToHost));
+    // the class rows alone read no patch row: any image of at least one row will do, and the grid is cut as if every row were a patch row
+    const bool patches = d_mean || d_z;
+    if (row0[0] < 0 || !feat_pool_chunks(row0.data(), n, patches ? T : 0, pc0.data())) {
+        set_error("%s: with the mean asked for every image needs at least one patch row behind its T = %d prefix rows (row0 ascending from >= 0)", name, T);
+        return VITX_ERR_ARG;
+    }
+    const int chunks = pc0[n];
+    int *d_pc0 = nullptr;
+    float *d_part = nullptr;
+    hipError_t e = hipMalloc((void **)&d_pc0, pc0.size() * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_part, (size_t)chunks * D * 4);
+    if (e == hipSuccess) e = hipMemcpy(d_pc0, pc0.data(), pc0.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_feat_pool_packed((const float *)d_x, (const int *)d_row0, d_pc0, n, chunks, T, (const float *)d_w, (const float *)d_b, eps, d_part, (float *)d_cls,
+                                                     (float *)d_mean, d_z, dtype, round_up(n, 8), D, (flags & VITX_FEAT_L2) != 0, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    (void)hipFree(d_pc0); (void)hipFree(d_part);
+    return op_rc(name, e, VITX_ERR_UNSUPPORTED);
+}
+// the same two launches on tables and a partial scratch the caller built and vouches for (d_pc0 from vitx_pack_mean_chunks, d_part [chunks][D] f32, d_z of m_pad
+// rows): null stream, only enqueues -- what a packed context does per forward, and what tools/pack_mean_cost.py times
+int vitx_op_feat_pool_packed_tables(int dtype, const void *d_x, const void *d_row0, const void *d_pc0, int n, int chunks, int T, int D, const void *d_w, const void *d_b, float eps,
+                                    void *d_part, void *d_cls, void *d_mean, void *d_z, int m_pad, int flags) {
+    const char *name = "vitx_op_feat_pool_packed_tables";
+    if (!d_x || !d_row0 || !d_pc0 || !d_w || !d_b || !d_part || (!d_cls && !d_mean && !d_z) || n <= 0 || chunks < n || T < 0 || (flags & ~VITX_FEAT_L2) ||
+        (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("%s: invalid argument", name); return VITX_ERR_ARG; }
+    if (!tuning_for_device(-1)) { set_error("%s: the device could not be opened", name); return VITX_ERR_HIP; }
+    return op_rc(name, launch_feat_pool_packed((const float *)d_x, (const int *)d_row0, (const int *)d_pc0, n, chunks, T, (const float *)d_w, (const float *)d_b, eps, (float *)d_part,
+                                               (float *)d_cls, (float *)d_mean, d_z, dtype, m_pad, D, (flags & VITX_FEAT_L2) != 0, nullptr), VITX_ERR_UNSUPPORTED);
+}
 // The map kernels on their own (the parity tests): d_cls [n_img][H][N] class-token rows, d_mean [n_img][N][N] mean_h A_h (either may be NULL).
 int vitx_op_attention_map(int dtype, const void *d_qkv, long lo_off, void *d_cls, void *d_mean, int n_img, int N, int D, int H, void *stream) {
     if (!d_qkv || (!d_cls && !d_mean) || n_img <= 0 || N <= 0 || D <= 0 || H <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_attention_map: invalid argument"); return VITX_ERR_ARG; }

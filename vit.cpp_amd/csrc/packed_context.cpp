@@ -158,15 +158,17 @@ int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_im
     int attn_kernel = opt ? opt->attn_kernel : VITX_PACK_ATTN_AUTO;
     if (attn_kernel < VITX_PACK_ATTN_AUTO || attn_kernel > VITX_PACK_ATTN_STAGED) { set_error("vitx_pack_create: unknown attn_kernel %d (0 auto, 1 generic, 2 staged)", attn_kernel); return VITX_ERR_ARG; }
     const int pool_head = opt ? opt->pool_head : 0;
-    if (pool_head != 0 && pool_head != VITX_PACK_POOL_MAP) { set_error("vitx_pack_create: unknown pool_head %d (0 the class-token head, 1 the attention-pooling head)", pool_head); return VITX_ERR_ARG; }
-    if (pool_head && m->head_pool != VITX_POOL_MAP) { set_error("vitx_pack_create: pool_head = 1 takes a file with the attention-pooling head; this file has another head"); return VITX_ERR_ARG; }
+    if (pool_head != 0 && pool_head != VITX_PACK_POOL_MAP && pool_head != VITX_PACK_POOL_CLS_MEAN) { set_error("vitx_pack_create: unknown pool_head %d (0 the class-token head, 1 the attention-pooling head, 2 the cls + mean head)", pool_head); return VITX_ERR_ARG; }
+    const bool pool_map = pool_head == VITX_PACK_POOL_MAP, pool_cm = pool_head == VITX_PACK_POOL_CLS_MEAN;
+    if (pool_map && m->head_pool != VITX_POOL_MAP) { set_error("vitx_pack_create: pool_head = 1 takes a file with the attention-pooling head; this file has another head"); return VITX_ERR_ARG; }
+    if (pool_cm && m->head_pool != VITX_POOL_CLS_MEAN) { set_error("vitx_pack_create: pool_head = 2 takes a file with the pooled (cls + mean) head; this file has another head"); return VITX_ERR_ARG; }
     // every refusal before the first device call: nothing is launched after one
     if (m->in_chans == 1) { set_error("vitx_pack_create: a ViTSTR (one-channel) model takes no packed context"); return VITX_ERR_UNSUPPORTED; }
     if (m->head_pool != VITX_POOL_CLS && !pool_head) { set_error("vitx_pack_create: packed contexts take the class-token head only, not the pooled (cls + mean) or the attention-pooling head"); return VITX_ERR_UNSUPPORTED; }
     const vitx_hparams &hp = m->hp;
     const int D = hp.hidden_size, H = hp.num_attention_heads, F1 = m->mlp_fc1_rows();
-    if (pool_head && H > kPoolPackMaxHeads) { set_error("vitx_pack_create: the packed attention-pooling kernel takes at most %d heads (this model: %d)", kPoolPackMaxHeads, H); return VITX_ERR_UNSUPPORTED; }
-    if (pool_head && !attention_pool_packed_fits(D)) { set_error("vitx_pack_create: the staging tiles of hidden size %d do not fit the packed attention-pooling kernel's LDS", D); return VITX_ERR_UNSUPPORTED; }
+    if (pool_map && H > kPoolPackMaxHeads) { set_error("vitx_pack_create: the packed attention-pooling kernel takes at most %d heads (this model: %d)", kPoolPackMaxHeads, H); return VITX_ERR_UNSUPPORTED; }
+    if (pool_map && !attention_pool_packed_fits(D)) { set_error("vitx_pack_create: the staging tiles of hidden size %d do not fit the packed attention-pooling kernel's LDS", D); return VITX_ERR_UNSUPPORTED; }
     if (!attention_packed_supports(D, H)) { set_error("vitx_pack_create: attention needs a head_dim that is a multiple of 8 up to 128 (this model: %d / %d)", D, H); return VITX_ERR_UNSUPPORTED; }
     PackedAttn attn;
     if (resolve_attention_packed(attn_kernel, D, H, &attn) != PACKED_ATTN_OK) { set_error("vitx_pack_create: the staged attention kernel needs head_dim 64 (this model: %d / %d)", D, H); return VITX_ERR_UNSUPPORTED; }
@@ -181,7 +183,7 @@ int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_im
     if (!p) return VITX_ERR_NOMEM;
     p->model = m; p->device = device; p->dtype = dtype; p->tune = tune;
     p->D = D; p->L = hp.num_hidden_layers; p->H = H; p->C = hp.num_classes; p->C_pad = head_cols_pad(m); p->P = hp.patch_size;
-    p->pool_map = pool_head == VITX_PACK_POOL_MAP;
+    p->pool_map = pool_map; p->pool_cm = pool_cm;
     p->nreg = m->num_registers; p->Tp = p->pool_map ? 0 : 1 + p->nreg; p->g_in = hp.img_size / hp.patch_size; p->Kpe_pad = patch_k_pad(m);
     p->glu = m->glu_kind != VITX_GLU_NONE; p->F = m->mlp_hidden(); p->F1 = F1; p->rope = m->rope_kind != VITX_ROPE_NONE;
     p->fc1_epi = p->glu ? EPI_BIAS : act_epi(m->activation); p->eps = hp.eps;
@@ -203,7 +205,11 @@ int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_im
     if ((rc = dmalloc(&p->QKV, Mp * 3 * D * 2))) return rc;
     if ((rc = dmalloc(&p->Hbuf, Mp * (size_t)F1 * 2))) return rc;
     if (p->glu && (rc = dmalloc(&p->Hg, Mp * (size_t)p->F * 2))) return rc;
-    if ((rc = dmalloc(&p->Z, Bp * D * 2))) return rc;
+    if ((rc = dmalloc(&p->Z, Bp * D * (pool_cm ? 4 : 2)))) return rc;
+    if (pool_cm) {       // the mean's part scratch (every image adds at most one partly filled chunk)
+        const size_t bytes = ((size_t)max_tokens / kFeatPoolChunkRows + max_images) * D * 4;
+        if (!alloc_counted(p->mean_part, bytes, &p->scratch_bytes)) { set_error("vitx_pack_create: cannot allocate the mean's partial sums (%zu bytes)", bytes); return VITX_ERR_NOMEM; }
+    }
     if ((rc = dmalloc((void **)&p->logits, Bp * (size_t)p->C_pad * 4))) return rc;
     if ((rc = dmalloc((void **)&p->probs, (size_t)max_images * p->C * 4))) return rc;
     if ((rc = dmalloc((void **)&p->logits_out, (size_t)max_images * p->C * 4))) return rc;

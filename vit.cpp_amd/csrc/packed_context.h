@@ -6,7 +6,8 @@
 // Four opt-in PARTS bring segment tables and state of a call with them: the dense head, the depth head, u8 sources, attention rollout.  Each is
 // one bit (PackPart), one or two lines of kPackTables, one struct of what its check gives a call (PackDenseCall, PackDepthCall in heads.h,
 // PackU8Call, PackRolloutCall here) and one struct of what its set call holds (PackDense, PackDepth in heads.h, PackU8, PackAttn here).
-// DESIGN.md ("Packed batches", Parts) lists the places a new part is added in.
+// DESIGN.md ("Packed batches", Parts) lists the places a new part is added in.  Two more bits carry one table each and no set call of their own: kPoolMap
+// (the attention-pooling head, from creation) and kFeatPool (the mean patch embedding: the cls + mean head from creation, VITX_FEAT_MEAN while it is on).
 // Internal: callers see the opaque vitx_pack of include/vitx.h.
 #pragma once
 #include <memory>
@@ -15,7 +16,7 @@
 
 using namespace vitx;
 
-enum PackPart : unsigned { kDense = 1u << 0, kDepth = 1u << 1, kU8 = 1u << 2, kRollout = 1u << 3, kPoolMap = 1u << 4 };
+enum PackPart : unsigned { kDense = 1u << 0, kDepth = 1u << 1, kU8 = 1u << 2, kRollout = 1u << 3, kPoolMap = 1u << 4, kFeatPool = 1u << 5 };
 
 // The segment tables of a call, in their order in vitx_pack::tab / host: `per_image` ints per image the context holds (cap = max_images) and `plus`
 // more.  A table of part 0 is always there, another while its part is on.  One buffer, one upload; a new table goes at the end of this list.
@@ -27,12 +28,13 @@ constexpr PackTable kPackTables[] = {
     {kU8, 1, 1}, {kU8, kPpSegInts, 0},                               // ptile0 [cap + 1] | pseg [cap][kPpSegInts]                (pp_pack_tables)
     {kRollout, 1, 1}, {kRollout, 1, 1},                              // rblk0 [cap + 1] | sq0 [cap + 1]                          (attn_pack_tables)
     {kPoolMap, 1, 1},                                                // chunk0 [cap + 1]                                         (pool_pack_chunks)
+    {kFeatPool, 1, 1},                                               // pc0 [cap + 1]                                            (feat_pool_chunks)
 };
 
 struct PackLayout {
     size_t cap;
     unsigned parts;                      // PackPart bits: the parts whose tables the buffer holds
-    enum Table { kRow0, kQb0, kToff, kTile0, kSeg, kFtile0, kOtile0, kDseg, kPtile0, kPseg, kRblk0, kSq0, kChunk0, kTables };
+    enum Table { kRow0, kQb0, kToff, kTile0, kSeg, kFtile0, kOtile0, kDseg, kPtile0, kPseg, kRblk0, kSq0, kChunk0, kPc0, kTables };
     static_assert(sizeof(kPackTables) / sizeof(kPackTables[0]) == kTables, "one name per table");
     // the ints in front of table t: the tables before it whose part is on (a table of a part that is off is placed as if that part alone were on too)
     size_t at(int t) const {
@@ -54,6 +56,7 @@ struct PackLayout {
     size_t rblk0() const { return at(kRblk0); }
     size_t sq0() const { return at(kSq0); }
     size_t chunk0() const { return at(kChunk0); }
+    size_t pc0() const { return at(kPc0); }
     size_t ints() const { return at(kTables); }
 };
 
@@ -82,6 +85,7 @@ struct PackCall {
     PackU8Call u8;                       // with u8 sources declared for the call
     PackRolloutCall roll;                // with attention rollout on
     std::vector<int32_t> chunk0;         // a context of an attention-pooling file: the running chunk count of the pooling launch [n + 1] (pool_pack_chunks)
+    std::vector<int32_t> pc0;            // with the cls + mean head or VITX_FEAT_MEAN on: the running chunk count of the mean's part launch [n + 1] (feat_pool_chunks)
 };
 
 // Attention maps (vitx_pack_attn_enable): the image context's AttnMaps per image of a pack.  Image i's floats of `out` start at row0[i] * fpt: the
@@ -128,6 +132,7 @@ struct vitx_pack {
     int F = 0, F1 = 0;                   // MLP widths: fc2's K and fc1's N (4 D both, or F and 2 F of a `glu` file)
     bool glu = false, rope = false;
     bool pool_map = false;               // options.pool_head: an attention-pooling file -- no prefix rows (Tp = 0), the pooled tail in place of the class rows
+    bool pool_cm = false;                // options.pool_head = VITX_PACK_POOL_CLS_MEAN: Z [Bpad][2 D] = RNE(class row) | RNE(mean of the patch rows), the head's K is 2 D
     int fc1_epi = EPI_BIAS_GELU;
     float eps = 1e-6f;
     int tm = 256, tn = 128;
@@ -141,7 +146,7 @@ struct vitx_pack {
     std::vector<void *> allocs;
     float *X = nullptr;                  // [Mpad][D] f32 residual stream, Mpad = max_tokens rounded up to the GEMMs' row tile
     void *U = nullptr, *QKV = nullptr, *Hbuf = nullptr, *Hg = nullptr;      // [Mpad][D], [Mpad][3 D], [Mpad][F1], [Mpad][F] (glu) operand type
-    void *Z = nullptr;                   // [Bpad][D] operand type: the class rows through the final norm, Bpad = max_images rounded up
+    void *Z = nullptr;                   // [Bpad][D] operand type: the class rows through the final norm, Bpad = max_images rounded up ([Bpad][2 D] with pool_cm)
     float *logits = nullptr, *probs = nullptr;      // [Bpad][C_pad], [max_images][C] f32
     float *logits_out = nullptr;         // [max_images][C] f32: the dense logits of the host entry point
     // pool_map only, allocated at creation: the pooling launch's partial scratch [max_chunks][H][D + 2] f32, then one row per image -- Mp [Bpad][H][D] =
@@ -172,6 +177,11 @@ struct vitx_pack {
     DevMem feat;                         // [max_tokens][D] f32 final-norm rows of the last forward (allocated by vitx_pack_feat_enable)
     int feat_n = 0;                      // images of the last forward with features on (0: none)
     DevMem feat_cls;                     // pool_map with VITX_FEAT_CLS: [max_images][D] f32, the pooled embeddings e of the last forward
+    // the mean patch embedding (features_packed.hip), with pool_cm (allocated at creation) or VITX_FEAT_MEAN (by vitx_pack_feat_enable): the part launch's
+    // scratch [max_tokens / kFeatPoolChunkRows + max_images][D] f32 and, with VITX_FEAT_MEAN, the means of the last forward [max_images][D] f32
+    DevMem mean_part, feat_mean;
+    std::vector<int32_t> pc0;            // PackCall::pc0 of the last call that passed its checks
+    bool mean_on() const { return pool_cm || (feat_flags & VITX_FEAT_MEAN); }
     std::unique_ptr<PackDense> dense;    // vitx_pack_dense_set (null: off); its device memory is its own
     std::unique_ptr<PackDepth> depth;    // vitx_pack_depth_set (null: off); its device memory is its own
     std::unique_ptr<PackU8> u8;          // vitx_pack_u8_set (null: off)
@@ -179,7 +189,7 @@ struct vitx_pack {
     bool rollout() const { return attn && attn->rollout(); }         // the rollout tables are there; class maps alone add no table
     int launches = 0, pe_launches = 0;   // kernel launches of the last forward, and how many of them were patch embeddings
     size_t scratch_bytes = 0;            // device bytes of activation scratch and tables held now
-    unsigned parts() const { return (dense ? kDense : 0u) | (depth ? kDepth : 0u) | (u8 ? kU8 : 0u) | (rollout() ? kRollout : 0u) | (pool_map ? kPoolMap : 0u); }
+    unsigned parts() const { return (dense ? kDense : 0u) | (depth ? kDepth : 0u) | (u8 ? kU8 : 0u) | (rollout() ? kRollout : 0u) | (pool_map ? kPoolMap : 0u) | (mean_on() ? kFeatPool : 0u); }
     PackLayout layout() const { return PackLayout{(size_t)max_images, parts()}; }
     // image i of the last call that passed its checks: its patch rows, and where they start in an output that holds every image's patch rows end to end
     size_t patch_rows(int i) const { return (size_t)(row0[i + 1] - row0[i] - Tp); }

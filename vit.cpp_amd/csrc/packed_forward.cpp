@@ -167,6 +167,10 @@ int check_call(vitx_pack *p, const void *d_imgs, const int32_t *shapes, int n, P
         c->chunk0.resize((size_t)n + 1);
         if (!pool_pack_chunks(rows.data(), n, c->chunk0.data())) { set_error("vitx_pack_forward: the call's images make more than 2^31 - 1 pooling chunks"); return VITX_ERR_ARG; }
     }
+    if (p->mean_on()) {  // the chunk table of the mean's part launch; an image's rows are its patches (a shape has at least one)
+        c->pc0.resize((size_t)n + 1);
+        if (!feat_pool_chunks(c->row0.data(), n, p->Tp, c->pc0.data())) { set_error("vitx_pack_forward: the call's images make more than 2^31 - 1 chunks of patch rows"); return VITX_ERR_ARG; }
+    }
     if (p->rollout() && (rc = check_attn("vitx_pack_forward", c->row0.data(), n, p->attn->max_sq, &c->roll))) return rc;
     if (from_u8) {
         if ((uintptr_t)d_imgs & 3) { set_error("vitx_pack_forward: the u8 sources must be 4-byte aligned"); return VITX_ERR_ARG; }
@@ -265,7 +269,7 @@ int pack_forward(vitx_pack *p, PackCall &c, const void *d_imgs, const int32_t *s
     PackDepth *dp = p->depth.get();
     PackAttn *am = p->attn.get();
     HIP_TRY(hipSetDevice(p->device));
-    p->row0.swap(c.row0); p->chunk0.swap(c.chunk0); p->feat_n = 0;
+    p->row0.swap(c.row0); p->chunk0.swap(c.chunk0); p->pc0.swap(c.pc0); p->feat_n = 0;
     if (dn) { std::swap(dn->last, c.dense); dn->n = 0; }
     if (dp) { std::swap(dp->last, c.depth); dp->n = 0; }
     if (am) { std::swap(am->last, c.roll); am->n = 0; }
@@ -292,6 +296,7 @@ int pack_forward(vitx_pack *p, PackCall &c, const void *d_imgs, const int32_t *s
     if (c.u8.on) u8_tables(c.u8, at, host);
     if (at.parts & kRollout) rollout_tables(am->last, at, host);
     if (p->pool_map) std::copy(p->chunk0.begin(), p->chunk0.end(), host + at.chunk0());
+    if (at.parts & kFeatPool) std::copy(p->pc0.begin(), p->pc0.end(), host + at.pc0());
     HIP_TRY(hipMemcpyAsync(p->tab, p->host.data(), p->host.size() * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(p->uploaded, st));
     p->uploaded_pending = true;
@@ -350,14 +355,28 @@ int pack_forward(vitx_pack *p, PackCall &c, const void *d_imgs, const int32_t *s
     }
     // the class rows through the final norm (row0[i] is image i's class row), the head GEMM in f32, the class softmax; an attention-pooling file has no
     // class row: its Z comes out of the pooled tail
+    // The cls + mean head (options.pool_head = 2): Z = RNE(class row) | RNE(mean of the patch rows) from the two launches of features_packed.hip, which
+    // also leave the f32 mean when VITX_FEAT_MEAN is on -- from the registers the operand is rounded from
+    const bool feat_mean = !p->pool_map && (p->feat_flags & VITX_FEAT_MEAN) != 0, l2 = (p->feat_flags & VITX_FEAT_L2) != 0;
+    const int *d_pc0 = p->tab + at.pc0();
     if (p->pool_map) { if ((rc = pack_pooled_tail(p, at, n, Mh, st))) return rc; }
-    else { HIP_TRY(launch_pool_rows(dt, p->X, d_row0, ws.norm_w, ws.norm_b, p->Z, n, Mh, D, p->eps, st)); ++p->launches; }
+    else if (p->pool_cm) {
+        HIP_TRY(launch_feat_pool_packed(p->X, d_row0, d_pc0, n, p->pc0[n], Tp, ws.norm_w, ws.norm_b, p->eps, p->mean_part.as<float>(), nullptr,
+                                        feat_mean ? p->feat_mean.as<float>() : nullptr, p->Z, dt, Mh, D, l2, st));
+        p->launches += 2;
+    } else { HIP_TRY(launch_pool_rows(dt, p->X, d_row0, ws.norm_w, ws.norm_b, p->Z, n, Mh, D, p->eps, st)); ++p->launches; }
     float *lg = d_logits ? d_logits : p->logits;
     const int ldl = d_logits ? p->C : p->C_pad;
-    if ((rc = pack_gemm(p, EPI_BIAS_F32, dense_gemm(p->Z, ws.head_w, ws.head_b, lg, Mh, n, p->C, p->C_pad, D, ldl), st))) return rc;
+    if ((rc = pack_gemm(p, EPI_BIAS_F32, dense_gemm(p->Z, ws.head_w, ws.head_b, lg, Mh, n, p->C, p->C_pad, p->pool_cm ? 2 * D : D, ldl), st))) return rc;
     HIP_TRY(launch_softmax(dt, lg, d_probs, n, p->C, ldl, st)); ++p->launches;
     // features (vitx_pack_feat_enable): the f32 final norm of every row of the pack; vitx_pack_feat_read gathers the rows it was asked for
-    if (p->pool_map ? (p->feat_flags & VITX_FEAT_TOKENS) != 0 : p->feat_flags != 0) { HIP_TRY(launch_layernorm_f32(p->X, ws.norm_w, ws.norm_b, p->feat.as<float>(), rows, D, p->eps, st)); ++p->launches; }
+    if (p->feat_flags & (p->pool_map ? VITX_FEAT_TOKENS : VITX_FEAT_CLS | VITX_FEAT_TOKENS)) { HIP_TRY(launch_layernorm_f32(p->X, ws.norm_w, ws.norm_b, p->feat.as<float>(), rows, D, p->eps, st)); ++p->launches; }
+    // VITX_FEAT_MEAN on a class-token pack: the same two launches for the mean alone
+    if (feat_mean && !p->pool_cm) {
+        HIP_TRY(launch_feat_pool_packed(p->X, d_row0, d_pc0, n, p->pc0[n], Tp, ws.norm_w, ws.norm_b, p->eps, p->mean_part.as<float>(), nullptr, p->feat_mean.as<float>(), nullptr, dt, n, D,
+                                        l2, st));
+        p->launches += 2;
+    }
     if (p->feat_flags) p->feat_n = n;
     // the dense head: the logits of every row of the pack, then one label launch over the images' own output shapes (2 launches; the memset of
     // the operand's pad rows is not a kernel)

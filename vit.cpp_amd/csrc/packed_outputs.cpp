@@ -36,16 +36,30 @@ int pack_head_window(const char *api, const vitx_pack *p, size_t Mp, int Dc, siz
 extern "C" {
 
 int vitx_pack_feat_enable(vitx_pack *p, int flags) {
-    if (!p || (flags & ~(VITX_FEAT_CLS | VITX_FEAT_TOKENS | (p->pool_map ? VITX_FEAT_L2 : 0)))) { set_error("vitx_pack_feat_enable: flags are VITX_FEAT_CLS | VITX_FEAT_TOKENS (0 = off), and VITX_FEAT_L2 on a context of an attention-pooling file"); return VITX_ERR_ARG; }
+    if (!p || (flags & ~(VITX_FEAT_CLS | VITX_FEAT_TOKENS | (p->pool_map ? VITX_FEAT_L2 : VITX_FEAT_MEAN | VITX_FEAT_L2))) || (!p->pool_map && (flags & VITX_FEAT_L2) && !(flags & VITX_FEAT_MEAN))) {
+        set_error("vitx_pack_feat_enable: flags are VITX_FEAT_CLS | VITX_FEAT_TOKENS (0 = off); VITX_FEAT_MEAN, and VITX_FEAT_L2 with it, except on a context of an attention-pooling file, "
+                  "which takes VITX_FEAT_L2 but no VITX_FEAT_MEAN");
+        return VITX_ERR_ARG;
+    }
     HIP_TRY(hipSetDevice(p->device));
     if (p->pool_map) {   // cls is the pooled embedding, one row per image; the final-norm rows are kept for the tokens only
         if (const int rc = pack_quiesce(p)) return rc;
         if ((flags & VITX_FEAT_CLS) && !p->feat_cls && !alloc_counted(p->feat_cls, (size_t)p->max_images * p->D * 4, &p->scratch_bytes)) { set_error("vitx_pack_feat_enable: cannot allocate the embeddings of %d images", p->max_images); return VITX_ERR_NOMEM; }
         if ((flags & VITX_FEAT_TOKENS) && !p->feat && !alloc_counted(p->feat, (size_t)p->max_tokens * p->D * 4, &p->scratch_bytes)) { set_error("vitx_pack_feat_enable: cannot allocate the features of %d token rows", p->max_tokens); return VITX_ERR_NOMEM; }
-    } else if (flags && !p->feat) {
+    } else if ((flags & (VITX_FEAT_CLS | VITX_FEAT_TOKENS)) && !p->feat) {
         const size_t bytes = (size_t)p->max_tokens * p->D * 4;
         HIP_TRY(hipMalloc(&p->feat.p, bytes));
         p->scratch_bytes += bytes;
+    }
+    if (!p->pool_map && ((flags | p->feat_flags) & VITX_FEAT_MEAN)) {       // the mean's table comes or goes (a cls + mean pack keeps it), its buffers come
+        const size_t D = (size_t)p->D;
+        if (const int rc = pack_quiesce(p)) return rc;
+        if (flags & VITX_FEAT_MEAN) {
+            if (!p->feat_mean && !alloc_counted(p->feat_mean, (size_t)p->max_images * D * 4, &p->scratch_bytes)) { set_error("vitx_pack_feat_enable: cannot allocate the means of %d images", p->max_images); return VITX_ERR_NOMEM; }
+            if (!p->mean_part && !alloc_counted(p->mean_part, ((size_t)p->max_tokens / kFeatPoolChunkRows + p->max_images) * D * 4, &p->scratch_bytes)) { set_error("vitx_pack_feat_enable: cannot allocate the mean's partial sums"); return VITX_ERR_NOMEM; }
+        }
+        const unsigned parts = (flags & VITX_FEAT_MEAN) || p->pool_cm ? p->parts() | kFeatPool : p->parts() & ~kFeatPool;
+        if (const int rc = resize_tables(p, "vitx_pack_feat_enable", parts)) return rc;
     }
     p->feat_flags = flags; p->feat_n = 0;
     return VITX_OK;
@@ -63,6 +77,17 @@ int vitx_pack_feat_read(vitx_pack *p, float *cls, float *tokens) {
     if (cls && p->pool_map) HIP_TRY(hipMemcpy(cls, p->feat_cls.p, n * D * 4, hipMemcpyDeviceToHost));
     else if (cls) for (int i = 0; i < n; ++i) HIP_TRY(hipMemcpy(cls + i * D, p->feat.as<float>() + p->row0[i] * D, D * 4, hipMemcpyDeviceToHost));
     return tokens ? read_patch_rows(p, n, p->feat.as<float>(), D, tokens) : VITX_OK;
+}
+
+// The last forward's mean patch embeddings [n][D] (VITX_FEAT_MEAN), one row per image as the combine launch left them
+int vitx_pack_feat_read_mean(vitx_pack *p, float *mean) {
+    if (!p || !mean) { set_error("vitx_pack_feat_read_mean: NULL argument"); return VITX_ERR_ARG; }
+    if (!(p->feat_flags & VITX_FEAT_MEAN)) { set_error("vitx_pack_feat_read_mean: vitx_pack_feat_enable did not select VITX_FEAT_MEAN"); return VITX_ERR_ARG; }
+    if (!p->feat_n) { set_error("vitx_pack_feat_read_mean: no forward has run with features on since vitx_pack_feat_enable"); return VITX_ERR_ARG; }
+    HIP_TRY(hipSetDevice(p->device));
+    if (p->done_pending) HIP_TRY(hipEventSynchronize(p->done));
+    HIP_TRY(hipMemcpy(mean, p->feat_mean.p, (size_t)p->feat_n * p->D * 4, hipMemcpyDeviceToHost));
+    return VITX_OK;
 }
 
 // Attention maps of a packed context (include/vitx.h "packed batches")
