@@ -124,9 +124,9 @@ int vitx_model_seq_len(const vitx_model *m);
  * keeps the class-rows-only last layer.  ViTSTR (one-channel) files with either extension, and VITX_MXFP8 contexts of such files, are
  * VITX_ERR_UNSUPPORTED at context creation.
  * LayerScale needs no slot: the converter folds it into attn.proj / mlp.fc2 (convert.py). */
-enum vitx_head_pool { VITX_POOL_CLS = 0, VITX_POOL_CLS_MEAN = 1, VITX_POOL_MAP = 2 };
+enum vitx_head_pool { VITX_POOL_CLS = 0, VITX_POOL_CLS_MEAN = 1, VITX_POOL_MAP = 2, VITX_POOL_MEAN = 3, VITX_POOL_MEAN_NORM = 4 };
 int vitx_model_num_registers(const vitx_model *m);   /* R; 0 without reg_token (and for NULL) */
-int vitx_model_head_pool(const vitx_model *m);       /* enum vitx_head_pool, from head.weight's shape and the presence of attn_pool.* */
+int vitx_model_head_pool(const vitx_model *m);       /* enum vitx_head_pool, from head.weight's shape, the presence of attn_pool.* and the `pool` tensor */
 /* ---- no class token and the attention-pooling head (SigLIP-class models) --------
  * One more optional extension, recognised by the presence of the thirteen `attn_pool.*` tensors (timm's AttentionPoolLatent names; transformers'
  * SiglipMultiheadAttentionPoolingHead), written after norm.bias and before head.*: VITX_POOL_MAP.
@@ -155,7 +155,36 @@ int vitx_model_head_pool(const vitx_model *m);       /* enum vitx_head_pool, fro
  * VITX_ERR_UNSUPPORTED: ViTSTR files with the extension and VITX_MXFP8 contexts of such files (at context creation); vitx_attn_enable on such a
  * context (the maps are defined by the class-token row, which does not exist); a context at another img_size than the file's and
  * vitx_model_resize_file of such a file (the g^2-row position table has no resampling path yet). */
-int vitx_model_num_prefix(const vitx_model *m);      /* tokens in front of the patches: 0 for a VITX_POOL_MAP file, 1 + R otherwise (0 for NULL) */
+int vitx_model_num_prefix(const vitx_model *m);      /* T, tokens in front of the patches: 1 + R with a class token, R without one (VITX_POOL_MAP: 0; 0 for NULL) */
+/* ---- the mean-pool head (timm global_pool='avg', SiglipForImageClassification) ----
+ * One more optional marker in the style of `rope` / `glu` / `mlp`: `pool` f32 [4] = {1, order, 0, 0}, in front of the first blocks.* record (behind
+ * `glu` / `mlp` when present).  The head reads ONE row [D] per image, pooled over the patch rows t = T .. N-1; head.weight stays [C][D]:
+ *   order 0, VITX_POOL_MEAN:       the final norm on every row, then the mean: z = RNE(mean of F[t]), F and the mean exactly VITX_FEAT_MEAN's (the
+ *                                  same launch, its fixed order), so RNE(VITX_FEAT_MEAN feature) == the head operand bit for bit;
+ *   order 1, VITX_POOL_MEAN_NORM:  the mean m of the RAW f32 residual rows X[t], then the norm on that one row: e = LN(m), z = RNE(e).
+ * norm.weight / norm.bias are the LayerNorm's parameters in both orders (the converter writes timm's fc_norm.* there).
+ * Summation order of m (order 1), fixed and independent of the batch: the patch rows are cut into chunks of VITX_POOL_MEAN_CHUNK_ROWS rows from
+ * row T; in a chunk, row-lane l of RL (a constant of the hidden size) adds its rows T + 64 c + l, + RL, + 2 RL, ... in ascending order onto 0; the
+ * row-lanes are added in ascending order, ((a_0 + a_1) + a_2) + ...; the chunks are added in ascending order and the sum is divided once by N - T.
+ * Every step is an f32 add; e = the one LayerNorm definition of every kernel here.  An image's m, e, z bits do not depend on the batch size, its
+ * position or its neighbours (NaN included).
+ * With `pool`, cls_token is optional.  Present: the layout above, T = 1 + R.  Absent: pos_embed has g^2 rows, rows 0 .. R-1 of an image are
+ * reg_token[r] as they are, patch p + pos_embed[p] follows at row T = R, and R may be 0.  A class token exists iff num_prefix == 1 + num_registers.
+ * VITX_ERR_FORMAT: `pool` beside attn_pool.* or beside a [C][2 D] head; an order other than 0 or 1; a slot 0 other than 1 or non-zero reserved
+ * slots; a pos_embed whose row count does not fit the presence of cls_token; `pool` behind a blocks.* record.  Without `pool` every earlier rule
+ * stands.  vitx_quantize_file copies the tensor through; vitx_model_resize_file and a context at another size work for a file with a class
+ * token and are VITX_ERR_UNSUPPORTED for a class-less one (VITX_POOL_MAP's rule).
+ * A mean-pool context evaluates every row of the last layer, as a VITX_POOL_CLS_MEAN context does.  VITX_FEAT_CLS is the f32 pooled embedding
+ * the head reads (the mean for order 0, e for order 1; the last layer only, any other layer in the mask is VITX_ERR_ARG; its RNE equals the
+ * head operand); VITX_FEAT_MEAN and VITX_FEAT_TOKENS keep their meaning over rows T .. N-1.  A class-less context refuses vitx_attn_enable and a
+ * depth head's class half (VITX_ERR_UNSUPPORTED).  VITX_ERR_UNSUPPORTED at creation: VITX_MXFP8 contexts, ViTSTR files, and packed contexts
+ * (vitx_pack_create, with any pool_head) of such a file.
+ * vitx_op_pool_mean: the two kernels of order 1 on their own.  TEST ONLY: it allocates its scratch, runs on the null stream and synchronises.
+ *   Row t of image i is read at d_x + i * img_stride + t * row_stride (floats), rows first .. N-1 are averaged and no other row is read; d_m
+ *   (or NULL) [n_img][D] f32 = m, d_e (or NULL) [n_img][D] f32 = e, d_z [m_pad][D] in `dtype` = RNE(e), rows n_img .. m_pad - 1 zeros. */
+#define VITX_POOL_MEAN_CHUNK_ROWS 64
+int vitx_op_pool_mean(int dtype, const void *d_x, long row_stride, long img_stride, const void *d_ln_w, const void *d_ln_b, float eps, void *d_m /* or NULL */,
+                      void *d_e /* or NULL */, void *d_z, int n_img, int m_pad, int N, int first, int D);
 /* u [H][D] f32 of a VITX_POOL_MAP file (above); host only.  VITX_ERR_ARG for NULL or a file without the head. */
 int vitx_model_pool_query(const vitx_model *m, float *out /* [H][D] */);
 /* ---- activation, epsilon and pre-norm (HuggingFace ViT, timm, DINOv2, CLIP) ----

@@ -15,7 +15,7 @@ import numpy as np
 
 # the enums a model file or a zero-shot bank carries are numbered once, in ggml_file.py (which needs no library)
 from .ggml_file import (ACT_TANH as ACT_GELU_TANH, ACT_ERF as ACT_GELU_ERF, ACT_QUICK as ACT_QUICK_GELU,      # vitx_model_activation (tanh-GELU without `arch`)
-                        ZS_SOFTMAX, ZS_SIGMOID, POOL_CLS, POOL_CLS_MEAN, POOL_MAP,                           # vitx_zs_kind, vitx_model_head_pool
+                        ZS_SOFTMAX, ZS_SIGMOID, POOL_CLS, POOL_CLS_MEAN, POOL_MAP, POOL_MEAN, POOL_MEAN_NORM,                           # vitx_zs_kind, vitx_model_head_pool
                         PP_REF_BICUBIC, PP_REF_BILINEAR, PP_PIL_BILINEAR, PP_PIL_BICUBIC, PP_STRETCH, PP_SHORTEST_EDGE)      # vitx_pp_filter, vitx_pp_resize
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -83,6 +83,7 @@ EXPORTS = [
     "vitx_op_attention_map_packed", "vitx_op_rollout_step_packed", "vitx_op_rollout_row_packed",
     "vitx_pack_pool_chunk_rows", "vitx_pack_pool_chunks", "vitx_op_attention_pool_packed", "vitx_op_attention_pool_packed_tables",
     "vitx_pack_feat_read_mean", "vitx_pack_mean_chunks", "vitx_op_feat_pool_packed", "vitx_op_feat_pool_packed_tables",
+    "vitx_op_pool_mean",
 ]
 
 
@@ -255,6 +256,8 @@ def lib():
             L.vitx_model_num_prefix.argtypes = [vp]
             L.vitx_model_pool_query.argtypes = [vp, C.POINTER(C.c_float)]
             L.vitx_op_attention_pool.argtypes = [vp, C.c_long, C.c_long, vp, vp, C.c_float, vp, vp, vp, ip, ip, ip, ip, vp]
+        if hasattr(L, "vitx_op_pool_mean"):
+            L.vitx_op_pool_mean.argtypes = [ip, vp, C.c_long, C.c_long, vp, vp, C.c_float, vp, vp, vp, ip, ip, ip, ip, ip]
         if hasattr(L, "vitx_zeroshot_set"):
             fp = C.POINTER(C.c_float)
             L.vitx_zeroshot_set.argtypes = [vp, fp, ip, ip, ip, C.c_float, C.c_float]
@@ -462,10 +465,10 @@ class Model:
     def num_registers(self) -> int:                                                 # register tokens (reg_token [1][R][D]); 0 without
         return lib().vitx_model_num_registers(self._h) if hasattr(lib(), "vitx_model_num_registers") else 0
     @property
-    def head_pool(self) -> int:                                                     # POOL_CLS, or POOL_CLS_MEAN for a [C][2 D] head
+    def head_pool(self) -> int:                                                     # POOL_CLS, POOL_CLS_MEAN for a [C][2 D] head, POOL_MAP, POOL_MEAN / POOL_MEAN_NORM with `pool`
         return lib().vitx_model_head_pool(self._h) if hasattr(lib(), "vitx_model_head_pool") else 0
     @property
-    def num_prefix(self) -> int:                                                    # tokens in front of the patches: 1 + registers, or 0 for a POOL_MAP file
+    def num_prefix(self) -> int:                                                    # tokens in front of the patches: 1 + registers with a class token, the registers without one
         return lib().vitx_model_num_prefix(self._h) if hasattr(lib(), "vitx_model_num_prefix") else 1 + self.num_registers
 
     def pool_query(self) -> np.ndarray:
@@ -1901,6 +1904,13 @@ def op_patch_embed_rect(dtype: int, d_img: int, d_w: int, d_bias: int, d_pos: in
                         P: int, Cin: int, D: int) -> None:
     """vitx_op_patch_embed_rect (test only; synchronous): vitx_op_patch_embed on [n, img_h, img_w, Cin] images; d_pos [prefix rows + (img_h/P)(img_w/P), D]."""
     check(lib().vitx_op_patch_embed_rect(dtype, d_img, d_w, d_bias, d_pos, d_cls or None, d_reg or None, R, n_img, img_h, img_w, P, Cin, D, d_X), "vitx_op_patch_embed_rect")
+
+
+def op_pool_mean(dtype: int, d_x: int, row_stride: int, img_stride: int, d_ln_w: int, d_ln_b: int, eps: float, d_m: int, d_e: int, d_z: int,
+                 n_img: int, m_pad: int, N: int, first: int, D: int) -> None:
+    """vitx_op_pool_mean (test only; null stream, synchronous): the raw-mean head's two kernels (device pointers, strides in floats): rows first .. N-1 of
+    every image -> m [n_img, D] f32 (0: not wanted), e = LN(m) [n_img, D] f32 (0: not wanted), z [m_pad, D] = RNE(e) in `dtype`, pad rows zero."""
+    check(lib().vitx_op_pool_mean(dtype, d_x, row_stride, img_stride, d_ln_w, d_ln_b, eps, d_m or None, d_e or None, d_z, n_img, m_pad, N, first, D), "vitx_op_pool_mean")
 
 
 def op_attention_pool(d_x: int, row_stride: int, img_stride: int, d_ln_w: int, d_ln_b: int, eps: float, d_u: int, d_M: int, d_p: int,

@@ -38,7 +38,7 @@ processor: the --pp-* options state one (cli_preproc); with none of them no tens
 What is refused, by name: an activation the forward path does not evaluate; a plain MLP that is not 4 x hidden (SigLIP SO400M's 4304) unless mlp_width=True / --mlp-width opts in to the `mlp` tensor {F, 0, 0, 0}; a head_dim that
 is no multiple of 8 up to 128; qkv_bias=False; SwiGLU (use_swiglu_ffn) and DINOv3's gated MLP (use_gated_mlp) unless gated_mlp=True / --gated-mlp opts in, a gate
 activation other than silu and a gated width that is no multiple of 64; qk-norm, fc_norm and distillation tokens; a SigLIP tower without its pooling head
-(vision_use_head = False), SiglipForImageClassification (a mean-pool classifier: no slot), Siglip2VisionModel (NaFlex: its patch embedding is a
+(vision_use_head = False), SiglipForImageClassification (a mean-pool classifier: no slot) unless mean_pool=True / --mean-pool opts in to the `pool` tensor, Siglip2VisionModel (NaFlex: its patch embedding is a
 Linear); --no-head on a ViT, and a model without classifier or projection converted without it; --vitstr on anything but a one-channel ViT; in a
 preprocessor_config whatever the engine's preprocess cannot honour -- another resample code, do_resize off, padding, a channel flip, a final size
 that is not the model's -- with the field's name.
@@ -248,6 +248,30 @@ def _require_mlp_4x(cfg, field: str, want: int, note: str = "", mlp_width: bool 
     have = getattr(cfg, field, want)
     if have != want and not mlp_width:
         raise ValueError(f"{field} {have}: the file format holds a 4 x hidden MLP{note}")
+
+
+def _with_pool(tensors: dict, order: int) -> dict:
+    """`tensors` with the `pool` tensor {1, order, 0, 0} in front (include/vitx.h "the mean-pool head"): 0 the final norm then the mean, 1 the mean of the
+    raw patch rows then the norm.  It goes in before `mlp` / `arch` do, so it ends up behind them and in front of the blocks."""
+    return {"pool": np.array([1, order, 0, 0], np.float32), **tensors}
+
+
+def siglip_classifier_to_timm(sd: Dict[str, np.ndarray], cfg, mlp_width: bool = False) -> Dict[str, np.ndarray]:
+    """An HF SiglipForImageClassification state dict under the file's names: the tower of siglip_state_dict_to_timm without its attention-pooling head
+    (the classifier does not use it), post_layernorm -> norm, classifier -> head, and `pool` order 0: the model averages last_hidden_state, which is
+    the final norm of every patch row.  No class token."""
+    pre = "vision_model."
+    e = pre + "embeddings."
+    if e + "patch_embedding.weight" not in sd or np.ndim(sd[e + "patch_embedding.weight"]) != 4 or "classifier.weight" not in sd:
+        raise ValueError("not a SiglipForImageClassification state dict (vision_model.embeddings.patch_embedding, classifier)")
+    D = int(cfg.hidden_size)
+    _require_mlp_4x(cfg, "intermediate_size", 4 * D, " (SO400M's 4304 is not supported)", mlp_width)
+    out = {"pos_embed": np.reshape(sd[e + "position_embedding.weight"], (1, -1, D))}
+    _put(out, "patch_embed.proj", sd, e + "patch_embedding")
+    map_blocks(out, sd, CLIP_BLOCKS, cfg.num_hidden_layers, pre)
+    _put(out, "norm", sd, pre + "post_layernorm")
+    _put(out, "head", sd, "classifier")
+    return _with_pool(_f32(out), 0)
 
 
 def _with_mlp_width(tensors: dict, D: int) -> dict:
@@ -528,6 +552,7 @@ _VIT = Family("ViT", lambda sd, cfg, no_head, mlp_width=False: state_dict_to_tim
 _DINOV2 = Family("DINOv2", dinov2_state_dict_to_timm, 1, _config_labels, "optional", ("AutoModelForImageClassification", "AutoModel"))
 _CLIP = Family("CLIP", clip_state_dict_to_timm, 1, lambda cfg, E: {i: f"dim_{i}" for i in range(E)}, "optional", ("CLIPVisionModelWithProjection", "CLIPVisionModel"))
 _SIGLIP = Family("SigLIP", lambda sd, cfg, no_head, mlp_width=False: siglip_state_dict_to_timm(sd, cfg, mlp_width), 0, None, "never", ("SiglipVisionModel",) * 2)
+_SIGLIP_CLS = Family("SigLIP classifier", lambda sd, cfg, no_head, mlp_width=False: siglip_classifier_to_timm(sd, cfg, mlp_width), 0, _config_labels, "always", ("SiglipForImageClassification",) * 2)
 _DINOV3 = Family("DINOv3", lambda sd, cfg, no_head, gated_mlp=False, mlp_width=False: dinov3_state_dict_to_timm(sd, cfg, gated_mlp, mlp_width), 1, None, "never", ("DINOv3ViTModel",) * 2)
 # text towers (convert_hf_text_model): no patch grid (prefix_rows is not read), no labels -- the "classes" are the projection's columns --, always with the projection
 _CLIP_TEXT = Family("CLIP text", clip_text_state_dict, 0, lambda cfg, E: {}, "always", ("CLIPTextModelWithProjection",) * 2)
@@ -562,7 +587,7 @@ def _family_tensors(model, cfg, fam, no_head: bool, head_dim_note: str = "", gat
 
 
 def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_head: bool = False, preprocessor_config: dict | None = None,
-                     gated_mlp: bool = False, mlp_width: bool = False) -> HParams:
+                     gated_mlp: bool = False, mlp_width: bool = False, mean_pool: bool = False) -> HParams:
     """model: a transformers model of one of FAMILIES, in eval mode (the module docstring lists the classes); no_head=True converts a model
     without classifier or projection, whose file gets the zero head labelled "(no head)" (a SigLIP tower always does).  The activation and the
     LayerNorm epsilon are the config's (with_arch); the class count and the image size are read off head.weight and pos_embed.
@@ -573,6 +598,8 @@ def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_
     mlp_width=True opts in to a plain MLP whose width is not 4 x hidden (SigLIP SO400M's 4304; any ViT, CLIP, SigLIP, non-gated DINOv2 / DINOv3 model):
     the file carries the `mlp` tensor {F, 0, 0, 0} (include/vitx.h "MLP width"), which neither the reference nor an engine build before it can read;
     without it such a model is refused as before.  A ViTSTR model takes none.
+    mean_pool=True opts in to SiglipForImageClassification: the file carries the `pool` tensor {1, 0, 0, 0} (include/vitx.h "the mean-pool head") and no
+    class token; without it the class is refused as before, and any other class refuses the flag.
     vitstr=True: the model is a ViTSTR scene-text recogniser (the reference's extensions/vitstr.cpp/convert-pth-to-ggml.py: a ViT with ONE input
     channel whose classifier is applied to the first 25 tokens); the file then carries the character set as labels, and the one-channel patch
     kernel is what makes vit_model_load / vitx_model_load treat it as a ViTSTR model (vitstr.cpp:482)."""
@@ -580,6 +607,18 @@ def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_
     cls_name = type(model).__name__
     if cls_name.startswith("Siglip2") or getattr(cfg, "model_type", "").startswith("siglip2"):
         raise ValueError(f"{cls_name} (Siglip2VisionModel, NaFlex) is not supported: its patch embedding is a Linear over flattened patches")
+    if mean_pool and cls_name != "SiglipForImageClassification":
+        raise ValueError(f"mean_pool=True: {cls_name} is no mean-pool classifier this converter knows (SiglipForImageClassification; timm state dicts take --timm-state-dict --mean-pool)")
+    if cls_name == "SiglipForImageClassification" and mean_pool:
+        vcfg = cfg.vision_config
+        if vitstr or no_head or gated_mlp:
+            raise ValueError("mean_pool=True: SiglipForImageClassification takes none of vitstr, no_head, gated_mlp")
+        tensors, act, eps = _family_tensors(model, vcfg, _SIGLIP_CLS, False, " (64 runs the tuned attention kernels)", False, mlp_width)
+        g = grid_side(tensors["pos_embed"], 0)
+        hp = HParams(vcfg.hidden_size, vcfg.num_hidden_layers, vcfg.num_attention_heads, int(tensors["head.weight"].shape[0]), vcfg.patch_size, g * vcfg.patch_size, ftype)
+        write_model(path, hp, with_arch(tensors, act, eps), id2label=_config_labels(cfg, hp.num_classes), ftype=ftype,
+                    preproc=hf_preproc(preprocessor_config, hp.img_size) if preprocessor_config is not None else None)
+        return hp
     if cls_name == "SiglipForImageClassification":
         raise ValueError("SiglipForImageClassification is not supported: it classifies the mean of the patch tokens and has no attention-pooling head (no slot for it)")
     if getattr(cfg, "model_type", "") in _TWO_TOWERS:
@@ -683,7 +722,7 @@ def _placed_after(t: dict, anchor: str, names) -> dict:
 
 
 def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2label=None, act: str = "tanh", eps: float = 1e-6, preproc: dict | None = None,
-                            mlp_width: bool = False) -> HParams:
+                            mlp_width: bool = False, mean_pool: bool = False) -> HParams:
     """sd: a timm VisionTransformer state_dict (name -> array / tensor), e.g. torch.load("vit_base_patch16_224.pth").  It already carries the names
     the file uses -- the reference's convert-pth-to-ggml.py:96-158 writes `timm_model.state_dict()` verbatim -- so no `timm` is needed: hidden
     size, depth, classes, patch and image size come from the tensor shapes (the reference reads them off the timm module), `norm_pre.*` is skipped
@@ -698,7 +737,10 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
     (tanh, 1e-6) writes the reference's file, without `arch`; timm's VisionTransformer was trained with nn.GELU and wants act="erf" (its eps is 1e-6).
     preproc: the keyword arguments of cli_preproc (resize, crop, filt, mean, std, crop_round) -- the checkpoint's preprocessing, written as the
     `preproc` tensor; None or all unset: no tensor.  mlp_width=True: a checkpoint whose mlp.fc1 has other than 4 x hidden rows (so400m, so150m, any
-    mlp_ratio) gets the `mlp` tensor {F, 0, 0, 0} in front (include/vitx.h "MLP width"); without it the file is written as ever and does not load."""
+    mlp_ratio) gets the `mlp` tensor {F, 0, 0, 0} in front (include/vitx.h "MLP width"); without it the file is written as ever and does not load.
+    mean_pool=True: a global_pool='avg' checkpoint (include/vitx.h "the mean-pool head").  fc_norm.* (and no norm.*) is written as norm.* with `pool` order 1
+    (the mean of the raw patch tokens, then the norm: reg4_gap, MAE fine-tunes); norm.* without fc_norm.* gets order 0 (the *_siglip_gap_* towers).  cls_token
+    is optional: without it pos_embed keeps its g^2 rows and the registers, if any, open an image.  Without the flag fc_norm stays refused by name."""
     if act not in _ACT_NAMES:
         raise ValueError(f"act {act!r}: one of {sorted(_ACT_NAMES)}")
     if isinstance(sd, dict) and "model" in sd and not hasattr(sd["model"], "shape"):
@@ -707,10 +749,19 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
     t = {k: v for k, v in t.items() if not k.startswith("norm_pre")}
     for k in t:
         for u, what in _TIMM_UNSUPPORTED.items():
-            if u in k:
+            if u in k and not (mean_pool and u == "fc_norm."):
                 raise ValueError(f"tensor {k!r}: {what} is not supported (the file format has no slot for it)")
     t = _f32(t)
     map_head = any(k.startswith("attn_pool.") for k in t)
+    pool_order = -1
+    if mean_pool:
+        fc = "fc_norm.weight" in t
+        if map_head or (fc and "norm.weight" in t):
+            raise ValueError("mean_pool=True: the checkpoint has attn_pool.*, or both norm.* and fc_norm.*: not a mean-pool classifier the file holds")
+        if fc:                                            # in place: the tensors keep their order
+            t = {k.replace("fc_norm.", "norm."): v for k, v in t.items()}
+        pool_order = 1 if fc else 0
+    no_cls = mean_pool and "cls_token" not in t
     if map_head:
         if "cls_token" in t or "reg_token" in t:
             raise ValueError("attn_pool.* beside cls_token / reg_token: the attention-pooling head is taken only from a model without a class token")
@@ -725,9 +776,9 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
             id2label = id2label if id2label is not None else NO_HEAD_LABELS
         t["attn_pool.latent"] = t["attn_pool.latent"].reshape(1, 1, D)
     for need in ("cls_token", "pos_embed", "patch_embed.proj.weight", "patch_embed.proj.bias", "norm.weight", "norm.bias", "head.weight", "head.bias"):
-        if need not in t and not (map_head and need == "cls_token"):
+        if need not in t and not ((map_head or no_cls) and need == "cls_token"):
             raise ValueError(f"not a timm VisionTransformer state_dict: {need!r} is missing")
-    D = int(t["pos_embed"].shape[-1] if map_head else t["cls_token"].shape[-1])
+    D = int(t["pos_embed"].shape[-1] if map_head or no_cls else t["cls_token"].shape[-1])
     L = 1 + max(int(k.split(".")[1]) for k in t if k.startswith("blocks."))
     # LayerScale: folded, no file slot.  A model has it on both branches of every block or not at all: a partial set is a damaged checkpoint
     ls_keys = [f"blocks.{i}.{ls}.gamma" for i in range(L) for ls in ("ls1", "ls2")]
@@ -737,7 +788,7 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
     for gk in ls_have:
         p = gk.replace(".ls1.gamma", ".attn.proj.").replace(".ls2.gamma", ".mlp.fc2.")
         t[p + "weight"], t[p + "bias"] = fold_layer_scale(t[p + "weight"], t[p + "bias"], t.pop(gk))
-    if "reg_token" in t:
+    if "reg_token" in t and not no_cls:
         n_rows = int(t["pos_embed"].shape[1])
         if int(round(n_rows ** 0.5)) ** 2 == n_rows and n_rows > 1:       # no_embed_class: g^2 rows, none for the class token
             t["pos_embed"] = np.ascontiguousarray(np.concatenate([np.zeros((1, 1, D), np.float32), t["pos_embed"]], axis=1))
@@ -746,7 +797,7 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
         last = [k for k in t if not k.startswith(("attn_pool.", "head."))][-1]
         t = _placed_after(t, last, pool + [k for k in t if k.startswith("head.")])
     Dw, cin, P, P2 = t["patch_embed.proj.weight"].shape
-    g = grid_side(t["pos_embed"], 0 if map_head else 1)
+    g = grid_side(t["pos_embed"], 0 if map_head or no_cls else 1)
     if Dw != D or P != P2 or cin not in (1, 3):
         raise ValueError(f"unexpected shapes: patch kernel {t['patch_embed.proj.weight'].shape}, pos_embed {t['pos_embed'].shape}")
     H = heads or _TIMM_HEADS.get(D, 0)
@@ -760,9 +811,13 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
         if hp.num_classes == len(VITSTR_LABELS):
             id2label = dict(VITSTR_LABELS)
     # pos_embed, the patch kernel and bias, 12 per block, norm.* and head.*; the class token (+ registers) or the thirteen of the pooling head
-    expected = 3 + 12 * L + 4 + (len(_POOL_ORDER) if map_head else 1 + ("reg_token" in t))
+    expected = 3 + 12 * L + 4 + (len(_POOL_ORDER) if map_head else (0 if no_cls else 1) + ("reg_token" in t))
     if len(t) != expected:
         raise ValueError(f"{len(t)} tensors after filtering, the file format holds exactly {expected} for {L} layers (vit.cpp:512-574)")
+    if mean_pool:
+        if cin == 1:
+            raise ValueError("mean_pool=True: a ViTSTR model takes no `pool` tensor")
+        t = _with_pool(t, pool_order)
     if mlp_width:
         if cin == 1:
             raise ValueError("mlp_width=True: a ViTSTR model takes no `mlp` width tensor")
@@ -1018,6 +1073,8 @@ def main(argv=None) -> int:
                                                             "carries the `glu` tensor, which the reference and engine builds before it cannot read")
     ap.add_argument("--mlp-width", action="store_true", help="opt in to a plain MLP whose width is not 4 x hidden (SigLIP SO400M's 4304, any mlp_ratio): the file carries the "
                     "`mlp` tensor, which neither the reference nor an engine build before it can read; applies to --text-out too")
+    ap.add_argument("--mean-pool", action="store_true", help="opt in to a mean-pool classifier (timm global_pool='avg' state dicts with fc_norm.* or norm.*, class token optional; "
+                    "SiglipForImageClassification): the file carries the `pool` tensor, which neither the reference nor an engine build before it can read")
     ap.add_argument("--timm-state-dict", action="store_true", help="`model` is a torch-saved timm VisionTransformer state_dict (.pth); no timm import needed")
     ap.add_argument("--heads", type=int, default=0, help="attention heads of a timm checkpoint (inferred only for the widths of released timm ViTs; required otherwise)")
     ap.add_argument("--act", default="tanh", choices=sorted(_ACT_NAMES), help="MLP activation of a timm checkpoint (a state dict carries no config): tanh = ggml's GELU, the "
@@ -1063,7 +1120,7 @@ def main(argv=None) -> int:
         sd = torch.load(a.model, map_location="cpu", weights_only=True)
         labels = {int(k): str(v) for k, v in json.load(open(a.labels)).items()} if a.labels else None
         pp_cli = dict(resize=a.pp_resize, crop=a.pp_crop, filt=a.pp_filter, mean=a.pp_mean, std=a.pp_std, crop_round=a.pp_crop_round)
-        hp = convert_timm_state_dict(sd, a.out, a.ftype, heads=a.heads, id2label=labels, act=a.act, eps=a.eps, preproc=None if a.no_preproc else pp_cli, mlp_width=a.mlp_width)
+        hp = convert_timm_state_dict(sd, a.out, a.ftype, heads=a.heads, id2label=labels, act=a.act, eps=a.eps, preproc=None if a.no_preproc else pp_cli, mlp_width=a.mlp_width, mean_pool=a.mean_pool)
     else:
         import transformers
         model_type = transformers.AutoConfig.from_pretrained(a.model).model_type
@@ -1079,7 +1136,7 @@ def main(argv=None) -> int:
             print(f"wrote {a.text_out}: text tower, hidden {thp.hidden_size}, layers {thp.num_hidden_layers}, heads {thp.num_attention_heads}, width {thp.num_classes}, tokens {thp.img_size}, ftype {a.ftype}")
             if model_type not in _TWO_TOWERS:
                 return 0                                   # a text tower alone: there is no vision file to write
-        fam = FAMILIES.get(model_type, _VIT)
+        fam = _SIGLIP_CLS if a.mean_pool and model_type == "siglip" else FAMILIES.get(model_type, _VIT)
         m = getattr(transformers, fam.loaders[1 if a.no_head and fam.head == "optional" else 0]).from_pretrained(a.model).eval()
         pc, pc_path = None, os.path.join(a.model, "preprocessor_config.json")
         if not a.no_preproc and not a.vitstr:
@@ -1088,7 +1145,7 @@ def main(argv=None) -> int:
                     pc = json.load(f)
             else:
                 print(f"note: no preprocessor_config.json beside '{a.model}': the file is written without a `preproc` tensor")
-        hp = convert_hf_model(m, a.out, a.ftype, vitstr=a.vitstr, no_head=a.no_head, preprocessor_config=pc, gated_mlp=a.gated_mlp, mlp_width=a.mlp_width)
+        hp = convert_hf_model(m, a.out, a.ftype, vitstr=a.vitstr, no_head=a.no_head, preprocessor_config=pc, gated_mlp=a.gated_mlp, mlp_width=a.mlp_width, mean_pool=a.mean_pool)
     if a.img_size and a.img_size != hp.img_size:           # written at the checkpoint's size first, then replaced by its --img-size version
         from . import binding
         tmp = a.out + f".src{os.getpid()}"

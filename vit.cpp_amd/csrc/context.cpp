@@ -35,10 +35,10 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
     const int img_size = opt.img_size > 0 ? opt.img_size : m->hp.img_size;
     const int img_h = rect ? rect_h : img_size, img_w = rect ? rect_w : img_size;
     const bool own_shape = img_h == m->hp.img_size && img_w == m->hp.img_size;      // the file's own geometry
-    if (m->in_chans == 1 && (m->num_registers || m->head_pool != VITX_POOL_CLS)) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes neither register tokens nor a pooled or attention-pooling head"); return VITX_ERR_UNSUPPORTED; }
-    if (dtype == VITX_MXFP8 && (m->num_registers || m->head_pool != VITX_POOL_CLS)) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts do not take models with register tokens, the pooled head or the attention-pooling head"); return VITX_ERR_UNSUPPORTED; }
-    if (m->head_pool == VITX_POOL_MAP && !own_shape) {
-        set_error("vitx_ctx_create_ex: a model with the attention-pooling head stays at the file's img_size (%d): its position table has no class row and no resampling path yet", m->hp.img_size);
+    if (m->in_chans == 1 && (m->num_registers || m->head_pool != VITX_POOL_CLS)) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes neither register tokens nor a pooled, attention-pooling or mean-pool head"); return VITX_ERR_UNSUPPORTED; }
+    if (dtype == VITX_MXFP8 && (m->num_registers || m->head_pool != VITX_POOL_CLS)) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts do not take models with register tokens, the pooled head, the attention-pooling head or the mean-pool head"); return VITX_ERR_UNSUPPORTED; }
+    if (!m->has_cls && !own_shape) {
+        set_error("vitx_ctx_create_ex: a model without a class token stays at the file's img_size (%d): its position table has no class row and no resampling path yet", m->hp.img_size);
         return VITX_ERR_UNSUPPORTED;
     }
     if (m->rope_kind && dtype == VITX_MXFP8) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts do not take models with rotary position embeddings"); return VITX_ERR_UNSUPPORTED; }
@@ -67,7 +67,8 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
     c->glu = m->glu_kind != VITX_GLU_NONE; c->F = m->mlp_hidden(); c->F1 = m->mlp_fc1_rows();
     c->fc1_epi = c->glu ? EPI_BIAS : act_epi(m->activation);       // a gated MLP: the plain bias epilogue, the gate is a launch of its own
     c->nreg = m->num_registers; c->pool = m->head_pool == VITX_POOL_CLS_MEAN; c->map = m->head_pool == VITX_POOL_MAP;
-    c->Tp = c->map ? 0 : 1 + c->nreg;
+    c->mean = m->mean_pool() ? m->head_pool : 0; c->has_cls = m->has_cls;
+    c->Tp = m->num_prefix();
     if (c->map && c->H > kPoolMaxHeads) { set_error("vitx_ctx_create: the attention-pooling kernel takes at most %d heads (this model: %d)", kPoolMaxHeads, c->H); return VITX_ERR_UNSUPPORTED; }
     c->gh = c->Sh / c->P; c->gw = c->Sw / c->P;
     if ((long)c->gh * c->gw + c->Tp > 0x7fffffffl / 4) { set_error("vitx_ctx_create: %d x %d patches are more tokens than a context takes", c->gh, c->gw); return VITX_ERR_UNSUPPORTED; }
@@ -84,8 +85,8 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
     c->split_first = opt.split_first;
     c->prec_attn = dtype == VITX_F16 && c->D == c->H * 64 && !opt.f16_fast_attention;
     c->quant_on_device = !opt.quant_on_host;
-    // the pooled head averages every patch row of the last layer, the attention-pooling head attends over them: such a context runs exactly as one created with last_layer_all_rows = 1
-    c->cls_tail = !opt.last_layer_all_rows && !c->pool && !c->map && c->R == 1 && attention_cls_supports(c->N, c->D, c->H);
+    // the pooled and the mean-pool head average every patch row of the last layer, the attention-pooling head attends over them: such a context runs exactly as one created with last_layer_all_rows = 1
+    c->cls_tail = !opt.last_layer_all_rows && !c->pool && !c->map && !c->mean && c->R == 1 && attention_cls_supports(c->N, c->D, c->H);
     c->q4_fused_rows = opt.q4_fused_rows;
     c->graphs_on = opt.graph != 0;
     // fault injection for the parity tests: honoured only with the key in the upper half (VITX_LN_TEST_KEY | mode), so that no caller sets it by accident
@@ -132,6 +133,7 @@ int alloc_slice(vitx_ctx *c, vitx_ctx::Slice &sl, size_t hcols, bool internal) {
     }
     if ((c->cls_tail || c->map) && (rc = c->dmalloc((void **)&sl.Xc, Bpad * D * 4, true))) return rc;
     if (c->map && (rc = c->dmalloc(&sl.Mp, Bpad * c->H * D * 2, true))) return rc;
+    if (c->mean == VITX_POOL_MEAN_NORM && (rc = c->dmalloc((void **)&sl.Pm, (size_t)sl.cap * pool_mean_chunks(c->N - c->Tp) * D * 4, false))) return rc;
     if ((rc = c->dmalloc((void **)&sl.logits, Bpad * c->C_pad * 4, true))) return rc;
     // expansion scratch for quantised matrices: one buffer per matrix kind, shared by all layers (the largest layer decides)
     for (int k = 0; k < W_PER_LAYER; ++k) {

@@ -41,13 +41,18 @@ struct vitx_ctx {
     int R = 1;                           // probability rows per image: 1 (cls token) or 25 (ViTSTR: tokens 0..24, vitstr.cpp:864-904)
     // Token layout of an image (include/vitx.h "Register tokens and the pooled head"): row 0 = class token, rows 1 .. nreg = register tokens,
     // rows Tp .. N - 1 = patches in raster order; N = gh * gw + Tp
-    int nreg = 0, Tp = 1;                // register tokens of the model (reg_token), prefix tokens 1 + nreg (0 for a VITX_POOL_MAP model: no class token)
+    int nreg = 0, Tp = 1;                // register tokens of the model (reg_token), prefix tokens 1 + nreg (nreg without a class token: vitx_model_num_prefix)
     int fc1_epi = EPI_BIAS_GELU;         // the fc1 epilogue of the model's activation (vitx_model_activation), taken once at creation; EPI_BIAS in a `glu` context
     // The MLP widths of the blocks: F = the hidden width, fc2's K; F1 = fc1's N.  4 D both, or -- a file with `glu` (include/vitx.h "gated MLP") --
     // the file's F and 2 F: fc1 writes gate | up into Hbuf [Mpad][2 F], the gate kernel (swiglu.hip) the compact Hg [Mpad][F] that fc2 reads
     int F = 0, F1 = 0;
     bool glu = false;
     bool pool = false;                   // VITX_POOL_CLS_MEAN: the head reads concat(cls, mean of the patch tokens) of the final norm, K = 2 D
+    // VITX_POOL_MEAN / VITX_POOL_MEAN_NORM (0: neither): the head reads the mean of the patch rows, K = D -- of the final norm (the feature pass, mean-only
+    // operand form), or of the raw stream and then normalised (pool_mean.hip); every row of the last layer is evaluated
+    int mean = 0;
+    bool has_cls = true;                 // row 0 of an image is a class token (false: VITX_POOL_MAP, or a mean-pool file without cls_token)
+    bool pooled_cls() const { return map || mean; }      // VITX_FEAT_CLS is the pooled embedding the head reads (last layer only), not a class row
     bool map = false;                    // VITX_POOL_MAP: no class token; the head reads the attention-pooled embedding e (SliceForward::pooled_tail)
     int tm = 128, tn = 128;
     const Tuning *tune = nullptr;        // per-device launch parameters (CU count, kernel selection), immutable
@@ -122,6 +127,7 @@ struct vitx_ctx {
         uint8_t *Umx = nullptr, *Umx_s = nullptr, *U2mx = nullptr, *U2mx_s = nullptr, *Hmx = nullptr, *Hmx_s = nullptr;
         void *Wq[W_PER_LAYER] = {nullptr, nullptr, nullptr, nullptr};   // just-in-time expansion of the current layer's quantised matrices
         void *Wq_head = nullptr;
+        float *Pm = nullptr;         // VITX_POOL_MEAN_NORM: [cap][pool_mean_chunks(N - Tp)][D] f32 chunk sums of the raw patch rows (pool_mean.hip)
         float *logits = nullptr;     // [Bpad][C_pad]
         hipStream_t stream = nullptr;
         hipEvent_t done = nullptr;

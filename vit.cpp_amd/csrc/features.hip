@@ -12,6 +12,8 @@
 //   * the W partial sums are added into one LDS row in wave order, ((p_0 + p_1) + p_2) + ..., then divided by N - T.
 // The pooled head (VITX_POOL_CLS_MEAN) takes its operand from the same pass: z[i] = RNE(F[0]) ‖ RNE(mean) in the operand type, rounded from
 // the very registers the f32 features are stored from (before VITX_FEAT_L2), so RNE(feature) == the head operand by construction.
+// The mean-pool head (VITX_POOL_MEAN) takes the mean-only form of that operand: z[i] = RNE(mean), rows of D; no class row is read, and the class
+// feature of such a context is the same pooled embedding.
 // No atomics, nothing depends on the batch: an image's bits are a function of its own rows, N and D only.
 // Column ownership follows the statistics helpers: lane l holds columns c * 256 + 4 l .. + 3 of tile c (tiled widths: 16-byte loads and
 // stores, 1 KiB contiguous per wave instruction) or (i * 64 + l) * VEC .. of piece i (flat widths, VEC of the instantiation table).
@@ -30,7 +32,7 @@ constexpr int feat_waves(int D) { return D <= 768 ? 16 : 8; }
 template <int VEC, int NV>
 __global__ __launch_bounds__(feat_waves(64 * VEC * NV) * 64) void features_kernel(const float *__restrict__ x, long row_stride, long img_stride, const float *__restrict__ w,
                                                                    const float *__restrict__ b, float *__restrict__ cls, float *__restrict__ mean, float *__restrict__ tokens,
-                                                                   long out_img_stride, int N, float eps, int l2, int first, void *__restrict__ z, int z_bf16) {
+                                                                   long out_img_stride, int N, float eps, int l2, int first, void *__restrict__ z, int z_bf16, int zw /* z rows of zw * D: 2 = cls ‖ mean, 1 = the mean alone */) {
     typedef LnRow<VEC, NV> R;
     constexpr int D = 64 * VEC * NV;
     constexpr int U = D <= 1024 ? 2 : 1;          // patch rows per step of a wave
@@ -39,7 +41,7 @@ __global__ __launch_bounds__(feat_waves(64 * VEC * NV) * 64) void features_kerne
     const float *xi = x + (size_t)blockIdx.x * img_stride;
     const size_t out_off = (size_t)blockIdx.x * out_img_stride;
     float f[U][NV][VEC];
-    if ((cls || z) && wave == W - 1) {
+    if (zw == 2 && (cls || z) && wave == W - 1) {
         R::norm(xi, w, b, eps, lane, f[0]);
         if (z) {
             if (z_bf16) R::store_rne((__bf16 *)z + (size_t)blockIdx.x * 2 * D, lane, f[0]);
@@ -89,12 +91,14 @@ __global__ __launch_bounds__(feat_waves(64 * VEC * NV) * 64) void features_kerne
 #pragma unroll
         for (int j = 0; j < VEC; ++j) f[0][i][j] = pool[R::col(i, lane) + j] / cnt;
     if (z) {
-        if (z_bf16) R::store_rne((__bf16 *)z + (size_t)blockIdx.x * 2 * D + D, lane, f[0]);
-        else R::store_rne((_Float16 *)z + (size_t)blockIdx.x * 2 * D + D, lane, f[0]);
+        if (z_bf16) R::store_rne((__bf16 *)z + ((size_t)blockIdx.x * zw + zw - 1) * D, lane, f[0]);
+        else R::store_rne((_Float16 *)z + ((size_t)blockIdx.x * zw + zw - 1) * D, lane, f[0]);
     }
-    if (!mean) return;
+    if (zw == 2) cls = nullptr;          // cls ‖ mean form: the class feature is stored above; the mean-only form (zw == 1) writes the pooled embedding to cls as well
+    if (!mean && !cls) return;
     if (l2) R::l2(f[0]);
-    R::store(mean + out_off, lane, f[0]);
+    if (mean) R::store(mean + out_off, lane, f[0]);
+    if (cls) R::store(cls + out_off, lane, f[0]);
 }
 
 }  // namespace
@@ -102,14 +106,15 @@ __global__ __launch_bounds__(feat_waves(64 * VEC * NV) * 64) void features_kerne
 // F of n_img images of N rows (row t of image i at x + i * img_stride + t * row_stride), T = first: cls[i * out_img_stride ..] = F[0] [D],
 // mean[i * out_img_stride ..] = mean of F[T .. N-1] [D], tokens[i * out_img_stride ..] = F[T .. N-1] [N - T][D]; any output may be nullptr.
 // z: the pooled head's operand rows [n_img][2 D] in `dtype` (kernels.h).  Row 0 is read only for cls / z, rows T .. only for mean / tokens / z.
-// hipErrorInvalidValue: no instantiation for D (layernorm_supports), first outside 0 .. N, or first = 0 with cls / z.
+// z_mean_only: z rows [D] = RNE(mean), cls (if asked for) = the mean.  hipErrorInvalidValue: no instantiation for D (layernorm_supports), first outside 0 .. N, first = 0
+// with cls / z of the cls ‖ mean form, or z_mean_only without z.
 hipError_t launch_features(const float *x, long row_stride, long img_stride, const float *w, const float *b, float *cls, float *mean, float *tokens,
-                           long out_img_stride, int n_img, int N, int D, float eps, bool l2, hipStream_t stream, int first, void *z, int dtype) {
-    if (first < 0 || first > N || (first == 0 && (cls || z))) return hipErrorInvalidValue;     // first = 0: a model without prefix tokens has no class row
-    const bool rows = mean || tokens || z;
+                           long out_img_stride, int n_img, int N, int D, float eps, bool l2, hipStream_t stream, int first, void *z, int dtype, bool z_mean_only) {
+    if (first < 0 || first > N || (first == 0 && !z_mean_only && (cls || z)) || (z_mean_only && !z)) return hipErrorInvalidValue;     // first = 0: a model without prefix tokens has no class row
+    const bool rows = mean || tokens || z;      // (the mean-only form always has z)
     const dim3 grid(n_img), blk(64 * (rows ? feat_waves(D) : 1));
     const bool ok = ln_for_width(D, [&](auto vec, auto nv) {
-        hipLaunchKernelGGL((features_kernel<vec(), nv()>), grid, blk, 0, stream, x, row_stride, img_stride, w, b, cls, mean, tokens, out_img_stride, N, eps, l2 ? 1 : 0, first, z, dtype == DT_BF16 ? 1 : 0);
+        hipLaunchKernelGGL((features_kernel<vec(), nv()>), grid, blk, 0, stream, x, row_stride, img_stride, w, b, cls, mean, tokens, out_img_stride, N, eps, l2 ? 1 : 0, first, z, dtype == DT_BF16 ? 1 : 0, z_mean_only ? 1 : 2);
     });
     return ok ? hipGetLastError() : hipErrorInvalidValue;
 }

@@ -133,14 +133,27 @@ struct SliceForward {
         const int fl = sel ? ft->flags : 0, Tp = c->Tp;
         float *o_cls = nullptr, *o_mean = nullptr, *o_tok = nullptr;
         if (sel) ft->slots(first_img, il, &o_cls, &o_mean, &o_tok);
-        if (c->map) {        // no class row: VITX_FEAT_CLS of such a context is the pooled embedding, written by pooled_tail
+        const bool zm = z && c->mean == VITX_POOL_MEAN;      // the mean-only operand form: the same launch writes the pooled embedding as the class feature
+        if (c->pooled_cls() && !zm) {        // VITX_FEAT_CLS of such a context is the pooled embedding, written by pooled_tail / mean_tail
             o_cls = nullptr;
             if (!o_mean && !o_tok) return VITX_OK;
         }
-        const double rows = (double)n * ((o_cls || z ? 1 : 0) + (o_mean || o_tok || z ? N - Tp : 0));
-        ProfScope ps(c, st, sel ? PC_FEATURES : PC_HEAD_POOL, 0, rows * D * 4 + (double)n * D * 4 * ((o_cls ? 1 : 0) + (o_mean ? 1 : 0) + (o_tok ? N - Tp : 0)) + (z ? (double)n * 2 * D * eb : 0.0));
+        const double rows = (double)n * (((o_cls || z) && !zm ? 1 : 0) + (o_mean || o_tok || z ? N - Tp : 0));
+        ProfScope ps(c, st, sel ? PC_FEATURES : PC_HEAD_POOL, 0, rows * D * 4 + (double)n * D * 4 * ((o_cls ? 1 : 0) + (o_mean ? 1 : 0) + (o_tok ? N - Tp : 0)) + (z ? (double)n * (zm ? 1 : 2) * D * eb : 0.0));
         HIP_TRY(launch_features(cls_rows ? sl.Xc : sl.X, D, cls_rows ? (long)D : (long)N * D, ws.norm_w, ws.norm_b, o_cls, o_mean, o_tok, ft ? ft->fpi : 0,
-                                n, cls_rows ? 1 : N, D, c->hp.eps, (fl & VITX_FEAT_L2) != 0, st, cls_rows ? 1 : Tp, z, dt));
+                                n, cls_rows ? 1 : N, D, c->hp.eps, (fl & VITX_FEAT_L2) != 0, st, cls_rows ? 1 : Tp, z, dt, zm));
+        return VITX_OK;
+    }
+    // The raw-mean head (VITX_POOL_MEAN_NORM; pool_mean.hip) on the n images of this sub-batch, after the last layer: the chunk sums of the raw patch
+    // rows -> Pm, then per image m, e = the final norm of m, Z = RNE(e) with its pad rows, and the VITX_FEAT_CLS feature e.  2 launches.
+    int mean_tail() {
+        float *o_cls = nullptr, *o_mean, *o_tok;
+        const Features *ft = c->feat.get();
+        const bool sel = ft && ft->selects(c->L - 1);
+        if (sel) ft->slots(first_img, c->L - 1, &o_cls, &o_mean, &o_tok);
+        ProfScope ps(c, st, PC_HEAD_POOL, 0, (double)n * (N - c->Tp) * D * 4 + (double)n * D * (eb + (o_cls ? 4 : 0)));
+        HIP_TRY(launch_pool_mean(sl.X, D, (long)N * D, n, N, c->Tp, D, ws.norm_w, ws.norm_b, c->hp.eps, sl.Pm, nullptr, o_cls, ft ? ft->fpi : 0, ft && (ft->flags & VITX_FEAT_L2), sl.Z, dt,
+                                 round_up(n, tm), st));
         return VITX_OK;
     }
     // The attention-pooling head (VITX_POOL_MAP; include/vitx.h) on the n images of this sub-batch, after the last layer: the pooling pass over the
@@ -353,7 +366,7 @@ struct SliceForward {
         }
         if ((rc = resid_gemm_ln(r, r.pc_fc2, c->glu ? sl.Hg : sl.Hbuf, Wl[W_FC2], w.fc2_b, F, Fl[W_FC2], nx ? nx->ln1_w : nullptr, nx ? nx->ln1_b : nullptr, sl.U, &fix_u))) return rc;
         if (!c->trace_ids.empty() && (rc = trace(il + 1))) return rc;
-        if ((rc = features(il, tail_now, c->pool && il + 1 == c->L ? sl.Z : nullptr))) return rc;
+        if ((rc = features(il, tail_now, (c->pool || c->mean == VITX_POOL_MEAN) && il + 1 == c->L ? sl.Z : nullptr))) return rc;
         return patch_head_rows(il);
     }
     int run(const void *d_imgs, void *d_probs, void *d_logits) {
@@ -395,7 +408,9 @@ struct SliceForward {
         // classifier: one row per image, row stride N*D; ViTSTR: groups of R consecutive token rows (stride D), group stride N*D
         // pooled head: Z [n][2 D] was written by the last layer's feature launch above (final norm of row 0 ‖ mean of the patch rows' final norm)
         // attention-pooling head: one row per image comes out of pooled_tail
-        if (c->pool) rc = VITX_OK;
+        // mean-pool head: Z [n][D] = RNE(mean of the final norm) came from the same launch; the raw-mean order runs its two launches here
+        if (c->pool || c->mean == VITX_POOL_MEAN) rc = VITX_OK;
+        else if (c->mean) rc = mean_tail();
         else if (c->map) rc = pooled_tail();             // Z = RNE(e), the attention-pooled embedding
         else if (tail) rc = layernorm(sl.Xc, D, ws.norm_w, ws.norm_b, sl.Z, n);
         else rc = layernorm(sl.X, c->R == 1 ? (long)N * D : (long)D, ws.norm_w, ws.norm_b, sl.Z, nR, c->R, (long)N * D);

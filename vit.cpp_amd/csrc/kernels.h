@@ -52,6 +52,7 @@ struct GemmArgs {
     int prefix = 1;  // EPI_PATCH: tokens of an image in front of its patches: the class token + R register tokens (an image has tpi + prefix rows); 0: none, and pos has no class row
     long hilo_off;  // EPI_BIAS_HILO: ELEMENT offset of the lo plane behind `out` (a whole number of rows; the byte offset must fit 32 bits)
     int dbg;      // ablation bits of the ring kernel's laboratory build (VITX_LAB only; 0 in the product)
+    int pos0 = 1; // EPI_PATCH: the row of pos that patch 0 takes: 1 with a class row in the table, 0 without (it fills the padding in front of Wscale)
     // q4_0 weights kept in block form (launch_gemm_q4 only): W = nibble plane [N_pad][K/2] bytes (16 per block), Wscale = f16 block
     // scales [N_pad][K/32]; both planes are the file's block_q4_0 fields re-laid out, 4.5 bits per weight
     const uint16_t *Wscale;
@@ -149,8 +150,8 @@ int gemm_tile_n();
 // X[b * N + T + t][:] = W . patch(b, t) + bias + pos[1 + t], X[b * N][:] = cls + pos[0], X[b * N + 1 + r][:] = reg[r] (no position term).
 // img: f32 HWC [n_img][img_h][img_w][Cin], both sides multiples of P, patches in raster order with img_w / P per row (Cin = 3: RGB classifier input; 1: the grey ViTSTR input, extensions/vitstr.cpp/vitstr.cpp:713-731);
 // w_perm: the [n_pad][k_pad] operand-type kernel with its K axis permuted by patch_embed_permute_k (host side, at upload); pos [1 + patches][D],
-// cls [D], reg [n_reg][D] (nullptr when n_reg == 0).  cls == nullptr (n_reg == 0): no prefix token at all -- N = patches, X[b * N + t][:] = W . patch(b, t) + bias + pos[t],
-// pos [patches][D] (a VITX_POOL_MAP model).
+// cls [D], reg [n_reg][D] (nullptr when n_reg == 0).  cls == nullptr: no class token -- T = n_reg (0 or more), X[b * N + r][:] = reg[r], X[b * N + T + t][:] = W . patch(b, t) +
+// bias + pos[t], pos [patches][D] (a VITX_POOL_MAP model, or a mean-pool model without a class token).
 hipError_t launch_patch_embed(int dtype, const float *img, const void *w_perm, const float *bias, const float *pos, const float *cls, const float *reg, int n_reg,
                               float *X, int n_img, int img_h, int img_w, int P, int Cin, int D, int n_pad, int k_pad, hipStream_t stream);
 void patch_embed_permute_k(const uint16_t *w, uint16_t *w_perm, int N, int Cin, int P, int k_pad);
@@ -204,9 +205,20 @@ hipError_t launch_rollout_row_packed(const float *cls, long cfpt, int cslot, con
 // only for mean / tokens / z, rows 1 .. T-1 never); l2: cls and mean divided by their norm.
 // z != nullptr: the pooled head's operand (VITX_POOL_CLS_MEAN), z[i][0 .. D) = RNE(F[0]), z[i][D .. 2 D) = RNE(mean) in the operand type `dtype`,
 // rows of 2 D elements, rounded BEFORE any l2 -- the same launch that serves the features.
+// z_mean_only (VITX_POOL_MEAN): z rows are [D] = RNE(mean) alone, row 0 is not read for z, first = 0 is allowed with z, and cls != nullptr receives the
+// mean as well (the pooled embedding is such a context's VITX_FEAT_CLS).
 // Every width of VITX_LN_WIDTHS; pointers 16-byte aligned, strides multiples of 4 floats.
 hipError_t launch_features(const float *x, long row_stride, long img_stride, const float *w, const float *b, float *cls, float *mean, float *tokens,
-                           long out_img_stride, int n_img, int N, int D, float eps, bool l2, hipStream_t stream, int first = 1, void *z = nullptr, int dtype = DT_F16);
+                           long out_img_stride, int n_img, int N, int D, float eps, bool l2, hipStream_t stream, int first = 1, void *z = nullptr, int dtype = DT_F16, bool z_mean_only = false);
+// The raw-mean head (pool_mean.hip; include/vitx.h "the mean-pool head", VITX_POOL_MEAN_NORM): m[i] = the mean of the raw rows first .. N-1 of image i (read as
+// launch_features reads them), e[i] = LnRow::norm(m[i]) with w, b, eps, z[i] = RNE(e[i]) in `dtype`, rows of D elements; rows n_img .. m_pad - 1 of z are written
+// as zeros.  Two launches: the part kernel, one workgroup per (image, chunk of kPoolMeanChunkRows rows), writes column sums to part [n_img][pool_mean_chunks(N - first)][D]
+// f32; the combine kernel adds an image's chunks in ascending order and divides once.  m [n_img][D] and e (row i at e + i * e_stride; l2: divided by its norm) may be
+// nullptr.  Every width of VITX_LN_WIDTHS, 0 <= first < N; hipErrorInvalidValue otherwise.
+constexpr int kPoolMeanChunkRows = VITX_POOL_MEAN_CHUNK_ROWS;
+constexpr int pool_mean_chunks(int rows) { return (rows + kPoolMeanChunkRows - 1) / kPoolMeanChunkRows; }
+hipError_t launch_pool_mean(const float *x, long row_stride, long img_stride, int n_img, int N, int first, int D, const float *w, const float *b, float eps, float *part,
+                            float *m, float *e, long e_stride, bool l2, void *z, int dtype, int m_pad, hipStream_t stream);
 // The pooling kernel of the attention-pooling head (attention_pool.hip; include/vitx.h "no class token and the attention-pooling head"): with F[t] the
 // f32 final-norm row of token t (launch_features' F, same statistics and operation order), s_{h,t} = u_h . F[t], p_h = softmax_t(s_h),
 // M_h = sum_t p_{h,t} F[t], all f32.  Row t of image i is read at x + i * img_stride + t * row_stride; u [H][D] f32.  Outputs, each may be nullptr:

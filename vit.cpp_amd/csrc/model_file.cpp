@@ -16,6 +16,8 @@
 // One more (include/vitx.h "rotary position embeddings"): `rope` f32 [4] = {kind, theta, 0, 0} of a DINOv3-class model; its pos_embed is all zero.
 // One more (include/vitx.h "gated MLP"): `glu` f32 [4] = {kind, F, 0, 0} in front of the first blocks.* record; mlp.fc1.* then has 2 F rows and
 // mlp.fc2.weight rows of F.
+// One more (include/vitx.h "the mean-pool head"): `pool` f32 [4] = {1, order, 0, 0} in front of the first blocks.* record; cls_token is then optional, and a file
+// without it has a pos_embed of g^2 rows and its reg_token rows (if any) at the front of an image.
 // A text-tower file (include/vitx.h "the text tower") is told by patch_size == 0: token_embed.weight [V][D] (f16 or f32) and pos_embed [T][D]
 // in place of the image front, the same blocks, norm.* and head.* [E][D]; `arch` is then required and its last two slots are {causal, eos + 1};
 // `zs` f32 [4] = {kind, scale, bias, 0} is optional.  cls_token, reg_token, pre_norm.*, preproc and attn_pool.* do not belong in one.
@@ -185,6 +187,7 @@ static int load_impl(const char *path, vitx_model &m) {
     auto pool_expect = text ? std::map<std::string, Expect>() : pool_tensors(hp);       // (`mlp` rewrites the MLP shapes of both maps)
     int n_optional = 0;                                              // `arch`, `preproc`, `pre_norm.*` records seen
     int n_pool = 0;                                                  // `attn_pool.*` records seen
+    int pool_order = -1;                                             // `pool`: 0 norm then mean, 1 mean then norm; -1: no such record
     bool pos_no_cls = false;                                         // pos_embed has g^2 rows (no class row)
     bool seen_block = false;                                         // a blocks.* record has been read
     for (;;) {
@@ -332,6 +335,26 @@ static int load_impl(const char *path, vitx_model &m) {
             ++n_optional;
             continue;
         }
+        if (t.name == "pool") {                                      // optional: f32 [4] = {1, order, 0, 0} (include/vitx.h "the mean-pool head")
+            if (m.index.count(t.name)) { set_error("vitx_model_load: duplicate tensor '%s'", t.name.c_str()); return VITX_ERR_FORMAT; }
+            if (text) { set_error("vitx_model_load: text-tower file: tensor 'pool' belongs to image files"); return VITX_ERR_FORMAT; }
+            if (ttype != T_F32 || n_dims != 1 || t.ne[0] != 4) {
+                set_error("vitx_model_load: tensor 'pool' must be f32 [4] = {1, order, 0, 0}: got type %d, %d dims [%lld, ..]", ttype, n_dims, (long long)t.ne[0]);
+                return VITX_ERR_FORMAT;
+            }
+            if (seen_block) { set_error("vitx_model_load: tensor 'pool' stands behind a blocks.* record: it must come in front of the first one"); return VITX_ERR_FORMAT; }
+            t.raw.resize(16);
+            if (fread(t.raw.data(), 1, 16, f) != 16) { set_error("vitx_model_load: tensor '%s' is truncated", t.name.c_str()); return VITX_ERR_IO; }
+            float a[4]; memcpy(a, t.raw.data(), 16);
+            if (a[0] != 1.0f) { set_error("vitx_model_load: tensor 'pool' names kind %g: only 1 (the mean of the patch rows) exists", (double)a[0]); return VITX_ERR_FORMAT; }
+            if (a[1] != 0.0f && a[1] != 1.0f) { set_error("vitx_model_load: tensor 'pool' names order %g: 0 (final norm, then the mean) and 1 (the mean, then the norm) exist", (double)a[1]); return VITX_ERR_FORMAT; }
+            if (a[2] != 0.0f || a[3] != 0.0f) { set_error("vitx_model_load: tensor 'pool' has reserved slots {%g, %g}: they must be 0", (double)a[2], (double)a[3]); return VITX_ERR_FORMAT; }
+            pool_order = (int)a[1];
+            m.index[t.name] = (int)m.tensors.size();
+            m.tensors.push_back(std::move(t));
+            ++n_optional;
+            continue;
+        }
         if (t.name == "preproc") {                                   // optional: f32 [16], the model's own preprocessing (include/vitx.h "each model's own preprocessing")
             if (m.index.count(t.name)) { set_error("vitx_model_load: duplicate tensor '%s'", t.name.c_str()); return VITX_ERR_FORMAT; }
             if (ttype != T_F32 || n_dims != 1 || t.ne[0] != 16) {
@@ -418,8 +441,16 @@ static int load_impl(const char *path, vitx_model &m) {
     if (m.has_preproc && m.in_chans == 1) { set_error("vitx_model_load: tensor 'preproc' in a one-channel (ViTSTR) file: its preprocessing is fixed"); return VITX_ERR_FORMAT; }
     if (!m.has_preproc) m.preproc = pp_default(hp.img_size);
     // the attention-pooling head: all thirteen tensors, no class or register token, a position table without a class row -- or none of it
-    const bool has_cls = m.find("cls_token") != nullptr;
-    if (n_pool) {
+    const bool has_cls = m.has_cls = m.find("cls_token") != nullptr;
+    if (pool_order >= 0) {                                           // the mean-pool head: cls_token is optional, the position table follows it
+        if (n_pool) { set_error("vitx_model_load: tensor 'pool' together with attn_pool.*: a file has one pooling head"); return VITX_ERR_FORMAT; }
+        if (m.head_pool != VITX_POOL_CLS) { set_error("vitx_model_load: tensor 'pool' together with a [C][2 D] head: the mean-pool head reads one row [D]"); return VITX_ERR_FORMAT; }
+        if (pos_no_cls == has_cls && m.find("pos_embed")) {
+            set_error("vitx_model_load: tensor 'pos_embed' does not fit: a mean-pool file %s a class token has %s rows", has_cls ? "with" : "without", has_cls ? "1 + g^2" : "g^2");
+            return VITX_ERR_FORMAT;
+        }
+        m.head_pool = pool_order ? VITX_POOL_MEAN_NORM : VITX_POOL_MEAN;
+    } else if (n_pool) {
         if (m.rope_kind) { set_error("vitx_model_load: tensor 'rope' together with attn_pool.*: the attention-pooling head has no rotary form"); return VITX_ERR_FORMAT; }
         if (m.glu_kind) { set_error("vitx_model_load: tensor 'glu' together with attn_pool.*: the attention-pooling head's MLP has no gated form"); return VITX_ERR_FORMAT; }
         for (const auto &kv : pool_expect)
@@ -432,7 +463,7 @@ static int load_impl(const char *path, vitx_model &m) {
         if (!has_cls) { set_error("vitx_model_load: tensor 'cls_token' is missing (only a file with the attn_pool.* tensors has no class token)"); return VITX_ERR_FORMAT; }
         if (pos_no_cls) { set_error("vitx_model_load: tensor 'pos_embed' has no class row, but the file has a class token"); return VITX_ERR_FORMAT; }
     }
-    const size_t n_expect = expect.size() - (n_pool ? 1 : 0) + (size_t)n_pool + (m.num_registers ? 1 : 0) + (size_t)n_optional;
+    const size_t n_expect = expect.size() - (has_cls ? 0 : 1) + (size_t)n_pool + (m.num_registers ? 1 : 0) + (size_t)n_optional;
     if (m.tensors.size() != n_expect) {
         set_error("vitx_model_load: model file has %d tensors, but %d tensors were expected", (int)m.tensors.size(), (int)n_expect);
         return VITX_ERR_FORMAT;
@@ -491,7 +522,7 @@ int vitx_model_num_labels(const vitx_model *m) { return m ? (int)m->id2label.siz
 int vitx_model_in_channels(const vitx_model *m) { return m ? m->in_chans : 0; }
 int vitx_model_num_registers(const vitx_model *m) { return m ? m->num_registers : 0; }
 int vitx_model_head_pool(const vitx_model *m) { return m ? m->head_pool : 0; }
-int vitx_model_num_prefix(const vitx_model *m) { return m ? (m->head_pool == VITX_POOL_MAP ? 0 : 1 + m->num_registers) : 0; }
+int vitx_model_num_prefix(const vitx_model *m) { return m ? m->num_prefix() : 0; }
 // u_h = Wk_h^T q_h / sqrt(d), q = Wq latent + bq, in double from the file's f32 decode; rounded once to f32 (include/vitx.h)
 int vitx_model_pool_query(const vitx_model *m, float *out) {
     if (!m || !out) { vitx::set_error("vitx_model_pool_query: NULL argument"); return VITX_ERR_ARG; }

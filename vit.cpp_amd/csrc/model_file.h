@@ -34,6 +34,10 @@ struct vitx_model {
     int num_registers = 0;                            // R of an optional `reg_token` [1][R][D]: tokens between the class token and the patches
     int head_pool = VITX_POOL_CLS;                    // VITX_POOL_CLS_MEAN: head.weight is [C][2 D], over concat(cls, mean of the patch tokens);
                                                       // VITX_POOL_MAP: the thirteen attn_pool.* tensors, no cls_token, pos_embed of g^2 rows
+    // VITX_POOL_MEAN / VITX_POOL_MEAN_NORM: `pool` [4] = {1, order, 0, 0}, the head reads the mean of the patch rows (include/vitx.h "the mean-pool head")
+    bool has_cls = true;                              // the file has cls_token (image files; false: VITX_POOL_MAP, or a mean-pool file without one)
+    int num_prefix() const { return (has_cls ? 1 : 0) + num_registers; }      // T: rows in front of an image's patches
+    bool mean_pool() const { return head_pool == VITX_POOL_MEAN || head_pool == VITX_POOL_MEAN_NORM; }
     int activation = VITX_ACT_GELU_TANH;              // MLP activation, from an optional `arch` [4] = {activation, eps, 0, 0}; hp.eps carries its eps
     bool has_pre_norm = false;                        // `pre_norm.weight` / `pre_norm.bias` [D]: LayerNorm of every token row in front of layer 0
     int rope_kind = VITX_ROPE_NONE;                   // `rope` [4] = {kind, theta, 0, 0}: rotary position embeddings on q and k of the patch tokens (include/vitx.h)

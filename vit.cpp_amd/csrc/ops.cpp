@@ -356,6 +356,25 @@ int vitx_op_patch_embed_rect(int dtype, const void *d_img, const void *d_w, cons
                              int n_img, int img_h, int img_w, int P, int Cin, int D, void *d_X) {
     return op_patch_embed("vitx_op_patch_embed_rect", dtype, d_img, d_w, d_bias, d_pos, d_cls, d_reg, R, d_X, n_img, img_h, img_w, P, Cin, D, nullptr);
 }
+// The raw-mean head's two kernels on their own (TEST ONLY: allocates the chunk scratch, runs on the null stream and synchronises).  Every argument
+// check comes before the first device call.
+int vitx_op_pool_mean(int dtype, const void *d_x, long row_stride, long img_stride, const void *d_ln_w, const void *d_ln_b, float eps, void *d_m, void *d_e, void *d_z,
+                      int n_img, int m_pad, int N, int first, int D) {
+    if (!d_x || !d_ln_w || !d_ln_b || !d_z || n_img <= 0 || m_pad < n_img || N <= 0 || first < 0 || first >= N || D <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) {
+        set_error("vitx_op_pool_mean: invalid argument (0 <= first < N, m_pad >= n_img)"); return VITX_ERR_ARG;
+    }
+    for (const void *p : {d_x, d_ln_w, d_ln_b, (const void *)d_m, (const void *)d_e, (const void *)d_z})
+        if ((uintptr_t)p % 16) { set_error("vitx_op_pool_mean: pointers must be 16-byte aligned"); return VITX_ERR_ARG; }
+    if (row_stride % 4 || img_stride % 4) { set_error("vitx_op_pool_mean: strides must be multiples of 4 floats"); return VITX_ERR_ARG; }
+    if (!layernorm_supports(D)) { set_error("vitx_op_pool_mean: hidden size %d has no LayerNorm instantiation", D); return VITX_ERR_UNSUPPORTED; }
+    float *part = nullptr;
+    if (hipMalloc((void **)&part, (size_t)n_img * pool_mean_chunks(N - first) * D * 4) != hipSuccess) { set_error("vitx_op_pool_mean: cannot allocate the chunk scratch"); return VITX_ERR_NOMEM; }
+    const DevMem part_own(part);
+    hipError_t e = launch_pool_mean((const float *)d_x, row_stride, img_stride, n_img, N, first, D, (const float *)d_ln_w, (const float *)d_ln_b, eps, part, (float *)d_m, (float *)d_e, D,
+                                    false, d_z, dtype, m_pad, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    return op_rc("vitx_op_pool_mean", e);
+}
 // The pooling kernel of the attention-pooling head on its own.  Every argument check comes before the first device call.
 int vitx_op_attention_pool(const void *d_x, long row_stride, long img_stride, const void *d_ln_w, const void *d_ln_b, float eps, const void *d_u, void *d_M, void *d_p,
                            int n_img, int N, int D, int H, void *stream) {

@@ -191,7 +191,7 @@ int vitx_attn_enable(vitx_ctx *c, uint64_t layer_mask, int flags) {
     if (c->L < 64 && (layer_mask >> c->L)) { set_error("vitx_attn_enable: layer mask 0x%llx names layers beyond the model's %d", (unsigned long long)layer_mask, c->L); return VITX_ERR_ARG; }
     const bool on = layer_mask != 0 || flags != 0, rollout = (flags & VITX_ATTN_ROLLOUT) != 0;
     if (on && c->R != 1) { set_error("vitx_attn_enable: attention maps are not available for ViTSTR contexts"); return VITX_ERR_UNSUPPORTED; }
-    if (on && c->map) { set_error("vitx_attn_enable: the maps are defined by the class-token row, and a model with the attention-pooling head has no class token"); return VITX_ERR_UNSUPPORTED; }
+    if (on && !c->has_cls) { set_error("vitx_attn_enable: the maps are defined by the class-token row, and this model (attention-pooling head, or a mean-pool file without cls_token) has no class token"); return VITX_ERR_UNSUPPORTED; }
     if (on && !attention_map_supports(c->N, c->D, c->H)) { set_error("vitx_attn_enable: head_dim %d is not covered by the map kernels", c->D / c->H); return VITX_ERR_UNSUPPORTED; }
     if (rollout && !attention_mean_supports(c->N, c->D, c->H)) { set_error("vitx_attn_enable: rollout keeps two N x N matrices per image and takes at most %d tokens (this model: %d)", kAttnMeanMaxTokens, c->N); return VITX_ERR_UNSUPPORTED; }
     if (const int rc = quiesce(c)) return rc;
@@ -227,8 +227,8 @@ int vitx_feat_enable(vitx_ctx *c, int flags, uint64_t layer_mask) {
     c->feat.reset();
     if (!flags) return VITX_OK;
     if (!layer_mask) layer_mask = 1ull << (c->L - 1);
-    if (c->map && (flags & VITX_FEAT_CLS) && layer_mask != 1ull << (c->L - 1)) {      // the one refusal that comes after the free: the features are off now
-        set_error("vitx_feat_enable: VITX_FEAT_CLS of a model with the attention-pooling head is the pooled embedding: it exists for the last layer only (mask 0x%llx)", (unsigned long long)layer_mask);
+    if (c->pooled_cls() && (flags & VITX_FEAT_CLS) && layer_mask != 1ull << (c->L - 1)) {      // the one refusal that comes after the free: the features are off now
+        set_error("vitx_feat_enable: VITX_FEAT_CLS of a model with the attention-pooling or the mean-pool head is the pooled embedding: it exists for the last layer only (mask 0x%llx)", (unsigned long long)layer_mask);
         return VITX_ERR_ARG;
     }
     auto ft = std::make_unique<Features>(flags, layer_mask, c->D, c->N - c->Tp, c->L);
@@ -450,7 +450,7 @@ int vitx_depth_set(vitx_ctx *c, const float *Wp, const float *Wc, const float *b
         if (const int rc = patch_head_shape(c, "vitx_depth_set", &oh, &ow)) return rc;
         if (const int rc = depth_head_values("vitx_depth_set", Wp, Wc, bias, bins, K, Dc, min_depth, max_depth, upsample)) return rc;
         if (c->R != 1) { set_error("vitx_depth_set: the depth head is not available for ViTSTR contexts"); return VITX_ERR_UNSUPPORTED; }
-        if (Wc && c->map) { set_error("vitx_depth_set: a class half on a context without a class token (VITX_POOL_MAP)"); return VITX_ERR_UNSUPPORTED; }
+        if (Wc && !c->has_cls) { set_error("vitx_depth_set: a class half on a context without a class token (VITX_POOL_MAP, or a mean-pool file without cls_token)"); return VITX_ERR_UNSUPPORTED; }
         if (oh < fh || ow < fw || oh > kDepthMaxOut || ow > kDepthMaxOut) {
             set_error("vitx_depth_set: output %d x %d outside the fine plane %d x %d .. %d (upsampling only)", oh, ow, fh, fw, kDepthMaxOut);
             return VITX_ERR_UNSUPPORTED;

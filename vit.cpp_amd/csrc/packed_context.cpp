@@ -159,6 +159,7 @@ int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_im
     if (attn_kernel < VITX_PACK_ATTN_AUTO || attn_kernel > VITX_PACK_ATTN_STAGED) { set_error("vitx_pack_create: unknown attn_kernel %d (0 auto, 1 generic, 2 staged)", attn_kernel); return VITX_ERR_ARG; }
     const int pool_head = opt ? opt->pool_head : 0;
     if (pool_head != 0 && pool_head != VITX_PACK_POOL_MAP && pool_head != VITX_PACK_POOL_CLS_MEAN) { set_error("vitx_pack_create: unknown pool_head %d (0 the class-token head, 1 the attention-pooling head, 2 the cls + mean head)", pool_head); return VITX_ERR_ARG; }
+    if (m->mean_pool()) { set_error("vitx_pack_create: packed contexts do not take files with the mean-pool head (`pool`) yet, with any pool_head"); return VITX_ERR_UNSUPPORTED; }
     const bool pool_map = pool_head == VITX_PACK_POOL_MAP, pool_cm = pool_head == VITX_PACK_POOL_CLS_MEAN;
     if (pool_map && m->head_pool != VITX_POOL_MAP) { set_error("vitx_pack_create: pool_head = 1 takes a file with the attention-pooling head; this file has another head"); return VITX_ERR_ARG; }
     if (pool_cm && m->head_pool != VITX_POOL_CLS_MEAN) { set_error("vitx_pack_create: pool_head = 2 takes a file with the pooled (cls + mean) head; this file has another head"); return VITX_ERR_ARG; }

@@ -199,7 +199,7 @@ int upload_image(const Upload &u) {
     const int D = u.D, tn = u.tn;
     const bool pool = m->head_pool == VITX_POOL_CLS_MEAN, map = m->head_pool == VITX_POOL_MAP;
     int rc;
-    if (!map && (rc = upload_f32(u, u.T("cls_token"), &ws.cls))) return rc;
+    if (m->has_cls && (rc = upload_f32(u, u.T("cls_token"), &ws.cls))) return rc;
     if (m->num_registers && (rc = upload_f32(u, u.T("reg_token"), &ws.reg))) return rc;
     if ((rc = upload_f32(u, u.T("pos_embed"), &ws.pos))) return rc;
     if (m->has_pre_norm && ((rc = upload_f32(u, u.T("pre_norm.weight"), &ws.pre_w)) || (rc = upload_f32(u, u.T("pre_norm.bias"), &ws.pre_b)))) return rc;

@@ -85,6 +85,7 @@ class ModelFile:
 ACT_TANH, ACT_ERF, ACT_QUICK = 0, 1, 2                  # enum vitx_activation (slot 0 of `arch`): tanh-GELU, erf-GELU, QuickGELU
 ZS_SOFTMAX, ZS_SIGMOID = 0, 1                           # enum vitx_zs_kind: CLIP's softmax over the classes, SigLIP's sigmoid per class
 POOL_CLS, POOL_CLS_MEAN, POOL_MAP = 0, 1, 2             # enum vitx_head_pool: the head reads the class token, concat(cls, mean of the patches), or the pooled embedding
+POOL_MEAN, POOL_MEAN_NORM = 3, 4                       # ... or the mean of the patch rows: of the final norm (`pool` order 0), or of the raw rows, then normalised (order 1)
 PP_REF_BICUBIC, PP_REF_BILINEAR, PP_PIL_BILINEAR, PP_PIL_BICUBIC = 0, 1, 2, 3      # enum vitx_pp_filter: the reference's two, Pillow's Image.resize on u8
 PP_STRETCH, PP_SHORTEST_EDGE = 0, 1                                                # enum vitx_pp_resize
 
@@ -267,7 +268,8 @@ def write_model(path: str, hp: HParams, tensors: Dict[str, np.ndarray], id2label
     (convert-pth-to-ggml.py:141-148).  ftype in {2,3,6,7,8} additionally quantises the 2-D
     '*weight' tensors exactly like quantize.cpp:207-303 does to an f16 file.
     registers / head_pool (optional) state what the caller means to write -- R register tokens (`reg_token` [1][R][D], f32, directly
-    after cls_token) and the head kind (0 class token: head.weight [C][D]; 1 cls + mean: [C][2 D]) -- and are checked against `tensors`.
+    after cls_token) and the head kind (0 class token, 3 / 4 mean-pool: head.weight [C][D]; 1 cls + mean: [C][2 D]) -- and are checked against `tensors`.
+    `pool` = [1, order, 0, 0] (a mean-pool file; include/vitx.h) stands in front of the first blocks.* tensor; cls_token is then optional.
     preproc (optional): the 16 slots of the `preproc` tensor (preproc_slots), written directly after `arch`; None writes the file without it."""
     tensors = with_preproc(tensors, preproc)
     D = hp.hidden_size
@@ -275,7 +277,9 @@ def write_model(path: str, hp: HParams, tensors: Dict[str, np.ndarray], id2label
     if "reg_token" in tensors:
         if tuple(np.shape(tensors["reg_token"])) != (1, have_r, D) or have_r < 1:
             raise ValueError(f"reg_token must be [1][R][{D}] with R >= 1, got {np.shape(tensors['reg_token'])}")
-        if list(tensors)[list(tensors).index("reg_token") - 1] != "cls_token":
+        if "cls_token" not in tensors and "pool" not in tensors:
+            raise ValueError("reg_token without cls_token: only a mean-pool file (`pool`) has registers and no class token")
+        if "cls_token" in tensors and list(tensors)[list(tensors).index("reg_token") - 1] != "cls_token":
             raise ValueError("reg_token is written directly after cls_token")
     if registers is not None and registers != have_r:
         raise ValueError(f"registers={registers}, but the tensors hold {have_r} register tokens")
@@ -290,8 +294,15 @@ def write_model(path: str, hp: HParams, tensors: Dict[str, np.ndarray], id2label
         hw = np.shape(tensors["head.weight"])
         if len(hw) != 2 or hw[1] not in (D, 2 * D):
             raise ValueError(f"head.weight must be [C][{D}] (class-token head) or [C][{2 * D}] (cls + mean head), got {hw}")
-        if head_pool is not None and hw[1] != (2 * D if head_pool else D):
+        if head_pool is not None and hw[1] != (D if head_pool in (POOL_CLS, POOL_MEAN, POOL_MEAN_NORM) else 2 * D):
             raise ValueError(f"head_pool={head_pool}, but head.weight is {hw}")
+    if "pool" in tensors:
+        pool = np.asarray(tensors["pool"], np.float32).reshape(-1)
+        if pool.shape != (4,) or pool[0] != 1 or pool[1] not in (0, 1) or pool[2] != 0 or pool[3] != 0:
+            raise ValueError(f"pool must be [1, order, 0, 0] with order 0 or 1, got {pool}")
+        names = list(tensors)
+        if any(k.startswith("blocks.") for k in names[:names.index("pool")]):
+            raise ValueError("pool is written in front of the first blocks.* tensor")
     if "glu" in tensors:
         glu = np.asarray(tensors["glu"], np.float32).reshape(-1)
         F = int(glu[1]) if glu.shape == (4,) else 0

@@ -63,11 +63,13 @@ def gflop_per_image(hp: HParams, glu: int = 0) -> float:
 
 
 def make_weights(hp: HParams, seed: int = 1234, head_scale: float = 8.0, in_chans: int = 3, registers: int = 0, head_pool: int = 0,
-                 reg_scale: float = 1.0, glu: int = 0) -> Dict[str, np.ndarray]:
+                 reg_scale: float = 1.0, glu: int = 0, cls_token: bool = True) -> Dict[str, np.ndarray]:
     """registers > 0 adds `reg_token` [1][R][D] (x reg_scale), head_pool = 1 widens head.weight to [C][2 D] (cls ‖ mean of the patch tokens).
     Both are drawn AFTER every draw of the plain model, so files without them keep their bytes (tests/golden/weights_sha1.json).
     glu = F > 0: a gated MLP of hidden width F (include/vitx.h "gated MLP") -- `glu` = {1, F, 0, 0} in front, mlp.fc1 [2 F][D] / [2 F] (gate rows, then
-    up rows) and mlp.fc2.weight [D][F]; such a file draws other numbers than the plain one from the first block on."""
+    up rows) and mlp.fc2.weight [D][F]; such a file draws other numbers than the plain one from the first block on.
+    head_pool = 3 / 4 (POOL_MEAN / POOL_MEAN_NORM): the `pool` tensor {1, order, 0, 0} in front, head.weight stays [C][D]; cls_token=False (such a file only)
+    drops the class token and the class row of pos_embed -- nothing new is drawn, so every other tensor keeps its numbers."""
     rng = np.random.default_rng(seed)
     D, L, C, P = hp.hidden_size, hp.num_hidden_layers, hp.num_classes, hp.patch_size
     N = hp.n_tokens
@@ -97,7 +99,7 @@ def make_weights(hp: HParams, seed: int = 1234, head_scale: float = 8.0, in_chan
     t["norm.weight"] = vec(D, 1.0); t["norm.bias"] = vec(D)
     t["head.weight"] = (mat(C, D) * np.float32(head_scale)).astype(np.float32)
     t["head.bias"] = vec(C)
-    if head_pool:
+    if head_pool == 1:
         t["head.weight"] = np.concatenate([t["head.weight"], (mat(C, D) * np.float32(head_scale)).astype(np.float32)], axis=1)
     if registers:
         reg = (mat(1, registers, D) * np.float32(reg_scale)).astype(np.float32)
@@ -107,32 +109,39 @@ def make_weights(hp: HParams, seed: int = 1234, head_scale: float = 8.0, in_chan
             if k == "cls_token":
                 out["reg_token"] = reg
         t = out
+    if head_pool in (3, 4):
+        t = {"pool": np.array([1, head_pool - 3, 0, 0], np.float32), **t}
+        if not cls_token:
+            del t["cls_token"]
+            t["pos_embed"] = np.ascontiguousarray(t["pos_embed"][:, 1:])
+    elif not cls_token:
+        raise ValueError("cls_token=False takes head_pool 3 or 4 (a mean-pool file)")
     return t
 
 
 def write_synthetic(path: str, name: str, ftype: int = 1, seed: int = 1234, head_scale: float = 8.0, registers: int = 0, head_pool: int = 0,
-                    preproc=None) -> HParams:
+                    preproc=None, cls_token: bool = True) -> HParams:
     """preproc: the 16 slots of a `preproc` tensor (ggml_file.preproc_slots) for the file to carry; None = a file without one."""
     hp = hparams_for(name, ftype)
     ic = IN_CHANS.get(name, 3)
-    write_model(path, hp, make_weights(hp, seed, head_scale, in_chans=ic, registers=registers, head_pool=head_pool), ftype=ftype,
+    write_model(path, hp, make_weights(hp, seed, head_scale, in_chans=ic, registers=registers, head_pool=head_pool, cls_token=cls_token), ftype=ftype,
                 id2label=dict(VITSTR_LABELS) if ic == 1 else None, registers=registers, head_pool=head_pool, preproc=preproc)
     return hp
 
 
 def cached_synthetic(name: str, ftype: int = 1, seed: int = 1234, head_scale: float = 8.0, cache_dir: str | None = None, registers: int = 0,
-                     head_pool: int = 0, preproc=None) -> str:
+                     head_pool: int = 0, preproc=None, cls_token: bool = True) -> str:
     """Write (once) and return the path of a synthetic model file under a scratch dir."""
     cache_dir = cache_dir or os.environ.get("VITX_CACHE", "/tmp/vitx_cache")
     os.makedirs(cache_dir, exist_ok=True)
-    ext = (f"-r{registers}" if registers else "") + ("-pool" if head_pool else "")
+    ext = (f"-r{registers}" if registers else "") + ("-pool" if head_pool == 1 else f"-pool{head_pool}" if head_pool else "") + ("" if cls_token else "-nocls")
     if preproc is not None:
         import hashlib
         ext += "-pp" + hashlib.sha1(np.asarray(preproc, "<f4").tobytes()).hexdigest()[:10]
     path = os.path.join(cache_dir, f"{name}-s{seed}-h{head_scale:g}-ft{ftype}{ext}.gguf")
     if not os.path.exists(path):
         tmp = path + f".tmp{os.getpid()}"
-        write_synthetic(tmp, name, ftype, seed, head_scale, registers, head_pool, preproc)
+        write_synthetic(tmp, name, ftype, seed, head_scale, registers, head_pool, preproc, cls_token)
         os.replace(tmp, path)
     return path
 
