@@ -493,6 +493,37 @@ int vitx_model_rope(const vitx_model *m, int *kind, float *theta);
 int vitx_model_rope_table(const vitx_model *m, int gh, int gw, float *cos_out, float *sin_out);
 int vitx_op_rope(int dtype, void *d_qkv, long lo_off, const void *d_cos, const void *d_sin, int n_img, int N, int prefix, int D, int H, void *stream);
 
+/* ---- relative position bias (BEiT, BEiT v2) ---------------------- */
+/* A file may carry `rel_bias`, f32 [Lb][H][(2g-1)^2 + 3] (torch order; g = img_size / patch_size): a learned term added to the attention scores,
+ * softmax(q k^T / sqrt(dh) + B) v, in place of an absolute position table (such a file's pos_embed is all zero).  Lb is 1 -- one table shared by
+ * every layer (BEiT's use_shared_rel_pos_bias) -- or L.  A head's row is timm's relative_position_bias_table transposed, num = (2g-1)^2 + 3 long;
+ * the index rule is timm's gen_relative_position_index (and HuggingFace BEiT's), class token first:
+ *   patch (qy, qx) -> patch (ky, kx):  (qy - ky + g - 1)(2g - 1) + (qx - kx + g - 1)
+ *   class -> patch: num - 3;   patch -> class: num - 2;   class -> class: num - 1
+ * The loader refuses (VITX_ERR_FORMAT) a file without cls_token, one that also has reg_token, `rope` or attn_pool.*, an Lb outside {1, L}, a last
+ * dimension other than (2g-1)^2 + 3, an entry that is not finite, `rel_bias` in a text-tower file and `rel_bias` behind a blocks.* record (the
+ * converter writes it in front of the first one, with `rope` / `glu` / `pool`).  vitx_quantize_file copies the tensor byte for byte.  A file
+ * without `rel_bias` loads, runs and hashes exactly as before.
+ * A context of such a file uploads the table once with the weight set and runs attention_bias.hip in every layer in place of the other attention
+ * families: the bias is added to the f32 score accumulators before the row maximum, gathered from the head's table in LDS -- a dense [H][N][N]
+ * bias never exists.  Head dim 64 only.  Every row of the last layer is evaluated (as with last_layer_all_rows: the class-row tail kernel has no
+ * bias); a VITX_F16 context uses plain fp16 q, k, v (as with f16_fast_attention).  Every head kind and every output that reads the residual stream
+ * works.  VITX_ERR_UNSUPPORTED, with a message naming the relative position bias: VITX_MXFP8, ViTSTR and packed contexts, img_size or rectangular
+ * contexts away from the file's own grid, vitx_model_resize_file, vitx_attn_enable (the maps would omit the term), another head dim, and a grid
+ * whose table does not fit the kernel's LDS (41 x 41 and up).  Contexts of every other file launch and allocate exactly what they did before.
+ *   vitx_model_rel_bias        1 and *Lb / *table_len (either may be NULL) for a file with `rel_bias`, 0 without (and for NULL)
+ *   vitx_model_rel_bias_dense  host only: out [H][N][N] f32, N = gh gw + 1, = B of `layer` (0 <= layer < L; a shared table serves every layer) by the
+ *                              index rule, for any 1 <= gh, gw <= g -- offsets are taken around the table's centre, (dy + g - 1)(2g - 1) + dx + g - 1.
+ *                              VITX_ERR_ARG for NULL, a file without `rel_bias`, a layer or a grid out of range
+ *   vitx_op_attention_bias     attention_bias.hip on device pointers: d_qkv [n_img * N][3 D] of `dtype` (VITX_F16 / VITX_BF16), N = gh gw + 1 >= 2,
+ *                              d_table f32 [H][(2 gh - 1)(2 gw - 1) + 3] by the index rule with (gh, gw) for (g, g) -> d_out [n_img * N][D].  An
+ *                              all-zero table gives the bits of vitx_op_attention_generic.  NULL, non-positive sizes, another dtype: VITX_ERR_ARG;
+ *                              a head dim other than 64 or a table beyond the LDS: VITX_ERR_UNSUPPORTED.  TEST ENTRY: null stream (it only enqueues
+ *                              there); the forward reaches the kernel with its own stream. */
+int vitx_model_rel_bias(const vitx_model *m, int *Lb, int *table_len);
+int vitx_model_rel_bias_dense(const vitx_model *m, int layer, int gh, int gw, float *out);
+int vitx_op_attention_bias(int dtype, const void *d_qkv, const void *d_table, void *d_out, int n_img, int gh, int gw, int D, int H);
+
 /* ---- gated MLP (DINOv2 ViT-g/14, DINOv3 ViT-H+) ---------------------------------- */
 /* A file may carry `glu`, f32 [4] = {kind, F, 0, 0}: the MLP of every block is then fc2( act(gate(x)) . up(x) ) with hidden width F instead of
  * fc2( act(fc1(x)) ) with hidden width 4 D.  kind 1 (VITX_GLU_SWIGLU, the only one): h = silu(gate) . up, silu(g) = g / (1 + exp(-g)).  With it every

@@ -84,6 +84,7 @@ EXPORTS = [
     "vitx_pack_pool_chunk_rows", "vitx_pack_pool_chunks", "vitx_op_attention_pool_packed", "vitx_op_attention_pool_packed_tables",
     "vitx_pack_feat_read_mean", "vitx_pack_mean_chunks", "vitx_op_feat_pool_packed", "vitx_op_feat_pool_packed_tables",
     "vitx_op_pool_mean",
+    "vitx_model_rel_bias", "vitx_model_rel_bias_dense", "vitx_op_attention_bias",
 ]
 
 
@@ -321,6 +322,10 @@ def lib():
             L.vitx_model_mlp_width.argtypes = [vp]
         if hasattr(L, "vitx_op_attention_wide"):
             L.vitx_op_attention_wide.argtypes = [ip, vp, vp, ip, ip, ip, ip]
+        if hasattr(L, "vitx_op_attention_bias"):
+            L.vitx_model_rel_bias.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
+            L.vitx_model_rel_bias_dense.argtypes = [vp, ip, ip, ip, C.POINTER(C.c_float)]
+            L.vitx_op_attention_bias.argtypes = [ip, vp, vp, vp, ip, ip, ip, ip, ip]
         if hasattr(L, "vitx_op_rope"):
             L.vitx_model_rope.argtypes = [vp, C.POINTER(ip), C.POINTER(C.c_float)]
             L.vitx_model_rope_table.argtypes = [vp, ip, ip, C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -483,6 +488,20 @@ class Model:
         """(kind, theta) of a file with a `rope` tensor (rotary position embeddings on q and k of the patch tokens), or None."""
         k, t = C.c_int(), C.c_float()
         return (k.value, t.value) if lib().vitx_model_rope(self._h, C.byref(k), C.byref(t)) else None
+
+    def rel_bias(self):
+        """(Lb, table_len) of a file with a `rel_bias` tensor (a relative position bias inside the attention: Lb tables [H][table_len], 1 = shared by
+        every layer), or None."""
+        n, t = C.c_int(), C.c_int()
+        return (n.value, t.value) if lib().vitx_model_rel_bias(self._h, C.byref(n), C.byref(t)) else None
+
+    def rel_bias_dense(self, layer: int, grid) -> np.ndarray:
+        """vitx_model_rel_bias_dense: the bias of `layer` as f32 [H, N, N], N = gh gw + 1, for a grid g or (gh, gw) up to the file's (host only)."""
+        gh, gw = _grid(grid)
+        N = max(gh, 0) * max(gw, 0) + 1
+        out = np.empty((self.hparams.num_attention_heads, N, N), np.float32)
+        check(lib().vitx_model_rel_bias_dense(self._h, layer, gh, gw, out.ctypes.data_as(C.POINTER(C.c_float))), "vitx_model_rel_bias_dense")
+        return out
 
     @property
     def glu(self):
@@ -1978,6 +1997,12 @@ def op_attention_text(dtype: int, d_qkv: int, d_out: int, n: int, T: int, D: int
 def op_attention_wide(dtype: int, d_qkv: int, d_out: int, n_img: int, N: int, D: int, H: int) -> None:
     """vitx_op_attention_wide: the LDS-staged attention of head dims 72 .. 128 on qkv [n_img * N][3 D] -> out [n_img * N][D]; null stream."""
     check(lib().vitx_op_attention_wide(dtype, d_qkv, d_out, n_img, N, D, H), "vitx_op_attention_wide")
+
+
+def attention_bias(dtype: int, d_qkv: int, d_table: int, d_out: int, n_img: int, gh: int, gw: int, D: int, H: int) -> None:
+    """vitx_op_attention_bias: attention with a relative position bias on qkv [n_img * N][3 D] -> out [n_img * N][D], N = gh gw + 1, head dim 64;
+    d_table f32 [H][(2 gh - 1)(2 gw - 1) + 3]; null stream."""
+    check(lib().vitx_op_attention_bias(dtype, d_qkv, d_table, d_out, n_img, gh, gw, D, H), "vitx_op_attention_bias")
 
 
 def zeroshot_max_classes(E: int) -> int:

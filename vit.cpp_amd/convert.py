@@ -16,6 +16,10 @@ What is converted
   SigLIP   SiglipVisionModel, SiglipModel (its vision tower): no class token, the attention-pooling head.
   DINOv3   DINOv3ViTModel (ViT-S/B/L): class token, register tokens, folded LayerScale, and rotary position embeddings -- the `rope` tensor,
            f32 [4] = {1, rope_theta, 0, 0}, beside an all-zero pos_embed (include/vitx.h "rotary position embeddings").  A backbone: the zero head.
+  BEiT     BeitForImageClassification, with --no-head BeitModel (BEiT, BEiT v2; Data2VecVision* classes are not taken), and timm Beit state dicts: the relative position bias
+           tables (one per layer, or the shared one) become the `rel_bias` tensor, f32 [Lb][H][(2g-1)^2 + 3] (include/vitx.h "relative position bias");
+           the relative_position_index buffers are dropped; the qkv bias is (q_bias, 0, v_bias); LayerScale (lambda_1 / gamma_1, ..) is folded; pos_embed
+           is zeros where the model has none.  A mean-pooling model (use_mean_pooling / fc_norm) takes --mean-pool: `pool` order 1.
   gated    DINOv2 ViT-g/14 (use_swiglu_ffn) and DINOv3 ViT-H+ (use_gated_mlp), OPT-IN: convert_hf_model(..., gated_mlp=True) / --gated-mlp.  The MLP is
            fc2(silu(gate(x)) . up(x)) with a hidden width F that is not 4 x hidden: the `glu` tensor, f32 [4] = {1, F, 0, 0}, directly after `arch` /
            `rope`; mlp.fc1 = [2 F][D], gate rows then up rows (DINOv2's weights_in as it is; DINOv3's cat(gate_proj, up_proj)), mlp.fc2 = [D][F]
@@ -499,6 +503,59 @@ LN_WIDTHS = (64, 128, 192, 256, 384, 512, 768, 1024, 1280, 1536, 320, 448, 576, 
 TEXT_MAX_TOKENS = 128
 
 
+BEIT_BLOCKS_V4 = BlockNames("encoder.layer.{i}.", _HF_QKV, "layernorm_before", "attention.output.dense", "layernorm_after", "intermediate.dense", "output.dense", "lambda_1", "lambda_2")
+BEIT_BLOCKS_V5 = BlockNames("layers.{i}.", ("attention.q_proj", "attention.k_proj", "attention.v_proj"), "layernorm_before", "attention.o_proj", "layernorm_after", "mlp.fc1", "mlp.fc2",
+                            "lambda_1", "lambda_2")
+
+
+def rel_bias_tensor(tables, heads: int) -> np.ndarray:
+    """The file's `rel_bias` [Lb][H][(2g-1)^2 + 3] (include/vitx.h "relative position bias") from Lb relative_position_bias_table tensors [num][H]: one
+    shared by every layer, or one per layer in layer order; each is transposed, so that a head's entries are contiguous."""
+    rb = np.stack([np.asarray(t, np.float32).T for t in tables])
+    side = int(round((rb.shape[2] - 3) ** 0.5))
+    if rb.shape[1] != heads or side % 2 == 0 or side * side + 3 != rb.shape[2] or not np.isfinite(rb).all():
+        raise ValueError(f"relative_position_bias_table {rb.shape[::-1][:2]}: expected finite [(2g-1)^2 + 3][{heads}]")
+    return np.ascontiguousarray(rb)
+
+
+def beit_state_dict_to_timm(sd: Dict[str, np.ndarray], cfg, no_head: bool = False, mean_pool: bool = False) -> Dict[str, np.ndarray]:
+    """An HF BeitForImageClassification (or, no_head, BeitModel) state dict under the file's names.  The relative position bias tables -- one per layer, or
+    the shared one -- become `rel_bias` in front; the relative_position_index buffers are dropped (the index rule is the file format's); key has no bias
+    in BEiT, so the fused qkv bias is (q_bias, 0, v_bias); lambda_1 / lambda_2 (LayerScale) are folded; without absolute position embeddings pos_embed
+    is a table of zeros.  A mean-pooling model (use_mean_pooling) has its norm in the pooler, behind the mean: mean_pool=True writes it as norm.* with
+    `pool` order 1.  The two namings of the blocks are told apart by probing for transformers 5's `layers.0`."""
+    pre = "beit." if any(k.startswith("beit.") for k in sd) else ""
+    e, D, L = pre + "embeddings.", int(cfg.hidden_size), int(cfg.num_hidden_layers)
+    v5 = pre + "layers.0.attention.q_proj.weight" in sd
+    names = BEIT_BLOCKS_V5 if v5 else BEIT_BLOCKS_V4
+    if pre + names.layer.format(i=0) + names.ls1 not in sd:
+        names = names._replace(ls1="", ls2="")
+    shared = pre + ("shared_position_bias." if v5 else "encoder.relative_position_bias.") + "relative_position_bias_table"
+    per_layer = ("relative_position_bias." if v5 else "attention.attention.relative_position_bias.") + "relative_position_bias_table"
+    tables = [sd[shared]] if shared in sd else [sd.get(pre + names.layer.format(i=i) + per_layer) for i in range(L)]
+    if any(t is None for t in tables):
+        raise ValueError("a BEiT model without relative position bias tables (use_relative_position_bias / use_shared_relative_position_bias) is a plain ViT: not this mapper's")
+    pooled = bool(getattr(cfg, "use_mean_pooling", False)) and pre + "pooler.layernorm.weight" in sd
+    if pooled != mean_pool:
+        raise ValueError("this BEiT model classifies the mean of the patch tokens behind fc_norm (use_mean_pooling): pass mean_pool=True / --mean-pool" if pooled else
+                         "mean_pool=True: this BEiT model reads its class token (use_mean_pooling is off)")
+    _require_mlp_4x(cfg, "intermediate_size", 4 * D)
+    sd = dict(sd)
+    for i in range(L):                                    # key has no bias
+        sd[pre + names.layer.format(i=i) + names.qkv[1] + ".bias"] = np.zeros((D,), np.float32)
+    out = {"rel_bias": rel_bias_tensor(tables, int(cfg.num_attention_heads)), "cls_token": sd[e + "cls_token"]}
+    g = int(round((out["rel_bias"].shape[2] - 3) ** 0.5) + 1) // 2
+    out["pos_embed"] = sd[e + "position_embeddings"] if e + "position_embeddings" in sd else np.zeros((1, 1 + g * g, D), np.float32)
+    _put(out, "patch_embed.proj", sd, e + "patch_embeddings.projection")
+    map_blocks(out, sd, names, L, pre)
+    _put(out, "norm", sd, pre + ("pooler.layernorm" if pooled else "layernorm"))
+    if no_head:
+        _zero_head(out, D)
+    else:
+        _put(out, "head", sd, "classifier")
+    return _f32(_with_pool(out, 1) if pooled else out)
+
+
 def _text_prefix(sd) -> str:
     pre = next((p for p in ("text_model.", "") if p + "embeddings.token_embedding.weight" in sd), None)
     if pre is None:
@@ -554,16 +611,17 @@ _CLIP = Family("CLIP", clip_state_dict_to_timm, 1, lambda cfg, E: {i: f"dim_{i}"
 _SIGLIP = Family("SigLIP", lambda sd, cfg, no_head, mlp_width=False: siglip_state_dict_to_timm(sd, cfg, mlp_width), 0, None, "never", ("SiglipVisionModel",) * 2)
 _SIGLIP_CLS = Family("SigLIP classifier", lambda sd, cfg, no_head, mlp_width=False: siglip_classifier_to_timm(sd, cfg, mlp_width), 0, _config_labels, "always", ("SiglipForImageClassification",) * 2)
 _DINOV3 = Family("DINOv3", lambda sd, cfg, no_head, gated_mlp=False, mlp_width=False: dinov3_state_dict_to_timm(sd, cfg, gated_mlp, mlp_width), 1, None, "never", ("DINOv3ViTModel",) * 2)
+_BEIT = Family("BEiT", beit_state_dict_to_timm, 1, _config_labels, "optional", ("BeitForImageClassification", "BeitModel"))
 # text towers (convert_hf_text_model): no patch grid (prefix_rows is not read), no labels -- the "classes" are the projection's columns --, always with the projection
 _CLIP_TEXT = Family("CLIP text", clip_text_state_dict, 0, lambda cfg, E: {}, "always", ("CLIPTextModelWithProjection",) * 2)
 _SIGLIP_TEXT = Family("SigLIP text", siglip_text_state_dict, 0, lambda cfg, E: {}, "always", ("SiglipTextModel",) * 2)
 _TWO_TOWERS = ("clip", "siglip")          # converted as their vision tower (config.vision_config); convert_hf_text_model takes config.text_config
 # by model_type, the vision tower's or, for main(), the checkpoint's; any other model_type is taken for a ViT
 FAMILIES = {"vit": _VIT, "dinov2": _DINOV2, "dinov2_with_registers": _DINOV2, "clip_vision_model": _CLIP, "clip": _CLIP, "siglip_vision_model": _SIGLIP, "siglip": _SIGLIP,
-            "dinov3_vit": _DINOV3, "clip_text_model": _CLIP_TEXT, "siglip_text_model": _SIGLIP_TEXT}
+            "dinov3_vit": _DINOV3, "beit": _BEIT, "clip_text_model": _CLIP_TEXT, "siglip_text_model": _SIGLIP_TEXT}
 
 
-def _family_tensors(model, cfg, fam, no_head: bool, head_dim_note: str = "", gated_mlp: bool = False, mlp_width: bool = False):
+def _family_tensors(model, cfg, fam, no_head: bool, head_dim_note: str = "", gated_mlp: bool = False, mlp_width: bool = False, mean_pool: bool = False):
     """The front both converters share: the head-dim refusal, the state dict as numpy arrays, the config's activation and epsilon, and the
     family's mapper.  Returns (the file's tensors in its order, activation, eps); each converter then states its header and calls write_model."""
     hd = cfg.hidden_size // cfg.num_attention_heads
@@ -577,6 +635,8 @@ def _family_tensors(model, cfg, fam, no_head: bool, head_dim_note: str = "", gat
     opt = dict(gated_mlp=True) if gated_mlp else {}
     if mlp_width:
         opt["mlp_width"] = True
+    if mean_pool:
+        opt["mean_pool"] = True
     tensors = fam.mapper(sd, cfg, no_head, **opt)
     if mlp_width:
         tensors = _with_mlp_width(tensors, int(cfg.hidden_size))
@@ -607,7 +667,7 @@ def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_
     cls_name = type(model).__name__
     if cls_name.startswith("Siglip2") or getattr(cfg, "model_type", "").startswith("siglip2"):
         raise ValueError(f"{cls_name} (Siglip2VisionModel, NaFlex) is not supported: its patch embedding is a Linear over flattened patches")
-    if mean_pool and cls_name != "SiglipForImageClassification":
+    if mean_pool and cls_name != "SiglipForImageClassification" and FAMILIES.get(getattr(cfg, "model_type", "")) is not _BEIT:
         raise ValueError(f"mean_pool=True: {cls_name} is no mean-pool classifier this converter knows (SiglipForImageClassification; timm state dicts take --timm-state-dict --mean-pool)")
     if cls_name == "SiglipForImageClassification" and mean_pool:
         vcfg = cfg.vision_config
@@ -637,7 +697,9 @@ def convert_hf_model(model, path: str, ftype: int = 1, vitstr: bool = False, no_
     if vitstr and mlp_width:
         raise ValueError("mlp_width=True: a ViTSTR model takes no `mlp` width tensor")
     headless = fam.head == "never" or no_head
-    tensors, act, eps = _family_tensors(model, cfg, fam, no_head, " (64 runs the tuned attention kernels)", gated_mlp, mlp_width)
+    if fam is _BEIT and (vitstr or gated_mlp or mlp_width):
+        raise ValueError("a BEiT model takes none of vitstr, gated_mlp, mlp_width")
+    tensors, act, eps = _family_tensors(model, cfg, fam, no_head, " (64 runs the tuned attention kernels)", gated_mlp, mlp_width, mean_pool)
     g = grid_side(tensors["pos_embed"], fam.prefix_rows)          # the checkpoint's own grid (config.image_size states it too)
     hp = HParams(cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, int(tensors["head.weight"].shape[0]), cfg.patch_size, g * cfg.patch_size, ftype)
     id2label = NO_HEAD_LABELS if headless else fam.labels(cfg, hp.num_classes)
@@ -721,6 +783,37 @@ def _placed_after(t: dict, anchor: str, names) -> dict:
     return out
 
 
+def _beit_timm_fields(t: dict, heads: int):
+    """A timm Beit state dict (BEiT, BEiT v2; in place) under VisionTransformer's names; returns the file's `rel_bias`, or None for any other checkpoint.
+    attn.relative_position_bias_table per block, or the shared rel_pos_bias.*, become the returned tensor; the relative_position_index buffers are
+    dropped (the index rule is the file format's); q_bias / v_bias with a zero k bias (k_bias, where a checkpoint stores that buffer, is dropped) become
+    attn.qkv.bias directly behind attn.qkv.weight; gamma_1 / gamma_2 take LayerScale's names and are folded with it; without pos_embed the table is zeros."""
+    tabs = [k for k in t if k.endswith("relative_position_bias_table")]
+    if not tabs:
+        return None
+    L = 1 + max(int(k.split(".")[1]) for k in t if k.startswith("blocks."))
+    D = int(t["cls_token"].shape[-1])
+    shared = "rel_pos_bias.relative_position_bias_table"
+    names = [shared] if shared in t else [f"blocks.{i}.attn.relative_position_bias_table" for i in range(L)]
+    if sorted(tabs) != sorted(names):
+        raise ValueError(f"relative position bias tables {tabs}: expected the shared {shared!r} or one per block")
+    rel_bias = rel_bias_tensor([t[k] for k in names], heads or _TIMM_HEADS.get(D, 0) or t[names[0]].shape[1])
+    old = dict(t)
+    t.clear()
+    for k, v in old.items():
+        if k.endswith(("relative_position_bias_table", "relative_position_index", ".attn.k_bias", ".attn.v_bias")):
+            continue
+        if k.endswith(".attn.q_bias"):
+            continue
+        t[k.replace(".gamma_1", ".ls1.gamma").replace(".gamma_2", ".ls2.gamma")] = v
+        if k.endswith(".attn.qkv.weight") and k[:-10] + "q_bias" in old:
+            t[k[:-6] + "bias"] = np.concatenate([old[k[:-10] + "q_bias"], np.zeros((D,), np.float32), old[k[:-10] + "v_bias"]]).astype(np.float32)
+    if "pos_embed" not in t:
+        g = (int(round((rel_bias.shape[2] - 3) ** 0.5)) + 1) // 2
+        t["pos_embed"] = np.zeros((1, 1 + g * g, D), np.float32)
+    return rel_bias
+
+
 def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2label=None, act: str = "tanh", eps: float = 1e-6, preproc: dict | None = None,
                             mlp_width: bool = False, mean_pool: bool = False) -> HParams:
     """sd: a timm VisionTransformer state_dict (name -> array / tensor), e.g. torch.load("vit_base_patch16_224.pth").  It already carries the names
@@ -752,6 +845,7 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
             if u in k and not (mean_pool and u == "fc_norm."):
                 raise ValueError(f"tensor {k!r}: {what} is not supported (the file format has no slot for it)")
     t = _f32(t)
+    rel_bias = _beit_timm_fields(t, heads)
     map_head = any(k.startswith("attn_pool.") for k in t)
     pool_order = -1
     if mean_pool:
@@ -818,6 +912,8 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
         if cin == 1:
             raise ValueError("mean_pool=True: a ViTSTR model takes no `pool` tensor")
         t = _with_pool(t, pool_order)
+    if rel_bias is not None:
+        t = {"rel_bias": rel_bias, **t}
     if mlp_width:
         if cin == 1:
             raise ValueError("mlp_width=True: a ViTSTR model takes no `mlp` width tensor")

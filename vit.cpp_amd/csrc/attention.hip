@@ -45,6 +45,7 @@ hipError_t prepare_attention() {
     if (e == hipSuccess) e = prepare_attention_stream();
     if (e == hipSuccess) e = prepare_attention_persist();
     if (e == hipSuccess) e = prepare_attention_single();
+    if (e == hipSuccess) e = prepare_attention_bias();
     return e;
 }
 

@@ -50,6 +50,16 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
     if (m->in_chans == 1 && (m->has_pre_norm || m->activation != VITX_ACT_GELU_TANH)) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes neither a pre-norm nor an activation other than tanh-GELU"); return VITX_ERR_UNSUPPORTED; }
     if (dtype == VITX_MXFP8 && m->activation != VITX_ACT_GELU_TANH) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts evaluate tanh-GELU only (this model's activation: %d)", m->activation); return VITX_ERR_UNSUPPORTED; }
     if (m->in_chans == 1 && !own_shape) { set_error("vitx_ctx_create_ex: a ViTSTR context stays at the file's img_size (%d)", m->hp.img_size); return VITX_ERR_UNSUPPORTED; }
+    if (m->rel_bias_layers) {            // the relative position bias (include/vitx.h): attention_bias.hip at the file's own grid, bf16 or fp16 operands
+        const int g = m->hp.img_size / m->hp.patch_size;
+        if (dtype == VITX_MXFP8) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts do not take models with a relative position bias"); return VITX_ERR_UNSUPPORTED; }
+        if (m->in_chans == 1) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes no relative position bias"); return VITX_ERR_UNSUPPORTED; }
+        if (!own_shape) { set_error("vitx_ctx_create_ex: a model with a relative position bias stays at the file's img_size (%d): its table belongs to that grid", m->hp.img_size); return VITX_ERR_UNSUPPORTED; }
+        if (!attention_bias_supports(g, g, m->hp.hidden_size, m->hp.num_attention_heads)) {
+            set_error("vitx_ctx_create_ex: the relative position bias kernel takes head dim 64 and a table within its LDS (this model: %d heads of hidden size %d, grid %d x %d)", m->hp.num_attention_heads, m->hp.hidden_size, g, g);
+            return VITX_ERR_UNSUPPORTED;
+        }
+    }
     const Tuning *tune = nullptr;
     if (int rc = open_device("vitx_ctx_create", device, &tune)) return rc;
     const vitx_hparams &hp = m->hp;
@@ -83,10 +93,11 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
     }
     if (!layernorm_supports(c->D)) { set_error("vitx_ctx_create: hidden_size %d has no LayerNorm instantiation (64, 128, 192, 256, 320, 384, 448, 512, 576, 640, 768, 896, 1024, 1152, 1280, 1408, 1536, 1664, 2048)", c->D); return VITX_ERR_UNSUPPORTED; }
     c->split_first = opt.split_first;
-    c->prec_attn = dtype == VITX_F16 && c->D == c->H * 64 && !opt.f16_fast_attention;
+    c->prec_attn = dtype == VITX_F16 && c->D == c->H * 64 && !opt.f16_fast_attention && !m->rel_bias_layers;
     c->quant_on_device = !opt.quant_on_host;
     // the pooled and the mean-pool head average every patch row of the last layer, the attention-pooling head attends over them: such a context runs exactly as one created with last_layer_all_rows = 1
-    c->cls_tail = !opt.last_layer_all_rows && !c->pool && !c->map && !c->mean && c->R == 1 && attention_cls_supports(c->N, c->D, c->H);
+    // (so does a context of a file with `rel_bias`: the class-row tail kernel has no bias)
+    c->cls_tail = !opt.last_layer_all_rows && !c->pool && !c->map && !c->mean && !m->rel_bias_layers && c->R == 1 && attention_cls_supports(c->N, c->D, c->H);
     c->q4_fused_rows = opt.q4_fused_rows;
     c->graphs_on = opt.graph != 0;
     // fault injection for the parity tests: honoured only with the key in the upper half (VITX_LN_TEST_KEY | mode), so that no caller sets it by accident
@@ -195,6 +206,8 @@ static int ctx_create(const vitx_model *m, int device, int max_batch, int dtype,
         c->rope_sin = c->rope_cos + tab;
         HIP_TRY(hipMemcpy(c->rope_cos, h.data(), 2 * tab * 4, hipMemcpyHostToDevice));
     }
+
+    if (m->rel_bias_layers) { c->rel_bias = c->wset->rel_bias; c->rel_bias_stride = m->rel_bias_layers == 1 ? 0 : (size_t)c->H * m->find("rel_bias")->ne[0]; }
 
     // sub-batch slices (vitx_ctx_options::streams; 1 = single stream).  Small contexts stay single-slice.
     int ns = opt.streams > 0 ? opt.streams : 2;      // (configure: 0 .. 4)

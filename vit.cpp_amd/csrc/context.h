@@ -69,6 +69,10 @@ struct vitx_ctx {
     // rotary position embeddings of a file with `rope` (include/vitx.h): cos and sin [gh * gw][hd / 2] f32 for THIS context's grid, one allocation in
     // `allocs` (the table depends on the context's size, not on the weights); nullptr for every other file: nothing is allocated or launched
     float *rope_cos = nullptr, *rope_sin = nullptr;
+    // relative position bias of a file with `rel_bias` (include/vitx.h): wset->rel_bias, layer il's [H][len] table rel_bias_stride * il floats in (0: one
+    // shared table).  Such a context runs attention_bias.hip in every layer, evaluates every row of the last one and keeps plain fp16 q, k, v in F16
+    const float *rel_bias = nullptr;
+    size_t rel_bias_stride = 0;
     bool weights_shared = false;         // this context found the set already uploaded (vitx_ctx_shares_weights)
     // quantised files: vitx_ctx_options::quant_on_host restores the r01 behaviour (expand once on the host at upload, 16 bits per weight in HBM)
     bool quant_on_device = true;

@@ -332,7 +332,8 @@ struct SliceForward {
         } else {          // attention (vit.cpp:826-866)
             ProfScope ps(c, st, PC_ATTENTION, 4.0 * n * c->H * (double)N * N * (D / c->H), (double)M_real * (c->prec_attn ? 7 : 4) * D * eb);
             if (!(skip & 1)) {
-                if (c->prec_attn) HIP_TRY(launch_attention_stream(dt, true, sl.QKV, sl.U, n, N, D, c->H, lo_off, st));
+                if (c->rel_bias) HIP_TRY(launch_attention_bias(dt, sl.QKV, c->rel_bias + (size_t)il * c->rel_bias_stride, sl.U, n, c->gh, c->gw, D, c->H, st));      // this layer's table
+                else if (c->prec_attn) HIP_TRY(launch_attention_stream(dt, true, sl.QKV, sl.U, n, N, D, c->H, lo_off, st));
                 else HIP_TRY(launch_attention(*c->tune, dt, sl.QKV, sl.U, n, N, D, c->H, st));
             }
         }

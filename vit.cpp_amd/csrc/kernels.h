@@ -464,6 +464,11 @@ bool gemm_w4_supports(const GemmArgs &a);
 bool attention_persist_supports(int n_img, int N, int D);      // attention_persist.hip: 193..224 tokens, the whole QKV tensor below 0xf0000000 bytes
 bool attention_generic_supports(int D, int H);                 // attention_generic.hip: head_dim any multiple of 8 up to 128
 bool attention_wide_supports(int N, int D, int H);             // attention_wide.hip: head_dim 72, 80, .., 128, an image's qkv rows below 0xf0000000 bytes
+// Attention with a relative position bias (attention_bias.hip; include/vitx.h "relative position bias"): qkv [n_img * N][3 D] -> out [n_img * N][D],
+// N = gh gw + 1, head dim 64; table [H][(2 gh - 1)(2 gw - 1) + 3] f32 on the device.  hipErrorInvalidValue, nothing launched, for another head dim
+// or where the chunks and both tables exceed 64 KiB of LDS.  A zero table gives launch_attention_generic's bits.
+hipError_t launch_attention_bias(int dtype, const void *qkv, const float *table, void *out, int n_img, int gh, int gw, int D, int H, hipStream_t stream);
+bool attention_bias_supports(int gh, int gw, int D, int H);
 
 // FN<_Float16>(args) for DT_F16, FN<__bf16>(args) for any other dtype: how a launcher that takes `int dtype` enters its per-type template.
 // VITX_BY_DTYPE2: FN has one more template argument X after the type.
@@ -487,6 +492,7 @@ hipError_t prepare_attention_single();
 hipError_t prepare_attention_flow();
 hipError_t prepare_attention_persist();
 hipError_t prepare_attention_stream();
+hipError_t prepare_attention_bias();                   // attention_bias.hip
 hipError_t prepare_attention_text();                   // attention_text.hip
 hipError_t prepare_dense();                            // dense_label.hip
 hipError_t prepare_depth();                            // depth_map.hip

@@ -18,6 +18,8 @@
 // mlp.fc2.weight rows of F.
 // One more (include/vitx.h "the mean-pool head"): `pool` f32 [4] = {1, order, 0, 0} in front of the first blocks.* record; cls_token is then optional, and a file
 // without it has a pos_embed of g^2 rows and its reg_token rows (if any) at the front of an image.
+// One more (include/vitx.h "relative position bias"): `rel_bias` f32 [Lb][H][(2g-1)^2 + 3], Lb 1 or L, in front of the first blocks.* record: the tables of a
+// BEiT-class model's attention bias, every entry finite; such a file has cls_token and neither reg_token, `rope` nor attn_pool.*.
 // A text-tower file (include/vitx.h "the text tower") is told by patch_size == 0: token_embed.weight [V][D] (f16 or f32) and pos_embed [T][D]
 // in place of the image front, the same blocks, norm.* and head.* [E][D]; `arch` is then required and its last two slots are {causal, eos + 1};
 // `zs` f32 [4] = {kind, scale, bias, 0} is optional.  cls_token, reg_token, pre_norm.*, preproc and attn_pool.* do not belong in one.
@@ -273,6 +275,29 @@ static int load_impl(const char *path, vitx_model &m) {
             ++n_optional;
             continue;
         }
+        if (t.name == "rel_bias") {                                  // optional: f32 [Lb][H][(2g-1)^2 + 3] (include/vitx.h "relative position bias")
+            if (m.index.count(t.name)) { set_error("vitx_model_load: duplicate tensor '%s'", t.name.c_str()); return VITX_ERR_FORMAT; }
+            if (text) { set_error("vitx_model_load: text-tower file: tensor 'rel_bias' belongs to image files"); return VITX_ERR_FORMAT; }
+            const int64_t g = hp.img_size / hp.patch_size, len = (2 * g - 1) * (2 * g - 1) + 3;
+            if (ttype != T_F32 || n_dims != 3 || t.ne[0] != len || t.ne[1] != hp.num_attention_heads || (t.ne[2] != 1 && t.ne[2] != hp.num_hidden_layers)) {
+                set_error("vitx_model_load: tensor 'rel_bias' must be f32 [Lb][%d][%lld] with Lb 1 or %d ((2g-1)^2 + 3 entries per head at grid %lld): got type %d, %d dims [%lld, %lld, %lld]",
+                          hp.num_attention_heads, (long long)len, hp.num_hidden_layers, (long long)g, ttype, n_dims, (long long)t.ne[0], (long long)t.ne[1], (long long)t.ne[2]);
+                return VITX_ERR_FORMAT;
+            }
+            if (seen_block) { set_error("vitx_model_load: tensor 'rel_bias' stands behind a blocks.* record: it must come in front of the first one"); return VITX_ERR_FORMAT; }
+            const size_t nbytes = (size_t)t.nelements() * 4;
+            t.raw.resize(nbytes);
+            if (fread(t.raw.data(), 1, nbytes, f) != nbytes) { set_error("vitx_model_load: tensor '%s' is truncated", t.name.c_str()); return VITX_ERR_IO; }
+            for (size_t i = 0; i < nbytes / 4; ++i) {
+                float v; memcpy(&v, t.raw.data() + 4 * i, 4);
+                if (!std::isfinite(v)) { set_error("vitx_model_load: tensor 'rel_bias' entry %lld is not finite", (long long)i); return VITX_ERR_FORMAT; }
+            }
+            m.rel_bias_layers = (int)t.ne[2];
+            m.index[t.name] = (int)m.tensors.size();
+            m.tensors.push_back(std::move(t));
+            ++n_optional;
+            continue;
+        }
         if (t.name == "glu") {                                       // optional: f32 [4] = {kind, F, 0, 0} (include/vitx.h "gated MLP")
             if (m.index.count(t.name)) { set_error("vitx_model_load: duplicate tensor '%s'", t.name.c_str()); return VITX_ERR_FORMAT; }
             if (text) { set_error("vitx_model_load: text-tower file: tensor 'glu' belongs to image files"); return VITX_ERR_FORMAT; }
@@ -463,6 +488,11 @@ static int load_impl(const char *path, vitx_model &m) {
         if (!has_cls) { set_error("vitx_model_load: tensor 'cls_token' is missing (only a file with the attn_pool.* tensors has no class token)"); return VITX_ERR_FORMAT; }
         if (pos_no_cls) { set_error("vitx_model_load: tensor 'pos_embed' has no class row, but the file has a class token"); return VITX_ERR_FORMAT; }
     }
+    if (m.rel_bias_layers) {      // the relative position bias: a class token, no registers, no rotary signal (attn_pool.* comes without cls_token: refused as such)
+        const char *with = !has_cls ? nullptr : m.num_registers ? "reg_token" : m.rope_kind ? "rope" : "";
+        if (!with) { set_error("vitx_model_load: tensor 'rel_bias' in a file without cls_token: the index rule has the class token in front"); return VITX_ERR_FORMAT; }
+        if (*with) { set_error("vitx_model_load: tensor 'rel_bias' together with %s: the relative position bias knows the class token and the patches only", with); return VITX_ERR_FORMAT; }
+    }
     const size_t n_expect = expect.size() - (has_cls ? 0 : 1) + (size_t)n_pool + (m.num_registers ? 1 : 0) + (size_t)n_optional;
     if (m.tensors.size() != n_expect) {
         set_error("vitx_model_load: model file has %d tensors, but %d tensors were expected", (int)m.tensors.size(), (int)n_expect);
@@ -546,6 +576,36 @@ int vitx_model_rope(const vitx_model *m, int *kind, float *theta) {
     if (kind) *kind = m->rope_kind;
     if (theta) *theta = m->rope_theta;
     return 1;
+}
+int vitx_model_rel_bias(const vitx_model *m, int *Lb, int *table_len) {
+    if (!m || !m->rel_bias_layers) return 0;
+    if (Lb) *Lb = m->rel_bias_layers;
+    if (table_len) *table_len = (int)m->find("rel_bias")->ne[0];
+    return 1;
+}
+// B[h][q][k] of `layer` by the index rule (include/vitx.h "relative position bias"), offsets around the centre of the file's (2g-1)^2 table
+int vitx_model_rel_bias_dense(const vitx_model *m, int layer, int gh, int gw, float *out) {
+    if (!m || !out) { vitx::set_error("vitx_model_rel_bias_dense: NULL argument"); return VITX_ERR_ARG; }
+    if (!m->rel_bias_layers) { vitx::set_error("vitx_model_rel_bias_dense: the model has no `rel_bias` tensor"); return VITX_ERR_ARG; }
+    const int g = m->hp.img_size / m->hp.patch_size, H = m->hp.num_attention_heads, W = 2 * g - 1, len = W * W + 3;
+    if (layer < 0 || layer >= m->hp.num_hidden_layers || gh < 1 || gw < 1 || gh > g || gw > g) {
+        vitx::set_error("vitx_model_rel_bias_dense: layer %d or grid %d x %d is out of range (%d layers, the file's grid is %d x %d)", layer, gh, gw, m->hp.num_hidden_layers, g, g);
+        return VITX_ERR_ARG;
+    }
+    const float *tab = (const float *)m->find("rel_bias")->raw.data() + (size_t)(m->rel_bias_layers == 1 ? 0 : layer) * H * len;
+    const int N = gh * gw + 1;
+    for (int h = 0; h < H; ++h) {
+        const float *th = tab + (size_t)h * len;
+        float *o = out + (size_t)h * N * N;
+        o[0] = th[len - 1];
+        for (int k = 1; k < N; ++k) { o[k] = th[len - 3]; o[(size_t)k * N] = th[len - 2]; }
+        for (int q = 1; q < N; ++q)
+            for (int k = 1; k < N; ++k) {
+                const int dy = (q - 1) / gw - (k - 1) / gw, dx = (q - 1) % gw - (k - 1) % gw;
+                o[(size_t)q * N + k] = th[(dy + g - 1) * W + dx + g - 1];
+            }
+    }
+    return VITX_OK;
 }
 int vitx_model_mlp_width(const vitx_model *m) { return !m ? 0 : m->glu_kind ? m->glu_width : m->mlp_file_rows(); }      // the file's F (4 D without `mlp` or `glu`)
 int vitx_model_glu(const vitx_model *m, int *kind, int *width) {

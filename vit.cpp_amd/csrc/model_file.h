@@ -42,6 +42,7 @@ struct vitx_model {
     bool has_pre_norm = false;                        // `pre_norm.weight` / `pre_norm.bias` [D]: LayerNorm of every token row in front of layer 0
     int rope_kind = VITX_ROPE_NONE;                   // `rope` [4] = {kind, theta, 0, 0}: rotary position embeddings on q and k of the patch tokens (include/vitx.h)
     float rope_theta = 0.0f;
+    int rel_bias_layers = 0;                          // `rel_bias` f32 [Lb][H][(2g-1)^2 + 3]: Lb (1: shared by every layer, or L); 0 without it (include/vitx.h "relative position bias")
     int glu_kind = VITX_GLU_NONE;                     // `glu` [4] = {kind, F, 0, 0}: a gated MLP (include/vitx.h "gated MLP"); fc1 is then [2 F][D], fc2 [D][F]
     int glu_width = 0;                                // F, the MLP hidden width of such a file (fc2's K); 0 without `glu`: the width is 4 D
     int mlp_width = 0;                                // `mlp` [4] = {F, 0, 0, 0}: a plain MLP of the file's own width (include/vitx.h "MLP width"); 0 without it

@@ -901,6 +901,16 @@ int vitx_op_attention_generic(int dtype, const void *d_qkv, void *d_out, int n_i
     if (!attention_generic_supports(D, H)) { set_error("vitx_op_attention_generic: head_dim must be a multiple of 8 up to 128 (D %d, H %d)", D, H); return VITX_ERR_UNSUPPORTED; }
     return op_rc("vitx_op_attention_generic", launch_attention_generic(dtype, d_qkv, d_out, n_img, N, D, H, (hipStream_t)stream));
 }
+// Attention with a relative position bias (attention_bias.hip; include/vitx.h "relative position bias") on its own.  Null stream, only enqueues.
+int vitx_op_attention_bias(int dtype, const void *d_qkv, const void *d_table, void *d_out, int n_img, int gh, int gw, int D, int H) {
+    if (!d_qkv || !d_table || !d_out || n_img <= 0 || gh <= 0 || gw <= 0 || D <= 0 || H <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_attention_bias: invalid argument"); return VITX_ERR_ARG; }
+    if (!attention_bias_supports(gh, gw, D, H)) {
+        set_error("vitx_op_attention_bias: the relative position bias kernel takes head dim 64 (D %d, H %d) and a grid whose table fits its LDS with the key chunks (%d x %d)", D, H, gh, gw);
+        return VITX_ERR_UNSUPPORTED;
+    }
+    if (!tuning_for_device(-1)) { set_error("vitx_op_attention_bias: kernel bring-up failed"); return VITX_ERR_HIP; }
+    return op_rc("vitx_op_attention_bias", launch_attention_bias(dtype, d_qkv, (const float *)d_table, d_out, n_img, gh, gw, D, H, nullptr), VITX_ERR_UNSUPPORTED);
+}
 // The staged kernel of head dims 72 .. 128 (attention_wide.hip) on its own, beside the generic one it must match bit for bit.  Null stream, only enqueues.
 int vitx_op_attention_wide(int dtype, const void *d_qkv, void *d_out, int n_img, int N, int D, int H) {
     if (!d_qkv || !d_out || n_img <= 0 || N <= 0 || D <= 0 || H <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_attention_wide: invalid argument"); return VITX_ERR_ARG; }

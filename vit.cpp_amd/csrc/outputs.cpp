@@ -192,6 +192,7 @@ int vitx_attn_enable(vitx_ctx *c, uint64_t layer_mask, int flags) {
     const bool on = layer_mask != 0 || flags != 0, rollout = (flags & VITX_ATTN_ROLLOUT) != 0;
     if (on && c->R != 1) { set_error("vitx_attn_enable: attention maps are not available for ViTSTR contexts"); return VITX_ERR_UNSUPPORTED; }
     if (on && !c->has_cls) { set_error("vitx_attn_enable: the maps are defined by the class-token row, and this model (attention-pooling head, or a mean-pool file without cls_token) has no class token"); return VITX_ERR_UNSUPPORTED; }
+    if (on && c->rel_bias) { set_error("vitx_attn_enable: this model adds a relative position bias to its attention scores, and the map kernels would omit it"); return VITX_ERR_UNSUPPORTED; }
     if (on && !attention_map_supports(c->N, c->D, c->H)) { set_error("vitx_attn_enable: head_dim %d is not covered by the map kernels", c->D / c->H); return VITX_ERR_UNSUPPORTED; }
     if (rollout && !attention_mean_supports(c->N, c->D, c->H)) { set_error("vitx_attn_enable: rollout keeps two N x N matrices per image and takes at most %d tokens (this model: %d)", kAttnMeanMaxTokens, c->N); return VITX_ERR_UNSUPPORTED; }
     if (const int rc = quiesce(c)) return rc;

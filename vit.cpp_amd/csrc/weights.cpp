@@ -202,6 +202,7 @@ int upload_image(const Upload &u) {
     if (m->has_cls && (rc = upload_f32(u, u.T("cls_token"), &ws.cls))) return rc;
     if (m->num_registers && (rc = upload_f32(u, u.T("reg_token"), &ws.reg))) return rc;
     if ((rc = upload_f32(u, u.T("pos_embed"), &ws.pos))) return rc;
+    if (m->rel_bias_layers && (rc = upload_f32(u, u.T("rel_bias"), &ws.rel_bias))) return rc;      // [Lb][H][len] as filed: attention_bias.hip scales as it fills its LDS
     if (m->has_pre_norm && ((rc = upload_f32(u, u.T("pre_norm.weight"), &ws.pre_w)) || (rc = upload_f32(u, u.T("pre_norm.bias"), &ws.pre_b)))) return rc;
     if ((rc = upload_f32(u, u.T("patch_embed.proj.bias"), &ws.pe_b, round_up(D, tn)))) return rc;
     if ((rc = upload_matrix(u, u.T("patch_embed.proj.weight"), D, patch_k(m), round_up(D, tn), patch_k_pad(m), &ws.pe_w, m->hp.patch_size, m->in_chans))) return rc;

@@ -57,6 +57,7 @@ struct WeightSet {
     std::vector<void *> allocs;
     float *pre_w = nullptr, *pre_b = nullptr;      // pre_norm.* (nullptr without them): LayerNorm of the token rows in front of layer 0
     float *cls = nullptr, *reg = nullptr, *pos = nullptr, *pe_b = nullptr, *norm_w = nullptr, *norm_b = nullptr, *head_b = nullptr;
+    float *rel_bias = nullptr;       // `rel_bias` [Lb][H][(2g-1)^2 + 3] f32 (nullptr without it): the relative position bias tables of attention_bias.hip
     void *pe_w = nullptr, *head_w = nullptr;
     QuantW head_q;
     void *tok = nullptr;             // a text tower's token table [V][D] as filed: f16 (tok_f16) or f32
