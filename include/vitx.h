@@ -524,6 +524,43 @@ int vitx_model_rel_bias(const vitx_model *m, int *Lb, int *table_len);
 int vitx_model_rel_bias_dense(const vitx_model *m, int layer, int gh, int gw, float *out);
 int vitx_op_attention_bias(int dtype, const void *d_qkv, const void *d_table, void *d_out, int n_img, int gh, int gw, int D, int H);
 
+/* ---- windowed attention and decomposed relative position (ViTDet, the Segment-Anything image encoder) ---------------------- */
+/* Most layers of these encoders attend inside non-overlapping windows of the class-less token grid, a few attend globally, and every score gets a
+ * position term that is a product with the query:
+ *   softmax( scale . q . k + q . Rh[qy - ky + wh - 1] + q . Rw[qx - kx + ww - 1] ) v        (q unscaled; Rh [2 wh - 1][dh], Rw [2 ww - 1][dh] per layer)
+ * with (qy, qx), (ky, kx) the positions of query and key inside their window of wh x ww tokens; a global layer is one window, (wh, ww) = (gh, gw).
+ * The grid is cut from its top left corner; a window that reaches past the grid is filled with PAD tokens, which the model inserts as zero rows
+ * behind norm1: a pad token is a real key whose k and v are the qkv bias, and a pad query is dropped.
+ * A file of such a model carries, in front of the first blocks.* record (where `rope` / `glu` / `pool` / `rel_bias` go), `window` f32 [2 + L] =
+ * {ws, identity_final_norm (0 / 1), then per layer 1 = windowed, 0 = global}, and inside each block blocks.i.attn.rel_pos_h and rel_pos_w, f32
+ * [2 w - 1][dh] with w = ws for a windowed layer and the grid side for a global one.  It has no class token and carries the `pool` marker
+ * (VITX_POOL_MEAN) and a head.  The loader refuses (VITX_ERR_FORMAT): cls_token, reg_token, `rope`, `rel_bias`, attn_pool.*, `glu` beside `window`; a
+ * file without `pool`; `window` in a text-tower file or behind a blocks.* record; a missing or mis-sized table; a table entry that is not finite;
+ * ws < 1 or not whole; a flag other than 0 or 1.  vitx_quantize_file copies `window` and the tables byte for byte.  A file without `window` loads,
+ * runs and hashes exactly as before.
+ * A context of such a file uploads the tables rounded to the operand type with the weight set and runs attention_window.hip in every layer with that
+ * layer's extents, tables and qkv bias; every row of the last layer is evaluated and a VITX_F16 context keeps plain fp16 q, k, v.  With
+ * identity_final_norm = 1 the feature pass (VITX_FEAT_TOKENS, VITX_FEAT_MEAN) and the head operand take the raw f32 residual rows (one more
+ * instantiation of the feature kernel; the dense and depth heads still apply norm.*).  VITX_ERR_UNSUPPORTED, naming the windowed attention: VITX_MXFP8,
+ * ViTSTR and packed contexts, vitx_model_resize_file, vitx_attn_enable, a head dim other than 64 or a side above 64, contexts away from the file's
+ * grid; vitx_dense_set, and vitx_depth_set with VITX_DEPTH_NORM, on an identity_final_norm context (they read the final norm).  Contexts of every
+ * other file launch and allocate exactly what they did.  convert.py --sam writes such a file from a segment-anything image_encoder.* state dict.
+ * NOT BUILT: the encoder's neck.
+ *   vitx_model_window          1 and *ws / *flags (bit 0: identity_final_norm) / layer_is_windowed[L] (any may be NULL) for a file with `window`, 0 without
+ *   vitx_op_attention_window   on device pointers: d_qkv [n_img * gh gw][3 D] of `dtype` (VITX_F16 / VITX_BF16), tokens in raster order, head dim 64;
+ *                              d_rel_h [2 wh - 1][64] and d_rel_w [2 ww - 1][64] of `dtype` (the layer's tables, shared by the heads); d_qkv_bias f32
+ *                              [3 D] (a pad key of head h is RNE of entries D + 64 h .. and 2 D + 64 h ..) -> d_out [n_img * gh gw][D].  One launch is
+ *                              one layer; 1 <= wh, ww <= 64 (the bias panels live in the kernel's LDS); wh > gh or ww > gw is one padded window.
+ *                              The position term is computed in f32 from the wave's q fragments on the matrix pipe and added to the f32 score
+ *                              accumulators before the row maximum; nothing of size N^2 reaches global memory.  All-zero tables and one global
+ *                              window give the bits of vitx_op_attention_generic at N = gh gw; all-zero tables on a grid that is a multiple of
+ *                              the window give, per window, the generic kernel's bits on that window's rows gathered as an image.  An image's
+ *                              rows depend on that image, the tables and the bias alone.  NULL, non-positive sizes, another dtype: VITX_ERR_ARG;
+ *                              a head dim other than 64 or a window side above 64: VITX_ERR_UNSUPPORTED, naming the windowed attention.
+ *                              TEST ENTRY: null stream (it only enqueues there). */
+int vitx_model_window(const vitx_model *m, int *ws, int *flags, int *layer_is_windowed);
+int vitx_op_attention_window(int dtype, const void *d_qkv, const void *d_rel_h, const void *d_rel_w, const float *d_qkv_bias, void *d_out, int n_img, int gh, int gw, int wh, int ww, int D, int H);
+
 /* ---- gated MLP (DINOv2 ViT-g/14, DINOv3 ViT-H+) ---------------------------------- */
 /* A file may carry `glu`, f32 [4] = {kind, F, 0, 0}: the MLP of every block is then fc2( act(gate(x)) . up(x) ) with hidden width F instead of
  * fc2( act(fc1(x)) ) with hidden width 4 D.  kind 1 (VITX_GLU_SWIGLU, the only one): h = silu(gate) . up, silu(g) = g / (1 + exp(-g)).  With it every

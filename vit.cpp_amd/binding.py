@@ -85,6 +85,7 @@ EXPORTS = [
     "vitx_pack_feat_read_mean", "vitx_pack_mean_chunks", "vitx_op_feat_pool_packed", "vitx_op_feat_pool_packed_tables",
     "vitx_op_pool_mean",
     "vitx_model_rel_bias", "vitx_model_rel_bias_dense", "vitx_op_attention_bias",
+    "vitx_model_window", "vitx_op_attention_window",
 ]
 
 
@@ -326,6 +327,9 @@ def lib():
             L.vitx_model_rel_bias.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
             L.vitx_model_rel_bias_dense.argtypes = [vp, ip, ip, ip, C.POINTER(C.c_float)]
             L.vitx_op_attention_bias.argtypes = [ip, vp, vp, vp, ip, ip, ip, ip, ip]
+        if hasattr(L, "vitx_op_attention_window"):
+            L.vitx_op_attention_window.argtypes = [ip, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, ip]
+            L.vitx_model_window.argtypes = [vp, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]
         if hasattr(L, "vitx_op_rope"):
             L.vitx_model_rope.argtypes = [vp, C.POINTER(ip), C.POINTER(C.c_float)]
             L.vitx_model_rope_table.argtypes = [vp, ip, ip, C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -494,6 +498,12 @@ class Model:
         every layer), or None."""
         n, t = C.c_int(), C.c_int()
         return (n.value, t.value) if lib().vitx_model_rel_bias(self._h, C.byref(n), C.byref(t)) else None
+
+    def window(self):
+        """(ws, identity_final_norm, [layer is windowed] * L) of a file with a `window` tensor (windowed attention with a decomposed relative position
+        term; a layer that is not windowed attends globally), or None."""
+        ws, fl, lay = C.c_int(), C.c_int(), (C.c_int * self.hparams.num_hidden_layers)()
+        return (ws.value, fl.value, [bool(x) for x in lay]) if lib().vitx_model_window(self._h, C.byref(ws), C.byref(fl), lay) else None
 
     def rel_bias_dense(self, layer: int, grid) -> np.ndarray:
         """vitx_model_rel_bias_dense: the bias of `layer` as f32 [H, N, N], N = gh gw + 1, for a grid g or (gh, gw) up to the file's (host only)."""
@@ -2003,6 +2013,14 @@ def attention_bias(dtype: int, d_qkv: int, d_table: int, d_out: int, n_img: int,
     """vitx_op_attention_bias: attention with a relative position bias on qkv [n_img * N][3 D] -> out [n_img * N][D], N = gh gw + 1, head dim 64;
     d_table f32 [H][(2 gh - 1)(2 gw - 1) + 3]; null stream."""
     check(lib().vitx_op_attention_bias(dtype, d_qkv, d_table, d_out, n_img, gh, gw, D, H), "vitx_op_attention_bias")
+
+
+def attention_window(dtype: int, d_qkv: int, d_rel_h: int, d_rel_w: int, d_qkv_bias: int, d_out: int, n_img: int, grid, window, D: int, H: int) -> None:
+    """vitx_op_attention_window: windowed attention with a decomposed relative position term on class-less qkv [n_img * gh gw][3 D] -> out
+    [n_img * gh gw][D], head dim 64; window (wh, ww), the grid itself for a global layer; d_rel_h [2 wh - 1][64], d_rel_w [2 ww - 1][64] of `dtype`,
+    d_qkv_bias f32 [3 D]; null stream."""
+    (gh, gw), (wh, ww) = _grid(grid), _grid(window)
+    check(lib().vitx_op_attention_window(dtype, d_qkv, d_rel_h, d_rel_w, d_qkv_bias, d_out, n_img, gh, gw, wh, ww, D, H), "vitx_op_attention_window")
 
 
 def zeroshot_max_classes(E: int) -> int:

@@ -925,6 +925,64 @@ def convert_timm_state_dict(sd, path: str, ftype: int = 1, heads: int = 0, id2la
     return hp
 
 
+def convert_sam_state_dict(sd, path: str, ftype: int = 1, heads: int = 0) -> HParams:
+    """sd: a segment-anything checkpoint (sam_vit_b / _l / _h: the tensors image_encoder.*; every other module is dropped with a note) or the state dict
+    of its ImageEncoderViT alone, under segment-anything's own names -- no `segment_anything` import.  Writes a class-less file with windowed attention
+    (include/vitx.h "windowed attention and decomposed relative position"): patch_embed.proj.*, pos_embed [1][g][g][D] as [1][g^2][D], per block norm1,
+    attn.qkv, attn.proj, attn.rel_pos_h / rel_pos_w, norm2 and mlp.lin1 / lin2 as mlp.fc1 / fc2.  A layer whose tables have 2 g - 1 rows is global, any
+    other length 2 ws - 1 is windowed (one ws per file); `window` = {ws, 1, flags}: the encoder has no final norm in front of its neck, so norm.* is
+    written as (1, 0) and the identity flag is set.  `arch` = erf-GELU, eps 1e-6; `pool` order 0 and the zero head, as --no-head writes.  neck.* (two
+    convolutions and two channel LayerNorms) has no slot and is dropped with a printed note: the file's product is the backbone's tokens."""
+    if isinstance(sd, dict) and "model" in sd and not hasattr(sd["model"], "shape"):
+        sd = sd["model"]
+    pre = "image_encoder."
+    if any(k.startswith(pre) for k in sd):
+        other = sorted({k.split(".")[0] for k in sd if not k.startswith(pre)})
+        if other:
+            print(f"note: dropped {other}: only the image encoder is converted")
+        sd = {k[len(pre):]: v for k, v in sd.items() if k.startswith(pre)}
+    neck = [k for k in sd if k.startswith("neck.")]
+    if neck:
+        print(f"note: dropped {len(neck)} neck.* tensors: the file holds the backbone, its tokens are the product (vitx_feat_*)")
+    s = _f32({k: v for k, v in sd.items() if not k.startswith("neck.")})
+    for need in ("pos_embed", "patch_embed.proj.weight", "patch_embed.proj.bias", "blocks.0.attn.rel_pos_h", "blocks.0.mlp.lin1.weight"):
+        if need not in s:
+            raise ValueError(f"not a segment-anything image encoder state dict: {need!r} is missing")
+    if s["pos_embed"].ndim != 4 or s["pos_embed"].shape[1] != s["pos_embed"].shape[2]:
+        raise ValueError(f"pos_embed {s['pos_embed'].shape}: expected [1][g][g][D]")
+    g, D = int(s["pos_embed"].shape[1]), int(s["pos_embed"].shape[3])
+    L = 1 + max(int(k.split(".")[1]) for k in s if k.startswith("blocks."))
+    Dw, cin, P, P2 = s["patch_embed.proj.weight"].shape
+    H = heads or _TIMM_HEADS.get(D, 0)
+    if Dw != D or P != P2 or cin != 3 or H <= 0 or D % H:
+        raise ValueError(f"unexpected shapes: patch kernel {s['patch_embed.proj.weight'].shape}, pos_embed {s['pos_embed'].shape}, heads {H} (pass --heads for an unreleased width)")
+    out: Dict[str, np.ndarray] = {"pos_embed": s["pos_embed"].reshape(1, g * g, D), "patch_embed.proj.weight": s["patch_embed.proj.weight"], "patch_embed.proj.bias": s["patch_embed.proj.bias"]}
+    sides = []
+    for i in range(L):
+        p = f"blocks.{i}."
+        rh, rw = s[p + "attn.rel_pos_h"], s[p + "attn.rel_pos_w"]
+        if rh.shape != rw.shape or rh.ndim != 2 or rh.shape[1] != D // H or rh.shape[0] % 2 == 0:
+            raise ValueError(f"{p}attn.rel_pos_h {rh.shape} / rel_pos_w {rw.shape}: expected two tables [2 w - 1][{D // H}]")
+        sides.append((rh.shape[0] + 1) // 2)
+        for dst, src in (("norm1", "norm1"), ("attn.qkv", "attn.qkv"), ("attn.proj", "attn.proj"), ("norm2", "norm2"), ("mlp.fc1", "mlp.lin1"), ("mlp.fc2", "mlp.lin2")):
+            for e in ("weight", "bias"):
+                out[f"{p}{dst}.{e}"] = s[f"{p}{src}.{e}"]
+                if dst == "attn.qkv" and e == "bias":
+                    out[p + "attn.rel_pos_h"], out[p + "attn.rel_pos_w"] = rh, rw
+    used = 3 + 14 * L
+    if len(s) != used:
+        raise ValueError(f"{len(s)} image encoder tensors, the file holds exactly {used} for {L} layers: unknown {[k for k in s if not k.startswith(('blocks.', 'pos_embed', 'patch_embed.'))][:4]}")
+    ws = sorted({w for w in sides if w != g})
+    if len(ws) > 1:
+        raise ValueError(f"windowed layers of sides {ws}: a file holds one window size")
+    out["norm.weight"], out["norm.bias"] = np.ones(D, np.float32), np.zeros(D, np.float32)
+    _zero_head(out, D)
+    window = np.array([ws[0] if ws else g, 1] + [float(w != g) for w in sides], np.float32)
+    hp = HParams(D, L, H, 1, int(P), g * int(P), ftype)
+    write_model(path, hp, with_arch({"window": window, **_with_pool(out, 0)}, ACT_ERF, 1e-6), id2label=NO_HEAD_LABELS, ftype=ftype)
+    return hp
+
+
 # --------------------------------------------------------------------------- zero-shot banks
 def _l2_rows(x: np.ndarray) -> np.ndarray:
     return x / np.sqrt((x * x).sum(axis=1, keepdims=True))
@@ -1172,6 +1230,8 @@ def main(argv=None) -> int:
     ap.add_argument("--mean-pool", action="store_true", help="opt in to a mean-pool classifier (timm global_pool='avg' state dicts with fc_norm.* or norm.*, class token optional; "
                     "SiglipForImageClassification): the file carries the `pool` tensor, which neither the reference nor an engine build before it can read")
     ap.add_argument("--timm-state-dict", action="store_true", help="`model` is a torch-saved timm VisionTransformer state_dict (.pth); no timm import needed")
+    ap.add_argument("--sam", action="store_true", help="`model` is a torch-saved segment-anything checkpoint (sam_vit_b / _l) or its image encoder's state dict: write the backbone "
+                    "with windowed attention and decomposed relative position (the `window` tensor); neck.* is dropped; no segment_anything import needed")
     ap.add_argument("--heads", type=int, default=0, help="attention heads of a timm checkpoint (inferred only for the widths of released timm ViTs; required otherwise)")
     ap.add_argument("--act", default="tanh", choices=sorted(_ACT_NAMES), help="MLP activation of a timm checkpoint (a state dict carries no config): tanh = ggml's GELU, the "
                                                                                   "reference's (default); erf = nn.GELU, what timm's VisionTransformer uses; quick = QuickGELU")
@@ -1211,7 +1271,12 @@ def main(argv=None) -> int:
         ap.error("a zero-shot bank needs the text tower of a HuggingFace CLIPModel / SiglipModel, not a timm state dict")
     if not a.timm_state_dict and any((a.pp_resize, a.pp_crop, a.pp_filter, a.pp_mean, a.pp_std, a.pp_crop_round)):
         ap.error("--pp-* describe a timm checkpoint (--timm-state-dict); a HuggingFace checkpoint brings its preprocessor_config.json")
-    if a.timm_state_dict:
+    if a.sam:
+        if a.timm_state_dict or a.vitstr or a.no_head or a.gated_mlp or a.mlp_width or a.mean_pool or a.text_out or a.zero_shot_out or a.img_size:
+            ap.error("--sam takes --ftype and --heads only")
+        import torch
+        hp = convert_sam_state_dict(torch.load(a.model, map_location="cpu", weights_only=True), a.out, a.ftype, heads=a.heads)
+    elif a.timm_state_dict:
         import torch
         sd = torch.load(a.model, map_location="cpu", weights_only=True)
         labels = {int(k): str(v) for k, v in json.load(open(a.labels)).items()} if a.labels else None

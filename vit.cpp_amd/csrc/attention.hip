@@ -46,6 +46,7 @@ hipError_t prepare_attention() {
     if (e == hipSuccess) e = prepare_attention_persist();
     if (e == hipSuccess) e = prepare_attention_single();
     if (e == hipSuccess) e = prepare_attention_bias();
+    if (e == hipSuccess) e = prepare_attention_window();
     return e;
 }
 

@@ -35,6 +35,16 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
     const int img_size = opt.img_size > 0 ? opt.img_size : m->hp.img_size;
     const int img_h = rect ? rect_h : img_size, img_w = rect ? rect_w : img_size;
     const bool own_shape = img_h == m->hp.img_size && img_w == m->hp.img_size;      // the file's own geometry
+    if (m->window) {                     // windowed attention (include/vitx.h): attention_window.hip at the file's own grid, bf16 or fp16 operands
+        const int g = m->hp.img_size / m->hp.patch_size, ws = m->window;
+        if (dtype == VITX_MXFP8) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts do not take models with windowed attention"); return VITX_ERR_UNSUPPORTED; }
+        if (m->in_chans == 1) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes no windowed attention"); return VITX_ERR_UNSUPPORTED; }
+        if (!own_shape) { set_error("vitx_ctx_create_ex: a model with windowed attention stays at the file's img_size (%d): its global tables belong to that grid", m->hp.img_size); return VITX_ERR_UNSUPPORTED; }
+        if (!attention_window_supports(g, g, g, g, m->hp.hidden_size, m->hp.num_attention_heads) || !attention_window_supports(g, g, ws, ws, m->hp.hidden_size, m->hp.num_attention_heads)) {
+            set_error("vitx_ctx_create_ex: the windowed attention kernel takes head dim 64 and windows of at most 64 tokens a side (this model: %d heads of hidden size %d, grid %d x %d, ws %d)", m->hp.num_attention_heads, m->hp.hidden_size, g, g, ws);
+            return VITX_ERR_UNSUPPORTED;
+        }
+    }
     if (m->in_chans == 1 && (m->num_registers || m->head_pool != VITX_POOL_CLS)) { set_error("vitx_ctx_create_ex: a ViTSTR (one-channel) model takes neither register tokens nor a pooled, attention-pooling or mean-pool head"); return VITX_ERR_UNSUPPORTED; }
     if (dtype == VITX_MXFP8 && (m->num_registers || m->head_pool != VITX_POOL_CLS)) { set_error("vitx_ctx_create_ex: VITX_MXFP8 contexts do not take models with register tokens, the pooled head, the attention-pooling head or the mean-pool head"); return VITX_ERR_UNSUPPORTED; }
     if (!m->has_cls && !own_shape) {
@@ -93,7 +103,7 @@ int configure(const vitx_model *m, int device, int max_batch, int dtype, const v
     }
     if (!layernorm_supports(c->D)) { set_error("vitx_ctx_create: hidden_size %d has no LayerNorm instantiation (64, 128, 192, 256, 320, 384, 448, 512, 576, 640, 768, 896, 1024, 1152, 1280, 1408, 1536, 1664, 2048)", c->D); return VITX_ERR_UNSUPPORTED; }
     c->split_first = opt.split_first;
-    c->prec_attn = dtype == VITX_F16 && c->D == c->H * 64 && !opt.f16_fast_attention && !m->rel_bias_layers;
+    c->prec_attn = dtype == VITX_F16 && c->D == c->H * 64 && !opt.f16_fast_attention && !m->rel_bias_layers && !m->window;
     c->quant_on_device = !opt.quant_on_host;
     // the pooled and the mean-pool head average every patch row of the last layer, the attention-pooling head attends over them: such a context runs exactly as one created with last_layer_all_rows = 1
     // (so does a context of a file with `rel_bias`: the class-row tail kernel has no bias)
@@ -207,6 +217,7 @@ static int ctx_create(const vitx_model *m, int device, int max_batch, int dtype,
         HIP_TRY(hipMemcpy(c->rope_cos, h.data(), 2 * tab * 4, hipMemcpyHostToDevice));
     }
 
+    if (m->window) { c->ident_norm = m->window_identity_norm; for (int i = 0; i < c->L; ++i) c->win_side.push_back(m->window_side(i)); }
     if (m->rel_bias_layers) { c->rel_bias = c->wset->rel_bias; c->rel_bias_stride = m->rel_bias_layers == 1 ? 0 : (size_t)c->H * m->find("rel_bias")->ne[0]; }
 
     // sub-batch slices (vitx_ctx_options::streams; 1 = single stream).  Small contexts stay single-slice.

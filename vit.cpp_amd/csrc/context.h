@@ -73,6 +73,10 @@ struct vitx_ctx {
     // shared table).  Such a context runs attention_bias.hip in every layer, evaluates every row of the last one and keeps plain fp16 q, k, v in F16
     const float *rel_bias = nullptr;
     size_t rel_bias_stride = 0;
+    // windowed attention of a file with `window` (include/vitx.h): layer il's window side (ws, or the grid's for a global layer); empty for every other
+    // file.  Such a context runs attention_window.hip in every layer and keeps plain fp16 q, k, v in F16.  ident_norm: the final norm is the identity
+    std::vector<int> win_side;
+    bool ident_norm = false;
     bool weights_shared = false;         // this context found the set already uploaded (vitx_ctx_shares_weights)
     // quantised files: vitx_ctx_options::quant_on_host restores the r01 behaviour (expand once on the host at upload, 16 bits per weight in HBM)
     bool quant_on_device = true;

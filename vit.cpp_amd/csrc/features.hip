@@ -29,7 +29,21 @@ namespace {
 // weights of a piece need more than 128 registers per lane (checked with -save-temps: no instantiation spills)
 constexpr int feat_waves(int D) { return D <= 768 ? 16 : 8; }
 
-template <int VEC, int NV>
+// F of one row: LnRow::norm, or (IDENT: a file whose final norm is the identity, include/vitx.h "windowed attention") the raw f32 row as loaded
+template <int VEC, int NV, bool IDENT>
+__device__ __forceinline__ void feat_row(const float *__restrict__ xr, const float *__restrict__ w, const float *__restrict__ b, float eps, int lane, float (&f)[NV][VEC]) {
+    typedef LnRow<VEC, NV> R;
+    if constexpr (IDENT) {
+        typename R::Raw r;
+        R::load(xr, lane, r);
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) f[i][j] = r[i][j];
+    } else R::norm(xr, w, b, eps, lane, f);
+}
+
+template <int VEC, int NV, bool IDENT = false>
 __global__ __launch_bounds__(feat_waves(64 * VEC * NV) * 64) void features_kernel(const float *__restrict__ x, long row_stride, long img_stride, const float *__restrict__ w,
                                                                    const float *__restrict__ b, float *__restrict__ cls, float *__restrict__ mean, float *__restrict__ tokens,
                                                                    long out_img_stride, int N, float eps, int l2, int first, void *__restrict__ z, int z_bf16, int zw /* z rows of zw * D: 2 = cls ‖ mean, 1 = the mean alone */) {
@@ -42,7 +56,7 @@ __global__ __launch_bounds__(feat_waves(64 * VEC * NV) * 64) void features_kerne
     const size_t out_off = (size_t)blockIdx.x * out_img_stride;
     float f[U][NV][VEC];
     if (zw == 2 && (cls || z) && wave == W - 1) {
-        R::norm(xi, w, b, eps, lane, f[0]);
+        feat_row<VEC, NV, IDENT>(xi, w, b, eps, lane, f[0]);
         if (z) {
             if (z_bf16) R::store_rne((__bf16 *)z + (size_t)blockIdx.x * 2 * D, lane, f[0]);
             else R::store_rne((_Float16 *)z + (size_t)blockIdx.x * 2 * D, lane, f[0]);
@@ -62,7 +76,7 @@ __global__ __launch_bounds__(feat_waves(64 * VEC * NV) * 64) void features_kerne
     for (int t = first + wave; t < N; t += U * W) {
 #pragma unroll
         for (int u = 0; u < U; ++u)
-            if (t + u * W < N) R::norm(xi + (size_t)(t + u * W) * row_stride, w, b, eps, lane, f[u]);
+            if (t + u * W < N) feat_row<VEC, NV, IDENT>(xi + (size_t)(t + u * W) * row_stride, w, b, eps, lane, f[u]);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (t + u * W >= N) break;
@@ -113,8 +127,9 @@ hipError_t launch_features(const float *x, long row_stride, long img_stride, con
     if (first < 0 || first > N || (first == 0 && !z_mean_only && (cls || z)) || (z_mean_only && !z)) return hipErrorInvalidValue;     // first = 0: a model without prefix tokens has no class row
     const bool rows = mean || tokens || z;      // (the mean-only form always has z)
     const dim3 grid(n_img), blk(64 * (rows ? feat_waves(D) : 1));
-    const bool ok = ln_for_width(D, [&](auto vec, auto nv) {
-        hipLaunchKernelGGL((features_kernel<vec(), nv()>), grid, blk, 0, stream, x, row_stride, img_stride, w, b, cls, mean, tokens, out_img_stride, N, eps, l2 ? 1 : 0, first, z, dtype == DT_BF16 ? 1 : 0, z_mean_only ? 1 : 2);
+    const bool ok = ln_for_width(D, [&](auto vec, auto nv) {       // w == nullptr: the identity in place of the norm (forward.cpp, a `window` file with identity_final_norm)
+        if (!w) hipLaunchKernelGGL((features_kernel<vec(), nv(), true>), grid, blk, 0, stream, x, row_stride, img_stride, w, b, cls, mean, tokens, out_img_stride, N, eps, l2 ? 1 : 0, first, z, dtype == DT_BF16 ? 1 : 0, z_mean_only ? 1 : 2);
+        else hipLaunchKernelGGL((features_kernel<vec(), nv()>), grid, blk, 0, stream, x, row_stride, img_stride, w, b, cls, mean, tokens, out_img_stride, N, eps, l2 ? 1 : 0, first, z, dtype == DT_BF16 ? 1 : 0, z_mean_only ? 1 : 2);
     });
     return ok ? hipGetLastError() : hipErrorInvalidValue;
 }

@@ -140,7 +140,7 @@ struct SliceForward {
         }
         const double rows = (double)n * (((o_cls || z) && !zm ? 1 : 0) + (o_mean || o_tok || z ? N - Tp : 0));
         ProfScope ps(c, st, sel ? PC_FEATURES : PC_HEAD_POOL, 0, rows * D * 4 + (double)n * D * 4 * ((o_cls ? 1 : 0) + (o_mean ? 1 : 0) + (o_tok ? N - Tp : 0)) + (z ? (double)n * (zm ? 1 : 2) * D * eb : 0.0));
-        HIP_TRY(launch_features(cls_rows ? sl.Xc : sl.X, D, cls_rows ? (long)D : (long)N * D, ws.norm_w, ws.norm_b, o_cls, o_mean, o_tok, ft ? ft->fpi : 0,
+        HIP_TRY(launch_features(cls_rows ? sl.Xc : sl.X, D, cls_rows ? (long)D : (long)N * D, c->ident_norm ? nullptr : ws.norm_w, ws.norm_b, o_cls, o_mean, o_tok, ft ? ft->fpi : 0,
                                 n, cls_rows ? 1 : N, D, c->hp.eps, (fl & VITX_FEAT_L2) != 0, st, cls_rows ? 1 : Tp, z, dt, zm));
         return VITX_OK;
     }
@@ -332,7 +332,8 @@ struct SliceForward {
         } else {          // attention (vit.cpp:826-866)
             ProfScope ps(c, st, PC_ATTENTION, 4.0 * n * c->H * (double)N * N * (D / c->H), (double)M_real * (c->prec_attn ? 7 : 4) * D * eb);
             if (!(skip & 1)) {
-                if (c->rel_bias) HIP_TRY(launch_attention_bias(dt, sl.QKV, c->rel_bias + (size_t)il * c->rel_bias_stride, sl.U, n, c->gh, c->gw, D, c->H, st));      // this layer's table
+                if (!c->win_side.empty()) HIP_TRY(launch_attention_window(dt, sl.QKV, w.rel_h, w.rel_w, w.qkv_b, sl.U, n, c->gh, c->gw, c->win_side[il], c->win_side[il], D, c->H, st));      // this layer's extents and tables
+                else if (c->rel_bias) HIP_TRY(launch_attention_bias(dt, sl.QKV, c->rel_bias + (size_t)il * c->rel_bias_stride, sl.U, n, c->gh, c->gw, D, c->H, st));      // this layer's table
                 else if (c->prec_attn) HIP_TRY(launch_attention_stream(dt, true, sl.QKV, sl.U, n, N, D, c->H, lo_off, st));
                 else HIP_TRY(launch_attention(*c->tune, dt, sl.QKV, sl.U, n, N, D, c->H, st));
             }

@@ -208,6 +208,7 @@ hipError_t launch_rollout_row_packed(const float *cls, long cfpt, int cslot, con
 // z_mean_only (VITX_POOL_MEAN): z rows are [D] = RNE(mean) alone, row 0 is not read for z, first = 0 is allowed with z, and cls != nullptr receives the
 // mean as well (the pooled embedding is such a context's VITX_FEAT_CLS).
 // Every width of VITX_LN_WIDTHS; pointers 16-byte aligned, strides multiples of 4 floats.
+// w == nullptr: the final norm is the identity (a `window` file with identity_final_norm; forward.cpp alone passes it): F is the raw row, b and eps are not read.
 hipError_t launch_features(const float *x, long row_stride, long img_stride, const float *w, const float *b, float *cls, float *mean, float *tokens,
                            long out_img_stride, int n_img, int N, int D, float eps, bool l2, hipStream_t stream, int first = 1, void *z = nullptr, int dtype = DT_F16, bool z_mean_only = false);
 // The raw-mean head (pool_mean.hip; include/vitx.h "the mean-pool head", VITX_POOL_MEAN_NORM): m[i] = the mean of the raw rows first .. N-1 of image i (read as
@@ -469,6 +470,13 @@ bool attention_wide_supports(int N, int D, int H);             // attention_wide
 // or where the chunks and both tables exceed 64 KiB of LDS.  A zero table gives launch_attention_generic's bits.
 hipError_t launch_attention_bias(int dtype, const void *qkv, const float *table, void *out, int n_img, int gh, int gw, int D, int H, hipStream_t stream);
 bool attention_bias_supports(int gh, int gw, int D, int H);
+// Windowed attention with a decomposed relative position term (attention_window.hip; include/vitx.h "windowed attention and decomposed relative
+// position"): qkv [n_img * gh gw][3 D] -> out [n_img * gh gw][D], class-less, head dim 64; windows of wh x ww slots ((gh, gw): one global window);
+// rel_h [2 wh - 1][64], rel_w [2 ww - 1][64] in the operand type, qkv_bias f32 [3 D] (k and v of a pad slot), all on the device.
+// hipErrorInvalidValue, nothing launched, for another head dim or a window side above 64.  Zero tables and a global window give launch_attention_generic's bits.
+hipError_t launch_attention_window(int dtype, const void *qkv, const void *rel_h, const void *rel_w, const float *qkv_bias, void *out, int n_img, int gh, int gw, int wh, int ww, int D, int H,
+                                   hipStream_t stream);
+bool attention_window_supports(int gh, int gw, int wh, int ww, int D, int H);
 
 // FN<_Float16>(args) for DT_F16, FN<__bf16>(args) for any other dtype: how a launcher that takes `int dtype` enters its per-type template.
 // VITX_BY_DTYPE2: FN has one more template argument X after the type.
@@ -493,6 +501,7 @@ hipError_t prepare_attention_flow();
 hipError_t prepare_attention_persist();
 hipError_t prepare_attention_stream();
 hipError_t prepare_attention_bias();                   // attention_bias.hip
+hipError_t prepare_attention_window();                 // attention_window.hip
 hipError_t prepare_attention_text();                   // attention_text.hip
 hipError_t prepare_dense();                            // dense_label.hip
 hipError_t prepare_depth();                            // depth_map.hip

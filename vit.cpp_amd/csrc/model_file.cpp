@@ -298,6 +298,35 @@ static int load_impl(const char *path, vitx_model &m) {
             ++n_optional;
             continue;
         }
+        if (t.name == "window") {                                    // optional: f32 [2 + L] (include/vitx.h "windowed attention and decomposed relative position")
+            if (m.index.count(t.name)) { set_error("vitx_model_load: duplicate tensor '%s'", t.name.c_str()); return VITX_ERR_FORMAT; }
+            if (text) { set_error("vitx_model_load: text-tower file: tensor 'window' belongs to image files"); return VITX_ERR_FORMAT; }
+            const int L = hp.num_hidden_layers;
+            if (ttype != T_F32 || n_dims != 1 || t.ne[0] != 2 + L) {
+                set_error("vitx_model_load: tensor 'window' must be f32 [%d] = {ws, identity_final_norm, a flag per layer}: got type %d, %d dims [%lld, ..]", 2 + L, ttype, n_dims, (long long)t.ne[0]);
+                return VITX_ERR_FORMAT;
+            }
+            if (seen_block) { set_error("vitx_model_load: tensor 'window' stands behind a blocks.* record: it sets their tables and must come in front of the first one"); return VITX_ERR_FORMAT; }
+            const size_t nbytes = (size_t)(2 + L) * 4;
+            t.raw.resize(nbytes);
+            if (fread(t.raw.data(), 1, nbytes, f) != nbytes) { set_error("vitx_model_load: tensor '%s' is truncated", t.name.c_str()); return VITX_ERR_IO; }
+            std::vector<float> a(2 + L); memcpy(a.data(), t.raw.data(), nbytes);
+            if (!(a[0] >= 1.0f && a[0] <= 4096.0f) || a[0] != (float)(int)a[0]) { set_error("vitx_model_load: tensor 'window' names ws %g: a window side is a whole number >= 1", (double)a[0]); return VITX_ERR_FORMAT; }
+            for (int i = 1; i < 2 + L; ++i)
+                if (a[i] != 0.0f && a[i] != 1.0f) { set_error("vitx_model_load: tensor 'window' slot %d is %g: identity_final_norm and the layer flags are 0 or 1", i, (double)a[i]); return VITX_ERR_FORMAT; }
+            m.window = (int)a[0]; m.window_identity_norm = a[1] == 1.0f;
+            m.window_layers.resize(L);
+            const int64_t dh = hp.hidden_size / hp.num_attention_heads, g = hp.img_size / hp.patch_size;
+            for (int i = 0; i < L; ++i) {                            // this layer's two tables, f32 [2 w - 1][dh]
+                m.window_layers[i] = a[2 + i] == 1.0f;
+                const int64_t rows = 2 * (m.window_layers[i] ? (int64_t)m.window : g) - 1;
+                for (const char *n : {"rel_pos_h", "rel_pos_w"}) expect["blocks." + std::to_string(i) + ".attn." + n] = {{dh, rows, 1, 1}, 0};
+            }
+            m.index[t.name] = (int)m.tensors.size();
+            m.tensors.push_back(std::move(t));
+            ++n_optional;
+            continue;
+        }
         if (t.name == "glu") {                                       // optional: f32 [4] = {kind, F, 0, 0} (include/vitx.h "gated MLP")
             if (m.index.count(t.name)) { set_error("vitx_model_load: duplicate tensor '%s'", t.name.c_str()); return VITX_ERR_FORMAT; }
             if (text) { set_error("vitx_model_load: text-tower file: tensor 'glu' belongs to image files"); return VITX_ERR_FORMAT; }
@@ -488,6 +517,21 @@ static int load_impl(const char *path, vitx_model &m) {
         if (!has_cls) { set_error("vitx_model_load: tensor 'cls_token' is missing (only a file with the attn_pool.* tensors has no class token)"); return VITX_ERR_FORMAT; }
         if (pos_no_cls) { set_error("vitx_model_load: tensor 'pos_embed' has no class row, but the file has a class token"); return VITX_ERR_FORMAT; }
     }
+    if (m.window) {               // windowed attention: a class-less grid with the mean-pool marker, no other position signal, plain MLPs, finite tables
+        const char *with = has_cls ? "cls_token" : m.num_registers ? "reg_token" : m.rope_kind ? "rope" : m.rel_bias_layers ? "rel_bias" : n_pool ? "attn_pool.*" : m.glu_kind ? "glu" : nullptr;
+        if (with) { set_error("vitx_model_load: tensor 'window' together with %s: the windowed attention knows a class-less grid of patch tokens with plain blocks only", with); return VITX_ERR_FORMAT; }
+        if (m.head_pool != VITX_POOL_MEAN) { set_error("vitx_model_load: tensor 'window' without `pool` = {1, 0, 0, 0}: such a file has no class token and carries the mean-pool marker"); return VITX_ERR_FORMAT; }
+        for (int i = 0; i < hp.num_hidden_layers; ++i)
+            for (const char *n : {"rel_pos_h", "rel_pos_w"}) {
+                const std::string name = "blocks." + std::to_string(i) + ".attn." + n;
+                const HostTensor *t = m.find(name);
+                if (!t) { set_error("vitx_model_load: tensor '%s' is missing: `window` asks for both tables of every layer", name.c_str()); return VITX_ERR_FORMAT; }
+                for (int64_t k = 0; k < t->nelements(); ++k) {
+                    float v; memcpy(&v, t->raw.data() + 4 * k, 4);
+                    if (!std::isfinite(v)) { set_error("vitx_model_load: tensor '%s' entry %lld is not finite", name.c_str(), (long long)k); return VITX_ERR_FORMAT; }
+                }
+            }
+    }
     if (m.rel_bias_layers) {      // the relative position bias: a class token, no registers, no rotary signal (attn_pool.* comes without cls_token: refused as such)
         const char *with = !has_cls ? nullptr : m.num_registers ? "reg_token" : m.rope_kind ? "rope" : "";
         if (!with) { set_error("vitx_model_load: tensor 'rel_bias' in a file without cls_token: the index rule has the class token in front"); return VITX_ERR_FORMAT; }
@@ -575,6 +619,13 @@ int vitx_model_rope(const vitx_model *m, int *kind, float *theta) {
     if (!m || !m->rope_kind) return 0;
     if (kind) *kind = m->rope_kind;
     if (theta) *theta = m->rope_theta;
+    return 1;
+}
+int vitx_model_window(const vitx_model *m, int *ws, int *flags, int *layer_is_windowed) {
+    if (!m || !m->window) return 0;
+    if (ws) *ws = m->window;
+    if (flags) *flags = m->window_identity_norm ? 1 : 0;
+    if (layer_is_windowed) for (int i = 0; i < m->hp.num_hidden_layers; ++i) layer_is_windowed[i] = m->window_layers[i];
     return 1;
 }
 int vitx_model_rel_bias(const vitx_model *m, int *Lb, int *table_len) {

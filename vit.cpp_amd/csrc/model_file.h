@@ -43,6 +43,10 @@ struct vitx_model {
     int rope_kind = VITX_ROPE_NONE;                   // `rope` [4] = {kind, theta, 0, 0}: rotary position embeddings on q and k of the patch tokens (include/vitx.h)
     float rope_theta = 0.0f;
     int rel_bias_layers = 0;                          // `rel_bias` f32 [Lb][H][(2g-1)^2 + 3]: Lb (1: shared by every layer, or L); 0 without it (include/vitx.h "relative position bias")
+    int window = 0;                                   // `window` f32 [2 + L] = {ws, identity_final_norm, per layer 1 windowed / 0 global}: ws, 0 without it (include/vitx.h "windowed attention")
+    bool window_identity_norm = false;
+    std::vector<char> window_layers;                  // [L]: 1 = the layer attends in ws x ws windows, 0 = globally
+    int window_side(int il) const { return window_layers[il] ? window : hp.img_size / hp.patch_size; }
     int glu_kind = VITX_GLU_NONE;                     // `glu` [4] = {kind, F, 0, 0}: a gated MLP (include/vitx.h "gated MLP"); fc1 is then [2 F][D], fc2 [D][F]
     int glu_width = 0;                                // F, the MLP hidden width of such a file (fc2's K); 0 without `glu`: the width is 4 D
     int mlp_width = 0;                                // `mlp` [4] = {F, 0, 0, 0}: a plain MLP of the file's own width (include/vitx.h "MLP width"); 0 without it

@@ -911,6 +911,20 @@ int vitx_op_attention_bias(int dtype, const void *d_qkv, const void *d_table, vo
     if (!tuning_for_device(-1)) { set_error("vitx_op_attention_bias: kernel bring-up failed"); return VITX_ERR_HIP; }
     return op_rc("vitx_op_attention_bias", launch_attention_bias(dtype, d_qkv, (const float *)d_table, d_out, n_img, gh, gw, D, H, nullptr), VITX_ERR_UNSUPPORTED);
 }
+// Windowed attention with a decomposed relative position term (attention_window.hip; include/vitx.h "windowed attention and decomposed relative
+// position") on its own.  Null stream, only enqueues.
+int vitx_op_attention_window(int dtype, const void *d_qkv, const void *d_rel_h, const void *d_rel_w, const float *d_qkv_bias, void *d_out, int n_img, int gh, int gw, int wh, int ww, int D, int H) {
+    if (!d_qkv || !d_rel_h || !d_rel_w || !d_qkv_bias || !d_out || n_img <= 0 || gh <= 0 || gw <= 0 || wh <= 0 || ww <= 0 || D <= 0 || H <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) {
+        set_error("vitx_op_attention_window: invalid argument");
+        return VITX_ERR_ARG;
+    }
+    if (!attention_window_supports(gh, gw, wh, ww, D, H)) {
+        set_error("vitx_op_attention_window: the windowed attention kernel takes head dim 64 (D %d, H %d) and windows of at most 64 slots a side (%d x %d on a %d x %d grid)", D, H, wh, ww, gh, gw);
+        return VITX_ERR_UNSUPPORTED;
+    }
+    if (!tuning_for_device(-1)) { set_error("vitx_op_attention_window: kernel bring-up failed"); return VITX_ERR_HIP; }
+    return op_rc("vitx_op_attention_window", launch_attention_window(dtype, d_qkv, d_rel_h, d_rel_w, d_qkv_bias, d_out, n_img, gh, gw, wh, ww, D, H, nullptr), VITX_ERR_UNSUPPORTED);
+}
 // The staged kernel of head dims 72 .. 128 (attention_wide.hip) on its own, beside the generic one it must match bit for bit.  Null stream, only enqueues.
 int vitx_op_attention_wide(int dtype, const void *d_qkv, void *d_out, int n_img, int N, int D, int H) {
     if (!d_qkv || !d_out || n_img <= 0 || N <= 0 || D <= 0 || H <= 0 || (dtype != VITX_F16 && dtype != VITX_BF16)) { set_error("vitx_op_attention_wide: invalid argument"); return VITX_ERR_ARG; }

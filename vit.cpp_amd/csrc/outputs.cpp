@@ -191,6 +191,7 @@ int vitx_attn_enable(vitx_ctx *c, uint64_t layer_mask, int flags) {
     if (c->L < 64 && (layer_mask >> c->L)) { set_error("vitx_attn_enable: layer mask 0x%llx names layers beyond the model's %d", (unsigned long long)layer_mask, c->L); return VITX_ERR_ARG; }
     const bool on = layer_mask != 0 || flags != 0, rollout = (flags & VITX_ATTN_ROLLOUT) != 0;
     if (on && c->R != 1) { set_error("vitx_attn_enable: attention maps are not available for ViTSTR contexts"); return VITX_ERR_UNSUPPORTED; }
+    if (on && !c->win_side.empty()) { set_error("vitx_attn_enable: this model runs windowed attention with a position term, which the map kernels do not know"); return VITX_ERR_UNSUPPORTED; }
     if (on && !c->has_cls) { set_error("vitx_attn_enable: the maps are defined by the class-token row, and this model (attention-pooling head, or a mean-pool file without cls_token) has no class token"); return VITX_ERR_UNSUPPORTED; }
     if (on && c->rel_bias) { set_error("vitx_attn_enable: this model adds a relative position bias to its attention scores, and the map kernels would omit it"); return VITX_ERR_UNSUPPORTED; }
     if (on && !attention_map_supports(c->N, c->D, c->H)) { set_error("vitx_attn_enable: head_dim %d is not covered by the map kernels", c->D / c->H); return VITX_ERR_UNSUPPORTED; }
@@ -388,6 +389,7 @@ int vitx_dense_set(vitx_ctx *c, const float *W, const float *bias, int K, int Dc
         if (const int rc = patch_head_shape(c, "vitx_dense_set", &oh, &ow)) return rc;
         if (const int rc = dense_head_values("vitx_dense_set", W, bias, K, Dc)) return rc;
         if (c->R != 1) { set_error("vitx_dense_set: the dense head is not available for ViTSTR contexts"); return VITX_ERR_UNSUPPORTED; }
+        if (c->ident_norm) { set_error("vitx_dense_set: the dense head reads the final norm, and this model (windowed attention, identity_final_norm) has none"); return VITX_ERR_UNSUPPORTED; }
         if (oh < c->gh || ow < c->gw || oh > kDenseMaxOut || ow > kDenseMaxOut) {
             set_error("vitx_dense_set: output %d x %d outside the patch grid %d x %d .. %d (upsampling only)", oh, ow, c->gh, c->gw, kDenseMaxOut);
             return VITX_ERR_UNSUPPORTED;
@@ -451,6 +453,7 @@ int vitx_depth_set(vitx_ctx *c, const float *Wp, const float *Wc, const float *b
         if (const int rc = patch_head_shape(c, "vitx_depth_set", &oh, &ow)) return rc;
         if (const int rc = depth_head_values("vitx_depth_set", Wp, Wc, bias, bins, K, Dc, min_depth, max_depth, upsample)) return rc;
         if (c->R != 1) { set_error("vitx_depth_set: the depth head is not available for ViTSTR contexts"); return VITX_ERR_UNSUPPORTED; }
+        if (c->ident_norm && (flags & VITX_DEPTH_NORM)) { set_error("vitx_depth_set: VITX_DEPTH_NORM reads the final norm, and this model (windowed attention, identity_final_norm) has none"); return VITX_ERR_UNSUPPORTED; }
         if (Wc && !c->has_cls) { set_error("vitx_depth_set: a class half on a context without a class token (VITX_POOL_MAP, or a mean-pool file without cls_token)"); return VITX_ERR_UNSUPPORTED; }
         if (oh < fh || ow < fw || oh > kDepthMaxOut || ow > kDepthMaxOut) {
             set_error("vitx_depth_set: output %d x %d outside the fine plane %d x %d .. %d (upsampling only)", oh, ow, fh, fw, kDepthMaxOut);

@@ -152,6 +152,7 @@ int vitx_pack_create(const vitx_model *m, int device, int max_tokens, int max_im
     if (m->kind != VITX_KIND_IMAGE) { set_error("vitx_pack_create: a text-tower model takes a text context (vitx_text_create), not a packed context"); return VITX_ERR_ARG; }
     if (dtype == VITX_MXFP8) { set_error("vitx_pack_create: VITX_MXFP8 is not supported by packed contexts (VITX_F16 or VITX_BF16)"); return VITX_ERR_UNSUPPORTED; }
     if (dtype != VITX_F16 && dtype != VITX_BF16) { set_error("vitx_pack_create: unknown dtype %d", dtype); return VITX_ERR_ARG; }
+    if (m->window) { set_error("vitx_pack_create: packed contexts do not take models with windowed attention (`window`): its global tables belong to one grid"); return VITX_ERR_UNSUPPORTED; }
     if (m->rel_bias_layers) { set_error("vitx_pack_create: packed contexts do not take models with a relative position bias (`rel_bias`): its table belongs to one grid"); return VITX_ERR_UNSUPPORTED; }
     const int pos_interp = opt ? opt->pos_interp : VITX_POS_BICUBIC, max_grids = opt && opt->max_grids ? opt->max_grids : 32;
     if (pos_interp != VITX_POS_BICUBIC && pos_interp != VITX_POS_BICUBIC_AA) { set_error("vitx_pack_create: unknown pos_interp %d (0 bicubic, 1 bicubic with antialias)", pos_interp); return VITX_ERR_ARG; }

@@ -51,6 +51,7 @@ extern "C" int vitx_model_resize_file(const char *path_in, const char *path_out,
     int rc = vitx_model_load(path_in, &m);
     if (rc != VITX_OK) return rc;
     if (m->kind != VITX_KIND_IMAGE) { vitx_model_free(m); set_error("vitx_model_resize_file: '%s' is a text-tower file: it has no image size", path_in); return VITX_ERR_ARG; }
+    if (m->window) { vitx_model_free(m); set_error("vitx_model_resize_file: '%s' runs windowed attention (`window`): its global tables belong to the file's own grid", path_in); return VITX_ERR_UNSUPPORTED; }
     if (m->rel_bias_layers) { vitx_model_free(m); set_error("vitx_model_resize_file: '%s' carries a relative position bias (`rel_bias`): its table belongs to the file's own grid", path_in); return VITX_ERR_UNSUPPORTED; }
     const vitx_hparams hp = m->hp;
     const int in_chans = m->in_chans;

@@ -161,6 +161,11 @@ int upload_blocks(const Upload &u) {
         auto matrix = [&](const char *name, int k, int N, int K, void **dense, int n_run = 0, int k_run = 0) {
             return u.mx && k != W_PROJ ? upload_mx(u, u.T(p + name), N, K, round_up(N, 128), &w.mx[k]) : upload_weight(u, u.T(p + name), N, K, round_up(std::max(N, n_run), tn), dense, &w.q[k], k_run);
         };
+        if (u.m->window) {               // the layer's two position tables, rounded once like every weight
+            const int rows = 2 * u.m->window_side(i) - 1, dh = D / u.m->hp.num_attention_heads;
+            if ((rc = upload_matrix(u, u.T(p + "attn.rel_pos_h"), rows, dh, rows, dh, &w.rel_h))) return rc;
+            if ((rc = upload_matrix(u, u.T(p + "attn.rel_pos_w"), rows, dh, rows, dh, &w.rel_w))) return rc;
+        }
         if ((rc = matrix("attn.qkv.weight", W_QKV, 3 * D, D, &w.qkv_w))) return rc;
         if ((rc = matrix("mlp.fc1.weight", W_FC1, F1f, D, &w.fc1_w, F1))) return rc;
         if ((rc = matrix("mlp.fc2.weight", W_FC2, D, Ff, &w.fc2_w, 0, F))) return rc;

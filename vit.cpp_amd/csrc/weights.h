@@ -35,6 +35,7 @@ struct MxW {
 };
 struct LayerW {
     float *ln1_w, *ln1_b, *ln2_w, *ln2_b, *qkv_b, *proj_b, *fc1_b, *fc2_b;
+    void *rel_h, *rel_w;             // blocks.i.attn.rel_pos_h / rel_pos_w [2 w - 1][dh] in the operand type, RNE (nullptr without `window`): attention_window.hip's tables
     void *qkv_w, *proj_w, *fc1_w, *fc2_w;      // expanded operand-type matrices; nullptr where the blocks stay quantised (q[]) or are MX (mx[])
     QuantW q[W_PER_LAYER];
     MxW mx[W_PER_LAYER];                       // VITX_MXFP8: qkv, fc1 and fc2 (proj stays bf16)

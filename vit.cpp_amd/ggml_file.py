@@ -271,6 +271,7 @@ def write_model(path: str, hp: HParams, tensors: Dict[str, np.ndarray], id2label
     after cls_token) and the head kind (0 class token, 3 / 4 mean-pool: head.weight [C][D]; 1 cls + mean: [C][2 D]) -- and are checked against `tensors`.
     `pool` = [1, order, 0, 0] (a mean-pool file; include/vitx.h) stands in front of the first blocks.* tensor; cls_token is then optional.
     `rel_bias` [Lb][H][(2g-1)^2 + 3] (a relative position bias; include/vitx.h) stays f32 and stands in front of the first blocks.* tensor too.
+    `window` [2 + L] (windowed attention; include/vitx.h) stands there as well; the blocks' attn.rel_pos_h / rel_pos_w tables stay f32.
     preproc (optional): the 16 slots of the `preproc` tensor (preproc_slots), written directly after `arch`; None writes the file without it."""
     tensors = with_preproc(tensors, preproc)
     D = hp.hidden_size
@@ -331,7 +332,7 @@ def write_model(path: str, hp: HParams, tensors: Dict[str, np.ndarray], id2label
             data = np.asarray(t, np.float32)
             if name == "patch_embed.proj.bias":
                 data = data.reshape(1, data.shape[0], 1, 1)              # convert:150-151
-            keep_f32 = data.ndim == 1 or name in ("pos_embed", "cls_token", "reg_token", "attn_pool.latent", "rel_bias") or name == "patch_embed.proj.bias"
+            keep_f32 = data.ndim == 1 or name in ("pos_embed", "cls_token", "reg_token", "attn_pool.latent", "rel_bias") or name == "patch_embed.proj.bias" or name.endswith((".attn.rel_pos_h", ".attn.rel_pos_w"))
             if ftype == 0 and not (patch_f16 and name == "patch_embed.proj.weight"):
                 keep_f32 = True
             ttype = F32 if keep_f32 else F16

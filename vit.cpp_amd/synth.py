@@ -119,6 +119,25 @@ def make_weights(hp: HParams, seed: int = 1234, head_scale: float = 8.0, in_chan
     return t
 
 
+def make_window_weights(hp: HParams, ws: int, global_layers=(), identity_norm: bool = True, seed: int = 1234, head_scale: float = 8.0,
+                        table_scale: float = 0.5) -> Dict[str, np.ndarray]:
+    """A class-less mean-pool file with windowed attention (include/vitx.h "windowed attention and decomposed relative position"): `window` =
+    {ws, identity_norm, per layer 1 windowed / 0 global} in front, and behind each block's qkv bias its tables attn.rel_pos_h / rel_pos_w
+    [2 w - 1][head dim], w = ws or the grid side, uniform in +-table_scale (drawn from a generator of their own: the other tensors are make_weights')."""
+    t = make_weights(hp, seed, head_scale, head_pool=3, cls_token=False)
+    rng = np.random.default_rng(seed + 1)
+    g, dh = hp.img_size // hp.patch_size, hp.hidden_size // hp.num_attention_heads
+    flags = [0.0 if i in global_layers else 1.0 for i in range(hp.num_hidden_layers)]
+    out: Dict[str, np.ndarray] = {"window": np.array([ws, float(identity_norm)] + flags, np.float32)}
+    for k, v in t.items():
+        out[k] = v
+        if k.endswith(".attn.qkv.bias"):
+            i = int(k.split(".")[1])
+            for n in ("rel_pos_h", "rel_pos_w"):
+                out[f"blocks.{i}.attn.{n}"] = rng.uniform(-table_scale, table_scale, (2 * (ws if flags[i] else g) - 1, dh)).astype(np.float32)
+    return out
+
+
 def write_synthetic(path: str, name: str, ftype: int = 1, seed: int = 1234, head_scale: float = 8.0, registers: int = 0, head_pool: int = 0,
                     preproc=None, cls_token: bool = True) -> HParams:
     """preproc: the 16 slots of a `preproc` tensor (ggml_file.preproc_slots) for the file to carry; None = a file without one."""
